@@ -9,15 +9,23 @@ the timed region starts (JU_LOC_DEVICE images); weights are seeded random-init o
 the reference's default architecture ("PSP quality", see BASELINE.json).
 
 `value` is ALWAYS taken through that one-frame-per-call boundary unless `--lookahead N`
-or `--location host` is given explicitly (A/B work; the line then says so).  The same
-line carries, each timed with the same barrier / synchronise / max-over-ranks method in a
-region of its own after the contract's timed region:
+or `--location host` is given explicitly (A/B work; the line then says so).
+
+A plain run does only what `value` needs: set-up, the fixed pre-roll, --warmup, the --steps
+timed frames, and the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` and the facts of that timed region).  `--dump-outputs DIR` also writes the
+output frame of the last timed step as DIR/output.npy (float32; the inputs are seeded, so two
+builds compare output for output).  With `--full` the same line also carries, each timed with
+the same barrier / synchronise / max-over-ranks method in a region of its own after the
+contract's timed region:
   frame_by_frame_value   ju_process over >= 200 frames whatever --steps was
   lookahead_value        ju_process_batch, passes of 8 device frames (an extension of the
                          boundary for callers that can read ahead; one output buffer per frame)
   host_frames_value      ju_process on host frames (PCIe-inclusive; the reference's own timing
                          loop, scripts/inference/tensorrt/inference.py:245-251)
   host_frames_lookahead_value   ju_process_batch, passes of 8 host frames
+and the roofline of the dominant kernel (a second runtime of the test flavour), the shader
+clock during the pre-roll and, on one GPU, the CPU baseline.
 
 N GPUs = N independent streams, one process per GPU, one RCCL broadcast of the
 model container at start-up, no per-frame communication ("replicas only").
@@ -26,6 +34,7 @@ Prints ONE JSON line on rank 0.
 """
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -179,6 +188,23 @@ def cpu_baseline(blob: bytes, cfg, frames: np.ndarray, budget_s: float) -> dict:
                       f"host has {os.cpu_count()} logical CPUs)"}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy in float32.  An array larger than its share of the 64 MB budget
+    (ps2-quality's 2560x1792 frame) is written as a fixed sample of its elements: seeded indices in ascending order,
+    the same for every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays) - 4096   # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            pick = np.random.Generator(np.random.PCG64(0)).choice(a.size, share // 4, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -199,12 +225,20 @@ def main() -> int:
                          "reference's one-frame boundary; the line's config.boundary then says so.  Default: `value` is "
                          "ju_process frame by frame, and the look-ahead figure is reported beside it as lookahead_value")
     ap.add_argument("--extra-frames", type=int, default=256,
-                    help="frames per secondary region (frame_by_frame_value, lookahead_value, host_frames_*); 0 = none")
+                    help="with --full: frames per secondary region (frame_by_frame_value, lookahead_value, "
+                         "host_frames_*); 0 = none")
     ap.add_argument("--no-prepare", action="store_true",
                     help="do not register the frame buffers (ju_prepare_frames): graphs are then captured "
                          "inside ju_process at a pair's second use, and a timed region that contains such a "
                          "capture or an eager run is refused")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary regions, the roofline, the pre-roll's shader clock and the CPU baseline "
+                         "(a plain run times --steps frames and reports those alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output frame of the last timed step to DIR/output.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, local_rank, world = jdist.env_world()
     if world != args.gpus:
@@ -321,7 +355,7 @@ def main() -> int:
         return jdist.max_over_ranks(elapsed, device), own, region
 
     host_main = args.location == "host"
-    extra = max(0, args.extra_frames)
+    extra = max(0, args.extra_frames) if args.full else 0
     phases = (args.preroll, args.warmup, args.steps)
     prepared = 0
     if not args.no_prepare:
@@ -329,12 +363,17 @@ def main() -> int:
         if extra:
             prepared += register(rt, (extra,), 8, host_too=True)
 
-    with SclkSampler(local_rank) as sclk:
+    with SclkSampler(local_rank) if args.full else contextlib.nullcontext() as sclk:
         run_phase(rt, args.preroll, look, host_main)  # clock-warm, fixed, outside the contract's warm-up
     run_phase(rt, args.warmup, look, host_main)
     # ---- the contract's timed region: EXACTLY --steps frames through the boundary -----------------------------------
     elapsed, own_elapsed, timed_region = timed(args.steps, look, host_main)
     rank_fps = jdist.gather_floats(args.steps / own_elapsed, device)
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received in its last step: the output frame of timed frame steps - 1 (every
+        # phase starts at ring position 0), taken before anything else runs on the ring's buffers
+        last = (args.steps - 1) % RING
+        dump_outputs(args.dump_outputs, {"output": out_host[last % 8] if host_main else d_out[last].cpu().numpy()})
 
     # ---- secondary regions (same runtime, same box, same method; each after a short warm-up of its own kind) --------
     def secondary(per_call: int, host: bool):
@@ -375,15 +414,57 @@ def main() -> int:
         return 3
     if rank == 0:
         fps = world * args.steps / elapsed
-        # dominant kernel: the 3x3 64->64 convolution of the residual tower,
-        # timed with HIP events on the engine's own stream
         fp8 = args.dtype == "fp8"
-        # product-side facts first: the measuring runtime below shares the device with `rt` (two resident towers of
-        # different libraries must not run at once: `rt` is idle from here on)
+        in_passes = timed_region["lookahead_frames"] > 0
+        # product-side facts first: with --full the measuring runtime below shares the device with `rt` (two resident
+        # towers of different libraries must not run at once: `rt` is idle from here on)
         product = {"fallbacks": int(rt.stat("fallbacks")), "graph_replays": rt.stat("graph_replays"),
                    "eager_runs": rt.stat("eager_runs"), "direct_graphs": rt.stat("direct_graphs"),
                    "graph_captures": rt.stat("graph_captures"), "resident_tower": rt.stat("resident_tower"),
                    "library": os.path.basename(R.library_path(False))}
+        result = {
+            "metric": "frames/sec 480x270->1920x1080 recurrent SR" if args.preset.startswith("psp")
+                      else f"frames/sec {w}x{h}->{4 * w}x{4 * h} recurrent SR",
+            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "preroll": args.preroll, "untimed_frames": args.preroll + args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.dtype, "data": "synthetic",
+            "config": {
+                "workload": f"{args.preset}: {w}x{h}->{4 * w}x{4 * h} recurrent loop, 1 stream per GPU, "
+                            f"{args.dtype} MFMA operands, fp32 accumulate, frames resident in "
+                            f"{'HBM' if args.location == 'device' else 'host memory (PCIe-inclusive)'}",
+                "weights": "seeded random-init (seed 42), reference default architecture",
+                "streams": world, "parallelism": f"replicas x{world}",
+                "model_broadcast": dict(jdist.LAST_BROADCAST, seconds=broadcast_s),
+                "per_rank_fps": {"values": rank_fps, "min": min(rank_fps), "max": max(rank_fps)},
+                "affinity": AFFINITY,
+                "boundary": ("ju_process_batch (synchronous; passes of %d consecutive frames: the flow fields of a pass in one "
+                             "sweep of the flow net's launches, warp / tower / tail frame by frame; bytes equal "
+                             "ju_process) -- NOT the reference's boundary: an explicit --lookahead run" % look) if in_passes
+                            else "ju_process (synchronous processImage, one frame per call: core.h:68-69)",
+                "library": {"timed": product["library"]},
+                "timed_region": timed_region,
+                "resident_fallbacks": product["fallbacks"],
+                "preroll_frames": args.preroll,
+                "submission": {"graph_replays": product["graph_replays"], "eager_runs": product["eager_runs"],
+                               "cached_graphs": product["direct_graphs"], "prepared_captures": prepared,
+                               "inline_captures": product["graph_captures"],
+                               "how": "one hipGraph per (input, output, binding set) tuple of device frames -- per tuple "
+                                      "of a look-ahead pass's frame buffers when the boundary is ju_process_batch --, "
+                                      "captured in set-up by ju_prepare_frames / ju_prepare_batch (unregistered tuples: at "
+                                      "their second use), replayed afterwards"},
+                "tower": "resident (one launch)" if product["resident_tower"] else "per-layer launches",
+            },
+        }
+        if fp8:
+            result["config"]["fp8_scheme"] = (
+                "self-defined (csrc/fp8.h): e4m3 operands with power-of-two per-channel weight / per-tensor "
+                "activation scales, fp16 residual stream; the gfx950 counterpart of the reference's TensorRT INT8 "
+                "engines, not a restatement of them -- parity is against the oracle's restatement of THIS scheme")
+    if rank == 0 and args.full:
+        # dominant kernel: the 3x3 64->64 convolution of the residual tower,
+        # timed with HIP events on the engine's own stream
         rt.synchronize()
         rt_timed, rt = rt, R.Runtime(blob, device=local_rank, dtype=dt, hooks=True)
         # The GPU idled while that runtime was set up, and ju_time_steps runs its frames on the runtime's own staging
@@ -402,7 +483,6 @@ def main() -> int:
         # figure of the launches alone is reported beside it)
         # (inside look-ahead passes when the timed region ran them: the towers of consecutive frames then follow one
         # another with only the warp in between -- another power state than frame-by-frame calls)
-        in_passes = timed_region["lookahead_frames"] > 0
         ctx = "@pass" if in_passes else "@frame"
         ms, launches, flops = rt.time_steps("tower" + ctx, args.roofline_iters)
         ms_alone = rt.time_steps("tower", args.roofline_iters)[0]
@@ -494,12 +574,7 @@ def main() -> int:
             fp8_roofline["traffic_unit"] = "bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)"
             if traffic and fp8_roofline.get("launch_ms"):
                 fp8_roofline["frac_of_counted_traffic"] = traffic / (fp8_roofline["launch_ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS
-        result = {
-            "metric": "frames/sec 480x270->1920x1080 recurrent SR" if args.preset.startswith("psp")
-                      else f"frames/sec {w}x{h}->{4 * w}x{4 * h} recurrent SR",
-            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "preroll": args.preroll, "untimed_frames": args.preroll + args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
+        result.update({
             # Secondary figures: the same runtime, the same box, each in a timed region of its own right after the
             # contract's (same barrier / synchronise / max-over-ranks method, `extra_frames` frames each, one output
             # buffer per frame).  In reading order: the drop-in boundary over a longer sample than --steps; the look-ahead
@@ -510,72 +585,41 @@ def main() -> int:
             "host_frames_value": host_fbf and host_fbf["value"],
             "host_frames_lookahead_value": host_la and host_la["value"],
             "extra_frames": extra,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
-            "config": {
-                "workload": f"{args.preset}: {w}x{h}->{4 * w}x{4 * h} recurrent loop, 1 stream per GPU, "
-                            f"{args.dtype} MFMA operands, fp32 accumulate, frames resident in "
-                            f"{'HBM' if args.location == 'device' else 'host memory (PCIe-inclusive)'}",
-                "weights": "seeded random-init (seed 42), reference default architecture",
-                "streams": world, "parallelism": f"replicas x{world}",
-                "model_broadcast": dict(jdist.LAST_BROADCAST, seconds=broadcast_s),
-                "per_rank_fps": {"values": rank_fps, "min": min(rank_fps), "max": max(rank_fps)},
-                "affinity": AFFINITY,
-                "boundary": ("ju_process_batch (synchronous; passes of %d consecutive frames: the flow fields of a pass in one "
-                             "sweep of the flow net's launches, warp / tower / tail frame by frame; bytes equal "
-                             "ju_process) -- NOT the reference's boundary: an explicit --lookahead run" % look) if in_passes
-                            else "ju_process (synchronous processImage, one frame per call: core.h:68-69)",
-                "secondary": {
-                    "how": "each figure: its own timed region after the contract's (barrier + synchronise on both sides, slowest "
-                           "rank), %d frames after 32 warm-up frames of its kind, a ring of %d inputs and one output buffer per "
-                           "frame" % (extra, RING),
-                    "frame_by_frame": fbf, "lookahead": la_dev, "host_frames": host_fbf, "host_frames_lookahead": host_la,
-                    "tower_launch_ms_inside_passes": tower_in_pass_ms,
-                },
-                "library": {"timed": product["library"], "kernel_times": os.path.basename(R.library_path(True))},
-                "timed_region": timed_region,
-                "resident_fallbacks": product["fallbacks"],
-                "preroll_frames": args.preroll,
-                "sclk_mhz_during_preroll": sclk.result(),
-                "submission": {"graph_replays": product["graph_replays"], "eager_runs": product["eager_runs"],
-                               "cached_graphs": product["direct_graphs"], "prepared_captures": prepared,
-                               "inline_captures": product["graph_captures"],
-                               "how": "one hipGraph per (input, output, binding set) tuple of device frames -- per tuple "
-                                      "of a look-ahead pass's frame buffers when the boundary is ju_process_batch --, "
-                                      "captured in set-up by ju_prepare_frames / ju_prepare_batch (unregistered tuples: at "
-                                      "their second use), replayed afterwards"},
-                "tower": "resident (one launch)" if product["resident_tower"] else "per-layer launches",
-                "latency_ms": latency,
-                "gflop_per_frame": total_flops / 1e9,
-                "whole_frame_tflops": total_flops * fps / world / 1e12,
+        })
+        result["config"].update({
+            "secondary": {
+                "how": "each figure: its own timed region after the contract's (barrier + synchronise on both sides, slowest "
+                       "rank), %d frames after 32 warm-up frames of its kind, a ring of %d inputs and one output buffer per "
+                       "frame" % (extra, RING),
+                "frame_by_frame": fbf, "lookahead": la_dev, "host_frames": host_fbf, "host_frames_lookahead": host_la,
+                "tower_launch_ms_inside_passes": tower_in_pass_ms,
             },
-            "roofline": {
-                "kernel": ("tower8_resident_kernel: all 3x3 64->64 e4m3 convs of the residual blocks, one launch" if fp8
-                           else "tower_resident_kernel: generator conv_1 + all 3x3 64->64 convs of the residual blocks"
-                                + (" + the generator tail on the LDS-resident last layer" if tail_inside else "") + ", one launch")
-                          if launches == 1 else
-                          ("res_block_fp8_kernel: one residual block (two 3x3 64->64 e4m3 convs) per launch" if fp8
-                           else "res_block_pipe_kernel (ReLU blocks; res_block_kernel otherwise): one residual block "
-                                "(two 3x3 64->64 convs) per launch"),
-                "bound": "mfma", "achieved": achieved, "peak": peak,
-                "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
-                "traffic_unit": "bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)",
-                "traffic_source": traffic_source,
-                "launch_ms": ms, "launches_per_frame": launches,
-                "launch_ms_how": "HIP events around the kernel's launches inside whole frames on the engine's stream "
-                                 "(ju_time_steps tag%s), mean over %d %s" % (ctx, args.roofline_iters, "passes" if in_passes else "frames"),
-                "launch_ms_back_to_back": ms_alone,
-                # rounds 1-2 priced `frac` on the back-to-back figure; both are kept side by side
-                "frac_back_to_back": (flops_per_launch / (ms_alone * 1e-3) / 1e12 / peak) if ms_alone > 0 and launches == 1 else None,
-                "flops_per_launch": flops_per_launch,
-            },
+            "sclk_mhz_during_preroll": sclk.result(),
+            "latency_ms": latency,
+            "gflop_per_frame": total_flops / 1e9,
+            "whole_frame_tflops": total_flops * fps / world / 1e12,
+        })
+        result["config"]["library"]["kernel_times"] = os.path.basename(R.library_path(True))
+        result["roofline"] = fp8_roofline or {
+            "kernel": ("tower8_resident_kernel: all 3x3 64->64 e4m3 convs of the residual blocks, one launch" if fp8
+                       else "tower_resident_kernel: generator conv_1 + all 3x3 64->64 convs of the residual blocks"
+                            + (" + the generator tail on the LDS-resident last layer" if tail_inside else "") + ", one launch")
+                      if launches == 1 else
+                      ("res_block_fp8_kernel: one residual block (two 3x3 64->64 e4m3 convs) per launch" if fp8
+                       else "res_block_pipe_kernel (ReLU blocks; res_block_kernel otherwise): one residual block "
+                            "(two 3x3 64->64 convs) per launch"),
+            "bound": "mfma", "achieved": achieved, "peak": peak,
+            "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
+            "traffic_unit": "bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)",
+            "traffic_source": traffic_source,
+            "launch_ms": ms, "launches_per_frame": launches,
+            "launch_ms_how": "HIP events around the kernel's launches inside whole frames on the engine's stream "
+                             "(ju_time_steps tag%s), mean over %d %s" % (ctx, args.roofline_iters, "passes" if in_passes else "frames"),
+            "launch_ms_back_to_back": ms_alone,
+            # rounds 1-2 priced `frac` on the back-to-back figure; both are kept side by side
+            "frac_back_to_back": (flops_per_launch / (ms_alone * 1e-3) / 1e12 / peak) if ms_alone > 0 and launches == 1 else None,
+            "flops_per_launch": flops_per_launch,
         }
-        if fp8_roofline:
-            result["roofline"] = fp8_roofline
-            result["config"]["fp8_scheme"] = (
-                "self-defined (csrc/fp8.h): e4m3 operands with power-of-two per-channel weight / per-tensor "
-                "activation scales, fp16 residual stream; the gfx950 counterpart of the reference's TensorRT INT8 "
-                "engines, not a restatement of them -- parity is against the oracle's restatement of THIS scheme")
         clk = result["config"]["sclk_mhz_during_preroll"]
         if clk and clk["median"] > 0 and result["roofline"].get("bound") == "mfma":
             # `peak` is the guide's figure, quoted at 2400 MHz; the chip held `median` MHz under this load (power): the
@@ -584,9 +628,10 @@ def main() -> int:
             result["roofline"]["frac_at_measured_clock"] = result["roofline"]["frac"] * 2400.0 / clk["median"]
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(blob, cfg, clip, args.cpu_seconds)
-        print(json.dumps(result), flush=True)
         rt.close()
         rt = rt_timed
+    if rank == 0:
+        print(json.dumps(result), flush=True)
     jdist.barrier()
     rt.close()
     if torch.distributed.is_initialized():

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from helpers import M, ROOT
@@ -32,14 +33,14 @@ def test_native_rccl_communicator_single_rank():
         R.Comm(uid, 2, 1, 0)                                   # rank outside the world
 
 
-def test_bench_under_torchrun_uses_the_native_broadcast():
+def test_bench_under_torchrun_uses_the_native_broadcast(tmp_path):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--preset", "psp-fast",
-           "--dtype", "fp16"]
+           "--dtype", "fp16", "--full", "--dump-outputs", str(tmp_path / "full")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -84,13 +85,24 @@ def test_bench_under_torchrun_uses_the_native_broadcast():
     assert "how" in res["config"]["affinity"] and res["config"]["model_broadcast"]["seconds"] > 0
     # N = 1 under the launcher measures what a bare N = 1 run measures (the driver computes
     # scaling efficiency from the per-N values: the launcher itself must not cost frames)
+    # (a plain run: the timed region and its line alone -- no secondary regions, roofline or CPU baseline)
     bare = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                           "--no-cpu-baseline", "--preset", "psp-fast", "--dtype", "fp16"],
+                           "--preset", "psp-fast", "--dtype", "fp16", "--dump-outputs", str(tmp_path / "plain")],
                           capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert bare.returncode == 0, bare.stderr[-2000:]
     res1 = json.loads([ln for ln in bare.stdout.splitlines() if ln.startswith("{")][-1])
     assert res1["config"]["timed_region"] == {"replays": 20, "eager": 0, "captures": 0, "lookahead_frames": 0}
     assert abs(res["value"] / res1["value"] - 1.0) < 0.06, (res["value"], res1["value"])
+    assert res1["value"] == pytest.approx(1e3 / res1["ms_per_step"], rel=1e-6) and res1["steps"] == 20
+    assert res1["unit"] == "frames/s" and res1["higher_is_better"] is True and res1["dtype"] == "fp16"
+    assert not {"roofline", "cpu_baseline", "frame_by_frame_value", "lookahead_value"} & set(res1)
+    assert not {"secondary", "latency_ms", "sclk_mhz_during_preroll"} & set(res1["config"])
+    # --dump-outputs: the last timed frame's output, float32; the same seeded inputs give the same bytes with and
+    # without --full, under the launcher and bare
+    out_full, out_plain = np.load(tmp_path / "full" / "output.npy"), np.load(tmp_path / "plain" / "output.npy")
+    assert out_plain.dtype == np.float32 and out_plain.shape == (1080, 1920, 4)
+    assert (out_plain[..., 3] == 0).all() and out_plain[..., :3].std() > 1.0
+    assert np.array_equal(out_full, out_plain)
     # a timed region that is not pure replay is not reported: without registered buffers the 20
     # timed steps would be eager first sightings and inline captures (round 2's driver figure)
     dirty = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
@@ -116,7 +128,7 @@ def test_bench_with_frame_look_ahead_times_pure_replays_of_registered_passes():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "1", "--steps", "21", "--warmup", "5",
-                        "--no-cpu-baseline", "--preset", "psp-fast", "--dtype", "fp16", "--lookahead", "4"],
+                        "--no-cpu-baseline", "--preset", "psp-fast", "--dtype", "fp16", "--lookahead", "4", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

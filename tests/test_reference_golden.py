@@ -135,16 +135,18 @@ def test_generator_cases_are_loadable_and_round_trip_through_the_importer():
         assert keras_import.activation_fields(spec)[0] == cfg.gen_activation
 
 
-def test_generator_script_says_what_it_needs_without_tensorflow():
+def test_generator_script_says_what_it_needs_without_tensorflow(tmp_path):
     try:
         import tensorflow  # noqa: F401
         pytest.skip("TensorFlow is installed here: run the script instead")
     except ImportError:
         pass
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "scripts", "training")):
-        out = subprocess.run([sys.executable, SCRIPT, "--reference", "/nonexistent"], capture_output=True, text=True)
-        assert out.returncode != 0 and "models.py not found" in out.stderr
-        return
-    out = subprocess.run([sys.executable, SCRIPT, "--reference", ref], capture_output=True, text=True)
+    out = subprocess.run([sys.executable, SCRIPT, "--reference", str(tmp_path / "nonexistent")],
+                         capture_output=True, text=True)
+    assert out.returncode != 0 and "models.py not found" in out.stderr
+    # a stand-in checkout: the script looks for scripts/training/models.py, then for TensorFlow before it imports it
+    training = tmp_path / "checkout" / "scripts" / "training"
+    training.mkdir(parents=True)
+    (training / "models.py").write_text("raise AssertionError('imported before its dependencies were checked')\n")
+    out = subprocess.run([sys.executable, SCRIPT, "--reference", str(tmp_path / "checkout")], capture_output=True, text=True)
     assert out.returncode != 0 and "needs the reference's Python dependencies" in out.stderr, out.stderr

@@ -5,7 +5,7 @@
 ARGS="$1"; shift
 for r in 1 2 3; do
   for L in "$@"; do
-    JU_LIBRARY=$PWD/$L python3 bench.py $ARGS --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "
+    JU_LIBRARY=$PWD/$L python3 bench.py --full $ARGS --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json, os
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']; c = d['config'].get('sclk_mhz_during_preroll') or {}

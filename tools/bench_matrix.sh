@@ -5,7 +5,7 @@ D=gpurun_out/$1; shift
 mkdir -p $D
 for cfg in "psp-quality bf16" "psp-fast fp16" "ps2-quality fp8" "psp-quality fp8" "ps2-quality bf16" "psp-quality-lrelu bf16" "psp-quality fp16" "psp-quality-flowres bf16"; do
   set -- $cfg
-  python3 bench.py --preset $1 --dtype $2 --no-cpu-baseline "${@:3}" > $D/bench_$1_$2.json 2>> $D/bench.err
+  python3 bench.py --full --preset $1 --dtype $2 --no-cpu-baseline "${@:3}" > $D/bench_$1_$2.json 2>> $D/bench.err
   python3 - "$D/bench_$1_$2.json" "$1 $2" <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ OUT=gpurun_out/clock_under_load.txt
 {
 echo "== idle"; rocm-smi --showclocks 2>&1 | grep -iE "sclk|mclk|fclk" | head -4
 rocm-smi --showpower --showmaxpower 2>&1 | grep -iE "power|watt" | head -4
-python3 bench.py --steps 60000 --warmup 30 --no-cpu-baseline > gpurun_out/clock_bench.json 2>/dev/null &
+python3 bench.py --full --steps 60000 --warmup 30 --no-cpu-baseline > "${OUT%/*}/clock_bench.json" 2>/dev/null &
 BP=$!
 sleep 12
 for i in 1 2 3 4 5 6; do

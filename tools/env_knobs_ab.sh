@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 cd $R
 run() {
   echo -n "$1: "
-  env $1 python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python3 -c "
+  env $1 python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ for r in 1 2 3; do
   for preset in "psp-quality bf16" "psp-fast fp16"; do
     set -- $preset
     for wide in 0 2; do
-      JU_FLOW_WIDE=$wide python3 bench.py --preset $1 --dtype $2 --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python3 -c "
+      JU_FLOW_WIDE=$wide python3 bench.py --full --preset $1 --dtype $2 --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 c = d['config'].get('sclk_mhz_during_preroll') or {}

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 run() {
   echo "== $*"
-  env "${@:2}" timeout 300 python3 bench.py --no-cpu-baseline --steps 200 --warmup 20 $1 2>/dev/null | tail -1 | python3 -c '
+  env "${@:2}" timeout 300 python3 bench.py --full --no-cpu-baseline --steps 200 --warmup 20 $1 2>/dev/null | tail -1 | python3 -c '
 import json, sys
 d = json.loads(sys.stdin.read())
 r = d["roofline"]

@@ -7,7 +7,7 @@ export JU_LIBRARY=$PWD/build/ablate/libJoshUpscale_test.so
 for r in 1 2 3; do
   for mode in "0 -1" "16 9" "16 -1" "9 -1" "25 25"; do
     set -- $mode
-    JU_FB_SKIP=$1 JU_FB_SKIP_ALT=$2 python3 bench.py --preset ps2-quality --dtype fp8 --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python3 -c "
+    JU_FB_SKIP=$1 JU_FB_SKIP_ALT=$2 python3 bench.py --full --preset ps2-quality --dtype fp8 --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 cd $R
 for m in 0 1 2 3 4 0 1; do
   echo "== ps2-quality fp8, JU_WAVE_PRIO=$m"
-  JU_WAVE_PRIO=$m python3 bench.py --preset ps2-quality --dtype fp8 --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python3 -c "
+  JU_WAVE_PRIO=$m python3 bench.py --full --preset ps2-quality --dtype fp8 --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

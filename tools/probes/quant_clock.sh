@@ -15,7 +15,7 @@ PY
 echo "clock file: $CARD"
 for i in 1 2; do for m in split fused; do
   if [ $m = split ]; then export JU_QUANT=split; else unset JU_QUANT; fi
-  JU_LIBRARY=build/ab/lib_quant.so python3 bench.py --preset ps2-quality --dtype fp8 --steps 12000 --warmup 30 --no-cpu-baseline > /tmp/qc.json 2>/dev/null &
+  JU_LIBRARY=build/ab/lib_quant.so python3 bench.py --full --preset ps2-quality --dtype fp8 --steps 12000 --warmup 30 --no-cpu-baseline > /tmp/qc.json 2>/dev/null &
   BP=$!
   sleep 6
   S=""
