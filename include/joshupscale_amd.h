@@ -211,7 +211,9 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * (graphs captured INSIDE ju_process / ju_enqueue so far; captures by ju_prepare_frames:
  * "prepared_captures"), "registered_pairs", "direct_graphs"
  * (graphs cached for JU_LOC_DEVICE frame tuples), "resident_tower" / "resident_flow"
- * (1 when the one-launch tower kernel is in use), "launches_per_frame", "tower_variant". */
+ * (1 when the one-launch tower kernel is in use), "launches_per_frame", "tower_variant",
+ * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,
+ * flow_arch "none" of the container -- every frame is upscaled on its own, ju_reset does nothing). */
 JU_API int ju_get_stat(const ju_runtime *runtime, const char *key, double *value);
 
 /* Library version string, e.g. "joshupscale-amd 0.1 (gfx950)". */

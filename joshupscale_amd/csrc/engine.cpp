@@ -533,8 +533,9 @@ void Engine::buildProgram(int set) {
 	void *packedOut = m_Packed[set ^ 1].get();
 	// the recurrent state this program reads / writes: m_State[set] -> m_State[set ^ 1], read at launch (capture)
 	// time -- a look-ahead pass binds its frames' programs to its own chain of state buffers (submitBatch)
-	m_StateBind[set].in = m_State[set].get();
-	m_StateBind[set].out = m_State[set ^ 1].get();
+	// (a flow-free model: one scratch state that nothing reads -- the tail still writes its HR output there)
+	m_StateBind[set].in = m_State[c.recurrent() ? set : 0].get();
+	m_StateBind[set].out = m_State[c.recurrent() ? set ^ 1 : 0].get();
 	const StateBind *sb = &m_StateBind[set];
 	const int nIn = c.numFlowInputs;
 	auto T = [&](const std::string &n) -> void * { return m_Tensors.at(n).buf.get(); };
@@ -542,8 +543,18 @@ void Engine::buildProgram(int set) {
 	const Operand none{};
 
 	// normalize_brightness: three integer channel sums per frame, consumed by the pack,
-	// warp and tail kernels (models.py:772-779, 802-803, 809-810)
-	const unsigned *sums = c.normalizeBrightness ? m_TailB2.as<unsigned>() + 4 : nullptr;
+	// warp and tail kernels (models.py:772-779, 802-803, 809-810) -- in a flow-free model the flag touches
+	// nothing: it shifts only the flow input, pre_warp and the fed-back state, none of which exists
+	const unsigned *sums = c.normalizeBrightness && c.recurrent() ? m_TailB2.as<unsigned>() + 4 : nullptr;
+	if (!c.recurrent()) {
+		// ---- flow-free model (remove_flow.py): no flow net, no warp, no frame history -- ONE staging
+		// launch writes the LR frame into the generator input, then the generator as below ----
+		const Operand genInOp = Op("gen_in");
+		void *genIn = genInOp.ptr;
+		const int genPitch = genInOp.pitch;
+		prog.push_back({"lr_pack", 0.0,
+		    [=](hipStream_t s) { launchLrPack(dt, io->in, io->inStride, genIn, genPitch, H, W, s); }});
+	}
 	if (sums) {
 		unsigned *sumsOut = m_TailB2.as<unsigned>() + 4;
 		prog.push_back({"pack", 0.0,
@@ -551,7 +562,7 @@ void Engine::buildProgram(int set) {
 	}
 	// (the flow net's first block builds the packed tensor itself when it runs as one launch)
 	const bool packInBlock = flowPacksInBlock();
-	if (!packInBlock) {
+	if (!packInBlock && c.recurrent()) {
 		prog.push_back({"pack", 0.0, [=](hipStream_t s) {
 			                launchPackFrames(dt, io->in, io->inStride, packedIn, packedOut, H, W, PH, PW,
 			                    padTop, padLeft, nIn, sums, s);
@@ -583,7 +594,9 @@ void Engine::buildProgram(int set) {
 	Operand cur{packedOut, 0};
 	int h = PH, w = PW;
 	bool flowHeadDone = false;  // the fused head block wrote the flow tensor
-	if (c.flowArch == 0) {
+	if (!c.recurrent()) {
+		flowHeadDone = true;  // (no flow net)
+	} else if (c.flowArch == 0) {
 		addFlowAutoencoder(&prog, set, 1);
 		flowHeadDone = true;  // (or its own head launch: addFlowAutoencoder)
 	} else if (m_ResidentFlow) {
@@ -636,7 +649,7 @@ void Engine::buildProgram(int set) {
 	}
 	if (!flowHeadDone) addConvStep(&prog, "flow", "flow/conv_2", cur, none, Op("flow"), h, w, false, true);
 	// ---- warp + space-to-depth + concat ----
-	{
+	if (c.recurrent()) {
 		m_FlowCur = T("flow");
 		const void *const *flowSlot = &m_FlowCur;  // (a look-ahead pass points it at its frame's field)
 		// the generator input lives in the tower layout (zero border = conv_1's padding), so that conv_1 can run
@@ -748,7 +761,7 @@ void Engine::buildProgram(int set) {
 			tf.slope = -1.0f;
 		}
 		prog.push_back({"tower",
-		    2.0 * H * W * 9.0 * (51.0 * 64 + 64.0 * 64 * 2 * c.genBlocks) +
+		    2.0 * H * W * 9.0 * ((c.recurrent() ? 51.0 : 3.0) * 64 + 64.0 * 64 * 2 * c.genBlocks) +
 		        (tailInTower ? 2.0 * H * W * (64.0 * 128 + 4 * 4 * 32 * 3) : 0.0),
 		    [=](hipStream_t s) {
 			    ResidentTowerParams r = rp;
@@ -1001,11 +1014,19 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 	m_InStage = DeviceBuffer(lr * 4);
 	m_OutStage = DeviceBuffer(lr * 16 * 4);
 	m_RawStage = DeviceBuffer(lr * 16 * 4);
-	for (int i = 0; i < 2; ++i) {
-		m_State[i] = DeviceBuffer(lr * 16 * 4 * 2);  // f16 [4H][4W][4]
-		m_Packed[i] = DeviceBuffer(plr * 16 * 2);     // [PH][PW][16]
+	if (!c.recurrent()) {
+		// flow-free: no frame history, no flow tensors, no state ping-pong -- one scratch state for the tail's
+		// HR output, which nothing reads; gen_in's slots other than 12..14 stay zero for good (lr_pack)
+		m_State[0] = DeviceBuffer(lr * 16 * 4 * 2);
+	} else {
+		for (int i = 0; i < 2; ++i) {
+			m_State[i] = DeviceBuffer(lr * 16 * 4 * 2);  // f16 [4H][4W][4]
+			m_Packed[i] = DeviceBuffer(plr * 16 * 2);     // [PH][PW][16]
+		}
 	}
-	if (c.flowArch == 0) {
+	if (!c.recurrent()) {
+		// (no flow net)
+	} else if (c.flowArch == 0) {
 		const int nb = static_cast<int>(c.flowFilters.size()) / 2;
 		std::size_t px = plr;
 		for (int i = 0; i < 2 * nb; ++i) {
@@ -1026,7 +1047,7 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 		addTensor("flow/x1", plr * c.flowResFilters);
 		addTensor("flow/t", plr * c.flowResFilters);
 	}
-	addTensor("flow", plr * 32, false, true);  // the flow head: f16 whatever the compute type
+	if (c.recurrent()) addTensor("flow", plr * 32, false, true);  // the flow head: f16 whatever the compute type
 	addTowerTensor("gen_in", H, W, 64);
 	if (c.temporalStrength > 0.0f) {
 		addTensor("pre_warp", lr * 16 * 4);  // f16 [4H][4W][4]
@@ -1275,9 +1296,11 @@ void Engine::maybeRestoreResident() {
 
 void Engine::reset() {
 	DeviceGuard g(m_Device);
-	for (int i = 0; i < 2; ++i) {
-		m_State[i].zeroAsync(m_Stream);
-		m_Packed[i].zeroAsync(m_Stream);
+	if (m_Config.recurrent()) {  // (a flow-free model has no state: nothing to zero)
+		for (int i = 0; i < 2; ++i) {
+			m_State[i].zeroAsync(m_Stream);
+			m_Packed[i].zeroAsync(m_Stream);
+		}
 	}
 	m_Stream.synchronize();
 	m_Idx = 0;
@@ -1548,6 +1571,14 @@ int Engine::prepareFrames(const Frame &in, const Frame &out) {
 // pass -- a pass that failed (resident tower: bounded wait expired) can be run again frame by frame.
 // ---------------------------------------------------------------------------------------------------------------
 bool Engine::batchPlanned(int items) {
+	if (!m_Config.recurrent()) {
+		// a flow-free model: a pass is its frames' generator programs under one synchronisation -- no flow launches,
+		// no pass tensors, and every frame's tail writes the one scratch state
+		if (m_BatchUnsupported || m_Calibrate) return false;
+		for (int set = 0; set < 2; ++set) m_BatchFlow[{items, set}];
+		m_BatchCap = std::max({m_BatchCap, items, m_BatchMax});
+		return true;
+	}
 	if (m_BatchUnsupported || m_Calibrate || m_Config.flowArch != 0 || !flowPacksInBlock() || m_Config.normalizeBrightness) {
 		return false;
 	}
@@ -1623,8 +1654,9 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		if (around) (*around)(st, true);
 	};
 	const std::vector<Step> &flow = m_BatchFlow.at({n, set});
-	const long flowItem = static_cast<long>(m_Tensors.at("flow").count) * 2;
-	const unsigned char *flowBase = m_BatchTensors.at("flow").buf.as<unsigned char>();
+	const bool recurrent = m_Config.recurrent();  // (flow-free: no flow fields, no state chain)
+	const long flowItem = recurrent ? static_cast<long>(m_Tensors.at("flow").count) * 2 : 0;
+	const unsigned char *flowBase = recurrent ? m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
 	const FrameIO keepIO = m_IO;
 	const StateBind keepBind = m_StateBind[set];
 	const void *keepFlow = m_FlowCur;
@@ -1639,9 +1671,11 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 	for (const Step &st : flow) run(st);
 	for (int i = 0; i < n; ++i) {
 		m_IO = m_BatchIO[i];
-		m_FlowCur = flowBase + i * flowItem;
-		m_StateBind[set].in = i == 0 ? keepBind.in : m_BatchState[i - 1].get();
-		m_StateBind[set].out = i + 1 == n ? keepBind.out : m_BatchState[i].get();
+		if (recurrent) {
+			m_FlowCur = flowBase + i * flowItem;
+			m_StateBind[set].in = i == 0 ? keepBind.in : m_BatchState[i - 1].get();
+			m_StateBind[set].out = i + 1 == n ? keepBind.out : m_BatchState[i].get();
+		}
 		for (const Step &st : m_Program[set]) {
 			if (st.tag != "flow" && st.tag != "pack") run(st);
 		}
@@ -2007,7 +2041,8 @@ void Engine::synchronize() {
 }
 
 std::vector<std::string> Engine::tensorNames() const {
-	std::vector<std::string> names = {"state", "flow_in", "trunk"};
+	std::vector<std::string> names = {"trunk"};
+	if (m_Config.recurrent()) names.insert(names.begin(), {"state", "flow_in"});
 	for (const auto &kv : m_Tensors) names.push_back(kv.first);
 	return names;
 }
@@ -2020,6 +2055,9 @@ std::size_t Engine::readTensor(const std::string &name, float *dst, std::size_t 
 	const Tensor *tw = nullptr;
 	DType dt = m_DType;
 	const std::size_t lr = static_cast<std::size_t>(m_Config.frameHeight) * m_Config.frameWidth;
+	if (!m_Config.recurrent() && (name == "state" || name == "flow_in")) {
+		throw std::invalid_argument("unknown tensor " + name + " (a flow-free model has no recurrent state)");
+	}
 	if (name == "state") {  // the state the NEXT frame will read = last output_raw
 		src = m_State[m_Idx].get();
 		count = lr * 16 * 4;
@@ -2208,6 +2246,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "graph_captures") return static_cast<double>(m_InlineCaptures);
 	if (key == "prepared_captures") return static_cast<double>(m_PreparedCaptures);
 	if (key == "registered_pairs") return static_cast<double>(m_RegisteredPairs.size());
+	if (key == "recurrent") return m_Config.recurrent() ? 1.0 : 0.0;  // 0: a flow-free model (stateless)
 	if (key == "resident_tower") return m_Resident ? 1.0 : 0.0;
 	if (key == "resident_flow") return m_ResidentFlow ? 1.0 : 0.0;
 	if (key == "tower_fast") {  // the generator's resident tower runs the fast schedule (16-bit models, every region of its shape)

@@ -10,6 +10,7 @@
 //                       skip, clip, HR state write and truncating BGRX u8 pack
 //                       (reference models.py:552-593, keras_layers.py:211-230,
 //                       core/src/cuda_convert.cc.cu:95-108); tail = two-kernel form
+//  * lr_pack            the flow-free model's generator input: the LR frame alone (remove_flow.py)
 //  * temporal_*         moving-average output filter (frame_moving_avg.py)
 //  * copy_rows/to_float staging and introspection helpers
 #include <algorithm>
@@ -210,6 +211,40 @@ __global__ __launch_bounds__(256) void warp_pack_kernel(const f16 *__restrict__ 
 	T *dst = out + ((size_t)h * outPitch + w) * 64 + i * 16;
 	*reinterpret_cast<Vec8<T> *>(dst) = o0;
 	*reinterpret_cast<Vec8<T> *>(dst + 8) = o1;
+}
+
+// ---------------------------------------------------------------------------
+// flow-free generator input (remove_flow.py): the LR frame alone
+// ---------------------------------------------------------------------------
+// One thread per LR pixel: the pixel's B,G,R -> x/255 - 0.5 -> T, as warpQuarter makes slots 12..14 of
+// quarter 0 (same preprocessU8, same conversion: the record equals the recurrent model's in every slot
+// a flow-free conv_1 weighs).  One 16-byte store of slots 8..15; the other 56 slots stay zero.
+template <typename T>
+__global__ __launch_bounds__(256) void lr_pack_kernel(const std::uint8_t *__restrict__ frame,
+    std::ptrdiff_t frameStride, T *__restrict__ out, int outPitch, int H, int W) {
+	const int pix = blockIdx.x * 256 + threadIdx.x;
+	if (pix >= H * W) return;
+	const int w = pix % W;
+	const int h = pix / W;
+	const std::uint8_t *p = frame + h * frameStride + w * 4;
+	unsigned b, g, r;
+	if ((reinterpret_cast<std::uintptr_t>(p) & 3) == 0) {
+		const unsigned v = *reinterpret_cast<const unsigned *>(p);
+		b = v & 0xff;
+		g = (v >> 8) & 0xff;
+		r = (v >> 16) & 0xff;
+	} else {
+		b = p[0];
+		g = p[1];
+		r = p[2];
+	}
+	Vec8<T> o;
+#pragma unroll
+	for (int k = 0; k < 8; ++k) o[k] = static_cast<T>(0.f);
+	o[4] = static_cast<T>(preprocessU8(b));
+	o[5] = static_cast<T>(preprocessU8(g));
+	o[6] = static_cast<T>(preprocessU8(r));
+	*reinterpret_cast<Vec8<T> *>(out + ((size_t)h * outPitch + w) * 64 + 8) = o;
 }
 
 // ---------------------------------------------------------------------------
@@ -677,6 +712,20 @@ void launchWarpPack(DType dt, const void *state, const void *flow, const std::ui
 		    W, PW, padTop, padLeft, sums, static_cast<f16 *>(preWarpOut));
 	}
 	hipCheckLaunch("warp_pack");
+}
+
+void launchLrPack(DType dt, const std::uint8_t *frame, std::ptrdiff_t frameStride, void *out, int outPitch, int H,
+    int W, hipStream_t stream) {
+	if (outPitch <= 0) outPitch = W;
+	const unsigned nb = blocksFor((size_t)H * W);
+	if (dt == kF16) {
+		hipLaunchKernelGGL(lr_pack_kernel<f16>, dim3(nb), dim3(256), 0, stream, frame, frameStride, static_cast<f16 *>(out),
+		    outPitch, H, W);
+	} else {
+		hipLaunchKernelGGL(lr_pack_kernel<bf16>, dim3(nb), dim3(256), 0, stream, frame, frameStride,
+		    static_cast<bf16 *>(out), outPitch, H, W);
+	}
+	hipCheckLaunch("lr_pack");
 }
 
 namespace {

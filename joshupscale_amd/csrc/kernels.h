@@ -350,6 +350,14 @@ void launchWarpPack(DType dt, const void *state, const void *flow,
     const std::uint8_t *frame, std::ptrdiff_t frameStride, void *out, int outPitch, int H, int W, int PW,
     int padTop, int padLeft, const unsigned *sums, void *preWarpOut, hipStream_t stream);  // out at image pixel (0, 0), outPitch in pixels (0: W)
 
+// The generator input of a flow-free model (flow_arch "none", remove_flow.py): the LR frame's B,G,R as
+// slots 12..14 of each pixel's 64-slot record, converted exactly as launchWarpPack converts them.  One
+// 16-byte store per pixel covers slots 8..15 ({0,0,0,0,B,G,R,0}); the other slots of `out` must already
+// be zero (allocated zeroed, written by nothing else).  `frame` / `frameStride`: any address and any
+// signed stride (byte loads where the pixel is not 4-byte aligned).
+void launchLrPack(DType dt, const std::uint8_t *frame, std::ptrdiff_t frameStride, void *out, int outPitch, int H,
+    int W, hipStream_t stream);  // out at image pixel (0, 0), outPitch in pixels (0: W)
+
 // Temporal moving-average output filter with the scene-cut gate of
 // scripts/inference/onnx/frame_moving_avg.py:146-302, every mode of that script: global or
 // windowed gate (window in HR pixels), sign or tanh(gain * .) gate, L1 / L2 norm, limited

@@ -81,6 +81,18 @@ ModelFile::ModelFile(const void *blob, std::size_t size) {
 		c.temporalLimit = (flags & 2u) != 0;
 		c.temporalLuma = (flags & 4u) != 0;
 	}
+	if (c.flowArch == kFlowNone) {
+		// a flow-free model: its flow fields are written at their defaults and mean nothing (model_file.py);
+		// they are reset here so that nothing downstream (padded sizes, activation checks) reads them
+		const ModelConfig d;
+		c.numFlowInputs = d.numFlowInputs;
+		c.flowPadFactor = d.flowPadFactor;
+		c.flowResFilters = d.flowResFilters;
+		c.flowResBlocks = d.flowResBlocks;
+		c.flowFilters.clear();
+		c.flowActivation = d.flowActivation;
+		c.flowNegativeSlope = d.flowNegativeSlope;
+	}
 	if (scale != 4) throw std::invalid_argument("Invalid model: scale must be 4");
 	if (nTensors < 0 || headerBytes + static_cast<std::size_t>(nTensors) * kEntryBytes > size) {
 		throw std::invalid_argument("Invalid model: truncated tensor table");
@@ -116,6 +128,14 @@ ModelFile::ModelFile(const void *blob, std::size_t size) {
 		}
 	}
 	validateConfig(m_Config);
+	if (c.flowArch == kFlowNone) {  // model_file.py validate_tensors states the same checks with the same messages
+		for (const auto &kv : m_Tensors) {
+			if (kv.first.rfind("flow/", 0) == 0) throw std::invalid_argument("Invalid model: a flow-free model carries no flow/* tensors");
+		}
+		if (has("generator/conv_1/kernel") && tensor("generator/conv_1/kernel").dims != std::vector<int>{3, 3, 3, c.genFilters}) {
+			throw std::invalid_argument("Invalid model: a flow-free model's generator/conv_1/kernel must be [3, 3, 3, gen_filters]");
+		}
+	}
 }
 
 void validateConfig(const ModelConfig &c) {
@@ -123,12 +143,13 @@ void validateConfig(const ModelConfig &c) {
 	if (c.frameHeight < 2 || c.frameWidth < 2 || c.frameHeight > 8192 || c.frameWidth > 8192) {
 		bad("unsupported frame size");
 	}
-	if (c.numFlowInputs < 1 || c.numFlowInputs > 5) bad("1..5 flow inputs supported");
-	if (c.flowArch != 0 && c.flowArch != 1) bad("unknown flow architecture");
+	const bool flow = c.flowArch != kFlowNone;  // (a flow-free model: every flow field is ignored)
+	if (flow && (c.numFlowInputs < 1 || c.numFlowInputs > 5)) bad("1..5 flow inputs supported");
+	if (c.flowArch != 0 && c.flowArch != 1 && c.flowArch != kFlowNone) bad("unknown flow architecture");
 	if (c.computeDtype != kF16 && c.computeDtype != kBF16 && c.computeDtype != 2) {
 		bad("unknown compute dtype");  // 2 = JU_DTYPE_FP8 (e4m3 block convolutions over fp16)
 	}
-	if (c.flowPadFactor < 0 || c.flowPadFactor > 256) bad("flow_pad_factor must be in 0..256");
+	if (flow && (c.flowPadFactor < 0 || c.flowPadFactor > 256)) bad("flow_pad_factor must be in 0..256");
 	// Widths: the reference constructors take any integer (models.py:257-263, 334-339, 484-491); this
 	// engine admits what its GPU parity tests run against the oracle (tests/test_gpu_parity.py
 	// test_nondefault_widths_match_oracle): multiples of the 32-channel MFMA block up to the largest
@@ -137,6 +158,8 @@ void validateConfig(const ModelConfig &c) {
 		bad("gen_filters must be a multiple of 32 (at most 256)");
 	}
 	if (c.genBlocks < 0 || c.genBlocks > 256) bad("gen_blocks must be in 0..256");
+	// the temporal filter blends pre_warp, the warped previous output: there is none without the flow net
+	if (!flow && c.temporalStrength > 0.0f) bad("the temporal filter needs a flow net");
 	if (!(c.bnEps > 0.0f) || !std::isfinite(c.bnEps)) bad("bn_eps must be positive and finite");
 	if (!(c.temporalStrength >= 0.0f && c.temporalStrength <= 1.0f) ||
 	    !(c.temporalThreshold >= 0.0f && c.temporalThreshold <= 1.0f)) {
@@ -153,7 +176,7 @@ void validateConfig(const ModelConfig &c) {
 		}
 		if (act == 0 && slope != 0.0f) bad(std::string(what) + " negative_slope set on a relu model");
 	};
-	checkAct(c.flowActivation, c.flowNegativeSlope, "flow");
+	if (flow) checkAct(c.flowActivation, c.flowNegativeSlope, "flow");
 	checkAct(c.genActivation, c.genNegativeSlope, "generator");
 	if (c.flowArch == 0) {
 		const int nb = static_cast<int>(c.flowFilters.size()) / 2;
@@ -176,7 +199,7 @@ void validateConfig(const ModelConfig &c) {
 	// a 64-channel layer).  64-channel models: 33 M pixels (8192 x 4064, 5760 x 5800); tests/test_gpu_presets.py runs the
 	// engines at that size.  The reference has no such limit -- TensorRT builds an engine for whatever frame it is given.
 	{
-		int widest = std::max(64, c.genFilters);
+		int widest = std::max(64, c.genFilters);  // (a flow-free model: the generator's widths only)
 		if (c.flowArch == 0) {
 			for (std::size_t i = 0; i < c.flowFilters.size(); ++i) {
 				// (level of unit i: 0, 1, .., nb - 1, bottom, .., 0: a level-k tensor has 4^-k of the pixels)
@@ -184,11 +207,12 @@ void validateConfig(const ModelConfig &c) {
 				const int level = static_cast<int>(i) < nb ? static_cast<int>(i) : std::max(0, 2 * nb - 1 - static_cast<int>(i));
 				widest = std::max(widest, c.flowFilters[i] >> (2 * std::min(level, 4)));
 			}
-		} else {
+		} else if (c.flowArch == 1) {
 			widest = std::max(widest, c.flowResFilters);
 		}
-		const unsigned long long rows = static_cast<unsigned long long>((c.paddedHeight() + 7) / 8 * 8 + 2);
-		const unsigned long long pitch = static_cast<unsigned long long>((c.paddedWidth() + 31) / 32 * 32 + 2);
+		const int ph = flow ? c.paddedHeight() : c.frameHeight, pw = flow ? c.paddedWidth() : c.frameWidth;
+		const unsigned long long rows = static_cast<unsigned long long>((ph + 7) / 8 * 8 + 2);
+		const unsigned long long pitch = static_cast<unsigned long long>((pw + 31) / 32 * 32 + 2);
 		if (rows * pitch * 2ull * static_cast<unsigned long long>(widest) > 0xFFC00000ull) {
 			bad("frame too large for this model: an activation tensor would reach 4 GiB (" + std::to_string(widest) +
 			    " channels x " + std::to_string(rows * pitch) + " pixels x 2 bytes)");
@@ -360,6 +384,16 @@ std::vector<int> generatorInputMap() {
 	return m;
 }
 
+// The same record for a flow-free model (conv_1 has the 3 LR input channels only): the LR frame in
+// slots 12..14, where the recurrent model's record carries it, every other slot a zero weight.
+std::vector<int> lrInputMap() {
+	std::vector<int> m(64, -1);
+	m[12] = 0;
+	m[13] = 1;
+	m[14] = 2;
+	return m;
+}
+
 }  // namespace
 
 std::vector<ConvSpec> foldModel(const ModelFile &model) {
@@ -386,7 +420,9 @@ std::vector<ConvSpec> foldModel(const ModelFile &model) {
 	// ---- flow (models.py:257-331, 334-481) ----
 	int cin = 3 * c.numFlowInputs;
 	int h = c.paddedHeight(), w = c.paddedWidth();
-	if (c.flowArch == 0) {
+	if (c.flowArch == kFlowNone) {
+		// (no flow net)
+	} else if (c.flowArch == 0) {
 		const int nb = static_cast<int>(c.flowFilters.size()) / 2;
 		for (int i = 0; i < 2 * nb; ++i) {
 			const std::string n = "flow/block_" + std::to_string(i + 1);
@@ -418,8 +454,9 @@ std::vector<ConvSpec> foldModel(const ModelFile &model) {
 		add("flow/conv_2", "", true, h, w, 1, n, 32);
 	}
 	// ---- generator (models.py:484-595) ----
-	add("generator/conv_1", "generator/bn_1", false, H, W, 9, 51, c.genFilters);
-	out.back().cinMap = generatorInputMap();
+	// (flow-free: 3 input channels, packed into the same 64-slot record -- every conv_1 route reads it)
+	add("generator/conv_1", "generator/bn_1", false, H, W, 9, c.recurrent() ? 51 : 3, c.genFilters);
+	out.back().cinMap = c.recurrent() ? generatorInputMap() : lrInputMap();
 	for (int i = 0; i < c.genBlocks; ++i) {
 		const std::string b = "generator/block_" + std::to_string(i + 1);
 		add(b + "/conv_1", b + "/bn_1", false, H, W, 9, c.genFilters, c.genFilters);

@@ -15,11 +15,13 @@
 
 namespace ju {
 
+constexpr int kFlowNone = 2;  // ModelConfig::flowArch of a flow-free model
+
 struct ModelConfig {
 	int frameHeight = 0;
 	int frameWidth = 0;
 	int numFlowInputs = 4;
-	int flowArch = 0;  // 0 = autoencoder, 1 = resnet
+	int flowArch = 0;  // 0 = autoencoder, 1 = resnet, 2 = none (flow-free single-image model, remove_flow.py)
 	int flowPadFactor = 0;
 	bool normalizeBrightness = false;
 	int genFilters = 64;
@@ -41,6 +43,9 @@ struct ModelConfig {
 	// 0 = relu, 1 = lrelu (keras LeakyReLU(negative_slope))
 	int flowActivation = 0, genActivation = 0;
 	float flowNegativeSlope = 0.0f, genNegativeSlope = 0.0f;
+
+	// false: flow_arch "none" -- no flow net, no warp, no state: the generator sees the LR frame only
+	bool recurrent() const { return flowArch != kFlowNone; }
 
 	// reference scripts/training/models.py:735-744
 	int paddedHeight() const {

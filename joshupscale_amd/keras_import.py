@@ -35,6 +35,7 @@ from typing import Dict, List, Mapping, Sequence, Tuple
 
 import numpy as np
 
+from . import model_file as M
 from .model_file import ACTIVATION, DEFAULT_NEGATIVE_SLOPE, ModelConfig
 
 BN_VARS = ("gamma", "beta", "moving_mean", "moving_variance")
@@ -121,7 +122,7 @@ def _count_blocks(layers: Layers) -> int:
     return n
 
 
-def container_weights(generator: Layers, flow: Layers, base: ModelConfig
+def container_weights(generator: Layers, flow: Layers, base: ModelConfig, remove_flow: bool = False
                       ) -> Tuple[ModelConfig, Dict[str, np.ndarray]]:
     """Map the two sub-models' layers to container tensors.
 
@@ -130,12 +131,20 @@ def container_weights(generator: Layers, flow: Layers, base: ModelConfig
     :func:`activation_fields`); filters, block counts,
     the flow architecture and the number of flow inputs are read off the shapes
     and override ``base``.
+
+    ``remove_flow=True``: the full model is imported and then cut down to the flow-free
+    single-image model (``model_file.remove_flow``, scripts/inference/onnx/remove_flow.py).
+    A generator-only layer set (``flow`` empty) whose ``conv_1`` is ``(3, 3, 3, F)`` -- an
+    already flow-free model -- imports as ``flow_arch="none"``.
     """
+    if remove_flow:
+        return M.remove_flow(*container_weights(generator, flow, base))
     w: Dict[str, np.ndarray] = {}
 
     # ---- generator (models.py:521-593) ----
     k = _put_conv(w, "generator/conv_1", _need(generator, "generator", "conv_1"), bias=False)
-    if k.shape[:3] != (3, 3, 51):
+    flow_free = not flow and k.shape[:3] == (3, 3, 3)
+    if k.shape[:3] != (3, 3, 51) and not flow_free:
         raise ValueError(f"generator/conv_1/kernel: shape {k.shape}, expected (3, 3, 51, F)")
     nf = int(k.shape[3])
     _put_bn(w, "generator/bn_1", _need(generator, "generator", "bn_1"), nf)
@@ -157,6 +166,11 @@ def container_weights(generator: Layers, flow: Layers, base: ModelConfig
                     bias=True)
     if kt2.shape != (2, 2, 3, 32) or w["generator/conv_trans_2/bias"].shape != (3,):
         raise ValueError(f"generator/conv_trans_2: kernel {kt2.shape}, expected (2, 2, 3, 32) + bias (3,)")
+    if flow_free:
+        d = ModelConfig()
+        cfg = replace(base, flow_arch="none", gen_filters=nf, gen_blocks=gen_blocks,
+                      **{f: getattr(d, f) for f in M.FLOW_FIELDS})
+        return cfg, w
 
     # ---- flow (models.py:257-331 resnet, 334-481 autoencoder) ----
     head = np.asarray(_need(flow, "flow", "conv_2")[0])

@@ -18,7 +18,7 @@ Layout (all little endian):
     8   u32      version (1)
     12  u32      header_bytes (offset of the tensor table)
     16  u32      frame_height, frame_width, scale(=4), num_flow_inputs
-    32  u32      flow_arch (0 autoencoder, 1 resnet), flow_pad_factor,
+    32  u32      flow_arch (0 autoencoder, 1 resnet, 2 none), flow_pad_factor,
                  normalize_brightness, gen_filters
     48  u32      gen_blocks, flow_res_filters, flow_res_blocks, n_flow_filters
     64  u32[8]   flow_filters
@@ -29,6 +29,9 @@ Layout (all little endian):
     116 u32      activations: bits 0-7 flow net, bits 8-15 generator (0 relu, 1 lrelu)
     120 f32      flow negative_slope, generator negative_slope (read only for lrelu)
                                                     -> header_bytes = 128
+    flow_arch 2 ("none"): a flow-free single-image model (scripts/inference/onnx/remove_flow.py, see
+    remove_flow): no flow/* tensors, generator/conv_1/kernel [3, 3, 3, gen_filters]; both loaders
+    ignore the flow fields (remove_flow sets them to their ModelConfig defaults).
     -- only when the temporal filter uses a non-default mode, header_bytes = 160: --
     128 u32      temporal_window (HR pixels, 0 = global gate)
     132 f32      temporal_gain (0 = sign gate, else tanh(gain * (m - t)))
@@ -42,7 +45,7 @@ Layout (all little endian):
 from __future__ import annotations
 
 import struct
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, Tuple
 
 import numpy as np
@@ -55,7 +58,7 @@ DTYPE_F16 = 0
 DTYPE_BF16 = 1
 DTYPE_FP8 = 2  # e4m3 block convolutions over fp16 (csrc/fp8.h)
 
-FLOW_ARCH = {"autoencoder": 0, "resnet": 1}
+FLOW_ARCH = {"autoencoder": 0, "resnet": 1, "none": 2}
 FLOW_ARCH_INV = {v: k for k, v in FLOW_ARCH.items()}
 # ACTIVATIONS of scripts/training/models.py:24-27
 ACTIVATION = {"relu": 0, "lrelu": 1}
@@ -129,7 +132,13 @@ PRESETS: Dict[str, ModelConfig] = {
     # `activation: lrelu` in both sub-models (reference models.py:24-27; the INT8 quantiser of the
     # deployed graphs lists LeakyRelu, quantize_int8.py:177-178), keras' default slope
     "psp-quality-lrelu": ModelConfig(flow_activation="lrelu", gen_activation="lrelu"),
+    # psp-quality with its flow net cut out (remove_flow): a stateless single-image 4x upscaler
+    "psp-quality-noflow": ModelConfig(flow_arch="none"),
 }
+
+# the header fields that describe the flow net: a flow-free model carries them at these defaults
+FLOW_FIELDS = ("num_flow_inputs", "flow_filters", "flow_res_filters", "flow_res_blocks", "flow_pad_factor",
+               "flow_activation", "flow_negative_slope")
 
 
 def _bn(rng: np.random.Generator, c: int) -> Dict[str, np.ndarray]:
@@ -151,6 +160,11 @@ def make_seeded_weights(cfg: ModelConfig, seed: int = 42) -> Dict[str, np.ndarra
     flow head scaled so that |flow| stays within a few HR pixels.
     Names follow the Keras layer names of scripts/training/models.py.
     """
+    if cfg.flow_arch == "none":
+        # the seeded recurrent model of the same generator (auto-encoder flow net, filter off) with its
+        # flow net removed: psp-quality-noflow's weights are remove_flow(psp-quality's)
+        twin = replace(cfg, flow_arch="autoencoder", temporal_strength=0.0)
+        return remove_flow(twin, make_seeded_weights(twin, seed))[1]
     rng = np.random.default_rng(seed)
     w: Dict[str, np.ndarray] = {}
 
@@ -220,37 +234,85 @@ def validate_config(cfg: ModelConfig) -> None:
     engine admits what its GPU parity tests run against the oracle."""
     def bad(what: str):
         raise ValueError("Invalid model: " + what)
-    if not 1 <= cfg.num_flow_inputs <= 5:
+    flow = cfg.flow_arch != "none"  # (a flow-free model: every flow field is ignored)
+    if flow and not 1 <= cfg.num_flow_inputs <= 5:
         bad("1..5 flow inputs supported")
     if cfg.gen_filters <= 0 or cfg.gen_filters > 256 or cfg.gen_filters % 32:
         bad("gen_filters must be a multiple of 32 (at most 256)")
     if not 0 <= cfg.gen_blocks <= 256:
         bad("gen_blocks must be in 0..256")
+    if not flow and cfg.temporal_strength > 0:
+        bad(NO_FLOW_TEMPORAL)
     if cfg.flow_arch == "autoencoder":
         nb = len(cfg.flow_filters) // 2
         if nb < 1 or cfg.padded_height % (1 << nb) or cfg.padded_width % (1 << nb):
             bad("padded frame size must be divisible by 2^(flow depth)")
         if any(f <= 0 or f > 512 or f % 32 for f in cfg.flow_filters):
             bad("flow filters must be multiples of 32 (at most 512)")
-    else:
+    elif cfg.flow_arch == "resnet":
         if cfg.flow_res_filters <= 0 or cfg.flow_res_filters > 256 or cfg.flow_res_filters % 32:
             bad("flow_res_filters must be a multiple of 32 (at most 256)")
         if not 0 <= cfg.flow_res_blocks <= 256:
             bad("flow_res_blocks must be in 0..256")
     # no activation tensor may reach 4 GiB (32-bit byte offsets in several kernels; csrc/model.cpp states the rule)
-    widest = max(64, cfg.gen_filters)
+    widest = max(64, cfg.gen_filters)  # (a flow-free model: the generator's widths only)
     if cfg.flow_arch == "autoencoder":
         nb = len(cfg.flow_filters) // 2
         for i, f in enumerate(cfg.flow_filters):
             level = i if i < nb else max(0, 2 * nb - 1 - i)
             widest = max(widest, f >> (2 * min(level, 4)))
-    else:
+    elif cfg.flow_arch == "resnet":
         widest = max(widest, cfg.flow_res_filters)
-    rows = (cfg.padded_height + 7) // 8 * 8 + 2
-    pitch = (cfg.padded_width + 31) // 32 * 32 + 2
+    ph, pw = (cfg.padded_height, cfg.padded_width) if flow else (cfg.frame_height, cfg.frame_width)
+    rows = (ph + 7) // 8 * 8 + 2
+    pitch = (pw + 31) // 32 * 32 + 2
     if rows * pitch * 2 * widest > 0xFFC00000:
         bad(f"frame too large for this model: an activation tensor would reach 4 GiB ({widest} channels x "
             f"{rows * pitch} pixels x 2 bytes)")
+
+
+# the flow-free model's own checks (csrc/model.cpp states them with the same messages)
+NO_FLOW_TEMPORAL = "the temporal filter needs a flow net"
+NO_FLOW_TENSORS = "a flow-free model carries no flow/* tensors"
+NO_FLOW_CONV_1 = "a flow-free model's generator/conv_1/kernel must be [3, 3, 3, gen_filters]"
+
+
+def validate_tensors(cfg: ModelConfig, weights: Dict[str, np.ndarray]) -> None:
+    """The tensor checks of a flow-free container (csrc/model.cpp ModelFile, same messages); the
+    C++ loader checks every other layer's shape when it folds the model."""
+    if cfg.flow_arch != "none":
+        return
+    if any(n.startswith("flow/") for n in weights):
+        raise ValueError("Invalid model: " + NO_FLOW_TENSORS)
+    k = weights.get("generator/conv_1/kernel")
+    if k is not None and tuple(np.shape(k)) != (3, 3, 3, cfg.gen_filters):
+        raise ValueError("Invalid model: " + NO_FLOW_CONV_1)
+
+
+def remove_flow(cfg: ModelConfig, weights: Dict[str, np.ndarray]
+                ) -> Tuple[ModelConfig, Dict[str, np.ndarray]]:
+    """scripts/inference/onnx/remove_flow.py on a container: the flow net is cut out and the
+    generator sees the current LR frame only -- ``generator/conv_1``'s kernel keeps input channels
+    0..2, the LR image (remove_flow.py:67-76 in ONNX layout [out, in, kh, kw]; here Keras
+    [kh, kw, in, out], channel order of models.py:523-530).  Every other generator tensor is kept
+    byte for byte.  The result is a stateless single-image 4x upscaler (flow_arch "none")."""
+    if cfg.flow_arch == "none":
+        raise ValueError("remove_flow: the model has no flow net")
+    if cfg.temporal_strength > 0:
+        raise ValueError("Invalid model: " + NO_FLOW_TEMPORAL)
+    d = ModelConfig()
+    out_cfg = replace(cfg, flow_arch="none", temporal_strength=0.0,
+                      **{f: getattr(d, f) for f in FLOW_FIELDS + (
+                          "temporal_threshold", "temporal_window", "temporal_gain", "temporal_norm",
+                          "temporal_limit", "temporal_luma")})
+    out = {}
+    for n, v in weights.items():
+        if n.startswith("flow/"):
+            continue
+        if n == "generator/conv_1/kernel":
+            v = np.asarray(v)[:, :, :3, :]
+        out[n] = np.ascontiguousarray(v, dtype=np.float32)
+    return out_cfg, out
 
 
 def serialize(cfg: ModelConfig, weights: Dict[str, np.ndarray], validate: bool = True) -> bytes:
@@ -258,6 +320,7 @@ def serialize(cfg: ModelConfig, weights: Dict[str, np.ndarray], validate: bool =
     (the loader tests need such files)."""
     if validate:
         validate_config(cfg)
+        validate_tensors(cfg, weights)
     names = list(weights.keys())
     ff = list(cfg.flow_filters) + [0] * (8 - len(cfg.flow_filters))
     if len(cfg.flow_filters) > 8:

@@ -289,9 +289,15 @@ class Runtime:
         _check(self._lib, read(self._h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.size, C.byref(n)))
         return arr
 
+    @property
+    def recurrent(self) -> bool:
+        """False for a flow-free model (flow_arch "none", ``model_file.remove_flow``): no state,
+        every frame is upscaled on its own and ``reset`` does nothing."""
+        return self.stat("recurrent") != 0
+
     def stat(self, key: str) -> float:
         """``ju_get_stat``: "graph_replays", "eager_runs", "direct_graphs",
-        "resident_tower", "resident_flow", "launches_per_frame"."""
+        "resident_tower", "resident_flow", "launches_per_frame", "recurrent"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
