@@ -69,6 +69,33 @@ typedef struct ju_image {
 	size_t height;
 } ju_image;
 
+/* ---- 8-bit 4:2:0 YUV frames (no reference counterpart: the reference takes BGRX Images only) ------------------
+ * Video decoders emit and encoders take NV12 / I420 (AviSynth: YV12 = I420 with the chroma planes swapped -- planes
+ * are passed by pointer, so their order in memory does not matter).  ju_process_frame converts on the GPU, inside the
+ * runtime's own staging: a YUV input is decoded into the BGRX frame the network consumes, the network's BGRX output is
+ * encoded into the caller's planes.  Input and output formats are independent (all nine pairs).  A YUV frame is one
+ * step of the same recurrent stream: ju_process, ju_process_frame and ju_process_batch may be mixed on one runtime.
+ *
+ * The conversion is integer arithmetic, defined exactly ("YUV frames"): BT.601 / BT.709 coefficients,
+ * limited (16..235 / 16..240) or full range, chroma sited as MPEG-2 / H.264 by default (co-sited horizontally with the
+ * even luma columns, centred vertically between two rows); decoding upsamples chroma bilinearly (weights 3:1 vertically,
+ * 1:1 horizontally), encoding filters [1,2,1] x [1,1].
+ *
+ * Limits: 8-bit 4:2:0 only (no P010 / 10-bit); no YUV graphics resources (GL textures stay BGRX); no YUV frames in
+ * ju_process_batch look-ahead passes; the C++ plugin surface (JoshUpscale/core.h) is unchanged and takes BGRX only. */
+enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2 };
+enum { JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3 };
+
+typedef struct ju_frame {
+	int format;            /* JU_FMT_* */
+	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX */
+	uint8_t location;      /* JU_LOC_CPU or JU_LOC_DEVICE (BGRX: any location a ju_image takes) */
+	size_t width, height;  /* in pixels (luma); even for I420 / NV12 */
+	void *planes[3];       /* BGRX: [0]; I420: Y, U, V; NV12: Y, interleaved UV (U first) */
+	ptrdiff_t strides[3];  /* bytes per row of each plane (first logical row at planes[k]), any sign,
+	                          |stride| >= the plane's row bytes: Y = width, U / V = width / 2, UV = width, BGRX = 4 width */
+} ju_frame;
+
 /* Replaces createRuntime(int deviceId, const std::filesystem::path &modelPath)
  * (core/public/JoshUpscale/core.h:91-92, core/src/core.cc:153-175, 197-199):
  * reads the whole model file, selects the device for the duration of the call,
@@ -134,6 +161,18 @@ JU_API int ju_prepare_batch(ju_runtime *runtime, const ju_image *inputs, const j
  * strictly ordered (the recurrence is carried by stream order). */
 JU_API int ju_enqueue(ju_runtime *runtime, const ju_image *input, const ju_image *output);
 JU_API int ju_synchronize(ju_runtime *runtime);
+
+/* One step of the stream on frames of any format (ju_frame; synchronous, like ju_process).  A pair of BGRX frames
+ * behaves exactly as ju_process with the same pointers, strides and locations (GL resources and the direct device path
+ * included).  Where a side is YUV its conversion kernel replaces that side's staging copy; host planes are uploaded /
+ * copied out plane by plane (4:2:0 moves 1.5 bytes per pixel over PCIe instead of BGRX's 4).
+ * JU_ERR_INVALID_ARGUMENT, checked before anything is launched (a refused call leaves the runtime and its state as
+ * they were): an odd width or height of a YUV frame, a size other than the runtime's, a NULL plane, an unknown format
+ * or colour space, a YUV frame at JU_LOC_GRAPHICS_RESOURCE, a |stride| smaller than the plane's row. */
+JU_API int ju_process_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output);
+/* Asynchronous form (like ju_enqueue): JU_LOC_DEVICE frames only -- a host frame is JU_ERR_INVALID_ARGUMENT;
+ * ju_synchronize waits. */
+JU_API int ju_enqueue_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output);
 
 /* Registers a pair of JU_LOC_DEVICE frame buffers the caller is going to pass to ju_process /
  * ju_enqueue: the hipGraphs of the pair (one per binding set) are captured NOW, so that no

@@ -54,6 +54,12 @@ JU_API int ju_debug_set(const char *key, int value);
  * that the CPU tests can pin it against the oracle's restatement.  No device needed. */
 JU_API int ju_debug_e4m3(const float *values, unsigned char *codes, size_t count);
 
+/* One of the two colour conversion kernels of ju_process_frame alone, on caller-supplied device buffers, on the
+ * current device (synchronous).  direction 0: planes (format JU_FMT_I420 / JU_FMT_NV12) -> BGRX at `bgrx`;
+ * 1: BGRX -> planes.  Any byte alignment, any signed strides (as in ju_frame). */
+JU_API int ju_debug_yuv(int direction, int format, int colorspace, size_t width, size_t height, void *bgrx,
+    ptrdiff_t bgrx_stride, void *const planes[3], const ptrdiff_t strides[3]);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -75,6 +75,34 @@ ju::Frame toFrame(const ju_image *img) {
 	    img->height};
 }
 
+// A ju_frame as the engine's AnyFrame; BGRX frames exactly as toFrame makes them of a ju_image
+ju::AnyFrame toAnyFrame(const ju_frame *f) {
+	if (f == nullptr) throw std::invalid_argument("frame is NULL");
+	ju::AnyFrame a;
+	if (f->format == JU_FMT_BGRX) {
+		const ju_image img{f->planes[0], f->location, f->strides[0], f->width, f->height};
+		a.bgrx = toFrame(&img);
+		return a;
+	}
+	if (f->format != JU_FMT_I420 && f->format != JU_FMT_NV12) {
+		throw std::invalid_argument("frame has an unknown format " + std::to_string(f->format));
+	}
+	if (f->location > JU_LOC_GRAPHICS_RESOURCE) throw std::invalid_argument("frame has an unknown location");
+	a.yuv = true;
+	a.planes.format = static_cast<ju::PixelFormat>(f->format);
+	a.planes.colorspace = f->colorspace;
+	a.planes.location = static_cast<ju::Location>(f->location);
+	a.planes.width = f->width;
+	a.planes.height = f->height;
+	for (int k = 0; k < 3; ++k) {
+		a.planes.planes[k] = f->planes[k];
+		a.planes.strides[k] = f->strides[k];
+	}
+	return a;
+}
+
+ju::Location locationOf(const ju::AnyFrame &f) { return f.yuv ? f.planes.location : f.bgrx.location; }
+
 ju::Engine &engineOf(ju_runtime *rt) {
 	if (rt == nullptr || !rt->engine) throw std::invalid_argument("runtime is NULL");
 	return *rt->engine;
@@ -179,6 +207,33 @@ int ju_enqueue(ju_runtime *runtime, const ju_image *input, const ju_image *outpu
 			throw std::invalid_argument("ju_enqueue needs JU_LOC_DEVICE images");
 		}
 		engineOf(runtime).enqueue(in, out);
+	});
+}
+
+int ju_process_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output) {
+	return guarded([&] {
+		ju::Engine &e = engineOf(runtime);
+		const ju::AnyFrame in = toAnyFrame(input), out = toAnyFrame(output);
+		if (!in.yuv && !out.yuv) {
+			e.process(in.bgrx, out.bgrx);
+		} else {
+			e.processFrame(in, out);
+		}
+	});
+}
+
+int ju_enqueue_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output) {
+	return guarded([&] {
+		ju::Engine &e = engineOf(runtime);
+		const ju::AnyFrame in = toAnyFrame(input), out = toAnyFrame(output);
+		if (locationOf(in) != ju::Location::Device || locationOf(out) != ju::Location::Device) {
+			throw std::invalid_argument("ju_enqueue_frame needs device frames");
+		}
+		if (!in.yuv && !out.yuv) {
+			e.enqueue(in.bgrx, out.bgrx);
+		} else {
+			e.enqueueFrame(in, out);
+		}
 	});
 }
 
@@ -313,6 +368,38 @@ int ju_debug_set(const char *key, int value) {
 		else if (k == "res_block_plain") ju::setResBlockPlain(value);
 		else if (k == "fp8_block_form") ju::setFp8BlockForm(value);
 		else throw std::invalid_argument("unknown debug key " + k);
+	});
+}
+
+int ju_debug_yuv(int direction, int format, int colorspace, size_t width, size_t height, void *bgrx,
+    ptrdiff_t bgrx_stride, void *const planes[3], const ptrdiff_t strides[3]) {
+	return guarded([&] {
+		if (direction != 0 && direction != 1) throw std::invalid_argument("ju_debug_yuv: direction must be 0 or 1");
+		if (format != JU_FMT_I420 && format != JU_FMT_NV12) throw std::invalid_argument("ju_debug_yuv: not a YUV format");
+		if (width == 0 || height == 0 || width % 2 || height % 2 || width > (1u << 15) || height > (1u << 15)) {
+			throw std::invalid_argument("ju_debug_yuv: width and height must be even, 2 .. 32768");
+		}
+		if (bgrx == nullptr || planes == nullptr || strides == nullptr || planes[0] == nullptr || planes[1] == nullptr ||
+		    (format == JU_FMT_I420 && planes[2] == nullptr)) {
+			throw std::invalid_argument("ju_debug_yuv: null buffer");
+		}
+		ju::YuvPlanes p;
+		p.y = static_cast<std::uint8_t *>(planes[0]);
+		p.u = static_cast<std::uint8_t *>(planes[1]);
+		p.v = format == JU_FMT_I420 ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
+		p.yStride = strides[0];
+		p.uStride = strides[1];
+		p.vStride = format == JU_FMT_I420 ? strides[2] : 0;
+		const bool nv12 = format == JU_FMT_NV12;
+		const int w = static_cast<int>(width), h = static_cast<int>(height);
+		if (direction == 0) {
+			ju::launchYuv420ToBgrx(nv12, p, ju::yuvDecodeCoefficients(colorspace), static_cast<std::uint8_t *>(bgrx),
+			    bgrx_stride, w, h, nullptr);
+		} else {
+			ju::launchBgrxToYuv420(nv12, static_cast<const std::uint8_t *>(bgrx), bgrx_stride,
+			    ju::yuvEncodeCoefficients(colorspace), p, w, h, nullptr);
+		}
+		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }
 

@@ -1,0 +1,329 @@
+// 8-bit 4:2:0 YUV (I420 / YV12 / NV12) <-> BGRX conversion on gfx950: the colour staging of ju_process_frame.
+//
+// Both kernels are integer arithmetic and compute exactly the numpy definition of tests/yuv_reference.py (formulas:
+// INTEGRATION.md, "YUV frames").  They are HBM-bound: one thread covers a strip of 16 pixels x 2 luma rows (one row of
+// chroma cells), lanes run along the strip's row and wrap to the next row pair, so a wave reads and writes contiguous
+// bytes; where a row is 16-byte aligned (every staging buffer, every plane a decoder allocates) its bytes move as
+// 16-byte loads / stores, elsewhere (odd offsets, odd strides, the last strip of a row) byte by byte.  Rows are
+// addressed with their signed stride: bottom-up planes need no flip pass.
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <stdexcept>
+
+#include "kernel_common.h"
+#include "kernels.h"
+
+namespace ju {
+namespace {
+
+constexpr int kStrip = 16;  // luma pixels per thread and row
+
+__device__ inline bool alignedTo(const void *p, unsigned a) {
+	return (reinterpret_cast<std::uintptr_t>(p) & (a - 1)) == 0;
+}
+
+__device__ inline int byteOf(const unsigned *w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255; }
+
+__device__ inline int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// `N` (8 or 16) bytes of one row from byte `col` on, as words; `fast`: in range and aligned (else byte by byte, the
+// column index clamped to `last`)
+template <int N>
+__device__ inline void loadBytes(const std::uint8_t *row, int col, int last, bool fast, unsigned (&w)[N / 4]) {
+	if (fast && alignedTo(row + col, N)) {
+		if constexpr (N == 16) {
+			const uint4 v = *reinterpret_cast<const uint4 *>(row + col);
+			w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+		} else {
+			const uint2 v = *reinterpret_cast<const uint2 *>(row + col);
+			w[0] = v.x, w[1] = v.y;
+		}
+		return;
+	}
+	if (fast && alignedTo(row + col, 4)) {
+#pragma unroll
+		for (int q = 0; q < N / 4; ++q) w[q] = reinterpret_cast<const unsigned *>(row + col)[q];
+		return;
+	}
+#pragma unroll
+	for (int q = 0; q < N / 4; ++q) {
+		unsigned x = 0;
+#pragma unroll
+		for (int b = 0; b < 4; ++b) x |= static_cast<unsigned>(row[min(col + 4 * q + b, last)]) << (8 * b);
+		w[q] = x;
+	}
+}
+
+// `N` bytes (8 or 16) of one row from byte `col` on; `fast`: all in range (else only the first `n`)
+template <int N>
+__device__ inline void storeBytes(std::uint8_t *row, int col, int n, bool fast, const unsigned (&w)[N / 4]) {
+	if (fast && alignedTo(row + col, N)) {
+		if constexpr (N == 16) {
+			*reinterpret_cast<uint4 *>(row + col) = make_uint4(w[0], w[1], w[2], w[3]);
+		} else {
+			*reinterpret_cast<uint2 *>(row + col) = make_uint2(w[0], w[1]);
+		}
+		return;
+	}
+	if (fast && alignedTo(row + col, 4)) {
+#pragma unroll
+		for (int q = 0; q < N / 4; ++q) reinterpret_cast<unsigned *>(row + col)[q] = w[q];
+		return;
+	}
+#pragma unroll
+	for (int k = 0; k < N; ++k) {
+		if (fast || k < n) row[col + k] = static_cast<std::uint8_t>(byteOf(w, k));
+	}
+}
+
+// Y, U, V (I420) or Y, UV (NV12) -> BGRX.  Thread = chroma row j (luma rows 2j, 2j + 1) x luma columns x0 .. x0 + 15;
+// it reads chroma rows j - 1 .. j + 1 at columns x0 / 2 .. x0 / 2 + 8 (clamped to the plane).
+template <bool NV12>
+__global__ __launch_bounds__(256) void yuv420_to_bgrx_kernel(YuvPlanes src, YuvDecode k, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H) {
+	const int strips = (W + kStrip - 1) / kStrip;
+	const int idx = blockIdx.x * 256 + threadIdx.x;
+	if (idx >= strips * (H / 2)) return;
+	const int j = idx / strips;
+	const int x0 = (idx - j * strips) * kStrip;
+	const int CW = W / 2, CH = H / 2;
+	const int c0 = x0 / 2;
+	const bool full = x0 + kStrip <= W;
+
+	// chroma rows j - 1, j, j + 1 (clamped), 9 samples each: columns c0 .. c0 + 8 (clamped)
+	int cu[3][9], cv[3][9];
+#pragma unroll
+	for (int r = 0; r < 3; ++r) {
+		const int jr = min(max(j - 1 + r, 0), CH - 1);
+		const int last = min(c0 + 8, CW - 1);
+		if constexpr (NV12) {
+			const std::uint8_t *row = src.u + static_cast<std::ptrdiff_t>(jr) * src.uStride;
+			if (!full) {  // (the last strip of a row: U and V clamped to the last cell each)
+#pragma unroll
+				for (int i = 0; i < 8; ++i) {
+					const int c = min(c0 + i, CW - 1);
+					cu[r][i] = row[2 * c];
+					cv[r][i] = row[2 * c + 1];
+				}
+			} else {
+				unsigned w[4];
+				loadBytes<16>(row, 2 * c0, 2 * CW - 1, true, w);
+#pragma unroll
+				for (int i = 0; i < 8; ++i) {
+					cu[r][i] = byteOf(w, 2 * i);
+					cv[r][i] = byteOf(w, 2 * i + 1);
+				}
+			}
+			cu[r][8] = row[2 * last];
+			cv[r][8] = row[2 * last + 1];
+		} else {
+			const std::uint8_t *rowU = src.u + static_cast<std::ptrdiff_t>(jr) * src.uStride;
+			const std::uint8_t *rowV = src.v + static_cast<std::ptrdiff_t>(jr) * src.vStride;
+			unsigned wu[2], wv[2];
+			loadBytes<8>(rowU, c0, CW - 1, full, wu);
+			loadBytes<8>(rowV, c0, CW - 1, full, wv);
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				cu[r][i] = byteOf(wu, i);
+				cv[r][i] = byteOf(wv, i);
+			}
+			cu[r][8] = rowU[last];
+			cv[r][8] = rowV[last];
+		}
+	}
+
+#pragma unroll
+	for (int r = 0; r < 2; ++r) {
+		const int y = 2 * j + r;
+		unsigned yw[4];
+		loadBytes<16>(src.y + static_cast<std::ptrdiff_t>(y) * src.yStride, x0, W - 1, full, yw);
+		// vertical: 3 x row j + row j - 1 (even luma row) or j + 1 (odd)
+		int vu[9], vv[9];
+#pragma unroll
+		for (int i = 0; i < 9; ++i) {
+			vu[i] = 3 * cu[1][i] + cu[r == 0 ? 0 : 2][i];
+			vv[i] = 3 * cv[1][i] + cv[r == 0 ? 0 : 2][i];
+		}
+		unsigned px[16];
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			const int i = p >> 1;
+			const int du = ((p & 1) ? vu[i] + vu[i + 1] : 2 * vu[i]) - 1024;
+			const int dv = ((p & 1) ? vv[i] + vv[i + 1] : 2 * vv[i]) - 1024;
+			const int yd = k.ky * (8 * (byteOf(yw, p) - k.oy));
+			const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
+			const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
+			const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+			px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
+		}
+		std::uint8_t *row = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
+		const int n = min(kStrip, W - x0);
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const unsigned w[4] = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
+			storeBytes<16>(row, 4 * (x0 + 4 * q), 4 * (n - 4 * q), full, w);
+		}
+	}
+}
+
+// BGRX -> Y, U, V (I420) or Y, UV (NV12).  Thread = luma rows 2j, 2j + 1 x columns x0 .. x0 + 15 (+ column x0 - 1,
+// clamped to 0, for the chroma filter) -> 2 x 16 luma bytes and chroma cells x0 / 2 .. x0 / 2 + 7 of row j.
+template <bool NV12>
+__global__ __launch_bounds__(256) void bgrx_to_yuv420_kernel(const std::uint8_t *__restrict__ src,
+    std::ptrdiff_t srcStride, YuvEncode k, YuvPlanes dst, int W, int H) {
+	const int strips = (W + kStrip - 1) / kStrip;
+	const int idx = blockIdx.x * 256 + threadIdx.x;
+	if (idx >= strips * (H / 2)) return;
+	const int j = idx / strips;
+	const int x0 = (idx - j * strips) * kStrip;
+	const bool full = x0 + kStrip <= W;
+	const int n = min(kStrip, W - x0);  // luma columns of this strip (even)
+
+	// per chroma cell: the [1, 2, 1] x [1, 1] sums of R, G, B (8 x C)
+	int sr[8], sg[8], sb[8];
+#pragma unroll
+	for (int i = 0; i < 8; ++i) sr[i] = sg[i] = sb[i] = 0;
+#pragma unroll
+	for (int r = 0; r < 2; ++r) {
+		const int y = 2 * j + r;
+		const std::uint8_t *row = src + static_cast<std::ptrdiff_t>(y) * srcStride;
+		unsigned px[17];  // px[0] = column x0 - 1 (clamped), px[1 + p] = column x0 + p
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			unsigned w[4];
+			// (byte path: whole pixels, the column clamped to W - 1)
+			if (full) {
+				loadBytes<16>(row, 4 * (x0 + 4 * q), 4 * W - 1, true, w);
+			} else {
+#pragma unroll
+				for (int b = 0; b < 4; ++b) {
+					const std::uint8_t *p = row + 4 * min(x0 + 4 * q + b, W - 1);
+					w[b] = p[0] | (p[1] << 8) | (p[2] << 16);
+				}
+			}
+#pragma unroll
+			for (int b = 0; b < 4; ++b) px[1 + 4 * q + b] = w[b];
+		}
+		{
+			const std::uint8_t *p = row + 4 * max(x0 - 1, 0);
+			px[0] = p[0] | (p[1] << 8) | (p[2] << 16);
+		}
+		unsigned yw[4] = {0, 0, 0, 0};
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			const int B = px[1 + p] & 255, G = (px[1 + p] >> 8) & 255, R = (px[1 + p] >> 16) & 255;
+			const int Y = clamp255(k.oy + ((k.yr * R + k.yg * G + k.yb * B + (1 << 15)) >> 16));
+			yw[p >> 2] |= static_cast<unsigned>(Y) << (8 * (p & 3));
+		}
+		storeBytes<16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, yw);
+#pragma unroll
+		for (int i = 0; i < 8; ++i) {
+			// columns 2i - 1, 2i, 2i + 1 of the strip = px[2i], px[2i + 1], px[2i + 2]
+			const unsigned a = px[2 * i], b = px[2 * i + 1], c = px[2 * i + 2];
+			sb[i] += (a & 255) + 2 * (b & 255) + (c & 255);
+			sg[i] += ((a >> 8) & 255) + 2 * ((b >> 8) & 255) + ((c >> 8) & 255);
+			sr[i] += ((a >> 16) & 255) + 2 * ((b >> 16) & 255) + ((c >> 16) & 255);
+		}
+	}
+	unsigned uw[2] = {0, 0}, vw[2] = {0, 0};
+#pragma unroll
+	for (int i = 0; i < 8; ++i) {
+		const int U = clamp255(128 + ((k.ur * sr[i] + k.ug * sg[i] + k.ub * sb[i] + (1 << 18)) >> 19));
+		const int V = clamp255(128 + ((k.vr * sr[i] + k.vg * sg[i] + k.vb * sb[i] + (1 << 18)) >> 19));
+		uw[i >> 2] |= static_cast<unsigned>(U) << (8 * (i & 3));
+		vw[i >> 2] |= static_cast<unsigned>(V) << (8 * (i & 3));
+	}
+	const int c0 = x0 / 2;
+	if constexpr (NV12) {
+		unsigned w[4];
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {  // U0 V0 U1 V1 from cells 2q, 2q + 1
+			const unsigned u = (uw[q >> 1] >> (16 * (q & 1))) & 0xffff, v = (vw[q >> 1] >> (16 * (q & 1))) & 0xffff;
+			w[q] = (u & 255) | ((v & 255) << 8) | ((u >> 8) << 16) | ((v >> 8) << 24);
+		}
+		storeBytes<16>(dst.u + static_cast<std::ptrdiff_t>(j) * dst.uStride, 2 * c0, n, full, w);
+	} else {
+		storeBytes<8>(dst.u + static_cast<std::ptrdiff_t>(j) * dst.uStride, c0, n / 2, full, uw);
+		storeBytes<8>(dst.v + static_cast<std::ptrdiff_t>(j) * dst.vStride, c0, n / 2, full, vw);
+	}
+}
+
+int roundHalfAway(double x) { return static_cast<int>(std::copysign(std::floor(std::fabs(x) * 65536.0 + 0.5), x)); }
+
+void colourSpace(int cs, double *kr, double *kb, bool *limited) {
+	if (cs < 0 || cs > 3) throw std::invalid_argument("unknown colour space");
+	const bool bt601 = cs == 0 || cs == 1;
+	*kr = bt601 ? 0.299 : 0.2126;
+	*kb = bt601 ? 0.114 : 0.0722;
+	*limited = cs == 0 || cs == 2;
+}
+
+}  // namespace
+
+YuvDecode yuvDecodeCoefficients(int colorspace) {
+	double kr, kb;
+	bool limited;
+	colourSpace(colorspace, &kr, &kb, &limited);
+	const double kg = 1.0 - kr - kb;
+	const double s = limited ? 255.0 / 224.0 : 1.0;
+	YuvDecode k;
+	k.ky = roundHalfAway(limited ? 255.0 / 219.0 : 1.0);
+	k.krv = roundHalfAway(2 * (1 - kr) * s);
+	k.kbu = roundHalfAway(2 * (1 - kb) * s);
+	k.kgu = roundHalfAway(2 * kb * (1 - kb) / kg * s);
+	k.kgv = roundHalfAway(2 * kr * (1 - kr) / kg * s);
+	k.oy = limited ? 16 : 0;
+	return k;
+}
+
+YuvEncode yuvEncodeCoefficients(int colorspace) {
+	double kr, kb;
+	bool limited;
+	colourSpace(colorspace, &kr, &kb, &limited);
+	const double kg = 1.0 - kr - kb;
+	const double sy = limited ? 219.0 / 255.0 : 1.0, sc = limited ? 224.0 / 255.0 : 1.0;
+	const double du = sc / (2 * (1 - kb)), dv = sc / (2 * (1 - kr));
+	YuvEncode k;
+	k.yr = roundHalfAway(sy * kr);
+	k.yg = roundHalfAway(sy * kg);
+	k.yb = roundHalfAway(sy * kb);
+	k.ur = roundHalfAway(-kr * du);
+	k.ug = roundHalfAway(-kg * du);
+	k.ub = roundHalfAway((1 - kb) * du);
+	k.vr = roundHalfAway((1 - kr) * dv);
+	k.vg = roundHalfAway(-kg * dv);
+	k.vb = roundHalfAway(-kb * dv);
+	k.oy = limited ? 16 : 0;
+	return k;
+}
+
+void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream) {
+	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
+	if (nv12) {
+		hipLaunchKernelGGL(yuv420_to_bgrx_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
+		    dstStride, width, height);
+	} else {
+		hipLaunchKernelGGL(yuv420_to_bgrx_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
+		    dstStride, width, height);
+	}
+	hipCheckLaunch("yuv420_to_bgrx");
+}
+
+void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
+	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
+	if (nv12) {
+		hipLaunchKernelGGL(bgrx_to_yuv420_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, srcStride,
+		    k, dst, width, height);
+	} else {
+		hipLaunchKernelGGL(bgrx_to_yuv420_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src,
+		    srcStride, k, dst, width, height);
+	}
+	hipCheckLaunch("bgrx_to_yuv420");
+}
+
+}  // namespace ju

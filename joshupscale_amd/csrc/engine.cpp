@@ -1014,6 +1014,9 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 	m_InStage = DeviceBuffer(lr * 4);
 	m_OutStage = DeviceBuffer(lr * 16 * 4);
 	m_RawStage = DeviceBuffer(lr * 16 * 4);
+	// host YUV frames (ju_process_frame): their planes, rows padded to 64 bytes
+	m_YuvInStage = DeviceBuffer(yuvStageBytes(W, H));
+	m_YuvOutStage = DeviceBuffer(yuvStageBytes(4 * W, 4 * H));
 	if (!c.recurrent()) {
 		// flow-free: no frame history, no flow tensors, no state ping-pong -- one scratch state for the tail's
 		// HR output, which nothing reads; gen_in's slots other than 12..14 stay zero for good (lr_pack)
@@ -1438,6 +1441,156 @@ void Engine::stageOut(const Frame &out) {
 	default:
 		throw std::invalid_argument(
 		    "processImage: GRAPHICS_RESOURCE images are not supported by this runtime");
+	}
+}
+
+namespace {
+// Plane k of a 4:2:0 frame of the given luma size: rows, bytes per row (I420: Y, U, V; NV12: Y, UV)
+struct PlaneShape {
+	std::size_t rows, rowBytes;
+};
+PlaneShape planeShape(PixelFormat f, std::size_t w, std::size_t h, int k) {
+	if (k == 0) return {h, w};
+	return {h / 2, f == PixelFormat::Nv12 ? w : w / 2};
+}
+int planeCount(PixelFormat f) { return f == PixelFormat::Nv12 ? 2 : 3; }
+std::size_t stagePitch(std::size_t rowBytes) { return (rowBytes + 63) / 64 * 64; }
+const char *formatName(PixelFormat f) { return f == PixelFormat::Nv12 ? "NV12" : "I420"; }
+}  // namespace
+
+// bytes of a staging buffer that holds any 4:2:0 frame of the size (I420's three planes take the most)
+std::size_t Engine::yuvStageBytes(std::size_t w, std::size_t h) {
+	std::size_t n = 0;
+	for (int k = 0; k < 3; ++k) {
+		const PlaneShape p = planeShape(PixelFormat::I420, w, h, k);
+		n += stagePitch(p.rowBytes) * p.rows;
+	}
+	return std::max(n, stagePitch(w) * h + stagePitch(w) * (h / 2));
+}
+
+// Everything a frame call can refuse, checked before anything is launched (the BGRX side repeats what stageIn /
+// stageOut would throw, so that a refused call has not run the step).
+void Engine::checkFrame(const AnyFrame &f, bool input) const {
+	const FrameSize fs = frameSize();
+	const std::size_t w = input ? fs.inputWidth : fs.outputWidth, h = input ? fs.inputHeight : fs.outputHeight;
+	const std::string side = input ? "input" : "output";
+	const std::string size = std::to_string(w) + "x" + std::to_string(h);
+	if (!f.yuv) {
+		const Frame &b = f.bgrx;
+		if (b.location == Location::GraphicsResource) {
+			if (b.ptr == nullptr) throw std::invalid_argument("processFrame: NULL graphics resource");
+			return;  // (the texture's own extent is checked when it is mapped)
+		}
+		if (b.ptr == nullptr || b.width != w || b.height != h) {
+			throw std::invalid_argument("processFrame: " + side + " image must be exactly " + size);
+		}
+		const auto row = static_cast<std::ptrdiff_t>(w * 4);
+		if (b.stride > -row && b.stride < row) throw std::invalid_argument("processFrame: |stride| smaller than a row");
+		return;
+	}
+	const YuvFrame &y = f.planes;
+	if (y.format != PixelFormat::I420 && y.format != PixelFormat::Nv12) {
+		throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
+	}
+	if (y.colorspace < 0 || y.colorspace > 3) {
+		throw std::invalid_argument("processFrame: unknown " + side + " colour space " + std::to_string(y.colorspace));
+	}
+	if (y.location != Location::Host && y.location != Location::Device) {
+		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) + " " + side +
+		                            " frames must be host or device memory (no graphics resources)");
+	}
+	if (y.width % 2 || y.height % 2) {
+		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) +
+		                            " needs an even width and height");
+	}
+	if (y.width != w || y.height != h) {
+		throw std::invalid_argument("processFrame: " + side + " frame must be exactly " + size);
+	}
+	for (int k = 0; k < planeCount(y.format); ++k) {
+		if (y.planes[k] == nullptr) {
+			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) + " is NULL");
+		}
+		const auto row = static_cast<std::ptrdiff_t>(planeShape(y.format, w, h, k).rowBytes);
+		if (y.strides[k] > -row && y.strides[k] < row) {
+			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) +
+			                            ": |stride| smaller than a row");
+		}
+	}
+}
+
+void Engine::stageInYuv(const YuvFrame &in) {
+	const FrameSize fs = frameSize();
+	const std::size_t w = fs.inputWidth, h = fs.inputHeight;
+	std::uint8_t *plane[3] = {};
+	std::ptrdiff_t stride[3] = {};
+	if (in.location == Location::Device) {
+		for (int k = 0; k < 3; ++k) {
+			plane[k] = static_cast<std::uint8_t *>(in.planes[k]);
+			stride[k] = in.strides[k];
+		}
+	} else {
+		// upload the rows in memory order; a bottom-up plane stays bottom-up in the staging buffer and the kernel
+		// reads it with a negative pitch
+		auto *stage = m_YuvInStage.as<std::uint8_t>();
+		for (int k = 0; k < planeCount(in.format); ++k) {
+			const PlaneShape p = planeShape(in.format, w, h, k);
+			const auto pitch = static_cast<std::ptrdiff_t>(stagePitch(p.rowBytes));
+			const auto *src = static_cast<const std::uint8_t *>(in.planes[k]);
+			const std::ptrdiff_t s = in.strides[k];
+			const std::uint8_t *lowest = s > 0 ? src : src + static_cast<std::ptrdiff_t>(p.rows - 1) * s;
+			JU_HIP(hipMemcpy2DAsync(stage, pitch, lowest, static_cast<std::size_t>(s > 0 ? s : -s), p.rowBytes, p.rows,
+			    hipMemcpyHostToDevice, m_Stream));
+			plane[k] = s > 0 ? stage : stage + static_cast<std::ptrdiff_t>(p.rows - 1) * pitch;
+			stride[k] = s > 0 ? pitch : -pitch;
+			stage += pitch * static_cast<std::ptrdiff_t>(p.rows);
+		}
+	}
+	YuvPlanes pl;
+	pl.y = plane[0], pl.u = plane[1], pl.v = plane[2];
+	pl.yStride = stride[0], pl.uStride = stride[1], pl.vStride = stride[2];
+	launchYuv420ToBgrx(in.format == PixelFormat::Nv12, pl, yuvDecodeCoefficients(in.colorspace),
+	    m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4), static_cast<int>(w), static_cast<int>(h),
+	    m_Stream);
+}
+
+void Engine::stageOutYuv(const YuvFrame &out) {
+	const FrameSize fs = frameSize();
+	const std::size_t w = fs.outputWidth, h = fs.outputHeight;
+	const bool host = out.location == Location::Host;
+	std::uint8_t *plane[3] = {};
+	std::ptrdiff_t stride[3] = {};
+	auto *stage = m_YuvOutStage.as<std::uint8_t>();
+	for (int k = 0; k < planeCount(out.format); ++k) {
+		if (!host) {
+			plane[k] = static_cast<std::uint8_t *>(out.planes[k]);
+			stride[k] = out.strides[k];
+			continue;
+		}
+		// the kernel writes the staging buffer in the caller's row order (memory order), copied out below
+		const PlaneShape p = planeShape(out.format, w, h, k);
+		const auto pitch = static_cast<std::ptrdiff_t>(stagePitch(p.rowBytes));
+		const bool up = out.strides[k] > 0;
+		plane[k] = up ? stage : stage + static_cast<std::ptrdiff_t>(p.rows - 1) * pitch;
+		stride[k] = up ? pitch : -pitch;
+		stage += pitch * static_cast<std::ptrdiff_t>(p.rows);
+	}
+	YuvPlanes pl;
+	pl.y = plane[0], pl.u = plane[1], pl.v = plane[2];
+	pl.yStride = stride[0], pl.uStride = stride[1], pl.vStride = stride[2];
+	launchBgrxToYuv420(out.format == PixelFormat::Nv12, m_OutStage.as<std::uint8_t>(),
+	    static_cast<std::ptrdiff_t>(w * 4), yuvEncodeCoefficients(out.colorspace), pl, static_cast<int>(w),
+	    static_cast<int>(h), m_Stream);
+	if (!host) return;
+	stage = m_YuvOutStage.as<std::uint8_t>();
+	for (int k = 0; k < planeCount(out.format); ++k) {
+		const PlaneShape p = planeShape(out.format, w, h, k);
+		const auto pitch = stagePitch(p.rowBytes);
+		auto *dst = static_cast<std::uint8_t *>(out.planes[k]);
+		const std::ptrdiff_t s = out.strides[k];
+		std::uint8_t *lowest = s > 0 ? dst : dst + static_cast<std::ptrdiff_t>(p.rows - 1) * s;
+		JU_HIP(hipMemcpy2DAsync(lowest, static_cast<std::size_t>(s > 0 ? s : -s), stage, pitch, p.rowBytes, p.rows,
+		    hipMemcpyDeviceToHost, m_Stream));
+		stage += pitch * p.rows;
 	}
 }
 
@@ -1974,8 +2127,15 @@ void Engine::runProgram() {
 	++m_EagerRuns;
 }
 
-void Engine::submit(const Frame &in, const Frame &out) {
+void Engine::bindStaging() {
 	const FrameSize fs = frameSize();
+	m_IO.in = m_InStage.as<std::uint8_t>();
+	m_IO.inStride = static_cast<std::ptrdiff_t>(fs.inputWidth) * 4;
+	m_IO.out = m_OutStage.as<std::uint8_t>();
+	m_IO.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth) * 4;
+}
+
+void Engine::submit(const Frame &in, const Frame &out) {
 	// Device-resident frames: the kernels read the caller's input and write the caller's
 	// output directly (any signed stride), no staging copies.
 	m_DirectIO = directEligible(in, out);
@@ -1990,10 +2150,7 @@ void Engine::submit(const Frame &in, const Frame &out) {
 		m_IO.out = static_cast<std::uint8_t *>(out.ptr);
 		m_IO.outStride = out.stride;
 	} else {
-		m_IO.in = m_InStage.as<std::uint8_t>();
-		m_IO.inStride = static_cast<std::ptrdiff_t>(fs.inputWidth) * 4;
-		m_IO.out = m_OutStage.as<std::uint8_t>();
-		m_IO.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth) * 4;
+		bindStaging();
 		stageIn(in);
 	}
 	{
@@ -2010,9 +2167,9 @@ void Engine::enqueue(const Frame &in, const Frame &out) {
 	submit(in, out);
 }
 
-void Engine::process(const Frame &in, const Frame &out) {
-	DeviceGuard g(m_Device);
-	submit(in, out);
+template <typename Submit>
+void Engine::runSynchronous(const Submit &submitOne) {
+	submitOne();
 	m_Stream.synchronizeSpin(m_SpinUs);
 	if (const unsigned code = takeResidentError()) {
 		// the frame's inputs (previous state, frame history) are intact: the step only
@@ -2021,11 +2178,54 @@ void Engine::process(const Frame &in, const Frame &out) {
 		// fallback or the re-run throws, the failed frame must not count as a step either.)
 		m_Idx ^= 1;
 		fallbackToLayers(code);
-		submit(in, out);
+		submitOne();
 		m_Stream.synchronize();
 	} else {
 		maybeRestoreResident();
 	}
+}
+
+void Engine::process(const Frame &in, const Frame &out) {
+	DeviceGuard g(m_Device);
+	runSynchronous([&] { submit(in, out); });
+}
+
+// YUV frames (ju_process_frame): always through the staging buffers -- the conversion kernel takes the place of the
+// staging copy on its side and the binding set's staged graph replays unchanged.  The conversions are eager launches
+// on m_Stream OUTSIDE the per-device chain lock, like the staging copies of submit().
+void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
+	m_DirectIO = false;
+	bindStaging();
+	if (in.yuv) {
+		stageInYuv(in.planes);
+	} else {
+		stageIn(in.bgrx);
+	}
+	{
+		std::unique_lock<std::mutex> chain = chainBegin();
+		runProgram();
+		chainEnd(chain);
+	}
+	if (out.yuv) {
+		stageOutYuv(out.planes);
+	} else {
+		stageOut(out.bgrx);
+	}
+	m_Idx ^= 1;
+}
+
+void Engine::processFrame(const AnyFrame &in, const AnyFrame &out) {
+	DeviceGuard g(m_Device);
+	checkFrame(in, true);
+	checkFrame(out, false);
+	runSynchronous([&] { submitFrame(in, out); });
+}
+
+void Engine::enqueueFrame(const AnyFrame &in, const AnyFrame &out) {
+	DeviceGuard g(m_Device);
+	checkFrame(in, true);
+	checkFrame(out, false);
+	submitFrame(in, out);
 }
 
 void Engine::synchronize() {

@@ -40,6 +40,27 @@ struct Frame {
 	std::size_t height;
 };
 
+// An 8-bit 4:2:0 frame of ju_process_frame (include/joshupscale_amd.h, ju_frame): planes Y, U, V (I420 / YV12) or
+// Y, interleaved UV (NV12), each addressing its first logical row, strides in bytes of any sign.  Host or device.
+enum class PixelFormat : int { Bgrx = 0, I420 = 1, Nv12 = 2 };
+
+struct YuvFrame {
+	PixelFormat format;
+	int colorspace;  // 0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full
+	Location location;
+	std::size_t width;
+	std::size_t height;
+	void *planes[3];
+	std::ptrdiff_t strides[3];
+};
+
+// One side of a frame call: a BGRX frame (exactly as ju_process takes it) or a YUV one.
+struct AnyFrame {
+	bool yuv = false;
+	Frame bgrx{};
+	YuvFrame planes{};
+};
+
 struct FrameSize {
 	std::size_t inputWidth, inputHeight, outputWidth, outputHeight;
 };
@@ -69,6 +90,11 @@ public:
 	// Asynchronous variant for device-resident frames: enqueue only.
 	void enqueue(const Frame &in, const Frame &out);
 	void synchronize();
+	// Frames of which at least one side is YUV (ju_process_frame / ju_enqueue_frame): the same step as process() /
+	// enqueue(), its colour conversion taking the place of the staging copy on that side (colour_kernels.hip).  Both
+	// frames are checked before anything is launched.  BGRX-only pairs go through process() / enqueue() instead.
+	void processFrame(const AnyFrame &in, const AnyFrame &out);
+	void enqueueFrame(const AnyFrame &in, const AnyFrame &out);
 	// Registers a pair of device-resident frame buffers the caller is going to hand to
 	// process() / enqueue(): the per-frame graphs of the pair (one per binding set) are
 	// captured NOW, so that no later call pays a capture -- the reference captures its graphs
@@ -156,6 +182,18 @@ private:
 	void buildProgram(int set);
 	void stageIn(const Frame &in);
 	void stageOut(const Frame &out);
+	// YUV frames: decode into m_InStage / encode from m_OutStage; host planes go through m_YuvInStage / m_YuvOutStage
+	void checkFrame(const AnyFrame &f, bool input) const;
+	void stageInYuv(const YuvFrame &in);
+	void stageOutYuv(const YuvFrame &out);
+	void submitFrame(const AnyFrame &in, const AnyFrame &out);
+	void bindStaging();
+	// submit (a callable that enqueues one frame), wait, and on a resident-tower failure run the frame again on the
+	// per-layer path (process, processFrame)
+	template <typename Submit>
+	void runSynchronous(const Submit &submit);
+	DeviceBuffer m_YuvInStage, m_YuvOutStage;
+	static std::size_t yuvStageBytes(std::size_t width, std::size_t height);
 	void runProgram();
 	// Frame buffers the kernels read / write in THIS call.  Graph replay always uses
 	// the internal staging buffers (static pointers); eager launches of device-resident

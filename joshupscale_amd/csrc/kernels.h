@@ -411,6 +411,29 @@ void launchTailFused(DType dt, const TailFusedLaunch &p, hipStream_t stream);
 void launchCopyRows(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint8_t *dst,
     std::ptrdiff_t dstStride, std::size_t rowBytes, std::size_t rows, hipStream_t stream);
 
+// ---- 8-bit 4:2:0 YUV <-> BGRX (colour_kernels.hip; ju_process_frame's colour staging) ----------------------------
+// Planes of a 4:2:0 frame: luma [H][W]; I420 chroma u, v [H/2][W/2]; NV12 one interleaved plane u [H/2][W] (v unused).
+// Pointers address the first logical row, strides are bytes and may be negative; any byte alignment.
+struct YuvPlanes {
+	std::uint8_t *y = nullptr, *u = nullptr, *v = nullptr;
+	std::ptrdiff_t yStride = 0, uStride = 0, vStride = 0;
+};
+// x 65536, rounded half away from zero (tests/yuv_reference.py); oy = luma offset (16 limited, 0 full range)
+struct YuvDecode {
+	int ky, krv, kbu, kgu, kgv, oy;
+};
+struct YuvEncode {
+	int yr, yg, yb, ur, ug, ub, vr, vg, vb, oy;
+};
+// colorspace: 0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full (std::invalid_argument otherwise)
+YuvDecode yuvDecodeCoefficients(int colorspace);
+YuvEncode yuvEncodeCoefficients(int colorspace);
+// width, height even.  dst: BGRX rows (X = 0) / src: BGRX rows (X ignored).
+void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
+void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream);
+
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).
 void launchSignalHost(unsigned *word, hipStream_t stream);

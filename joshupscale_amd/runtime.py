@@ -44,6 +44,18 @@ class JuImage(C.Structure):
                 ("height", C.c_size_t)]
 
 
+# 8-bit 4:2:0 frames of ju_process_frame (include/joshupscale_amd.h; formulas: INTEGRATION.md, "YUV frames")
+FMT_BGRX, FMT_I420, FMT_NV12 = 0, 1, 2
+CS_BT601_LIMITED, CS_BT601_FULL, CS_BT709_LIMITED, CS_BT709_FULL = 0, 1, 2, 3
+
+
+class JuFrame(C.Structure):
+    """``ju_frame``: a BGRX, I420 (YV12) or NV12 frame, host or device."""
+    _fields_ = [("format", C.c_int), ("colorspace", C.c_int), ("location", C.c_uint8),
+                ("width", C.c_size_t), ("height", C.c_size_t),
+                ("planes", C.c_void_p * 3), ("strides", C.c_ssize_t * 3)]
+
+
 LOG_CALLBACK = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p)
 
 
@@ -84,6 +96,8 @@ _PRODUCT_SIGS = {
     "ju_enqueue": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
     "ju_synchronize": (C.c_int, [C.c_void_p]),
     "ju_prepare_frames": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage), _P(C.c_int)]),
+    "ju_process_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
+    "ju_enqueue_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
     "ju_get_size": (C.c_int, [C.c_void_p] + [_P(C.c_size_t)] * 4),
     "ju_reset": (C.c_int, [C.c_void_p]),
     "ju_last_error": (C.c_char_p, []),
@@ -106,6 +120,8 @@ _HOOK_SIGS = {
     "ju_debug_fake_gl_texture": (C.c_int, [C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_debug_fake_gl_counters": (None, [_P(C.c_int)] * 4),
     "ju_debug_e4m3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ju_debug_yuv": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
+                               _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
@@ -275,6 +291,33 @@ class Runtime:
         self.process(host_image(frame_bgrx), host_image(out))
         return out
 
+    def process_frame(self, inp: JuFrame, out: JuFrame) -> None:
+        """``ju_process_frame``: one step on frames of any format (synchronous)."""
+        _check(self._lib, self._lib.ju_process_frame(self._h, C.byref(inp), C.byref(out)))
+
+    def enqueue_frame(self, inp: JuFrame, out: JuFrame) -> None:
+        """``ju_enqueue_frame``: device frames only; ``synchronize`` waits."""
+        _check(self._lib, self._lib.ju_enqueue_frame(self._h, C.byref(inp), C.byref(out)))
+
+    def process_yuv(self, y: np.ndarray, u: np.ndarray, v: Optional[np.ndarray] = None, fmt: int = FMT_I420,
+                    colorspace: int = CS_BT709_LIMITED, out_format: Optional[int] = None):
+        """Host planes in, host planes out.  ``fmt`` FMT_I420: ``y, u, v``; FMT_NV12: ``y, uv`` (``v`` None).
+        ``out_format`` (default: ``fmt``): FMT_I420 -> ``(y, u, v)``, FMT_NV12 -> ``(y, uv)``, FMT_BGRX -> the
+        ``[4H, 4W, 4]`` BGRX frame."""
+        out_format = fmt if out_format is None else out_format
+        planes = [y, u] if fmt == FMT_NV12 else [y, u, v]
+        inp = host_frame(fmt, planes, colorspace)
+        ow, oh = self.output_width, self.output_height
+        if out_format == FMT_BGRX:
+            res = [np.empty((oh, ow, 4), np.uint8)]
+        elif out_format == FMT_NV12:
+            res = [np.empty((oh, ow), np.uint8), np.empty((oh // 2, ow), np.uint8)]
+        else:
+            res = [np.empty((oh, ow), np.uint8), np.empty((oh // 2, ow // 2), np.uint8),
+                   np.empty((oh // 2, ow // 2), np.uint8)]
+        self.process_frame(inp, host_frame(out_format, res, colorspace))
+        return res[0] if out_format == FMT_BGRX else tuple(res)
+
     def device_image(self, ptr: int, width: int, height: int,
                      stride: Optional[int] = None) -> JuImage:
         return JuImage(ptr, LOC_DEVICE, width * 4 if stride is None else stride,
@@ -377,6 +420,37 @@ def release_gl_image(img: JuImage) -> None:
 def host_image(arr: np.ndarray) -> JuImage:
     """Describe a ``[H, W, 4]`` uint8 numpy array (any row stride) as an image."""
     return JuImage(arr.ctypes.data, LOC_CPU, arr.strides[0], arr.shape[1], arr.shape[0])
+
+
+def _frame(fmt: int, colorspace: int, location: int, width: int, height: int, ptrs, strides) -> JuFrame:
+    f = JuFrame()
+    f.format, f.colorspace, f.location, f.width, f.height = fmt, colorspace, location, width, height
+    for k, (p, s) in enumerate(zip(ptrs, strides)):
+        f.planes[k], f.strides[k] = p, s
+    return f
+
+
+def host_frame(fmt: int, planes, colorspace: int = CS_BT709_LIMITED) -> JuFrame:
+    """Describe numpy planes as a host frame.  FMT_BGRX: ``[bgrx [H, W, 4]]``; FMT_I420: ``[y [H, W], u, v
+    [H/2, W/2]]``; FMT_NV12: ``[y [H, W], uv [H/2, W]]``.  Any row stride (a ``[::-1]`` view is bottom-up); the
+    columns must be contiguous.  The arrays must outlive the call."""
+    for p in planes:
+        if p.dtype != np.uint8 or p.strides[1] != (4 if fmt == FMT_BGRX else 1):
+            raise ValueError("planes must be uint8 with contiguous columns")
+    y = planes[0]
+    return _frame(fmt, colorspace, LOC_CPU, y.shape[1], y.shape[0], [p.ctypes.data for p in planes],
+                  [p.strides[0] for p in planes])
+
+
+def device_frame(fmt: int, width: int, height: int, ptrs, strides=None,
+                 colorspace: int = CS_BT709_LIMITED) -> JuFrame:
+    """A device frame from raw device pointers (or torch tensors: their ``data_ptr()``); ``strides`` default to
+    dense rows (BGRX 4W, Y W, I420 chroma W/2, NV12 chroma W)."""
+    ptrs = [p.data_ptr() if hasattr(p, "data_ptr") else int(p) for p in ptrs]
+    if strides is None:
+        strides = {FMT_BGRX: [4 * width], FMT_I420: [width, width // 2, width // 2],
+                   FMT_NV12: [width, width]}[fmt]
+    return _frame(fmt, colorspace, LOC_DEVICE, width, height, ptrs, strides)
 
 
 class Session:
