@@ -156,6 +156,29 @@ JU_API int ju_set_lookahead(ju_runtime *runtime, int frames);
  * by this call; 0 for a tuple that will not run as one pass. */
 JU_API int ju_prepare_batch(ju_runtime *runtime, const ju_image *inputs, const ju_image *outputs, int count, int *captured);
 
+/* Several streams on one GPU (no reference counterpart): one frame for each of `count` runtimes, synchronously -- the
+ * same bytes, in every output and in every runtime's recurrent state and frame history, as
+ * ju_process(runtimes[i], &inputs[i], &outputs[i]) for i = 0 .. count-1.  For a server of live streams (several OBS
+ * sources, one runtime per incoming video): it cannot read ahead in one stream, but it holds one frame of every stream at
+ * each tick, and their flow nets are as independent as a look-ahead pass's.  So runtimes[0], the lead, runs the flow
+ * net's launches ONCE over up to its ju_set_lookahead cap (default 8) of the frames, each with its own runtime's frame
+ * history, and then every runtime's warp, tower and tail in turn -- all on the lead's stream, under one synchronisation.
+ * Longer calls split into consecutive passes.
+ * Members: distinct runtimes on one device, created from byte-identical model data with the same dtype (ju_get_dtype).
+ * JU_ERR_INVALID_ARGUMENT, checked before anything is launched (a refused call changes no runtime's state): a NULL
+ * pointer, count < 0, a runtime twice, runtimes that do not match, an image of the wrong size or |stride| or an
+ * unknown location.  count == 0 does nothing; count == 1 is ju_process.
+ * Member by member, as ju_process calls in list order (same bytes, no pass): models without the look-ahead's one-launch
+ * flow plan (flow res-net, normalize_brightness) or a lead whose look-ahead is unavailable, and any call in which an
+ * output overlaps an input of the call (host and device addresses apart).  Images a pass cannot take (GL resources,
+ * JU_LOC_DEVICE images off 4-byte (input) / 8-byte (output) alignment) run on their own after the pass.  Host images
+ * ride in the pass as in ju_process_batch.  Flow-free models: the pass is the members' generator programs.
+ * Work a member has enqueued (ju_enqueue) runs before its frame; the runtimes may be driven by other calls between
+ * group calls (ju_process, ju_process_batch, ju_reset), each by one thread at a time.  Memory: the lead holds the pass's
+ * flow tensors -- those of ju_process_batch, about 210 MB at 480x270 for 8 frames, shared with its look-ahead
+ * passes; the other members allocate nothing.  ju_get_stat "group_frames": frames a runtime got from group passes. */
+JU_API int ju_process_group(ju_runtime *const *runtimes, const ju_image *inputs, const ju_image *outputs, int count);
+
 /* Asynchronous form for JU_LOC_DEVICE images: enqueues the same work on the
  * runtime's stream and returns; ju_synchronize() waits.  Frames are still
  * strictly ordered (the recurrence is carried by stream order). */
@@ -251,6 +274,7 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * "prepared_captures"), "registered_pairs", "direct_graphs"
  * (graphs cached for JU_LOC_DEVICE frame tuples), "resident_tower" / "resident_flow"
  * (1 when the one-launch tower kernel is in use), "launches_per_frame", "tower_variant",
+ * "group_frames" (frames this runtime got from ju_process_group passes),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,
  * flow_arch "none" of the container -- every frame is upscaled on its own, ju_reset does nothing). */
 JU_API int ju_get_stat(const ju_runtime *runtime, const char *key, double *value);

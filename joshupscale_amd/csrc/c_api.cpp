@@ -180,6 +180,22 @@ int ju_process_batch(ju_runtime *runtime, const ju_image *inputs, const ju_image
 	});
 }
 
+int ju_process_group(ju_runtime *const *runtimes, const ju_image *inputs, const ju_image *outputs, int count) {
+	return guarded([&] {
+		if (count < 0 || (count > 0 && (runtimes == nullptr || inputs == nullptr || outputs == nullptr))) {
+			throw std::invalid_argument("ju_process_group: NULL arguments or a negative count");
+		}
+		std::vector<ju::Engine *> engines(static_cast<std::size_t>(count));
+		std::vector<ju::Frame> in(static_cast<std::size_t>(count)), out(static_cast<std::size_t>(count));
+		for (int i = 0; i < count; ++i) {
+			engines[i] = &engineOf(runtimes[i]);
+			in[i] = toFrame(inputs + i);
+			out[i] = toFrame(outputs + i);
+		}
+		ju::Engine::processGroup(engines.data(), in.data(), out.data(), count);
+	});
+}
+
 int ju_prepare_batch(ju_runtime *runtime, const ju_image *inputs, const ju_image *outputs, int count, int *captured) {
 	if (captured) *captured = 0;
 	return guarded([&] {

@@ -320,16 +320,18 @@ void Engine::addConvStep(std::vector<Step> *prog, const std::string &tag,
 // > 1 for a look-ahead pass -- the same launches over `items` consecutive frames (grid.z), on the batch tensors, the
 // first block reading the frames of m_BatchIO (submitBatch).  A look-ahead pass exists only where every launch of
 // the plan has an item dimension (the one-launch blocks and the split-K convolutions): std::logic_error otherwise.
-void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items) {
+void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, bool group) {
 	std::vector<Step> &prog = *progOut;
 	const ModelConfig &c = m_Config;
 	const DType dt = m_DType;
-	const bool batch = items > 1;
+	const bool batch = items > 1 || group;
 	const int H = c.frameHeight, W = c.frameWidth;
 	const int PH = c.paddedHeight(), PW = c.paddedWidth();
 	const int padTop = (PH - H) / 2, padLeft = (PW - W) / 2;  // models.py:783-787
 	const FrameIO *io = &m_IO;
 	const FrameIO *batchIO = m_BatchIO;
+	const void *const *groupPrev = m_GroupPrev;
+	void *const *groupOut = m_GroupOut;
 	const void *packedIn = m_Packed[set].get();
 	void *packedOut = m_Packed[set ^ 1].get();
 	const int nIn = c.numFlowInputs;
@@ -397,13 +399,22 @@ void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items) 
 			fb.padLeft = padLeft;
 			fb.numInputs = nIn;
 			fb.sums = sums;
-			prog.push_back({"flow", flops, [dt, fb, io, batchIO, items](hipStream_t s) {
+			if (group) {  // every item the next frame of its own stream: its history from / to that stream's buffers
+				fb.packPrev = nullptr;
+				fb.packOut = nullptr;
+				fb.independentItems = true;
+			}
+			prog.push_back({"flow", flops, [dt, fb, io, batchIO, groupPrev, groupOut, items, group](hipStream_t s) {
 				                FlowBlockLaunch f = fb;  // the caller's frames are known at launch time only
 				                f.packFrame = io->in;
 				                f.packFrameStride = io->inStride;
-				                for (int i = 0; i < items && items > 1; ++i) {
+				                for (int i = 0; i < items && (items > 1 || group); ++i) {
 					                f.packFrames[i] = batchIO[i].in;
 					                f.packFrameStrides[i] = batchIO[i].inStride;
+					                if (group) {
+						                f.packPrevs[i] = groupPrev[i];
+						                f.packOuts[i] = groupOut[i];
+					                }
 				                }
 				                launchFlowBlock(dt, f, s);
 			                }});
@@ -925,6 +936,12 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 	m_Config = model.config();
 	const ModelConfig &c = m_Config;
 	int dt = dtypeOverride >= 0 ? dtypeOverride : c.computeDtype;
+	// (the identity a group pass checks its members against: processGroup)
+	m_ModelDigest = 14695981039346656037ull;  // FNV-1a, 64 bit
+	for (std::size_t i = 0; i < size; ++i) {
+		m_ModelDigest = (m_ModelDigest ^ static_cast<const unsigned char *>(blob)[i]) * 1099511628211ull;
+	}
+	m_DtypeOverride = dt;
 	if (dt == 2) {
 		// JU_DTYPE_FP8: the 64->64 block convolutions run on e4m3 operands (fp8.h); the
 		// residual stream and every other layer stay fp16
@@ -1723,19 +1740,20 @@ int Engine::prepareFrames(const Frame &in, const Frame &out) {
 // ONE process() call would: the pass flips the binding set once, and -- since nothing it wrote is read before the
 // pass -- a pass that failed (resident tower: bounded wait expired) can be run again frame by frame.
 // ---------------------------------------------------------------------------------------------------------------
-bool Engine::batchPlanned(int items) {
+bool Engine::batchPlanned(int items, bool group) {
 	if (!m_Config.recurrent()) {
 		// a flow-free model: a pass is its frames' generator programs under one synchronisation -- no flow launches,
 		// no pass tensors, and every frame's tail writes the one scratch state
 		if (m_BatchUnsupported || m_Calibrate) return false;
 		for (int set = 0; set < 2; ++set) m_BatchFlow[{items, set}];
+		m_BatchFlow[{items, kGroupSet}];
 		m_BatchCap = std::max({m_BatchCap, items, m_BatchMax});
 		return true;
 	}
 	if (m_BatchUnsupported || m_Calibrate || m_Config.flowArch != 0 || !flowPacksInBlock() || m_Config.normalizeBrightness) {
 		return false;
 	}
-	if (items <= m_BatchCap && m_BatchFlow.count({items, 0})) return true;
+	if (items <= m_BatchCap && m_BatchFlow.count({items, group ? kGroupSet : 0})) return true;
 	try {
 		if (items > m_BatchCap) {
 			// (the tensors of every pass so far are too small: start over)
@@ -1756,10 +1774,16 @@ bool Engine::batchPlanned(int items) {
 				t.buf = DeviceBuffer(t.count * (t.isF32 ? 4 : 2));
 				m_BatchTensors.emplace(kv.first, std::move(t));
 			}
-			for (int i = 0; i + 1 < cap; ++i) {
-				if (!m_BatchState[i].get()) m_BatchState[i] = DeviceBuffer(m_State[0].bytes());
-			}
 			m_BatchCap = cap;
+		}
+		if (group) {  // (a group pass chains no states: each member reads and writes its own)
+			std::vector<Step> prog;
+			addFlowAutoencoder(&prog, 0, items, true);
+			m_BatchFlow[{items, kGroupSet}] = std::move(prog);
+			return true;
+		}
+		for (int i = 0; i + 1 < m_BatchCap; ++i) {
+			if (!m_BatchState[i].get()) m_BatchState[i] = DeviceBuffer(m_State[0].bytes());
 		}
 		for (int set = 0; set < 2; ++set) {
 			std::vector<Step> prog;
@@ -2093,6 +2117,197 @@ void Engine::processBatch(const Frame *in, const Frame *out, int count) {
 			for (int k = 0; k < n; ++k) maybeRestoreResident();
 		}
 		i += n;
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Group passes (processGroup).  A server of N live streams has N frames at every tick, one per stream, and their flow
+// nets are as independent as a look-ahead pass's: the flow net reads LR frames and each stream's own history only.  So
+// the lead (members[0]) runs the flow net's launches ONCE over the n frames of a pass, on its batch tensors -- item i is
+// member i's frame with member i's history (flow_block_kernel's independent-items form: m_GroupPrev / m_GroupOut) --
+// and then, member by member on the lead's stream, each member's own non-flow steps, bound to its frame, flow item i
+// and its state m_State[set_i] -> m_State[set_i ^ 1].  Per member that is the arithmetic of process(): the same kernels
+// add the same terms in the same order whatever the launch's size.  Like a look-ahead pass, the pass writes nothing it
+// reads (every member's state and history go to the other half of its ping-pong, the overlap test below keeps outputs
+// off inputs), so a pass whose resident tower timed out runs again member by member.  The launches are eager: round 6
+// measured eager launches per frame equal to graph replay.
+// ---------------------------------------------------------------------------------------------------------------
+bool Engine::sameModel(const Engine &o) const {
+	return m_Device == o.m_Device && m_ModelDigest == o.m_ModelDigest && m_DtypeOverride == o.m_DtypeOverride;
+}
+
+// What process() would refuse for its size, checked up front (a group call launches nothing before every frame passed)
+void Engine::checkGroupFrame(const Frame &f, bool input) const {
+	const FrameSize fs = frameSize();
+	const std::size_t w = input ? fs.inputWidth : fs.outputWidth, h = input ? fs.inputHeight : fs.outputHeight;
+	const char *side = input ? "input" : "output";
+	if (f.ptr == nullptr) throw std::invalid_argument(std::string("ju_process_group: NULL ") + side + " image");
+	if (f.width != w || f.height != h) {
+		throw std::invalid_argument(std::string("ju_process_group: ") + side + " image must be exactly " + std::to_string(w) +
+		                            "x" + std::to_string(h));
+	}
+	const auto row = static_cast<std::ptrdiff_t>(w * 4);
+	if (f.location != Location::GraphicsResource && f.stride > -row && f.stride < row) {
+		throw std::invalid_argument(std::string("ju_process_group: |stride| of an ") + side + " image smaller than a row");
+	}
+}
+
+void Engine::processGroup(Engine *const *members, const Frame *in, const Frame *out, int count) {
+	if (count < 0 || (count > 0 && (members == nullptr || in == nullptr || out == nullptr))) {
+		throw std::invalid_argument("ju_process_group: NULL arguments or a negative count");
+	}
+	if (count == 0) return;
+	std::set<const Engine *> seen;
+	for (int i = 0; i < count; ++i) {
+		if (members[i] == nullptr) throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " is NULL");
+		if (!seen.insert(members[i]).second) {
+			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " appears twice");
+		}
+		if (!members[i]->sameModel(*members[0])) {
+			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) +
+			                            " does not match runtime 0 (device, model bytes or dtype)");
+		}
+		members[i]->checkGroupFrame(in[i], true);
+		members[i]->checkGroupFrame(out[i], false);
+	}
+	Engine &lead = *members[0];
+	DeviceGuard g(lead.m_Device);
+	auto alone = [&](int i) { members[i]->process(in[i], out[i]); };
+	if (count == 1) return alone(0);
+	// An output over an input of the call (same address space; any two members, also one member's own pair): member by
+	// member in list order, as ju_process calls would run -- a pass reads every input before any tail writes
+	auto range = [](const Frame &f) {
+		const auto rows = static_cast<std::ptrdiff_t>(f.height);
+		const auto *p0 = static_cast<const std::uint8_t *>(f.ptr);
+		const std::uint8_t *lo = f.stride >= 0 ? p0 : p0 + (rows - 1) * f.stride;
+		const std::size_t bytes = static_cast<std::size_t>(rows - 1) * static_cast<std::size_t>(f.stride >= 0 ? f.stride : -f.stride) + f.width * 4;
+		return std::make_pair(lo, lo + bytes);
+	};
+	bool clash = false;
+	for (int i = 0; i < count && !clash; ++i) {
+		if (out[i].location == Location::GraphicsResource) continue;
+		const auto w = range(out[i]);
+		for (int j = 0; j < count && !clash; ++j) {
+			if (in[j].location != out[i].location) continue;  // (host and device addresses are different spaces)
+			const auto r = range(in[j]);
+			clash = w.first < r.second && r.first < w.second;
+		}
+	}
+	std::vector<int> pass, rest;
+	for (int i = 0; i < count; ++i) (members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
+	const int cap = lead.m_BatchMax;
+	if (clash || pass.size() < 2 || cap < 2) {
+		for (int i = 0; i < count; ++i) alone(i);
+		return;
+	}
+	// consecutive passes of at most the lead's look-ahead cap; a pass of one member is a plain process()
+	for (std::size_t k = 0; k < pass.size(); k += static_cast<std::size_t>(cap)) {
+		const int n = static_cast<int>(std::min(pass.size() - k, static_cast<std::size_t>(cap)));
+		if (n < 2 || !lead.batchPlanned(n, true)) {
+			for (int j = 0; j < n; ++j) alone(pass[k + j]);
+			continue;
+		}
+		Engine *m[kFlowBatchMax];
+		Frame fi[kFlowBatchMax], fo[kFlowBatchMax];
+		for (int j = 0; j < n; ++j) {
+			m[j] = members[pass[k + j]];
+			fi[j] = in[pass[k + j]];
+			fo[j] = out[pass[k + j]];
+		}
+		runGroupPass(lead, m, fi, fo, n);
+	}
+	// frames a pass cannot take (graphics resources, device frames off the kernels' alignment): on their own.  No
+	// buffer of the call overlaps another here, so the order changes no byte.
+	for (int i : rest) alone(i);
+}
+
+void Engine::runGroupPass(Engine &L, Engine *const *m, const Frame *in, const Frame *out, int n) {
+	int sets[kFlowBatchMax];
+	for (int i = 0; i < n; ++i) sets[i] = m[i]->m_Idx;
+	L.bindBatch(in, out, n, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
+	L.uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
+	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
+	// 1. work a member has pending on its own stream (ju_enqueue) runs first
+	for (int i = 0; i < n; ++i) {
+		if (m[i] == &L) continue;
+		const hipError_t st = hipStreamQuery(m[i]->m_Stream);
+		if (st == hipSuccess) continue;  // (idle: everything it was given has completed)
+		if (st != hipErrorNotReady) JU_HIP(st);
+		m[i]->m_GroupEvent.record(m[i]->m_Stream);
+		JU_HIP(hipStreamWaitEvent(L.m_Stream, m[i]->m_GroupEvent.get(), 0));
+	}
+	const bool recurrent = L.m_Config.recurrent();
+	const long flowItem = recurrent ? static_cast<long>(L.m_Tensors.at("flow").count) * 2 : 0;
+	const unsigned char *flowBase = recurrent ? L.m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
+	{
+		// 5. the device chain, once for the whole pass (chainBegin / chainEnd, for a pass that may hold several
+		// members' resident towers): ordered after the frame submitted last by any other resident runtime, and any
+		// member's next frame is ordered after the pass (lastOwner = the lead)
+		DeviceChain &c = chainOf(L.m_Device);
+		std::unique_lock<std::mutex> chain(c.mutex);
+		bool resident = false;
+		for (int i = 0; i < n; ++i) resident = resident || m[i]->m_Resident;
+		if (c.engines > 1 && resident && c.last != nullptr && c.lastOwner != &L) JU_HIP(hipStreamWaitEvent(L.m_Stream, c.last, 0));
+		// 2. the flow net once over all items
+		for (int i = 0; i < n; ++i) {
+			L.m_GroupPrev[i] = m[i]->m_Packed[sets[i]].get();
+			L.m_GroupOut[i] = m[i]->m_Packed[sets[i] ^ 1].get();
+		}
+		for (const Step &st : L.m_BatchFlow.at({n, kGroupSet})) st.run(L.m_Stream);
+		// 3. member by member, its own steps on the lead's stream, bound to its frame and its flow item
+		for (int i = 0; i < n; ++i) {
+			Engine &e = *m[i];
+			const FrameIO keepIO = e.m_IO;
+			const void *keepFlow = e.m_FlowCur;
+			struct Restore {
+				Engine &e;
+				FrameIO io;
+				const void *flow;
+				~Restore() {
+					e.m_IO = io;
+					e.m_FlowCur = flow;
+				}
+			} restore{e, keepIO, keepFlow};
+			e.m_IO = L.m_BatchIO[i];
+			if (recurrent) e.m_FlowCur = flowBase + i * flowItem;
+			for (const Step &st : e.m_Program[sets[i]]) {
+				if (st.tag != "flow" && st.tag != "pack") st.run(L.m_Stream);
+			}
+			if (L.m_BatchHost[i].hostOut) launchSignalHost(L.m_PassSignal.device(), L.m_Stream);
+		}
+		if (c.engines > 1 && resident) {
+			L.m_FrameDone.record(L.m_Stream);
+			c.last = L.m_FrameDone.get();
+			c.lastOwner = &L;
+		}
+	}
+	// 4. every member's stream after the pass
+	L.m_GroupEvent.record(L.m_Stream);
+	for (int i = 0; i < n; ++i) {
+		if (m[i] != &L) JU_HIP(hipStreamWaitEvent(m[i]->m_Stream, L.m_GroupEvent.get(), 0));
+	}
+	L.drainPassOutputs(out, n);  // host frames: each copied out while the next member runs
+	L.m_Stream.synchronizeSpin(L.m_SpinUs);
+	// one synchronisation; then every member's resident-tower error word
+	unsigned codes[kFlowBatchMax];
+	bool failed = false;
+	for (int i = 0; i < n; ++i) {
+		codes[i] = m[i]->takeResidentError();
+		failed = failed || codes[i] != 0;
+	}
+	if (failed) {
+		// nothing the pass wrote is one of its inputs: the same frames again, member by member, each through its own
+		// process() -- a member whose tower timed out on its per-block kernels from now on
+		for (int i = 0; i < n; ++i) {
+			if (codes[i]) m[i]->fallbackToLayers(codes[i]);
+		}
+		for (int i = 0; i < n; ++i) m[i]->process(in[i], out[i]);
+		return;
+	}
+	for (int i = 0; i < n; ++i) {
+		m[i]->m_Idx = sets[i] ^ 1;
+		++m[i]->m_GroupFrames;
+		m[i]->maybeRestoreResident();
 	}
 }
 
@@ -2457,6 +2672,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "lookahead_frames") return static_cast<double>(m_BatchFrames);  // frames that went through look-ahead passes
 	if (key == "lookahead_host_frames") return static_cast<double>(m_BatchHostFrames);  // ... of them with a host image
 	if (key == "lookahead_max") return static_cast<double>(m_BatchMax);
+	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
 	if (key == "launches_per_frame") return static_cast<double>(m_Program[0].size());
 	if (key == "tower_variant") return static_cast<double>(towerVariant());  // (developer switch, tests)
 	if (key == "direct_graphs") {

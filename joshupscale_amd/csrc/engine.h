@@ -87,6 +87,12 @@ public:
 	int prepareBatch(const Frame *in, const Frame *out, int count);
 	// Frames per look-ahead pass, 1 (off) .. kFlowBatchMax, clamped.  Default: kFlowBatchMax, or JU_LOOKAHEAD at creation.
 	void setLookahead(int frames);
+	// One frame for each of `count` runtimes, synchronously: the bytes process(in[i], out[i]) for i = 0 .. count - 1 would
+	// write, in every output and every member's state.  The members (distinct, one device, byte-identical model data,
+	// one dtype override: std::invalid_argument otherwise, before anything is launched) share a pass where they can:
+	// members[0] (the lead) runs the flow net ONCE over up to its look-ahead cap of frames, each the next frame of its
+	// own stream, then every member's own recurrent steps, all on the lead's stream (engine.cpp, "Group passes").
+	static void processGroup(Engine *const *members, const Frame *in, const Frame *out, int count);
 	// Asynchronous variant for device-resident frames: enqueue only.
 	void enqueue(const Frame &in, const Frame &out);
 	void synchronize();
@@ -174,7 +180,8 @@ private:
 	void addConvStep(std::vector<Step> *prog, const std::string &tag, const std::string &wname,
 	    Operand in, Operand res, Operand out, int H, int W, bool relu, bool outHead,
 	    bool tower = false, bool pool = false, bool upsample = false, ItemStride item = ItemStride());
-	void addFlowAutoencoder(std::vector<Step> *prog, int set, int items);
+	// group: the launches of a group pass (independent items: processGroup) -- `set` is then unused
+	void addFlowAutoencoder(std::vector<Step> *prog, int set, int items, bool group = false);
 	bool flowPacksInBlock() const;
 	Operand operand(const std::string &name);
 	Tensor &addTowerTensor(const std::string &name, int H, int W, int C);
@@ -371,12 +378,28 @@ private:
 	static constexpr std::size_t kMaxBatchGraphs = 64;          // unregistered tuples (LRU)
 	static constexpr std::size_t kMaxRegisteredBatches = 256;   // tuples registered through prepareBatch
 	std::uint64_t m_BatchFrames = 0;
-	bool batchPlanned(int items);
+	// group: the flow launches of a group pass over `items` streams (processGroup), in m_BatchFlow at {items, kGroupSet}
+	bool batchPlanned(int items, bool group = false);
+	static constexpr int kGroupSet = 2;
 	void submitBatch(const Frame *in, const Frame *out, int n);
 	void runBatch(int set, int n, const std::function<void(const Step &, bool)> *around = nullptr);
 	void dropBatchGraphs();
 	std::vector<DirectKey> bindBatch(const Frame *in, const Frame *out, int n, int set);
 	DirectEntry &batchEntry(const std::vector<DirectKey> &key);
+	// Group passes (processGroup).  The model's identity: FNV-1a of the container bytes the engine was built from, and
+	// the dtype it was asked for.  As the lead of a pass: the history each item's first flow block reads / writes (read
+	// at launch time).  As a member: an event its stream records for the lead to wait on, and the frames it got from
+	// passes ("group_frames").
+	std::uint64_t m_ModelDigest = 0;
+	int m_DtypeOverride = -1;
+	const void *m_GroupPrev[kFlowBatchMax] = {};
+	void *m_GroupOut[kFlowBatchMax] = {};
+	Event m_GroupEvent;
+	std::uint64_t m_GroupFrames = 0;
+	bool sameModel(const Engine &o) const;
+	void checkGroupFrame(const Frame &f, bool input) const;
+	// one pass over members m[0 .. n) on `lead`'s stream and tensors (the lead need not be one of them)
+	static void runGroupPass(Engine &lead, Engine *const *m, const Frame *in, const Frame *out, int n);
 	std::uint64_t m_DirectClock = 0;
 	bool m_DirectGraph = true;  // JU_DIRECT_GRAPH=0: device frames always launch eagerly
 	static constexpr std::size_t kMaxDirectGraphs = 64;     // unregistered tuples (LRU)

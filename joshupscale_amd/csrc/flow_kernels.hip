@@ -60,6 +60,10 @@ struct FlowBlockParams {
 	long inItem, outItem;
 	const std::uint8_t *frames[kFlowBatchMax];
 	std::ptrdiff_t frameStrides[kFlowBatchMax];
+	// independent items (INDEP instantiation, Engine::processGroup): item i is the next frame of its OWN stream --
+	// history from packPrevs[i], new history to packOuts[i]; packPrev / packOut are unused
+	const void *packPrevs[kFlowBatchMax];
+	void *packOuts[kFlowBatchMax];
 };
 
 template <int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, int NW = 4>
@@ -113,9 +117,10 @@ struct FbGeom {
 // NW waves per workgroup: 8 (two per SIMD) wherever the kernel fits 256 registers -- the
 // staging, expansion and epilogue phases are VALU work that one wave per SIMD issues at
 // half rate, and a partner wave's epilogue runs beside the other's MFMAs.
-template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, int NW, bool PACK = false>
+template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, int NW, bool PACK = false, bool INDEP = false>
 __global__ __launch_bounds__(NW * 64, NW / 4) void flow_block_kernel(FlowBlockParams p) {
 	static_assert(!PACK || (CIN == 16 && !UPS), "PACK: the 16-channel flow input");
+	static_assert(!INDEP || PACK, "INDEP: a form of the input packing");
 	using G = FbGeom<CIN, CMID, TH, UPS, POOL, OUTK, NW>;
 	constexpr int NT = NW * 64;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -227,11 +232,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void flow_block_kernel(FlowBlockPa
 		// A look-ahead launch (item = blockIdx.z of gridDim.z frames) takes history slot k of item i from frame i - k of
 		// the launch where there is one -- the same conversion of the same bytes the earlier frame's own pack did -- and
 		// from the previous tensor's slot k - i - 1 otherwise; the last item alone writes the new history.
+		// INDEP (a group pass: every item the next frame of a stream of its own): slot 0 from frames[i], the rest from
+		// packPrevs[i], and every item writes packOuts[i] -- per item the arithmetic of a one-frame launch.
 		const float bright = brightnessOf(p.sums, 1.0f / static_cast<float>(p.frameH * p.frameW));
-		const T *__restrict__ prev = static_cast<const T *>(p.packPrev);
-		T *__restrict__ cur = item + 1 == static_cast<int>(gridDim.z) ? static_cast<T *>(p.packOut) : nullptr;
+		const T *__restrict__ prev = static_cast<const T *>(INDEP ? p.packPrevs[item] : p.packPrev);
+		T *__restrict__ cur = INDEP ? static_cast<T *>(p.packOuts[item])
+		                            : (item + 1 == static_cast<int>(gridDim.z) ? static_cast<T *>(p.packOut) : nullptr);
 		const int nch = 3 * p.numInputs;
-		const int fromFrames = min(item + 1, p.numInputs);  // history slots 0 .. fromFrames - 1 come from frames
+		const int fromFrames = INDEP ? 1 : min(item + 1, p.numInputs);  // history slots 0 .. fromFrames - 1 come from frames
 		constexpr int NPIX = G::XR * kFbW;
 		for (int q = tid; q < NPIX; q += NT) {
 			const int r = q / kFbW, k = q - r * kFbW;
@@ -602,12 +610,12 @@ constexpr int fbWaves() {
 	return (CIN > 64 || CMID > 64) ? 4 : 8;
 }
 
-template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, bool PACK = false>
+template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, bool PACK = false, bool INDEP = false>
 void launchFlowBlockInst(const FlowBlockParams &p, int items, hipStream_t stream) {
 	constexpr int NW = fbWaves<CIN, CMID>();
 	using G = FbGeom<CIN, CMID, TH, UPS, POOL, OUTK, NW>;
 	static_assert(G::FITS, "tile does not fit LDS");
-	auto kern = flow_block_kernel<T, CIN, CMID, TH, UPS, POOL, OUTK, NW, PACK>;
+	auto kern = flow_block_kernel<T, CIN, CMID, TH, UPS, POOL, OUTK, NW, PACK, INDEP>;
 	static std::atomic<std::uint64_t> ldsDone{0};
 	ensureDynamicLds(reinterpret_cast<const void *>(kern), G::LDS, &ldsDone, "flow block");
 	if (launchesAreDry()) return;
@@ -636,7 +644,7 @@ inline int fbForcedTile() {
 	return forced;
 }
 
-template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK, int... THS>
+template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK, bool INDEP, int... THS>
 void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, hipStream_t stream) {
 	const long tilesX = (p.W + kFbOutW - 1) / kFbOutW;
 	int best = 0;
@@ -655,7 +663,7 @@ void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, hipStr
 		constexpr int TH = decltype(thTag)::value;
 		if constexpr (FbGeom<CIN, CMID, TH, UPS, POOL, OUTK, fbWaves<CIN, CMID>()>::FITS) {
 			if (!done && best == TH) {
-				launchFlowBlockInst<T, CIN, CMID, TH, UPS, POOL, OUTK, PACK>(p, items, stream);
+				launchFlowBlockInst<T, CIN, CMID, TH, UPS, POOL, OUTK, PACK, INDEP>(p, items, stream);
 				done = true;
 			}
 		}
@@ -664,20 +672,20 @@ void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, hipStr
 	if (!done) throw std::logic_error("flow block: no tile height fits");
 }
 
-template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK = false>
+template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK = false, bool INDEP = false>
 void launchFlowBlockT(const FlowBlockParams &p, int items, int numCUs, hipStream_t stream) {
 	if constexpr (OUTK == 2) {
 		// (64 -> 64 -> 64 residual block, JU_RES_BLOCK=tile only: two 128-byte tiles; 14 rows is what fits)
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, kFbMid, 6>(p, items, numCUs, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, kFbMid, 6>(p, items, numCUs, stream);
 	} else if constexpr (CMID == 128) {
 		// (the 128-filter blocks, 68 x 120 at 480 x 270: a few thousand pixels -- short tiles, or most of the chip idles;
 		// measured for the encoder / decoder block: 2 rows 11.7 / 23.8 us, 4 rows 16.0 / 32.1, 6 rows 19.9 / 39.1.  One
 		// frame is a single round of 2-row tiles; a look-ahead launch of 8 frames is five such rounds or two of 6-row
 		// tiles -- the cost rule above picks.  The decoder block's taller tiles keep two of its four input planes in LDS
 		// at a time: FbGeom::XPAIR.)
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, 6, 4, 2>(p, items, numCUs, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 6, 4, 2>(p, items, numCUs, stream);
 	} else {
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, 20, 18, 10, 6>(p, items, numCUs, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 20, 18, 10, 6>(p, items, numCUs, stream);
 	}
 }
 
@@ -711,20 +719,28 @@ void launchFlowBlockDT(const FlowBlockLaunch &q, hipStream_t stream) {
 	if (items > kFlowBatchMax) throw std::invalid_argument("flow block: more look-ahead frames than kFlowBatchMax");
 	p.inItem = items > 1 ? q.inItemBytes : 0;
 	p.outItem = items > 1 ? q.outItemBytes : 0;
+	const bool many = items > 1 || q.independentItems;  // (the frames of packFrames[], not packFrame)
 	for (int i = 0; i < kFlowBatchMax; ++i) {
-		p.frames[i] = items > 1 ? (i < items ? q.packFrames[i] : nullptr) : (i == 0 ? q.packFrame : nullptr);
-		p.frameStrides[i] = items > 1 ? (i < items ? q.packFrameStrides[i] : 0) : (i == 0 ? q.packFrameStride : 0);
+		p.frames[i] = many ? (i < items ? q.packFrames[i] : nullptr) : (i == 0 ? q.packFrame : nullptr);
+		p.frameStrides[i] = many ? (i < items ? q.packFrameStrides[i] : 0) : (i == 0 ? q.packFrameStride : 0);
+		p.packPrevs[i] = q.independentItems && i < items ? q.packPrevs[i] : nullptr;
+		p.packOuts[i] = q.independentItems && i < items ? q.packOuts[i] : nullptr;
 	}
 	if (items > 1 && q.residual) throw std::invalid_argument("flow block: the residual form has no look-ahead launch");
 	const int cus = currentDeviceCUs();
-	if (q.packOut != nullptr) {
-		if (items > 1 && q.sums != nullptr) throw std::invalid_argument("flow block: look-ahead packing has no brightness sums");
+	if (q.packOut != nullptr || q.independentItems) {
+		if (many && q.sums != nullptr) throw std::invalid_argument("flow block: look-ahead packing has no brightness sums");
 		for (int i = 0; i < items; ++i) {
 			if (p.frames[i] == nullptr) throw std::invalid_argument("flow block: input packing needs every frame of the launch");
+			if (q.independentItems && (p.packPrevs[i] == nullptr || p.packOuts[i] == nullptr)) {
+				throw std::invalid_argument("flow block: independent items need every item's history buffers");
+			}
 		}
-		if (!(q.cin == 16 && q.cmid == 32 && !q.upsample && q.pool && !q.outHead && !q.residual && q.packPrev)) {
+		if (!(q.cin == 16 && q.cmid == 32 && !q.upsample && q.pool && !q.outHead && !q.residual &&
+		        (q.packPrev || q.independentItems))) {
 			throw std::invalid_argument("flow block: input packing is built for the first block (16 -> 32 -> 32, pool)");
 		}
+		if (q.independentItems) return launchFlowBlockT<T, 16, 32, false, true, 0, true, true>(p, items, cus, stream);
 		return launchFlowBlockT<T, 16, 32, false, true, 0, true>(p, items, cus, stream);
 	}
 	if (q.upsample && (q.H % 2 || q.W % 2)) throw std::invalid_argument("flow block: fused upsampling needs even H and W");

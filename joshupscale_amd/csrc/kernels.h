@@ -164,6 +164,12 @@ struct FlowBlockLaunch {
 	long inItemBytes, outItemBytes;
 	const std::uint8_t *packFrames[kFlowBatchMax];
 	std::ptrdiff_t packFrameStrides[kFlowBatchMax];
+	// Independent items (Engine::processGroup): item i of `items` (>= 1) is the next frame of a stream of its own --
+	// frame packFrames[i], history packPrevs[i], new history written to packOuts[i] by every item; per item the
+	// arithmetic of a one-frame launch.  packPrev / packOut / packFrame are ignored, `sums` must be null.
+	bool independentItems;
+	const void *packPrevs[kFlowBatchMax];
+	void *packOuts[kFlowBatchMax];
 };
 // H x W: the block's resolution (the 128-filter blocks run as one launch only where their 2-row tiles are ONE round of the
 // chip: flow_kernels.hip); 0 = shape only

@@ -91,6 +91,7 @@ _PRODUCT_SIGS = {
     "ju_destroy": (None, [C.c_void_p]),
     "ju_process": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
     "ju_process_batch": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage), C.c_int]),
+    "ju_process_group": (C.c_int, [_P(C.c_void_p), _P(JuImage), _P(JuImage), C.c_int]),
     "ju_prepare_batch": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage), C.c_int, _P(C.c_int)]),
     "ju_set_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_enqueue": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
@@ -402,6 +403,27 @@ class Comm:
             self.close()
         except Exception:  # pragma: no cover
             pass
+
+
+def process_group(runtimes, inputs, outputs) -> None:
+    """``ju_process_group``: one frame for each runtime in one synchronous call -- the bytes of ``runtimes[i].process(
+    inputs[i], outputs[i])`` in list order, the flow nets of the frames computed in shared passes (``runtimes[0]``
+    leads).  The runtimes must be distinct, on one device, built from the same model bytes with the same dtype, and go
+    through one library.  Unequal lists and items that are not :class:`Runtime` raise before any native call."""
+    runtimes, inputs, outputs = list(runtimes), list(inputs), list(outputs)
+    n = len(runtimes)
+    if len(inputs) != n or len(outputs) != n:
+        raise ValueError("process_group: as many inputs and outputs as runtimes")
+    if not all(isinstance(rt, Runtime) for rt in runtimes):
+        raise TypeError("process_group: every member must be a Runtime")
+    if n == 0:
+        return
+    lib = runtimes[0]._lib
+    if any(rt._lib is not lib for rt in runtimes):
+        raise ValueError("process_group: the runtimes were created through different libraries")
+    hs = (C.c_void_p * n)(*[rt._h.value for rt in runtimes])
+    ins, outs = (JuImage * n)(*inputs), (JuImage * n)(*outputs)
+    _check(lib, lib.ju_process_group(hs, ins, outs, n))
 
 
 def gl_image(texture: int, output: bool) -> JuImage:
