@@ -33,6 +33,16 @@ dB, fp16 64.9-68.8 dB; small models 60.4-72.1 dB); flow 0.0018 / 0.0128, output_
 the reference, cuda_convert.cc.cu:76-81, turns any sub-LSB difference at an integer
 boundary into 1 LSB.)  Byte-level paths (staging, strides, X byte, state reset, graph
 replay, device-direct frames) are bit-exact.
+
+The tower's own output (`trunk`) against its rounding-faithful restatement fed the engine's tower input
+(tests/tower_faithful.py, test_gpu_tower_faithful.py), in units of the stream type's spacing (floored at 1/16 of
+the trunk's RMS): share of elements more than 1 unit off / max units / |mean signed units|.  Measured (every
+geometry of that file, 1-3 frames each, 146 comparisons): bf16 0.0093 / 34.5 / 0.0011 at 1-5 blocks (24 blocks:
+0.346 / 90 / 0.013), fp16 0.0356 / 50 / 0.011 (0.356 / 108 / 0.016) -- the level of the float32-reordered restatement, which drifts with
+depth; bounds 1.4 x those.  8-bit towers of 1-2 blocks: 0.341 / 620 / 0.057 (bounds 0.374 / 794 / 0.08, set on
+the first part of that measurement: 1.1-1.4 x).  The 8-bit deviation is larger because the e4m3 matrix instruction
+does not return correctly rounded sums (tools/probes/fp8_mfma_accumulation_probe.hip); deeper 8-bit towers are not
+compared element for element.
 """
 
 import json
