@@ -74,15 +74,17 @@ typedef struct ju_image {
  * are passed by pointer, so their order in memory does not matter).  ju_process_frame converts on the GPU, inside the
  * runtime's own staging: a YUV input is decoded into the BGRX frame the network consumes, the network's BGRX output is
  * encoded into the caller's planes.  Input and output formats are independent (all nine pairs).  A YUV frame is one
- * step of the same recurrent stream: ju_process, ju_process_frame and ju_process_batch may be mixed on one runtime.
+ * step of the same recurrent stream: ju_process, ju_process_frame, ju_process_frames and ju_process_batch may be mixed
+ * on one runtime.
  *
  * The conversion is integer arithmetic, defined exactly ("YUV frames"): BT.601 / BT.709 coefficients,
  * limited (16..235 / 16..240) or full range, chroma sited as MPEG-2 / H.264 by default (co-sited horizontally with the
  * even luma columns, centred vertically between two rows); decoding upsamples chroma bilinearly (weights 3:1 vertically,
  * 1:1 horizontally), encoding filters [1,2,1] x [1,1].
  *
- * Limits: 8-bit 4:2:0 only (no P010 / 10-bit); no YUV graphics resources (GL textures stay BGRX); no YUV frames in
- * ju_process_batch look-ahead passes; the C++ plugin surface (JoshUpscale/core.h) is unchanged and takes BGRX only. */
+ * Limits: 8-bit 4:2:0 only (no P010 / 10-bit); no YUV graphics resources (GL textures stay BGRX); look-ahead passes
+ * take YUV frames through ju_process_frames (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not
+ * ju_process_group; the C++ plugin surface (JoshUpscale/core.h) is unchanged and takes BGRX only. */
 enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2 };
 enum { JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3 };
 
@@ -193,6 +195,29 @@ JU_API int ju_synchronize(ju_runtime *runtime);
  * they were): an odd width or height of a YUV frame, a size other than the runtime's, a NULL plane, an unknown format
  * or colour space, a YUV frame at JU_LOC_GRAPHICS_RESOURCE, a |stride| smaller than the plane's row. */
 JU_API int ju_process_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output);
+/* Frame look-ahead on frames of any format: `count` CONSECUTIVE frames of the stream in one synchronous call.
+ * outputs[i] receives exactly the bytes ju_process_frame(&inputs[i], &outputs[i]) called in order would have written --
+ * every plane, and nothing around it -- and the recurrent state and frame history afterwards are the same; ALL inputs
+ * must hold their pixels when the call is made.  For the transcoder that reads ahead AND holds NV12 / I420: inside a pass
+ * a host 4:2:0 frame pair moves 3.3 MB over PCIe instead of BGRX's 8.8 MB, the outputs' planes copied out while the next
+ * frame's kernels run.  Formats, colour spaces, locations and strides (any sign) are independent per frame and per side,
+ * as in ju_process_frame; a call of BGRX frames only behaves as ju_process_batch.
+ * Passes are those of ju_process_batch: at most ju_set_lookahead frames each, longer calls split into consecutive
+ * passes; a frame a pass cannot take (a GL resource, a JU_LOC_DEVICE BGRX image off 4-byte (input) / 8-byte (output)
+ * alignment, any frame of a model without the one-launch flow plan) runs on its own in stream order, as
+ * ju_process_frame would run it, and the passes continue behind it.  A frame with an input plane over an output plane of
+ * an earlier frame of the pass (same address space), or an output plane over an earlier input plane, starts a new pass.
+ * The YUV inputs of a pass are decoded by ONE launch in front of the flow net's; every YUV output is encoded behind its
+ * frame's tail.  Device planes are read and written in place; nothing of the caller's is page-locked.
+ * JU_ERR_INVALID_ARGUMENT: a NULL array or count < 0; and whatever ju_process_frame refuses, for ANY frame of the call --
+ * every pair is checked before anything is launched or uploaded, the message names the frame's index, and the runtime
+ * and its state stay as they were.  count == 0 does nothing.
+ * ju_get_stat "lookahead_yuv_frames": frames with a YUV side that went through passes (also counted by
+ * "lookahead_frames" and, with a host side, "lookahead_host_frames").
+ * Not provided: a ju_prepare_* counterpart (an unregistered tuple of device planes is captured at its second use, as in
+ * ju_process_batch; all-host passes of one shape share one graph); YUV frames in ju_process_group; 10-bit formats; the
+ * C++ plugin surface. */
+JU_API int ju_process_frames(ju_runtime *runtime, const ju_frame *inputs, const ju_frame *outputs, int count);
 /* Asynchronous form (like ju_enqueue): JU_LOC_DEVICE frames only -- a host frame is JU_ERR_INVALID_ARGUMENT;
  * ju_synchronize waits. */
 JU_API int ju_enqueue_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output);
@@ -275,6 +300,8 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * (graphs cached for JU_LOC_DEVICE frame tuples), "resident_tower" / "resident_flow"
  * (1 when the one-launch tower kernel is in use), "launches_per_frame", "tower_variant",
  * "group_frames" (frames this runtime got from ju_process_group passes),
+ * "lookahead_frames" (frames that went through look-ahead passes; of them "lookahead_host_frames" with a host side,
+ * "lookahead_yuv_frames" with a YUV side),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,
  * flow_arch "none" of the container -- every frame is upscaled on its own, ju_reset does nothing). */
 JU_API int ju_get_stat(const ju_runtime *runtime, const char *key, double *value);

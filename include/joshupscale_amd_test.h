@@ -47,7 +47,9 @@ JU_API int ju_time_steps(ju_runtime *runtime, const char *tag, int iters, double
  * caller).  Keys: "tower_variant" (0 = product kernel, 4 = phase profile, 5 = per-layer
  * output maxima for quantisation calibration, 8 = the resident tower's plain schedule:
  * same bytes, tests compare it with the product's); "resident_fault" n
- * (launch the resident tower n workgroups short: tests the fallback). */
+ * (launch the resident tower n workgroups short: tests the fallback); "pass_rerun" 1 (a look-ahead
+ * pass that completed normally is run again frame by frame, as after a resident-tower report but without the
+ * fallback: the re-run's bookkeeping; no kernel misbehaves). */
 JU_API int ju_debug_set(const char *key, int value);
 
 /* The loader's e4m3 quantiser (round to nearest even, saturating at +-448), exposed so
@@ -59,6 +61,14 @@ JU_API int ju_debug_e4m3(const float *values, unsigned char *codes, size_t count
  * 1: BGRX -> planes.  Any byte alignment, any signed strides (as in ju_frame). */
 JU_API int ju_debug_yuv(int direction, int format, int colorspace, size_t width, size_t height, void *bgrx,
     ptrdiff_t bgrx_stride, void *const planes[3], const ptrdiff_t strides[3]);
+
+/* The decode kernel of ju_process_frames' look-ahead passes alone (yuv420_to_bgrx_items_kernel: the YUV inputs of a
+ * pass in one launch), on caller-supplied device buffers, synchronously: `count` (1 .. 8) items of one width x height,
+ * item i = format formats[i] (JU_FMT_I420 / JU_FMT_NV12), colour space colorspaces[i], planes planes[3 i .. 3 i + 2] with
+ * strides[3 i .. 3 i + 2] (the third unused for NV12) -> BGRX rows at bgrx[i], bgrx_strides[i] bytes apart.  Any byte
+ * alignment, any signed strides.  Per item the bytes of ju_debug_yuv direction 0. */
+JU_API int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, size_t width, size_t height,
+    void *const *bgrx, const ptrdiff_t *bgrx_strides, void *const *planes, const ptrdiff_t *strides);
 
 #ifdef __cplusplus
 } /* extern "C" */

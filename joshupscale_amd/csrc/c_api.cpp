@@ -238,6 +238,26 @@ int ju_process_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame 
 	});
 }
 
+int ju_process_frames(ju_runtime *runtime, const ju_frame *inputs, const ju_frame *outputs, int count) {
+	return guarded([&] {
+		if (count < 0 || (count > 0 && (inputs == nullptr || outputs == nullptr))) {
+			throw std::invalid_argument("ju_process_frames: NULL frames or a negative count");
+		}
+		if (count == 0) return;
+		ju::Engine &e = engineOf(runtime);
+		std::vector<ju::AnyFrame> in(static_cast<std::size_t>(count)), out(static_cast<std::size_t>(count));
+		for (int i = 0; i < count; ++i) {
+			try {
+				in[i] = toAnyFrame(inputs + i);
+				out[i] = toAnyFrame(outputs + i);
+			} catch (const std::invalid_argument &err) {
+				throw std::invalid_argument("ju_process_frames: frame " + std::to_string(i) + ": " + err.what());
+			}
+		}
+		e.processFrames(in.data(), out.data(), count);
+	});
+}
+
 int ju_enqueue_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output) {
 	return guarded([&] {
 		ju::Engine &e = engineOf(runtime);
@@ -383,6 +403,7 @@ int ju_debug_set(const char *key, int value) {
 		else if (k == "tower_fast") ju::setResidentTowerFast(value);
 		else if (k == "res_block_plain") ju::setResBlockPlain(value);
 		else if (k == "fp8_block_form") ju::setFp8BlockForm(value);
+		else if (k == "pass_rerun") ju::setPassRerun(value);
 		else throw std::invalid_argument("unknown debug key " + k);
 	});
 }
@@ -415,6 +436,41 @@ int ju_debug_yuv(int direction, int format, int colorspace, size_t width, size_t
 			ju::launchBgrxToYuv420(nv12, static_cast<const std::uint8_t *>(bgrx), bgrx_stride,
 			    ju::yuvEncodeCoefficients(colorspace), p, w, h, nullptr);
 		}
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, size_t width, size_t height,
+    void *const *bgrx, const ptrdiff_t *bgrx_strides, void *const *planes, const ptrdiff_t *strides) {
+	return guarded([&] {
+		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_yuv_items: 1 .. 8 items");
+		if (width == 0 || height == 0 || width % 2 || height % 2 || width > (1u << 15) || height > (1u << 15)) {
+			throw std::invalid_argument("ju_debug_yuv_items: width and height must be even, 2 .. 32768");
+		}
+		if (!formats || !colorspaces || !bgrx || !bgrx_strides || !planes || !strides) {
+			throw std::invalid_argument("ju_debug_yuv_items: null argument");
+		}
+		ju::YuvDecodeItems items{};
+		for (int i = 0; i < count; ++i) {
+			const int f = formats[i];
+			if (f != JU_FMT_I420 && f != JU_FMT_NV12) throw std::invalid_argument("ju_debug_yuv_items: not a YUV format");
+			void *const *p = planes + 3 * i;
+			if (bgrx[i] == nullptr || p[0] == nullptr || p[1] == nullptr || (f == JU_FMT_I420 && p[2] == nullptr)) {
+				throw std::invalid_argument("ju_debug_yuv_items: null buffer");
+			}
+			ju::YuvDecodeItem &it = items.item[i];
+			it.src.y = static_cast<std::uint8_t *>(p[0]);
+			it.src.u = static_cast<std::uint8_t *>(p[1]);
+			it.src.v = f == JU_FMT_I420 ? static_cast<std::uint8_t *>(p[2]) : nullptr;
+			it.src.yStride = strides[3 * i];
+			it.src.uStride = strides[3 * i + 1];
+			it.src.vStride = f == JU_FMT_I420 ? strides[3 * i + 2] : 0;
+			it.k = ju::yuvDecodeCoefficients(colorspaces[i]);
+			it.dst = static_cast<std::uint8_t *>(bgrx[i]);
+			it.dstStride = bgrx_strides[i];
+			it.nv12 = f == JU_FMT_NV12 ? 1 : 0;
+		}
+		ju::launchYuv420ToBgrxItems(items, count, static_cast<int>(width), static_cast<int>(height), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

@@ -80,12 +80,12 @@ __device__ inline void storeBytes(std::uint8_t *row, int col, int n, bool fast, 
 }
 
 // Y, U, V (I420) or Y, UV (NV12) -> BGRX.  Thread = chroma row j (luma rows 2j, 2j + 1) x luma columns x0 .. x0 + 15;
-// it reads chroma rows j - 1 .. j + 1 at columns x0 / 2 .. x0 / 2 + 8 (clamped to the plane).
+// it reads chroma rows j - 1 .. j + 1 at columns x0 / 2 .. x0 / 2 + 8 (clamped to the plane).  The strip of thread `idx`:
+// the body of both decode kernels below, so that a frame decoded inside a look-ahead pass has the single frame's bytes.
 template <bool NV12>
-__global__ __launch_bounds__(256) void yuv420_to_bgrx_kernel(YuvPlanes src, YuvDecode k, std::uint8_t *__restrict__ dst,
-    std::ptrdiff_t dstStride, int W, int H) {
+__device__ inline void yuv420ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H, int idx) {
 	const int strips = (W + kStrip - 1) / kStrip;
-	const int idx = blockIdx.x * 256 + threadIdx.x;
 	if (idx >= strips * (H / 2)) return;
 	const int j = idx / strips;
 	const int x0 = (idx - j * strips) * kStrip;
@@ -166,6 +166,26 @@ __global__ __launch_bounds__(256) void yuv420_to_bgrx_kernel(YuvPlanes src, YuvD
 			const unsigned w[4] = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
 			storeBytes<16>(row, 4 * (x0 + 4 * q), 4 * (n - 4 * q), full, w);
 		}
+	}
+}
+
+template <bool NV12>
+__global__ __launch_bounds__(256) void yuv420_to_bgrx_kernel(YuvPlanes src, YuvDecode k, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H) {
+	yuv420ToBgrxStrip<NV12>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+// The YUV inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item --
+// its planes, coefficients and destination, from the kernel arguments -- and its format is a branch every lane of the
+// workgroup takes alike.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
+// launch latencies for one round of work (the shape addFlowAutoencoder's batched launches fixed for the flow net).
+__global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
+	const YuvDecodeItem &it = items.item[blockIdx.y];
+	const int idx = blockIdx.x * 256 + threadIdx.x;
+	if (it.nv12) {
+		yuv420ToBgrxStrip<true>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	} else {
+		yuv420ToBgrxStrip<false>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
 	}
 }
 
@@ -311,6 +331,14 @@ void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std
 		    dstStride, width, height);
 	}
 	hipCheckLaunch("yuv420_to_bgrx");
+}
+
+void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream) {
+	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("yuv420_to_bgrx_items: 1 .. 8 items");
+	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
+	hipLaunchKernelGGL(yuv420_to_bgrx_items_kernel, dim3(blocksFor(threads), count), dim3(256), 0, stream, items, width,
+	    height);
+	hipCheckLaunch("yuv420_to_bgrx_items");
 }
 
 void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,

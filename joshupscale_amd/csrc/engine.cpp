@@ -3,6 +3,7 @@
 #include <cstdio>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -1473,6 +1474,53 @@ PlaneShape planeShape(PixelFormat f, std::size_t w, std::size_t h, int k) {
 int planeCount(PixelFormat f) { return f == PixelFormat::Nv12 ? 2 : 3; }
 std::size_t stagePitch(std::size_t rowBytes) { return (rowBytes + 63) / 64 * 64; }
 const char *formatName(PixelFormat f) { return f == PixelFormat::Nv12 ? "NV12" : "I420"; }
+
+// The caller's device planes as a conversion kernel takes them
+YuvPlanes callerPlanes(const YuvFrame &f) {
+	YuvPlanes pl;
+	std::uint8_t **plane[3] = {&pl.y, &pl.u, &pl.v};
+	std::ptrdiff_t *stride[3] = {&pl.yStride, &pl.uStride, &pl.vStride};
+	for (int k = 0; k < planeCount(f.format); ++k) {
+		*plane[k] = static_cast<std::uint8_t *>(f.planes[k]);
+		*stride[k] = f.strides[k];
+	}
+	return pl;
+}
+
+// A host frame's planes in a device staging buffer: plane after plane, rows padded to stagePitch, in the caller's MEMORY
+// order -- a bottom-up plane stays bottom-up there and the kernel addresses it from its last row with a negative pitch.
+YuvPlanes stagedPlanes(const YuvFrame &f, std::uint8_t *stage) {
+	YuvPlanes pl;
+	std::uint8_t **plane[3] = {&pl.y, &pl.u, &pl.v};
+	std::ptrdiff_t *stride[3] = {&pl.yStride, &pl.uStride, &pl.vStride};
+	for (int k = 0; k < planeCount(f.format); ++k) {
+		const PlaneShape p = planeShape(f.format, f.width, f.height, k);
+		const auto pitch = static_cast<std::ptrdiff_t>(stagePitch(p.rowBytes));
+		const bool up = f.strides[k] > 0;
+		*plane[k] = up ? stage : stage + static_cast<std::ptrdiff_t>(p.rows - 1) * pitch;
+		*stride[k] = up ? pitch : -pitch;
+		stage += pitch * static_cast<std::ptrdiff_t>(p.rows);
+	}
+	return pl;
+}
+
+// The pageable copies between a host frame's planes and that staging layout, plane by plane on `stream`
+void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream_t stream) {
+	for (int k = 0; k < planeCount(f.format); ++k) {
+		const PlaneShape p = planeShape(f.format, f.width, f.height, k);
+		const std::size_t pitch = stagePitch(p.rowBytes);
+		auto *first = static_cast<std::uint8_t *>(f.planes[k]);
+		const std::ptrdiff_t s = f.strides[k];
+		std::uint8_t *lowest = s > 0 ? first : first + static_cast<std::ptrdiff_t>(p.rows - 1) * s;
+		const std::size_t hostPitch = static_cast<std::size_t>(s > 0 ? s : -s);
+		if (toDevice) {
+			JU_HIP(hipMemcpy2DAsync(stage, pitch, lowest, hostPitch, p.rowBytes, p.rows, hipMemcpyHostToDevice, stream));
+		} else {
+			JU_HIP(hipMemcpy2DAsync(lowest, hostPitch, stage, pitch, p.rowBytes, p.rows, hipMemcpyDeviceToHost, stream));
+		}
+		stage += pitch * p.rows;
+	}
+}
 }  // namespace
 
 // bytes of a staging buffer that holds any 4:2:0 frame of the size (I420's three planes take the most)
@@ -1538,33 +1586,9 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 void Engine::stageInYuv(const YuvFrame &in) {
 	const FrameSize fs = frameSize();
 	const std::size_t w = fs.inputWidth, h = fs.inputHeight;
-	std::uint8_t *plane[3] = {};
-	std::ptrdiff_t stride[3] = {};
-	if (in.location == Location::Device) {
-		for (int k = 0; k < 3; ++k) {
-			plane[k] = static_cast<std::uint8_t *>(in.planes[k]);
-			stride[k] = in.strides[k];
-		}
-	} else {
-		// upload the rows in memory order; a bottom-up plane stays bottom-up in the staging buffer and the kernel
-		// reads it with a negative pitch
-		auto *stage = m_YuvInStage.as<std::uint8_t>();
-		for (int k = 0; k < planeCount(in.format); ++k) {
-			const PlaneShape p = planeShape(in.format, w, h, k);
-			const auto pitch = static_cast<std::ptrdiff_t>(stagePitch(p.rowBytes));
-			const auto *src = static_cast<const std::uint8_t *>(in.planes[k]);
-			const std::ptrdiff_t s = in.strides[k];
-			const std::uint8_t *lowest = s > 0 ? src : src + static_cast<std::ptrdiff_t>(p.rows - 1) * s;
-			JU_HIP(hipMemcpy2DAsync(stage, pitch, lowest, static_cast<std::size_t>(s > 0 ? s : -s), p.rowBytes, p.rows,
-			    hipMemcpyHostToDevice, m_Stream));
-			plane[k] = s > 0 ? stage : stage + static_cast<std::ptrdiff_t>(p.rows - 1) * pitch;
-			stride[k] = s > 0 ? pitch : -pitch;
-			stage += pitch * static_cast<std::ptrdiff_t>(p.rows);
-		}
-	}
-	YuvPlanes pl;
-	pl.y = plane[0], pl.u = plane[1], pl.v = plane[2];
-	pl.yStride = stride[0], pl.uStride = stride[1], pl.vStride = stride[2];
+	const bool host = in.location != Location::Device;
+	if (host) copyPlanes(in, m_YuvInStage.as<std::uint8_t>(), true, m_Stream);
+	const YuvPlanes pl = host ? stagedPlanes(in, m_YuvInStage.as<std::uint8_t>()) : callerPlanes(in);
 	launchYuv420ToBgrx(in.format == PixelFormat::Nv12, pl, yuvDecodeCoefficients(in.colorspace),
 	    m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4), static_cast<int>(w), static_cast<int>(h),
 	    m_Stream);
@@ -1574,41 +1598,12 @@ void Engine::stageOutYuv(const YuvFrame &out) {
 	const FrameSize fs = frameSize();
 	const std::size_t w = fs.outputWidth, h = fs.outputHeight;
 	const bool host = out.location == Location::Host;
-	std::uint8_t *plane[3] = {};
-	std::ptrdiff_t stride[3] = {};
-	auto *stage = m_YuvOutStage.as<std::uint8_t>();
-	for (int k = 0; k < planeCount(out.format); ++k) {
-		if (!host) {
-			plane[k] = static_cast<std::uint8_t *>(out.planes[k]);
-			stride[k] = out.strides[k];
-			continue;
-		}
-		// the kernel writes the staging buffer in the caller's row order (memory order), copied out below
-		const PlaneShape p = planeShape(out.format, w, h, k);
-		const auto pitch = static_cast<std::ptrdiff_t>(stagePitch(p.rowBytes));
-		const bool up = out.strides[k] > 0;
-		plane[k] = up ? stage : stage + static_cast<std::ptrdiff_t>(p.rows - 1) * pitch;
-		stride[k] = up ? pitch : -pitch;
-		stage += pitch * static_cast<std::ptrdiff_t>(p.rows);
-	}
-	YuvPlanes pl;
-	pl.y = plane[0], pl.u = plane[1], pl.v = plane[2];
-	pl.yStride = stride[0], pl.uStride = stride[1], pl.vStride = stride[2];
+	// (a host frame: the kernel writes the staging buffer in the caller's row order, copied out below)
+	const YuvPlanes pl = host ? stagedPlanes(out, m_YuvOutStage.as<std::uint8_t>()) : callerPlanes(out);
 	launchBgrxToYuv420(out.format == PixelFormat::Nv12, m_OutStage.as<std::uint8_t>(),
 	    static_cast<std::ptrdiff_t>(w * 4), yuvEncodeCoefficients(out.colorspace), pl, static_cast<int>(w),
 	    static_cast<int>(h), m_Stream);
-	if (!host) return;
-	stage = m_YuvOutStage.as<std::uint8_t>();
-	for (int k = 0; k < planeCount(out.format); ++k) {
-		const PlaneShape p = planeShape(out.format, w, h, k);
-		const auto pitch = stagePitch(p.rowBytes);
-		auto *dst = static_cast<std::uint8_t *>(out.planes[k]);
-		const std::ptrdiff_t s = out.strides[k];
-		std::uint8_t *lowest = s > 0 ? dst : dst + static_cast<std::ptrdiff_t>(p.rows - 1) * s;
-		JU_HIP(hipMemcpy2DAsync(lowest, static_cast<std::size_t>(s > 0 ? s : -s), stage, pitch, p.rowBytes, p.rows,
-		    hipMemcpyDeviceToHost, m_Stream));
-		stage += pitch * p.rows;
-	}
+	if (host) copyPlanes(out, m_YuvOutStage.as<std::uint8_t>(), false, m_Stream);
 }
 
 bool Engine::directEligible(const Frame &in, const Frame &out) const {
@@ -1845,6 +1840,23 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		m_StateBind[set] = keepBind;
 		m_FlowCur = keepFlow;
 	}};
+	// the pass's YUV inputs into their frames' BGRX buffers, all in one launch (a flow-free pass has no launch before it)
+	YuvDecodeItems items{};
+	int decodes = 0;
+	for (int i = 0; i < n; ++i) {
+		const PassFrame &pf = m_BatchHost[i];
+		if (!pf.yuvIn) continue;
+		YuvDecodeItem &it = items.item[decodes++];
+		it.src = pf.decode;
+		it.k = yuvDecodeCoefficients(pf.csIn);
+		it.dst = const_cast<std::uint8_t *>(m_BatchIO[i].in);
+		it.dstStride = m_BatchIO[i].inStride;
+		it.nv12 = pf.nv12In ? 1 : 0;
+	}
+	if (decodes) {
+		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),
+		    m_Stream);
+	}
 	for (const Step &st : flow) run(st);
 	for (int i = 0; i < n; ++i) {
 		m_IO = m_BatchIO[i];
@@ -1856,78 +1868,155 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		for (const Step &st : m_Program[set]) {
 			if (st.tag != "flow" && st.tag != "pack") run(st);
 		}
-		// (a host frame: its bytes are complete in m_PassOut[i] -- tell the thread that copies them out)
+		if (m_BatchHost[i].yuvOut) {  // the frame's BGRX output (m_PassOut[i]) into the caller's device planes / the staging slot
+			const FrameSize fs = frameSize();
+			launchBgrxToYuv420(m_BatchHost[i].nv12Out, m_BatchIO[i].out, m_BatchIO[i].outStride,
+			    yuvEncodeCoefficients(m_BatchHost[i].csOut), m_BatchHost[i].encode, static_cast<int>(fs.outputWidth),
+			    static_cast<int>(fs.outputHeight), m_Stream);
+		}
+		// (a host frame: its bytes are complete in m_PassOut[i] / m_PassYuvOut[i] -- tell the thread that copies them out)
 		if (m_BatchHost[i].hostOut) launchSignalHost(m_PassSignal.device(), m_Stream);
 	}
 }
 
 // A frame may go into a pass when each of its two images is either a device-resident one the kernels can read / write in
 // place (directEligible's conditions) or a host image of the right size (staged through the pass's own device buffers).
-bool Engine::passEligible(const Frame &in, const Frame &out) const {
+// A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
+bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
 	const FrameSize fs = frameSize();
-	const auto inRow = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
-	const auto outRow = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
-	auto sized = [](const Frame &f, std::size_t w, std::size_t h, std::ptrdiff_t row) {
-		return f.ptr != nullptr && f.width == w && f.height == h && (f.stride >= row || -f.stride >= row);
-	};
-	if (!sized(in, fs.inputWidth, fs.inputHeight, inRow) || !sized(out, fs.outputWidth, fs.outputHeight, outRow)) return false;
-	auto side = [&](const Frame &f, unsigned align) {
+	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align) {
+		if (a.yuv) {
+			const YuvFrame &y = a.planes;
+			return (y.location == Location::Host || y.location == Location::Device) && y.width == w && y.height == h;
+		}
+		const Frame &f = a.bgrx;
+		const auto row = static_cast<std::ptrdiff_t>(w * 4);
+		if (f.ptr == nullptr || f.width != w || f.height != h || !(f.stride >= row || -f.stride >= row)) return false;
 		if (f.location == Location::Host) return true;
 		return f.location == Location::Device && m_PreferDirect && reinterpret_cast<std::uintptr_t>(f.ptr) % align == 0 &&
 		       f.stride % static_cast<std::ptrdiff_t>(align) == 0;
 	};
-	return side(in, 4) && side(out, 8);
+	return side(in, fs.inputWidth, fs.inputHeight, 4) && side(out, fs.outputWidth, fs.outputHeight, 8);
 }
+
+namespace {
+AnyFrame anyOf(const Frame &f) {
+	AnyFrame a;
+	a.bgrx = f;
+	return a;
+}
+std::vector<AnyFrame> anyOf(const Frame *f, int n) {
+	std::vector<AnyFrame> a(static_cast<std::size_t>(std::max(n, 0)));
+	for (int i = 0; i < n; ++i) a[static_cast<std::size_t>(i)].bgrx = f[i];
+	return a;
+}
+}  // namespace
+
+bool Engine::passEligible(const Frame &in, const Frame &out) const { return passEligible(anyOf(in), anyOf(out)); }
 
 // Binds the n frames of a pass: m_BatchIO[i] = what frame i's kernels read and write -- the caller's device memory, or
 // for a host image the pass's device buffer i, addressed with the SIGN of the caller's stride (a bottom-up host frame is
 // uploaded / downloaded in memory order and read / written bottom-up by the kernels: no flip pass).  The key of the
 // pass's graph is made of those bindings, so all-host passes of one length and orientation share one graph.
-std::vector<Engine::DirectKey> Engine::bindBatch(const Frame *in, const Frame *out, int n, int set) {
+//
+// YUV frames in look-ahead passes (processFrames).  A YUV input of frame i is decoded into m_PassIn[i], a YUV output
+// encoded from m_PassOut[i] (top-down BGRX rows both), whatever the planes' location: m_BatchHost[i].decode / .encode
+// are the planes those conversion launches read / write.  Device planes: the caller's, in place.  Host planes: slot i of
+// m_PassYuvIn / m_PassYuvOut, plane after plane with rows padded to stagePitch and in the caller's MEMORY order, so a
+// bottom-up plane is addressed from its last row with a negative pitch -- the layout of stageInYuv / stageOutYuv.
+std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set) {
 	const FrameSize fs = frameSize();
 	const auto inRow = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
 	const auto outRow = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
-	std::vector<DirectKey> key(static_cast<std::size_t>(n));
+	// the planes a conversion launch addresses, and what of them the graph bakes in
+	auto bindPlanes = [](const YuvFrame &y, DeviceBuffer *stage, YuvKey *key) {
+		key->format = static_cast<int>(y.format);
+		key->colorspace = y.colorspace;
+		for (int k = 0; k < planeCount(y.format); ++k) {
+			key->planes[k] = stage ? nullptr : y.planes[k];
+			key->strides[k] = stage ? (y.strides[k] > 0 ? 1 : -1) : y.strides[k];
+		}
+		if (stage == nullptr) return callerPlanes(y);
+		if (!stage->get()) *stage = DeviceBuffer(yuvStageBytes(y.width, y.height));
+		return stagedPlanes(y, stage->as<std::uint8_t>());
+	};
+	std::vector<PassKey> key(static_cast<std::size_t>(n));
 	for (int i = 0; i < n; ++i) {
 		FrameIO &io = m_BatchIO[i];
-		m_BatchHost[i].hostIn = in[i].location == Location::Host;
-		m_BatchHost[i].hostOut = out[i].location == Location::Host;
-		if (m_BatchHost[i].hostIn) {
+		PassFrame &pf = m_BatchHost[i];
+		PassKey &k = key[static_cast<std::size_t>(i)];
+		pf = PassFrame{};
+		if (in[i].yuv) {
+			const YuvFrame &y = in[i].planes;
+			pf.yuvIn = true;
+			pf.hostIn = y.location == Location::Host;
+			pf.nv12In = y.format == PixelFormat::Nv12;
+			pf.csIn = y.colorspace;
 			if (!m_PassIn[i].get()) m_PassIn[i] = DeviceBuffer(fs.inputHeight * static_cast<std::size_t>(inRow));
-			auto *base = m_PassIn[i].as<std::uint8_t>();
-			io.in = in[i].stride >= 0 ? base : base + static_cast<std::ptrdiff_t>(fs.inputHeight - 1) * inRow;
-			io.inStride = in[i].stride >= 0 ? inRow : -inRow;
+			io.in = m_PassIn[i].as<std::uint8_t>();
+			io.inStride = inRow;
+			pf.decode = bindPlanes(y, pf.hostIn ? &m_PassYuvIn[i] : nullptr, &k.in);
 		} else {
-			io.in = static_cast<const std::uint8_t *>(in[i].ptr);
-			io.inStride = in[i].stride;
+			const Frame &f = in[i].bgrx;
+			pf.hostIn = f.location == Location::Host;
+			if (pf.hostIn) {
+				if (!m_PassIn[i].get()) m_PassIn[i] = DeviceBuffer(fs.inputHeight * static_cast<std::size_t>(inRow));
+				auto *base = m_PassIn[i].as<std::uint8_t>();
+				io.in = f.stride >= 0 ? base : base + static_cast<std::ptrdiff_t>(fs.inputHeight - 1) * inRow;
+				io.inStride = f.stride >= 0 ? inRow : -inRow;
+			} else {
+				io.in = static_cast<const std::uint8_t *>(f.ptr);
+				io.inStride = f.stride;
+			}
 		}
-		if (m_BatchHost[i].hostOut) {
+		if (out[i].yuv) {
+			const YuvFrame &y = out[i].planes;
+			pf.yuvOut = true;
+			pf.hostOut = y.location == Location::Host;
+			pf.nv12Out = y.format == PixelFormat::Nv12;
+			pf.csOut = y.colorspace;
 			if (!m_PassOut[i].get()) m_PassOut[i] = DeviceBuffer(fs.outputHeight * static_cast<std::size_t>(outRow));
+			io.out = m_PassOut[i].as<std::uint8_t>();
+			io.outStride = outRow;
+			pf.encode = bindPlanes(y, pf.hostOut ? &m_PassYuvOut[i] : nullptr, &k.out);
+		} else {
+			const Frame &f = out[i].bgrx;
+			pf.hostOut = f.location == Location::Host;
+			if (pf.hostOut) {
+				if (!m_PassOut[i].get()) m_PassOut[i] = DeviceBuffer(fs.outputHeight * static_cast<std::size_t>(outRow));
+				auto *base = m_PassOut[i].as<std::uint8_t>();
+				io.out = f.stride >= 0 ? base : base + static_cast<std::ptrdiff_t>(fs.outputHeight - 1) * outRow;
+				io.outStride = f.stride >= 0 ? outRow : -outRow;
+			} else {
+				io.out = static_cast<std::uint8_t *>(f.ptr);
+				io.outStride = f.stride;
+			}
+		}
+		if (pf.hostOut) {
 			if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
 			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
-			auto *base = m_PassOut[i].as<std::uint8_t>();
-			io.out = out[i].stride >= 0 ? base : base + static_cast<std::ptrdiff_t>(fs.outputHeight - 1) * outRow;
-			io.outStride = out[i].stride >= 0 ? outRow : -outRow;
-		} else {
-			io.out = static_cast<std::uint8_t *>(out[i].ptr);
-			io.outStride = out[i].stride;
 		}
-		key[i] = DirectKey{io.in, io.inStride, io.out, io.outStride, set};
+		k.io = DirectKey{io.in, io.inStride, io.out, io.outStride, set};
 	}
 	return key;
 }
 
 // Every host input of the pass into its device buffer, rows in MEMORY order (the binding carries the orientation), on the
 // engine's stream in front of the pass's launches.  Pageable memory: the runtime stages or page-locks per call, as in
-// stageIn; 0.52 MB per frame.
-void Engine::uploadPassInputs(const Frame *in, int n) {
+// stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in stageInYuv.
+void Engine::uploadPassInputs(const AnyFrame *in, int n) {
 	const FrameSize fs = frameSize();
 	const std::size_t rowBytes = fs.inputWidth * 4, rows = fs.inputHeight;
 	for (int i = 0; i < n; ++i) {
 		if (!m_BatchHost[i].hostIn) continue;
-		const auto *p0 = static_cast<const std::uint8_t *>(in[i].ptr);
-		const std::uint8_t *lowest = in[i].stride >= 0 ? p0 : p0 + static_cast<std::ptrdiff_t>(rows - 1) * in[i].stride;
-		const std::size_t pitch = static_cast<std::size_t>(in[i].stride >= 0 ? in[i].stride : -in[i].stride);
+		if (in[i].yuv) {
+			copyPlanes(in[i].planes, m_PassYuvIn[i].as<std::uint8_t>(), true, m_Stream);
+			continue;
+		}
+		const Frame &f = in[i].bgrx;
+		const auto *p0 = static_cast<const std::uint8_t *>(f.ptr);
+		const std::uint8_t *lowest = f.stride >= 0 ? p0 : p0 + static_cast<std::ptrdiff_t>(rows - 1) * f.stride;
+		const std::size_t pitch = static_cast<std::size_t>(f.stride >= 0 ? f.stride : -f.stride);
 		if (pitch == rowBytes) {
 			JU_HIP(hipMemcpyAsync(m_PassIn[i].get(), lowest, rowBytes * rows, hipMemcpyHostToDevice, m_Stream));
 		} else {
@@ -1938,8 +2027,9 @@ void Engine::uploadPassInputs(const Frame *in, int n) {
 
 // The thread blocked in processBatch: wait for frame i's completion count, copy frame i out on the copy stream while the
 // GPU runs frame i + 1, in order.  The wait is bounded by the pass itself: once the engine's stream has drained, a count
-// that has not arrived never will.
-void Engine::drainPassOutputs(const Frame *out, int n) {
+// that has not arrived never will.  A YUV frame goes out plane by plane from its staging slot (3.1 MB at 1080p instead of
+// BGRX's 8.3 MB), as in stageOutYuv.
+void Engine::drainPassOutputs(const AnyFrame *out, int n) {
 	const FrameSize fs = frameSize();
 	const std::size_t rowBytes = fs.outputWidth * 4, rows = fs.outputHeight;
 	volatile unsigned *word = m_PassSignal.host();
@@ -1961,20 +2051,25 @@ void Engine::drainPassOutputs(const Frame *out, int n) {
 				__builtin_ia32_pause();
 			}
 		}
-		auto *p0 = static_cast<std::uint8_t *>(out[i].ptr);
-		std::uint8_t *lowest = out[i].stride >= 0 ? p0 : p0 + static_cast<std::ptrdiff_t>(rows - 1) * out[i].stride;
-		const std::size_t pitch = static_cast<std::size_t>(out[i].stride >= 0 ? out[i].stride : -out[i].stride);
+		any = true;
+		if (out[i].yuv) {
+			copyPlanes(out[i].planes, m_PassYuvOut[i].as<std::uint8_t>(), false, *m_CopyStream);
+			continue;
+		}
+		const Frame &f = out[i].bgrx;
+		auto *p0 = static_cast<std::uint8_t *>(f.ptr);
+		std::uint8_t *lowest = f.stride >= 0 ? p0 : p0 + static_cast<std::ptrdiff_t>(rows - 1) * f.stride;
+		const std::size_t pitch = static_cast<std::size_t>(f.stride >= 0 ? f.stride : -f.stride);
 		if (pitch == rowBytes) {
 			JU_HIP(hipMemcpyAsync(lowest, m_PassOut[i].get(), rowBytes * rows, hipMemcpyDeviceToHost, *m_CopyStream));
 		} else {
 			JU_HIP(hipMemcpy2DAsync(lowest, pitch, m_PassOut[i].get(), rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, *m_CopyStream));
 		}
-		any = true;
 	}
 	if (any) JU_HIP(hipStreamSynchronize(*m_CopyStream));
 }
 
-Engine::DirectEntry &Engine::batchEntry(const std::vector<DirectKey> &key) {
+Engine::DirectEntry &Engine::batchEntry(const std::vector<PassKey> &key) {
 	auto it = m_BatchGraphs.find(key);
 	if (it == m_BatchGraphs.end()) {
 		// least recently used out -- among the tuples nobody registered: a tuple handed to prepareBatch keeps its graphs
@@ -2008,10 +2103,11 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 		if (!passEligible(in[i], out[i])) return 0;
 	}
 	if (!batchPlanned(n)) return 0;
+	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
 	std::unique_lock<std::mutex> chain = chainBegin();  // (no capture while another engine's constructor drains the device)
 	int captured = 0;
 	for (int set = 0; set < 2; ++set) {
-		DirectEntry &e = batchEntry(bindBatch(in, out, n, set));
+		DirectEntry &e = batchEntry(bindBatch(anyIn.data(), anyOut.data(), n, set));
 		e.registered = true;
 		if (e.graph.valid()) continue;
 		{
@@ -2027,12 +2123,15 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 }
 
 // One look-ahead pass over frames [0, n): enqueue only.  On return the binding set is flipped ONCE (see above).
-void Engine::submitBatch(const Frame *in, const Frame *out, int n) {
+void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	const int set = m_Idx;
-	const std::vector<DirectKey> key = bindBatch(in, out, n, set);
+	const std::vector<PassKey> key = bindBatch(in, out, n, set);
 	uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
 	m_PassSignalBase = m_PassSignal.host() ? *m_PassSignal.host() : 0u;
-	for (int i = 0; i < n; ++i) m_BatchHostFrames += (m_BatchHost[i].hostIn || m_BatchHost[i].hostOut) ? 1 : 0;
+	for (int i = 0; i < n; ++i) {
+		m_BatchHostFrames += (m_BatchHost[i].hostIn || m_BatchHost[i].hostOut) ? 1 : 0;
+		m_BatchYuvFrames += (m_BatchHost[i].yuvIn || m_BatchHost[i].yuvOut) ? 1 : 0;
+	}
 	{
 		std::unique_lock<std::mutex> chain = chainBegin();
 		bool replayed = false;
@@ -2060,41 +2159,107 @@ void Engine::submitBatch(const Frame *in, const Frame *out, int n) {
 	m_BatchFrames += static_cast<std::uint64_t>(n);
 }
 
+namespace {
+std::atomic<int> g_PassRerun{0};
+}  // namespace
+void setPassRerun(int on) { g_PassRerun = on; }
+
 void Engine::processBatch(const Frame *in, const Frame *out, int count) {
 	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("processBatch: bad arguments");
+	const std::vector<AnyFrame> anyIn = anyOf(in, count), anyOut = anyOf(out, count);
+	runPasses(anyIn.data(), anyOut.data(), count);
+}
+
+void Engine::processFrames(const AnyFrame *in, const AnyFrame *out, int count) {
+	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) {
+		throw std::invalid_argument("ju_process_frames: NULL frames or a negative count");
+	}
+	for (int i = 0; i < count; ++i) {
+		try {
+			checkFrame(in[i], true);
+			checkFrame(out[i], false);
+		} catch (const std::invalid_argument &e) {
+			throw std::invalid_argument("ju_process_frames: frame " + std::to_string(i) + ": " + e.what());
+		}
+	}
+	runPasses(in, out, count);
+}
+
+// one frame's launches, enqueue only: submit() for a BGRX pair, submitFrame() where a side is YUV
+void Engine::submitAny(const AnyFrame &in, const AnyFrame &out) {
+	if (!in.yuv && !out.yuv) {
+		submit(in.bgrx, out.bgrx);
+	} else {
+		submitFrame(in, out);
+	}
+}
+
+void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 	DeviceGuard g(m_Device);
+	// the bytes of every plane of a frame (BGRX: its one image), and their address space
+	using Range = std::pair<const std::uint8_t *, const std::uint8_t *>;
+	struct Extent {
+		Range r[3];
+		int planes = 0;
+		Location location = Location::Host;
+	};
+	auto rowsRange = [](const void *ptr, std::ptrdiff_t stride, std::size_t rowCount, std::size_t rowBytes) {
+		const auto rows = static_cast<std::ptrdiff_t>(rowCount);
+		const auto *p0 = static_cast<const std::uint8_t *>(ptr);
+		const std::uint8_t *lo = stride >= 0 ? p0 : p0 + (rows - 1) * stride;
+		const std::size_t bytes = static_cast<std::size_t>(rows - 1) * static_cast<std::size_t>(stride >= 0 ? stride : -stride) + rowBytes;
+		return std::make_pair(lo, lo + bytes);
+	};
+	auto extent = [&](const AnyFrame &a) {
+		Extent e;
+		if (!a.yuv) {
+			e.r[0] = rowsRange(a.bgrx.ptr, a.bgrx.stride, a.bgrx.height, a.bgrx.width * 4);
+			e.planes = 1;
+			e.location = a.bgrx.location;
+			return e;
+		}
+		const YuvFrame &y = a.planes;
+		e.planes = planeCount(y.format);
+		e.location = y.location;
+		for (int k = 0; k < e.planes; ++k) {
+			const PlaneShape p = planeShape(y.format, y.width, y.height, k);
+			e.r[k] = rowsRange(y.planes[k], y.strides[k], p.rows, p.rowBytes);
+		}
+		return e;
+	};
+	auto overlap = [](const Extent &a, const Extent &b) {
+		if (a.location != b.location) return false;  // (host and device addresses are different spaces)
+		for (int i = 0; i < a.planes; ++i) {
+			for (int j = 0; j < b.planes; ++j) {
+				if (a.r[i].first < b.r[j].second && b.r[j].first < a.r[i].second) return true;
+			}
+		}
+		return false;
+	};
 	int i = 0;
 	while (i < count) {
-		// the longest run of frames from i that can go as one pass: device-resident, and none of them READING what an
-		// earlier frame of the pass writes (frame by frame such an input would be read after that write; the pass's flow
-		// sweep reads every input first)
-		auto range = [](const Frame &f) {
-			const auto rows = static_cast<std::ptrdiff_t>(f.height);
-			const auto *p0 = static_cast<const std::uint8_t *>(f.ptr);
-			const std::uint8_t *lo = f.stride >= 0 ? p0 : p0 + (rows - 1) * f.stride;
-			const std::size_t bytes = static_cast<std::size_t>(rows - 1) * static_cast<std::size_t>(f.stride >= 0 ? f.stride : -f.stride) + f.width * 4;
-			return std::make_pair(lo, lo + bytes);
-		};
+		// the longest run of frames from i that can go as one pass: none of them READING what an earlier frame of the
+		// pass writes (frame by frame such an input would be read after that write; the pass's flow sweep and its YUV
+		// decode read every input first)
 		// ... nor WRITING what an earlier frame of the pass reads: on the normal path that write comes after the read
 		// (frame k's tail after frame j's, j < k), but a pass whose resident tower timed out is run again frame by frame
-		// from its inputs, which must then still be what they were (advisor, round 5)
-		auto overlap = [](const std::pair<const std::uint8_t *, const std::uint8_t *> &a,
-		                  const std::pair<const std::uint8_t *, const std::uint8_t *> &b) {
-			return a.first < b.second && b.first < a.second;
-		};
+		// from its inputs, which must then still be what they were (advisor, round 5).  Every plane of a YUV frame counts.
+		Extent reads[kFlowBatchMax], writes[kFlowBatchMax];
 		int n = 0;
 		while (i + n < count && n < m_BatchMax && passEligible(in[i + n], out[i + n])) {
-			const auto r = range(in[i + n]), w = range(out[i + n]);
+			reads[n] = extent(in[i + n]);
+			writes[n] = extent(out[i + n]);
 			bool clash = false;
-			for (int k = 0; k < n && !clash; ++k) {  // (host and device addresses are different spaces)
-				clash = (in[i + n].location == out[i + k].location && overlap(r, range(out[i + k]))) ||
-				        (out[i + n].location == in[i + k].location && overlap(w, range(in[i + k])));
-			}
+			for (int k = 0; k < n && !clash; ++k) clash = overlap(reads[n], writes[k]) || overlap(writes[n], reads[k]);
 			if (clash) break;
 			++n;
 		}
 		if (n < 2 || !batchPlanned(n)) {
-			process(in[i], out[i]);
+			if (!in[i].yuv && !out[i].yuv) {
+				process(in[i].bgrx, out[i].bgrx);
+			} else {
+				runSynchronous([&] { submitFrame(in[i], out[i]); });
+			}
 			++i;
 			continue;
 		}
@@ -2102,16 +2267,24 @@ void Engine::processBatch(const Frame *in, const Frame *out, int count) {
 		submitBatch(in + i, out + i, n);
 		drainPassOutputs(out + i, n);  // host frames: each copied out while the next one runs
 		m_Stream.synchronizeSpin(m_SpinUs);
-		if (const unsigned code = takeResidentError()) {
+		const unsigned code = takeResidentError();
+		if (code || g_PassRerun.load(std::memory_order_relaxed)) {
 			// nothing the pass wrote was one of its inputs -- neither the state (see above) nor a frame buffer (the pass
 			// splitter): the same frames again, one by one, on the per-block kernels
 			m_Idx = set;
 			m_BatchFrames -= static_cast<std::uint64_t>(n);
-			for (int k = 0; k < n; ++k) m_BatchHostFrames -= (m_BatchHost[k].hostIn || m_BatchHost[k].hostOut) ? 1 : 0;
-			fallbackToLayers(code);
 			for (int k = 0; k < n; ++k) {
-				submit(in[i + k], out[i + k]);
-				m_Stream.synchronize();
+				m_BatchHostFrames -= (m_BatchHost[k].hostIn || m_BatchHost[k].hostOut) ? 1 : 0;
+				m_BatchYuvFrames -= (m_BatchHost[k].yuvIn || m_BatchHost[k].yuvOut) ? 1 : 0;
+			}
+			if (code) fallbackToLayers(code);
+			for (int k = 0; k < n; ++k) {
+				if (code) {
+					submitAny(in[i + k], out[i + k]);
+					m_Stream.synchronize();
+				} else {  // (the debug switch: the pass was sound, the resident tower still runs and may report)
+					runSynchronous([&] { submitAny(in[i + k], out[i + k]); });
+				}
 			}
 		} else {
 			for (int k = 0; k < n; ++k) maybeRestoreResident();
@@ -2224,8 +2397,9 @@ void Engine::processGroup(Engine *const *members, const Frame *in, const Frame *
 void Engine::runGroupPass(Engine &L, Engine *const *m, const Frame *in, const Frame *out, int n) {
 	int sets[kFlowBatchMax];
 	for (int i = 0; i < n; ++i) sets[i] = m[i]->m_Idx;
-	L.bindBatch(in, out, n, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
-	L.uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
+	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
+	L.bindBatch(anyIn.data(), anyOut.data(), n, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
+	L.uploadPassInputs(anyIn.data(), n);  // (outside the chain lock: a pageable upload blocks its caller)
 	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
 	// 1. work a member has pending on its own stream (ju_enqueue) runs first
 	for (int i = 0; i < n; ++i) {
@@ -2286,7 +2460,7 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const Frame *in, const Fr
 	for (int i = 0; i < n; ++i) {
 		if (m[i] != &L) JU_HIP(hipStreamWaitEvent(m[i]->m_Stream, L.m_GroupEvent.get(), 0));
 	}
-	L.drainPassOutputs(out, n);  // host frames: each copied out while the next member runs
+	L.drainPassOutputs(anyOut.data(), n);  // host frames: each copied out while the next member runs
 	L.m_Stream.synchronizeSpin(L.m_SpinUs);
 	// one synchronisation; then every member's resident-tower error word
 	unsigned codes[kFlowBatchMax];
@@ -2671,6 +2845,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "fallbacks") return static_cast<double>(m_Fallbacks);
 	if (key == "lookahead_frames") return static_cast<double>(m_BatchFrames);  // frames that went through look-ahead passes
 	if (key == "lookahead_host_frames") return static_cast<double>(m_BatchHostFrames);  // ... of them with a host image
+	if (key == "lookahead_yuv_frames") return static_cast<double>(m_BatchYuvFrames);  // ... of them with a YUV side
 	if (key == "lookahead_max") return static_cast<double>(m_BatchMax);
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
 	if (key == "launches_per_frame") return static_cast<double>(m_Program[0].size());

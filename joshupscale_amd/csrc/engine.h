@@ -65,6 +65,10 @@ struct FrameSize {
 	std::size_t inputWidth, inputHeight, outputWidth, outputHeight;
 };
 
+// Test flavour only (ju_debug_set "pass_rerun"): a look-ahead pass that completed normally is treated as one that must
+// be run again -- binding set and counters restored, its frames one by one, without the fallback to the per-block kernels.
+void setPassRerun(int on);
+
 class Engine {
 public:
 	// dtypeOverride: -1 = the container's hint, else kF16 / kBF16.
@@ -101,6 +105,12 @@ public:
 	// frames are checked before anything is launched.  BGRX-only pairs go through process() / enqueue() instead.
 	void processFrame(const AnyFrame &in, const AnyFrame &out);
 	void enqueueFrame(const AnyFrame &in, const AnyFrame &out);
+	// processBatch for frames of any format (ju_process_frames): the bytes and the state of processFrame / process called
+	// frame by frame in order.  EVERY pair is checked before anything is launched or uploaded (std::invalid_argument names
+	// the frame; runtime and state as they were).  YUV sides ride in the passes: the pass's YUV inputs are decoded by one
+	// launch in front of the flow net's, each YUV output is encoded behind its frame's tail (engine.cpp, "YUV frames in
+	// look-ahead passes").
+	void processFrames(const AnyFrame *in, const AnyFrame *out, int count);
 	// Registers a pair of device-resident frame buffers the caller is going to hand to
 	// process() / enqueue(): the per-frame graphs of the pair (one per binding set) are
 	// captured NOW, so that no later call pays a capture -- the reference captures its graphs
@@ -348,12 +358,31 @@ private:
 	// m_BatchCap frames, the state buffers between the frames of a pass, the flow launches per (frames, binding set)
 	// and the graphs per tuple of frame buffers
 	FrameIO m_BatchIO[kFlowBatchMax];
+	// The key of a pass's graph: per frame, everything a launch of the pass bakes in.  `io`: what the frame's kernels read
+	// and write (bindBatch).  A YUV side adds its format and colour space and, for device planes, their pointers and
+	// strides; for host planes (staged in the pass's own buffers) only the sign of each stride -- all-host passes of one
+	// shape share one graph whatever the caller's addresses.  BGRX sides leave their YuvKey zero.
+	struct YuvKey {
+		int format = 0, colorspace = 0;
+		const void *planes[3] = {};
+		std::ptrdiff_t strides[3] = {};
+		auto tie() const { return std::tie(format, colorspace, planes[0], planes[1], planes[2], strides[0], strides[1], strides[2]); }
+	};
+	struct PassKey {
+		DirectKey io;
+		YuvKey in, out;
+		bool operator<(const PassKey &o) const {
+			if (io < o.io) return true;
+			if (o.io < io) return false;
+			return std::make_tuple(in.tie(), out.tie()) < std::make_tuple(o.in.tie(), o.out.tie());
+		}
+	};
 	std::map<std::string, Tensor> m_BatchTensors;
 	DeviceBuffer m_BatchState[kFlowBatchMax - 1];
 	int m_BatchCap = 0, m_BatchMax = kFlowBatchMax;
 	bool m_BatchUnsupported = false;
 	std::map<std::pair<int, int>, std::vector<Step>> m_BatchFlow;
-	std::map<std::vector<DirectKey>, DirectEntry> m_BatchGraphs;
+	std::map<std::vector<PassKey>, DirectEntry> m_BatchGraphs;
 	// Host frames inside look-ahead passes (round 6; the AviSynth caller's frames, avisynth_plugin/src/main.cc:113-144, and
 	// the only path the reference's own timer measures, scripts/inference/tensorrt/inference.py:245-251).  Frame by frame
 	// the 8.3 MB of an output cross the PCIe link while the GPU idles -- the frame's rows all appear in its last
@@ -363,29 +392,41 @@ private:
 	// blocked in processBatch copies frame i out on a second stream (SDMA, no CU) while frame i + 1 runs: only the last
 	// frame's copy is exposed.  The copies go from / to the caller's pageable rows through the HIP runtime as in
 	// stageIn / stageOut (cuda_convert.cc.cu:360-459); nothing of the caller's is page-locked (section 7 of DESIGN.md).
+	// YUV sides: the frame's kernels read / write BGRX in m_PassIn[i] / m_PassOut[i] whatever the side's location;
+	// `decode` / `encode` are the planes the conversion launches of the pass read / write -- the caller's device planes, or
+	// for host planes slot i of m_PassYuvIn / m_PassYuvOut (rows padded to stagePitch, in the caller's memory order).
 	struct PassFrame {
 		bool hostIn = false, hostOut = false;
+		bool yuvIn = false, yuvOut = false;
+		bool nv12In = false, nv12Out = false;
+		int csIn = 0, csOut = 0;
+		YuvPlanes decode, encode;
 	};
 	PassFrame m_BatchHost[kFlowBatchMax];
 	DeviceBuffer m_PassIn[kFlowBatchMax], m_PassOut[kFlowBatchMax];
+	DeviceBuffer m_PassYuvIn[kFlowBatchMax], m_PassYuvOut[kFlowBatchMax];
 	std::unique_ptr<Stream> m_CopyStream;
 	PinnedWords m_PassSignal;
 	unsigned m_PassSignalBase = 0;
-	std::uint64_t m_BatchHostFrames = 0;
+	std::uint64_t m_BatchHostFrames = 0, m_BatchYuvFrames = 0;
+	bool passEligible(const AnyFrame &in, const AnyFrame &out) const;
 	bool passEligible(const Frame &in, const Frame &out) const;
-	void uploadPassInputs(const Frame *in, int n);
-	void drainPassOutputs(const Frame *out, int n);
+	void uploadPassInputs(const AnyFrame *in, int n);
+	void drainPassOutputs(const AnyFrame *out, int n);
+	// the passes of processBatch / processFrames over checked frames
+	void runPasses(const AnyFrame *in, const AnyFrame *out, int count);
+	void submitAny(const AnyFrame &in, const AnyFrame &out);
 	static constexpr std::size_t kMaxBatchGraphs = 64;          // unregistered tuples (LRU)
 	static constexpr std::size_t kMaxRegisteredBatches = 256;   // tuples registered through prepareBatch
 	std::uint64_t m_BatchFrames = 0;
 	// group: the flow launches of a group pass over `items` streams (processGroup), in m_BatchFlow at {items, kGroupSet}
 	bool batchPlanned(int items, bool group = false);
 	static constexpr int kGroupSet = 2;
-	void submitBatch(const Frame *in, const Frame *out, int n);
+	void submitBatch(const AnyFrame *in, const AnyFrame *out, int n);
 	void runBatch(int set, int n, const std::function<void(const Step &, bool)> *around = nullptr);
 	void dropBatchGraphs();
-	std::vector<DirectKey> bindBatch(const Frame *in, const Frame *out, int n, int set);
-	DirectEntry &batchEntry(const std::vector<DirectKey> &key);
+	std::vector<PassKey> bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set);
+	DirectEntry &batchEntry(const std::vector<PassKey> &key);
 	// Group passes (processGroup).  The model's identity: FNV-1a of the container bytes the engine was built from, and
 	// the dtype it was asked for.  As the lead of a pass: the history each item's first flow block reads / writes (read
 	// at launch time).  As a member: an event its stream records for the lead to wait on, and the frames it got from

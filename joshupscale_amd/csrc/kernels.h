@@ -439,6 +439,20 @@ void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std
     std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
 void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
     const YuvPlanes &dst, int width, int height, hipStream_t stream);
+// The YUV inputs of a look-ahead pass (Engine::processFrames), decoded in one launch: item i of `count` (1 ..
+// kFlowBatchMax) = planes, coefficients and BGRX destination of one frame; all frames width x height.  Per item the
+// bytes of launchYuv420ToBgrx.  The struct is the launch's by-value argument (768 bytes).
+struct YuvDecodeItem {
+	YuvPlanes src;
+	YuvDecode k;
+	std::uint8_t *dst = nullptr;
+	std::ptrdiff_t dstStride = 0;
+	int nv12 = 0;
+};
+struct YuvDecodeItems {
+	YuvDecodeItem item[kFlowBatchMax];
+};
+void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream);
 
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).

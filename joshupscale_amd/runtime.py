@@ -98,6 +98,7 @@ _PRODUCT_SIGS = {
     "ju_synchronize": (C.c_int, [C.c_void_p]),
     "ju_prepare_frames": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage), _P(C.c_int)]),
     "ju_process_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
+    "ju_process_frames": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame), C.c_int]),
     "ju_enqueue_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
     "ju_get_size": (C.c_int, [C.c_void_p] + [_P(C.c_size_t)] * 4),
     "ju_reset": (C.c_int, [C.c_void_p]),
@@ -123,6 +124,8 @@ _HOOK_SIGS = {
     "ju_debug_e4m3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "ju_debug_yuv": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_yuv_items": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_size_t, C.c_size_t, _P(C.c_void_p),
+                                     _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
@@ -296,6 +299,17 @@ class Runtime:
         """``ju_process_frame``: one step on frames of any format (synchronous)."""
         _check(self._lib, self._lib.ju_process_frame(self._h, C.byref(inp), C.byref(out)))
 
+    def process_frames(self, inputs, outputs) -> None:
+        """``ju_process_frames``: consecutive frames of the stream, of any format, in one synchronous call (frame
+        look-ahead -- every input must hold its pixels now); the bytes of ``process_frame`` called frame by frame.
+        Lists of unequal length raise before any native call."""
+        inputs, outputs = list(inputs), list(outputs)
+        n = len(inputs)
+        if len(outputs) != n:
+            raise ValueError("process_frames: as many outputs as inputs")
+        ins, outs = (JuFrame * n)(*inputs), (JuFrame * n)(*outputs)
+        _check(self._lib, self._lib.ju_process_frames(self._h, ins, outs, n))
+
     def enqueue_frame(self, inp: JuFrame, out: JuFrame) -> None:
         """``ju_enqueue_frame``: device frames only; ``synchronize`` waits."""
         _check(self._lib, self._lib.ju_enqueue_frame(self._h, C.byref(inp), C.byref(out)))
@@ -341,7 +355,8 @@ class Runtime:
 
     def stat(self, key: str) -> float:
         """``ju_get_stat``: "graph_replays", "eager_runs", "direct_graphs",
-        "resident_tower", "resident_flow", "launches_per_frame", "recurrent"."""
+        "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "lookahead_frames",
+        "lookahead_host_frames", "lookahead_yuv_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -3,7 +3,13 @@
 Every variant goes through the same runtime in turn (interleaved rounds of --frames-per-round frames), each call
 synchronous (ju_process_frame / ju_process), so that the clock and the other work on the machine are shared alike.
 Prints one JSON line.  --kernels instead runs the two conversion kernels alone at --kernel-size (default 1920x1080)
-through ju_debug_yuv, for a `rocprofv3 --kernel-trace --stats` run (the test flavour of the library is needed)."""
+through ju_debug_yuv, for a `rocprofv3 --kernel-trace --stats` run (the test flavour of the library is needed).
+
+--passes N adds the look-ahead variants, N frames per call: nv12_host_pass, i420_host_pass, nv12_device_pass
+(ju_process_frames) and bgrx_host_pass, bgrx_device_pass (ju_process_batch), interleaved with the per-call variants in
+the same process; --runs repeats the whole measurement, and the result also goes to --out
+(profiles/yuv_pass_bench.json); --only limits the variants (a `rocprofv3 --kernel-trace --memory-copy-trace` run).  --kernels --items K: K frames at --kernel-size through ONE launch of the pass's decode
+kernel (ju_debug_yuv_items) and through K launches of the single-frame kernel, for the same kind of trace."""
 
 import argparse
 import ctypes as C
@@ -50,7 +56,7 @@ def frame_bench(args):
     h, w = cfg.frame_height, cfg.frame_width
     cs = R.CS_BT709_LIMITED
     clip = M.synthetic_frames(8, h, w, seed=1234, kind="smooth")
-    variants = {}
+    variants, passes = {}, {}
     keep = []
     rt = R.Runtime(blob, 0, {"bf16": R.DTYPE_BF16, "fp16": R.DTYPE_F16, "fp8": R.DTYPE_FP8}[args.dtype], hooks=False)
     for name, fmt in FORMATS.items():
@@ -73,34 +79,75 @@ def frame_bench(args):
                     rt.prepare_frames(R.JuImage(a.planes[0], R.LOC_DEVICE, a.strides[0], w, h),
                                       R.JuImage(b.planes[0], R.LOC_DEVICE, b.strides[0], 4 * w, 4 * h))
             variants[f"{name}_{loc}"] = [(C.byref(a), C.byref(b)) for a, b in pairs]
+            n = args.passes
+            if n > 1 and (name, loc) != ("i420", "device"):
+                # the same buffers, n consecutive ones per call (the clip's 8 buffers as a ring)
+                ring = [pairs[i % len(pairs)] for i in range(max(n, len(pairs)))]
+                calls = []
+                for at in range(0, len(ring) - n + 1, n):
+                    chunk = ring[at:at + n]
+                    if fmt == R.FMT_BGRX:
+                        img = lambda f: R.JuImage(f.planes[0], f.location, f.strides[0], f.width, f.height)
+                        calls.append(((R.JuImage * n)(*[img(a) for a, _ in chunk]), (R.JuImage * n)(*[img(b) for _, b in chunk])))
+                    else:
+                        calls.append(((R.JuFrame * n)(*[a for a, _ in chunk]), (R.JuFrame * n)(*[b for _, b in chunk])))
+                passes[f"{name}_{loc}_pass"] = (rt._lib.ju_process_batch if fmt == R.FMT_BGRX else rt._lib.ju_process_frames, calls)
     torch.cuda.synchronize()
     lib, handle = rt._lib, rt._h
     call = lib.ju_process_frame
-    for name, refs in variants.items():         # warm-up: every variant, every buffer
-        for _ in range(args.warmup):
-            for a, b in refs:
+
+    def run(name, count):
+        """`count` frames of a variant; returns the frames actually run (whole calls)"""
+        if name in variants:
+            refs = variants[name]
+            for i in range(count):
+                a, b = refs[i % len(refs)]
                 if call(handle, a, b) != 0:
                     raise RuntimeError(lib.ju_last_error().decode())
-    times = {k: 0.0 for k in variants}
-    frames = {k: 0 for k in variants}
-    for _ in range(args.rounds):
-        for name, refs in variants.items():
-            n = args.frames_per_round
-            t0 = time.perf_counter()
-            for i in range(n):
-                a, b = refs[i % len(refs)]
-                call(handle, a, b)
-            times[name] += time.perf_counter() - t0
-            frames[name] += n
+            return count
+        fn, calls = passes[name]
+        done = 0
+        for i in range(max(1, count // args.passes)):
+            a, b = calls[i % len(calls)]
+            if fn(handle, a, b, args.passes) != 0:
+                raise RuntimeError(lib.ju_last_error().decode())
+            done += args.passes
+        return done
+
+    names = list(variants) + list(passes)
+    if args.only:
+        names = [k for k in names if k in args.only.split(",")]
+    for name in names:                          # warm-up: every variant, every buffer
+        run(name, args.warmup * len(clip))
+    runs = []
+    for _ in range(args.runs):
+        times = {k: 0.0 for k in names}
+        frames = {k: 0 for k in names}
+        for _ in range(args.rounds):
+            for name in names:
+                t0 = time.perf_counter()
+                frames[name] += run(name, args.frames_per_round)
+                times[name] += time.perf_counter() - t0
+        runs.append({k: round(frames[k] / times[k], 1) for k in names})
+    stats = {k: rt.stat(k) for k in ("lookahead_frames", "lookahead_host_frames", "lookahead_yuv_frames", "graph_captures",
+                                     "fallbacks")}
     err = lib.ju_last_error().decode()
     rt.close()
-    fps = {k: round(frames[k] / times[k], 1) for k in variants}
+    fps = runs[0]
     bytes_per_frame = {name: int(sum(p.nbytes for p in planes_for(fmt, h, w, clip[0], cs)) +
                                  sum(p.nbytes for p in empty_planes(fmt, 4 * h, 4 * w)))
                        for name, fmt in FORMATS.items()}
-    print(json.dumps({"metric": "ju_process_frame per-call frames/s", "preset": args.preset, "dtype": args.dtype,
-                      "size": f"{w}x{h}", "frames_per_variant": frames[next(iter(frames))], "fps": fps,
-                      "host_bytes_per_frame": bytes_per_frame, "last_error": err}))
+    res = {"metric": "ju_process_frame per-call frames/s", "preset": args.preset, "dtype": args.dtype,
+           "size": f"{w}x{h}", "frames_per_variant": frames[next(iter(frames))], "fps": fps,
+           "host_bytes_per_frame": bytes_per_frame, "last_error": err}
+    if passes:
+        res.update({"metric": "frames/s per call (ju_process_frame) and per look-ahead pass (*_pass)",
+                    "frames_per_pass": args.passes, "runs": runs, "stats": stats})
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    print(json.dumps(res))
 
 
 def kernel_bench(args):
@@ -129,6 +176,33 @@ def kernel_bench(args):
                       "size": f"{w}x{h}", "iters": args.iters, **res}))
 
 
+def items_bench(args):
+    """K frames at args.kernel_size: one launch of the pass's decode kernel, then K launches of the single-frame one."""
+    dev = torch.device("cuda", 0)
+    w, h = (int(x) for x in args.kernel_size.split("x"))
+    k = args.items
+    lib = R.load_library(True)
+    rng = np.random.default_rng(0)
+    outs = [torch.zeros((h, w, 4), dtype=torch.uint8, device=dev) for _ in range(k)]
+    planes = [[torch.from_numpy(rng.integers(0, 256, p.shape, dtype=np.uint8)).to(dev) for p in empty_planes(R.FMT_NV12, h, w)]
+              for _ in range(k)]
+    ptrs = (C.c_void_p * (3 * k))(*[q for pl in planes for q in (pl[0].data_ptr(), pl[1].data_ptr(), None)])
+    strides = (C.c_ssize_t * (3 * k))(*[q for _ in planes for q in (w, w, 0)])
+    fmts, css = (C.c_int * k)(*[R.FMT_NV12] * k), (C.c_int * k)(*[R.CS_BT709_LIMITED] * k)
+    dst, dst_strides = (C.c_void_p * k)(*[o.data_ptr() for o in outs]), (C.c_ssize_t * k)(*[4 * w] * k)
+    torch.cuda.synchronize()
+    for _ in range(args.iters):
+        if lib.ju_debug_yuv_items(k, fmts, css, w, h, dst, dst_strides, ptrs, strides) != 0:
+            raise RuntimeError(lib.ju_last_error().decode())
+        for i in range(k):
+            one = (C.c_void_p * 3)(planes[i][0].data_ptr(), planes[i][1].data_ptr(), None)
+            one_strides = (C.c_ssize_t * 3)(w, w, 0)
+            if lib.ju_debug_yuv(0, R.FMT_NV12, R.CS_BT709_LIMITED, w, h, outs[i].data_ptr(), 4 * w, one, one_strides) != 0:
+                raise RuntimeError(lib.ju_last_error().decode())
+    print(json.dumps({"metric": "decode launches for a kernel trace", "size": f"{w}x{h}", "items": k, "iters": args.iters,
+                      "launches": {"yuv420_to_bgrx_items_kernel": args.iters, "yuv420_to_bgrx_kernel": args.iters * k}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--preset", default="psp-quality", choices=sorted(M.PRESETS))
@@ -139,8 +213,15 @@ def main():
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--kernel-size", default="1920x1080")
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--passes", type=int, default=0, help="frames per look-ahead call (2..8) of the *_pass variants; 0: none")
+    ap.add_argument("--runs", type=int, default=1, help="repeat the whole interleaved measurement")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "yuv_pass_bench.json"))
+    ap.add_argument("--only", default="", help="comma-separated variants to run (for a trace), e.g. nv12_host_pass")
+    ap.add_argument("--items", type=int, default=0, help="with --kernels: the pass's decode kernel over this many frames")
     args = ap.parse_args()
-    if args.kernels:
+    if args.kernels and args.items:
+        items_bench(args)
+    elif args.kernels:
         kernel_bench(args)
     else:
         frame_bench(args)
