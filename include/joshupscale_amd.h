@@ -303,7 +303,11 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * "lookahead_frames" (frames that went through look-ahead passes; of them "lookahead_host_frames" with a host side,
  * "lookahead_yuv_frames" with a YUV side),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,
- * flow_arch "none" of the container -- every frame is upscaled on its own, ju_reset does nothing). */
+ * flow_arch "none" of the container -- every frame is upscaled on its own, ju_reset does nothing),
+ * "output_select" (0: the frames are the generator's; 1: an output_flow model, header word 140 of the container --
+ * every frame is pre_warp, the previous output warped by the flow field, while state and history advance exactly as
+ * in the plain model.  The model file decides it.  There is no setter: every per-frame program and every captured
+ * graph is built from the model at creation, and a switch would have to forget all of them). */
 JU_API int ju_get_stat(const ju_runtime *runtime, const char *key, double *value);
 
 /* Library version string, e.g. "joshupscale-amd 0.1 (gfx950)". */

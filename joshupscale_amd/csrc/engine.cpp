@@ -558,6 +558,15 @@ void Engine::buildProgram(int set) {
 	// warp and tail kernels (models.py:772-779, 802-803, 809-810) -- in a flow-free model the flag touches
 	// nothing: it shifts only the flow input, pre_warp and the fed-back state, none of which exists
 	const unsigned *sums = c.normalizeBrightness && c.recurrent() ? m_TailB2.as<unsigned>() + 4 : nullptr;
+	// The u8 frame the generator's writers produce (the fused tail of the resident tower, the tails, the temporal
+	// filter): the caller's frame -- or, in the output_flow variant (outputSelect pre_warp), a scratch frame
+	// nobody reads: there the warp step writes the caller's frame, and everything the generator does for the state
+	// stays exactly the plain model's.  The tower kernels are not edited for it; the price is their 4H x 4W x 4
+	// store into the scratch.  Read at launch (capture) time, like io.
+	std::uint8_t *const discard = c.outputsPreWarp() ? m_DiscardFrame.as<std::uint8_t>() : nullptr;
+	const std::ptrdiff_t discardStride = static_cast<std::ptrdiff_t>(W) * 16;
+	auto genOutU8 = [=] { return discard ? discard : io->out; };
+	auto genOutStride = [=] { return discard ? discardStride : io->outStride; };
 	if (!c.recurrent()) {
 		// ---- flow-free model (remove_flow.py): no flow net, no warp, no frame history -- ONE staging
 		// launch writes the LR frame into the generator input, then the generator as below ----
@@ -671,8 +680,9 @@ void Engine::buildProgram(int set) {
 		const int genPitch = genInOp.pitch;
 		void *preWarp = c.temporalStrength > 0.0f ? T("pre_warp") : nullptr;
 		prog.push_back({"warp", 0.0, [=](hipStream_t s) {
+			                // (output_flow variant: this launch also writes the caller's frame, from the record it stores)
 			                launchWarpPack(dt, sb->in, *flowSlot, io->in, io->inStride, genIn, genPitch, H, W, PW,
-			                    padTop, padLeft, sums, preWarp, s);
+			                    padTop, padLeft, sums, preWarp, discard ? io->out : nullptr, discard ? io->outStride : 0, s);
 		                }});
 	}
 	// ---- generator ----
@@ -786,8 +796,8 @@ void Engine::buildProgram(int set) {
 				    t.state = sb->out;
 				    t.frame = io->in;
 				    t.frameStride = io->inStride;
-				    t.outU8 = io->out;
-				    t.outStride = io->outStride;
+				    t.outU8 = genOutU8();
+				    t.outStride = genOutStride();
 				    launchTailFused(dt, t, s);
 				    return;
 			    }
@@ -795,8 +805,8 @@ void Engine::buildProgram(int set) {
 				    r.state = sb->out;
 				    r.frame = io->in;
 				    r.frameStride = io->inStride;
-				    r.outU8 = io->out;
-				    r.outStride = io->outStride;
+				    r.outU8 = genOutU8();
+				    r.outStride = genOutStride();
 			    }
 			    launchResidentTower(dt, r, s);
 		    }});
@@ -897,8 +907,8 @@ void Engine::buildProgram(int set) {
 			                t.state = sb->out;
 			                t.frame = io->in;
 			                t.frameStride = io->inStride;
-			                t.outU8 = io->out;
-			                t.outStride = io->outStride;
+			                t.outU8 = genOutU8();
+			                t.outStride = genOutStride();
 			                launchTailFused(dt, t, s);
 		                }});
 	} else {
@@ -908,8 +918,8 @@ void Engine::buildProgram(int set) {
 		const float *w2 = m_TailW2.as<float>();
 		const float *b2 = m_TailB2.as<float>();
 		prog.push_back({"tail", 2.0 * (2 * H) * (2 * W) * 4 * 32 * 3, [=](hipStream_t s) {
-			                launchTail(dt, y, w2, b2, io->in, io->inStride, sb->out, io->out,
-			                    io->outStride, H, W, sums, s);
+			                launchTail(dt, y, w2, b2, io->in, io->inStride, sb->out, genOutU8(),
+			                    genOutStride(), H, W, sums, s);
 		                }});
 	}
 	// ---- optional output filter (frame_moving_avg.py): replaces the clip output for
@@ -920,7 +930,7 @@ void Engine::buildProgram(int set) {
 		const TemporalParams tp{c.temporalStrength, c.temporalThreshold, c.temporalGain, c.temporalWindow,
 		    c.temporalL2 ? 1 : 0, c.temporalLimit ? 1 : 0, c.temporalLuma ? 1 : 0};
 		prog.push_back({"temporal", 0.0, [=](hipStream_t s) {
-			                launchTemporalFilter(sb->out, preWarp, io->out, io->outStride, H, W, sums,
+			                launchTemporalFilter(sb->out, preWarp, genOutU8(), genOutStride(), H, W, sums,
 			                    acc, tp, s);
 		                }});
 	}
@@ -1032,6 +1042,7 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 	m_InStage = DeviceBuffer(lr * 4);
 	m_OutStage = DeviceBuffer(lr * 16 * 4);
 	m_RawStage = DeviceBuffer(lr * 16 * 4);
+	if (c.outputsPreWarp()) m_DiscardFrame = DeviceBuffer(lr * 16 * 4);  // (buildProgram: where the generator's frame goes)
 	// host YUV frames (ju_process_frame): their planes, rows padded to 64 bytes
 	m_YuvInStage = DeviceBuffer(yuvStageBytes(W, H));
 	m_YuvOutStage = DeviceBuffer(yuvStageBytes(4 * W, 4 * H));
@@ -2836,6 +2847,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "prepared_captures") return static_cast<double>(m_PreparedCaptures);
 	if (key == "registered_pairs") return static_cast<double>(m_RegisteredPairs.size());
 	if (key == "recurrent") return m_Config.recurrent() ? 1.0 : 0.0;  // 0: a flow-free model (stateless)
+	if (key == "output_select") return static_cast<double>(m_Config.outputSelect);  // 1: the output_flow variant (pre_warp)
 	if (key == "resident_tower") return m_Resident ? 1.0 : 0.0;
 	if (key == "resident_flow") return m_ResidentFlow ? 1.0 : 0.0;
 	if (key == "tower_fast") {  // the generator's resident tower runs the fast schedule (16-bit models, every region of its shape)

@@ -286,6 +286,8 @@ private:
 	bool m_FusedTail = true;  // JU_TAIL=split: convT1 as a conv launch + the VALU tail kernel
 	bool m_TailInTower = false;  // JU_TAIL=tower: the fused tail runs inside the resident tower launch
 	DeviceBuffer m_InStage, m_OutStage, m_RawStage;
+	// output_flow variant only: the u8 frame of the generator's writers, which nobody reads (buildProgram)
+	DeviceBuffer m_DiscardFrame;
 	DeviceBuffer m_State[2], m_Packed[2];
 	// resident tower (one launch for all residual-block convolutions)
 	bool m_Resident = false;

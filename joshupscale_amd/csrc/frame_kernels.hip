@@ -182,11 +182,31 @@ __global__ __launch_bounds__(256) void upsample2_kernel(
 // channels plus 4 spare slots = one 32-byte quarter of the pixel's 128-byte
 // generator-input record.  Four consecutive lanes fill one record, a wavefront
 // writes 2 KiB contiguously.
-template <typename T>
+//
+// kEmitU8 (the output_flow model variant, scripts/inference/onnx/output_flow.py): the thread's four warped
+// pixels are also the 16-byte run of BGRX row 4h+i, columns 4w .. 4w+3, of the caller's frame -- a wavefront
+// (16 LR pixels x 4 rows) writes 256 contiguous bytes on each of its four rows.  A byte is
+//   trunc(clamp((v + 0.5f) * 255.0f, 0, 255)),  v = the slot AS STORED in the record (type T), widened to f32,
+// X = 0: the tails' post-process function on what the generator reads, plus a clamp -- with
+// normalize_brightness pre_warp = warp(state) + b leaves +-0.5 when the brightness jumps between frames, and
+// the reference's cast of such a float is undefined.  A compile-time flag: the plain instantiations carry
+// neither the parameters' loads nor the stores.
+struct NoFrameOut {};
+struct FrameOut {
+	std::uint8_t *ptr;      // row 0 of the BGRX frame; 4-byte aligned, any signed stride that is a multiple of 4
+	std::ptrdiff_t stride;
+};
+
+__device__ __forceinline__ unsigned preWarpByte(float v) {
+	return static_cast<unsigned>(fminf(fmaxf((v + 0.5f) * 255.0f, 0.0f), 255.0f));
+}
+
+template <typename T, bool kEmitU8>
 __global__ __launch_bounds__(256) void warp_pack_kernel(const f16 *__restrict__ state,
     const f16 *__restrict__ flow, const std::uint8_t *__restrict__ frame,
     std::ptrdiff_t frameStride, T *__restrict__ out, int outPitch, int H, int W, int PW, int padTop,
-    int padLeft, const unsigned *__restrict__ sums, f16 *__restrict__ preWarpOut) {
+    int padLeft, const unsigned *__restrict__ sums, f16 *__restrict__ preWarpOut,
+    std::conditional_t<kEmitU8, FrameOut, NoFrameOut> frameOut) {
 	const int idx = blockIdx.x * 256 + threadIdx.x;
 	if (idx >= H * W * 4) return;
 	const float bright = brightnessOf(sums, 1.0f / static_cast<float>(H * W));  // pre_warp += b (models.py:803)
@@ -211,6 +231,33 @@ __global__ __launch_bounds__(256) void warp_pack_kernel(const f16 *__restrict__ 
 	T *dst = out + ((size_t)h * outPitch + w) * 64 + i * 16;
 	*reinterpret_cast<Vec8<T> *>(dst) = o0;
 	*reinterpret_cast<Vec8<T> *>(dst + 8) = o1;
+	if constexpr (kEmitU8) {
+		unsigned px[4];
+#pragma unroll
+		for (int j = 0; j < 4; ++j) {
+			px[j] = 0;
+#pragma unroll
+			for (int c = 0; c < 3; ++c) {
+				const int k = j * 3 + c;  // slots 0..11 of the quarter: o0[0..7], o1[0..3]
+				const float v = static_cast<float>(k < 8 ? o0[k] : o1[k - 8]);
+				px[j] |= preWarpByte(v) << (8 * c);
+			}
+		}
+		// (h < H, w < W: row 4h+i < 4H, bytes 16w .. 16w+15 < 16W -- inside the frame for any signed stride)
+		std::uint8_t *p = frameOut.ptr + (std::ptrdiff_t)(4 * h + i) * frameOut.stride + (std::ptrdiff_t)w * 16;
+		const auto a = reinterpret_cast<std::uintptr_t>(p);
+		// the widest store the row's alignment admits: 16w keeps the row's own (device-direct outputs are 8-byte
+		// aligned with strides of any multiple of 8, so rows may alternate between 16 and 8)
+		if ((a & 15) == 0) {
+			*reinterpret_cast<uint4 *>(p) = make_uint4(px[0], px[1], px[2], px[3]);
+		} else if ((a & 7) == 0) {
+			*reinterpret_cast<uint2 *>(p) = make_uint2(px[0], px[1]);
+			*reinterpret_cast<uint2 *>(p + 8) = make_uint2(px[2], px[3]);
+		} else {
+#pragma unroll
+			for (int j = 0; j < 4; ++j) *reinterpret_cast<unsigned *>(p + 4 * j) = px[j];
+		}
+	}
 }
 
 // ---------------------------------------------------------------------------
@@ -699,17 +746,29 @@ void launchUpsample2(DType dt, const void *in, void *out, int H, int W, int C, h
 
 void launchWarpPack(DType dt, const void *state, const void *flow, const std::uint8_t *frame,
     std::ptrdiff_t frameStride, void *out, int outPitch, int H, int W, int PW, int padTop, int padLeft,
-    const unsigned *sums, void *preWarpOut, hipStream_t stream) {
+    const unsigned *sums, void *preWarpOut, std::uint8_t *outU8, std::ptrdiff_t outStride, hipStream_t stream) {
 	if (outPitch <= 0) outPitch = W;
 	const unsigned nb = blocksFor((size_t)H * W * 4);
-	if (dt == kF16) {
-		hipLaunchKernelGGL(warp_pack_kernel<f16>, dim3(nb), dim3(256), 0, stream,
-		    static_cast<const f16 *>(state), static_cast<const f16 *>(flow), frame, frameStride, static_cast<f16 *>(out), outPitch, H,
-		    W, PW, padTop, padLeft, sums, static_cast<f16 *>(preWarpOut));
+	auto launch = [&](auto *typedOut, auto emit, auto frameOut) {
+		using T = std::remove_pointer_t<decltype(typedOut)>;
+		hipLaunchKernelGGL((warp_pack_kernel<T, decltype(emit)::value>), dim3(nb), dim3(256), 0, stream,
+		    static_cast<const f16 *>(state), static_cast<const f16 *>(flow), frame, frameStride, typedOut, outPitch, H,
+		    W, PW, padTop, padLeft, sums, static_cast<f16 *>(preWarpOut), frameOut);
+	};
+	if (outU8 != nullptr) {
+		if (reinterpret_cast<std::uintptr_t>(outU8) % 4 != 0 || outStride % 4 != 0) {
+			throw std::invalid_argument("warp_pack: the frame output must be 4-byte aligned");
+		}
+		const FrameOut fo{outU8, outStride};
+		if (dt == kF16) {
+			launch(static_cast<f16 *>(out), std::true_type{}, fo);
+		} else {
+			launch(static_cast<bf16 *>(out), std::true_type{}, fo);
+		}
+	} else if (dt == kF16) {
+		launch(static_cast<f16 *>(out), std::false_type{}, NoFrameOut{});
 	} else {
-		hipLaunchKernelGGL(warp_pack_kernel<bf16>, dim3(nb), dim3(256), 0, stream,
-		    static_cast<const f16 *>(state), static_cast<const f16 *>(flow), frame, frameStride, static_cast<bf16 *>(out), outPitch, H,
-		    W, PW, padTop, padLeft, sums, static_cast<f16 *>(preWarpOut));
+		launch(static_cast<bf16 *>(out), std::false_type{}, NoFrameOut{});
 	}
 	hipCheckLaunch("warp_pack");
 }

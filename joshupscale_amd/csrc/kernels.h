@@ -352,9 +352,15 @@ void launchUpsample2(DType dt, const void *in, void *out, int H, int W, int C, h
 //         ch 12,13,14 = current LR frame B,G,R, other spare slots zero.
 // preWarpOut (may be null): the warped previous output itself, f16 [4H][4W][4], for
 // the temporal filter below.
+// outU8 / outStride (outU8 may be null): the output_flow model variant -- the launch also writes the BGRX
+// frame [4H][4W] of the warped previous output, byte = trunc(clamp((v + 0.5) * 255, 0, 255)) of the value v
+// stored in `out` (its type, widened to f32), X = 0.  4-byte aligned, any signed stride that is a multiple of
+// 4; 16-byte stores where a row is 16-byte aligned, 8- or 4-byte ones otherwise.  Null: the launch is the
+// plain kernel, which has no such parameter.
 void launchWarpPack(DType dt, const void *state, const void *flow,
     const std::uint8_t *frame, std::ptrdiff_t frameStride, void *out, int outPitch, int H, int W, int PW,
-    int padTop, int padLeft, const unsigned *sums, void *preWarpOut, hipStream_t stream);  // out at image pixel (0, 0), outPitch in pixels (0: W)
+    int padTop, int padLeft, const unsigned *sums, void *preWarpOut, std::uint8_t *outU8, std::ptrdiff_t outStride,
+    hipStream_t stream);  // out at image pixel (0, 0), outPitch in pixels (0: W)
 
 // The generator input of a flow-free model (flow_arch "none", remove_flow.py): the LR frame's B,G,R as
 // slots 12..14 of each pixel's 64-slot record, converted exactly as launchWarpPack converts them.  One

@@ -80,6 +80,7 @@ ModelFile::ModelFile(const void *blob, std::size_t size) {
 		c.temporalL2 = (flags & 1u) != 0;
 		c.temporalLimit = (flags & 2u) != 0;
 		c.temporalLuma = (flags & 4u) != 0;
+		c.outputSelect = u32(140);  // (0 in every container written before the word had a meaning: it was reserved)
 	}
 	if (c.flowArch == kFlowNone) {
 		// a flow-free model: its flow fields are written at their defaults and mean nothing (model_file.py);
@@ -160,6 +161,9 @@ void validateConfig(const ModelConfig &c) {
 	if (c.genBlocks < 0 || c.genBlocks > 256) bad("gen_blocks must be in 0..256");
 	// the temporal filter blends pre_warp, the warped previous output: there is none without the flow net
 	if (!flow && c.temporalStrength > 0.0f) bad("the temporal filter needs a flow net");
+	if (c.outputSelect != kOutputFrame && c.outputSelect != kOutputPreWarp) bad("unknown output selection");
+	// pre_warp is the warp of the previous output by the flow field: a flow-free model has neither
+	if (!flow && c.outputsPreWarp()) bad("output pre_warp needs a flow net");
 	if (!(c.bnEps > 0.0f) || !std::isfinite(c.bnEps)) bad("bn_eps must be positive and finite");
 	if (!(c.temporalStrength >= 0.0f && c.temporalStrength <= 1.0f) ||
 	    !(c.temporalThreshold >= 0.0f && c.temporalThreshold <= 1.0f)) {

@@ -16,6 +16,7 @@
 namespace ju {
 
 constexpr int kFlowNone = 2;  // ModelConfig::flowArch of a flow-free model
+constexpr int kOutputFrame = 0, kOutputPreWarp = 1;  // ModelConfig::outputSelect
 
 struct ModelConfig {
 	int frameHeight = 0;
@@ -43,6 +44,10 @@ struct ModelConfig {
 	// 0 = relu, 1 = lrelu (keras LeakyReLU(negative_slope))
 	int flowActivation = 0, genActivation = 0;
 	float flowNegativeSlope = 0.0f, genNegativeSlope = 0.0f;
+	// what the caller's frame shows (header word 140): 0 = the generator's frame, 1 = pre_warp, the warped previous
+	// frame (scripts/inference/onnx/output_flow.py); state, history and brightness are the plain model's either way
+	int outputSelect = 0;
+	bool outputsPreWarp() const { return outputSelect == kOutputPreWarp; }
 
 	// false: flow_arch "none" -- no flow net, no warp, no state: the generator sees the LR frame only
 	bool recurrent() const { return flowArch != kFlowNone; }

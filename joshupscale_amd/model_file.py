@@ -32,11 +32,16 @@ Layout (all little endian):
     flow_arch 2 ("none"): a flow-free single-image model (scripts/inference/onnx/remove_flow.py, see
     remove_flow): no flow/* tensors, generator/conv_1/kernel [3, 3, 3, gen_filters]; both loaders
     ignore the flow fields (remove_flow sets them to their ModelConfig defaults).
-    -- only when the temporal filter uses a non-default mode, header_bytes = 160: --
+    -- only when the temporal filter uses a non-default mode or the output is not the generator's
+    frame, header_bytes = 160: --
     128 u32      temporal_window (HR pixels, 0 = global gate)
     132 f32      temporal_gain (0 = sign gate, else tanh(gain * (m - t)))
     136 u32      temporal flags: bit 0 L2 norm, bit 1 limit pre_warp, bit 2 luma weighting
-    140 u32      reserved[5]
+    140 u32      output selection: 0 the generator's frame, 1 pre_warp, the warped previous frame
+                 (scripts/inference/onnx/output_flow.py, see output_flow); other values are refused.
+                 The container version stays 1: a build older than this word never reads it and
+                 runs such a container as the plain model.
+    144 u32      reserved[4]
     table: n_tensors x { char name[92]; u32 ndim; u32 dims[4]; u64 offset;
                          u64 count }                (128 bytes each)
     data:  float32, each tensor 64-byte aligned, offsets from file start
@@ -60,6 +65,9 @@ DTYPE_FP8 = 2  # e4m3 block convolutions over fp16 (csrc/fp8.h)
 
 FLOW_ARCH = {"autoencoder": 0, "resnet": 1, "none": 2}
 FLOW_ARCH_INV = {v: k for k, v in FLOW_ARCH.items()}
+# what the caller's frame shows (header word 140)
+OUTPUT = {"frame": 0, "pre_warp": 1}
+OUTPUT_INV = {v: k for k, v in OUTPUT.items()}
 # ACTIVATIONS of scripts/training/models.py:24-27
 ACTIVATION = {"relu": 0, "lrelu": 1}
 ACTIVATION_INV = {v: k for k, v in ACTIVATION.items()}
@@ -103,6 +111,9 @@ class ModelConfig:
     temporal_norm: str = "L1"
     temporal_limit: bool = False
     temporal_luma: bool = False
+    # "frame": the generator's frame; "pre_warp": the warped previous frame, the model variant of
+    # scripts/inference/onnx/output_flow.py (output_flow below).  State and history are the plain model's.
+    output: str = "frame"
 
     @property
     def temporal_extended(self) -> bool:
@@ -243,6 +254,10 @@ def validate_config(cfg: ModelConfig) -> None:
         bad("gen_blocks must be in 0..256")
     if not flow and cfg.temporal_strength > 0:
         bad(NO_FLOW_TEMPORAL)
+    if cfg.output not in OUTPUT:
+        bad(UNKNOWN_OUTPUT)
+    if not flow and cfg.output == "pre_warp":
+        bad(NO_FLOW_PRE_WARP)
     if cfg.flow_arch == "autoencoder":
         nb = len(cfg.flow_filters) // 2
         if nb < 1 or cfg.padded_height % (1 << nb) or cfg.padded_width % (1 << nb):
@@ -274,6 +289,8 @@ def validate_config(cfg: ModelConfig) -> None:
 # the flow-free model's own checks (csrc/model.cpp states them with the same messages)
 NO_FLOW_TEMPORAL = "the temporal filter needs a flow net"
 NO_FLOW_TENSORS = "a flow-free model carries no flow/* tensors"
+NO_FLOW_PRE_WARP = "output pre_warp needs a flow net"
+UNKNOWN_OUTPUT = "unknown output selection"
 NO_FLOW_CONV_1 = "a flow-free model's generator/conv_1/kernel must be [3, 3, 3, gen_filters]"
 
 
@@ -315,6 +332,19 @@ def remove_flow(cfg: ModelConfig, weights: Dict[str, np.ndarray]
     return out_cfg, out
 
 
+def output_flow(cfg: ModelConfig, weights: Dict[str, np.ndarray]
+                ) -> Tuple[ModelConfig, Dict[str, np.ndarray]]:
+    """scripts/inference/onnx/output_flow.py on a container: the model's output becomes the warped
+    previous frame -- the post-processing node takes ``pre_warp`` (models.py:799-803), the tensor that
+    feeds the generator's SpaceToDepth, instead of the clip output (output_flow.py:38-74).  Everything
+    else stays: the generator still runs, output_raw is still fed back, the LR history still
+    advances; the weights are untouched.  The caller's frame is u8((pre_warp + 0.5) * 255), clamped
+    to 0..255 (csrc/frame_kernels.hip states the byte)."""
+    if cfg.flow_arch == "none":
+        raise ValueError("Invalid model: " + NO_FLOW_PRE_WARP)
+    return replace(cfg, output="pre_warp"), weights
+
+
 def serialize(cfg: ModelConfig, weights: Dict[str, np.ndarray], validate: bool = True) -> bytes:
     """Build the container bytes.  ``validate=False`` writes a header the loader will reject
     (the loader tests need such files)."""
@@ -327,10 +357,15 @@ def serialize(cfg: ModelConfig, weights: Dict[str, np.ndarray], validate: bool =
         raise ValueError("at most 8 flow filters")
     acts = ACTIVATION[cfg.flow_activation] | ACTIVATION[cfg.gen_activation] << 8
     ext = b""
-    if cfg.temporal_extended:
+    output = OUTPUT[cfg.output] if cfg.output in OUTPUT else int(cfg.output)  # (validate=False: any code)
+    if cfg.temporal_extended or output != 0:
+        # (output "frame": the word stays zero, the file is byte-identical to one written before it
+        # existed; a filter in its default mode, or off, writes its three words as their defaults)
+        te = cfg.temporal_extended
         flags = ({"L1": 0, "L2": 1}[cfg.temporal_norm] | int(cfg.temporal_limit) << 1
-                 | int(cfg.temporal_luma) << 2)
-        ext = struct.pack("<IfI5I", cfg.temporal_window, cfg.temporal_gain, flags, 0, 0, 0, 0, 0)
+                 | int(cfg.temporal_luma) << 2) if te else 0
+        ext = struct.pack("<IfI5I", cfg.temporal_window if te else 0, cfg.temporal_gain if te else 0.0,
+                          flags, output, 0, 0, 0, 0)
     header_bytes = HEADER_BYTES + len(ext)
     hdr = MAGIC + struct.pack(
         "<2I4I4I4I8IfIIffIff", VERSION, header_bytes,
@@ -394,9 +429,14 @@ def deserialize(blob: bytes) -> Tuple[ModelConfig, Dict[str, np.ndarray]]:
                       fslope if fact == "lrelu" else DEFAULT_NEGATIVE_SLOPE,
                       gslope if gact == "lrelu" else DEFAULT_NEGATIVE_SLOPE)
     if header_bytes >= 160:
-        win, gain, flags = struct.unpack_from("<IfI", blob, 128)
+        win, gain, flags, output = struct.unpack_from("<IfII", blob, 128)
         if flags >> 3:
             raise ValueError("Invalid model: unknown temporal filter flags")
+        if output not in OUTPUT_INV:
+            raise ValueError("Invalid model: " + UNKNOWN_OUTPUT)
+        if output == OUTPUT["pre_warp"] and arch == FLOW_ARCH["none"]:
+            raise ValueError("Invalid model: " + NO_FLOW_PRE_WARP)
+        cfg.output = OUTPUT_INV[output]
         cfg.temporal_window, cfg.temporal_gain = win, gain
         cfg.temporal_norm = "L2" if flags & 1 else "L1"
         cfg.temporal_limit, cfg.temporal_luma = bool(flags & 2), bool(flags & 4)

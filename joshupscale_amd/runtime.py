@@ -353,9 +353,15 @@ class Runtime:
         every frame is upscaled on its own and ``reset`` does nothing."""
         return self.stat("recurrent") != 0
 
+    @property
+    def output(self) -> str:
+        """What the frames show: ``"frame"``, the generator's frame, or ``"pre_warp"``, the warped previous
+        frame of an output_flow model (``model_file.output_flow``).  Fixed by the model file."""
+        return {0: "frame", 1: "pre_warp"}[int(self.stat("output_select"))]
+
     def stat(self, key: str) -> float:
         """``ju_get_stat``: "graph_replays", "eager_runs", "direct_graphs",
-        "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "lookahead_frames",
+        "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "output_select", "lookahead_frames",
         "lookahead_host_frames", "lookahead_yuv_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
