@@ -69,11 +69,11 @@ typedef struct ju_image {
 	size_t height;
 } ju_image;
 
-/* ---- 8-bit 4:2:0 YUV frames (no reference counterpart: the reference takes BGRX Images only) ------------------
+/* ---- 4:2:0 YUV frames, 8- and 10-bit (no reference counterpart: the reference takes BGRX Images only) ------------
  * Video decoders emit and encoders take NV12 / I420 (AviSynth: YV12 = I420 with the chroma planes swapped -- planes
  * are passed by pointer, so their order in memory does not matter).  ju_process_frame converts on the GPU, inside the
  * runtime's own staging: a YUV input is decoded into the BGRX frame the network consumes, the network's BGRX output is
- * encoded into the caller's planes.  Input and output formats are independent (all nine pairs).  A YUV frame is one
+ * encoded into the caller's planes.  Input and output formats are independent (all 25 pairs).  A YUV frame is one
  * step of the same recurrent stream: ju_process, ju_process_frame, ju_process_frames and ju_process_batch may be mixed
  * on one runtime.
  *
@@ -82,20 +82,32 @@ typedef struct ju_image {
  * even luma columns, centred vertically between two rows); decoding upsamples chroma bilinearly (weights 3:1 vertically,
  * 1:1 horizontally), encoding filters [1,2,1] x [1,1].
  *
- * Limits: 8-bit 4:2:0 only (no P010 / 10-bit); no YUV graphics resources (GL textures stay BGRX); look-ahead passes
- * take YUV frames through ju_process_frames (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not
- * ju_process_group; the C++ plugin surface (JoshUpscale/core.h) is unchanged and takes BGRX only. */
-enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2 };
+ *
+ * 10-bit 4:2:0 (what HEVC Main10 / AV1 decoders and encoders and high-bit-depth AviSynth+ scripts hold): samples are
+ * 16-bit little-endian words.  JU_FMT_P010: planes as NV12, the 10-bit value in the UPPER bits (word = value << 6); on
+ * input the low 6 bits are ignored, on output they are written 0.  JU_FMT_I010 (yuv420p10le): planes as I420, the value
+ * in the LOW 10 bits; on input the upper 6 bits are ignored, on output they are 0.  Limited range is 64..940 / 64..960.
+ * A 10-bit input is decoded to the same 8-bit BGRX frame the network consumes.  A 10-bit OUTPUT is encoded from the
+ * runtime's f16 recurrent state -- the frame in float, before the truncation to 8 bits -- so it carries real 10-bit
+ * precision; models whose state is not the frame (normalize_brightness, output_flow) encode it from the 8-bit frame
+ * instead (257 x u8).  ju_get_stat "hbd_from_state" tells which (1 / 0); it is fixed at creation.
+ *
+ * Limits: 4:2:0 only, 8- and 10-bit (no P016 / 12-bit, no 4:2:2 / 4:4:4, no 16-bit RGB output, no dithering); no YUV
+ * graphics resources (GL textures stay BGRX); look-ahead passes take YUV frames through ju_process_frames
+ * (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not ju_process_group; the C++ plugin surface
+ * (JoshUpscale/core.h) is unchanged and takes BGRX only. */
+enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2, JU_FMT_P010 = 3, JU_FMT_I010 = 4 };
 enum { JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3 };
 
 typedef struct ju_frame {
 	int format;            /* JU_FMT_* */
 	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX */
 	uint8_t location;      /* JU_LOC_CPU or JU_LOC_DEVICE (BGRX: any location a ju_image takes) */
-	size_t width, height;  /* in pixels (luma); even for I420 / NV12 */
-	void *planes[3];       /* BGRX: [0]; I420: Y, U, V; NV12: Y, interleaved UV (U first) */
-	ptrdiff_t strides[3];  /* bytes per row of each plane (first logical row at planes[k]), any sign,
-	                          |stride| >= the plane's row bytes: Y = width, U / V = width / 2, UV = width, BGRX = 4 width */
+	size_t width, height;  /* in pixels (luma); even for the YUV formats */
+	void *planes[3];       /* BGRX: [0]; I420 / I010: Y, U, V; NV12 / P010: Y, interleaved UV (U first) */
+	ptrdiff_t strides[3];  /* BYTES per row of each plane (first logical row at planes[k]), any sign,
+	                          |stride| >= the plane's row bytes: Y = width, U / V = width / 2, UV = width, BGRX = 4 width;
+	                          P010 / I010: twice that, and plane addresses and strides are multiples of 2 */
 } ju_frame;
 
 /* Replaces createRuntime(int deviceId, const std::filesystem::path &modelPath)
@@ -215,8 +227,8 @@ JU_API int ju_process_frame(ju_runtime *runtime, const ju_frame *input, const ju
  * ju_get_stat "lookahead_yuv_frames": frames with a YUV side that went through passes (also counted by
  * "lookahead_frames" and, with a host side, "lookahead_host_frames").
  * Not provided: a ju_prepare_* counterpart (an unregistered tuple of device planes is captured at its second use, as in
- * ju_process_batch; all-host passes of one shape share one graph); YUV frames in ju_process_group; 10-bit formats; the
- * C++ plugin surface. */
+ * ju_process_batch; all-host passes of one shape share one graph); YUV frames in ju_process_group; the C++ plugin
+ * surface. */
 JU_API int ju_process_frames(ju_runtime *runtime, const ju_frame *inputs, const ju_frame *outputs, int count);
 /* Asynchronous form (like ju_enqueue): JU_LOC_DEVICE frames only -- a host frame is JU_ERR_INVALID_ARGUMENT;
  * ju_synchronize waits. */
@@ -301,7 +313,9 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * (1 when the one-launch tower kernel is in use), "launches_per_frame", "tower_variant",
  * "group_frames" (frames this runtime got from ju_process_group passes),
  * "lookahead_frames" (frames that went through look-ahead passes; of them "lookahead_host_frames" with a host side,
- * "lookahead_yuv_frames" with a YUV side),
+ * "lookahead_yuv_frames" with a YUV side, 8- or 10-bit),
+ * "hbd_from_state" (1: this runtime encodes JU_FMT_P010 / JU_FMT_I010 outputs from its f16 state; 0: from the 8-bit
+ * frame -- normalize_brightness and output_flow models),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,
  * flow_arch "none" of the container -- every frame is upscaled on its own, ju_reset does nothing),
  * "output_select" (0: the frames are the generator's; 1: an output_flow model, header word 140 of the container --

@@ -64,11 +64,20 @@ JU_API int ju_debug_yuv(int direction, int format, int colorspace, size_t width,
 
 /* The decode kernel of ju_process_frames' look-ahead passes alone (yuv420_to_bgrx_items_kernel: the YUV inputs of a
  * pass in one launch), on caller-supplied device buffers, synchronously: `count` (1 .. 8) items of one width x height,
- * item i = format formats[i] (JU_FMT_I420 / JU_FMT_NV12), colour space colorspaces[i], planes planes[3 i .. 3 i + 2] with
+ * item i = format formats[i] (JU_FMT_I420 / JU_FMT_NV12 / JU_FMT_P010 / JU_FMT_I010, mixed freely), colour space colorspaces[i], planes planes[3 i .. 3 i + 2] with
  * strides[3 i .. 3 i + 2] (the third unused for NV12) -> BGRX rows at bgrx[i], bgrx_strides[i] bytes apart.  Any byte
- * alignment, any signed strides.  Per item the bytes of ju_debug_yuv direction 0. */
+ * alignment, any signed strides (10-bit items: multiples of 2).  Per item the bytes of ju_debug_yuv direction 0 /
+ * ju_debug_yuv10 op 0. */
 JU_API int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, size_t width, size_t height,
     void *const *bgrx, const ptrdiff_t *bgrx_strides, void *const *planes, const ptrdiff_t *strides);
+
+/* One of the three 10-bit conversion kernels alone (format JU_FMT_P010 / JU_FMT_I010), on caller-supplied device buffers,
+ * on the current device (synchronous).  op 0: planes -> BGRX u8 rows at `image`, image_stride bytes apart; op 1: BGRX u8
+ * rows at `image` -> planes (the encode of runtimes whose state is not the frame: P = 257 u8); op 2: the dense f16 tensor
+ * [height][width][4] (B, G, R, unused) at `image`, 16-byte aligned, image_stride ignored -> planes (the encode from the
+ * recurrent state: P = floor((s + 0.5) * 65536), saturated).  Plane addresses and strides: bytes, multiples of 2, any sign. */
+JU_API int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size_t height, void *image,
+    ptrdiff_t image_stride, void *const planes[3], const ptrdiff_t strides[3]);
 
 #ifdef __cplusplus
 } /* extern "C" */

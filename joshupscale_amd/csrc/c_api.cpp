@@ -84,7 +84,7 @@ ju::AnyFrame toAnyFrame(const ju_frame *f) {
 		a.bgrx = toFrame(&img);
 		return a;
 	}
-	if (f->format != JU_FMT_I420 && f->format != JU_FMT_NV12) {
+	if (f->format != JU_FMT_I420 && f->format != JU_FMT_NV12 && f->format != JU_FMT_P010 && f->format != JU_FMT_I010) {
 		throw std::invalid_argument("frame has an unknown format " + std::to_string(f->format));
 	}
 	if (f->location > JU_LOC_GRAPHICS_RESOURCE) throw std::invalid_argument("frame has an unknown location");
@@ -453,24 +453,76 @@ int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, si
 		ju::YuvDecodeItems items{};
 		for (int i = 0; i < count; ++i) {
 			const int f = formats[i];
-			if (f != JU_FMT_I420 && f != JU_FMT_NV12) throw std::invalid_argument("ju_debug_yuv_items: not a YUV format");
+			if (f != JU_FMT_I420 && f != JU_FMT_NV12 && f != JU_FMT_P010 && f != JU_FMT_I010) {
+				throw std::invalid_argument("ju_debug_yuv_items: not a YUV format");
+			}
+			const bool planar = f == JU_FMT_I420 || f == JU_FMT_I010, deep = f == JU_FMT_P010 || f == JU_FMT_I010;
 			void *const *p = planes + 3 * i;
-			if (bgrx[i] == nullptr || p[0] == nullptr || p[1] == nullptr || (f == JU_FMT_I420 && p[2] == nullptr)) {
+			if (bgrx[i] == nullptr || p[0] == nullptr || p[1] == nullptr || (planar && p[2] == nullptr)) {
 				throw std::invalid_argument("ju_debug_yuv_items: null buffer");
+			}
+			for (int k = 0; deep && k < (planar ? 3 : 2); ++k) {
+				if (reinterpret_cast<std::uintptr_t>(p[k]) % 2 || strides[3 * i + k] % 2) {
+					throw std::invalid_argument("ju_debug_yuv_items: 16-bit planes need even addresses and strides");
+				}
 			}
 			ju::YuvDecodeItem &it = items.item[i];
 			it.src.y = static_cast<std::uint8_t *>(p[0]);
 			it.src.u = static_cast<std::uint8_t *>(p[1]);
-			it.src.v = f == JU_FMT_I420 ? static_cast<std::uint8_t *>(p[2]) : nullptr;
+			it.src.v = planar ? static_cast<std::uint8_t *>(p[2]) : nullptr;
 			it.src.yStride = strides[3 * i];
 			it.src.uStride = strides[3 * i + 1];
-			it.src.vStride = f == JU_FMT_I420 ? strides[3 * i + 2] : 0;
-			it.k = ju::yuvDecodeCoefficients(colorspaces[i]);
+			it.src.vStride = planar ? strides[3 * i + 2] : 0;
+			it.k = deep ? ju::yuvDecodeCoefficients10(colorspaces[i]) : ju::yuvDecodeCoefficients(colorspaces[i]);
+			it.deep = f == JU_FMT_P010 ? 1 : (f == JU_FMT_I010 ? 2 : 0);
 			it.dst = static_cast<std::uint8_t *>(bgrx[i]);
 			it.dstStride = bgrx_strides[i];
 			it.nv12 = f == JU_FMT_NV12 ? 1 : 0;
 		}
 		ju::launchYuv420ToBgrxItems(items, count, static_cast<int>(width), static_cast<int>(height), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size_t height, void *image, ptrdiff_t image_stride,
+    void *const planes[3], const ptrdiff_t strides[3]) {
+	return guarded([&] {
+		if (op < 0 || op > 2) throw std::invalid_argument("ju_debug_yuv10: op must be 0, 1 or 2");
+		if (format != JU_FMT_P010 && format != JU_FMT_I010) throw std::invalid_argument("ju_debug_yuv10: not a 10-bit format");
+		if (width == 0 || height == 0 || width % 2 || height % 2 || width > (1u << 15) || height > (1u << 15)) {
+			throw std::invalid_argument("ju_debug_yuv10: width and height must be even, 2 .. 32768");
+		}
+		const bool planar = format == JU_FMT_I010;
+		if (image == nullptr || planes == nullptr || strides == nullptr || planes[0] == nullptr || planes[1] == nullptr ||
+		    (planar && planes[2] == nullptr)) {
+			throw std::invalid_argument("ju_debug_yuv10: null buffer");
+		}
+		for (int k = 0; k < (planar ? 3 : 2); ++k) {
+			if (reinterpret_cast<std::uintptr_t>(planes[k]) % 2 || strides[k] % 2) {
+				throw std::invalid_argument("ju_debug_yuv10: 16-bit planes need even addresses and strides");
+			}
+		}
+		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) {
+			throw std::invalid_argument("ju_debug_yuv10: the f16 tensor must be 16-byte aligned");
+		}
+		ju::YuvPlanes p;
+		p.y = static_cast<std::uint8_t *>(planes[0]);
+		p.u = static_cast<std::uint8_t *>(planes[1]);
+		p.v = planar ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
+		p.yStride = strides[0];
+		p.uStride = strides[1];
+		p.vStride = planar ? strides[2] : 0;
+		const bool p010 = format == JU_FMT_P010;
+		const int w = static_cast<int>(width), h = static_cast<int>(height);
+		if (op == 0) {
+			ju::launchYuv420p10ToBgrx(p010, p, ju::yuvDecodeCoefficients10(colorspace), static_cast<std::uint8_t *>(image),
+			    image_stride, w, h, nullptr);
+		} else if (op == 1) {
+			ju::launchBgrxToYuv420p10(p010, static_cast<const std::uint8_t *>(image), image_stride,
+			    ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
+		} else {
+			ju::launchStateToYuv420p10(p010, image, ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
+		}
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

@@ -175,20 +175,6 @@ __global__ __launch_bounds__(256) void yuv420_to_bgrx_kernel(YuvPlanes src, YuvD
 	yuv420ToBgrxStrip<NV12>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
-// The YUV inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item --
-// its planes, coefficients and destination, from the kernel arguments -- and its format is a branch every lane of the
-// workgroup takes alike.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
-// launch latencies for one round of work (the shape addFlowAutoencoder's batched launches fixed for the flow net).
-__global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
-	const YuvDecodeItem &it = items.item[blockIdx.y];
-	const int idx = blockIdx.x * 256 + threadIdx.x;
-	if (it.nv12) {
-		yuv420ToBgrxStrip<true>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	} else {
-		yuv420ToBgrxStrip<false>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	}
-}
-
 // BGRX -> Y, U, V (I420) or Y, UV (NV12).  Thread = luma rows 2j, 2j + 1 x columns x0 .. x0 + 15 (+ column x0 - 1,
 // clamped to 0, for the chroma filter) -> 2 x 16 luma bytes and chroma cells x0 / 2 .. x0 / 2 + 7 of row j.
 template <bool NV12>
@@ -271,6 +257,329 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv420_kernel(const std::uint8_t 
 	}
 }
 
+// ---- 10-bit 4:2:0: P010 (Y, interleaved UV; the value in the upper 10 bits of each word) / I010 (Y, U, V; the value
+// in the low 10 bits) ------------------------------------------------------------------------------------------------
+__device__ inline int sampleOf(const unsigned *w, int k) { return (w[k >> 1] >> (16 * (k & 1))) & 0xffff; }
+
+__device__ inline int clamp1023(int v) { return v < 0 ? 0 : (v > 1023 ? 1023 : v); }
+
+__device__ inline unsigned wordAt(const std::uint8_t *row, int sample) {
+	return *reinterpret_cast<const std::uint16_t *>(row + 2 * static_cast<std::ptrdiff_t>(sample));
+}
+
+// `N` (8 or 16) 16-bit samples of one row from sample `col` on, two per word; `fast`: in range (16-byte loads where
+// the address is 16-byte aligned, dwords at 4), else sample by sample, the index clamped to `last`
+template <int N>
+__device__ inline void loadSamples(const std::uint8_t *row, int col, int last, bool fast, unsigned (&w)[N / 2]) {
+	const std::uint8_t *p = row + 2 * static_cast<std::ptrdiff_t>(col);
+	if (fast && alignedTo(p, 16)) {
+#pragma unroll
+		for (int q = 0; q < N / 8; ++q) {
+			const uint4 v = reinterpret_cast<const uint4 *>(p)[q];
+			w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+		}
+		return;
+	}
+	if (fast && alignedTo(p, 4)) {
+#pragma unroll
+		for (int q = 0; q < N / 2; ++q) w[q] = reinterpret_cast<const unsigned *>(p)[q];
+		return;
+	}
+#pragma unroll
+	for (int q = 0; q < N / 2; ++q) {
+		w[q] = wordAt(row, min(col + 2 * q, last)) | (wordAt(row, min(col + 2 * q + 1, last)) << 16);
+	}
+}
+
+// `N` (8 or 16) 16-bit samples of one row from sample `col` on; `fast`: all in range (else only the first `n`)
+template <int N>
+__device__ inline void storeSamples(std::uint8_t *row, int col, int n, bool fast, const unsigned (&w)[N / 2]) {
+	std::uint8_t *p = row + 2 * static_cast<std::ptrdiff_t>(col);
+	if (fast && alignedTo(p, 16)) {
+#pragma unroll
+		for (int q = 0; q < N / 8; ++q) {
+			reinterpret_cast<uint4 *>(p)[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+		}
+		return;
+	}
+	if (fast && alignedTo(p, 4)) {
+#pragma unroll
+		for (int q = 0; q < N / 2; ++q) reinterpret_cast<unsigned *>(p)[q] = w[q];
+		return;
+	}
+#pragma unroll
+	for (int k = 0; k < N; ++k) {
+		if (fast || k < n) reinterpret_cast<std::uint16_t *>(p)[k] = static_cast<std::uint16_t>(sampleOf(w, k));
+	}
+}
+
+// P010 / I010 -> BGRX (u8): the strip of yuv420ToBgrxStrip with 16-bit samples -- 32 B of Y per row, 16 (+2) B of each
+// chroma plane row or 32 (+4) B of UV, from three chroma rows.  `k`: yuvDecodeCoefficients10.
+template <bool P010>
+__device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H, int idx) {
+	constexpr int kShift = P010 ? 6 : 0;  // (word >> 6, or word & 0x3ff)
+	const int strips = (W + kStrip - 1) / kStrip;
+	if (idx >= strips * (H / 2)) return;
+	const int j = idx / strips;
+	const int x0 = (idx - j * strips) * kStrip;
+	const int CW = W / 2, CH = H / 2;
+	const int c0 = x0 / 2;
+	const bool full = x0 + kStrip <= W;
+
+	int cu[3][9], cv[3][9];
+#pragma unroll
+	for (int r = 0; r < 3; ++r) {
+		const int jr = min(max(j - 1 + r, 0), CH - 1);
+		const int last = min(c0 + 8, CW - 1);
+		if constexpr (P010) {
+			const std::uint8_t *row = src.u + static_cast<std::ptrdiff_t>(jr) * src.uStride;
+			if (!full) {  // (the last strip of a row: U and V clamped to the last cell each)
+#pragma unroll
+				for (int i = 0; i < 8; ++i) {
+					const int c = min(c0 + i, CW - 1);
+					cu[r][i] = wordAt(row, 2 * c) >> kShift;
+					cv[r][i] = wordAt(row, 2 * c + 1) >> kShift;
+				}
+			} else {
+				unsigned w[8];
+				loadSamples<16>(row, 2 * c0, 2 * CW - 1, true, w);
+#pragma unroll
+				for (int i = 0; i < 8; ++i) {
+					cu[r][i] = sampleOf(w, 2 * i) >> kShift;
+					cv[r][i] = sampleOf(w, 2 * i + 1) >> kShift;
+				}
+			}
+			cu[r][8] = wordAt(row, 2 * last) >> kShift;
+			cv[r][8] = wordAt(row, 2 * last + 1) >> kShift;
+		} else {
+			const std::uint8_t *rowU = src.u + static_cast<std::ptrdiff_t>(jr) * src.uStride;
+			const std::uint8_t *rowV = src.v + static_cast<std::ptrdiff_t>(jr) * src.vStride;
+			unsigned wu[4], wv[4];
+			loadSamples<8>(rowU, c0, CW - 1, full, wu);
+			loadSamples<8>(rowV, c0, CW - 1, full, wv);
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				cu[r][i] = sampleOf(wu, i) & 0x3ff;
+				cv[r][i] = sampleOf(wv, i) & 0x3ff;
+			}
+			cu[r][8] = wordAt(rowU, last) & 0x3ff;
+			cv[r][8] = wordAt(rowV, last) & 0x3ff;
+		}
+	}
+
+#pragma unroll
+	for (int r = 0; r < 2; ++r) {
+		const int y = 2 * j + r;
+		unsigned yw[8];
+		loadSamples<16>(src.y + static_cast<std::ptrdiff_t>(y) * src.yStride, x0, W - 1, full, yw);
+		int vu[9], vv[9];
+#pragma unroll
+		for (int i = 0; i < 9; ++i) {
+			vu[i] = 3 * cu[1][i] + cu[r == 0 ? 0 : 2][i];
+			vv[i] = 3 * cv[1][i] + cv[r == 0 ? 0 : 2][i];
+		}
+		unsigned px[16];
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			const int i = p >> 1;
+			const int du = ((p & 1) ? vu[i] + vu[i + 1] : 2 * vu[i]) - 8 * 512;
+			const int dv = ((p & 1) ? vv[i] + vv[i + 1] : 2 * vv[i]) - 8 * 512;
+			const int Y = P010 ? sampleOf(yw, p) >> kShift : sampleOf(yw, p) & 0x3ff;
+			const int yd = k.ky * (8 * (Y - k.oy));
+			const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
+			const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
+			const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+			px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
+		}
+		std::uint8_t *row = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
+		const int n = min(kStrip, W - x0);
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const unsigned w[4] = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
+			storeBytes<16>(row, 4 * (x0 + 4 * q), 4 * (n - 4 * q), full, w);
+		}
+	}
+}
+
+template <bool P010>
+__global__ __launch_bounds__(256) void yuv420p10_to_bgrx_kernel(YuvPlanes src, YuvDecode k,
+    std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int W, int H) {
+	yuv420p10ToBgrxStrip<P010>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+// The 16-bit samples P (0 .. 65535) of 17 pixels of one row -- column x0 - 1 (clamped to 0) and columns x0 .. x0 + 15
+// (clamped to W - 1) -- as the two sources of the 10-bit encode form them; kept packed (registers), read through b / g / r.
+// From the engine's f16 state [H][W][4] (B, G, R, 0; dense, 16-byte aligned): floor((s + 0.5) * 65536), saturated.  In
+// f32 that is exact: every f16 of magnitude up to 0.5 is a multiple of 2^-24, and s + 0.5 then has 24 significant bits.
+struct StateSource {
+	using Pixel = uint2;  // x = P_B | P_G << 16, y = P_R
+	const f16 *state;
+	static constexpr int kScale = 1;
+	__device__ static unsigned sample(unsigned bits) {
+		const float s = static_cast<float>(__builtin_bit_cast(f16, static_cast<unsigned short>(bits)));
+		return static_cast<unsigned>(fminf(fmaxf(floorf((s + 0.5f) * 65536.0f), 0.0f), 65535.0f));
+	}
+	__device__ static Pixel unpack(unsigned lo, unsigned hi) {
+		return make_uint2(sample(lo & 0xffff) | (sample(lo >> 16) << 16), sample(hi & 0xffff));
+	}
+	__device__ static int b(Pixel p) { return static_cast<int>(p.x & 0xffff); }
+	__device__ static int g(Pixel p) { return static_cast<int>(p.x >> 16); }
+	__device__ static int r(Pixel p) { return static_cast<int>(p.y); }
+	__device__ void load(int y, int x0, int W, bool full, Pixel (&px)[17]) const {
+		const f16 *row = state + static_cast<std::size_t>(y) * W * 4;
+		{
+			const uint2 v = *reinterpret_cast<const uint2 *>(row + 4 * max(x0 - 1, 0));
+			px[0] = unpack(v.x, v.y);
+		}
+		if (full) {
+#pragma unroll
+			for (int q = 0; q < 8; ++q) {
+				const uint4 v = *reinterpret_cast<const uint4 *>(row + 4 * (x0 + 2 * q));
+				px[1 + 2 * q] = unpack(v.x, v.y);
+				px[2 + 2 * q] = unpack(v.z, v.w);
+			}
+		} else {
+#pragma unroll
+			for (int p = 0; p < 16; ++p) {
+				const uint2 v = *reinterpret_cast<const uint2 *>(row + 4 * min(x0 + p, W - 1));
+				px[1 + p] = unpack(v.x, v.y);
+			}
+		}
+	}
+};
+
+// From a u8 BGRX frame (any alignment, signed stride): P = 257 u8 -- the bytes stay bytes, see kScale.
+struct Bgrx8Source {
+	using Pixel = unsigned;  // B | G << 8 | R << 16, as in the frame
+	const std::uint8_t *src;
+	std::ptrdiff_t stride;
+	static constexpr int kScale = 257;  // (applied to the weighted sums: 257 sum(c u8) = sum(c P), in integers)
+	__device__ static int b(Pixel p) { return static_cast<int>(p & 255); }
+	__device__ static int g(Pixel p) { return static_cast<int>((p >> 8) & 255); }
+	__device__ static int r(Pixel p) { return static_cast<int>((p >> 16) & 255); }
+	__device__ void load(int y, int x0, int W, bool full, Pixel (&px)[17]) const {
+		const std::uint8_t *row = src + static_cast<std::ptrdiff_t>(y) * stride;
+		{
+			const std::uint8_t *p = row + 4 * max(x0 - 1, 0);
+			px[0] = p[0] | (p[1] << 8) | (p[2] << 16);
+		}
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			unsigned w[4];
+			if (full) {
+				loadBytes<16>(row, 4 * (x0 + 4 * q), 4 * W - 1, true, w);
+			} else {
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const std::uint8_t *p = row + 4 * min(x0 + 4 * q + i, W - 1);
+					w[i] = p[0] | (p[1] << 8) | (p[2] << 16);
+				}
+			}
+#pragma unroll
+			for (int i = 0; i < 4; ++i) px[1 + 4 * q + i] = w[i];
+		}
+	}
+};
+
+// P -> Y, U, V (I010) or Y, UV (P010): the strip body of both 10-bit encodes.  Thread = luma rows 2j, 2j + 1 x columns
+// x0 .. x0 + 15 -> 2 x 32 B of Y and 16 B of U and of V (32 B of UV).  64-bit accumulators: the products reach 2^45.
+template <bool P010, typename Source>
+__device__ inline void toYuv420p10Strip(const Source &source, const YuvEncode10 &k, const YuvPlanes &dst, int W, int H,
+    int idx) {
+	constexpr int kShift = P010 ? 6 : 0;
+	const int strips = (W + kStrip - 1) / kStrip;
+	if (idx >= strips * (H / 2)) return;
+	const int j = idx / strips;
+	const int x0 = (idx - j * strips) * kStrip;
+	const bool full = x0 + kStrip <= W;
+	const int n = min(kStrip, W - x0);  // luma columns of this strip (even)
+
+	int sr[8], sg[8], sb[8];  // per chroma cell: the [1, 2, 1] x [1, 1] sums of the source's samples (8 x the mean)
+#pragma unroll
+	for (int i = 0; i < 8; ++i) sr[i] = sg[i] = sb[i] = 0;
+#pragma unroll
+	for (int r = 0; r < 2; ++r) {
+		const int y = 2 * j + r;
+		typename Source::Pixel px[17];  // [0] = column x0 - 1 (clamped), [1 + p] = column x0 + p
+		source.load(y, x0, W, full, px);
+		unsigned yw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			const long long acc = (static_cast<long long>(k.yr) * Source::r(px[1 + p]) +
+			                       static_cast<long long>(k.yg) * Source::g(px[1 + p]) +
+			                       static_cast<long long>(k.yb) * Source::b(px[1 + p])) * Source::kScale + (1ll << 31);
+			const int Y = clamp1023(k.oy + static_cast<int>(acc >> 32));
+			yw[p >> 1] |= static_cast<unsigned>(Y << kShift) << (16 * (p & 1));
+		}
+		storeSamples<16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, yw);
+#pragma unroll
+		for (int i = 0; i < 8; ++i) {
+			// columns 2i - 1, 2i, 2i + 1 of the strip = px[2i], px[2i + 1], px[2i + 2]
+			sb[i] += Source::b(px[2 * i]) + 2 * Source::b(px[2 * i + 1]) + Source::b(px[2 * i + 2]);
+			sg[i] += Source::g(px[2 * i]) + 2 * Source::g(px[2 * i + 1]) + Source::g(px[2 * i + 2]);
+			sr[i] += Source::r(px[2 * i]) + 2 * Source::r(px[2 * i + 1]) + Source::r(px[2 * i + 2]);
+		}
+	}
+	unsigned uw[4] = {0, 0, 0, 0}, vw[4] = {0, 0, 0, 0};
+#pragma unroll
+	for (int i = 0; i < 8; ++i) {
+		const long long au = (static_cast<long long>(k.ur) * sr[i] + static_cast<long long>(k.ug) * sg[i] +
+		                      static_cast<long long>(k.ub) * sb[i]) * Source::kScale + (1ll << 34);
+		const long long av = (static_cast<long long>(k.vr) * sr[i] + static_cast<long long>(k.vg) * sg[i] +
+		                      static_cast<long long>(k.vb) * sb[i]) * Source::kScale + (1ll << 34);
+		const int U = clamp1023(512 + static_cast<int>(au >> 35));
+		const int V = clamp1023(512 + static_cast<int>(av >> 35));
+		uw[i >> 1] |= static_cast<unsigned>(U << kShift) << (16 * (i & 1));
+		vw[i >> 1] |= static_cast<unsigned>(V << kShift) << (16 * (i & 1));
+	}
+	const int c0 = x0 / 2;
+	if constexpr (P010) {
+		unsigned w[8];
+#pragma unroll
+		for (int i = 0; i < 8; ++i) {  // U_i V_i
+			w[i] = ((uw[i >> 1] >> (16 * (i & 1))) & 0xffff) | (((vw[i >> 1] >> (16 * (i & 1))) & 0xffff) << 16);
+		}
+		storeSamples<16>(dst.u + static_cast<std::ptrdiff_t>(j) * dst.uStride, 2 * c0, n, full, w);
+	} else {
+		storeSamples<8>(dst.u + static_cast<std::ptrdiff_t>(j) * dst.uStride, c0, n / 2, full, uw);
+		storeSamples<8>(dst.v + static_cast<std::ptrdiff_t>(j) * dst.vStride, c0, n / 2, full, vw);
+	}
+}
+
+template <bool P010>
+__global__ __launch_bounds__(256) void state_to_yuv420p10_kernel(const f16 *__restrict__ state, YuvEncode10 k,
+    YuvPlanes dst, int W, int H) {
+	toYuv420p10Strip<P010>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+// (214 VGPRs: the scheduler hoists the byte extractions of a row over its 64-bit sums; held to 128 registers with
+// amdgpu_waves_per_eu the kernel spills 352 B per lane, so it is left alone -- at 1920x1080 the grid is 254 workgroups on
+// 256 CUs, one wave per SIMD, and the occupancy limit is never reached)
+template <bool P010>
+__global__ __launch_bounds__(256) void bgrx_to_yuv420p10_kernel(const std::uint8_t *__restrict__ src,
+    std::ptrdiff_t srcStride, YuvEncode10 k, YuvPlanes dst, int W, int H) {
+	toYuv420p10Strip<P010>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+// The YUV inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item --
+// its planes, coefficients and destination, from the kernel arguments -- and its format is a branch every lane of the
+// workgroup takes alike.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
+// launch latencies for one round of work (the shape addFlowAutoencoder's batched launches fixed for the flow net).
+__global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
+	const YuvDecodeItem &it = items.item[blockIdx.y];
+	const int idx = blockIdx.x * 256 + threadIdx.x;
+	if (it.deep == 1) {  // (P010; 2: I010 -- 10-bit items, as uniform per workgroup as the 8-bit formats)
+		yuv420p10ToBgrxStrip<true>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	} else if (it.deep == 2) {
+		yuv420p10ToBgrxStrip<false>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	} else if (it.nv12) {
+		yuv420ToBgrxStrip<true>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	} else {
+		yuv420ToBgrxStrip<false>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	}
+}
+
 int roundHalfAway(double x) { return static_cast<int>(std::copysign(std::floor(std::fabs(x) * 65536.0 + 0.5), x)); }
 
 void colourSpace(int cs, double *kr, double *kb, bool *limited) {
@@ -320,6 +629,47 @@ YuvEncode yuvEncodeCoefficients(int colorspace) {
 	return k;
 }
 
+YuvDecode yuvDecodeCoefficients10(int colorspace) {
+	double kr, kb;
+	bool limited;
+	colourSpace(colorspace, &kr, &kb, &limited);
+	const double kg = 1.0 - kr - kb;
+	const double s = limited ? 255.0 / 896.0 : 255.0 / 1023.0;
+	YuvDecode k;
+	k.ky = roundHalfAway(limited ? 255.0 / 876.0 : 255.0 / 1023.0);
+	k.krv = roundHalfAway(2 * (1 - kr) * s);
+	k.kbu = roundHalfAway(2 * (1 - kb) * s);
+	k.kgu = roundHalfAway(2 * kb * (1 - kb) / kg * s);
+	k.kgv = roundHalfAway(2 * kr * (1 - kr) / kg * s);
+	k.oy = limited ? 64 : 0;
+	return k;
+}
+
+YuvEncode10 yuvEncodeCoefficients10(int colorspace) {
+	double kr, kb;
+	bool limited;
+	colourSpace(colorspace, &kr, &kb, &limited);
+	const double kg = 1.0 - kr - kb;
+	const double sy = limited ? 876.0 : 1023.0, sc = limited ? 896.0 : 1023.0;
+	const double du = sc / (2 * (1 - kb)), dv = sc / (2 * (1 - kr));
+	// x 2^32 / 65535 (the 16-bit sample's full scale), rounded half away from zero: each below 2^26
+	auto c = [](double x) {
+		return static_cast<int>(std::copysign(std::floor(std::fabs(x / 65535.0 * 4294967296.0) + 0.5), x));
+	};
+	YuvEncode10 k;
+	k.yr = c(sy * kr);
+	k.yg = c(sy * kg);
+	k.yb = c(sy * kb);
+	k.ur = c(-kr * du);
+	k.ug = c(-kg * du);
+	k.ub = c((1 - kb) * du);
+	k.vr = c((1 - kr) * dv);
+	k.vg = c(-kg * dv);
+	k.vb = c(-kb * dv);
+	k.oy = limited ? 64 : 0;
+	return k;
+}
+
 void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
     std::ptrdiff_t dstStride, int width, int height, hipStream_t stream) {
 	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
@@ -352,6 +702,45 @@ void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcSt
 		    srcStride, k, dst, width, height);
 	}
 	hipCheckLaunch("bgrx_to_yuv420");
+}
+
+void launchYuv420p10ToBgrx(bool p010, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream) {
+	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
+	if (p010) {
+		hipLaunchKernelGGL(yuv420p10_to_bgrx_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
+		    dstStride, width, height);
+	} else {
+		hipLaunchKernelGGL(yuv420p10_to_bgrx_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
+		    dstStride, width, height);
+	}
+	hipCheckLaunch("yuv420p10_to_bgrx");
+}
+
+void launchStateToYuv420p10(bool p010, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
+    int height, hipStream_t stream) {
+	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
+	if (p010) {
+		hipLaunchKernelGGL(state_to_yuv420p10_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream,
+		    static_cast<const f16 *>(state), k, dst, width, height);
+	} else {
+		hipLaunchKernelGGL(state_to_yuv420p10_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream,
+		    static_cast<const f16 *>(state), k, dst, width, height);
+	}
+	hipCheckLaunch("state_to_yuv420p10");
+}
+
+void launchBgrxToYuv420p10(bool p010, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
+	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
+	if (p010) {
+		hipLaunchKernelGGL(bgrx_to_yuv420p10_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src,
+		    srcStride, k, dst, width, height);
+	} else {
+		hipLaunchKernelGGL(bgrx_to_yuv420p10_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src,
+		    srcStride, k, dst, width, height);
+	}
+	hipCheckLaunch("bgrx_to_yuv420p10");
 }
 
 }  // namespace ju

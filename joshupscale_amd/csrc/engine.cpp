@@ -1043,6 +1043,10 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 	m_OutStage = DeviceBuffer(lr * 16 * 4);
 	m_RawStage = DeviceBuffer(lr * 16 * 4);
 	if (c.outputsPreWarp()) m_DiscardFrame = DeviceBuffer(lr * 16 * 4);  // (buildProgram: where the generator's frame goes)
+	// 10-bit outputs come from the f16 state wherever the state the step leaves is the frame in float: not with
+	// normalize_brightness (the state is output_raw - b; flow-free models ignore the flag) nor in the output_flow
+	// variant (the frame is pre_warp)
+	m_HbdFromState = !(c.normalizeBrightness && c.recurrent()) && !c.outputsPreWarp();
 	// host YUV frames (ju_process_frame): their planes, rows padded to 64 bytes
 	m_YuvInStage = DeviceBuffer(yuvStageBytes(W, H));
 	m_YuvOutStage = DeviceBuffer(yuvStageBytes(4 * W, 4 * H));
@@ -1474,17 +1478,29 @@ void Engine::stageOut(const Frame &out) {
 }
 
 namespace {
-// Plane k of a 4:2:0 frame of the given luma size: rows, bytes per row (I420: Y, U, V; NV12: Y, UV)
+// Plane k of a 4:2:0 frame of the given luma size: rows, bytes per row (I420 / I010: Y, U, V; NV12 / P010: Y, UV;
+// P010 / I010: two bytes per sample)
 struct PlaneShape {
 	std::size_t rows, rowBytes;
 };
+bool semiPlanar(PixelFormat f) { return f == PixelFormat::Nv12 || f == PixelFormat::P010; }
+bool tenBit(PixelFormat f) { return f == PixelFormat::P010 || f == PixelFormat::I010; }
+std::size_t bytesPerSample(PixelFormat f) { return tenBit(f) ? 2 : 1; }
 PlaneShape planeShape(PixelFormat f, std::size_t w, std::size_t h, int k) {
-	if (k == 0) return {h, w};
-	return {h / 2, f == PixelFormat::Nv12 ? w : w / 2};
+	const std::size_t b = bytesPerSample(f);
+	if (k == 0) return {h, w * b};
+	return {h / 2, (semiPlanar(f) ? w : w / 2) * b};
 }
-int planeCount(PixelFormat f) { return f == PixelFormat::Nv12 ? 2 : 3; }
+int planeCount(PixelFormat f) { return semiPlanar(f) ? 2 : 3; }
 std::size_t stagePitch(std::size_t rowBytes) { return (rowBytes + 63) / 64 * 64; }
-const char *formatName(PixelFormat f) { return f == PixelFormat::Nv12 ? "NV12" : "I420"; }
+const char *formatName(PixelFormat f) {
+	switch (f) {
+	case PixelFormat::Nv12: return "NV12";
+	case PixelFormat::P010: return "P010";
+	case PixelFormat::I010: return "I010";
+	default: return "I420";
+	}
+}
 
 // The caller's device planes as a conversion kernel takes them
 YuvPlanes callerPlanes(const YuvFrame &f) {
@@ -1534,14 +1550,18 @@ void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream
 }
 }  // namespace
 
-// bytes of a staging buffer that holds any 4:2:0 frame of the size (I420's three planes take the most)
+// bytes of a staging buffer that holds any 4:2:0 frame of the size, 8- or 10-bit (the three planes of I010 take the most)
 std::size_t Engine::yuvStageBytes(std::size_t w, std::size_t h) {
-	std::size_t n = 0;
-	for (int k = 0; k < 3; ++k) {
-		const PlaneShape p = planeShape(PixelFormat::I420, w, h, k);
-		n += stagePitch(p.rowBytes) * p.rows;
+	std::size_t most = 0;
+	for (PixelFormat f : {PixelFormat::I420, PixelFormat::Nv12, PixelFormat::P010, PixelFormat::I010}) {
+		std::size_t n = 0;
+		for (int k = 0; k < planeCount(f); ++k) {
+			const PlaneShape p = planeShape(f, w, h, k);
+			n += stagePitch(p.rowBytes) * p.rows;
+		}
+		most = std::max(most, n);
 	}
-	return std::max(n, stagePitch(w) * h + stagePitch(w) * (h / 2));
+	return most;
 }
 
 // Everything a frame call can refuse, checked before anything is launched (the BGRX side repeats what stageIn /
@@ -1565,7 +1585,8 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 		return;
 	}
 	const YuvFrame &y = f.planes;
-	if (y.format != PixelFormat::I420 && y.format != PixelFormat::Nv12) {
+	if (y.format != PixelFormat::I420 && y.format != PixelFormat::Nv12 && y.format != PixelFormat::P010 &&
+	    y.format != PixelFormat::I010) {
 		throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
 	}
 	if (y.colorspace < 0 || y.colorspace > 3) {
@@ -1586,6 +1607,11 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 		if (y.planes[k] == nullptr) {
 			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) + " is NULL");
 		}
+		if (tenBit(y.format) && (reinterpret_cast<std::uintptr_t>(y.planes[k]) % 2 != 0 || y.strides[k] % 2 != 0)) {
+			throw std::invalid_argument(std::string("processFrame: ") + side + " plane " + std::to_string(k) + ": " +
+			                            formatName(y.format) + " samples are 16-bit words -- the plane's address and its " +
+			                            "stride must be multiples of 2");
+		}
 		const auto row = static_cast<std::ptrdiff_t>(planeShape(y.format, w, h, k).rowBytes);
 		if (y.strides[k] > -row && y.strides[k] < row) {
 			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) +
@@ -1595,25 +1621,54 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 }
 
 void Engine::stageInYuv(const YuvFrame &in) {
-	const FrameSize fs = frameSize();
-	const std::size_t w = fs.inputWidth, h = fs.inputHeight;
+	const std::size_t w = frameSize().inputWidth;
 	const bool host = in.location != Location::Device;
 	if (host) copyPlanes(in, m_YuvInStage.as<std::uint8_t>(), true, m_Stream);
 	const YuvPlanes pl = host ? stagedPlanes(in, m_YuvInStage.as<std::uint8_t>()) : callerPlanes(in);
-	launchYuv420ToBgrx(in.format == PixelFormat::Nv12, pl, yuvDecodeCoefficients(in.colorspace),
-	    m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4), static_cast<int>(w), static_cast<int>(h),
-	    m_Stream);
+	decodeYuv(in.format, in.colorspace, pl, m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4));
+}
+
+// one decode launch on the engine's stream: planes of an input-sized frame -> BGRX rows
+void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::uint8_t *bgrx,
+    std::ptrdiff_t bgrxStride) {
+	const FrameSize fs = frameSize();
+	const int w = static_cast<int>(fs.inputWidth), h = static_cast<int>(fs.inputHeight);
+	if (tenBit(format)) {
+		launchYuv420p10ToBgrx(format == PixelFormat::P010, planes, yuvDecodeCoefficients10(colorspace), bgrx, bgrxStride,
+		    w, h, m_Stream);
+	} else {
+		launchYuv420ToBgrx(format == PixelFormat::Nv12, planes, yuvDecodeCoefficients(colorspace), bgrx, bgrxStride, w, h,
+		    m_Stream);
+	}
+}
+
+// one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit format
+// of a runtime whose state is the frame in float (m_HbdFromState), the f16 state that frame left -- -> planes
+void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, const std::uint8_t *bgrx,
+    std::ptrdiff_t bgrxStride, const void *state) {
+	const FrameSize fs = frameSize();
+	const int w = static_cast<int>(fs.outputWidth), h = static_cast<int>(fs.outputHeight);
+	if (!tenBit(format)) {
+		launchBgrxToYuv420(format == PixelFormat::Nv12, bgrx, bgrxStride, yuvEncodeCoefficients(colorspace), planes, w, h,
+		    m_Stream);
+	} else if (m_HbdFromState) {
+		launchStateToYuv420p10(format == PixelFormat::P010, state, yuvEncodeCoefficients10(colorspace), planes, w, h,
+		    m_Stream);
+	} else {
+		launchBgrxToYuv420p10(format == PixelFormat::P010, bgrx, bgrxStride, yuvEncodeCoefficients10(colorspace), planes,
+		    w, h, m_Stream);
+	}
 }
 
 void Engine::stageOutYuv(const YuvFrame &out) {
 	const FrameSize fs = frameSize();
-	const std::size_t w = fs.outputWidth, h = fs.outputHeight;
+	const std::size_t w = fs.outputWidth;
 	const bool host = out.location == Location::Host;
 	// (a host frame: the kernel writes the staging buffer in the caller's row order, copied out below)
 	const YuvPlanes pl = host ? stagedPlanes(out, m_YuvOutStage.as<std::uint8_t>()) : callerPlanes(out);
-	launchBgrxToYuv420(out.format == PixelFormat::Nv12, m_OutStage.as<std::uint8_t>(),
-	    static_cast<std::ptrdiff_t>(w * 4), yuvEncodeCoefficients(out.colorspace), pl, static_cast<int>(w),
-	    static_cast<int>(h), m_Stream);
+	// (called behind the frame's program and before the flip: the state this frame wrote is the binding set's output)
+	encodeYuv(out.format, out.colorspace, pl, m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4),
+	    m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get());
 	if (host) copyPlanes(out, m_YuvOutStage.as<std::uint8_t>(), false, m_Stream);
 }
 
@@ -1859,10 +1914,11 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		if (!pf.yuvIn) continue;
 		YuvDecodeItem &it = items.item[decodes++];
 		it.src = pf.decode;
-		it.k = yuvDecodeCoefficients(pf.csIn);
+		it.k = tenBit(pf.formatIn) ? yuvDecodeCoefficients10(pf.csIn) : yuvDecodeCoefficients(pf.csIn);
 		it.dst = const_cast<std::uint8_t *>(m_BatchIO[i].in);
 		it.dstStride = m_BatchIO[i].inStride;
-		it.nv12 = pf.nv12In ? 1 : 0;
+		it.nv12 = pf.formatIn == PixelFormat::Nv12 ? 1 : 0;
+		it.deep = pf.formatIn == PixelFormat::P010 ? 1 : (pf.formatIn == PixelFormat::I010 ? 2 : 0);
 	}
 	if (decodes) {
 		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),
@@ -1880,10 +1936,11 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 			if (st.tag != "flow" && st.tag != "pack") run(st);
 		}
 		if (m_BatchHost[i].yuvOut) {  // the frame's BGRX output (m_PassOut[i]) into the caller's device planes / the staging slot
-			const FrameSize fs = frameSize();
-			launchBgrxToYuv420(m_BatchHost[i].nv12Out, m_BatchIO[i].out, m_BatchIO[i].outStride,
-			    yuvEncodeCoefficients(m_BatchHost[i].csOut), m_BatchHost[i].encode, static_cast<int>(fs.outputWidth),
-			    static_cast<int>(fs.outputHeight), m_Stream);
+			// (a 10-bit output from the state: THIS frame's link of the chain -- m_BatchState[i], the last frame's
+			// m_State[set ^ 1]; a flow-free pass has one scratch state that the next frame's tail overwrites, so the encode
+			// stays on this stream in front of the next frame's kernels)
+			encodeYuv(m_BatchHost[i].formatOut, m_BatchHost[i].csOut, m_BatchHost[i].encode, m_BatchIO[i].out,
+			    m_BatchIO[i].outStride, m_StateBind[set].out);
 		}
 		// (a host frame: its bytes are complete in m_PassOut[i] / m_PassYuvOut[i] -- tell the thread that copies them out)
 		if (m_BatchHost[i].hostOut) launchSignalHost(m_PassSignal.device(), m_Stream);
@@ -1961,7 +2018,7 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 			const YuvFrame &y = in[i].planes;
 			pf.yuvIn = true;
 			pf.hostIn = y.location == Location::Host;
-			pf.nv12In = y.format == PixelFormat::Nv12;
+			pf.formatIn = y.format;
 			pf.csIn = y.colorspace;
 			if (!m_PassIn[i].get()) m_PassIn[i] = DeviceBuffer(fs.inputHeight * static_cast<std::size_t>(inRow));
 			io.in = m_PassIn[i].as<std::uint8_t>();
@@ -1984,7 +2041,7 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 			const YuvFrame &y = out[i].planes;
 			pf.yuvOut = true;
 			pf.hostOut = y.location == Location::Host;
-			pf.nv12Out = y.format == PixelFormat::Nv12;
+			pf.formatOut = y.format;
 			pf.csOut = y.colorspace;
 			if (!m_PassOut[i].get()) m_PassOut[i] = DeviceBuffer(fs.outputHeight * static_cast<std::size_t>(outRow));
 			io.out = m_PassOut[i].as<std::uint8_t>();
@@ -2857,6 +2914,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "fallbacks") return static_cast<double>(m_Fallbacks);
 	if (key == "lookahead_frames") return static_cast<double>(m_BatchFrames);  // frames that went through look-ahead passes
 	if (key == "lookahead_host_frames") return static_cast<double>(m_BatchHostFrames);  // ... of them with a host image
+	if (key == "hbd_from_state") return m_HbdFromState ? 1.0 : 0.0;  // 10-bit outputs: from the f16 state (1) / the u8 frame (0)
 	if (key == "lookahead_yuv_frames") return static_cast<double>(m_BatchYuvFrames);  // ... of them with a YUV side
 	if (key == "lookahead_max") return static_cast<double>(m_BatchMax);
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes

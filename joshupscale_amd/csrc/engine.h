@@ -40,9 +40,10 @@ struct Frame {
 	std::size_t height;
 };
 
-// An 8-bit 4:2:0 frame of ju_process_frame (include/joshupscale_amd.h, ju_frame): planes Y, U, V (I420 / YV12) or
-// Y, interleaved UV (NV12), each addressing its first logical row, strides in bytes of any sign.  Host or device.
-enum class PixelFormat : int { Bgrx = 0, I420 = 1, Nv12 = 2 };
+// A 4:2:0 frame of ju_process_frame (include/joshupscale_amd.h, ju_frame): planes Y, U, V (I420 / YV12, I010) or
+// Y, interleaved UV (NV12, P010), each addressing its first logical row, strides in bytes of any sign.  Host or device.
+// P010 / I010: 16-bit little-endian samples (the 10-bit value in the upper / the low bits).
+enum class PixelFormat : int { Bgrx = 0, I420 = 1, Nv12 = 2, P010 = 3, I010 = 4 };
 
 struct YuvFrame {
 	PixelFormat format;
@@ -199,7 +200,14 @@ private:
 	void buildProgram(int set);
 	void stageIn(const Frame &in);
 	void stageOut(const Frame &out);
-	// YUV frames: decode into m_InStage / encode from m_OutStage; host planes go through m_YuvInStage / m_YuvOutStage
+	// YUV frames: decode into m_InStage / encode from m_OutStage; host planes go through m_YuvInStage / m_YuvOutStage.
+	// A 10-bit output is encoded from the f16 state the step left (m_HbdFromState: the state IS the frame in float --
+	// every model but normalize_brightness, whose state is output_raw - b, and output_flow, whose frame is pre_warp) or,
+	// for those two, from the u8 frame like an 8-bit output.  Decided once, at creation; ju_get_stat "hbd_from_state".
+	bool m_HbdFromState = true;
+	void decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::uint8_t *bgrx, std::ptrdiff_t bgrxStride);
+	void encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, const std::uint8_t *bgrx,
+	    std::ptrdiff_t bgrxStride, const void *state);
 	void checkFrame(const AnyFrame &f, bool input) const;
 	void stageInYuv(const YuvFrame &in);
 	void stageOutYuv(const YuvFrame &out);
@@ -400,7 +408,7 @@ private:
 	struct PassFrame {
 		bool hostIn = false, hostOut = false;
 		bool yuvIn = false, yuvOut = false;
-		bool nv12In = false, nv12Out = false;
+		PixelFormat formatIn = PixelFormat::Bgrx, formatOut = PixelFormat::Bgrx;
 		int csIn = 0, csOut = 0;
 		YuvPlanes decode, encode;
 	};

@@ -454,11 +454,30 @@ struct YuvDecodeItem {
 	std::uint8_t *dst = nullptr;
 	std::ptrdiff_t dstStride = 0;
 	int nv12 = 0;
+	int deep = 0;  // 0: an 8-bit item (I420 / NV12 by `nv12`); 1: P010, 2: I010 (k = yuvDecodeCoefficients10)
 };
 struct YuvDecodeItems {
 	YuvDecodeItem item[kFlowBatchMax];
 };
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream);
+
+// ---- 10-bit 4:2:0 (P010: Y, interleaved UV, value << 6; I010: Y, U, V, value in the low bits) <-> BGRX ----------------
+// YuvPlanes as above with 16-bit little-endian samples: strides stay bytes, pointers and strides multiples of 2.
+// tests/yuv10_reference.py is the definition.  Decode coefficients x 65536 for 10-bit samples -> u8 (oy 64 | 0); encode
+// coefficients x 2^32 / 65535, applied to a 16-bit sample P per channel (each below 2^26; products summed in 64 bits).
+struct YuvEncode10 {
+	int yr, yg, yb, ur, ug, ub, vr, vg, vb, oy;
+};
+YuvDecode yuvDecodeCoefficients10(int colorspace);
+YuvEncode10 yuvEncodeCoefficients10(int colorspace);
+void launchYuv420p10ToBgrx(bool p010, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
+// P = floor((s + 0.5) * 65536), saturated, of the dense f16 state [height][width][4] (B, G, R, 0; 16-byte aligned)
+void launchStateToYuv420p10(bool p010, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
+    int height, hipStream_t stream);
+// P = 257 u8 of a BGRX frame (any alignment, signed stride)
+void launchBgrxToYuv420p10(bool p010, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream);
 
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).

@@ -44,13 +44,14 @@ class JuImage(C.Structure):
                 ("height", C.c_size_t)]
 
 
-# 8-bit 4:2:0 frames of ju_process_frame (include/joshupscale_amd.h; formulas: INTEGRATION.md, "YUV frames")
-FMT_BGRX, FMT_I420, FMT_NV12 = 0, 1, 2
+# 4:2:0 frames of ju_process_frame (include/joshupscale_amd.h; formulas: INTEGRATION.md, "YUV frames"); P010 / I010:
+# 10-bit samples in 16-bit words (uint16 planes; P010 the value << 6, I010 the value in the low bits)
+FMT_BGRX, FMT_I420, FMT_NV12, FMT_P010, FMT_I010 = 0, 1, 2, 3, 4
 CS_BT601_LIMITED, CS_BT601_FULL, CS_BT709_LIMITED, CS_BT709_FULL = 0, 1, 2, 3
 
 
 class JuFrame(C.Structure):
-    """``ju_frame``: a BGRX, I420 (YV12) or NV12 frame, host or device."""
+    """``ju_frame``: a BGRX, I420 (YV12), NV12, P010 or I010 frame, host or device."""
     _fields_ = [("format", C.c_int), ("colorspace", C.c_int), ("location", C.c_uint8),
                 ("width", C.c_size_t), ("height", C.c_size_t),
                 ("planes", C.c_void_p * 3), ("strides", C.c_ssize_t * 3)]
@@ -124,6 +125,8 @@ _HOOK_SIGS = {
     "ju_debug_e4m3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "ju_debug_yuv": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_yuv10": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
+                                 _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_yuv_items": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_size_t, C.c_size_t, _P(C.c_void_p),
                                      _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
@@ -316,20 +319,22 @@ class Runtime:
 
     def process_yuv(self, y: np.ndarray, u: np.ndarray, v: Optional[np.ndarray] = None, fmt: int = FMT_I420,
                     colorspace: int = CS_BT709_LIMITED, out_format: Optional[int] = None):
-        """Host planes in, host planes out.  ``fmt`` FMT_I420: ``y, u, v``; FMT_NV12: ``y, uv`` (``v`` None).
-        ``out_format`` (default: ``fmt``): FMT_I420 -> ``(y, u, v)``, FMT_NV12 -> ``(y, uv)``, FMT_BGRX -> the
-        ``[4H, 4W, 4]`` BGRX frame."""
+        """Host planes in, host planes out.  ``fmt`` FMT_I420 / FMT_I010: ``y, u, v``; FMT_NV12 / FMT_P010: ``y, uv``
+        (``v`` None); the 10-bit formats take and return ``uint16`` planes.  ``out_format`` (default: ``fmt``):
+        FMT_I420 / FMT_I010 -> ``(y, u, v)``, FMT_NV12 / FMT_P010 -> ``(y, uv)``, FMT_BGRX -> the ``[4H, 4W, 4]`` BGRX
+        frame."""
         out_format = fmt if out_format is None else out_format
-        planes = [y, u] if fmt == FMT_NV12 else [y, u, v]
+        planes = [y, u] if fmt in (FMT_NV12, FMT_P010) else [y, u, v]
         inp = host_frame(fmt, planes, colorspace)
         ow, oh = self.output_width, self.output_height
+        sample = np.uint16 if out_format in (FMT_P010, FMT_I010) else np.uint8
         if out_format == FMT_BGRX:
             res = [np.empty((oh, ow, 4), np.uint8)]
-        elif out_format == FMT_NV12:
-            res = [np.empty((oh, ow), np.uint8), np.empty((oh // 2, ow), np.uint8)]
+        elif out_format in (FMT_NV12, FMT_P010):
+            res = [np.empty((oh, ow), sample), np.empty((oh // 2, ow), sample)]
         else:
-            res = [np.empty((oh, ow), np.uint8), np.empty((oh // 2, ow // 2), np.uint8),
-                   np.empty((oh // 2, ow // 2), np.uint8)]
+            res = [np.empty((oh, ow), sample), np.empty((oh // 2, ow // 2), sample),
+                   np.empty((oh // 2, ow // 2), sample)]
         self.process_frame(inp, host_frame(out_format, res, colorspace))
         return res[0] if out_format == FMT_BGRX else tuple(res)
 
@@ -475,11 +480,13 @@ def _frame(fmt: int, colorspace: int, location: int, width: int, height: int, pt
 
 def host_frame(fmt: int, planes, colorspace: int = CS_BT709_LIMITED) -> JuFrame:
     """Describe numpy planes as a host frame.  FMT_BGRX: ``[bgrx [H, W, 4]]``; FMT_I420: ``[y [H, W], u, v
-    [H/2, W/2]]``; FMT_NV12: ``[y [H, W], uv [H/2, W]]``.  Any row stride (a ``[::-1]`` view is bottom-up); the
-    columns must be contiguous.  The arrays must outlive the call."""
+    [H/2, W/2]]``; FMT_NV12: ``[y [H, W], uv [H/2, W]]``; FMT_I010 / FMT_P010: the same shapes as ``uint16``.  Any
+    row stride (a ``[::-1]`` view is bottom-up; the frame's strides are the arrays' byte strides); the columns must be
+    contiguous.  The arrays must outlive the call."""
+    deep = fmt in (FMT_P010, FMT_I010)
     for p in planes:
-        if p.dtype != np.uint8 or p.strides[1] != (4 if fmt == FMT_BGRX else 1):
-            raise ValueError("planes must be uint8 with contiguous columns")
+        if p.dtype != (np.uint16 if deep else np.uint8) or p.strides[1] != (4 if fmt == FMT_BGRX else (2 if deep else 1)):
+            raise ValueError("planes must be uint8 (P010 / I010: uint16) with contiguous columns")
     y = planes[0]
     return _frame(fmt, colorspace, LOC_CPU, y.shape[1], y.shape[0], [p.ctypes.data for p in planes],
                   [p.strides[0] for p in planes])
@@ -488,11 +495,12 @@ def host_frame(fmt: int, planes, colorspace: int = CS_BT709_LIMITED) -> JuFrame:
 def device_frame(fmt: int, width: int, height: int, ptrs, strides=None,
                  colorspace: int = CS_BT709_LIMITED) -> JuFrame:
     """A device frame from raw device pointers (or torch tensors: their ``data_ptr()``); ``strides`` default to
-    dense rows (BGRX 4W, Y W, I420 chroma W/2, NV12 chroma W)."""
+    dense rows in bytes (BGRX 4W, Y W, I420 chroma W/2, NV12 chroma W; P010 / I010 twice that)."""
     ptrs = [p.data_ptr() if hasattr(p, "data_ptr") else int(p) for p in ptrs]
     if strides is None:
         strides = {FMT_BGRX: [4 * width], FMT_I420: [width, width // 2, width // 2],
-                   FMT_NV12: [width, width]}[fmt]
+                   FMT_NV12: [width, width], FMT_P010: [2 * width, 2 * width],
+                   FMT_I010: [2 * width, width, width]}[fmt]
     return _frame(fmt, colorspace, LOC_DEVICE, width, height, ptrs, strides)
 
 

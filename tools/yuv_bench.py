@@ -1,12 +1,14 @@
-"""Per-call frames/s of ju_process_frame on BGRX, NV12 and I420 frames, host and device, psp-quality at 480x270.
+"""Per-call frames/s of ju_process_frame on BGRX, NV12, I420 and P010 frames, host and device, psp-quality at 480x270.
 
 Every variant goes through the same runtime in turn (interleaved rounds of --frames-per-round frames), each call
 synchronous (ju_process_frame / ju_process), so that the clock and the other work on the machine are shared alike.
 Prints one JSON line.  --kernels instead runs the two conversion kernels alone at --kernel-size (default 1920x1080)
-through ju_debug_yuv, for a `rocprofv3 --kernel-trace --stats` run (the test flavour of the library is needed).
+through ju_debug_yuv, for a `rocprofv3 --kernel-trace --stats` run (the test flavour of the library is needed), and in
+the same run the three 10-bit kernels (ju_debug_yuv10: decode, encode from a u8 frame, encode from an f16 tensor; P010
+and I010) at that size plus their decode at --small-size (default 480x270, the LR frame of the flagship workload).
 
 --passes N adds the look-ahead variants, N frames per call: nv12_host_pass, i420_host_pass, nv12_device_pass
-(ju_process_frames) and bgrx_host_pass, bgrx_device_pass (ju_process_batch), interleaved with the per-call variants in
+(ju_process_frames), p010_host_pass, p010_device_pass alike, and bgrx_host_pass, bgrx_device_pass (ju_process_batch), interleaved with the per-call variants in
 the same process; --runs repeats the whole measurement, and the result also goes to --out
 (profiles/yuv_pass_bench.json); --only limits the variants (a `rocprofv3 --kernel-trace --memory-copy-trace` run).  --kernels --items K: K frames at --kernel-size through ONE launch of the pass's decode
 kernel (ju_debug_yuv_items) and through K launches of the single-frame kernel, for the same kind of trace."""
@@ -29,13 +31,17 @@ import torch  # noqa: E402  (torch's HIP runtime first, as bench.py does)
 from joshupscale_amd import model_file as M  # noqa: E402
 from joshupscale_amd import runtime as R  # noqa: E402
 import yuv_reference as Y  # noqa: E402
+import yuv10_reference as T  # noqa: E402
 
-FORMATS = {"bgrx": R.FMT_BGRX, "nv12": R.FMT_NV12, "i420": R.FMT_I420}
+FORMATS = {"bgrx": R.FMT_BGRX, "nv12": R.FMT_NV12, "i420": R.FMT_I420, "p010": R.FMT_P010}
+TEN = (R.FMT_P010, R.FMT_I010)
 
 
 def planes_for(fmt, h, w, bgrx, cs):
     if fmt == R.FMT_BGRX:
         return [bgrx]
+    if fmt in TEN:
+        return T.to_words(fmt, *T.encode10(T.p_from_u8(bgrx), cs))
     y, u, v = Y.encode(bgrx, cs)
     return [y, Y.to_nv12(u, v)] if fmt == R.FMT_NV12 else [y, u, v]
 
@@ -43,9 +49,15 @@ def planes_for(fmt, h, w, bgrx, cs):
 def empty_planes(fmt, h, w):
     if fmt == R.FMT_BGRX:
         return [np.zeros((h, w, 4), np.uint8)]
-    if fmt == R.FMT_NV12:
-        return [np.zeros((h, w), np.uint8), np.zeros((h // 2, w), np.uint8)]
-    return [np.zeros((h, w), np.uint8), np.zeros((h // 2, w // 2), np.uint8), np.zeros((h // 2, w // 2), np.uint8)]
+    dt = np.uint16 if fmt in TEN else np.uint8
+    if fmt in (R.FMT_NV12, R.FMT_P010):
+        return [np.zeros((h, w), dt), np.zeros((h // 2, w), dt)]
+    return [np.zeros((h, w), dt), np.zeros((h // 2, w // 2), dt), np.zeros((h // 2, w // 2), dt)]
+
+
+def to_device(plane, dev):
+    """A device copy of a host plane (uint16 planes travel as int16: the bytes are what counts)."""
+    return torch.from_numpy(plane.view(np.int16) if plane.dtype == np.uint16 else plane).to(dev)
 
 
 def frame_bench(args):
@@ -69,8 +81,8 @@ def frame_bench(args):
                     keep.append((pin, pout))
                     pairs.append((R.host_frame(fmt, pin, cs), R.host_frame(fmt, pout, cs)))
                 else:
-                    din = [torch.from_numpy(p).to(dev) for p in pin]
-                    dout = [torch.zeros(p.shape, dtype=torch.uint8, device=dev) for p in pout]
+                    din = [to_device(p, dev) for p in pin]
+                    dout = [to_device(p, dev) for p in pout]
                     keep.append((din, dout))
                     pairs.append((R.device_frame(fmt, w, h, din, colorspace=cs),
                                   R.device_frame(fmt, 4 * w, 4 * h, dout, colorspace=cs)))
@@ -172,8 +184,27 @@ def kernel_bench(args):
                     raise RuntimeError(lib.ju_last_error().decode())
             res[f"{name}_{'encode' if direction else 'decode'}_ms_per_call"] = \
                 round((time.perf_counter() - t0) * 1e3 / args.iters, 4)
-    print(json.dumps({"metric": "ju_debug_yuv host time per synchronous call (kernel time: the trace)",
-                      "size": f"{w}x{h}", "iters": args.iters, **res}))
+    # the 10-bit kernels in the same run: decode, encode from a u8 frame, encode from an f16 tensor
+    sw, sh = (int(x) for x in args.small_size.split("x"))
+    state = torch.from_numpy(rng.uniform(-0.5, 0.5, (h, w, 4)).astype(np.float16)).to(dev)
+    small_out = torch.zeros((sh, sw, 4), dtype=torch.uint8, device=dev)
+    for name, fmt in (("p010", R.FMT_P010), ("i010", R.FMT_I010)):
+        for (pw, ph), ops in (((w, h), ((1, "encode8", bgrx, 4 * w), (2, "encode_state", state, 0), (0, "decode", out, 4 * w))),
+                              ((sw, sh), ((0, "decode_small", small_out, 4 * sw),))):
+            planes = [to_device(rng.integers(0, 1024, p.shape, dtype=np.uint16) << (6 if fmt == R.FMT_P010 else 0), dev)
+                      for p in empty_planes(fmt, ph, pw)]
+            ptrs = (C.c_void_p * 3)(*([p.data_ptr() for p in planes] + [None] * (3 - len(planes))))
+            strides = (C.c_ssize_t * 3)(*([2 * p.stride(0) for p in planes] + [0] * (3 - len(planes))))
+            torch.cuda.synchronize()
+            for op, what, image, image_stride in ops:
+                t0 = time.perf_counter()
+                for _ in range(args.iters):
+                    rc = lib.ju_debug_yuv10(op, fmt, R.CS_BT709_LIMITED, pw, ph, image.data_ptr(), image_stride, ptrs, strides)
+                    if rc != 0:
+                        raise RuntimeError(lib.ju_last_error().decode())
+                res[f"{name}_{what}_ms_per_call"] = round((time.perf_counter() - t0) * 1e3 / args.iters, 4)
+    print(json.dumps({"metric": "ju_debug_yuv / ju_debug_yuv10 host time per synchronous call (kernel time: the trace)",
+                      "size": f"{w}x{h}", "small_size": f"{sw}x{sh}", "iters": args.iters, **res}))
 
 
 def items_bench(args):
@@ -212,6 +243,7 @@ def main():
     ap.add_argument("--frames-per-round", type=int, default=64)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--kernel-size", default="1920x1080")
+    ap.add_argument("--small-size", default="480x270", help="with --kernels: the second size of the 10-bit decode")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--passes", type=int, default=0, help="frames per look-ahead call (2..8) of the *_pass variants; 0: none")
     ap.add_argument("--runs", type=int, default=1, help="repeat the whole interleaved measurement")
