@@ -255,6 +255,45 @@ JU_API int ju_get_size(const ju_runtime *runtime, size_t *input_width, size_t *i
  * runtime as the OBS filter does on a model switch (obs_plugin/src/filter.cc:146-151). */
 JU_API int ju_reset(ju_runtime *runtime);
 
+/* ---- sources of any size, masked pass-through (docs/source_stage.md) ------------------------------------------------
+ * What the reference's only caller of its shipped models, the OBS filter, does around processImage in its graphics API:
+ * it draws a source of any size into the model's input texture (obs_plugin/src/filter.cc:351-379) and draws the
+ * point-sampled source back over the upscaled frame through a mask, so that HUD and text stay the crisp source
+ * (filter.cc:215-217, 393-402, obs_plugin/data/effects/blend.effect, obs_plugin/data/mask.png).  Here both are kernels
+ * inside the runtime, in integers, defined exactly (docs/source_stage.md; tests/source_reference.py).  Both settings are
+ * opt-in and per runtime; with neither set every entry point behaves byte for byte as without them.  ju_reset keeps both.
+ *
+ * ju_set_source_size: input frames are src_width x src_height from now on -- on EVERY entry point, exactly that size
+ * (YUV: even), anything else is JU_ERR_INVALID_ARGUMENT before anything is launched -- and are scaled to the model's
+ * input on the GPU: out = (sum qy qx src + 2^23) >> 24 with 12-bit triangle-filter coefficients (Pillow's BILINEAR
+ * before its quantisation), X = 0; a source of the model's size passes through byte for byte.  A YUV source is decoded
+ * at source size by the conversion of ju_process_frame, unchanged, then scaled.  Host sources upload at source size.
+ * (0, 0) turns it off.  filter: JU_SCALE_TRIANGLE, the only value.  Limits (JU_ERR_INVALID_ARGUMENT): each source axis
+ * 2 .. 8192 and within a factor of 16 of the model's input axis, either way (at most 33 taps per axis).
+ * ju_get_size keeps reporting the model's sizes; ju_get_source_size reports (0, 0) while off.
+ *
+ * ju_set_source_mask: a BGRX image of any size (1 .. 16384 per axis), JU_LOC_CPU or JU_LOC_DEVICE, copied to device
+ * memory by the call; NULL removes it.  For output pixel (x, y) of the OW x OH frame the source texel is
+ * (floor((2x+1) SW / (2 OW)), floor((2y+1) SH / (2 OH))) -- point sampled, the source being the (decoded) frame at source
+ * size, or the model-size input frame while no source size is set -- the mask texel likewise with the mask's size,
+ * a = 765 - (Rm + Gm + Bm), out = (src a + gen (765 - a) + 382) / 765 per channel, X = 0: a white mask shows the network's
+ * frame, a black one the source.  The blend touches only the frame handed to the caller: recurrent state, frame history
+ * and f16 state are those of the unmasked run.  While a mask is set a JU_FMT_P010 / JU_FMT_I010 output is encoded from
+ * the blended 8-bit frame (257 x u8), whatever "hbd_from_state" says -- that stat keeps reporting the model's property.
+ *
+ * While either is set every frame of ju_process, ju_enqueue, ju_process_frame, ju_enqueue_frame, ju_process_frames,
+ * ju_process_batch, ju_process_group and the C++ processImage runs on its own, in stream order, through the runtime's
+ * staging buffers (scale, the staged graph, blend, stage-out): no direct device path, no look-ahead or group pass
+ * ("lookahead_frames" / "group_frames" do not count them, "source_stage_frames" does), ju_prepare_frames /
+ * ju_prepare_batch capture nothing.  JU_LOC_GRAPHICS_RESOURCE inputs are refused while a source size is set (outputs,
+ * and inputs under a mask alone, are taken).  Turning both off restores the other paths.
+ * Not provided: scaled or masked frames inside look-ahead or group passes; a scaler on the output side; filters other
+ * than the triangle; OBS's own OBS_EFFECT_BILINEAR_LOWRES arithmetic (it is not in the reference tree). */
+enum { JU_SCALE_TRIANGLE = 0 };
+JU_API int ju_set_source_size(ju_runtime *runtime, size_t src_width, size_t src_height, int filter);
+JU_API int ju_get_source_size(const ju_runtime *runtime, size_t *src_width, size_t *src_height);
+JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
+
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing
  * call on the same thread. */
@@ -314,6 +353,8 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * "group_frames" (frames this runtime got from ju_process_group passes),
  * "lookahead_frames" (frames that went through look-ahead passes; of them "lookahead_host_frames" with a host side,
  * "lookahead_yuv_frames" with a YUV side, 8- or 10-bit),
+ * "source_scaled" / "source_mask" (1 while ju_set_source_size / ju_set_source_mask is in effect), "source_stage_frames"
+ * (frames that went through the source stage),
  * "hbd_from_state" (1: this runtime encodes JU_FMT_P010 / JU_FMT_I010 outputs from its f16 state; 0: from the 8-bit
  * frame -- normalize_brightness and output_flow models),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,

@@ -79,6 +79,17 @@ JU_API int ju_debug_yuv_items(int count, const int *formats, const int *colorspa
 JU_API int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size_t height, void *image,
     ptrdiff_t image_stride, void *const planes[3], const ptrdiff_t strides[3]);
 
+/* The source stage's kernels alone (docs/source_stage.md), on caller-supplied device buffers of BGRX rows with any byte
+ * alignment and any signed strides, on the current device (synchronous).  op 0: the scaler -- `src` (src_width x
+ * src_height) -> `dst` (dst_width x dst_height), tables built as ju_set_source_size builds them; the mask arguments are
+ * ignored.  op 1: the blend -- `dst` is the frame (the network's output, rewritten in place), `src` the source that shows
+ * where the mask is dark, `mask` the mask, each of its own size.  op 2: no device and no buffers -- only the limits
+ * ju_set_source_size applies to a source of src_width x src_height for a model input of dst_width x dst_height, with its
+ * message (JU_ERR_INVALID_ARGUMENT) or JU_OK. */
+JU_API int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, const void *src,
+    ptrdiff_t src_stride, size_t src_width, size_t src_height, const void *mask, ptrdiff_t mask_stride, size_t mask_width,
+    size_t mask_height);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

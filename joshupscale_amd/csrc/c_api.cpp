@@ -296,6 +296,23 @@ int ju_get_size(const ju_runtime *runtime, size_t *input_width, size_t *input_he
 	});
 }
 
+int ju_set_source_size(ju_runtime *runtime, size_t src_width, size_t src_height, int filter) {
+	return guarded([&] { engineOf(runtime).setSourceSize(src_width, src_height, filter); });
+}
+
+int ju_get_source_size(const ju_runtime *runtime, size_t *src_width, size_t *src_height) {
+	return guarded([&] { engineOf(const_cast<ju_runtime *>(runtime)).sourceSize(src_width, src_height); });
+}
+
+int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask) {
+	return guarded([&] {
+		ju::Engine &e = engineOf(runtime);
+		if (mask == nullptr) return e.setSourceMask(nullptr);
+		const ju::Frame f = toFrame(mask);
+		e.setSourceMask(&f);
+	});
+}
+
 int ju_reset(ju_runtime *runtime) {
 	return guarded([&] { engineOf(runtime).reset(); });
 }
@@ -523,6 +540,50 @@ int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size_t heig
 		} else {
 			ju::launchStateToYuv420p10(p010, image, ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
 		}
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, const void *src,
+    ptrdiff_t src_stride, size_t src_width, size_t src_height, const void *mask, ptrdiff_t mask_stride, size_t mask_width,
+    size_t mask_height) {
+	return guarded([&] {
+		if (op == 2) {  // the limits of ju_set_source_size alone: no device
+			const std::string problem = ju::sourceSizeProblem(src_width, src_height, dst_width, dst_height);
+			if (!problem.empty()) throw std::invalid_argument("ju_set_source_size: " + problem);
+			return;
+		}
+		if (op != 0 && op != 1) throw std::invalid_argument("ju_debug_source: op must be 0, 1 or 2");
+		constexpr size_t kMost = 1u << 15;
+		if (dst == nullptr || src == nullptr || dst_width < 1 || dst_height < 1 || src_width < 1 || src_height < 1 ||
+		    dst_width > kMost || dst_height > kMost || src_width > kMost || src_height > kMost) {
+			throw std::invalid_argument("ju_debug_source: null buffer or a size outside 1 .. 32768");
+		}
+		const int dw = static_cast<int>(dst_width), dh = static_cast<int>(dst_height);
+		const int sw = static_cast<int>(src_width), sh = static_cast<int>(src_height);
+		if (op == 0) {
+			const ju::ScaleAxisHost x = ju::buildScaleAxis(sw, dw), y = ju::buildScaleAxis(sh, dh);
+			auto upload = [](const ju::ScaleAxisHost &a, ju::DeviceBuffer *start, ju::DeviceBuffer *taps) {
+				*start = ju::DeviceBuffer(a.start.size() * sizeof(int));
+				start->upload(a.start.data(), a.start.size() * sizeof(int));
+				*taps = ju::DeviceBuffer(a.taps.size() * sizeof(std::uint16_t));
+				taps->upload(a.taps.data(), a.taps.size() * sizeof(std::uint16_t));
+			};
+			ju::DeviceBuffer xs, xt, ys, yt;
+			upload(x, &xs, &xt);
+			upload(y, &ys, &yt);
+			ju::launchScaleBgrx(static_cast<const std::uint8_t *>(src), src_stride, sw, sh, static_cast<std::uint8_t *>(dst),
+			    dst_stride, dw, dh, {xs.as<int>(), xt.as<std::uint16_t>()}, {ys.as<int>(), yt.as<std::uint16_t>()},
+			    ju::scaleSpan(x), nullptr);
+			JU_HIP(hipStreamSynchronize(nullptr));
+			return;
+		}
+		if (mask == nullptr || mask_width < 1 || mask_height < 1 || mask_width > kMost || mask_height > kMost) {
+			throw std::invalid_argument("ju_debug_source: null mask or a mask size outside 1 .. 32768");
+		}
+		ju::launchMaskBlend(static_cast<std::uint8_t *>(dst), dst_stride, dw, dh, static_cast<const std::uint8_t *>(src),
+		    src_stride, sw, sh, static_cast<const std::uint8_t *>(mask), mask_stride, static_cast<int>(mask_width),
+		    static_cast<int>(mask_height), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

@@ -1330,6 +1330,19 @@ void Engine::maybeRestoreResident() {
 	}
 }
 
+namespace {
+AnyFrame anyOf(const Frame &f) {
+	AnyFrame a;
+	a.bgrx = f;
+	return a;
+}
+std::vector<AnyFrame> anyOf(const Frame *f, int n) {
+	std::vector<AnyFrame> a(static_cast<std::size_t>(std::max(n, 0)));
+	for (int i = 0; i < n; ++i) a[static_cast<std::size_t>(i)].bgrx = f[i];
+	return a;
+}
+}  // namespace
+
 void Engine::reset() {
 	DeviceGuard g(m_Device);
 	if (m_Config.recurrent()) {  // (a flow-free model has no state: nothing to zero)
@@ -1568,11 +1581,17 @@ std::size_t Engine::yuvStageBytes(std::size_t w, std::size_t h) {
 // stageOut would throw, so that a refused call has not run the step).
 void Engine::checkFrame(const AnyFrame &f, bool input) const {
 	const FrameSize fs = frameSize();
-	const std::size_t w = input ? fs.inputWidth : fs.outputWidth, h = input ? fs.inputHeight : fs.outputHeight;
+	const bool scaled = input && m_SrcW != 0;  // (input frames are the source's size while one is set)
+	const std::size_t w = scaled ? m_SrcW : (input ? fs.inputWidth : fs.outputWidth);
+	const std::size_t h = scaled ? m_SrcH : (input ? fs.inputHeight : fs.outputHeight);
 	const std::string side = input ? "input" : "output";
-	const std::string size = std::to_string(w) + "x" + std::to_string(h);
+	const std::string size = std::to_string(w) + "x" + std::to_string(h) + (scaled ? " (the source size set)" : "");
 	if (!f.yuv) {
 		const Frame &b = f.bgrx;
+		if (scaled && b.location == Location::GraphicsResource) {
+			throw std::invalid_argument("processFrame: graphics resources cannot be inputs while a source size is set "
+			                            "(the scaler reads host or device memory)");
+		}
 		if (b.location == Location::GraphicsResource) {
 			if (b.ptr == nullptr) throw std::invalid_argument("processFrame: NULL graphics resource");
 			return;  // (the texture's own extent is checked when it is mapped)
@@ -1630,9 +1649,9 @@ void Engine::stageInYuv(const YuvFrame &in) {
 
 // one decode launch on the engine's stream: planes of an input-sized frame -> BGRX rows
 void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::uint8_t *bgrx,
-    std::ptrdiff_t bgrxStride) {
+    std::ptrdiff_t bgrxStride, std::size_t width, std::size_t height) {
 	const FrameSize fs = frameSize();
-	const int w = static_cast<int>(fs.inputWidth), h = static_cast<int>(fs.inputHeight);
+	const int w = static_cast<int>(width ? width : fs.inputWidth), h = static_cast<int>(height ? height : fs.inputHeight);
 	if (tenBit(format)) {
 		launchYuv420p10ToBgrx(format == PixelFormat::P010, planes, yuvDecodeCoefficients10(colorspace), bgrx, bgrxStride,
 		    w, h, m_Stream);
@@ -1651,7 +1670,7 @@ void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
 	if (!tenBit(format)) {
 		launchBgrxToYuv420(format == PixelFormat::Nv12, bgrx, bgrxStride, yuvEncodeCoefficients(colorspace), planes, w, h,
 		    m_Stream);
-	} else if (m_HbdFromState) {
+	} else if (m_HbdFromState && m_MaskW == 0) {  // (a mask: the blended frame exists in 8 bits only)
 		launchStateToYuv420p10(format == PixelFormat::P010, state, yuvEncodeCoefficients10(colorspace), planes, w, h,
 		    m_Stream);
 	} else {
@@ -1670,6 +1689,122 @@ void Engine::stageOutYuv(const YuvFrame &out) {
 	encodeYuv(out.format, out.colorspace, pl, m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4),
 	    m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get());
 	if (host) copyPlanes(out, m_YuvOutStage.as<std::uint8_t>(), false, m_Stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Source stage (docs/source_stage.md).  What the reference's OBS filter does around processImage in its graphics API
+// (obs_plugin/src/filter.cc:351-379: any source drawn into the model's input texture; :393-402 with blend.effect: the
+// point-sampled source drawn back over the output through mask.png), as two kernels around the staged graph of
+// submitFrame: scale_bgrx_kernel fills m_InStage from the source frame, mask_blend_kernel rewrites m_OutStage.  Both
+// settings are per runtime and opt-in; neither touches a captured graph, the state or the frame history.
+// ---------------------------------------------------------------------------------------------------------------
+void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
+	DeviceGuard g(m_Device);
+	if (filter != 0) {
+		throw std::invalid_argument("ju_set_source_size: unknown filter " + std::to_string(filter) +
+		                            " (JU_SCALE_TRIANGLE is the only one)");
+	}
+	if (width == 0 && height == 0) {
+		m_Stream.synchronize();  // (enqueued frames may still read the tables)
+		m_SrcW = m_SrcH = 0;
+		m_ScaleX = DeviceBuffer();
+		m_ScaleY = DeviceBuffer();
+		m_SrcStage = DeviceBuffer();
+		m_SrcYuvStage = DeviceBuffer();
+		return;
+	}
+	const FrameSize fs = frameSize();
+	const std::string problem = sourceSizeProblem(width, height, fs.inputWidth, fs.inputHeight);
+	if (!problem.empty()) throw std::invalid_argument("ju_set_source_size: " + problem);
+	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(width), static_cast<int>(fs.inputWidth));
+	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(height), static_cast<int>(fs.inputHeight));
+	// one buffer per axis: the start indices, then the taps
+	auto uploadAxis = [](const ScaleAxisHost &a) {
+		const std::size_t startBytes = a.start.size() * sizeof(int), tapBytes = a.taps.size() * sizeof(std::uint16_t);
+		std::vector<unsigned char> host(startBytes + tapBytes);
+		std::memcpy(host.data(), a.start.data(), startBytes);
+		std::memcpy(host.data() + startBytes, a.taps.data(), tapBytes);
+		DeviceBuffer buf(host.size());
+		buf.upload(host.data(), host.size());
+		return buf;
+	};
+	DeviceBuffer bx = uploadAxis(x), by = uploadAxis(y);
+	DeviceBuffer stage(width * height * 4), yuvStage(yuvStageBytes(width, height));
+	m_Stream.synchronize();
+	m_ScaleX = std::move(bx);
+	m_ScaleY = std::move(by);
+	m_SrcStage = std::move(stage);
+	m_SrcYuvStage = std::move(yuvStage);
+	m_ScaleXDev = {m_ScaleX.as<int>(), reinterpret_cast<const std::uint16_t *>(m_ScaleX.as<int>() + x.start.size())};
+	m_ScaleYDev = {m_ScaleY.as<int>(), reinterpret_cast<const std::uint16_t *>(m_ScaleY.as<int>() + y.start.size())};
+	m_ScaleSpan = scaleSpan(x);
+	m_SrcW = width;
+	m_SrcH = height;
+}
+
+void Engine::sourceSize(std::size_t *width, std::size_t *height) const {
+	if (width) *width = m_SrcW;
+	if (height) *height = m_SrcH;
+}
+
+void Engine::setSourceMask(const Frame *mask) {
+	DeviceGuard g(m_Device);
+	if (mask == nullptr) {
+		m_Stream.synchronize();
+		m_Mask = DeviceBuffer();
+		m_MaskW = m_MaskH = 0;
+		m_MaskStride = 0;
+		return;
+	}
+	if (mask->location != Location::Host && mask->location != Location::Device) {
+		throw std::invalid_argument("ju_set_source_mask: the mask must be host or device memory");
+	}
+	constexpr std::size_t kMaskMax = 16384;
+	if (mask->ptr == nullptr || mask->width < 1 || mask->height < 1 || mask->width > kMaskMax || mask->height > kMaskMax) {
+		throw std::invalid_argument("ju_set_source_mask: the mask must be 1 .. 16384 pixels on each axis");
+	}
+	const std::size_t rowBytes = mask->width * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	if (mask->stride > -plain && mask->stride < plain) {
+		throw std::invalid_argument("ju_set_source_mask: |stride| smaller than a row");
+	}
+	// copied once, in the caller's memory order (a bottom-up mask stays bottom-up and is read with a negative stride)
+	DeviceBuffer buf(rowBytes * mask->height);
+	const bool up = mask->stride > 0;
+	const auto *first = static_cast<const std::uint8_t *>(mask->ptr);
+	const std::uint8_t *lowest = up ? first : first + static_cast<std::ptrdiff_t>(mask->height - 1) * mask->stride;
+	JU_HIP(hipMemcpy2D(buf.get(), rowBytes, lowest, static_cast<std::size_t>(up ? mask->stride : -mask->stride), rowBytes,
+	    mask->height, mask->location == Location::Host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+	m_Stream.synchronize();
+	m_Mask = std::move(buf);
+	m_MaskW = mask->width;
+	m_MaskH = mask->height;
+	m_MaskStride = up ? plain : -plain;
+}
+
+// The input of a frame while a source size is set, as BGRX rows at source size: a device image is read where it is, a
+// host image is uploaded in its memory order, YUV planes are decoded by the existing conversion, unchanged.
+Engine::SourceView Engine::stageInSource(const AnyFrame &in) {
+	const std::size_t rowBytes = m_SrcW * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	auto *stage = m_SrcStage.as<std::uint8_t>();
+	if (in.yuv) {
+		const YuvFrame &y = in.planes;
+		const bool host = y.location != Location::Device;
+		if (host) copyPlanes(y, m_SrcYuvStage.as<std::uint8_t>(), true, m_Stream);
+		const YuvPlanes pl = host ? stagedPlanes(y, m_SrcYuvStage.as<std::uint8_t>()) : callerPlanes(y);
+		decodeYuv(y.format, y.colorspace, pl, stage, plain, m_SrcW, m_SrcH);
+		return {stage, plain};
+	}
+	const Frame &b = in.bgrx;
+	auto *src = static_cast<std::uint8_t *>(b.ptr);
+	if (b.location == Location::Device) return {src, b.stride};
+	const bool up = b.stride > 0;
+	const std::uint8_t *lowest = up ? src : src + static_cast<std::ptrdiff_t>(m_SrcH - 1) * b.stride;
+	JU_HIP(hipMemcpy2DAsync(stage, rowBytes, lowest, static_cast<std::size_t>(up ? b.stride : -b.stride), rowBytes, m_SrcH,
+	    hipMemcpyHostToDevice, m_Stream));
+	if (up) return {stage, plain};
+	return {stage + static_cast<std::ptrdiff_t>(m_SrcH - 1) * plain, -plain};
 }
 
 bool Engine::directEligible(const Frame &in, const Frame &out) const {
@@ -1717,6 +1852,11 @@ void Engine::captureDirect(DirectEntry *e, int idx) {
 int Engine::prepareFrames(const Frame &in, const Frame &out) {
 	DeviceGuard g(m_Device);
 	const FrameSize fs = frameSize();
+	if (sourceStage()) {  // every frame goes through the staging buffers, whose graphs exist
+		checkFrame(anyOf(in), true);
+		checkFrame(anyOf(out), false);
+		return 0;
+	}
 	if (in.location != Location::GraphicsResource &&
 	    (in.ptr == nullptr || in.width != fs.inputWidth || in.height != fs.inputHeight)) {
 		throw std::invalid_argument("prepareFrames: input image must be exactly " + std::to_string(fs.inputWidth) + "x" +
@@ -1951,6 +2091,7 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 // place (directEligible's conditions) or a host image of the right size (staged through the pass's own device buffers).
 // A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
+	if (sourceStage()) return false;  // (scaled / masked frames run one by one through submitFrame)
 	const FrameSize fs = frameSize();
 	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align) {
 		if (a.yuv) {
@@ -1966,19 +2107,6 @@ bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
 	};
 	return side(in, fs.inputWidth, fs.inputHeight, 4) && side(out, fs.outputWidth, fs.outputHeight, 8);
 }
-
-namespace {
-AnyFrame anyOf(const Frame &f) {
-	AnyFrame a;
-	a.bgrx = f;
-	return a;
-}
-std::vector<AnyFrame> anyOf(const Frame *f, int n) {
-	std::vector<AnyFrame> a(static_cast<std::size_t>(std::max(n, 0)));
-	for (int i = 0; i < n; ++i) a[static_cast<std::size_t>(i)].bgrx = f[i];
-	return a;
-}
-}  // namespace
 
 bool Engine::passEligible(const Frame &in, const Frame &out) const { return passEligible(anyOf(in), anyOf(out)); }
 
@@ -2235,6 +2363,7 @@ void setPassRerun(int on) { g_PassRerun = on; }
 void Engine::processBatch(const Frame *in, const Frame *out, int count) {
 	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("processBatch: bad arguments");
 	const std::vector<AnyFrame> anyIn = anyOf(in, count), anyOut = anyOf(out, count);
+	if (sourceStage()) return processFrames(anyIn.data(), anyOut.data(), count);  // (every frame checked before the first runs)
 	runPasses(anyIn.data(), anyOut.data(), count);
 }
 
@@ -2380,8 +2509,13 @@ bool Engine::sameModel(const Engine &o) const {
 // What process() would refuse for its size, checked up front (a group call launches nothing before every frame passed)
 void Engine::checkGroupFrame(const Frame &f, bool input) const {
 	const FrameSize fs = frameSize();
-	const std::size_t w = input ? fs.inputWidth : fs.outputWidth, h = input ? fs.inputHeight : fs.outputHeight;
+	const bool scaled = input && m_SrcW != 0;
+	const std::size_t w = scaled ? m_SrcW : (input ? fs.inputWidth : fs.outputWidth);
+	const std::size_t h = scaled ? m_SrcH : (input ? fs.inputHeight : fs.outputHeight);
 	const char *side = input ? "input" : "output";
+	if (scaled && f.location == Location::GraphicsResource) {
+		throw std::invalid_argument("ju_process_group: graphics resources cannot be inputs while a source size is set");
+	}
 	if (f.ptr == nullptr) throw std::invalid_argument(std::string("ju_process_group: NULL ") + side + " image");
 	if (f.width != w || f.height != h) {
 		throw std::invalid_argument(std::string("ju_process_group: ") + side + " image must be exactly " + std::to_string(w) +
@@ -2620,6 +2754,7 @@ void Engine::submit(const Frame &in, const Frame &out) {
 }
 
 void Engine::enqueue(const Frame &in, const Frame &out) {
+	if (sourceStage()) return enqueueFrame(anyOf(in), anyOf(out));
 	DeviceGuard g(m_Device);
 	submit(in, out);
 }
@@ -2634,6 +2769,7 @@ void Engine::runSynchronous(const Submit &submitOne) {
 		// (submit() flipped m_Idx; the re-run needs the same binding set again.  If the
 		// fallback or the re-run throws, the failed frame must not count as a step either.)
 		m_Idx ^= 1;
+		if (sourceStage()) --m_SourceFrames;  // (submitFrame counts the frame again)
 		fallbackToLayers(code);
 		submitOne();
 		m_Stream.synchronize();
@@ -2643,6 +2779,7 @@ void Engine::runSynchronous(const Submit &submitOne) {
 }
 
 void Engine::process(const Frame &in, const Frame &out) {
+	if (sourceStage()) return processFrame(anyOf(in), anyOf(out));
 	DeviceGuard g(m_Device);
 	runSynchronous([&] { submit(in, out); });
 }
@@ -2653,7 +2790,16 @@ void Engine::process(const Frame &in, const Frame &out) {
 void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 	m_DirectIO = false;
 	bindStaging();
-	if (in.yuv) {
+	const FrameSize fs = frameSize();
+	const int inW = static_cast<int>(fs.inputWidth), inH = static_cast<int>(fs.inputHeight);
+	// what the mask lets through: the source frame at source size, or the model-size input frame
+	SourceView source{m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4)};
+	if (m_SrcW != 0) {
+		source = stageInSource(in);
+		launchScaleBgrx(source.ptr, source.stride, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH),
+		    m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4), inW, inH, m_ScaleXDev, m_ScaleYDev,
+		    m_ScaleSpan, m_Stream);
+	} else if (in.yuv) {
 		stageInYuv(in.planes);
 	} else {
 		stageIn(in.bgrx);
@@ -2663,6 +2809,15 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 		runProgram();
 		chainEnd(chain);
 	}
+	if (m_MaskW != 0) {
+		// over the frame handed to the caller only: state and history are the unmasked run's
+		launchMaskBlend(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4),
+		    static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight), source.ptr, source.stride,
+		    m_SrcW != 0 ? static_cast<int>(m_SrcW) : inW, m_SrcW != 0 ? static_cast<int>(m_SrcH) : inH,
+		    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0),
+		    m_MaskStride, static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), m_Stream);
+	}
+	if (sourceStage()) ++m_SourceFrames;
 	if (out.yuv) {
 		stageOutYuv(out.planes);
 	} else {
@@ -2917,6 +3072,9 @@ double Engine::stat(const std::string &key) const {
 	if (key == "hbd_from_state") return m_HbdFromState ? 1.0 : 0.0;  // 10-bit outputs: from the f16 state (1) / the u8 frame (0)
 	if (key == "lookahead_yuv_frames") return static_cast<double>(m_BatchYuvFrames);  // ... of them with a YUV side
 	if (key == "lookahead_max") return static_cast<double>(m_BatchMax);
+	if (key == "source_scaled") return m_SrcW != 0 ? 1.0 : 0.0;
+	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
+	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
 	if (key == "launches_per_frame") return static_cast<double>(m_Program[0].size());
 	if (key == "tower_variant") return static_cast<double>(towerVariant());  // (developer switch, tests)

@@ -125,6 +125,16 @@ public:
 	// in the reference: obs_plugin/src/filter.cc:146-151).
 	void reset();
 
+	// The source stage (docs/source_stage.md; engine.cpp, "Source stage").  setSourceSize: input frames are
+	// width x height from now on and are scaled to the model's input on the GPU ((0, 0): off; filter 0 = triangle, the
+	// only one).  setSourceMask: a BGRX image of any size, host or device, copied now (nullptr: no mask); the source is
+	// drawn over every output frame through it.  While either is set every frame of every entry point runs one by one
+	// through the staged path of submitFrame.  reset() keeps both.
+	void setSourceSize(std::size_t width, std::size_t height, int filter);
+	void sourceSize(std::size_t *width, std::size_t *height) const;
+	void setSourceMask(const Frame *mask);
+	bool sourceStage() const { return m_SrcW != 0 || m_MaskW != 0; }
+
 	FrameSize frameSize() const;
 	int device() const { return m_Device; }
 	DType dtype() const { return m_DType; }
@@ -205,7 +215,26 @@ private:
 	// every model but normalize_brightness, whose state is output_raw - b, and output_flow, whose frame is pre_warp) or,
 	// for those two, from the u8 frame like an 8-bit output.  Decided once, at creation; ju_get_stat "hbd_from_state".
 	bool m_HbdFromState = true;
-	void decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::uint8_t *bgrx, std::ptrdiff_t bgrxStride);
+	// (width x height: the frame's own size; 0 = the model's input)
+	void decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::uint8_t *bgrx, std::ptrdiff_t bgrxStride,
+	    std::size_t width = 0, std::size_t height = 0);
+	// Source stage: the size input frames must have (m_SrcW x m_SrcH, 0 = the model's input), the per-axis tables of the
+	// scaler on the device, the BGRX source frame at source size (host uploads, decoded YUV) and the host planes of a YUV
+	// source; the mask in device memory, in the caller's row order (m_MaskStride < 0: bottom-up).  m_SourceFrames: frames
+	// that went through the stage ("source_stage_frames").
+	std::size_t m_SrcW = 0, m_SrcH = 0;
+	DeviceBuffer m_ScaleX, m_ScaleY, m_SrcStage, m_SrcYuvStage;
+	ScaleAxisDev m_ScaleXDev, m_ScaleYDev;
+	int m_ScaleSpan = 0;
+	DeviceBuffer m_Mask;
+	std::size_t m_MaskW = 0, m_MaskH = 0;
+	std::ptrdiff_t m_MaskStride = 0;
+	std::uint64_t m_SourceFrames = 0;
+	struct SourceView {  // the BGRX source frame the scaler and the blend read in this call
+		const std::uint8_t *ptr = nullptr;
+		std::ptrdiff_t stride = 0;
+	};
+	SourceView stageInSource(const AnyFrame &in);
 	void encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, const std::uint8_t *bgrx,
 	    std::ptrdiff_t bgrxStride, const void *state);
 	void checkFrame(const AnyFrame &f, bool input) const;

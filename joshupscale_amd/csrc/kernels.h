@@ -11,6 +11,8 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <string>
+#include <vector>
 
 namespace ju {
 
@@ -478,6 +480,42 @@ void launchStateToYuv420p10(bool p010, const void *state, const YuvEncode10 &k, 
 // P = 257 u8 of a BGRX frame (any alignment, signed stride)
 void launchBgrxToYuv420p10(bool p010, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
     const YuvPlanes &dst, int width, int height, hipStream_t stream);
+
+// ---- source stage (source_kernels.hip; docs/source_stage.md): sources of any size, masked pass-through ---------------
+// One axis of the triangle scaler, N source samples -> M destination samples, in integers (buildScaleAxis is the
+// definition; tests/source_reference.py restates it): per destination index the first source index, the tap count
+// (at most kScaleMaxTaps) and the taps, u16, summing to exactly 4096.
+constexpr int kScaleMaxTaps = 33;
+constexpr int kScaleTapPitch = kScaleMaxTaps + 1;  // u16 per destination index: the taps, then the tap count
+constexpr int kSourceAxisMin = 2, kSourceAxisMax = 8192, kSourceRatioMax = 16;
+struct ScaleAxisHost {
+	int n = 0, m = 0;
+	std::vector<int> start;            // [m]
+	std::vector<std::uint16_t> taps;   // [m][kScaleTapPitch]
+};
+// std::invalid_argument unless 1 <= n, m and n <= 16 m and m <= 16 n (the bound that keeps an axis at 33 taps)
+ScaleAxisHost buildScaleAxis(int n, int m);
+// The same limits as one message for ju_set_source_size and its Python twin: "" when srcW x srcH may feed a model of
+// inW x inH
+std::string sourceSizeProblem(std::size_t srcW, std::size_t srcH, std::size_t inW, std::size_t inH);
+struct ScaleAxisDev {
+	const int *start = nullptr;
+	const std::uint16_t *taps = nullptr;
+};
+// BGRX rows of srcW x srcH -> BGRX rows of dstW x dstH (X = 0): out = (sum qy qx src + 2^23) >> 24 per channel.  Any
+// byte alignment, signed strides.  x / y: the device copies of buildScaleAxis(srcW, dstW) / (srcH, dstH); spanX: the most
+// source columns a tile of kScaleTileW destination columns reads (scaleSpan of the x axis).
+constexpr int kScaleTileW = 32, kScaleTileH = 8;
+int scaleSpan(const ScaleAxisHost &x);
+void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, int srcH, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int dstW, int dstH, const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX,
+    hipStream_t stream);
+// Masked pass-through over the frame `gen` (outW x outH BGRX rows, rewritten in place): per pixel the point-sampled
+// texel of `src` (srcW x srcH) and of `mask` (maskW x maskH), a = 765 - (Rm + Gm + Bm), out = (src a + gen (765 - a) +
+// 382) / 765 per channel, X = 0; pixels with a == 0 are not rewritten.  Any byte alignment, signed strides.
+void launchMaskBlend(std::uint8_t *gen, std::ptrdiff_t genStride, int outW, int outH, const std::uint8_t *src,
+    std::ptrdiff_t srcStride, int srcW, int srcH, const std::uint8_t *mask, std::ptrdiff_t maskStride, int maskW,
+    int maskH, hipStream_t stream);
 
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).

@@ -1,0 +1,248 @@
+// The source stage on gfx950 (docs/source_stage.md): a BGRX source of any size scaled to the model's input by an
+// integer triangle filter, and the source drawn back over the upscaled frame through a mask.
+//
+// Both kernels compute exactly the numpy definition of tests/source_reference.py.  The host builds the per-axis tables
+// (buildScaleAxis: start index, tap count and u16 taps summing to 4096 per destination index); the device only
+// multiplies and adds unsigned 32-bit integers:
+//
+//   scale_bgrx_kernel   one workgroup per tile of kScaleTileW x kScaleTileH destination pixels.  Vertical pass: every
+//                       source column the tile needs, for each of the tile's rows, sum qy * src (<= 255 * 4096 < 2^20,
+//                       exact) into LDS -- a thread takes four source columns, 16 bytes per load where the source rows
+//                       are 16-byte aligned, so a wave reads contiguous row segments.  Horizontal pass: a thread per
+//                       destination pixel, sum qx * LDS + 2^23 >> 24 (< 2^32).  Lanes of a half-wave read LDS columns
+//                       N / M apart (ds_read_b32: banks (a / 4) % 32 per 32-lane half), which is a 4-way conflict at
+//                       1920 -> 480; the tile stores column c at c + c / 32, which puts the 32 lanes of every power-
+//                       of-two ratio up to 16 on 32 different banks (and the vertical pass's four-column writes too).
+//   mask_blend_kernel   a thread per output pixel; mask and source are point sampled.
+//
+// Rows are addressed with their signed stride; pixels off 4-byte alignment move byte by byte.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+
+#include "kernel_common.h"
+#include "kernels.h"
+
+namespace ju {
+
+ScaleAxisHost buildScaleAxis(int n, int m) {
+	if (n < 1 || m < 1 || n > kSourceRatioMax * static_cast<long long>(m) || m > kSourceRatioMax * static_cast<long long>(n)) {
+		throw std::invalid_argument("buildScaleAxis: " + std::to_string(n) + " -> " + std::to_string(m) +
+		                            " is beyond a factor of " + std::to_string(kSourceRatioMax));
+	}
+	ScaleAxisHost a;
+	a.n = n;
+	a.m = m;
+	a.start.assign(static_cast<std::size_t>(m), 0);
+	a.taps.assign(static_cast<std::size_t>(m) * kScaleTapPitch, 0);
+	const long long N = n, M = m, D = 2 * std::max(N, M);
+	for (long long d = 0; d < M; ++d) {
+		const long long c = (2 * d + 1) * N;
+		// the first source index with a positive weight: (2 s + 1) M > c - D
+		long long s0 = (c - D) / (2 * M) - 1;
+		s0 = std::max(s0, 0LL);
+		while (s0 < N && (2 * s0 + 1) * M - c <= -D) ++s0;
+		long long w[kScaleMaxTaps];
+		int count = 0;
+		long long sum = 0;
+		for (long long s = s0; s < N; ++s) {
+			const long long t = (2 * s + 1) * M - c;
+			const long long v = D - (t < 0 ? -t : t);
+			if (v <= 0) break;
+			if (count == kScaleMaxTaps) throw std::logic_error("buildScaleAxis: more than 33 taps");
+			w[count++] = v;
+			sum += v;
+		}
+		if (count == 0) throw std::logic_error("buildScaleAxis: a destination index without taps");
+		std::uint16_t *q = a.taps.data() + static_cast<std::size_t>(d) * kScaleTapPitch;
+		long long total = 0;
+		int best = 0;
+		for (int i = 0; i < count; ++i) {
+			q[i] = static_cast<std::uint16_t>(w[i] * 4096 / sum);
+			total += q[i];
+			if (w[i] > w[best]) best = i;  // (the first of the largest)
+		}
+		q[best] = static_cast<std::uint16_t>(q[best] + (4096 - total));
+		q[kScaleMaxTaps] = static_cast<std::uint16_t>(count);
+		a.start[static_cast<std::size_t>(d)] = static_cast<int>(s0);
+	}
+	return a;
+}
+
+std::string sourceSizeProblem(std::size_t srcW, std::size_t srcH, std::size_t inW, std::size_t inH) {
+	auto axisOk = [](std::size_t n, std::size_t m) {
+		return n >= static_cast<std::size_t>(kSourceAxisMin) && n <= static_cast<std::size_t>(kSourceAxisMax) &&
+		       n <= kSourceRatioMax * m && m <= kSourceRatioMax * n;
+	};
+	if (axisOk(srcW, inW) && axisOk(srcH, inH)) return "";
+	return "source size " + std::to_string(srcW) + "x" + std::to_string(srcH) + ": each axis must be " +
+	       std::to_string(kSourceAxisMin) + " .. " + std::to_string(kSourceAxisMax) + " and within a factor of " +
+	       std::to_string(kSourceRatioMax) + " of the model's input " + std::to_string(inW) + "x" + std::to_string(inH);
+}
+
+int scaleSpan(const ScaleAxisHost &x) {
+	int span = 4;
+	for (int d0 = 0; d0 < x.m; d0 += kScaleTileW) {
+		const int d1 = std::min(d0 + kScaleTileW, x.m) - 1;
+		const int first = x.start[static_cast<std::size_t>(d0)] & ~3;
+		const int end = x.start[static_cast<std::size_t>(d1)] + x.taps[static_cast<std::size_t>(d1) * kScaleTapPitch + kScaleMaxTaps];
+		span = std::max(span, (end - first + 3) / 4 * 4);
+	}
+	return span;
+}
+
+namespace {
+
+__device__ inline unsigned loadPixel(const std::uint8_t *p) {
+	if ((reinterpret_cast<std::uintptr_t>(p) & 3) == 0) return *reinterpret_cast<const unsigned *>(p);
+	return static_cast<unsigned>(p[0]) | (static_cast<unsigned>(p[1]) << 8) | (static_cast<unsigned>(p[2]) << 16) |
+	       (static_cast<unsigned>(p[3]) << 24);
+}
+
+__device__ inline void storePixel(std::uint8_t *p, unsigned v) {
+	if ((reinterpret_cast<std::uintptr_t>(p) & 3) == 0) {
+		*reinterpret_cast<unsigned *>(p) = v;
+		return;
+	}
+	p[0] = static_cast<std::uint8_t>(v);
+	p[1] = static_cast<std::uint8_t>(v >> 8);
+	p[2] = static_cast<std::uint8_t>(v >> 16);
+	p[3] = static_cast<std::uint8_t>(v >> 24);
+}
+
+// LDS column of tile column c: one word of padding per 32 columns (see the head of the file)
+__device__ inline int ldsColumn(int c) { return c + (c >> 5); }
+
+__global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
+    int srcW, std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW, int dstH, ScaleAxisDev ax,
+    ScaleAxisDev ay, int pitch) {
+	extern __shared__ unsigned tile[];  // [3][kScaleTileH][pitch]: sum qy * src per channel
+	const int tid = threadIdx.x;
+	const int dx0 = blockIdx.x * kScaleTileW, dy0 = blockIdx.y * kScaleTileH;
+	const int dxLast = min(dx0 + kScaleTileW, dstW) - 1;
+	const int xs0 = ax.start[dx0] & ~3;
+	const int xs1 = ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps];
+	const int quads = (xs1 - xs0 + 3) >> 2;
+	const bool aligned = ((reinterpret_cast<std::uintptr_t>(src) | static_cast<std::uintptr_t>(srcStride)) & 15) == 0;
+
+	// vertical pass: item = (tile row, four source columns)
+	for (int item = tid; item < kScaleTileH * quads; item += 256) {
+		const int r = item / quads, q = item - r * quads;
+		const int dy = dy0 + r;
+		if (dy >= dstH) continue;
+		const int x = xs0 + 4 * q;
+		const std::uint16_t *qy = ay.taps + dy * kScaleTapPitch;
+		const int count = qy[kScaleMaxTaps];
+		const std::uint8_t *row = src + static_cast<std::ptrdiff_t>(ay.start[dy]) * srcStride;
+		unsigned acc[12];
+#pragma unroll
+		for (int i = 0; i < 12; ++i) acc[i] = 0;
+		for (int t = 0; t < count; ++t, row += srcStride) {
+			const unsigned w = qy[t];
+			unsigned px[4];
+			if (aligned && x + 4 <= srcW) {
+				const uint4 v = *reinterpret_cast<const uint4 *>(row + 4 * x);
+				px[0] = v.x, px[1] = v.y, px[2] = v.z, px[3] = v.w;
+			} else {
+#pragma unroll
+				for (int k = 0; k < 4; ++k) px[k] = loadPixel(row + 4 * min(x + k, srcW - 1));  // (past the row: never a tap)
+			}
+#pragma unroll
+			for (int k = 0; k < 4; ++k) {
+				acc[3 * k] += w * (px[k] & 255);
+				acc[3 * k + 1] += w * ((px[k] >> 8) & 255);
+				acc[3 * k + 2] += w * ((px[k] >> 16) & 255);
+			}
+		}
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int col = ldsColumn(4 * q + k);
+#pragma unroll
+			for (int c = 0; c < 3; ++c) tile[(c * kScaleTileH + r) * pitch + col] = acc[3 * k + c];
+		}
+	}
+	__syncthreads();
+
+	// horizontal pass: a thread per destination pixel
+	const int tx = tid & (kScaleTileW - 1), ty = tid / kScaleTileW;
+	const int dx = dx0 + tx, dy = dy0 + ty;
+	if (dx >= dstW || dy >= dstH) return;
+	const std::uint16_t *qx = ax.taps + dx * kScaleTapPitch;
+	const int count = qx[kScaleMaxTaps];
+	const int first = ax.start[dx] - xs0;
+	unsigned b = 1u << 23, g = 1u << 23, r = 1u << 23;
+	const unsigned *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
+	for (int t = 0; t < count; ++t) {
+		const unsigned w = qx[t];
+		const int col = ldsColumn(first + t);
+		b += w * tb[col];
+		g += w * tg[col];
+		r += w * tr[col];
+	}
+	storePixel(dst + static_cast<std::ptrdiff_t>(dy) * dstStride + 4 * dx, (b >> 24) | ((g >> 24) << 8) | ((r >> 24) << 16));
+}
+
+__global__ __launch_bounds__(256) void mask_blend_kernel(std::uint8_t *__restrict__ gen, std::ptrdiff_t genStride,
+    unsigned outW, unsigned outH, const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride, unsigned srcW,
+    unsigned srcH, const std::uint8_t *__restrict__ mask, std::ptrdiff_t maskStride, unsigned maskW, unsigned maskH) {
+	const unsigned x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+	if (x >= outW || y >= outH) return;
+	// texel of a W-wide texture under the centre of pixel x: floor((2 x + 1) W / (2 outW)), below 2^32 (launchMaskBlend)
+	const unsigned mx = (2 * x + 1) * maskW / (2 * outW), my = (2 * y + 1) * maskH / (2 * outH);
+	const unsigned m = loadPixel(mask + static_cast<std::ptrdiff_t>(my) * maskStride + 4 * mx);
+	const unsigned a = 765 - ((m & 255) + ((m >> 8) & 255) + ((m >> 16) & 255));
+	if (a == 0) return;
+	const unsigned sx = (2 * x + 1) * srcW / (2 * outW), sy = (2 * y + 1) * srcH / (2 * outH);
+	const unsigned s = loadPixel(src + static_cast<std::ptrdiff_t>(sy) * srcStride + 4 * sx);
+	std::uint8_t *p = gen + static_cast<std::ptrdiff_t>(y) * genStride + 4 * x;
+	const unsigned g = loadPixel(p);
+	unsigned out = 0;
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const unsigned sc = (s >> (8 * c)) & 255, gc = (g >> (8 * c)) & 255;
+		out |= ((sc * a + gc * (765 - a) + 382) / 765) << (8 * c);
+	}
+	storePixel(p, out);
+}
+
+}  // namespace
+
+void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, int srcH, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int dstW, int dstH, const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX,
+    hipStream_t stream) {
+	if (src == nullptr || dst == nullptr || srcW < 1 || srcH < 1 || dstW < 1 || dstH < 1 || spanX < 4 || spanX % 4) {
+		throw std::invalid_argument("launchScaleBgrx: bad arguments");
+	}
+	const int pitch = spanX + spanX / 32 + 1;
+	const std::size_t lds = static_cast<std::size_t>(3) * kScaleTileH * static_cast<std::size_t>(pitch) * sizeof(unsigned);
+	if (lds > 64 * 1024) throw std::invalid_argument("launchScaleBgrx: the tile does not fit the LDS");
+	const dim3 grid(static_cast<unsigned>((dstW + kScaleTileW - 1) / kScaleTileW),
+	    static_cast<unsigned>((dstH + kScaleTileH - 1) / kScaleTileH));
+	hipLaunchKernelGGL(scale_bgrx_kernel, grid, dim3(256), lds, stream, src, srcStride, srcW, dst, dstStride, dstW, dstH, x,
+	    y, pitch);
+	hipCheckLaunch("scale_bgrx");
+}
+
+void launchMaskBlend(std::uint8_t *gen, std::ptrdiff_t genStride, int outW, int outH, const std::uint8_t *src,
+    std::ptrdiff_t srcStride, int srcW, int srcH, const std::uint8_t *mask, std::ptrdiff_t maskStride, int maskW,
+    int maskH, hipStream_t stream) {
+	if (gen == nullptr || src == nullptr || mask == nullptr || outW < 1 || outH < 1 || srcW < 1 || srcH < 1 || maskW < 1 ||
+	    maskH < 1) {
+		throw std::invalid_argument("launchMaskBlend: bad arguments");
+	}
+	const auto below32 = [](int out, int tex) { return 2ull * static_cast<unsigned>(out) * static_cast<unsigned>(tex) < (1ull << 32); };
+	if (!below32(outW, srcW) || !below32(outW, maskW) || !below32(outH, srcH) || !below32(outH, maskH)) {
+		throw std::invalid_argument("launchMaskBlend: 2 x output extent x texture extent must stay below 2^32");
+	}
+	const dim3 grid(static_cast<unsigned>((outW + 63) / 64), static_cast<unsigned>((outH + 3) / 4));
+	hipLaunchKernelGGL(mask_blend_kernel, grid, dim3(64, 4), 0, stream, gen, genStride, static_cast<unsigned>(outW),
+	    static_cast<unsigned>(outH), src, srcStride, static_cast<unsigned>(srcW), static_cast<unsigned>(srcH), mask,
+	    maskStride, static_cast<unsigned>(maskW), static_cast<unsigned>(maskH));
+	hipCheckLaunch("mask_blend");
+}
+
+}  // namespace ju

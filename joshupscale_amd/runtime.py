@@ -57,6 +57,22 @@ class JuFrame(C.Structure):
                 ("planes", C.c_void_p * 3), ("strides", C.c_ssize_t * 3)]
 
 
+# the source stage (docs/source_stage.md): the one filter of ju_set_source_size and its limits
+SCALE_TRIANGLE = 0
+SOURCE_AXIS_MIN, SOURCE_AXIS_MAX, SOURCE_RATIO_MAX = 2, 8192, 16
+
+
+def source_size_problem(src_width: int, src_height: int, input_width: int, input_height: int) -> str:
+    """The limits of ``ju_set_source_size`` for a model input of ``input_width x input_height``, with the C layer's
+    message; ``""`` when the source size may be set."""
+    def ok(n, m):
+        return SOURCE_AXIS_MIN <= n <= SOURCE_AXIS_MAX and n <= SOURCE_RATIO_MAX * m and m <= SOURCE_RATIO_MAX * n
+    if ok(src_width, input_width) and ok(src_height, input_height):
+        return ""
+    return (f"source size {src_width}x{src_height}: each axis must be {SOURCE_AXIS_MIN} .. {SOURCE_AXIS_MAX} and within "
+            f"a factor of {SOURCE_RATIO_MAX} of the model's input {input_width}x{input_height}")
+
+
 LOG_CALLBACK = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p)
 
 
@@ -103,6 +119,9 @@ _PRODUCT_SIGS = {
     "ju_enqueue_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
     "ju_get_size": (C.c_int, [C.c_void_p] + [_P(C.c_size_t)] * 4),
     "ju_reset": (C.c_int, [C.c_void_p]),
+    "ju_set_source_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
+    "ju_get_source_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
+    "ju_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
     "ju_last_error": (C.c_char_p, []),
     "ju_set_log_callback": (None, [LOG_CALLBACK, C.c_void_p]),
     "ju_get_gl_device_index": (C.c_int, [_P(C.c_int)]),
@@ -129,6 +148,8 @@ _HOOK_SIGS = {
                                  _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_yuv_items": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_size_t, C.c_size_t, _P(C.c_void_p),
                                      _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_source": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
+                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
@@ -283,6 +304,36 @@ class Runtime:
     def reset(self) -> None:
         _check(self._lib, self._lib.ju_reset(self._h))
 
+    # -- the source stage (docs/source_stage.md) ----------------------------------
+    def set_source_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
+        """``ju_set_source_size``: input frames are ``width x height`` from now on and are scaled to the model's input on
+        the GPU; ``(0, 0)`` turns it off.  The limits raise ``ValueError`` with the C layer's message before any native
+        call."""
+        width, height = int(width), int(height)
+        if (width, height) != (0, 0):
+            problem = source_size_problem(width, height, self.input_width, self.input_height)
+            if problem:
+                raise ValueError("ju_set_source_size: " + problem)
+        _check(self._lib, self._lib.ju_set_source_size(self._h, width, height, int(filter)))
+
+    def get_source_size(self) -> Tuple[int, int]:
+        """``ju_get_source_size``: ``(width, height)``, ``(0, 0)`` while no source size is set."""
+        w, h = C.c_size_t(), C.c_size_t()
+        _check(self._lib, self._lib.ju_get_source_size(self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def set_source_mask(self, mask) -> None:
+        """``ju_set_source_mask``: ``mask`` is a ``[H, W, 4]`` uint8 BGRX array of any size, a :class:`JuImage` (host or
+        device), or ``None`` to remove the mask.  The runtime copies it."""
+        if mask is None:
+            _check(self._lib, self._lib.ju_set_source_mask(self._h, None))
+            return
+        if not isinstance(mask, JuImage):
+            if mask.dtype != np.uint8 or mask.ndim != 3 or mask.shape[2] != 4 or mask.strides[2] != 1 or mask.strides[1] != 4:
+                raise ValueError("expected a [H, W, 4] uint8 BGRX mask with contiguous pixels")
+            mask = host_image(mask)
+        _check(self._lib, self._lib.ju_set_source_mask(self._h, C.byref(mask)))
+
     def process_image(self, frame_bgrx: np.ndarray,
                       out: Optional[np.ndarray] = None) -> np.ndarray:
         """Host frames: ``[H, W, 4]`` uint8 in, ``[4H, 4W, 4]`` uint8 out.  Any
@@ -367,7 +418,7 @@ class Runtime:
     def stat(self, key: str) -> float:
         """``ju_get_stat``: "graph_replays", "eager_runs", "direct_graphs",
         "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "output_select", "lookahead_frames",
-        "lookahead_host_frames", "lookahead_yuv_frames"."""
+        "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -528,3 +579,14 @@ class Session:
 
     def reset(self) -> None:
         self.runtime.reset()
+
+    def set_source_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
+        """``run`` takes ``width x height`` images from now on (``Runtime.set_source_size``)."""
+        self.runtime.set_source_size(width, height, filter)
+
+    def get_source_size(self) -> Tuple[int, int]:
+        return self.runtime.get_source_size()
+
+    def set_source_mask(self, mask) -> None:
+        """The source shows through ``mask`` in every frame ``run`` returns (``Runtime.set_source_mask``)."""
+        self.runtime.set_source_mask(mask)
