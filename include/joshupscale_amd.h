@@ -92,22 +92,51 @@ typedef struct ju_image {
  * precision; models whose state is not the frame (normalize_brightness, output_flow) encode it from the 8-bit frame
  * instead (257 x u8).  ju_get_stat "hbd_from_state" tells which (1 / 0); it is fixed at creation.
  *
- * Limits: 4:2:0 only, 8- and 10-bit (no P016 / 12-bit, no 4:2:2 / 4:4:4, no 16-bit RGB output, no dithering); no YUV
+ * 4:2:2 and 4:4:4 (what capture devices deliver -- YUY2 / UYVY -- and what keeps the colour detail of the 4x output).
+ * Chroma is co-sited horizontally with the even luma columns, as above; every row has its own chroma row.  Decoding a
+ * 4:2:2 frame takes the chroma sample at even columns and the mean of two at odd ones; encoding filters [1,2,1] along
+ * the row.  4:4:4 resamples nothing.  Coefficients, ranges, the 10-bit words and the source of a 10-bit output are those
+ * of the 4:2:0 formats of the same depth.
+ *
+ *   format        sampling  bits  planes and layout
+ *   JU_FMT_YUY2   4:2:2     8     one plane, [H][2W] bytes: Y0 U Y1 V per pixel pair
+ *   JU_FMT_UYVY   4:2:2     8     one plane, [H][2W] bytes: U Y0 V Y1
+ *   JU_FMT_I422   4:2:2     8     Y [H][W], U and V [H][W/2] (AviSynth YV16: pass the pointers swapped)
+ *   JU_FMT_P210   4:2:2     10    Y [H][W] words, UV [H][W] words (U first); value in the UPPER 10 bits, as P010
+ *   JU_FMT_I210   4:2:2     10    Y [H][W], U and V [H][W/2] words; value in the LOW 10 bits, as I010
+ *   JU_FMT_I444   4:4:4     8     Y, U, V [H][W] (YV24)
+ *   JU_FMT_I410   4:4:4     10    Y, U, V [H][W] words; value in the low 10 bits (yuv444p10le)
+ *
+ * 4:2:2 needs an even width (any height), 4:4:4 neither; the 4:2:0 formats need both even.  With these coefficients a
+ * JU_FMT_I410 frame carries an 8-bit frame without loss: decoding the encoding of 257 x u8 returns every colour.
+ *
+ * Memory: each runtime holds two staging buffers for host planes that fit the largest format (JU_FMT_I410, 6 bytes per
+ * pixel: 12.4 MB for a 1920x1080 output, 6.2 MB more than the 4:2:0 formats needed), and ju_process_frames allocates one
+ * such slot per frame of a pass on first use (twice the former size).
+ *
+ * Limits: 8- and 10-bit (no P016 / 12-bit, no NV16, no packed 10-bit Y210 / v210 / Y410, no 16-bit RGB output, no
+ * dithering, no other chroma siting); no YUV
  * graphics resources (GL textures stay BGRX); look-ahead passes take YUV frames through ju_process_frames
  * (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not ju_process_group; the C++ plugin surface
  * (JoshUpscale/core.h) is unchanged and takes BGRX only. */
 enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2, JU_FMT_P010 = 3, JU_FMT_I010 = 4 };
+enum {
+	JU_FMT_YUY2 = 16, JU_FMT_UYVY = 17, JU_FMT_I422 = 18, JU_FMT_P210 = 19, JU_FMT_I210 = 20,
+	JU_FMT_I444 = 24, JU_FMT_I410 = 25
+};
 enum { JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3 };
 
 typedef struct ju_frame {
 	int format;            /* JU_FMT_* */
 	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX */
 	uint8_t location;      /* JU_LOC_CPU or JU_LOC_DEVICE (BGRX: any location a ju_image takes) */
-	size_t width, height;  /* in pixels (luma); even for the YUV formats */
-	void *planes[3];       /* BGRX: [0]; I420 / I010: Y, U, V; NV12 / P010: Y, interleaved UV (U first) */
+	size_t width, height;  /* in pixels (luma); even for the 4:2:0 formats, an even width for 4:2:2 */
+	void *planes[3];       /* BGRX, YUY2, UYVY: [0]; planar formats: Y, U, V; NV12 / P010 / P210: Y, interleaved UV (U
+	                          first); planes beyond a format's count are not read */
 	ptrdiff_t strides[3];  /* BYTES per row of each plane (first logical row at planes[k]), any sign,
-	                          |stride| >= the plane's row bytes: Y = width, U / V = width / 2, UV = width, BGRX = 4 width;
-	                          P010 / I010: twice that, and plane addresses and strides are multiples of 2 */
+	                          |stride| >= the plane's row bytes: Y = width, U / V = width / 2 (4:4:4: width), UV = width,
+	                          YUY2 / UYVY = 2 width, BGRX = 4 width; the 10-bit formats: twice that, and plane addresses
+	                          and strides are multiples of 2 */
 } ju_frame;
 
 /* Replaces createRuntime(int deviceId, const std::filesystem::path &modelPath)

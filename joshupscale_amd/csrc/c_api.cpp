@@ -75,6 +75,22 @@ ju::Frame toFrame(const ju_image *img) {
 	    img->height};
 }
 
+// A JU_FMT_* value through the one table of the YUV formats (kernels.h): its planes (0: not a YUV format), whether
+// its samples are 16-bit words, and whether it is one of the 4:2:2 / 4:4:4 formats
+int planesOfFormat(int format) {
+	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
+	return info ? info->planes : 0;
+}
+[[maybe_unused]] bool wordsOfFormat(int format) {
+	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
+	return info && info->bits == 10;
+}
+[[maybe_unused]] int samplingOfFormat(int format) {
+	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
+	return info ? info->sampling : 0;
+}
+[[maybe_unused]] bool sampledFormat(int format) { return samplingOfFormat(format) == 422 || samplingOfFormat(format) == 444; }
+
 // A ju_frame as the engine's AnyFrame; BGRX frames exactly as toFrame makes them of a ju_image
 ju::AnyFrame toAnyFrame(const ju_frame *f) {
 	if (f == nullptr) throw std::invalid_argument("frame is NULL");
@@ -84,9 +100,7 @@ ju::AnyFrame toAnyFrame(const ju_frame *f) {
 		a.bgrx = toFrame(&img);
 		return a;
 	}
-	if (f->format != JU_FMT_I420 && f->format != JU_FMT_NV12 && f->format != JU_FMT_P010 && f->format != JU_FMT_I010) {
-		throw std::invalid_argument("frame has an unknown format " + std::to_string(f->format));
-	}
+	if (planesOfFormat(f->format) == 0) throw std::invalid_argument("frame has an unknown format " + std::to_string(f->format));
 	if (f->location > JU_LOC_GRAPHICS_RESOURCE) throw std::invalid_argument("frame has an unknown location");
 	a.yuv = true;
 	a.planes.format = static_cast<ju::PixelFormat>(f->format);
@@ -461,37 +475,46 @@ int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, si
     void *const *bgrx, const ptrdiff_t *bgrx_strides, void *const *planes, const ptrdiff_t *strides) {
 	return guarded([&] {
 		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_yuv_items: 1 .. 8 items");
-		if (width == 0 || height == 0 || width % 2 || height % 2 || width > (1u << 15) || height > (1u << 15)) {
-			throw std::invalid_argument("ju_debug_yuv_items: width and height must be even, 2 .. 32768");
-		}
 		if (!formats || !colorspaces || !bgrx || !bgrx_strides || !planes || !strides) {
 			throw std::invalid_argument("ju_debug_yuv_items: null argument");
+		}
+		// (4:2:0 items need an even size, 4:2:2 items an even width, 4:4:4 items neither)
+		bool needEvenWidth = false, needEvenHeight = false;
+		for (int i = 0; i < count; ++i) {
+			if (planesOfFormat(formats[i]) == 0) throw std::invalid_argument("ju_debug_yuv_items: not a YUV format");
+			if (samplingOfFormat(formats[i]) != 444) needEvenWidth = true;
+			if (samplingOfFormat(formats[i]) == 420) needEvenHeight = true;
+		}
+		if (width == 0 || height == 0 || width > (1u << 15) || height > (1u << 15)) {
+			throw std::invalid_argument("ju_debug_yuv_items: width and height must be 1 .. 32768");
+		}
+		if ((needEvenWidth && width % 2) || (needEvenHeight && height % 2)) {
+			throw std::invalid_argument("ju_debug_yuv_items: 4:2:0 items need an even width and height, 4:2:2 items an even width");
 		}
 		ju::YuvDecodeItems items{};
 		for (int i = 0; i < count; ++i) {
 			const int f = formats[i];
-			if (f != JU_FMT_I420 && f != JU_FMT_NV12 && f != JU_FMT_P010 && f != JU_FMT_I010) {
-				throw std::invalid_argument("ju_debug_yuv_items: not a YUV format");
-			}
-			const bool planar = f == JU_FMT_I420 || f == JU_FMT_I010, deep = f == JU_FMT_P010 || f == JU_FMT_I010;
+			const int count_k = planesOfFormat(f);
+			const bool planar = count_k == 3, deep = wordsOfFormat(f);
 			void *const *p = planes + 3 * i;
-			if (bgrx[i] == nullptr || p[0] == nullptr || p[1] == nullptr || (planar && p[2] == nullptr)) {
+			if (bgrx[i] == nullptr || p[0] == nullptr || (count_k > 1 && p[1] == nullptr) || (planar && p[2] == nullptr)) {
 				throw std::invalid_argument("ju_debug_yuv_items: null buffer");
 			}
-			for (int k = 0; deep && k < (planar ? 3 : 2); ++k) {
+			for (int k = 0; deep && k < count_k; ++k) {
 				if (reinterpret_cast<std::uintptr_t>(p[k]) % 2 || strides[3 * i + k] % 2) {
 					throw std::invalid_argument("ju_debug_yuv_items: 16-bit planes need even addresses and strides");
 				}
 			}
 			ju::YuvDecodeItem &it = items.item[i];
 			it.src.y = static_cast<std::uint8_t *>(p[0]);
-			it.src.u = static_cast<std::uint8_t *>(p[1]);
+			it.src.u = count_k > 1 ? static_cast<std::uint8_t *>(p[1]) : nullptr;
 			it.src.v = planar ? static_cast<std::uint8_t *>(p[2]) : nullptr;
 			it.src.yStride = strides[3 * i];
-			it.src.uStride = strides[3 * i + 1];
+			it.src.uStride = count_k > 1 ? strides[3 * i + 1] : 0;
 			it.src.vStride = planar ? strides[3 * i + 2] : 0;
 			it.k = deep ? ju::yuvDecodeCoefficients10(colorspaces[i]) : ju::yuvDecodeCoefficients(colorspaces[i]);
 			it.deep = f == JU_FMT_P010 ? 1 : (f == JU_FMT_I010 ? 2 : 0);
+			it.sampled = sampledFormat(f) ? f : 0;
 			it.dst = static_cast<std::uint8_t *>(bgrx[i]);
 			it.dstStride = bgrx_strides[i];
 			it.nv12 = f == JU_FMT_NV12 ? 1 : 0;
@@ -539,6 +562,54 @@ int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size_t heig
 			    ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
 		} else {
 			ju::launchStateToYuv420p10(p010, image, ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
+		}
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_yuv_sampled(int op, int format, int colorspace, size_t width, size_t height, void *image,
+    ptrdiff_t image_stride, void *const planes[3], const ptrdiff_t strides[3]) {
+	return guarded([&] {
+		if (op < 0 || op > 2) throw std::invalid_argument("ju_debug_yuv_sampled: op must be 0, 1 or 2");
+		if (!sampledFormat(format)) throw std::invalid_argument("ju_debug_yuv_sampled: not a 4:2:2 / 4:4:4 format");
+		const bool full = samplingOfFormat(format) == 444, deep = wordsOfFormat(format);
+		if (op == 2 && !deep) throw std::invalid_argument("ju_debug_yuv_sampled: op 2 takes the 10-bit formats only");
+		if (width == 0 || height == 0 || (!full && width % 2) || width > (1u << 15) || height > (1u << 15)) {
+			throw std::invalid_argument("ju_debug_yuv_sampled: sizes 1 .. 32768, an even width for 4:2:2");
+		}
+		const int count = planesOfFormat(format);
+		if (image == nullptr || planes == nullptr || strides == nullptr) {
+			throw std::invalid_argument("ju_debug_yuv_sampled: null buffer");
+		}
+		for (int k = 0; k < count; ++k) {
+			if (planes[k] == nullptr) throw std::invalid_argument("ju_debug_yuv_sampled: null buffer");
+			if (deep && (reinterpret_cast<std::uintptr_t>(planes[k]) % 2 || strides[k] % 2)) {
+				throw std::invalid_argument("ju_debug_yuv_sampled: 16-bit planes need even addresses and strides");
+			}
+		}
+		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) {
+			throw std::invalid_argument("ju_debug_yuv_sampled: the f16 tensor must be 16-byte aligned");
+		}
+		ju::YuvPlanes p;
+		p.y = static_cast<std::uint8_t *>(planes[0]);
+		p.u = count > 1 ? static_cast<std::uint8_t *>(planes[1]) : nullptr;
+		p.v = count > 2 ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
+		p.yStride = strides[0];
+		p.uStride = count > 1 ? strides[1] : 0;
+		p.vStride = count > 2 ? strides[2] : 0;
+		const int w = static_cast<int>(width), h = static_cast<int>(height);
+		if (op == 0) {
+			ju::launchYuvSampledToBgrx(format, p,
+			    deep ? ju::yuvDecodeCoefficients10(colorspace) : ju::yuvDecodeCoefficients(colorspace),
+			    static_cast<std::uint8_t *>(image), image_stride, w, h, nullptr);
+		} else if (op == 2) {
+			ju::launchStateToYuvSampled10(format, image, ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
+		} else if (deep) {
+			ju::launchBgrxToYuvSampled10(format, static_cast<const std::uint8_t *>(image), image_stride,
+			    ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
+		} else {
+			ju::launchBgrxToYuvSampled(format, static_cast<const std::uint8_t *>(image), image_stride,
+			    ju::yuvEncodeCoefficients(colorspace), p, w, h, nullptr);
 		}
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
+#include <string>
 
 #include "kernel_common.h"
 #include "kernels.h"
@@ -432,7 +433,7 @@ struct StateSource {
 			const uint2 v = *reinterpret_cast<const uint2 *>(row + 4 * max(x0 - 1, 0));
 			px[0] = unpack(v.x, v.y);
 		}
-		if (full) {
+		if (full && alignedTo(row, 16)) {  // (a row of an odd width starts at 8 bytes: pixel by pixel below)
 #pragma unroll
 			for (int q = 0; q < 8; ++q) {
 				const uint4 v = *reinterpret_cast<const uint4 *>(row + 4 * (x0 + 2 * q));
@@ -562,13 +563,356 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv420p10_kernel(const std::uint8
 	toYuv420p10Strip<P010>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
+// ---- 4:2:2 and 4:4:4, 8- and 10-bit (tests/yuv_sampled_reference.py; docs/yuv_io.md, "4:2:2 and 4:4:4") ----------------
+// Nothing couples rows here, so a thread's strip is 16 luma pixels of ONE row: thread idx = row idx / strips, columns
+// x0 .. x0 + 15.  Chroma is co-sited with the even luma columns (4:2:2) or with every pixel (4:4:4); the luma formulas,
+// the coefficients and the sample P are those of the 4:2:0 kernels above.  F is the frame's YuvSampled value.
+template <int F>
+struct SampledTraits {
+	static constexpr bool kPacked = F == kYuy2 || F == kUyvy;
+	static constexpr bool kDeep = F == kP210 || F == kI210 || F == kI410;
+	static constexpr bool kFull = F == kI444 || F == kI410;  // (4:4:4: a chroma sample per pixel)
+	static constexpr bool kSemi = F == kP210;
+	static constexpr int kShift = F == kP210 ? 6 : 0;        // (word >> 6, or word & 0x3ff)
+	static constexpr int kYByte = F == kYuy2 ? 0 : 1;        // packed: the byte of Y0 in a pair's four (U: 1 - kYByte)
+	static constexpr int kMid = kDeep ? 512 : 128;
+};
+
+// The strip's 16 luma samples and its chroma samples as integers: 4:4:4 cu / cv[0 .. 15]; 4:2:2 cu / cv[0 .. 7] = cells
+// x0 / 2 .. x0 / 2 + 7 and [8] = the next cell, for the odd column of the last pixel.  Every index is clamped to its row.
+template <int F>
+__device__ inline void loadSampledStrip(const YuvPlanes &src, int y, int x0, int W, bool full, int (&ys)[16],
+    int (&cu)[17], int (&cv)[17]) {
+	using T = SampledTraits<F>;
+	const int CW = T::kFull ? W : W / 2;
+	const int c0 = T::kFull ? x0 : x0 / 2;
+	const std::uint8_t *rowY = src.y + static_cast<std::ptrdiff_t>(y) * src.yStride;
+	if constexpr (T::kPacked) {
+		constexpr int yb = T::kYByte, cb = 1 - T::kYByte;
+		if (full) {
+			unsigned w[8];
+#pragma unroll
+			for (int q = 0; q < 2; ++q) {
+				unsigned h[4];
+				loadBytes<16>(rowY, 2 * x0 + 16 * q, 2 * W - 1, true, h);
+#pragma unroll
+				for (int i = 0; i < 4; ++i) w[4 * q + i] = h[i];
+			}
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {  // one word per pixel pair
+				ys[2 * i] = (w[i] >> (8 * yb)) & 255;
+				ys[2 * i + 1] = (w[i] >> (8 * yb + 16)) & 255;
+				cu[i] = (w[i] >> (8 * cb)) & 255;
+				cv[i] = (w[i] >> (8 * cb + 16)) & 255;
+			}
+		} else {
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				const std::uint8_t *p = rowY + 4 * min(c0 + i, CW - 1);
+				ys[2 * i] = p[yb];
+				ys[2 * i + 1] = p[yb + 2];
+				cu[i] = p[cb];
+				cv[i] = p[cb + 2];
+			}
+		}
+		const std::uint8_t *p = rowY + 4 * min(c0 + 8, CW - 1);
+		cu[8] = p[cb];
+		cv[8] = p[cb + 2];
+		return;
+	}
+	if constexpr (T::kDeep) {
+		unsigned yw[8];
+		loadSamples<16>(rowY, x0, W - 1, full, yw);
+#pragma unroll
+		for (int p = 0; p < 16; ++p) ys[p] = T::kShift ? sampleOf(yw, p) >> T::kShift : sampleOf(yw, p) & 0x3ff;
+	} else {
+		unsigned yw[4];
+		loadBytes<16>(rowY, x0, W - 1, full, yw);
+#pragma unroll
+		for (int p = 0; p < 16; ++p) ys[p] = byteOf(yw, p);
+	}
+	const std::uint8_t *rowU = src.u + static_cast<std::ptrdiff_t>(y) * src.uStride;
+	if constexpr (T::kSemi) {  // P210: U_i V_i words
+		if (full) {
+			unsigned w[8];
+			loadSamples<16>(rowU, 2 * c0, 2 * CW - 1, true, w);
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				cu[i] = sampleOf(w, 2 * i) >> T::kShift;
+				cv[i] = sampleOf(w, 2 * i + 1) >> T::kShift;
+			}
+		} else {
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				const int c = min(c0 + i, CW - 1);
+				cu[i] = wordAt(rowU, 2 * c) >> T::kShift;
+				cv[i] = wordAt(rowU, 2 * c + 1) >> T::kShift;
+			}
+		}
+		const int last = min(c0 + 8, CW - 1);
+		cu[8] = wordAt(rowU, 2 * last) >> T::kShift;
+		cv[8] = wordAt(rowU, 2 * last + 1) >> T::kShift;
+		return;
+	} else {
+		const std::uint8_t *rowV = src.v + static_cast<std::ptrdiff_t>(y) * src.vStride;
+		constexpr int N = T::kFull ? 16 : 8;
+		if constexpr (T::kDeep) {
+			unsigned wu[N / 2], wv[N / 2];
+			loadSamples<N>(rowU, c0, CW - 1, full, wu);
+			loadSamples<N>(rowV, c0, CW - 1, full, wv);
+#pragma unroll
+			for (int i = 0; i < N; ++i) {
+				cu[i] = sampleOf(wu, i) & 0x3ff;
+				cv[i] = sampleOf(wv, i) & 0x3ff;
+			}
+			if constexpr (!T::kFull) {
+				const int last = min(c0 + 8, CW - 1);
+				cu[8] = wordAt(rowU, last) & 0x3ff;
+				cv[8] = wordAt(rowV, last) & 0x3ff;
+			}
+		} else {
+			unsigned wu[N / 4], wv[N / 4];
+			loadBytes<N>(rowU, c0, CW - 1, full, wu);
+			loadBytes<N>(rowV, c0, CW - 1, full, wv);
+#pragma unroll
+			for (int i = 0; i < N; ++i) {
+				cu[i] = byteOf(wu, i);
+				cv[i] = byteOf(wv, i);
+			}
+			if constexpr (!T::kFull) {
+				const int last = min(c0 + 8, CW - 1);
+				cu[8] = rowU[last];
+				cv[8] = rowV[last];
+			}
+		}
+	}
+}
+
+// planes -> BGRX: the strip of thread `idx`; the body of the single-frame kernel and of the items kernel's branch.
+// `k`: yuvDecodeCoefficients (8-bit formats) or yuvDecodeCoefficients10.
+template <int F>
+__device__ inline void yuvSampledToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H, int idx) {
+	using T = SampledTraits<F>;
+	const int strips = (W + kStrip - 1) / kStrip;
+	if (idx >= strips * H) return;
+	const int y = idx / strips;
+	const int x0 = (idx - y * strips) * kStrip;
+	const bool full = x0 + kStrip <= W;
+	int ys[16], cu[17], cv[17];
+	loadSampledStrip<F>(src, y, x0, W, full, ys, cu, cv);
+	unsigned px[16];
+#pragma unroll
+	for (int p = 0; p < 16; ++p) {
+		int du, dv;  // 8 x chroma at the pixel, less 8 x the mid value
+		if constexpr (T::kFull) {
+			du = 8 * cu[p];
+			dv = 8 * cv[p];
+		} else {
+			const int i = p >> 1;
+			du = (p & 1) ? 4 * (cu[i] + cu[i + 1]) : 8 * cu[i];
+			dv = (p & 1) ? 4 * (cv[i] + cv[i + 1]) : 8 * cv[i];
+		}
+		du -= 8 * T::kMid;
+		dv -= 8 * T::kMid;
+		const int yd = k.ky * (8 * (ys[p] - k.oy));
+		const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
+		const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
+		const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+		px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
+	}
+	std::uint8_t *row = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
+	const int n = min(kStrip, W - x0);
+#pragma unroll
+	for (int q = 0; q < 4; ++q) {
+		const unsigned w[4] = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
+		storeBytes<16>(row, 4 * (x0 + 4 * q), 4 * (n - 4 * q), full, w);
+	}
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void yuv_sampled_to_bgrx_kernel(YuvPlanes src, YuvDecode k,
+    std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int W, int H) {
+	yuvSampledToBgrxStrip<F>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+// The strip's samples (8-bit: bytes, 10-bit: values 0 .. 1023) into the planes of format F: `n` luma columns of row y
+// from x0 (all 16 where `full`), `cu` / `cv` per chroma cell (4:2:2: 8) or per pixel (4:4:4: 16).
+template <int F>
+__device__ inline void storeSampledStrip(const YuvPlanes &dst, int y, int x0, int n, bool full, const int (&ys)[16],
+    const int (&cu)[16], const int (&cv)[16]) {
+	using T = SampledTraits<F>;
+	const int c0 = T::kFull ? x0 : x0 / 2;
+	const int cn = T::kFull ? n : n / 2;
+	std::uint8_t *rowY = dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride;
+	if constexpr (T::kPacked) {
+		constexpr int yb = T::kYByte, cb = 1 - T::kYByte;
+#pragma unroll
+		for (int q = 0; q < 2; ++q) {
+			unsigned w[4];
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				const int c = 4 * q + i;
+				w[i] = (static_cast<unsigned>(ys[2 * c]) << (8 * yb)) | (static_cast<unsigned>(ys[2 * c + 1]) << (8 * yb + 16)) |
+				       (static_cast<unsigned>(cu[c]) << (8 * cb)) | (static_cast<unsigned>(cv[c]) << (8 * cb + 16));
+			}
+			storeBytes<16>(rowY, 2 * x0 + 16 * q, 2 * n - 16 * q, full, w);
+		}
+		return;
+	}
+	constexpr int N = T::kFull ? 16 : 8;
+	if constexpr (T::kDeep) {
+		unsigned yw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+		for (int p = 0; p < 16; ++p) yw[p >> 1] |= static_cast<unsigned>(ys[p] << T::kShift) << (16 * (p & 1));
+		storeSamples<16>(rowY, x0, n, full, yw);
+		std::uint8_t *rowU = dst.u + static_cast<std::ptrdiff_t>(y) * dst.uStride;
+		if constexpr (T::kSemi) {
+			unsigned w[8];
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {  // U_i V_i
+				w[i] = static_cast<unsigned>(cu[i] << T::kShift) | (static_cast<unsigned>(cv[i] << T::kShift) << 16);
+			}
+			storeSamples<16>(rowU, 2 * c0, 2 * cn, full, w);
+		} else {
+			unsigned uw[N / 2], vw[N / 2];
+#pragma unroll
+			for (int i = 0; i < N / 2; ++i) {
+				uw[i] = static_cast<unsigned>(cu[2 * i]) | (static_cast<unsigned>(cu[2 * i + 1]) << 16);
+				vw[i] = static_cast<unsigned>(cv[2 * i]) | (static_cast<unsigned>(cv[2 * i + 1]) << 16);
+			}
+			storeSamples<N>(rowU, c0, cn, full, uw);
+			storeSamples<N>(dst.v + static_cast<std::ptrdiff_t>(y) * dst.vStride, c0, cn, full, vw);
+		}
+	} else {
+		unsigned yw[4] = {0, 0, 0, 0}, uw[N / 4], vw[N / 4];
+#pragma unroll
+		for (int p = 0; p < 16; ++p) yw[p >> 2] |= static_cast<unsigned>(ys[p]) << (8 * (p & 3));
+#pragma unroll
+		for (int i = 0; i < N / 4; ++i) {
+			uw[i] = static_cast<unsigned>(cu[4 * i]) | (static_cast<unsigned>(cu[4 * i + 1]) << 8) |
+			        (static_cast<unsigned>(cu[4 * i + 2]) << 16) | (static_cast<unsigned>(cu[4 * i + 3]) << 24);
+			vw[i] = static_cast<unsigned>(cv[4 * i]) | (static_cast<unsigned>(cv[4 * i + 1]) << 8) |
+			        (static_cast<unsigned>(cv[4 * i + 2]) << 16) | (static_cast<unsigned>(cv[4 * i + 3]) << 24);
+		}
+		storeBytes<16>(rowY, x0, n, full, yw);
+		storeBytes<N>(dst.u + static_cast<std::ptrdiff_t>(y) * dst.uStride, c0, cn, full, uw);
+		storeBytes<N>(dst.v + static_cast<std::ptrdiff_t>(y) * dst.vStride, c0, cn, full, vw);
+	}
+}
+
+// BGRX u8 -> the 8-bit formats (YUY2, UYVY, I422, I444).  4:2:2: the [1, 2, 1] sum of a row (4 x the mean), 4:4:4: the
+// pixel itself; the rounding constant and the shift follow the sum's weight.
+template <int F>
+__global__ __launch_bounds__(256) void bgrx_to_yuv_sampled_kernel(const std::uint8_t *__restrict__ src,
+    std::ptrdiff_t srcStride, YuvEncode k, YuvPlanes dst, int W, int H) {
+	using T = SampledTraits<F>;
+	const int strips = (W + kStrip - 1) / kStrip;
+	const int idx = blockIdx.x * 256 + threadIdx.x;
+	if (idx >= strips * H) return;
+	const int y = idx / strips;
+	const int x0 = (idx - y * strips) * kStrip;
+	const bool full = x0 + kStrip <= W;
+	const int n = min(kStrip, W - x0);
+	unsigned px[17];  // [0] = column x0 - 1 (clamped), [1 + p] = column x0 + p
+	Bgrx8Source{src, srcStride}.load(y, x0, W, full, px);
+	int ys[16], cu[16], cv[16];
+#pragma unroll
+	for (int p = 0; p < 16; ++p) {
+		const int B = px[1 + p] & 255, G = (px[1 + p] >> 8) & 255, R = (px[1 + p] >> 16) & 255;
+		ys[p] = clamp255(k.oy + ((k.yr * R + k.yg * G + k.yb * B + (1 << 15)) >> 16));
+	}
+	constexpr int kW = T::kFull ? 0 : 2;  // log2 of the chroma sum's weight
+#pragma unroll
+	for (int i = 0; i < (T::kFull ? 16 : 8); ++i) {
+		int sr, sg, sb;
+		if constexpr (T::kFull) {
+			sb = px[1 + i] & 255, sg = (px[1 + i] >> 8) & 255, sr = (px[1 + i] >> 16) & 255;
+		} else {  // columns 2i - 1, 2i, 2i + 1 of the strip = px[2i], px[2i + 1], px[2i + 2]
+			const unsigned a = px[2 * i], b = px[2 * i + 1], c = px[2 * i + 2];
+			sb = (a & 255) + 2 * (b & 255) + (c & 255);
+			sg = ((a >> 8) & 255) + 2 * ((b >> 8) & 255) + ((c >> 8) & 255);
+			sr = ((a >> 16) & 255) + 2 * ((b >> 16) & 255) + ((c >> 16) & 255);
+		}
+		cu[i] = clamp255(128 + ((k.ur * sr + k.ug * sg + k.ub * sb + (1 << (15 + kW))) >> (16 + kW)));
+		cv[i] = clamp255(128 + ((k.vr * sr + k.vg * sg + k.vb * sb + (1 << (15 + kW))) >> (16 + kW)));
+	}
+	storeSampledStrip<F>(dst, y, x0, n, full, ys, cu, cv);
+}
+
+// P -> the 10-bit formats (P210, I210, I410): the strip body of both sources, as toYuv420p10Strip is for 4:2:0.
+template <int F, typename Source>
+__device__ inline void toYuvSampled10Strip(const Source &source, const YuvEncode10 &k, const YuvPlanes &dst, int W, int H,
+    int idx) {
+	using T = SampledTraits<F>;
+	const int strips = (W + kStrip - 1) / kStrip;
+	if (idx >= strips * H) return;
+	const int y = idx / strips;
+	const int x0 = (idx - y * strips) * kStrip;
+	const bool full = x0 + kStrip <= W;
+	const int n = min(kStrip, W - x0);
+	typename Source::Pixel px[17];  // [0] = column x0 - 1 (clamped), [1 + p] = column x0 + p
+	source.load(y, x0, W, full, px);
+	int ys[16], cu[16], cv[16];
+#pragma unroll
+	for (int p = 0; p < 16; ++p) {
+		const long long acc = (static_cast<long long>(k.yr) * Source::r(px[1 + p]) +
+		                       static_cast<long long>(k.yg) * Source::g(px[1 + p]) +
+		                       static_cast<long long>(k.yb) * Source::b(px[1 + p])) * Source::kScale + (1ll << 31);
+		ys[p] = clamp1023(k.oy + static_cast<int>(acc >> 32));
+	}
+	constexpr int kW = T::kFull ? 0 : 2;  // log2 of the chroma sum's weight
+#pragma unroll
+	for (int i = 0; i < (T::kFull ? 16 : 8); ++i) {
+		int sr, sg, sb;
+		if constexpr (T::kFull) {
+			sb = Source::b(px[1 + i]), sg = Source::g(px[1 + i]), sr = Source::r(px[1 + i]);
+		} else {
+			sb = Source::b(px[2 * i]) + 2 * Source::b(px[2 * i + 1]) + Source::b(px[2 * i + 2]);
+			sg = Source::g(px[2 * i]) + 2 * Source::g(px[2 * i + 1]) + Source::g(px[2 * i + 2]);
+			sr = Source::r(px[2 * i]) + 2 * Source::r(px[2 * i + 1]) + Source::r(px[2 * i + 2]);
+		}
+		const long long au = (static_cast<long long>(k.ur) * sr + static_cast<long long>(k.ug) * sg +
+		                      static_cast<long long>(k.ub) * sb) * Source::kScale + (1ll << (31 + kW));
+		const long long av = (static_cast<long long>(k.vr) * sr + static_cast<long long>(k.vg) * sg +
+		                      static_cast<long long>(k.vb) * sb) * Source::kScale + (1ll << (31 + kW));
+		cu[i] = clamp1023(512 + static_cast<int>(au >> (32 + kW)));
+		cv[i] = clamp1023(512 + static_cast<int>(av >> (32 + kW)));
+	}
+	storeSampledStrip<F>(dst, y, x0, n, full, ys, cu, cv);
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void state_to_yuv_sampled10_kernel(const f16 *__restrict__ state, YuvEncode10 k,
+    YuvPlanes dst, int W, int H) {
+	toYuvSampled10Strip<F>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void bgrx_to_yuv_sampled10_kernel(const std::uint8_t *__restrict__ src,
+    std::ptrdiff_t srcStride, YuvEncode10 k, YuvPlanes dst, int W, int H) {
+	toYuvSampled10Strip<F>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
 // The YUV inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item --
 // its planes, coefficients and destination, from the kernel arguments -- and its format is a branch every lane of the
 // workgroup takes alike.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
 // launch latencies for one round of work (the shape addFlowAutoencoder's batched launches fixed for the flow net).
+// (a 4:2:2 / 4:4:4 item has a strip per row: the grid then covers strips x H threads and a 4:2:0 item's upper half of
+// them returns at once)
 __global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
 	const YuvDecodeItem &it = items.item[blockIdx.y];
 	const int idx = blockIdx.x * 256 + threadIdx.x;
+	switch (it.sampled) {
+	case kYuy2: return yuvSampledToBgrxStrip<kYuy2>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	case kUyvy: return yuvSampledToBgrxStrip<kUyvy>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	case kI422: return yuvSampledToBgrxStrip<kI422>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	case kP210: return yuvSampledToBgrxStrip<kP210>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	case kI210: return yuvSampledToBgrxStrip<kI210>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	case kI444: return yuvSampledToBgrxStrip<kI444>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	case kI410: return yuvSampledToBgrxStrip<kI410>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	default: break;
+	}
 	if (it.deep == 1) {  // (P010; 2: I010 -- 10-bit items, as uniform per workgroup as the 8-bit formats)
 		yuv420p10ToBgrxStrip<true>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
 	} else if (it.deep == 2) {
@@ -685,7 +1029,9 @@ void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std
 
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream) {
 	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("yuv420_to_bgrx_items: 1 .. 8 items");
-	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
+	bool perRow = false;  // (a 4:2:2 / 4:4:4 item: a strip per row, not per row pair)
+	for (int i = 0; i < count; ++i) perRow = perRow || items.item[i].sampled != 0;
+	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (perRow ? height : height / 2);
 	hipLaunchKernelGGL(yuv420_to_bgrx_items_kernel, dim3(blocksFor(threads), count), dim3(256), 0, stream, items, width,
 	    height);
 	hipCheckLaunch("yuv420_to_bgrx_items");
@@ -741,6 +1087,90 @@ void launchBgrxToYuv420p10(bool p010, const std::uint8_t *src, std::ptrdiff_t sr
 		    srcStride, k, dst, width, height);
 	}
 	hipCheckLaunch("bgrx_to_yuv420p10");
+}
+
+namespace {
+std::size_t sampledThreads(int width, int height) {
+	return static_cast<std::size_t>((width + kStrip - 1) / kStrip) * static_cast<std::size_t>(height);
+}
+[[noreturn]] void notSampled(const char *what, int format) {
+	throw std::invalid_argument(std::string(what) + ": format " + std::to_string(format) + " has no such kernel");
+}
+}  // namespace
+
+void launchYuvSampledToBgrx(int format, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream) {
+	const dim3 grid(blocksFor(sampledThreads(width, height)));
+#define JU_SAMPLED_DECODE(F) \
+	case F: \
+		hipLaunchKernelGGL(yuv_sampled_to_bgrx_kernel<F>, grid, dim3(256), 0, stream, src, k, dst, dstStride, width, height); \
+		break;
+	switch (format) {
+		JU_SAMPLED_DECODE(kYuy2)
+		JU_SAMPLED_DECODE(kUyvy)
+		JU_SAMPLED_DECODE(kI422)
+		JU_SAMPLED_DECODE(kP210)
+		JU_SAMPLED_DECODE(kI210)
+		JU_SAMPLED_DECODE(kI444)
+		JU_SAMPLED_DECODE(kI410)
+	default: notSampled("yuv_sampled_to_bgrx", format);
+	}
+#undef JU_SAMPLED_DECODE
+	hipCheckLaunch("yuv_sampled_to_bgrx");
+}
+
+void launchBgrxToYuvSampled(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
+	const dim3 grid(blocksFor(sampledThreads(width, height)));
+#define JU_SAMPLED_ENCODE(F) \
+	case F: \
+		hipLaunchKernelGGL(bgrx_to_yuv_sampled_kernel<F>, grid, dim3(256), 0, stream, src, srcStride, k, dst, width, height); \
+		break;
+	switch (format) {
+		JU_SAMPLED_ENCODE(kYuy2)
+		JU_SAMPLED_ENCODE(kUyvy)
+		JU_SAMPLED_ENCODE(kI422)
+		JU_SAMPLED_ENCODE(kI444)
+	default: notSampled("bgrx_to_yuv_sampled", format);
+	}
+#undef JU_SAMPLED_ENCODE
+	hipCheckLaunch("bgrx_to_yuv_sampled");
+}
+
+void launchStateToYuvSampled10(int format, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
+    int height, hipStream_t stream) {
+	const dim3 grid(blocksFor(sampledThreads(width, height)));
+	const f16 *s = static_cast<const f16 *>(state);
+#define JU_SAMPLED_ENCODE(F) \
+	case F: \
+		hipLaunchKernelGGL(state_to_yuv_sampled10_kernel<F>, grid, dim3(256), 0, stream, s, k, dst, width, height); \
+		break;
+	switch (format) {
+		JU_SAMPLED_ENCODE(kP210)
+		JU_SAMPLED_ENCODE(kI210)
+		JU_SAMPLED_ENCODE(kI410)
+	default: notSampled("state_to_yuv_sampled10", format);
+	}
+#undef JU_SAMPLED_ENCODE
+	hipCheckLaunch("state_to_yuv_sampled10");
+}
+
+void launchBgrxToYuvSampled10(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
+	const dim3 grid(blocksFor(sampledThreads(width, height)));
+#define JU_SAMPLED_ENCODE(F) \
+	case F: \
+		hipLaunchKernelGGL(bgrx_to_yuv_sampled10_kernel<F>, grid, dim3(256), 0, stream, src, srcStride, k, dst, width, \
+		    height); \
+		break;
+	switch (format) {
+		JU_SAMPLED_ENCODE(kP210)
+		JU_SAMPLED_ENCODE(kI210)
+		JU_SAMPLED_ENCODE(kI410)
+	default: notSampled("bgrx_to_yuv_sampled10", format);
+	}
+#undef JU_SAMPLED_ENCODE
+	hipCheckLaunch("bgrx_to_yuv_sampled10");
 }
 
 }  // namespace ju

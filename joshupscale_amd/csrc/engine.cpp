@@ -1491,29 +1491,35 @@ void Engine::stageOut(const Frame &out) {
 }
 
 namespace {
-// Plane k of a 4:2:0 frame of the given luma size: rows, bytes per row (I420 / I010: Y, U, V; NV12 / P010: Y, UV;
-// P010 / I010: two bytes per sample)
+// Plane k of a YUV frame of the given luma size: rows, bytes per row (planar: Y, U, V; semi-planar: Y, UV; packed
+// YUY2 / UYVY: one plane of 2 bytes per pixel; the 10-bit formats: two bytes per sample)
 struct PlaneShape {
 	std::size_t rows, rowBytes;
 };
-bool semiPlanar(PixelFormat f) { return f == PixelFormat::Nv12 || f == PixelFormat::P010; }
-bool tenBit(PixelFormat f) { return f == PixelFormat::P010 || f == PixelFormat::I010; }
+// A format = sampling (420 / 422 / 444) x storage (planar Y, U, V / semi-planar Y, UV / packed: one plane) x depth:
+// all of it from the one table, yuvFormatInfo (kernels.h)
+bool knownYuv(PixelFormat f) { return yuvFormatInfo(static_cast<int>(f)) != nullptr; }
+const YuvFormatInfo &infoOf(PixelFormat f) {
+	const YuvFormatInfo *info = yuvFormatInfo(static_cast<int>(f));
+	if (info == nullptr) throw std::invalid_argument("unknown frame format " + std::to_string(static_cast<int>(f)));
+	return *info;
+}
+int sampling(PixelFormat f) { return infoOf(f).sampling; }
+bool packed(PixelFormat f) { return infoOf(f).planes == 1; }
+bool semiPlanar(PixelFormat f) { return infoOf(f).planes == 2; }
+bool tenBit(PixelFormat f) { return infoOf(f).bits == 10; }
 std::size_t bytesPerSample(PixelFormat f) { return tenBit(f) ? 2 : 1; }
 PlaneShape planeShape(PixelFormat f, std::size_t w, std::size_t h, int k) {
 	const std::size_t b = bytesPerSample(f);
+	if (packed(f)) return {h, 2 * w};
 	if (k == 0) return {h, w * b};
-	return {h / 2, (semiPlanar(f) ? w : w / 2) * b};
+	const int s = sampling(f);
+	const std::size_t cw = s == 444 ? w : w / 2;  // chroma samples per row (a semi-planar row holds both planes')
+	return {s == 420 ? h / 2 : h, (semiPlanar(f) ? 2 * cw : cw) * b};
 }
-int planeCount(PixelFormat f) { return semiPlanar(f) ? 2 : 3; }
+int planeCount(PixelFormat f) { return infoOf(f).planes; }
 std::size_t stagePitch(std::size_t rowBytes) { return (rowBytes + 63) / 64 * 64; }
-const char *formatName(PixelFormat f) {
-	switch (f) {
-	case PixelFormat::Nv12: return "NV12";
-	case PixelFormat::P010: return "P010";
-	case PixelFormat::I010: return "I010";
-	default: return "I420";
-	}
-}
+const char *formatName(PixelFormat f) { return infoOf(f).name; }
 
 // The caller's device planes as a conversion kernel takes them
 YuvPlanes callerPlanes(const YuvFrame &f) {
@@ -1563,10 +1569,13 @@ void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream
 }
 }  // namespace
 
-// bytes of a staging buffer that holds any 4:2:0 frame of the size, 8- or 10-bit (the three planes of I010 take the most)
+// bytes of a staging buffer that holds any YUV frame of the size (the three full planes of I410 take the most: 6 bytes
+// per pixel and the row padding)
 std::size_t Engine::yuvStageBytes(std::size_t w, std::size_t h) {
 	std::size_t most = 0;
-	for (PixelFormat f : {PixelFormat::I420, PixelFormat::Nv12, PixelFormat::P010, PixelFormat::I010}) {
+	for (PixelFormat f : {PixelFormat::I420, PixelFormat::Nv12, PixelFormat::P010, PixelFormat::I010, PixelFormat::Yuy2,
+	         PixelFormat::Uyvy, PixelFormat::I422, PixelFormat::P210, PixelFormat::I210, PixelFormat::I444,
+	         PixelFormat::I410}) {
 		std::size_t n = 0;
 		for (int k = 0; k < planeCount(f); ++k) {
 			const PlaneShape p = planeShape(f, w, h, k);
@@ -1604,10 +1613,7 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 		return;
 	}
 	const YuvFrame &y = f.planes;
-	if (y.format != PixelFormat::I420 && y.format != PixelFormat::Nv12 && y.format != PixelFormat::P010 &&
-	    y.format != PixelFormat::I010) {
-		throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
-	}
+	if (!knownYuv(y.format)) throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
 	if (y.colorspace < 0 || y.colorspace > 3) {
 		throw std::invalid_argument("processFrame: unknown " + side + " colour space " + std::to_string(y.colorspace));
 	}
@@ -1615,9 +1621,13 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) + " " + side +
 		                            " frames must be host or device memory (no graphics resources)");
 	}
-	if (y.width % 2 || y.height % 2) {
+	if (sampling(y.format) == 420 && (y.width % 2 || y.height % 2)) {
 		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) +
 		                            " needs an even width and height");
+	}
+	if (sampling(y.format) == 422 && y.width % 2) {
+		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) +
+		                            " (4:2:2) needs an even width");
 	}
 	if (y.width != w || y.height != h) {
 		throw std::invalid_argument("processFrame: " + side + " frame must be exactly " + size);
@@ -1652,7 +1662,11 @@ void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
     std::ptrdiff_t bgrxStride, std::size_t width, std::size_t height) {
 	const FrameSize fs = frameSize();
 	const int w = static_cast<int>(width ? width : fs.inputWidth), h = static_cast<int>(height ? height : fs.inputHeight);
-	if (tenBit(format)) {
+	if (sampling(format) != 420) {
+		launchYuvSampledToBgrx(static_cast<int>(format), planes,
+		    tenBit(format) ? yuvDecodeCoefficients10(colorspace) : yuvDecodeCoefficients(colorspace), bgrx, bgrxStride, w, h,
+		    m_Stream);
+	} else if (tenBit(format)) {
 		launchYuv420p10ToBgrx(format == PixelFormat::P010, planes, yuvDecodeCoefficients10(colorspace), bgrx, bgrxStride,
 		    w, h, m_Stream);
 	} else {
@@ -1667,10 +1681,20 @@ void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
     std::ptrdiff_t bgrxStride, const void *state) {
 	const FrameSize fs = frameSize();
 	const int w = static_cast<int>(fs.outputWidth), h = static_cast<int>(fs.outputHeight);
-	if (!tenBit(format)) {
+	const bool fromState = m_HbdFromState && m_MaskW == 0;  // (a mask: the blended frame exists in 8 bits only)
+	if (sampling(format) != 420) {  // 4:2:2 / 4:4:4: the same three sources
+		const int f = static_cast<int>(format);
+		if (!tenBit(format)) {
+			launchBgrxToYuvSampled(f, bgrx, bgrxStride, yuvEncodeCoefficients(colorspace), planes, w, h, m_Stream);
+		} else if (fromState) {
+			launchStateToYuvSampled10(f, state, yuvEncodeCoefficients10(colorspace), planes, w, h, m_Stream);
+		} else {
+			launchBgrxToYuvSampled10(f, bgrx, bgrxStride, yuvEncodeCoefficients10(colorspace), planes, w, h, m_Stream);
+		}
+	} else if (!tenBit(format)) {
 		launchBgrxToYuv420(format == PixelFormat::Nv12, bgrx, bgrxStride, yuvEncodeCoefficients(colorspace), planes, w, h,
 		    m_Stream);
-	} else if (m_HbdFromState && m_MaskW == 0) {  // (a mask: the blended frame exists in 8 bits only)
+	} else if (fromState) {
 		launchStateToYuv420p10(format == PixelFormat::P010, state, yuvEncodeCoefficients10(colorspace), planes, w, h,
 		    m_Stream);
 	} else {
@@ -2059,6 +2083,7 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		it.dstStride = m_BatchIO[i].inStride;
 		it.nv12 = pf.formatIn == PixelFormat::Nv12 ? 1 : 0;
 		it.deep = pf.formatIn == PixelFormat::P010 ? 1 : (pf.formatIn == PixelFormat::I010 ? 2 : 0);
+		it.sampled = sampling(pf.formatIn) != 420 ? static_cast<int>(pf.formatIn) : 0;
 	}
 	if (decodes) {
 		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),

@@ -43,7 +43,12 @@ struct Frame {
 // A 4:2:0 frame of ju_process_frame (include/joshupscale_amd.h, ju_frame): planes Y, U, V (I420 / YV12, I010) or
 // Y, interleaved UV (NV12, P010), each addressing its first logical row, strides in bytes of any sign.  Host or device.
 // P010 / I010: 16-bit little-endian samples (the 10-bit value in the upper / the low bits).
-enum class PixelFormat : int { Bgrx = 0, I420 = 1, Nv12 = 2, P010 = 3, I010 = 4 };
+// From 16 on, 4:2:2 (chroma rows of full height) and 4:4:4: packed YUY2 / UYVY (ONE plane, 2 bytes per pixel), I422 and
+// I210 (Y, U, V; I210 words as I010), P210 (Y, UV; words as P010), I444 and I410 (three full planes; I410 words as I010).
+enum class PixelFormat : int {
+	Bgrx = 0, I420 = 1, Nv12 = 2, P010 = 3, I010 = 4,
+	Yuy2 = 16, Uyvy = 17, I422 = 18, P210 = 19, I210 = 20, I444 = 24, I410 = 25
+};
 
 struct YuvFrame {
 	PixelFormat format;

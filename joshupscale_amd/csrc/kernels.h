@@ -447,9 +447,30 @@ void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std
     std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
 void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
     const YuvPlanes &dst, int width, int height, hipStream_t stream);
+// 4:2:2 and 4:4:4 formats (colour_kernels.hip, "4:2:2 and 4:4:4"): the values of PixelFormat / JU_FMT_*.
+enum YuvSampled : int { kYuy2 = 16, kUyvy = 17, kI422 = 18, kP210 = 19, kI210 = 20, kI444 = 24, kI410 = 25 };
+// THE table of the YUV frame formats, by PixelFormat / JU_FMT_* value: the C API and the engine classify a format
+// through it alone.  planes: 3 planar (Y, U, V), 2 semi-planar (Y, UV), 1 packed (two bytes per pixel).
+struct YuvFormatInfo {
+	int value;
+	const char *name;
+	int sampling;  // 420, 422 or 444
+	int planes;
+	int bits;      // 8, or 10 in 16-bit words
+};
+inline const YuvFormatInfo *yuvFormatInfo(int value) {  // nullptr: not a YUV format
+	static constexpr YuvFormatInfo kTable[] = {
+	    {1, "I420", 420, 3, 8},      {2, "NV12", 420, 2, 8},      {3, "P010", 420, 2, 10},     {4, "I010", 420, 3, 10},
+	    {kYuy2, "YUY2", 422, 1, 8},  {kUyvy, "UYVY", 422, 1, 8},  {kI422, "I422", 422, 3, 8},  {kP210, "P210", 422, 2, 10},
+	    {kI210, "I210", 422, 3, 10}, {kI444, "I444", 444, 3, 8},  {kI410, "I410", 444, 3, 10}};
+	for (const YuvFormatInfo &f : kTable) {
+		if (f.value == value) return &f;
+	}
+	return nullptr;
+}
 // The YUV inputs of a look-ahead pass (Engine::processFrames), decoded in one launch: item i of `count` (1 ..
 // kFlowBatchMax) = planes, coefficients and BGRX destination of one frame; all frames width x height.  Per item the
-// bytes of launchYuv420ToBgrx.  The struct is the launch's by-value argument (768 bytes).
+// bytes of launchYuv420ToBgrx.  The struct is the launch's by-value argument (832 bytes).
 struct YuvDecodeItem {
 	YuvPlanes src;
 	YuvDecode k;
@@ -457,6 +478,7 @@ struct YuvDecodeItem {
 	std::ptrdiff_t dstStride = 0;
 	int nv12 = 0;
 	int deep = 0;  // 0: an 8-bit item (I420 / NV12 by `nv12`); 1: P010, 2: I010 (k = yuvDecodeCoefficients10)
+	int sampled = 0;  // 0: a 4:2:0 item, as above; else its YuvSampled value (the bytes of launchYuvSampledToBgrx)
 };
 struct YuvDecodeItems {
 	YuvDecodeItem item[kFlowBatchMax];
@@ -480,6 +502,21 @@ void launchStateToYuv420p10(bool p010, const void *state, const YuvEncode10 &k, 
 // P = 257 u8 of a BGRX frame (any alignment, signed stride)
 void launchBgrxToYuv420p10(bool p010, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
     const YuvPlanes &dst, int width, int height, hipStream_t stream);
+
+// ---- 4:2:2 (YUY2 / UYVY packed, I422, P210, I210) and 4:4:4 (I444, I410) <-> BGRX ------------------------------------------
+// `format`: a YuvSampled value (std::invalid_argument for one the kernel does not take).  Planes as YuvPlanes: a packed
+// frame is plane y alone, rows of 2 width bytes; chroma planes have `height` rows of width / 2 (4:2:2; P210: width
+// interleaved) or width (4:4:4) samples.  4:2:2 needs an even width; any height, and for 4:4:4 any width.  Chroma is
+// co-sited with the even luma columns; tests/yuv_sampled_reference.py is the definition.  Coefficients: those of the
+// 4:2:0 launches of the same depth.
+void launchYuvSampledToBgrx(int format, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
+    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
+void launchBgrxToYuvSampled(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream);  // the 8-bit formats
+void launchStateToYuvSampled10(int format, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
+    int height, hipStream_t stream);  // the 10-bit formats, P as launchStateToYuv420p10
+void launchBgrxToYuvSampled10(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
+    const YuvPlanes &dst, int width, int height, hipStream_t stream);  // the 10-bit formats, P = 257 u8
 
 // ---- source stage (source_kernels.hip; docs/source_stage.md): sources of any size, masked pass-through ---------------
 // One axis of the triangle scaler, N source samples -> M destination samples, in integers (buildScaleAxis is the

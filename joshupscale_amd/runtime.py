@@ -47,6 +47,10 @@ class JuImage(C.Structure):
 # 4:2:0 frames of ju_process_frame (include/joshupscale_amd.h; formulas: INTEGRATION.md, "YUV frames"); P010 / I010:
 # 10-bit samples in 16-bit words (uint16 planes; P010 the value << 6, I010 the value in the low bits)
 FMT_BGRX, FMT_I420, FMT_NV12, FMT_P010, FMT_I010 = 0, 1, 2, 3, 4
+# 4:2:2 (packed YUY2 / UYVY, planar I422 / I210, semi-planar P210) and 4:4:4 (I444, I410)
+FMT_YUY2, FMT_UYVY, FMT_I422, FMT_P210, FMT_I210, FMT_I444, FMT_I410 = 16, 17, 18, 19, 20, 24, 25
+_FMT_DEEP = (FMT_P010, FMT_I010, FMT_P210, FMT_I210, FMT_I410)
+_FMT_PACKED = (FMT_YUY2, FMT_UYVY)
 CS_BT601_LIMITED, CS_BT601_FULL, CS_BT709_LIMITED, CS_BT709_FULL = 0, 1, 2, 3
 
 
@@ -146,6 +150,8 @@ _HOOK_SIGS = {
                                _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_yuv10": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                  _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_yuv_sampled": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
+                                       _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_yuv_items": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_size_t, C.c_size_t, _P(C.c_void_p),
                                      _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_source": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
@@ -531,27 +537,36 @@ def _frame(fmt: int, colorspace: int, location: int, width: int, height: int, pt
 
 def host_frame(fmt: int, planes, colorspace: int = CS_BT709_LIMITED) -> JuFrame:
     """Describe numpy planes as a host frame.  FMT_BGRX: ``[bgrx [H, W, 4]]``; FMT_I420: ``[y [H, W], u, v
-    [H/2, W/2]]``; FMT_NV12: ``[y [H, W], uv [H/2, W]]``; FMT_I010 / FMT_P010: the same shapes as ``uint16``.  Any
+    [H/2, W/2]]``; FMT_NV12: ``[y [H, W], uv [H/2, W]]``; FMT_I010 / FMT_P010: the same shapes as ``uint16``.
+    FMT_YUY2 / FMT_UYVY: ONE ``[H, 2W]`` uint8 array; FMT_I422 / FMT_I210: ``[y [H, W], u, v [H, W/2]]``; FMT_P210:
+    ``[y [H, W], uv [H, W]]``; FMT_I444 / FMT_I410: ``[y, u, v [H, W]]`` (the 10-bit formats ``uint16``).  Any
     row stride (a ``[::-1]`` view is bottom-up; the frame's strides are the arrays' byte strides); the columns must be
     contiguous.  The arrays must outlive the call."""
-    deep = fmt in (FMT_P010, FMT_I010)
+    deep = fmt in _FMT_DEEP
     for p in planes:
         if p.dtype != (np.uint16 if deep else np.uint8) or p.strides[1] != (4 if fmt == FMT_BGRX else (2 if deep else 1)):
-            raise ValueError("planes must be uint8 (P010 / I010: uint16) with contiguous columns")
+            raise ValueError("planes must be uint8 (the 10-bit formats: uint16) with contiguous columns")
     y = planes[0]
-    return _frame(fmt, colorspace, LOC_CPU, y.shape[1], y.shape[0], [p.ctypes.data for p in planes],
+    if fmt in _FMT_PACKED and (len(planes) != 1 or y.ndim != 2 or y.shape[1] % 4):
+        raise ValueError("a packed 4:2:2 frame is one [H, 2W] uint8 array, W even")
+    width = y.shape[1] // 2 if fmt in _FMT_PACKED else y.shape[1]
+    return _frame(fmt, colorspace, LOC_CPU, width, y.shape[0], [p.ctypes.data for p in planes],
                   [p.strides[0] for p in planes])
 
 
 def device_frame(fmt: int, width: int, height: int, ptrs, strides=None,
                  colorspace: int = CS_BT709_LIMITED) -> JuFrame:
     """A device frame from raw device pointers (or torch tensors: their ``data_ptr()``); ``strides`` default to
-    dense rows in bytes (BGRX 4W, Y W, I420 chroma W/2, NV12 chroma W; P010 / I010 twice that)."""
+    dense rows in bytes (BGRX 4W, Y W, I420 / I422 chroma W/2, NV12 chroma W, I444 chroma W, YUY2 / UYVY 2W; the 10-bit
+    formats twice that)."""
     ptrs = [p.data_ptr() if hasattr(p, "data_ptr") else int(p) for p in ptrs]
     if strides is None:
         strides = {FMT_BGRX: [4 * width], FMT_I420: [width, width // 2, width // 2],
                    FMT_NV12: [width, width], FMT_P010: [2 * width, 2 * width],
-                   FMT_I010: [2 * width, width, width]}[fmt]
+                   FMT_I010: [2 * width, width, width],
+                   FMT_YUY2: [2 * width], FMT_UYVY: [2 * width], FMT_I422: [width, width // 2, width // 2],
+                   FMT_P210: [2 * width, 2 * width], FMT_I210: [2 * width, width, width],
+                   FMT_I444: [width, width, width], FMT_I410: [2 * width, 2 * width, 2 * width]}[fmt]
     return _frame(fmt, colorspace, LOC_DEVICE, width, height, ptrs, strides)
 
 
