@@ -110,13 +110,43 @@ typedef struct ju_image {
  * 4:2:2 needs an even width (any height), 4:4:4 neither; the 4:2:0 formats need both even.  With these coefficients a
  * JU_FMT_I410 frame carries an 8-bit frame without loss: decoding the encoding of 257 x u8 returns every colour.
  *
- * Memory: each runtime holds two staging buffers for host planes that fit the largest format (JU_FMT_I410, 6 bytes per
- * pixel: 12.4 MB for a 1920x1080 output, 6.2 MB more than the 4:2:0 formats needed), and ju_process_frames allocates one
- * such slot per frame of a pass on first use (twice the former size).
+ * RGB in other layouts and depths (what OpenCV, ffmpeg rgb24 / bgr24 / gbrp* / gbrpf32le / bgra64le, VapourSynth RGBS /
+ * RGBH and AviSynth+ RGBP* / RGB64 hold; BGR96F is the [1,H,W,3] float tensor of a model whose uint8 input and output were
+ * turned into float).  `colorspace` is ignored, as for BGRX.  Planar planes are passed as planes[0..2] = R, G, B: a caller
+ * whose memory order is G, B, R (ffmpeg gbrp*, AviSynth+) passes the pointers in that order, as for YV12 above.
  *
- * Limits: 8- and 10-bit (no P016 / 12-bit, no NV16, no packed 10-bit Y210 / v210 / Y410, no 16-bit RGB output, no
- * dithering, no other chroma siting); no YUV
- * graphics resources (GL textures stay BGRX); look-ahead passes take YUV frames through ju_process_frames
+ *   format          layout
+ *   JU_FMT_BGR24    one plane, [H][3W] bytes B,G,R
+ *   JU_FMT_RGB24    one plane, [H][3W] bytes R,G,B
+ *   JU_FMT_RGBX     one plane, [H][4W] bytes R,G,B,X (X ignored in, 0 out)
+ *   JU_FMT_BGRX64   one plane, [H][4W] 16-bit LE words B,G,R,X (X ignored in, 0 out)
+ *   JU_FMT_RGBP8    R, G, B [H][W] bytes
+ *   JU_FMT_RGBP10   R, G, B [H][W] words, value in the LOW 10 bits (upper 6 ignored in, 0 out)
+ *   JU_FMT_RGBP16   R, G, B [H][W] words
+ *   JU_FMT_RGBPH    R, G, B [H][W] IEEE f16, nominal range 0..1
+ *   JU_FMT_RGBPS    R, G, B [H][W] IEEE f32, nominal range 0..1
+ *   JU_FMT_BGR96F   one plane, [H][3W] f32 B,G,R, nominal range 0..255
+ *
+ * Any width and height.  Every input is reduced to the 8-bit BGRX frame the network consumes: the 8-bit formats are a
+ * permutation of bytes; a 16-bit word P gives (P + 128) / 257; a 10-bit value p is widened to P = (p << 6) | (p >> 4)
+ * first; an f16 / f32 sample v gives floor(clamp(v, 0, 1) * 255 + 0.5) and a BGR96F sample floor(clamp(v, 0, 255) + 0.5)
+ * (NaN gives 0, infinities clamp).  This ROUNDS where the reference's castKernel truncates; on integer-valued floats,
+ * which is all the reference ever produces, the two agree.  8-bit outputs are a permutation of the BGRX output's bytes.
+ * The deep outputs (BGRX64, RGBP10 / 16 / H / S, BGR96F) come from the same source as a 10-bit YUV output ("hbd_from_state"):
+ * from the f16 state s, t = s + 0.5, the word is floor(65536 t) saturated (RGBP10: its upper 10 bits), RGBPS is clamp(t, 0,
+ * 1), RGBPH that value rounded to f16, BGR96F clamp(t, 0, 1) * 255 -- the frame in float without the truncating cast;
+ * from the 8-bit frame (normalize_brightness and output_flow models, or while a source mask is set) the word is 257 u8,
+ * RGBPS u8 / 255, BGR96F u8.  tests/rgb_reference.py is the definition, bit for bit.
+ *
+ * Memory: each runtime holds two staging buffers for host planes that fit the largest format (JU_FMT_BGR96F / JU_FMT_RGBPS,
+ * 12 bytes per pixel: 24.9 MB for a 1920x1080 output, 12.4 MB more than the YUV formats needed; 1.6 MB for a 480x270
+ * input), and ju_process_frames allocates one such slot per frame of a pass on first use (twice the former size).  All
+ * are sized once for the largest format: nothing is regrown behind a captured graph.
+ *
+ * Limits: 8- and 10-bit YUV (no P016 / 12-bit, no NV16, no packed 10-bit Y210 / v210 / Y410, no other chroma siting); RGB
+ * without 12-bit, without packed 10-bit (x2rgb10, R10G10B10A2), without dithering and without alpha (X is ignored and
+ * written 0); float inputs are quantised to 8 bits like every input, they do not reach the network unquantised; no YUV
+ * or RGB graphics resources (GL textures stay BGRX); look-ahead passes take these frames through ju_process_frames
  * (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not ju_process_group; the C++ plugin surface
  * (JoshUpscale/core.h) is unchanged and takes BGRX only. */
 enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2, JU_FMT_P010 = 3, JU_FMT_I010 = 4 };
@@ -124,19 +154,24 @@ enum {
 	JU_FMT_YUY2 = 16, JU_FMT_UYVY = 17, JU_FMT_I422 = 18, JU_FMT_P210 = 19, JU_FMT_I210 = 20,
 	JU_FMT_I444 = 24, JU_FMT_I410 = 25
 };
+enum {
+	JU_FMT_BGR24 = 32, JU_FMT_RGB24 = 33, JU_FMT_RGBX = 34, JU_FMT_BGRX64 = 35, JU_FMT_RGBP8 = 36, JU_FMT_RGBP10 = 37,
+	JU_FMT_RGBP16 = 38, JU_FMT_RGBPH = 39, JU_FMT_RGBPS = 40, JU_FMT_BGR96F = 41
+};
 enum { JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3 };
 
 typedef struct ju_frame {
 	int format;            /* JU_FMT_* */
-	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX */
+	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX and the RGB formats (32..41) */
 	uint8_t location;      /* JU_LOC_CPU or JU_LOC_DEVICE (BGRX: any location a ju_image takes) */
 	size_t width, height;  /* in pixels (luma); even for the 4:2:0 formats, an even width for 4:2:2 */
-	void *planes[3];       /* BGRX, YUY2, UYVY: [0]; planar formats: Y, U, V; NV12 / P010 / P210: Y, interleaved UV (U
-	                          first); planes beyond a format's count are not read */
+	void *planes[3];       /* BGRX, YUY2, UYVY and the packed RGB formats: [0]; planar formats: Y, U, V or R, G, B; NV12 /
+	                          P010 / P210: Y, interleaved UV (U first); planes beyond a format's count are not read */
 	ptrdiff_t strides[3];  /* BYTES per row of each plane (first logical row at planes[k]), any sign,
 	                          |stride| >= the plane's row bytes: Y = width, U / V = width / 2 (4:4:4: width), UV = width,
-	                          YUY2 / UYVY = 2 width, BGRX = 4 width; the 10-bit formats: twice that, and plane addresses
-	                          and strides are multiples of 2 */
+	                          YUY2 / UYVY = 2 width, BGRX = 4 width; the 10-bit formats: twice that; RGB: width x 3 (BGR24 /
+	                          RGB24), 4 (RGBX), 8 (BGRX64), 12 (BGR96F), planar width x 1, 2 or 4.  Plane addresses and
+	                          strides are multiples of 2 for 16-bit and f16 samples and of 4 for f32 samples */
 } ju_frame;
 
 /* Replaces createRuntime(int deviceId, const std::filesystem::path &modelPath)

@@ -87,6 +87,14 @@ JU_API int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size
 JU_API int ju_debug_yuv_sampled(int op, int format, int colorspace, size_t width, size_t height, void *image,
     ptrdiff_t image_stride, void *const planes[3], const ptrdiff_t strides[3]);
 
+/* One of the RGB conversion kernels alone (format JU_FMT_BGR24 .. JU_FMT_BGR96F; tests/rgb_reference.py), on
+ * caller-supplied device buffers, on the current device (synchronous).  op 0: planes -> BGRX rows at `image`; op 1: BGRX
+ * u8 rows at `image` -> planes (deep formats: from the 8-bit frame); op 2, deep formats only: the dense f16 tensor
+ * [height][width][4] at `image`, 16-byte aligned, image_stride ignored -> planes.  Any width and height; plane addresses
+ * and strides are multiples of the sample size.  ju_debug_yuv_items takes these formats as items too. */
+JU_API int ju_debug_rgb(int op, int format, size_t width, size_t height, void *image, ptrdiff_t image_stride,
+    void *const planes[3], const ptrdiff_t strides[3]);
+
 /* The source stage's kernels alone (docs/source_stage.md), on caller-supplied device buffers of BGRX rows with any byte
  * alignment and any signed strides, on the current device (synchronous).  op 0: the scaler -- `src` (src_width x
  * src_height) -> `dst` (dst_width x dst_height), tables built as ju_set_source_size builds them; the mask arguments are

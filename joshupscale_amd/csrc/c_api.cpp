@@ -75,21 +75,26 @@ ju::Frame toFrame(const ju_image *img) {
 	    img->height};
 }
 
-// A JU_FMT_* value through the one table of the YUV formats (kernels.h): its planes (0: not a YUV format), whether
-// its samples are 16-bit words, and whether it is one of the 4:2:2 / 4:4:4 formats
+// A JU_FMT_* value through the one table of the formats beside BGRX (kernels.h): its planes (0: not in the table), whether
+// its samples are 10-bit YUV words, whether it is one of the 4:2:2 / 4:4:4 formats or an RGB format, its sample size
 int planesOfFormat(int format) {
 	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
 	return info ? info->planes : 0;
 }
 [[maybe_unused]] bool wordsOfFormat(int format) {
 	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
-	return info && info->bits == 10;
+	return info && info->bits == 10 && info->sampling != 0;  // (10-bit YUV words; not RGBP10)
 }
 [[maybe_unused]] int samplingOfFormat(int format) {
 	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
 	return info ? info->sampling : 0;
 }
 [[maybe_unused]] bool sampledFormat(int format) { return samplingOfFormat(format) == 422 || samplingOfFormat(format) == 444; }
+[[maybe_unused]] bool rgbFormat(int format) { return planesOfFormat(format) != 0 && samplingOfFormat(format) == 0; }
+[[maybe_unused]] int sampleBytesOfFormat(int format) {
+	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
+	return info ? info->sampleBytes : 1;
+}
 
 // A ju_frame as the engine's AnyFrame; BGRX frames exactly as toFrame makes them of a ju_image
 ju::AnyFrame toAnyFrame(const ju_frame *f) {
@@ -482,6 +487,7 @@ int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, si
 		bool needEvenWidth = false, needEvenHeight = false;
 		for (int i = 0; i < count; ++i) {
 			if (planesOfFormat(formats[i]) == 0) throw std::invalid_argument("ju_debug_yuv_items: not a YUV format");
+			if (rgbFormat(formats[i])) continue;  // (any size)
 			if (samplingOfFormat(formats[i]) != 444) needEvenWidth = true;
 			if (samplingOfFormat(formats[i]) == 420) needEvenHeight = true;
 		}
@@ -500,9 +506,11 @@ int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, si
 			if (bgrx[i] == nullptr || p[0] == nullptr || (count_k > 1 && p[1] == nullptr) || (planar && p[2] == nullptr)) {
 				throw std::invalid_argument("ju_debug_yuv_items: null buffer");
 			}
-			for (int k = 0; deep && k < count_k; ++k) {
-				if (reinterpret_cast<std::uintptr_t>(p[k]) % 2 || strides[3 * i + k] % 2) {
-					throw std::invalid_argument("ju_debug_yuv_items: 16-bit planes need even addresses and strides");
+			const int sample = sampleBytesOfFormat(f);
+			for (int k = 0; sample > 1 && k < count_k; ++k) {
+				if (reinterpret_cast<std::uintptr_t>(p[k]) % sample || strides[3 * i + k] % sample) {
+					throw std::invalid_argument(sample == 2 ? "ju_debug_yuv_items: 16-bit planes need even addresses and strides"
+					                                        : "ju_debug_yuv_items: 32-bit planes need addresses and strides that are multiples of 4");
 				}
 			}
 			ju::YuvDecodeItem &it = items.item[i];
@@ -512,9 +520,9 @@ int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, si
 			it.src.yStride = strides[3 * i];
 			it.src.uStride = count_k > 1 ? strides[3 * i + 1] : 0;
 			it.src.vStride = planar ? strides[3 * i + 2] : 0;
-			it.k = deep ? ju::yuvDecodeCoefficients10(colorspaces[i]) : ju::yuvDecodeCoefficients(colorspaces[i]);
+			if (!rgbFormat(f)) it.k = deep ? ju::yuvDecodeCoefficients10(colorspaces[i]) : ju::yuvDecodeCoefficients(colorspaces[i]);
 			it.deep = f == JU_FMT_P010 ? 1 : (f == JU_FMT_I010 ? 2 : 0);
-			it.sampled = sampledFormat(f) ? f : 0;
+			it.sampled = sampledFormat(f) || rgbFormat(f) ? f : 0;
 			it.dst = static_cast<std::uint8_t *>(bgrx[i]);
 			it.dstStride = bgrx_strides[i];
 			it.nv12 = f == JU_FMT_NV12 ? 1 : 0;
@@ -610,6 +618,52 @@ int ju_debug_yuv_sampled(int op, int format, int colorspace, size_t width, size_
 		} else {
 			ju::launchBgrxToYuvSampled(format, static_cast<const std::uint8_t *>(image), image_stride,
 			    ju::yuvEncodeCoefficients(colorspace), p, w, h, nullptr);
+		}
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_rgb(int op, int format, size_t width, size_t height, void *image, ptrdiff_t image_stride,
+    void *const planes[3], const ptrdiff_t strides[3]) {
+	return guarded([&] {
+		if (op < 0 || op > 2) throw std::invalid_argument("ju_debug_rgb: op must be 0, 1 or 2");
+		if (!rgbFormat(format)) throw std::invalid_argument("ju_debug_rgb: not an RGB format");
+		const ju::YuvFormatInfo &info = *ju::yuvFormatInfo(format);
+		if (op == 2 && info.bits == 8) throw std::invalid_argument("ju_debug_rgb: op 2 takes the deep formats only");
+		if (width == 0 || height == 0 || width > (1u << 15) || height > (1u << 15)) {
+			throw std::invalid_argument("ju_debug_rgb: sizes 1 .. 32768");
+		}
+		if (image == nullptr || planes == nullptr || strides == nullptr) {
+			throw std::invalid_argument("ju_debug_rgb: null buffer");
+		}
+		const auto row = static_cast<ptrdiff_t>((info.planes == 1 ? info.pixelBytes : info.sampleBytes) * width);
+		for (int k = 0; k < info.planes; ++k) {
+			if (planes[k] == nullptr) throw std::invalid_argument("ju_debug_rgb: null buffer");
+			if (reinterpret_cast<std::uintptr_t>(planes[k]) % info.sampleBytes || strides[k] % info.sampleBytes) {
+				throw std::invalid_argument("ju_debug_rgb: plane addresses and strides must be multiples of the sample size");
+			}
+			if (strides[k] > -row && strides[k] < row) throw std::invalid_argument("ju_debug_rgb: |stride| smaller than a row");
+		}
+		if (op != 2 && image_stride > -static_cast<ptrdiff_t>(4 * width) && image_stride < static_cast<ptrdiff_t>(4 * width)) {
+			throw std::invalid_argument("ju_debug_rgb: |image_stride| smaller than a row");
+		}
+		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) {
+			throw std::invalid_argument("ju_debug_rgb: the f16 tensor must be 16-byte aligned");
+		}
+		ju::YuvPlanes p;
+		p.y = static_cast<std::uint8_t *>(planes[0]);
+		p.u = info.planes > 1 ? static_cast<std::uint8_t *>(planes[1]) : nullptr;
+		p.v = info.planes > 2 ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
+		p.yStride = strides[0];
+		p.uStride = info.planes > 1 ? strides[1] : 0;
+		p.vStride = info.planes > 2 ? strides[2] : 0;
+		const int w = static_cast<int>(width), h = static_cast<int>(height);
+		if (op == 0) {
+			ju::launchRgbToBgrx(format, p, static_cast<std::uint8_t *>(image), image_stride, w, h, nullptr);
+		} else if (op == 1) {
+			ju::launchBgrxToRgb(format, static_cast<const std::uint8_t *>(image), image_stride, p, w, h, nullptr);
+		} else {
+			ju::launchStateToRgb(format, image, p, w, h, nullptr);
 		}
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});

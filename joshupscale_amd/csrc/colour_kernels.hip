@@ -22,6 +22,10 @@ namespace {
 
 constexpr int kStrip = 16;  // luma pixels per thread and row
 
+// four dwords moved as ONE 16-byte access (a struct of four members is split into member accesses, which the compiler
+// then merges with an equal dword path and loses the width)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
 __device__ inline bool alignedTo(const void *p, unsigned a) {
 	return (reinterpret_cast<std::uintptr_t>(p) & (a - 1)) == 0;
 }
@@ -409,6 +413,9 @@ __global__ __launch_bounds__(256) void yuv420p10_to_bgrx_kernel(YuvPlanes src, Y
 	yuv420p10ToBgrxStrip<P010>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
+// the sample kinds of the RGB formats ("RGB formats" below)
+enum RgbKind : int { kU8, kW16, kW10, kHalf, kUnit, kF255 };
+
 // The 16-bit samples P (0 .. 65535) of 17 pixels of one row -- column x0 - 1 (clamped to 0) and columns x0 .. x0 + 15
 // (clamped to W - 1) -- as the two sources of the 10-bit encode form them; kept packed (registers), read through b / g / r.
 // From the engine's f16 state [H][W][4] (B, G, R, 0; dense, 16-byte aligned): floor((s + 0.5) * 65536), saturated.  In
@@ -448,6 +455,39 @@ struct StateSource {
 			}
 		}
 	}
+	// An RGB encode ("RGB formats" below) reads the strip's 16 pixels as they lie in memory (no neighbour column: nothing
+	// is filtered) and forms one channel's sample of kind K (RgbKind): t = s + 0.5, exact in f32; W16 is `sample`, W10 its
+	// upper 10 bits, the float kinds clamp(t, 0, 1), that as f16 rounded to nearest even, or x 255.
+	using Raw = uint2;  // the pixel's four f16: x = B | G << 16, y = R | unused << 16
+	__device__ static unsigned rawB(Raw p) { return p.x & 0xffff; }
+	__device__ static unsigned rawG(Raw p) { return p.x >> 16; }
+	__device__ static unsigned rawR(Raw p) { return p.y & 0xffff; }
+	template <int K>
+	__device__ static unsigned deep(unsigned bits) {
+		if constexpr (K == kW16) return sample(bits);
+		else if constexpr (K == kW10) return sample(bits) >> 6;
+		else {
+			const float t = static_cast<float>(__builtin_bit_cast(f16, static_cast<unsigned short>(bits))) + 0.5f;
+			const float u = fminf(fmaxf(t, 0.0f), 1.0f);
+			if constexpr (K == kUnit) return __builtin_bit_cast(unsigned, u);
+			else if constexpr (K == kHalf) return __builtin_bit_cast(unsigned short, static_cast<f16>(u));
+			else return __builtin_bit_cast(unsigned, u * 255.0f);
+		}
+	}
+	__device__ void loadRaw(int y, int x0, int W, bool full, Raw (&px)[16]) const {
+		const f16 *row = state + static_cast<std::size_t>(y) * W * 4;
+		if (full && alignedTo(row, 16)) {  // (a row of an odd width starts at 8 bytes: pixel by pixel below)
+#pragma unroll
+			for (int q = 0; q < 8; ++q) {
+				const u32x4 v = *reinterpret_cast<const u32x4 *>(row + 4 * (x0 + 2 * q));
+				px[2 * q] = make_uint2(v.x, v.y);
+				px[2 * q + 1] = make_uint2(v.z, v.w);
+			}
+		} else {
+#pragma unroll
+			for (int p = 0; p < 16; ++p) px[p] = *reinterpret_cast<const uint2 *>(row + 4 * min(x0 + p, W - 1));
+		}
+	}
 };
 
 // From a u8 BGRX frame (any alignment, signed stride): P = 257 u8 -- the bytes stay bytes, see kScale.
@@ -479,6 +519,39 @@ struct Bgrx8Source {
 			}
 #pragma unroll
 			for (int i = 0; i < 4; ++i) px[1 + 4 * q + i] = w[i];
+		}
+	}
+	// For an RGB encode: P = 257 u8; the float kinds f32(u8) / 255 (one correctly rounded division), that as f16, or f32(u8).
+	using Raw = unsigned;  // B | G << 8 | R << 16, as in the frame
+	__device__ static unsigned rawB(Raw p) { return p & 255; }
+	__device__ static unsigned rawG(Raw p) { return (p >> 8) & 255; }
+	__device__ static unsigned rawR(Raw p) { return (p >> 16) & 255; }
+	template <int K>
+	__device__ static unsigned deep(unsigned u) {
+		if constexpr (K == kW16) return 257 * u;
+		else if constexpr (K == kW10) return (257 * u) >> 6;
+		else if constexpr (K == kUnit) return __builtin_bit_cast(unsigned, static_cast<float>(u) / 255.0f);
+		else if constexpr (K == kHalf) {
+			return __builtin_bit_cast(unsigned short, static_cast<f16>(static_cast<float>(u) / 255.0f));
+		} else if constexpr (K == kF255) return __builtin_bit_cast(unsigned, static_cast<float>(u));
+		else return u;
+	}
+	__device__ void loadRaw(int y, int x0, int W, bool full, Raw (&px)[16]) const {
+		const std::uint8_t *row = src + static_cast<std::ptrdiff_t>(y) * stride;
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			unsigned w[4];
+			if (full) {
+				loadBytes<16>(row, 4 * (x0 + 4 * q), 4 * W - 1, true, w);
+			} else {
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const std::uint8_t *p = row + 4 * min(x0 + 4 * q + i, W - 1);
+					w[i] = p[0] | (p[1] << 8) | (p[2] << 16);
+				}
+			}
+#pragma unroll
+			for (int i = 0; i < 4; ++i) px[4 * q + i] = w[i];
 		}
 	}
 };
@@ -894,12 +967,250 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled10_kernel(const std::u
 	toYuvSampled10Strip<F>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
+// ---- RGB formats: 24-bit, RGBX, planar 8 / 10 / 16 bit, f16, f32 (tests/rgb_reference.py; docs/yuv_io.md, "RGB formats") ----
+// The network's BGRX frame in another layout and, for the deep formats, another sample kind; no colour space.  The
+// thread shape of the 4:2:2 / 4:4:4 section: 16 pixels of ONE row per thread.  A strip is a run of samples in each plane
+// it touches (planar: 16 in each of R, G, B; packed: 48 or 64 in the one plane) that moves as 16-byte accesses where the
+// run starts 16-byte aligned, as dwords at 4, else sample by sample -- tested per run, since dense rows of 3-byte pixels
+// start at every alignment.  F is the frame's RgbFormat value.
+
+template <int B>
+__device__ inline void putSample(unsigned *w, int k, unsigned v) {  // (into words that start as 0)
+	if constexpr (B == 4) w[k] = v;
+	else if constexpr (B == 2) w[k >> 1] |= v << (16 * (k & 1));
+	else w[k >> 2] |= v << (8 * (k & 3));
+}
+
+template <int B>
+__device__ inline unsigned loadSample(const std::uint8_t *p) {
+	if constexpr (B == 4) return *reinterpret_cast<const unsigned *>(p);
+	else if constexpr (B == 2) return *reinterpret_cast<const std::uint16_t *>(p);
+	else return *p;
+}
+
+// `N` samples of `B` bytes of one row from sample `first` on, little-endian in words.  `fast`: all in range -- 16-byte
+// loads where the run starts 16-byte aligned, dwords at 4, else sample by sample from the one address; not `fast`: sample
+// by sample in groups of `G` (a packed pixel; `first` a multiple of G), the group's index clamped to `lastGroup`
+template <int B, int N, int G>
+__device__ inline void loadRun(const std::uint8_t *row, int first, int lastGroup, bool fast, unsigned (&w)[N * B / 4]) {
+	constexpr int kWords = N * B / 4;
+	static_assert(kWords % 4 == 0 && N % G == 0, "a run is whole 16-byte groups and whole pixels");
+	const std::uint8_t *p = row + static_cast<std::ptrdiff_t>(first) * B;
+	if (fast && alignedTo(p, 16)) {
+#pragma unroll
+		for (int q = 0; q < kWords / 4; ++q) {
+			const u32x4 v = reinterpret_cast<const u32x4 *>(p)[q];
+			w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+		}
+		return;
+	}
+	if (fast && alignedTo(p, 4)) {
+#pragma unroll
+		for (int q = 0; q < kWords; ++q) w[q] = reinterpret_cast<const unsigned *>(p)[q];
+		return;
+	}
+#pragma unroll
+	for (int q = 0; q < kWords; ++q) w[q] = 0;
+	if (fast) {
+#pragma unroll
+		for (int k = 0; k < N; ++k) putSample<B>(w, k, loadSample<B>(p + k * B));
+		return;
+	}
+#pragma unroll
+	for (int g = 0; g < N / G; ++g) {
+		const std::uint8_t *pg = row + static_cast<std::ptrdiff_t>(min(first / G + g, lastGroup)) * (G * B);
+#pragma unroll
+		for (int i = 0; i < G; ++i) putSample<B>(w, g * G + i, loadSample<B>(pg + i * B));
+	}
+}
+
+template <int B>
+__device__ inline unsigned sampleAt(const unsigned *w, int k) {
+	if constexpr (B == 4) return w[k];
+	else if constexpr (B == 2) return static_cast<unsigned>(sampleOf(w, k));
+	else return static_cast<unsigned>(byteOf(w, k));
+}
+
+// `N` samples of `B` bytes of one row from sample `first` on; `fast`: all in range (else only the first `n`)
+template <int B, int N>
+__device__ inline void storeRun(std::uint8_t *row, int first, int n, bool fast, const unsigned (&w)[N * B / 4]) {
+	constexpr int kWords = N * B / 4;
+	std::uint8_t *p = row + static_cast<std::ptrdiff_t>(first) * B;
+	if (fast && alignedTo(p, 16)) {
+#pragma unroll
+		for (int q = 0; q < kWords / 4; ++q) {
+			const u32x4 v = {w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+			reinterpret_cast<u32x4 *>(p)[q] = v;
+		}
+		return;
+	}
+	if (fast && alignedTo(p, 4)) {
+#pragma unroll
+		for (int q = 0; q < kWords; ++q) reinterpret_cast<unsigned *>(p)[q] = w[q];
+		return;
+	}
+#pragma unroll
+	for (int k = 0; k < N; ++k) {
+		if (fast || k < n) {
+			if constexpr (B == 4) reinterpret_cast<unsigned *>(p)[k] = w[k];
+			else if constexpr (B == 2) reinterpret_cast<std::uint16_t *>(p)[k] = static_cast<std::uint16_t>(sampleOf(w, k));
+			else p[k] = static_cast<std::uint8_t>(byteOf(w, k));
+		}
+	}
+}
+
+template <int F>
+struct RgbTraits {
+	static constexpr bool kPlanar = F >= kRgbp8 && F <= kRgbps;  // planes R, G, B; else ONE plane of kPixel samples a pixel
+	static constexpr int kPixel = kPlanar ? 1 : ((F == kRgbx || F == kBgrx64) ? 4 : 3);
+	static constexpr int kB = (F == kRgb24 || F == kRgbx) ? 2 : 0, kG = 1, kR = 2 - kB;  // a packed pixel's samples
+	static constexpr int kKind = (F == kBgrx64 || F == kRgbp16) ? kW16
+	    : F == kRgbp10 ? kW10 : F == kRgbph ? kHalf : F == kRgbps ? kUnit : F == kBgr96f ? kF255 : kU8;
+	static constexpr int kBytes = kKind == kU8 ? 1 : ((kKind == kUnit || kKind == kF255) ? 4 : 2);
+};
+
+// floor(clamp(v, 0, top) scale + 0.5) with the product rounded to f32 BEFORE the sum (no fused multiply-add: the
+// definition is a multiply followed by an add); NaN -> 0, +-inf clamp
+__device__ inline unsigned roundedU8(float v, float top, float scale) {
+#pragma clang fp contract(off)
+	v = v >= 0.0f ? v : 0.0f;  // (false for NaN)
+	v = v > top ? top : v;
+	const float scaled = v * scale;
+	return static_cast<unsigned>(floorf(scaled + 0.5f));
+}
+
+// one sample of kind K (its bits) -> the u8 the network consumes
+template <int K>
+__device__ inline unsigned u8OfSample(unsigned s) {
+	if constexpr (K == kW16) return (s + 128) / 257;
+	else if constexpr (K == kW10) {
+		const unsigned p = s & 0x3ff;
+		return (((p << 6) | (p >> 4)) + 128) / 257;
+	} else if constexpr (K == kHalf) {
+		return roundedU8(static_cast<float>(__builtin_bit_cast(f16, static_cast<unsigned short>(s))), 1.0f, 255.0f);
+	} else if constexpr (K == kUnit) return roundedU8(__builtin_bit_cast(float, s), 1.0f, 255.0f);
+	else if constexpr (K == kF255) return roundedU8(__builtin_bit_cast(float, s), 255.0f, 1.0f);
+	else return s;
+}
+
+// planes -> BGRX: the strip of thread `idx`; the body of the single-frame kernel and of the items kernel's branch
+template <int F>
+__device__ __forceinline__ void rgbToBgrxStrip(const YuvPlanes &src, std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride,
+    int W, int H, int idx) {
+	using T = RgbTraits<F>;
+	constexpr int B = T::kBytes, K = T::kKind;
+	const int strips = (W + kStrip - 1) / kStrip;
+	if (idx >= strips * H) return;
+	const int y = idx / strips;
+	const int x0 = (idx - y * strips) * kStrip;
+	const bool full = x0 + kStrip <= W;
+	const int n = min(kStrip, W - x0);
+	std::uint8_t *out = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
+	if constexpr (T::kPlanar) {
+		unsigned wr[4 * B], wg[4 * B], wb[4 * B];
+		loadRun<B, 16, 1>(src.y + static_cast<std::ptrdiff_t>(y) * src.yStride, x0, W - 1, full, wr);
+		loadRun<B, 16, 1>(src.u + static_cast<std::ptrdiff_t>(y) * src.uStride, x0, W - 1, full, wg);
+		loadRun<B, 16, 1>(src.v + static_cast<std::ptrdiff_t>(y) * src.vStride, x0, W - 1, full, wb);
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			unsigned px[4];
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				const int p = 4 * q + i;
+				px[i] = u8OfSample<K>(sampleAt<B>(wb, p)) | (u8OfSample<K>(sampleAt<B>(wg, p)) << 8) |
+				        (u8OfSample<K>(sampleAt<B>(wr, p)) << 16);
+			}
+			storeBytes<16>(out, 4 * (x0 + 4 * q), 4 * (n - 4 * q), full, px);
+		}
+	} else {
+		// in runs of C pixels, the fewest whose bytes are whole 16-byte groups (BGR24 / RGB24: all 16, 48 B; else 4); four
+		// pixels are 16 bytes of BGRX, stored as they are formed
+		constexpr int P = T::kPixel, C = (4 * P * B) % 16 == 0 ? 4 : 16;
+		const std::uint8_t *row = src.y + static_cast<std::ptrdiff_t>(y) * src.yStride;
+#pragma unroll
+		for (int c = 0; c < 16 / C; ++c) {
+			unsigned w[C * P * B / 4];
+			loadRun<B, C * P, P>(row, (x0 + c * C) * P, W - 1, full, w);
+#pragma unroll
+			for (int q = 0; q < C / 4; ++q) {
+				unsigned px[4];
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const int p = 4 * q + i;
+					px[i] = u8OfSample<K>(sampleAt<B>(w, p * P + T::kB)) | (u8OfSample<K>(sampleAt<B>(w, p * P + T::kG)) << 8) |
+					        (u8OfSample<K>(sampleAt<B>(w, p * P + T::kR)) << 16);
+				}
+				const int x = c * C + 4 * q;  // (first pixel of the four, within the strip)
+				storeBytes<16>(out, 4 * (x0 + x), 4 * (n - x), full, px);
+			}
+		}
+	}
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void rgb_to_bgrx_kernel(YuvPlanes src, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H) {
+	rgbToBgrxStrip<F>(src, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+// source -> the planes of format F: the strip body of both encodes.  The X samples of RGBX / BGRX64 are written 0.
+template <int F, typename Source>
+__device__ inline void toRgbStrip(const Source &source, const YuvPlanes &dst, int W, int H, int idx) {
+	using T = RgbTraits<F>;
+	constexpr int B = T::kBytes, K = T::kKind;
+	const int strips = (W + kStrip - 1) / kStrip;
+	if (idx >= strips * H) return;
+	const int y = idx / strips;
+	const int x0 = (idx - y * strips) * kStrip;
+	const bool full = x0 + kStrip <= W;
+	const int n = min(kStrip, W - x0);
+	typename Source::Raw px[16];
+	source.loadRaw(y, x0, W, full, px);
+	if constexpr (T::kPlanar) {
+		unsigned wr[4 * B], wg[4 * B], wb[4 * B];
+#pragma unroll
+		for (int q = 0; q < 4 * B; ++q) wr[q] = wg[q] = wb[q] = 0;
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			putSample<B>(wr, p, Source::template deep<K>(Source::rawR(px[p])));
+			putSample<B>(wg, p, Source::template deep<K>(Source::rawG(px[p])));
+			putSample<B>(wb, p, Source::template deep<K>(Source::rawB(px[p])));
+		}
+		storeRun<B, 16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, wr);
+		storeRun<B, 16>(dst.u + static_cast<std::ptrdiff_t>(y) * dst.uStride, x0, n, full, wg);
+		storeRun<B, 16>(dst.v + static_cast<std::ptrdiff_t>(y) * dst.vStride, x0, n, full, wb);
+	} else {
+		constexpr int P = T::kPixel;
+		unsigned w[4 * P * B];
+#pragma unroll
+		for (int q = 0; q < 4 * P * B; ++q) w[q] = 0;
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			putSample<B>(w, p * P + T::kB, Source::template deep<K>(Source::rawB(px[p])));
+			putSample<B>(w, p * P + T::kG, Source::template deep<K>(Source::rawG(px[p])));
+			putSample<B>(w, p * P + T::kR, Source::template deep<K>(Source::rawR(px[p])));
+		}
+		storeRun<B, 16 * P>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0 * P, n * P, full, w);
+	}
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void bgrx_to_rgb_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
+    YuvPlanes dst, int W, int H) {
+	toRgbStrip<F>(Bgrx8Source{src, srcStride}, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void state_to_rgb_kernel(const f16 *__restrict__ state, YuvPlanes dst, int W, int H) {
+	toRgbStrip<F>(StateSource{state}, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
 // The YUV inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item --
 // its planes, coefficients and destination, from the kernel arguments -- and its format is a branch every lane of the
 // workgroup takes alike.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
 // launch latencies for one round of work (the shape addFlowAutoencoder's batched launches fixed for the flow net).
-// (a 4:2:2 / 4:4:4 item has a strip per row: the grid then covers strips x H threads and a 4:2:0 item's upper half of
-// them returns at once)
+// (a 4:2:2 / 4:4:4 or RGB item has a strip per row: the grid then covers strips x H threads and a 4:2:0 item's upper half
+// of them returns at once; `sampled` carries an RGB item's format value too, and its coefficients are not read)
 __global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
 	const YuvDecodeItem &it = items.item[blockIdx.y];
 	const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -911,6 +1222,16 @@ __global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItem
 	case kI210: return yuvSampledToBgrxStrip<kI210>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
 	case kI444: return yuvSampledToBgrxStrip<kI444>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
 	case kI410: return yuvSampledToBgrxStrip<kI410>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	case kBgr24: return rgbToBgrxStrip<kBgr24>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kRgb24: return rgbToBgrxStrip<kRgb24>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kRgbx: return rgbToBgrxStrip<kRgbx>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kBgrx64: return rgbToBgrxStrip<kBgrx64>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kRgbp8: return rgbToBgrxStrip<kRgbp8>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kRgbp10: return rgbToBgrxStrip<kRgbp10>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kRgbp16: return rgbToBgrxStrip<kRgbp16>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kRgbph: return rgbToBgrxStrip<kRgbph>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kRgbps: return rgbToBgrxStrip<kRgbps>(it.src, it.dst, it.dstStride, W, H, idx);
+	case kBgr96f: return rgbToBgrxStrip<kBgr96f>(it.src, it.dst, it.dstStride, W, H, idx);
 	default: break;
 	}
 	if (it.deep == 1) {  // (P010; 2: I010 -- 10-bit items, as uniform per workgroup as the 8-bit formats)
@@ -1029,7 +1350,7 @@ void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std
 
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream) {
 	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("yuv420_to_bgrx_items: 1 .. 8 items");
-	bool perRow = false;  // (a 4:2:2 / 4:4:4 item: a strip per row, not per row pair)
+	bool perRow = false;  // (a 4:2:2 / 4:4:4 or RGB item: a strip per row, not per row pair)
 	for (int i = 0; i < count; ++i) perRow = perRow || items.item[i].sampled != 0;
 	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (perRow ? height : height / 2);
 	hipLaunchKernelGGL(yuv420_to_bgrx_items_kernel, dim3(blocksFor(threads), count), dim3(256), 0, stream, items, width,
@@ -1171,6 +1492,74 @@ void launchBgrxToYuvSampled10(int format, const std::uint8_t *src, std::ptrdiff_
 	}
 #undef JU_SAMPLED_ENCODE
 	hipCheckLaunch("bgrx_to_yuv_sampled10");
+}
+
+void launchRgbToBgrx(int format, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride, int width, int height,
+    hipStream_t stream) {
+	const dim3 grid(blocksFor(sampledThreads(width, height)));
+#define JU_RGB_DECODE(F) \
+	case F: \
+		hipLaunchKernelGGL(rgb_to_bgrx_kernel<F>, grid, dim3(256), 0, stream, src, dst, dstStride, width, height); \
+		break;
+	switch (format) {
+		JU_RGB_DECODE(kBgr24)
+		JU_RGB_DECODE(kRgb24)
+		JU_RGB_DECODE(kRgbx)
+		JU_RGB_DECODE(kBgrx64)
+		JU_RGB_DECODE(kRgbp8)
+		JU_RGB_DECODE(kRgbp10)
+		JU_RGB_DECODE(kRgbp16)
+		JU_RGB_DECODE(kRgbph)
+		JU_RGB_DECODE(kRgbps)
+		JU_RGB_DECODE(kBgr96f)
+	default: notSampled("rgb_to_bgrx", format);
+	}
+#undef JU_RGB_DECODE
+	hipCheckLaunch("rgb_to_bgrx");
+}
+
+void launchBgrxToRgb(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst, int width,
+    int height, hipStream_t stream) {
+	const dim3 grid(blocksFor(sampledThreads(width, height)));
+#define JU_RGB_ENCODE(F) \
+	case F: \
+		hipLaunchKernelGGL(bgrx_to_rgb_kernel<F>, grid, dim3(256), 0, stream, src, srcStride, dst, width, height); \
+		break;
+	switch (format) {
+		JU_RGB_ENCODE(kBgr24)
+		JU_RGB_ENCODE(kRgb24)
+		JU_RGB_ENCODE(kRgbx)
+		JU_RGB_ENCODE(kBgrx64)
+		JU_RGB_ENCODE(kRgbp8)
+		JU_RGB_ENCODE(kRgbp10)
+		JU_RGB_ENCODE(kRgbp16)
+		JU_RGB_ENCODE(kRgbph)
+		JU_RGB_ENCODE(kRgbps)
+		JU_RGB_ENCODE(kBgr96f)
+	default: notSampled("bgrx_to_rgb", format);
+	}
+#undef JU_RGB_ENCODE
+	hipCheckLaunch("bgrx_to_rgb");
+}
+
+void launchStateToRgb(int format, const void *state, const YuvPlanes &dst, int width, int height, hipStream_t stream) {
+	const dim3 grid(blocksFor(sampledThreads(width, height)));
+	const f16 *s = static_cast<const f16 *>(state);
+#define JU_RGB_ENCODE(F) \
+	case F: \
+		hipLaunchKernelGGL(state_to_rgb_kernel<F>, grid, dim3(256), 0, stream, s, dst, width, height); \
+		break;
+	switch (format) {
+		JU_RGB_ENCODE(kBgrx64)
+		JU_RGB_ENCODE(kRgbp10)
+		JU_RGB_ENCODE(kRgbp16)
+		JU_RGB_ENCODE(kRgbph)
+		JU_RGB_ENCODE(kRgbps)
+		JU_RGB_ENCODE(kBgr96f)
+	default: notSampled("state_to_rgb", format);
+	}
+#undef JU_RGB_ENCODE
+	hipCheckLaunch("state_to_rgb");
 }
 
 }  // namespace ju

@@ -1491,13 +1491,13 @@ void Engine::stageOut(const Frame &out) {
 }
 
 namespace {
-// Plane k of a YUV frame of the given luma size: rows, bytes per row (planar: Y, U, V; semi-planar: Y, UV; packed
-// YUY2 / UYVY: one plane of 2 bytes per pixel; the 10-bit formats: two bytes per sample)
+// Plane k of a frame of the given size: rows, bytes per row (planar: Y, U, V or R, G, B; semi-planar: Y, UV; packed: one
+// plane of pixelBytes per pixel -- YUY2 / UYVY 2, BGR24 3, RGBX 4, BGRX64 8, BGR96F 12; samples of 1, 2 or 4 bytes)
 struct PlaneShape {
 	std::size_t rows, rowBytes;
 };
-// A format = sampling (420 / 422 / 444) x storage (planar Y, U, V / semi-planar Y, UV / packed: one plane) x depth:
-// all of it from the one table, yuvFormatInfo (kernels.h)
+// A format = sampling (420 / 422 / 444; 0: RGB, every plane full size) x storage (planar / semi-planar Y, UV / packed: one
+// plane) x sample size: all of it from the one table, yuvFormatInfo (kernels.h)
 bool knownYuv(PixelFormat f) { return yuvFormatInfo(static_cast<int>(f)) != nullptr; }
 const YuvFormatInfo &infoOf(PixelFormat f) {
 	const YuvFormatInfo *info = yuvFormatInfo(static_cast<int>(f));
@@ -1505,14 +1505,16 @@ const YuvFormatInfo &infoOf(PixelFormat f) {
 	return *info;
 }
 int sampling(PixelFormat f) { return infoOf(f).sampling; }
+bool rgb(PixelFormat f) { return infoOf(f).sampling == 0; }
 bool packed(PixelFormat f) { return infoOf(f).planes == 1; }
 bool semiPlanar(PixelFormat f) { return infoOf(f).planes == 2; }
-bool tenBit(PixelFormat f) { return infoOf(f).bits == 10; }
-std::size_t bytesPerSample(PixelFormat f) { return tenBit(f) ? 2 : 1; }
+bool tenBit(PixelFormat f) { return infoOf(f).bits == 10 && infoOf(f).sampling != 0; }  // (10-bit YUV words; not RGBP10)
+bool deepFormat(PixelFormat f) { return infoOf(f).bits > 8; }  // (more than the 8-bit frame holds: encoded from the state)
+std::size_t bytesPerSample(PixelFormat f) { return static_cast<std::size_t>(infoOf(f).sampleBytes); }
 PlaneShape planeShape(PixelFormat f, std::size_t w, std::size_t h, int k) {
 	const std::size_t b = bytesPerSample(f);
-	if (packed(f)) return {h, 2 * w};
-	if (k == 0) return {h, w * b};
+	if (packed(f)) return {h, static_cast<std::size_t>(infoOf(f).pixelBytes) * w};
+	if (k == 0 || rgb(f)) return {h, w * b};
 	const int s = sampling(f);
 	const std::size_t cw = s == 444 ? w : w / 2;  // chroma samples per row (a semi-planar row holds both planes')
 	return {s == 420 ? h / 2 : h, (semiPlanar(f) ? 2 * cw : cw) * b};
@@ -1569,13 +1571,13 @@ void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream
 }
 }  // namespace
 
-// bytes of a staging buffer that holds any YUV frame of the size (the three full planes of I410 take the most: 6 bytes
-// per pixel and the row padding)
+// bytes of a staging buffer that holds a frame of the size in any format of the table (BGR96F and the three f32 planes
+// of RGBPS take the most: 12 bytes per pixel and the row padding)
 std::size_t Engine::yuvStageBytes(std::size_t w, std::size_t h) {
 	std::size_t most = 0;
-	for (PixelFormat f : {PixelFormat::I420, PixelFormat::Nv12, PixelFormat::P010, PixelFormat::I010, PixelFormat::Yuy2,
-	         PixelFormat::Uyvy, PixelFormat::I422, PixelFormat::P210, PixelFormat::I210, PixelFormat::I444,
-	         PixelFormat::I410}) {
+	for (int value = 1; value < kFormatValueEnd; ++value) {
+		if (yuvFormatInfo(value) == nullptr) continue;
+		const auto f = static_cast<PixelFormat>(value);
 		std::size_t n = 0;
 		for (int k = 0; k < planeCount(f); ++k) {
 			const PlaneShape p = planeShape(f, w, h, k);
@@ -1614,7 +1616,7 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 	}
 	const YuvFrame &y = f.planes;
 	if (!knownYuv(y.format)) throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
-	if (y.colorspace < 0 || y.colorspace > 3) {
+	if (!rgb(y.format) && (y.colorspace < 0 || y.colorspace > 3)) {  // (an RGB frame has none: the field is ignored)
 		throw std::invalid_argument("processFrame: unknown " + side + " colour space " + std::to_string(y.colorspace));
 	}
 	if (y.location != Location::Host && y.location != Location::Device) {
@@ -1636,10 +1638,13 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 		if (y.planes[k] == nullptr) {
 			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) + " is NULL");
 		}
-		if (tenBit(y.format) && (reinterpret_cast<std::uintptr_t>(y.planes[k]) % 2 != 0 || y.strides[k] % 2 != 0)) {
+		const std::size_t sample = bytesPerSample(y.format);
+		if (sample > 1 && (reinterpret_cast<std::uintptr_t>(y.planes[k]) % sample != 0 ||
+		                   y.strides[k] % static_cast<std::ptrdiff_t>(sample) != 0)) {
 			throw std::invalid_argument(std::string("processFrame: ") + side + " plane " + std::to_string(k) + ": " +
-			                            formatName(y.format) + " samples are 16-bit words -- the plane's address and its " +
-			                            "stride must be multiples of 2");
+			                            formatName(y.format) + " samples are " + (sample == 2 ? "16-bit" : "32-bit") +
+			                            " words -- the plane's address and its stride must be multiples of " +
+			                            std::to_string(sample));
 		}
 		const auto row = static_cast<std::ptrdiff_t>(planeShape(y.format, w, h, k).rowBytes);
 		if (y.strides[k] > -row && y.strides[k] < row) {
@@ -1662,7 +1667,9 @@ void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
     std::ptrdiff_t bgrxStride, std::size_t width, std::size_t height) {
 	const FrameSize fs = frameSize();
 	const int w = static_cast<int>(width ? width : fs.inputWidth), h = static_cast<int>(height ? height : fs.inputHeight);
-	if (sampling(format) != 420) {
+	if (rgb(format)) {
+		launchRgbToBgrx(static_cast<int>(format), planes, bgrx, bgrxStride, w, h, m_Stream);
+	} else if (sampling(format) != 420) {
 		launchYuvSampledToBgrx(static_cast<int>(format), planes,
 		    tenBit(format) ? yuvDecodeCoefficients10(colorspace) : yuvDecodeCoefficients(colorspace), bgrx, bgrxStride, w, h,
 		    m_Stream);
@@ -1675,14 +1682,21 @@ void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
 	}
 }
 
-// one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit format
-// of a runtime whose state is the frame in float (m_HbdFromState), the f16 state that frame left -- -> planes
+// one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit YUV or
+// a deep RGB format of a runtime whose state is the frame in float (m_HbdFromState), the f16 state that frame left -- -> planes
 void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, const std::uint8_t *bgrx,
     std::ptrdiff_t bgrxStride, const void *state) {
 	const FrameSize fs = frameSize();
 	const int w = static_cast<int>(fs.outputWidth), h = static_cast<int>(fs.outputHeight);
 	const bool fromState = m_HbdFromState && m_MaskW == 0;  // (a mask: the blended frame exists in 8 bits only)
-	if (sampling(format) != 420) {  // 4:2:2 / 4:4:4: the same three sources
+	if (rgb(format)) {  // 8-bit formats permute the frame's bytes; the deep ones take the state where it is the frame
+		const int f = static_cast<int>(format);
+		if (deepFormat(format) && fromState) {
+			launchStateToRgb(f, state, planes, w, h, m_Stream);
+		} else {
+			launchBgrxToRgb(f, bgrx, bgrxStride, planes, w, h, m_Stream);
+		}
+	} else if (sampling(format) != 420) {  // 4:2:2 / 4:4:4: the same three sources
 		const int f = static_cast<int>(format);
 		if (!tenBit(format)) {
 			launchBgrxToYuvSampled(f, bgrx, bgrxStride, yuvEncodeCoefficients(colorspace), planes, w, h, m_Stream);
@@ -2078,7 +2092,7 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		if (!pf.yuvIn) continue;
 		YuvDecodeItem &it = items.item[decodes++];
 		it.src = pf.decode;
-		it.k = tenBit(pf.formatIn) ? yuvDecodeCoefficients10(pf.csIn) : yuvDecodeCoefficients(pf.csIn);
+		if (!rgb(pf.formatIn)) it.k = tenBit(pf.formatIn) ? yuvDecodeCoefficients10(pf.csIn) : yuvDecodeCoefficients(pf.csIn);
 		it.dst = const_cast<std::uint8_t *>(m_BatchIO[i].in);
 		it.dstStride = m_BatchIO[i].inStride;
 		it.nv12 = pf.formatIn == PixelFormat::Nv12 ? 1 : 0;
@@ -2152,7 +2166,7 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 	// the planes a conversion launch addresses, and what of them the graph bakes in
 	auto bindPlanes = [](const YuvFrame &y, DeviceBuffer *stage, YuvKey *key) {
 		key->format = static_cast<int>(y.format);
-		key->colorspace = y.colorspace;
+		key->colorspace = rgb(y.format) ? 0 : y.colorspace;  // (ignored for RGB: no second graph for another value)
 		for (int k = 0; k < planeCount(y.format); ++k) {
 			key->planes[k] = stage ? nullptr : y.planes[k];
 			key->strides[k] = stage ? (y.strides[k] > 0 ? 1 : -1) : y.strides[k];

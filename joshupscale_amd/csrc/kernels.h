@@ -449,20 +449,32 @@ void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcSt
     const YuvPlanes &dst, int width, int height, hipStream_t stream);
 // 4:2:2 and 4:4:4 formats (colour_kernels.hip, "4:2:2 and 4:4:4"): the values of PixelFormat / JU_FMT_*.
 enum YuvSampled : int { kYuy2 = 16, kUyvy = 17, kI422 = 18, kP210 = 19, kI210 = 20, kI444 = 24, kI410 = 25 };
-// THE table of the YUV frame formats, by PixelFormat / JU_FMT_* value: the C API and the engine classify a format
-// through it alone.  planes: 3 planar (Y, U, V), 2 semi-planar (Y, UV), 1 packed (two bytes per pixel).
+// The RGB formats (colour_kernels.hip, "RGB formats"): the values of PixelFormat / JU_FMT_*.
+enum RgbFormat : int {
+	kBgr24 = 32, kRgb24 = 33, kRgbx = 34, kBgrx64 = 35, kRgbp8 = 36, kRgbp10 = 37, kRgbp16 = 38, kRgbph = 39, kRgbps = 40,
+	kBgr96f = 41
+};
+// THE table of the frame formats beside BGRX, by PixelFormat / JU_FMT_* value: the C API and the engine classify a
+// format through it alone.  planes: 3 planar (Y, U, V / R, G, B), 2 semi-planar (Y, UV), 1 packed (pixelBytes per pixel).
 struct YuvFormatInfo {
 	int value;
 	const char *name;
-	int sampling;  // 420, 422 or 444
+	int sampling;     // 420, 422 or 444; 0: an RGB format (no colour space, no chroma planes)
 	int planes;
-	int bits;      // 8, or 10 in 16-bit words
+	int bits;         // 8, or 10 in 16-bit words; RGB: 8, 10, 16 (words and f16) or 32 (f32)
+	int sampleBytes;  // 1, 2 or 4: what a plane's address and stride must be a multiple of
+	int pixelBytes;   // packed formats: bytes per pixel (2, 3, 4, 8 or 12); else 0
 };
-inline const YuvFormatInfo *yuvFormatInfo(int value) {  // nullptr: not a YUV format
+constexpr int kFormatValueEnd = 42;  // (one past the largest value of the table)
+inline const YuvFormatInfo *yuvFormatInfo(int value) {  // nullptr: not in the table
 	static constexpr YuvFormatInfo kTable[] = {
-	    {1, "I420", 420, 3, 8},      {2, "NV12", 420, 2, 8},      {3, "P010", 420, 2, 10},     {4, "I010", 420, 3, 10},
-	    {kYuy2, "YUY2", 422, 1, 8},  {kUyvy, "UYVY", 422, 1, 8},  {kI422, "I422", 422, 3, 8},  {kP210, "P210", 422, 2, 10},
-	    {kI210, "I210", 422, 3, 10}, {kI444, "I444", 444, 3, 8},  {kI410, "I410", 444, 3, 10}};
+	    {1, "I420", 420, 3, 8, 1, 0},        {2, "NV12", 420, 2, 8, 1, 0},        {3, "P010", 420, 2, 10, 2, 0},
+	    {4, "I010", 420, 3, 10, 2, 0},       {kYuy2, "YUY2", 422, 1, 8, 1, 2},    {kUyvy, "UYVY", 422, 1, 8, 1, 2},
+	    {kI422, "I422", 422, 3, 8, 1, 0},    {kP210, "P210", 422, 2, 10, 2, 0},   {kI210, "I210", 422, 3, 10, 2, 0},
+	    {kI444, "I444", 444, 3, 8, 1, 0},    {kI410, "I410", 444, 3, 10, 2, 0},   {kBgr24, "BGR24", 0, 1, 8, 1, 3},
+	    {kRgb24, "RGB24", 0, 1, 8, 1, 3},    {kRgbx, "RGBX", 0, 1, 8, 1, 4},      {kBgrx64, "BGRX64", 0, 1, 16, 2, 8},
+	    {kRgbp8, "RGBP8", 0, 3, 8, 1, 0},    {kRgbp10, "RGBP10", 0, 3, 10, 2, 0}, {kRgbp16, "RGBP16", 0, 3, 16, 2, 0},
+	    {kRgbph, "RGBPH", 0, 3, 16, 2, 0},   {kRgbps, "RGBPS", 0, 3, 32, 4, 0},   {kBgr96f, "BGR96F", 0, 1, 32, 4, 12}};
 	for (const YuvFormatInfo &f : kTable) {
 		if (f.value == value) return &f;
 	}
@@ -478,7 +490,8 @@ struct YuvDecodeItem {
 	std::ptrdiff_t dstStride = 0;
 	int nv12 = 0;
 	int deep = 0;  // 0: an 8-bit item (I420 / NV12 by `nv12`); 1: P010, 2: I010 (k = yuvDecodeCoefficients10)
-	int sampled = 0;  // 0: a 4:2:0 item, as above; else its YuvSampled value (the bytes of launchYuvSampledToBgrx)
+	int sampled = 0;  // 0: a 4:2:0 item, as above; else its YuvSampled value (the bytes of launchYuvSampledToBgrx) or its
+	                  // RgbFormat value (the bytes of launchRgbToBgrx; k is not read)
 };
 struct YuvDecodeItems {
 	YuvDecodeItem item[kFlowBatchMax];
@@ -517,6 +530,19 @@ void launchStateToYuvSampled10(int format, const void *state, const YuvEncode10 
     int height, hipStream_t stream);  // the 10-bit formats, P as launchStateToYuv420p10
 void launchBgrxToYuvSampled10(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
     const YuvPlanes &dst, int width, int height, hipStream_t stream);  // the 10-bit formats, P = 257 u8
+
+// ---- RGB formats (BGR24, RGB24, RGBX, BGRX64, planar RGBP8 / 10 / 16 / H / S, BGR96F) <-> BGRX ----------------------------
+// `format`: an RgbFormat value (std::invalid_argument for one the kernel does not take).  Planes as YuvPlanes: a packed
+// frame is plane y alone, rows of 3, 4, 8 or 12 x width bytes; a planar frame is y, u, v = R, G, B, rows of width samples.
+// Any width and height, signed strides; addresses and strides multiples of the sample size (1, 2 or 4 bytes).
+// tests/rgb_reference.py is the definition: inputs are reduced to the u8 frame the network consumes (rounded to nearest);
+// 8-bit outputs are a permutation of the frame's bytes, deep outputs come from the f16 state or from the u8 frame.
+void launchRgbToBgrx(int format, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride, int width, int height,
+    hipStream_t stream);
+void launchBgrxToRgb(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst, int width,
+    int height, hipStream_t stream);  // every format; deep ones: P = 257 u8, u8 / 255, u8
+void launchStateToRgb(int format, const void *state, const YuvPlanes &dst, int width, int height,
+    hipStream_t stream);  // the deep formats, from the dense f16 state as launchStateToYuv420p10 reads it
 
 // ---- source stage (source_kernels.hip; docs/source_stage.md): sources of any size, masked pass-through ---------------
 // One axis of the triangle scaler, N source samples -> M destination samples, in integers (buildScaleAxis is the

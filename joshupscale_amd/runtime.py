@@ -51,11 +51,20 @@ FMT_BGRX, FMT_I420, FMT_NV12, FMT_P010, FMT_I010 = 0, 1, 2, 3, 4
 FMT_YUY2, FMT_UYVY, FMT_I422, FMT_P210, FMT_I210, FMT_I444, FMT_I410 = 16, 17, 18, 19, 20, 24, 25
 _FMT_DEEP = (FMT_P010, FMT_I010, FMT_P210, FMT_I210, FMT_I410)
 _FMT_PACKED = (FMT_YUY2, FMT_UYVY)
+# RGB in other layouts and depths (tests/rgb_reference.py; `colorspace` is ignored).  Packed, ONE array: BGR24 / RGB24
+# [H, W, 3] uint8, RGBX [H, W, 4] uint8, BGRX64 [H, W, 4] uint16, BGR96F [H, W, 3] float32 (0..255).  Planar, three [H, W]
+# arrays R, G, B: RGBP8 uint8, RGBP10 / RGBP16 uint16, RGBPH float16, RGBPS float32 (0..1).
+(FMT_BGR24, FMT_RGB24, FMT_RGBX, FMT_BGRX64, FMT_RGBP8, FMT_RGBP10, FMT_RGBP16, FMT_RGBPH, FMT_RGBPS,
+ FMT_BGR96F) = range(32, 42)
+# format: (samples per packed pixel, or 0 for three planes; the planes' dtype)
+_FMT_RGB = {FMT_BGR24: (3, np.uint8), FMT_RGB24: (3, np.uint8), FMT_RGBX: (4, np.uint8), FMT_BGRX64: (4, np.uint16),
+            FMT_RGBP8: (0, np.uint8), FMT_RGBP10: (0, np.uint16), FMT_RGBP16: (0, np.uint16),
+            FMT_RGBPH: (0, np.float16), FMT_RGBPS: (0, np.float32), FMT_BGR96F: (3, np.float32)}
 CS_BT601_LIMITED, CS_BT601_FULL, CS_BT709_LIMITED, CS_BT709_FULL = 0, 1, 2, 3
 
 
 class JuFrame(C.Structure):
-    """``ju_frame``: a BGRX, I420 (YV12), NV12, P010 or I010 frame, host or device."""
+    """``ju_frame``: a BGRX, YUV (FMT_I420 .. FMT_I410) or RGB (FMT_BGR24 .. FMT_BGR96F) frame, host or device."""
     _fields_ = [("format", C.c_int), ("colorspace", C.c_int), ("location", C.c_uint8),
                 ("width", C.c_size_t), ("height", C.c_size_t),
                 ("planes", C.c_void_p * 3), ("strides", C.c_ssize_t * 3)]
@@ -152,6 +161,8 @@ _HOOK_SIGS = {
                                  _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_yuv_sampled": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                        _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_rgb": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t, _P(C.c_void_p),
+                               _P(C.c_ssize_t)]),
     "ju_debug_yuv_items": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_size_t, C.c_size_t, _P(C.c_void_p),
                                      _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_source": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
@@ -395,6 +406,24 @@ class Runtime:
         self.process_frame(inp, host_frame(out_format, res, colorspace))
         return res[0] if out_format == FMT_BGRX else tuple(res)
 
+    def process_rgb(self, planes, fmt: int, out_format: Optional[int] = None):
+        """Host planes of an RGB format in (``host_frame``'s arrays: ONE array for a packed format, ``[r, g, b]`` for a
+        planar one -- a single array may be passed bare), host planes out.  ``out_format`` (default: ``fmt``): an RGB
+        format or FMT_BGRX.  Returns the ``[4H, 4W, ...]`` array of a packed format (FMT_BGRX included), the tuple
+        ``(r, g, b)`` of a planar one."""
+        out_format = fmt if out_format is None else out_format
+        planes = [planes] if isinstance(planes, np.ndarray) else list(planes)
+        ow, oh = self.output_width, self.output_height
+        if out_format == FMT_BGRX:
+            res = [np.empty((oh, ow, 4), np.uint8)]
+        elif out_format in _FMT_RGB:
+            samples, dt = _FMT_RGB[out_format]
+            res = [np.empty((oh, ow, samples), dt)] if samples else [np.empty((oh, ow), dt) for _ in range(3)]
+        else:
+            raise ValueError("process_rgb: out_format must be FMT_BGRX or an RGB format")
+        self.process_frame(host_frame(fmt, planes), host_frame(out_format, res))
+        return res[0] if len(res) == 1 else tuple(res)
+
     def device_image(self, ptr: int, width: int, height: int,
                      stride: Optional[int] = None) -> JuImage:
         return JuImage(ptr, LOC_DEVICE, width * 4 if stride is None else stride,
@@ -539,9 +568,27 @@ def host_frame(fmt: int, planes, colorspace: int = CS_BT709_LIMITED) -> JuFrame:
     """Describe numpy planes as a host frame.  FMT_BGRX: ``[bgrx [H, W, 4]]``; FMT_I420: ``[y [H, W], u, v
     [H/2, W/2]]``; FMT_NV12: ``[y [H, W], uv [H/2, W]]``; FMT_I010 / FMT_P010: the same shapes as ``uint16``.
     FMT_YUY2 / FMT_UYVY: ONE ``[H, 2W]`` uint8 array; FMT_I422 / FMT_I210: ``[y [H, W], u, v [H, W/2]]``; FMT_P210:
-    ``[y [H, W], uv [H, W]]``; FMT_I444 / FMT_I410: ``[y, u, v [H, W]]`` (the 10-bit formats ``uint16``).  Any
+    ``[y [H, W], uv [H, W]]``; FMT_I444 / FMT_I410: ``[y, u, v [H, W]]`` (the 10-bit formats ``uint16``).
+    The RGB formats: FMT_BGR24 / FMT_RGB24 ONE ``[H, W, 3]`` uint8 array, FMT_RGBX ``[H, W, 4]`` uint8, FMT_BGRX64
+    ``[H, W, 4]`` uint16, FMT_BGR96F ``[H, W, 3]`` float32; FMT_RGBP8 / FMT_RGBP10 / FMT_RGBP16 / FMT_RGBPH / FMT_RGBPS
+    three ``[H, W]`` arrays ``[r, g, b]`` of uint8 / uint16 / uint16 / float16 / float32 (``colorspace`` is ignored).  Any
     row stride (a ``[::-1]`` view is bottom-up; the frame's strides are the arrays' byte strides); the columns must be
     contiguous.  The arrays must outlive the call."""
+    if fmt in _FMT_RGB:
+        samples, dt = _FMT_RGB[fmt]
+        planes = list(planes)
+        if len(planes) != (1 if samples else 3):
+            raise ValueError("a packed RGB frame is one array, a planar one three arrays [r, g, b]")
+        y = planes[0]
+        for p in planes:
+            if p.dtype != np.dtype(dt):
+                raise ValueError(f"planes of this format must be {np.dtype(dt).name}")
+            if p.shape != y.shape or p.ndim != (3 if samples else 2) or (samples and p.shape[2] != samples):
+                raise ValueError("a packed RGB frame is [H, W, samples], a planar one three equal [H, W] arrays")
+            if p.strides[1] != p.itemsize * max(samples, 1) or (samples and p.strides[2] != p.itemsize):
+                raise ValueError("planes need contiguous columns")
+        return _frame(fmt, colorspace, LOC_CPU, y.shape[1], y.shape[0], [p.ctypes.data for p in planes],
+                      [p.strides[0] for p in planes])
     deep = fmt in _FMT_DEEP
     for p in planes:
         if p.dtype != (np.uint16 if deep else np.uint8) or p.strides[1] != (4 if fmt == FMT_BGRX else (2 if deep else 1)):
@@ -558,8 +605,11 @@ def device_frame(fmt: int, width: int, height: int, ptrs, strides=None,
                  colorspace: int = CS_BT709_LIMITED) -> JuFrame:
     """A device frame from raw device pointers (or torch tensors: their ``data_ptr()``); ``strides`` default to
     dense rows in bytes (BGRX 4W, Y W, I420 / I422 chroma W/2, NV12 chroma W, I444 chroma W, YUY2 / UYVY 2W; the 10-bit
-    formats twice that)."""
+    formats twice that; RGB: W x the bytes of a packed pixel, or of a planar sample)."""
     ptrs = [p.data_ptr() if hasattr(p, "data_ptr") else int(p) for p in ptrs]
+    if strides is None and fmt in _FMT_RGB:
+        samples, dt = _FMT_RGB[fmt]
+        strides = [width * np.dtype(dt).itemsize * max(samples, 1)] * (1 if samples else 3)
     if strides is None:
         strides = {FMT_BGRX: [4 * width], FMT_I420: [width, width // 2, width // 2],
                    FMT_NV12: [width, width], FMT_P010: [2 * width, 2 * width],

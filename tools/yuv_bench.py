@@ -1,5 +1,5 @@
-"""Per-call frames/s of ju_process_frame on BGRX, NV12, I420, P010, YUY2, I444 and P210 frames, host and device,
-psp-quality at 480x270.
+"""Per-call frames/s of ju_process_frame on BGRX, NV12, I420, P010, YUY2, I444, P210, BGR24, RGBP16, RGBPS and BGR96F
+frames, host and device, psp-quality at 480x270.
 
 Every variant goes through the same runtime in turn (interleaved rounds of --frames-per-round frames), each call
 synchronous (ju_process_frame / ju_process), so that the clock and the other work on the machine are shared alike.
@@ -8,7 +8,7 @@ through ju_debug_yuv, for a `rocprofv3 --kernel-trace --stats` run (the test fla
 the same run the three 10-bit kernels (ju_debug_yuv10: decode, encode from a u8 frame, encode from an f16 tensor; P010
 and I010) at that size plus their decode at --small-size (default 480x270, the LR frame of the flagship workload), and
 the 4:2:2 / 4:4:4 kernels (ju_debug_yuv_sampled: every format's decode and encodes at that size, its decode at
---small-size).
+--small-size), and the RGB kernels alike (ju_debug_rgb: all ten formats).
 
 --passes N adds the look-ahead variants, N frames per call: nv12_host_pass, i420_host_pass, nv12_device_pass
 (ju_process_frames), p010_*_pass, yuy2_*_pass, i444_*_pass, p210_*_pass alike, and bgrx_host_pass, bgrx_device_pass (ju_process_batch), interleaved with the per-call variants in
@@ -36,15 +36,19 @@ from joshupscale_amd import runtime as R  # noqa: E402
 import yuv_reference as Y  # noqa: E402
 import yuv10_reference as T  # noqa: E402
 import yuv_sampled_reference as S  # noqa: E402
+import rgb_reference as G  # noqa: E402
 
 FORMATS = {"bgrx": R.FMT_BGRX, "nv12": R.FMT_NV12, "i420": R.FMT_I420, "p010": R.FMT_P010, "yuy2": R.FMT_YUY2,
-           "i444": R.FMT_I444, "p210": R.FMT_P210}
+           "i444": R.FMT_I444, "p210": R.FMT_P210, "bgr24": R.FMT_BGR24, "rgbp16": R.FMT_RGBP16, "rgbps": R.FMT_RGBPS,
+           "bgr96f": R.FMT_BGR96F}
 TEN = (R.FMT_P010, R.FMT_I010)
 
 
 def planes_for(fmt, h, w, bgrx, cs):
     if fmt == R.FMT_BGRX:
         return [bgrx]
+    if fmt in G.NEW_FORMATS:
+        return G.encode_planes(fmt, frame=bgrx)
     if fmt in S.NEW_FORMATS:
         return S.encode_planes(fmt, cs, frame=bgrx)
     if fmt in TEN:
@@ -56,6 +60,8 @@ def planes_for(fmt, h, w, bgrx, cs):
 def empty_planes(fmt, h, w):
     if fmt == R.FMT_BGRX:
         return [np.zeros((h, w, 4), np.uint8)]
+    if fmt in G.NEW_FORMATS:
+        return G.blank_planes(fmt, h, w)
     if fmt in S.NEW_FORMATS:
         return S.blank_planes(fmt, h, w)
     dt = np.uint16 if fmt in TEN else np.uint8
@@ -231,7 +237,25 @@ def kernel_bench(args):
                     if rc != 0:
                         raise RuntimeError(lib.ju_last_error().decode())
                 res[f"{name}_{what}_ms_per_call"] = round((time.perf_counter() - t0) * 1e3 / args.iters, 4)
-    print(json.dumps({"metric": "ju_debug_yuv / ju_debug_yuv10 / ju_debug_yuv_sampled host time per synchronous call (kernel time: the trace)",
+    # the RGB kernels in the same run: every format's encode from a u8 frame, the deep formats' encode from an f16 tensor,
+    # the decode at both sizes
+    for fmt in G.NEW_FORMATS:
+        name, deep = G.FORMAT_NAMES[fmt], fmt in G.DEEP
+        full_ops = ((1, "encode8", bgrx, 4 * w),) + (((2, "encode_state", state, 0),) if deep else ()) + ((0, "decode", out, 4 * w),)
+        for (pw, ph), ops in (((w, h), full_ops), ((sw, sh), ((0, "decode_small", small_out, 4 * sw),))):
+            held = G.encode_planes(fmt, frame=rng.integers(0, 256, (ph, pw, 4), dtype=np.uint8))
+            planes = [to_device(p, dev) for p in held]
+            ptrs = (C.c_void_p * 3)(*([p.data_ptr() for p in planes] + [None] * (3 - len(planes))))
+            strides = (C.c_ssize_t * 3)(*([p.nbytes // p.shape[0] for p in held] + [0] * (3 - len(planes))))
+            torch.cuda.synchronize()
+            for op, what, image, image_stride in ops:
+                t0 = time.perf_counter()
+                for _ in range(args.iters):
+                    rc = lib.ju_debug_rgb(op, fmt, pw, ph, image.data_ptr(), image_stride, ptrs, strides)
+                    if rc != 0:
+                        raise RuntimeError(lib.ju_last_error().decode())
+                res[f"{name}_{what}_ms_per_call"] = round((time.perf_counter() - t0) * 1e3 / args.iters, 4)
+    print(json.dumps({"metric": "ju_debug_yuv / ju_debug_yuv10 / ju_debug_yuv_sampled / ju_debug_rgb host time per synchronous call (kernel time: the trace)",
                       "size": f"{w}x{h}", "small_size": f"{sw}x{sh}", "iters": args.iters, **res}))
 
 
