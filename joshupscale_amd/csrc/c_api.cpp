@@ -75,27 +75,6 @@ ju::Frame toFrame(const ju_image *img) {
 	    img->height};
 }
 
-// A JU_FMT_* value through the one table of the formats beside BGRX (kernels.h): its planes (0: not in the table), whether
-// its samples are 10-bit YUV words, whether it is one of the 4:2:2 / 4:4:4 formats or an RGB format, its sample size
-int planesOfFormat(int format) {
-	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
-	return info ? info->planes : 0;
-}
-[[maybe_unused]] bool wordsOfFormat(int format) {
-	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
-	return info && info->bits == 10 && info->sampling != 0;  // (10-bit YUV words; not RGBP10)
-}
-[[maybe_unused]] int samplingOfFormat(int format) {
-	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
-	return info ? info->sampling : 0;
-}
-[[maybe_unused]] bool sampledFormat(int format) { return samplingOfFormat(format) == 422 || samplingOfFormat(format) == 444; }
-[[maybe_unused]] bool rgbFormat(int format) { return planesOfFormat(format) != 0 && samplingOfFormat(format) == 0; }
-[[maybe_unused]] int sampleBytesOfFormat(int format) {
-	const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
-	return info ? info->sampleBytes : 1;
-}
-
 // A ju_frame as the engine's AnyFrame; BGRX frames exactly as toFrame makes them of a ju_image
 ju::AnyFrame toAnyFrame(const ju_frame *f) {
 	if (f == nullptr) throw std::invalid_argument("frame is NULL");
@@ -105,7 +84,7 @@ ju::AnyFrame toAnyFrame(const ju_frame *f) {
 		a.bgrx = toFrame(&img);
 		return a;
 	}
-	if (planesOfFormat(f->format) == 0) throw std::invalid_argument("frame has an unknown format " + std::to_string(f->format));
+	if (ju::yuvFormatInfo(f->format) == nullptr) throw std::invalid_argument("frame has an unknown format " + std::to_string(f->format));
 	if (f->location > JU_LOC_GRAPHICS_RESOURCE) throw std::invalid_argument("frame has an unknown location");
 	a.yuv = true;
 	a.planes.format = static_cast<ju::PixelFormat>(f->format);
@@ -444,227 +423,114 @@ int ju_debug_set(const char *key, int value) {
 	});
 }
 
+namespace {
+// What the single-kernel conversion hooks and ju_debug_yuv_items share.  A hook = its name, the formats of the table it
+// admits (`family`: how its refusal of another calls them) and its ops: 0 decode planes -> BGRX `image`, 1 encode the BGRX
+// `image` -> planes and, where ops == 3, 2 encode the dense f16 tensor `image` -> planes, the deep formats only.
+struct ConversionHook {
+	const char *name, *family;
+	bool (*admits)(const ju::YuvFormatInfo &);
+	int ops;
+	bool rowStrides;  // refuse strides smaller than a row
+	[[noreturn]] void refuse(const std::string &why) const { throw std::invalid_argument(std::string(name) + ": " + why); }
+
+	const ju::YuvFormatInfo &format(int value) const {
+		const ju::YuvFormatInfo *info = ju::yuvFormatInfo(value);
+		if (info == nullptr || !admits(*info)) refuse(std::string("not ") + family + " format");
+		return *info;
+	}
+	// Everything a hook refuses about one frame before a launch, in the order size, null, alignment; then its planes
+	ju::YuvPlanes planes(const ju::YuvFormatInfo &info, int op, size_t width, size_t height, const void *image,
+	    ptrdiff_t image_stride, void *const *planes, const ptrdiff_t *strides) const {
+		if (op == 2 && !info.deep()) refuse("op 2 takes the deep formats only (10-bit YUV; RGB of more than 8 bits)");
+		if (width == 0 || height == 0 || width > (1u << 15) || height > (1u << 15) ||
+		    (info.sampling == 420 && height % 2) || ((info.sampling == 420 || info.sampling == 422) && width % 2)) {
+			refuse("sizes 1 .. 32768, an even width for 4:2:0 and 4:2:2, an even height for 4:2:0");
+		}
+		if (image == nullptr || planes == nullptr || strides == nullptr) refuse("null buffer");
+		const auto row = static_cast<ptrdiff_t>((info.planes == 1 ? info.pixelBytes : info.sampleBytes) * width);
+		for (int k = 0; k < info.planes; ++k) {
+			if (planes[k] == nullptr) refuse("null buffer");
+			if (reinterpret_cast<std::uintptr_t>(planes[k]) % info.sampleBytes || strides[k] % info.sampleBytes) {
+				refuse(info.sampleBytes == 2 ? "16-bit planes need even addresses and strides"
+				                             : "32-bit planes need addresses and strides that are multiples of 4");
+			}
+			if (rowStrides && strides[k] > -row && strides[k] < row) refuse("|stride| smaller than a row");
+		}
+		const auto imageRow = static_cast<ptrdiff_t>(4 * width);
+		if (rowStrides && op != 2 && image_stride > -imageRow && image_stride < imageRow) {
+			refuse("|image_stride| smaller than a row");
+		}
+		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) refuse("the f16 tensor must be 16-byte aligned");
+		ju::YuvPlanes p;
+		std::uint8_t **plane[3] = {&p.y, &p.u, &p.v};
+		std::ptrdiff_t *stride[3] = {&p.yStride, &p.uStride, &p.vStride};
+		for (int k = 0; k < info.planes; ++k) {
+			*plane[k] = static_cast<std::uint8_t *>(planes[k]);
+			*stride[k] = strides[k];
+		}
+		return p;
+	}
+	int run(int op, int format, int colorspace, size_t width, size_t height, void *image, ptrdiff_t image_stride,
+	    void *const *planes, const ptrdiff_t *strides) const {
+		return guarded([&] {
+			if (op < 0 || op >= ops) refuse(ops == 2 ? "direction must be 0 or 1" : "op must be 0, 1 or 2");
+			const ju::YuvPlanes p = this->planes(this->format(format), op, width, height, image, image_stride, planes, strides);
+			const int w = static_cast<int>(width), h = static_cast<int>(height);
+			if (op == 0) {
+				ju::launchDecodeFrame(format, colorspace, p, static_cast<std::uint8_t *>(image), image_stride, w, h, nullptr);
+			} else if (op == 1) {
+				ju::launchEncodeFrame(format, colorspace, static_cast<const std::uint8_t *>(image), image_stride, p, w, h, nullptr);
+			} else {
+				ju::launchEncodeState(format, colorspace, image, p, w, h, nullptr);
+			}
+			JU_HIP(hipStreamSynchronize(nullptr));
+		});
+	}
+};
+using Info = const ju::YuvFormatInfo &;
+const ConversionHook kDebugYuv{"ju_debug_yuv", "a YUV", [](Info f) { return f.sampling == 420 && !f.deep(); }, 2, false};
+const ConversionHook kDebugYuv10{"ju_debug_yuv10", "a 10-bit", [](Info f) { return f.sampling == 420 && f.deep(); }, 3, false};
+const ConversionHook kDebugYuvSampled{"ju_debug_yuv_sampled", "a 4:2:2 / 4:4:4",
+    [](Info f) { return f.sampling == 422 || f.sampling == 444; }, 3, false};
+const ConversionHook kDebugRgb{"ju_debug_rgb", "an RGB", [](Info f) { return f.rgb(); }, 3, true};
+const ConversionHook kDebugYuvItems{"ju_debug_yuv_items", "a YUV", [](Info) { return true; }, 1, false};
+}  // namespace
+
 int ju_debug_yuv(int direction, int format, int colorspace, size_t width, size_t height, void *bgrx,
     ptrdiff_t bgrx_stride, void *const planes[3], const ptrdiff_t strides[3]) {
-	return guarded([&] {
-		if (direction != 0 && direction != 1) throw std::invalid_argument("ju_debug_yuv: direction must be 0 or 1");
-		if (format != JU_FMT_I420 && format != JU_FMT_NV12) throw std::invalid_argument("ju_debug_yuv: not a YUV format");
-		if (width == 0 || height == 0 || width % 2 || height % 2 || width > (1u << 15) || height > (1u << 15)) {
-			throw std::invalid_argument("ju_debug_yuv: width and height must be even, 2 .. 32768");
-		}
-		if (bgrx == nullptr || planes == nullptr || strides == nullptr || planes[0] == nullptr || planes[1] == nullptr ||
-		    (format == JU_FMT_I420 && planes[2] == nullptr)) {
-			throw std::invalid_argument("ju_debug_yuv: null buffer");
-		}
-		ju::YuvPlanes p;
-		p.y = static_cast<std::uint8_t *>(planes[0]);
-		p.u = static_cast<std::uint8_t *>(planes[1]);
-		p.v = format == JU_FMT_I420 ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
-		p.yStride = strides[0];
-		p.uStride = strides[1];
-		p.vStride = format == JU_FMT_I420 ? strides[2] : 0;
-		const bool nv12 = format == JU_FMT_NV12;
-		const int w = static_cast<int>(width), h = static_cast<int>(height);
-		if (direction == 0) {
-			ju::launchYuv420ToBgrx(nv12, p, ju::yuvDecodeCoefficients(colorspace), static_cast<std::uint8_t *>(bgrx),
-			    bgrx_stride, w, h, nullptr);
-		} else {
-			ju::launchBgrxToYuv420(nv12, static_cast<const std::uint8_t *>(bgrx), bgrx_stride,
-			    ju::yuvEncodeCoefficients(colorspace), p, w, h, nullptr);
-		}
-		JU_HIP(hipStreamSynchronize(nullptr));
-	});
+	return kDebugYuv.run(direction, format, colorspace, width, height, bgrx, bgrx_stride, planes, strides);
+}
+
+int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size_t height, void *image, ptrdiff_t image_stride,
+    void *const planes[3], const ptrdiff_t strides[3]) {
+	return kDebugYuv10.run(op, format, colorspace, width, height, image, image_stride, planes, strides);
+}
+
+int ju_debug_yuv_sampled(int op, int format, int colorspace, size_t width, size_t height, void *image,
+    ptrdiff_t image_stride, void *const planes[3], const ptrdiff_t strides[3]) {
+	return kDebugYuvSampled.run(op, format, colorspace, width, height, image, image_stride, planes, strides);
+}
+
+int ju_debug_rgb(int op, int format, size_t width, size_t height, void *image, ptrdiff_t image_stride,
+    void *const planes[3], const ptrdiff_t strides[3]) {
+	return kDebugRgb.run(op, format, 0, width, height, image, image_stride, planes, strides);
 }
 
 int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, size_t width, size_t height,
     void *const *bgrx, const ptrdiff_t *bgrx_strides, void *const *planes, const ptrdiff_t *strides) {
 	return guarded([&] {
-		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_yuv_items: 1 .. 8 items");
-		if (!formats || !colorspaces || !bgrx || !bgrx_strides || !planes || !strides) {
-			throw std::invalid_argument("ju_debug_yuv_items: null argument");
-		}
-		// (4:2:0 items need an even size, 4:2:2 items an even width, 4:4:4 items neither)
-		bool needEvenWidth = false, needEvenHeight = false;
-		for (int i = 0; i < count; ++i) {
-			if (planesOfFormat(formats[i]) == 0) throw std::invalid_argument("ju_debug_yuv_items: not a YUV format");
-			if (rgbFormat(formats[i])) continue;  // (any size)
-			if (samplingOfFormat(formats[i]) != 444) needEvenWidth = true;
-			if (samplingOfFormat(formats[i]) == 420) needEvenHeight = true;
-		}
-		if (width == 0 || height == 0 || width > (1u << 15) || height > (1u << 15)) {
-			throw std::invalid_argument("ju_debug_yuv_items: width and height must be 1 .. 32768");
-		}
-		if ((needEvenWidth && width % 2) || (needEvenHeight && height % 2)) {
-			throw std::invalid_argument("ju_debug_yuv_items: 4:2:0 items need an even width and height, 4:2:2 items an even width");
-		}
+		const ConversionHook &hook = kDebugYuvItems;
+		if (count < 1 || count > ju::kFlowBatchMax) hook.refuse("1 .. 8 items");
+		if (!formats || !colorspaces || !bgrx || !bgrx_strides || !planes || !strides) hook.refuse("null argument");
+		for (int i = 0; i < count; ++i) hook.format(formats[i]);  // (every format before any buffer)
 		ju::YuvDecodeItems items{};
 		for (int i = 0; i < count; ++i) {
-			const int f = formats[i];
-			const int count_k = planesOfFormat(f);
-			const bool planar = count_k == 3, deep = wordsOfFormat(f);
-			void *const *p = planes + 3 * i;
-			if (bgrx[i] == nullptr || p[0] == nullptr || (count_k > 1 && p[1] == nullptr) || (planar && p[2] == nullptr)) {
-				throw std::invalid_argument("ju_debug_yuv_items: null buffer");
-			}
-			const int sample = sampleBytesOfFormat(f);
-			for (int k = 0; sample > 1 && k < count_k; ++k) {
-				if (reinterpret_cast<std::uintptr_t>(p[k]) % sample || strides[3 * i + k] % sample) {
-					throw std::invalid_argument(sample == 2 ? "ju_debug_yuv_items: 16-bit planes need even addresses and strides"
-					                                        : "ju_debug_yuv_items: 32-bit planes need addresses and strides that are multiples of 4");
-				}
-			}
-			ju::YuvDecodeItem &it = items.item[i];
-			it.src.y = static_cast<std::uint8_t *>(p[0]);
-			it.src.u = count_k > 1 ? static_cast<std::uint8_t *>(p[1]) : nullptr;
-			it.src.v = planar ? static_cast<std::uint8_t *>(p[2]) : nullptr;
-			it.src.yStride = strides[3 * i];
-			it.src.uStride = count_k > 1 ? strides[3 * i + 1] : 0;
-			it.src.vStride = planar ? strides[3 * i + 2] : 0;
-			if (!rgbFormat(f)) it.k = deep ? ju::yuvDecodeCoefficients10(colorspaces[i]) : ju::yuvDecodeCoefficients(colorspaces[i]);
-			it.deep = f == JU_FMT_P010 ? 1 : (f == JU_FMT_I010 ? 2 : 0);
-			it.sampled = sampledFormat(f) || rgbFormat(f) ? f : 0;
-			it.dst = static_cast<std::uint8_t *>(bgrx[i]);
-			it.dstStride = bgrx_strides[i];
-			it.nv12 = f == JU_FMT_NV12 ? 1 : 0;
+			const ju::YuvPlanes p = hook.planes(hook.format(formats[i]), 0, width, height, bgrx[i], bgrx_strides[i],
+			    planes + 3 * i, strides + 3 * i);
+			items.item[i] = ju::yuvDecodeItem(formats[i], colorspaces[i], p, static_cast<std::uint8_t *>(bgrx[i]), bgrx_strides[i]);
 		}
 		ju::launchYuv420ToBgrxItems(items, count, static_cast<int>(width), static_cast<int>(height), nullptr);
-		JU_HIP(hipStreamSynchronize(nullptr));
-	});
-}
-
-int ju_debug_yuv10(int op, int format, int colorspace, size_t width, size_t height, void *image, ptrdiff_t image_stride,
-    void *const planes[3], const ptrdiff_t strides[3]) {
-	return guarded([&] {
-		if (op < 0 || op > 2) throw std::invalid_argument("ju_debug_yuv10: op must be 0, 1 or 2");
-		if (format != JU_FMT_P010 && format != JU_FMT_I010) throw std::invalid_argument("ju_debug_yuv10: not a 10-bit format");
-		if (width == 0 || height == 0 || width % 2 || height % 2 || width > (1u << 15) || height > (1u << 15)) {
-			throw std::invalid_argument("ju_debug_yuv10: width and height must be even, 2 .. 32768");
-		}
-		const bool planar = format == JU_FMT_I010;
-		if (image == nullptr || planes == nullptr || strides == nullptr || planes[0] == nullptr || planes[1] == nullptr ||
-		    (planar && planes[2] == nullptr)) {
-			throw std::invalid_argument("ju_debug_yuv10: null buffer");
-		}
-		for (int k = 0; k < (planar ? 3 : 2); ++k) {
-			if (reinterpret_cast<std::uintptr_t>(planes[k]) % 2 || strides[k] % 2) {
-				throw std::invalid_argument("ju_debug_yuv10: 16-bit planes need even addresses and strides");
-			}
-		}
-		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) {
-			throw std::invalid_argument("ju_debug_yuv10: the f16 tensor must be 16-byte aligned");
-		}
-		ju::YuvPlanes p;
-		p.y = static_cast<std::uint8_t *>(planes[0]);
-		p.u = static_cast<std::uint8_t *>(planes[1]);
-		p.v = planar ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
-		p.yStride = strides[0];
-		p.uStride = strides[1];
-		p.vStride = planar ? strides[2] : 0;
-		const bool p010 = format == JU_FMT_P010;
-		const int w = static_cast<int>(width), h = static_cast<int>(height);
-		if (op == 0) {
-			ju::launchYuv420p10ToBgrx(p010, p, ju::yuvDecodeCoefficients10(colorspace), static_cast<std::uint8_t *>(image),
-			    image_stride, w, h, nullptr);
-		} else if (op == 1) {
-			ju::launchBgrxToYuv420p10(p010, static_cast<const std::uint8_t *>(image), image_stride,
-			    ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
-		} else {
-			ju::launchStateToYuv420p10(p010, image, ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
-		}
-		JU_HIP(hipStreamSynchronize(nullptr));
-	});
-}
-
-int ju_debug_yuv_sampled(int op, int format, int colorspace, size_t width, size_t height, void *image,
-    ptrdiff_t image_stride, void *const planes[3], const ptrdiff_t strides[3]) {
-	return guarded([&] {
-		if (op < 0 || op > 2) throw std::invalid_argument("ju_debug_yuv_sampled: op must be 0, 1 or 2");
-		if (!sampledFormat(format)) throw std::invalid_argument("ju_debug_yuv_sampled: not a 4:2:2 / 4:4:4 format");
-		const bool full = samplingOfFormat(format) == 444, deep = wordsOfFormat(format);
-		if (op == 2 && !deep) throw std::invalid_argument("ju_debug_yuv_sampled: op 2 takes the 10-bit formats only");
-		if (width == 0 || height == 0 || (!full && width % 2) || width > (1u << 15) || height > (1u << 15)) {
-			throw std::invalid_argument("ju_debug_yuv_sampled: sizes 1 .. 32768, an even width for 4:2:2");
-		}
-		const int count = planesOfFormat(format);
-		if (image == nullptr || planes == nullptr || strides == nullptr) {
-			throw std::invalid_argument("ju_debug_yuv_sampled: null buffer");
-		}
-		for (int k = 0; k < count; ++k) {
-			if (planes[k] == nullptr) throw std::invalid_argument("ju_debug_yuv_sampled: null buffer");
-			if (deep && (reinterpret_cast<std::uintptr_t>(planes[k]) % 2 || strides[k] % 2)) {
-				throw std::invalid_argument("ju_debug_yuv_sampled: 16-bit planes need even addresses and strides");
-			}
-		}
-		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) {
-			throw std::invalid_argument("ju_debug_yuv_sampled: the f16 tensor must be 16-byte aligned");
-		}
-		ju::YuvPlanes p;
-		p.y = static_cast<std::uint8_t *>(planes[0]);
-		p.u = count > 1 ? static_cast<std::uint8_t *>(planes[1]) : nullptr;
-		p.v = count > 2 ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
-		p.yStride = strides[0];
-		p.uStride = count > 1 ? strides[1] : 0;
-		p.vStride = count > 2 ? strides[2] : 0;
-		const int w = static_cast<int>(width), h = static_cast<int>(height);
-		if (op == 0) {
-			ju::launchYuvSampledToBgrx(format, p,
-			    deep ? ju::yuvDecodeCoefficients10(colorspace) : ju::yuvDecodeCoefficients(colorspace),
-			    static_cast<std::uint8_t *>(image), image_stride, w, h, nullptr);
-		} else if (op == 2) {
-			ju::launchStateToYuvSampled10(format, image, ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
-		} else if (deep) {
-			ju::launchBgrxToYuvSampled10(format, static_cast<const std::uint8_t *>(image), image_stride,
-			    ju::yuvEncodeCoefficients10(colorspace), p, w, h, nullptr);
-		} else {
-			ju::launchBgrxToYuvSampled(format, static_cast<const std::uint8_t *>(image), image_stride,
-			    ju::yuvEncodeCoefficients(colorspace), p, w, h, nullptr);
-		}
-		JU_HIP(hipStreamSynchronize(nullptr));
-	});
-}
-
-int ju_debug_rgb(int op, int format, size_t width, size_t height, void *image, ptrdiff_t image_stride,
-    void *const planes[3], const ptrdiff_t strides[3]) {
-	return guarded([&] {
-		if (op < 0 || op > 2) throw std::invalid_argument("ju_debug_rgb: op must be 0, 1 or 2");
-		if (!rgbFormat(format)) throw std::invalid_argument("ju_debug_rgb: not an RGB format");
-		const ju::YuvFormatInfo &info = *ju::yuvFormatInfo(format);
-		if (op == 2 && info.bits == 8) throw std::invalid_argument("ju_debug_rgb: op 2 takes the deep formats only");
-		if (width == 0 || height == 0 || width > (1u << 15) || height > (1u << 15)) {
-			throw std::invalid_argument("ju_debug_rgb: sizes 1 .. 32768");
-		}
-		if (image == nullptr || planes == nullptr || strides == nullptr) {
-			throw std::invalid_argument("ju_debug_rgb: null buffer");
-		}
-		const auto row = static_cast<ptrdiff_t>((info.planes == 1 ? info.pixelBytes : info.sampleBytes) * width);
-		for (int k = 0; k < info.planes; ++k) {
-			if (planes[k] == nullptr) throw std::invalid_argument("ju_debug_rgb: null buffer");
-			if (reinterpret_cast<std::uintptr_t>(planes[k]) % info.sampleBytes || strides[k] % info.sampleBytes) {
-				throw std::invalid_argument("ju_debug_rgb: plane addresses and strides must be multiples of the sample size");
-			}
-			if (strides[k] > -row && strides[k] < row) throw std::invalid_argument("ju_debug_rgb: |stride| smaller than a row");
-		}
-		if (op != 2 && image_stride > -static_cast<ptrdiff_t>(4 * width) && image_stride < static_cast<ptrdiff_t>(4 * width)) {
-			throw std::invalid_argument("ju_debug_rgb: |image_stride| smaller than a row");
-		}
-		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) {
-			throw std::invalid_argument("ju_debug_rgb: the f16 tensor must be 16-byte aligned");
-		}
-		ju::YuvPlanes p;
-		p.y = static_cast<std::uint8_t *>(planes[0]);
-		p.u = info.planes > 1 ? static_cast<std::uint8_t *>(planes[1]) : nullptr;
-		p.v = info.planes > 2 ? static_cast<std::uint8_t *>(planes[2]) : nullptr;
-		p.yStride = strides[0];
-		p.uStride = info.planes > 1 ? strides[1] : 0;
-		p.vStride = info.planes > 2 ? strides[2] : 0;
-		const int w = static_cast<int>(width), h = static_cast<int>(height);
-		if (op == 0) {
-			ju::launchRgbToBgrx(format, p, static_cast<std::uint8_t *>(image), image_stride, w, h, nullptr);
-		} else if (op == 1) {
-			ju::launchBgrxToRgb(format, static_cast<const std::uint8_t *>(image), image_stride, p, w, h, nullptr);
-		} else {
-			ju::launchStateToRgb(format, image, p, w, h, nullptr);
-		}
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

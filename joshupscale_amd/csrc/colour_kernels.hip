@@ -13,11 +13,21 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "kernel_common.h"
 #include "kernels.h"
 
 namespace ju {
+// Encode coefficients (kernel arguments).  8-bit: x 65536, rounded half away from zero (tests/yuv_reference.py).  10-bit
+// (tests/yuv10_reference.py): x 2^32 / 65535, applied to a 16-bit sample P per channel (each below 2^26; products summed in
+// 64 bits).  oy = luma offset (16 / 64 limited, 0 full range).
+struct YuvEncode {
+	int yr, yg, yb, ur, ug, ub, vr, vg, vb, oy;
+};
+struct YuvEncode10 {
+	int yr, yg, yb, ur, ug, ub, vr, vg, vb, oy;
+};
 namespace {
 
 constexpr int kStrip = 16;  // luma pixels per thread and row
@@ -319,7 +329,7 @@ __device__ inline void storeSamples(std::uint8_t *row, int col, int n, bool fast
 }
 
 // P010 / I010 -> BGRX (u8): the strip of yuv420ToBgrxStrip with 16-bit samples -- 32 B of Y per row, 16 (+2) B of each
-// chroma plane row or 32 (+4) B of UV, from three chroma rows.  `k`: yuvDecodeCoefficients10.
+// chroma plane row or 32 (+4) B of UV, from three chroma rows.  `k`: the coefficients for 10-bit words.
 template <bool P010>
 __device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H, int idx) {
@@ -639,7 +649,7 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv420p10_kernel(const std::uint8
 // ---- 4:2:2 and 4:4:4, 8- and 10-bit (tests/yuv_sampled_reference.py; docs/yuv_io.md, "4:2:2 and 4:4:4") ----------------
 // Nothing couples rows here, so a thread's strip is 16 luma pixels of ONE row: thread idx = row idx / strips, columns
 // x0 .. x0 + 15.  Chroma is co-sited with the even luma columns (4:2:2) or with every pixel (4:4:4); the luma formulas,
-// the coefficients and the sample P are those of the 4:2:0 kernels above.  F is the frame's YuvSampled value.
+// the coefficients and the sample P are those of the 4:2:0 kernels above.  F is the frame's PixelFormat value.
 template <int F>
 struct SampledTraits {
 	static constexpr bool kPacked = F == kYuy2 || F == kUyvy;
@@ -762,7 +772,7 @@ __device__ inline void loadSampledStrip(const YuvPlanes &src, int y, int x0, int
 }
 
 // planes -> BGRX: the strip of thread `idx`; the body of the single-frame kernel and of the items kernel's branch.
-// `k`: yuvDecodeCoefficients (8-bit formats) or yuvDecodeCoefficients10.
+// `k`: decodeCoefficients for the format (8-bit samples or 10-bit words).
 template <int F>
 __device__ inline void yuvSampledToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H, int idx) {
@@ -972,7 +982,7 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled10_kernel(const std::u
 // thread shape of the 4:2:2 / 4:4:4 section: 16 pixels of ONE row per thread.  A strip is a run of samples in each plane
 // it touches (planar: 16 in each of R, G, B; packed: 48 or 64 in the one plane) that moves as 16-byte accesses where the
 // run starts 16-byte aligned, as dwords at 4, else sample by sample -- tested per run, since dense rows of 3-byte pixels
-// start at every alignment.  F is the frame's RgbFormat value.
+// start at every alignment.  F is the frame's PixelFormat value.
 
 template <int B>
 __device__ inline void putSample(unsigned *w, int k, unsigned v) {  // (into words that start as 0)
@@ -1205,44 +1215,44 @@ __global__ __launch_bounds__(256) void state_to_rgb_kernel(const f16 *__restrict
 	toRgbStrip<F>(StateSource{state}, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
-// The YUV inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item --
-// its planes, coefficients and destination, from the kernel arguments -- and its format is a branch every lane of the
+// The formats each kernel family instantiates, ONE list per family: the launchers below and the items kernel reach a
+// format's kernel or strip body through forFormat alone.  4:2:0: <NV12> / <P010> = the list's second format; the encodes of
+// the other two families pick the 8-bit or the deep kernel from the format's traits.
+template <int... Fs>
+struct Formats {};
+using Yuv420 = Formats<kI420, kNv12>;
+using Yuv420p10 = Formats<kI010, kP010>;
+using Sampled = Formats<kYuy2, kUyvy, kI422, kP210, kI210, kI444, kI410>;
+using Rgb = Formats<kBgr24, kRgb24, kRgbx, kBgrx64, kRgbp8, kRgbp10, kRgbp16, kRgbph, kRgbps, kBgr96f>;
+// fn(std::integral_constant<int, F>, args...) for the F of the list that equals `format`; false: the list has no such format
+template <int... Fs, typename Fn, typename... A>
+__host__ __device__ inline bool forFormat(Formats<Fs...>, int format, Fn &&fn, const A &...args) {
+	return ((format == Fs && (fn(std::integral_constant<int, Fs>{}, args...), true)) || ...);
+}
+
+// The inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item -- its
+// format, planes, coefficients and destination, from the kernel arguments -- and the format is a branch every lane of the
 // workgroup takes alike.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
 // launch latencies for one round of work (the shape addFlowAutoencoder's batched launches fixed for the flow net).
 // (a 4:2:2 / 4:4:4 or RGB item has a strip per row: the grid then covers strips x H threads and a 4:2:0 item's upper half
-// of them returns at once; `sampled` carries an RGB item's format value too, and its coefficients are not read)
+// of them returns at once; an RGB item's coefficients are not read)
 __global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
 	const YuvDecodeItem &it = items.item[blockIdx.y];
 	const int idx = blockIdx.x * 256 + threadIdx.x;
-	switch (it.sampled) {
-	case kYuy2: return yuvSampledToBgrxStrip<kYuy2>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	case kUyvy: return yuvSampledToBgrxStrip<kUyvy>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	case kI422: return yuvSampledToBgrxStrip<kI422>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	case kP210: return yuvSampledToBgrxStrip<kP210>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	case kI210: return yuvSampledToBgrxStrip<kI210>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	case kI444: return yuvSampledToBgrxStrip<kI444>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	case kI410: return yuvSampledToBgrxStrip<kI410>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	case kBgr24: return rgbToBgrxStrip<kBgr24>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kRgb24: return rgbToBgrxStrip<kRgb24>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kRgbx: return rgbToBgrxStrip<kRgbx>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kBgrx64: return rgbToBgrxStrip<kBgrx64>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kRgbp8: return rgbToBgrxStrip<kRgbp8>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kRgbp10: return rgbToBgrxStrip<kRgbp10>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kRgbp16: return rgbToBgrxStrip<kRgbp16>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kRgbph: return rgbToBgrxStrip<kRgbph>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kRgbps: return rgbToBgrxStrip<kRgbps>(it.src, it.dst, it.dstStride, W, H, idx);
-	case kBgr96f: return rgbToBgrxStrip<kBgr96f>(it.src, it.dst, it.dstStride, W, H, idx);
-	default: break;
-	}
-	if (it.deep == 1) {  // (P010; 2: I010 -- 10-bit items, as uniform per workgroup as the 8-bit formats)
-		yuv420p10ToBgrxStrip<true>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	} else if (it.deep == 2) {
-		yuv420p10ToBgrxStrip<false>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	} else if (it.nv12) {
-		yuv420ToBgrxStrip<true>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	} else {
-		yuv420ToBgrxStrip<false>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	}
+	// (captureless: a strip body sees the item as the kernel's own argument, which is what lets the inliner fold it in)
+	using Item = const YuvDecodeItem &;
+	(void)(forFormat(Yuv420{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       yuv420ToBgrxStrip<f() == kNv12>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Yuv420p10{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       yuv420p10ToBgrxStrip<f() == kP010>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Sampled{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       yuvSampledToBgrxStrip<f()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Rgb{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       rgbToBgrxStrip<f()>(it.src, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx));
 }
 
 int roundHalfAway(double x) { return static_cast<int>(std::copysign(std::floor(std::fabs(x) * 65536.0 + 0.5), x)); }
@@ -1255,25 +1265,26 @@ void colourSpace(int cs, double *kr, double *kb, bool *limited) {
 	*limited = cs == 0 || cs == 2;
 }
 
-}  // namespace
-
-YuvDecode yuvDecodeCoefficients(int colorspace) {
+// x 65536 for 8-bit samples, or for 10-bit words -> u8 (oy 64 | 0); an RGB format has none and its colour space is not read
+YuvDecode decodeCoefficients(const YuvFormatInfo &info, int colorspace) {
+	if (info.rgb()) return YuvDecode{};
 	double kr, kb;
 	bool limited;
 	colourSpace(colorspace, &kr, &kb, &limited);
 	const double kg = 1.0 - kr - kb;
-	const double s = limited ? 255.0 / 224.0 : 1.0;
+	const bool words = info.words10();
+	const double s = words ? (limited ? 255.0 / 896.0 : 255.0 / 1023.0) : (limited ? 255.0 / 224.0 : 1.0);
 	YuvDecode k;
-	k.ky = roundHalfAway(limited ? 255.0 / 219.0 : 1.0);
+	k.ky = roundHalfAway(words ? (limited ? 255.0 / 876.0 : 255.0 / 1023.0) : (limited ? 255.0 / 219.0 : 1.0));
 	k.krv = roundHalfAway(2 * (1 - kr) * s);
 	k.kbu = roundHalfAway(2 * (1 - kb) * s);
 	k.kgu = roundHalfAway(2 * kb * (1 - kb) / kg * s);
 	k.kgv = roundHalfAway(2 * kr * (1 - kr) / kg * s);
-	k.oy = limited ? 16 : 0;
+	k.oy = limited ? (words ? 64 : 16) : 0;
 	return k;
 }
 
-YuvEncode yuvEncodeCoefficients(int colorspace) {
+YuvEncode encodeCoefficients(int colorspace) {
 	double kr, kb;
 	bool limited;
 	colourSpace(colorspace, &kr, &kb, &limited);
@@ -1294,23 +1305,7 @@ YuvEncode yuvEncodeCoefficients(int colorspace) {
 	return k;
 }
 
-YuvDecode yuvDecodeCoefficients10(int colorspace) {
-	double kr, kb;
-	bool limited;
-	colourSpace(colorspace, &kr, &kb, &limited);
-	const double kg = 1.0 - kr - kb;
-	const double s = limited ? 255.0 / 896.0 : 255.0 / 1023.0;
-	YuvDecode k;
-	k.ky = roundHalfAway(limited ? 255.0 / 876.0 : 255.0 / 1023.0);
-	k.krv = roundHalfAway(2 * (1 - kr) * s);
-	k.kbu = roundHalfAway(2 * (1 - kb) * s);
-	k.kgu = roundHalfAway(2 * kb * (1 - kb) / kg * s);
-	k.kgv = roundHalfAway(2 * kr * (1 - kr) / kg * s);
-	k.oy = limited ? 64 : 0;
-	return k;
-}
-
-YuvEncode10 yuvEncodeCoefficients10(int colorspace) {
+YuvEncode10 encodeCoefficients10(int colorspace) {
 	double kr, kb;
 	bool limited;
 	colourSpace(colorspace, &kr, &kb, &limited);
@@ -1335,231 +1330,96 @@ YuvEncode10 yuvEncodeCoefficients10(int colorspace) {
 	return k;
 }
 
-void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
-    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream) {
-	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
-	if (nv12) {
-		hipLaunchKernelGGL(yuv420_to_bgrx_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
-		    dstStride, width, height);
-	} else {
-		hipLaunchKernelGGL(yuv420_to_bgrx_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
-		    dstStride, width, height);
+// One strip kernel over a frame: a thread per 16 pixels of a row or, for 4:2:0, of a row pair; every kernel's arguments
+// end in the frame's width and height
+struct StripLaunch {
+	const YuvFormatInfo &info;
+	int width, height;
+	hipStream_t stream;
+	template <typename... P, typename... A>
+	void operator()(const char *name, void (*kernel)(P...), const A &...args) const {
+		const std::size_t strips = static_cast<std::size_t>((width + kStrip - 1) / kStrip);
+		const dim3 grid(blocksFor(strips * (info.perRow() ? height : height / 2)));
+		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, args..., width, height);
+		hipCheckLaunch(name);
 	}
-	hipCheckLaunch("yuv420_to_bgrx");
+};
+
+[[noreturn]] void noKernel(const char *what, int format) {
+	throw std::invalid_argument(std::string(what) + ": format " + std::to_string(format) + " has no such kernel");
+}
+
+}  // namespace
+
+void launchDecodeFrame(int format, int colorspace, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride,
+    int width, int height, hipStream_t stream) {
+	const StripLaunch run{formatInfo(format), width, height, stream};
+	const YuvDecode k = decodeCoefficients(run.info, colorspace);
+	if (!(forFormat(Yuv420{}, format,
+	          [&](auto f) { run("yuv420_to_bgrx", yuv420_to_bgrx_kernel<f() == kNv12>, src, k, dst, dstStride); }) ||
+	        forFormat(Yuv420p10{}, format,
+	            [&](auto f) { run("yuv420p10_to_bgrx", yuv420p10_to_bgrx_kernel<f() == kP010>, src, k, dst, dstStride); }) ||
+	        forFormat(Sampled{}, format,
+	            [&](auto f) { run("yuv_sampled_to_bgrx", yuv_sampled_to_bgrx_kernel<f()>, src, k, dst, dstStride); }) ||
+	        forFormat(Rgb{}, format, [&](auto f) { run("rgb_to_bgrx", rgb_to_bgrx_kernel<f()>, src, dst, dstStride); }))) {
+		noKernel("decode", format);
+	}
+}
+
+YuvDecodeItem yuvDecodeItem(int format, int colorspace, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride) {
+	YuvDecodeItem it;
+	it.src = src;
+	it.k = decodeCoefficients(formatInfo(format), colorspace);
+	it.dst = dst;
+	it.dstStride = dstStride;
+	it.format = format;
+	return it;
 }
 
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream) {
 	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("yuv420_to_bgrx_items: 1 .. 8 items");
-	bool perRow = false;  // (a 4:2:2 / 4:4:4 or RGB item: a strip per row, not per row pair)
-	for (int i = 0; i < count; ++i) perRow = perRow || items.item[i].sampled != 0;
+	bool perRow = false;
+	for (int i = 0; i < count; ++i) perRow = perRow || formatInfo(items.item[i].format).perRow();
 	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (perRow ? height : height / 2);
 	hipLaunchKernelGGL(yuv420_to_bgrx_items_kernel, dim3(blocksFor(threads), count), dim3(256), 0, stream, items, width,
 	    height);
 	hipCheckLaunch("yuv420_to_bgrx_items");
 }
 
-void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
-	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
-	if (nv12) {
-		hipLaunchKernelGGL(bgrx_to_yuv420_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, srcStride,
-		    k, dst, width, height);
-	} else {
-		hipLaunchKernelGGL(bgrx_to_yuv420_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src,
-		    srcStride, k, dst, width, height);
-	}
-	hipCheckLaunch("bgrx_to_yuv420");
+void launchEncodeFrame(int format, int colorspace, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst,
+    int width, int height, hipStream_t stream) {
+	const StripLaunch run{formatInfo(format), width, height, stream};
+	const bool done = forFormat(Yuv420{}, format, [&](auto f) {
+		run("bgrx_to_yuv420", bgrx_to_yuv420_kernel<f() == kNv12>, src, srcStride, encodeCoefficients(colorspace), dst);
+	}) || forFormat(Yuv420p10{}, format, [&](auto f) {
+		run("bgrx_to_yuv420p10", bgrx_to_yuv420p10_kernel<f() == kP010>, src, srcStride, encodeCoefficients10(colorspace), dst);
+	}) || forFormat(Sampled{}, format, [&](auto f) {
+		if constexpr (SampledTraits<f()>::kDeep) {
+			run("bgrx_to_yuv_sampled10", bgrx_to_yuv_sampled10_kernel<f()>, src, srcStride, encodeCoefficients10(colorspace), dst);
+		} else {
+			run("bgrx_to_yuv_sampled", bgrx_to_yuv_sampled_kernel<f()>, src, srcStride, encodeCoefficients(colorspace), dst);
+		}
+	}) || forFormat(Rgb{}, format, [&](auto f) { run("bgrx_to_rgb", bgrx_to_rgb_kernel<f()>, src, srcStride, dst); });
+	if (!done) noKernel("encode", format);
 }
 
-void launchYuv420p10ToBgrx(bool p010, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
-    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream) {
-	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
-	if (p010) {
-		hipLaunchKernelGGL(yuv420p10_to_bgrx_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
-		    dstStride, width, height);
-	} else {
-		hipLaunchKernelGGL(yuv420p10_to_bgrx_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src, k, dst,
-		    dstStride, width, height);
-	}
-	hipCheckLaunch("yuv420p10_to_bgrx");
-}
-
-void launchStateToYuv420p10(bool p010, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
-    int height, hipStream_t stream) {
-	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
-	if (p010) {
-		hipLaunchKernelGGL(state_to_yuv420p10_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream,
-		    static_cast<const f16 *>(state), k, dst, width, height);
-	} else {
-		hipLaunchKernelGGL(state_to_yuv420p10_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream,
-		    static_cast<const f16 *>(state), k, dst, width, height);
-	}
-	hipCheckLaunch("state_to_yuv420p10");
-}
-
-void launchBgrxToYuv420p10(bool p010, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
-	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (height / 2);
-	if (p010) {
-		hipLaunchKernelGGL(bgrx_to_yuv420p10_kernel<true>, dim3(blocksFor(threads)), dim3(256), 0, stream, src,
-		    srcStride, k, dst, width, height);
-	} else {
-		hipLaunchKernelGGL(bgrx_to_yuv420p10_kernel<false>, dim3(blocksFor(threads)), dim3(256), 0, stream, src,
-		    srcStride, k, dst, width, height);
-	}
-	hipCheckLaunch("bgrx_to_yuv420p10");
-}
-
-namespace {
-std::size_t sampledThreads(int width, int height) {
-	return static_cast<std::size_t>((width + kStrip - 1) / kStrip) * static_cast<std::size_t>(height);
-}
-[[noreturn]] void notSampled(const char *what, int format) {
-	throw std::invalid_argument(std::string(what) + ": format " + std::to_string(format) + " has no such kernel");
-}
-}  // namespace
-
-void launchYuvSampledToBgrx(int format, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
-    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream) {
-	const dim3 grid(blocksFor(sampledThreads(width, height)));
-#define JU_SAMPLED_DECODE(F) \
-	case F: \
-		hipLaunchKernelGGL(yuv_sampled_to_bgrx_kernel<F>, grid, dim3(256), 0, stream, src, k, dst, dstStride, width, height); \
-		break;
-	switch (format) {
-		JU_SAMPLED_DECODE(kYuy2)
-		JU_SAMPLED_DECODE(kUyvy)
-		JU_SAMPLED_DECODE(kI422)
-		JU_SAMPLED_DECODE(kP210)
-		JU_SAMPLED_DECODE(kI210)
-		JU_SAMPLED_DECODE(kI444)
-		JU_SAMPLED_DECODE(kI410)
-	default: notSampled("yuv_sampled_to_bgrx", format);
-	}
-#undef JU_SAMPLED_DECODE
-	hipCheckLaunch("yuv_sampled_to_bgrx");
-}
-
-void launchBgrxToYuvSampled(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
-	const dim3 grid(blocksFor(sampledThreads(width, height)));
-#define JU_SAMPLED_ENCODE(F) \
-	case F: \
-		hipLaunchKernelGGL(bgrx_to_yuv_sampled_kernel<F>, grid, dim3(256), 0, stream, src, srcStride, k, dst, width, height); \
-		break;
-	switch (format) {
-		JU_SAMPLED_ENCODE(kYuy2)
-		JU_SAMPLED_ENCODE(kUyvy)
-		JU_SAMPLED_ENCODE(kI422)
-		JU_SAMPLED_ENCODE(kI444)
-	default: notSampled("bgrx_to_yuv_sampled", format);
-	}
-#undef JU_SAMPLED_ENCODE
-	hipCheckLaunch("bgrx_to_yuv_sampled");
-}
-
-void launchStateToYuvSampled10(int format, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
-    int height, hipStream_t stream) {
-	const dim3 grid(blocksFor(sampledThreads(width, height)));
-	const f16 *s = static_cast<const f16 *>(state);
-#define JU_SAMPLED_ENCODE(F) \
-	case F: \
-		hipLaunchKernelGGL(state_to_yuv_sampled10_kernel<F>, grid, dim3(256), 0, stream, s, k, dst, width, height); \
-		break;
-	switch (format) {
-		JU_SAMPLED_ENCODE(kP210)
-		JU_SAMPLED_ENCODE(kI210)
-		JU_SAMPLED_ENCODE(kI410)
-	default: notSampled("state_to_yuv_sampled10", format);
-	}
-#undef JU_SAMPLED_ENCODE
-	hipCheckLaunch("state_to_yuv_sampled10");
-}
-
-void launchBgrxToYuvSampled10(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream) {
-	const dim3 grid(blocksFor(sampledThreads(width, height)));
-#define JU_SAMPLED_ENCODE(F) \
-	case F: \
-		hipLaunchKernelGGL(bgrx_to_yuv_sampled10_kernel<F>, grid, dim3(256), 0, stream, src, srcStride, k, dst, width, \
-		    height); \
-		break;
-	switch (format) {
-		JU_SAMPLED_ENCODE(kP210)
-		JU_SAMPLED_ENCODE(kI210)
-		JU_SAMPLED_ENCODE(kI410)
-	default: notSampled("bgrx_to_yuv_sampled10", format);
-	}
-#undef JU_SAMPLED_ENCODE
-	hipCheckLaunch("bgrx_to_yuv_sampled10");
-}
-
-void launchRgbToBgrx(int format, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride, int width, int height,
+void launchEncodeState(int format, int colorspace, const void *state, const YuvPlanes &dst, int width, int height,
     hipStream_t stream) {
-	const dim3 grid(blocksFor(sampledThreads(width, height)));
-#define JU_RGB_DECODE(F) \
-	case F: \
-		hipLaunchKernelGGL(rgb_to_bgrx_kernel<F>, grid, dim3(256), 0, stream, src, dst, dstStride, width, height); \
-		break;
-	switch (format) {
-		JU_RGB_DECODE(kBgr24)
-		JU_RGB_DECODE(kRgb24)
-		JU_RGB_DECODE(kRgbx)
-		JU_RGB_DECODE(kBgrx64)
-		JU_RGB_DECODE(kRgbp8)
-		JU_RGB_DECODE(kRgbp10)
-		JU_RGB_DECODE(kRgbp16)
-		JU_RGB_DECODE(kRgbph)
-		JU_RGB_DECODE(kRgbps)
-		JU_RGB_DECODE(kBgr96f)
-	default: notSampled("rgb_to_bgrx", format);
-	}
-#undef JU_RGB_DECODE
-	hipCheckLaunch("rgb_to_bgrx");
-}
-
-void launchBgrxToRgb(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst, int width,
-    int height, hipStream_t stream) {
-	const dim3 grid(blocksFor(sampledThreads(width, height)));
-#define JU_RGB_ENCODE(F) \
-	case F: \
-		hipLaunchKernelGGL(bgrx_to_rgb_kernel<F>, grid, dim3(256), 0, stream, src, srcStride, dst, width, height); \
-		break;
-	switch (format) {
-		JU_RGB_ENCODE(kBgr24)
-		JU_RGB_ENCODE(kRgb24)
-		JU_RGB_ENCODE(kRgbx)
-		JU_RGB_ENCODE(kBgrx64)
-		JU_RGB_ENCODE(kRgbp8)
-		JU_RGB_ENCODE(kRgbp10)
-		JU_RGB_ENCODE(kRgbp16)
-		JU_RGB_ENCODE(kRgbph)
-		JU_RGB_ENCODE(kRgbps)
-		JU_RGB_ENCODE(kBgr96f)
-	default: notSampled("bgrx_to_rgb", format);
-	}
-#undef JU_RGB_ENCODE
-	hipCheckLaunch("bgrx_to_rgb");
-}
-
-void launchStateToRgb(int format, const void *state, const YuvPlanes &dst, int width, int height, hipStream_t stream) {
-	const dim3 grid(blocksFor(sampledThreads(width, height)));
+	const StripLaunch run{formatInfo(format), width, height, stream};
 	const f16 *s = static_cast<const f16 *>(state);
-#define JU_RGB_ENCODE(F) \
-	case F: \
-		hipLaunchKernelGGL(state_to_rgb_kernel<F>, grid, dim3(256), 0, stream, s, dst, width, height); \
-		break;
-	switch (format) {
-		JU_RGB_ENCODE(kBgrx64)
-		JU_RGB_ENCODE(kRgbp10)
-		JU_RGB_ENCODE(kRgbp16)
-		JU_RGB_ENCODE(kRgbph)
-		JU_RGB_ENCODE(kRgbps)
-		JU_RGB_ENCODE(kBgr96f)
-	default: notSampled("state_to_rgb", format);
-	}
-#undef JU_RGB_ENCODE
-	hipCheckLaunch("state_to_rgb");
+	const bool done = forFormat(Yuv420p10{}, format, [&](auto f) {
+		run("state_to_yuv420p10", state_to_yuv420p10_kernel<f() == kP010>, s, encodeCoefficients10(colorspace), dst);
+	}) || forFormat(Sampled{}, format, [&](auto f) {
+		if constexpr (SampledTraits<f()>::kDeep) {
+			run("state_to_yuv_sampled10", state_to_yuv_sampled10_kernel<f()>, s, encodeCoefficients10(colorspace), dst);
+		} else {
+			noKernel("encode from the state", format);
+		}
+	}) || forFormat(Rgb{}, format, [&](auto f) {
+		if constexpr (RgbTraits<f()>::kKind != kU8) run("state_to_rgb", state_to_rgb_kernel<f()>, s, dst);
+		else noKernel("encode from the state", format);
+	});
+	if (!done) noKernel("encode from the state", format);
 }
 
 }  // namespace ju

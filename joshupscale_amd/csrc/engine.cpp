@@ -1497,31 +1497,17 @@ struct PlaneShape {
 	std::size_t rows, rowBytes;
 };
 // A format = sampling (420 / 422 / 444; 0: RGB, every plane full size) x storage (planar / semi-planar Y, UV / packed: one
-// plane) x sample size: all of it from the one table, yuvFormatInfo (kernels.h)
-bool knownYuv(PixelFormat f) { return yuvFormatInfo(static_cast<int>(f)) != nullptr; }
-const YuvFormatInfo &infoOf(PixelFormat f) {
-	const YuvFormatInfo *info = yuvFormatInfo(static_cast<int>(f));
-	if (info == nullptr) throw std::invalid_argument("unknown frame format " + std::to_string(static_cast<int>(f)));
-	return *info;
-}
-int sampling(PixelFormat f) { return infoOf(f).sampling; }
-bool rgb(PixelFormat f) { return infoOf(f).sampling == 0; }
-bool packed(PixelFormat f) { return infoOf(f).planes == 1; }
-bool semiPlanar(PixelFormat f) { return infoOf(f).planes == 2; }
-bool tenBit(PixelFormat f) { return infoOf(f).bits == 10 && infoOf(f).sampling != 0; }  // (10-bit YUV words; not RGBP10)
-bool deepFormat(PixelFormat f) { return infoOf(f).bits > 8; }  // (more than the 8-bit frame holds: encoded from the state)
-std::size_t bytesPerSample(PixelFormat f) { return static_cast<std::size_t>(infoOf(f).sampleBytes); }
+// plane) x sample size: all of it from the one table, formatInfo (kernels.h)
 PlaneShape planeShape(PixelFormat f, std::size_t w, std::size_t h, int k) {
-	const std::size_t b = bytesPerSample(f);
-	if (packed(f)) return {h, static_cast<std::size_t>(infoOf(f).pixelBytes) * w};
-	if (k == 0 || rgb(f)) return {h, w * b};
-	const int s = sampling(f);
-	const std::size_t cw = s == 444 ? w : w / 2;  // chroma samples per row (a semi-planar row holds both planes')
-	return {s == 420 ? h / 2 : h, (semiPlanar(f) ? 2 * cw : cw) * b};
+	const YuvFormatInfo &info = formatInfo(f);
+	const auto b = static_cast<std::size_t>(info.sampleBytes);
+	if (info.planes == 1) return {h, static_cast<std::size_t>(info.pixelBytes) * w};
+	if (k == 0 || info.rgb()) return {h, w * b};
+	const std::size_t cw = info.sampling == 444 ? w : w / 2;  // chroma samples per row (a semi-planar row holds both planes')
+	return {info.perRow() ? h : h / 2, (info.planes == 2 ? 2 * cw : cw) * b};
 }
-int planeCount(PixelFormat f) { return infoOf(f).planes; }
+int planeCount(PixelFormat f) { return formatInfo(f).planes; }
 std::size_t stagePitch(std::size_t rowBytes) { return (rowBytes + 63) / 64 * 64; }
-const char *formatName(PixelFormat f) { return infoOf(f).name; }
 
 // The caller's device planes as a conversion kernel takes them
 YuvPlanes callerPlanes(const YuvFrame &f) {
@@ -1615,34 +1601,34 @@ void Engine::checkFrame(const AnyFrame &f, bool input) const {
 		return;
 	}
 	const YuvFrame &y = f.planes;
-	if (!knownYuv(y.format)) throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
-	if (!rgb(y.format) && (y.colorspace < 0 || y.colorspace > 3)) {  // (an RGB frame has none: the field is ignored)
+	const YuvFormatInfo *known = yuvFormatInfo(fmt(y.format));
+	if (known == nullptr) throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
+	const YuvFormatInfo &info = *known;
+	if (!info.rgb() && (y.colorspace < 0 || y.colorspace > 3)) {  // (an RGB frame has none: the field is ignored)
 		throw std::invalid_argument("processFrame: unknown " + side + " colour space " + std::to_string(y.colorspace));
 	}
 	if (y.location != Location::Host && y.location != Location::Device) {
-		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) + " " + side +
+		throw std::invalid_argument(std::string("processFrame: ") + info.name + " " + side +
 		                            " frames must be host or device memory (no graphics resources)");
 	}
-	if (sampling(y.format) == 420 && (y.width % 2 || y.height % 2)) {
-		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) +
-		                            " needs an even width and height");
+	if (info.sampling == 420 && (y.width % 2 || y.height % 2)) {
+		throw std::invalid_argument(std::string("processFrame: ") + info.name + " needs an even width and height");
 	}
-	if (sampling(y.format) == 422 && y.width % 2) {
-		throw std::invalid_argument(std::string("processFrame: ") + formatName(y.format) +
-		                            " (4:2:2) needs an even width");
+	if (info.sampling == 422 && y.width % 2) {
+		throw std::invalid_argument(std::string("processFrame: ") + info.name + " (4:2:2) needs an even width");
 	}
 	if (y.width != w || y.height != h) {
 		throw std::invalid_argument("processFrame: " + side + " frame must be exactly " + size);
 	}
-	for (int k = 0; k < planeCount(y.format); ++k) {
+	for (int k = 0; k < info.planes; ++k) {
 		if (y.planes[k] == nullptr) {
 			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) + " is NULL");
 		}
-		const std::size_t sample = bytesPerSample(y.format);
+		const auto sample = static_cast<std::size_t>(info.sampleBytes);
 		if (sample > 1 && (reinterpret_cast<std::uintptr_t>(y.planes[k]) % sample != 0 ||
 		                   y.strides[k] % static_cast<std::ptrdiff_t>(sample) != 0)) {
 			throw std::invalid_argument(std::string("processFrame: ") + side + " plane " + std::to_string(k) + ": " +
-			                            formatName(y.format) + " samples are " + (sample == 2 ? "16-bit" : "32-bit") +
+			                            info.name + " samples are " + (sample == 2 ? "16-bit" : "32-bit") +
 			                            " words -- the plane's address and its stride must be multiples of " +
 			                            std::to_string(sample));
 		}
@@ -1667,19 +1653,7 @@ void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
     std::ptrdiff_t bgrxStride, std::size_t width, std::size_t height) {
 	const FrameSize fs = frameSize();
 	const int w = static_cast<int>(width ? width : fs.inputWidth), h = static_cast<int>(height ? height : fs.inputHeight);
-	if (rgb(format)) {
-		launchRgbToBgrx(static_cast<int>(format), planes, bgrx, bgrxStride, w, h, m_Stream);
-	} else if (sampling(format) != 420) {
-		launchYuvSampledToBgrx(static_cast<int>(format), planes,
-		    tenBit(format) ? yuvDecodeCoefficients10(colorspace) : yuvDecodeCoefficients(colorspace), bgrx, bgrxStride, w, h,
-		    m_Stream);
-	} else if (tenBit(format)) {
-		launchYuv420p10ToBgrx(format == PixelFormat::P010, planes, yuvDecodeCoefficients10(colorspace), bgrx, bgrxStride,
-		    w, h, m_Stream);
-	} else {
-		launchYuv420ToBgrx(format == PixelFormat::Nv12, planes, yuvDecodeCoefficients(colorspace), bgrx, bgrxStride, w, h,
-		    m_Stream);
-	}
+	launchDecodeFrame(fmt(format), colorspace, planes, bgrx, bgrxStride, w, h, m_Stream);
 }
 
 // one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit YUV or
@@ -1688,32 +1662,11 @@ void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
     std::ptrdiff_t bgrxStride, const void *state) {
 	const FrameSize fs = frameSize();
 	const int w = static_cast<int>(fs.outputWidth), h = static_cast<int>(fs.outputHeight);
-	const bool fromState = m_HbdFromState && m_MaskW == 0;  // (a mask: the blended frame exists in 8 bits only)
-	if (rgb(format)) {  // 8-bit formats permute the frame's bytes; the deep ones take the state where it is the frame
-		const int f = static_cast<int>(format);
-		if (deepFormat(format) && fromState) {
-			launchStateToRgb(f, state, planes, w, h, m_Stream);
-		} else {
-			launchBgrxToRgb(f, bgrx, bgrxStride, planes, w, h, m_Stream);
-		}
-	} else if (sampling(format) != 420) {  // 4:2:2 / 4:4:4: the same three sources
-		const int f = static_cast<int>(format);
-		if (!tenBit(format)) {
-			launchBgrxToYuvSampled(f, bgrx, bgrxStride, yuvEncodeCoefficients(colorspace), planes, w, h, m_Stream);
-		} else if (fromState) {
-			launchStateToYuvSampled10(f, state, yuvEncodeCoefficients10(colorspace), planes, w, h, m_Stream);
-		} else {
-			launchBgrxToYuvSampled10(f, bgrx, bgrxStride, yuvEncodeCoefficients10(colorspace), planes, w, h, m_Stream);
-		}
-	} else if (!tenBit(format)) {
-		launchBgrxToYuv420(format == PixelFormat::Nv12, bgrx, bgrxStride, yuvEncodeCoefficients(colorspace), planes, w, h,
-		    m_Stream);
-	} else if (fromState) {
-		launchStateToYuv420p10(format == PixelFormat::P010, state, yuvEncodeCoefficients10(colorspace), planes, w, h,
-		    m_Stream);
+	// (a mask: the blended frame exists in 8 bits only)
+	if (m_HbdFromState && m_MaskW == 0 && formatInfo(format).deep()) {
+		launchEncodeState(fmt(format), colorspace, state, planes, w, h, m_Stream);
 	} else {
-		launchBgrxToYuv420p10(format == PixelFormat::P010, bgrx, bgrxStride, yuvEncodeCoefficients10(colorspace), planes,
-		    w, h, m_Stream);
+		launchEncodeFrame(fmt(format), colorspace, bgrx, bgrxStride, planes, w, h, m_Stream);
 	}
 }
 
@@ -2090,14 +2043,8 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 	for (int i = 0; i < n; ++i) {
 		const PassFrame &pf = m_BatchHost[i];
 		if (!pf.yuvIn) continue;
-		YuvDecodeItem &it = items.item[decodes++];
-		it.src = pf.decode;
-		if (!rgb(pf.formatIn)) it.k = tenBit(pf.formatIn) ? yuvDecodeCoefficients10(pf.csIn) : yuvDecodeCoefficients(pf.csIn);
-		it.dst = const_cast<std::uint8_t *>(m_BatchIO[i].in);
-		it.dstStride = m_BatchIO[i].inStride;
-		it.nv12 = pf.formatIn == PixelFormat::Nv12 ? 1 : 0;
-		it.deep = pf.formatIn == PixelFormat::P010 ? 1 : (pf.formatIn == PixelFormat::I010 ? 2 : 0);
-		it.sampled = sampling(pf.formatIn) != 420 ? static_cast<int>(pf.formatIn) : 0;
+		items.item[decodes++] = yuvDecodeItem(fmt(pf.formatIn), pf.csIn, pf.decode, const_cast<std::uint8_t *>(m_BatchIO[i].in),
+		    m_BatchIO[i].inStride);
 	}
 	if (decodes) {
 		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),
@@ -2166,7 +2113,7 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 	// the planes a conversion launch addresses, and what of them the graph bakes in
 	auto bindPlanes = [](const YuvFrame &y, DeviceBuffer *stage, YuvKey *key) {
 		key->format = static_cast<int>(y.format);
-		key->colorspace = rgb(y.format) ? 0 : y.colorspace;  // (ignored for RGB: no second graph for another value)
+		key->colorspace = formatInfo(y.format).rgb() ? 0 : y.colorspace;  // (ignored for RGB: no second graph for another value)
 		for (int k = 0; k < planeCount(y.format); ++k) {
 			key->planes[k] = stage ? nullptr : y.planes[k];
 			key->strides[k] = stage ? (y.strides[k] > 0 ? 1 : -1) : y.strides[k];

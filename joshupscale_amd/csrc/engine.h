@@ -40,20 +40,9 @@ struct Frame {
 	std::size_t height;
 };
 
-// A 4:2:0 frame of ju_process_frame (include/joshupscale_amd.h, ju_frame): planes Y, U, V (I420 / YV12, I010) or
-// Y, interleaved UV (NV12, P010), each addressing its first logical row, strides in bytes of any sign.  Host or device.
-// P010 / I010: 16-bit little-endian samples (the 10-bit value in the upper / the low bits).
-// From 16 on, 4:2:2 (chroma rows of full height) and 4:4:4: packed YUY2 / UYVY (ONE plane, 2 bytes per pixel), I422 and
-// I210 (Y, U, V; I210 words as I010), P210 (Y, UV; words as P010), I444 and I410 (three full planes; I410 words as I010).
-// From 32 on, RGB (no colour space: `colorspace` is ignored): packed BGR24 / RGB24 (3 bytes per pixel), RGBX, BGRX64 (four
-// 16-bit words per pixel) and BGR96F (three f32 per pixel, 0..255) are ONE plane; RGBP8 / RGBP10 / RGBP16 / RGBPH / RGBPS are
-// planes R, G, B of bytes, words (RGBP10: the value in the low 10 bits), f16 and f32 (0..1).  tests/rgb_reference.py.
-enum class PixelFormat : int {
-	Bgrx = 0, I420 = 1, Nv12 = 2, P010 = 3, I010 = 4,
-	Yuy2 = 16, Uyvy = 17, I422 = 18, P210 = 19, I210 = 20, I444 = 24, I410 = 25,
-	Bgr24 = 32, Rgb24 = 33, Rgbx = 34, Bgrx64 = 35, Rgbp8 = 36, Rgbp10 = 37, Rgbp16 = 38, Rgbph = 39, Rgbps = 40, Bgr96f = 41
-};
-
+// A frame of ju_process_frame that is not BGRX (include/joshupscale_amd.h, ju_frame): a format of the table in kernels.h
+// (PixelFormat: planes, words and sample kinds are described there), its planes each addressing their first logical row,
+// strides in bytes of any sign.  Host or device.  An RGB format has no colour space: `colorspace` is ignored.
 struct YuvFrame {
 	PixelFormat format;
 	int colorspace;  // 0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full

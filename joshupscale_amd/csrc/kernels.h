@@ -11,6 +11,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -425,37 +426,31 @@ void launchTailFused(DType dt, const TailFusedLaunch &p, hipStream_t stream);
 void launchCopyRows(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint8_t *dst,
     std::ptrdiff_t dstStride, std::size_t rowBytes, std::size_t rows, hipStream_t stream);
 
-// ---- 8-bit 4:2:0 YUV <-> BGRX (colour_kernels.hip; ju_process_frame's colour staging) ----------------------------
-// Planes of a 4:2:0 frame: luma [H][W]; I420 chroma u, v [H/2][W/2]; NV12 one interleaved plane u [H/2][W] (v unused).
-// Pointers address the first logical row, strides are bytes and may be negative; any byte alignment.
-struct YuvPlanes {
-	std::uint8_t *y = nullptr, *u = nullptr, *v = nullptr;
-	std::ptrdiff_t yStride = 0, uStride = 0, vStride = 0;
+// ---- frame formats beside BGRX <-> BGRX (colour_kernels.hip; docs/yuv_io.md) -------------------------------------------
+// THE list of the frame formats: the values of JU_FMT_* (include/joshupscale_amd.h).  4:2:0: planes Y, U, V (I420 / YV12,
+// I010) or Y, interleaved UV (NV12, P010); P010 / I010: 16-bit little-endian samples, the 10-bit value in the upper / the
+// low bits.  From 16 on, 4:2:2 (chroma rows of full height) and 4:4:4: packed YUY2 / UYVY (ONE plane, 2 bytes per pixel),
+// I422 and I210 (Y, U, V; I210 words as I010), P210 (Y, UV; words as P010), I444 and I410 (three full planes; I410 words as
+// I010).  From 32 on, RGB (no colour space): packed BGR24 / RGB24 (3 bytes per pixel), RGBX, BGRX64 (four 16-bit words per
+// pixel) and BGR96F (three f32 per pixel, 0..255) are ONE plane; RGBP8 / RGBP10 / RGBP16 / RGBPH / RGBPS are planes R, G, B
+// of bytes, words (RGBP10: the value in the low 10 bits), f16 and f32 (0..1).
+enum class PixelFormat : int {
+	Bgrx = 0, I420 = 1, Nv12 = 2, P010 = 3, I010 = 4,
+	Yuy2 = 16, Uyvy = 17, I422 = 18, P210 = 19, I210 = 20, I444 = 24, I410 = 25,
+	Bgr24 = 32, Rgb24 = 33, Rgbx = 34, Bgrx64 = 35, Rgbp8 = 36, Rgbp10 = 37, Rgbp16 = 38, Rgbph = 39, Rgbps = 40, Bgr96f = 41
 };
-// x 65536, rounded half away from zero (tests/yuv_reference.py); oy = luma offset (16 limited, 0 full range)
-struct YuvDecode {
-	int ky, krv, kbu, kgu, kgv, oy;
-};
-struct YuvEncode {
-	int yr, yg, yb, ur, ug, ub, vr, vg, vb, oy;
-};
-// colorspace: 0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full (std::invalid_argument otherwise)
-YuvDecode yuvDecodeCoefficients(int colorspace);
-YuvEncode yuvEncodeCoefficients(int colorspace);
-// width, height even.  dst: BGRX rows (X = 0) / src: BGRX rows (X ignored).
-void launchYuv420ToBgrx(bool nv12, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
-    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
-void launchBgrxToYuv420(bool nv12, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream);
-// 4:2:2 and 4:4:4 formats (colour_kernels.hip, "4:2:2 and 4:4:4"): the values of PixelFormat / JU_FMT_*.
-enum YuvSampled : int { kYuy2 = 16, kUyvy = 17, kI422 = 18, kP210 = 19, kI210 = 20, kI444 = 24, kI410 = 25 };
-// The RGB formats (colour_kernels.hip, "RGB formats"): the values of PixelFormat / JU_FMT_*.
-enum RgbFormat : int {
-	kBgr24 = 32, kRgb24 = 33, kRgbx = 34, kBgrx64 = 35, kRgbp8 = 36, kRgbp10 = 37, kRgbp16 = 38, kRgbph = 39, kRgbps = 40,
-	kBgr96f = 41
-};
-// THE table of the frame formats beside BGRX, by PixelFormat / JU_FMT_* value: the C API and the engine classify a
-// format through it alone.  planes: 3 planar (Y, U, V / R, G, B), 2 semi-planar (Y, UV), 1 packed (pixelBytes per pixel).
+// (the same values as integers: what a launcher's `format` argument and a kernel's `template <int F>` parameter hold)
+constexpr int fmt(PixelFormat f) { return static_cast<int>(f); }
+constexpr int kI420 = fmt(PixelFormat::I420), kNv12 = fmt(PixelFormat::Nv12), kP010 = fmt(PixelFormat::P010),
+              kI010 = fmt(PixelFormat::I010), kYuy2 = fmt(PixelFormat::Yuy2), kUyvy = fmt(PixelFormat::Uyvy),
+              kI422 = fmt(PixelFormat::I422), kP210 = fmt(PixelFormat::P210), kI210 = fmt(PixelFormat::I210),
+              kI444 = fmt(PixelFormat::I444), kI410 = fmt(PixelFormat::I410), kBgr24 = fmt(PixelFormat::Bgr24),
+              kRgb24 = fmt(PixelFormat::Rgb24), kRgbx = fmt(PixelFormat::Rgbx), kBgrx64 = fmt(PixelFormat::Bgrx64),
+              kRgbp8 = fmt(PixelFormat::Rgbp8), kRgbp10 = fmt(PixelFormat::Rgbp10), kRgbp16 = fmt(PixelFormat::Rgbp16),
+              kRgbph = fmt(PixelFormat::Rgbph), kRgbps = fmt(PixelFormat::Rgbps), kBgr96f = fmt(PixelFormat::Bgr96f);
+
+// THE table of the frame formats beside BGRX: the C API, the engine and the launchers below classify a format through it
+// alone.  planes: 3 planar (Y, U, V / R, G, B), 2 semi-planar (Y, UV), 1 packed (pixelBytes per pixel).
 struct YuvFormatInfo {
 	int value;
 	const char *name;
@@ -464,85 +459,79 @@ struct YuvFormatInfo {
 	int bits;         // 8, or 10 in 16-bit words; RGB: 8, 10, 16 (words and f16) or 32 (f32)
 	int sampleBytes;  // 1, 2 or 4: what a plane's address and stride must be a multiple of
 	int pixelBytes;   // packed formats: bytes per pixel (2, 3, 4, 8 or 12); else 0
+	constexpr bool rgb() const { return sampling == 0; }
+	constexpr bool words10() const { return bits == 10 && sampling != 0; }  // 10-bit YUV words (not RGBP10): the 10-bit coefficients
+	constexpr bool deep() const { return bits > 8; }  // more than the 8-bit frame holds: encodable from the f16 state
+	constexpr bool perRow() const { return sampling != 420; }  // decode and encode run a strip per row (4:2:0: per row pair)
 };
-constexpr int kFormatValueEnd = 42;  // (one past the largest value of the table)
+inline constexpr YuvFormatInfo kFormatTable[] = {
+    {kI420, "I420", 420, 3, 8, 1, 0},    {kNv12, "NV12", 420, 2, 8, 1, 0},    {kP010, "P010", 420, 2, 10, 2, 0},
+    {kI010, "I010", 420, 3, 10, 2, 0},   {kYuy2, "YUY2", 422, 1, 8, 1, 2},    {kUyvy, "UYVY", 422, 1, 8, 1, 2},
+    {kI422, "I422", 422, 3, 8, 1, 0},    {kP210, "P210", 422, 2, 10, 2, 0},   {kI210, "I210", 422, 3, 10, 2, 0},
+    {kI444, "I444", 444, 3, 8, 1, 0},    {kI410, "I410", 444, 3, 10, 2, 0},   {kBgr24, "BGR24", 0, 1, 8, 1, 3},
+    {kRgb24, "RGB24", 0, 1, 8, 1, 3},    {kRgbx, "RGBX", 0, 1, 8, 1, 4},      {kBgrx64, "BGRX64", 0, 1, 16, 2, 8},
+    {kRgbp8, "RGBP8", 0, 3, 8, 1, 0},    {kRgbp10, "RGBP10", 0, 3, 10, 2, 0}, {kRgbp16, "RGBP16", 0, 3, 16, 2, 0},
+    {kRgbph, "RGBPH", 0, 3, 16, 2, 0},   {kRgbps, "RGBPS", 0, 3, 32, 4, 0},   {kBgr96f, "BGR96F", 0, 1, 32, 4, 12}};
+constexpr int kFormatValueEnd = kBgr96f + 1;  // (one past the largest value of the table)
 inline const YuvFormatInfo *yuvFormatInfo(int value) {  // nullptr: not in the table
-	static constexpr YuvFormatInfo kTable[] = {
-	    {1, "I420", 420, 3, 8, 1, 0},        {2, "NV12", 420, 2, 8, 1, 0},        {3, "P010", 420, 2, 10, 2, 0},
-	    {4, "I010", 420, 3, 10, 2, 0},       {kYuy2, "YUY2", 422, 1, 8, 1, 2},    {kUyvy, "UYVY", 422, 1, 8, 1, 2},
-	    {kI422, "I422", 422, 3, 8, 1, 0},    {kP210, "P210", 422, 2, 10, 2, 0},   {kI210, "I210", 422, 3, 10, 2, 0},
-	    {kI444, "I444", 444, 3, 8, 1, 0},    {kI410, "I410", 444, 3, 10, 2, 0},   {kBgr24, "BGR24", 0, 1, 8, 1, 3},
-	    {kRgb24, "RGB24", 0, 1, 8, 1, 3},    {kRgbx, "RGBX", 0, 1, 8, 1, 4},      {kBgrx64, "BGRX64", 0, 1, 16, 2, 8},
-	    {kRgbp8, "RGBP8", 0, 3, 8, 1, 0},    {kRgbp10, "RGBP10", 0, 3, 10, 2, 0}, {kRgbp16, "RGBP16", 0, 3, 16, 2, 0},
-	    {kRgbph, "RGBPH", 0, 3, 16, 2, 0},   {kRgbps, "RGBPS", 0, 3, 32, 4, 0},   {kBgr96f, "BGR96F", 0, 1, 32, 4, 12}};
-	for (const YuvFormatInfo &f : kTable) {
+	for (const YuvFormatInfo &f : kFormatTable) {
 		if (f.value == value) return &f;
 	}
 	return nullptr;
 }
-// The YUV inputs of a look-ahead pass (Engine::processFrames), decoded in one launch: item i of `count` (1 ..
-// kFlowBatchMax) = planes, coefficients and BGRX destination of one frame; all frames width x height.  Per item the
-// bytes of launchYuv420ToBgrx.  The struct is the launch's by-value argument (832 bytes).
+inline const YuvFormatInfo &formatInfo(int value) {
+	const YuvFormatInfo *info = yuvFormatInfo(value);
+	if (info == nullptr) throw std::invalid_argument("unknown frame format " + std::to_string(value));
+	return *info;
+}
+inline const YuvFormatInfo &formatInfo(PixelFormat f) { return formatInfo(fmt(f)); }
+
+// Planes of a frame: Y, U, V / R, G, B (planar), Y and one interleaved plane u (semi-planar; v unused) or y alone (packed:
+// rows of pixelBytes x width bytes).  Chroma planes have height / 2 (4:2:0) or height rows of width / 2 (4:2:0, 4:2:2;
+// interleaved: width) or width (4:4:4) samples.  Pointers address the first logical row, strides are bytes and may be
+// negative; addresses and strides are multiples of the sample size (1, 2 or 4 bytes), any alignment beyond that.
+struct YuvPlanes {
+	std::uint8_t *y = nullptr, *u = nullptr, *v = nullptr;
+	std::ptrdiff_t yStride = 0, uStride = 0, vStride = 0;
+};
+// The three launches of the colour staging, for any format of the table (std::invalid_argument for another value).  Each
+// chooses the kernel and, from `colorspace` (0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full;
+// std::invalid_argument otherwise), the coefficients; an RGB format's `colorspace` is not read.  4:2:0 needs an even
+// width and height, 4:2:2 an even width.  The definitions are tests/yuv_reference.py, yuv10_reference.py (10-bit words;
+// the 16-bit sample P of an encode), yuv_sampled_reference.py (4:2:2 / 4:4:4: chroma co-sited with the even luma columns)
+// and rgb_reference.py (inputs reduced to the u8 frame the network consumes; 8-bit outputs permute the frame's bytes).
+// planes -> BGRX rows (X = 0)
+void launchDecodeFrame(int format, int colorspace, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride,
+    int width, int height, hipStream_t stream);
+// BGRX rows (X ignored; any alignment, signed stride) -> planes; the deep formats: P = 257 u8, u8 / 255, u8
+void launchEncodeFrame(int format, int colorspace, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst,
+    int width, int height, hipStream_t stream);
+// the dense f16 state [height][width][4] (B, G, R, 0; 16-byte aligned) -> planes, the deep formats only
+// (std::invalid_argument for another): P = floor((s + 0.5) * 65536), saturated
+void launchEncodeState(int format, int colorspace, const void *state, const YuvPlanes &dst, int width, int height,
+    hipStream_t stream);
+
+// The inputs of a look-ahead pass (Engine::processFrames) that are not BGRX, decoded in one launch: item i of `count` (1 ..
+// kFlowBatchMax) = format, planes, coefficients and BGRX destination of one frame; all frames width x height.  Per item
+// the bytes of launchDecodeFrame.  YuvDecodeItems is the launch's by-value argument.
+struct YuvDecode {  // x 65536, rounded half away from zero (tests/yuv_reference.py); oy = luma offset (0 full range)
+	int ky, krv, kbu, kgu, kgv, oy;
+};
 struct YuvDecodeItem {
 	YuvPlanes src;
-	YuvDecode k;
+	YuvDecode k;  // (an RGB item: not read)
 	std::uint8_t *dst = nullptr;
 	std::ptrdiff_t dstStride = 0;
-	int nv12 = 0;
-	int deep = 0;  // 0: an 8-bit item (I420 / NV12 by `nv12`); 1: P010, 2: I010 (k = yuvDecodeCoefficients10)
-	int sampled = 0;  // 0: a 4:2:0 item, as above; else its YuvSampled value (the bytes of launchYuvSampledToBgrx) or its
-	                  // RgbFormat value (the bytes of launchRgbToBgrx; k is not read)
+	int format = 0;
 };
 struct YuvDecodeItems {
 	YuvDecodeItem item[kFlowBatchMax];
 };
+static_assert(sizeof(YuvDecodeItems) <= 832, "the by-value argument of the items kernel must not grow");
+// the item of one frame, coefficients included (the checks of launchDecodeFrame on format and colour space)
+YuvDecodeItem yuvDecodeItem(int format, int colorspace, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride);
+// (a per-row item in the pass: strips x height threads per item, of which a 4:2:0 item's upper half returns at once)
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream);
-
-// ---- 10-bit 4:2:0 (P010: Y, interleaved UV, value << 6; I010: Y, U, V, value in the low bits) <-> BGRX ----------------
-// YuvPlanes as above with 16-bit little-endian samples: strides stay bytes, pointers and strides multiples of 2.
-// tests/yuv10_reference.py is the definition.  Decode coefficients x 65536 for 10-bit samples -> u8 (oy 64 | 0); encode
-// coefficients x 2^32 / 65535, applied to a 16-bit sample P per channel (each below 2^26; products summed in 64 bits).
-struct YuvEncode10 {
-	int yr, yg, yb, ur, ug, ub, vr, vg, vb, oy;
-};
-YuvDecode yuvDecodeCoefficients10(int colorspace);
-YuvEncode10 yuvEncodeCoefficients10(int colorspace);
-void launchYuv420p10ToBgrx(bool p010, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
-    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
-// P = floor((s + 0.5) * 65536), saturated, of the dense f16 state [height][width][4] (B, G, R, 0; 16-byte aligned)
-void launchStateToYuv420p10(bool p010, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
-    int height, hipStream_t stream);
-// P = 257 u8 of a BGRX frame (any alignment, signed stride)
-void launchBgrxToYuv420p10(bool p010, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream);
-
-// ---- 4:2:2 (YUY2 / UYVY packed, I422, P210, I210) and 4:4:4 (I444, I410) <-> BGRX ------------------------------------------
-// `format`: a YuvSampled value (std::invalid_argument for one the kernel does not take).  Planes as YuvPlanes: a packed
-// frame is plane y alone, rows of 2 width bytes; chroma planes have `height` rows of width / 2 (4:2:2; P210: width
-// interleaved) or width (4:4:4) samples.  4:2:2 needs an even width; any height, and for 4:4:4 any width.  Chroma is
-// co-sited with the even luma columns; tests/yuv_sampled_reference.py is the definition.  Coefficients: those of the
-// 4:2:0 launches of the same depth.
-void launchYuvSampledToBgrx(int format, const YuvPlanes &src, const YuvDecode &k, std::uint8_t *dst,
-    std::ptrdiff_t dstStride, int width, int height, hipStream_t stream);
-void launchBgrxToYuvSampled(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream);  // the 8-bit formats
-void launchStateToYuvSampled10(int format, const void *state, const YuvEncode10 &k, const YuvPlanes &dst, int width,
-    int height, hipStream_t stream);  // the 10-bit formats, P as launchStateToYuv420p10
-void launchBgrxToYuvSampled10(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvEncode10 &k,
-    const YuvPlanes &dst, int width, int height, hipStream_t stream);  // the 10-bit formats, P = 257 u8
-
-// ---- RGB formats (BGR24, RGB24, RGBX, BGRX64, planar RGBP8 / 10 / 16 / H / S, BGR96F) <-> BGRX ----------------------------
-// `format`: an RgbFormat value (std::invalid_argument for one the kernel does not take).  Planes as YuvPlanes: a packed
-// frame is plane y alone, rows of 3, 4, 8 or 12 x width bytes; a planar frame is y, u, v = R, G, B, rows of width samples.
-// Any width and height, signed strides; addresses and strides multiples of the sample size (1, 2 or 4 bytes).
-// tests/rgb_reference.py is the definition: inputs are reduced to the u8 frame the network consumes (rounded to nearest);
-// 8-bit outputs are a permutation of the frame's bytes, deep outputs come from the f16 state or from the u8 frame.
-void launchRgbToBgrx(int format, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride, int width, int height,
-    hipStream_t stream);
-void launchBgrxToRgb(int format, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst, int width,
-    int height, hipStream_t stream);  // every format; deep ones: P = 257 u8, u8 / 255, u8
-void launchStateToRgb(int format, const void *state, const YuvPlanes &dst, int width, int height,
-    hipStream_t stream);  // the deep formats, from the dense f16 state as launchStateToYuv420p10 reads it
 
 // ---- source stage (source_kernels.hip; docs/source_stage.md): sources of any size, masked pass-through ---------------
 // One axis of the triangle scaler, N source samples -> M destination samples, in integers (buildScaleAxis is the

@@ -69,6 +69,63 @@ def test_items_kernel_equals_the_numpy_definition_and_the_single_frame_kernel(mi
                     p.check(d)
 
 
+def run_single(fmt, cs, w, h, out, planes):
+    """The format's single-kernel hook, op 0: planes -> BGRX."""
+    lib = R.load_library(True)
+    ptrs = (C.c_void_p * 3)(*([p.ptr for p in planes] + [None] * (3 - len(planes))))
+    strides = (C.c_ssize_t * 3)(*([p.stride for p in planes] + [0] * (3 - len(planes))))
+    if fmt >= R.FMT_BGR24:
+        rc = lib.ju_debug_rgb(0, fmt, w, h, out.ptr, out.stride, ptrs, strides)
+    else:
+        hook = (lib.ju_debug_yuv if fmt in FMTS else lib.ju_debug_yuv10 if fmt in (R.FMT_P010, R.FMT_I010)
+                else lib.ju_debug_yuv_sampled)
+        rc = hook(0, fmt, cs, w, h, out.ptr, out.stride, ptrs, strides)
+    assert rc == 0, lib.ju_last_error()
+
+
+# all 21 formats in three launches, each mixing 4:2:0, 4:2:2 / 4:4:4 and RGB items and both sample depths; then NV12 alone
+ITEM_LAUNCHES = [
+    (R.FMT_I420, R.FMT_YUY2, R.FMT_BGR24, R.FMT_P010, R.FMT_I444, R.FMT_RGBP10, R.FMT_P210, R.FMT_BGR96F),
+    (R.FMT_NV12, R.FMT_UYVY, R.FMT_RGB24, R.FMT_I410, R.FMT_BGRX64, R.FMT_RGBPS, R.FMT_RGBP8, R.FMT_RGBX),
+    (R.FMT_I010, R.FMT_I422, R.FMT_RGBP16, R.FMT_I210, R.FMT_RGBPH),
+    (R.FMT_NV12,)]
+
+
+def test_items_kernel_dispatches_every_format_to_its_single_frame_strip():
+    """Every format of the table as an item: its BGRX bytes equal those of the format's own single-kernel hook on the same
+    planes (which the format's own suite holds to its numpy definition), guards and inputs intact.  34 x 6: two whole
+    strips and a two-pixel tail, three row pairs, one workgroup, the upper half of a 4:2:0 item's threads returning.
+    276 x 32: 18 strips with a four-pixel tail -- 576 threads, three workgroups per per-row item, of which a 4:2:0 item
+    fills two and leaves the third idle.  The last launch is 4:2:0 alone: strips x H / 2 threads.  Random bytes in every
+    plane (so junk in the bits and lanes a format ignores, and every kind of float), the four colour spaces in turn for
+    the YUV items, a value outside them for the RGB items, which do not read it."""
+    import test_gpu_rgb as G                                    # (imports this module: not at the top)
+    assert sorted(f for launch in ITEM_LAUNCHES[:3] for f in launch) == sorted(
+        list(G.NEW) + list(G.YS.NEW) + [I420, NV12, R.FMT_P010, R.FMT_I010])
+    rng = np.random.default_rng(2026)
+    for (w, h) in [(34, 6), (276, 32)]:
+        for n, launch in enumerate(ITEM_LAUNCHES):
+            fmts, css, outs, singles, srcs, held = list(launch), [], [], [], [], []
+            for i, fmt in enumerate(launch):
+                blank = G.blank(fmt, h, w)
+                lay = G.layout(G.LAYOUT_NAMES[(i + n) % len(G.LAYOUT_NAMES)], blank[0].dtype.itemsize)
+                css.append(9 + i if fmt >= R.FMT_BGR24 else CSS[(i + n) % len(CSS)])
+                held.append([rng.integers(0, 256, (p.shape[0], p[0].nbytes), dtype=np.uint8) for p in blank])
+                srcs.append([DevPlane(p, **lay) for p in held[i]])
+                mk = lambda: DevPlane(np.zeros((h, w, 4), np.uint8), pad=lay["pad"] * 4, offset=lay["offset"], flip=lay["flip"])
+                outs.append(mk())
+                singles.append(mk())
+            run_items(fmts, css, w, h, outs, srcs)
+            for i, fmt in enumerate(launch):
+                run_single(fmt, css[i], w, h, singles[i], srcs[i])
+                want = singles[i]._rows(singles[i].buf.cpu().numpy()).reshape(h, w, 4)
+                assert want[..., 3].max() == 0 and want.any(), (fmt, w, h)
+                singles[i].check(want)
+                outs[i].check(want)
+                for p, d in zip(srcs[i], held[i]):
+                    p.check(d)
+
+
 # ---- frames, buffers and the twin -----------------------------------------------------------------------------------
 def source(frame_bgrx, fmt, cs):
     """The planes of one input frame of the clip in the given format."""
