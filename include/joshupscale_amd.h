@@ -351,12 +351,39 @@ JU_API int ju_reset(ju_runtime *runtime);
  * ("lookahead_frames" / "group_frames" do not count them, "source_stage_frames" does), ju_prepare_frames /
  * ju_prepare_batch capture nothing.  JU_LOC_GRAPHICS_RESOURCE inputs are refused while a source size is set (outputs,
  * and inputs under a mask alone, are taken).  Turning both off restores the other paths.
- * Not provided: scaled or masked frames inside look-ahead or group passes; a scaler on the output side; filters other
- * than the triangle; OBS's own OBS_EFFECT_BILINEAR_LOWRES arithmetic (it is not in the reference tree). */
+ * Not provided: scaled or masked frames inside look-ahead or group passes; filters other than the triangle; OBS's own
+ * OBS_EFFECT_BILINEAR_LOWRES arithmetic (it is not in the reference tree).  The scaler on the output side is
+ * ju_set_output_size, below. */
 enum { JU_SCALE_TRIANGLE = 0 };
 JU_API int ju_set_source_size(ju_runtime *runtime, size_t src_width, size_t src_height, int filter);
 JU_API int ju_get_source_size(const ju_runtime *runtime, size_t *src_width, size_t *src_height);
 JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
+
+/* ---- an output size: the upscaled frame at any size (docs/output_stage.md) ----------------------------------------------
+ * The models hand their frame back at exactly 4 x their input; the reference's OBS caller resizes it with OBS's canvas
+ * scaling, behind processImage, on the GPU.  A transcoder, a stream server or an AviSynth script has no graphics API to
+ * do that with, so the runtime scales the frame itself.  Opt-in and per runtime; with no output size set every entry
+ * point behaves byte for byte as without it.  ju_reset keeps the setting.
+ *
+ * ju_set_output_size: output frames are width x height from now on -- on EVERY entry point, exactly that size (the YUV
+ * parity rules apply to it), anything else is JU_ERR_INVALID_ARGUMENT before anything is launched.  The frame is scaled
+ * behind the network and the mask blend by the source stage's filter with the output axes' tables:
+ * out = (sum qy qx v + 2^23) >> 24, an output of the model's size passing through unchanged.
+ *   8-bit formats, and every format while a mask is set or "hbd_from_state" is 0: v is the 8-bit BGRX frame (after the
+ *   blend); deep formats are then encoded from the scaled 8-bit frame (257 x u8), as without an output size.
+ *   Deep formats otherwise (JU_FMT_P010, I010, P210, I210, I410, BGRX64, RGBP10, RGBP16, RGBPH, RGBPS, BGR96F): v is the
+ *   state's 16-bit sample P = floor((s + 0.5) * 65536), saturated; the scaled P is encoded -- 10-bit YUV as from the state,
+ *   16-bit words P, 10-bit words P >> 6, unit floats f32(P) / 65535 (RGBPH: that as f16), BGR96F f32(P) / 257.
+ * (0, 0) turns it off.  filter: JU_SCALE_TRIANGLE, the only value.  Limits (JU_ERR_INVALID_ARGUMENT): each axis 2 .. 16384
+ * and within a factor of 16 of the model's output axis, either way.  ju_get_size keeps reporting the model's sizes;
+ * ju_get_output_size reports (0, 0) while off.  Recurrent state, frame history and flow inputs are the unscaled run's.
+ *
+ * While it is set frames are routed as for a source size: one by one through the staging buffers, no direct device path,
+ * no look-ahead or group pass ("source_stage_frames" counts them), ju_prepare_* capture nothing.  A JU_LOC_DEVICE BGRX
+ * output is written in place, any alignment and signed stride.  JU_LOC_GRAPHICS_RESOURCE outputs are refused.
+ * ju_get_stat: "output_scaled" (1 / 0). */
+JU_API int ju_set_output_size(ju_runtime *runtime, size_t width, size_t height, int filter);
+JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height);
 
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing
@@ -418,7 +445,8 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * "lookahead_frames" (frames that went through look-ahead passes; of them "lookahead_host_frames" with a host side,
  * "lookahead_yuv_frames" with a YUV side, 8- or 10-bit),
  * "source_scaled" / "source_mask" (1 while ju_set_source_size / ju_set_source_mask is in effect), "source_stage_frames"
- * (frames that went through the source stage),
+ * (frames that went through the source stage or the output stage), "output_scaled" (1 while ju_set_output_size is in
+ * effect),
  * "hbd_from_state" (1: this runtime encodes JU_FMT_P010 / JU_FMT_I010 outputs from its f16 state; 0: from the 8-bit
  * frame -- normalize_brightness and output_flow models),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,

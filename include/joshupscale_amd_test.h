@@ -106,6 +106,17 @@ JU_API int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_w
     ptrdiff_t src_stride, size_t src_width, size_t src_height, const void *mask, ptrdiff_t mask_stride, size_t mask_width,
     size_t mask_height);
 
+/* The output stage's pieces alone (docs/output_stage.md; tests/output_reference.py), on the current device (synchronous).
+ * op 0: scale_state_kernel -- `src`, the dense f16 tensor [src_height][src_width][4] (16-byte aligned), -> `dst`, the dense
+ * u16 frame [dst_height][dst_width][4] (8-byte aligned), tables built as ju_set_output_size builds them; format,
+ * colorspace, planes and strides are ignored.  op 1: the encode of one deep format from the dense u16 frame `src` of
+ * dst_width x dst_height into planes / strides (bytes, multiples of the sample size, any sign), as ju_debug_rgb takes
+ * them; `dst` and the source size are ignored; a format that is not deep is JU_ERR_INVALID_ARGUMENT.  op 2: no device and
+ * no buffers -- only the limits ju_set_output_size applies to an output size of dst_width x dst_height for a model output
+ * of src_width x src_height and the filter passed in `format`, with its message (JU_ERR_INVALID_ARGUMENT) or JU_OK. */
+JU_API int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_height, const void *src, size_t src_width,
+    size_t src_height, int format, int colorspace, void *const planes[3], const ptrdiff_t strides[3]);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

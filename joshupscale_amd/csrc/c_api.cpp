@@ -311,6 +311,14 @@ int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask) {
 	});
 }
 
+int ju_set_output_size(ju_runtime *runtime, size_t width, size_t height, int filter) {
+	return guarded([&] { engineOf(runtime).setOutputSize(width, height, filter); });
+}
+
+int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height) {
+	return guarded([&] { engineOf(const_cast<ju_runtime *>(runtime)).outputSize(width, height); });
+}
+
 int ju_reset(ju_runtime *runtime) {
 	return guarded([&] { engineOf(runtime).reset(); });
 }
@@ -575,6 +583,61 @@ int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_width, s
 		ju::launchMaskBlend(static_cast<std::uint8_t *>(dst), dst_stride, dw, dh, static_cast<const std::uint8_t *>(src),
 		    src_stride, sw, sh, static_cast<const std::uint8_t *>(mask), mask_stride, static_cast<int>(mask_width),
 		    static_cast<int>(mask_height), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_height, const void *src, size_t src_width,
+    size_t src_height, int format, int colorspace, void *const planes[3], const ptrdiff_t strides[3]) {
+	return guarded([&] {
+		if (op == 2) {  // the limits of ju_set_output_size alone: no device
+			const std::string problem = ju::outputSizeProblem(dst_width, dst_height, src_width, src_height, format);
+			if (!problem.empty()) throw std::invalid_argument("ju_set_output_size: " + problem);
+			return;
+		}
+		if (op != 0 && op != 1) throw std::invalid_argument("ju_debug_output: op must be 0, 1 or 2");
+		constexpr size_t kMost = 1u << 15;
+		if (src == nullptr || dst_width < 1 || dst_height < 1 || dst_width > kMost || dst_height > kMost) {
+			throw std::invalid_argument("ju_debug_output: null buffer or a size outside 1 .. 32768");
+		}
+		const int dw = static_cast<int>(dst_width), dh = static_cast<int>(dst_height);
+		if (op == 0) {
+			if (dst == nullptr || src_width < 1 || src_height < 1 || src_width > kMost || src_height > kMost) {
+				throw std::invalid_argument("ju_debug_output: null buffer or a size outside 1 .. 32768");
+			}
+			const int sw = static_cast<int>(src_width), sh = static_cast<int>(src_height);
+			const ju::ScaleAxisHost x = ju::buildScaleAxis(sw, dw), y = ju::buildScaleAxis(sh, dh);
+			auto upload = [](const ju::ScaleAxisHost &a, ju::DeviceBuffer *start, ju::DeviceBuffer *taps) {
+				*start = ju::DeviceBuffer(a.start.size() * sizeof(int));
+				start->upload(a.start.data(), a.start.size() * sizeof(int));
+				*taps = ju::DeviceBuffer(a.taps.size() * sizeof(std::uint16_t));
+				taps->upload(a.taps.data(), a.taps.size() * sizeof(std::uint16_t));
+			};
+			ju::DeviceBuffer xs, xt, ys, yt;
+			upload(x, &xs, &xt);
+			upload(y, &ys, &yt);
+			ju::launchScaleState(src, sw, sh, static_cast<std::uint16_t *>(dst), dw, dh, {xs.as<int>(), xt.as<std::uint16_t>()},
+			    {ys.as<int>(), yt.as<std::uint16_t>()}, ju::scaleSpan(x), nullptr);
+			JU_HIP(hipStreamSynchronize(nullptr));
+			return;
+		}
+		const ju::YuvFormatInfo *info = ju::yuvFormatInfo(format);
+		if (info == nullptr || !info->deep()) {
+			throw std::invalid_argument("ju_debug_output: op 1 takes the deep formats only (10-bit YUV; RGB of more than 8 bits)");
+		}
+		if (reinterpret_cast<std::uintptr_t>(src) % 8) throw std::invalid_argument("ju_debug_output: the u16 frame must be 8-byte aligned");
+		const ConversionHook hook{"ju_debug_output", "a deep", [](Info f) { return f.deep(); }, 2, false};
+		// (op 1 of the hook's checks: sizes, parity, null planes, sample alignment)
+		const ju::YuvPlanes p = hook.planes(*info, 1, dst_width, dst_height, src, static_cast<ptrdiff_t>(8 * dst_width), planes, strides);
+		for (int k = 0; k < info->planes; ++k) {  // strides of at least the plane's own row: a chroma row may be half a luma row
+			const size_t b = static_cast<size_t>(info->sampleBytes);
+			const size_t cw = info->sampling == 444 ? dst_width : dst_width / 2;
+			const size_t bytes = info->planes == 1 ? static_cast<size_t>(info->pixelBytes) * dst_width
+			    : (k == 0 || info->rgb()) ? dst_width * b : (info->planes == 2 ? 2 * cw : cw) * b;
+			const auto row = static_cast<ptrdiff_t>(bytes);
+			if (strides[k] > -row && strides[k] < row) hook.refuse("|stride| smaller than a row");
+		}
+		ju::launchEncodeFrame16(format, colorspace, static_cast<const std::uint16_t *>(src), p, dw, dh, nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

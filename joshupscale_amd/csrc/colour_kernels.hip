@@ -566,6 +566,54 @@ struct Bgrx8Source {
 	}
 };
 
+// From a dense u16 BGRX frame [H][W][4] (B, G, R, unused; 8-byte aligned: the output stage's scaled 16-bit frame,
+// docs/output_stage.md): the sample is P itself.  Rows of an odd width start at 8 bytes, as the state's.
+struct Bgrx16Source {
+	using Pixel = uint2;  // x = P_B | P_G << 16, y = P_R | unused << 16
+	const std::uint16_t *frame;
+	static constexpr int kScale = 1;
+	__device__ static int b(Pixel p) { return static_cast<int>(p.x & 0xffff); }
+	__device__ static int g(Pixel p) { return static_cast<int>(p.x >> 16); }
+	__device__ static int r(Pixel p) { return static_cast<int>(p.y & 0xffff); }
+	__device__ void load(int y, int x0, int W, bool full, Pixel (&px)[17]) const {
+		const std::uint16_t *row = frame + static_cast<std::size_t>(y) * W * 4;
+		px[0] = *reinterpret_cast<const uint2 *>(row + 4 * max(x0 - 1, 0));
+		Raw raw[16];
+		loadRaw(y, x0, W, full, raw);
+#pragma unroll
+		for (int p = 0; p < 16; ++p) px[1 + p] = raw[p];
+	}
+	// For an RGB encode: W16 = P, W10 = P >> 6; the float kinds f32(P) / 65535 (one correctly rounded division), that as
+	// f16 rounded to nearest even, or f32(P) / 257.
+	using Raw = uint2;
+	__device__ static unsigned rawB(Raw p) { return p.x & 0xffff; }
+	__device__ static unsigned rawG(Raw p) { return p.x >> 16; }
+	__device__ static unsigned rawR(Raw p) { return p.y & 0xffff; }
+	template <int K>
+	__device__ static unsigned deep(unsigned p) {
+		if constexpr (K == kW16) return p;
+		else if constexpr (K == kW10) return p >> 6;
+		else if constexpr (K == kUnit) return __builtin_bit_cast(unsigned, static_cast<float>(p) / 65535.0f);
+		else if constexpr (K == kHalf) {
+			return __builtin_bit_cast(unsigned short, static_cast<f16>(static_cast<float>(p) / 65535.0f));
+		} else return __builtin_bit_cast(unsigned, static_cast<float>(p) / 257.0f);
+	}
+	__device__ void loadRaw(int y, int x0, int W, bool full, Raw (&px)[16]) const {
+		const std::uint16_t *row = frame + static_cast<std::size_t>(y) * W * 4;
+		if (full && alignedTo(row, 16)) {
+#pragma unroll
+			for (int q = 0; q < 8; ++q) {
+				const u32x4 v = *reinterpret_cast<const u32x4 *>(row + 4 * (x0 + 2 * q));
+				px[2 * q] = make_uint2(v.x, v.y);
+				px[2 * q + 1] = make_uint2(v.z, v.w);
+			}
+		} else {
+#pragma unroll
+			for (int p = 0; p < 16; ++p) px[p] = *reinterpret_cast<const uint2 *>(row + 4 * min(x0 + p, W - 1));
+		}
+	}
+};
+
 // P -> Y, U, V (I010) or Y, UV (P010): the strip body of both 10-bit encodes.  Thread = luma rows 2j, 2j + 1 x columns
 // x0 .. x0 + 15 -> 2 x 32 B of Y and 16 B of U and of V (32 B of UV).  64-bit accumulators: the products reach 2^45.
 template <bool P010, typename Source>
@@ -635,6 +683,12 @@ template <bool P010>
 __global__ __launch_bounds__(256) void state_to_yuv420p10_kernel(const f16 *__restrict__ state, YuvEncode10 k,
     YuvPlanes dst, int W, int H) {
 	toYuv420p10Strip<P010>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+template <bool P010>
+__global__ __launch_bounds__(256) void frame16_to_yuv420p10_kernel(const std::uint16_t *__restrict__ frame, YuvEncode10 k,
+    YuvPlanes dst, int W, int H) {
+	toYuv420p10Strip<P010>(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // (214 VGPRs: the scheduler hoists the byte extractions of a row over its 64-bit sums; held to 128 registers with
@@ -972,6 +1026,12 @@ __global__ __launch_bounds__(256) void state_to_yuv_sampled10_kernel(const f16 *
 }
 
 template <int F>
+__global__ __launch_bounds__(256) void frame16_to_yuv_sampled10_kernel(const std::uint16_t *__restrict__ frame,
+    YuvEncode10 k, YuvPlanes dst, int W, int H) {
+	toYuvSampled10Strip<F>(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+template <int F>
 __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled10_kernel(const std::uint8_t *__restrict__ src,
     std::ptrdiff_t srcStride, YuvEncode10 k, YuvPlanes dst, int W, int H) {
 	toYuvSampled10Strip<F>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
@@ -1215,6 +1275,12 @@ __global__ __launch_bounds__(256) void state_to_rgb_kernel(const f16 *__restrict
 	toRgbStrip<F>(StateSource{state}, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
+template <int F>
+__global__ __launch_bounds__(256) void frame16_to_rgb_kernel(const std::uint16_t *__restrict__ frame, YuvPlanes dst, int W,
+    int H) {
+	toRgbStrip<F>(Bgrx16Source{frame}, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
 // The formats each kernel family instantiates, ONE list per family: the launchers below and the items kernel reach a
 // format's kernel or strip body through forFormat alone.  4:2:0: <NV12> / <P010> = the list's second format; the encodes of
 // the other two families pick the 8-bit or the deep kernel from the format's traits.
@@ -1420,6 +1486,24 @@ void launchEncodeState(int format, int colorspace, const void *state, const YuvP
 		else noKernel("encode from the state", format);
 	});
 	if (!done) noKernel("encode from the state", format);
+}
+
+void launchEncodeFrame16(int format, int colorspace, const std::uint16_t *frame, const YuvPlanes &dst, int width, int height,
+    hipStream_t stream) {
+	const StripLaunch run{formatInfo(format), width, height, stream};
+	const bool done = forFormat(Yuv420p10{}, format, [&](auto f) {
+		run("frame16_to_yuv420p10", frame16_to_yuv420p10_kernel<f() == kP010>, frame, encodeCoefficients10(colorspace), dst);
+	}) || forFormat(Sampled{}, format, [&](auto f) {
+		if constexpr (SampledTraits<f()>::kDeep) {
+			run("frame16_to_yuv_sampled10", frame16_to_yuv_sampled10_kernel<f()>, frame, encodeCoefficients10(colorspace), dst);
+		} else {
+			noKernel("encode from a 16-bit frame", format);
+		}
+	}) || forFormat(Rgb{}, format, [&](auto f) {
+		if constexpr (RgbTraits<f()>::kKind != kU8) run("frame16_to_rgb", frame16_to_rgb_kernel<f()>, frame, dst);
+		else noKernel("encode from a 16-bit frame", format);
+	});
+	if (!done) noKernel("encode from a 16-bit frame", format);
 }
 
 }  // namespace ju

@@ -1436,8 +1436,8 @@ void Engine::stageIn(const Frame &in) {
 	}
 }
 
-void Engine::stageOut(const Frame &out) {
-	const FrameSize fs = frameSize();
+void Engine::stageOut(const Frame &out, std::size_t width, std::size_t height, const std::uint8_t *src, std::uint8_t *raw) {
+	const FrameSize fs{0, 0, width, height};  // (the frame's own size: the model's output, or the output size set)
 	if (out.location == Location::GraphicsResource) {  // cuda_convert.cc.cu:419-436
 		MappedResource m(out.ptr, m_Stream);
 		if (!m.array.fourBytes || m.array.width != fs.outputWidth || m.array.height != fs.outputHeight ||
@@ -1445,8 +1445,7 @@ void Engine::stageOut(const Frame &out) {
 			throw std::invalid_argument("processImage: output texture must be " + std::to_string(fs.outputWidth) + "x" +
 			                            std::to_string(fs.outputHeight) + " with four 8-bit channels");
 		}
-		m.h->backend->copyToArray(m.array, m_OutStage.get(), fs.outputWidth * 4, fs.outputWidth * 4, fs.outputHeight,
-		    m_Stream);
+		m.h->backend->copyToArray(m.array, src, fs.outputWidth * 4, fs.outputWidth * 4, fs.outputHeight, m_Stream);
 		return;
 	}
 	if (out.ptr == nullptr || out.width != fs.outputWidth || out.height != fs.outputHeight) {
@@ -1457,7 +1456,6 @@ void Engine::stageOut(const Frame &out) {
 	const std::size_t rowBytes = fs.outputWidth * 4;
 	const std::size_t rows = fs.outputHeight;
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	const auto *src = m_OutStage.as<std::uint8_t>();
 	auto *dst = static_cast<std::uint8_t *>(out.ptr);
 	if (out.stride > -plain && out.stride < plain) {
 		throw std::invalid_argument("processImage: |stride| smaller than a row");
@@ -1470,7 +1468,6 @@ void Engine::stageOut(const Frame &out) {
 			JU_HIP(hipMemcpy2DAsync(dst, static_cast<std::size_t>(out.stride), src, rowBytes,
 			    rowBytes, rows, hipMemcpyDeviceToHost, m_Stream));
 		} else {
-			auto *raw = m_RawStage.as<std::uint8_t>();
 			launchCopyRows(src, plain, raw + (rows - 1) * rowBytes, -plain, rowBytes, rows, m_Stream);
 			std::uint8_t *lowest = dst + static_cast<std::ptrdiff_t>(rows - 1) * out.stride;
 			JU_HIP(hipMemcpy2DAsync(lowest, static_cast<std::size_t>(-out.stride), raw, rowBytes,
@@ -1579,12 +1576,18 @@ std::size_t Engine::yuvStageBytes(std::size_t w, std::size_t h) {
 void Engine::checkFrame(const AnyFrame &f, bool input) const {
 	const FrameSize fs = frameSize();
 	const bool scaled = input && m_SrcW != 0;  // (input frames are the source's size while one is set)
-	const std::size_t w = scaled ? m_SrcW : (input ? fs.inputWidth : fs.outputWidth);
-	const std::size_t h = scaled ? m_SrcH : (input ? fs.inputHeight : fs.outputHeight);
+	const bool resized = !input && m_OutW != 0;  // (and output frames the output size)
+	const std::size_t w = scaled ? m_SrcW : (resized ? m_OutW : (input ? fs.inputWidth : fs.outputWidth));
+	const std::size_t h = scaled ? m_SrcH : (resized ? m_OutH : (input ? fs.inputHeight : fs.outputHeight));
 	const std::string side = input ? "input" : "output";
-	const std::string size = std::to_string(w) + "x" + std::to_string(h) + (scaled ? " (the source size set)" : "");
+	const std::string size = std::to_string(w) + "x" + std::to_string(h) +
+	                         (scaled ? " (the source size set)" : (resized ? " (the output size set)" : ""));
 	if (!f.yuv) {
 		const Frame &b = f.bgrx;
+		if (resized && b.location == Location::GraphicsResource) {
+			throw std::invalid_argument("processFrame: graphics resources cannot be outputs while an output size is set "
+			                            "(the scaler writes host or device memory)");
+		}
 		if (scaled && b.location == Location::GraphicsResource) {
 			throw std::invalid_argument("processFrame: graphics resources cannot be inputs while a source size is set "
 			                            "(the scaler reads host or device memory)");
@@ -1656,30 +1659,34 @@ void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &plan
 	launchDecodeFrame(fmt(format), colorspace, planes, bgrx, bgrxStride, w, h, m_Stream);
 }
 
+bool Engine::deepFromState(PixelFormat format) const {
+	// (a mask: the blended frame exists in 8 bits only)
+	return m_HbdFromState && m_MaskW == 0 && formatInfo(format).deep();
+}
+
 // one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit YUV or
 // a deep RGB format of a runtime whose state is the frame in float (m_HbdFromState), the f16 state that frame left -- -> planes
-void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, const std::uint8_t *bgrx,
-    std::ptrdiff_t bgrxStride, const void *state) {
-	const FrameSize fs = frameSize();
-	const int w = static_cast<int>(fs.outputWidth), h = static_cast<int>(fs.outputHeight);
-	// (a mask: the blended frame exists in 8 bits only)
-	if (m_HbdFromState && m_MaskW == 0 && formatInfo(format).deep()) {
-		launchEncodeState(fmt(format), colorspace, state, planes, w, h, m_Stream);
-	} else {
+void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::size_t width, std::size_t height,
+    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16) {
+	const int w = static_cast<int>(width), h = static_cast<int>(height);
+	if (!deepFromState(format)) {
 		launchEncodeFrame(fmt(format), colorspace, bgrx, bgrxStride, planes, w, h, m_Stream);
+	} else if (frame16 != nullptr) {  // (the output stage: the state's samples, scaled)
+		launchEncodeFrame16(fmt(format), colorspace, frame16, planes, w, h, m_Stream);
+	} else {
+		launchEncodeState(fmt(format), colorspace, state, planes, w, h, m_Stream);
 	}
 }
 
-void Engine::stageOutYuv(const YuvFrame &out) {
-	const FrameSize fs = frameSize();
-	const std::size_t w = fs.outputWidth;
+// the frame of out.width x out.height -- its dense BGRX rows, or for deepFromState formats the state or the 16-bit frame
+void Engine::stageOutYuv(const YuvFrame &out, const std::uint8_t *bgrx, const void *state, const std::uint16_t *frame16,
+    std::uint8_t *stage) {
 	const bool host = out.location == Location::Host;
 	// (a host frame: the kernel writes the staging buffer in the caller's row order, copied out below)
-	const YuvPlanes pl = host ? stagedPlanes(out, m_YuvOutStage.as<std::uint8_t>()) : callerPlanes(out);
-	// (called behind the frame's program and before the flip: the state this frame wrote is the binding set's output)
-	encodeYuv(out.format, out.colorspace, pl, m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4),
-	    m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get());
-	if (host) copyPlanes(out, m_YuvOutStage.as<std::uint8_t>(), false, m_Stream);
+	const YuvPlanes pl = host ? stagedPlanes(out, stage) : callerPlanes(out);
+	encodeYuv(out.format, out.colorspace, pl, out.width, out.height, bgrx, static_cast<std::ptrdiff_t>(out.width * 4), state,
+	    frame16);
+	if (host) copyPlanes(out, stage, false, m_Stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1689,6 +1696,22 @@ void Engine::stageOutYuv(const YuvFrame &out) {
 // submitFrame: scale_bgrx_kernel fills m_InStage from the source frame, mask_blend_kernel rewrites m_OutStage.  Both
 // settings are per runtime and opt-in; neither touches a captured graph, the state or the frame history.
 // ---------------------------------------------------------------------------------------------------------------
+namespace {
+// one device buffer per axis of the scaler: the start indices, then the taps
+DeviceBuffer uploadScaleAxis(const ScaleAxisHost &a) {
+	const std::size_t startBytes = a.start.size() * sizeof(int), tapBytes = a.taps.size() * sizeof(std::uint16_t);
+	std::vector<unsigned char> host(startBytes + tapBytes);
+	std::memcpy(host.data(), a.start.data(), startBytes);
+	std::memcpy(host.data() + startBytes, a.taps.data(), tapBytes);
+	DeviceBuffer buf(host.size());
+	buf.upload(host.data(), host.size());
+	return buf;
+}
+ScaleAxisDev scaleAxisDev(const DeviceBuffer &buf, const ScaleAxisHost &a) {
+	return {buf.as<int>(), reinterpret_cast<const std::uint16_t *>(buf.as<int>() + a.start.size())};
+}
+}  // namespace
+
 void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	DeviceGuard g(m_Device);
 	if (filter != 0) {
@@ -1709,25 +1732,15 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	if (!problem.empty()) throw std::invalid_argument("ju_set_source_size: " + problem);
 	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(width), static_cast<int>(fs.inputWidth));
 	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(height), static_cast<int>(fs.inputHeight));
-	// one buffer per axis: the start indices, then the taps
-	auto uploadAxis = [](const ScaleAxisHost &a) {
-		const std::size_t startBytes = a.start.size() * sizeof(int), tapBytes = a.taps.size() * sizeof(std::uint16_t);
-		std::vector<unsigned char> host(startBytes + tapBytes);
-		std::memcpy(host.data(), a.start.data(), startBytes);
-		std::memcpy(host.data() + startBytes, a.taps.data(), tapBytes);
-		DeviceBuffer buf(host.size());
-		buf.upload(host.data(), host.size());
-		return buf;
-	};
-	DeviceBuffer bx = uploadAxis(x), by = uploadAxis(y);
+	DeviceBuffer bx = uploadScaleAxis(x), by = uploadScaleAxis(y);
 	DeviceBuffer stage(width * height * 4), yuvStage(yuvStageBytes(width, height));
 	m_Stream.synchronize();
 	m_ScaleX = std::move(bx);
 	m_ScaleY = std::move(by);
 	m_SrcStage = std::move(stage);
 	m_SrcYuvStage = std::move(yuvStage);
-	m_ScaleXDev = {m_ScaleX.as<int>(), reinterpret_cast<const std::uint16_t *>(m_ScaleX.as<int>() + x.start.size())};
-	m_ScaleYDev = {m_ScaleY.as<int>(), reinterpret_cast<const std::uint16_t *>(m_ScaleY.as<int>() + y.start.size())};
+	m_ScaleXDev = scaleAxisDev(m_ScaleX, x);
+	m_ScaleYDev = scaleAxisDev(m_ScaleY, y);
 	m_ScaleSpan = scaleSpan(x);
 	m_SrcW = width;
 	m_SrcH = height;
@@ -1771,6 +1784,82 @@ void Engine::setSourceMask(const Frame *mask) {
 	m_MaskW = mask->width;
 	m_MaskH = mask->height;
 	m_MaskStride = up ? plain : -plain;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Output stage (docs/output_stage.md).  What the reference's OBS caller gets from OBS's canvas scaling behind
+// processImage: the upscaled frame at any size.  Behind the staged graph and the mask blend of submitFrame the frame is
+// scaled by the source stage's triangle filter with the output axes' tables: the 8-bit frame in m_OutStage by
+// scale_bgrx_kernel, or -- for a deep format that is encoded from the state (deepFromState) -- the state's 16-bit samples
+// by scale_state_kernel into m_OutScaled16, which launchEncodeFrame16 encodes.  Nothing of the step itself changes.
+// ---------------------------------------------------------------------------------------------------------------
+void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
+	DeviceGuard g(m_Device);
+	const FrameSize fs = frameSize();
+	const bool off = width == 0 && height == 0;
+	const std::string problem = outputSizeProblem(off ? fs.outputWidth : width, off ? fs.outputHeight : height, fs.outputWidth,
+	    fs.outputHeight, filter);
+	if (!problem.empty()) throw std::invalid_argument("ju_set_output_size: " + problem);
+	if (off) {
+		m_Stream.synchronize();  // (enqueued frames may still read the tables and write the buffers)
+		m_OutW = m_OutH = 0;
+		for (DeviceBuffer *b : {&m_OutScaleX, &m_OutScaleY, &m_OutScaled8, &m_OutScaled16, &m_OutYuvStage, &m_OutRawStage}) {
+			*b = DeviceBuffer();
+		}
+		return;
+	}
+	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(fs.outputWidth), static_cast<int>(width));
+	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(fs.outputHeight), static_cast<int>(height));
+	DeviceBuffer bx = uploadScaleAxis(x), by = uploadScaleAxis(y);
+	DeviceBuffer scaled8(width * height * 4), scaled16(width * height * 8), raw(width * height * 4);
+	DeviceBuffer yuvStage(yuvStageBytes(width, height));
+	m_Stream.synchronize();
+	m_OutScaleX = std::move(bx);
+	m_OutScaleY = std::move(by);
+	m_OutScaled8 = std::move(scaled8);
+	m_OutScaled16 = std::move(scaled16);
+	m_OutRawStage = std::move(raw);
+	m_OutYuvStage = std::move(yuvStage);
+	m_OutScaleXDev = scaleAxisDev(m_OutScaleX, x);
+	m_OutScaleYDev = scaleAxisDev(m_OutScaleY, y);
+	m_OutScaleSpan = scaleSpan(x);
+	m_OutW = width;
+	m_OutH = height;
+}
+
+void Engine::outputSize(std::size_t *width, std::size_t *height) const {
+	if (width) *width = m_OutW;
+	if (height) *height = m_OutH;
+}
+
+// The stage-out of a frame while an output size is set: scale, then copy or encode at output size.  A device BGRX image
+// is written in place (the kernel takes any alignment and signed stride); a host image and YUV planes go through the
+// scaled staging buffers.
+void Engine::stageOutScaled(const AnyFrame &out) {
+	const FrameSize fs = frameSize();
+	const int mw = static_cast<int>(fs.outputWidth), mh = static_cast<int>(fs.outputHeight);
+	const int ow = static_cast<int>(m_OutW), oh = static_cast<int>(m_OutH);
+	auto scale8 = [&](std::uint8_t *dst, std::ptrdiff_t stride) {
+		launchScaleBgrx(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4), mw, mh, dst, stride, ow,
+		    oh, m_OutScaleXDev, m_OutScaleYDev, m_OutScaleSpan, m_Stream);
+	};
+	auto *scaled8 = m_OutScaled8.as<std::uint8_t>();
+	const auto plain = static_cast<std::ptrdiff_t>(m_OutW * 4);
+	if (!out.yuv) {
+		const Frame &b = out.bgrx;
+		if (b.location == Location::Device) return scale8(static_cast<std::uint8_t *>(b.ptr), b.stride);
+		scale8(scaled8, plain);
+		return stageOut(b, m_OutW, m_OutH, scaled8, m_OutRawStage.as<std::uint8_t>());
+	}
+	auto *yuvStage = m_OutYuvStage.as<std::uint8_t>();
+	if (deepFromState(out.planes.format)) {
+		auto *scaled16 = m_OutScaled16.as<std::uint16_t>();
+		launchScaleState(m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get(), mw, mh, scaled16, ow, oh, m_OutScaleXDev,
+		    m_OutScaleYDev, m_OutScaleSpan, m_Stream);
+		return stageOutYuv(out.planes, nullptr, nullptr, scaled16, yuvStage);
+	}
+	scale8(scaled8, plain);
+	stageOutYuv(out.planes, scaled8, nullptr, nullptr, yuvStage);
 }
 
 // The input of a frame while a source size is set, as BGRX rows at source size: a device image is read where it is, a
@@ -2065,8 +2154,9 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 			// (a 10-bit output from the state: THIS frame's link of the chain -- m_BatchState[i], the last frame's
 			// m_State[set ^ 1]; a flow-free pass has one scratch state that the next frame's tail overwrites, so the encode
 			// stays on this stream in front of the next frame's kernels)
-			encodeYuv(m_BatchHost[i].formatOut, m_BatchHost[i].csOut, m_BatchHost[i].encode, m_BatchIO[i].out,
-			    m_BatchIO[i].outStride, m_StateBind[set].out);
+			const FrameSize fs = frameSize();
+			encodeYuv(m_BatchHost[i].formatOut, m_BatchHost[i].csOut, m_BatchHost[i].encode, fs.outputWidth, fs.outputHeight,
+			    m_BatchIO[i].out, m_BatchIO[i].outStride, m_StateBind[set].out);
 		}
 		// (a host frame: its bytes are complete in m_PassOut[i] / m_PassYuvOut[i] -- tell the thread that copies them out)
 		if (m_BatchHost[i].hostOut) launchSignalHost(m_PassSignal.device(), m_Stream);
@@ -2495,17 +2585,20 @@ bool Engine::sameModel(const Engine &o) const {
 // What process() would refuse for its size, checked up front (a group call launches nothing before every frame passed)
 void Engine::checkGroupFrame(const Frame &f, bool input) const {
 	const FrameSize fs = frameSize();
-	const bool scaled = input && m_SrcW != 0;
-	const std::size_t w = scaled ? m_SrcW : (input ? fs.inputWidth : fs.outputWidth);
-	const std::size_t h = scaled ? m_SrcH : (input ? fs.inputHeight : fs.outputHeight);
+	const bool scaled = input && m_SrcW != 0, resized = !input && m_OutW != 0;
+	const std::size_t w = scaled ? m_SrcW : (resized ? m_OutW : (input ? fs.inputWidth : fs.outputWidth));
+	const std::size_t h = scaled ? m_SrcH : (resized ? m_OutH : (input ? fs.inputHeight : fs.outputHeight));
 	const char *side = input ? "input" : "output";
 	if (scaled && f.location == Location::GraphicsResource) {
 		throw std::invalid_argument("ju_process_group: graphics resources cannot be inputs while a source size is set");
 	}
+	if (resized && f.location == Location::GraphicsResource) {
+		throw std::invalid_argument("ju_process_group: graphics resources cannot be outputs while an output size is set");
+	}
 	if (f.ptr == nullptr) throw std::invalid_argument(std::string("ju_process_group: NULL ") + side + " image");
 	if (f.width != w || f.height != h) {
 		throw std::invalid_argument(std::string("ju_process_group: ") + side + " image must be exactly " + std::to_string(w) +
-		                            "x" + std::to_string(h));
+		                            "x" + std::to_string(h) + (resized ? " (the output size set)" : ""));
 	}
 	const auto row = static_cast<std::ptrdiff_t>(w * 4);
 	if (f.location != Location::GraphicsResource && f.stride > -row && f.stride < row) {
@@ -2735,7 +2828,10 @@ void Engine::submit(const Frame &in, const Frame &out) {
 		runProgram();
 		chainEnd(chain);
 	}
-	if (!m_DirectIO) stageOut(out);
+	if (!m_DirectIO) {
+		const FrameSize fs = frameSize();
+		stageOut(out, fs.outputWidth, fs.outputHeight, m_OutStage.as<std::uint8_t>(), m_RawStage.as<std::uint8_t>());
+	}
 	m_Idx ^= 1;  // state ping-pong (tensorrt_backend.cc:277)
 }
 
@@ -2804,10 +2900,14 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 		    m_MaskStride, static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), m_Stream);
 	}
 	if (sourceStage()) ++m_SourceFrames;
-	if (out.yuv) {
-		stageOutYuv(out.planes);
+	// (behind the frame's program and before the flip: the state this frame wrote is the binding set's output)
+	if (m_OutW != 0) {
+		stageOutScaled(out);
+	} else if (out.yuv) {
+		stageOutYuv(out.planes, m_OutStage.as<std::uint8_t>(), m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get(), nullptr,
+		    m_YuvOutStage.as<std::uint8_t>());
 	} else {
-		stageOut(out.bgrx);
+		stageOut(out.bgrx, fs.outputWidth, fs.outputHeight, m_OutStage.as<std::uint8_t>(), m_RawStage.as<std::uint8_t>());
 	}
 	m_Idx ^= 1;
 }
@@ -3059,6 +3159,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "lookahead_yuv_frames") return static_cast<double>(m_BatchYuvFrames);  // ... of them with a YUV side
 	if (key == "lookahead_max") return static_cast<double>(m_BatchMax);
 	if (key == "source_scaled") return m_SrcW != 0 ? 1.0 : 0.0;
+	if (key == "output_scaled") return m_OutW != 0 ? 1.0 : 0.0;
 	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes

@@ -131,7 +131,13 @@ public:
 	void setSourceSize(std::size_t width, std::size_t height, int filter);
 	void sourceSize(std::size_t *width, std::size_t *height) const;
 	void setSourceMask(const Frame *mask);
-	bool sourceStage() const { return m_SrcW != 0 || m_MaskW != 0; }
+	// The output stage (docs/output_stage.md; engine.cpp, "Output stage").  setOutputSize: output frames are
+	// width x height from now on -- the upscaled frame scaled on the GPU behind the graph and the mask blend ((0, 0): off;
+	// filter 0 = triangle, the only one).  State, frame history and flow inputs are the unscaled run's.  While it is set
+	// every frame of every entry point runs one by one through submitFrame, as for a source size.  reset() keeps it.
+	void setOutputSize(std::size_t width, std::size_t height, int filter);
+	void outputSize(std::size_t *width, std::size_t *height) const;
+	bool sourceStage() const { return m_SrcW != 0 || m_MaskW != 0 || m_OutW != 0; }
 
 	FrameSize frameSize() const;
 	int device() const { return m_Device; }
@@ -207,7 +213,9 @@ private:
 	void buildWeights(const ModelFile &model);
 	void buildProgram(int set);
 	void stageIn(const Frame &in);
-	void stageOut(const Frame &out);
+	// the dense BGRX frame `src` of width x height -> the caller's image; raw: width x height x 4 bytes of scratch (the
+	// flip of a bottom-up host image)
+	void stageOut(const Frame &out, std::size_t width, std::size_t height, const std::uint8_t *src, std::uint8_t *raw);
 	// YUV frames: decode into m_InStage / encode from m_OutStage; host planes go through m_YuvInStage / m_YuvOutStage.
 	// A 10-bit output is encoded from the f16 state the step left (m_HbdFromState: the state IS the frame in float --
 	// every model but normalize_brightness, whose state is output_raw - b, and output_flow, whose frame is pre_warp) or,
@@ -233,11 +241,23 @@ private:
 		std::ptrdiff_t stride = 0;
 	};
 	SourceView stageInSource(const AnyFrame &in);
-	void encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, const std::uint8_t *bgrx,
-	    std::ptrdiff_t bgrxStride, const void *state);
+	// (width x height: the size of the frame encoded; of bgrx / state / frame16 the one the format's path reads)
+	void encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::size_t width, std::size_t height,
+	    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16 = nullptr);
+	// a deep format of a runtime whose state is the frame in float, without a mask: encoded from 16-bit samples
+	bool deepFromState(PixelFormat format) const;
+	// Output stage: the size output frames must have (0 = the model's output), the scaler's tables for the output axes,
+	// the scaled 8-bit and 16-bit frames, the planes of a host YUV output and the flip scratch of a bottom-up host image
+	std::size_t m_OutW = 0, m_OutH = 0;
+	DeviceBuffer m_OutScaleX, m_OutScaleY, m_OutScaled8, m_OutScaled16, m_OutYuvStage, m_OutRawStage;
+	ScaleAxisDev m_OutScaleXDev, m_OutScaleYDev;
+	int m_OutScaleSpan = 0;
+	void stageOutScaled(const AnyFrame &out);
 	void checkFrame(const AnyFrame &f, bool input) const;
 	void stageInYuv(const YuvFrame &in);
-	void stageOutYuv(const YuvFrame &out);
+	// (stage: where a host frame's planes are written before they are copied out)
+	void stageOutYuv(const YuvFrame &out, const std::uint8_t *bgrx, const void *state, const std::uint16_t *frame16,
+	    std::uint8_t *stage);
 	void submitFrame(const AnyFrame &in, const AnyFrame &out);
 	void bindStaging();
 	// submit (a callable that enqueues one frame), wait, and on a resident-tower failure run the frame again on the

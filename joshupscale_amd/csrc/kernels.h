@@ -510,6 +510,12 @@ void launchEncodeFrame(int format, int colorspace, const std::uint8_t *src, std:
 // (std::invalid_argument for another): P = floor((s + 0.5) * 65536), saturated
 void launchEncodeState(int format, int colorspace, const void *state, const YuvPlanes &dst, int width, int height,
     hipStream_t stream);
+// the dense u16 frame [height][width][4] (B, G, R, unused; 8-byte aligned: what launchScaleState writes) -> planes, the
+// deep formats only (std::invalid_argument for another): the sample is P itself -- 10-bit YUV as from the state, W16 = P,
+// W10 = P >> 6, the unit floats f32(P) / 65535 (one division; RGBPH that as f16, to nearest even), BGR96F f32(P) / 257
+// (tests/output_reference.py)
+void launchEncodeFrame16(int format, int colorspace, const std::uint16_t *frame, const YuvPlanes &dst, int width, int height,
+    hipStream_t stream);
 
 // The inputs of a look-ahead pass (Engine::processFrames) that are not BGRX, decoded in one launch: item i of `count` (1 ..
 // kFlowBatchMax) = format, planes, coefficients and BGRX destination of one frame; all frames width x height.  Per item
@@ -562,6 +568,15 @@ int scaleSpan(const ScaleAxisHost &x);
 void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, int srcH, std::uint8_t *dst,
     std::ptrdiff_t dstStride, int dstW, int dstH, const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX,
     hipStream_t stream);
+// The output stage's 16-bit path (docs/output_stage.md): the dense f16 state [srcH][srcW][4] (16-byte aligned) -> the dense
+// u16 frame [dstH][dstW][4] (8-byte aligned; X = 0), out = (sum qy qx P + 2^23) >> 24 with P = floor((s + 0.5) * 65536)
+// saturated, summed exactly (64 bits).  x / y / spanX as for launchScaleBgrx.
+void launchScaleState(const void *state, int srcW, int srcH, std::uint16_t *dst, int dstW, int dstH, const ScaleAxisDev &x,
+    const ScaleAxisDev &y, int spanX, hipStream_t stream);
+// The limits of ju_set_output_size as one message shared with its Python twin: "" when outW x outH may be the output
+// size of a model whose output is modelW x modelH (each axis 2 .. 16384 and within a factor of 16 either way; filter 0)
+constexpr int kOutputAxisMin = 2, kOutputAxisMax = 16384;
+std::string outputSizeProblem(std::size_t outW, std::size_t outH, std::size_t modelW, std::size_t modelH, int filter);
 // Masked pass-through over the frame `gen` (outW x outH BGRX rows, rewritten in place): per pixel the point-sampled
 // texel of `src` (srcW x srcH) and of `mask` (maskW x maskH), a = 765 - (Rm + Gm + Bm), out = (src a + gen (765 - a) +
 // 382) / 765 per channel, X = 0; pixels with a == 0 are not rewritten.  Any byte alignment, signed strides.

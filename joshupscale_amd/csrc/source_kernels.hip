@@ -14,6 +14,10 @@
 //                       1920 -> 480; the tile stores column c at c + c / 32, which puts the 32 lanes of every power-
 //                       of-two ratio up to 16 on 32 different banks (and the vertical pass's four-column writes too).
 //   mask_blend_kernel   a thread per output pixel; mask and source are point sampled.
+//   scale_state_kernel  the output stage's 16-bit path (docs/output_stage.md): scale_bgrx_kernel's tile over the dense f16
+//                       state, each sample first P = floor((s + 0.5) * 65536) saturated (StateSource::sample of
+//                       colour_kernels.hip).  Vertical sums reach 65535 * 4096 < 2^28 (32 bits in LDS), the horizontal
+//                       sum 2^40: a 64-bit accumulator.  Two source pixels per 16-byte load, one 8-byte store per pixel.
 //
 // Rows are addressed with their signed stride; pixels off 4-byte alignment move byte by byte.
 
@@ -82,6 +86,20 @@ std::string sourceSizeProblem(std::size_t srcW, std::size_t srcH, std::size_t in
 	return "source size " + std::to_string(srcW) + "x" + std::to_string(srcH) + ": each axis must be " +
 	       std::to_string(kSourceAxisMin) + " .. " + std::to_string(kSourceAxisMax) + " and within a factor of " +
 	       std::to_string(kSourceRatioMax) + " of the model's input " + std::to_string(inW) + "x" + std::to_string(inH);
+}
+
+std::string outputSizeProblem(std::size_t outW, std::size_t outH, std::size_t modelW, std::size_t modelH, int filter) {
+	if (filter != 0) {
+		return "unknown filter " + std::to_string(filter) + " (JU_SCALE_TRIANGLE is the only one)";
+	}
+	auto axisOk = [](std::size_t m, std::size_t n) {
+		return m >= static_cast<std::size_t>(kOutputAxisMin) && m <= static_cast<std::size_t>(kOutputAxisMax) &&
+		       n <= kSourceRatioMax * m && m <= kSourceRatioMax * n;
+	};
+	if (axisOk(outW, modelW) && axisOk(outH, modelH)) return "";
+	return "output size " + std::to_string(outW) + "x" + std::to_string(outH) + ": each axis must be " +
+	       std::to_string(kOutputAxisMin) + " .. " + std::to_string(kOutputAxisMax) + " and within a factor of " +
+	       std::to_string(kSourceRatioMax) + " of the model's output " + std::to_string(modelW) + "x" + std::to_string(modelH);
 }
 
 int scaleSpan(const ScaleAxisHost &x) {
@@ -186,6 +204,86 @@ __global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__r
 	storePixel(dst + static_cast<std::ptrdiff_t>(dy) * dstStride + 4 * dx, (b >> 24) | ((g >> 24) << 8) | ((r >> 24) << 16));
 }
 
+// P of one f16 of the state, as StateSource::sample (colour_kernels.hip) forms it: exact in f32
+__device__ inline unsigned stateSample(unsigned bits) {
+	const float s = static_cast<float>(__builtin_bit_cast(f16, static_cast<unsigned short>(bits)));
+	return static_cast<unsigned>(fminf(fmaxf(floorf((s + 0.5f) * 65536.0f), 0.0f), 65535.0f));
+}
+
+// The dense f16 state [srcH][srcW][4] (B, G, R, unused) -> the dense u16 frame [dstH][dstW][4] (B, G, R, 0):
+// out = (sum qy qx P + 2^23) >> 24.  The tile, the tables and the LDS layout of scale_bgrx_kernel; an item of the
+// vertical pass is (tile row, two source columns): 16 bytes per tap where that pair is 16-byte aligned (every pair of
+// an even width, every other row of an odd one), else two 8-byte loads, the column clamped to the row.
+__global__ __launch_bounds__(256) void scale_state_kernel(const f16 *__restrict__ src, int srcW,
+    std::uint16_t *__restrict__ dst, int dstW, int dstH, ScaleAxisDev ax, ScaleAxisDev ay, int pitch) {
+	extern __shared__ unsigned tile[];  // [3][kScaleTileH][pitch]: sum qy * P per channel, below 2^28
+	const int tid = threadIdx.x;
+	const int dx0 = blockIdx.x * kScaleTileW, dy0 = blockIdx.y * kScaleTileH;
+	const int dxLast = min(dx0 + kScaleTileW, dstW) - 1;
+	const int xs0 = ax.start[dx0] & ~3;
+	const int xs1 = ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps];
+	const int pairs = (xs1 - xs0 + 1) >> 1;
+	const std::size_t rowWords = static_cast<std::size_t>(srcW) * 4;  // f16 per state row
+
+	for (int item = tid; item < kScaleTileH * pairs; item += 256) {
+		const int r = item / pairs, q = item - r * pairs;
+		const int dy = dy0 + r;
+		if (dy >= dstH) continue;
+		const int x = xs0 + 2 * q;
+		const std::uint16_t *qy = ay.taps + dy * kScaleTapPitch;
+		const int count = qy[kScaleMaxTaps];
+		const f16 *row = src + static_cast<std::size_t>(ay.start[dy]) * rowWords;
+		unsigned acc[6];
+#pragma unroll
+		for (int i = 0; i < 6; ++i) acc[i] = 0;
+		for (int t = 0; t < count; ++t, row += rowWords) {
+			const unsigned w = qy[t];
+			uint2 px[2];
+			const f16 *p = row + 4 * static_cast<std::size_t>(x);
+			if (x + 2 <= srcW && (reinterpret_cast<std::uintptr_t>(p) & 15) == 0) {
+				const uint4 v = *reinterpret_cast<const uint4 *>(p);
+				px[0] = make_uint2(v.x, v.y), px[1] = make_uint2(v.z, v.w);
+			} else {
+#pragma unroll
+				for (int k = 0; k < 2; ++k) {  // (past the row: never a tap)
+					px[k] = *reinterpret_cast<const uint2 *>(row + 4 * static_cast<std::size_t>(min(x + k, srcW - 1)));
+				}
+			}
+#pragma unroll
+			for (int k = 0; k < 2; ++k) {
+				acc[3 * k] += w * stateSample(px[k].x & 0xffff);
+				acc[3 * k + 1] += w * stateSample(px[k].x >> 16);
+				acc[3 * k + 2] += w * stateSample(px[k].y & 0xffff);
+			}
+		}
+#pragma unroll
+		for (int k = 0; k < 2; ++k) {
+			const int col = ldsColumn(2 * q + k);
+#pragma unroll
+			for (int c = 0; c < 3; ++c) tile[(c * kScaleTileH + r) * pitch + col] = acc[3 * k + c];
+		}
+	}
+	__syncthreads();
+
+	const int tx = tid & (kScaleTileW - 1), ty = tid / kScaleTileW;
+	const int dx = dx0 + tx, dy = dy0 + ty;
+	if (dx >= dstW || dy >= dstH) return;
+	const std::uint16_t *qx = ax.taps + dx * kScaleTapPitch;
+	const int count = qx[kScaleMaxTaps];
+	const int first = ax.start[dx] - xs0;
+	unsigned long long b = 1ull << 23, g = 1ull << 23, r = 1ull << 23;  // (each sum stays below 2^40)
+	const unsigned *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
+	for (int t = 0; t < count; ++t) {
+		const unsigned long long w = qx[t];
+		const int col = ldsColumn(first + t);
+		b += w * tb[col];
+		g += w * tg[col];
+		r += w * tr[col];
+	}
+	const unsigned lo = static_cast<unsigned>(b >> 24) | (static_cast<unsigned>(g >> 24) << 16);
+	*reinterpret_cast<uint2 *>(dst + (static_cast<std::size_t>(dy) * dstW + dx) * 4) = make_uint2(lo, static_cast<unsigned>(r >> 24));
+}
+
 __global__ __launch_bounds__(256) void mask_blend_kernel(std::uint8_t *__restrict__ gen, std::ptrdiff_t genStride,
     unsigned outW, unsigned outH, const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride, unsigned srcW,
     unsigned srcH, const std::uint8_t *__restrict__ mask, std::ptrdiff_t maskStride, unsigned maskW, unsigned maskH) {
@@ -225,6 +323,22 @@ void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW
 	hipLaunchKernelGGL(scale_bgrx_kernel, grid, dim3(256), lds, stream, src, srcStride, srcW, dst, dstStride, dstW, dstH, x,
 	    y, pitch);
 	hipCheckLaunch("scale_bgrx");
+}
+
+void launchScaleState(const void *state, int srcW, int srcH, std::uint16_t *dst, int dstW, int dstH, const ScaleAxisDev &x,
+    const ScaleAxisDev &y, int spanX, hipStream_t stream) {
+	if (state == nullptr || dst == nullptr || srcW < 1 || srcH < 1 || dstW < 1 || dstH < 1 || spanX < 4 || spanX % 4 ||
+	    (reinterpret_cast<std::uintptr_t>(state) & 15) != 0 || (reinterpret_cast<std::uintptr_t>(dst) & 7) != 0) {
+		throw std::invalid_argument("launchScaleState: bad arguments");
+	}
+	const int pitch = spanX + spanX / 32 + 1;
+	const std::size_t lds = static_cast<std::size_t>(3) * kScaleTileH * static_cast<std::size_t>(pitch) * sizeof(unsigned);
+	if (lds > 64 * 1024) throw std::invalid_argument("launchScaleState: the tile does not fit the LDS");
+	const dim3 grid(static_cast<unsigned>((dstW + kScaleTileW - 1) / kScaleTileW),
+	    static_cast<unsigned>((dstH + kScaleTileH - 1) / kScaleTileH));
+	hipLaunchKernelGGL(scale_state_kernel, grid, dim3(256), lds, stream, static_cast<const f16 *>(state), srcW, dst, dstW,
+	    dstH, x, y, pitch);
+	hipCheckLaunch("scale_state");
 }
 
 void launchMaskBlend(std::uint8_t *gen, std::ptrdiff_t genStride, int outW, int outH, const std::uint8_t *src,

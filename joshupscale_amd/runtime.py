@@ -86,6 +86,24 @@ def source_size_problem(src_width: int, src_height: int, input_width: int, input
             f"a factor of {SOURCE_RATIO_MAX} of the model's input {input_width}x{input_height}")
 
 
+# the output stage (docs/output_stage.md): the limits of ju_set_output_size
+OUTPUT_AXIS_MIN, OUTPUT_AXIS_MAX, OUTPUT_RATIO_MAX = 2, 16384, 16
+
+
+def output_size_problem(width: int, height: int, model_width: int, model_height: int, filter: int = SCALE_TRIANGLE) -> str:
+    """The limits of ``ju_set_output_size`` for a model output of ``model_width x model_height``, with the C layer's
+    message; ``""`` when the output size may be set."""
+    if filter != SCALE_TRIANGLE:
+        return f"unknown filter {filter} (JU_SCALE_TRIANGLE is the only one)"
+
+    def ok(m, n):
+        return OUTPUT_AXIS_MIN <= m <= OUTPUT_AXIS_MAX and n <= OUTPUT_RATIO_MAX * m and m <= OUTPUT_RATIO_MAX * n
+    if ok(width, model_width) and ok(height, model_height):
+        return ""
+    return (f"output size {width}x{height}: each axis must be {OUTPUT_AXIS_MIN} .. {OUTPUT_AXIS_MAX} and within "
+            f"a factor of {OUTPUT_RATIO_MAX} of the model's output {model_width}x{model_height}")
+
+
 LOG_CALLBACK = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p)
 
 
@@ -135,6 +153,8 @@ _PRODUCT_SIGS = {
     "ju_set_source_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_get_source_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
+    "ju_set_output_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
+    "ju_get_output_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_last_error": (C.c_char_p, []),
     "ju_set_log_callback": (None, [LOG_CALLBACK, C.c_void_p]),
     "ju_get_gl_device_index": (C.c_int, [_P(C.c_int)]),
@@ -167,6 +187,8 @@ _HOOK_SIGS = {
                                      _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_source": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
+    "ju_debug_output": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                  C.c_int, _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
@@ -351,16 +373,40 @@ class Runtime:
             mask = host_image(mask)
         _check(self._lib, self._lib.ju_set_source_mask(self._h, C.byref(mask)))
 
+    # -- the output stage (docs/output_stage.md) ----------------------------------
+    def set_output_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
+        """``ju_set_output_size``: output frames are ``width x height`` from now on, the upscaled frame scaled on the GPU;
+        ``(0, 0)`` turns it off.  The limits raise ``ValueError`` with the C layer's message before any native call."""
+        width, height, filter = int(width), int(height), int(filter)
+        off = (width, height) == (0, 0)
+        problem = output_size_problem(self.output_width if off else width, self.output_height if off else height,
+                                      self.output_width, self.output_height, filter)
+        if problem:
+            raise ValueError("ju_set_output_size: " + problem)
+        _check(self._lib, self._lib.ju_set_output_size(self._h, width, height, filter))
+
+    def get_output_size(self) -> Tuple[int, int]:
+        """``ju_get_output_size``: ``(width, height)``, ``(0, 0)`` while no output size is set."""
+        w, h = C.c_size_t(), C.c_size_t()
+        _check(self._lib, self._lib.ju_get_output_size(self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def frame_output_size(self) -> Tuple[int, int]:
+        """``(width, height)`` of the frames the runtime hands out now: the output size set, else the model's output."""
+        w, h = self.get_output_size()
+        return (w, h) if w else (self.output_width, self.output_height)
+
     def process_image(self, frame_bgrx: np.ndarray,
                       out: Optional[np.ndarray] = None) -> np.ndarray:
-        """Host frames: ``[H, W, 4]`` uint8 in, ``[4H, 4W, 4]`` uint8 out.  Any
-        row stride (also negative, i.e. a ``[::-1]`` view) is passed through."""
+        """Host frames: ``[H, W, 4]`` uint8 in, ``[4H, 4W, 4]`` uint8 out (``[OH, OW, 4]`` while an output size is
+        set).  Any row stride (also negative, i.e. a ``[::-1]`` view) is passed through."""
         if frame_bgrx.dtype != np.uint8 or frame_bgrx.ndim != 3 or frame_bgrx.shape[2] != 4:
             raise ValueError("expected a [H, W, 4] uint8 BGRX frame")
         if frame_bgrx.strides[2] != 1 or frame_bgrx.strides[1] != 4:
             frame_bgrx = np.ascontiguousarray(frame_bgrx)
         if out is None:
-            out = np.empty((self.output_height, self.output_width, 4), np.uint8)
+            ow, oh = self.frame_output_size()
+            out = np.empty((oh, ow, 4), np.uint8)
         if out.strides[2] != 1 or out.strides[1] != 4:
             raise ValueError("output must have contiguous pixels")
         self.process(host_image(frame_bgrx), host_image(out))
@@ -394,7 +440,7 @@ class Runtime:
         out_format = fmt if out_format is None else out_format
         planes = [y, u] if fmt in (FMT_NV12, FMT_P010) else [y, u, v]
         inp = host_frame(fmt, planes, colorspace)
-        ow, oh = self.output_width, self.output_height
+        ow, oh = self.frame_output_size()
         sample = np.uint16 if out_format in (FMT_P010, FMT_I010) else np.uint8
         if out_format == FMT_BGRX:
             res = [np.empty((oh, ow, 4), np.uint8)]
@@ -413,7 +459,7 @@ class Runtime:
         ``(r, g, b)`` of a planar one."""
         out_format = fmt if out_format is None else out_format
         planes = [planes] if isinstance(planes, np.ndarray) else list(planes)
-        ow, oh = self.output_width, self.output_height
+        ow, oh = self.frame_output_size()
         if out_format == FMT_BGRX:
             res = [np.empty((oh, ow, 4), np.uint8)]
         elif out_format in _FMT_RGB:
@@ -453,7 +499,8 @@ class Runtime:
     def stat(self, key: str) -> float:
         """``ju_get_stat``: "graph_replays", "eager_runs", "direct_graphs",
         "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "output_select", "lookahead_frames",
-        "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames"."""
+        "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames",
+        "output_scaled"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -655,3 +702,10 @@ class Session:
     def set_source_mask(self, mask) -> None:
         """The source shows through ``mask`` in every frame ``run`` returns (``Runtime.set_source_mask``)."""
         self.runtime.set_source_mask(mask)
+
+    def set_output_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
+        """``run`` returns ``width x height`` images from now on (``Runtime.set_output_size``)."""
+        self.runtime.set_output_size(width, height, filter)
+
+    def get_output_size(self) -> Tuple[int, int]:
+        return self.runtime.get_output_size()
