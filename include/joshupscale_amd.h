@@ -332,8 +332,14 @@ JU_API int ju_reset(ju_runtime *runtime);
  * input on the GPU: out = (sum qy qx src + 2^23) >> 24 with 12-bit triangle-filter coefficients (Pillow's BILINEAR
  * before its quantisation), X = 0; a source of the model's size passes through byte for byte.  A YUV source is decoded
  * at source size by the conversion of ju_process_frame, unchanged, then scaled.  Host sources upload at source size.
- * (0, 0) turns it off.  filter: JU_SCALE_TRIANGLE, the only value.  Limits (JU_ERR_INVALID_ARGUMENT): each source axis
- * 2 .. 8192 and within a factor of 16 of the model's input axis, either way (at most 33 taps per axis).
+ * (0, 0) turns it off.  filter: JU_SCALE_TRIANGLE (the above), JU_SCALE_CATMULL_ROM (the bicubic of Pillow's BICUBIC,
+ * a = -0.5) or JU_SCALE_MITCHELL (Mitchell-Netravali, B = C = 1/3); the value 1 is reserved and refused, as is every other
+ * value.  The cubic filters have negative coefficients, so their result is clamped: out = clamp((sum qy qx src + 2^23) >>
+ * 24, 0, 255), nothing rounded or clipped between the axes (docs/source_stage.md "Filters";
+ * tests/scale_filter_reference.py).  Catmull-Rom interpolates: a source of the model's size passes through byte for
+ * byte, as with the triangle.  Mitchell does not: it filters (softens) such a source too.  Limits
+ * (JU_ERR_INVALID_ARGUMENT): each source axis 2 .. 8192, at least a 16th of the model's input axis and at most 16 times
+ * it -- 8 times with a cubic filter, whose support is twice as wide (at most 33 taps per axis).
  * ju_get_size keeps reporting the model's sizes; ju_get_source_size reports (0, 0) while off.
  *
  * ju_set_source_mask: a BGRX image of any size (1 .. 16384 per axis), JU_LOC_CPU or JU_LOC_DEVICE, copied to device
@@ -351,10 +357,11 @@ JU_API int ju_reset(ju_runtime *runtime);
  * ("lookahead_frames" / "group_frames" do not count them, "source_stage_frames" does), ju_prepare_frames /
  * ju_prepare_batch capture nothing.  JU_LOC_GRAPHICS_RESOURCE inputs are refused while a source size is set (outputs,
  * and inputs under a mask alone, are taken).  Turning both off restores the other paths.
- * Not provided: scaled or masked frames inside look-ahead or group passes; filters other than the triangle; OBS's own
+ * Not provided: scaled or masked frames inside look-ahead or group passes; Lanczos or any other filter whose weights
+ * need a transcendental function (they would not be defined bit for bit: docs/source_stage.md); OBS's own
  * OBS_EFFECT_BILINEAR_LOWRES arithmetic (it is not in the reference tree).  The scaler on the output side is
  * ju_set_output_size, below. */
-enum { JU_SCALE_TRIANGLE = 0 };
+enum { JU_SCALE_TRIANGLE = 0, JU_SCALE_CATMULL_ROM = 2, JU_SCALE_MITCHELL = 3 }; /* (1: reserved, refused) */
 JU_API int ju_set_source_size(ju_runtime *runtime, size_t src_width, size_t src_height, int filter);
 JU_API int ju_get_source_size(const ju_runtime *runtime, size_t *src_width, size_t *src_height);
 JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
@@ -374,14 +381,17 @@ JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
  *   Deep formats otherwise (JU_FMT_P010, I010, P210, I210, I410, BGRX64, RGBP10, RGBP16, RGBPH, RGBPS, BGR96F): v is the
  *   state's 16-bit sample P = floor((s + 0.5) * 65536), saturated; the scaled P is encoded -- 10-bit YUV as from the state,
  *   16-bit words P, 10-bit words P >> 6, unit floats f32(P) / 65535 (RGBPH: that as f16), BGR96F f32(P) / 257.
- * (0, 0) turns it off.  filter: JU_SCALE_TRIANGLE, the only value.  Limits (JU_ERR_INVALID_ARGUMENT): each axis 2 .. 16384
- * and within a factor of 16 of the model's output axis, either way.  ju_get_size keeps reporting the model's sizes;
+ * (0, 0) turns it off.  filter: JU_SCALE_TRIANGLE, JU_SCALE_CATMULL_ROM or JU_SCALE_MITCHELL, as for ju_set_source_size
+ * (1 and every other value: refused); with a cubic filter out = clamp((sum qy qx v + 2^23) >> 24, 0, top), top = 255 for
+ * the 8-bit frame and 65535 for P.  An output of the model's size passes through unchanged with the triangle and with
+ * Catmull-Rom; Mitchell filters it.  Limits (JU_ERR_INVALID_ARGUMENT): each axis 2 .. 16384, at most 16 times the model's
+ * output axis and at least a 16th of it -- an 8th with a cubic filter.  ju_get_size keeps reporting the model's sizes;
  * ju_get_output_size reports (0, 0) while off.  Recurrent state, frame history and flow inputs are the unscaled run's.
  *
  * While it is set frames are routed as for a source size: one by one through the staging buffers, no direct device path,
  * no look-ahead or group pass ("source_stage_frames" counts them), ju_prepare_* capture nothing.  A JU_LOC_DEVICE BGRX
  * output is written in place, any alignment and signed stride.  JU_LOC_GRAPHICS_RESOURCE outputs are refused.
- * ju_get_stat: "output_scaled" (1 / 0). */
+ * ju_get_stat: "output_scaled" (1 / 0), "output_filter" (the JU_SCALE_* value in effect, 0 while off). */
 JU_API int ju_set_output_size(ju_runtime *runtime, size_t width, size_t height, int filter);
 JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height);
 
@@ -446,7 +456,8 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * "lookahead_yuv_frames" with a YUV side, 8- or 10-bit),
  * "source_scaled" / "source_mask" (1 while ju_set_source_size / ju_set_source_mask is in effect), "source_stage_frames"
  * (frames that went through the source stage or the output stage), "output_scaled" (1 while ju_set_output_size is in
- * effect),
+ * effect), "source_filter" / "output_filter" (the JU_SCALE_* value ju_set_source_size / ju_set_output_size has in effect;
+ * 0 while off),
  * "hbd_from_state" (1: this runtime encodes JU_FMT_P010 / JU_FMT_I010 outputs from its f16 state; 0: from the 8-bit
  * frame -- normalize_brightness and output_flow models),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,

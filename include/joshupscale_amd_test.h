@@ -117,6 +117,18 @@ JU_API int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_w
 JU_API int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_height, const void *src, size_t src_width,
     size_t src_height, int format, int colorspace, void *const planes[3], const ptrdiff_t strides[3]);
 
+/* The scalers with a filter argument (docs/source_stage.md "Filters"; tests/scale_filter_reference.py); `filter` is a
+ * JU_SCALE_* value.  op 0: the 8-bit scaler -- buffers, sizes and strides as ju_debug_source op 0.  op 1: the state
+ * scaler -- `src` the dense f16 tensor, `dst` the dense u16 frame, as ju_debug_output op 0; the strides are ignored.
+ * op 2 / op 3: no device and no buffers -- the limits ju_set_source_size (a source of src_width x src_height for a model
+ * input of dst_width x dst_height) / ju_set_output_size (an output size of dst_width x dst_height for a model output of
+ * src_width x src_height) apply for the filter, with their message (JU_ERR_INVALID_ARGUMENT) or JU_OK.  op 4: no device --
+ * the table of one axis, src_width source samples -> dst_width destination samples, as the setters build it, copied into
+ * host arrays: start[dst_width], count[dst_width] and taps[dst_width][33] (taps beyond a row's count are 0); the heights
+ * and the buffers are ignored.  Ops 0 .. 3 ignore start, count and taps. */
+JU_API int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height,
+    const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height, int *start, int *count, int16_t *taps);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -642,6 +642,61 @@ int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_height, cons
 	});
 }
 
+int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, const void *src,
+    ptrdiff_t src_stride, size_t src_width, size_t src_height, int *start, int *count, int16_t *taps) {
+	return guarded([&] {
+		if (op == 2 || op == 3) {  // the limits of ju_set_source_size / ju_set_output_size for a filter: no device
+			const std::string problem = op == 2 ? ju::sourceSizeProblem(src_width, src_height, dst_width, dst_height, filter)
+			                                    : ju::outputSizeProblem(dst_width, dst_height, src_width, src_height, filter);
+			if (!problem.empty()) {
+				throw std::invalid_argument(std::string(op == 2 ? "ju_set_source_size: " : "ju_set_output_size: ") + problem);
+			}
+			return;
+		}
+		if (op == 4) {  // one axis' table, src_width -> dst_width: no device
+			constexpr size_t kMost = 1u << 15;
+			if (start == nullptr || count == nullptr || taps == nullptr || src_width < 1 || dst_width < 1 || src_width > kMost ||
+			    dst_width > kMost) {
+				throw std::invalid_argument("ju_debug_scale: null array or an extent outside 1 .. 32768");
+			}
+			const ju::ScaleAxisHost a = ju::buildScaleAxis(static_cast<int>(src_width), static_cast<int>(dst_width), filter);
+			for (size_t d = 0; d < dst_width; ++d) {
+				const std::uint16_t *row = a.taps.data() + d * ju::kScaleTapPitch;
+				start[d] = a.start[d];
+				count[d] = row[ju::kScaleMaxTaps];
+				for (int t = 0; t < ju::kScaleMaxTaps; ++t) taps[d * ju::kScaleMaxTaps + t] = static_cast<int16_t>(row[t]);
+			}
+			return;
+		}
+		if (op != 0 && op != 1) throw std::invalid_argument("ju_debug_scale: op must be 0 .. 4");
+		constexpr size_t kMost = 1u << 15;
+		if (dst == nullptr || src == nullptr || dst_width < 1 || dst_height < 1 || src_width < 1 || src_height < 1 ||
+		    dst_width > kMost || dst_height > kMost || src_width > kMost || src_height > kMost) {
+			throw std::invalid_argument("ju_debug_scale: null buffer or a size outside 1 .. 32768");
+		}
+		const int dw = static_cast<int>(dst_width), dh = static_cast<int>(dst_height);
+		const int sw = static_cast<int>(src_width), sh = static_cast<int>(src_height);
+		const ju::ScaleAxisHost x = ju::buildScaleAxis(sw, dw, filter), y = ju::buildScaleAxis(sh, dh, filter);
+		auto upload = [](const ju::ScaleAxisHost &a, ju::DeviceBuffer *start, ju::DeviceBuffer *taps) {
+			*start = ju::DeviceBuffer(a.start.size() * sizeof(int));
+			start->upload(a.start.data(), a.start.size() * sizeof(int));
+			*taps = ju::DeviceBuffer(a.taps.size() * sizeof(std::uint16_t));
+			taps->upload(a.taps.data(), a.taps.size() * sizeof(std::uint16_t));
+		};
+		ju::DeviceBuffer xs, xt, ys, yt;
+		upload(x, &xs, &xt);
+		upload(y, &ys, &yt);
+		const ju::ScaleAxisDev dx{xs.as<int>(), xt.as<std::uint16_t>(), filter}, dy{ys.as<int>(), yt.as<std::uint16_t>(), filter};
+		if (op == 0) {
+			ju::launchScaleBgrx(static_cast<const std::uint8_t *>(src), src_stride, sw, sh, static_cast<std::uint8_t *>(dst),
+			    dst_stride, dw, dh, dx, dy, ju::scaleSpan(x), nullptr);
+		} else {
+			ju::launchScaleState(src, sw, sh, static_cast<std::uint16_t *>(dst), dw, dh, dx, dy, ju::scaleSpan(x), nullptr);
+		}
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
 int ju_debug_e4m3(const float *values, unsigned char *codes, size_t count) {
 	return guarded([&] {
 		if (count && (!values || !codes)) throw std::invalid_argument("ju_debug_e4m3: null buffer");

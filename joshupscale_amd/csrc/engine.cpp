@@ -1708,19 +1708,18 @@ DeviceBuffer uploadScaleAxis(const ScaleAxisHost &a) {
 	return buf;
 }
 ScaleAxisDev scaleAxisDev(const DeviceBuffer &buf, const ScaleAxisHost &a) {
-	return {buf.as<int>(), reinterpret_cast<const std::uint16_t *>(buf.as<int>() + a.start.size())};
+	return {buf.as<int>(), reinterpret_cast<const std::uint16_t *>(buf.as<int>() + a.start.size()), a.filter};
 }
 }  // namespace
 
 void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	DeviceGuard g(m_Device);
-	if (filter != 0) {
-		throw std::invalid_argument("ju_set_source_size: unknown filter " + std::to_string(filter) +
-		                            " (JU_SCALE_TRIANGLE is the only one)");
-	}
+	const std::string unknown = scaleFilterProblem(filter);
+	if (!unknown.empty()) throw std::invalid_argument("ju_set_source_size: " + unknown);
 	if (width == 0 && height == 0) {
 		m_Stream.synchronize();  // (enqueued frames may still read the tables)
 		m_SrcW = m_SrcH = 0;
+		m_SrcFilter = 0;
 		m_ScaleX = DeviceBuffer();
 		m_ScaleY = DeviceBuffer();
 		m_SrcStage = DeviceBuffer();
@@ -1728,10 +1727,10 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 		return;
 	}
 	const FrameSize fs = frameSize();
-	const std::string problem = sourceSizeProblem(width, height, fs.inputWidth, fs.inputHeight);
+	const std::string problem = sourceSizeProblem(width, height, fs.inputWidth, fs.inputHeight, filter);
 	if (!problem.empty()) throw std::invalid_argument("ju_set_source_size: " + problem);
-	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(width), static_cast<int>(fs.inputWidth));
-	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(height), static_cast<int>(fs.inputHeight));
+	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(width), static_cast<int>(fs.inputWidth), filter);
+	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(height), static_cast<int>(fs.inputHeight), filter);
 	DeviceBuffer bx = uploadScaleAxis(x), by = uploadScaleAxis(y);
 	DeviceBuffer stage(width * height * 4), yuvStage(yuvStageBytes(width, height));
 	m_Stream.synchronize();
@@ -1744,6 +1743,7 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	m_ScaleSpan = scaleSpan(x);
 	m_SrcW = width;
 	m_SrcH = height;
+	m_SrcFilter = filter;
 }
 
 void Engine::sourceSize(std::size_t *width, std::size_t *height) const {
@@ -1789,7 +1789,7 @@ void Engine::setSourceMask(const Frame *mask) {
 // ---------------------------------------------------------------------------------------------------------------
 // Output stage (docs/output_stage.md).  What the reference's OBS caller gets from OBS's canvas scaling behind
 // processImage: the upscaled frame at any size.  Behind the staged graph and the mask blend of submitFrame the frame is
-// scaled by the source stage's triangle filter with the output axes' tables: the 8-bit frame in m_OutStage by
+// scaled by the source stage's scaler (the triangle or a cubic filter) with the output axes' tables: the 8-bit frame in m_OutStage by
 // scale_bgrx_kernel, or -- for a deep format that is encoded from the state (deepFromState) -- the state's 16-bit samples
 // by scale_state_kernel into m_OutScaled16, which launchEncodeFrame16 encodes.  Nothing of the step itself changes.
 // ---------------------------------------------------------------------------------------------------------------
@@ -1803,13 +1803,14 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 	if (off) {
 		m_Stream.synchronize();  // (enqueued frames may still read the tables and write the buffers)
 		m_OutW = m_OutH = 0;
+		m_OutFilter = 0;
 		for (DeviceBuffer *b : {&m_OutScaleX, &m_OutScaleY, &m_OutScaled8, &m_OutScaled16, &m_OutYuvStage, &m_OutRawStage}) {
 			*b = DeviceBuffer();
 		}
 		return;
 	}
-	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(fs.outputWidth), static_cast<int>(width));
-	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(fs.outputHeight), static_cast<int>(height));
+	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(fs.outputWidth), static_cast<int>(width), filter);
+	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(fs.outputHeight), static_cast<int>(height), filter);
 	DeviceBuffer bx = uploadScaleAxis(x), by = uploadScaleAxis(y);
 	DeviceBuffer scaled8(width * height * 4), scaled16(width * height * 8), raw(width * height * 4);
 	DeviceBuffer yuvStage(yuvStageBytes(width, height));
@@ -1825,6 +1826,7 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 	m_OutScaleSpan = scaleSpan(x);
 	m_OutW = width;
 	m_OutH = height;
+	m_OutFilter = filter;
 }
 
 void Engine::outputSize(std::size_t *width, std::size_t *height) const {
@@ -3160,6 +3162,8 @@ double Engine::stat(const std::string &key) const {
 	if (key == "lookahead_max") return static_cast<double>(m_BatchMax);
 	if (key == "source_scaled") return m_SrcW != 0 ? 1.0 : 0.0;
 	if (key == "output_scaled") return m_OutW != 0 ? 1.0 : 0.0;
+	if (key == "source_filter") return static_cast<double>(m_SrcFilter);  // (0 while off: the setters clear it)
+	if (key == "output_filter") return static_cast<double>(m_OutFilter);
 	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes

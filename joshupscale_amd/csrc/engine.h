@@ -124,8 +124,8 @@ public:
 	void reset();
 
 	// The source stage (docs/source_stage.md; engine.cpp, "Source stage").  setSourceSize: input frames are
-	// width x height from now on and are scaled to the model's input on the GPU ((0, 0): off; filter 0 = triangle, the
-	// only one).  setSourceMask: a BGRX image of any size, host or device, copied now (nullptr: no mask); the source is
+	// width x height from now on and are scaled to the model's input on the GPU ((0, 0): off; filter: a JU_SCALE_* value --
+	// 0 triangle, 2 Catmull-Rom, 3 Mitchell).  setSourceMask: a BGRX image of any size, host or device, copied now (nullptr: no mask); the source is
 	// drawn over every output frame through it.  While either is set every frame of every entry point runs one by one
 	// through the staged path of submitFrame.  reset() keeps both.
 	void setSourceSize(std::size_t width, std::size_t height, int filter);
@@ -133,7 +133,7 @@ public:
 	void setSourceMask(const Frame *mask);
 	// The output stage (docs/output_stage.md; engine.cpp, "Output stage").  setOutputSize: output frames are
 	// width x height from now on -- the upscaled frame scaled on the GPU behind the graph and the mask blend ((0, 0): off;
-	// filter 0 = triangle, the only one).  State, frame history and flow inputs are the unscaled run's.  While it is set
+	// filter: a JU_SCALE_* value, as for the source size).  State, frame history and flow inputs are the unscaled run's.  While it is set
 	// every frame of every entry point runs one by one through submitFrame, as for a source size.  reset() keeps it.
 	void setOutputSize(std::size_t width, std::size_t height, int filter);
 	void outputSize(std::size_t *width, std::size_t *height) const;
@@ -229,6 +229,7 @@ private:
 	// source; the mask in device memory, in the caller's row order (m_MaskStride < 0: bottom-up).  m_SourceFrames: frames
 	// that went through the stage ("source_stage_frames").
 	std::size_t m_SrcW = 0, m_SrcH = 0;
+	int m_SrcFilter = 0;  // the filter in effect (JU_SCALE_*; 0 while off): "source_filter"
 	DeviceBuffer m_ScaleX, m_ScaleY, m_SrcStage, m_SrcYuvStage;
 	ScaleAxisDev m_ScaleXDev, m_ScaleYDev;
 	int m_ScaleSpan = 0;
@@ -249,6 +250,7 @@ private:
 	// Output stage: the size output frames must have (0 = the model's output), the scaler's tables for the output axes,
 	// the scaled 8-bit and 16-bit frames, the planes of a host YUV output and the flip scratch of a bottom-up host image
 	std::size_t m_OutW = 0, m_OutH = 0;
+	int m_OutFilter = 0;  // "output_filter"
 	DeviceBuffer m_OutScaleX, m_OutScaleY, m_OutScaled8, m_OutScaled16, m_OutYuvStage, m_OutRawStage;
 	ScaleAxisDev m_OutScaleXDev, m_OutScaleYDev;
 	int m_OutScaleSpan = 0;

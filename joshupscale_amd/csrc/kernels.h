@@ -540,27 +540,41 @@ YuvDecodeItem yuvDecodeItem(int format, int colorspace, const YuvPlanes &src, st
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream);
 
 // ---- source stage (source_kernels.hip; docs/source_stage.md): sources of any size, masked pass-through ---------------
-// One axis of the triangle scaler, N source samples -> M destination samples, in integers (buildScaleAxis is the
-// definition; tests/source_reference.py restates it): per destination index the first source index, the tap count
-// (at most kScaleMaxTaps) and the taps, u16, summing to exactly 4096.
+// One axis of the scaler, N source samples -> M destination samples, in integers (buildScaleAxis is the definition;
+// tests/source_reference.py and tests/scale_filter_reference.py restate it): per destination index the first source
+// index, the tap count (at most kScaleMaxTaps) and the taps, 16 bits each, summing to exactly 4096.  The filters are the
+// values of JU_SCALE_* (include/joshupscale_amd.h): the triangle's taps are u16; the two cubic filters' taps can be
+// negative and are read as i16, and their rows hold sum |q| <= kScaleAbsSumMax (what the signed kernels' widths rest on).
 constexpr int kScaleMaxTaps = 33;
 constexpr int kScaleTapPitch = kScaleMaxTaps + 1;  // u16 per destination index: the taps, then the tap count
 constexpr int kSourceAxisMin = 2, kSourceAxisMax = 8192, kSourceRatioMax = 16;
+constexpr int kScaleTriangle = 0, kScaleCatmullRom = 2, kScaleMitchell = 3;  // (1 is reserved and refused)
+constexpr int kCubicDownMax = 8;       // a cubic filter's support is twice the triangle's: 33 taps at a factor of 8
+constexpr int kScaleAbsSumMax = 6144;
+inline bool scaleFilterKnown(int filter) { return filter == kScaleTriangle || filter == kScaleCatmullRom || filter == kScaleMitchell; }
+// the largest N / M of a filter (M / N: kSourceRatioMax for all of them)
+inline int scaleDownMax(int filter) { return filter == kScaleTriangle ? kSourceRatioMax : kCubicDownMax; }
+// "" for a known filter, else the message ju_set_source_size / ju_set_output_size and their Python twins give
+std::string scaleFilterProblem(int filter);
 struct ScaleAxisHost {
 	int n = 0, m = 0;
+	int filter = kScaleTriangle;
 	std::vector<int> start;            // [m]
-	std::vector<std::uint16_t> taps;   // [m][kScaleTapPitch]
+	std::vector<std::uint16_t> taps;   // [m][kScaleTapPitch]; i16 in the same words for a cubic filter
 };
-// std::invalid_argument unless 1 <= n, m and n <= 16 m and m <= 16 n (the bound that keeps an axis at 33 taps)
-ScaleAxisHost buildScaleAxis(int n, int m);
+// std::invalid_argument unless the filter is known, 1 <= n, m, m <= 16 n and n <= 16 m (triangle) or 8 m (cubic): the
+// bounds that keep an axis at 33 taps
+ScaleAxisHost buildScaleAxis(int n, int m, int filter = kScaleTriangle);
 // The same limits as one message for ju_set_source_size and its Python twin: "" when srcW x srcH may feed a model of
-// inW x inH
-std::string sourceSizeProblem(std::size_t srcW, std::size_t srcH, std::size_t inW, std::size_t inH);
+// inW x inH through `filter`
+std::string sourceSizeProblem(std::size_t srcW, std::size_t srcH, std::size_t inW, std::size_t inH, int filter = kScaleTriangle);
 struct ScaleAxisDev {
 	const int *start = nullptr;
 	const std::uint16_t *taps = nullptr;
+	int filter = kScaleTriangle;       // (the host's choice of kernel form; the kernels take the two pointers)
 };
-// BGRX rows of srcW x srcH -> BGRX rows of dstW x dstH (X = 0): out = (sum qy qx src + 2^23) >> 24 per channel.  Any
+// BGRX rows of srcW x srcH -> BGRX rows of dstW x dstH (X = 0): out = (sum qy qx src + 2^23) >> 24 per channel, clamped
+// to 0 .. 255 where an axis' filter is cubic (the signed form of the kernel; the triangle's form is unchanged).  Any
 // byte alignment, signed strides.  x / y: the device copies of buildScaleAxis(srcW, dstW) / (srcH, dstH); spanX: the most
 // source columns a tile of kScaleTileW destination columns reads (scaleSpan of the x axis).
 constexpr int kScaleTileW = 32, kScaleTileH = 8;
@@ -570,11 +584,13 @@ void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW
     hipStream_t stream);
 // The output stage's 16-bit path (docs/output_stage.md): the dense f16 state [srcH][srcW][4] (16-byte aligned) -> the dense
 // u16 frame [dstH][dstW][4] (8-byte aligned; X = 0), out = (sum qy qx P + 2^23) >> 24 with P = floor((s + 0.5) * 65536)
-// saturated, summed exactly (64 bits).  x / y / spanX as for launchScaleBgrx.
+// saturated, summed exactly (64 bits), clamped to 0 .. 65535 where an axis' filter is cubic.  x / y / spanX as for
+// launchScaleBgrx.
 void launchScaleState(const void *state, int srcW, int srcH, std::uint16_t *dst, int dstW, int dstH, const ScaleAxisDev &x,
     const ScaleAxisDev &y, int spanX, hipStream_t stream);
 // The limits of ju_set_output_size as one message shared with its Python twin: "" when outW x outH may be the output
-// size of a model whose output is modelW x modelH (each axis 2 .. 16384 and within a factor of 16 either way; filter 0)
+// size of a model whose output is modelW x modelH (each axis 2 .. 16384, at most 16 times the model's and at least a
+// 16th of it -- an 8th for a cubic filter; a known filter)
 constexpr int kOutputAxisMin = 2, kOutputAxisMax = 16384;
 std::string outputSizeProblem(std::size_t outW, std::size_t outH, std::size_t modelW, std::size_t modelH, int filter);
 // Masked pass-through over the frame `gen` (outW x outH BGRX rows, rewritten in place): per pixel the point-sampled

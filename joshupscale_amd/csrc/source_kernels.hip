@@ -1,9 +1,10 @@
 // The source stage on gfx950 (docs/source_stage.md): a BGRX source of any size scaled to the model's input by an
-// integer triangle filter, and the source drawn back over the upscaled frame through a mask.
+// integer filter -- the triangle, or one of two cubic filters (Catmull-Rom, Mitchell-Netravali) -- and the source drawn
+// back over the upscaled frame through a mask.
 //
-// Both kernels compute exactly the numpy definition of tests/source_reference.py.  The host builds the per-axis tables
-// (buildScaleAxis: start index, tap count and u16 taps summing to 4096 per destination index); the device only
-// multiplies and adds unsigned 32-bit integers:
+// The kernels compute exactly the numpy definitions of tests/source_reference.py and tests/scale_filter_reference.py.
+// The host builds the per-axis tables (buildScaleAxis: start index, tap count and 16-bit taps summing to 4096 per
+// destination index); the device only multiplies and adds integers.  The triangle's form (<false>), unsigned:
 //
 //   scale_bgrx_kernel   one workgroup per tile of kScaleTileW x kScaleTileH destination pixels.  Vertical pass: every
 //                       source column the tile needs, for each of the tile's rows, sum qy * src (<= 255 * 4096 < 2^20,
@@ -19,6 +20,12 @@
 //                       colour_kernels.hip).  Vertical sums reach 65535 * 4096 < 2^28 (32 bits in LDS), the horizontal
 //                       sum 2^40: a 64-bit accumulator.  Two source pixels per 16-byte load, one 8-byte store per pixel.
 //
+// The cubic filters' form (<true>) of both scale kernels is the same code on signed types (ScaleForm): taps read as i16,
+// rows of sum |q| <= 6144, so a vertical sum is below 2^21 (2^29 for the state) in size and still one signed LDS word
+// under the same tile, padding and loads; the horizontal sum is 64 bits signed (2^34 / 2^42 in size), shifted with its
+// sign and clamped to 0 .. 255 / 65535.  The triangle's instantiations are, instruction for instruction, the kernels
+// from before the template (docs/source_stage.md "Filters").
+//
 // Rows are addressed with their signed stride; pixels off 4-byte alignment move byte by byte.
 
 #include <hip/hip_runtime.h>
@@ -27,17 +34,98 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "kernel_common.h"
 #include "kernels.h"
 
 namespace ju {
 
-ScaleAxisHost buildScaleAxis(int n, int m) {
-	if (n < 1 || m < 1 || n > kSourceRatioMax * static_cast<long long>(m) || m > kSourceRatioMax * static_cast<long long>(n)) {
-		throw std::invalid_argument("buildScaleAxis: " + std::to_string(n) + " -> " + std::to_string(m) +
-		                            " is beyond a factor of " + std::to_string(kSourceRatioMax));
+std::string scaleFilterProblem(int filter) {
+	if (scaleFilterKnown(filter)) return "";
+	return "unknown filter " + std::to_string(filter) +
+	       " (the filters are JU_SCALE_TRIANGLE = 0, JU_SCALE_CATMULL_ROM = 2 and JU_SCALE_MITCHELL = 3)";
+}
+
+namespace {
+
+// The raw weight of a cubic filter at distance u / D, u >= 0: the kernel times 2 D^3 (Catmull-Rom, a = -0.5) or 18 D^3
+// (Mitchell-Netravali, B = C = 1/3), 0 from 2 D on.  D <= 32768: every term stays below 2^53.
+long long cubicWeight(int filter, long long u, long long D) {
+	if (u >= 2 * D) return 0;
+	if (filter == kScaleCatmullRom) {
+		return u < D ? 3 * u * u * u - 5 * u * u * D + 2 * D * D * D : -u * u * u + 5 * u * u * D - 8 * u * D * D + 4 * D * D * D;
 	}
+	return u < D ? 21 * u * u * u - 36 * u * u * D + 16 * D * D * D
+	             : -7 * u * u * u + 36 * u * u * D - 60 * u * D * D + 32 * D * D * D;
+}
+
+// One axis of a cubic filter (tests/scale_filter_reference.py axis_table): the run of source indices with u < 2 D, zero
+// weights trimmed at both ends; q = floor(4096 w / S) toward minus infinity; the remainder to the first largest w.
+ScaleAxisHost buildCubicAxis(int n, int m, int filter) {
+	ScaleAxisHost a;
+	a.n = n;
+	a.m = m;
+	a.filter = filter;
+	a.start.assign(static_cast<std::size_t>(m), 0);
+	a.taps.assign(static_cast<std::size_t>(m) * kScaleTapPitch, 0);
+	const long long N = n, M = m, D = 2 * std::max(N, M);
+	if (D > 32768) throw std::logic_error("buildScaleAxis: an axis beyond 16384 samples");
+	long long firstMost = 0, endMost = 0;
+	for (long long d = 0; d < M; ++d) {
+		const long long c = (2 * d + 1) * N;
+		const auto weight = [&](long long s) {
+			const long long t = (2 * s + 1) * M - c;
+			return cubicWeight(filter, t < 0 ? -t : t, D);
+		};
+		// from a little before the support to a little behind it, then trimmed to the first and the last weight that is not 0
+		long long s0 = std::max((c - 2 * D) / (2 * M) - 1, 0LL), s1 = std::min((c + 2 * D) / (2 * M) + 2, N);
+		while (s0 < s1 && weight(s0) == 0) ++s0;
+		while (s1 > s0 && weight(s1 - 1) == 0) --s1;
+		if (s1 == s0) throw std::logic_error("buildScaleAxis: a destination index without taps");
+		if (s1 - s0 > kScaleMaxTaps) throw std::logic_error("buildScaleAxis: more than 33 taps");
+		const int count = static_cast<int>(s1 - s0);
+		long long w[kScaleMaxTaps];
+		long long sum = 0;
+		int best = 0;
+		for (int i = 0; i < count; ++i) {
+			w[i] = weight(s0 + i);
+			sum += w[i];
+			if (w[i] > w[best]) best = i;  // (the first of the largest)
+		}
+		if (sum <= 0) throw std::logic_error("buildScaleAxis: a row whose weights do not sum above 0");
+		long long q[kScaleMaxTaps];
+		long long total = 0, absSum = 0;
+		for (int i = 0; i < count; ++i) {
+			const long long num = w[i] * 4096;  // (|w| <= 32 D^3 <= 2^50)
+			q[i] = num / sum - (num % sum < 0 ? 1 : 0);
+			total += q[i];
+		}
+		q[best] += 4096 - total;
+		for (int i = 0; i < count; ++i) absSum += q[i] < 0 ? -q[i] : q[i];
+		if (absSum > kScaleAbsSumMax) throw std::logic_error("buildScaleAxis: a row with sum |q| above 6144");
+		std::uint16_t *out = a.taps.data() + static_cast<std::size_t>(d) * kScaleTapPitch;
+		for (int i = 0; i < count; ++i) out[i] = static_cast<std::uint16_t>(static_cast<std::int16_t>(q[i]));
+		out[kScaleMaxTaps] = static_cast<std::uint16_t>(count);
+		a.start[static_cast<std::size_t>(d)] = static_cast<int>(s0);
+		// what the kernels' tile span rests on (tileFirst / tileEnd): no earlier row starts or ends more than one index later
+		firstMost = std::max(firstMost, s0);
+		endMost = std::max(endMost, s1);
+		if (s0 < firstMost - 1 || s1 < endMost - 1) throw std::logic_error("buildScaleAxis: rows more than one index out of order");
+	}
+	return a;
+}
+
+}  // namespace
+
+ScaleAxisHost buildScaleAxis(int n, int m, int filter) {
+	const std::string unknown = scaleFilterProblem(filter);
+	if (!unknown.empty()) throw std::invalid_argument("buildScaleAxis: " + unknown);
+	if (n < 1 || m < 1 || n > scaleDownMax(filter) * static_cast<long long>(m) || m > kSourceRatioMax * static_cast<long long>(n)) {
+		throw std::invalid_argument("buildScaleAxis: " + std::to_string(n) + " -> " + std::to_string(m) +
+		                            " is beyond a factor of " + std::to_string(n > m ? scaleDownMax(filter) : kSourceRatioMax));
+	}
+	if (filter != kScaleTriangle) return buildCubicAxis(n, m, filter);
 	ScaleAxisHost a;
 	a.n = n;
 	a.m = m;
@@ -77,37 +165,68 @@ ScaleAxisHost buildScaleAxis(int n, int m) {
 	return a;
 }
 
-std::string sourceSizeProblem(std::size_t srcW, std::size_t srcH, std::size_t inW, std::size_t inH) {
-	auto axisOk = [](std::size_t n, std::size_t m) {
+namespace {
+// "within a factor of 16 of" for the triangle; a cubic filter reduces by 8 at the most: "at most 8 times" the model's
+// input for a source, "at least an 8th of" the model's output for an output size
+std::string ratioWords(int filter, bool sourceSide) {
+	if (filter == kScaleTriangle) return " and within a factor of " + std::to_string(kSourceRatioMax) + " of";
+	const std::string up = std::to_string(kSourceRatioMax), down = std::to_string(kCubicDownMax);
+	return sourceSide ? ", at most " + down + " times and at least a " + up + "th of"
+	                  : ", at most " + up + " times and at least an " + down + "th of";
+}
+}  // namespace
+
+std::string sourceSizeProblem(std::size_t srcW, std::size_t srcH, std::size_t inW, std::size_t inH, int filter) {
+	const std::string unknown = scaleFilterProblem(filter);
+	if (!unknown.empty()) return unknown;
+	const std::size_t down = static_cast<std::size_t>(scaleDownMax(filter));
+	auto axisOk = [down](std::size_t n, std::size_t m) {
 		return n >= static_cast<std::size_t>(kSourceAxisMin) && n <= static_cast<std::size_t>(kSourceAxisMax) &&
-		       n <= kSourceRatioMax * m && m <= kSourceRatioMax * n;
+		       n <= down * m && m <= kSourceRatioMax * n;
 	};
 	if (axisOk(srcW, inW) && axisOk(srcH, inH)) return "";
 	return "source size " + std::to_string(srcW) + "x" + std::to_string(srcH) + ": each axis must be " +
-	       std::to_string(kSourceAxisMin) + " .. " + std::to_string(kSourceAxisMax) + " and within a factor of " +
-	       std::to_string(kSourceRatioMax) + " of the model's input " + std::to_string(inW) + "x" + std::to_string(inH);
+	       std::to_string(kSourceAxisMin) + " .. " + std::to_string(kSourceAxisMax) + ratioWords(filter, true) +
+	       " the model's input " + std::to_string(inW) + "x" + std::to_string(inH);
 }
 
 std::string outputSizeProblem(std::size_t outW, std::size_t outH, std::size_t modelW, std::size_t modelH, int filter) {
-	if (filter != 0) {
-		return "unknown filter " + std::to_string(filter) + " (JU_SCALE_TRIANGLE is the only one)";
-	}
-	auto axisOk = [](std::size_t m, std::size_t n) {
+	const std::string unknown = scaleFilterProblem(filter);
+	if (!unknown.empty()) return unknown;
+	const std::size_t down = static_cast<std::size_t>(scaleDownMax(filter));
+	auto axisOk = [down](std::size_t m, std::size_t n) {
 		return m >= static_cast<std::size_t>(kOutputAxisMin) && m <= static_cast<std::size_t>(kOutputAxisMax) &&
-		       n <= kSourceRatioMax * m && m <= kSourceRatioMax * n;
+		       n <= down * m && m <= kSourceRatioMax * n;
 	};
 	if (axisOk(outW, modelW) && axisOk(outH, modelH)) return "";
 	return "output size " + std::to_string(outW) + "x" + std::to_string(outH) + ": each axis must be " +
-	       std::to_string(kOutputAxisMin) + " .. " + std::to_string(kOutputAxisMax) + " and within a factor of " +
-	       std::to_string(kSourceRatioMax) + " of the model's output " + std::to_string(modelW) + "x" + std::to_string(modelH);
+	       std::to_string(kOutputAxisMin) + " .. " + std::to_string(kOutputAxisMax) + ratioWords(filter, false) +
+	       " the model's output " + std::to_string(modelW) + "x" + std::to_string(modelH);
 }
+
+namespace {
+// The source columns of a tile of destination columns d0 .. d1: from the first tap of d0 to the last tap of d1 for the
+// triangle, whose rows start and end in ascending order.  A cubic row loses a tap whose weight is exactly 0 at either
+// end (Catmull-Rom at distance 1, Mitchell at 8/7), at most one per end, so a row inside the tile can reach one column
+// further than the tile's outer rows (buildCubicAxis checks that it is never more): one column of slack on either side.
+template <bool kSigned>
+__host__ __device__ inline int tileFirst(int first) {
+	return kSigned ? (first > 0 ? first - 1 : 0) : first;
+}
+template <bool kSigned>
+__host__ __device__ inline int tileEnd(int end, int n) {
+	return kSigned ? (end < n ? end + 1 : n) : end;
+}
+}  // namespace
 
 int scaleSpan(const ScaleAxisHost &x) {
 	int span = 4;
 	for (int d0 = 0; d0 < x.m; d0 += kScaleTileW) {
 		const int d1 = std::min(d0 + kScaleTileW, x.m) - 1;
-		const int first = x.start[static_cast<std::size_t>(d0)] & ~3;
-		const int end = x.start[static_cast<std::size_t>(d1)] + x.taps[static_cast<std::size_t>(d1) * kScaleTapPitch + kScaleMaxTaps];
+		int first = x.start[static_cast<std::size_t>(d0)];
+		int end = x.start[static_cast<std::size_t>(d1)] + x.taps[static_cast<std::size_t>(d1) * kScaleTapPitch + kScaleMaxTaps];
+		if (x.filter != kScaleTriangle) first = tileFirst<true>(first), end = tileEnd<true>(end, x.n);  // (as the signed kernels)
+		first &= ~3;
 		span = std::max(span, (end - first + 3) / 4 * 4);
 	}
 	return span;
@@ -135,15 +254,48 @@ __device__ inline void storePixel(std::uint8_t *p, unsigned v) {
 // LDS column of tile column c: one word of padding per 32 columns (see the head of the file)
 __device__ inline int ldsColumn(int c) { return c + (c >> 5); }
 
+// the tables of one axis as the kernels take them (ScaleAxisDev without the host's choice of form)
+struct ScaleTaps {
+	const int *start;
+	const std::uint16_t *taps;
+};
+
+// The two forms of a scale kernel.  Unsigned, the triangle: u16 taps, unsigned sums, no clamp (rows of non-negative taps
+// summing to 4096 cannot leave the range).  Signed, the cubic filters: the same words read as i16, signed 32-bit
+// vertical sums in LDS (|sum| <= top * 6144: < 2^21 for 8-bit samples, < 2^29 for 16-bit ones), a signed 64-bit horizontal
+// sum (|sum| < 2^34 / 2^42), and the shifted result -- narrow again: below 2^18 in size -- clamped to 0 .. top.
+template <bool kSigned>
+struct ScaleForm {
+	using Tap = std::conditional_t<kSigned, std::int16_t, std::uint16_t>;
+	using Sum = std::conditional_t<kSigned, int, unsigned>;                    // a tap in a register; a vertical sum
+	using Sum8 = std::conditional_t<kSigned, long long, unsigned>;             // the horizontal sum of 8-bit samples
+	using Sum16 = std::conditional_t<kSigned, long long, unsigned long long>;  // ... of 16-bit samples
+};
+
+// (sum + 2^23) >> 24 of a horizontal sum that already holds the 2^23: floor; the signed form clamps to 0 .. kTop
+template <bool kSigned, int kTop, typename T>
+__device__ inline unsigned scaleResult(T sum) {
+	if constexpr (kSigned) {
+		return static_cast<unsigned>(min(max(static_cast<int>(sum >> 24), 0), kTop));
+	} else {
+		return static_cast<unsigned>(sum >> 24);
+	}
+}
+
+template <bool kSigned>
 __global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
-    int srcW, std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW, int dstH, ScaleAxisDev ax,
-    ScaleAxisDev ay, int pitch) {
-	extern __shared__ unsigned tile[];  // [3][kScaleTileH][pitch]: sum qy * src per channel
+    int srcW, std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW, int dstH, ScaleTaps ax,
+    ScaleTaps ay, int pitch) {
+	using Tap = typename ScaleForm<kSigned>::Tap;
+	using Sum = typename ScaleForm<kSigned>::Sum;
+	using Wide = typename ScaleForm<kSigned>::Sum8;
+	extern __shared__ unsigned tileWords[];  // [3][kScaleTileH][pitch]: sum qy * src per channel
+	Sum *tile = reinterpret_cast<Sum *>(tileWords);
 	const int tid = threadIdx.x;
 	const int dx0 = blockIdx.x * kScaleTileW, dy0 = blockIdx.y * kScaleTileH;
 	const int dxLast = min(dx0 + kScaleTileW, dstW) - 1;
-	const int xs0 = ax.start[dx0] & ~3;
-	const int xs1 = ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps];
+	const int xs0 = tileFirst<kSigned>(ax.start[dx0]) & ~3;
+	const int xs1 = tileEnd<kSigned>(ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps], srcW);
 	const int quads = (xs1 - xs0 + 3) >> 2;
 	const bool aligned = ((reinterpret_cast<std::uintptr_t>(src) | static_cast<std::uintptr_t>(srcStride)) & 15) == 0;
 
@@ -153,14 +305,14 @@ __global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__r
 		const int dy = dy0 + r;
 		if (dy >= dstH) continue;
 		const int x = xs0 + 4 * q;
-		const std::uint16_t *qy = ay.taps + dy * kScaleTapPitch;
+		const Tap *qy = reinterpret_cast<const Tap *>(ay.taps) + dy * kScaleTapPitch;
 		const int count = qy[kScaleMaxTaps];
 		const std::uint8_t *row = src + static_cast<std::ptrdiff_t>(ay.start[dy]) * srcStride;
-		unsigned acc[12];
+		Sum acc[12];
 #pragma unroll
 		for (int i = 0; i < 12; ++i) acc[i] = 0;
 		for (int t = 0; t < count; ++t, row += srcStride) {
-			const unsigned w = qy[t];
+			const Sum w = qy[t];
 			unsigned px[4];
 			if (aligned && x + 4 <= srcW) {
 				const uint4 v = *reinterpret_cast<const uint4 *>(row + 4 * x);
@@ -171,9 +323,9 @@ __global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__r
 			}
 #pragma unroll
 			for (int k = 0; k < 4; ++k) {
-				acc[3 * k] += w * (px[k] & 255);
-				acc[3 * k + 1] += w * ((px[k] >> 8) & 255);
-				acc[3 * k + 2] += w * ((px[k] >> 16) & 255);
+				acc[3 * k] += w * static_cast<Sum>(px[k] & 255);
+				acc[3 * k + 1] += w * static_cast<Sum>((px[k] >> 8) & 255);
+				acc[3 * k + 2] += w * static_cast<Sum>((px[k] >> 16) & 255);
 			}
 		}
 #pragma unroll
@@ -189,19 +341,20 @@ __global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__r
 	const int tx = tid & (kScaleTileW - 1), ty = tid / kScaleTileW;
 	const int dx = dx0 + tx, dy = dy0 + ty;
 	if (dx >= dstW || dy >= dstH) return;
-	const std::uint16_t *qx = ax.taps + dx * kScaleTapPitch;
+	const Tap *qx = reinterpret_cast<const Tap *>(ax.taps) + dx * kScaleTapPitch;
 	const int count = qx[kScaleMaxTaps];
 	const int first = ax.start[dx] - xs0;
-	unsigned b = 1u << 23, g = 1u << 23, r = 1u << 23;
-	const unsigned *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
+	Wide b = 1u << 23, g = 1u << 23, r = 1u << 23;
+	const Sum *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
 	for (int t = 0; t < count; ++t) {
-		const unsigned w = qx[t];
+		const Wide w = qx[t];
 		const int col = ldsColumn(first + t);
-		b += w * tb[col];
+		b += w * tb[col];  // (the signed form: i32 x i32 + i64, one v_mad_i64_i32)
 		g += w * tg[col];
 		r += w * tr[col];
 	}
-	storePixel(dst + static_cast<std::ptrdiff_t>(dy) * dstStride + 4 * dx, (b >> 24) | ((g >> 24) << 8) | ((r >> 24) << 16));
+	storePixel(dst + static_cast<std::ptrdiff_t>(dy) * dstStride + 4 * dx, scaleResult<kSigned, 255>(b) |
+	    (scaleResult<kSigned, 255>(g) << 8) | (scaleResult<kSigned, 255>(r) << 16));
 }
 
 // P of one f16 of the state, as StateSource::sample (colour_kernels.hip) forms it: exact in f32
@@ -214,14 +367,19 @@ __device__ inline unsigned stateSample(unsigned bits) {
 // out = (sum qy qx P + 2^23) >> 24.  The tile, the tables and the LDS layout of scale_bgrx_kernel; an item of the
 // vertical pass is (tile row, two source columns): 16 bytes per tap where that pair is 16-byte aligned (every pair of
 // an even width, every other row of an odd one), else two 8-byte loads, the column clamped to the row.
+template <bool kSigned>
 __global__ __launch_bounds__(256) void scale_state_kernel(const f16 *__restrict__ src, int srcW,
-    std::uint16_t *__restrict__ dst, int dstW, int dstH, ScaleAxisDev ax, ScaleAxisDev ay, int pitch) {
-	extern __shared__ unsigned tile[];  // [3][kScaleTileH][pitch]: sum qy * P per channel, below 2^28
+    std::uint16_t *__restrict__ dst, int dstW, int dstH, ScaleTaps ax, ScaleTaps ay, int pitch) {
+	using Tap = typename ScaleForm<kSigned>::Tap;
+	using Sum = typename ScaleForm<kSigned>::Sum;
+	using Wide = typename ScaleForm<kSigned>::Sum16;
+	extern __shared__ unsigned tileWords[];  // [3][kScaleTileH][pitch]: sum qy * P per channel, below 2^28 (signed: 2^29 in size)
+	Sum *tile = reinterpret_cast<Sum *>(tileWords);
 	const int tid = threadIdx.x;
 	const int dx0 = blockIdx.x * kScaleTileW, dy0 = blockIdx.y * kScaleTileH;
 	const int dxLast = min(dx0 + kScaleTileW, dstW) - 1;
-	const int xs0 = ax.start[dx0] & ~3;
-	const int xs1 = ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps];
+	const int xs0 = tileFirst<kSigned>(ax.start[dx0]) & ~3;
+	const int xs1 = tileEnd<kSigned>(ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps], srcW);
 	const int pairs = (xs1 - xs0 + 1) >> 1;
 	const std::size_t rowWords = static_cast<std::size_t>(srcW) * 4;  // f16 per state row
 
@@ -230,14 +388,14 @@ __global__ __launch_bounds__(256) void scale_state_kernel(const f16 *__restrict_
 		const int dy = dy0 + r;
 		if (dy >= dstH) continue;
 		const int x = xs0 + 2 * q;
-		const std::uint16_t *qy = ay.taps + dy * kScaleTapPitch;
+		const Tap *qy = reinterpret_cast<const Tap *>(ay.taps) + dy * kScaleTapPitch;
 		const int count = qy[kScaleMaxTaps];
 		const f16 *row = src + static_cast<std::size_t>(ay.start[dy]) * rowWords;
-		unsigned acc[6];
+		Sum acc[6];
 #pragma unroll
 		for (int i = 0; i < 6; ++i) acc[i] = 0;
 		for (int t = 0; t < count; ++t, row += rowWords) {
-			const unsigned w = qy[t];
+			const Sum w = qy[t];
 			uint2 px[2];
 			const f16 *p = row + 4 * static_cast<std::size_t>(x);
 			if (x + 2 <= srcW && (reinterpret_cast<std::uintptr_t>(p) & 15) == 0) {
@@ -251,9 +409,9 @@ __global__ __launch_bounds__(256) void scale_state_kernel(const f16 *__restrict_
 			}
 #pragma unroll
 			for (int k = 0; k < 2; ++k) {
-				acc[3 * k] += w * stateSample(px[k].x & 0xffff);
-				acc[3 * k + 1] += w * stateSample(px[k].x >> 16);
-				acc[3 * k + 2] += w * stateSample(px[k].y & 0xffff);
+				acc[3 * k] += w * static_cast<Sum>(stateSample(px[k].x & 0xffff));
+				acc[3 * k + 1] += w * static_cast<Sum>(stateSample(px[k].x >> 16));
+				acc[3 * k + 2] += w * static_cast<Sum>(stateSample(px[k].y & 0xffff));
 			}
 		}
 #pragma unroll
@@ -268,20 +426,20 @@ __global__ __launch_bounds__(256) void scale_state_kernel(const f16 *__restrict_
 	const int tx = tid & (kScaleTileW - 1), ty = tid / kScaleTileW;
 	const int dx = dx0 + tx, dy = dy0 + ty;
 	if (dx >= dstW || dy >= dstH) return;
-	const std::uint16_t *qx = ax.taps + dx * kScaleTapPitch;
+	const Tap *qx = reinterpret_cast<const Tap *>(ax.taps) + dx * kScaleTapPitch;
 	const int count = qx[kScaleMaxTaps];
 	const int first = ax.start[dx] - xs0;
-	unsigned long long b = 1ull << 23, g = 1ull << 23, r = 1ull << 23;  // (each sum stays below 2^40)
-	const unsigned *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
+	Wide b = 1u << 23, g = 1u << 23, r = 1u << 23;  // (each sum stays below 2^40; the signed form: 2^42 in size)
+	const Sum *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
 	for (int t = 0; t < count; ++t) {
-		const unsigned long long w = qx[t];
+		const Wide w = qx[t];
 		const int col = ldsColumn(first + t);
 		b += w * tb[col];
 		g += w * tg[col];
 		r += w * tr[col];
 	}
-	const unsigned lo = static_cast<unsigned>(b >> 24) | (static_cast<unsigned>(g >> 24) << 16);
-	*reinterpret_cast<uint2 *>(dst + (static_cast<std::size_t>(dy) * dstW + dx) * 4) = make_uint2(lo, static_cast<unsigned>(r >> 24));
+	const unsigned lo = scaleResult<kSigned, 65535>(b) | (scaleResult<kSigned, 65535>(g) << 16);
+	*reinterpret_cast<uint2 *>(dst + (static_cast<std::size_t>(dy) * dstW + dx) * 4) = make_uint2(lo, scaleResult<kSigned, 65535>(r));
 }
 
 __global__ __launch_bounds__(256) void mask_blend_kernel(std::uint8_t *__restrict__ gen, std::ptrdiff_t genStride,
@@ -320,8 +478,10 @@ void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW
 	if (lds > 64 * 1024) throw std::invalid_argument("launchScaleBgrx: the tile does not fit the LDS");
 	const dim3 grid(static_cast<unsigned>((dstW + kScaleTileW - 1) / kScaleTileW),
 	    static_cast<unsigned>((dstH + kScaleTileH - 1) / kScaleTileH));
-	hipLaunchKernelGGL(scale_bgrx_kernel, grid, dim3(256), lds, stream, src, srcStride, srcW, dst, dstStride, dstW, dstH, x,
-	    y, pitch);
+	const ScaleTaps tx{x.start, x.taps}, ty{y.start, y.taps};
+	if (x.filter != y.filter) throw std::invalid_argument("launchScaleBgrx: the two axes' tables must be of one filter");
+	const auto kernel = x.filter != kScaleTriangle ? scale_bgrx_kernel<true> : scale_bgrx_kernel<false>;  // (spanX is of that form too)
+	hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, src, srcStride, srcW, dst, dstStride, dstW, dstH, tx, ty, pitch);
 	hipCheckLaunch("scale_bgrx");
 }
 
@@ -336,8 +496,10 @@ void launchScaleState(const void *state, int srcW, int srcH, std::uint16_t *dst,
 	if (lds > 64 * 1024) throw std::invalid_argument("launchScaleState: the tile does not fit the LDS");
 	const dim3 grid(static_cast<unsigned>((dstW + kScaleTileW - 1) / kScaleTileW),
 	    static_cast<unsigned>((dstH + kScaleTileH - 1) / kScaleTileH));
-	hipLaunchKernelGGL(scale_state_kernel, grid, dim3(256), lds, stream, static_cast<const f16 *>(state), srcW, dst, dstW,
-	    dstH, x, y, pitch);
+	const ScaleTaps tx{x.start, x.taps}, ty{y.start, y.taps};
+	if (x.filter != y.filter) throw std::invalid_argument("launchScaleState: the two axes' tables must be of one filter");
+	const auto kernel = x.filter != kScaleTriangle ? scale_state_kernel<true> : scale_state_kernel<false>;  // (spanX is of that form too)
+	hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, static_cast<const f16 *>(state), srcW, dst, dstW, dstH, tx, ty, pitch);
 	hipCheckLaunch("scale_state");
 }
 

@@ -70,20 +70,45 @@ class JuFrame(C.Structure):
                 ("planes", C.c_void_p * 3), ("strides", C.c_ssize_t * 3)]
 
 
-# the source stage (docs/source_stage.md): the one filter of ju_set_source_size and its limits
-SCALE_TRIANGLE = 0
+# the source stage (docs/source_stage.md): the filters of ju_set_source_size / ju_set_output_size (JU_SCALE_*; 1 is
+# reserved and refused) and the limits.  A cubic filter's support is twice the triangle's: it reduces by 8 at the most.
+SCALE_TRIANGLE, SCALE_CATMULL_ROM, SCALE_MITCHELL = 0, 2, 3
+SCALE_FILTERS = (SCALE_TRIANGLE, SCALE_CATMULL_ROM, SCALE_MITCHELL)
 SOURCE_AXIS_MIN, SOURCE_AXIS_MAX, SOURCE_RATIO_MAX = 2, 8192, 16
+CUBIC_DOWN_MAX = 8
 
 
-def source_size_problem(src_width: int, src_height: int, input_width: int, input_height: int) -> str:
+def scale_filter_problem(filter: int) -> str:
+    """``""`` for a known filter, else the C layer's message."""
+    if filter in SCALE_FILTERS:
+        return ""
+    return (f"unknown filter {filter} (the filters are JU_SCALE_TRIANGLE = 0, JU_SCALE_CATMULL_ROM = 2 and "
+            "JU_SCALE_MITCHELL = 3)")
+
+
+def _ratio_words(filter: int, source_side: bool) -> str:
+    if filter == SCALE_TRIANGLE:
+        return f" and within a factor of {SOURCE_RATIO_MAX} of"
+    if source_side:
+        return f", at most {CUBIC_DOWN_MAX} times and at least a {SOURCE_RATIO_MAX}th of"
+    return f", at most {SOURCE_RATIO_MAX} times and at least an {CUBIC_DOWN_MAX}th of"
+
+
+def source_size_problem(src_width: int, src_height: int, input_width: int, input_height: int,
+                        filter: int = SCALE_TRIANGLE) -> str:
     """The limits of ``ju_set_source_size`` for a model input of ``input_width x input_height``, with the C layer's
     message; ``""`` when the source size may be set."""
+    unknown = scale_filter_problem(filter)
+    if unknown:
+        return unknown
+    down = SOURCE_RATIO_MAX if filter == SCALE_TRIANGLE else CUBIC_DOWN_MAX
+
     def ok(n, m):
-        return SOURCE_AXIS_MIN <= n <= SOURCE_AXIS_MAX and n <= SOURCE_RATIO_MAX * m and m <= SOURCE_RATIO_MAX * n
+        return SOURCE_AXIS_MIN <= n <= SOURCE_AXIS_MAX and n <= down * m and m <= SOURCE_RATIO_MAX * n
     if ok(src_width, input_width) and ok(src_height, input_height):
         return ""
-    return (f"source size {src_width}x{src_height}: each axis must be {SOURCE_AXIS_MIN} .. {SOURCE_AXIS_MAX} and within "
-            f"a factor of {SOURCE_RATIO_MAX} of the model's input {input_width}x{input_height}")
+    return (f"source size {src_width}x{src_height}: each axis must be {SOURCE_AXIS_MIN} .. {SOURCE_AXIS_MAX}"
+            f"{_ratio_words(filter, True)} the model's input {input_width}x{input_height}")
 
 
 # the output stage (docs/output_stage.md): the limits of ju_set_output_size
@@ -93,15 +118,17 @@ OUTPUT_AXIS_MIN, OUTPUT_AXIS_MAX, OUTPUT_RATIO_MAX = 2, 16384, 16
 def output_size_problem(width: int, height: int, model_width: int, model_height: int, filter: int = SCALE_TRIANGLE) -> str:
     """The limits of ``ju_set_output_size`` for a model output of ``model_width x model_height``, with the C layer's
     message; ``""`` when the output size may be set."""
-    if filter != SCALE_TRIANGLE:
-        return f"unknown filter {filter} (JU_SCALE_TRIANGLE is the only one)"
+    unknown = scale_filter_problem(filter)
+    if unknown:
+        return unknown
+    down = OUTPUT_RATIO_MAX if filter == SCALE_TRIANGLE else CUBIC_DOWN_MAX
 
     def ok(m, n):
-        return OUTPUT_AXIS_MIN <= m <= OUTPUT_AXIS_MAX and n <= OUTPUT_RATIO_MAX * m and m <= OUTPUT_RATIO_MAX * n
+        return OUTPUT_AXIS_MIN <= m <= OUTPUT_AXIS_MAX and n <= down * m and m <= OUTPUT_RATIO_MAX * n
     if ok(width, model_width) and ok(height, model_height):
         return ""
-    return (f"output size {width}x{height}: each axis must be {OUTPUT_AXIS_MIN} .. {OUTPUT_AXIS_MAX} and within "
-            f"a factor of {OUTPUT_RATIO_MAX} of the model's output {model_width}x{model_height}")
+    return (f"output size {width}x{height}: each axis must be {OUTPUT_AXIS_MIN} .. {OUTPUT_AXIS_MAX}"
+            f"{_ratio_words(filter, False)} the model's output {model_width}x{model_height}")
 
 
 LOG_CALLBACK = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p)
@@ -189,6 +216,8 @@ _HOOK_SIGS = {
                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
     "ju_debug_output": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                   C.c_int, _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_scale": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
+                                 C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
@@ -346,14 +375,15 @@ class Runtime:
     # -- the source stage (docs/source_stage.md) ----------------------------------
     def set_source_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
         """``ju_set_source_size``: input frames are ``width x height`` from now on and are scaled to the model's input on
-        the GPU; ``(0, 0)`` turns it off.  The limits raise ``ValueError`` with the C layer's message before any native
-        call."""
-        width, height = int(width), int(height)
-        if (width, height) != (0, 0):
-            problem = source_size_problem(width, height, self.input_width, self.input_height)
-            if problem:
-                raise ValueError("ju_set_source_size: " + problem)
-        _check(self._lib, self._lib.ju_set_source_size(self._h, width, height, int(filter)))
+        the GPU by ``filter`` (``SCALE_TRIANGLE``, ``SCALE_CATMULL_ROM`` or ``SCALE_MITCHELL``); ``(0, 0)`` turns it off.
+        The limits and an unknown filter raise ``ValueError`` with the C layer's message before any native call."""
+        width, height, filter = int(width), int(height), int(filter)
+        off = (width, height) == (0, 0)
+        problem = scale_filter_problem(filter) if off else \
+            source_size_problem(width, height, self.input_width, self.input_height, filter)
+        if problem:
+            raise ValueError("ju_set_source_size: " + problem)
+        _check(self._lib, self._lib.ju_set_source_size(self._h, width, height, filter))
 
     def get_source_size(self) -> Tuple[int, int]:
         """``ju_get_source_size``: ``(width, height)``, ``(0, 0)`` while no source size is set."""
@@ -375,8 +405,8 @@ class Runtime:
 
     # -- the output stage (docs/output_stage.md) ----------------------------------
     def set_output_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
-        """``ju_set_output_size``: output frames are ``width x height`` from now on, the upscaled frame scaled on the GPU;
-        ``(0, 0)`` turns it off.  The limits raise ``ValueError`` with the C layer's message before any native call."""
+        """``ju_set_output_size``: output frames are ``width x height`` from now on, the upscaled frame scaled on the GPU
+        by ``filter`` (as for ``set_source_size``); ``(0, 0)`` turns it off.  The limits raise ``ValueError`` with the C layer's message before any native call."""
         width, height, filter = int(width), int(height), int(filter)
         off = (width, height) == (0, 0)
         problem = output_size_problem(self.output_width if off else width, self.output_height if off else height,
@@ -500,7 +530,7 @@ class Runtime:
         """``ju_get_stat``: "graph_replays", "eager_runs", "direct_graphs",
         "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "output_select", "lookahead_frames",
         "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames",
-        "output_scaled"."""
+        "output_scaled", "source_filter", "output_filter"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -8,6 +8,11 @@ and the other work on the machine are shared alike:
   nv12_1280x720  / p010_1280x720    ju_set_output_size(1280, 720): scale_bgrx on the 8-bit frame / scale_state + the
   nv12_3840x2160 / p010_3840x2160   encode from the 16-bit frame; and the same at 3840x2160
 
+--filter NAME[,NAME...] (triangle, catmull-rom, mitchell; default triangle) chooses the filter of the scaled variants;
+with several names every scaled variant exists once per filter, its name ending in the filter's (the triangle's has no
+suffix), all in the same process and the same rounds -- the triangle is the comparison point of the cubic filters.
+--sizes WxH[,WxH...] replaces the two output sizes.
+
 Prints one JSON line.  --profile N instead runs N frames of each scaled variant only, for a
 `rocprofv3 --kernel-trace --stats -- python tools/output_bench.py --profile N` run."""
 
@@ -31,6 +36,7 @@ import yuv_reference as Y  # noqa: E402
 
 CS = R.CS_BT709_LIMITED
 SIZES = ((1280, 720), (3840, 2160))
+FILTERS = {"triangle": R.SCALE_TRIANGLE, "catmull-rom": R.SCALE_CATMULL_ROM, "mitchell": R.SCALE_MITCHELL}
 
 
 def nv12_device(frames, dev, keep):
@@ -57,7 +63,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--frames-per-round", type=int, default=300)
     ap.add_argument("--profile", type=int, default=0)
+    ap.add_argument("--filter", default="triangle")
+    ap.add_argument("--sizes", default=",".join(f"{w}x{h}" for w, h in SIZES))
     args = ap.parse_args()
+    filters = [(name, FILTERS[name]) for name in args.filter.split(",")]
+    sizes = tuple(tuple(int(x) for x in s.split("x")) for s in args.sizes.split(","))
     dev = torch.device("cuda", 0)
     torch.zeros(1, device=dev)
     cfg = M.PRESETS[args.preset]
@@ -67,12 +77,14 @@ def main():
     inputs = nv12_device(M.synthetic_frames(4, h, w, seed=1234, kind="smooth"), dev, keep)
     runtimes, outputs = {}, {}
     for fmt, tag in ((R.FMT_NV12, "nv12"), (R.FMT_P010, "p010")):
-        for (ow, oh) in ((4 * w, 4 * h),) + SIZES:
-            name = f"{tag}_{ow}x{oh}"
-            rt = R.Runtime(blob, 0, R.DTYPE_BF16, hooks=False)
-            if (ow, oh) != (4 * w, 4 * h):
-                rt.set_output_size(ow, oh)
-            runtimes[name], outputs[name] = rt, out_frame(fmt, ow, oh, dev, keep)
+        name = f"{tag}_{4 * w}x{4 * h}"
+        runtimes[name], outputs[name] = R.Runtime(blob, 0, R.DTYPE_BF16, hooks=False), out_frame(fmt, 4 * w, 4 * h, dev, keep)
+        for (ow, oh) in sizes:
+            for fname, filt in filters:
+                name = f"{tag}_{ow}x{oh}" + ("" if filt == R.SCALE_TRIANGLE else "_" + fname)
+                rt = R.Runtime(blob, 0, R.DTYPE_BF16, hooks=False)
+                rt.set_output_size(ow, oh, filt)
+                runtimes[name], outputs[name] = rt, out_frame(fmt, ow, oh, dev, keep)
     torch.cuda.synchronize()
 
     def run(name, count):
@@ -96,7 +108,7 @@ def main():
             run(name, args.frames_per_round)
             rates[name].append(args.frames_per_round / (time.perf_counter() - t0))
     result = {"tool": "output_bench", "preset": args.preset, "dtype": "bf16", "input": f"nv12 {w}x{h}",
-              "frames_per_round": args.frames_per_round,
+              "frames_per_round": args.frames_per_round, "filters": [f for f, _ in filters],
               "frames_per_s": {k: {"median": round(float(np.median(v)), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
                                for k, v in rates.items()},
               "source_stage_frames": {k: runtimes[k].stat("source_stage_frames") for k in names}}

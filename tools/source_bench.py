@@ -9,7 +9,11 @@ and the other work on the machine are shared alike:
   nv12_masked   the same with the mask of tests/golden/obs_mask.png set as well: + blend, NV12 encoded from the blended frame
   bgrx_model    ju_process on model-size device BGRX frames through the direct path, for scale (the stage gives it up)
 
-Prints one JSON line.  --profile N instead runs N frames of nv12_masked only, for a `rocprofv3 --kernel-trace --stats`
+--filter NAME[,NAME...] (triangle, catmull-rom, mitchell; default triangle) chooses the filter of nv12_scaled and
+nv12_masked; with several names both exist once per filter, the name ending in the filter's (the triangle's has no suffix),
+all in the same process and the same rounds.
+
+Prints one JSON line.  --profile N instead runs N frames of nv12_masked (of every filter) only, for a `rocprofv3 --kernel-trace --stats`
 run (the program after `--`)."""
 
 import argparse
@@ -33,6 +37,7 @@ import source_reference as S  # noqa: E402
 import yuv_reference as Y  # noqa: E402
 
 CS = R.CS_BT709_LIMITED
+FILTERS = {"triangle": R.SCALE_TRIANGLE, "catmull-rom": R.SCALE_CATMULL_ROM, "mitchell": R.SCALE_MITCHELL}
 
 
 def nv12_device(frames, dev, keep):
@@ -53,7 +58,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--frames-per-round", type=int, default=300)
     ap.add_argument("--profile", type=int, default=0)
+    ap.add_argument("--filter", default="triangle")
     args = ap.parse_args()
+    filters = [(name, FILTERS[name]) for name in args.filter.split(",")]
+    suffix = lambda fname, filt: "" if filt == R.SCALE_TRIANGLE else "_" + fname
     sw, sh = (int(x) for x in args.source.split("x"))
     dev = torch.device("cuda", 0)
     torch.zeros(1, device=dev)
@@ -69,12 +77,15 @@ def main():
     out_nv12 = R.device_frame(R.FMT_NV12, 4 * w, 4 * h, out_planes, colorspace=CS)
     out_bgrx = torch.zeros((4 * h, 4 * w, 4), dtype=torch.uint8, device=dev)
     d_small = [torch.from_numpy(f).to(dev) for f in small]
-    runtimes = {name: R.Runtime(blob, 0, R.DTYPE_BF16, hooks=False) for name in ("nv12_model", "nv12_scaled", "nv12_masked", "bgrx_model")}
-    for name in ("nv12_scaled", "nv12_masked"):
-        runtimes[name].set_source_size(sw, sh)
-    runtimes["nv12_masked"].set_source_mask(mask)
-    inputs = {"nv12_model": nv12_device(small, dev, keep), "nv12_scaled": nv12_device(big, dev, keep)}
-    inputs["nv12_masked"] = inputs["nv12_scaled"]
+    scaled = [base + suffix(*f) for f in filters for base in ("nv12_scaled", "nv12_masked")]
+    runtimes = {name: R.Runtime(blob, 0, R.DTYPE_BF16, hooks=False) for name in ["nv12_model"] + scaled + ["bgrx_model"]}
+    inputs = {"nv12_model": nv12_device(small, dev, keep)}
+    big_frames = nv12_device(big, dev, keep)
+    for fname, filt in filters:
+        for base in ("nv12_scaled", "nv12_masked"):
+            runtimes[base + suffix(fname, filt)].set_source_size(sw, sh, filt)
+            inputs[base + suffix(fname, filt)] = big_frames
+        runtimes["nv12_masked" + suffix(fname, filt)].set_source_mask(mask)
     rb = runtimes["bgrx_model"]
     pairs = [(rb.device_image(t.data_ptr(), w, h), rb.device_image(out_bgrx.data_ptr(), 4 * w, 4 * h)) for t in d_small]
     for a, b in pairs:
@@ -92,8 +103,10 @@ def main():
             rt.process_frame(frames[i % len(frames)], out_nv12)
 
     if args.profile:
-        run("nv12_masked", args.profile)
-        print(json.dumps({"profiled": "nv12_masked", "frames": args.profile, "source": args.source}))
+        masked = ["nv12_masked" + suffix(*f) for f in filters]
+        for name in masked:
+            run(name, args.profile)
+        print(json.dumps({"profiled": masked, "frames": args.profile, "source": args.source}))
         return
     names = list(runtimes)
     for name in names:
@@ -105,7 +118,7 @@ def main():
             run(name, args.frames_per_round)
             rates[name].append(args.frames_per_round / (time.perf_counter() - t0))
     result = {"tool": "source_bench", "preset": args.preset, "dtype": "bf16", "source": args.source,
-              "frames_per_round": args.frames_per_round,
+              "frames_per_round": args.frames_per_round, "filters": [f for f, _ in filters],
               "frames_per_s": {k: {"median": round(float(np.median(v)), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
                                for k, v in rates.items()},
               "source_stage_frames": {k: runtimes[k].stat("source_stage_frames") for k in names}}
