@@ -75,6 +75,12 @@ ju::Frame toFrame(const ju_image *img) {
 	    img->height};
 }
 
+std::vector<ju::Frame> toFrames(const ju_image *images, int count) {
+	std::vector<ju::Frame> frames(static_cast<std::size_t>(count));
+	for (int i = 0; i < count; ++i) frames[static_cast<std::size_t>(i)] = toFrame(images + i);
+	return frames;
+}
+
 // A ju_frame as the engine's AnyFrame; BGRX frames exactly as toFrame makes them of a ju_image
 ju::AnyFrame toAnyFrame(const ju_frame *f) {
 	if (f == nullptr) throw std::invalid_argument("frame is NULL");
@@ -98,8 +104,6 @@ ju::AnyFrame toAnyFrame(const ju_frame *f) {
 	}
 	return a;
 }
-
-ju::Location locationOf(const ju::AnyFrame &f) { return f.yuv ? f.planes.location : f.bgrx.location; }
 
 ju::Engine &engineOf(ju_runtime *rt) {
 	if (rt == nullptr || !rt->engine) throw std::invalid_argument("runtime is NULL");
@@ -161,7 +165,7 @@ void ju_destroy(ju_runtime *runtime) {
 }
 
 int ju_process(ju_runtime *runtime, const ju_image *input, const ju_image *output) {
-	return guarded([&] { engineOf(runtime).process(toFrame(input), toFrame(output)); });
+	return guarded([&] { engineOf(runtime).process(ju::anyOf(toFrame(input)), ju::anyOf(toFrame(output))); });
 }
 
 int ju_process_batch(ju_runtime *runtime, const ju_image *inputs, const ju_image *outputs, int count) {
@@ -169,11 +173,7 @@ int ju_process_batch(ju_runtime *runtime, const ju_image *inputs, const ju_image
 		if (count < 0 || (count > 0 && (inputs == nullptr || outputs == nullptr))) {
 			throw std::invalid_argument("ju_process_batch: NULL images or a negative count");
 		}
-		std::vector<ju::Frame> in(static_cast<std::size_t>(count)), out(static_cast<std::size_t>(count));
-		for (int i = 0; i < count; ++i) {
-			in[i] = toFrame(inputs + i);
-			out[i] = toFrame(outputs + i);
-		}
+		const std::vector<ju::Frame> in = toFrames(inputs, count), out = toFrames(outputs, count);
 		engineOf(runtime).processBatch(in.data(), out.data(), count);
 	});
 }
@@ -200,11 +200,7 @@ int ju_prepare_batch(ju_runtime *runtime, const ju_image *inputs, const ju_image
 		if (count < 0 || (count > 0 && (inputs == nullptr || outputs == nullptr))) {
 			throw std::invalid_argument("ju_prepare_batch: NULL images or a negative count");
 		}
-		std::vector<ju::Frame> in(static_cast<std::size_t>(count)), out(static_cast<std::size_t>(count));
-		for (int i = 0; i < count; ++i) {
-			in[i] = toFrame(inputs + i);
-			out[i] = toFrame(outputs + i);
-		}
+		const std::vector<ju::Frame> in = toFrames(inputs, count), out = toFrames(outputs, count);
 		const int n = engineOf(runtime).prepareBatch(in.data(), out.data(), count);
 		if (captured) *captured = n;
 	});
@@ -220,19 +216,13 @@ int ju_enqueue(ju_runtime *runtime, const ju_image *input, const ju_image *outpu
 		if (in.location != ju::Location::Device || out.location != ju::Location::Device) {
 			throw std::invalid_argument("ju_enqueue needs JU_LOC_DEVICE images");
 		}
-		engineOf(runtime).enqueue(in, out);
+		engineOf(runtime).enqueue(ju::anyOf(in), ju::anyOf(out));
 	});
 }
 
 int ju_process_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame *output) {
 	return guarded([&] {
-		ju::Engine &e = engineOf(runtime);
-		const ju::AnyFrame in = toAnyFrame(input), out = toAnyFrame(output);
-		if (!in.yuv && !out.yuv) {
-			e.process(in.bgrx, out.bgrx);
-		} else {
-			e.processFrame(in, out);
-		}
+		engineOf(runtime).process(toAnyFrame(input), toAnyFrame(output));
 	});
 }
 
@@ -260,14 +250,10 @@ int ju_enqueue_frame(ju_runtime *runtime, const ju_frame *input, const ju_frame 
 	return guarded([&] {
 		ju::Engine &e = engineOf(runtime);
 		const ju::AnyFrame in = toAnyFrame(input), out = toAnyFrame(output);
-		if (locationOf(in) != ju::Location::Device || locationOf(out) != ju::Location::Device) {
+		if (ju::locationOf(in) != ju::Location::Device || ju::locationOf(out) != ju::Location::Device) {
 			throw std::invalid_argument("ju_enqueue_frame needs device frames");
 		}
-		if (!in.yuv && !out.yuv) {
-			e.enqueue(in.bgrx, out.bgrx);
-		} else {
-			e.enqueueFrame(in, out);
-		}
+		e.enqueue(in, out);
 	});
 }
 
@@ -561,19 +547,9 @@ int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_width, s
 		const int dw = static_cast<int>(dst_width), dh = static_cast<int>(dst_height);
 		const int sw = static_cast<int>(src_width), sh = static_cast<int>(src_height);
 		if (op == 0) {
-			const ju::ScaleAxisHost x = ju::buildScaleAxis(sw, dw), y = ju::buildScaleAxis(sh, dh);
-			auto upload = [](const ju::ScaleAxisHost &a, ju::DeviceBuffer *start, ju::DeviceBuffer *taps) {
-				*start = ju::DeviceBuffer(a.start.size() * sizeof(int));
-				start->upload(a.start.data(), a.start.size() * sizeof(int));
-				*taps = ju::DeviceBuffer(a.taps.size() * sizeof(std::uint16_t));
-				taps->upload(a.taps.data(), a.taps.size() * sizeof(std::uint16_t));
-			};
-			ju::DeviceBuffer xs, xt, ys, yt;
-			upload(x, &xs, &xt);
-			upload(y, &ys, &yt);
-			ju::launchScaleBgrx(static_cast<const std::uint8_t *>(src), src_stride, sw, sh, static_cast<std::uint8_t *>(dst),
-			    dst_stride, dw, dh, {xs.as<int>(), xt.as<std::uint16_t>()}, {ys.as<int>(), yt.as<std::uint16_t>()},
-			    ju::scaleSpan(x), nullptr);
+			ju::Scaler scale;
+			scale.build(src_width, src_height, dst_width, dst_height, ju::kScaleTriangle);
+			scale.scaleBgrx(static_cast<const std::uint8_t *>(src), src_stride, static_cast<std::uint8_t *>(dst), dst_stride, nullptr);
 			JU_HIP(hipStreamSynchronize(nullptr));
 			return;
 		}
@@ -605,19 +581,9 @@ int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_height, cons
 			if (dst == nullptr || src_width < 1 || src_height < 1 || src_width > kMost || src_height > kMost) {
 				throw std::invalid_argument("ju_debug_output: null buffer or a size outside 1 .. 32768");
 			}
-			const int sw = static_cast<int>(src_width), sh = static_cast<int>(src_height);
-			const ju::ScaleAxisHost x = ju::buildScaleAxis(sw, dw), y = ju::buildScaleAxis(sh, dh);
-			auto upload = [](const ju::ScaleAxisHost &a, ju::DeviceBuffer *start, ju::DeviceBuffer *taps) {
-				*start = ju::DeviceBuffer(a.start.size() * sizeof(int));
-				start->upload(a.start.data(), a.start.size() * sizeof(int));
-				*taps = ju::DeviceBuffer(a.taps.size() * sizeof(std::uint16_t));
-				taps->upload(a.taps.data(), a.taps.size() * sizeof(std::uint16_t));
-			};
-			ju::DeviceBuffer xs, xt, ys, yt;
-			upload(x, &xs, &xt);
-			upload(y, &ys, &yt);
-			ju::launchScaleState(src, sw, sh, static_cast<std::uint16_t *>(dst), dw, dh, {xs.as<int>(), xt.as<std::uint16_t>()},
-			    {ys.as<int>(), yt.as<std::uint16_t>()}, ju::scaleSpan(x), nullptr);
+			ju::Scaler scale;
+			scale.build(src_width, src_height, dst_width, dst_height, ju::kScaleTriangle);
+			scale.scaleState(src, static_cast<std::uint16_t *>(dst), nullptr);
 			JU_HIP(hipStreamSynchronize(nullptr));
 			return;
 		}
@@ -630,11 +596,7 @@ int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_height, cons
 		// (op 1 of the hook's checks: sizes, parity, null planes, sample alignment)
 		const ju::YuvPlanes p = hook.planes(*info, 1, dst_width, dst_height, src, static_cast<ptrdiff_t>(8 * dst_width), planes, strides);
 		for (int k = 0; k < info->planes; ++k) {  // strides of at least the plane's own row: a chroma row may be half a luma row
-			const size_t b = static_cast<size_t>(info->sampleBytes);
-			const size_t cw = info->sampling == 444 ? dst_width : dst_width / 2;
-			const size_t bytes = info->planes == 1 ? static_cast<size_t>(info->pixelBytes) * dst_width
-			    : (k == 0 || info->rgb()) ? dst_width * b : (info->planes == 2 ? 2 * cw : cw) * b;
-			const auto row = static_cast<ptrdiff_t>(bytes);
+			const auto row = static_cast<ptrdiff_t>(ju::planeShape(*info, dst_width, dst_height, k).rowBytes);
 			if (strides[k] > -row && strides[k] < row) hook.refuse("|stride| smaller than a row");
 		}
 		ju::launchEncodeFrame16(format, colorspace, static_cast<const std::uint16_t *>(src), p, dw, dh, nullptr);
@@ -674,24 +636,12 @@ int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t d
 		    dst_width > kMost || dst_height > kMost || src_width > kMost || src_height > kMost) {
 			throw std::invalid_argument("ju_debug_scale: null buffer or a size outside 1 .. 32768");
 		}
-		const int dw = static_cast<int>(dst_width), dh = static_cast<int>(dst_height);
-		const int sw = static_cast<int>(src_width), sh = static_cast<int>(src_height);
-		const ju::ScaleAxisHost x = ju::buildScaleAxis(sw, dw, filter), y = ju::buildScaleAxis(sh, dh, filter);
-		auto upload = [](const ju::ScaleAxisHost &a, ju::DeviceBuffer *start, ju::DeviceBuffer *taps) {
-			*start = ju::DeviceBuffer(a.start.size() * sizeof(int));
-			start->upload(a.start.data(), a.start.size() * sizeof(int));
-			*taps = ju::DeviceBuffer(a.taps.size() * sizeof(std::uint16_t));
-			taps->upload(a.taps.data(), a.taps.size() * sizeof(std::uint16_t));
-		};
-		ju::DeviceBuffer xs, xt, ys, yt;
-		upload(x, &xs, &xt);
-		upload(y, &ys, &yt);
-		const ju::ScaleAxisDev dx{xs.as<int>(), xt.as<std::uint16_t>(), filter}, dy{ys.as<int>(), yt.as<std::uint16_t>(), filter};
+		ju::Scaler scale;
+		scale.build(src_width, src_height, dst_width, dst_height, filter);
 		if (op == 0) {
-			ju::launchScaleBgrx(static_cast<const std::uint8_t *>(src), src_stride, sw, sh, static_cast<std::uint8_t *>(dst),
-			    dst_stride, dw, dh, dx, dy, ju::scaleSpan(x), nullptr);
+			scale.scaleBgrx(static_cast<const std::uint8_t *>(src), src_stride, static_cast<std::uint8_t *>(dst), dst_stride, nullptr);
 		} else {
-			ju::launchScaleState(src, sw, sh, static_cast<std::uint16_t *>(dst), dw, dh, dx, dy, ju::scaleSpan(x), nullptr);
+			scale.scaleState(src, static_cast<std::uint16_t *>(dst), nullptr);
 		}
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});

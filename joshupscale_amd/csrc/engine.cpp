@@ -78,18 +78,18 @@ DeviceChain &chainOf(int device) {
 }
 }  // namespace
 
-std::unique_lock<std::mutex> Engine::chainBegin() {
+std::unique_lock<std::mutex> Engine::chainBegin(bool resident) {
 	DeviceChain &c = chainOf(m_Device);
 	std::unique_lock<std::mutex> lock(c.mutex);
-	if (c.engines > 1 && m_Resident && c.last != nullptr && c.lastOwner != this) {
+	if (c.engines > 1 && resident && c.last != nullptr && c.lastOwner != this) {
 		JU_HIP(hipStreamWaitEvent(m_Stream, c.last, 0));
 	}
 	return lock;
 }
 
-void Engine::chainEnd(std::unique_lock<std::mutex> &lock) {
+void Engine::chainEnd(std::unique_lock<std::mutex> &lock, bool resident) {
 	DeviceChain &c = chainOf(m_Device);
-	if (c.engines > 1 && m_Resident) {
+	if (c.engines > 1 && resident) {
 		m_FrameDone.record(m_Stream);
 		c.last = m_FrameDone.get();
 		c.lastOwner = this;
@@ -1048,8 +1048,8 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 	// variant (the frame is pre_warp)
 	m_HbdFromState = !(c.normalizeBrightness && c.recurrent()) && !c.outputsPreWarp();
 	// host YUV frames (ju_process_frame): their planes, rows padded to 64 bytes
-	m_YuvInStage = DeviceBuffer(yuvStageBytes(W, H));
-	m_YuvOutStage = DeviceBuffer(yuvStageBytes(4 * W, 4 * H));
+	m_YuvInStage = DeviceBuffer(yuvStageBytes(kFormatTable, W, H));
+	m_YuvOutStage = DeviceBuffer(yuvStageBytes(kFormatTable, 4 * W, 4 * H));
 	if (!c.recurrent()) {
 		// flow-free: no frame history, no flow tensors, no state ping-pong -- one scratch state for the tail's
 		// HR output, which nothing reads; gen_in's slots other than 12..14 stay zero for good (lr_pack)
@@ -1330,19 +1330,6 @@ void Engine::maybeRestoreResident() {
 	}
 }
 
-namespace {
-AnyFrame anyOf(const Frame &f) {
-	AnyFrame a;
-	a.bgrx = f;
-	return a;
-}
-std::vector<AnyFrame> anyOf(const Frame *f, int n) {
-	std::vector<AnyFrame> a(static_cast<std::size_t>(std::max(n, 0)));
-	for (int i = 0; i < n; ++i) a[static_cast<std::size_t>(i)].bgrx = f[i];
-	return a;
-}
-}  // namespace
-
 void Engine::reset() {
 	DeviceGuard g(m_Device);
 	if (m_Config.recurrent()) {  // (a flow-free model has no state: nothing to zero)
@@ -1359,534 +1346,6 @@ FrameSize Engine::frameSize() const {
 	const auto w = static_cast<std::size_t>(m_Config.frameWidth);
 	const auto h = static_cast<std::size_t>(m_Config.frameHeight);
 	return {w, h, w * 4, h * 4};
-}
-
-namespace {
-// Scoped map of a graphics resource on the engine's stream (cuda.h:310-349 GraphicsResource):
-// unmapped again when the copy has been enqueued, also when that throws.
-struct MappedResource {
-	GraphicsHandle *h;
-	hipStream_t stream;
-	GraphicsArray array;
-	MappedResource(void *handle, hipStream_t s) : h(static_cast<GraphicsHandle *>(handle)), stream(s) {
-		if (h == nullptr || h->backend == nullptr) throw std::invalid_argument("processImage: NULL graphics resource");
-		array = h->backend->map(h->resource, stream);
-	}
-	~MappedResource() { h->backend->unmap(h->resource, stream); }
-	MappedResource(const MappedResource &) = delete;
-	MappedResource &operator=(const MappedResource &) = delete;
-};
-}  // namespace
-
-void Engine::stageIn(const Frame &in) {
-	const FrameSize fs = frameSize();
-	if (in.location == Location::GraphicsResource) {
-		// map -> texture array -> staging buffer -> unmap (cuda_convert.h:57-77,
-		// cuda_convert.cc.cu:380-397); the array's own extent is what counts
-		MappedResource m(in.ptr, m_Stream);
-		if (!m.array.fourBytes || m.array.width != fs.inputWidth || m.array.height != fs.inputHeight ||
-		    in.width != fs.inputWidth || in.height != fs.inputHeight) {
-			throw std::invalid_argument("processImage: input texture must be " + std::to_string(fs.inputWidth) + "x" +
-			                            std::to_string(fs.inputHeight) + " with four 8-bit channels");
-		}
-		m.h->backend->copyFromArray(m_InStage.get(), fs.inputWidth * 4, m.array, fs.inputWidth * 4, fs.inputHeight,
-		    m_Stream);
-		return;
-	}
-	if (in.ptr == nullptr || in.width != fs.inputWidth || in.height != fs.inputHeight) {
-		throw std::invalid_argument("processImage: input image must be exactly " +
-		                            std::to_string(fs.inputWidth) + "x" +
-		                            std::to_string(fs.inputHeight));
-	}
-	const std::size_t rowBytes = fs.inputWidth * 4;
-	const std::size_t rows = fs.inputHeight;
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	auto *dst = m_InStage.as<std::uint8_t>();
-	auto *src = static_cast<std::uint8_t *>(in.ptr);
-	if (in.stride > -plain && in.stride < plain) {
-		throw std::invalid_argument("processImage: |stride| smaller than a row");
-	}
-	switch (in.location) {
-	case Location::Host:
-		if (in.stride == plain) {
-			JU_HIP(hipMemcpyAsync(dst, src, rowBytes * rows, hipMemcpyHostToDevice, m_Stream));
-		} else if (in.stride > 0) {
-			JU_HIP(hipMemcpy2DAsync(dst, rowBytes, src, static_cast<std::size_t>(in.stride),
-			    rowBytes, rows, hipMemcpyHostToDevice, m_Stream));
-		} else {
-			// bottom-up frame (AviSynth RGB32, avisynth_plugin/src/main.cc:125-142): upload
-			// the rows in memory order, then flip on the device.
-			auto *raw = m_RawStage.as<std::uint8_t>();
-			const std::uint8_t *lowest = src + static_cast<std::ptrdiff_t>(rows - 1) * in.stride;
-			JU_HIP(hipMemcpy2DAsync(raw, rowBytes, lowest, static_cast<std::size_t>(-in.stride),
-			    rowBytes, rows, hipMemcpyHostToDevice, m_Stream));
-			launchCopyRows(raw + (rows - 1) * rowBytes, -plain, dst, plain, rowBytes, rows, m_Stream);
-		}
-		break;
-	case Location::Device:
-		if (in.stride == plain) {
-			JU_HIP(hipMemcpyAsync(dst, src, rowBytes * rows, hipMemcpyDeviceToDevice, m_Stream));
-		} else {
-			launchCopyRows(src, in.stride, dst, plain, rowBytes, rows, m_Stream);
-		}
-		break;
-	default:
-		throw std::invalid_argument(
-		    "processImage: GRAPHICS_RESOURCE images are not supported by this runtime");
-	}
-}
-
-void Engine::stageOut(const Frame &out, std::size_t width, std::size_t height, const std::uint8_t *src, std::uint8_t *raw) {
-	const FrameSize fs{0, 0, width, height};  // (the frame's own size: the model's output, or the output size set)
-	if (out.location == Location::GraphicsResource) {  // cuda_convert.cc.cu:419-436
-		MappedResource m(out.ptr, m_Stream);
-		if (!m.array.fourBytes || m.array.width != fs.outputWidth || m.array.height != fs.outputHeight ||
-		    out.width != fs.outputWidth || out.height != fs.outputHeight) {
-			throw std::invalid_argument("processImage: output texture must be " + std::to_string(fs.outputWidth) + "x" +
-			                            std::to_string(fs.outputHeight) + " with four 8-bit channels");
-		}
-		m.h->backend->copyToArray(m.array, src, fs.outputWidth * 4, fs.outputWidth * 4, fs.outputHeight, m_Stream);
-		return;
-	}
-	if (out.ptr == nullptr || out.width != fs.outputWidth || out.height != fs.outputHeight) {
-		throw std::invalid_argument("processImage: output image must be exactly " +
-		                            std::to_string(fs.outputWidth) + "x" +
-		                            std::to_string(fs.outputHeight));
-	}
-	const std::size_t rowBytes = fs.outputWidth * 4;
-	const std::size_t rows = fs.outputHeight;
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	auto *dst = static_cast<std::uint8_t *>(out.ptr);
-	if (out.stride > -plain && out.stride < plain) {
-		throw std::invalid_argument("processImage: |stride| smaller than a row");
-	}
-	switch (out.location) {
-	case Location::Host:
-		if (out.stride == plain) {
-			JU_HIP(hipMemcpyAsync(dst, src, rowBytes * rows, hipMemcpyDeviceToHost, m_Stream));
-		} else if (out.stride > 0) {
-			JU_HIP(hipMemcpy2DAsync(dst, static_cast<std::size_t>(out.stride), src, rowBytes,
-			    rowBytes, rows, hipMemcpyDeviceToHost, m_Stream));
-		} else {
-			launchCopyRows(src, plain, raw + (rows - 1) * rowBytes, -plain, rowBytes, rows, m_Stream);
-			std::uint8_t *lowest = dst + static_cast<std::ptrdiff_t>(rows - 1) * out.stride;
-			JU_HIP(hipMemcpy2DAsync(lowest, static_cast<std::size_t>(-out.stride), raw, rowBytes,
-			    rowBytes, rows, hipMemcpyDeviceToHost, m_Stream));
-		}
-		break;
-	case Location::Device:
-		if (out.stride == plain) {
-			JU_HIP(hipMemcpyAsync(dst, src, rowBytes * rows, hipMemcpyDeviceToDevice, m_Stream));
-		} else {
-			launchCopyRows(src, plain, dst, out.stride, rowBytes, rows, m_Stream);
-		}
-		break;
-	default:
-		throw std::invalid_argument(
-		    "processImage: GRAPHICS_RESOURCE images are not supported by this runtime");
-	}
-}
-
-namespace {
-// Plane k of a frame of the given size: rows, bytes per row (planar: Y, U, V or R, G, B; semi-planar: Y, UV; packed: one
-// plane of pixelBytes per pixel -- YUY2 / UYVY 2, BGR24 3, RGBX 4, BGRX64 8, BGR96F 12; samples of 1, 2 or 4 bytes)
-struct PlaneShape {
-	std::size_t rows, rowBytes;
-};
-// A format = sampling (420 / 422 / 444; 0: RGB, every plane full size) x storage (planar / semi-planar Y, UV / packed: one
-// plane) x sample size: all of it from the one table, formatInfo (kernels.h)
-PlaneShape planeShape(PixelFormat f, std::size_t w, std::size_t h, int k) {
-	const YuvFormatInfo &info = formatInfo(f);
-	const auto b = static_cast<std::size_t>(info.sampleBytes);
-	if (info.planes == 1) return {h, static_cast<std::size_t>(info.pixelBytes) * w};
-	if (k == 0 || info.rgb()) return {h, w * b};
-	const std::size_t cw = info.sampling == 444 ? w : w / 2;  // chroma samples per row (a semi-planar row holds both planes')
-	return {info.perRow() ? h : h / 2, (info.planes == 2 ? 2 * cw : cw) * b};
-}
-int planeCount(PixelFormat f) { return formatInfo(f).planes; }
-std::size_t stagePitch(std::size_t rowBytes) { return (rowBytes + 63) / 64 * 64; }
-
-// The caller's device planes as a conversion kernel takes them
-YuvPlanes callerPlanes(const YuvFrame &f) {
-	YuvPlanes pl;
-	std::uint8_t **plane[3] = {&pl.y, &pl.u, &pl.v};
-	std::ptrdiff_t *stride[3] = {&pl.yStride, &pl.uStride, &pl.vStride};
-	for (int k = 0; k < planeCount(f.format); ++k) {
-		*plane[k] = static_cast<std::uint8_t *>(f.planes[k]);
-		*stride[k] = f.strides[k];
-	}
-	return pl;
-}
-
-// A host frame's planes in a device staging buffer: plane after plane, rows padded to stagePitch, in the caller's MEMORY
-// order -- a bottom-up plane stays bottom-up there and the kernel addresses it from its last row with a negative pitch.
-YuvPlanes stagedPlanes(const YuvFrame &f, std::uint8_t *stage) {
-	YuvPlanes pl;
-	std::uint8_t **plane[3] = {&pl.y, &pl.u, &pl.v};
-	std::ptrdiff_t *stride[3] = {&pl.yStride, &pl.uStride, &pl.vStride};
-	for (int k = 0; k < planeCount(f.format); ++k) {
-		const PlaneShape p = planeShape(f.format, f.width, f.height, k);
-		const auto pitch = static_cast<std::ptrdiff_t>(stagePitch(p.rowBytes));
-		const bool up = f.strides[k] > 0;
-		*plane[k] = up ? stage : stage + static_cast<std::ptrdiff_t>(p.rows - 1) * pitch;
-		*stride[k] = up ? pitch : -pitch;
-		stage += pitch * static_cast<std::ptrdiff_t>(p.rows);
-	}
-	return pl;
-}
-
-// The pageable copies between a host frame's planes and that staging layout, plane by plane on `stream`
-void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream_t stream) {
-	for (int k = 0; k < planeCount(f.format); ++k) {
-		const PlaneShape p = planeShape(f.format, f.width, f.height, k);
-		const std::size_t pitch = stagePitch(p.rowBytes);
-		auto *first = static_cast<std::uint8_t *>(f.planes[k]);
-		const std::ptrdiff_t s = f.strides[k];
-		std::uint8_t *lowest = s > 0 ? first : first + static_cast<std::ptrdiff_t>(p.rows - 1) * s;
-		const std::size_t hostPitch = static_cast<std::size_t>(s > 0 ? s : -s);
-		if (toDevice) {
-			JU_HIP(hipMemcpy2DAsync(stage, pitch, lowest, hostPitch, p.rowBytes, p.rows, hipMemcpyHostToDevice, stream));
-		} else {
-			JU_HIP(hipMemcpy2DAsync(lowest, hostPitch, stage, pitch, p.rowBytes, p.rows, hipMemcpyDeviceToHost, stream));
-		}
-		stage += pitch * p.rows;
-	}
-}
-}  // namespace
-
-// bytes of a staging buffer that holds a frame of the size in any format of the table (BGR96F and the three f32 planes
-// of RGBPS take the most: 12 bytes per pixel and the row padding)
-std::size_t Engine::yuvStageBytes(std::size_t w, std::size_t h) {
-	std::size_t most = 0;
-	for (int value = 1; value < kFormatValueEnd; ++value) {
-		if (yuvFormatInfo(value) == nullptr) continue;
-		const auto f = static_cast<PixelFormat>(value);
-		std::size_t n = 0;
-		for (int k = 0; k < planeCount(f); ++k) {
-			const PlaneShape p = planeShape(f, w, h, k);
-			n += stagePitch(p.rowBytes) * p.rows;
-		}
-		most = std::max(most, n);
-	}
-	return most;
-}
-
-// Everything a frame call can refuse, checked before anything is launched (the BGRX side repeats what stageIn /
-// stageOut would throw, so that a refused call has not run the step).
-void Engine::checkFrame(const AnyFrame &f, bool input) const {
-	const FrameSize fs = frameSize();
-	const bool scaled = input && m_SrcW != 0;  // (input frames are the source's size while one is set)
-	const bool resized = !input && m_OutW != 0;  // (and output frames the output size)
-	const std::size_t w = scaled ? m_SrcW : (resized ? m_OutW : (input ? fs.inputWidth : fs.outputWidth));
-	const std::size_t h = scaled ? m_SrcH : (resized ? m_OutH : (input ? fs.inputHeight : fs.outputHeight));
-	const std::string side = input ? "input" : "output";
-	const std::string size = std::to_string(w) + "x" + std::to_string(h) +
-	                         (scaled ? " (the source size set)" : (resized ? " (the output size set)" : ""));
-	if (!f.yuv) {
-		const Frame &b = f.bgrx;
-		if (resized && b.location == Location::GraphicsResource) {
-			throw std::invalid_argument("processFrame: graphics resources cannot be outputs while an output size is set "
-			                            "(the scaler writes host or device memory)");
-		}
-		if (scaled && b.location == Location::GraphicsResource) {
-			throw std::invalid_argument("processFrame: graphics resources cannot be inputs while a source size is set "
-			                            "(the scaler reads host or device memory)");
-		}
-		if (b.location == Location::GraphicsResource) {
-			if (b.ptr == nullptr) throw std::invalid_argument("processFrame: NULL graphics resource");
-			return;  // (the texture's own extent is checked when it is mapped)
-		}
-		if (b.ptr == nullptr || b.width != w || b.height != h) {
-			throw std::invalid_argument("processFrame: " + side + " image must be exactly " + size);
-		}
-		const auto row = static_cast<std::ptrdiff_t>(w * 4);
-		if (b.stride > -row && b.stride < row) throw std::invalid_argument("processFrame: |stride| smaller than a row");
-		return;
-	}
-	const YuvFrame &y = f.planes;
-	const YuvFormatInfo *known = yuvFormatInfo(fmt(y.format));
-	if (known == nullptr) throw std::invalid_argument("processFrame: unknown " + side + " pixel format");
-	const YuvFormatInfo &info = *known;
-	if (!info.rgb() && (y.colorspace < 0 || y.colorspace > 3)) {  // (an RGB frame has none: the field is ignored)
-		throw std::invalid_argument("processFrame: unknown " + side + " colour space " + std::to_string(y.colorspace));
-	}
-	if (y.location != Location::Host && y.location != Location::Device) {
-		throw std::invalid_argument(std::string("processFrame: ") + info.name + " " + side +
-		                            " frames must be host or device memory (no graphics resources)");
-	}
-	if (info.sampling == 420 && (y.width % 2 || y.height % 2)) {
-		throw std::invalid_argument(std::string("processFrame: ") + info.name + " needs an even width and height");
-	}
-	if (info.sampling == 422 && y.width % 2) {
-		throw std::invalid_argument(std::string("processFrame: ") + info.name + " (4:2:2) needs an even width");
-	}
-	if (y.width != w || y.height != h) {
-		throw std::invalid_argument("processFrame: " + side + " frame must be exactly " + size);
-	}
-	for (int k = 0; k < info.planes; ++k) {
-		if (y.planes[k] == nullptr) {
-			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) + " is NULL");
-		}
-		const auto sample = static_cast<std::size_t>(info.sampleBytes);
-		if (sample > 1 && (reinterpret_cast<std::uintptr_t>(y.planes[k]) % sample != 0 ||
-		                   y.strides[k] % static_cast<std::ptrdiff_t>(sample) != 0)) {
-			throw std::invalid_argument(std::string("processFrame: ") + side + " plane " + std::to_string(k) + ": " +
-			                            info.name + " samples are " + (sample == 2 ? "16-bit" : "32-bit") +
-			                            " words -- the plane's address and its stride must be multiples of " +
-			                            std::to_string(sample));
-		}
-		const auto row = static_cast<std::ptrdiff_t>(planeShape(y.format, w, h, k).rowBytes);
-		if (y.strides[k] > -row && y.strides[k] < row) {
-			throw std::invalid_argument("processFrame: " + side + " plane " + std::to_string(k) +
-			                            ": |stride| smaller than a row");
-		}
-	}
-}
-
-void Engine::stageInYuv(const YuvFrame &in) {
-	const std::size_t w = frameSize().inputWidth;
-	const bool host = in.location != Location::Device;
-	if (host) copyPlanes(in, m_YuvInStage.as<std::uint8_t>(), true, m_Stream);
-	const YuvPlanes pl = host ? stagedPlanes(in, m_YuvInStage.as<std::uint8_t>()) : callerPlanes(in);
-	decodeYuv(in.format, in.colorspace, pl, m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(w * 4));
-}
-
-// one decode launch on the engine's stream: planes of an input-sized frame -> BGRX rows
-void Engine::decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::uint8_t *bgrx,
-    std::ptrdiff_t bgrxStride, std::size_t width, std::size_t height) {
-	const FrameSize fs = frameSize();
-	const int w = static_cast<int>(width ? width : fs.inputWidth), h = static_cast<int>(height ? height : fs.inputHeight);
-	launchDecodeFrame(fmt(format), colorspace, planes, bgrx, bgrxStride, w, h, m_Stream);
-}
-
-bool Engine::deepFromState(PixelFormat format) const {
-	// (a mask: the blended frame exists in 8 bits only)
-	return m_HbdFromState && m_MaskW == 0 && formatInfo(format).deep();
-}
-
-// one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit YUV or
-// a deep RGB format of a runtime whose state is the frame in float (m_HbdFromState), the f16 state that frame left -- -> planes
-void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::size_t width, std::size_t height,
-    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16) {
-	const int w = static_cast<int>(width), h = static_cast<int>(height);
-	if (!deepFromState(format)) {
-		launchEncodeFrame(fmt(format), colorspace, bgrx, bgrxStride, planes, w, h, m_Stream);
-	} else if (frame16 != nullptr) {  // (the output stage: the state's samples, scaled)
-		launchEncodeFrame16(fmt(format), colorspace, frame16, planes, w, h, m_Stream);
-	} else {
-		launchEncodeState(fmt(format), colorspace, state, planes, w, h, m_Stream);
-	}
-}
-
-// the frame of out.width x out.height -- its dense BGRX rows, or for deepFromState formats the state or the 16-bit frame
-void Engine::stageOutYuv(const YuvFrame &out, const std::uint8_t *bgrx, const void *state, const std::uint16_t *frame16,
-    std::uint8_t *stage) {
-	const bool host = out.location == Location::Host;
-	// (a host frame: the kernel writes the staging buffer in the caller's row order, copied out below)
-	const YuvPlanes pl = host ? stagedPlanes(out, stage) : callerPlanes(out);
-	encodeYuv(out.format, out.colorspace, pl, out.width, out.height, bgrx, static_cast<std::ptrdiff_t>(out.width * 4), state,
-	    frame16);
-	if (host) copyPlanes(out, stage, false, m_Stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Source stage (docs/source_stage.md).  What the reference's OBS filter does around processImage in its graphics API
-// (obs_plugin/src/filter.cc:351-379: any source drawn into the model's input texture; :393-402 with blend.effect: the
-// point-sampled source drawn back over the output through mask.png), as two kernels around the staged graph of
-// submitFrame: scale_bgrx_kernel fills m_InStage from the source frame, mask_blend_kernel rewrites m_OutStage.  Both
-// settings are per runtime and opt-in; neither touches a captured graph, the state or the frame history.
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-// one device buffer per axis of the scaler: the start indices, then the taps
-DeviceBuffer uploadScaleAxis(const ScaleAxisHost &a) {
-	const std::size_t startBytes = a.start.size() * sizeof(int), tapBytes = a.taps.size() * sizeof(std::uint16_t);
-	std::vector<unsigned char> host(startBytes + tapBytes);
-	std::memcpy(host.data(), a.start.data(), startBytes);
-	std::memcpy(host.data() + startBytes, a.taps.data(), tapBytes);
-	DeviceBuffer buf(host.size());
-	buf.upload(host.data(), host.size());
-	return buf;
-}
-ScaleAxisDev scaleAxisDev(const DeviceBuffer &buf, const ScaleAxisHost &a) {
-	return {buf.as<int>(), reinterpret_cast<const std::uint16_t *>(buf.as<int>() + a.start.size()), a.filter};
-}
-}  // namespace
-
-void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
-	DeviceGuard g(m_Device);
-	const std::string unknown = scaleFilterProblem(filter);
-	if (!unknown.empty()) throw std::invalid_argument("ju_set_source_size: " + unknown);
-	if (width == 0 && height == 0) {
-		m_Stream.synchronize();  // (enqueued frames may still read the tables)
-		m_SrcW = m_SrcH = 0;
-		m_SrcFilter = 0;
-		m_ScaleX = DeviceBuffer();
-		m_ScaleY = DeviceBuffer();
-		m_SrcStage = DeviceBuffer();
-		m_SrcYuvStage = DeviceBuffer();
-		return;
-	}
-	const FrameSize fs = frameSize();
-	const std::string problem = sourceSizeProblem(width, height, fs.inputWidth, fs.inputHeight, filter);
-	if (!problem.empty()) throw std::invalid_argument("ju_set_source_size: " + problem);
-	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(width), static_cast<int>(fs.inputWidth), filter);
-	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(height), static_cast<int>(fs.inputHeight), filter);
-	DeviceBuffer bx = uploadScaleAxis(x), by = uploadScaleAxis(y);
-	DeviceBuffer stage(width * height * 4), yuvStage(yuvStageBytes(width, height));
-	m_Stream.synchronize();
-	m_ScaleX = std::move(bx);
-	m_ScaleY = std::move(by);
-	m_SrcStage = std::move(stage);
-	m_SrcYuvStage = std::move(yuvStage);
-	m_ScaleXDev = scaleAxisDev(m_ScaleX, x);
-	m_ScaleYDev = scaleAxisDev(m_ScaleY, y);
-	m_ScaleSpan = scaleSpan(x);
-	m_SrcW = width;
-	m_SrcH = height;
-	m_SrcFilter = filter;
-}
-
-void Engine::sourceSize(std::size_t *width, std::size_t *height) const {
-	if (width) *width = m_SrcW;
-	if (height) *height = m_SrcH;
-}
-
-void Engine::setSourceMask(const Frame *mask) {
-	DeviceGuard g(m_Device);
-	if (mask == nullptr) {
-		m_Stream.synchronize();
-		m_Mask = DeviceBuffer();
-		m_MaskW = m_MaskH = 0;
-		m_MaskStride = 0;
-		return;
-	}
-	if (mask->location != Location::Host && mask->location != Location::Device) {
-		throw std::invalid_argument("ju_set_source_mask: the mask must be host or device memory");
-	}
-	constexpr std::size_t kMaskMax = 16384;
-	if (mask->ptr == nullptr || mask->width < 1 || mask->height < 1 || mask->width > kMaskMax || mask->height > kMaskMax) {
-		throw std::invalid_argument("ju_set_source_mask: the mask must be 1 .. 16384 pixels on each axis");
-	}
-	const std::size_t rowBytes = mask->width * 4;
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	if (mask->stride > -plain && mask->stride < plain) {
-		throw std::invalid_argument("ju_set_source_mask: |stride| smaller than a row");
-	}
-	// copied once, in the caller's memory order (a bottom-up mask stays bottom-up and is read with a negative stride)
-	DeviceBuffer buf(rowBytes * mask->height);
-	const bool up = mask->stride > 0;
-	const auto *first = static_cast<const std::uint8_t *>(mask->ptr);
-	const std::uint8_t *lowest = up ? first : first + static_cast<std::ptrdiff_t>(mask->height - 1) * mask->stride;
-	JU_HIP(hipMemcpy2D(buf.get(), rowBytes, lowest, static_cast<std::size_t>(up ? mask->stride : -mask->stride), rowBytes,
-	    mask->height, mask->location == Location::Host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
-	m_Stream.synchronize();
-	m_Mask = std::move(buf);
-	m_MaskW = mask->width;
-	m_MaskH = mask->height;
-	m_MaskStride = up ? plain : -plain;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Output stage (docs/output_stage.md).  What the reference's OBS caller gets from OBS's canvas scaling behind
-// processImage: the upscaled frame at any size.  Behind the staged graph and the mask blend of submitFrame the frame is
-// scaled by the source stage's scaler (the triangle or a cubic filter) with the output axes' tables: the 8-bit frame in m_OutStage by
-// scale_bgrx_kernel, or -- for a deep format that is encoded from the state (deepFromState) -- the state's 16-bit samples
-// by scale_state_kernel into m_OutScaled16, which launchEncodeFrame16 encodes.  Nothing of the step itself changes.
-// ---------------------------------------------------------------------------------------------------------------
-void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
-	DeviceGuard g(m_Device);
-	const FrameSize fs = frameSize();
-	const bool off = width == 0 && height == 0;
-	const std::string problem = outputSizeProblem(off ? fs.outputWidth : width, off ? fs.outputHeight : height, fs.outputWidth,
-	    fs.outputHeight, filter);
-	if (!problem.empty()) throw std::invalid_argument("ju_set_output_size: " + problem);
-	if (off) {
-		m_Stream.synchronize();  // (enqueued frames may still read the tables and write the buffers)
-		m_OutW = m_OutH = 0;
-		m_OutFilter = 0;
-		for (DeviceBuffer *b : {&m_OutScaleX, &m_OutScaleY, &m_OutScaled8, &m_OutScaled16, &m_OutYuvStage, &m_OutRawStage}) {
-			*b = DeviceBuffer();
-		}
-		return;
-	}
-	const ScaleAxisHost x = buildScaleAxis(static_cast<int>(fs.outputWidth), static_cast<int>(width), filter);
-	const ScaleAxisHost y = buildScaleAxis(static_cast<int>(fs.outputHeight), static_cast<int>(height), filter);
-	DeviceBuffer bx = uploadScaleAxis(x), by = uploadScaleAxis(y);
-	DeviceBuffer scaled8(width * height * 4), scaled16(width * height * 8), raw(width * height * 4);
-	DeviceBuffer yuvStage(yuvStageBytes(width, height));
-	m_Stream.synchronize();
-	m_OutScaleX = std::move(bx);
-	m_OutScaleY = std::move(by);
-	m_OutScaled8 = std::move(scaled8);
-	m_OutScaled16 = std::move(scaled16);
-	m_OutRawStage = std::move(raw);
-	m_OutYuvStage = std::move(yuvStage);
-	m_OutScaleXDev = scaleAxisDev(m_OutScaleX, x);
-	m_OutScaleYDev = scaleAxisDev(m_OutScaleY, y);
-	m_OutScaleSpan = scaleSpan(x);
-	m_OutW = width;
-	m_OutH = height;
-	m_OutFilter = filter;
-}
-
-void Engine::outputSize(std::size_t *width, std::size_t *height) const {
-	if (width) *width = m_OutW;
-	if (height) *height = m_OutH;
-}
-
-// The stage-out of a frame while an output size is set: scale, then copy or encode at output size.  A device BGRX image
-// is written in place (the kernel takes any alignment and signed stride); a host image and YUV planes go through the
-// scaled staging buffers.
-void Engine::stageOutScaled(const AnyFrame &out) {
-	const FrameSize fs = frameSize();
-	const int mw = static_cast<int>(fs.outputWidth), mh = static_cast<int>(fs.outputHeight);
-	const int ow = static_cast<int>(m_OutW), oh = static_cast<int>(m_OutH);
-	auto scale8 = [&](std::uint8_t *dst, std::ptrdiff_t stride) {
-		launchScaleBgrx(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4), mw, mh, dst, stride, ow,
-		    oh, m_OutScaleXDev, m_OutScaleYDev, m_OutScaleSpan, m_Stream);
-	};
-	auto *scaled8 = m_OutScaled8.as<std::uint8_t>();
-	const auto plain = static_cast<std::ptrdiff_t>(m_OutW * 4);
-	if (!out.yuv) {
-		const Frame &b = out.bgrx;
-		if (b.location == Location::Device) return scale8(static_cast<std::uint8_t *>(b.ptr), b.stride);
-		scale8(scaled8, plain);
-		return stageOut(b, m_OutW, m_OutH, scaled8, m_OutRawStage.as<std::uint8_t>());
-	}
-	auto *yuvStage = m_OutYuvStage.as<std::uint8_t>();
-	if (deepFromState(out.planes.format)) {
-		auto *scaled16 = m_OutScaled16.as<std::uint16_t>();
-		launchScaleState(m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get(), mw, mh, scaled16, ow, oh, m_OutScaleXDev,
-		    m_OutScaleYDev, m_OutScaleSpan, m_Stream);
-		return stageOutYuv(out.planes, nullptr, nullptr, scaled16, yuvStage);
-	}
-	scale8(scaled8, plain);
-	stageOutYuv(out.planes, scaled8, nullptr, nullptr, yuvStage);
-}
-
-// The input of a frame while a source size is set, as BGRX rows at source size: a device image is read where it is, a
-// host image is uploaded in its memory order, YUV planes are decoded by the existing conversion, unchanged.
-Engine::SourceView Engine::stageInSource(const AnyFrame &in) {
-	const std::size_t rowBytes = m_SrcW * 4;
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	auto *stage = m_SrcStage.as<std::uint8_t>();
-	if (in.yuv) {
-		const YuvFrame &y = in.planes;
-		const bool host = y.location != Location::Device;
-		if (host) copyPlanes(y, m_SrcYuvStage.as<std::uint8_t>(), true, m_Stream);
-		const YuvPlanes pl = host ? stagedPlanes(y, m_SrcYuvStage.as<std::uint8_t>()) : callerPlanes(y);
-		decodeYuv(y.format, y.colorspace, pl, stage, plain, m_SrcW, m_SrcH);
-		return {stage, plain};
-	}
-	const Frame &b = in.bgrx;
-	auto *src = static_cast<std::uint8_t *>(b.ptr);
-	if (b.location == Location::Device) return {src, b.stride};
-	const bool up = b.stride > 0;
-	const std::uint8_t *lowest = up ? src : src + static_cast<std::ptrdiff_t>(m_SrcH - 1) * b.stride;
-	JU_HIP(hipMemcpy2DAsync(stage, rowBytes, lowest, static_cast<std::size_t>(up ? b.stride : -b.stride), rowBytes, m_SrcH,
-	    hipMemcpyHostToDevice, m_Stream));
-	if (up) return {stage, plain};
-	return {stage + static_cast<std::ptrdiff_t>(m_SrcH - 1) * plain, -plain};
 }
 
 bool Engine::directEligible(const Frame &in, const Frame &out) const {
@@ -1979,7 +1438,7 @@ int Engine::prepareFrames(const Frame &in, const Frame &out) {
 		}
 		m_RegisteredPairs.insert(pair);
 	}
-	std::unique_lock<std::mutex> chain = chainBegin();  // (no capture while another engine's constructor drains the device)
+	std::unique_lock<std::mutex> chain = chainBegin(m_Resident);  // (no capture while another engine's constructor drains the device)
 	const FrameIO keep = m_IO;
 	m_IO.in = static_cast<const std::uint8_t *>(in.ptr);
 	m_IO.inStride = in.stride;
@@ -2004,768 +1463,6 @@ int Engine::prepareFrames(const Frame &in, const Frame &out) {
 	}
 	m_IO = keep;
 	return captured;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Frame look-ahead.  The flow net reads LR frames only -- never the HR state (models.py:790, 823: its input is the
-// packed history of the last num_flow_inputs frames) -- so the flow fields of n consecutive frames can be computed
-// before the first of them is upscaled: ONE pass of the flow net's eight launches over n frames instead of n passes.
-// At 480x270 each of those launches is ONE round of 136-240 workgroups on 256 CUs -- a 7-24 us latency chain (weights,
-// staging, conv A, conv B, stores) with most SIMDs idle most of the time (0.3-0.6 waves per SIMD,
-// profiles/r05_pmc_stall_flow.txt): over 8 frames the same launches take 62 instead of 105 us per frame
-// (profiles/r05_flow_layers_pass.txt; priced beforehand by tools/probes/flow_batch_estimate.py), and a pass pays one
-// synchronisation instead of eight: 2163 -> 2461 frames/s (profiles/r05_lookahead_bench_box_a.txt).  The recurrent part -- warp, tower,
-// tail -- stays strictly frame by frame, and every frame's bytes are those of process(): the same kernels add the
-// same terms in the same order whatever the launch's size.
-//
-// State.  Frame i of a pass reads the state frame i - 1 wrote; the pass owns the n - 1 buffers in between, reads
-// m_State[set] and leaves the last frame's state in m_State[set ^ 1] and the last history in m_Packed[set ^ 1], as
-// ONE process() call would: the pass flips the binding set once, and -- since nothing it wrote is read before the
-// pass -- a pass that failed (resident tower: bounded wait expired) can be run again frame by frame.
-// ---------------------------------------------------------------------------------------------------------------
-bool Engine::batchPlanned(int items, bool group) {
-	if (!m_Config.recurrent()) {
-		// a flow-free model: a pass is its frames' generator programs under one synchronisation -- no flow launches,
-		// no pass tensors, and every frame's tail writes the one scratch state
-		if (m_BatchUnsupported || m_Calibrate) return false;
-		for (int set = 0; set < 2; ++set) m_BatchFlow[{items, set}];
-		m_BatchFlow[{items, kGroupSet}];
-		m_BatchCap = std::max({m_BatchCap, items, m_BatchMax});
-		return true;
-	}
-	if (m_BatchUnsupported || m_Calibrate || m_Config.flowArch != 0 || !flowPacksInBlock() || m_Config.normalizeBrightness) {
-		return false;
-	}
-	if (items <= m_BatchCap && m_BatchFlow.count({items, group ? kGroupSet : 0})) return true;
-	try {
-		if (items > m_BatchCap) {
-			// (the tensors of every pass so far are too small: start over)
-			m_Stream.synchronize();
-			m_BatchGraphs.clear();
-			m_BatchFlow.clear();
-			m_BatchTensors.clear();
-			// (the whole cap at once: growing later reallocates the tensors every captured pass is bound to -- also the
-			// registered ones -- and round 6's bench lost a registered short pass that way.  ~210 MB at 480x270 for 8 frames.)
-			const int cap = std::max(items, m_BatchMax);
-			for (const auto &kv : m_Tensors) {
-				const bool flowTensor = kv.first == "flow" || kv.first.rfind("flow/", 0) == 0;
-				if (!flowTensor) continue;
-				Tensor t;
-				t.count = kv.second.count * cap;
-				t.isF32 = kv.second.isF32;
-				t.isState = kv.second.isState;
-				t.buf = DeviceBuffer(t.count * (t.isF32 ? 4 : 2));
-				m_BatchTensors.emplace(kv.first, std::move(t));
-			}
-			m_BatchCap = cap;
-		}
-		if (group) {  // (a group pass chains no states: each member reads and writes its own)
-			std::vector<Step> prog;
-			addFlowAutoencoder(&prog, 0, items, true);
-			m_BatchFlow[{items, kGroupSet}] = std::move(prog);
-			return true;
-		}
-		for (int i = 0; i + 1 < m_BatchCap; ++i) {
-			if (!m_BatchState[i].get()) m_BatchState[i] = DeviceBuffer(m_State[0].bytes());
-		}
-		for (int set = 0; set < 2; ++set) {
-			std::vector<Step> prog;
-			addFlowAutoencoder(&prog, set, items);
-			m_BatchFlow[{items, set}] = std::move(prog);
-		}
-		return true;
-	} catch (const std::exception &e) {
-		// (std::logic_error: a launch of this model's flow plan has no item dimension; anything else -- the pass's
-		// tensors did not fit the device -- equally means "frame by frame from now on", not a failed call)
-		logMessage(dynamic_cast<const std::logic_error *>(&e) ? LogLevel::Info : LogLevel::Warning, "Engine",
-		    std::string("frame look-ahead is off for this runtime: ") + e.what());
-		m_BatchUnsupported = true;
-		m_BatchFlow.clear();
-		m_BatchTensors.clear();
-		m_BatchCap = 0;
-		return false;
-	}
-}
-
-void Engine::setLookahead(int frames) {
-	DeviceGuard g(m_Device);
-	const int cap = std::min(std::max(frames, 1), kFlowBatchMax);
-	if (cap < m_BatchMax) {
-		// graphs of longer passes can no longer be asked for: drop them (their launches may still be in flight)
-		m_Stream.synchronize();
-		for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
-			it = static_cast<int>(it->first.size()) > cap ? m_BatchGraphs.erase(it) : std::next(it);
-		}
-	}
-	m_BatchMax = cap;
-}
-
-void Engine::dropBatchGraphs() {
-	m_BatchGraphs.clear();
-}
-
-// The launches of one look-ahead pass over the n frames of m_BatchIO, in stream order (recorded when m_Stream is
-// capturing): the flow net over all frames, then frame by frame the rest of binding set `set`'s per-frame program,
-// bound to the frame's buffers, its flow field and its link of the state chain.
-void Engine::runBatch(int set, int n, const std::function<void(const Step &, bool)> *around) {
-	auto run = [&](const Step &st) {
-		if (around) (*around)(st, false);
-		st.run(m_Stream);
-		if (around) (*around)(st, true);
-	};
-	const std::vector<Step> &flow = m_BatchFlow.at({n, set});
-	const bool recurrent = m_Config.recurrent();  // (flow-free: no flow fields, no state chain)
-	const long flowItem = recurrent ? static_cast<long>(m_Tensors.at("flow").count) * 2 : 0;
-	const unsigned char *flowBase = recurrent ? m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
-	const FrameIO keepIO = m_IO;
-	const StateBind keepBind = m_StateBind[set];
-	const void *keepFlow = m_FlowCur;
-	struct Restore {
-		std::function<void()> f;
-		~Restore() { f(); }
-	} restore{[&] {
-		m_IO = keepIO;
-		m_StateBind[set] = keepBind;
-		m_FlowCur = keepFlow;
-	}};
-	// the pass's YUV inputs into their frames' BGRX buffers, all in one launch (a flow-free pass has no launch before it)
-	YuvDecodeItems items{};
-	int decodes = 0;
-	for (int i = 0; i < n; ++i) {
-		const PassFrame &pf = m_BatchHost[i];
-		if (!pf.yuvIn) continue;
-		items.item[decodes++] = yuvDecodeItem(fmt(pf.formatIn), pf.csIn, pf.decode, const_cast<std::uint8_t *>(m_BatchIO[i].in),
-		    m_BatchIO[i].inStride);
-	}
-	if (decodes) {
-		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),
-		    m_Stream);
-	}
-	for (const Step &st : flow) run(st);
-	for (int i = 0; i < n; ++i) {
-		m_IO = m_BatchIO[i];
-		if (recurrent) {
-			m_FlowCur = flowBase + i * flowItem;
-			m_StateBind[set].in = i == 0 ? keepBind.in : m_BatchState[i - 1].get();
-			m_StateBind[set].out = i + 1 == n ? keepBind.out : m_BatchState[i].get();
-		}
-		for (const Step &st : m_Program[set]) {
-			if (st.tag != "flow" && st.tag != "pack") run(st);
-		}
-		if (m_BatchHost[i].yuvOut) {  // the frame's BGRX output (m_PassOut[i]) into the caller's device planes / the staging slot
-			// (a 10-bit output from the state: THIS frame's link of the chain -- m_BatchState[i], the last frame's
-			// m_State[set ^ 1]; a flow-free pass has one scratch state that the next frame's tail overwrites, so the encode
-			// stays on this stream in front of the next frame's kernels)
-			const FrameSize fs = frameSize();
-			encodeYuv(m_BatchHost[i].formatOut, m_BatchHost[i].csOut, m_BatchHost[i].encode, fs.outputWidth, fs.outputHeight,
-			    m_BatchIO[i].out, m_BatchIO[i].outStride, m_StateBind[set].out);
-		}
-		// (a host frame: its bytes are complete in m_PassOut[i] / m_PassYuvOut[i] -- tell the thread that copies them out)
-		if (m_BatchHost[i].hostOut) launchSignalHost(m_PassSignal.device(), m_Stream);
-	}
-}
-
-// A frame may go into a pass when each of its two images is either a device-resident one the kernels can read / write in
-// place (directEligible's conditions) or a host image of the right size (staged through the pass's own device buffers).
-// A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
-bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
-	if (sourceStage()) return false;  // (scaled / masked frames run one by one through submitFrame)
-	const FrameSize fs = frameSize();
-	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align) {
-		if (a.yuv) {
-			const YuvFrame &y = a.planes;
-			return (y.location == Location::Host || y.location == Location::Device) && y.width == w && y.height == h;
-		}
-		const Frame &f = a.bgrx;
-		const auto row = static_cast<std::ptrdiff_t>(w * 4);
-		if (f.ptr == nullptr || f.width != w || f.height != h || !(f.stride >= row || -f.stride >= row)) return false;
-		if (f.location == Location::Host) return true;
-		return f.location == Location::Device && m_PreferDirect && reinterpret_cast<std::uintptr_t>(f.ptr) % align == 0 &&
-		       f.stride % static_cast<std::ptrdiff_t>(align) == 0;
-	};
-	return side(in, fs.inputWidth, fs.inputHeight, 4) && side(out, fs.outputWidth, fs.outputHeight, 8);
-}
-
-bool Engine::passEligible(const Frame &in, const Frame &out) const { return passEligible(anyOf(in), anyOf(out)); }
-
-// Binds the n frames of a pass: m_BatchIO[i] = what frame i's kernels read and write -- the caller's device memory, or
-// for a host image the pass's device buffer i, addressed with the SIGN of the caller's stride (a bottom-up host frame is
-// uploaded / downloaded in memory order and read / written bottom-up by the kernels: no flip pass).  The key of the
-// pass's graph is made of those bindings, so all-host passes of one length and orientation share one graph.
-//
-// YUV frames in look-ahead passes (processFrames).  A YUV input of frame i is decoded into m_PassIn[i], a YUV output
-// encoded from m_PassOut[i] (top-down BGRX rows both), whatever the planes' location: m_BatchHost[i].decode / .encode
-// are the planes those conversion launches read / write.  Device planes: the caller's, in place.  Host planes: slot i of
-// m_PassYuvIn / m_PassYuvOut, plane after plane with rows padded to stagePitch and in the caller's MEMORY order, so a
-// bottom-up plane is addressed from its last row with a negative pitch -- the layout of stageInYuv / stageOutYuv.
-std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set) {
-	const FrameSize fs = frameSize();
-	const auto inRow = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
-	const auto outRow = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
-	// the planes a conversion launch addresses, and what of them the graph bakes in
-	auto bindPlanes = [](const YuvFrame &y, DeviceBuffer *stage, YuvKey *key) {
-		key->format = static_cast<int>(y.format);
-		key->colorspace = formatInfo(y.format).rgb() ? 0 : y.colorspace;  // (ignored for RGB: no second graph for another value)
-		for (int k = 0; k < planeCount(y.format); ++k) {
-			key->planes[k] = stage ? nullptr : y.planes[k];
-			key->strides[k] = stage ? (y.strides[k] > 0 ? 1 : -1) : y.strides[k];
-		}
-		if (stage == nullptr) return callerPlanes(y);
-		if (!stage->get()) *stage = DeviceBuffer(yuvStageBytes(y.width, y.height));
-		return stagedPlanes(y, stage->as<std::uint8_t>());
-	};
-	std::vector<PassKey> key(static_cast<std::size_t>(n));
-	for (int i = 0; i < n; ++i) {
-		FrameIO &io = m_BatchIO[i];
-		PassFrame &pf = m_BatchHost[i];
-		PassKey &k = key[static_cast<std::size_t>(i)];
-		pf = PassFrame{};
-		if (in[i].yuv) {
-			const YuvFrame &y = in[i].planes;
-			pf.yuvIn = true;
-			pf.hostIn = y.location == Location::Host;
-			pf.formatIn = y.format;
-			pf.csIn = y.colorspace;
-			if (!m_PassIn[i].get()) m_PassIn[i] = DeviceBuffer(fs.inputHeight * static_cast<std::size_t>(inRow));
-			io.in = m_PassIn[i].as<std::uint8_t>();
-			io.inStride = inRow;
-			pf.decode = bindPlanes(y, pf.hostIn ? &m_PassYuvIn[i] : nullptr, &k.in);
-		} else {
-			const Frame &f = in[i].bgrx;
-			pf.hostIn = f.location == Location::Host;
-			if (pf.hostIn) {
-				if (!m_PassIn[i].get()) m_PassIn[i] = DeviceBuffer(fs.inputHeight * static_cast<std::size_t>(inRow));
-				auto *base = m_PassIn[i].as<std::uint8_t>();
-				io.in = f.stride >= 0 ? base : base + static_cast<std::ptrdiff_t>(fs.inputHeight - 1) * inRow;
-				io.inStride = f.stride >= 0 ? inRow : -inRow;
-			} else {
-				io.in = static_cast<const std::uint8_t *>(f.ptr);
-				io.inStride = f.stride;
-			}
-		}
-		if (out[i].yuv) {
-			const YuvFrame &y = out[i].planes;
-			pf.yuvOut = true;
-			pf.hostOut = y.location == Location::Host;
-			pf.formatOut = y.format;
-			pf.csOut = y.colorspace;
-			if (!m_PassOut[i].get()) m_PassOut[i] = DeviceBuffer(fs.outputHeight * static_cast<std::size_t>(outRow));
-			io.out = m_PassOut[i].as<std::uint8_t>();
-			io.outStride = outRow;
-			pf.encode = bindPlanes(y, pf.hostOut ? &m_PassYuvOut[i] : nullptr, &k.out);
-		} else {
-			const Frame &f = out[i].bgrx;
-			pf.hostOut = f.location == Location::Host;
-			if (pf.hostOut) {
-				if (!m_PassOut[i].get()) m_PassOut[i] = DeviceBuffer(fs.outputHeight * static_cast<std::size_t>(outRow));
-				auto *base = m_PassOut[i].as<std::uint8_t>();
-				io.out = f.stride >= 0 ? base : base + static_cast<std::ptrdiff_t>(fs.outputHeight - 1) * outRow;
-				io.outStride = f.stride >= 0 ? outRow : -outRow;
-			} else {
-				io.out = static_cast<std::uint8_t *>(f.ptr);
-				io.outStride = f.stride;
-			}
-		}
-		if (pf.hostOut) {
-			if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
-			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
-		}
-		k.io = DirectKey{io.in, io.inStride, io.out, io.outStride, set};
-	}
-	return key;
-}
-
-// Every host input of the pass into its device buffer, rows in MEMORY order (the binding carries the orientation), on the
-// engine's stream in front of the pass's launches.  Pageable memory: the runtime stages or page-locks per call, as in
-// stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in stageInYuv.
-void Engine::uploadPassInputs(const AnyFrame *in, int n) {
-	const FrameSize fs = frameSize();
-	const std::size_t rowBytes = fs.inputWidth * 4, rows = fs.inputHeight;
-	for (int i = 0; i < n; ++i) {
-		if (!m_BatchHost[i].hostIn) continue;
-		if (in[i].yuv) {
-			copyPlanes(in[i].planes, m_PassYuvIn[i].as<std::uint8_t>(), true, m_Stream);
-			continue;
-		}
-		const Frame &f = in[i].bgrx;
-		const auto *p0 = static_cast<const std::uint8_t *>(f.ptr);
-		const std::uint8_t *lowest = f.stride >= 0 ? p0 : p0 + static_cast<std::ptrdiff_t>(rows - 1) * f.stride;
-		const std::size_t pitch = static_cast<std::size_t>(f.stride >= 0 ? f.stride : -f.stride);
-		if (pitch == rowBytes) {
-			JU_HIP(hipMemcpyAsync(m_PassIn[i].get(), lowest, rowBytes * rows, hipMemcpyHostToDevice, m_Stream));
-		} else {
-			JU_HIP(hipMemcpy2DAsync(m_PassIn[i].get(), rowBytes, lowest, pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream));
-		}
-	}
-}
-
-// The thread blocked in processBatch: wait for frame i's completion count, copy frame i out on the copy stream while the
-// GPU runs frame i + 1, in order.  The wait is bounded by the pass itself: once the engine's stream has drained, a count
-// that has not arrived never will.  A YUV frame goes out plane by plane from its staging slot (3.1 MB at 1080p instead of
-// BGRX's 8.3 MB), as in stageOutYuv.
-void Engine::drainPassOutputs(const AnyFrame *out, int n) {
-	const FrameSize fs = frameSize();
-	const std::size_t rowBytes = fs.outputWidth * 4, rows = fs.outputHeight;
-	volatile unsigned *word = m_PassSignal.host();
-	unsigned due = 0;
-	bool any = false;
-	for (int i = 0; i < n; ++i) {
-		if (!m_BatchHost[i].hostOut) continue;
-		++due;
-		auto arrived = [&] { return static_cast<int>(*word - m_PassSignalBase) >= static_cast<int>(due); };
-		for (unsigned spins = 1; !arrived(); ++spins) {
-			if ((spins & 255u) == 0) {
-				const hipError_t st = hipStreamQuery(m_Stream);
-				if (st == hipSuccess) {
-					if (arrived()) break;
-					throw std::runtime_error("look-ahead pass: the completion count of a host frame did not arrive");
-				}
-				if (st != hipErrorNotReady) JU_HIP(st);
-			} else {
-				__builtin_ia32_pause();
-			}
-		}
-		any = true;
-		if (out[i].yuv) {
-			copyPlanes(out[i].planes, m_PassYuvOut[i].as<std::uint8_t>(), false, *m_CopyStream);
-			continue;
-		}
-		const Frame &f = out[i].bgrx;
-		auto *p0 = static_cast<std::uint8_t *>(f.ptr);
-		std::uint8_t *lowest = f.stride >= 0 ? p0 : p0 + static_cast<std::ptrdiff_t>(rows - 1) * f.stride;
-		const std::size_t pitch = static_cast<std::size_t>(f.stride >= 0 ? f.stride : -f.stride);
-		if (pitch == rowBytes) {
-			JU_HIP(hipMemcpyAsync(lowest, m_PassOut[i].get(), rowBytes * rows, hipMemcpyDeviceToHost, *m_CopyStream));
-		} else {
-			JU_HIP(hipMemcpy2DAsync(lowest, pitch, m_PassOut[i].get(), rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, *m_CopyStream));
-		}
-	}
-	if (any) JU_HIP(hipStreamSynchronize(*m_CopyStream));
-}
-
-Engine::DirectEntry &Engine::batchEntry(const std::vector<PassKey> &key) {
-	auto it = m_BatchGraphs.find(key);
-	if (it == m_BatchGraphs.end()) {
-		// least recently used out -- among the tuples nobody registered: a tuple handed to prepareBatch keeps its graphs
-		// (the header promises that process calls on it never capture), as registered pairs do; only a caller that keeps
-		// registering new tuples (more than kMaxRegisteredBatches) loses the registered one it used least recently
-		std::size_t registered = 0;
-		for (const auto &kv : m_BatchGraphs) registered += kv.second.registered ? 1 : 0;
-		if (m_BatchGraphs.size() - registered >= kMaxBatchGraphs || registered >= kMaxRegisteredBatches) {
-			const bool fromRegistered = m_BatchGraphs.size() - registered < kMaxBatchGraphs;
-			auto victim = m_BatchGraphs.end();
-			for (auto j = m_BatchGraphs.begin(); j != m_BatchGraphs.end(); ++j) {
-				if (j->second.registered != fromRegistered) continue;
-				if (victim == m_BatchGraphs.end() || j->second.lastUse < victim->second.lastUse) victim = j;
-			}
-			if (victim != m_BatchGraphs.end()) m_BatchGraphs.erase(victim);
-		}
-		it = m_BatchGraphs.emplace(key, DirectEntry{}).first;
-	}
-	it->second.lastUse = ++m_DirectClock;
-	return it->second;
-}
-
-// ju_prepare_batch: the graphs of a tuple of frame buffers a caller is going to hand to processBatch, one per
-// binding set, captured NOW (as prepareFrames does for one pair): nothing executes, no buffer is touched.  Returns
-// the graphs captured; 0 for a tuple that will not go as one pass.
-int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
-	if (n < 0 || (n > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("prepareBatch: bad arguments");
-	DeviceGuard g(m_Device);
-	if (n < 2 || n > m_BatchMax || !m_UseGraph || !m_DirectGraph) return 0;
-	for (int i = 0; i < n; ++i) {
-		if (!passEligible(in[i], out[i])) return 0;
-	}
-	if (!batchPlanned(n)) return 0;
-	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
-	std::unique_lock<std::mutex> chain = chainBegin();  // (no capture while another engine's constructor drains the device)
-	int captured = 0;
-	for (int set = 0; set < 2; ++set) {
-		DirectEntry &e = batchEntry(bindBatch(anyIn.data(), anyOut.data(), n, set));
-		e.registered = true;
-		if (e.graph.valid()) continue;
-		{
-			DryLaunchScope dry;  // the attributes of the tile heights this pass's launch sizes choose
-			for (const Step &st : m_BatchFlow.at({n, set})) st.run(m_Stream);
-		}
-		e.graph = GraphExec::capture(m_Stream, [&] { runBatch(set, n); });
-		e.seen = 2;
-		++captured;
-		++m_PreparedCaptures;
-	}
-	return captured;
-}
-
-// One look-ahead pass over frames [0, n): enqueue only.  On return the binding set is flipped ONCE (see above).
-void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
-	const int set = m_Idx;
-	const std::vector<PassKey> key = bindBatch(in, out, n, set);
-	uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
-	m_PassSignalBase = m_PassSignal.host() ? *m_PassSignal.host() : 0u;
-	for (int i = 0; i < n; ++i) {
-		m_BatchHostFrames += (m_BatchHost[i].hostIn || m_BatchHost[i].hostOut) ? 1 : 0;
-		m_BatchYuvFrames += (m_BatchHost[i].yuvIn || m_BatchHost[i].yuvOut) ? 1 : 0;
-	}
-	{
-		std::unique_lock<std::mutex> chain = chainBegin();
-		bool replayed = false;
-		if (m_UseGraph && m_DirectGraph) {
-			DirectEntry &e = batchEntry(key);
-			// (first sighting: eager -- it also sets the dynamic-LDS attribute of a tile height this pass's launch
-			// sizes choose for the first time, which must not happen inside a capture; second: capture and replay)
-			if (!e.graph.valid() && ++e.seen >= 2) {
-				e.graph = GraphExec::capture(m_Stream, [&] { runBatch(set, n); });
-				++m_InlineCaptures;
-			}
-			if (e.graph.valid()) {
-				e.graph.launch(m_Stream);
-				++m_GraphReplays;
-				replayed = true;
-			}
-		}
-		if (!replayed) {
-			runBatch(set, n);
-			++m_EagerRuns;
-		}
-		chainEnd(chain);
-	}
-	m_Idx = set ^ 1;
-	m_BatchFrames += static_cast<std::uint64_t>(n);
-}
-
-namespace {
-std::atomic<int> g_PassRerun{0};
-}  // namespace
-void setPassRerun(int on) { g_PassRerun = on; }
-
-void Engine::processBatch(const Frame *in, const Frame *out, int count) {
-	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("processBatch: bad arguments");
-	const std::vector<AnyFrame> anyIn = anyOf(in, count), anyOut = anyOf(out, count);
-	if (sourceStage()) return processFrames(anyIn.data(), anyOut.data(), count);  // (every frame checked before the first runs)
-	runPasses(anyIn.data(), anyOut.data(), count);
-}
-
-void Engine::processFrames(const AnyFrame *in, const AnyFrame *out, int count) {
-	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) {
-		throw std::invalid_argument("ju_process_frames: NULL frames or a negative count");
-	}
-	for (int i = 0; i < count; ++i) {
-		try {
-			checkFrame(in[i], true);
-			checkFrame(out[i], false);
-		} catch (const std::invalid_argument &e) {
-			throw std::invalid_argument("ju_process_frames: frame " + std::to_string(i) + ": " + e.what());
-		}
-	}
-	runPasses(in, out, count);
-}
-
-// one frame's launches, enqueue only: submit() for a BGRX pair, submitFrame() where a side is YUV
-void Engine::submitAny(const AnyFrame &in, const AnyFrame &out) {
-	if (!in.yuv && !out.yuv) {
-		submit(in.bgrx, out.bgrx);
-	} else {
-		submitFrame(in, out);
-	}
-}
-
-void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
-	DeviceGuard g(m_Device);
-	// the bytes of every plane of a frame (BGRX: its one image), and their address space
-	using Range = std::pair<const std::uint8_t *, const std::uint8_t *>;
-	struct Extent {
-		Range r[3];
-		int planes = 0;
-		Location location = Location::Host;
-	};
-	auto rowsRange = [](const void *ptr, std::ptrdiff_t stride, std::size_t rowCount, std::size_t rowBytes) {
-		const auto rows = static_cast<std::ptrdiff_t>(rowCount);
-		const auto *p0 = static_cast<const std::uint8_t *>(ptr);
-		const std::uint8_t *lo = stride >= 0 ? p0 : p0 + (rows - 1) * stride;
-		const std::size_t bytes = static_cast<std::size_t>(rows - 1) * static_cast<std::size_t>(stride >= 0 ? stride : -stride) + rowBytes;
-		return std::make_pair(lo, lo + bytes);
-	};
-	auto extent = [&](const AnyFrame &a) {
-		Extent e;
-		if (!a.yuv) {
-			e.r[0] = rowsRange(a.bgrx.ptr, a.bgrx.stride, a.bgrx.height, a.bgrx.width * 4);
-			e.planes = 1;
-			e.location = a.bgrx.location;
-			return e;
-		}
-		const YuvFrame &y = a.planes;
-		e.planes = planeCount(y.format);
-		e.location = y.location;
-		for (int k = 0; k < e.planes; ++k) {
-			const PlaneShape p = planeShape(y.format, y.width, y.height, k);
-			e.r[k] = rowsRange(y.planes[k], y.strides[k], p.rows, p.rowBytes);
-		}
-		return e;
-	};
-	auto overlap = [](const Extent &a, const Extent &b) {
-		if (a.location != b.location) return false;  // (host and device addresses are different spaces)
-		for (int i = 0; i < a.planes; ++i) {
-			for (int j = 0; j < b.planes; ++j) {
-				if (a.r[i].first < b.r[j].second && b.r[j].first < a.r[i].second) return true;
-			}
-		}
-		return false;
-	};
-	int i = 0;
-	while (i < count) {
-		// the longest run of frames from i that can go as one pass: none of them READING what an earlier frame of the
-		// pass writes (frame by frame such an input would be read after that write; the pass's flow sweep and its YUV
-		// decode read every input first)
-		// ... nor WRITING what an earlier frame of the pass reads: on the normal path that write comes after the read
-		// (frame k's tail after frame j's, j < k), but a pass whose resident tower timed out is run again frame by frame
-		// from its inputs, which must then still be what they were (advisor, round 5).  Every plane of a YUV frame counts.
-		Extent reads[kFlowBatchMax], writes[kFlowBatchMax];
-		int n = 0;
-		while (i + n < count && n < m_BatchMax && passEligible(in[i + n], out[i + n])) {
-			reads[n] = extent(in[i + n]);
-			writes[n] = extent(out[i + n]);
-			bool clash = false;
-			for (int k = 0; k < n && !clash; ++k) clash = overlap(reads[n], writes[k]) || overlap(writes[n], reads[k]);
-			if (clash) break;
-			++n;
-		}
-		if (n < 2 || !batchPlanned(n)) {
-			if (!in[i].yuv && !out[i].yuv) {
-				process(in[i].bgrx, out[i].bgrx);
-			} else {
-				runSynchronous([&] { submitFrame(in[i], out[i]); });
-			}
-			++i;
-			continue;
-		}
-		const int set = m_Idx;
-		submitBatch(in + i, out + i, n);
-		drainPassOutputs(out + i, n);  // host frames: each copied out while the next one runs
-		m_Stream.synchronizeSpin(m_SpinUs);
-		const unsigned code = takeResidentError();
-		if (code || g_PassRerun.load(std::memory_order_relaxed)) {
-			// nothing the pass wrote was one of its inputs -- neither the state (see above) nor a frame buffer (the pass
-			// splitter): the same frames again, one by one, on the per-block kernels
-			m_Idx = set;
-			m_BatchFrames -= static_cast<std::uint64_t>(n);
-			for (int k = 0; k < n; ++k) {
-				m_BatchHostFrames -= (m_BatchHost[k].hostIn || m_BatchHost[k].hostOut) ? 1 : 0;
-				m_BatchYuvFrames -= (m_BatchHost[k].yuvIn || m_BatchHost[k].yuvOut) ? 1 : 0;
-			}
-			if (code) fallbackToLayers(code);
-			for (int k = 0; k < n; ++k) {
-				if (code) {
-					submitAny(in[i + k], out[i + k]);
-					m_Stream.synchronize();
-				} else {  // (the debug switch: the pass was sound, the resident tower still runs and may report)
-					runSynchronous([&] { submitAny(in[i + k], out[i + k]); });
-				}
-			}
-		} else {
-			for (int k = 0; k < n; ++k) maybeRestoreResident();
-		}
-		i += n;
-	}
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Group passes (processGroup).  A server of N live streams has N frames at every tick, one per stream, and their flow
-// nets are as independent as a look-ahead pass's: the flow net reads LR frames and each stream's own history only.  So
-// the lead (members[0]) runs the flow net's launches ONCE over the n frames of a pass, on its batch tensors -- item i is
-// member i's frame with member i's history (flow_block_kernel's independent-items form: m_GroupPrev / m_GroupOut) --
-// and then, member by member on the lead's stream, each member's own non-flow steps, bound to its frame, flow item i
-// and its state m_State[set_i] -> m_State[set_i ^ 1].  Per member that is the arithmetic of process(): the same kernels
-// add the same terms in the same order whatever the launch's size.  Like a look-ahead pass, the pass writes nothing it
-// reads (every member's state and history go to the other half of its ping-pong, the overlap test below keeps outputs
-// off inputs), so a pass whose resident tower timed out runs again member by member.  The launches are eager: round 6
-// measured eager launches per frame equal to graph replay.
-// ---------------------------------------------------------------------------------------------------------------
-bool Engine::sameModel(const Engine &o) const {
-	return m_Device == o.m_Device && m_ModelDigest == o.m_ModelDigest && m_DtypeOverride == o.m_DtypeOverride;
-}
-
-// What process() would refuse for its size, checked up front (a group call launches nothing before every frame passed)
-void Engine::checkGroupFrame(const Frame &f, bool input) const {
-	const FrameSize fs = frameSize();
-	const bool scaled = input && m_SrcW != 0, resized = !input && m_OutW != 0;
-	const std::size_t w = scaled ? m_SrcW : (resized ? m_OutW : (input ? fs.inputWidth : fs.outputWidth));
-	const std::size_t h = scaled ? m_SrcH : (resized ? m_OutH : (input ? fs.inputHeight : fs.outputHeight));
-	const char *side = input ? "input" : "output";
-	if (scaled && f.location == Location::GraphicsResource) {
-		throw std::invalid_argument("ju_process_group: graphics resources cannot be inputs while a source size is set");
-	}
-	if (resized && f.location == Location::GraphicsResource) {
-		throw std::invalid_argument("ju_process_group: graphics resources cannot be outputs while an output size is set");
-	}
-	if (f.ptr == nullptr) throw std::invalid_argument(std::string("ju_process_group: NULL ") + side + " image");
-	if (f.width != w || f.height != h) {
-		throw std::invalid_argument(std::string("ju_process_group: ") + side + " image must be exactly " + std::to_string(w) +
-		                            "x" + std::to_string(h) + (resized ? " (the output size set)" : ""));
-	}
-	const auto row = static_cast<std::ptrdiff_t>(w * 4);
-	if (f.location != Location::GraphicsResource && f.stride > -row && f.stride < row) {
-		throw std::invalid_argument(std::string("ju_process_group: |stride| of an ") + side + " image smaller than a row");
-	}
-}
-
-void Engine::processGroup(Engine *const *members, const Frame *in, const Frame *out, int count) {
-	if (count < 0 || (count > 0 && (members == nullptr || in == nullptr || out == nullptr))) {
-		throw std::invalid_argument("ju_process_group: NULL arguments or a negative count");
-	}
-	if (count == 0) return;
-	std::set<const Engine *> seen;
-	for (int i = 0; i < count; ++i) {
-		if (members[i] == nullptr) throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " is NULL");
-		if (!seen.insert(members[i]).second) {
-			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " appears twice");
-		}
-		if (!members[i]->sameModel(*members[0])) {
-			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) +
-			                            " does not match runtime 0 (device, model bytes or dtype)");
-		}
-		members[i]->checkGroupFrame(in[i], true);
-		members[i]->checkGroupFrame(out[i], false);
-	}
-	Engine &lead = *members[0];
-	DeviceGuard g(lead.m_Device);
-	auto alone = [&](int i) { members[i]->process(in[i], out[i]); };
-	if (count == 1) return alone(0);
-	// An output over an input of the call (same address space; any two members, also one member's own pair): member by
-	// member in list order, as ju_process calls would run -- a pass reads every input before any tail writes
-	auto range = [](const Frame &f) {
-		const auto rows = static_cast<std::ptrdiff_t>(f.height);
-		const auto *p0 = static_cast<const std::uint8_t *>(f.ptr);
-		const std::uint8_t *lo = f.stride >= 0 ? p0 : p0 + (rows - 1) * f.stride;
-		const std::size_t bytes = static_cast<std::size_t>(rows - 1) * static_cast<std::size_t>(f.stride >= 0 ? f.stride : -f.stride) + f.width * 4;
-		return std::make_pair(lo, lo + bytes);
-	};
-	bool clash = false;
-	for (int i = 0; i < count && !clash; ++i) {
-		if (out[i].location == Location::GraphicsResource) continue;
-		const auto w = range(out[i]);
-		for (int j = 0; j < count && !clash; ++j) {
-			if (in[j].location != out[i].location) continue;  // (host and device addresses are different spaces)
-			const auto r = range(in[j]);
-			clash = w.first < r.second && r.first < w.second;
-		}
-	}
-	std::vector<int> pass, rest;
-	for (int i = 0; i < count; ++i) (members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
-	const int cap = lead.m_BatchMax;
-	if (clash || pass.size() < 2 || cap < 2) {
-		for (int i = 0; i < count; ++i) alone(i);
-		return;
-	}
-	// consecutive passes of at most the lead's look-ahead cap; a pass of one member is a plain process()
-	for (std::size_t k = 0; k < pass.size(); k += static_cast<std::size_t>(cap)) {
-		const int n = static_cast<int>(std::min(pass.size() - k, static_cast<std::size_t>(cap)));
-		if (n < 2 || !lead.batchPlanned(n, true)) {
-			for (int j = 0; j < n; ++j) alone(pass[k + j]);
-			continue;
-		}
-		Engine *m[kFlowBatchMax];
-		Frame fi[kFlowBatchMax], fo[kFlowBatchMax];
-		for (int j = 0; j < n; ++j) {
-			m[j] = members[pass[k + j]];
-			fi[j] = in[pass[k + j]];
-			fo[j] = out[pass[k + j]];
-		}
-		runGroupPass(lead, m, fi, fo, n);
-	}
-	// frames a pass cannot take (graphics resources, device frames off the kernels' alignment): on their own.  No
-	// buffer of the call overlaps another here, so the order changes no byte.
-	for (int i : rest) alone(i);
-}
-
-void Engine::runGroupPass(Engine &L, Engine *const *m, const Frame *in, const Frame *out, int n) {
-	int sets[kFlowBatchMax];
-	for (int i = 0; i < n; ++i) sets[i] = m[i]->m_Idx;
-	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
-	L.bindBatch(anyIn.data(), anyOut.data(), n, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
-	L.uploadPassInputs(anyIn.data(), n);  // (outside the chain lock: a pageable upload blocks its caller)
-	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
-	// 1. work a member has pending on its own stream (ju_enqueue) runs first
-	for (int i = 0; i < n; ++i) {
-		if (m[i] == &L) continue;
-		const hipError_t st = hipStreamQuery(m[i]->m_Stream);
-		if (st == hipSuccess) continue;  // (idle: everything it was given has completed)
-		if (st != hipErrorNotReady) JU_HIP(st);
-		m[i]->m_GroupEvent.record(m[i]->m_Stream);
-		JU_HIP(hipStreamWaitEvent(L.m_Stream, m[i]->m_GroupEvent.get(), 0));
-	}
-	const bool recurrent = L.m_Config.recurrent();
-	const long flowItem = recurrent ? static_cast<long>(L.m_Tensors.at("flow").count) * 2 : 0;
-	const unsigned char *flowBase = recurrent ? L.m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
-	{
-		// 5. the device chain, once for the whole pass (chainBegin / chainEnd, for a pass that may hold several
-		// members' resident towers): ordered after the frame submitted last by any other resident runtime, and any
-		// member's next frame is ordered after the pass (lastOwner = the lead)
-		DeviceChain &c = chainOf(L.m_Device);
-		std::unique_lock<std::mutex> chain(c.mutex);
-		bool resident = false;
-		for (int i = 0; i < n; ++i) resident = resident || m[i]->m_Resident;
-		if (c.engines > 1 && resident && c.last != nullptr && c.lastOwner != &L) JU_HIP(hipStreamWaitEvent(L.m_Stream, c.last, 0));
-		// 2. the flow net once over all items
-		for (int i = 0; i < n; ++i) {
-			L.m_GroupPrev[i] = m[i]->m_Packed[sets[i]].get();
-			L.m_GroupOut[i] = m[i]->m_Packed[sets[i] ^ 1].get();
-		}
-		for (const Step &st : L.m_BatchFlow.at({n, kGroupSet})) st.run(L.m_Stream);
-		// 3. member by member, its own steps on the lead's stream, bound to its frame and its flow item
-		for (int i = 0; i < n; ++i) {
-			Engine &e = *m[i];
-			const FrameIO keepIO = e.m_IO;
-			const void *keepFlow = e.m_FlowCur;
-			struct Restore {
-				Engine &e;
-				FrameIO io;
-				const void *flow;
-				~Restore() {
-					e.m_IO = io;
-					e.m_FlowCur = flow;
-				}
-			} restore{e, keepIO, keepFlow};
-			e.m_IO = L.m_BatchIO[i];
-			if (recurrent) e.m_FlowCur = flowBase + i * flowItem;
-			for (const Step &st : e.m_Program[sets[i]]) {
-				if (st.tag != "flow" && st.tag != "pack") st.run(L.m_Stream);
-			}
-			if (L.m_BatchHost[i].hostOut) launchSignalHost(L.m_PassSignal.device(), L.m_Stream);
-		}
-		if (c.engines > 1 && resident) {
-			L.m_FrameDone.record(L.m_Stream);
-			c.last = L.m_FrameDone.get();
-			c.lastOwner = &L;
-		}
-	}
-	// 4. every member's stream after the pass
-	L.m_GroupEvent.record(L.m_Stream);
-	for (int i = 0; i < n; ++i) {
-		if (m[i] != &L) JU_HIP(hipStreamWaitEvent(m[i]->m_Stream, L.m_GroupEvent.get(), 0));
-	}
-	L.drainPassOutputs(anyOut.data(), n);  // host frames: each copied out while the next member runs
-	L.m_Stream.synchronizeSpin(L.m_SpinUs);
-	// one synchronisation; then every member's resident-tower error word
-	unsigned codes[kFlowBatchMax];
-	bool failed = false;
-	for (int i = 0; i < n; ++i) {
-		codes[i] = m[i]->takeResidentError();
-		failed = failed || codes[i] != 0;
-	}
-	if (failed) {
-		// nothing the pass wrote is one of its inputs: the same frames again, member by member, each through its own
-		// process() -- a member whose tower timed out on its per-block kernels from now on
-		for (int i = 0; i < n; ++i) {
-			if (codes[i]) m[i]->fallbackToLayers(codes[i]);
-		}
-		for (int i = 0; i < n; ++i) m[i]->process(in[i], out[i]);
-		return;
-	}
-	for (int i = 0; i < n; ++i) {
-		m[i]->m_Idx = sets[i] ^ 1;
-		++m[i]->m_GroupFrames;
-		m[i]->maybeRestoreResident();
-	}
 }
 
 void Engine::runProgram() {
@@ -2826,9 +1523,9 @@ void Engine::submit(const Frame &in, const Frame &out) {
 		stageIn(in);
 	}
 	{
-		std::unique_lock<std::mutex> chain = chainBegin();
+		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
 		runProgram();
-		chainEnd(chain);
+		chainEnd(chain, m_Resident);
 	}
 	if (!m_DirectIO) {
 		const FrameSize fs = frameSize();
@@ -2837,15 +1534,22 @@ void Engine::submit(const Frame &in, const Frame &out) {
 	m_Idx ^= 1;  // state ping-pong (tensorrt_backend.cc:277)
 }
 
-void Engine::enqueue(const Frame &in, const Frame &out) {
-	if (sourceStage()) return enqueueFrame(anyOf(in), anyOf(out));
-	DeviceGuard g(m_Device);
-	submit(in, out);
+void Engine::submitAny(const AnyFrame &in, const AnyFrame &out) {
+	if (staged(in, out)) {
+		submitFrame(in, out);
+	} else {
+		submit(in.bgrx, out.bgrx);
+	}
 }
 
-template <typename Submit>
-void Engine::runSynchronous(const Submit &submitOne) {
-	submitOne();
+void Engine::enqueue(const AnyFrame &in, const AnyFrame &out) {
+	DeviceGuard g(m_Device);
+	checkPair(in, out);
+	submitAny(in, out);
+}
+
+void Engine::runSynchronous(const AnyFrame &in, const AnyFrame &out) {
+	submitAny(in, out);
 	m_Stream.synchronizeSpin(m_SpinUs);
 	if (const unsigned code = takeResidentError()) {
 		// the frame's inputs (previous state, frame history) are intact: the step only
@@ -2855,77 +1559,17 @@ void Engine::runSynchronous(const Submit &submitOne) {
 		m_Idx ^= 1;
 		if (sourceStage()) --m_SourceFrames;  // (submitFrame counts the frame again)
 		fallbackToLayers(code);
-		submitOne();
+		submitAny(in, out);
 		m_Stream.synchronize();
 	} else {
 		maybeRestoreResident();
 	}
 }
 
-void Engine::process(const Frame &in, const Frame &out) {
-	if (sourceStage()) return processFrame(anyOf(in), anyOf(out));
+void Engine::process(const AnyFrame &in, const AnyFrame &out) {
 	DeviceGuard g(m_Device);
-	runSynchronous([&] { submit(in, out); });
-}
-
-// YUV frames (ju_process_frame): always through the staging buffers -- the conversion kernel takes the place of the
-// staging copy on its side and the binding set's staged graph replays unchanged.  The conversions are eager launches
-// on m_Stream OUTSIDE the per-device chain lock, like the staging copies of submit().
-void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
-	m_DirectIO = false;
-	bindStaging();
-	const FrameSize fs = frameSize();
-	const int inW = static_cast<int>(fs.inputWidth), inH = static_cast<int>(fs.inputHeight);
-	// what the mask lets through: the source frame at source size, or the model-size input frame
-	SourceView source{m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4)};
-	if (m_SrcW != 0) {
-		source = stageInSource(in);
-		launchScaleBgrx(source.ptr, source.stride, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH),
-		    m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4), inW, inH, m_ScaleXDev, m_ScaleYDev,
-		    m_ScaleSpan, m_Stream);
-	} else if (in.yuv) {
-		stageInYuv(in.planes);
-	} else {
-		stageIn(in.bgrx);
-	}
-	{
-		std::unique_lock<std::mutex> chain = chainBegin();
-		runProgram();
-		chainEnd(chain);
-	}
-	if (m_MaskW != 0) {
-		// over the frame handed to the caller only: state and history are the unmasked run's
-		launchMaskBlend(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4),
-		    static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight), source.ptr, source.stride,
-		    m_SrcW != 0 ? static_cast<int>(m_SrcW) : inW, m_SrcW != 0 ? static_cast<int>(m_SrcH) : inH,
-		    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0),
-		    m_MaskStride, static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), m_Stream);
-	}
-	if (sourceStage()) ++m_SourceFrames;
-	// (behind the frame's program and before the flip: the state this frame wrote is the binding set's output)
-	if (m_OutW != 0) {
-		stageOutScaled(out);
-	} else if (out.yuv) {
-		stageOutYuv(out.planes, m_OutStage.as<std::uint8_t>(), m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get(), nullptr,
-		    m_YuvOutStage.as<std::uint8_t>());
-	} else {
-		stageOut(out.bgrx, fs.outputWidth, fs.outputHeight, m_OutStage.as<std::uint8_t>(), m_RawStage.as<std::uint8_t>());
-	}
-	m_Idx ^= 1;
-}
-
-void Engine::processFrame(const AnyFrame &in, const AnyFrame &out) {
-	DeviceGuard g(m_Device);
-	checkFrame(in, true);
-	checkFrame(out, false);
-	runSynchronous([&] { submitFrame(in, out); });
-}
-
-void Engine::enqueueFrame(const AnyFrame &in, const AnyFrame &out) {
-	DeviceGuard g(m_Device);
-	checkFrame(in, true);
-	checkFrame(out, false);
-	submitFrame(in, out);
+	checkPair(in, out);
+	runSynchronous(in, out);
 }
 
 void Engine::synchronize() {
@@ -3069,7 +1713,7 @@ double Engine::timeSteps(const std::string &tagSpecIn, int iters, int *launches)
 	m_IO.out = m_OutStage.as<std::uint8_t>();
 	m_IO.outStride = static_cast<std::ptrdiff_t>(m_Config.frameWidth) * 16;
 	double ms = 0.0;
-	std::unique_lock<std::mutex> chain = chainBegin();  // (the timed launches may be resident towers)
+	std::unique_lock<std::mutex> chain = chainBegin(m_Resident);  // (the timed launches may be resident towers)
 	if (inPass) {
 		const int n = m_BatchMax, set = m_Idx;
 		for (int i = 0; i < n; ++i) {  // (every frame of the pass on the staging buffers)
@@ -3084,7 +1728,7 @@ double Engine::timeSteps(const std::string &tagSpecIn, int iters, int *launches)
 		};
 		runBatch(set, n);  // warm
 		for (int i = 0; i < iters; ++i) runBatch(set, n, &around);
-		chainEnd(chain);
+		chainEnd(chain, m_Resident);
 		m_Stream.synchronize();
 		double sum = 0.0;
 		for (std::size_t i = 0; i + 1 < ev.size(); i += 2) sum += static_cast<double>(Event::elapsedMs(*ev[i], *ev[i + 1]));
@@ -3107,7 +1751,7 @@ double Engine::timeSteps(const std::string &tagSpecIn, int iters, int *launches)
 				}
 			}
 		}
-		chainEnd(chain);
+		chainEnd(chain, m_Resident);
 		m_Stream.synchronize();
 		double sum = 0.0;
 		for (std::size_t i = 0; i + 1 < ev.size(); i += 2) sum += static_cast<double>(Event::elapsedMs(*ev[i], *ev[i + 1]));
@@ -3120,7 +1764,7 @@ double Engine::timeSteps(const std::string &tagSpecIn, int iters, int *launches)
 			for (const Step *s : steps) s->run(m_Stream);
 		}
 		t1.record(m_Stream);
-		chainEnd(chain);
+		chainEnd(chain, m_Resident);
 		t1.synchronize();
 		ms = static_cast<double>(Event::elapsedMs(t0, t1)) / (static_cast<double>(iters) * steps.size());
 	}
@@ -3160,10 +1804,10 @@ double Engine::stat(const std::string &key) const {
 	if (key == "hbd_from_state") return m_HbdFromState ? 1.0 : 0.0;  // 10-bit outputs: from the f16 state (1) / the u8 frame (0)
 	if (key == "lookahead_yuv_frames") return static_cast<double>(m_BatchYuvFrames);  // ... of them with a YUV side
 	if (key == "lookahead_max") return static_cast<double>(m_BatchMax);
-	if (key == "source_scaled") return m_SrcW != 0 ? 1.0 : 0.0;
-	if (key == "output_scaled") return m_OutW != 0 ? 1.0 : 0.0;
-	if (key == "source_filter") return static_cast<double>(m_SrcFilter);  // (0 while off: the setters clear it)
-	if (key == "output_filter") return static_cast<double>(m_OutFilter);
+	if (key == "source_scaled") return m_SrcScale.set() ? 1.0 : 0.0;
+	if (key == "output_scaled") return m_OutScale.set() ? 1.0 : 0.0;
+	if (key == "source_filter") return static_cast<double>(m_SrcScale.filter());  // (0 while off: the setters clear it)
+	if (key == "output_filter") return static_cast<double>(m_OutScale.filter());
 	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes

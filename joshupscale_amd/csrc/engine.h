@@ -21,44 +21,12 @@
 #include <tuple>
 #include <vector>
 
+#include "frame_io.h"
 #include "hip_util.h"
 #include "kernels.h"
 #include "model.h"
 
 namespace ju {
-
-// Frame descriptor of the boundary (reference core/public/JoshUpscale/core.h:30-38):
-// 4 bytes per pixel B,G,R,X; `stride` in bytes, may be negative (bottom-up);
-// `ptr` addresses the first logical row.
-enum class Location : std::uint8_t { Host = 0, Device = 1, GraphicsResource = 2 };
-
-struct Frame {
-	void *ptr;
-	Location location;
-	std::ptrdiff_t stride;
-	std::size_t width;
-	std::size_t height;
-};
-
-// A frame of ju_process_frame that is not BGRX (include/joshupscale_amd.h, ju_frame): a format of the table in kernels.h
-// (PixelFormat: planes, words and sample kinds are described there), its planes each addressing their first logical row,
-// strides in bytes of any sign.  Host or device.  An RGB format has no colour space: `colorspace` is ignored.
-struct YuvFrame {
-	PixelFormat format;
-	int colorspace;  // 0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full
-	Location location;
-	std::size_t width;
-	std::size_t height;
-	void *planes[3];
-	std::ptrdiff_t strides[3];
-};
-
-// One side of a frame call: a BGRX frame (exactly as ju_process takes it) or a YUV one.
-struct AnyFrame {
-	bool yuv = false;
-	Frame bgrx{};
-	YuvFrame planes{};
-};
 
 struct FrameSize {
 	std::size_t inputWidth, inputHeight, outputWidth, outputHeight;
@@ -76,13 +44,17 @@ public:
 	Engine(const Engine &) = delete;
 	Engine &operator=(const Engine &) = delete;
 
-	// Synchronous, like Runtime::processImage (tensorrt_backend.cc:270-278).
-	void process(const Frame &in, const Frame &out);
+	// One frame, synchronously, like Runtime::processImage (tensorrt_backend.cc:270-278): ju_process and ju_process_frame.
+	// A BGRX pair while no source or output stage is set takes the caller's pointers or the staging copies (submit) and
+	// is refused, if at all, where it is staged -- exactly as ju_process always behaved.  Every other pair -- a YUV side,
+	// whose colour conversion takes the place of the staging copy on that side (colour_kernels.hip), or any pair while a
+	// stage is set -- is checked before anything is launched and goes through the staging buffers (submitFrame).
+	void process(const AnyFrame &in, const AnyFrame &out);
 	// `count` consecutive frames of the stream, synchronously: the frames process(in[0], out[0]) ...
 	// process(in[count - 1], out[count - 1]) would write, byte for byte -- but every input must hold its pixels when
 	// the call is made (frame look-ahead): where the model and the frames allow (device-resident frames, the flow
 	// auto-encoder's one-launch plan) the flow fields of up to kFlowBatchMax frames are computed in one pass of the
-	// flow net's launches (engine.cpp, "Frame look-ahead"); anything else runs frame by frame.
+	// flow net's launches (engine_passes.cpp, "Frame look-ahead"); anything else runs frame by frame.
 	void processBatch(const Frame *in, const Frame *out, int count);
 	// Registers a tuple of device-resident frame buffers the caller is going to hand to processBatch as ONE pass
 	// (2 .. JU_LOOKAHEAD frames): its graphs, one per binding set, are captured now -- what prepareFrames is to
@@ -94,21 +66,16 @@ public:
 	// write, in every output and every member's state.  The members (distinct, one device, byte-identical model data,
 	// one dtype override: std::invalid_argument otherwise, before anything is launched) share a pass where they can:
 	// members[0] (the lead) runs the flow net ONCE over up to its look-ahead cap of frames, each the next frame of its
-	// own stream, then every member's own recurrent steps, all on the lead's stream (engine.cpp, "Group passes").
+	// own stream, then every member's own recurrent steps, all on the lead's stream (engine_passes.cpp, "Group passes").
 	static void processGroup(Engine *const *members, const Frame *in, const Frame *out, int count);
-	// Asynchronous variant for device-resident frames: enqueue only.
-	void enqueue(const Frame &in, const Frame &out);
+	// process() for device-resident frames without the wait (ju_enqueue, ju_enqueue_frame): enqueue only.
+	void enqueue(const AnyFrame &in, const AnyFrame &out);
 	void synchronize();
-	// Frames of which at least one side is YUV (ju_process_frame / ju_enqueue_frame): the same step as process() /
-	// enqueue(), its colour conversion taking the place of the staging copy on that side (colour_kernels.hip).  Both
-	// frames are checked before anything is launched.  BGRX-only pairs go through process() / enqueue() instead.
-	void processFrame(const AnyFrame &in, const AnyFrame &out);
-	void enqueueFrame(const AnyFrame &in, const AnyFrame &out);
-	// processBatch for frames of any format (ju_process_frames): the bytes and the state of processFrame / process called
-	// frame by frame in order.  EVERY pair is checked before anything is launched or uploaded (std::invalid_argument names
+	// processBatch for frames of any format (ju_process_frames): the bytes and the state of process called frame by
+	// frame in order.  EVERY pair is checked before anything is launched or uploaded (std::invalid_argument names
 	// the frame; runtime and state as they were).  YUV sides ride in the passes: the pass's YUV inputs are decoded by one
-	// launch in front of the flow net's, each YUV output is encoded behind its frame's tail (engine.cpp, "YUV frames in
-	// look-ahead passes").
+	// launch in front of the flow net's, each YUV output is encoded behind its frame's tail (engine_passes.cpp, "YUV
+	// frames in look-ahead passes").
 	void processFrames(const AnyFrame *in, const AnyFrame *out, int count);
 	// Registers a pair of device-resident frame buffers the caller is going to hand to
 	// process() / enqueue(): the per-frame graphs of the pair (one per binding set) are
@@ -123,7 +90,7 @@ public:
 	// in the reference: obs_plugin/src/filter.cc:146-151).
 	void reset();
 
-	// The source stage (docs/source_stage.md; engine.cpp, "Source stage").  setSourceSize: input frames are
+	// The source stage (docs/source_stage.md; engine_frames.cpp, "Source stage").  setSourceSize: input frames are
 	// width x height from now on and are scaled to the model's input on the GPU ((0, 0): off; filter: a JU_SCALE_* value --
 	// 0 triangle, 2 Catmull-Rom, 3 Mitchell).  setSourceMask: a BGRX image of any size, host or device, copied now (nullptr: no mask); the source is
 	// drawn over every output frame through it.  While either is set every frame of every entry point runs one by one
@@ -131,13 +98,13 @@ public:
 	void setSourceSize(std::size_t width, std::size_t height, int filter);
 	void sourceSize(std::size_t *width, std::size_t *height) const;
 	void setSourceMask(const Frame *mask);
-	// The output stage (docs/output_stage.md; engine.cpp, "Output stage").  setOutputSize: output frames are
+	// The output stage (docs/output_stage.md; engine_frames.cpp, "Output stage").  setOutputSize: output frames are
 	// width x height from now on -- the upscaled frame scaled on the GPU behind the graph and the mask blend ((0, 0): off;
 	// filter: a JU_SCALE_* value, as for the source size).  State, frame history and flow inputs are the unscaled run's.  While it is set
 	// every frame of every entry point runs one by one through submitFrame, as for a source size.  reset() keeps it.
 	void setOutputSize(std::size_t width, std::size_t height, int filter);
 	void outputSize(std::size_t *width, std::size_t *height) const;
-	bool sourceStage() const { return m_SrcW != 0 || m_MaskW != 0 || m_OutW != 0; }
+	bool sourceStage() const { return m_SrcScale.set() || m_MaskW != 0 || m_OutScale.set(); }
 
 	FrameSize frameSize() const;
 	int device() const { return m_Device; }
@@ -221,18 +188,12 @@ private:
 	// every model but normalize_brightness, whose state is output_raw - b, and output_flow, whose frame is pre_warp) or,
 	// for those two, from the u8 frame like an 8-bit output.  Decided once, at creation; ju_get_stat "hbd_from_state".
 	bool m_HbdFromState = true;
-	// (width x height: the frame's own size; 0 = the model's input)
-	void decodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::uint8_t *bgrx, std::ptrdiff_t bgrxStride,
-	    std::size_t width = 0, std::size_t height = 0);
-	// Source stage: the size input frames must have (m_SrcW x m_SrcH, 0 = the model's input), the per-axis tables of the
-	// scaler on the device, the BGRX source frame at source size (host uploads, decoded YUV) and the host planes of a YUV
-	// source; the mask in device memory, in the caller's row order (m_MaskStride < 0: bottom-up).  m_SourceFrames: frames
-	// that went through the stage ("source_stage_frames").
-	std::size_t m_SrcW = 0, m_SrcH = 0;
-	int m_SrcFilter = 0;  // the filter in effect (JU_SCALE_*; 0 while off): "source_filter"
-	DeviceBuffer m_ScaleX, m_ScaleY, m_SrcStage, m_SrcYuvStage;
-	ScaleAxisDev m_ScaleXDev, m_ScaleYDev;
-	int m_ScaleSpan = 0;
+	// Source stage: the scaler from the size input frames must have (its source size; not set = the model's input) to
+	// the model's input, its filter the one in effect ("source_filter"); the BGRX source frame at source size (host
+	// uploads, decoded YUV) and the host planes of a YUV source; the mask in device memory, in the caller's row order
+	// (m_MaskStride < 0: bottom-up).  m_SourceFrames: frames that went through the stage ("source_stage_frames").
+	Scaler m_SrcScale;
+	DeviceBuffer m_SrcStage, m_SrcYuvStage;
 	DeviceBuffer m_Mask;
 	std::size_t m_MaskW = 0, m_MaskH = 0;
 	std::ptrdiff_t m_MaskStride = 0;
@@ -247,27 +208,32 @@ private:
 	    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16 = nullptr);
 	// a deep format of a runtime whose state is the frame in float, without a mask: encoded from 16-bit samples
 	bool deepFromState(PixelFormat format) const;
-	// Output stage: the size output frames must have (0 = the model's output), the scaler's tables for the output axes,
-	// the scaled 8-bit and 16-bit frames, the planes of a host YUV output and the flip scratch of a bottom-up host image
-	std::size_t m_OutW = 0, m_OutH = 0;
-	int m_OutFilter = 0;  // "output_filter"
-	DeviceBuffer m_OutScaleX, m_OutScaleY, m_OutScaled8, m_OutScaled16, m_OutYuvStage, m_OutRawStage;
-	ScaleAxisDev m_OutScaleXDev, m_OutScaleYDev;
-	int m_OutScaleSpan = 0;
+	// Output stage: the scaler from the model's output to the size output frames must have (its destination size; not
+	// set = the model's output; "output_filter"), the scaled 8-bit and 16-bit frames, the planes of a host YUV output and
+	// the flip scratch of a bottom-up host image
+	Scaler m_OutScale;
+	DeviceBuffer m_OutScaled8, m_OutScaled16, m_OutYuvStage, m_OutRawStage;
 	void stageOutScaled(const AnyFrame &out);
-	void checkFrame(const AnyFrame &f, bool input) const;
-	void stageInYuv(const YuvFrame &in);
+	// Everything a frame call can refuse, before anything is launched; `who` names the entry point in the message.
+	// declaredSize (ju_process_group): a NULL pointer is refused first and by name, and a graphics resource's DECLARED
+	// size counts too -- otherwise the texture's own extent is checked when it is mapped, behind other members' launches.
+	void checkFrame(const AnyFrame &f, bool input, const char *who = "processFrame", bool declaredSize = false) const;
+	// THE pair decision (process, enqueue, the frames of runPasses): false = a BGRX pair while no source or output stage
+	// is set -- submit(), unchecked; true = checkPair, then submitFrame()
+	bool staged(const AnyFrame &in, const AnyFrame &out) const { return in.yuv || out.yuv || sourceStage(); }
+	void checkPair(const AnyFrame &in, const AnyFrame &out) const;
+	// one frame's launches by that decision, enqueue only
+	void submitAny(const AnyFrame &in, const AnyFrame &out);
+	// one decode launch: the planes of `in` (host planes through `stage` first) -> dense BGRX rows of the frame's own size
+	void stageInYuv(const YuvFrame &in, std::uint8_t *stage, std::uint8_t *bgrx);
 	// (stage: where a host frame's planes are written before they are copied out)
 	void stageOutYuv(const YuvFrame &out, const std::uint8_t *bgrx, const void *state, const std::uint16_t *frame16,
 	    std::uint8_t *stage);
 	void submitFrame(const AnyFrame &in, const AnyFrame &out);
 	void bindStaging();
-	// submit (a callable that enqueues one frame), wait, and on a resident-tower failure run the frame again on the
-	// per-layer path (process, processFrame)
-	template <typename Submit>
-	void runSynchronous(const Submit &submit);
+	// submitAny, wait, and on a resident-tower failure run the frame again on the per-layer path
+	void runSynchronous(const AnyFrame &in, const AnyFrame &out);
 	DeviceBuffer m_YuvInStage, m_YuvOutStage;
-	static std::size_t yuvStageBytes(std::size_t width, std::size_t height);
 	void runProgram();
 	// Frame buffers the kernels read / write in THIS call.  Graph replay always uses
 	// the internal staging buffers (static pointers); eager launches of device-resident
@@ -373,8 +339,10 @@ private:
 	// device therefore chain their frames through events when more than one of them uses the
 	// resident kernel; a single runtime pays nothing.
 	Event m_FrameDone;
-	std::unique_lock<std::mutex> chainBegin();
-	void chainEnd(std::unique_lock<std::mutex> &lock);
+	// (resident: whether the launches in between hold a resident tower -- m_Resident, or for a group pass, which the
+	// lead chains once for all its members, any member's)
+	std::unique_lock<std::mutex> chainBegin(bool resident);
+	void chainEnd(std::unique_lock<std::mutex> &lock, bool resident);
 	PinnedWords m_ResError;              // pinned, device-visible: word 0 = the tower's error report
 	unsigned *m_ResErrorDev = nullptr;
 	unsigned takeResidentError();        // 0 = none; clears it
@@ -413,7 +381,7 @@ private:
 	bool directEligible(const Frame &in, const Frame &out) const;
 	DirectEntry &directEntry(const DirectKey &key);
 	void captureDirect(DirectEntry *e, int idx);
-	// frame look-ahead (processBatch; engine.cpp): the frames of the pass being recorded, the flow net's tensors for
+	// frame look-ahead (processBatch; engine_passes.cpp): the frames of the pass being recorded, the flow net's tensors for
 	// m_BatchCap frames, the state buffers between the frames of a pass, the flow launches per (frames, binding set)
 	// and the graphs per tuple of frame buffers
 	FrameIO m_BatchIO[kFlowBatchMax];
@@ -452,16 +420,30 @@ private:
 	// frame's copy is exposed.  The copies go from / to the caller's pageable rows through the HIP runtime as in
 	// stageIn / stageOut (cuda_convert.cc.cu:360-459); nothing of the caller's is page-locked (section 7 of DESIGN.md).
 	// YUV sides: the frame's kernels read / write BGRX in m_PassIn[i] / m_PassOut[i] whatever the side's location;
-	// `decode` / `encode` are the planes the conversion launches of the pass read / write -- the caller's device planes, or
-	// for host planes slot i of m_PassYuvIn / m_PassYuvOut (rows padded to stagePitch, in the caller's memory order).
+	// `planes` are what the side's conversion launch of the pass reads (in: decode) / writes (out: encode) -- the caller's
+	// device planes, or for host planes slot i of m_PassYuvIn / m_PassYuvOut (rows padded to stagePitch, in the caller's
+	// memory order).
+	struct PassSide {
+		bool host = false, yuv = false;
+		PixelFormat format = PixelFormat::Bgrx;
+		int colorspace = 0;
+		YuvPlanes planes;
+	};
 	struct PassFrame {
-		bool hostIn = false, hostOut = false;
-		bool yuvIn = false, yuvOut = false;
-		PixelFormat formatIn = PixelFormat::Bgrx, formatOut = PixelFormat::Bgrx;
-		int csIn = 0, csOut = 0;
-		YuvPlanes decode, encode;
+		PassSide in, out;
+		bool host() const { return in.host || out.host; }
+		bool yuv() const { return in.yuv || out.yuv; }
 	};
 	PassFrame m_BatchHost[kFlowBatchMax];
+	// binds one side of a pass's frame (bindBatch): fills `side` and the side's part of the graph key, returns what the
+	// frame's kernels read / write there.  image / planes: the pass's own device buffers of that side and frame, made here
+	// when first needed.
+	struct BoundRows {
+		std::uint8_t *ptr;
+		std::ptrdiff_t stride;
+	};
+	BoundRows bindSide(const AnyFrame &a, std::size_t width, std::size_t height, DeviceBuffer *image, DeviceBuffer *planes,
+	    PassSide *side, YuvKey *key);
 	DeviceBuffer m_PassIn[kFlowBatchMax], m_PassOut[kFlowBatchMax];
 	DeviceBuffer m_PassYuvIn[kFlowBatchMax], m_PassYuvOut[kFlowBatchMax];
 	std::unique_ptr<Stream> m_CopyStream;
@@ -469,12 +451,10 @@ private:
 	unsigned m_PassSignalBase = 0;
 	std::uint64_t m_BatchHostFrames = 0, m_BatchYuvFrames = 0;
 	bool passEligible(const AnyFrame &in, const AnyFrame &out) const;
-	bool passEligible(const Frame &in, const Frame &out) const;
 	void uploadPassInputs(const AnyFrame *in, int n);
 	void drainPassOutputs(const AnyFrame *out, int n);
-	// the passes of processBatch / processFrames over checked frames
+	// the passes of processBatch / processFrames (whose staged pairs are checked: processFrames)
 	void runPasses(const AnyFrame *in, const AnyFrame *out, int count);
-	void submitAny(const AnyFrame &in, const AnyFrame &out);
 	static constexpr std::size_t kMaxBatchGraphs = 64;          // unregistered tuples (LRU)
 	static constexpr std::size_t kMaxRegisteredBatches = 256;   // tuples registered through prepareBatch
 	std::uint64_t m_BatchFrames = 0;
@@ -497,9 +477,8 @@ private:
 	Event m_GroupEvent;
 	std::uint64_t m_GroupFrames = 0;
 	bool sameModel(const Engine &o) const;
-	void checkGroupFrame(const Frame &f, bool input) const;
 	// one pass over members m[0 .. n) on `lead`'s stream and tensors (the lead need not be one of them)
-	static void runGroupPass(Engine &lead, Engine *const *m, const Frame *in, const Frame *out, int n);
+	static void runGroupPass(Engine &lead, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n);
 	std::uint64_t m_DirectClock = 0;
 	bool m_DirectGraph = true;  // JU_DIRECT_GRAPH=0: device frames always launch eagerly
 	static constexpr std::size_t kMaxDirectGraphs = 64;     // unregistered tuples (LRU)

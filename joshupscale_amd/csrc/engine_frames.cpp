@@ -1,0 +1,415 @@
+// Frames in and out of the engine: the staging copies of BGRX images, the one frame check, YUV planes through the
+// conversion kernels, the source stage (scale, mask) and the output stage, and submitFrame, the staged path that strings
+// them around a frame's program.  engine.cpp holds the program and submit(), the direct path; engine_passes.cpp the
+// look-ahead and group passes.
+#include <stdexcept>
+#include <string>
+
+#include "engine.h"
+#include "graphics.h"
+
+namespace ju {
+
+namespace {
+// Scoped map of a graphics resource on the engine's stream (cuda.h:310-349 GraphicsResource):
+// unmapped again when the copy has been enqueued, also when that throws.
+struct MappedResource {
+	GraphicsHandle *h;
+	hipStream_t stream;
+	GraphicsArray array;
+	MappedResource(void *handle, hipStream_t s) : h(static_cast<GraphicsHandle *>(handle)), stream(s) {
+		if (h == nullptr || h->backend == nullptr) throw std::invalid_argument("processImage: NULL graphics resource");
+		array = h->backend->map(h->resource, stream);
+	}
+	~MappedResource() { h->backend->unmap(h->resource, stream); }
+	MappedResource(const MappedResource &) = delete;
+	MappedResource &operator=(const MappedResource &) = delete;
+};
+}  // namespace
+
+void Engine::stageIn(const Frame &in) {
+	const FrameSize fs = frameSize();
+	checkFrame(anyOf(in), true, "processImage");  // (a pair that takes submit() is refused here, not up front)
+	if (in.location == Location::GraphicsResource) {
+		// map -> texture array -> staging buffer -> unmap (cuda_convert.h:57-77,
+		// cuda_convert.cc.cu:380-397); the array's own extent is what counts
+		MappedResource m(in.ptr, m_Stream);
+		if (!m.array.fourBytes || m.array.width != fs.inputWidth || m.array.height != fs.inputHeight ||
+		    in.width != fs.inputWidth || in.height != fs.inputHeight) {
+			throw std::invalid_argument("processImage: input texture must be " + std::to_string(fs.inputWidth) + "x" +
+			                            std::to_string(fs.inputHeight) + " with four 8-bit channels");
+		}
+		m.h->backend->copyFromArray(m_InStage.get(), fs.inputWidth * 4, m.array, fs.inputWidth * 4, fs.inputHeight,
+		    m_Stream);
+		return;
+	}
+	const std::size_t rowBytes = fs.inputWidth * 4;
+	const std::size_t rows = fs.inputHeight;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	auto *dst = m_InStage.as<std::uint8_t>();
+	auto *src = static_cast<std::uint8_t *>(in.ptr);
+	const RowSpan span = rowSpan(src, in.stride, rows);
+	switch (in.location) {
+	case Location::Host:
+		if (span.topDown) {
+			copyRows(dst, rowBytes, span.lowest, span.pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream);
+		} else {
+			// bottom-up frame (AviSynth RGB32, avisynth_plugin/src/main.cc:125-142): upload
+			// the rows in memory order, then flip on the device.
+			auto *raw = m_RawStage.as<std::uint8_t>();
+			copyRows(raw, rowBytes, span.lowest, span.pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream);
+			launchCopyRows(raw + (rows - 1) * rowBytes, -plain, dst, plain, rowBytes, rows, m_Stream);
+		}
+		break;
+	case Location::Device:
+		if (in.stride == plain) {
+			copyRows(dst, rowBytes, src, rowBytes, rowBytes, rows, hipMemcpyDeviceToDevice, m_Stream);
+		} else {
+			launchCopyRows(src, in.stride, dst, plain, rowBytes, rows, m_Stream);
+		}
+		break;
+	default:
+		throw std::invalid_argument(
+		    "processImage: GRAPHICS_RESOURCE images are not supported by this runtime");
+	}
+}
+
+void Engine::stageOut(const Frame &out, std::size_t width, std::size_t height, const std::uint8_t *src, std::uint8_t *raw) {
+	const FrameSize fs{0, 0, width, height};  // (the frame's own size: the model's output, or the output size set)
+	checkFrame(anyOf(out), false, "processImage");  // (behind the step, for a pair that takes submit(): as ju_process always did)
+	if (out.location == Location::GraphicsResource) {  // cuda_convert.cc.cu:419-436
+		MappedResource m(out.ptr, m_Stream);
+		if (!m.array.fourBytes || m.array.width != fs.outputWidth || m.array.height != fs.outputHeight ||
+		    out.width != fs.outputWidth || out.height != fs.outputHeight) {
+			throw std::invalid_argument("processImage: output texture must be " + std::to_string(fs.outputWidth) + "x" +
+			                            std::to_string(fs.outputHeight) + " with four 8-bit channels");
+		}
+		m.h->backend->copyToArray(m.array, src, fs.outputWidth * 4, fs.outputWidth * 4, fs.outputHeight, m_Stream);
+		return;
+	}
+	const std::size_t rowBytes = fs.outputWidth * 4;
+	const std::size_t rows = fs.outputHeight;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	auto *dst = static_cast<std::uint8_t *>(out.ptr);
+	const RowSpan span = rowSpan(dst, out.stride, rows);
+	switch (out.location) {
+	case Location::Host:
+		if (span.topDown) {
+			copyRows(span.lowest, span.pitch, src, rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, m_Stream);
+		} else {  // (bottom-up: flip on the device, download the rows in memory order)
+			launchCopyRows(src, plain, raw + (rows - 1) * rowBytes, -plain, rowBytes, rows, m_Stream);
+			copyRows(span.lowest, span.pitch, raw, rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, m_Stream);
+		}
+		break;
+	case Location::Device:
+		if (out.stride == plain) {
+			copyRows(dst, rowBytes, src, rowBytes, rowBytes, rows, hipMemcpyDeviceToDevice, m_Stream);
+		} else {
+			launchCopyRows(src, plain, dst, out.stride, rowBytes, rows, m_Stream);
+		}
+		break;
+	default:
+		throw std::invalid_argument(
+		    "processImage: GRAPHICS_RESOURCE images are not supported by this runtime");
+	}
+}
+
+// Everything a frame call can refuse, checked before anything is launched (the BGRX side repeats what stageIn /
+// stageOut would throw, so that a refused call has not run the step).
+void Engine::checkFrame(const AnyFrame &f, bool input, const char *who, bool declaredSize) const {
+	const FrameSize fs = frameSize();
+	const bool scaled = input && m_SrcScale.set();  // (input frames are the source's size while one is set)
+	const bool resized = !input && m_OutScale.set();  // (and output frames the output size)
+	const std::size_t w = scaled ? m_SrcScale.srcW() : (resized ? m_OutScale.dstW() : (input ? fs.inputWidth : fs.outputWidth));
+	const std::size_t h = scaled ? m_SrcScale.srcH() : (resized ? m_OutScale.dstH() : (input ? fs.inputHeight : fs.outputHeight));
+	const std::string side = input ? "input" : "output";
+	const std::string size = std::to_string(w) + "x" + std::to_string(h) +
+	                         (scaled ? " (the source size set)" : (resized ? " (the output size set)" : ""));
+	auto refuse = [who](const std::string &why) { throw std::invalid_argument(std::string(who) + ": " + why); };
+	if (!f.yuv) {
+		const Frame &b = f.bgrx;
+		const bool resource = b.location == Location::GraphicsResource;
+		if (resized && resource) {
+			refuse("graphics resources cannot be outputs while an output size is set (the scaler writes host or device memory)");
+		}
+		if (scaled && resource) {
+			refuse("graphics resources cannot be inputs while a source size is set (the scaler reads host or device memory)");
+		}
+		if (resource && !declaredSize) {
+			if (b.ptr == nullptr) refuse("NULL graphics resource");
+			return;  // (the texture's own extent is checked when it is mapped)
+		}
+		if (declaredSize && b.ptr == nullptr) refuse("NULL " + side + " image");
+		if (b.ptr == nullptr || b.width != w || b.height != h) refuse(side + " image must be exactly " + size);
+		const auto row = static_cast<std::ptrdiff_t>(w * 4);
+		if (!resource && b.stride > -row && b.stride < row) refuse("|stride| smaller than a row");
+		return;
+	}
+	const YuvFrame &y = f.planes;
+	const YuvFormatInfo *known = yuvFormatInfo(fmt(y.format));
+	if (known == nullptr) refuse("unknown " + side + " pixel format");
+	const YuvFormatInfo &info = *known;
+	const std::string name = info.name;
+	// (an RGB frame has no colour space: the field is ignored)
+	if (!info.rgb() && (y.colorspace < 0 || y.colorspace > 3)) refuse("unknown " + side + " colour space " + std::to_string(y.colorspace));
+	if (y.location != Location::Host && y.location != Location::Device) {
+		refuse(name + " " + side + " frames must be host or device memory (no graphics resources)");
+	}
+	if (info.sampling == 420 && (y.width % 2 || y.height % 2)) refuse(name + " needs an even width and height");
+	if (info.sampling == 422 && y.width % 2) refuse(name + " (4:2:2) needs an even width");
+	if (y.width != w || y.height != h) refuse(side + " frame must be exactly " + size);
+	for (int k = 0; k < info.planes; ++k) {
+		const std::string plane = side + " plane " + std::to_string(k);
+		if (y.planes[k] == nullptr) refuse(plane + " is NULL");
+		const auto sample = static_cast<std::size_t>(info.sampleBytes);
+		if (sample > 1 && (reinterpret_cast<std::uintptr_t>(y.planes[k]) % sample != 0 ||
+		                   y.strides[k] % static_cast<std::ptrdiff_t>(sample) != 0)) {
+			refuse(plane + ": " + name + " samples are " + (sample == 2 ? "16-bit" : "32-bit") +
+			       " words -- the plane's address and its stride must be multiples of " + std::to_string(sample));
+		}
+		const auto row = static_cast<std::ptrdiff_t>(planeShape(info, w, h, k).rowBytes);
+		if (y.strides[k] > -row && y.strides[k] < row) refuse(plane + ": |stride| smaller than a row");
+	}
+}
+
+void Engine::checkPair(const AnyFrame &in, const AnyFrame &out) const {
+	if (!staged(in, out)) return;  // (a pair that takes submit() is refused where it is staged, as ju_process always did)
+	checkFrame(in, true);
+	checkFrame(out, false);
+}
+
+void Engine::stageInYuv(const YuvFrame &in, std::uint8_t *stage, std::uint8_t *bgrx) {
+	const bool host = in.location != Location::Device;
+	if (host) copyPlanes(in, stage, true, m_Stream);
+	const YuvPlanes pl = host ? stagedPlanes(in, stage) : callerPlanes(in);
+	launchDecodeFrame(fmt(in.format), in.colorspace, pl, bgrx, static_cast<std::ptrdiff_t>(in.width * 4), static_cast<int>(in.width),
+	    static_cast<int>(in.height), m_Stream);
+}
+
+bool Engine::deepFromState(PixelFormat format) const {
+	// (a mask: the blended frame exists in 8 bits only)
+	return m_HbdFromState && m_MaskW == 0 && formatInfo(format).deep();
+}
+
+// one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit YUV or
+// a deep RGB format of a runtime whose state is the frame in float (m_HbdFromState), the f16 state that frame left -- -> planes
+void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::size_t width, std::size_t height,
+    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16) {
+	const int w = static_cast<int>(width), h = static_cast<int>(height);
+	if (!deepFromState(format)) {
+		launchEncodeFrame(fmt(format), colorspace, bgrx, bgrxStride, planes, w, h, m_Stream);
+	} else if (frame16 != nullptr) {  // (the output stage: the state's samples, scaled)
+		launchEncodeFrame16(fmt(format), colorspace, frame16, planes, w, h, m_Stream);
+	} else {
+		launchEncodeState(fmt(format), colorspace, state, planes, w, h, m_Stream);
+	}
+}
+
+// the frame of out.width x out.height -- its dense BGRX rows, or for deepFromState formats the state or the 16-bit frame
+void Engine::stageOutYuv(const YuvFrame &out, const std::uint8_t *bgrx, const void *state, const std::uint16_t *frame16,
+    std::uint8_t *stage) {
+	const bool host = out.location == Location::Host;
+	// (a host frame: the kernel writes the staging buffer in the caller's row order, copied out below)
+	const YuvPlanes pl = host ? stagedPlanes(out, stage) : callerPlanes(out);
+	encodeYuv(out.format, out.colorspace, pl, out.width, out.height, bgrx, static_cast<std::ptrdiff_t>(out.width * 4), state,
+	    frame16);
+	if (host) copyPlanes(out, stage, false, m_Stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Source stage (docs/source_stage.md).  What the reference's OBS filter does around processImage in its graphics API
+// (obs_plugin/src/filter.cc:351-379: any source drawn into the model's input texture; :393-402 with blend.effect: the
+// point-sampled source drawn back over the output through mask.png), as two kernels around the staged graph of
+// submitFrame: scale_bgrx_kernel fills m_InStage from the source frame, mask_blend_kernel rewrites m_OutStage.  Both
+// settings are per runtime and opt-in; neither touches a captured graph, the state or the frame history.
+// ---------------------------------------------------------------------------------------------------------------
+void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
+	DeviceGuard g(m_Device);
+	const std::string unknown = scaleFilterProblem(filter);
+	if (!unknown.empty()) throw std::invalid_argument("ju_set_source_size: " + unknown);
+	if (width == 0 && height == 0) {
+		m_Stream.synchronize();  // (enqueued frames may still read the tables)
+		m_SrcScale.clear();
+		m_SrcStage = DeviceBuffer();
+		m_SrcYuvStage = DeviceBuffer();
+		return;
+	}
+	const FrameSize fs = frameSize();
+	const std::string problem = sourceSizeProblem(width, height, fs.inputWidth, fs.inputHeight, filter);
+	if (!problem.empty()) throw std::invalid_argument("ju_set_source_size: " + problem);
+	Scaler scale;
+	scale.build(width, height, fs.inputWidth, fs.inputHeight, filter);
+	DeviceBuffer stage(width * height * 4), yuvStage(yuvStageBytes(kFormatTable, width, height));
+	m_Stream.synchronize();
+	m_SrcScale = std::move(scale);
+	m_SrcStage = std::move(stage);
+	m_SrcYuvStage = std::move(yuvStage);
+}
+
+void Engine::sourceSize(std::size_t *width, std::size_t *height) const {
+	if (width) *width = m_SrcScale.srcW();
+	if (height) *height = m_SrcScale.srcH();
+}
+
+void Engine::setSourceMask(const Frame *mask) {
+	DeviceGuard g(m_Device);
+	if (mask == nullptr) {
+		m_Stream.synchronize();
+		m_Mask = DeviceBuffer();
+		m_MaskW = m_MaskH = 0;
+		m_MaskStride = 0;
+		return;
+	}
+	if (mask->location != Location::Host && mask->location != Location::Device) {
+		throw std::invalid_argument("ju_set_source_mask: the mask must be host or device memory");
+	}
+	constexpr std::size_t kMaskMax = 16384;
+	if (mask->ptr == nullptr || mask->width < 1 || mask->height < 1 || mask->width > kMaskMax || mask->height > kMaskMax) {
+		throw std::invalid_argument("ju_set_source_mask: the mask must be 1 .. 16384 pixels on each axis");
+	}
+	const std::size_t rowBytes = mask->width * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	if (mask->stride > -plain && mask->stride < plain) {
+		throw std::invalid_argument("ju_set_source_mask: |stride| smaller than a row");
+	}
+	// copied once, in the caller's memory order (a bottom-up mask stays bottom-up and is read with a negative stride)
+	DeviceBuffer buf(rowBytes * mask->height);
+	const RowSpan rows = rowSpan(mask->ptr, mask->stride, mask->height);
+	copyRows(buf.get(), rowBytes, rows.lowest, rows.pitch, rowBytes, mask->height,
+	    mask->location == Location::Host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, nullptr);
+	// (on the null stream and waited for, as a blocking copy is: behind what the caller's own default-stream work wrote)
+	JU_HIP(hipStreamSynchronize(nullptr));
+	m_Stream.synchronize();
+	m_Mask = std::move(buf);
+	m_MaskW = mask->width;
+	m_MaskH = mask->height;
+	m_MaskStride = rows.topDown ? plain : -plain;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Output stage (docs/output_stage.md).  What the reference's OBS caller gets from OBS's canvas scaling behind
+// processImage: the upscaled frame at any size.  Behind the staged graph and the mask blend of submitFrame the frame is
+// scaled by the source stage's scaler (the triangle or a cubic filter) with the output axes' tables: the 8-bit frame in m_OutStage by
+// scale_bgrx_kernel, or -- for a deep format that is encoded from the state (deepFromState) -- the state's 16-bit samples
+// by scale_state_kernel into m_OutScaled16, which launchEncodeFrame16 encodes.  Nothing of the step itself changes.
+// ---------------------------------------------------------------------------------------------------------------
+void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
+	DeviceGuard g(m_Device);
+	const FrameSize fs = frameSize();
+	const bool off = width == 0 && height == 0;
+	const std::string problem = outputSizeProblem(off ? fs.outputWidth : width, off ? fs.outputHeight : height, fs.outputWidth,
+	    fs.outputHeight, filter);
+	if (!problem.empty()) throw std::invalid_argument("ju_set_output_size: " + problem);
+	if (off) {
+		m_Stream.synchronize();  // (enqueued frames may still read the tables and write the buffers)
+		m_OutScale.clear();
+		for (DeviceBuffer *b : {&m_OutScaled8, &m_OutScaled16, &m_OutYuvStage, &m_OutRawStage}) *b = DeviceBuffer();
+		return;
+	}
+	Scaler scale;
+	scale.build(fs.outputWidth, fs.outputHeight, width, height, filter);
+	DeviceBuffer scaled8(width * height * 4), scaled16(width * height * 8), raw(width * height * 4);
+	DeviceBuffer yuvStage(yuvStageBytes(kFormatTable, width, height));
+	m_Stream.synchronize();
+	m_OutScale = std::move(scale);
+	m_OutScaled8 = std::move(scaled8);
+	m_OutScaled16 = std::move(scaled16);
+	m_OutRawStage = std::move(raw);
+	m_OutYuvStage = std::move(yuvStage);
+}
+
+void Engine::outputSize(std::size_t *width, std::size_t *height) const {
+	if (width) *width = m_OutScale.dstW();
+	if (height) *height = m_OutScale.dstH();
+}
+
+// The stage-out of a frame while an output size is set: scale, then copy or encode at output size.  A device BGRX image
+// is written in place (the kernel takes any alignment and signed stride); a host image and YUV planes go through the
+// scaled staging buffers.
+void Engine::stageOutScaled(const AnyFrame &out) {
+	const std::size_t ow = m_OutScale.dstW(), oh = m_OutScale.dstH();
+	auto scale8 = [&](std::uint8_t *dst, std::ptrdiff_t stride) {
+		m_OutScale.scaleBgrx(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(m_OutScale.srcW() * 4), dst, stride, m_Stream);
+	};
+	auto *scaled8 = m_OutScaled8.as<std::uint8_t>();
+	const auto plain = static_cast<std::ptrdiff_t>(ow * 4);
+	if (!out.yuv) {
+		const Frame &b = out.bgrx;
+		if (b.location == Location::Device) return scale8(static_cast<std::uint8_t *>(b.ptr), b.stride);
+		scale8(scaled8, plain);
+		return stageOut(b, ow, oh, scaled8, m_OutRawStage.as<std::uint8_t>());
+	}
+	auto *yuvStage = m_OutYuvStage.as<std::uint8_t>();
+	if (deepFromState(out.planes.format)) {
+		auto *scaled16 = m_OutScaled16.as<std::uint16_t>();
+		m_OutScale.scaleState(m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get(), scaled16, m_Stream);
+		return stageOutYuv(out.planes, nullptr, nullptr, scaled16, yuvStage);
+	}
+	scale8(scaled8, plain);
+	stageOutYuv(out.planes, scaled8, nullptr, nullptr, yuvStage);
+}
+
+// The input of a frame while a source size is set, as BGRX rows at source size: a device image is read where it is, a
+// host image is uploaded in its memory order, YUV planes are decoded by the existing conversion, unchanged.
+Engine::SourceView Engine::stageInSource(const AnyFrame &in) {
+	const std::size_t rowBytes = m_SrcScale.srcW() * 4, height = m_SrcScale.srcH();
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	auto *stage = m_SrcStage.as<std::uint8_t>();
+	if (in.yuv) {
+		stageInYuv(in.planes, m_SrcYuvStage.as<std::uint8_t>(), stage);
+		return {stage, plain};
+	}
+	const Frame &b = in.bgrx;
+	if (b.location == Location::Device) return {static_cast<std::uint8_t *>(b.ptr), b.stride};
+	const RowSpan rows = rowSpan(b.ptr, b.stride, height);
+	copyRows(stage, rowBytes, rows.lowest, rows.pitch, rowBytes, height, hipMemcpyHostToDevice, m_Stream);
+	if (rows.topDown) return {stage, plain};
+	return {stage + static_cast<std::ptrdiff_t>(height - 1) * plain, -plain};
+}
+
+// Staged frames (a YUV side; any pair while a source or output stage is set): always through the staging buffers -- the conversion kernel takes the place of the
+// staging copy on its side and the binding set's staged graph replays unchanged.  The conversions are eager launches
+// on m_Stream OUTSIDE the per-device chain lock, like the staging copies of submit().
+void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
+	m_DirectIO = false;
+	bindStaging();
+	const FrameSize fs = frameSize();
+	const int inW = static_cast<int>(fs.inputWidth), inH = static_cast<int>(fs.inputHeight);
+	// what the mask lets through: the source frame at source size, or the model-size input frame
+	SourceView source{m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4)};
+	if (m_SrcScale.set()) {
+		source = stageInSource(in);
+		m_SrcScale.scaleBgrx(source.ptr, source.stride, m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4),
+		    m_Stream);
+	} else if (in.yuv) {
+		stageInYuv(in.planes, m_YuvInStage.as<std::uint8_t>(), m_InStage.as<std::uint8_t>());
+	} else {
+		stageIn(in.bgrx);
+	}
+	{
+		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
+		runProgram();
+		chainEnd(chain, m_Resident);
+	}
+	if (m_MaskW != 0) {
+		// over the frame handed to the caller only: state and history are the unmasked run's
+		launchMaskBlend(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4),
+		    static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight), source.ptr, source.stride,
+		    m_SrcScale.set() ? static_cast<int>(m_SrcScale.srcW()) : inW, m_SrcScale.set() ? static_cast<int>(m_SrcScale.srcH()) : inH,
+		    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0),
+		    m_MaskStride, static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), m_Stream);
+	}
+	if (sourceStage()) ++m_SourceFrames;
+	// (behind the frame's program and before the flip: the state this frame wrote is the binding set's output)
+	if (m_OutScale.set()) {
+		stageOutScaled(out);
+	} else if (out.yuv) {
+		stageOutYuv(out.planes, m_OutStage.as<std::uint8_t>(), m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get(), nullptr,
+		    m_YuvOutStage.as<std::uint8_t>());
+	} else {
+		stageOut(out.bgrx, fs.outputWidth, fs.outputHeight, m_OutStage.as<std::uint8_t>(), m_RawStage.as<std::uint8_t>());
+	}
+	m_Idx ^= 1;
+}
+
+}  // namespace ju

@@ -1,0 +1,643 @@
+// Look-ahead passes (processBatch, processFrames) and group passes (processGroup): several frames under the flow net's
+// launches of one.  engine.cpp holds the per-frame program they reuse, engine_frames.cpp the staged path of the frames
+// that run one by one.
+#include <algorithm>
+#include <atomic>
+#include <set>
+#include <stdexcept>
+#include <string>
+
+#include "engine.h"
+#include "log.h"
+
+namespace ju {
+
+// ---------------------------------------------------------------------------------------------------------------
+// Frame look-ahead.  The flow net reads LR frames only -- never the HR state (models.py:790, 823: its input is the
+// packed history of the last num_flow_inputs frames) -- so the flow fields of n consecutive frames can be computed
+// before the first of them is upscaled: ONE pass of the flow net's eight launches over n frames instead of n passes.
+// At 480x270 each of those launches is ONE round of 136-240 workgroups on 256 CUs -- a 7-24 us latency chain (weights,
+// staging, conv A, conv B, stores) with most SIMDs idle most of the time (0.3-0.6 waves per SIMD,
+// profiles/r05_pmc_stall_flow.txt): over 8 frames the same launches take 62 instead of 105 us per frame
+// (profiles/r05_flow_layers_pass.txt; priced beforehand by tools/probes/flow_batch_estimate.py), and a pass pays one
+// synchronisation instead of eight: 2163 -> 2461 frames/s (profiles/r05_lookahead_bench_box_a.txt).  The recurrent part -- warp, tower,
+// tail -- stays strictly frame by frame, and every frame's bytes are those of process(): the same kernels add the
+// same terms in the same order whatever the launch's size.
+//
+// State.  Frame i of a pass reads the state frame i - 1 wrote; the pass owns the n - 1 buffers in between, reads
+// m_State[set] and leaves the last frame's state in m_State[set ^ 1] and the last history in m_Packed[set ^ 1], as
+// ONE process() call would: the pass flips the binding set once, and -- since nothing it wrote is read before the
+// pass -- a pass that failed (resident tower: bounded wait expired) can be run again frame by frame.
+// ---------------------------------------------------------------------------------------------------------------
+bool Engine::batchPlanned(int items, bool group) {
+	if (!m_Config.recurrent()) {
+		// a flow-free model: a pass is its frames' generator programs under one synchronisation -- no flow launches,
+		// no pass tensors, and every frame's tail writes the one scratch state
+		if (m_BatchUnsupported || m_Calibrate) return false;
+		for (int set = 0; set < 2; ++set) m_BatchFlow[{items, set}];
+		m_BatchFlow[{items, kGroupSet}];
+		m_BatchCap = std::max({m_BatchCap, items, m_BatchMax});
+		return true;
+	}
+	if (m_BatchUnsupported || m_Calibrate || m_Config.flowArch != 0 || !flowPacksInBlock() || m_Config.normalizeBrightness) {
+		return false;
+	}
+	if (items <= m_BatchCap && m_BatchFlow.count({items, group ? kGroupSet : 0})) return true;
+	try {
+		if (items > m_BatchCap) {
+			// (the tensors of every pass so far are too small: start over)
+			m_Stream.synchronize();
+			m_BatchGraphs.clear();
+			m_BatchFlow.clear();
+			m_BatchTensors.clear();
+			// (the whole cap at once: growing later reallocates the tensors every captured pass is bound to -- also the
+			// registered ones -- and round 6's bench lost a registered short pass that way.  ~210 MB at 480x270 for 8 frames.)
+			const int cap = std::max(items, m_BatchMax);
+			for (const auto &kv : m_Tensors) {
+				const bool flowTensor = kv.first == "flow" || kv.first.rfind("flow/", 0) == 0;
+				if (!flowTensor) continue;
+				Tensor t;
+				t.count = kv.second.count * cap;
+				t.isF32 = kv.second.isF32;
+				t.isState = kv.second.isState;
+				t.buf = DeviceBuffer(t.count * (t.isF32 ? 4 : 2));
+				m_BatchTensors.emplace(kv.first, std::move(t));
+			}
+			m_BatchCap = cap;
+		}
+		if (group) {  // (a group pass chains no states: each member reads and writes its own)
+			std::vector<Step> prog;
+			addFlowAutoencoder(&prog, 0, items, true);
+			m_BatchFlow[{items, kGroupSet}] = std::move(prog);
+			return true;
+		}
+		for (int i = 0; i + 1 < m_BatchCap; ++i) {
+			if (!m_BatchState[i].get()) m_BatchState[i] = DeviceBuffer(m_State[0].bytes());
+		}
+		for (int set = 0; set < 2; ++set) {
+			std::vector<Step> prog;
+			addFlowAutoencoder(&prog, set, items);
+			m_BatchFlow[{items, set}] = std::move(prog);
+		}
+		return true;
+	} catch (const std::exception &e) {
+		// (std::logic_error: a launch of this model's flow plan has no item dimension; anything else -- the pass's
+		// tensors did not fit the device -- equally means "frame by frame from now on", not a failed call)
+		logMessage(dynamic_cast<const std::logic_error *>(&e) ? LogLevel::Info : LogLevel::Warning, "Engine",
+		    std::string("frame look-ahead is off for this runtime: ") + e.what());
+		m_BatchUnsupported = true;
+		m_BatchFlow.clear();
+		m_BatchTensors.clear();
+		m_BatchCap = 0;
+		return false;
+	}
+}
+
+void Engine::setLookahead(int frames) {
+	DeviceGuard g(m_Device);
+	const int cap = std::min(std::max(frames, 1), kFlowBatchMax);
+	if (cap < m_BatchMax) {
+		// graphs of longer passes can no longer be asked for: drop them (their launches may still be in flight)
+		m_Stream.synchronize();
+		for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
+			it = static_cast<int>(it->first.size()) > cap ? m_BatchGraphs.erase(it) : std::next(it);
+		}
+	}
+	m_BatchMax = cap;
+}
+
+void Engine::dropBatchGraphs() {
+	m_BatchGraphs.clear();
+}
+
+// The launches of one look-ahead pass over the n frames of m_BatchIO, in stream order (recorded when m_Stream is
+// capturing): the flow net over all frames, then frame by frame the rest of binding set `set`'s per-frame program,
+// bound to the frame's buffers, its flow field and its link of the state chain.
+void Engine::runBatch(int set, int n, const std::function<void(const Step &, bool)> *around) {
+	auto run = [&](const Step &st) {
+		if (around) (*around)(st, false);
+		st.run(m_Stream);
+		if (around) (*around)(st, true);
+	};
+	const std::vector<Step> &flow = m_BatchFlow.at({n, set});
+	const bool recurrent = m_Config.recurrent();  // (flow-free: no flow fields, no state chain)
+	const long flowItem = recurrent ? static_cast<long>(m_Tensors.at("flow").count) * 2 : 0;
+	const unsigned char *flowBase = recurrent ? m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
+	const FrameIO keepIO = m_IO;
+	const StateBind keepBind = m_StateBind[set];
+	const void *keepFlow = m_FlowCur;
+	struct Restore {
+		std::function<void()> f;
+		~Restore() { f(); }
+	} restore{[&] {
+		m_IO = keepIO;
+		m_StateBind[set] = keepBind;
+		m_FlowCur = keepFlow;
+	}};
+	// the pass's YUV inputs into their frames' BGRX buffers, all in one launch (a flow-free pass has no launch before it)
+	YuvDecodeItems items{};
+	int decodes = 0;
+	for (int i = 0; i < n; ++i) {
+		const PassFrame &pf = m_BatchHost[i];
+		if (!pf.in.yuv) continue;
+		items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(m_BatchIO[i].in),
+		    m_BatchIO[i].inStride);
+	}
+	if (decodes) {
+		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),
+		    m_Stream);
+	}
+	for (const Step &st : flow) run(st);
+	for (int i = 0; i < n; ++i) {
+		m_IO = m_BatchIO[i];
+		if (recurrent) {
+			m_FlowCur = flowBase + i * flowItem;
+			m_StateBind[set].in = i == 0 ? keepBind.in : m_BatchState[i - 1].get();
+			m_StateBind[set].out = i + 1 == n ? keepBind.out : m_BatchState[i].get();
+		}
+		for (const Step &st : m_Program[set]) {
+			if (st.tag != "flow" && st.tag != "pack") run(st);
+		}
+		if (m_BatchHost[i].out.yuv) {  // the frame's BGRX output (m_PassOut[i]) into the caller's device planes / the staging slot
+			// (a 10-bit output from the state: THIS frame's link of the chain -- m_BatchState[i], the last frame's
+			// m_State[set ^ 1]; a flow-free pass has one scratch state that the next frame's tail overwrites, so the encode
+			// stays on this stream in front of the next frame's kernels)
+			const FrameSize fs = frameSize();
+			encodeYuv(m_BatchHost[i].out.format, m_BatchHost[i].out.colorspace, m_BatchHost[i].out.planes, fs.outputWidth, fs.outputHeight,
+			    m_BatchIO[i].out, m_BatchIO[i].outStride, m_StateBind[set].out);
+		}
+		// (a host frame: its bytes are complete in m_PassOut[i] / m_PassYuvOut[i] -- tell the thread that copies them out)
+		if (m_BatchHost[i].out.host) launchSignalHost(m_PassSignal.device(), m_Stream);
+	}
+}
+
+// A frame may go into a pass when each of its two images is either a device-resident one the kernels can read / write in
+// place (directEligible's conditions) or a host image of the right size (staged through the pass's own device buffers).
+// A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
+bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
+	if (sourceStage()) return false;  // (scaled / masked frames run one by one through submitFrame)
+	const FrameSize fs = frameSize();
+	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align) {
+		if (a.yuv) {
+			const YuvFrame &y = a.planes;
+			return (y.location == Location::Host || y.location == Location::Device) && y.width == w && y.height == h;
+		}
+		const Frame &f = a.bgrx;
+		const auto row = static_cast<std::ptrdiff_t>(w * 4);
+		if (f.ptr == nullptr || f.width != w || f.height != h || !(f.stride >= row || -f.stride >= row)) return false;
+		if (f.location == Location::Host) return true;
+		return f.location == Location::Device && m_PreferDirect && reinterpret_cast<std::uintptr_t>(f.ptr) % align == 0 &&
+		       f.stride % static_cast<std::ptrdiff_t>(align) == 0;
+	};
+	return side(in, fs.inputWidth, fs.inputHeight, 4) && side(out, fs.outputWidth, fs.outputHeight, 8);
+}
+
+// Binds the n frames of a pass: m_BatchIO[i] = what frame i's kernels read and write -- the caller's device memory, or
+// for a host image the pass's device buffer i, addressed with the SIGN of the caller's stride (a bottom-up host frame is
+// uploaded / downloaded in memory order and read / written bottom-up by the kernels: no flip pass).  The key of the
+// pass's graph is made of those bindings, so all-host passes of one length and orientation share one graph.
+//
+// YUV frames in look-ahead passes (processFrames).  A YUV input of frame i is decoded into m_PassIn[i], a YUV output
+// encoded from m_PassOut[i] (top-down BGRX rows both), whatever the planes' location: m_BatchHost[i].in / .out hold
+// the planes those conversion launches read / write.  Device planes: the caller's, in place.  Host planes: slot i of
+// m_PassYuvIn / m_PassYuvOut, plane after plane with rows padded to stagePitch and in the caller's MEMORY order, so a
+// bottom-up plane is addressed from its last row with a negative pitch -- the layout of stageInYuv / stageOutYuv.
+std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set) {
+	const FrameSize fs = frameSize();
+	std::vector<PassKey> key(static_cast<std::size_t>(n));
+	for (int i = 0; i < n; ++i) {
+		FrameIO &io = m_BatchIO[i];
+		PassFrame &pf = m_BatchHost[i];
+		PassKey &k = key[static_cast<std::size_t>(i)];
+		const BoundRows r = bindSide(in[i], fs.inputWidth, fs.inputHeight, &m_PassIn[i], &m_PassYuvIn[i], &pf.in, &k.in);
+		const BoundRows w = bindSide(out[i], fs.outputWidth, fs.outputHeight, &m_PassOut[i], &m_PassYuvOut[i], &pf.out, &k.out);
+		io = FrameIO{r.ptr, r.stride, w.ptr, w.stride};
+		if (pf.out.host) {
+			if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
+			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
+		}
+		k.io = DirectKey{io.in, io.inStride, io.out, io.outStride, set};
+	}
+	return key;
+}
+
+Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::size_t height, DeviceBuffer *image,
+    DeviceBuffer *planes, PassSide *side, YuvKey *key) {
+	*side = PassSide{};
+	side->yuv = a.yuv;
+	side->host = locationOf(a) == Location::Host;
+	// (a device image: the caller's, in place)
+	if (!a.yuv && !side->host) return {static_cast<std::uint8_t *>(a.bgrx.ptr), a.bgrx.stride};
+	const auto row = static_cast<std::ptrdiff_t>(width * 4);
+	if (!image->get()) *image = DeviceBuffer(height * static_cast<std::size_t>(row));
+	auto *base = image->as<std::uint8_t>();
+	if (!a.yuv) {  // a host image: the pass's buffer in the caller's memory order
+		const bool up = a.bgrx.stride >= 0;
+		return {up ? base : base + static_cast<std::ptrdiff_t>(height - 1) * row, up ? row : -row};
+	}
+	// a YUV side: the planes its conversion launch addresses, and what of them the graph bakes in
+	const YuvFrame &y = a.planes;
+	const YuvFormatInfo &info = formatInfo(y.format);
+	side->format = y.format;
+	side->colorspace = y.colorspace;
+	key->format = static_cast<int>(y.format);
+	key->colorspace = info.rgb() ? 0 : y.colorspace;  // (ignored for RGB: no second graph for another value)
+	for (int k = 0; k < info.planes; ++k) {
+		key->planes[k] = side->host ? nullptr : y.planes[k];
+		key->strides[k] = side->host ? (y.strides[k] > 0 ? 1 : -1) : y.strides[k];
+	}
+	if (side->host) {
+		if (!planes->get()) *planes = DeviceBuffer(yuvStageBytes(kFormatTable, y.width, y.height));
+		side->planes = stagedPlanes(y, planes->as<std::uint8_t>());
+	} else {
+		side->planes = callerPlanes(y);
+	}
+	return {base, row};
+}
+
+// Every host input of the pass into its device buffer, rows in MEMORY order (the binding carries the orientation), on the
+// engine's stream in front of the pass's launches.  Pageable memory: the runtime stages or page-locks per call, as in
+// stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in stageInYuv.
+void Engine::uploadPassInputs(const AnyFrame *in, int n) {
+	const FrameSize fs = frameSize();
+	const std::size_t rowBytes = fs.inputWidth * 4, rows = fs.inputHeight;
+	for (int i = 0; i < n; ++i) {
+		if (!m_BatchHost[i].in.host) continue;
+		if (in[i].yuv) {
+			copyPlanes(in[i].planes, m_PassYuvIn[i].as<std::uint8_t>(), true, m_Stream);
+			continue;
+		}
+		const RowSpan host = rowSpan(in[i].bgrx.ptr, in[i].bgrx.stride, rows);
+		copyRows(m_PassIn[i].get(), rowBytes, host.lowest, host.pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream);
+	}
+}
+
+// The thread blocked in processBatch: wait for frame i's completion count, copy frame i out on the copy stream while the
+// GPU runs frame i + 1, in order.  The wait is bounded by the pass itself: once the engine's stream has drained, a count
+// that has not arrived never will.  A YUV frame goes out plane by plane from its staging slot (3.1 MB at 1080p instead of
+// BGRX's 8.3 MB), as in stageOutYuv.
+void Engine::drainPassOutputs(const AnyFrame *out, int n) {
+	const FrameSize fs = frameSize();
+	const std::size_t rowBytes = fs.outputWidth * 4, rows = fs.outputHeight;
+	volatile unsigned *word = m_PassSignal.host();
+	unsigned due = 0;
+	bool any = false;
+	for (int i = 0; i < n; ++i) {
+		if (!m_BatchHost[i].out.host) continue;
+		++due;
+		auto arrived = [&] { return static_cast<int>(*word - m_PassSignalBase) >= static_cast<int>(due); };
+		for (unsigned spins = 1; !arrived(); ++spins) {
+			if ((spins & 255u) == 0) {
+				const hipError_t st = hipStreamQuery(m_Stream);
+				if (st == hipSuccess) {
+					if (arrived()) break;
+					throw std::runtime_error("look-ahead pass: the completion count of a host frame did not arrive");
+				}
+				if (st != hipErrorNotReady) JU_HIP(st);
+			} else {
+				__builtin_ia32_pause();
+			}
+		}
+		any = true;
+		if (out[i].yuv) {
+			copyPlanes(out[i].planes, m_PassYuvOut[i].as<std::uint8_t>(), false, *m_CopyStream);
+			continue;
+		}
+		const RowSpan host = rowSpan(out[i].bgrx.ptr, out[i].bgrx.stride, rows);
+		copyRows(host.lowest, host.pitch, m_PassOut[i].get(), rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, *m_CopyStream);
+	}
+	if (any) JU_HIP(hipStreamSynchronize(*m_CopyStream));
+}
+
+Engine::DirectEntry &Engine::batchEntry(const std::vector<PassKey> &key) {
+	auto it = m_BatchGraphs.find(key);
+	if (it == m_BatchGraphs.end()) {
+		// least recently used out -- among the tuples nobody registered: a tuple handed to prepareBatch keeps its graphs
+		// (the header promises that process calls on it never capture), as registered pairs do; only a caller that keeps
+		// registering new tuples (more than kMaxRegisteredBatches) loses the registered one it used least recently
+		std::size_t registered = 0;
+		for (const auto &kv : m_BatchGraphs) registered += kv.second.registered ? 1 : 0;
+		if (m_BatchGraphs.size() - registered >= kMaxBatchGraphs || registered >= kMaxRegisteredBatches) {
+			const bool fromRegistered = m_BatchGraphs.size() - registered < kMaxBatchGraphs;
+			auto victim = m_BatchGraphs.end();
+			for (auto j = m_BatchGraphs.begin(); j != m_BatchGraphs.end(); ++j) {
+				if (j->second.registered != fromRegistered) continue;
+				if (victim == m_BatchGraphs.end() || j->second.lastUse < victim->second.lastUse) victim = j;
+			}
+			if (victim != m_BatchGraphs.end()) m_BatchGraphs.erase(victim);
+		}
+		it = m_BatchGraphs.emplace(key, DirectEntry{}).first;
+	}
+	it->second.lastUse = ++m_DirectClock;
+	return it->second;
+}
+
+// ju_prepare_batch: the graphs of a tuple of frame buffers a caller is going to hand to processBatch, one per
+// binding set, captured NOW (as prepareFrames does for one pair): nothing executes, no buffer is touched.  Returns
+// the graphs captured; 0 for a tuple that will not go as one pass.
+int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
+	if (n < 0 || (n > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("prepareBatch: bad arguments");
+	DeviceGuard g(m_Device);
+	if (n < 2 || n > m_BatchMax || !m_UseGraph || !m_DirectGraph) return 0;
+	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
+	for (int i = 0; i < n; ++i) {
+		if (!passEligible(anyIn[i], anyOut[i])) return 0;
+	}
+	if (!batchPlanned(n)) return 0;
+	std::unique_lock<std::mutex> chain = chainBegin(m_Resident);  // (no capture while another engine's constructor drains the device)
+	int captured = 0;
+	for (int set = 0; set < 2; ++set) {
+		DirectEntry &e = batchEntry(bindBatch(anyIn.data(), anyOut.data(), n, set));
+		e.registered = true;
+		if (e.graph.valid()) continue;
+		{
+			DryLaunchScope dry;  // the attributes of the tile heights this pass's launch sizes choose
+			for (const Step &st : m_BatchFlow.at({n, set})) st.run(m_Stream);
+		}
+		e.graph = GraphExec::capture(m_Stream, [&] { runBatch(set, n); });
+		e.seen = 2;
+		++captured;
+		++m_PreparedCaptures;
+	}
+	return captured;
+}
+
+// One look-ahead pass over frames [0, n): enqueue only.  On return the binding set is flipped ONCE (see above).
+void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
+	const int set = m_Idx;
+	const std::vector<PassKey> key = bindBatch(in, out, n, set);
+	uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
+	m_PassSignalBase = m_PassSignal.host() ? *m_PassSignal.host() : 0u;
+	for (int i = 0; i < n; ++i) {
+		m_BatchHostFrames += m_BatchHost[i].host() ? 1 : 0;
+		m_BatchYuvFrames += m_BatchHost[i].yuv() ? 1 : 0;
+	}
+	{
+		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
+		bool replayed = false;
+		if (m_UseGraph && m_DirectGraph) {
+			DirectEntry &e = batchEntry(key);
+			// (first sighting: eager -- it also sets the dynamic-LDS attribute of a tile height this pass's launch
+			// sizes choose for the first time, which must not happen inside a capture; second: capture and replay)
+			if (!e.graph.valid() && ++e.seen >= 2) {
+				e.graph = GraphExec::capture(m_Stream, [&] { runBatch(set, n); });
+				++m_InlineCaptures;
+			}
+			if (e.graph.valid()) {
+				e.graph.launch(m_Stream);
+				++m_GraphReplays;
+				replayed = true;
+			}
+		}
+		if (!replayed) {
+			runBatch(set, n);
+			++m_EagerRuns;
+		}
+		chainEnd(chain, m_Resident);
+	}
+	m_Idx = set ^ 1;
+	m_BatchFrames += static_cast<std::uint64_t>(n);
+}
+
+namespace {
+std::atomic<int> g_PassRerun{0};
+}  // namespace
+void setPassRerun(int on) { g_PassRerun = on; }
+
+void Engine::processBatch(const Frame *in, const Frame *out, int count) {
+	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("processBatch: bad arguments");
+	const std::vector<AnyFrame> anyIn = anyOf(in, count), anyOut = anyOf(out, count);
+	if (sourceStage()) return processFrames(anyIn.data(), anyOut.data(), count);  // (every frame checked before the first runs)
+	runPasses(anyIn.data(), anyOut.data(), count);
+}
+
+void Engine::processFrames(const AnyFrame *in, const AnyFrame *out, int count) {
+	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) {
+		throw std::invalid_argument("ju_process_frames: NULL frames or a negative count");
+	}
+	for (int i = 0; i < count; ++i) {
+		try {
+			checkFrame(in[i], true);  // (every pair, also those that take submit())
+			checkFrame(out[i], false);
+		} catch (const std::invalid_argument &e) {
+			throw std::invalid_argument("ju_process_frames: frame " + std::to_string(i) + ": " + e.what());
+		}
+	}
+	runPasses(in, out, count);
+}
+
+void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
+	DeviceGuard g(m_Device);
+	int i = 0;
+	while (i < count) {
+		// the longest run of frames from i that can go as one pass: none of them READING what an earlier frame of the
+		// pass writes (frame by frame such an input would be read after that write; the pass's flow sweep and its YUV
+		// decode read every input first)
+		// ... nor WRITING what an earlier frame of the pass reads: on the normal path that write comes after the read
+		// (frame k's tail after frame j's, j < k), but a pass whose resident tower timed out is run again frame by frame
+		// from its inputs, which must then still be what they were (advisor, round 5).  Every plane of a YUV frame counts.
+		FrameExtent reads[kFlowBatchMax], writes[kFlowBatchMax];
+		int n = 0;
+		while (i + n < count && n < m_BatchMax && passEligible(in[i + n], out[i + n])) {
+			reads[n] = extentOf(in[i + n]);
+			writes[n] = extentOf(out[i + n]);
+			bool clash = false;
+			for (int k = 0; k < n && !clash; ++k) clash = overlap(reads[n], writes[k]) || overlap(writes[n], reads[k]);
+			if (clash) break;
+			++n;
+		}
+		if (n < 2 || !batchPlanned(n)) {
+			runSynchronous(in[i], out[i]);
+			++i;
+			continue;
+		}
+		const int set = m_Idx;
+		submitBatch(in + i, out + i, n);
+		drainPassOutputs(out + i, n);  // host frames: each copied out while the next one runs
+		m_Stream.synchronizeSpin(m_SpinUs);
+		const unsigned code = takeResidentError();
+		if (code || g_PassRerun.load(std::memory_order_relaxed)) {
+			// nothing the pass wrote was one of its inputs -- neither the state (see above) nor a frame buffer (the pass
+			// splitter): the same frames again, one by one, on the per-block kernels
+			m_Idx = set;
+			m_BatchFrames -= static_cast<std::uint64_t>(n);
+			for (int k = 0; k < n; ++k) {
+				m_BatchHostFrames -= m_BatchHost[k].host() ? 1 : 0;
+				m_BatchYuvFrames -= m_BatchHost[k].yuv() ? 1 : 0;
+			}
+			if (code) fallbackToLayers(code);
+			for (int k = 0; k < n; ++k) {
+				if (code) {
+					submitAny(in[i + k], out[i + k]);
+					m_Stream.synchronize();
+				} else {  // (the debug switch: the pass was sound, the resident tower still runs and may report)
+					runSynchronous(in[i + k], out[i + k]);
+				}
+			}
+		} else {
+			for (int k = 0; k < n; ++k) maybeRestoreResident();
+		}
+		i += n;
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Group passes (processGroup).  A server of N live streams has N frames at every tick, one per stream, and their flow
+// nets are as independent as a look-ahead pass's: the flow net reads LR frames and each stream's own history only.  So
+// the lead (members[0]) runs the flow net's launches ONCE over the n frames of a pass, on its batch tensors -- item i is
+// member i's frame with member i's history (flow_block_kernel's independent-items form: m_GroupPrev / m_GroupOut) --
+// and then, member by member on the lead's stream, each member's own non-flow steps, bound to its frame, flow item i
+// and its state m_State[set_i] -> m_State[set_i ^ 1].  Per member that is the arithmetic of process(): the same kernels
+// add the same terms in the same order whatever the launch's size.  Like a look-ahead pass, the pass writes nothing it
+// reads (every member's state and history go to the other half of its ping-pong, the overlap test below keeps outputs
+// off inputs), so a pass whose resident tower timed out runs again member by member.  The launches are eager: round 6
+// measured eager launches per frame equal to graph replay.
+// ---------------------------------------------------------------------------------------------------------------
+bool Engine::sameModel(const Engine &o) const {
+	return m_Device == o.m_Device && m_ModelDigest == o.m_ModelDigest && m_DtypeOverride == o.m_DtypeOverride;
+}
+
+void Engine::processGroup(Engine *const *members, const Frame *bgrxIn, const Frame *bgrxOut, int count) {
+	if (count < 0 || (count > 0 && (members == nullptr || bgrxIn == nullptr || bgrxOut == nullptr))) {
+		throw std::invalid_argument("ju_process_group: NULL arguments or a negative count");
+	}
+	if (count == 0) return;
+	const std::vector<AnyFrame> in = anyOf(bgrxIn, count), out = anyOf(bgrxOut, count);
+	std::set<const Engine *> seen;
+	for (int i = 0; i < count; ++i) {
+		if (members[i] == nullptr) throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " is NULL");
+		if (!seen.insert(members[i]).second) {
+			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " appears twice");
+		}
+		if (!members[i]->sameModel(*members[0])) {
+			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) +
+			                            " does not match runtime 0 (device, model bytes or dtype)");
+		}
+		// what process() would refuse for its size, up front: a group call launches nothing before every frame passed
+		members[i]->checkFrame(in[i], true, "ju_process_group", true);
+		members[i]->checkFrame(out[i], false, "ju_process_group", true);
+	}
+	Engine &lead = *members[0];
+	DeviceGuard g(lead.m_Device);
+	auto alone = [&](int i) { members[i]->process(in[i], out[i]); };
+	if (count == 1) return alone(0);
+	// An output over an input of the call (same address space; any two members, also one member's own pair): member by
+	// member in list order, as ju_process calls would run -- a pass reads every input before any tail writes
+	bool clash = false;
+	for (int i = 0; i < count && !clash; ++i) {
+		const FrameExtent w = extentOf(out[i]);
+		for (int j = 0; j < count && !clash; ++j) clash = overlap(w, extentOf(in[j]));
+	}
+	std::vector<int> pass, rest;
+	for (int i = 0; i < count; ++i) (members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
+	const int cap = lead.m_BatchMax;
+	if (clash || pass.size() < 2 || cap < 2) {
+		for (int i = 0; i < count; ++i) alone(i);
+		return;
+	}
+	// consecutive passes of at most the lead's look-ahead cap; a pass of one member is a plain process()
+	for (std::size_t k = 0; k < pass.size(); k += static_cast<std::size_t>(cap)) {
+		const int n = static_cast<int>(std::min(pass.size() - k, static_cast<std::size_t>(cap)));
+		if (n < 2 || !lead.batchPlanned(n, true)) {
+			for (int j = 0; j < n; ++j) alone(pass[k + j]);
+			continue;
+		}
+		Engine *m[kFlowBatchMax];
+		AnyFrame fi[kFlowBatchMax], fo[kFlowBatchMax];
+		for (int j = 0; j < n; ++j) {
+			m[j] = members[pass[k + j]];
+			fi[j] = in[pass[k + j]];
+			fo[j] = out[pass[k + j]];
+		}
+		runGroupPass(lead, m, fi, fo, n);
+	}
+	// frames a pass cannot take (graphics resources, device frames off the kernels' alignment): on their own.  No
+	// buffer of the call overlaps another here, so the order changes no byte.
+	for (int i : rest) alone(i);
+}
+
+void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n) {
+	int sets[kFlowBatchMax];
+	for (int i = 0; i < n; ++i) sets[i] = m[i]->m_Idx;
+	L.bindBatch(in, out, n, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
+	L.uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
+	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
+	// 1. work a member has pending on its own stream (ju_enqueue) runs first
+	for (int i = 0; i < n; ++i) {
+		if (m[i] == &L) continue;
+		const hipError_t st = hipStreamQuery(m[i]->m_Stream);
+		if (st == hipSuccess) continue;  // (idle: everything it was given has completed)
+		if (st != hipErrorNotReady) JU_HIP(st);
+		m[i]->m_GroupEvent.record(m[i]->m_Stream);
+		JU_HIP(hipStreamWaitEvent(L.m_Stream, m[i]->m_GroupEvent.get(), 0));
+	}
+	const bool recurrent = L.m_Config.recurrent();
+	const long flowItem = recurrent ? static_cast<long>(L.m_Tensors.at("flow").count) * 2 : 0;
+	const unsigned char *flowBase = recurrent ? L.m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
+	{
+		// 5. the device chain, once for the whole pass (chainBegin / chainEnd, for a pass that may hold several
+		// members' resident towers): ordered after the frame submitted last by any other resident runtime, and any
+		// member's next frame is ordered after the pass (lastOwner = the lead)
+		bool resident = false;
+		for (int i = 0; i < n; ++i) resident = resident || m[i]->m_Resident;
+		std::unique_lock<std::mutex> chain = L.chainBegin(resident);
+		// 2. the flow net once over all items
+		for (int i = 0; i < n; ++i) {
+			L.m_GroupPrev[i] = m[i]->m_Packed[sets[i]].get();
+			L.m_GroupOut[i] = m[i]->m_Packed[sets[i] ^ 1].get();
+		}
+		for (const Step &st : L.m_BatchFlow.at({n, kGroupSet})) st.run(L.m_Stream);
+		// 3. member by member, its own steps on the lead's stream, bound to its frame and its flow item
+		for (int i = 0; i < n; ++i) {
+			Engine &e = *m[i];
+			const FrameIO keepIO = e.m_IO;
+			const void *keepFlow = e.m_FlowCur;
+			struct Restore {
+				Engine &e;
+				FrameIO io;
+				const void *flow;
+				~Restore() {
+					e.m_IO = io;
+					e.m_FlowCur = flow;
+				}
+			} restore{e, keepIO, keepFlow};
+			e.m_IO = L.m_BatchIO[i];
+			if (recurrent) e.m_FlowCur = flowBase + i * flowItem;
+			for (const Step &st : e.m_Program[sets[i]]) {
+				if (st.tag != "flow" && st.tag != "pack") st.run(L.m_Stream);
+			}
+			if (L.m_BatchHost[i].out.host) launchSignalHost(L.m_PassSignal.device(), L.m_Stream);
+		}
+		L.chainEnd(chain, resident);
+	}
+	// 4. every member's stream after the pass
+	L.m_GroupEvent.record(L.m_Stream);
+	for (int i = 0; i < n; ++i) {
+		if (m[i] != &L) JU_HIP(hipStreamWaitEvent(m[i]->m_Stream, L.m_GroupEvent.get(), 0));
+	}
+	L.drainPassOutputs(out, n);  // host frames: each copied out while the next member runs
+	L.m_Stream.synchronizeSpin(L.m_SpinUs);
+	// one synchronisation; then every member's resident-tower error word
+	unsigned codes[kFlowBatchMax];
+	bool failed = false;
+	for (int i = 0; i < n; ++i) {
+		codes[i] = m[i]->takeResidentError();
+		failed = failed || codes[i] != 0;
+	}
+	if (failed) {
+		// nothing the pass wrote is one of its inputs: the same frames again, member by member, each through its own
+		// process() -- a member whose tower timed out on its per-block kernels from now on
+		for (int i = 0; i < n; ++i) {
+			if (codes[i]) m[i]->fallbackToLayers(codes[i]);
+		}
+		for (int i = 0; i < n; ++i) m[i]->process(in[i], out[i]);
+		return;
+	}
+	for (int i = 0; i < n; ++i) {
+		m[i]->m_Idx = sets[i] ^ 1;
+		++m[i]->m_GroupFrames;
+		m[i]->maybeRestoreResident();
+	}
+}
+
+}  // namespace ju

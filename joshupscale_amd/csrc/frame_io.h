@@ -1,0 +1,114 @@
+// Frames at the engine's boundary and the host-side pieces every way in and out shares: the frame descriptors, the one
+// row copy, the planes of a YUV frame as the conversion kernels take them, and the scaler of the source and output
+// stages.  The arithmetic itself is frame_geometry.h.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "frame_geometry.h"
+#include "hip_util.h"
+#include "kernels.h"
+
+namespace ju {
+
+// Frame descriptor of the boundary (reference core/public/JoshUpscale/core.h:30-38):
+// 4 bytes per pixel B,G,R,X; `stride` in bytes, may be negative (bottom-up);
+// `ptr` addresses the first logical row.
+enum class Location : std::uint8_t { Host = 0, Device = 1, GraphicsResource = 2 };
+
+struct Frame {
+	void *ptr;
+	Location location;
+	std::ptrdiff_t stride;
+	std::size_t width;
+	std::size_t height;
+};
+
+// A frame of ju_process_frame that is not BGRX (include/joshupscale_amd.h, ju_frame): a format of the table in kernels.h
+// (PixelFormat: planes, words and sample kinds are described there), its planes each addressing their first logical row,
+// strides in bytes of any sign.  Host or device.  An RGB format has no colour space: `colorspace` is ignored.
+struct YuvFrame {
+	PixelFormat format;
+	int colorspace;  // 0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full
+	Location location;
+	std::size_t width;
+	std::size_t height;
+	void *planes[3];
+	std::ptrdiff_t strides[3];
+};
+
+// One side of a frame call: a BGRX frame (exactly as ju_process takes it) or a YUV one.
+struct AnyFrame {
+	bool yuv = false;
+	Frame bgrx{};
+	YuvFrame planes{};
+};
+
+inline AnyFrame anyOf(const Frame &f) {
+	AnyFrame a;
+	a.bgrx = f;
+	return a;
+}
+inline std::vector<AnyFrame> anyOf(const Frame *f, int n) {
+	std::vector<AnyFrame> a(static_cast<std::size_t>(n > 0 ? n : 0));
+	for (int i = 0; i < n; ++i) a[static_cast<std::size_t>(i)].bgrx = f[i];
+	return a;
+}
+inline Location locationOf(const AnyFrame &f) { return f.yuv ? f.planes.location : f.bgrx.location; }
+
+// The bytes a frame covers, every plane of it, in its address space.  A graphics resource covers none: its `ptr` is a
+// handle, not an address.
+inline FrameExtent extentOf(const AnyFrame &a) {
+	if (a.yuv) {
+		const YuvFrame &y = a.planes;
+		return frameExtent(formatInfo(y.format), y.width, y.height, y.planes, y.strides, static_cast<int>(y.location));
+	}
+	if (a.bgrx.location == Location::GraphicsResource) return FrameExtent{};
+	return imageExtent(a.bgrx.ptr, a.bgrx.stride, a.bgrx.width, a.bgrx.height, static_cast<int>(a.bgrx.location));
+}
+
+// THE row copy: `rows` rows of `rowBytes` from `src` to `dst` (each the row lowest in memory and the pitch between rows:
+// rowSpan), enqueued on `stream` -- one contiguous copy when both sides are dense, a 2-D copy otherwise.  Pageable host
+// memory goes through the HIP runtime's own bounce buffers (engine.h, "Host frames").
+void copyRows(void *dst, std::size_t dstPitch, const void *src, std::size_t srcPitch, std::size_t rowBytes, std::size_t rows,
+    hipMemcpyKind kind, hipStream_t stream);
+
+// The caller's device planes as a conversion kernel takes them
+YuvPlanes callerPlanes(const YuvFrame &f);
+// A host frame's planes in the device staging buffer `stage` (stagedLayout: plane after plane, rows padded, in the
+// caller's memory order)
+YuvPlanes stagedPlanes(const YuvFrame &f, std::uint8_t *stage);
+// The pageable copies between a host frame's planes and that staging layout, plane by plane on `stream`
+void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream_t stream);
+
+// The scaler of the source and the output stage (source_kernels.hip; docs/source_stage.md, docs/output_stage.md): both
+// axes' tables on the device -- one buffer per axis, the start indices, then the taps -- and what the launches need
+// beside them.  srcW x srcH -> dstW x dstH through one JU_SCALE_* filter.
+class Scaler {
+public:
+	// Allocates and uploads first and replaces the scaler's state last: a throw leaves it as it was.  (To replace a
+	// scaler whose tables enqueued launches may still read, build a new one, synchronise, then move it in.)
+	// std::invalid_argument: buildScaleAxis's, for an unknown filter or a ratio outside its bounds.
+	void build(std::size_t srcW, std::size_t srcH, std::size_t dstW, std::size_t dstH, int filter);
+	void clear() { *this = Scaler(); }
+	bool set() const { return m_SrcW != 0; }
+	std::size_t srcW() const { return m_SrcW; }
+	std::size_t srcH() const { return m_SrcH; }
+	std::size_t dstW() const { return m_DstW; }
+	std::size_t dstH() const { return m_DstH; }
+	int filter() const { return m_Filter; }  // (JU_SCALE_*; 0 while not set)
+	// launchScaleBgrx / launchScaleState (kernels.h) with the scaler's sizes and tables
+	void scaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint8_t *dst, std::ptrdiff_t dstStride,
+	    hipStream_t stream) const;
+	void scaleState(const void *state, std::uint16_t *dst, hipStream_t stream) const;
+
+private:
+	DeviceBuffer m_X, m_Y;
+	ScaleAxisDev m_XDev, m_YDev;
+	int m_Span = 0, m_Filter = 0;
+	std::size_t m_SrcW = 0, m_SrcH = 0, m_DstW = 0, m_DstH = 0;
+};
+
+}  // namespace ju

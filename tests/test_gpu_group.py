@@ -1,4 +1,4 @@
-"""Group passes (ju_process_group; engine.cpp "Group passes") -- needs an MI355X.
+"""Group passes (ju_process_group; engine_passes.cpp "Group passes") -- needs an MI355X.
 
 One frame for each of several runtimes in one call: the lead runs the flow net once over every member's frame, each
 with its own runtime's history, then every member's warp, tower and tail.  The contract is byte equality with
@@ -371,8 +371,8 @@ def test_temporal_filter_and_flow_free_models_ride_in_the_passes(variant):
 
 
 def test_refused_calls_change_nothing():
-    """NULL arguments, a runtime twice, members of other weights or another dtype, one wrong-sized frame: each
-    JU_ERR_INVALID_ARGUMENT, and every member's next frame still equals its twin's."""
+    """NULL arguments, a runtime twice, members of other weights or another dtype, one wrong-sized frame (also a
+    graphics resource of a wrong declared width): each JU_ERR_INVALID_ARGUMENT, and every member's next frame still equals its twin's."""
     torch, dev = _torch()
     cfg = small_config()
     h, w = cfg.frame_height, cfg.frame_width
@@ -420,6 +420,15 @@ def test_refused_calls_change_nothing():
         unknown = [f.img_in(rt, d_in[3]) for rt in m]
         unknown[1].location = 7
         assert call(m, ins=unknown) == JU_ERR_INVALID_ARGUMENT
+        # a texture whose DECLARED width is wrong, among members whose frames are fine: refused before any member runs
+        assert lib.ju_debug_fake_gl_texture(31, small.data_ptr(), (w - 2) * 4, w - 2, h, 4) == 0
+        try:
+            bad_gl = R.gl_image(31, output=False)
+            assert (bad_gl.location, bad_gl.width) == (R.LOC_GRAPHICS_RESOURCE, w - 2)
+            assert call(m, ins=[f.img_in(m[0], d_in[3]), bad_gl, f.img_in(m[2], d_in[3])]) == JU_ERR_INVALID_ARGUMENT
+            R.release_gl_image(bad_gl)
+        finally:
+            lib.ju_debug_fake_gl_texture(0, None, 0, 0, 0, 0)
         with pytest.raises(R.JoshUpscaleError):
             R.process_group([m[0], stranger], [f.img_in(m[0], d_in[1]), f.img_in(stranger, d_in[1])],
                             [f.img_out(m[0], f.out[0]), f.img_out(stranger, f.out[1])])

@@ -1,4 +1,4 @@
-"""Frame look-ahead (ju_process_batch; engine.cpp "Frame look-ahead") -- needs an MI355X.
+"""Frame look-ahead (ju_process_batch; engine_passes.cpp "Frame look-ahead") -- needs an MI355X.
 
 The flow net reads LR frames only (reference models.py:790, 823: its input is the current frame and the history of the last
 num_flow_inputs frames), so the flow fields of several consecutive frames are computed in one pass of the flow net's

@@ -1,5 +1,5 @@
 """The output stage on the GPU (csrc/source_kernels.hip scale_state_kernel, csrc/colour_kernels.hip Bgrx16Source,
-engine.cpp "Output stage"; docs/output_stage.md): the 16-bit scaler and the encode from a 16-bit frame alone against the
+engine_frames.cpp "Output stage"; docs/output_stage.md): the 16-bit scaler and the encode from a 16-bit frame alone against the
 numpy definition (tests/output_reference.py), byte for byte; a runtime with an output size set against a twin whose
 frame and state are scaled and encoded in numpy; with a source size and a mask; models whose deep outputs come from the
 8-bit frame; every entry point; turning it off; the refused calls."""

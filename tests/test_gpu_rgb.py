@@ -1,5 +1,5 @@
 """RGB frame formats on the GPU (BGR24, RGB24, RGBX, BGRX64, RGBP8 / 10 / 16 / H / S, BGR96F; csrc/colour_kernels.hip,
-engine.cpp): the conversion kernels alone against the numpy definition (tests/rgb_reference.py), bit for bit; inputs
+engine_frames.cpp): the conversion kernels alone against the numpy definition (tests/rgb_reference.py), bit for bit; inputs
 against a twin fed the decoded frame; outputs against the definition applied to the twin's frame or to the runtime's own
 f16 state; look-ahead passes against a twin driven frame by frame; the source stage; the refused calls."""
 

@@ -1,4 +1,4 @@
-"""The source stage on the GPU (csrc/source_kernels.hip, engine.cpp "Source stage"; docs/source_stage.md): the scale and
+"""The source stage on the GPU (csrc/source_kernels.hip, engine_frames.cpp "Source stage"; docs/source_stage.md): the scale and
 the blend kernel alone against the numpy definition (tests/source_reference.py), byte for byte; a runtime with a source
 size set against a twin fed scale(decode(source)) computed in numpy; the mask against the numpy blend of the twin's
 outputs, and the state against the unmasked twin's; every entry point; turning the settings off; the refused calls."""

@@ -1,4 +1,4 @@
-"""10-bit 4:2:0 frame I/O on the GPU (P010 / I010; csrc/colour_kernels.hip, engine.cpp): the three conversion kernels
+"""10-bit 4:2:0 frame I/O on the GPU (P010 / I010; csrc/colour_kernels.hip, engine_frames.cpp): the three conversion kernels
 alone against the numpy definition (tests/yuv10_reference.py), byte for byte; 10-bit inputs against a twin fed the
 decoded frame; 10-bit outputs against the definition applied to the runtime's own f16 state (or, for the models whose
 state is not the frame, to the twin's 8-bit frame); every format pair, location and call; look-ahead passes against a

@@ -1,4 +1,4 @@
-"""NV12 / I420 frames in look-ahead passes (ju_process_frames; engine.cpp "YUV frames in look-ahead passes") -- needs an
+"""NV12 / I420 frames in look-ahead passes (ju_process_frames; engine_passes.cpp "YUV frames in look-ahead passes") -- needs an
 MI355X.
 
 The contract is byte equality with ju_process_frame called frame by frame: the expected bytes of every test come from

@@ -1,4 +1,4 @@
-"""4:2:2 and 4:4:4 frame I/O on the GPU (YUY2, UYVY, I422, P210, I210, I444, I410; csrc/colour_kernels.hip, engine.cpp):
+"""4:2:2 and 4:4:4 frame I/O on the GPU (YUY2, UYVY, I422, P210, I210, I444, I410; csrc/colour_kernels.hip, engine_frames.cpp):
 the conversion kernels alone against the numpy definition (tests/yuv_sampled_reference.py), byte for byte; inputs
 against a twin fed the decoded frame; outputs against the definition applied to the twin's frame or to the runtime's own
 f16 state; formats, locations and layouts on both sides; look-ahead passes against a twin driven frame by frame; the
