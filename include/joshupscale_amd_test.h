@@ -43,6 +43,19 @@ JU_API int ju_read_tensor(ju_runtime *runtime, const char *name, float *dst, siz
 JU_API int ju_time_steps(ju_runtime *runtime, const char *tag, int iters, double *ms_per_launch,
     int *launches, double *flops);
 
+/* The launch plans this runtime's launchers of the flow net's convolution kernels (and of the residual blocks outside
+ * the resident tower) have really used since it was created: text, one line per distinct launch in first-launch order,
+ * '\n' after each, NUL-terminated.  *length receives the length without the NUL; dst may be NULL to query it.  A launcher
+ * ignores a forced value (JU_FLOW_TILE, JU_SPLITK_PLAN, JU_CONV_TILE, JU_CONV_DBUF, JU_RES_BLOCK) the
+ * shape does not have: what ran is what stands here.  Lines, every value a decimal number:
+ *   flow_block cin= cmid= ups= pool= outk= pack= indep= H= W= items= rows= heights=<a,b,..>
+ *       (outk 1 the f16 flow head, 2 the residual form; items: frames of the launch; rows: the tile height launched;
+ *        heights: every height this block shape has, i.e. that fits LDS)
+ *   conv_splitk cin= cout= pool= H= W= items= rows= blocks=      (blocks: cout blocks per workgroup)
+ *   conv_mfma taps= ck= cin= cout= ups= pool= H= W= items= nb= rw= stages=
+ *   res_block H= W=  /  res_block_pipe H= W= */
+JU_API int ju_plan_report(ju_runtime *runtime, char *dst, size_t capacity, size_t *length);
+
 /* Developer switches (timing ablations and fault injection; never needed by a
  * caller).  Keys: "tower_variant" (0 = product kernel, 4 = phase profile, 5 = per-layer
  * output maxima for quantisation calibration, 8 = the resident tower's plain schedule:

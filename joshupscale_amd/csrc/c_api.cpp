@@ -8,6 +8,7 @@
 #endif
 
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <ios>
 #include <new>
@@ -381,6 +382,16 @@ int ju_read_tensor(ju_runtime *runtime, const char *name, float *dst, size_t cap
 		if (name == nullptr) throw std::invalid_argument("name is NULL");
 		const std::size_t n = engineOf(runtime).readTensor(name, dst, capacity);
 		if (count) *count = n;
+	});
+}
+
+int ju_plan_report(ju_runtime *runtime, char *dst, size_t capacity, size_t *length) {
+	return guarded([&] {
+		const std::string text = engineOf(runtime).planReport();
+		if (length) *length = text.size();
+		if (dst == nullptr) return;
+		if (capacity < text.size() + 1) throw std::invalid_argument("ju_plan_report: buffer too small");
+		std::memcpy(dst, text.c_str(), text.size() + 1);
 	});
 }
 

@@ -550,9 +550,9 @@ void launchConvT(const ConvParams &p, hipStream_t stream) {
 	// (the coarsest flow levels): double-buffered staging, the only way such a
 	// workgroup overlaps its loads with its MFMAs.  Larger launches keep the
 	// single-stage kernel: two co-resident workgroups hide each other's latency and
-	// the doubled LDS would cost a second round of workgroups.  (JU_CONV_DBUF=0/1
-	// forces it off/on for A/B timing.)
-	static const char *dbufEnv = devSwitch(Dev::ConvDbuf);
+	// the doubled LDS would cost a second round of workgroups.  (JU_CONV_DBUF=0/1/2
+	// forces the depth for A/B timing and for tests/test_gpu_launch_plans.py: read where
+	// the runtime is constructed, it arrives as ConvParams::plan.)
 	const int cus = currentDeviceCUs();
 	// (a look-ahead launch covers `items` frames: that many times the workgroups, as fbLaunchCost and the split-K rule count)
 	const long wgs = (long)((p.W + kTW - 1) / kTW) * ((p.H + 4 * p.rw - 1) / (4 * p.rw)) *
@@ -562,8 +562,15 @@ void launchConvT(const ConvParams &p, hipStream_t stream) {
 	// per CU anyway, one stage (and a second barrier) when two can be co-resident.
 	const bool multi = ck == 64 && p.cin > 64 && p.nb == 1 && p.taps == 9;
 	int stages = multi ? (wgs <= cus ? 2 : 1) : 0;
-	if (dbufEnv && multi) stages = dbufEnv[0] - '0';  // A/B: 0 = plain staging, 1, 2
+	if (p.plan && p.plan->convStages >= 0 && p.plan->convStages <= 2 && multi) stages = p.plan->convStages;  // 0 = plain staging, 1, 2
 	const bool dbuf = stages > 0;
+	if (p.plan && p.plan->log) {
+		p.plan->log->note("conv_mfma taps=" + std::to_string(p.taps) + " ck=" + std::to_string(ck) + " cin=" + std::to_string(p.cin) +
+		                  " cout=" + std::to_string(p.cout) + " ups=" + std::to_string(p.upsample != 0) + " pool=" +
+		                  std::to_string(p.pool != 0) + " H=" + std::to_string(p.H) + " W=" + std::to_string(p.W) + " items=" +
+		                  std::to_string(p.items > 1 ? p.items : 1) + " nb=" + std::to_string(p.nb) + " rw=" + std::to_string(p.rw) +
+		                  " stages=" + std::to_string(p.upsample ? 0 : stages));
+	}
 	if (p.upsample) {
 		if (p.taps != 9 || ck != 64 || p.nb != 1 || p.H % 2 || p.W % 2 || p.pool) {
 			throw std::invalid_argument("conv: fused upsampling needs 3x3, cin % 64 == 0, nb = 1, even H and W");

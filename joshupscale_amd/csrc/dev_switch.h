@@ -35,10 +35,14 @@ enum class Dev : int {
 	TowerFast,    // JU_TOWER_FAST=0            the resident tower's general schedule
 	Fp8Grid,      // JU_FP8_GRID=<n>            grid of the per-conv 8-bit kernel
 	Fp8Block,     // JU_FP8_BLOCK=solo|duo      form of res_block_fp8_kernel
+	SplitKPlan,   // JU_SPLITK_PLAN=<rows>[x<cb>]  forced conv_splitk_kernel tile height / cout blocks per workgroup
+	ConvTile,     // JU_CONV_TILE=<nb>x<rw>     forced conv_mfma_kernel tile form where convTiling chooses it
 	Count
 };
 
 // The switch's value in the process environment -- in the test flavour; nullptr, always, in the product library.
 const char *devSwitch(Dev which);
+// true in the test flavour: a runtime then keeps its launch plan report (kernels.h PlanLog)
+bool devSwitchesExist();
 
 }  // namespace ju

@@ -119,7 +119,7 @@ void Engine::planFlowUnits() {
 		FlowUnit &u = m_FlowUnits[i];
 		const bool even = h % 2 == 0 && w % 2 == 0;
 		if ((!pool || (m_FusedPool && even)) && (!prevUps || even)) {
-			if (prevUps && flowBlockSupported(padTo16(cin), f, true, pool, false, h, w)) {
+			if (prevUps && m_FusedUpsample && flowBlockSupported(padTo16(cin), f, true, pool, false, h, w)) {
 				u.fused = u.upsIn = true;
 			} else if (flowBlockSupported(padTo16(cin), f, false, pool, false, h, w)) {
 				u.fused = true;
@@ -141,7 +141,7 @@ void Engine::planFlowUnits() {
 		FlowUnit &u = m_FlowUnits[2 * nb];
 		const bool even = h % 2 == 0 && w % 2 == 0;
 		if (f == 32) {
-			if (prevUps && even && flowBlockSupported(padTo16(cin), f, true, false, true)) {
+			if (prevUps && even && m_FusedUpsample && flowBlockSupported(padTo16(cin), f, true, false, true)) {
 				u.fused = u.upsIn = true;
 			} else if (flowBlockSupported(padTo16(cin), f, false, false, true)) {
 				u.fused = true;
@@ -182,6 +182,13 @@ Engine::ConvWeights &Engine::addConv(const std::string &name, const FoldedConv &
 		cw.splitK = true;
 	} else {
 		convTiling(H, W, f.cout, &cw.nb, &cw.rw);
+		// JU_CONV_TILE (developer switch): another of the kernel's tile forms where the layer has it -- here, so that the
+		// weights are packed for the same nb (a pooled / upsampling layer still gets the rw it needs: addConvStep)
+		if ((m_Plan.convNb == 1 || m_Plan.convNb == 2) && (m_Plan.convRw == 1 || m_Plan.convRw == 2) &&
+		    f.cout % (32 * m_Plan.convNb) == 0) {
+			cw.nb = m_Plan.convNb;
+			cw.rw = m_Plan.convRw;
+		}
 	}
 	const auto packed = packConvWeights(f, cinMap, cw.nb, m_DType);
 	cw.w = DeviceBuffer(packed.size() * 2);
@@ -288,6 +295,7 @@ void Engine::addConvStep(std::vector<Step> *prog, const std::string &tag,
 		p.pool = 1;
 		p.rw = 2;
 	}
+	p.plan = &m_Plan;
 	p.upsample = upsample ? 1 : 0;
 	if (upsample) {
 		// + the low-resolution patch: with rw = 2 the workgroup needs 96 KB of LDS and
@@ -386,6 +394,7 @@ void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, 
 		fb.act1 = flowAct;
 		fb.act2 = act2;
 		fb.slope = c.flowNegativeSlope;
+		fb.plan = &m_Plan;
 		fb.items = items;
 		fb.inItemBytes = inItem;
 		fb.outItemBytes = itemBytes(outName);
@@ -606,6 +615,7 @@ void Engine::buildProgram(int set) {
 		fb.W = bw;
 		fb.cin = fb.cmid = 64;
 		fb.residual = true;
+		fb.plan = &m_Plan;
 		fb.act1 = fb.act2 = act;
 		fb.slope = slope;
 		prog.push_back({tag, 2.0 * bh * bw * 9.0 * 64 * 64 * 2,
@@ -983,7 +993,23 @@ Engine::Engine(int device, const void *blob, std::size_t size, int dtypeOverride
 	const char *upMode = devSwitch(Dev::Upsample);
 	m_FusedUpsample = !(upMode && std::string(upMode) == "split");
 	const char *flowConv = devSwitch(Dev::FlowConv);
-	m_FlowFused = !(flowConv && std::string(flowConv) == "generic") && m_FusedUpsample;
+	// (JU_UPSAMPLE=split keeps the one-launch blocks: the decoder's take their non-upsampling form behind an
+	// upsample2_kernel launch -- planFlowUnits)
+	m_FlowFused = !(flowConv && std::string(flowConv) == "generic");
+	// The launch plan switches (kernels.h DevPlan), read HERE and nowhere else: the launch descriptors carry them, so two
+	// runtimes of one process can run different plans.  devSwitch() is null for every one of them in the product library.
+	if (const char *e = devSwitch(Dev::FlowTile)) m_Plan.flowTile = std::atoi(e);
+	if (const char *e = devSwitch(Dev::ResBlock)) m_Plan.resBlock = std::string(e) == "plain" ? 1 : (std::string(e) == "tile" ? 2 : 0);
+	if (const char *e = devSwitch(Dev::ConvDbuf)) m_Plan.convStages = (e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1;
+	if (const char *e = devSwitch(Dev::SplitKPlan)) {  // <rows>[x<blocks>]
+		m_Plan.splitkRows = std::atoi(e);
+		if (const char *x = std::strchr(e, 'x')) m_Plan.splitkBlocks = std::atoi(x + 1);
+	}
+	if (const char *e = devSwitch(Dev::ConvTile)) {  // <nb>x<rw>
+		m_Plan.convNb = std::atoi(e);
+		if (const char *x = std::strchr(e, 'x')) m_Plan.convRw = std::atoi(x + 1);
+	}
+	if (devSwitchesExist()) m_Plan.log = &m_PlanLog;
 	planFlowUnits();
 
 	buildWeights(model);

@@ -130,6 +130,10 @@ public:
 	// "graph_replays", "eager_runs", "direct_graphs", "resident_tower", "resident_flow",
 	// "launches_per_frame"
 	double stat(const std::string &key) const;
+	// Test flavour only: what the launchers of the flow net's convolution kernels (and the residual-block launcher)
+	// really launched for this runtime so far, one line per distinct launch (kernels.h PlanLog; the lines:
+	// include/joshupscale_amd_test.h ju_plan_report).  Empty in the product library.
+	std::string planReport() const { return m_PlanLog.text(); }
 
 private:
 	struct Tensor {
@@ -294,6 +298,10 @@ private:
 	};
 	std::vector<FlowUnit> m_FlowUnits;
 	bool m_FlowFused = true;
+	// developer launch plan (kernels.h): the plan switches as read by the constructor, carried by every launch
+	// descriptor of this runtime; all defaults, and no log, in the product library
+	DevPlan m_Plan;
+	PlanLog m_PlanLog;
 	// residual blocks outside the resident tower (more regions than CUs, LeakyReLU models,
 	// after a fallback): one launch per BLOCK (flow_block_kernel, intermediate tensor in LDS);
 	// JU_TOWER=convs keeps one launch per convolution

@@ -630,7 +630,8 @@ void launchFlowBlockInst(const FlowBlockParams &p, int items, hipStream_t stream
 // between the height that makes the LAST round full -- 640 x 448: 22 x 25 tiles of 18 rows are three rounds on 256 CUs,
 // 22 x 23 of 20 rows are two (measured: profiles/r04_flow_tile_heights.txt).  The bytes do not depend on the choice: an
 // output pixel's terms are added in the same order whatever tile it falls into.  JU_FLOW_TILE=<rows> forces a height
-// (developer switch, for that measurement).
+// (developer switch, for that measurement and for tests/test_gpu_launch_plans.py: read where the runtime is constructed,
+// it arrives as FlowBlockLaunch::plan).
 constexpr int kFbMid = 14;
 constexpr int kFbFixedRows = 8;  // the fixed part of a tile in units of one row's work (fitted to the measurement above)
 
@@ -639,25 +640,35 @@ inline long fbLaunchCost(int H, long tilesX, int TH, int numCUs, int items = 1) 
 	return (tiles + numCUs - 1) / numCUs * (TH + kFbFixedRows);
 }
 
-inline int fbForcedTile() {
-	static const int forced = [] { const char *e = devSwitch(Dev::FlowTile); return e ? std::atoi(e) : 0; }();
-	return forced;
+// the plan report's line of a block launch (kernels.h PlanLog): the instantiation, the launch and the heights the shape has
+void fbNotePlan(const DevPlan *plan, int cin, int cmid, bool ups, bool pool, int outk, bool pack, bool indep, int H, int W,
+    int items, int rows, const int *heights, int nHeights) {
+	std::string line = "flow_block cin=" + std::to_string(cin) + " cmid=" + std::to_string(cmid) + " ups=" + std::to_string(ups) +
+	                   " pool=" + std::to_string(pool) + " outk=" + std::to_string(outk) + " pack=" + std::to_string(pack) +
+	                   " indep=" + std::to_string(indep) + " H=" + std::to_string(H) + " W=" + std::to_string(W) +
+	                   " items=" + std::to_string(items) + " rows=" + std::to_string(rows) + " heights=";
+	for (int i = 0; i < nHeights; ++i) line += (i ? "," : "") + std::to_string(heights[i]);
+	plan->log->note(line);
 }
 
 template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK, bool INDEP, int... THS>
-void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, hipStream_t stream) {
+void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, const DevPlan *plan, hipStream_t stream) {
 	const long tilesX = (p.W + kFbOutW - 1) / kFbOutW;
+	const int forced = plan ? plan->flowTile : 0;
 	int best = 0;
 	long bestCost = 0;
+	int heights[sizeof...(THS)], nHeights = 0;  // (the plan report: the heights this shape has)
 	auto consider = [&](int TH, bool fits) {
 		if (!fits) return;
-		const long c = fbForcedTile() == TH ? -1 : fbLaunchCost(p.H, tilesX, TH, numCUs, items);
+		heights[nHeights++] = TH;
+		const long c = forced == TH ? -1 : fbLaunchCost(p.H, tilesX, TH, numCUs, items);
 		if (best == 0 || c < bestCost) {
 			best = TH;
 			bestCost = c;
 		}
 	};
 	(consider(THS, FbGeom<CIN, CMID, THS, UPS, POOL, OUTK, fbWaves<CIN, CMID>()>::FITS), ...);
+	if (plan && plan->log) fbNotePlan(plan, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, p.H, p.W, items, best, heights, nHeights);
 	bool done = false;
 	auto launch = [&](auto thTag) {
 		constexpr int TH = decltype(thTag)::value;
@@ -673,19 +684,19 @@ void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, hipStr
 }
 
 template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK = false, bool INDEP = false>
-void launchFlowBlockT(const FlowBlockParams &p, int items, int numCUs, hipStream_t stream) {
+void launchFlowBlockT(const FlowBlockParams &p, int items, int numCUs, const DevPlan *plan, hipStream_t stream) {
 	if constexpr (OUTK == 2) {
 		// (64 -> 64 -> 64 residual block, JU_RES_BLOCK=tile only: two 128-byte tiles; 14 rows is what fits)
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, kFbMid, 6>(p, items, numCUs, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, kFbMid, 6>(p, items, numCUs, plan, stream);
 	} else if constexpr (CMID == 128) {
 		// (the 128-filter blocks, 68 x 120 at 480 x 270: a few thousand pixels -- short tiles, or most of the chip idles;
 		// measured for the encoder / decoder block: 2 rows 11.7 / 23.8 us, 4 rows 16.0 / 32.1, 6 rows 19.9 / 39.1.  One
 		// frame is a single round of 2-row tiles; a look-ahead launch of 8 frames is five such rounds or two of 6-row
 		// tiles -- the cost rule above picks.  The decoder block's taller tiles keep two of its four input planes in LDS
 		// at a time: FbGeom::XPAIR.)
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 6, 4, 2>(p, items, numCUs, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 6, 4, 2>(p, items, numCUs, plan, stream);
 	} else {
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 20, 18, 10, 6>(p, items, numCUs, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 20, 18, 10, 6>(p, items, numCUs, plan, stream);
 	}
 }
 
@@ -740,8 +751,8 @@ void launchFlowBlockDT(const FlowBlockLaunch &q, hipStream_t stream) {
 		        (q.packPrev || q.independentItems))) {
 			throw std::invalid_argument("flow block: input packing is built for the first block (16 -> 32 -> 32, pool)");
 		}
-		if (q.independentItems) return launchFlowBlockT<T, 16, 32, false, true, 0, true, true>(p, items, cus, stream);
-		return launchFlowBlockT<T, 16, 32, false, true, 0, true>(p, items, cus, stream);
+		if (q.independentItems) return launchFlowBlockT<T, 16, 32, false, true, 0, true, true>(p, items, cus, q.plan, stream);
+		return launchFlowBlockT<T, 16, 32, false, true, 0, true>(p, items, cus, q.plan, stream);
 	}
 	if (q.upsample && (q.H % 2 || q.W % 2)) throw std::invalid_argument("flow block: fused upsampling needs even H and W");
 	if (q.pool && (q.H % 2 || q.W % 2)) throw std::invalid_argument("flow block: fused max-pool needs even H and W");
@@ -749,7 +760,7 @@ void launchFlowBlockDT(const FlowBlockLaunch &q, hipStream_t stream) {
 	const int outk = q.residual ? 2 : (q.outHead ? 1 : 0);
 #define JU_FB_CASE(CIN_, CMID_, UPS_, POOL_, OUTK_)                                              \
 	if (q.cin == CIN_ && q.cmid == CMID_ && q.upsample == UPS_ && q.pool == POOL_ && outk == OUTK_) { \
-		return launchFlowBlockT<T, CIN_, CMID_, UPS_, POOL_, OUTK_>(p, items, cus, stream);         \
+		return launchFlowBlockT<T, CIN_, CMID_, UPS_, POOL_, OUTK_>(p, items, cus, q.plan, stream); \
 	}
 	JU_FB_CASE(16, 32, false, true, 0)   // encoder block 1: 12(16) -> 32 -> 32, pool
 	JU_FB_CASE(32, 64, false, true, 0)   // encoder block 2: 32 -> 64 -> 64, pool
@@ -795,8 +806,8 @@ bool flowBlockSupported(int cin, int cmid, bool upsample, bool pool, bool outHea
 
 void launchFlowBlock(DType dt, const FlowBlockLaunch &q, hipStream_t stream) {
 	if (q.residual && q.cin == 64 && q.cmid == 64 && !q.upsample && !q.pool) {
-		static const char *mode = devSwitch(Dev::ResBlock);  // "tile": the non-persistent flow_block_kernel form (A/B)
-		if (!(mode && std::string(mode) == "tile")) {
+		// JU_RES_BLOCK=tile (the runtime's plan): the non-persistent flow_block_kernel form (A/B)
+		if (!(q.plan && q.plan->resBlock == 2)) {
 			launchResBlockPersistent(dt, q, stream);  // res_block_kernels.hip
 			return;
 		}

@@ -11,6 +11,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -20,6 +21,47 @@ namespace ju {
 enum DType : int { kF16 = 0, kBF16 = 1 };
 
 inline std::size_t dtypeSize(DType) { return 2; }
+
+// ---- developer launch plans (test flavour of the library only: dev_switch.h) ------------------
+// The launchers of the flow net's convolution kernels choose a launch plan -- tile height, cout blocks per workgroup,
+// staging depth -- from the tensor's size and the CU count; none of the choices changes a byte
+// (tests/test_gpu_launch_plans.py holds every plan to the default's bytes).  A runtime of the test flavour reads the
+// switches that force a plan ONCE, where it is constructed (Engine::Engine), into its DevPlan; the launch descriptors
+// below carry a pointer to it, so that two runtimes of one process can differ and no launch looks at the environment.
+// In the product library every descriptor's `plan` is null.
+// PlanLog: what the launchers of ONE runtime really launched -- a forced value that does not fit the shape is ignored by
+// its launcher, and a test reads from here that the plan it asked for ran.  One line per distinct launch, in first-launch
+// order (ju_plan_report, include/joshupscale_amd_test.h, documents the lines).
+class PlanLog {
+public:
+	void note(const std::string &line) {
+		std::lock_guard<std::mutex> lock(m_Mutex);
+		for (const std::string &l : m_Lines) {
+			if (l == line) return;
+		}
+		m_Lines.push_back(line);
+	}
+	std::string text() const {
+		std::lock_guard<std::mutex> lock(m_Mutex);
+		std::string out;
+		for (const std::string &l : m_Lines) out += l + "\n";
+		return out;
+	}
+
+private:
+	mutable std::mutex m_Mutex;
+	std::vector<std::string> m_Lines;
+};
+struct DevPlan {
+	int flowTile = 0;     // JU_FLOW_TILE=<rows>: flow_block_kernel's tile height where the shape has it (0: the cost rule)
+	int resBlock = 0;     // JU_RES_BLOCK: 0 res_block_pipe_kernel, 1 "plain" res_block_kernel, 2 "tile" flow_block_kernel
+	int convStages = -1;  // JU_CONV_DBUF=0|1|2: conv_mfma_kernel's staging depth on multi-chunk layers (-1: by launch size)
+	int splitkRows = 0;   // JU_SPLITK_PLAN=<rows>[x<blocks>]: conv_splitk_kernel's tile height (even, 2 .. 34; 0: the rule) ...
+	int splitkBlocks = 0; // ... and its cout blocks per workgroup (1 or 2; 2 only where the launcher's own rule may take it)
+	int convNb = 0;       // JU_CONV_TILE=<nb>x<rw>: conv_mfma_kernel's tile form where convTiling is consulted (0: its choice)
+	int convRw = 0;
+	PlanLog *log = nullptr;
+};
 
 // ---- implicit-GEMM convolution on MFMA -----------------------------------
 // in   : NHWC [H][W][cin]   16-bit, cin a multiple of 16
@@ -61,6 +103,8 @@ struct ConvParams {
 	// operand then) and launchConvSplitK; the flow block launcher has its own item fields (FlowBlockLaunch).
 	int items;
 	long inItemBytes, outItemBytes;
+	// developer launch plan of the runtime (host side only; null: none -- always in the product library)
+	const DevPlan *plan;
 };
 
 // Zero-bordered activation layout of the generator trunk ("tower layout"):
@@ -173,6 +217,7 @@ struct FlowBlockLaunch {
 	bool independentItems;
 	const void *packPrevs[kFlowBatchMax];
 	void *packOuts[kFlowBatchMax];
+	const DevPlan *plan;  // developer launch plan of the runtime (null: none -- always in the product library)
 };
 // H x W: the block's resolution (the 128-filter blocks run as one launch only where their 2-row tiles are ONE round of the
 // chip: flow_kernels.hip); 0 = shape only

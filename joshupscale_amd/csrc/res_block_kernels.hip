@@ -801,8 +801,9 @@ __global__ __launch_bounds__(256, 1) void res_block_pipe_kernel(ResBlockParams p
 #endif
 }
 
-// JU_RES_BLOCK=plain (or the tests' switch): res_block_kernel for every block
-static std::atomic<int> g_ResBlockPlain{[] { const char *e = devSwitch(Dev::ResBlock); return (e != nullptr && std::string(e) == "plain") ? 1 : 0; }()};
+// the tests' process-wide switch (ju_debug_set "res_block_plain"): res_block_kernel for every block of every runtime.
+// JU_RES_BLOCK=plain asks the same of ONE runtime: read where it is constructed, it arrives as FlowBlockLaunch::plan.
+static std::atomic<int> g_ResBlockPlain{0};
 }  // namespace
 void setResBlockPlain(int on) { g_ResBlockPlain = on ? 1 : 0; }
 bool resBlockPlain() { return g_ResBlockPlain.load() != 0; }
@@ -815,13 +816,17 @@ void launchResBlockT(const FlowBlockLaunch &q, hipStream_t stream) {
 	const int inPitch = q.inPitch ? q.inPitch : q.W, outPitch = q.outPitch ? q.outPitch : q.W;
 	const unsigned long long inBytes = 128ull * q.H * inPitch, outBytes = 128ull * q.H * outPitch;
 	// (tensors of 4 GiB and more: the plain kernel, which addresses with 64-bit pointers)
-	const bool pipe = !resBlockPlain() && q.act1 == 1 && q.act2 == 1 && ablationSkipBits() == 0 &&  // (ReLU blocks)
+	const bool plain = resBlockPlain() || (q.plan && q.plan->resBlock == 1);
+	const bool pipe = !plain && q.act1 == 1 && q.act2 == 1 && ablationSkipBits() == 0 &&  // (ReLU blocks)
 	                  inBytes <= kRpMaxTensorBytes && outBytes <= kRpMaxTensorBytes;
 	auto kern = pipe ? res_block_pipe_kernel<T> : res_block_kernel<T>;
 	const int ldsBytes = pipe ? kRpLds : kRbLds;
 	static std::atomic<std::uint64_t> ldsDone{0}, ldsDonePipe{0};
 	ensureDynamicLds(reinterpret_cast<const void *>(kern), ldsBytes, pipe ? &ldsDonePipe : &ldsDone, "res block");
 	const int cus = currentDeviceCUs();
+	if (q.plan && q.plan->log) {
+		q.plan->log->note(std::string(pipe ? "res_block_pipe" : "res_block") + " H=" + std::to_string(q.H) + " W=" + std::to_string(q.W));
+	}
 	ResBlockParams p{};
 	p.in = q.in;
 	p.out = q.out;

@@ -320,6 +320,18 @@ void launchConvSplitK(DType dt, const ConvParams &q, const void *zeros, hipStrea
 		}
 		if (th > 16) th = 16;
 	}
+	// JU_SPLITK_PLAN (developer switch, the runtime's plan): a forced height, and forced cout blocks where this shape has
+	// the two-block form.  The kernel takes any even height (a tile taller than the image is a partial tile) and adds an
+	// output's terms in the same order under every plan: tests/test_gpu_launch_plans.py.
+	if (q.plan && q.plan->splitkRows >= 2 && q.plan->splitkRows <= 34 && q.plan->splitkRows % 2 == 0) th = q.plan->splitkRows;
+	if (q.plan && (q.plan->splitkBlocks == 1 || (q.plan->splitkBlocks == 2 && q.cin == 128 && nCog % 2 == 0))) {
+		cb = q.plan->splitkBlocks;
+	}
+	if (q.plan && q.plan->log) {
+		q.plan->log->note("conv_splitk cin=" + std::to_string(q.cin) + " cout=" + std::to_string(q.cout) + " pool=" +
+		                  std::to_string(q.pool != 0) + " H=" + std::to_string(q.H) + " W=" + std::to_string(q.W) + " items=" +
+		                  std::to_string(items) + " rows=" + std::to_string(th) + " blocks=" + std::to_string(cb));
+	}
 	p.TH = th;
 	const int tilesY = (q.H + th - 1) / th;
 	const bool f16t = dt == kF16;

@@ -220,6 +220,7 @@ _HOOK_SIGS = {
                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
+    "ju_plan_report": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
 }
 PRODUCT_SYMBOLS = tuple(sorted(_PRODUCT_SIGS))
@@ -513,6 +514,24 @@ class Runtime:
         arr = np.empty(n.value, np.float32)
         _check(self._lib, read(self._h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.size, C.byref(n)))
         return arr
+
+    def plan_report(self) -> list:
+        """``ju_plan_report`` (test flavour): the launch plans this runtime's flow-net launchers really used, one
+        dict per distinct launch -- ``kernel`` plus the line's fields as integers (``heights``: a tuple)."""
+        report = _hook(self._lib, "ju_plan_report")
+        n = C.c_size_t()
+        _check(self._lib, report(self._h, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value + 1)
+        _check(self._lib, report(self._h, buf, n.value + 1, C.byref(n)))
+        plans = []
+        for line in buf.value.decode().splitlines():
+            kernel, *fields = line.split()
+            d = {"kernel": kernel}
+            for f in fields:
+                k, v = f.split("=")
+                d[k] = tuple(int(x) for x in v.split(",")) if k == "heights" else int(v)
+            plans.append(d)
+        return plans
 
     @property
     def recurrent(self) -> bool:
