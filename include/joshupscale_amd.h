@@ -138,17 +138,37 @@ typedef struct ju_image {
  * from the 8-bit frame (normalize_brightness and output_flow models, or while a source mask is set) the word is 257 u8,
  * RGBPS u8 / 255, BGR96F u8.  tests/rgb_reference.py is the definition, bit for bit.
  *
+ * Packed 10-bit (what capture cards, hardware decoders and 10-bit desktop surfaces really hold).  ONE plane of
+ * little-endian words each; arithmetic, coefficients and the source of an output are those of the planar format of the
+ * same sampling (P210, I410, RGBP10) -- only the words differ:
+ *
+ *   format          sampling  layout (samples are 10-bit fields, from bit 0 on)              row bytes
+ *   JU_FMT_V210     4:2:2     six pixels in four 32-bit words of three samples (bits 0-9,     16 ceil(W / 6)
+ *                             10-19, 20-29): Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5
+ *   JU_FMT_Y210     4:2:2     16-bit words Y0 U Y1 V per pixel pair, the value in the UPPER   4 W
+ *                             10 bits, as P010 (ffmpeg y210le)
+ *   JU_FMT_Y410     4:4:4     one 32-bit word per pixel: U, Y, V (ffmpeg xv30le)              4 W
+ *   JU_FMT_X2RGB10  RGB       one 32-bit word per pixel: B, G, R (ffmpeg x2rgb10le)           4 W
+ *   JU_FMT_X2BGR10  RGB       one 32-bit word per pixel: R, G, B (x2bgr10le, R10G10B10A2)     4 W
+ *
+ * Bits 30-31 of every 32-bit word, the low 6 bits of a Y210 word and the sample slots of V210's last group beyond the
+ * width (W mod 6 = 2 or 4) are ignored on input and written 0 on output; all 16 bytes of a last partial V210 group are
+ * written, and nothing beyond a row's bytes is read or written (the conventional V210 stride, 128 ceil(W / 48), is the
+ * caller's to pass).  V210 and Y210 need an even width; Y410 and the two RGB formats take any size.  Plane addresses and
+ * strides are multiples of 4 (Y210: of 2).  Like I410, a Y410 frame carries an 8-bit frame without loss.
+ * tests/packed10_reference.py is the definition, bit for bit.
+ *
  * Memory: each runtime holds two staging buffers for host planes that fit the largest format (JU_FMT_BGR96F / JU_FMT_RGBPS,
  * 12 bytes per pixel: 24.9 MB for a 1920x1080 output, 12.4 MB more than the YUV formats needed; 1.6 MB for a 480x270
  * input), and ju_process_frames allocates one such slot per frame of a pass on first use (twice the former size).  All
  * are sized once for the largest format: nothing is regrown behind a captured graph.
  *
- * Limits: 8- and 10-bit YUV (no P016 / 12-bit, no NV16, no packed 10-bit Y210 / v210 / Y410, no other chroma siting); RGB
- * without 12-bit, without packed 10-bit (x2rgb10, R10G10B10A2), without dithering and without alpha (X is ignored and
- * written 0); float inputs are quantised to 8 bits like every input, they do not reach the network unquantised; no YUV
- * or RGB graphics resources (GL textures stay BGRX); look-ahead passes take these frames through ju_process_frames
- * (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not ju_process_group; the C++ plugin surface
- * (JoshUpscale/core.h) is unchanged and takes BGRX only. */
+ * Limits: 8- and 10-bit YUV (no 12- or 16-bit: P016 and friends need an encode to 16-bit codes that is not defined yet;
+ * no NV16 / NV21, no other chroma siting); RGB without 12-bit, without dithering and without alpha (X, and the two top
+ * bits of an x2rgb10 / x2bgr10 word, are ignored and written 0); float inputs are quantised to 8 bits like every input,
+ * they do not reach the network unquantised; no YUV or RGB graphics resources (GL textures stay BGRX); look-ahead passes
+ * take these frames through ju_process_frames (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not
+ * ju_process_group; the C++ plugin surface (JoshUpscale/core.h) is unchanged and takes BGRX only. */
 enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2, JU_FMT_P010 = 3, JU_FMT_I010 = 4 };
 enum {
 	JU_FMT_YUY2 = 16, JU_FMT_UYVY = 17, JU_FMT_I422 = 18, JU_FMT_P210 = 19, JU_FMT_I210 = 20,
@@ -158,11 +178,12 @@ enum {
 	JU_FMT_BGR24 = 32, JU_FMT_RGB24 = 33, JU_FMT_RGBX = 34, JU_FMT_BGRX64 = 35, JU_FMT_RGBP8 = 36, JU_FMT_RGBP10 = 37,
 	JU_FMT_RGBP16 = 38, JU_FMT_RGBPH = 39, JU_FMT_RGBPS = 40, JU_FMT_BGR96F = 41
 };
+enum { JU_FMT_X2BGR10 = 44, JU_FMT_X2RGB10 = 45, JU_FMT_V210 = 48, JU_FMT_Y210 = 49, JU_FMT_Y410 = 50 }; /* packed 10-bit */
 enum { JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3 };
 
 typedef struct ju_frame {
 	int format;            /* JU_FMT_* */
-	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX and the RGB formats (32..41) */
+	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX and the RGB formats (32..45) */
 	uint8_t location;      /* JU_LOC_CPU or JU_LOC_DEVICE (BGRX: any location a ju_image takes) */
 	size_t width, height;  /* in pixels (luma); even for the 4:2:0 formats, an even width for 4:2:2 */
 	void *planes[3];       /* BGRX, YUY2, UYVY and the packed RGB formats: [0]; planar formats: Y, U, V or R, G, B; NV12 /
@@ -170,8 +191,9 @@ typedef struct ju_frame {
 	ptrdiff_t strides[3];  /* BYTES per row of each plane (first logical row at planes[k]), any sign,
 	                          |stride| >= the plane's row bytes: Y = width, U / V = width / 2 (4:4:4: width), UV = width,
 	                          YUY2 / UYVY = 2 width, BGRX = 4 width; the 10-bit formats: twice that; RGB: width x 3 (BGR24 /
-	                          RGB24), 4 (RGBX), 8 (BGRX64), 12 (BGR96F), planar width x 1, 2 or 4.  Plane addresses and
-	                          strides are multiples of 2 for 16-bit and f16 samples and of 4 for f32 samples */
+	                          RGB24), 4 (RGBX), 8 (BGRX64), 12 (BGR96F), planar width x 1, 2 or 4; packed 10-bit: V210
+	                          16 ceil(width / 6), Y210 / Y410 / X2RGB10 / X2BGR10 4 width.  Plane addresses and strides are
+	                          multiples of 2 for 16-bit and f16 samples and of 4 for f32 samples and 32-bit words */
 } ju_frame;
 
 /* Replaces createRuntime(int deviceId, const std::filesystem::path &modelPath)
@@ -378,7 +400,8 @@ JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
  * out = (sum qy qx v + 2^23) >> 24, an output of the model's size passing through unchanged.
  *   8-bit formats, and every format while a mask is set or "hbd_from_state" is 0: v is the 8-bit BGRX frame (after the
  *   blend); deep formats are then encoded from the scaled 8-bit frame (257 x u8), as without an output size.
- *   Deep formats otherwise (JU_FMT_P010, I010, P210, I210, I410, BGRX64, RGBP10, RGBP16, RGBPH, RGBPS, BGR96F): v is the
+ *   Deep formats otherwise (JU_FMT_P010, I010, P210, I210, I410, BGRX64, RGBP10, RGBP16, RGBPH, RGBPS, BGR96F and the five
+ *   packed 10-bit formats): v is the
  *   state's 16-bit sample P = floor((s + 0.5) * 65536), saturated; the scaled P is encoded -- 10-bit YUV as from the state,
  *   16-bit words P, 10-bit words P >> 6, unit floats f32(P) / 65535 (RGBPH: that as f16), BGR96F f32(P) / 257.
  * (0, 0) turns it off.  filter: JU_SCALE_TRIANGLE, JU_SCALE_CATMULL_ROM or JU_SCALE_MITCHELL, as for ju_set_source_size

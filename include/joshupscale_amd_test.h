@@ -108,6 +108,17 @@ JU_API int ju_debug_yuv_sampled(int op, int format, int colorspace, size_t width
 JU_API int ju_debug_rgb(int op, int format, size_t width, size_t height, void *image, ptrdiff_t image_stride,
     void *const planes[3], const ptrdiff_t strides[3]);
 
+/* One of the packed 10-bit conversion kernels alone (format JU_FMT_V210 / Y210 / Y410 / X2RGB10 / X2BGR10;
+ * tests/packed10_reference.py), on caller-supplied device buffers, on the current device (synchronous).  Another format,
+ * a NULL buffer, an odd V210 / Y210 width, a plane off its alignment (4 bytes; Y210: 2) or a stride below the row bytes
+ * is JU_ERR_INVALID_ARGUMENT before any device call.  op 0: the plane -> BGRX rows at `image`; op 1: BGRX u8 rows at
+ * `image` -> the plane (P = 257 u8); op 2: the dense f16 tensor [height][width][4] at `image`, 16-byte aligned,
+ * image_stride ignored -> the plane; op 3: the dense u16 frame [height][width][4] (B, G, R, unused) at `image`, 8-byte
+ * aligned, image_stride ignored -> the plane (the sample is P itself).  Only planes[0] / strides[0] are read; `colorspace`
+ * is ignored for the two RGB formats.  ju_debug_yuv_items takes these formats as items too. */
+JU_API int ju_debug_packed10(int op, int format, int colorspace, size_t width, size_t height, void *image,
+    ptrdiff_t image_stride, void *const planes[3], const ptrdiff_t strides[3]);
+
 /* The source stage's kernels alone (docs/source_stage.md), on caller-supplied device buffers of BGRX rows with any byte
  * alignment and any signed strides, on the current device (synchronous).  op 0: the scaler -- `src` (src_width x
  * src_height) -> `dst` (dst_width x dst_height), tables built as ju_set_source_size builds them; the mask arguments are

@@ -431,7 +431,8 @@ int ju_debug_set(const char *key, int value) {
 namespace {
 // What the single-kernel conversion hooks and ju_debug_yuv_items share.  A hook = its name, the formats of the table it
 // admits (`family`: how its refusal of another calls them) and its ops: 0 decode planes -> BGRX `image`, 1 encode the BGRX
-// `image` -> planes and, where ops == 3, 2 encode the dense f16 tensor `image` -> planes, the deep formats only.
+// `image` -> planes and, where ops >= 3, 2 encode the dense f16 tensor `image` -> planes, the deep formats only; where
+// ops == 4, 3 encode the dense u16 frame `image` (launchEncodeFrame16) -> planes.
 struct ConversionHook {
 	const char *name, *family;
 	bool (*admits)(const ju::YuvFormatInfo &);
@@ -453,7 +454,7 @@ struct ConversionHook {
 			refuse("sizes 1 .. 32768, an even width for 4:2:0 and 4:2:2, an even height for 4:2:0");
 		}
 		if (image == nullptr || planes == nullptr || strides == nullptr) refuse("null buffer");
-		const auto row = static_cast<ptrdiff_t>((info.planes == 1 ? info.pixelBytes : info.sampleBytes) * width);
+		const auto row = static_cast<ptrdiff_t>(info.planes == 1 ? ju::planeShape(info, width, height, 0).rowBytes : info.sampleBytes * width);
 		for (int k = 0; k < info.planes; ++k) {
 			if (planes[k] == nullptr) refuse("null buffer");
 			if (reinterpret_cast<std::uintptr_t>(planes[k]) % info.sampleBytes || strides[k] % info.sampleBytes) {
@@ -463,10 +464,11 @@ struct ConversionHook {
 			if (rowStrides && strides[k] > -row && strides[k] < row) refuse("|stride| smaller than a row");
 		}
 		const auto imageRow = static_cast<ptrdiff_t>(4 * width);
-		if (rowStrides && op != 2 && image_stride > -imageRow && image_stride < imageRow) {
+		if (rowStrides && op < 2 && image_stride > -imageRow && image_stride < imageRow) {
 			refuse("|image_stride| smaller than a row");
 		}
 		if (op == 2 && reinterpret_cast<std::uintptr_t>(image) % 16) refuse("the f16 tensor must be 16-byte aligned");
+		if (op == 3 && reinterpret_cast<std::uintptr_t>(image) % 8) refuse("the u16 frame must be 8-byte aligned");
 		ju::YuvPlanes p;
 		std::uint8_t **plane[3] = {&p.y, &p.u, &p.v};
 		std::ptrdiff_t *stride[3] = {&p.yStride, &p.uStride, &p.vStride};
@@ -479,15 +481,17 @@ struct ConversionHook {
 	int run(int op, int format, int colorspace, size_t width, size_t height, void *image, ptrdiff_t image_stride,
 	    void *const *planes, const ptrdiff_t *strides) const {
 		return guarded([&] {
-			if (op < 0 || op >= ops) refuse(ops == 2 ? "direction must be 0 or 1" : "op must be 0, 1 or 2");
+			if (op < 0 || op >= ops) refuse(ops == 2 ? "direction must be 0 or 1" : (ops == 3 ? "op must be 0, 1 or 2" : "op must be 0 .. 3"));
 			const ju::YuvPlanes p = this->planes(this->format(format), op, width, height, image, image_stride, planes, strides);
 			const int w = static_cast<int>(width), h = static_cast<int>(height);
 			if (op == 0) {
 				ju::launchDecodeFrame(format, colorspace, p, static_cast<std::uint8_t *>(image), image_stride, w, h, nullptr);
 			} else if (op == 1) {
 				ju::launchEncodeFrame(format, colorspace, static_cast<const std::uint8_t *>(image), image_stride, p, w, h, nullptr);
-			} else {
+			} else if (op == 2) {
 				ju::launchEncodeState(format, colorspace, image, p, w, h, nullptr);
+			} else {
+				ju::launchEncodeFrame16(format, colorspace, static_cast<const std::uint16_t *>(image), p, w, h, nullptr);
 			}
 			JU_HIP(hipStreamSynchronize(nullptr));
 		});
@@ -496,9 +500,12 @@ struct ConversionHook {
 using Info = const ju::YuvFormatInfo &;
 const ConversionHook kDebugYuv{"ju_debug_yuv", "a YUV", [](Info f) { return f.sampling == 420 && !f.deep(); }, 2, false};
 const ConversionHook kDebugYuv10{"ju_debug_yuv10", "a 10-bit", [](Info f) { return f.sampling == 420 && f.deep(); }, 3, false};
+// (the packed 10-bit formats -- one plane of 10-bit samples -- have a hook of their own; the two before it keep their families)
+constexpr bool packed10(Info f) { return f.planes == 1 && f.bits == 10; }
 const ConversionHook kDebugYuvSampled{"ju_debug_yuv_sampled", "a 4:2:2 / 4:4:4",
-    [](Info f) { return f.sampling == 422 || f.sampling == 444; }, 3, false};
-const ConversionHook kDebugRgb{"ju_debug_rgb", "an RGB", [](Info f) { return f.rgb(); }, 3, true};
+    [](Info f) { return (f.sampling == 422 || f.sampling == 444) && !packed10(f); }, 3, false};
+const ConversionHook kDebugRgb{"ju_debug_rgb", "an RGB", [](Info f) { return f.rgb() && !packed10(f); }, 3, true};
+const ConversionHook kDebugPacked10{"ju_debug_packed10", "a packed 10-bit", [](Info f) { return packed10(f); }, 4, true};
 const ConversionHook kDebugYuvItems{"ju_debug_yuv_items", "a YUV", [](Info) { return true; }, 1, false};
 }  // namespace
 
@@ -520,6 +527,11 @@ int ju_debug_yuv_sampled(int op, int format, int colorspace, size_t width, size_
 int ju_debug_rgb(int op, int format, size_t width, size_t height, void *image, ptrdiff_t image_stride,
     void *const planes[3], const ptrdiff_t strides[3]) {
 	return kDebugRgb.run(op, format, 0, width, height, image, image_stride, planes, strides);
+}
+
+int ju_debug_packed10(int op, int format, int colorspace, size_t width, size_t height, void *image, ptrdiff_t image_stride,
+    void *const planes[3], const ptrdiff_t strides[3]) {
+	return kDebugPacked10.run(op, format, colorspace, width, height, image, image_stride, planes, strides);
 }
 
 int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, size_t width, size_t height,

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -707,13 +708,19 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv420p10_kernel(const std::uint8
 template <int F>
 struct SampledTraits {
 	static constexpr bool kPacked = F == kYuy2 || F == kUyvy;
-	static constexpr bool kDeep = F == kP210 || F == kI210 || F == kI410;
-	static constexpr bool kFull = F == kI444 || F == kI410;  // (4:4:4: a chroma sample per pixel)
+	static constexpr bool kDeep = F == kP210 || F == kI210 || F == kI410 || F == kY210 || F == kY410;
+	static constexpr bool kFull = F == kI444 || F == kI410 || F == kY410;  // (4:4:4: a chroma sample per pixel)
 	static constexpr bool kSemi = F == kP210;
-	static constexpr int kShift = F == kP210 ? 6 : 0;        // (word >> 6, or word & 0x3ff)
+	static constexpr int kShift = (F == kP210 || F == kY210) ? 6 : 0;  // (word >> 6, or word & 0x3ff)
 	static constexpr int kYByte = F == kYuy2 ? 0 : 1;        // packed: the byte of Y0 in a pair's four (U: 1 - kYByte)
 	static constexpr int kMid = kDeep ? 512 : 128;
 };
+
+// (runs of samples: "RGB formats" below; Y410's dwords move as such a run)
+template <int B, int N, int G>
+__device__ inline void loadRun(const std::uint8_t *row, int first, int lastGroup, bool fast, unsigned (&w)[N * B / 4]);
+template <int B, int N>
+__device__ inline void storeRun(std::uint8_t *row, int first, int n, bool fast, const unsigned (&w)[N * B / 4]);
 
 // The strip's 16 luma samples and its chroma samples as integers: 4:4:4 cu / cv[0 .. 15]; 4:2:2 cu / cv[0 .. 7] = cells
 // x0 / 2 .. x0 / 2 + 7 and [8] = the next cell, for the odd column of the last pixel.  Every index is clamped to its row.
@@ -724,6 +731,49 @@ __device__ inline void loadSampledStrip(const YuvPlanes &src, int y, int x0, int
 	const int CW = T::kFull ? W : W / 2;
 	const int c0 = T::kFull ? x0 : x0 / 2;
 	const std::uint8_t *rowY = src.y + static_cast<std::ptrdiff_t>(y) * src.yStride;
+	if constexpr (F == kY210) {  // 16-bit words Y0 U Y1 V per pixel pair, two words a dword
+		if (full) {
+			unsigned w[16];
+#pragma unroll
+			for (int q = 0; q < 2; ++q) {
+				unsigned h[8];
+				loadSamples<16>(rowY, 2 * x0 + 16 * q, 2 * W - 1, true, h);
+#pragma unroll
+				for (int i = 0; i < 8; ++i) w[8 * q + i] = h[i];
+			}
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				ys[2 * i] = (w[2 * i] & 0xffff) >> T::kShift;
+				cu[i] = w[2 * i] >> (16 + T::kShift);
+				ys[2 * i + 1] = (w[2 * i + 1] & 0xffff) >> T::kShift;
+				cv[i] = w[2 * i + 1] >> (16 + T::kShift);
+			}
+		} else {
+#pragma unroll
+			for (int i = 0; i < 8; ++i) {
+				const int c = min(c0 + i, CW - 1);
+				ys[2 * i] = wordAt(rowY, 4 * c) >> T::kShift;
+				cu[i] = wordAt(rowY, 4 * c + 1) >> T::kShift;
+				ys[2 * i + 1] = wordAt(rowY, 4 * c + 2) >> T::kShift;
+				cv[i] = wordAt(rowY, 4 * c + 3) >> T::kShift;
+			}
+		}
+		const int last = min(c0 + 8, CW - 1);
+		cu[8] = wordAt(rowY, 4 * last + 1) >> T::kShift;
+		cv[8] = wordAt(rowY, 4 * last + 3) >> T::kShift;
+		return;
+	}
+	if constexpr (F == kY410) {  // one dword per pixel: U, Y, V from bit 0 on, bits 30-31 ignored
+		unsigned w[16];
+		loadRun<4, 16, 1>(rowY, x0, W - 1, full, w);
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			cu[p] = w[p] & 0x3ff;
+			ys[p] = (w[p] >> 10) & 0x3ff;
+			cv[p] = (w[p] >> 20) & 0x3ff;
+		}
+		return;
+	}
 	if constexpr (T::kPacked) {
 		constexpr int yb = T::kYByte, cb = 1 - T::kYByte;
 		if (full) {
@@ -882,6 +932,29 @@ __device__ inline void storeSampledStrip(const YuvPlanes &dst, int y, int x0, in
 	const int c0 = T::kFull ? x0 : x0 / 2;
 	const int cn = T::kFull ? n : n / 2;
 	std::uint8_t *rowY = dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride;
+	if constexpr (F == kY210) {  // (the low 6 bits of every word: 0)
+#pragma unroll
+		for (int q = 0; q < 2; ++q) {
+			unsigned w[8];
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				const int c = 4 * q + i;
+				w[2 * i] = static_cast<unsigned>(ys[2 * c] << T::kShift) | (static_cast<unsigned>(cu[c] << T::kShift) << 16);
+				w[2 * i + 1] = static_cast<unsigned>(ys[2 * c + 1] << T::kShift) | (static_cast<unsigned>(cv[c] << T::kShift) << 16);
+			}
+			storeSamples<16>(rowY, 2 * x0 + 16 * q, 2 * n - 16 * q, full, w);
+		}
+		return;
+	}
+	if constexpr (F == kY410) {  // (bits 30-31: 0)
+		unsigned w[16];
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			w[p] = static_cast<unsigned>(cu[p]) | (static_cast<unsigned>(ys[p]) << 10) | (static_cast<unsigned>(cv[p]) << 20);
+		}
+		storeRun<4, 16>(rowY, x0, n, full, w);
+		return;
+	}
 	if constexpr (T::kPacked) {
 		constexpr int yb = T::kYByte, cb = 1 - T::kYByte;
 #pragma unroll
@@ -1134,8 +1207,11 @@ struct RgbTraits {
 	static constexpr bool kPlanar = F >= kRgbp8 && F <= kRgbps;  // planes R, G, B; else ONE plane of kPixel samples a pixel
 	static constexpr int kPixel = kPlanar ? 1 : ((F == kRgbx || F == kBgrx64) ? 4 : 3);
 	static constexpr int kB = (F == kRgb24 || F == kRgbx) ? 2 : 0, kG = 1, kR = 2 - kB;  // a packed pixel's samples
+	// X2RGB10 / X2BGR10: ONE dword per pixel holding the three 10-bit samples from bits kBShift, 10 and 20 - kBShift on
+	static constexpr bool kWord10 = F == kX2rgb10 || F == kX2bgr10;
+	static constexpr int kBShift = F == kX2rgb10 ? 0 : 20;
 	static constexpr int kKind = (F == kBgrx64 || F == kRgbp16) ? kW16
-	    : F == kRgbp10 ? kW10 : F == kRgbph ? kHalf : F == kRgbps ? kUnit : F == kBgr96f ? kF255 : kU8;
+	    : (F == kRgbp10 || kWord10) ? kW10 : F == kRgbph ? kHalf : F == kRgbps ? kUnit : F == kBgr96f ? kF255 : kU8;
 	static constexpr int kBytes = kKind == kU8 ? 1 : ((kKind == kUnit || kKind == kF255) ? 4 : 2);
 };
 
@@ -1176,7 +1252,20 @@ __device__ __forceinline__ void rgbToBgrxStrip(const YuvPlanes &src, std::uint8_
 	const bool full = x0 + kStrip <= W;
 	const int n = min(kStrip, W - x0);
 	std::uint8_t *out = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
-	if constexpr (T::kPlanar) {
+	if constexpr (T::kWord10) {
+		unsigned w[16];
+		loadRun<4, 16, 1>(src.y + static_cast<std::ptrdiff_t>(y) * src.yStride, x0, W - 1, full, w);
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			unsigned px[4];
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {  // (u8OfSample reads the low 10 bits: bits 30-31 are ignored)
+				const unsigned v = w[4 * q + i];
+				px[i] = u8OfSample<K>(v >> T::kBShift) | (u8OfSample<K>(v >> 10) << 8) | (u8OfSample<K>(v >> (20 - T::kBShift)) << 16);
+			}
+			storeBytes<16>(out, 4 * (x0 + 4 * q), 4 * (n - 4 * q), full, px);
+		}
+	} else if constexpr (T::kPlanar) {
 		unsigned wr[4 * B], wg[4 * B], wb[4 * B];
 		loadRun<B, 16, 1>(src.y + static_cast<std::ptrdiff_t>(y) * src.yStride, x0, W - 1, full, wr);
 		loadRun<B, 16, 1>(src.u + static_cast<std::ptrdiff_t>(y) * src.uStride, x0, W - 1, full, wg);
@@ -1236,7 +1325,15 @@ __device__ inline void toRgbStrip(const Source &source, const YuvPlanes &dst, in
 	const int n = min(kStrip, W - x0);
 	typename Source::Raw px[16];
 	source.loadRaw(y, x0, W, full, px);
-	if constexpr (T::kPlanar) {
+	if constexpr (T::kWord10) {  // (bits 30-31: 0)
+		unsigned w[16];
+#pragma unroll
+		for (int p = 0; p < 16; ++p) {
+			w[p] = (Source::template deep<K>(Source::rawB(px[p])) << T::kBShift) | (Source::template deep<K>(Source::rawG(px[p])) << 10) |
+			       (Source::template deep<K>(Source::rawR(px[p])) << (20 - T::kBShift));
+		}
+		storeRun<4, 16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, w);
+	} else if constexpr (T::kPlanar) {
 		unsigned wr[4 * B], wg[4 * B], wb[4 * B];
 #pragma unroll
 		for (int q = 0; q < 4 * B; ++q) wr[q] = wg[q] = wb[q] = 0;
@@ -1281,6 +1378,152 @@ __global__ __launch_bounds__(256) void frame16_to_rgb_kernel(const std::uint16_t
 	toRgbStrip<F>(Bgrx16Source{frame}, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
+// ---- V210: 10-bit 4:2:2, six pixels in four dwords (tests/packed10_reference.py; docs/yuv_io.md, "Packed 10-bit") -------
+// A group of six pixels is 16 bytes: w0 = Cb0 Y0 Cr0, w1 = Y1 Cb1 Y2, w2 = Cr1 Y3 Cb2, w3 = Y4 Cr2 Y5, three 10-bit samples a
+// dword from bit 0 on, bits 30-31 unused.  A thread owns TWO whole groups of one row (12 pixels), so that no group is
+// shared between threads; a row is whole groups (its last one padded with unused sample slots: ignored in, 0 out), and
+// the plane is only 4-byte aligned, so a group moves as one 16-byte access where it lies so and as four dwords elsewhere.
+// The samples, the arithmetic and the sample P are P210's (the 4:2:2 section above).
+constexpr int kGroupStrip = 12;  // luma pixels per thread and row
+
+__device__ inline void loadGroup(const std::uint8_t *p, unsigned *w) {
+	if (alignedTo(p, 16)) {
+		const u32x4 v = *reinterpret_cast<const u32x4 *>(p);
+		w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+	} else {
+#pragma unroll
+		for (int q = 0; q < 4; ++q) w[q] = reinterpret_cast<const unsigned *>(p)[q];
+	}
+}
+
+__device__ inline void storeGroup(std::uint8_t *p, const unsigned *w) {
+	if (alignedTo(p, 16)) {
+		const u32x4 v = {w[0], w[1], w[2], w[3]};
+		*reinterpret_cast<u32x4 *>(p) = v;
+	} else {
+#pragma unroll
+		for (int q = 0; q < 4; ++q) reinterpret_cast<unsigned *>(p)[q] = w[q];
+	}
+}
+
+// the plane -> BGRX: the strip of thread `idx`; the body of the single-frame kernel and of the items kernel's branch.
+// Chroma cell c0 + 6, the right-hand neighbour of the strip's last odd column, is the first of the NEXT thread's groups;
+// cells beyond W / 2 - 1 -- that one in a row's last strip, and the unused slots of a partial group -- take the last cell's.
+__device__ inline void v210ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H, int idx) {
+	const int strips = (W + kGroupStrip - 1) / kGroupStrip;
+	if (idx >= strips * H) return;
+	const int y = idx / strips;
+	const int x0 = (idx - y * strips) * kGroupStrip;
+	const int groups = (W + 5) / 6, g0 = x0 / 6, CW = W / 2, c0 = x0 / 2;
+	const bool full = x0 + kGroupStrip <= W;
+	const std::uint8_t *row = src.y + static_cast<std::ptrdiff_t>(y) * src.yStride;
+	unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	loadGroup(row + 16 * g0, w);
+	if (g0 + 1 < groups) loadGroup(row + 16 * (g0 + 1), w + 4);
+	int ys[12], cu[7], cv[7];
+#pragma unroll
+	for (int g = 0; g < 2; ++g) {
+		const unsigned *q = w + 4 * g;
+		cu[3 * g] = q[0] & 0x3ff, ys[6 * g] = (q[0] >> 10) & 0x3ff, cv[3 * g] = (q[0] >> 20) & 0x3ff;
+		ys[6 * g + 1] = q[1] & 0x3ff, cu[3 * g + 1] = (q[1] >> 10) & 0x3ff, ys[6 * g + 2] = (q[1] >> 20) & 0x3ff;
+		cv[3 * g + 1] = q[2] & 0x3ff, ys[6 * g + 3] = (q[2] >> 10) & 0x3ff, cu[3 * g + 2] = (q[2] >> 20) & 0x3ff;
+		ys[6 * g + 4] = q[3] & 0x3ff, cv[3 * g + 2] = (q[3] >> 10) & 0x3ff, ys[6 * g + 5] = (q[3] >> 20) & 0x3ff;
+	}
+	cu[6] = cv[6] = 0;
+	if (g0 + 2 < groups) {  // (a group that exists begins with a cell that exists)
+		const unsigned next = *reinterpret_cast<const unsigned *>(row + 16 * (g0 + 2));
+		cu[6] = next & 0x3ff, cv[6] = (next >> 20) & 0x3ff;
+	}
+#pragma unroll
+	for (int i = 1; i < 7; ++i) {
+		if (c0 + i >= CW) cu[i] = cu[i - 1], cv[i] = cv[i - 1];
+	}
+	unsigned px[kGroupStrip];
+#pragma unroll
+	for (int p = 0; p < kGroupStrip; ++p) {
+		const int i = p >> 1;
+		const int du = ((p & 1) ? 4 * (cu[i] + cu[i + 1]) : 8 * cu[i]) - 8 * 512;
+		const int dv = ((p & 1) ? 4 * (cv[i] + cv[i + 1]) : 8 * cv[i]) - 8 * 512;
+		const int yd = k.ky * (8 * (ys[p] - k.oy));
+		const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
+		const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
+		const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+		px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
+	}
+	std::uint8_t *out = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
+	const int n = min(kGroupStrip, W - x0);
+#pragma unroll
+	for (int q = 0; q < 3; ++q) {
+		const unsigned v[4] = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
+		storeBytes<16>(out, 4 * (x0 + 4 * q), 4 * (n - 4 * q), full, v);
+	}
+}
+
+__global__ __launch_bounds__(256) void v210_to_bgrx_kernel(YuvPlanes src, YuvDecode k, std::uint8_t *__restrict__ dst,
+    std::ptrdiff_t dstStride, int W, int H) {
+	v210ToBgrxStrip(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+// P -> the plane: the strip body of the three encodes.  The source's load covers columns x0 - 1 (clamped to 0: the
+// left-hand neighbour of the [1, 2, 1] sum) and x0 .. x0 + 15 (clamped to W - 1), of which the strip uses the first 12; its
+// wide path needs all 16 in range.  Sample slots beyond W are written 0, and a group is written whole.
+template <typename Source>
+__device__ inline void toV210Strip(const Source &source, const YuvEncode10 &k, const YuvPlanes &dst, int W, int H, int idx) {
+	const int strips = (W + kGroupStrip - 1) / kGroupStrip;
+	if (idx >= strips * H) return;
+	const int y = idx / strips;
+	const int x0 = (idx - y * strips) * kGroupStrip;
+	const int groups = (W + 5) / 6, g0 = x0 / 6, CW = W / 2, c0 = x0 / 2;
+	typename Source::Pixel px[17];  // [0] = column x0 - 1 (clamped), [1 + p] = column x0 + p
+	source.load(y, x0, W, x0 + kStrip <= W, px);
+	unsigned ys[12], cu[6], cv[6];
+#pragma unroll
+	for (int p = 0; p < 12; ++p) {
+		const long long acc = (static_cast<long long>(k.yr) * Source::r(px[1 + p]) +
+		                       static_cast<long long>(k.yg) * Source::g(px[1 + p]) +
+		                       static_cast<long long>(k.yb) * Source::b(px[1 + p])) * Source::kScale + (1ll << 31);
+		ys[p] = x0 + p < W ? static_cast<unsigned>(clamp1023(k.oy + static_cast<int>(acc >> 32))) : 0u;
+	}
+#pragma unroll
+	for (int i = 0; i < 6; ++i) {
+		const int sb = Source::b(px[2 * i]) + 2 * Source::b(px[2 * i + 1]) + Source::b(px[2 * i + 2]);
+		const int sg = Source::g(px[2 * i]) + 2 * Source::g(px[2 * i + 1]) + Source::g(px[2 * i + 2]);
+		const int sr = Source::r(px[2 * i]) + 2 * Source::r(px[2 * i + 1]) + Source::r(px[2 * i + 2]);
+		const long long au = (static_cast<long long>(k.ur) * sr + static_cast<long long>(k.ug) * sg +
+		                      static_cast<long long>(k.ub) * sb) * Source::kScale + (1ll << 33);
+		const long long av = (static_cast<long long>(k.vr) * sr + static_cast<long long>(k.vg) * sg +
+		                      static_cast<long long>(k.vb) * sb) * Source::kScale + (1ll << 33);
+		cu[i] = c0 + i < CW ? static_cast<unsigned>(clamp1023(512 + static_cast<int>(au >> 34))) : 0u;
+		cv[i] = c0 + i < CW ? static_cast<unsigned>(clamp1023(512 + static_cast<int>(av >> 34))) : 0u;
+	}
+	std::uint8_t *row = dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride;
+#pragma unroll
+	for (int g = 0; g < 2; ++g) {
+		if (g0 + g >= groups) break;
+		const unsigned w[4] = {cu[3 * g] | (ys[6 * g] << 10) | (cv[3 * g] << 20),
+		    ys[6 * g + 1] | (cu[3 * g + 1] << 10) | (ys[6 * g + 2] << 20),
+		    cv[3 * g + 1] | (ys[6 * g + 3] << 10) | (cu[3 * g + 2] << 20),
+		    ys[6 * g + 4] | (cv[3 * g + 2] << 10) | (ys[6 * g + 5] << 20)};
+		storeGroup(row + 16 * (g0 + g), w);
+	}
+}
+
+__global__ __launch_bounds__(256) void bgrx_to_v210_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
+    YuvEncode10 k, YuvPlanes dst, int W, int H) {
+	toV210Strip(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void state_to_v210_kernel(const f16 *__restrict__ state, YuvEncode10 k, YuvPlanes dst, int W,
+    int H) {
+	toV210Strip(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void frame16_to_v210_kernel(const std::uint16_t *__restrict__ frame, YuvEncode10 k,
+    YuvPlanes dst, int W, int H) {
+	toV210Strip(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+}
+
 // The formats each kernel family instantiates, ONE list per family: the launchers below and the items kernel reach a
 // format's kernel or strip body through forFormat alone.  4:2:0: <NV12> / <P010> = the list's second format; the encodes of
 // the other two families pick the 8-bit or the deep kernel from the format's traits.
@@ -1288,8 +1531,9 @@ template <int... Fs>
 struct Formats {};
 using Yuv420 = Formats<kI420, kNv12>;
 using Yuv420p10 = Formats<kI010, kP010>;
-using Sampled = Formats<kYuy2, kUyvy, kI422, kP210, kI210, kI444, kI410>;
-using Rgb = Formats<kBgr24, kRgb24, kRgbx, kBgrx64, kRgbp8, kRgbp10, kRgbp16, kRgbph, kRgbps, kBgr96f>;
+using Sampled = Formats<kYuy2, kUyvy, kI422, kP210, kI210, kI444, kI410, kY210, kY410>;
+using Grouped = Formats<kV210>;
+using Rgb = Formats<kBgr24, kRgb24, kRgbx, kBgrx64, kRgbp8, kRgbp10, kRgbp16, kRgbph, kRgbps, kBgr96f, kX2rgb10, kX2bgr10>;
 // fn(std::integral_constant<int, F>, args...) for the F of the list that equals `format`; false: the list has no such format
 template <int... Fs, typename Fn, typename... A>
 __host__ __device__ inline bool forFormat(Formats<Fs...>, int format, Fn &&fn, const A &...args) {
@@ -1315,6 +1559,9 @@ __global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItem
 	       }, it, W, H, idx) ||
 	       forFormat(Sampled{}, it.format, [](auto f, Item it, int W, int H, int idx) {
 		       yuvSampledToBgrxStrip<f()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Grouped{}, it.format, [](auto, Item it, int W, int H, int idx) {
+		       v210ToBgrxStrip(it.src, it.k, it.dst, it.dstStride, W, H, idx);
 	       }, it, W, H, idx) ||
 	       forFormat(Rgb{}, it.format, [](auto f, Item it, int W, int H, int idx) {
 		       rgbToBgrxStrip<f()>(it.src, it.dst, it.dstStride, W, H, idx);
@@ -1396,16 +1643,20 @@ YuvEncode10 encodeCoefficients10(int colorspace) {
 	return k;
 }
 
-// One strip kernel over a frame: a thread per 16 pixels of a row or, for 4:2:0, of a row pair; every kernel's arguments
-// end in the frame's width and height
+// threads of a frame in a format: one per strip -- 16 pixels (V210: 12, two groups) of a row or, for 4:2:0, of a row pair
+std::size_t stripThreads(const YuvFormatInfo &info, int width, int height) {
+	const int strip = info.pixelBytes == kGroupedRow ? kGroupStrip : kStrip;
+	return static_cast<std::size_t>((width + strip - 1) / strip) * (info.perRow() ? height : height / 2);
+}
+
+// One strip kernel over a frame: a thread per strip; every kernel's arguments end in the frame's width and height
 struct StripLaunch {
 	const YuvFormatInfo &info;
 	int width, height;
 	hipStream_t stream;
 	template <typename... P, typename... A>
 	void operator()(const char *name, void (*kernel)(P...), const A &...args) const {
-		const std::size_t strips = static_cast<std::size_t>((width + kStrip - 1) / kStrip);
-		const dim3 grid(blocksFor(strips * (info.perRow() ? height : height / 2)));
+		const dim3 grid(blocksFor(stripThreads(info, width, height)));
 		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, args..., width, height);
 		hipCheckLaunch(name);
 	}
@@ -1427,6 +1678,7 @@ void launchDecodeFrame(int format, int colorspace, const YuvPlanes &src, std::ui
 	            [&](auto f) { run("yuv420p10_to_bgrx", yuv420p10_to_bgrx_kernel<f() == kP010>, src, k, dst, dstStride); }) ||
 	        forFormat(Sampled{}, format,
 	            [&](auto f) { run("yuv_sampled_to_bgrx", yuv_sampled_to_bgrx_kernel<f()>, src, k, dst, dstStride); }) ||
+	        forFormat(Grouped{}, format, [&](auto) { run("v210_to_bgrx", v210_to_bgrx_kernel, src, k, dst, dstStride); }) ||
 	        forFormat(Rgb{}, format, [&](auto f) { run("rgb_to_bgrx", rgb_to_bgrx_kernel<f()>, src, dst, dstStride); }))) {
 		noKernel("decode", format);
 	}
@@ -1444,9 +1696,8 @@ YuvDecodeItem yuvDecodeItem(int format, int colorspace, const YuvPlanes &src, st
 
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream) {
 	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("yuv420_to_bgrx_items: 1 .. 8 items");
-	bool perRow = false;
-	for (int i = 0; i < count; ++i) perRow = perRow || formatInfo(items.item[i].format).perRow();
-	const std::size_t threads = static_cast<std::size_t>((width + kStrip - 1) / kStrip) * (perRow ? height : height / 2);
+	std::size_t threads = 0;  // (the most any item needs; an item's strip body returns beyond its own count)
+	for (int i = 0; i < count; ++i) threads = std::max(threads, stripThreads(formatInfo(items.item[i].format), width, height));
 	hipLaunchKernelGGL(yuv420_to_bgrx_items_kernel, dim3(blocksFor(threads), count), dim3(256), 0, stream, items, width,
 	    height);
 	hipCheckLaunch("yuv420_to_bgrx_items");
@@ -1465,6 +1716,8 @@ void launchEncodeFrame(int format, int colorspace, const std::uint8_t *src, std:
 		} else {
 			run("bgrx_to_yuv_sampled", bgrx_to_yuv_sampled_kernel<f()>, src, srcStride, encodeCoefficients(colorspace), dst);
 		}
+	}) || forFormat(Grouped{}, format, [&](auto) {
+		run("bgrx_to_v210", bgrx_to_v210_kernel, src, srcStride, encodeCoefficients10(colorspace), dst);
 	}) || forFormat(Rgb{}, format, [&](auto f) { run("bgrx_to_rgb", bgrx_to_rgb_kernel<f()>, src, srcStride, dst); });
 	if (!done) noKernel("encode", format);
 }
@@ -1481,6 +1734,8 @@ void launchEncodeState(int format, int colorspace, const void *state, const YuvP
 		} else {
 			noKernel("encode from the state", format);
 		}
+	}) || forFormat(Grouped{}, format, [&](auto) {
+		run("state_to_v210", state_to_v210_kernel, s, encodeCoefficients10(colorspace), dst);
 	}) || forFormat(Rgb{}, format, [&](auto f) {
 		if constexpr (RgbTraits<f()>::kKind != kU8) run("state_to_rgb", state_to_rgb_kernel<f()>, s, dst);
 		else noKernel("encode from the state", format);
@@ -1499,6 +1754,8 @@ void launchEncodeFrame16(int format, int colorspace, const std::uint16_t *frame,
 		} else {
 			noKernel("encode from a 16-bit frame", format);
 		}
+	}) || forFormat(Grouped{}, format, [&](auto) {
+		run("frame16_to_v210", frame16_to_v210_kernel, frame, encodeCoefficients10(colorspace), dst);
 	}) || forFormat(Rgb{}, format, [&](auto f) {
 		if constexpr (RgbTraits<f()>::kKind != kU8) run("frame16_to_rgb", frame16_to_rgb_kernel<f()>, frame, dst);
 		else noKernel("encode from a 16-bit frame", format);

@@ -52,7 +52,8 @@ inline bool overlap(const FrameExtent &a, const FrameExtent &b) {
 }
 
 // Plane k of a frame of the given size: rows, bytes per row (planar: Y, U, V or R, G, B; semi-planar: Y, UV; packed: one
-// plane of pixelBytes per pixel -- YUY2 / UYVY 2, BGR24 3, RGBX 4, BGRX64 8, BGR96F 12; samples of 1, 2 or 4 bytes)
+// plane of pixelBytes per pixel -- YUY2 / UYVY 2, BGR24 3, RGBX 4, BGRX64 8, BGR96F 12; samples of 1, 2 or 4 bytes; a
+// negative pixelBytes: V210's rows of 16 bytes per six pixels, the last group whole)
 struct PlaneShape {
 	std::size_t rows, rowBytes;
 };
@@ -61,6 +62,7 @@ struct PlaneShape {
 template <typename Info>
 PlaneShape planeShape(const Info &info, std::size_t w, std::size_t h, int k) {
 	const auto b = static_cast<std::size_t>(info.sampleBytes);
+	if (info.planes == 1 && info.pixelBytes < 0) return {h, 16 * ((w + 5) / 6)};  // V210: whole groups of six pixels
 	if (info.planes == 1) return {h, static_cast<std::size_t>(info.pixelBytes) * w};
 	if (k == 0 || info.sampling == 0) return {h, w * b};
 	const std::size_t cw = info.sampling == 444 ? w : w / 2;  // chroma samples per row (a semi-planar row holds both planes')

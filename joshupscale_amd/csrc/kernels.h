@@ -478,11 +478,14 @@ void launchCopyRows(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint
 // I422 and I210 (Y, U, V; I210 words as I010), P210 (Y, UV; words as P010), I444 and I410 (three full planes; I410 words as
 // I010).  From 32 on, RGB (no colour space): packed BGR24 / RGB24 (3 bytes per pixel), RGBX, BGRX64 (four 16-bit words per
 // pixel) and BGR96F (three f32 per pixel, 0..255) are ONE plane; RGBP8 / RGBP10 / RGBP16 / RGBPH / RGBPS are planes R, G, B
-// of bytes, words (RGBP10: the value in the low 10 bits), f16 and f32 (0..1).
+// of bytes, words (RGBP10: the value in the low 10 bits), f16 and f32 (0..1).  Packed 10-bit, ONE plane of little-endian
+// words each: V210 (4:2:2; six pixels in four 32-bit words of three samples), Y210 (4:2:2; 16-bit words Y0 U Y1 V, words
+// as P010), Y410 (4:4:4) and X2RGB10 / X2BGR10 (RGB): one 32-bit word of three samples per pixel, bits 30-31 unused.
 enum class PixelFormat : int {
 	Bgrx = 0, I420 = 1, Nv12 = 2, P010 = 3, I010 = 4,
 	Yuy2 = 16, Uyvy = 17, I422 = 18, P210 = 19, I210 = 20, I444 = 24, I410 = 25,
-	Bgr24 = 32, Rgb24 = 33, Rgbx = 34, Bgrx64 = 35, Rgbp8 = 36, Rgbp10 = 37, Rgbp16 = 38, Rgbph = 39, Rgbps = 40, Bgr96f = 41
+	Bgr24 = 32, Rgb24 = 33, Rgbx = 34, Bgrx64 = 35, Rgbp8 = 36, Rgbp10 = 37, Rgbp16 = 38, Rgbph = 39, Rgbps = 40, Bgr96f = 41,
+	X2bgr10 = 44, X2rgb10 = 45, V210 = 48, Y210 = 49, Y410 = 50
 };
 // (the same values as integers: what a launcher's `format` argument and a kernel's `template <int F>` parameter hold)
 constexpr int fmt(PixelFormat f) { return static_cast<int>(f); }
@@ -492,7 +495,9 @@ constexpr int kI420 = fmt(PixelFormat::I420), kNv12 = fmt(PixelFormat::Nv12), kP
               kI444 = fmt(PixelFormat::I444), kI410 = fmt(PixelFormat::I410), kBgr24 = fmt(PixelFormat::Bgr24),
               kRgb24 = fmt(PixelFormat::Rgb24), kRgbx = fmt(PixelFormat::Rgbx), kBgrx64 = fmt(PixelFormat::Bgrx64),
               kRgbp8 = fmt(PixelFormat::Rgbp8), kRgbp10 = fmt(PixelFormat::Rgbp10), kRgbp16 = fmt(PixelFormat::Rgbp16),
-              kRgbph = fmt(PixelFormat::Rgbph), kRgbps = fmt(PixelFormat::Rgbps), kBgr96f = fmt(PixelFormat::Bgr96f);
+              kRgbph = fmt(PixelFormat::Rgbph), kRgbps = fmt(PixelFormat::Rgbps), kBgr96f = fmt(PixelFormat::Bgr96f),
+              kV210 = fmt(PixelFormat::V210), kY210 = fmt(PixelFormat::Y210), kY410 = fmt(PixelFormat::Y410),
+              kX2rgb10 = fmt(PixelFormat::X2rgb10), kX2bgr10 = fmt(PixelFormat::X2bgr10);
 
 // THE table of the frame formats beside BGRX: the C API, the engine and the launchers below classify a format through it
 // alone.  planes: 3 planar (Y, U, V / R, G, B), 2 semi-planar (Y, UV), 1 packed (pixelBytes per pixel).
@@ -503,12 +508,14 @@ struct YuvFormatInfo {
 	int planes;
 	int bits;         // 8, or 10 in 16-bit words; RGB: 8, 10, 16 (words and f16) or 32 (f32)
 	int sampleBytes;  // 1, 2 or 4: what a plane's address and stride must be a multiple of
-	int pixelBytes;   // packed formats: bytes per pixel (2, 3, 4, 8 or 12); else 0
+	int pixelBytes;   // packed formats: bytes per pixel (2, 3, 4, 8 or 12), or kGroupedRow (V210: rows of whole 16-byte
+	                  // groups of six pixels -- planeShape, frame_geometry.h); else 0
 	constexpr bool rgb() const { return sampling == 0; }
 	constexpr bool words10() const { return bits == 10 && sampling != 0; }  // 10-bit YUV words (not RGBP10): the 10-bit coefficients
 	constexpr bool deep() const { return bits > 8; }  // more than the 8-bit frame holds: encodable from the f16 state
 	constexpr bool perRow() const { return sampling != 420; }  // decode and encode run a strip per row (4:2:0: per row pair)
 };
+constexpr int kGroupedRow = -1;
 inline constexpr YuvFormatInfo kFormatTable[] = {
     {kI420, "I420", 420, 3, 8, 1, 0},    {kNv12, "NV12", 420, 2, 8, 1, 0},    {kP010, "P010", 420, 2, 10, 2, 0},
     {kI010, "I010", 420, 3, 10, 2, 0},   {kYuy2, "YUY2", 422, 1, 8, 1, 2},    {kUyvy, "UYVY", 422, 1, 8, 1, 2},
@@ -516,8 +523,10 @@ inline constexpr YuvFormatInfo kFormatTable[] = {
     {kI444, "I444", 444, 3, 8, 1, 0},    {kI410, "I410", 444, 3, 10, 2, 0},   {kBgr24, "BGR24", 0, 1, 8, 1, 3},
     {kRgb24, "RGB24", 0, 1, 8, 1, 3},    {kRgbx, "RGBX", 0, 1, 8, 1, 4},      {kBgrx64, "BGRX64", 0, 1, 16, 2, 8},
     {kRgbp8, "RGBP8", 0, 3, 8, 1, 0},    {kRgbp10, "RGBP10", 0, 3, 10, 2, 0}, {kRgbp16, "RGBP16", 0, 3, 16, 2, 0},
-    {kRgbph, "RGBPH", 0, 3, 16, 2, 0},   {kRgbps, "RGBPS", 0, 3, 32, 4, 0},   {kBgr96f, "BGR96F", 0, 1, 32, 4, 12}};
-constexpr int kFormatValueEnd = kBgr96f + 1;  // (one past the largest value of the table)
+    {kRgbph, "RGBPH", 0, 3, 16, 2, 0},   {kRgbps, "RGBPS", 0, 3, 32, 4, 0},   {kBgr96f, "BGR96F", 0, 1, 32, 4, 12},
+    {kV210, "V210", 422, 1, 10, 4, kGroupedRow}, {kY210, "Y210", 422, 1, 10, 2, 4}, {kY410, "Y410", 444, 1, 10, 4, 4},
+    {kX2rgb10, "X2RGB10", 0, 1, 10, 4, 4}, {kX2bgr10, "X2BGR10", 0, 1, 10, 4, 4}};
+constexpr int kFormatValueEnd = kY410 + 1;  // (one past the largest value of the table)
 inline const YuvFormatInfo *yuvFormatInfo(int value) {  // nullptr: not in the table
 	for (const YuvFormatInfo &f : kFormatTable) {
 		if (f.value == value) return &f;
@@ -532,7 +541,7 @@ inline const YuvFormatInfo &formatInfo(int value) {
 inline const YuvFormatInfo &formatInfo(PixelFormat f) { return formatInfo(fmt(f)); }
 
 // Planes of a frame: Y, U, V / R, G, B (planar), Y and one interleaved plane u (semi-planar; v unused) or y alone (packed:
-// rows of pixelBytes x width bytes).  Chroma planes have height / 2 (4:2:0) or height rows of width / 2 (4:2:0, 4:2:2;
+// rows of pixelBytes x width bytes; V210: 16 x ceil(width / 6)).  Chroma planes have height / 2 (4:2:0) or height rows of width / 2 (4:2:0, 4:2:2;
 // interleaved: width) or width (4:4:4) samples.  Pointers address the first logical row, strides are bytes and may be
 // negative; addresses and strides are multiples of the sample size (1, 2 or 4 bytes), any alignment beyond that.
 struct YuvPlanes {

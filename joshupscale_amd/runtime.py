@@ -60,6 +60,27 @@ _FMT_PACKED = (FMT_YUY2, FMT_UYVY)
 _FMT_RGB = {FMT_BGR24: (3, np.uint8), FMT_RGB24: (3, np.uint8), FMT_RGBX: (4, np.uint8), FMT_BGRX64: (4, np.uint16),
             FMT_RGBP8: (0, np.uint8), FMT_RGBP10: (0, np.uint16), FMT_RGBP16: (0, np.uint16),
             FMT_RGBPH: (0, np.float16), FMT_RGBPS: (0, np.float32), FMT_BGR96F: (3, np.float32)}
+# Packed 10-bit (tests/packed10_reference.py), ONE array of little-endian words each: V210 uint32 [H, 4 ceil(W / 6)] (six
+# pixels in four words; the array cannot tell W), Y210 uint16 [H, 2W] (Y0 U Y1 V, value << 6), Y410 / X2RGB10 / X2BGR10
+# uint32 [H, W] (three 10-bit fields from bit 0 on: U, Y, V / B, G, R / R, G, B).  `colorspace` is ignored for the last two.
+FMT_V210, FMT_Y210, FMT_Y410, FMT_X2RGB10, FMT_X2BGR10 = 48, 49, 50, 45, 44
+_FMT_PACKED10 = (FMT_V210, FMT_Y210, FMT_Y410, FMT_X2RGB10, FMT_X2BGR10)
+
+
+def v210_row_words(width: int) -> int:
+    """32-bit words of a V210 row of ``width`` pixels: whole groups of six pixels, four words each."""
+    return 4 * ((width + 5) // 6)
+
+
+def packed10_shape(fmt: int, width: int, height: int):
+    """``(dtype, shape)`` of the one array of a packed 10-bit frame (rows without padding)."""
+    if fmt == FMT_V210:
+        return np.uint32, (height, v210_row_words(width))
+    if fmt == FMT_Y210:
+        return np.uint16, (height, 2 * width)
+    return np.uint32, (height, width)
+
+
 CS_BT601_LIMITED, CS_BT601_FULL, CS_BT709_LIMITED, CS_BT709_FULL = 0, 1, 2, 3
 
 
@@ -210,6 +231,8 @@ _HOOK_SIGS = {
                                        _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_rgb": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t, _P(C.c_void_p),
                                _P(C.c_ssize_t)]),
+    "ju_debug_packed10": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
+                                    _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_yuv_items": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_size_t, C.c_size_t, _P(C.c_void_p),
                                      _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_source": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
@@ -462,25 +485,29 @@ class Runtime:
         """``ju_enqueue_frame``: device frames only; ``synchronize`` waits."""
         _check(self._lib, self._lib.ju_enqueue_frame(self._h, C.byref(inp), C.byref(out)))
 
-    def process_yuv(self, y: np.ndarray, u: np.ndarray, v: Optional[np.ndarray] = None, fmt: int = FMT_I420,
-                    colorspace: int = CS_BT709_LIMITED, out_format: Optional[int] = None):
+    def process_yuv(self, y: np.ndarray, u: Optional[np.ndarray] = None, v: Optional[np.ndarray] = None, fmt: int = FMT_I420,
+                    colorspace: int = CS_BT709_LIMITED, out_format: Optional[int] = None, width: Optional[int] = None):
         """Host planes in, host planes out.  ``fmt`` FMT_I420 / FMT_I010: ``y, u, v``; FMT_NV12 / FMT_P010: ``y, uv``
         (``v`` None); the 10-bit formats take and return ``uint16`` planes.  ``out_format`` (default: ``fmt``):
         FMT_I420 / FMT_I010 -> ``(y, u, v)``, FMT_NV12 / FMT_P010 -> ``(y, uv)``, FMT_BGRX -> the ``[4H, 4W, 4]`` BGRX
-        frame."""
+        frame.  The packed 10-bit formats (FMT_V210 / FMT_Y210 / FMT_Y410): ``y`` is the one array of words (``u``, ``v``
+        None; FMT_V210 needs ``width``), and such an ``out_format`` returns a one-element tuple with its array."""
         out_format = fmt if out_format is None else out_format
-        planes = [y, u] if fmt in (FMT_NV12, FMT_P010) else [y, u, v]
-        inp = host_frame(fmt, planes, colorspace)
+        planes = [y] if fmt in _FMT_PACKED10 else ([y, u] if fmt in (FMT_NV12, FMT_P010) else [y, u, v])
+        inp = host_frame(fmt, planes, colorspace, width=width)
         ow, oh = self.frame_output_size()
         sample = np.uint16 if out_format in (FMT_P010, FMT_I010) else np.uint8
         if out_format == FMT_BGRX:
             res = [np.empty((oh, ow, 4), np.uint8)]
+        elif out_format in _FMT_PACKED10:
+            dt, shape = packed10_shape(out_format, ow, oh)
+            res = [np.empty(shape, dt)]
         elif out_format in (FMT_NV12, FMT_P010):
             res = [np.empty((oh, ow), sample), np.empty((oh // 2, ow), sample)]
         else:
             res = [np.empty((oh, ow), sample), np.empty((oh // 2, ow // 2), sample),
                    np.empty((oh // 2, ow // 2), sample)]
-        self.process_frame(inp, host_frame(out_format, res, colorspace))
+        self.process_frame(inp, host_frame(out_format, res, colorspace, width=ow if out_format == FMT_V210 else None))
         return res[0] if out_format == FMT_BGRX else tuple(res)
 
     def process_rgb(self, planes, fmt: int, out_format: Optional[int] = None):
@@ -496,6 +523,8 @@ class Runtime:
         elif out_format in _FMT_RGB:
             samples, dt = _FMT_RGB[out_format]
             res = [np.empty((oh, ow, samples), dt)] if samples else [np.empty((oh, ow), dt) for _ in range(3)]
+        elif out_format in (FMT_X2RGB10, FMT_X2BGR10):
+            res = [np.empty((oh, ow), np.uint32)]
         else:
             raise ValueError("process_rgb: out_format must be FMT_BGRX or an RGB format")
         self.process_frame(host_frame(fmt, planes), host_frame(out_format, res))
@@ -660,16 +689,39 @@ def _frame(fmt: int, colorspace: int, location: int, width: int, height: int, pt
     return f
 
 
-def host_frame(fmt: int, planes, colorspace: int = CS_BT709_LIMITED) -> JuFrame:
+def host_frame(fmt: int, planes, colorspace: int = CS_BT709_LIMITED, width: Optional[int] = None) -> JuFrame:
     """Describe numpy planes as a host frame.  FMT_BGRX: ``[bgrx [H, W, 4]]``; FMT_I420: ``[y [H, W], u, v
     [H/2, W/2]]``; FMT_NV12: ``[y [H, W], uv [H/2, W]]``; FMT_I010 / FMT_P010: the same shapes as ``uint16``.
     FMT_YUY2 / FMT_UYVY: ONE ``[H, 2W]`` uint8 array; FMT_I422 / FMT_I210: ``[y [H, W], u, v [H, W/2]]``; FMT_P210:
     ``[y [H, W], uv [H, W]]``; FMT_I444 / FMT_I410: ``[y, u, v [H, W]]`` (the 10-bit formats ``uint16``).
     The RGB formats: FMT_BGR24 / FMT_RGB24 ONE ``[H, W, 3]`` uint8 array, FMT_RGBX ``[H, W, 4]`` uint8, FMT_BGRX64
     ``[H, W, 4]`` uint16, FMT_BGR96F ``[H, W, 3]`` float32; FMT_RGBP8 / FMT_RGBP10 / FMT_RGBP16 / FMT_RGBPH / FMT_RGBPS
-    three ``[H, W]`` arrays ``[r, g, b]`` of uint8 / uint16 / uint16 / float16 / float32 (``colorspace`` is ignored).  Any
+    three ``[H, W]`` arrays ``[r, g, b]`` of uint8 / uint16 / uint16 / float16 / float32 (``colorspace`` is ignored).
+    Packed 10-bit, ONE array: FMT_Y410 / FMT_X2RGB10 / FMT_X2BGR10 ``[H, W]`` uint32, FMT_Y210 ``[H, 2W]`` uint16, FMT_V210
+    ``[H, 4 ceil(W / 6)]`` uint32 or a wider one whose extra columns are padding -- the array cannot tell W, so
+    ``width=W`` is required for FMT_V210 (and only there).  Any
     row stride (a ``[::-1]`` view is bottom-up; the frame's strides are the arrays' byte strides); the columns must be
     contiguous.  The arrays must outlive the call."""
+    if fmt in _FMT_PACKED10:
+        planes = list(planes)
+        if len(planes) != 1:
+            raise ValueError("a packed 10-bit frame is one array")
+        y = planes[0]
+        dt = np.dtype(np.uint16 if fmt == FMT_Y210 else np.uint32)
+        if y.dtype != dt or y.ndim != 2 or y.strides[1] != dt.itemsize:
+            raise ValueError(f"a packed 10-bit frame of this format is one 2-D {dt.name} array with contiguous columns")
+        if fmt == FMT_V210:
+            if width is None:
+                raise ValueError("a V210 frame needs width=W: its array holds whole groups of six pixels")
+            if width < 2 or width % 2 or y.shape[1] < v210_row_words(width):
+                raise ValueError("a V210 frame is [H, 4 ceil(W / 6)] uint32 (or wider: padding), W even")
+        elif fmt == FMT_Y210:
+            if y.shape[1] == 0 or y.shape[1] % 4:
+                raise ValueError("a Y210 frame is one [H, 2W] uint16 array, W even")
+            width = y.shape[1] // 2
+        else:
+            width = y.shape[1]
+        return _frame(fmt, colorspace, LOC_CPU, width, y.shape[0], [y.ctypes.data], [y.strides[0]])
     if fmt in _FMT_RGB:
         samples, dt = _FMT_RGB[fmt]
         planes = list(planes)
@@ -701,11 +753,14 @@ def device_frame(fmt: int, width: int, height: int, ptrs, strides=None,
                  colorspace: int = CS_BT709_LIMITED) -> JuFrame:
     """A device frame from raw device pointers (or torch tensors: their ``data_ptr()``); ``strides`` default to
     dense rows in bytes (BGRX 4W, Y W, I420 / I422 chroma W/2, NV12 chroma W, I444 chroma W, YUY2 / UYVY 2W; the 10-bit
-    formats twice that; RGB: W x the bytes of a packed pixel, or of a planar sample)."""
+    formats twice that; RGB: W x the bytes of a packed pixel, or of a planar sample; packed 10-bit: 4W, FMT_V210
+    16 ceil(W / 6))."""
     ptrs = [p.data_ptr() if hasattr(p, "data_ptr") else int(p) for p in ptrs]
     if strides is None and fmt in _FMT_RGB:
         samples, dt = _FMT_RGB[fmt]
         strides = [width * np.dtype(dt).itemsize * max(samples, 1)] * (1 if samples else 3)
+    if strides is None and fmt in _FMT_PACKED10:
+        strides = [4 * v210_row_words(width) if fmt == FMT_V210 else 4 * width]
     if strides is None:
         strides = {FMT_BGRX: [4 * width], FMT_I420: [width, width // 2, width // 2],
                    FMT_NV12: [width, width], FMT_P010: [2 * width, 2 * width],
