@@ -418,6 +418,46 @@ JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
 JU_API int ju_set_output_size(ju_runtime *runtime, size_t width, size_t height, int filter);
 JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height);
 
+/* ---- scene cuts: detected on the GPU, the recurrence restarted at them (docs/scene_detect.md) -----------------------------
+ * Every frame is built from the previous output warped by a flow field and from three frames of history; across a hard
+ * cut all of that belongs to another scene.  ju_reset is the remedy, but the caller has to know where the cuts are and
+ * the call waits.  The detector finds them on the GPU, in exact integers, and restarts the recurrence there without a
+ * host round trip.  Opt-in and per runtime; with the mode off (the default) every entry point behaves byte for byte as
+ * without it.  ju_reset keeps the setting.
+ *
+ * Definition (tests/scene_reference.py).  c_t: the model-size BGRX frame step t consumes -- behind decoding and the
+ * source scaler -- of W x H pixels; the X byte is ignored; N = 3 W H.  S_t = sum |c_t - c_(t-1)| over the N colour bytes,
+ * a 64-bit integer, 0 while frame t-1 is not in the detector's memory.  D_t = min(S_t, |S_t - S_(t-1)|) when frames t-1
+ * and t-2 both are, else 0 (ffmpeg scdet's score as a raw sum: the first two frames after a start never cut).
+ * cut_t = (1000 D_t >= threshold_milli N).  threshold_milli: thousandths of an 8-bit code value per byte, 1 .. 255000;
+ * 10000 is scdet's default of 10.  The detector has no predecessor after ju_create, after ju_reset and after a
+ * ju_set_scene_detect call that changes the mode; a detected cut does not clear the detector's own memory (the frame
+ * after a flash is thereby told from a second cut).
+ *
+ * JU_SCENE_REPORT: cuts are recorded, no byte of any output or of the state changes.  JU_SCENE_RESET: at a cut the
+ * step's recurrent inputs are zeroed on the GPU in front of the step -- the frame, the state and the history are those
+ * of a ju_reset called before that frame.  A flow-free model ("recurrent" 0) takes JU_SCENE_RESET as JU_SCENE_REPORT.
+ * ju_set_scene_detect waits for the stream; an unknown mode, or a threshold outside 1 .. 255000 while the mode is not
+ * off, is JU_ERR_INVALID_ARGUMENT.  The same mode again changes the threshold only.
+ * ju_get_scene_info waits for the stream (valid after ju_enqueue and multi-frame calls) and returns the most recent
+ * min(count, 64, steps seen) records, oldest first; `step` counts detector steps from 0 at the call that turned the
+ * detector on and continues across ju_reset.  A frame refused by its checks does not reach the detector.
+ * ju_get_stat: "scene_mode", "scene_frames", "scene_cuts" (cumulative, as of the steps that have completed).
+ *
+ * While the mode is not off look-ahead and group passes are not formed (a pass computes the flow of all its frames
+ * from a history a cut inside it would invalidate): ju_process_batch, ju_process_frames and ju_process_group run such
+ * a runtime's frames one by one in stream order ("lookahead_frames" / "group_frames" do not count them), and
+ * ju_prepare_batch captures nothing; ju_prepare_frames works as before and the direct device path and its graphs stay
+ * in use.  Turning the mode off restores the passes.  Not provided: a pass split at a cut. */
+enum { JU_SCENE_OFF = 0, JU_SCENE_REPORT = 1, JU_SCENE_RESET = 2 };
+typedef struct ju_scene_info {
+	uint64_t step, sad, score; /* the detector step, S_t, D_t */
+	uint32_t cut, reserved;    /* cut_t (0 / 1) */
+} ju_scene_info;
+JU_API int ju_set_scene_detect(ju_runtime *runtime, int mode, uint32_t threshold_milli);
+JU_API int ju_get_scene_detect(const ju_runtime *runtime, int *mode, uint32_t *threshold_milli);
+JU_API int ju_get_scene_info(ju_runtime *runtime, ju_scene_info *out, int count, int *written);
+
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing
  * call on the same thread. */

@@ -62,7 +62,10 @@ JU_API int ju_plan_report(ju_runtime *runtime, char *dst, size_t capacity, size_
  * same bytes, tests compare it with the product's); "resident_fault" n
  * (launch the resident tower n workgroups short: tests the fallback); "pass_rerun" 1 (a look-ahead
  * pass that completed normally is run again frame by frame, as after a resident-tower report but without the
- * fallback: the re-run's bookkeeping; no kernel misbehaves). */
+ * fallback: the re-run's bookkeeping; no kernel misbehaves); "step_rerun" 1 (the same for a single frame: ju_process
+ * and the frame-by-frame steps of the multi-frame calls submit every frame a second time, as after a resident-tower
+ * report but without the fallback; the scene detector must not run for the second submission: ju_get_stat
+ * "scene_detector_runs" counts its runs). */
 JU_API int ju_debug_set(const char *key, int value);
 
 /* The loader's e4m3 quantiser (round to nearest even, saturating at +-448), exposed so
@@ -140,6 +143,20 @@ JU_API int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_w
  * of src_width x src_height and the filter passed in `format`, with its message (JU_ERR_INVALID_ARGUMENT) or JU_OK. */
 JU_API int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_height, const void *src, size_t src_width,
     size_t src_height, int format, int colorspace, void *const planes[3], const ptrdiff_t strides[3]);
+
+/* The scene detector's kernels alone (docs/scene_detect.md; tests/scene_reference.py), on the current device (synchronous).
+ * op 0: scene_sad_kernel -- `frame`, device BGRX rows of width x height at any 4-byte-aligned address with any signed
+ * stride of at least a row (bytes, a multiple of 4), against `prev`, the dense device BGRX frame kept so far, which is
+ * rewritten with `frame`; `state`: 40 bytes of device memory, zero before the first call (the accumulator and the
+ * ticket are zero again when the call returns, word 3 is the reset flag, bytes 16 .. 23 the S the next call compares
+ * with); has_prev: bit 0 frame t-1 is in `prev`, bit 1 frame t-2 went before it; *record receives the decision (step 0).
+ * op 1: scene_clear_kernel -- `state` is the device flag word; if it is not 0, clear_a[0 .. a_bytes) and
+ * clear_b[0 .. b_bytes) become 0, any alignment; the other arguments are ignored.  op 2: no device and no buffers --
+ * the refusals of ju_set_scene_detect for the mode passed in has_prev and threshold_milli, with their message
+ * (JU_ERR_INVALID_ARGUMENT) or JU_OK. */
+JU_API int ju_debug_scene(int op, const void *frame, ptrdiff_t stride, size_t width, size_t height, void *prev, void *state,
+    int has_prev, uint32_t threshold_milli, int reset_mode, ju_scene_info *record, void *clear_a, size_t a_bytes,
+    void *clear_b, size_t b_bytes);
 
 /* The scalers with a filter argument (docs/source_stage.md "Filters"; tests/scale_filter_reference.py); `filter` is a
  * JU_SCALE_* value.  op 0: the 8-bit scaler -- buffers, sizes and strides as ju_debug_source op 0.  op 1: the state

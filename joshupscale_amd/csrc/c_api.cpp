@@ -306,6 +306,23 @@ int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height)
 	return guarded([&] { engineOf(const_cast<ju_runtime *>(runtime)).outputSize(width, height); });
 }
 
+int ju_set_scene_detect(ju_runtime *runtime, int mode, uint32_t threshold_milli) {
+	return guarded([&] { engineOf(runtime).setSceneDetect(mode, threshold_milli); });
+}
+
+int ju_get_scene_detect(const ju_runtime *runtime, int *mode, uint32_t *threshold_milli) {
+	return guarded([&] { engineOf(const_cast<ju_runtime *>(runtime)).sceneDetect(mode, threshold_milli); });
+}
+
+int ju_get_scene_info(ju_runtime *runtime, ju_scene_info *out, int count, int *written) {
+	return guarded([&] {
+		static_assert(sizeof(ju_scene_info) == sizeof(ju::SceneRecord), "ju_scene_info is the kernel's record");
+		if (written) *written = 0;
+		const int n = engineOf(runtime).sceneInfo(reinterpret_cast<ju::SceneRecord *>(out), count);
+		if (written) *written = n;
+	});
+}
+
 int ju_reset(ju_runtime *runtime) {
 	return guarded([&] { engineOf(runtime).reset(); });
 }
@@ -410,6 +427,9 @@ int ju_time_steps(ju_runtime *runtime, const char *tag, int iters, double *ms_pe
 int ju_get_stat(const ju_runtime *runtime, const char *key, double *value) {
 	return guarded([&] {
 		if (key == nullptr || value == nullptr) throw std::invalid_argument("ju_get_stat: null argument");
+#ifndef JU_TEST_HOOKS  // a counter of the test flavour (joshupscale_amd_test.h, "step_rerun")
+		if (std::strcmp(key, "scene_detector_runs") == 0) throw std::invalid_argument("unknown stat scene_detector_runs");
+#endif
 		*value = engineOf(const_cast<ju_runtime *>(runtime)).stat(key);
 	});
 }
@@ -424,6 +444,7 @@ int ju_debug_set(const char *key, int value) {
 		else if (k == "res_block_plain") ju::setResBlockPlain(value);
 		else if (k == "fp8_block_form") ju::setFp8BlockForm(value);
 		else if (k == "pass_rerun") ju::setPassRerun(value);
+		else if (k == "step_rerun") ju::setStepRerun(value);
 		else throw std::invalid_argument("unknown debug key " + k);
 	});
 }
@@ -667,6 +688,45 @@ int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t d
 			scale.scaleState(src, static_cast<std::uint16_t *>(dst), nullptr);
 		}
 		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_scene(int op, const void *frame, ptrdiff_t stride, size_t width, size_t height, void *prev, void *state,
+    int has_prev, uint32_t threshold_milli, int reset_mode, ju_scene_info *record, void *clear_a, size_t a_bytes,
+    void *clear_b, size_t b_bytes) {
+	return guarded([&] {
+		if (op == 2) {  // the refusals of ju_set_scene_detect alone: no device
+			const std::string problem = ju::sceneDetectProblem(has_prev, threshold_milli);  // (has_prev: the mode)
+			if (!problem.empty()) throw std::invalid_argument("ju_set_scene_detect: " + problem);
+			return;
+		}
+		if (op == 1) {  // scene_clear_kernel alone; `state`: the device flag word
+			ju::launchSceneClear(static_cast<const unsigned *>(state), clear_a, a_bytes, clear_b, b_bytes, nullptr);
+			JU_HIP(hipStreamSynchronize(nullptr));
+			return;
+		}
+		if (op != 0) throw std::invalid_argument("ju_debug_scene: op must be 0, 1 or 2");
+		if (record == nullptr) throw std::invalid_argument("ju_debug_scene: record is NULL");
+		ju::PinnedWords ring(sizeof(ju::SceneRecord) * (ju::kSceneRing + 1));
+		ju::SceneSadLaunch q;
+		q.src = static_cast<const std::uint8_t *>(frame);
+		q.srcStride = stride;
+		q.width = static_cast<int>(std::min<size_t>(width, 1u << 20));
+		q.height = static_cast<int>(std::min<size_t>(height, 1u << 20));
+		q.prev = static_cast<std::uint32_t *>(prev);
+		q.state = static_cast<ju::SceneState *>(state);
+		q.ring = reinterpret_cast<ju::SceneRecord *>(ring.device());
+		q.hasPrev = has_prev;
+		q.thresholdMilli = threshold_milli;
+		q.resetMode = reset_mode != 0;
+		ju::launchSceneSad(q, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+		const auto *r = reinterpret_cast<const volatile ju::SceneRecord *>(ring.host());
+		record->step = r->step;
+		record->sad = r->sad;
+		record->score = r->score;
+		record->cut = r->cut;
+		record->reserved = 0;
 	});
 }
 

@@ -1366,6 +1366,7 @@ void Engine::reset() {
 	}
 	m_Stream.synchronize();
 	m_Idx = 0;
+	m_SceneSeen = 0;  // the scene detector has no predecessor after a reset; its setting and its step count stay
 }
 
 FrameSize Engine::frameSize() const {
@@ -1547,7 +1548,13 @@ void Engine::submit(const Frame &in, const Frame &out) {
 	} else {
 		bindStaging();
 		stageIn(in);
+		// With the scene detector on, what stageOut would refuse behind the step is refused here, in front of the
+		// detector: a refused frame must not reach it (it would overwrite the kept frame, count a step and, at a cut,
+		// clear the inputs of a step that then does not happen).  Off: as ju_process always behaved.  (A graphics
+		// resource's own extent is known only when it is mapped, in stageOut.)
+		if (m_SceneMode != 0) checkFrame(anyOf(out), false, "processImage");
 	}
+	sceneStep();
 	{
 		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
 		runProgram();
@@ -1574,18 +1581,33 @@ void Engine::enqueue(const AnyFrame &in, const AnyFrame &out) {
 	submitAny(in, out);
 }
 
+namespace {
+std::atomic<int> g_StepRerun{0};
+}  // namespace
+void setStepRerun(int on) { g_StepRerun = on; }
+
 void Engine::runSynchronous(const AnyFrame &in, const AnyFrame &out) {
 	submitAny(in, out);
 	m_Stream.synchronizeSpin(m_SpinUs);
-	if (const unsigned code = takeResidentError()) {
+	const unsigned code = takeResidentError();
+	if (code || g_StepRerun.load(std::memory_order_relaxed)) {
 		// the frame's inputs (previous state, frame history) are intact: the step only
 		// wrote the other half of the ping-pong -- run it again on the per-layer path
 		// (submit() flipped m_Idx; the re-run needs the same binding set again.  If the
 		// fallback or the re-run throws, the failed frame must not count as a step either.)
 		m_Idx ^= 1;
 		if (sourceStage()) --m_SourceFrames;  // (submitFrame counts the frame again)
-		fallbackToLayers(code);
-		submitAny(in, out);
+		if (code) fallbackToLayers(code);  // (else the debug switch: the frame was sound)
+		// the scene detector ran with the first submission: its decision stands, the kept frame is this frame already
+		// and, after a cut, the cleared inputs are still in place (the step wrote the other half only)
+		m_SceneRerun = true;
+		try {
+			submitAny(in, out);
+		} catch (...) {
+			m_SceneRerun = false;
+			throw;
+		}
+		m_SceneRerun = false;
 		m_Stream.synchronize();
 	} else {
 		maybeRestoreResident();
@@ -1837,6 +1859,18 @@ double Engine::stat(const std::string &key) const {
 	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
+	if (key == "scene_mode") return static_cast<double>(m_SceneMode);
+	// (the detector's own counters, as of the steps that have completed: the decision writes them to host-mapped memory)
+	if (key == "scene_frames" || key == "scene_cuts") {
+		const bool cuts = key == "scene_cuts";
+		std::uint64_t n = cuts ? m_SceneCutsBase : m_SceneFramesBase;
+		if (const volatile unsigned *w = m_SceneRing.host()) {
+			const auto *totals = reinterpret_cast<const volatile SceneRecord *>(w) + kSceneRing;
+			n += cuts ? totals->sad : totals->step;
+		}
+		return static_cast<double>(n);
+	}
+	if (key == "scene_detector_runs") return static_cast<double>(m_SceneRuns);  // launches of the detector (tests: once per step)
 	if (key == "launches_per_frame") return static_cast<double>(m_Program[0].size());
 	if (key == "tower_variant") return static_cast<double>(towerVariant());  // (developer switch, tests)
 	if (key == "direct_graphs") {

@@ -35,6 +35,9 @@ struct FrameSize {
 // Test flavour only (ju_debug_set "pass_rerun"): a look-ahead pass that completed normally is treated as one that must
 // be run again -- binding set and counters restored, its frames one by one, without the fallback to the per-block kernels.
 void setPassRerun(int on);
+// Test flavour only (ju_debug_set "step_rerun"): process() treats every frame that completed normally as one whose
+// resident tower reported -- binding set restored, the frame submitted again -- without the fallback to the per-block kernels.
+void setStepRerun(int on);
 
 class Engine {
 public:
@@ -105,6 +108,13 @@ public:
 	void setOutputSize(std::size_t width, std::size_t height, int filter);
 	void outputSize(std::size_t *width, std::size_t *height) const;
 	bool sourceStage() const { return m_SrcScale.set() || m_MaskW != 0 || m_OutScale.set(); }
+	// The scene detector (docs/scene_detect.md; "Scene detector" below).  setSceneDetect: mode 0 off / 1 report / 2 reset
+	// (JU_SCENE_*), thresholdMilli 1 .. 255000 while the mode is not off; waits for the stream; a call that changes the
+	// mode starts the detector over (no predecessor, step 0).  reset() keeps the setting and forgets the predecessors.
+	void setSceneDetect(int mode, std::uint32_t thresholdMilli);
+	void sceneDetect(int *mode, std::uint32_t *thresholdMilli) const;
+	// the most recent min(count, 64, steps seen) records, oldest first, after waiting for the stream; returns how many
+	int sceneInfo(SceneRecord *out, int count);
 
 	FrameSize frameSize() const;
 	int device() const { return m_Device; }
@@ -218,6 +228,20 @@ private:
 	Scaler m_OutScale;
 	DeviceBuffer m_OutScaled8, m_OutScaled16, m_OutYuvStage, m_OutRawStage;
 	void stageOutScaled(const AnyFrame &out);
+	// Scene detector: two eager launches on m_Stream in front of runProgram(), outside the chain lock and never captured
+	// (sceneStep: submit and submitFrame, once m_IO.in holds the frame the program will read).  m_ScenePrev: the frame
+	// compared against; m_SceneDev: the SceneState; m_SceneRing: kSceneRing records + the totals, host-mapped.
+	// m_SceneSeen: steps since the last start (decides the "has predecessor" bits); m_SceneSteps: steps since the mode was
+	// turned on (the record's `step`, the ring slot).  m_SceneRerun: set around the re-run of a frame (runSynchronous) --
+	// THE one place that keeps a step from running the detector twice; m_SceneRuns counts the runs ("scene_detector_runs").
+	int m_SceneMode = 0;
+	std::uint32_t m_SceneThreshold = 0;
+	DeviceBuffer m_ScenePrev, m_SceneDev;
+	PinnedWords m_SceneRing;
+	std::uint64_t m_SceneSeen = 0, m_SceneSteps = 0, m_SceneRuns = 0;
+	std::uint64_t m_SceneFramesBase = 0, m_SceneCutsBase = 0;  // "scene_frames" / "scene_cuts" of earlier on-periods
+	bool m_SceneRerun = false;
+	void sceneStep();
 	// Everything a frame call can refuse, before anything is launched; `who` names the entry point in the message.
 	// declaredSize (ju_process_group): a NULL pointer is refused first and by name, and a graphics resource's DECLARED
 	// size counts too -- otherwise the texture's own extent is checked when it is mapped, behind other members' launches.

@@ -386,6 +386,7 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 	} else {
 		stageIn(in.bgrx);
 	}
+	sceneStep();  // (the decoded, scaled frame: what the program reads)
 	{
 		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
 		runProgram();
@@ -410,6 +411,97 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 		stageOut(out.bgrx, fs.outputWidth, fs.outputHeight, m_OutStage.as<std::uint8_t>(), m_RawStage.as<std::uint8_t>());
 	}
 	m_Idx ^= 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Scene detector (docs/scene_detect.md).  Two eager launches per step in front of the step's program: the sum of
+// absolute differences against the kept frame with the decision in its last workgroup, and the conditional clear of
+// what the program is about to read as its recurrent inputs -- m_State[m_Idx] and m_Packed[m_Idx], the half reset()
+// would have left zero for this step.  The binding set is NOT reset: the two sets' programs differ in bindings only.
+// The host learns of a cut only when it asks (sceneInfo); nothing in the frame path waits for the decision.
+// ---------------------------------------------------------------------------------------------------------------
+void Engine::setSceneDetect(int mode, std::uint32_t thresholdMilli) {
+	const std::string problem = sceneDetectProblem(mode, thresholdMilli);
+	if (!problem.empty()) throw std::invalid_argument("ju_set_scene_detect: " + problem);
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();
+	if (mode == m_SceneMode) {  // the same mode: the threshold alone; the detector's memory stays
+		if (mode != 0) m_SceneThreshold = thresholdMilli;
+		return;
+	}
+	if (m_SceneRing.host()) {  // the counters of the period that ends here
+		const auto *totals = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host()) + kSceneRing;
+		m_SceneFramesBase += totals->step;
+		m_SceneCutsBase += totals->sad;
+	}
+	// a start: fresh (zeroed) memory, no predecessor, step 0.  No captured graph is bound to any of these buffers.
+	m_ScenePrev = DeviceBuffer();
+	m_SceneDev = DeviceBuffer();
+	m_SceneRing = PinnedWords();
+	if (mode != 0) {
+		const FrameSize fs = frameSize();
+		m_ScenePrev = DeviceBuffer(fs.inputWidth * fs.inputHeight * 4);
+		m_SceneDev = DeviceBuffer(sizeof(SceneState));
+		m_SceneRing = PinnedWords(sizeof(SceneRecord) * (kSceneRing + 1));
+	}
+	m_SceneMode = mode;
+	m_SceneThreshold = mode != 0 ? thresholdMilli : 0;
+	m_SceneSeen = 0;
+	m_SceneSteps = 0;
+}
+
+void Engine::sceneDetect(int *mode, std::uint32_t *thresholdMilli) const {
+	if (mode) *mode = m_SceneMode;
+	if (thresholdMilli) *thresholdMilli = m_SceneThreshold;
+}
+
+int Engine::sceneInfo(SceneRecord *out, int count) {
+	if (count < 0 || (count > 0 && out == nullptr)) throw std::invalid_argument("ju_get_scene_info: NULL records or a negative count");
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();
+	if (m_SceneMode == 0 || m_SceneRing.host() == nullptr) return 0;
+	const std::uint64_t have = std::min<std::uint64_t>(m_SceneSteps, kSceneRing);
+	const int n = static_cast<int>(std::min<std::uint64_t>(have, static_cast<std::uint64_t>(count)));
+	const auto *ring = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host());
+	for (int k = 0; k < n; ++k) {
+		const std::uint64_t step = m_SceneSteps - static_cast<std::uint64_t>(n) + static_cast<std::uint64_t>(k);
+		const volatile SceneRecord &r = ring[step % kSceneRing];
+		out[k].step = r.step;
+		out[k].sad = r.sad;
+		out[k].score = r.score;
+		out[k].cut = r.cut;
+		out[k].reserved = 0;
+	}
+	return n;
+}
+
+// One detector step on the frame m_IO.in holds when the program runs.  Called by submit / submitFrame for every step
+// exactly once: the re-run of a frame (runSynchronous) comes through here with m_SceneRerun set and launches nothing.
+void Engine::sceneStep() {
+	if (m_SceneMode == 0 || m_SceneRerun) return;
+	const FrameSize fs = frameSize();
+	SceneSadLaunch q;
+	q.src = m_IO.in;
+	q.srcStride = m_IO.inStride;
+	q.width = static_cast<int>(fs.inputWidth);
+	q.height = static_cast<int>(fs.inputHeight);
+	q.prev = m_ScenePrev.as<std::uint32_t>();
+	q.state = m_SceneDev.as<SceneState>();
+	q.ring = reinterpret_cast<SceneRecord *>(m_SceneRing.device());
+	q.slot = static_cast<int>(m_SceneSteps % kSceneRing);
+	q.step = m_SceneSteps;
+	q.hasPrev = (m_SceneSeen >= 1 ? 1 : 0) | (m_SceneSeen >= 2 ? 2 : 0);
+	q.thresholdMilli = m_SceneThreshold;
+	// (a flow-free model has no recurrent input to clear: JU_SCENE_RESET reports)
+	q.resetMode = m_SceneMode == 2 && m_Config.recurrent();
+	launchSceneSad(q, m_Stream);
+	if (q.resetMode) {
+		launchSceneClear(&q.state->resetNow, m_State[m_Idx].get(), m_State[m_Idx].bytes(), m_Packed[m_Idx].get(),
+		    m_Packed[m_Idx].bytes(), m_Stream);
+	}
+	++m_SceneSeen;
+	++m_SceneSteps;
+	++m_SceneRuns;
 }
 
 }  // namespace ju

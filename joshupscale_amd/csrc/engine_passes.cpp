@@ -176,6 +176,8 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 // A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
 	if (sourceStage()) return false;  // (scaled / masked frames run one by one through submitFrame)
+	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate)
+	if (m_SceneMode != 0) return false;
 	const FrameSize fs = frameSize();
 	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align) {
 		if (a.yuv) {

@@ -658,6 +658,42 @@ void launchMaskBlend(std::uint8_t *gen, std::ptrdiff_t genStride, int outW, int 
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).
 void launchSignalHost(unsigned *word, hipStream_t stream);
 
+// ---- scene-cut detection (scene_kernels.hip; docs/scene_detect.md) ----------------------------------------------------
+// SceneState: the detector's device memory, zero at a start.  acc / ticket: the sum being built and the workgroups
+// that have added to it -- both back at zero when a launch ends.  resetNow: what scene_clear_kernel obeys.
+struct SceneState {
+	unsigned long long acc;
+	unsigned ticket, resetNow;
+	unsigned long long prevSad, frames, cuts;
+};
+// One decision, in host-mapped memory: a ring of kSceneRing records, and behind them ONE more whose step / sad hold the
+// cumulative frames / cuts of the runtime (kSceneRing + 1 records in all).
+struct SceneRecord {
+	unsigned long long step, sad, score;
+	unsigned cut, reserved;
+};
+constexpr int kSceneRing = 64;
+constexpr int kSceneAxisMax = 1 << 15;
+struct SceneSadLaunch {
+	const std::uint8_t *src = nullptr;  // BGRX rows, 4-byte aligned, any signed stride of at least a row
+	std::ptrdiff_t srcStride = 0;
+	int width = 0, height = 0;
+	std::uint32_t *prev = nullptr;  // dense width x height BGRX: read as c_{t-1}, rewritten as c_t
+	SceneState *state = nullptr;
+	SceneRecord *ring = nullptr;  // device address of the host-mapped records
+	int slot = 0;
+	std::uint64_t step = 0;
+	int hasPrev = 0;  // bit 0: frame t-1 is in the detector's memory, bit 1: frame t-2 is
+	unsigned thresholdMilli = 0;
+	bool resetMode = false;  // a cut raises SceneState::resetNow
+};
+void launchSceneSad(const SceneSadLaunch &q, hipStream_t stream);
+// The refusals of ju_set_scene_detect as one message ("" when mode and threshold are fine): mode 0 .. 2, and while the
+// mode is not off a threshold of 1 .. 255000 thousandths of a code value
+std::string sceneDetectProblem(int mode, std::uint32_t thresholdMilli);
+// if (*flag) a[0 .. aBytes) = b[0 .. bBytes) = 0: any alignment; `flag` is read by every workgroup once
+void launchSceneClear(const unsigned *flag, void *a, std::size_t aBytes, void *b, std::size_t bBytes, hipStream_t stream);
+
 // max |x| over n 16-bit elements, atomically folded into *out as the bit pattern of a
 // non-negative float (the caller zeroes it per frame).  Calibration mode only.
 void launchAbsMax(DType dt, const void *in, std::size_t n, unsigned *out, hipStream_t stream);

@@ -1,0 +1,180 @@
+// Scene-cut detection on the GPU (docs/scene_detect.md; tests/scene_reference.py is the definition).
+//
+// scene_sad_kernel: S_t = sum |c_t - c_{t-1}| over the B, G and R bytes of the model-size BGRX frame the step consumes,
+// against the kept previous frame, which it overwrites with c_t in the same pass.  Per-thread u32 partials -> wave sum ->
+// workgroup sum -> ONE 64-bit integer atomic add per workgroup at agent scope: integer sums do not depend on the order
+// of arrival, so S_t is bit-reproducible.  The workgroup that draws the last ticket takes the decision (release in
+// every workgroup before its ticket, acquire in the last one behind it; no workgroup ever waits for another):
+// D_t = min(S_t, |S_t - S_{t-1}|), cut_t = 1000 D_t >= threshold_milli N, the record into the host-mapped ring, the
+// device flag reset_now, and the accumulator and the ticket back to zero for the next launch.
+//
+// scene_clear_kernel: launched behind it over the recurrent inputs of the step (the half of the state and of the frame
+// history its program reads).  Every workgroup loads reset_now once and returns if it is 0; otherwise zeros, written as
+// 16-byte vector stores with byte stores for an unaligned head and tail.  The decision never visits the host.
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+
+#include "kernel_common.h"
+#include "kernels.h"
+
+namespace ju {
+
+namespace {
+
+constexpr int kSadThreads = 256;
+// pixels per thread: 4 x 765 per thread and 1024 x 765 per workgroup stay far inside 32 bits
+constexpr int kSadPerThread = 4;
+constexpr int kSadPerGroup = kSadThreads * kSadPerThread;
+
+__global__ __launch_bounds__(kSadThreads) void scene_sad_kernel(const std::uint8_t *__restrict__ src, long long srcStride,
+    int W, long long pixels, std::uint32_t *__restrict__ prev, SceneState *st, SceneRecord *ring, int slot,
+    unsigned long long step, int hasPrev, unsigned thresholdMilli, int resetMode) {
+	__shared__ unsigned waveSums[kSadThreads / 64];
+	// (pixel indices in 32 bits: the launcher admits at most 2^15 x 2^15 = 2^30 pixels, so one 32-bit division per pixel)
+	const unsigned base = blockIdx.x * static_cast<unsigned>(kSadPerGroup) + threadIdx.x;
+	const unsigned width = static_cast<unsigned>(W), count = static_cast<unsigned>(pixels);
+	unsigned partial = 0;
+#pragma unroll
+	for (int k = 0; k < kSadPerThread; ++k) {
+		const unsigned i = base + static_cast<unsigned>(k * kSadThreads);
+		if (i < count) {
+			const unsigned row = i / width, x = i - row * width;
+			const unsigned cur = *reinterpret_cast<const std::uint32_t *>(src + static_cast<long long>(row) * srcStride + x * 4u);
+			const unsigned old = prev[i];
+			prev[i] = cur;
+			// (B, G, R are the three low bytes of the little-endian word; X is not compared)
+			partial = __builtin_amdgcn_sad_u8(cur & 0x00ffffffu, old & 0x00ffffffu, partial);
+		}
+	}
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) partial += __shfl_down(partial, off, 64);
+	if ((threadIdx.x & 63) == 0) waveSums[threadIdx.x >> 6] = partial;
+	__syncthreads();
+	if (threadIdx.x != 0) return;
+	unsigned long long groupSum = 0;
+#pragma unroll
+	for (int w = 0; w < kSadThreads / 64; ++w) groupSum += waveSums[w];
+	__hip_atomic_fetch_add(&st->acc, groupSum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	// publish the add before the ticket (fence, then its wait, then the ticket: in that order)
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	const unsigned ticket = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	if (ticket != gridDim.x - 1) return;
+	// ---- the last workgroup of the launch: the decision ----
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	// read the sum and re-arm the accumulator in one atomic; then the ticket
+	unsigned long long S = __hip_atomic_exchange(&st->acc, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	__hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	if (!(hasPrev & 1)) S = 0;  // no predecessor: what the kept frame held is not a frame of this stream
+	unsigned long long D = 0;
+	if ((hasPrev & 3) == 3) {
+		const unsigned long long before = st->prevSad;
+		const unsigned long long delta = S > before ? S - before : before - S;
+		D = S < delta ? S : delta;
+	}
+	const unsigned long long N = 3ull * static_cast<unsigned long long>(pixels);
+	const unsigned cut = 1000ull * D >= static_cast<unsigned long long>(thresholdMilli) * N ? 1u : 0u;
+	st->prevSad = S;
+	st->frames += 1;
+	st->cuts += cut;
+	st->resetNow = (cut && resetMode) ? 1u : 0u;
+	SceneRecord *r = ring + slot;
+	__hip_atomic_store(&r->step, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&r->sad, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&r->score, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&r->cut, cut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	// the cumulative counters, behind the ring's 64 records (ju_get_stat reads them without a synchronisation)
+	SceneRecord *totals = ring + kSceneRing;
+	__hip_atomic_store(&totals->step, st->frames, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&totals->sad, st->cuts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+constexpr int kClearThreads = 256;
+constexpr int kClearVecsPerThread = 4;
+constexpr long long kClearPerGroup = static_cast<long long>(kClearThreads) * kClearVecsPerThread * 16;
+
+// bytes [0, n) of `p` -> 0 for the part of it this workgroup owns: chunk `chunk` of kClearPerGroup bytes, counted
+// from the first 16-byte boundary at or behind p; chunk 0 also takes the bytes in front of that boundary
+__device__ __forceinline__ void clearChunk(std::uint8_t *p, long long n, long long chunk) {
+	long long head = static_cast<long long>((16 - (reinterpret_cast<std::uintptr_t>(p) & 15)) & 15);
+	if (head > n) head = n;
+	if (chunk == 0 && static_cast<long long>(threadIdx.x) < head) p[threadIdx.x] = 0;
+	const long long vecs = (n - head) / 16;
+	uint4 *v = reinterpret_cast<uint4 *>(p + head);
+	const long long first = chunk * (kClearPerGroup / 16);
+#pragma unroll
+	for (int k = 0; k < kClearVecsPerThread; ++k) {
+		const long long i = first + static_cast<long long>(k) * kClearThreads + threadIdx.x;
+		if (i < vecs) v[i] = make_uint4(0u, 0u, 0u, 0u);
+	}
+	// the tail behind the last whole vector, by the workgroup that owns the end of the buffer
+	const long long tailAt = head + vecs * 16, tail = n - tailAt;
+	const long long lastChunk = vecs == 0 ? 0 : (vecs - 1) / (kClearPerGroup / 16);
+	if (chunk == lastChunk && static_cast<long long>(threadIdx.x) < tail) p[tailAt + threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(kClearThreads) void scene_clear_kernel(const unsigned *__restrict__ flag, std::uint8_t *a,
+    long long aBytes, int aChunks, std::uint8_t *b, long long bBytes) {
+	if (*flag == 0) return;
+	const int g = static_cast<int>(blockIdx.x);
+	if (g < aChunks) {
+		clearChunk(a, aBytes, g);
+	} else {
+		clearChunk(b, bBytes, g - aChunks);
+	}
+}
+
+int clearChunks(std::size_t bytes) {
+	// (15 bytes of head at most; one chunk more than the vectors need never hurts: its stores are bounds-checked)
+	return bytes == 0 ? 0 : static_cast<int>((bytes + static_cast<std::size_t>(kClearPerGroup) - 1) / static_cast<std::size_t>(kClearPerGroup));
+}
+
+}  // namespace
+
+std::string sceneDetectProblem(int mode, std::uint32_t thresholdMilli) {
+	if (mode < 0 || mode > 2) {
+		return "mode must be JU_SCENE_OFF (0), JU_SCENE_REPORT (1) or JU_SCENE_RESET (2), got " + std::to_string(mode);
+	}
+	if (mode != 0 && (thresholdMilli < 1 || thresholdMilli > 255000)) {
+		return "threshold_milli must be 1 .. 255000, got " + std::to_string(thresholdMilli);
+	}
+	return "";
+}
+
+void launchSceneSad(const SceneSadLaunch &q, hipStream_t stream) {
+	if (q.src == nullptr || q.prev == nullptr || q.state == nullptr || q.ring == nullptr || q.width < 1 || q.height < 1 ||
+	    q.width > kSceneAxisMax || q.height > kSceneAxisMax) {
+		throw std::invalid_argument("scene_sad: null buffer or a size outside 1 .. " + std::to_string(kSceneAxisMax));
+	}
+	if (reinterpret_cast<std::uintptr_t>(q.src) % 4 != 0 || q.srcStride % 4 != 0) {
+		throw std::invalid_argument("scene_sad: the frame and its stride must be 4-byte aligned");
+	}
+	const auto row = static_cast<std::ptrdiff_t>(q.width) * 4;
+	if (q.srcStride > -row && q.srcStride < row) throw std::invalid_argument("scene_sad: |stride| smaller than a row");
+	if (q.slot < 0 || q.slot >= kSceneRing) throw std::invalid_argument("scene_sad: ring slot outside 0 .. 63");
+	const long long pixels = static_cast<long long>(q.width) * q.height;
+	const unsigned groups = static_cast<unsigned>((pixels + kSadPerGroup - 1) / kSadPerGroup);
+	hipLaunchKernelGGL(scene_sad_kernel, dim3(groups), dim3(kSadThreads), 0, stream, q.src, static_cast<long long>(q.srcStride),
+	    q.width, pixels, q.prev, q.state, q.ring, q.slot, static_cast<unsigned long long>(q.step), q.hasPrev, q.thresholdMilli,
+	    q.resetMode ? 1 : 0);
+	hipCheckLaunch("scene_sad");
+}
+
+void launchSceneClear(const unsigned *flag, void *a, std::size_t aBytes, void *b, std::size_t bBytes, hipStream_t stream) {
+	if (flag == nullptr || (a == nullptr && aBytes != 0) || (b == nullptr && bBytes != 0)) {
+		throw std::invalid_argument("scene_clear: null buffer");
+	}
+	const int aChunks = clearChunks(aBytes), bChunks = clearChunks(bBytes);
+	if (aChunks + bChunks == 0) return;
+	hipLaunchKernelGGL(scene_clear_kernel, dim3(static_cast<unsigned>(aChunks + bChunks)), dim3(kClearThreads), 0, stream, flag,
+	    static_cast<std::uint8_t *>(a), static_cast<long long>(aBytes), aChunks, static_cast<std::uint8_t *>(b),
+	    static_cast<long long>(bBytes));
+	hipCheckLaunch("scene_clear");
+}
+
+}  // namespace ju

@@ -162,6 +162,16 @@ class JoshUpscaleError(RuntimeError):
         self.message = message
 
 
+class JuSceneInfo(C.Structure):
+    """``ju_scene_info``: one decision of the scene detector (docs/scene_detect.md)."""
+    _fields_ = [("step", C.c_uint64), ("sad", C.c_uint64), ("score", C.c_uint64), ("cut", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+SCENE_OFF, SCENE_REPORT, SCENE_RESET = 0, 1, 2
+SCENE_RING = 64
+
+
 def hooks_default() -> bool:
     """``JU_TEST_HOOKS=1`` (set by tests/conftest.py and the developer tools): the process works
     through libJoshUpscale_test.so.  Unset -- every caller of the product -- it is the product library."""
@@ -198,6 +208,9 @@ _PRODUCT_SIGS = {
     "ju_enqueue_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
     "ju_get_size": (C.c_int, [C.c_void_p] + [_P(C.c_size_t)] * 4),
     "ju_reset": (C.c_int, [C.c_void_p]),
+    "ju_set_scene_detect": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "ju_get_scene_detect": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_uint32)]),
+    "ju_get_scene_info": (C.c_int, [C.c_void_p, _P(JuSceneInfo), C.c_int, _P(C.c_int)]),
     "ju_set_source_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_get_source_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
@@ -239,6 +252,8 @@ _HOOK_SIGS = {
                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
     "ju_debug_output": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                   C.c_int, _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_scene": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_uint32, C.c_int, _P(JuSceneInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "ju_debug_scale": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
@@ -395,6 +410,32 @@ class Runtime:
 
     def reset(self) -> None:
         _check(self._lib, self._lib.ju_reset(self._h))
+
+    # -- the scene detector (docs/scene_detect.md) --------------------------------
+    def set_scene_detect(self, mode: int, threshold_milli: int = 10000) -> None:
+        """``ju_set_scene_detect``: ``SCENE_OFF``, ``SCENE_REPORT`` (record cuts) or ``SCENE_RESET`` (and restart the
+        recurrence at them, on the GPU); ``threshold_milli`` in thousandths of a code value per byte, 1 .. 255000
+        (10000 = ffmpeg scdet's default).  An unknown mode or a threshold out of range raises
+        :class:`JoshUpscaleError` with the C layer's message."""
+        mode, threshold_milli = int(mode), int(threshold_milli)
+        if not 0 <= threshold_milli < 2 ** 32:
+            raise ValueError("threshold_milli must fit 32 bits")
+        _check(self._lib, self._lib.ju_set_scene_detect(self._h, mode, threshold_milli))
+
+    def get_scene_detect(self) -> Tuple[int, int]:
+        """``ju_get_scene_detect``: ``(mode, threshold_milli)``; the threshold is 0 while the mode is off."""
+        mode, thr = C.c_int(), C.c_uint32()
+        _check(self._lib, self._lib.ju_get_scene_detect(self._h, C.byref(mode), C.byref(thr)))
+        return mode.value, thr.value
+
+    def scene_info(self, count: int = SCENE_RING) -> list:
+        """``ju_get_scene_info``: waits for the stream; the most recent ``min(count, 64, steps seen)`` decisions, oldest
+        first, as dicts ``{"step", "sad", "score", "cut"}``."""
+        count = max(0, int(count))
+        recs = (JuSceneInfo * max(count, 1))()
+        got = C.c_int()
+        _check(self._lib, self._lib.ju_get_scene_info(self._h, recs, count, C.byref(got)))
+        return [{"step": r.step, "sad": r.sad, "score": r.score, "cut": int(r.cut)} for r in recs[:got.value]]
 
     # -- the source stage (docs/source_stage.md) ----------------------------------
     def set_source_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
@@ -578,7 +619,7 @@ class Runtime:
         """``ju_get_stat``: "graph_replays", "eager_runs", "direct_graphs",
         "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "output_select", "lookahead_frames",
         "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames",
-        "output_scaled", "source_filter", "output_filter"."""
+        "output_scaled", "source_filter", "output_filter", "scene_mode", "scene_frames", "scene_cuts"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
