@@ -170,6 +170,21 @@ JU_API int ju_debug_scene(int op, const void *frame, ptrdiff_t stride, size_t wi
 JU_API int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height,
     const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height, int *start, int *count, int16_t *taps);
 
+/* The temporal output filter alone (launchTemporalFilter: zero_words_kernel, temporal_reduce_kernel, temporal_blend_kernel;
+ * tests/temporal_reference.py), on caller-supplied device buffers, on the current device (synchronous).  `state`: the dense
+ * f16 tensor [4 height][4 width][4] (8-byte aligned), rewritten in place; `pre_warp`: the same shape, read only; `out`: BGRX
+ * rows of 4 width x 4 height at a 4-byte-aligned address with any signed stride that is a multiple of 4; `sums`: the six
+ * words of launchFrameSums on the device (4-byte aligned), or NULL for a model without normalize_brightness; width and
+ * height are the LR frame's, 1 .. 8192.  strength, threshold, gain and window are held to the model loader's bounds with
+ * its wording; `flags` are the mode bits of the model file: 1 L2, 2 limit, 4 luma.  The hook allocates the accumulator
+ * scratch itself -- the words the filter uses primed with ones, acc_capacity - temporalAccWords() further words with zeros --
+ * and, where `acc` is not NULL, copies acc_capacity words (at least temporalAccWords(); the window grid in row-major
+ * order, 32.32 fixed point) into that host array after the run.  A NULL buffer, a misaligned pointer or stride, a parameter
+ * out of bounds, an unknown flag bit or a capacity that is too small is JU_ERR_INVALID_ARGUMENT before any device call. */
+JU_API int ju_debug_temporal(void *state, const void *pre_warp, void *out, ptrdiff_t out_stride, const void *sums,
+    size_t width, size_t height, float strength, float threshold, float gain, int window, unsigned flags,
+    uint64_t *acc, size_t acc_capacity);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -730,6 +730,45 @@ int ju_debug_scene(int op, const void *frame, ptrdiff_t stride, size_t width, si
 	});
 }
 
+int ju_debug_temporal(void *state, const void *pre_warp, void *out, ptrdiff_t out_stride, const void *sums, size_t width,
+    size_t height, float strength, float threshold, float gain, int window, unsigned flags, uint64_t *acc,
+    size_t acc_capacity) {
+	return guarded([&] {
+		auto refuse = [](const std::string &why) { throw std::invalid_argument("ju_debug_temporal: " + why); };
+		if (state == nullptr || pre_warp == nullptr || out == nullptr) refuse("null buffer");
+		if (width < 1 || height < 1 || width > 8192 || height > 8192) refuse("a size outside 1 .. 8192");
+		if (reinterpret_cast<std::uintptr_t>(state) % 8 || reinterpret_cast<std::uintptr_t>(pre_warp) % 8) {
+			refuse("the f16 tensors must be 8-byte aligned");
+		}
+		if (reinterpret_cast<std::uintptr_t>(out) % 4 || out_stride % 4 || reinterpret_cast<std::uintptr_t>(sums) % 4) {
+			refuse("32-bit planes need addresses and strides that are multiples of 4");
+		}
+		// the model loader's bounds and wording (model.cpp validateConfig)
+		if (!(strength >= 0.0f && strength <= 1.0f) || !(threshold >= 0.0f && threshold <= 1.0f)) {
+			refuse("temporal filter strength/threshold must be in [0, 1]");
+		}
+		if (window < 0 || window > 4096) refuse("temporal filter window must be in 0..4096");
+		if (!(gain >= 0.0f && gain <= 1e6f)) refuse("temporal filter gain must be in [0, 1e6]");
+		if (flags & ~7u) refuse("unknown temporal flag bits");
+		const int H = static_cast<int>(height), W = static_cast<int>(width);
+		const std::size_t words = ju::temporalAccWords(H, W, window);
+		if ((acc == nullptr) != (acc_capacity == 0) || (acc != nullptr && acc_capacity < words)) {
+			refuse("acc and acc_capacity go together, and the capacity is at least the window grid");
+		}
+		// the filter's own words start as ones (zero_words_kernel has to clear them), the words behind them as zeros
+		const std::size_t total = std::max(words, acc_capacity);
+		ju::DeviceBuffer scratch(8 * total);
+		JU_HIP(hipMemset(scratch.get(), 0xff, 8 * words));
+		JU_HIP(hipStreamSynchronize(nullptr));
+		const ju::TemporalParams tp{strength, threshold, gain, window, (flags & 1u) ? 1 : 0, (flags & 2u) ? 1 : 0,
+		    (flags & 4u) ? 1 : 0};
+		ju::launchTemporalFilter(state, pre_warp, static_cast<std::uint8_t *>(out), out_stride, H, W,
+		    static_cast<const unsigned *>(sums), scratch.as<unsigned long long>(), tp, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+		if (acc != nullptr) JU_HIP(hipMemcpy(acc, scratch.get(), 8 * acc_capacity, hipMemcpyDeviceToHost));
+	});
+}
+
 int ju_debug_e4m3(const float *values, unsigned char *codes, size_t count) {
 	return guarded([&] {
 		if (count && (!values || !codes)) throw std::invalid_argument("ju_debug_e4m3: null buffer");

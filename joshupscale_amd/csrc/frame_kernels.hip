@@ -436,8 +436,10 @@ __global__ __launch_bounds__(256) void temporal_blend_kernel(f16 *__restrict__ s
 		if (g.limit) pw = fmaxf(fminf(pw, 0.5f), -0.5f);
 		const float r = pw * m1 + (static_cast<float>(gv[ch]) + bright) * m2;
 		st[ch] = static_cast<f16>(r - bright);
-		const unsigned u = static_cast<unsigned>((r + 0.5f) * 255.0f);  // postprocess, truncating
-		packed |= (u & 0xff) << (8 * ch);
+		// postprocess, truncating and saturated: r mixes in pre_warp, which nothing confines to +-0.5 (the fed-back
+		// state above stays unclipped, as the reference's is)
+		const unsigned u = static_cast<unsigned>(fminf(fmaxf((r + 0.5f) * 255.0f, 0.0f), 255.0f));
+		packed |= u << (8 * ch);
 	}
 	st[3] = static_cast<f16>(0.f);
 	*reinterpret_cast<Vec4<f16> *>(state + i * 4) = st;

@@ -424,6 +424,12 @@ void launchLrPack(DType dt, const std::uint8_t *frame, std::ptrdiff_t frameStrid
 // pre_warp, luma weighting.  state: the new HR state written by the tail (f16 [4H][4W][4],
 // generator output minus brightness), rewritten in place together with the u8 frame;
 // acc: temporalAccWords(...) 64-bit words of scratch (one 32.32 fixed-point sum per window).
+// The filtered value v mixes in pre_warp, which is not confined to +-0.5 (least of all with
+// normalize_brightness, when the brightness moves between frames): the byte saturates,
+// trunc(clamp((v + 0.5) * 255, 0, 255)), the fed-back state does not (the reference feeds back
+// the unclipped tensor too; its own byte is a C++ float -> uint8_t cast, cuda_convert.cc.cu:76-81,
+// which the language leaves undefined out of range).  A global sign gate that says "scene cut"
+// leaves both as the tail wrote them.
 struct TemporalParams {
 	float strength, threshold, gain;
 	int window;   // 0 = one global mean

@@ -256,6 +256,8 @@ _HOOK_SIGS = {
                                  C.c_uint32, C.c_int, _P(JuSceneInfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "ju_debug_scale": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ju_debug_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                    C.c_float, C.c_float, C.c_float, C.c_int, C.c_uint, C.c_void_p, C.c_size_t]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_plan_report": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, _P(C.c_size_t)]),

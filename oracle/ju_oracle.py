@@ -275,8 +275,12 @@ def postprocess(x: np.ndarray) -> np.ndarray:
     """``PostprocessLayer`` (keras_layers.py:211-230): ``(x + 0.5) * 255`` then a
     truncating cast to uint8 (``ops.cast``; the deployed graph keeps the value
     in float and core/src/cuda_convert.cc.cu:76-81 truncates instead).  The
-    input is already clipped to [-0.5, 0.5], so the value is in [0, 255]."""
-    return np.trunc((x + 0.5) * 255).astype(np.uint8)
+    generator's output is clipped to [-0.5, 0.5], so its value is in [0, 255]; the
+    temporal filter's is not (pre_warp is not confined, least of all with
+    normalize_brightness), and a C++ float -> uint8_t cast of a value outside
+    [0, 256) is undefined, so the reference defines nothing there: the byte
+    saturates here, as every other writer of this project does."""
+    return np.trunc(np.clip((x + 0.5) * 255, 0, 255)).astype(np.uint8)
 
 
 # --------------------------------------------------------------------------

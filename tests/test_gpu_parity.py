@@ -734,6 +734,45 @@ def test_temporal_filter_modes(mode, dtype):
     rt.close()
 
 
+def fade_clip():
+    """Six frames of one smooth picture with highlights and shadows (its contrast raised until both clip) whose mean
+    brightness moves by at most 0.15 of the range per frame, up and then down."""
+    base = M.synthetic_frames(1, 30, 48, seed=23, kind="smooth")[0]
+    picture = (base[..., :3].astype(np.float64) - 128.0) * 4.0 + 128.0
+    frames = np.zeros((6, 30, 48, 4), np.uint8)
+    for t, shift in enumerate((0.0, 0.2, 0.4, 0.2, 0.0, -0.2)):    # (of the values; the clipped ends move the mean by less)
+        frames[t, ..., :3] = np.clip(np.rint(picture + 255.0 * shift), 0, 255).astype(np.uint8)
+    return frames
+
+
+@pytest.mark.parametrize("dtype", [R.DTYPE_F16, R.DTYPE_BF16])
+def test_temporal_filter_saturates_through_a_fade(dtype):
+    """normalize_brightness with the temporal filter on, over a clip whose brightness moves: pre_warp = warp(previous
+    output - b_prev) + b_cur leaves [-0.5, 0.5] by the change of b, and so does the blend (no --limit).  The byte
+    saturates, the fed-back state keeps the unclipped value."""
+    cfg = small_config(normalize_brightness=True, temporal_strength=0.5, temporal_threshold=1.0)   # never cuts
+    wts, blob, rt = make(cfg, dtype)
+    sess = O.Session(wts, oracle_config(cfg))
+    frames = fade_clip()
+    means = frames[..., :3].reshape(6, -1).mean(axis=1) / 255.0
+    assert np.abs(np.diff(means)).max() <= 0.15 and means[2] > means[0] > means[5]
+    refs, states, raws = [], [], []
+    for f in frames:
+        refs.append(sess.run(f))
+        states.append(sess.state.pre_gen)
+        b = np.mean(O.preprocess(f[..., :3]) * O.BGR_LUMA * 3)
+        raws.append((sess.last.output_raw + b + 0.5) * 255)
+    raws = np.stack(raws)
+    over, under = float(np.mean(raws >= 256)), float(np.mean(raws < 0))
+    assert over >= 0.01 and under >= 0.01, (over, under)     # on the oracle's trace alone: the clip leaves the range both ways
+    for t, f in enumerate(frames):
+        out = rt.process_image(f)
+        check_u8(out, refs[t], dtype, ("temporal-fade", t))
+        state = rt.read_tensor("state").reshape(120, 192, 4)[..., :3]
+        assert err(state, states[t])["max_abs"] <= TOL[dtype]["raw"]
+    rt.close()
+
+
 def test_keras_import_runs_through_the_engine():
     """SURVEY 8f rank 1, end to end: Keras-ordered layer dictionaries (what
     tools/export_jupw_from_keras.py collects with layer.get_weights()) -> container_weights
