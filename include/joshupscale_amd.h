@@ -448,7 +448,20 @@ JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *
  * from a history a cut inside it would invalidate): ju_process_batch, ju_process_frames and ju_process_group run such
  * a runtime's frames one by one in stream order ("lookahead_frames" / "group_frames" do not count them), and
  * ju_prepare_batch captures nothing; ju_prepare_frames works as before and the direct device path and its graphs stay
- * in use.  Turning the mode off restores the passes.  Not provided: a pass split at a cut. */
+ * in use.  Turning the mode off restores the passes.
+ *
+ * ju_set_scene_lookahead(rt, 1) lifts that for look-ahead passes: ju_process_batch and ju_process_frames form their
+ * passes under all their usual rules (the cap, the overlap splitter, eligibility, host and YUV frames) and
+ * ju_prepare_batch captures, while the detector is on.  A pass then carries the detector itself: one launch in front of
+ * the flow net's takes the decisions of all its frames on the GPU, and in JU_SCENE_RESET mode the pass applies each cut
+ * without a host round trip -- the first flow block builds its history from the frames since the cut and zeros, and a
+ * conditional clear in front of each frame zeroes its input state.  Every output byte, the state, the history and every
+ * ju_scene_info record equal those of the same frames sent one by one through ju_process / ju_process_frame with the same
+ * detector setting.  The default is 0 (the paragraph above); a value other than 0 or 1 is JU_ERR_INVALID_ARGUMENT; the
+ * call waits for the stream; ju_reset and ju_set_scene_detect keep the setting.  ju_get_stat: "scene_lookahead" (1 / 0),
+ * "scene_pass_frames" (frames whose detector step ran inside a pass; "lookahead_frames" counts them too).  Frames under
+ * a source size, an output size or a mask stay one by one.  Not provided: group passes for a detecting runtime --
+ * ju_process_group runs it member by member whatever this setting. */
 enum { JU_SCENE_OFF = 0, JU_SCENE_REPORT = 1, JU_SCENE_RESET = 2 };
 typedef struct ju_scene_info {
 	uint64_t step, sad, score; /* the detector step, S_t, D_t */
@@ -457,6 +470,7 @@ typedef struct ju_scene_info {
 JU_API int ju_set_scene_detect(ju_runtime *runtime, int mode, uint32_t threshold_milli);
 JU_API int ju_get_scene_detect(const ju_runtime *runtime, int *mode, uint32_t *threshold_milli);
 JU_API int ju_get_scene_info(ju_runtime *runtime, ju_scene_info *out, int count, int *written);
+JU_API int ju_set_scene_lookahead(ju_runtime *runtime, int on);
 
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing

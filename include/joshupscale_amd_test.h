@@ -62,7 +62,8 @@ JU_API int ju_plan_report(ju_runtime *runtime, char *dst, size_t capacity, size_
  * same bytes, tests compare it with the product's); "resident_fault" n
  * (launch the resident tower n workgroups short: tests the fallback); "pass_rerun" 1 (a look-ahead
  * pass that completed normally is run again frame by frame, as after a resident-tower report but without the
- * fallback: the re-run's bookkeeping; no kernel misbehaves); "step_rerun" 1 (the same for a single frame: ju_process
+ * fallback: the re-run's bookkeeping; no kernel misbehaves -- a pass that carried the scene detector keeps its decisions,
+ * and the frames run again without it); "step_rerun" 1 (the same for a single frame: ju_process
  * and the frame-by-frame steps of the multi-frame calls submit every frame a second time, as after a resident-tower
  * report but without the fallback; the scene detector must not run for the second submission: ju_get_stat
  * "scene_detector_runs" counts its runs). */
@@ -157,6 +158,20 @@ JU_API int ju_debug_output(int op, void *dst, size_t dst_width, size_t dst_heigh
 JU_API int ju_debug_scene(int op, const void *frame, ptrdiff_t stride, size_t width, size_t height, void *prev, void *state,
     int has_prev, uint32_t threshold_milli, int reset_mode, ju_scene_info *record, void *clear_a, size_t a_bytes,
     void *clear_b, size_t b_bytes);
+
+/* scene_pass_kernel alone: the detector over the `count` (1 .. 8) frames of a look-ahead pass in one launch
+ * (docs/scene_detect.md "Passes"), on the current device (synchronous).  frames[i] / strides[i]: device BGRX rows of
+ * width x height, each at its own 4-byte-aligned address with its own signed stride of at least a row (a multiple of 4);
+ * item i is compared with item i - 1, item 0 with `prev`, the dense kept frame, which is rewritten with the last item.
+ * `state`: the 40 bytes of ju_debug_scene op 0 (bytes 16 .. 23: the S item 0 compares with, and afterwards the last
+ * item's; frames and cuts behind it).  `pass_state`: 136 bytes of device memory, zero before the first call -- eight
+ * 64-bit accumulators and the 32-bit ticket at byte 64 (all zero again when the call returns), then at byte 72
+ * resetAt[8] (uint32) and at byte 104 cutAt[8] (int32).  has_prev: what is in the detector's memory in front of item 0,
+ * as for op 0 of ju_debug_scene (0, 1 or 3).  records[i] receives item i's decision with step first_step + i;
+ * reset_at[i] = cut_i && reset_mode; cut_at[i] = the latest item <= i with reset_at set, else -1. */
+JU_API int ju_debug_scene_pass(int count, const void *const *frames, const ptrdiff_t *strides, size_t width, size_t height,
+    void *prev, void *state, void *pass_state, int has_prev, uint64_t first_step, uint32_t threshold_milli, int reset_mode,
+    ju_scene_info *records, uint32_t *reset_at, int32_t *cut_at);
 
 /* The scalers with a filter argument (docs/source_stage.md "Filters"; tests/scale_filter_reference.py); `filter` is a
  * JU_SCALE_* value.  op 0: the 8-bit scaler -- buffers, sizes and strides as ju_debug_source op 0.  op 1: the state

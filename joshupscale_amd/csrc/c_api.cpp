@@ -323,6 +323,10 @@ int ju_get_scene_info(ju_runtime *runtime, ju_scene_info *out, int count, int *w
 	});
 }
 
+int ju_set_scene_lookahead(ju_runtime *runtime, int on) {
+	return guarded([&] { engineOf(runtime).setSceneLookahead(on); });
+}
+
 int ju_reset(ju_runtime *runtime) {
 	return guarded([&] { engineOf(runtime).reset(); });
 }
@@ -727,6 +731,57 @@ int ju_debug_scene(int op, const void *frame, ptrdiff_t stride, size_t width, si
 		record->score = r->score;
 		record->cut = r->cut;
 		record->reserved = 0;
+	});
+}
+
+int ju_debug_scene_pass(int count, const void *const *frames, const ptrdiff_t *strides, size_t width, size_t height, void *prev,
+    void *state, void *pass_state, int has_prev, uint64_t first_step, uint32_t threshold_milli, int reset_mode,
+    ju_scene_info *records, uint32_t *reset_at, int32_t *cut_at) {
+	return guarded([&] {
+		static_assert(sizeof(ju::ScenePassState) == 136, "the layout include/joshupscale_amd_test.h describes");
+		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_scene_pass: count must be 1 .. 8");
+		if (frames == nullptr || strides == nullptr || records == nullptr || reset_at == nullptr || cut_at == nullptr) {
+			throw std::invalid_argument("ju_debug_scene_pass: NULL array");
+		}
+		if (has_prev != 0 && has_prev != 1 && has_prev != 3) throw std::invalid_argument("ju_debug_scene_pass: has_prev must be 0, 1 or 3");
+		ju::PinnedWords ring(sizeof(ju::SceneRecord) * (ju::kSceneRing + 1));
+		ju::PinnedWords dynWords(sizeof(ju::ScenePassDyn));
+		auto *dyn = reinterpret_cast<volatile ju::ScenePassDyn *>(dynWords.host());
+		dyn->stepBase = first_step;
+		dyn->seen = has_prev == 3 ? 2u : static_cast<unsigned>(has_prev);
+		dyn->thresholdMilli = threshold_milli;
+		dyn->slot = static_cast<unsigned>(first_step % ju::kSceneRing);
+		ju::ScenePassLaunch q;
+		q.items = count;
+		for (int i = 0; i < count; ++i) {
+			q.frames[i] = static_cast<const std::uint8_t *>(frames[i]);
+			q.strides[i] = strides[i];
+		}
+		q.width = static_cast<int>(std::min<size_t>(width, 1u << 20));
+		q.height = static_cast<int>(std::min<size_t>(height, 1u << 20));
+		q.prev = static_cast<std::uint32_t *>(prev);
+		q.state = static_cast<ju::SceneState *>(state);
+		q.pass = static_cast<ju::ScenePassState *>(pass_state);
+		q.dyn = reinterpret_cast<const ju::ScenePassDyn *>(dynWords.device());
+		q.ring = reinterpret_cast<ju::SceneRecord *>(ring.device());
+		q.resetMode = reset_mode != 0;
+		ju::launchScenePass(q, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+		const auto *r = reinterpret_cast<const volatile ju::SceneRecord *>(ring.host());
+		for (int i = 0; i < count; ++i) {
+			const volatile ju::SceneRecord &rec = r[(first_step + static_cast<uint64_t>(i)) % ju::kSceneRing];
+			records[i].step = rec.step;
+			records[i].sad = rec.sad;
+			records[i].score = rec.score;
+			records[i].cut = rec.cut;
+			records[i].reserved = 0;
+		}
+		ju::ScenePassState after;
+		JU_HIP(hipMemcpy(&after, pass_state, sizeof(after), hipMemcpyDeviceToHost));
+		for (int i = 0; i < count; ++i) {
+			reset_at[i] = after.resetAt[i];
+			cut_at[i] = after.cutAt[i];
+		}
 	});
 }
 

@@ -329,7 +329,7 @@ void Engine::addConvStep(std::vector<Step> *prog, const std::string &tag,
 // > 1 for a look-ahead pass -- the same launches over `items` consecutive frames (grid.z), on the batch tensors, the
 // first block reading the frames of m_BatchIO (submitBatch).  A look-ahead pass exists only where every launch of
 // the plan has an item dimension (the one-launch blocks and the split-K convolutions): std::logic_error otherwise.
-void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, bool group) {
+void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, bool group, bool cut) {
 	std::vector<Step> &prog = *progOut;
 	const ModelConfig &c = m_Config;
 	const DType dt = m_DType;
@@ -414,6 +414,7 @@ void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, 
 				fb.packOut = nullptr;
 				fb.independentItems = true;
 			}
+			if (cut) fb.cutAt = m_ScenePassDev.as<ScenePassState>()->cutAt;
 			prog.push_back({"flow", flops, [dt, fb, io, batchIO, groupPrev, groupOut, items, group](hipStream_t s) {
 				                FlowBlockLaunch f = fb;  // the caller's frames are known at launch time only
 				                f.packFrame = io->in;
@@ -1860,6 +1861,8 @@ double Engine::stat(const std::string &key) const {
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
 	if (key == "scene_mode") return static_cast<double>(m_SceneMode);
+	if (key == "scene_lookahead") return m_SceneLookahead ? 1.0 : 0.0;
+	if (key == "scene_pass_frames") return static_cast<double>(m_ScenePassFrames);
 	// (the detector's own counters, as of the steps that have completed: the decision writes them to host-mapped memory)
 	if (key == "scene_frames" || key == "scene_cuts") {
 		const bool cuts = key == "scene_cuts";

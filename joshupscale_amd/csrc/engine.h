@@ -115,6 +115,10 @@ public:
 	void sceneDetect(int *mode, std::uint32_t *thresholdMilli) const;
 	// the most recent min(count, 64, steps seen) records, oldest first, after waiting for the stream; returns how many
 	int sceneInfo(SceneRecord *out, int count);
+	// Look-ahead passes while the detector is on (ju_set_scene_lookahead; engine_passes.cpp, "The scene detector inside
+	// a pass"): 0 (default) = such a runtime's frames run one by one, 1 = passes are formed and carry the detector.
+	// Waits for the stream; reset() and setSceneDetect() keep it.
+	void setSceneLookahead(int on);
 
 	FrameSize frameSize() const;
 	int device() const { return m_Device; }
@@ -187,7 +191,8 @@ private:
 	    Operand in, Operand res, Operand out, int H, int W, bool relu, bool outHead,
 	    bool tower = false, bool pool = false, bool upsample = false, ItemStride item = ItemStride());
 	// group: the launches of a group pass (independent items: processGroup) -- `set` is then unused
-	void addFlowAutoencoder(std::vector<Step> *prog, int set, int items, bool group = false);
+	// cut: the first block takes its history by ScenePassState::cutAt (a pass that restarts the recurrence at scene cuts)
+	void addFlowAutoencoder(std::vector<Step> *prog, int set, int items, bool group = false, bool cut = false);
 	bool flowPacksInBlock() const;
 	Operand operand(const std::string &name);
 	Tensor &addTowerTensor(const std::string &name, int H, int W, int C);
@@ -242,6 +247,22 @@ private:
 	std::uint64_t m_SceneFramesBase = 0, m_SceneCutsBase = 0;  // "scene_frames" / "scene_cuts" of earlier on-periods
 	bool m_SceneRerun = false;
 	void sceneStep();
+	// The detector inside look-ahead passes.  m_ScenePassDev: the ScenePassState (accumulators, ticket, resetAt[], cutAt[]),
+	// allocated once and kept -- the cut-aware flow programs are bound to it; m_ScenePassDyn: the host-mapped ScenePassDyn
+	// the host refreshes in front of every pass; m_ScenePassFrames: "scene_pass_frames".
+	bool m_SceneLookahead = false;
+	DeviceBuffer m_ScenePassDev;
+	PinnedWords m_ScenePassDyn;
+	std::uint64_t m_ScenePassFrames = 0;
+	// what a pass formed now carries: 0 nothing, 1 the detector, 2 the detector and the restart at its cuts (reset mode
+	// on a recurrent model: clear nodes and the cut-aware flow program) -- part of the key of a pass's graph
+	int scenePass() const {
+		if (!m_SceneLookahead || m_SceneMode == 0) return 0;
+		return m_SceneMode == 2 && m_Config.recurrent() ? 2 : 1;
+	}
+	// binding set of the cut-aware flow launches in m_BatchFlow: {items, kCutSet + set}
+	static constexpr int kCutSet = 4;
+	void dropScenePassGraphs();  // the graphs of passes that carry the detector: bound to m_ScenePrev / m_SceneDev / m_SceneRing
 	// Everything a frame call can refuse, before anything is launched; `who` names the entry point in the message.
 	// declaredSize (ju_process_group): a NULL pointer is refused first and by name, and a graphics resource's DECLARED
 	// size counts too -- otherwise the texture's own extent is checked when it is mapped, behind other members' launches.
@@ -430,7 +451,9 @@ private:
 	struct PassKey {
 		DirectKey io;
 		YuvKey in, out;
+		int scene = 0;  // scenePass() when the pass was bound: no graph serves another detector configuration
 		bool operator<(const PassKey &o) const {
+			if (scene != o.scene) return scene < o.scene;
 			if (io < o.io) return true;
 			if (o.io < io) return false;
 			return std::make_tuple(in.tie(), out.tie()) < std::make_tuple(o.in.tie(), o.out.tie());

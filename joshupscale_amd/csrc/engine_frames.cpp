@@ -434,7 +434,9 @@ void Engine::setSceneDetect(int mode, std::uint32_t thresholdMilli) {
 		m_SceneFramesBase += totals->step;
 		m_SceneCutsBase += totals->sad;
 	}
-	// a start: fresh (zeroed) memory, no predecessor, step 0.  No captured graph is bound to any of these buffers.
+	// a start: fresh (zeroed) memory, no predecessor, step 0.  The only captured graphs bound to these buffers are those
+	// of passes that carry the detector (PassKey::scene != 0): they go with them.
+	dropScenePassGraphs();
 	m_ScenePrev = DeviceBuffer();
 	m_SceneDev = DeviceBuffer();
 	m_SceneRing = PinnedWords();
@@ -448,6 +450,23 @@ void Engine::setSceneDetect(int mode, std::uint32_t thresholdMilli) {
 	m_SceneThreshold = mode != 0 ? thresholdMilli : 0;
 	m_SceneSeen = 0;
 	m_SceneSteps = 0;
+}
+
+void Engine::dropScenePassGraphs() {
+	for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
+		it = (!it->first.empty() && it->first.front().scene != 0) ? m_BatchGraphs.erase(it) : std::next(it);
+	}
+}
+
+void Engine::setSceneLookahead(int on) {
+	if (on != 0 && on != 1) throw std::invalid_argument("ju_set_scene_lookahead: on must be 0 or 1, got " + std::to_string(on));
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();
+	if (on && !m_ScenePassDev.get()) {
+		m_ScenePassDev = DeviceBuffer(sizeof(ScenePassState));  // (DeviceBuffer memory starts zeroed)
+		m_ScenePassDyn = PinnedWords(sizeof(ScenePassDyn));
+	}
+	m_SceneLookahead = on != 0;
 }
 
 void Engine::sceneDetect(int *mode, std::uint32_t *thresholdMilli) const {

@@ -28,6 +28,14 @@ namespace ju {
 // m_State[set] and leaves the last frame's state in m_State[set ^ 1] and the last history in m_Packed[set ^ 1], as
 // ONE process() call would: the pass flips the binding set once, and -- since nothing it wrote is read before the
 // pass -- a pass that failed (resident tower: bounded wait expired) can be run again frame by frame.
+//
+// The scene detector inside a pass (setSceneLookahead; docs/scene_detect.md "Passes").  The detector reads the LR frames
+// only, and all of them are there before the pass's first launch: scene_pass_kernel takes the n decisions in ONE launch in
+// front of the flow net's and leaves resetAt[] / cutAt[] on the device.  In reset mode on a recurrent model the pass then
+// restarts the recurrence itself: the first flow block takes its history by cutAt[] (the flow programs at kCutSet + set),
+// and a scene_clear_kernel in front of frame i's steps zeroes its input state while resetAt[i] is set.  One exception
+// to "writes nothing it reads": that clear may zero m_State[set] for frame 0 -- what a re-run of the frames, whose
+// decisions stand, wants to find there too.
 // ---------------------------------------------------------------------------------------------------------------
 bool Engine::batchPlanned(int items, bool group) {
 	if (!m_Config.recurrent()) {
@@ -42,7 +50,11 @@ bool Engine::batchPlanned(int items, bool group) {
 	if (m_BatchUnsupported || m_Calibrate || m_Config.flowArch != 0 || !flowPacksInBlock() || m_Config.normalizeBrightness) {
 		return false;
 	}
-	if (items <= m_BatchCap && m_BatchFlow.count({items, group ? kGroupSet : 0})) return true;
+	// (a pass that restarts the recurrence at scene cuts has flow launches of its own: the first block's cut-aware history)
+	const bool cut = !group && scenePass() == 2;
+	if (items <= m_BatchCap && m_BatchFlow.count({items, group ? kGroupSet : 0}) && (!cut || m_BatchFlow.count({items, kCutSet}))) {
+		return true;
+	}
 	try {
 		if (items > m_BatchCap) {
 			// (the tensors of every pass so far are too small: start over)
@@ -75,9 +87,16 @@ bool Engine::batchPlanned(int items, bool group) {
 			if (!m_BatchState[i].get()) m_BatchState[i] = DeviceBuffer(m_State[0].bytes());
 		}
 		for (int set = 0; set < 2; ++set) {
-			std::vector<Step> prog;
-			addFlowAutoencoder(&prog, set, items);
-			m_BatchFlow[{items, set}] = std::move(prog);
+			if (!m_BatchFlow.count({items, set})) {
+				std::vector<Step> prog;
+				addFlowAutoencoder(&prog, set, items);
+				m_BatchFlow[{items, set}] = std::move(prog);
+			}
+			if (cut && !m_BatchFlow.count({items, kCutSet + set})) {
+				std::vector<Step> prog;
+				addFlowAutoencoder(&prog, set, items, false, true);
+				m_BatchFlow[{items, kCutSet + set}] = std::move(prog);
+			}
 		}
 		return true;
 	} catch (const std::exception &e) {
@@ -119,7 +138,8 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		st.run(m_Stream);
 		if (around) (*around)(st, true);
 	};
-	const std::vector<Step> &flow = m_BatchFlow.at({n, set});
+	const int scene = scenePass();
+	const std::vector<Step> &flow = m_BatchFlow.at({n, scene == 2 ? kCutSet + set : set});
 	const bool recurrent = m_Config.recurrent();  // (flow-free: no flow fields, no state chain)
 	const long flowItem = recurrent ? static_cast<long>(m_Tensors.at("flow").count) * 2 : 0;
 	const unsigned char *flowBase = recurrent ? m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
@@ -147,6 +167,29 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),
 		    m_Stream);
 	}
+	// The scene detector inside a pass: every frame of the pass is in place here (the caller's device frames, the upload
+	// slots, the BGRX buffers the decode launch above fills), so ONE launch takes all n decisions in front of the flow
+	// net's -- the records, and on the device resetAt[] for the clear in front of each frame and cutAt[] for the first
+	// flow block's history.  The frames are read where they are, each with its own address and stride.
+	ScenePassState *passState = scene ? m_ScenePassDev.as<ScenePassState>() : nullptr;
+	if (scene) {
+		const FrameSize fs = frameSize();
+		ScenePassLaunch q;
+		q.items = n;
+		for (int i = 0; i < n; ++i) {
+			q.frames[i] = m_BatchIO[i].in;
+			q.strides[i] = m_BatchIO[i].inStride;
+		}
+		q.width = static_cast<int>(fs.inputWidth);
+		q.height = static_cast<int>(fs.inputHeight);
+		q.prev = m_ScenePrev.as<std::uint32_t>();
+		q.state = m_SceneDev.as<SceneState>();
+		q.pass = passState;
+		q.dyn = reinterpret_cast<const ScenePassDyn *>(m_ScenePassDyn.device());
+		q.ring = reinterpret_cast<SceneRecord *>(m_SceneRing.device());
+		q.resetMode = scene == 2;
+		launchScenePass(q, m_Stream);
+	}
 	for (const Step &st : flow) run(st);
 	for (int i = 0; i < n; ++i) {
 		m_IO = m_BatchIO[i];
@@ -154,6 +197,11 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 			m_FlowCur = flowBase + i * flowItem;
 			m_StateBind[set].in = i == 0 ? keepBind.in : m_BatchState[i - 1].get();
 			m_StateBind[set].out = i + 1 == n ? keepBind.out : m_BatchState[i].get();
+			// a cut at frame i: its input state is zero, as after reset() -- behind frame i - 1's tail and its encode (which
+			// read that buffer: stream order), in front of frame i's warp; with the flag 0 every workgroup returns at once
+			if (scene == 2) {
+				launchSceneClear(&passState->resetAt[i], const_cast<void *>(m_StateBind[set].in), m_State[set].bytes(), nullptr, 0, m_Stream);
+			}
 		}
 		for (const Step &st : m_Program[set]) {
 			if (st.tag != "flow" && st.tag != "pack") run(st);
@@ -176,8 +224,9 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 // A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
 	if (sourceStage()) return false;  // (scaled / masked frames run one by one through submitFrame)
-	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate)
-	if (m_SceneMode != 0) return false;
+	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
+	// unless the pass carries the detector and applies the cuts itself: setSceneLookahead)
+	if (m_SceneMode != 0 && !m_SceneLookahead) return false;
 	const FrameSize fs = frameSize();
 	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align) {
 		if (a.yuv) {
@@ -219,6 +268,7 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
 		}
 		k.io = DirectKey{io.in, io.inStride, io.out, io.outStride, set};
+		k.scene = scenePass();
 	}
 	return key;
 }
@@ -354,7 +404,7 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 		if (e.graph.valid()) continue;
 		{
 			DryLaunchScope dry;  // the attributes of the tile heights this pass's launch sizes choose
-			for (const Step &st : m_BatchFlow.at({n, set})) st.run(m_Stream);
+			for (const Step &st : m_BatchFlow.at({n, scenePass() == 2 ? kCutSet + set : set})) st.run(m_Stream);
 		}
 		e.graph = GraphExec::capture(m_Stream, [&] { runBatch(set, n); });
 		e.seen = 2;
@@ -370,6 +420,17 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	const std::vector<PassKey> key = bindBatch(in, out, n, set);
 	uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
 	m_PassSignalBase = m_PassSignal.host() ? *m_PassSignal.host() : 0u;
+	const int scene = scenePass();
+	if (scene) {
+		// what a captured pass cannot bake in: the detector's kernel reads it from host-mapped memory.  Passes are
+		// synchronous, so no launch that reads the block is in flight while it is written.
+		auto *dyn = reinterpret_cast<volatile ScenePassDyn *>(m_ScenePassDyn.host());
+		dyn->stepBase = m_SceneSteps;
+		dyn->seen = static_cast<unsigned>(std::min<std::uint64_t>(m_SceneSeen, 2));
+		dyn->thresholdMilli = m_SceneThreshold;
+		dyn->slot = static_cast<unsigned>(m_SceneSteps % kSceneRing);
+		std::atomic_thread_fence(std::memory_order_seq_cst);
+	}
 	for (int i = 0; i < n; ++i) {
 		m_BatchHostFrames += m_BatchHost[i].host() ? 1 : 0;
 		m_BatchYuvFrames += m_BatchHost[i].yuv() ? 1 : 0;
@@ -399,6 +460,12 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	}
 	m_Idx = set ^ 1;
 	m_BatchFrames += static_cast<std::uint64_t>(n);
+	if (scene) {  // n detector steps, taken by the pass's one launch
+		m_SceneSeen += static_cast<std::uint64_t>(n);
+		m_SceneSteps += static_cast<std::uint64_t>(n);
+		m_SceneRuns += static_cast<std::uint64_t>(n);
+		m_ScenePassFrames += static_cast<std::uint64_t>(n);
+	}
 }
 
 namespace {
@@ -454,6 +521,8 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 			continue;
 		}
 		const int set = m_Idx;
+		const int scene = scenePass();
+		const std::uint64_t firstStep = m_SceneSteps;
 		submitBatch(in + i, out + i, n);
 		drainPassOutputs(out + i, n);  // host frames: each copied out while the next one runs
 		m_Stream.synchronizeSpin(m_SpinUs);
@@ -468,7 +537,21 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 				m_BatchYuvFrames -= m_BatchHost[k].yuv() ? 1 : 0;
 			}
 			if (code) fallbackToLayers(code);
+			struct Rerun {  // (the pass's detector has run: its n decisions stand, no frame meets it again)
+				bool &flag;
+				~Rerun() { flag = false; }
+			} rerun{m_SceneRerun};
 			for (int k = 0; k < n; ++k) {
+				if (scene) {
+					m_SceneRerun = true;
+					// the restart at a cut, as the per-frame detector does it: what this frame is about to read as its
+					// recurrent inputs is zero in front of exactly the frames whose record says so (the stream has drained)
+					const auto *ring = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host());
+					if (scene == 2 && ring[(firstStep + static_cast<std::uint64_t>(k)) % kSceneRing].cut) {
+						m_State[m_Idx].zeroAsync(m_Stream);
+						m_Packed[m_Idx].zeroAsync(m_Stream);
+					}
+				}
 				if (code) {
 					submitAny(in[i + k], out[i + k]);
 					m_Stream.synchronize();
@@ -531,7 +614,10 @@ void Engine::processGroup(Engine *const *members, const Frame *bgrxIn, const Fra
 		for (int j = 0; j < count && !clash; ++j) clash = overlap(w, extentOf(in[j]));
 	}
 	std::vector<int> pass, rest;
-	for (int i = 0; i < count; ++i) (members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
+	// (a detecting runtime stays member by member, whatever its look-ahead setting: a group pass carries no detector)
+	for (int i = 0; i < count; ++i) {
+		(members[i]->m_SceneMode == 0 && members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
+	}
 	const int cap = lead.m_BatchMax;
 	if (clash || pass.size() < 2 || cap < 2) {
 		for (int i = 0; i < count; ++i) alone(i);

@@ -64,6 +64,10 @@ struct FlowBlockParams {
 	// history from packPrevs[i], new history to packOuts[i]; packPrev / packOut are unused
 	const void *packPrevs[kFlowBatchMax];
 	void *packOuts[kFlowBatchMax];
+	// cut-aware history (CUT instantiation: the passes of a runtime whose scene detector restarts the recurrence): per
+	// item the latest item at or before it that starts a scene, or -1 (ScenePassState::cutAt, device memory).  Last in
+	// the struct: no other member moves.
+	const int *cutAt;
 };
 
 template <int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, int NW = 4>
@@ -117,10 +121,12 @@ struct FbGeom {
 // NW waves per workgroup: 8 (two per SIMD) wherever the kernel fits 256 registers -- the
 // staging, expansion and epilogue phases are VALU work that one wave per SIMD issues at
 // half rate, and a partner wave's epilogue runs beside the other's MFMAs.
-template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, int NW, bool PACK = false, bool INDEP = false>
+template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, int NW, bool PACK = false, bool INDEP = false,
+    bool CUT = false>
 __global__ __launch_bounds__(NW * 64, NW / 4) void flow_block_kernel(FlowBlockParams p) {
 	static_assert(!PACK || (CIN == 16 && !UPS), "PACK: the 16-channel flow input");
 	static_assert(!INDEP || PACK, "INDEP: a form of the input packing");
+	static_assert(!CUT || (PACK && !INDEP), "CUT: a form of the look-ahead input packing");
 	using G = FbGeom<CIN, CMID, TH, UPS, POOL, OUTK, NW>;
 	constexpr int NT = NW * 64;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -239,7 +245,17 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void flow_block_kernel(FlowBlockPa
 		T *__restrict__ cur = INDEP ? static_cast<T *>(p.packOuts[item])
 		                            : (item + 1 == static_cast<int>(gridDim.z) ? static_cast<T *>(p.packOut) : nullptr);
 		const int nch = 3 * p.numInputs;
-		const int fromFrames = INDEP ? 1 : min(item + 1, p.numInputs);  // history slots 0 .. fromFrames - 1 come from frames
+		int fromFrames = INDEP ? 1 : min(item + 1, p.numInputs);  // history slots 0 .. fromFrames - 1 come from frames
+		// CUT: item c = cutAt[item] >= 0 starts a scene -- slots that reach back to frames c .. item only, the rest stay
+		// the exact +0 a cleared history holds, and nothing of the previous tensor counts
+		[[maybe_unused]] bool fromPrev = true;
+		if constexpr (CUT) {
+			const int c = p.cutAt[item];
+			if (c >= 0) {
+				fromFrames = min(item - c + 1, p.numInputs);
+				fromPrev = false;
+			}
+		}
 		constexpr int NPIX = G::XR * kFbW;
 		for (int q = tid; q < NPIX; q += NT) {
 			const int r = q / kFbW, k = q - r * kFbW;
@@ -269,7 +285,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void flow_block_kernel(FlowBlockPa
 						o[3 * h + 2] = static_cast<T>(c2);
 					}
 				}
-				if (fromFrames < p.numInputs) {
+				if (fromFrames < p.numInputs && (!CUT || fromPrev)) {
 					const Vec8<T> p0 = *reinterpret_cast<const Vec8<T> *>(prev + idx * 16);
 					const Vec8<T> p1 = *reinterpret_cast<const Vec8<T> *>(prev + idx * 16 + 8);
 #pragma unroll
@@ -610,12 +626,12 @@ constexpr int fbWaves() {
 	return (CIN > 64 || CMID > 64) ? 4 : 8;
 }
 
-template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, bool PACK = false, bool INDEP = false>
+template <typename T, int CIN, int CMID, int TH, bool UPS, bool POOL, int OUTK, bool PACK = false, bool INDEP = false, bool CUT = false>
 void launchFlowBlockInst(const FlowBlockParams &p, int items, hipStream_t stream) {
 	constexpr int NW = fbWaves<CIN, CMID>();
 	using G = FbGeom<CIN, CMID, TH, UPS, POOL, OUTK, NW>;
 	static_assert(G::FITS, "tile does not fit LDS");
-	auto kern = flow_block_kernel<T, CIN, CMID, TH, UPS, POOL, OUTK, NW, PACK, INDEP>;
+	auto kern = flow_block_kernel<T, CIN, CMID, TH, UPS, POOL, OUTK, NW, PACK, INDEP, CUT>;
 	static std::atomic<std::uint64_t> ldsDone{0};
 	ensureDynamicLds(reinterpret_cast<const void *>(kern), G::LDS, &ldsDone, "flow block");
 	if (launchesAreDry()) return;
@@ -651,7 +667,7 @@ void fbNotePlan(const DevPlan *plan, int cin, int cmid, bool ups, bool pool, int
 	plan->log->note(line);
 }
 
-template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK, bool INDEP, int... THS>
+template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK, bool INDEP, bool CUT, int... THS>
 void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, const DevPlan *plan, hipStream_t stream) {
 	const long tilesX = (p.W + kFbOutW - 1) / kFbOutW;
 	const int forced = plan ? plan->flowTile : 0;
@@ -674,7 +690,7 @@ void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, const 
 		constexpr int TH = decltype(thTag)::value;
 		if constexpr (FbGeom<CIN, CMID, TH, UPS, POOL, OUTK, fbWaves<CIN, CMID>()>::FITS) {
 			if (!done && best == TH) {
-				launchFlowBlockInst<T, CIN, CMID, TH, UPS, POOL, OUTK, PACK, INDEP>(p, items, stream);
+				launchFlowBlockInst<T, CIN, CMID, TH, UPS, POOL, OUTK, PACK, INDEP, CUT>(p, items, stream);
 				done = true;
 			}
 		}
@@ -683,20 +699,20 @@ void launchFlowBlockBest(const FlowBlockParams &p, int items, int numCUs, const 
 	if (!done) throw std::logic_error("flow block: no tile height fits");
 }
 
-template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK = false, bool INDEP = false>
+template <typename T, int CIN, int CMID, bool UPS, bool POOL, int OUTK, bool PACK = false, bool INDEP = false, bool CUT = false>
 void launchFlowBlockT(const FlowBlockParams &p, int items, int numCUs, const DevPlan *plan, hipStream_t stream) {
 	if constexpr (OUTK == 2) {
 		// (64 -> 64 -> 64 residual block, JU_RES_BLOCK=tile only: two 128-byte tiles; 14 rows is what fits)
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, kFbMid, 6>(p, items, numCUs, plan, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, CUT, kFbMid, 6>(p, items, numCUs, plan, stream);
 	} else if constexpr (CMID == 128) {
 		// (the 128-filter blocks, 68 x 120 at 480 x 270: a few thousand pixels -- short tiles, or most of the chip idles;
 		// measured for the encoder / decoder block: 2 rows 11.7 / 23.8 us, 4 rows 16.0 / 32.1, 6 rows 19.9 / 39.1.  One
 		// frame is a single round of 2-row tiles; a look-ahead launch of 8 frames is five such rounds or two of 6-row
 		// tiles -- the cost rule above picks.  The decoder block's taller tiles keep two of its four input planes in LDS
 		// at a time: FbGeom::XPAIR.)
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 6, 4, 2>(p, items, numCUs, plan, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, CUT, 6, 4, 2>(p, items, numCUs, plan, stream);
 	} else {
-		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, 20, 18, 10, 6>(p, items, numCUs, plan, stream);
+		launchFlowBlockBest<T, CIN, CMID, UPS, POOL, OUTK, PACK, INDEP, CUT, 20, 18, 10, 6>(p, items, numCUs, plan, stream);
 	}
 }
 
@@ -752,6 +768,11 @@ void launchFlowBlockDT(const FlowBlockLaunch &q, hipStream_t stream) {
 			throw std::invalid_argument("flow block: input packing is built for the first block (16 -> 32 -> 32, pool)");
 		}
 		if (q.independentItems) return launchFlowBlockT<T, 16, 32, false, true, 0, true, true>(p, items, cus, q.plan, stream);
+		if (q.cutAt != nullptr) {  // the passes of a runtime whose scene detector restarts the recurrence
+			if (items < 2) throw std::invalid_argument("flow block: cut-aware history is a form of the look-ahead launch");
+			p.cutAt = q.cutAt;
+			return launchFlowBlockT<T, 16, 32, false, true, 0, true, false, true>(p, items, cus, q.plan, stream);
+		}
 		return launchFlowBlockT<T, 16, 32, false, true, 0, true>(p, items, cus, q.plan, stream);
 	}
 	if (q.upsample && (q.H % 2 || q.W % 2)) throw std::invalid_argument("flow block: fused upsampling needs even H and W");

@@ -217,6 +217,11 @@ struct FlowBlockLaunch {
 	bool independentItems;
 	const void *packPrevs[kFlowBatchMax];
 	void *packOuts[kFlowBatchMax];
+	// Cut-aware history (a look-ahead pass of a runtime whose scene detector restarts the recurrence: items > 1, not
+	// independent): device array of `items` ints, read by the kernel -- ScenePassState::cutAt.  With c = cutAt[i] >= 0,
+	// item i's history slot h is frame i - h while i - h >= c and exact +0 otherwise, and nothing is taken from
+	// packPrev; with cutAt[i] < 0 the arithmetic above.  The last item's record, written to packOut, is that record.
+	const int *cutAt;
 	const DevPlan *plan;  // developer launch plan of the runtime (null: none -- always in the product library)
 };
 // H x W: the block's resolution (the 128-filter blocks run as one launch only where their 2-row tiles are ONE round of the
@@ -694,6 +699,41 @@ struct SceneSadLaunch {
 	bool resetMode = false;  // a cut raises SceneState::resetNow
 };
 void launchSceneSad(const SceneSadLaunch &q, hipStream_t stream);
+// The detector over the `items` frames of a look-ahead pass in ONE launch (scene_pass_kernel): item i against item i - 1,
+// item 0 against the kept frame, the last item becomes the kept frame; the workgroup that draws the last ticket takes all
+// the decisions in order -- SceneState::prevSad / frames / cuts carried from item to item and from before the pass, one
+// ring record per item -- and leaves what the rest of the pass reads:
+//   resetAt[i] = cut_i && resetMode       (the flag of frame i's scene_clear_kernel)
+//   cutAt[i]   = the latest item <= i with resetAt set, else -1   (the first flow block's cut-aware history)
+// ScenePassState: device memory, zero at creation; acc / ticket are back at zero when a launch ends.
+struct ScenePassState {
+	unsigned long long acc[kFlowBatchMax];
+	unsigned ticket, reserved;
+	unsigned resetAt[kFlowBatchMax];
+	int cutAt[kFlowBatchMax];
+};
+// What changes between two replays of a captured pass, so no kernel argument: host-mapped memory the host writes in front
+// of the launch (a pass is synchronous: nothing reads it while the host writes).
+struct ScenePassDyn {
+	unsigned long long stepBase;  // the record's `step` of item 0
+	unsigned seen;                // frames in the detector's memory in front of item 0: 0, 1, or 2 for two and more
+	unsigned thresholdMilli;
+	unsigned slot;                // ring slot of item 0; item i takes (slot + i) % kSceneRing
+	unsigned reserved;
+};
+struct ScenePassLaunch {
+	int items = 0;  // 1 .. kFlowBatchMax
+	const std::uint8_t *frames[kFlowBatchMax] = {};  // each: BGRX rows, 4-byte aligned, any signed stride of at least a row
+	std::ptrdiff_t strides[kFlowBatchMax] = {};
+	int width = 0, height = 0;
+	std::uint32_t *prev = nullptr;  // the kept frame: read as item 0's predecessor, rewritten as the last item
+	SceneState *state = nullptr;
+	ScenePassState *pass = nullptr;
+	const ScenePassDyn *dyn = nullptr;  // device address of the host-mapped block
+	SceneRecord *ring = nullptr;
+	bool resetMode = false;
+};
+void launchScenePass(const ScenePassLaunch &q, hipStream_t stream);
 // The refusals of ju_set_scene_detect as one message ("" when mode and threshold are fine): mode 0 .. 2, and while the
 // mode is not off a threshold of 1 .. 255000 thousandths of a code value
 std::string sceneDetectProblem(int mode, std::uint32_t thresholdMilli);

@@ -11,6 +11,9 @@
 // scene_clear_kernel: launched behind it over the recurrent inputs of the step (the half of the state and of the frame
 // history its program reads).  Every workgroup loads reset_now once and returns if it is 0; otherwise zeros, written as
 // 16-byte vector stores with byte stores for an unaligned head and tail.  The decision never visits the host.
+//
+// scene_pass_kernel: the detector over the frames of a look-ahead pass in one launch (docs/scene_detect.md "Passes") -- the
+// same sums, item against item, and all the decisions in order in the last workgroup.
 
 #include <hip/hip_runtime.h>
 
@@ -94,6 +97,118 @@ __global__ __launch_bounds__(kSadThreads) void scene_sad_kernel(const std::uint8
 	__hip_atomic_store(&totals->sad, st->cuts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// scene_pass_kernel: scene_sad_kernel over the N frames of a look-ahead pass.  A thread owns its four pixels across ALL
+// items -- it reads the kept frame once, walks the items in order (item j against item j - 1) and writes the last item
+// over the kept frame -- so no workgroup reads a kept pixel another one writes.  The arithmetic per item is
+// scene_sad_kernel's: v_sad_u8 on the three low bytes, u32 partials -> wave sum -> workgroup sum -> one 64-bit integer
+// atomic add per item at agent scope; release, ticket, acquire in the last workgroup, which then takes the N decisions
+// in order.  What differs between two replays of a captured pass (first step, ring slot, predecessors, threshold) is
+// read from the host-mapped ScenePassDyn, by that one thread.
+struct ScenePassParams {
+	const std::uint8_t *frames[kFlowBatchMax];
+	long long strides[kFlowBatchMax];
+	int W, resetMode;
+	long long pixels;
+	std::uint32_t *prev;
+	SceneState *st;
+	ScenePassState *ps;
+	const ScenePassDyn *dyn;
+	SceneRecord *ring;
+};
+
+template <int N>
+__global__ __launch_bounds__(kSadThreads) void scene_pass_kernel(ScenePassParams p) {
+	__shared__ unsigned waveSums[N][kSadThreads / 64];
+	const unsigned base = blockIdx.x * static_cast<unsigned>(kSadPerGroup) + threadIdx.x;
+	const unsigned width = static_cast<unsigned>(p.W), count = static_cast<unsigned>(p.pixels);
+	unsigned partial[N];
+#pragma unroll
+	for (int j = 0; j < N; ++j) partial[j] = 0;
+#pragma unroll
+	for (int k = 0; k < kSadPerThread; ++k) {
+		const unsigned i = base + static_cast<unsigned>(k * kSadThreads);
+		if (i < count) {
+			const unsigned row = i / width, x = i - row * width;
+			unsigned before = p.prev[i];
+#pragma unroll
+			for (int j = 0; j < N; ++j) {
+				const unsigned cur = *reinterpret_cast<const std::uint32_t *>(p.frames[j] + static_cast<long long>(row) * p.strides[j] + x * 4u);
+				partial[j] = __builtin_amdgcn_sad_u8(cur & 0x00ffffffu, before & 0x00ffffffu, partial[j]);
+				before = cur;
+			}
+			p.prev[i] = before;
+		}
+	}
+#pragma unroll
+	for (int j = 0; j < N; ++j) {
+#pragma unroll
+		for (int off = 32; off > 0; off >>= 1) partial[j] += __shfl_down(partial[j], off, 64);
+		if ((threadIdx.x & 63) == 0) waveSums[j][threadIdx.x >> 6] = partial[j];
+	}
+	__syncthreads();
+	if (threadIdx.x != 0) return;
+#pragma unroll
+	for (int j = 0; j < N; ++j) {
+		unsigned long long groupSum = 0;
+#pragma unroll
+		for (int w = 0; w < kSadThreads / 64; ++w) groupSum += waveSums[j][w];
+		__hip_atomic_fetch_add(&p.ps->acc[j], groupSum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	// publish the adds before the ticket (fence, then its wait, then the ticket: in that order)
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	const unsigned ticket = __hip_atomic_fetch_add(&p.ps->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	if (ticket != gridDim.x - 1) return;
+	// ---- the last workgroup of the launch: the N decisions, in order ----
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	const unsigned long long stepBase = __hip_atomic_load(&p.dyn->stepBase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	const unsigned seen = __hip_atomic_load(&p.dyn->seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	const unsigned thresholdMilli = __hip_atomic_load(&p.dyn->thresholdMilli, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	const unsigned slot = __hip_atomic_load(&p.dyn->slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	const unsigned long long pixelBytes = 3ull * static_cast<unsigned long long>(p.pixels);
+	unsigned long long before = p.st->prevSad, frames = p.st->frames, cuts = p.st->cuts;
+	int latest = -1;
+	unsigned reset = 0;
+	for (int j = 0; j < N; ++j) {
+		// read the sum and re-arm the accumulator in one atomic
+		unsigned long long S = __hip_atomic_exchange(&p.ps->acc[j], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const unsigned inMemory = seen + static_cast<unsigned>(j);  // frames in the detector's memory in front of item j
+		if (inMemory < 1) S = 0;  // no predecessor: what the kept frame held is not a frame of this stream
+		unsigned long long D = 0;
+		if (inMemory >= 2) {
+			const unsigned long long delta = S > before ? S - before : before - S;
+			D = S < delta ? S : delta;
+		}
+		const unsigned cut = 1000ull * D >= static_cast<unsigned long long>(thresholdMilli) * pixelBytes ? 1u : 0u;
+		before = S;
+		frames += 1;
+		cuts += cut;
+		reset = (cut && p.resetMode) ? 1u : 0u;
+		if (reset) latest = j;
+		p.ps->resetAt[j] = reset;
+		p.ps->cutAt[j] = latest;
+		SceneRecord *r = p.ring + (slot + static_cast<unsigned>(j)) % static_cast<unsigned>(kSceneRing);
+		__hip_atomic_store(&r->step, stepBase + static_cast<unsigned long long>(j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		__hip_atomic_store(&r->sad, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		__hip_atomic_store(&r->score, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		__hip_atomic_store(&r->cut, cut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	}
+	__hip_atomic_store(&p.ps->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	p.st->prevSad = before;
+	p.st->frames = frames;
+	p.st->cuts = cuts;
+	p.st->resetNow = reset;  // (the last item's; the per-frame detector sets it anew in front of every clear that reads it)
+	SceneRecord *totals = p.ring + kSceneRing;
+	__hip_atomic_store(&totals->step, frames, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&totals->sad, cuts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <int N>
+void launchScenePassN(const ScenePassParams &p, unsigned groups, hipStream_t stream) {
+	hipLaunchKernelGGL(scene_pass_kernel<N>, dim3(groups), dim3(kSadThreads), 0, stream, p);
+}
+
 constexpr int kClearThreads = 256;
 constexpr int kClearVecsPerThread = 4;
 constexpr long long kClearPerGroup = static_cast<long long>(kClearThreads) * kClearVecsPerThread * 16;
@@ -163,6 +278,46 @@ void launchSceneSad(const SceneSadLaunch &q, hipStream_t stream) {
 	    q.width, pixels, q.prev, q.state, q.ring, q.slot, static_cast<unsigned long long>(q.step), q.hasPrev, q.thresholdMilli,
 	    q.resetMode ? 1 : 0);
 	hipCheckLaunch("scene_sad");
+}
+
+void launchScenePass(const ScenePassLaunch &q, hipStream_t stream) {
+	if (q.items < 1 || q.items > kFlowBatchMax) throw std::invalid_argument("scene_pass: 1 .. " + std::to_string(kFlowBatchMax) + " frames");
+	if (q.prev == nullptr || q.state == nullptr || q.pass == nullptr || q.dyn == nullptr || q.ring == nullptr || q.width < 1 ||
+	    q.height < 1 || q.width > kSceneAxisMax || q.height > kSceneAxisMax) {
+		throw std::invalid_argument("scene_pass: null buffer or a size outside 1 .. " + std::to_string(kSceneAxisMax));
+	}
+	const auto row = static_cast<std::ptrdiff_t>(q.width) * 4;
+	ScenePassParams p{};
+	for (int i = 0; i < q.items; ++i) {
+		if (q.frames[i] == nullptr) throw std::invalid_argument("scene_pass: frame " + std::to_string(i) + " is null");
+		if (reinterpret_cast<std::uintptr_t>(q.frames[i]) % 4 != 0 || q.strides[i] % 4 != 0) {
+			throw std::invalid_argument("scene_pass: every frame and its stride must be 4-byte aligned");
+		}
+		if (q.strides[i] > -row && q.strides[i] < row) throw std::invalid_argument("scene_pass: |stride| smaller than a row");
+		p.frames[i] = q.frames[i];
+		p.strides[i] = static_cast<long long>(q.strides[i]);
+	}
+	p.W = q.width;
+	p.resetMode = q.resetMode ? 1 : 0;
+	p.pixels = static_cast<long long>(q.width) * q.height;
+	p.prev = q.prev;
+	p.st = q.state;
+	p.ps = q.pass;
+	p.dyn = q.dyn;
+	p.ring = q.ring;
+	const unsigned groups = static_cast<unsigned>((p.pixels + kSadPerGroup - 1) / kSadPerGroup);
+	static_assert(kFlowBatchMax == 8, "one instantiation per pass length");
+	switch (q.items) {
+	case 1: launchScenePassN<1>(p, groups, stream); break;
+	case 2: launchScenePassN<2>(p, groups, stream); break;
+	case 3: launchScenePassN<3>(p, groups, stream); break;
+	case 4: launchScenePassN<4>(p, groups, stream); break;
+	case 5: launchScenePassN<5>(p, groups, stream); break;
+	case 6: launchScenePassN<6>(p, groups, stream); break;
+	case 7: launchScenePassN<7>(p, groups, stream); break;
+	default: launchScenePassN<8>(p, groups, stream); break;
+	}
+	hipCheckLaunch("scene_pass");
 }
 
 void launchSceneClear(const unsigned *flag, void *a, std::size_t aBytes, void *b, std::size_t bBytes, hipStream_t stream) {
