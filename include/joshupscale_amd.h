@@ -378,8 +378,9 @@ JU_API int ju_reset(ju_runtime *runtime);
  * staging buffers (scale, the staged graph, blend, stage-out): no direct device path, no look-ahead or group pass
  * ("lookahead_frames" / "group_frames" do not count them, "source_stage_frames" does), ju_prepare_frames /
  * ju_prepare_batch capture nothing.  JU_LOC_GRAPHICS_RESOURCE inputs are refused while a source size is set (outputs,
- * and inputs under a mask alone, are taken).  Turning both off restores the other paths.
- * Not provided: scaled or masked frames inside look-ahead or group passes; Lanczos or any other filter whose weights
+ * and inputs under a mask alone, are taken).  Turning both off restores the other paths.  ju_set_stage_lookahead
+ * (below, behind ju_set_output_size) lifts this for the look-ahead passes of ju_process_batch and ju_process_frames.
+ * Not provided: scaled or masked frames inside group passes; Lanczos or any other filter whose weights
  * need a transcendental function (they would not be defined bit for bit: docs/source_stage.md); OBS's own
  * OBS_EFFECT_BILINEAR_LOWRES arithmetic (it is not in the reference tree).  The scaler on the output side is
  * ju_set_output_size, below. */
@@ -414,9 +415,47 @@ JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
  * While it is set frames are routed as for a source size: one by one through the staging buffers, no direct device path,
  * no look-ahead or group pass ("source_stage_frames" counts them), ju_prepare_* capture nothing.  A JU_LOC_DEVICE BGRX
  * output is written in place, any alignment and signed stride.  JU_LOC_GRAPHICS_RESOURCE outputs are refused.
- * ju_get_stat: "output_scaled" (1 / 0), "output_filter" (the JU_SCALE_* value in effect, 0 while off). */
+ * ju_get_stat: "output_scaled" (1 / 0), "output_filter" (the JU_SCALE_* value in effect, 0 while off).
+ * ju_set_stage_lookahead, below, lifts the "no look-ahead pass" for ju_process_batch and ju_process_frames. */
 JU_API int ju_set_output_size(ju_runtime *runtime, size_t width, size_t height, int filter);
 JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height);
+
+/* ---- scaled and masked frames inside look-ahead passes (docs/source_stage.md, docs/output_stage.md: "Passes") ----------
+ * ju_set_stage_lookahead(rt, 1): while a source size, a mask or an output size is set, ju_process_batch and
+ * ju_process_frames form their look-ahead passes again, under all their usual rules (the cap, the overlap splitter, host
+ * and YUV frames, the scene detector with ju_set_scene_lookahead), and the passes carry the stages.  Every output byte,
+ * the state and the frame history equal those of the same frames sent one by one.  The default is 0: such frames run one
+ * by one, as described above, byte for byte and stat for stat.  A value other than 0 or 1 is JU_ERR_INVALID_ARGUMENT
+ * ("ju_set_stage_lookahead: on must be 0 or 1, got N"); the call waits for the stream; ju_reset keeps the setting.
+ *
+ * Eligibility.  A frame of a pass must be the source size on its input side if one is set, else the model's input, and
+ * the output size on its output side if one is set, else the model's output.  A JU_LOC_DEVICE BGRX image on a side that
+ * a scaler touches is read / written where it is, at any alignment and any signed stride; on a side that no scaler
+ * touches it keeps the conditions of the plain passes (input 4-byte, output 8-byte aligned address and stride; direct
+ * device access not turned off), else the frame runs on its own.  Host and YUV sides are taken as in plain passes.
+ * JU_LOC_GRAPHICS_RESOURCE frames are refused or run one by one, as without the setting.  The size and parity checks of
+ * every frame of the call run before anything is launched.
+ *
+ * Inside a pass: host sources upload at source size and YUV sources are decoded at source size, all in one launch; ONE
+ * launch then scales all the pass's sources to the model's input, in front of the scene detector and the flow net, which
+ * read exactly the frame they read one by one.  Behind each frame's last kernel, in stream order: the mask blend in
+ * place, then the output scaler and the encode by the rules of ju_set_output_size -- a deep format from that frame's own
+ * f16 state, or from the blended / scaled 8-bit frame while a mask is set or "hbd_from_state" is 0.
+ *
+ * Unchanged by the setting: ju_process, ju_enqueue, ju_process_frame, ju_enqueue_frame, ju_process_group and the C++
+ * processImage keep the staged single-frame route while a stage is set; ju_prepare_batch / ju_prepare_frames capture
+ * nothing while one is (a staged pass captures its graph at the second sighting of its buffers).
+ *
+ * Memory.  The pass keeps slots per frame of the look-ahead cap, made when first needed at the sizes set and dropped,
+ * with the staged passes' graphs, whenever ju_set_source_size, ju_set_source_mask, ju_set_output_size or this call
+ * changes anything: a model-size input and output (4 bytes per pixel each), a source-size BGRX frame for a host or YUV
+ * source, and for a host or YUV output an 8-bit frame at output size (4 bytes per pixel; 33 MB at 3840x2160) plus, for a
+ * deep format from the state, a 16-bit frame (8 bytes per pixel; 66 MB at 3840x2160) -- each times the cap (8).
+ *
+ * ju_get_stat: "stage_lookahead" (1 / 0) and "lookahead_staged_frames", the frames that went through a pass while a
+ * stage setting was on; "lookahead_frames", "lookahead_host_frames" / "lookahead_yuv_frames" and "source_stage_frames"
+ * count them too (the last says what a frame went through, not which route it took). */
+JU_API int ju_set_stage_lookahead(ju_runtime *runtime, int on);
 
 /* ---- scene cuts: detected on the GPU, the recurrence restarted at them (docs/scene_detect.md) -----------------------------
  * Every frame is built from the previous output warped by a flow field and from three frames of history; across a hard
@@ -460,7 +499,7 @@ JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *
  * detector setting.  The default is 0 (the paragraph above); a value other than 0 or 1 is JU_ERR_INVALID_ARGUMENT; the
  * call waits for the stream; ju_reset and ju_set_scene_detect keep the setting.  ju_get_stat: "scene_lookahead" (1 / 0),
  * "scene_pass_frames" (frames whose detector step ran inside a pass; "lookahead_frames" counts them too).  Frames under
- * a source size, an output size or a mask stay one by one.  Not provided: group passes for a detecting runtime --
+ * a source size, an output size or a mask stay one by one unless ju_set_stage_lookahead is set.  Not provided: group passes for a detecting runtime --
  * ju_process_group runs it member by member whatever this setting. */
 enum { JU_SCENE_OFF = 0, JU_SCENE_REPORT = 1, JU_SCENE_RESET = 2 };
 typedef struct ju_scene_info {

@@ -185,6 +185,14 @@ JU_API int ju_debug_scene_pass(int count, const void *const *frames, const ptrdi
 JU_API int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height,
     const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height, int *start, int *count, int16_t *taps);
 
+/* The sources of a look-ahead pass scaled in one launch (scale_bgrx_items_kernel; docs/source_stage.md "Passes"): ONE
+ * synchronous launch over `count` (1 .. 8) items on caller-supplied device buffers, on the current device.  Item i reads
+ * BGRX rows of src_width x src_height at src[i] with the signed stride src_strides[i] and writes dst_width x dst_height
+ * at dst[i] with dst_strides[i], any byte alignment each; sizes (1 .. 32768) and `filter` (a JU_SCALE_* value, held to
+ * its ratio limits) are shared by all items.  Per item the bytes of ju_debug_scale op 0. */
+JU_API int ju_debug_scale_items(int count, int filter, void *const *dst, const ptrdiff_t *dst_strides, size_t dst_width,
+    size_t dst_height, const void *const *src, const ptrdiff_t *src_strides, size_t src_width, size_t src_height);
+
 /* The temporal output filter alone (launchTemporalFilter: zero_words_kernel, temporal_reduce_kernel, temporal_blend_kernel;
  * tests/temporal_reference.py), on caller-supplied device buffers, on the current device (synchronous).  `state`: the dense
  * f16 tensor [4 height][4 width][4] (8-byte aligned), rewritten in place; `pre_warp`: the same shape, read only; `out`: BGRX

@@ -327,6 +327,10 @@ int ju_set_scene_lookahead(ju_runtime *runtime, int on) {
 	return guarded([&] { engineOf(runtime).setSceneLookahead(on); });
 }
 
+int ju_set_stage_lookahead(ju_runtime *runtime, int on) {
+	return guarded([&] { engineOf(runtime).setStageLookahead(on); });
+}
+
 int ju_reset(ju_runtime *runtime) {
 	return guarded([&] { engineOf(runtime).reset(); });
 }
@@ -691,6 +695,31 @@ int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t d
 		} else {
 			scale.scaleState(src, static_cast<std::uint16_t *>(dst), nullptr);
 		}
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_scale_items(int count, int filter, void *const *dst, const ptrdiff_t *dst_strides, size_t dst_width,
+    size_t dst_height, const void *const *src, const ptrdiff_t *src_strides, size_t src_width, size_t src_height) {
+	return guarded([&] {
+		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_scale_items: count must be 1 .. 8");
+		if (dst == nullptr || dst_strides == nullptr || src == nullptr || src_strides == nullptr) {
+			throw std::invalid_argument("ju_debug_scale_items: NULL array");
+		}
+		constexpr size_t kMost = 1u << 15;
+		if (dst_width < 1 || dst_height < 1 || src_width < 1 || src_height < 1 || dst_width > kMost || dst_height > kMost ||
+		    src_width > kMost || src_height > kMost) {
+			throw std::invalid_argument("ju_debug_scale_items: a size outside 1 .. 32768");
+		}
+		ju::ScaleItems items{};
+		for (int i = 0; i < count; ++i) {
+			if (dst[i] == nullptr || src[i] == nullptr) throw std::invalid_argument("ju_debug_scale_items: NULL buffer");
+			items.item[i] = ju::ScaleItem{static_cast<const std::uint8_t *>(src[i]), src_strides[i], static_cast<std::uint8_t *>(dst[i]),
+			    dst_strides[i]};
+		}
+		ju::Scaler scale;
+		scale.build(src_width, src_height, dst_width, dst_height, filter);
+		scale.scaleBgrxItems(items, count, nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

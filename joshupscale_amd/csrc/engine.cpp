@@ -1863,6 +1863,8 @@ double Engine::stat(const std::string &key) const {
 	if (key == "scene_mode") return static_cast<double>(m_SceneMode);
 	if (key == "scene_lookahead") return m_SceneLookahead ? 1.0 : 0.0;
 	if (key == "scene_pass_frames") return static_cast<double>(m_ScenePassFrames);
+	if (key == "stage_lookahead") return m_StageLookahead ? 1.0 : 0.0;
+	if (key == "lookahead_staged_frames") return static_cast<double>(m_BatchStagedFrames);  // ... of them under a stage setting
 	// (the detector's own counters, as of the steps that have completed: the decision writes them to host-mapped memory)
 	if (key == "scene_frames" || key == "scene_cuts") {
 		const bool cuts = key == "scene_cuts";

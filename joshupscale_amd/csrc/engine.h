@@ -97,14 +97,15 @@ public:
 	// width x height from now on and are scaled to the model's input on the GPU ((0, 0): off; filter: a JU_SCALE_* value --
 	// 0 triangle, 2 Catmull-Rom, 3 Mitchell).  setSourceMask: a BGRX image of any size, host or device, copied now (nullptr: no mask); the source is
 	// drawn over every output frame through it.  While either is set every frame of every entry point runs one by one
-	// through the staged path of submitFrame.  reset() keeps both.
+	// through the staged path of submitFrame -- but for the look-ahead passes setStageLookahead allows.  reset() keeps both.
 	void setSourceSize(std::size_t width, std::size_t height, int filter);
 	void sourceSize(std::size_t *width, std::size_t *height) const;
 	void setSourceMask(const Frame *mask);
 	// The output stage (docs/output_stage.md; engine_frames.cpp, "Output stage").  setOutputSize: output frames are
 	// width x height from now on -- the upscaled frame scaled on the GPU behind the graph and the mask blend ((0, 0): off;
 	// filter: a JU_SCALE_* value, as for the source size).  State, frame history and flow inputs are the unscaled run's.  While it is set
-	// every frame of every entry point runs one by one through submitFrame, as for a source size.  reset() keeps it.
+	// every frame of every entry point runs one by one through submitFrame, as for a source size (setStageLookahead: the
+	// look-ahead passes carry it).  reset() keeps it.
 	void setOutputSize(std::size_t width, std::size_t height, int filter);
 	void outputSize(std::size_t *width, std::size_t *height) const;
 	bool sourceStage() const { return m_SrcScale.set() || m_MaskW != 0 || m_OutScale.set(); }
@@ -119,6 +120,10 @@ public:
 	// a pass"): 0 (default) = such a runtime's frames run one by one, 1 = passes are formed and carry the detector.
 	// Waits for the stream; reset() and setSceneDetect() keep it.
 	void setSceneLookahead(int on);
+	// Look-ahead passes while a source size, a mask or an output size is set (ju_set_stage_lookahead; engine_passes.cpp,
+	// "Scaled and masked frames inside a pass"): 0 (default) = such a runtime's frames run one by one through submitFrame,
+	// 1 = processBatch / processFrames form passes that carry the stages.  Waits for the stream; reset() keeps it.
+	void setStageLookahead(int on);
 
 	FrameSize frameSize() const;
 	int device() const { return m_Device; }
@@ -452,8 +457,16 @@ private:
 		DirectKey io;
 		YuvKey in, out;
 		int scene = 0;  // scenePass() when the pass was bound: no graph serves another detector configuration
+		// stagePass() when the pass was bound: a staged pass and a plain pass over the same buffers never share a graph.
+		// `ends`: what a staged frame's scale, blend and encode launches read and write at the frame's own size -- the
+		// caller's device image or the pass's slot (`io` is then the model-size pair in between)
+		int stage = 0;
+		DirectKey ends{};
 		bool operator<(const PassKey &o) const {
 			if (scene != o.scene) return scene < o.scene;
+			if (stage != o.stage) return stage < o.stage;
+			if (ends < o.ends) return true;
+			if (o.ends < ends) return false;
 			if (io < o.io) return true;
 			if (o.io < io) return false;
 			return std::make_tuple(in.tie(), out.tie()) < std::make_tuple(o.in.tie(), o.out.tie());
@@ -501,6 +514,32 @@ private:
 	    PassSide *side, YuvKey *key);
 	DeviceBuffer m_PassIn[kFlowBatchMax], m_PassOut[kFlowBatchMax];
 	DeviceBuffer m_PassYuvIn[kFlowBatchMax], m_PassYuvOut[kFlowBatchMax];
+	// Scaled and masked frames inside look-ahead passes (setStageLookahead; engine_passes.cpp).  stagePass(): what a pass
+	// formed now carries -- 0 nothing, else bit 0 the source scaler, bit 1 the mask, bit 2 the output scaler; m_PassStage:
+	// that value for the pass bound last (bindBatch; a group pass: 0).  Per frame of the cap, made when first needed at
+	// the sizes set and dropped with the staged passes' graphs whenever a stage setter changes anything (dropStagePasses):
+	// m_StageSrc / m_StageSrcYuv the source-size BGRX frame and host planes, m_StageIn the model-size input the one scale
+	// launch fills, m_StageModelOut the model-size output the network writes under an output size, m_StageOut8 /
+	// m_StageOut16 / m_StageOutYuv the 8-bit frame, the 16-bit frame and the host planes at output size.
+	// m_PassEnds[i]: the frame's rows at its own size (PassKey::ends); m_PassUp / m_PassDown: the device buffers the host
+	// copies of frame i go to / come from (image, planes).
+	bool m_StageLookahead = false;
+	int m_PassStage = 0;
+	int stagePass() const {
+		if (!m_StageLookahead || !sourceStage()) return 0;
+		return (m_SrcScale.set() ? 1 : 0) | (m_MaskW != 0 ? 2 : 0) | (m_OutScale.set() ? 4 : 0);
+	}
+	DeviceBuffer m_StageSrc[kFlowBatchMax], m_StageSrcYuv[kFlowBatchMax], m_StageIn[kFlowBatchMax];
+	DeviceBuffer m_StageModelOut[kFlowBatchMax], m_StageOut8[kFlowBatchMax], m_StageOut16[kFlowBatchMax], m_StageOutYuv[kFlowBatchMax];
+	FrameIO m_PassEnds[kFlowBatchMax];
+	struct PassCopy {
+		DeviceBuffer *image = nullptr, *planes = nullptr;
+	};
+	PassCopy m_PassUp[kFlowBatchMax], m_PassDown[kFlowBatchMax];
+	std::uint64_t m_BatchStagedFrames = 0;
+	void dropStagePasses();
+	// the size frames must have on a side of a pass bound with `stage`
+	void passSizes(int stage, std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const;
 	std::unique_ptr<Stream> m_CopyStream;
 	PinnedWords m_PassSignal;
 	unsigned m_PassSignalBase = 0;
@@ -519,7 +558,8 @@ private:
 	void submitBatch(const AnyFrame *in, const AnyFrame *out, int n);
 	void runBatch(int set, int n, const std::function<void(const Step &, bool)> *around = nullptr);
 	void dropBatchGraphs();
-	std::vector<PassKey> bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set);
+	// stage: stagePass() for a look-ahead pass, 0 for a group pass (which carries no stage, whatever the lead's settings)
+	std::vector<PassKey> bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set, int stage);
 	DirectEntry &batchEntry(const std::vector<PassKey> &key);
 	// Group passes (processGroup).  The model's identity: FNV-1a of the container bytes the engine was built from, and
 	// the dtype it was asked for.  As the lead of a pass: the history each item's first flow block reads / writes (read

@@ -229,6 +229,7 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	if (!unknown.empty()) throw std::invalid_argument("ju_set_source_size: " + unknown);
 	if (width == 0 && height == 0) {
 		m_Stream.synchronize();  // (enqueued frames may still read the tables)
+		if (m_SrcScale.set()) dropStagePasses();
 		m_SrcScale.clear();
 		m_SrcStage = DeviceBuffer();
 		m_SrcYuvStage = DeviceBuffer();
@@ -241,6 +242,7 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	scale.build(width, height, fs.inputWidth, fs.inputHeight, filter);
 	DeviceBuffer stage(width * height * 4), yuvStage(yuvStageBytes(kFormatTable, width, height));
 	m_Stream.synchronize();
+	dropStagePasses();  // (the staged passes' graphs and slots are of the old size and tables)
 	m_SrcScale = std::move(scale);
 	m_SrcStage = std::move(stage);
 	m_SrcYuvStage = std::move(yuvStage);
@@ -255,6 +257,7 @@ void Engine::setSourceMask(const Frame *mask) {
 	DeviceGuard g(m_Device);
 	if (mask == nullptr) {
 		m_Stream.synchronize();
+		if (m_MaskW != 0) dropStagePasses();
 		m_Mask = DeviceBuffer();
 		m_MaskW = m_MaskH = 0;
 		m_MaskStride = 0;
@@ -280,6 +283,7 @@ void Engine::setSourceMask(const Frame *mask) {
 	// (on the null stream and waited for, as a blocking copy is: behind what the caller's own default-stream work wrote)
 	JU_HIP(hipStreamSynchronize(nullptr));
 	m_Stream.synchronize();
+	dropStagePasses();  // (their blend launches hold the old mask's address)
 	m_Mask = std::move(buf);
 	m_MaskW = mask->width;
 	m_MaskH = mask->height;
@@ -302,6 +306,7 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 	if (!problem.empty()) throw std::invalid_argument("ju_set_output_size: " + problem);
 	if (off) {
 		m_Stream.synchronize();  // (enqueued frames may still read the tables and write the buffers)
+		if (m_OutScale.set()) dropStagePasses();
 		m_OutScale.clear();
 		for (DeviceBuffer *b : {&m_OutScaled8, &m_OutScaled16, &m_OutYuvStage, &m_OutRawStage}) *b = DeviceBuffer();
 		return;
@@ -311,6 +316,7 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 	DeviceBuffer scaled8(width * height * 4), scaled16(width * height * 8), raw(width * height * 4);
 	DeviceBuffer yuvStage(yuvStageBytes(kFormatTable, width, height));
 	m_Stream.synchronize();
+	dropStagePasses();
 	m_OutScale = std::move(scale);
 	m_OutScaled8 = std::move(scaled8);
 	m_OutScaled16 = std::move(scaled16);

@@ -154,18 +154,29 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		m_StateBind[set] = keepBind;
 		m_FlowCur = keepFlow;
 	}};
-	// the pass's YUV inputs into their frames' BGRX buffers, all in one launch (a flow-free pass has no launch before it)
+	// the pass's YUV inputs into their frames' BGRX buffers, all in one launch (a flow-free pass has no launch before it):
+	// at the frames' own size -- the model's input, or under a source size the source-size slots (m_PassEnds)
+	const int stage = m_PassStage;
+	std::size_t inW, inH, outW, outH;
+	passSizes(stage, &inW, &inH, &outW, &outH);
 	YuvDecodeItems items{};
 	int decodes = 0;
 	for (int i = 0; i < n; ++i) {
 		const PassFrame &pf = m_BatchHost[i];
 		if (!pf.in.yuv) continue;
-		items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(m_BatchIO[i].in),
-		    m_BatchIO[i].inStride);
+		items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(m_PassEnds[i].in),
+		    m_PassEnds[i].inStride);
 	}
-	if (decodes) {
-		launchYuv420ToBgrxItems(items, decodes, static_cast<int>(m_Config.frameWidth), static_cast<int>(m_Config.frameHeight),
-		    m_Stream);
+	if (decodes) launchYuv420ToBgrxItems(items, decodes, static_cast<int>(inW), static_cast<int>(inH), m_Stream);
+	// a source size: ONE launch scales all n sources -- the caller's device images where they are, the upload slots, the
+	// slots the decode launch above fills -- into the pass's model-size inputs, in front of the detector and the flow net,
+	// which therefore read exactly what submitFrame gives them
+	if (stage & 1) {
+		ScaleItems scale{};
+		for (int i = 0; i < n; ++i) {
+			scale.item[i] = ScaleItem{m_PassEnds[i].in, m_PassEnds[i].inStride, const_cast<std::uint8_t *>(m_BatchIO[i].in), m_BatchIO[i].inStride};
+		}
+		m_SrcScale.scaleBgrxItems(scale, n, m_Stream);
 	}
 	// The scene detector inside a pass: every frame of the pass is in place here (the caller's device frames, the upload
 	// slots, the BGRX buffers the decode launch above fills), so ONE launch takes all n decisions in front of the flow
@@ -206,13 +217,32 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		for (const Step &st : m_Program[set]) {
 			if (st.tag != "flow" && st.tag != "pack") run(st);
 		}
-		if (m_BatchHost[i].out.yuv) {  // the frame's BGRX output (m_PassOut[i]) into the caller's device planes / the staging slot
+		const FrameIO &ends = m_PassEnds[i];
+		const PassSide &po = m_BatchHost[i].out;
+		if (stage & 2) {
+			// the mask, in place over the model-size frame the tail wrote, through submitFrame's `source`: the frame's own
+			// source rows, or the model-size input when no source size is set
+			const FrameSize fs = frameSize();
+			launchMaskBlend(m_BatchIO[i].out, m_BatchIO[i].outStride, static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight),
+			    ends.in, ends.inStride, static_cast<int>(inW), static_cast<int>(inH),
+			    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0),
+			    m_MaskStride, static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), m_Stream);
+		}
+		const std::uint16_t *frame16 = nullptr;
+		if (stage & 4) {  // stageOutScaled's rules: the 8-bit frame, or for a deep format from the state this frame's link
+			if (po.yuv && deepFromState(po.format)) {
+				auto *scaled16 = m_StageOut16[i].as<std::uint16_t>();
+				m_OutScale.scaleState(m_StateBind[set].out, scaled16, m_Stream);
+				frame16 = scaled16;
+			} else {
+				m_OutScale.scaleBgrx(m_BatchIO[i].out, m_BatchIO[i].outStride, ends.out, ends.outStride, m_Stream);
+			}
+		}
+		if (po.yuv) {  // the frame's BGRX output (its slot) into the caller's device planes / the staging slot
 			// (a 10-bit output from the state: THIS frame's link of the chain -- m_BatchState[i], the last frame's
 			// m_State[set ^ 1]; a flow-free pass has one scratch state that the next frame's tail overwrites, so the encode
 			// stays on this stream in front of the next frame's kernels)
-			const FrameSize fs = frameSize();
-			encodeYuv(m_BatchHost[i].out.format, m_BatchHost[i].out.colorspace, m_BatchHost[i].out.planes, fs.outputWidth, fs.outputHeight,
-			    m_BatchIO[i].out, m_BatchIO[i].outStride, m_StateBind[set].out);
+			encodeYuv(po.format, po.colorspace, po.planes, outW, outH, ends.out, ends.outStride, m_StateBind[set].out, frame16);
 		}
 		// (a host frame: its bytes are complete in m_PassOut[i] / m_PassYuvOut[i] -- tell the thread that copies them out)
 		if (m_BatchHost[i].out.host) launchSignalHost(m_PassSignal.device(), m_Stream);
@@ -223,12 +253,16 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 // place (directEligible's conditions) or a host image of the right size (staged through the pass's own device buffers).
 // A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
-	if (sourceStage()) return false;  // (scaled / masked frames run one by one through submitFrame)
+	// (scaled / masked frames run one by one through submitFrame unless the passes carry the stages: setStageLookahead)
+	const int stage = stagePass();
+	if (sourceStage() && !stage) return false;
 	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
 	// unless the pass carries the detector and applies the cuts itself: setSceneLookahead)
 	if (m_SceneMode != 0 && !m_SceneLookahead) return false;
-	const FrameSize fs = frameSize();
-	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align) {
+	std::size_t inW, inH, outW, outH;
+	passSizes(stage, &inW, &inH, &outW, &outH);
+	// scaled: the side's device image is read / written by a scale kernel, which takes any alignment and signed stride
+	auto side = [&](const AnyFrame &a, std::size_t w, std::size_t h, unsigned align, bool scaled) {
 		if (a.yuv) {
 			const YuvFrame &y = a.planes;
 			return (y.location == Location::Host || y.location == Location::Device) && y.width == w && y.height == h;
@@ -237,10 +271,48 @@ bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
 		const auto row = static_cast<std::ptrdiff_t>(w * 4);
 		if (f.ptr == nullptr || f.width != w || f.height != h || !(f.stride >= row || -f.stride >= row)) return false;
 		if (f.location == Location::Host) return true;
+		if (scaled) return f.location == Location::Device;
 		return f.location == Location::Device && m_PreferDirect && reinterpret_cast<std::uintptr_t>(f.ptr) % align == 0 &&
 		       f.stride % static_cast<std::ptrdiff_t>(align) == 0;
 	};
-	return side(in, fs.inputWidth, fs.inputHeight, 4) && side(out, fs.outputWidth, fs.outputHeight, 8);
+	return side(in, inW, inH, 4, (stage & 1) != 0) && side(out, outW, outH, 8, (stage & 4) != 0);
+}
+
+void Engine::passSizes(int stage, std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const {
+	const FrameSize fs = frameSize();
+	*inW = (stage & 1) ? m_SrcScale.srcW() : fs.inputWidth;
+	*inH = (stage & 1) ? m_SrcScale.srcH() : fs.inputHeight;
+	*outW = (stage & 4) ? m_OutScale.dstW() : fs.outputWidth;
+	*outH = (stage & 4) ? m_OutScale.dstH() : fs.outputHeight;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Scaled and masked frames inside a pass (setStageLookahead; docs/source_stage.md and docs/output_stage.md, "Passes").
+// The stages sit outside the recurrence -- the scaler in front of the model's input, blend and output scaler behind the
+// frame the tail wrote -- so a pass takes them as it takes the colour conversions: the n sources are scaled by ONE launch
+// (scale_bgrx_items_kernel) behind the one decode launch and in front of the detector and the flow net; blend, output
+// scale and encode follow each frame's tail in stream order, reading that frame's link of the state chain.  What the
+// network reads and writes in between are the pass's model-size slots (m_StageIn / m_StageModelOut); every launch is the
+// one submitFrame makes, with the same arguments but the buffers, so the bytes are the frame-by-frame route's.
+// ---------------------------------------------------------------------------------------------------------------
+void Engine::setStageLookahead(int on) {
+	if (on != 0 && on != 1) throw std::invalid_argument("ju_set_stage_lookahead: on must be 0 or 1, got " + std::to_string(on));
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();
+	if (m_StageLookahead != (on != 0)) dropStagePasses();
+	m_StageLookahead = on != 0;
+}
+
+// The staged passes' graphs and the slots they are bound to: whenever a stage setter changes anything (the scalers'
+// tables, the mask and the sizes are baked into those graphs).  The stream has drained: passes are synchronous.
+void Engine::dropStagePasses() {
+	m_Stream.synchronize();
+	for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
+		it = (!it->first.empty() && it->first.front().stage != 0) ? m_BatchGraphs.erase(it) : std::next(it);
+	}
+	for (DeviceBuffer *slots : {m_StageSrc, m_StageSrcYuv, m_StageIn, m_StageModelOut, m_StageOut8, m_StageOut16, m_StageOutYuv}) {
+		for (int i = 0; i < kFlowBatchMax; ++i) slots[i] = DeviceBuffer();
+	}
 }
 
 // Binds the n frames of a pass: m_BatchIO[i] = what frame i's kernels read and write -- the caller's device memory, or
@@ -253,22 +325,62 @@ bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
 // the planes those conversion launches read / write.  Device planes: the caller's, in place.  Host planes: slot i of
 // m_PassYuvIn / m_PassYuvOut, plane after plane with rows padded to stagePitch and in the caller's MEMORY order, so a
 // bottom-up plane is addressed from its last row with a negative pitch -- the layout of stageInYuv / stageOutYuv.
-std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set) {
+//
+// A staged pass (stage != 0): a side under a scaler is bound at the size set, to slots of its own (m_StageSrc ... /
+// m_StageOut8 ...), and lands in m_PassEnds[i]; m_BatchIO[i] is then the model-size slot between that scaler and the
+// network.  Without a scaler on a side the two are the same rows.  The slots of a kind are made for the whole cap when
+// the first of them is needed, so no later pass moves what a captured one is bound to.
+std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set, int stage) {
 	const FrameSize fs = frameSize();
+	m_PassStage = stage;
+	std::size_t inW, inH, outW, outH;
+	passSizes(stage, &inW, &inH, &outW, &outH);
+	const bool scaledIn = (stage & 1) != 0, scaledOut = (stage & 4) != 0;
+	const int cap = std::max(n, m_BatchMax);
+	const StageSlotBytes bytes = stageSlotBytes(inW, inH, fs.inputWidth, fs.inputHeight, fs.outputWidth, fs.outputHeight, outW, outH);
+	auto slots = [cap](DeviceBuffer *kind, std::size_t bytes) {
+		for (int k = 0; k < cap; ++k) {
+			if (!kind[k].get()) kind[k] = DeviceBuffer(bytes);
+		}
+	};
 	std::vector<PassKey> key(static_cast<std::size_t>(n));
 	for (int i = 0; i < n; ++i) {
 		FrameIO &io = m_BatchIO[i];
 		PassFrame &pf = m_BatchHost[i];
 		PassKey &k = key[static_cast<std::size_t>(i)];
-		const BoundRows r = bindSide(in[i], fs.inputWidth, fs.inputHeight, &m_PassIn[i], &m_PassYuvIn[i], &pf.in, &k.in);
-		const BoundRows w = bindSide(out[i], fs.outputWidth, fs.outputHeight, &m_PassOut[i], &m_PassYuvOut[i], &pf.out, &k.out);
+		if (scaledIn) {
+			if (in[i].yuv || locationOf(in[i]) == Location::Host) slots(m_StageSrc, bytes.source);
+			if (in[i].yuv && locationOf(in[i]) == Location::Host) slots(m_StageSrcYuv, yuvStageBytes(kFormatTable, inW, inH));
+			slots(m_StageIn, bytes.input);
+		}
+		if (scaledOut) {
+			if (out[i].yuv || locationOf(out[i]) == Location::Host) slots(m_StageOut8, bytes.out8);
+			if (out[i].yuv && locationOf(out[i]) == Location::Host) slots(m_StageOutYuv, yuvStageBytes(kFormatTable, outW, outH));
+			if (out[i].yuv && deepFromState(out[i].planes.format)) slots(m_StageOut16, bytes.out16);
+			slots(m_StageModelOut, bytes.modelOutput);
+		}
+		m_PassUp[i] = scaledIn ? PassCopy{&m_StageSrc[i], &m_StageSrcYuv[i]} : PassCopy{&m_PassIn[i], &m_PassYuvIn[i]};
+		m_PassDown[i] = scaledOut ? PassCopy{&m_StageOut8[i], &m_StageOutYuv[i]} : PassCopy{&m_PassOut[i], &m_PassYuvOut[i]};
+		const BoundRows r = bindSide(in[i], inW, inH, m_PassUp[i].image, m_PassUp[i].planes, &pf.in, &k.in);
+		const BoundRows w = bindSide(out[i], outW, outH, m_PassDown[i].image, m_PassDown[i].planes, &pf.out, &k.out);
 		io = FrameIO{r.ptr, r.stride, w.ptr, w.stride};
+		m_PassEnds[i] = io;
+		if (scaledIn) {
+			io.in = m_StageIn[i].as<std::uint8_t>();
+			io.inStride = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
+		}
+		if (scaledOut) {
+			io.out = m_StageModelOut[i].as<std::uint8_t>();
+			io.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
+		}
 		if (pf.out.host) {
 			if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
 			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
 		}
 		k.io = DirectKey{io.in, io.inStride, io.out, io.outStride, set};
 		k.scene = scenePass();
+		k.stage = stage;
+		if (stage) k.ends = DirectKey{m_PassEnds[i].in, m_PassEnds[i].inStride, m_PassEnds[i].out, m_PassEnds[i].outStride, 0};
 	}
 	return key;
 }
@@ -284,8 +396,8 @@ Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::si
 	if (!image->get()) *image = DeviceBuffer(height * static_cast<std::size_t>(row));
 	auto *base = image->as<std::uint8_t>();
 	if (!a.yuv) {  // a host image: the pass's buffer in the caller's memory order
-		const bool up = a.bgrx.stride >= 0;
-		return {up ? base : base + static_cast<std::ptrdiff_t>(height - 1) * row, up ? row : -row};
+		const SlotRows rows = slotRows(width, height, a.bgrx.stride >= 0);
+		return {base + rows.first, rows.stride};
 	}
 	// a YUV side: the planes its conversion launch addresses, and what of them the graph bakes in
 	const YuvFrame &y = a.planes;
@@ -311,16 +423,17 @@ Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::si
 // engine's stream in front of the pass's launches.  Pageable memory: the runtime stages or page-locks per call, as in
 // stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in stageInYuv.
 void Engine::uploadPassInputs(const AnyFrame *in, int n) {
-	const FrameSize fs = frameSize();
-	const std::size_t rowBytes = fs.inputWidth * 4, rows = fs.inputHeight;
+	std::size_t inW, inH, outW, outH;
+	passSizes(m_PassStage, &inW, &inH, &outW, &outH);  // (a staged pass: at source size, into the source-size slots)
+	const std::size_t rowBytes = inW * 4, rows = inH;
 	for (int i = 0; i < n; ++i) {
 		if (!m_BatchHost[i].in.host) continue;
 		if (in[i].yuv) {
-			copyPlanes(in[i].planes, m_PassYuvIn[i].as<std::uint8_t>(), true, m_Stream);
+			copyPlanes(in[i].planes, m_PassUp[i].planes->as<std::uint8_t>(), true, m_Stream);
 			continue;
 		}
 		const RowSpan host = rowSpan(in[i].bgrx.ptr, in[i].bgrx.stride, rows);
-		copyRows(m_PassIn[i].get(), rowBytes, host.lowest, host.pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream);
+		copyRows(m_PassUp[i].image->get(), rowBytes, host.lowest, host.pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream);
 	}
 }
 
@@ -329,8 +442,9 @@ void Engine::uploadPassInputs(const AnyFrame *in, int n) {
 // that has not arrived never will.  A YUV frame goes out plane by plane from its staging slot (3.1 MB at 1080p instead of
 // BGRX's 8.3 MB), as in stageOutYuv.
 void Engine::drainPassOutputs(const AnyFrame *out, int n) {
-	const FrameSize fs = frameSize();
-	const std::size_t rowBytes = fs.outputWidth * 4, rows = fs.outputHeight;
+	std::size_t inW, inH, outW, outH;
+	passSizes(m_PassStage, &inW, &inH, &outW, &outH);  // (a staged pass: rows and planes at the output size)
+	const std::size_t rowBytes = outW * 4, rows = outH;
 	volatile unsigned *word = m_PassSignal.host();
 	unsigned due = 0;
 	bool any = false;
@@ -352,11 +466,11 @@ void Engine::drainPassOutputs(const AnyFrame *out, int n) {
 		}
 		any = true;
 		if (out[i].yuv) {
-			copyPlanes(out[i].planes, m_PassYuvOut[i].as<std::uint8_t>(), false, *m_CopyStream);
+			copyPlanes(out[i].planes, m_PassDown[i].planes->as<std::uint8_t>(), false, *m_CopyStream);
 			continue;
 		}
 		const RowSpan host = rowSpan(out[i].bgrx.ptr, out[i].bgrx.stride, rows);
-		copyRows(host.lowest, host.pitch, m_PassOut[i].get(), rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, *m_CopyStream);
+		copyRows(host.lowest, host.pitch, m_PassDown[i].image->get(), rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, *m_CopyStream);
 	}
 	if (any) JU_HIP(hipStreamSynchronize(*m_CopyStream));
 }
@@ -391,6 +505,7 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 	if (n < 0 || (n > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("prepareBatch: bad arguments");
 	DeviceGuard g(m_Device);
 	if (n < 2 || n > m_BatchMax || !m_UseGraph || !m_DirectGraph) return 0;
+	if (sourceStage()) return 0;  // (nothing is captured while a stage setting is on, whatever setStageLookahead says)
 	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
 	for (int i = 0; i < n; ++i) {
 		if (!passEligible(anyIn[i], anyOut[i])) return 0;
@@ -399,7 +514,7 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 	std::unique_lock<std::mutex> chain = chainBegin(m_Resident);  // (no capture while another engine's constructor drains the device)
 	int captured = 0;
 	for (int set = 0; set < 2; ++set) {
-		DirectEntry &e = batchEntry(bindBatch(anyIn.data(), anyOut.data(), n, set));
+		DirectEntry &e = batchEntry(bindBatch(anyIn.data(), anyOut.data(), n, set, 0));
 		e.registered = true;
 		if (e.graph.valid()) continue;
 		{
@@ -417,7 +532,8 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 // One look-ahead pass over frames [0, n): enqueue only.  On return the binding set is flipped ONCE (see above).
 void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	const int set = m_Idx;
-	const std::vector<PassKey> key = bindBatch(in, out, n, set);
+	const int stage = stagePass();
+	const std::vector<PassKey> key = bindBatch(in, out, n, set, stage);
 	uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
 	m_PassSignalBase = m_PassSignal.host() ? *m_PassSignal.host() : 0u;
 	const int scene = scenePass();
@@ -460,6 +576,10 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	}
 	m_Idx = set ^ 1;
 	m_BatchFrames += static_cast<std::uint64_t>(n);
+	if (stage) {  // (what the frames went through, whichever route they took: "source_stage_frames" counts them too)
+		m_BatchStagedFrames += static_cast<std::uint64_t>(n);
+		m_SourceFrames += static_cast<std::uint64_t>(n);
+	}
 	if (scene) {  // n detector steps, taken by the pass's one launch
 		m_SceneSeen += static_cast<std::uint64_t>(n);
 		m_SceneSteps += static_cast<std::uint64_t>(n);
@@ -532,6 +652,10 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 			// splitter): the same frames again, one by one, on the per-block kernels
 			m_Idx = set;
 			m_BatchFrames -= static_cast<std::uint64_t>(n);
+			if (m_PassStage) {  // (submitFrame counts the frames again)
+				m_BatchStagedFrames -= static_cast<std::uint64_t>(n);
+				m_SourceFrames -= static_cast<std::uint64_t>(n);
+			}
 			for (int k = 0; k < n; ++k) {
 				m_BatchHostFrames -= m_BatchHost[k].host() ? 1 : 0;
 				m_BatchYuvFrames -= m_BatchHost[k].yuv() ? 1 : 0;
@@ -616,7 +740,8 @@ void Engine::processGroup(Engine *const *members, const Frame *bgrxIn, const Fra
 	std::vector<int> pass, rest;
 	// (a detecting runtime stays member by member, whatever its look-ahead setting: a group pass carries no detector)
 	for (int i = 0; i < count; ++i) {
-		(members[i]->m_SceneMode == 0 && members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
+		// (nor a stage: a scaled or masked member stays on the staged single-frame route, whatever setStageLookahead says)
+		(members[i]->m_SceneMode == 0 && !members[i]->sourceStage() && members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
 	}
 	const int cap = lead.m_BatchMax;
 	if (clash || pass.size() < 2 || cap < 2) {
@@ -647,7 +772,7 @@ void Engine::processGroup(Engine *const *members, const Frame *bgrxIn, const Fra
 void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n) {
 	int sets[kFlowBatchMax];
 	for (int i = 0; i < n; ++i) sets[i] = m[i]->m_Idx;
-	L.bindBatch(in, out, n, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
+	L.bindBatch(in, out, n, 0, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
 	L.uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
 	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
 	// 1. work a member has pending on its own stream (ju_enqueue) runs first

@@ -130,4 +130,26 @@ std::size_t yuvStageBytes(const Table &table, std::size_t w, std::size_t h) {
 	return most;
 }
 
+// A look-ahead pass's own dense BGRX image of width x height bound to a host caller's row order (Engine::bindSide): the
+// image is copied in MEMORY order, so a bottom-up caller's first logical row is the image's last and the kernels walk it
+// with a negative stride.  `first`: the byte offset of the first logical row.
+struct SlotRows {
+	std::size_t first;
+	std::ptrdiff_t stride;
+};
+inline SlotRows slotRows(std::size_t width, std::size_t height, bool topDown) {
+	const std::size_t row = width * 4;
+	return topDown ? SlotRows{0, static_cast<std::ptrdiff_t>(row)} : SlotRows{(height - 1) * row, -static_cast<std::ptrdiff_t>(row)};
+}
+
+// Bytes of the per-frame slots of a staged look-ahead pass (Engine::bindBatch; docs/output_stage.md "Passes"): the BGRX
+// frame at source size, the model-size input and output, the 8-bit and the 16-bit frame at output size.
+struct StageSlotBytes {
+	std::size_t source, input, modelOutput, out8, out16;
+};
+inline StageSlotBytes stageSlotBytes(std::size_t srcW, std::size_t srcH, std::size_t inW, std::size_t inH, std::size_t modelW,
+    std::size_t modelH, std::size_t outW, std::size_t outH) {
+	return {srcW * srcH * 4, inW * inH * 4, modelW * modelH * 4, outW * outH * 4, outW * outH * 8};
+}
+
 }  // namespace ju

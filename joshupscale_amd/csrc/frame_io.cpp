@@ -91,6 +91,11 @@ void Scaler::scaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, std::u
 	    static_cast<int>(m_DstH), m_XDev, m_YDev, m_Span, stream);
 }
 
+void Scaler::scaleBgrxItems(const ScaleItems &items, int count, hipStream_t stream) const {
+	launchScaleBgrxItems(items, count, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), static_cast<int>(m_DstW),
+	    static_cast<int>(m_DstH), m_XDev, m_YDev, m_Span, stream);
+}
+
 void Scaler::scaleState(const void *state, std::uint16_t *dst, hipStream_t stream) const {
 	launchScaleState(state, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), dst, static_cast<int>(m_DstW),
 	    static_cast<int>(m_DstH), m_XDev, m_YDev, m_Span, stream);

@@ -102,6 +102,8 @@ public:
 	// launchScaleBgrx / launchScaleState (kernels.h) with the scaler's sizes and tables
 	void scaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint8_t *dst, std::ptrdiff_t dstStride,
 	    hipStream_t stream) const;
+	// launchScaleBgrxItems: `count` frames of the scaler's sizes in one launch
+	void scaleBgrxItems(const ScaleItems &items, int count, hipStream_t stream) const;
 	void scaleState(const void *state, std::uint16_t *dst, hipStream_t stream) const;
 
 private:

@@ -647,6 +647,21 @@ int scaleSpan(const ScaleAxisHost &x);
 void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, int srcH, std::uint8_t *dst,
     std::ptrdiff_t dstStride, int dstW, int dstH, const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX,
     hipStream_t stream);
+// The sources of a look-ahead pass scaled in one launch (Engine::runBatch): item i of `count` (1 .. kFlowBatchMax) = the
+// source and destination rows of one frame, any byte alignment and signed strides each; sizes, tables and spanX shared by
+// all items.  Per item the bytes of launchScaleBgrx.  ScaleItems is the launch's by-value argument.
+struct ScaleItem {
+	const std::uint8_t *src = nullptr;
+	std::ptrdiff_t srcStride = 0;
+	std::uint8_t *dst = nullptr;
+	std::ptrdiff_t dstStride = 0;
+};
+struct ScaleItems {
+	ScaleItem item[kFlowBatchMax];
+};
+static_assert(sizeof(ScaleItems) <= 256, "the by-value argument of the items kernel must not grow");
+void launchScaleBgrxItems(const ScaleItems &items, int count, int srcW, int srcH, int dstW, int dstH, const ScaleAxisDev &x,
+    const ScaleAxisDev &y, int spanX, hipStream_t stream);
 // The output stage's 16-bit path (docs/output_stage.md): the dense f16 state [srcH][srcW][4] (16-byte aligned) -> the dense
 // u16 frame [dstH][dstW][4] (8-byte aligned; X = 0), out = (sum qy qx P + 2^23) >> 24 with P = floor((s + 0.5) * 65536)
 // saturated, summed exactly (64 bits), clamped to 0 .. 65535 where an axis' filter is cubic.  x / y / spanX as for

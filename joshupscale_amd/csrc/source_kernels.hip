@@ -14,6 +14,8 @@
 //                       N / M apart (ds_read_b32: banks (a / 4) % 32 per 32-lane half), which is a 4-way conflict at
 //                       1920 -> 480; the tile stores column c at c + c / 32, which puts the 32 lanes of every power-
 //                       of-two ratio up to 16 on 32 different banks (and the vertical pass's four-column writes too).
+//   scale_bgrx_items_kernel  the same tile (scaleBgrxTile, the one body of both) over the sources of a look-ahead pass:
+//                       grid.z = item, each with its own pointers and strides from a by-value table.
 //   mask_blend_kernel   a thread per output pixel; mask and source are point sampled.
 //   scale_state_kernel  the output stage's 16-bit path (docs/output_stage.md): scale_bgrx_kernel's tile over the dense f16
 //                       state, each sample first P = floor((s + 0.5) * 65536) saturated (StateSource::sample of
@@ -282,10 +284,11 @@ __device__ inline unsigned scaleResult(T sum) {
 	}
 }
 
+// One tile of scale_bgrx_kernel (the head of the file): the workgroup's tile is blockIdx.x, blockIdx.y.  THE body of both
+// launch forms -- the single frame and the items of a look-ahead pass -- so their bytes are equal by construction.
 template <bool kSigned>
-__global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
-    int srcW, std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW, int dstH, ScaleTaps ax,
-    ScaleTaps ay, int pitch) {
+__device__ __forceinline__ void scaleBgrxTile(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride, int srcW,
+    std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW, int dstH, ScaleTaps ax, ScaleTaps ay, int pitch) {
 	using Tap = typename ScaleForm<kSigned>::Tap;
 	using Sum = typename ScaleForm<kSigned>::Sum;
 	using Wide = typename ScaleForm<kSigned>::Sum8;
@@ -355,6 +358,24 @@ __global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__r
 	}
 	storePixel(dst + static_cast<std::ptrdiff_t>(dy) * dstStride + 4 * dx, scaleResult<kSigned, 255>(b) |
 	    (scaleResult<kSigned, 255>(g) << 8) | (scaleResult<kSigned, 255>(r) << 16));
+}
+
+template <bool kSigned>
+__global__ __launch_bounds__(256) void scale_bgrx_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
+    int srcW, std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW, int dstH, ScaleTaps ax,
+    ScaleTaps ay, int pitch) {
+	scaleBgrxTile<kSigned>(src, srcStride, srcW, dst, dstStride, dstW, dstH, ax, ay, pitch);
+}
+
+// The sources of a look-ahead pass in one launch (Engine::runBatch; docs/source_stage.md "Passes"): grid (tiles x, tiles
+// y, item), item blockIdx.z of the by-value table with its own pointers and strides -- a workgroup reads its item's four
+// words from the kernel arguments with scalar loads, uniform over the workgroup.  Sizes, taps and pitch are the launch's;
+// the 16-byte path is decided per item inside the tile, from the item's own address and stride.
+template <bool kSigned>
+__global__ __launch_bounds__(256) void scale_bgrx_items_kernel(ScaleItems items, int srcW, int dstW, int dstH, ScaleTaps ax,
+    ScaleTaps ay, int pitch) {
+	const ScaleItem &it = items.item[blockIdx.z];
+	scaleBgrxTile<kSigned>(it.src, it.srcStride, srcW, it.dst, it.dstStride, dstW, dstH, ax, ay, pitch);
 }
 
 // P of one f16 of the state, as StateSource::sample (colour_kernels.hip) forms it: exact in f32
@@ -483,6 +504,27 @@ void launchScaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW
 	const auto kernel = x.filter != kScaleTriangle ? scale_bgrx_kernel<true> : scale_bgrx_kernel<false>;  // (spanX is of that form too)
 	hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, src, srcStride, srcW, dst, dstStride, dstW, dstH, tx, ty, pitch);
 	hipCheckLaunch("scale_bgrx");
+}
+
+void launchScaleBgrxItems(const ScaleItems &items, int count, int srcW, int srcH, int dstW, int dstH, const ScaleAxisDev &x,
+    const ScaleAxisDev &y, int spanX, hipStream_t stream) {
+	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("launchScaleBgrxItems: 1 .. 8 items");
+	if (srcW < 1 || srcH < 1 || dstW < 1 || dstH < 1 || spanX < 4 || spanX % 4) {
+		throw std::invalid_argument("launchScaleBgrxItems: bad arguments");
+	}
+	for (int i = 0; i < count; ++i) {
+		if (items.item[i].src == nullptr || items.item[i].dst == nullptr) throw std::invalid_argument("launchScaleBgrxItems: bad arguments");
+	}
+	const int pitch = spanX + spanX / 32 + 1;
+	const std::size_t lds = static_cast<std::size_t>(3) * kScaleTileH * static_cast<std::size_t>(pitch) * sizeof(unsigned);
+	if (lds > 64 * 1024) throw std::invalid_argument("launchScaleBgrxItems: the tile does not fit the LDS");
+	const dim3 grid(static_cast<unsigned>((dstW + kScaleTileW - 1) / kScaleTileW),
+	    static_cast<unsigned>((dstH + kScaleTileH - 1) / kScaleTileH), static_cast<unsigned>(count));
+	const ScaleTaps tx{x.start, x.taps}, ty{y.start, y.taps};
+	if (x.filter != y.filter) throw std::invalid_argument("launchScaleBgrxItems: the two axes' tables must be of one filter");
+	const auto kernel = x.filter != kScaleTriangle ? scale_bgrx_items_kernel<true> : scale_bgrx_items_kernel<false>;
+	hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, items, srcW, dstW, dstH, tx, ty, pitch);
+	hipCheckLaunch("scale_bgrx_items");
 }
 
 void launchScaleState(const void *state, int srcW, int srcH, std::uint16_t *dst, int dstW, int dstH, const ScaleAxisDev &x,

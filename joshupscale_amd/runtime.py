@@ -212,6 +212,7 @@ _PRODUCT_SIGS = {
     "ju_get_scene_detect": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_uint32)]),
     "ju_get_scene_info": (C.c_int, [C.c_void_p, _P(JuSceneInfo), C.c_int, _P(C.c_int)]),
     "ju_set_scene_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
+    "ju_set_stage_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_set_source_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_get_source_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
@@ -260,6 +261,8 @@ _HOOK_SIGS = {
                                       _P(C.c_int32)]),
     "ju_debug_scale": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ju_debug_scale_items": (C.c_int, [C.c_int, C.c_int, _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
+                                       _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t]),
     "ju_debug_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                     C.c_float, C.c_float, C.c_float, C.c_int, C.c_uint, C.c_void_p, C.c_size_t]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
@@ -449,6 +452,13 @@ class Runtime:
         value other than 0 or 1 raises :class:`JoshUpscaleError` with the C layer's message."""
         _check(self._lib, self._lib.ju_set_scene_lookahead(self._h, int(on)))
 
+    def set_stage_lookahead(self, on) -> None:
+        """``ju_set_stage_lookahead``: 1 = ``process_batch`` / ``process_frames`` form look-ahead passes while a source
+        size, a mask or an output size is set, and the passes carry those stages (docs/source_stage.md and
+        docs/output_stage.md, "Passes"); 0 (the default) = such frames run one by one.  A value other than 0 or 1 raises
+        :class:`JoshUpscaleError` with the C layer's message."""
+        _check(self._lib, self._lib.ju_set_stage_lookahead(self._h, int(on)))
+
     # -- the source stage (docs/source_stage.md) ----------------------------------
     def set_source_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
         """``ju_set_source_size``: input frames are ``width x height`` from now on and are scaled to the model's input on
@@ -632,7 +642,7 @@ class Runtime:
         "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "output_select", "lookahead_frames",
         "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames",
         "output_scaled", "source_filter", "output_filter", "scene_mode", "scene_frames", "scene_cuts", "scene_lookahead",
-        "scene_pass_frames"."""
+        "scene_pass_frames", "stage_lookahead", "lookahead_staged_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
