@@ -167,8 +167,9 @@ typedef struct ju_image {
  * no NV16 / NV21, no other chroma siting); RGB without 12-bit, without dithering and without alpha (X, and the two top
  * bits of an x2rgb10 / x2bgr10 word, are ignored and written 0); float inputs are quantised to 8 bits like every input,
  * they do not reach the network unquantised; no YUV or RGB graphics resources (GL textures stay BGRX); look-ahead passes
- * take these frames through ju_process_frames (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX), not
- * ju_process_group; the C++ plugin surface (JoshUpscale/core.h) is unchanged and takes BGRX only. */
+ * take these frames through ju_process_frames (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX) and
+ * group passes through ju_process_group_frames (ju_process_group takes ju_image); the C++ plugin surface
+ * (JoshUpscale/core.h) is unchanged and takes BGRX only. */
 enum { JU_FMT_BGRX = 0, JU_FMT_I420 = 1, JU_FMT_NV12 = 2, JU_FMT_P010 = 3, JU_FMT_I010 = 4 };
 enum {
 	JU_FMT_YUY2 = 16, JU_FMT_UYVY = 17, JU_FMT_I422 = 18, JU_FMT_P210 = 19, JU_FMT_I210 = 20,
@@ -276,8 +277,34 @@ JU_API int ju_prepare_batch(ju_runtime *runtime, const ju_image *inputs, const j
  * Work a member has enqueued (ju_enqueue) runs before its frame; the runtimes may be driven by other calls between
  * group calls (ju_process, ju_process_batch, ju_reset), each by one thread at a time.  Memory: the lead holds the pass's
  * flow tensors -- those of ju_process_batch, about 210 MB at 480x270 for 8 frames, shared with its look-ahead
- * passes; the other members allocate nothing.  ju_get_stat "group_frames": frames a runtime got from group passes. */
+ * passes; the other members allocate nothing.  ju_get_stat "group_frames": frames a runtime got from group passes.
+ * A member whose scene detector is on runs on its own unless it asked to ride (ju_set_scene_group); a member under a
+ * source size, an output size or a mask always runs on its own, on the staged single-frame route. */
 JU_API int ju_process_group(ju_runtime *const *runtimes, const ju_image *inputs, const ju_image *outputs, int count);
+/* ju_process_group on frames of any format: one frame for each of `count` runtimes, synchronously.  Every plane of every
+ * output -- and nothing around it --, every member's recurrent state, frame history and f16 state are those of
+ * ju_process_frame(runtimes[i], &inputs[i], &outputs[i]) for i = 0 .. count-1.  For the stream server whose decoders hand
+ * over NV12 / P010 and whose capture cards hand over YUY2 / v210.  Formats, colour spaces, locations (host or device
+ * planes) and strides of any sign are independent per member and per side, as in ju_process_frames; a call of BGRX frames
+ * only behaves as ju_process_group with the same pointers.
+ * Membership, passes and the member-by-member cases are ju_process_group's; a member's pair rides in a pass where a
+ * look-ahead pass of ju_process_frames would take it, and otherwise runs on its own behind the pass.  An output plane over
+ * any input plane of any member of the call (same address space) sends the whole call member by member in list order.
+ * Inside a pass host planes are uploaded up front into the lead's slots, ONE launch in front of the flow net's decodes
+ * every non-BGRX input of the pass, each member's output is encoded behind that member's own steps on the lead's stream
+ * -- a deep format (P010, BGRX64, RGBPH, Y410, ...) of a runtime with "hbd_from_state" 1 from THAT member's f16 state --
+ * and host outputs are copied out while the next member's kernels run.  Memory: the lead holds one staging slot per
+ * member of a pass and side in use (as ju_process_frames does per frame).
+ * JU_ERR_INVALID_ARGUMENT: whatever ju_process_frame refuses, for ANY member; a NULL array, count < 0, a runtime twice,
+ * runtimes that do not match.  Every pair is checked before anything is launched or uploaded, the message names the
+ * member's index, and no runtime's state, frame history, detector memory or stats change.  count == 0 does nothing;
+ * count == 1 is ju_process_frame.
+ * ju_get_stat "group_yuv_frames": frames of a runtime that went through a group pass with a non-BGRX side (also counted
+ * by "group_frames").
+ * Not provided: members under a source size, an output size or a mask inside group passes (they stay on the staged
+ * single-frame route); graph capture of group passes (they are eager launches); a ju_prepare_* counterpart; the C++
+ * plugin surface. */
+JU_API int ju_process_group_frames(ju_runtime *const *runtimes, const ju_frame *inputs, const ju_frame *outputs, int count);
 
 /* Asynchronous form for JU_LOC_DEVICE images: enqueues the same work on the
  * runtime's stream and returns; ju_synchronize() waits.  Frames are still
@@ -313,8 +340,8 @@ JU_API int ju_process_frame(ju_runtime *runtime, const ju_frame *input, const ju
  * ju_get_stat "lookahead_yuv_frames": frames with a YUV side that went through passes (also counted by
  * "lookahead_frames" and, with a host side, "lookahead_host_frames").
  * Not provided: a ju_prepare_* counterpart (an unregistered tuple of device planes is captured at its second use, as in
- * ju_process_batch; all-host passes of one shape share one graph); YUV frames in ju_process_group; the C++ plugin
- * surface. */
+ * ju_process_batch; all-host passes of one shape share one graph); the C++ plugin surface.  (Group passes take these
+ * frames through ju_process_group_frames.) */
 JU_API int ju_process_frames(ju_runtime *runtime, const ju_frame *inputs, const ju_frame *outputs, int count);
 /* Asynchronous form (like ju_enqueue): JU_LOC_DEVICE frames only -- a host frame is JU_ERR_INVALID_ARGUMENT;
  * ju_synchronize waits. */
@@ -487,7 +514,7 @@ JU_API int ju_set_stage_lookahead(ju_runtime *runtime, int on);
  * from a history a cut inside it would invalidate): ju_process_batch, ju_process_frames and ju_process_group run such
  * a runtime's frames one by one in stream order ("lookahead_frames" / "group_frames" do not count them), and
  * ju_prepare_batch captures nothing; ju_prepare_frames works as before and the direct device path and its graphs stay
- * in use.  Turning the mode off restores the passes.
+ * in use.  Turning the mode off restores the passes; the two settings below let the passes carry the detector.
  *
  * ju_set_scene_lookahead(rt, 1) lifts that for look-ahead passes: ju_process_batch and ju_process_frames form their
  * passes under all their usual rules (the cap, the overlap splitter, eligibility, host and YUV frames) and
@@ -499,8 +526,22 @@ JU_API int ju_set_stage_lookahead(ju_runtime *runtime, int on);
  * detector setting.  The default is 0 (the paragraph above); a value other than 0 or 1 is JU_ERR_INVALID_ARGUMENT; the
  * call waits for the stream; ju_reset and ju_set_scene_detect keep the setting.  ju_get_stat: "scene_lookahead" (1 / 0),
  * "scene_pass_frames" (frames whose detector step ran inside a pass; "lookahead_frames" counts them too).  Frames under
- * a source size, an output size or a mask stay one by one unless ju_set_stage_lookahead is set.  Not provided: group passes for a detecting runtime --
- * ju_process_group runs it member by member whatever this setting. */
+ * a source size, an output size or a mask stay one by one unless ju_set_stage_lookahead is set.  Group passes have a
+ * setting of their own, whatever this one says:
+ *
+ * ju_set_scene_group(rt, 1) lets this runtime ride in the passes of ju_process_group and ju_process_group_frames while
+ * its detector is on (JU_SCENE_REPORT or JU_SCENE_RESET).  The members of a pass are independent streams, so a pass
+ * needs no cut-aware history: ONE launch behind the decode launch and in front of the flow net's takes the decision of
+ * every detecting member -- each against its own kept frame, with its own mode and threshold, into its own records --
+ * and in JU_SCENE_RESET mode ONE more zeroes the recurrent inputs (state and frame history) of the members that cut, on
+ * the GPU.  For every member, every output byte, the state, the history and every ju_scene_info record equal those of the
+ * same frames sent through ju_process / ju_process_frame with the same detector setting; step numbers continue from
+ * wherever the member stands, and ju_get_scene_info, the cumulative counters and the predecessor bits advance per member
+ * as one per-frame step does.  The setting is per member: members with the detector off, with it on and the setting on,
+ * and with it on and the setting off (these run alone, as before) may be mixed in one call; the lead needs no detector.
+ * The default is 0 (the paragraph above); a value other than 0 or 1 is JU_ERR_INVALID_ARGUMENT; the call waits for the
+ * stream; ju_reset and ju_set_scene_detect keep the setting.  ju_get_stat: "scene_group" (1 / 0), "scene_group_frames"
+ * (frames whose detector step ran inside a group pass; "group_frames" counts them too). */
 enum { JU_SCENE_OFF = 0, JU_SCENE_REPORT = 1, JU_SCENE_RESET = 2 };
 typedef struct ju_scene_info {
 	uint64_t step, sad, score; /* the detector step, S_t, D_t */
@@ -510,6 +551,7 @@ JU_API int ju_set_scene_detect(ju_runtime *runtime, int mode, uint32_t threshold
 JU_API int ju_get_scene_detect(const ju_runtime *runtime, int *mode, uint32_t *threshold_milli);
 JU_API int ju_get_scene_info(ju_runtime *runtime, ju_scene_info *out, int count, int *written);
 JU_API int ju_set_scene_lookahead(ju_runtime *runtime, int on);
+JU_API int ju_set_scene_group(ju_runtime *runtime, int on); /* default 0 */
 
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing
@@ -567,7 +609,8 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * "prepared_captures"), "registered_pairs", "direct_graphs"
  * (graphs cached for JU_LOC_DEVICE frame tuples), "resident_tower" / "resident_flow"
  * (1 when the one-launch tower kernel is in use), "launches_per_frame", "tower_variant",
- * "group_frames" (frames this runtime got from ju_process_group passes),
+ * "group_frames" (frames this runtime got from ju_process_group / ju_process_group_frames passes; of them
+ * "group_yuv_frames" with a non-BGRX side),
  * "lookahead_frames" (frames that went through look-ahead passes; of them "lookahead_host_frames" with a host side,
  * "lookahead_yuv_frames" with a YUV side, 8- or 10-bit),
  * "source_scaled" / "source_mask" (1 while ju_set_source_size / ju_set_source_mask is in effect), "source_stage_frames"

@@ -66,7 +66,9 @@ JU_API int ju_plan_report(ju_runtime *runtime, char *dst, size_t capacity, size_
  * and the frames run again without it); "step_rerun" 1 (the same for a single frame: ju_process
  * and the frame-by-frame steps of the multi-frame calls submit every frame a second time, as after a resident-tower
  * report but without the fallback; the scene detector must not run for the second submission: ju_get_stat
- * "scene_detector_runs" counts its runs). */
+ * "scene_detector_runs" counts its runs); "group_rerun" 1 ("pass_rerun" for the passes of ju_process_group and
+ * ju_process_group_frames: a group pass that completed normally is run again member by member; members whose detector
+ * the pass carried keep its decisions and run again without it). */
 JU_API int ju_debug_set(const char *key, int value);
 
 /* The loader's e4m3 quantiser (round to nearest even, saturating at +-448), exposed so
@@ -172,6 +174,25 @@ JU_API int ju_debug_scene(int op, const void *frame, ptrdiff_t stride, size_t wi
 JU_API int ju_debug_scene_pass(int count, const void *const *frames, const ptrdiff_t *strides, size_t width, size_t height,
     void *prev, void *state, void *pass_state, int has_prev, uint64_t first_step, uint32_t threshold_milli, int reset_mode,
     ju_scene_info *records, uint32_t *reset_at, int32_t *cut_at);
+
+/* scene_group_kernel alone: the detector over the `count` (1 .. 8) INDEPENDENT items of a group pass in one launch
+ * (docs/scene_detect.md "Group passes"), on the current device (synchronous).  Item i: frames[i] / strides[i], device BGRX
+ * rows of width x height at its own 4-byte-aligned address with its own signed stride of at least a row (a multiple of
+ * 4), against prev[i], its own dense kept frame, which is rewritten with it; states[i]: its own 40 bytes of
+ * ju_debug_scene op 0 (every accumulator and every ticket word are zero again when the call returns); has_prev[i] (0, 1
+ * or 3), first_steps[i] (the record's step, and modulo 64 its ring slot), threshold_milli[i] and modes[i]
+ * (JU_SCENE_REPORT or JU_SCENE_RESET) are what the kernel reads from the item's host-mapped words.  frames[i] == NULL:
+ * an absent item -- none of its memory is touched, records[i] and reset_flags[i] are zero.  records[i] receives item i's
+ * decision, reset_flags[i] = cut_i && modes[i] == JU_SCENE_RESET (the state's word 3). */
+JU_API int ju_debug_scene_group(int count, const void *const *frames, const ptrdiff_t *strides, size_t width, size_t height,
+    void *const *prev, void *const *states, const int *has_prev, const uint64_t *first_steps, const uint32_t *threshold_milli,
+    const int *modes, ju_scene_info *records, uint32_t *reset_flags);
+
+/* scene_clear_items_kernel alone: the conditional clear of `count` (1 .. 8) items in one launch.  flags[i]: the device
+ * address of item i's 32-bit flag word (NULL: an absent item); if the word is not 0, a[i][0 .. a_bytes[i]) and
+ * b[i][0 .. b_bytes[i]) become 0, any alignment and any sizes. */
+JU_API int ju_debug_scene_clear_items(int count, const void *const *flags, void *const *a, const size_t *a_bytes,
+    void *const *b, const size_t *b_bytes);
 
 /* The scalers with a filter argument (docs/source_stage.md "Filters"; tests/scale_filter_reference.py); `filter` is a
  * JU_SCALE_* value.  op 0: the 8-bit scaler -- buffers, sizes and strides as ju_debug_source op 0.  op 1: the state

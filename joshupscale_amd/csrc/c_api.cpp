@@ -195,6 +195,26 @@ int ju_process_group(ju_runtime *const *runtimes, const ju_image *inputs, const 
 	});
 }
 
+int ju_process_group_frames(ju_runtime *const *runtimes, const ju_frame *inputs, const ju_frame *outputs, int count) {
+	return guarded([&] {
+		if (count < 0 || (count > 0 && (runtimes == nullptr || inputs == nullptr || outputs == nullptr))) {
+			throw std::invalid_argument("ju_process_group_frames: NULL arguments or a negative count");
+		}
+		std::vector<ju::Engine *> engines(static_cast<std::size_t>(count));
+		std::vector<ju::AnyFrame> in(static_cast<std::size_t>(count)), out(static_cast<std::size_t>(count));
+		for (int i = 0; i < count; ++i) {
+			try {
+				engines[i] = &engineOf(runtimes[i]);
+				in[i] = toAnyFrame(inputs + i);
+				out[i] = toAnyFrame(outputs + i);
+			} catch (const std::invalid_argument &err) {
+				throw std::invalid_argument("ju_process_group_frames: member " + std::to_string(i) + ": " + err.what());
+			}
+		}
+		ju::Engine::processGroupFrames(engines.data(), in.data(), out.data(), count);
+	});
+}
+
 int ju_prepare_batch(ju_runtime *runtime, const ju_image *inputs, const ju_image *outputs, int count, int *captured) {
 	if (captured) *captured = 0;
 	return guarded([&] {
@@ -327,6 +347,10 @@ int ju_set_scene_lookahead(ju_runtime *runtime, int on) {
 	return guarded([&] { engineOf(runtime).setSceneLookahead(on); });
 }
 
+int ju_set_scene_group(ju_runtime *runtime, int on) {
+	return guarded([&] { engineOf(runtime).setSceneGroup(on); });
+}
+
 int ju_set_stage_lookahead(ju_runtime *runtime, int on) {
 	return guarded([&] { engineOf(runtime).setStageLookahead(on); });
 }
@@ -453,6 +477,7 @@ int ju_debug_set(const char *key, int value) {
 		else if (k == "fp8_block_form") ju::setFp8BlockForm(value);
 		else if (k == "pass_rerun") ju::setPassRerun(value);
 		else if (k == "step_rerun") ju::setStepRerun(value);
+		else if (k == "group_rerun") ju::setGroupRerun(value);
 		else throw std::invalid_argument("unknown debug key " + k);
 	});
 }
@@ -811,6 +836,77 @@ int ju_debug_scene_pass(int count, const void *const *frames, const ptrdiff_t *s
 			reset_at[i] = after.resetAt[i];
 			cut_at[i] = after.cutAt[i];
 		}
+	});
+}
+
+int ju_debug_scene_group(int count, const void *const *frames, const ptrdiff_t *strides, size_t width, size_t height,
+    void *const *prev, void *const *states, const int *has_prev, const uint64_t *first_steps, const uint32_t *threshold_milli,
+    const int *modes, ju_scene_info *records, uint32_t *reset_flags) {
+	return guarded([&] {
+		static_assert(sizeof(ju::SceneState) == 40, "the layout include/joshupscale_amd_test.h describes");
+		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_scene_group: count must be 1 .. 8");
+		if (frames == nullptr || strides == nullptr || prev == nullptr || states == nullptr || has_prev == nullptr ||
+		    first_steps == nullptr || threshold_milli == nullptr || modes == nullptr || records == nullptr || reset_flags == nullptr) {
+			throw std::invalid_argument("ju_debug_scene_group: NULL array");
+		}
+		const std::size_t ringBytes = sizeof(ju::SceneRecord) * (ju::kSceneRing + 1);
+		ju::PinnedWords rings(ringBytes * static_cast<std::size_t>(count));
+		ju::PinnedWords dynWords(sizeof(ju::SceneGroupDyn) * static_cast<std::size_t>(count));
+		auto *dyn = reinterpret_cast<volatile ju::SceneGroupDyn *>(dynWords.host());
+		ju::SceneGroupLaunch q;
+		q.items = count;
+		q.width = static_cast<int>(std::min<size_t>(width, 1u << 20));
+		q.height = static_cast<int>(std::min<size_t>(height, 1u << 20));
+		for (int i = 0; i < count; ++i) {
+			records[i] = ju_scene_info{};
+			reset_flags[i] = 0;
+			if (frames[i] == nullptr) continue;  // an absent item
+			const std::string who = "ju_debug_scene_group: item " + std::to_string(i);
+			if (has_prev[i] != 0 && has_prev[i] != 1 && has_prev[i] != 3) throw std::invalid_argument(who + ": has_prev must be 0, 1 or 3");
+			if (modes[i] != 1 && modes[i] != 2) throw std::invalid_argument(who + ": mode must be JU_SCENE_REPORT (1) or JU_SCENE_RESET (2)");
+			dyn[i].step = first_steps[i];
+			dyn[i].slotHasPrev = (first_steps[i] % ju::kSceneRing) | (static_cast<unsigned long long>(has_prev[i]) << 32);
+			dyn[i].thresholdMode = static_cast<unsigned long long>(threshold_milli[i]) | (static_cast<unsigned long long>(modes[i]) << 32);
+			ju::SceneGroupItem &it = q.item[i];
+			it.frame = static_cast<const std::uint8_t *>(frames[i]);
+			it.stride = strides[i];
+			it.prev = static_cast<std::uint32_t *>(prev[i]);
+			it.state = static_cast<ju::SceneState *>(states[i]);
+			it.ring = reinterpret_cast<ju::SceneRecord *>(reinterpret_cast<unsigned char *>(rings.device()) + ringBytes * static_cast<std::size_t>(i));
+			it.dyn = reinterpret_cast<const ju::SceneGroupDyn *>(dynWords.device()) + i;
+		}
+		ju::launchSceneGroup(q, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+		for (int i = 0; i < count; ++i) {
+			if (frames[i] == nullptr) continue;
+			const auto *ring = reinterpret_cast<const volatile ju::SceneRecord *>(
+			    reinterpret_cast<const volatile unsigned char *>(rings.host()) + ringBytes * static_cast<std::size_t>(i));
+			const volatile ju::SceneRecord &rec = ring[first_steps[i] % ju::kSceneRing];
+			records[i].step = rec.step;
+			records[i].sad = rec.sad;
+			records[i].score = rec.score;
+			records[i].cut = rec.cut;
+			records[i].reserved = 0;
+			ju::SceneState after;
+			JU_HIP(hipMemcpy(&after, states[i], sizeof(after), hipMemcpyDeviceToHost));
+			reset_flags[i] = after.resetNow;
+		}
+	});
+}
+
+int ju_debug_scene_clear_items(int count, const void *const *flags, void *const *a, const size_t *a_bytes, void *const *b,
+    const size_t *b_bytes) {
+	return guarded([&] {
+		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_scene_clear_items: count must be 1 .. 8");
+		if (flags == nullptr || a == nullptr || a_bytes == nullptr || b == nullptr || b_bytes == nullptr) {
+			throw std::invalid_argument("ju_debug_scene_clear_items: NULL array");
+		}
+		ju::SceneClearItem items[ju::kFlowBatchMax];
+		for (int i = 0; i < count; ++i) {
+			items[i] = ju::SceneClearItem{static_cast<const unsigned *>(flags[i]), a[i], a_bytes[i], b[i], b_bytes[i]};
+		}
+		ju::launchSceneClearItems(items, count, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }
 

@@ -1860,6 +1860,9 @@ double Engine::stat(const std::string &key) const {
 	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
+	if (key == "group_yuv_frames") return static_cast<double>(m_GroupYuvFrames);  // ... of them with a non-BGRX side
+	if (key == "scene_group") return m_SceneGroup ? 1.0 : 0.0;
+	if (key == "scene_group_frames") return static_cast<double>(m_SceneGroupFrames);  // detector steps taken inside group passes
 	if (key == "scene_mode") return static_cast<double>(m_SceneMode);
 	if (key == "scene_lookahead") return m_SceneLookahead ? 1.0 : 0.0;
 	if (key == "scene_pass_frames") return static_cast<double>(m_ScenePassFrames);

@@ -38,6 +38,9 @@ void setPassRerun(int on);
 // Test flavour only (ju_debug_set "step_rerun"): process() treats every frame that completed normally as one whose
 // resident tower reported -- binding set restored, the frame submitted again -- without the fallback to the per-block kernels.
 void setStepRerun(int on);
+// Test flavour only (ju_debug_set "group_rerun"): "pass_rerun" for group passes -- a group pass that completed normally
+// is treated as one that must be run again: its members one by one through process(), without the detector.
+void setGroupRerun(int on);
 
 class Engine {
 public:
@@ -71,6 +74,13 @@ public:
 	// members[0] (the lead) runs the flow net ONCE over up to its look-ahead cap of frames, each the next frame of its
 	// own stream, then every member's own recurrent steps, all on the lead's stream (engine_passes.cpp, "Group passes").
 	static void processGroup(Engine *const *members, const Frame *in, const Frame *out, int count);
+	// processGroup for frames of any format (ju_process_group_frames): formats, colour spaces, locations and strides are
+	// independent per member and side.  EVERY pair is checked before anything is launched or uploaded (std::invalid_argument
+	// names the member).  A pass decodes all its non-BGRX inputs in one launch in front of the flow net's and encodes each
+	// member's output behind that member's own steps -- a deep format from THAT member's f16 state (engine_passes.cpp,
+	// "Group passes").  who: the entry point in the messages; indexed: checkFrame's refusals name the member too.
+	static void processGroupFrames(Engine *const *members, const AnyFrame *in, const AnyFrame *out, int count,
+	    const char *who = "ju_process_group_frames", bool indexed = true);
 	// process() for device-resident frames without the wait (ju_enqueue, ju_enqueue_frame): enqueue only.
 	void enqueue(const AnyFrame &in, const AnyFrame &out);
 	void synchronize();
@@ -120,6 +130,10 @@ public:
 	// a pass"): 0 (default) = such a runtime's frames run one by one, 1 = passes are formed and carry the detector.
 	// Waits for the stream; reset() and setSceneDetect() keep it.
 	void setSceneLookahead(int on);
+	// Group passes while the detector is on (ju_set_scene_group; engine_passes.cpp, "The scene detector inside a group
+	// pass"): 0 (default) = processGroup runs this runtime on its own, 1 = it rides in the passes, which carry its
+	// detector.  Waits for the stream; reset() and setSceneDetect() keep it.
+	void setSceneGroup(int on);
 	// Look-ahead passes while a source size, a mask or an output size is set (ju_set_stage_lookahead; engine_passes.cpp,
 	// "Scaled and masked frames inside a pass"): 0 (default) = such a runtime's frames run one by one through submitFrame,
 	// 1 = processBatch / processFrames form passes that carry the stages.  Waits for the stream; reset() keeps it.
@@ -229,7 +243,8 @@ private:
 	SourceView stageInSource(const AnyFrame &in);
 	// (width x height: the size of the frame encoded; of bgrx / state / frame16 the one the format's path reads)
 	void encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::size_t width, std::size_t height,
-	    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16 = nullptr);
+	    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16 = nullptr,
+	    hipStream_t stream = nullptr);  // (stream: nullptr = m_Stream; a group pass encodes on its lead's)
 	// a deep format of a runtime whose state is the frame in float, without a mask: encoded from 16-bit samples
 	bool deepFromState(PixelFormat format) const;
 	// Output stage: the scaler from the model's output to the size output frames must have (its destination size; not
@@ -267,6 +282,11 @@ private:
 	}
 	// binding set of the cut-aware flow launches in m_BatchFlow: {items, kCutSet + set}
 	static constexpr int kCutSet = 4;
+	// The detector inside group passes.  m_SceneGroup: the setting; m_SceneGroupDyn: this member's host-mapped SceneGroupDyn,
+	// refreshed in front of every pass that carries it; m_SceneGroupFrames: "scene_group_frames".
+	bool m_SceneGroup = false;
+	PinnedWords m_SceneGroupDyn;
+	std::uint64_t m_SceneGroupFrames = 0;
 	void dropScenePassGraphs();  // the graphs of passes that carry the detector: bound to m_ScenePrev / m_SceneDev / m_SceneRing
 	// Everything a frame call can refuse, before anything is launched; `who` names the entry point in the message.
 	// declaredSize (ju_process_group): a NULL pointer is refused first and by name, and a graphics resource's DECLARED
@@ -544,7 +564,8 @@ private:
 	PinnedWords m_PassSignal;
 	unsigned m_PassSignalBase = 0;
 	std::uint64_t m_BatchHostFrames = 0, m_BatchYuvFrames = 0;
-	bool passEligible(const AnyFrame &in, const AnyFrame &out) const;
+	// group: as a member of a group pass -- no stage (the caller keeps staged members out) and whatever the detector's setting
+	bool passEligible(const AnyFrame &in, const AnyFrame &out, bool group = false) const;
 	void uploadPassInputs(const AnyFrame *in, int n);
 	void drainPassOutputs(const AnyFrame *out, int n);
 	// the passes of processBatch / processFrames (whose staged pairs are checked: processFrames)
@@ -570,7 +591,7 @@ private:
 	const void *m_GroupPrev[kFlowBatchMax] = {};
 	void *m_GroupOut[kFlowBatchMax] = {};
 	Event m_GroupEvent;
-	std::uint64_t m_GroupFrames = 0;
+	std::uint64_t m_GroupFrames = 0, m_GroupYuvFrames = 0;  // ("group_yuv_frames": those of them with a non-BGRX side)
 	bool sameModel(const Engine &o) const;
 	// one pass over members m[0 .. n) on `lead`'s stream and tensors (the lead need not be one of them)
 	static void runGroupPass(Engine &lead, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n);

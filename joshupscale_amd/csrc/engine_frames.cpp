@@ -194,14 +194,15 @@ bool Engine::deepFromState(PixelFormat format) const {
 // one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit YUV or
 // a deep RGB format of a runtime whose state is the frame in float (m_HbdFromState), the f16 state that frame left -- -> planes
 void Engine::encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::size_t width, std::size_t height,
-    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16) {
+    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16, hipStream_t stream) {
 	const int w = static_cast<int>(width), h = static_cast<int>(height);
+	if (stream == nullptr) stream = m_Stream;
 	if (!deepFromState(format)) {
-		launchEncodeFrame(fmt(format), colorspace, bgrx, bgrxStride, planes, w, h, m_Stream);
+		launchEncodeFrame(fmt(format), colorspace, bgrx, bgrxStride, planes, w, h, stream);
 	} else if (frame16 != nullptr) {  // (the output stage: the state's samples, scaled)
-		launchEncodeFrame16(fmt(format), colorspace, frame16, planes, w, h, m_Stream);
+		launchEncodeFrame16(fmt(format), colorspace, frame16, planes, w, h, stream);
 	} else {
-		launchEncodeState(fmt(format), colorspace, state, planes, w, h, m_Stream);
+		launchEncodeState(fmt(format), colorspace, state, planes, w, h, stream);
 	}
 }
 
@@ -473,6 +474,14 @@ void Engine::setSceneLookahead(int on) {
 		m_ScenePassDyn = PinnedWords(sizeof(ScenePassDyn));
 	}
 	m_SceneLookahead = on != 0;
+}
+
+void Engine::setSceneGroup(int on) {
+	if (on != 0 && on != 1) throw std::invalid_argument("ju_set_scene_group: on must be 0 or 1, got " + std::to_string(on));
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();
+	if (on && !m_SceneGroupDyn.host()) m_SceneGroupDyn = PinnedWords(sizeof(SceneGroupDyn));
+	m_SceneGroup = on != 0;
 }
 
 void Engine::sceneDetect(int *mode, std::uint32_t *thresholdMilli) const {

@@ -252,13 +252,13 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 // A frame may go into a pass when each of its two images is either a device-resident one the kernels can read / write in
 // place (directEligible's conditions) or a host image of the right size (staged through the pass's own device buffers).
 // A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
-bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out) const {
+bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out, bool group) const {
 	// (scaled / masked frames run one by one through submitFrame unless the passes carry the stages: setStageLookahead)
-	const int stage = stagePass();
+	const int stage = group ? 0 : stagePass();
 	if (sourceStage() && !stage) return false;
 	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
-	// unless the pass carries the detector and applies the cuts itself: setSceneLookahead)
-	if (m_SceneMode != 0 && !m_SceneLookahead) return false;
+	// unless the pass carries the detector and applies the cuts itself: setSceneLookahead; a group pass: setSceneGroup)
+	if (m_SceneMode != 0 && !(group ? m_SceneGroup : m_SceneLookahead)) return false;
 	std::size_t inW, inH, outW, outH;
 	passSizes(stage, &inW, &inH, &outW, &outH);
 	// scaled: the side's device image is read / written by a scale kernel, which takes any alignment and signed stride
@@ -589,9 +589,10 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 }
 
 namespace {
-std::atomic<int> g_PassRerun{0};
+std::atomic<int> g_PassRerun{0}, g_GroupRerun{0};
 }  // namespace
 void setPassRerun(int on) { g_PassRerun = on; }
+void setGroupRerun(int on) { g_GroupRerun = on; }
 
 void Engine::processBatch(const Frame *in, const Frame *out, int count) {
 	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("processBatch: bad arguments");
@@ -701,6 +702,21 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 // reads (every member's state and history go to the other half of its ping-pong, the overlap test below keeps outputs
 // off inputs), so a pass whose resident tower timed out runs again member by member.  The launches are eager: round 6
 // measured eager launches per frame equal to graph replay.
+//
+// Frames of any format (processGroupFrames).  A member's pair is bound as a look-ahead pass binds a frame's (bindBatch on
+// the lead: host planes into the lead's slots m_PassIn / m_PassYuvIn, uploaded up front); ONE decode launch in front of
+// the flow net covers every non-BGRX input of the pass (the items form of processFrames), and each member's encode sits
+// behind that member's own steps on the lead's stream -- a deep format from THAT member's f16 state, the half its step
+// just wrote.  Members under a source size, an output size or a mask stay on the staged single-frame route.
+//
+// The scene detector inside a group pass (setSceneGroup; docs/scene_detect.md "Group passes").  The members are
+// independent streams, so no cut-aware history is needed: scene_group_kernel takes the decision of every detecting
+// member in ONE launch behind the decode launch -- item i against member i's own kept frame, from and into member i's
+// own SceneState and ring -- and scene_clear_items_kernel zeroes, in ONE more launch, m_State[set_i] and m_Packed[set_i]
+// of the members whose flag was raised: exactly what the per-frame scene_clear_kernel covers, in front of the flow net
+// that reads m_Packed[set_i] as m_GroupPrev[i].  One exception to "writes nothing it reads", as in a look-ahead pass: those
+// two buffers may be zeroed -- which is what the re-run of the members, whose decisions stand (m_SceneRerun), wants to
+// find there too.
 // ---------------------------------------------------------------------------------------------------------------
 bool Engine::sameModel(const Engine &o) const {
 	return m_Device == o.m_Device && m_ModelDigest == o.m_ModelDigest && m_DtypeOverride == o.m_DtypeOverride;
@@ -712,36 +728,55 @@ void Engine::processGroup(Engine *const *members, const Frame *bgrxIn, const Fra
 	}
 	if (count == 0) return;
 	const std::vector<AnyFrame> in = anyOf(bgrxIn, count), out = anyOf(bgrxOut, count);
+	processGroupFrames(members, in.data(), out.data(), count, "ju_process_group", false);
+}
+
+void Engine::processGroupFrames(Engine *const *members, const AnyFrame *in, const AnyFrame *out, int count, const char *who,
+    bool indexed) {
+	const std::string name = who;
+	if (count < 0 || (count > 0 && (members == nullptr || in == nullptr || out == nullptr))) {
+		throw std::invalid_argument(name + ": NULL arguments or a negative count");
+	}
+	if (count == 0) return;
 	std::set<const Engine *> seen;
 	for (int i = 0; i < count; ++i) {
-		if (members[i] == nullptr) throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " is NULL");
+		if (members[i] == nullptr) throw std::invalid_argument(name + ": runtime " + std::to_string(i) + " is NULL");
 		if (!seen.insert(members[i]).second) {
-			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) + " appears twice");
+			throw std::invalid_argument(name + ": runtime " + std::to_string(i) + " appears twice");
 		}
 		if (!members[i]->sameModel(*members[0])) {
-			throw std::invalid_argument("ju_process_group: runtime " + std::to_string(i) +
+			throw std::invalid_argument(name + ": runtime " + std::to_string(i) +
 			                            " does not match runtime 0 (device, model bytes or dtype)");
 		}
-		// what process() would refuse for its size, up front: a group call launches nothing before every frame passed
-		members[i]->checkFrame(in[i], true, "ju_process_group", true);
-		members[i]->checkFrame(out[i], false, "ju_process_group", true);
+		// what process() would refuse, up front: a group call launches nothing before every frame passed
+		try {
+			members[i]->checkFrame(in[i], true, who, true);
+			members[i]->checkFrame(out[i], false, who, true);
+		} catch (const std::invalid_argument &e) {
+			if (!indexed) throw;
+			// ("<who>: <why>" -> "<who>: member i: <why>")
+			const std::string what = e.what(), prefix = name + ": ";
+			throw std::invalid_argument(prefix + "member " + std::to_string(i) + ": " +
+			                            (what.compare(0, prefix.size(), prefix) == 0 ? what.substr(prefix.size()) : what));
+		}
 	}
 	Engine &lead = *members[0];
 	DeviceGuard g(lead.m_Device);
 	auto alone = [&](int i) { members[i]->process(in[i], out[i]); };
 	if (count == 1) return alone(0);
-	// An output over an input of the call (same address space; any two members, also one member's own pair): member by
-	// member in list order, as ju_process calls would run -- a pass reads every input before any tail writes
+	// An output over an input of the call (same address space; any two members, also one member's own pair; every plane
+	// of a frame counts): member by member in list order, as ju_process_frame calls would run -- a pass reads every input
+	// before any tail writes
 	bool clash = false;
 	for (int i = 0; i < count && !clash; ++i) {
 		const FrameExtent w = extentOf(out[i]);
 		for (int j = 0; j < count && !clash; ++j) clash = overlap(w, extentOf(in[j]));
 	}
 	std::vector<int> pass, rest;
-	// (a detecting runtime stays member by member, whatever its look-ahead setting: a group pass carries no detector)
+	// (a detecting runtime stays member by member unless it asked to ride: setSceneGroup -- the pass then carries its detector)
 	for (int i = 0; i < count; ++i) {
-		// (nor a stage: a scaled or masked member stays on the staged single-frame route, whatever setStageLookahead says)
-		(members[i]->m_SceneMode == 0 && !members[i]->sourceStage() && members[i]->passEligible(in[i], out[i]) ? pass : rest).push_back(i);
+		// (no stage: a scaled or masked member stays on the staged single-frame route, whatever setStageLookahead says)
+		(!members[i]->sourceStage() && members[i]->passEligible(in[i], out[i], true) ? pass : rest).push_back(i);
 	}
 	const int cap = lead.m_BatchMax;
 	if (clash || pass.size() < 2 || cap < 2) {
@@ -775,6 +810,25 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 	L.bindBatch(in, out, n, 0, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
 	L.uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
 	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
+	// The detecting members (they ride because they asked to: setSceneGroup).  What their decisions read that varies from
+	// tick to tick goes into each member's own host-mapped words; the pass is synchronous, so nothing reads them now.
+	bool detects[kFlowBatchMax] = {};
+	bool anyDetects = false, anyRestarts = false;
+	for (int i = 0; i < n; ++i) {
+		Engine &e = *m[i];
+		detects[i] = e.m_SceneMode != 0;
+		if (!detects[i]) continue;
+		anyDetects = true;
+		// (a flow-free model has no recurrent input to clear: JU_SCENE_RESET reports)
+		const bool restarts = e.m_SceneMode == 2 && e.m_Config.recurrent();
+		anyRestarts = anyRestarts || restarts;
+		auto *dyn = reinterpret_cast<volatile SceneGroupDyn *>(e.m_SceneGroupDyn.host());
+		const unsigned long long hasPrev = (e.m_SceneSeen >= 1 ? 1u : 0u) | (e.m_SceneSeen >= 2 ? 2u : 0u);
+		dyn->step = e.m_SceneSteps;
+		dyn->slotHasPrev = (e.m_SceneSteps % kSceneRing) | (hasPrev << 32);
+		dyn->thresholdMode = static_cast<unsigned long long>(e.m_SceneThreshold) | (static_cast<unsigned long long>(restarts ? 2 : 1) << 32);
+	}
+	if (anyDetects) std::atomic_thread_fence(std::memory_order_seq_cst);
 	// 1. work a member has pending on its own stream (ju_enqueue) runs first
 	for (int i = 0; i < n; ++i) {
 		if (m[i] == &L) continue;
@@ -794,6 +848,54 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		bool resident = false;
 		for (int i = 0; i < n; ++i) resident = resident || m[i]->m_Resident;
 		std::unique_lock<std::mutex> chain = L.chainBegin(resident);
+		// 2a. the pass's non-BGRX inputs into their members' BGRX slots of the lead, all in ONE launch (runBatch's)
+		const FrameSize fs = L.frameSize();
+		YuvDecodeItems items{};
+		int decodes = 0;
+		for (int i = 0; i < n; ++i) {
+			const PassFrame &pf = L.m_BatchHost[i];
+			if (!pf.in.yuv) continue;
+			items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(L.m_BatchIO[i].in),
+			    L.m_BatchIO[i].inStride);
+		}
+		if (decodes) launchYuv420ToBgrxItems(items, decodes, static_cast<int>(fs.inputWidth), static_cast<int>(fs.inputHeight), L.m_Stream);
+		// 2b. the scene detector inside a group pass: every member's frame is in place (the caller's device frame, the lead's
+		// upload slot, the slot the decode launch fills), so ONE launch takes the decision of every detecting member -- each
+		// against its OWN kept frame, state and ring (the streams are independent: no cut-aware history) -- and ONE more
+		// clears, for the members whose flag it raised, what their step is about to read as its recurrent inputs:
+		// m_State[set_i] and m_Packed[set_i], the half the first flow block reads as m_GroupPrev[i].  After it a cut
+		// member's whole history is zero, which is what reset() leaves.
+		if (anyDetects) {
+			SceneGroupLaunch q;
+			q.items = n;
+			q.width = static_cast<int>(fs.inputWidth);
+			q.height = static_cast<int>(fs.inputHeight);
+			SceneClearItem clears[kFlowBatchMax];
+			for (int i = 0; i < n; ++i) {
+				if (!detects[i]) continue;
+				Engine &e = *m[i];
+				SceneGroupItem &it = q.item[i];
+				it.frame = L.m_BatchIO[i].in;
+				it.stride = L.m_BatchIO[i].inStride;
+				it.prev = e.m_ScenePrev.as<std::uint32_t>();
+				it.state = e.m_SceneDev.as<SceneState>();
+				it.ring = reinterpret_cast<SceneRecord *>(e.m_SceneRing.device());
+				it.dyn = reinterpret_cast<const SceneGroupDyn *>(e.m_SceneGroupDyn.device());
+				if (e.m_SceneMode == 2 && recurrent) {
+					clears[i] = SceneClearItem{&it.state->resetNow, e.m_State[sets[i]].get(), e.m_State[sets[i]].bytes(),
+					    e.m_Packed[sets[i]].get(), e.m_Packed[sets[i]].bytes()};
+				}
+			}
+			launchSceneGroup(q, L.m_Stream);
+			if (anyRestarts) launchSceneClearItems(clears, n, L.m_Stream);
+			for (int i = 0; i < n; ++i) {  // one detector step per detecting member, taken by the pass's one launch
+				if (!detects[i]) continue;
+				++m[i]->m_SceneSeen;
+				++m[i]->m_SceneSteps;
+				++m[i]->m_SceneRuns;
+				++m[i]->m_SceneGroupFrames;
+			}
+		}
 		// 2. the flow net once over all items
 		for (int i = 0; i < n; ++i) {
 			L.m_GroupPrev[i] = m[i]->m_Packed[sets[i]].get();
@@ -819,6 +921,14 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 			for (const Step &st : e.m_Program[sets[i]]) {
 				if (st.tag != "flow" && st.tag != "pack") st.run(L.m_Stream);
 			}
+			// a non-BGRX output: member i's BGRX slot of the lead into the caller's device planes / the staging slot, behind
+			// member i's own steps.  A deep format is encoded from the f16 state THIS MEMBER's step just wrote -- its own
+			// m_State[set_i ^ 1] (a flow-free member: its one scratch state), never the lead's
+			const PassSide &po = L.m_BatchHost[i].out;
+			if (po.yuv) {
+				e.encodeYuv(po.format, po.colorspace, po.planes, fs.outputWidth, fs.outputHeight, L.m_BatchIO[i].out, L.m_BatchIO[i].outStride,
+				    e.m_State[recurrent ? sets[i] ^ 1 : 0].get(), nullptr, L.m_Stream);
+			}
 			if (L.m_BatchHost[i].out.host) launchSignalHost(L.m_PassSignal.device(), L.m_Stream);
 		}
 		L.chainEnd(chain, resident);
@@ -837,18 +947,28 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		codes[i] = m[i]->takeResidentError();
 		failed = failed || codes[i] != 0;
 	}
-	if (failed) {
+	if (failed || g_GroupRerun.load(std::memory_order_relaxed)) {
 		// nothing the pass wrote is one of its inputs: the same frames again, member by member, each through its own
 		// process() -- a member whose tower timed out on its per-block kernels from now on
 		for (int i = 0; i < n; ++i) {
 			if (codes[i]) m[i]->fallbackToLayers(codes[i]);
 		}
-		for (int i = 0; i < n; ++i) m[i]->process(in[i], out[i]);
+		for (int i = 0; i < n; ++i) {
+			// (the pass's detector has run: the member's decision stands, its kept frame is this frame already and, after a
+			// cut, its cleared inputs are still in place -- the pass wrote the other halves only; no step meets it again)
+			struct Rerun {
+				bool &flag;
+				~Rerun() { flag = false; }
+			} rerun{m[i]->m_SceneRerun};
+			m[i]->m_SceneRerun = detects[i];
+			m[i]->process(in[i], out[i]);
+		}
 		return;
 	}
 	for (int i = 0; i < n; ++i) {
 		m[i]->m_Idx = sets[i] ^ 1;
 		++m[i]->m_GroupFrames;
+		m[i]->m_GroupYuvFrames += L.m_BatchHost[i].yuv() ? 1 : 0;
 		m[i]->maybeRestoreResident();
 	}
 }

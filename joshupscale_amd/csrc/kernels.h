@@ -749,6 +749,41 @@ struct ScenePassLaunch {
 	bool resetMode = false;
 };
 void launchScenePass(const ScenePassLaunch &q, hipStream_t stream);
+// The detector over the independent items of a group pass in ONE launch (scene_group_kernel; Engine::processGroup): item
+// i is member i's frame against member i's OWN kept frame, state and ring -- the arithmetic and the decision of
+// launchSceneSad per item, taken by the workgroup that draws the grid's last ticket (the first present item's
+// SceneState::ticket; every acc and that ticket are back at zero when the launch ends).
+// SceneGroupDyn: what varies between ticks, in the member's host-mapped memory, written by the host in front of the launch
+// (a group pass is synchronous: nothing reads it while the host writes) and read by the kernel as three 64-bit words.
+struct SceneGroupDyn {
+	unsigned long long step;           // the record's `step`
+	unsigned long long slotHasPrev;    // low word: the ring slot; high word: bit 0 frame t-1 is in the detector's memory, bit 1 frame t-2 is
+	unsigned long long thresholdMode;  // low word: threshold_milli; high word: 2 = a cut raises SceneState::resetNow, else it reports
+};
+struct SceneGroupItem {
+	const std::uint8_t *frame = nullptr;  // BGRX rows, 4-byte aligned, any signed stride of at least a row; nullptr: absent, skipped
+	std::ptrdiff_t stride = 0;
+	std::uint32_t *prev = nullptr;  // dense width x height BGRX: read as c_{t-1}, rewritten as c_t
+	SceneState *state = nullptr;
+	SceneRecord *ring = nullptr;       // device address of the member's host-mapped records
+	const SceneGroupDyn *dyn = nullptr;  // device address of the member's host-mapped words
+};
+struct SceneGroupLaunch {
+	int items = 0;  // 1 .. kFlowBatchMax, absent ones included; no launch when all are absent
+	SceneGroupItem item[kFlowBatchMax];
+	int width = 0, height = 0;  // of every item: the members of a pass share the model
+};
+void launchSceneGroup(const SceneGroupLaunch &q, hipStream_t stream);
+// The conditional clear of all members of a group pass in ONE launch (scene_clear_items_kernel): for item i, if (*flag)
+// a[0 .. aBytes) = b[0 .. bBytes) = 0, any alignment; an item with a null flag is absent.
+struct SceneClearItem {
+	const unsigned *flag = nullptr;
+	void *a = nullptr;
+	std::size_t aBytes = 0;
+	void *b = nullptr;
+	std::size_t bBytes = 0;
+};
+void launchSceneClearItems(const SceneClearItem *items, int n, hipStream_t stream);
 // The refusals of ju_set_scene_detect as one message ("" when mode and threshold are fine): mode 0 .. 2, and while the
 // mode is not off a threshold of 1 .. 255000 thousandths of a code value
 std::string sceneDetectProblem(int mode, std::uint32_t thresholdMilli);

@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -209,6 +210,105 @@ void launchScenePassN(const ScenePassParams &p, unsigned groups, hipStream_t str
 	hipLaunchKernelGGL(scene_pass_kernel<N>, dim3(groups), dim3(kSadThreads), 0, stream, p);
 }
 
+// scene_group_kernel: scene_sad_kernel over the n INDEPENDENT items of a group pass (Engine::processGroup) in one launch.
+// blockIdx.y is the item: member y's frame against member y's own kept frame, which the same thread rewrites; the sums
+// are scene_sad_kernel's (v_sad_u8 on the three low bytes, u32 partials -> wave sum -> workgroup sum -> one 64-bit
+// integer atomic add per item and workgroup at agent scope, into that member's SceneState::acc).  One ticket for the
+// whole grid (release in every workgroup before it, acquire in the last one behind it; nobody waits): the workgroup that
+// draws the last one takes the n decisions, lane j item j's -- from member j's own SceneState, written back to it, the
+// record into member j's own ring.  What varies between ticks (step, ring slot, predecessor bits, threshold, mode) is
+// read from member j's host-mapped SceneGroupDyn, three 64-bit loads per item, side by side across the lanes.
+struct SceneGroupParams {
+	const std::uint8_t *frames[kFlowBatchMax];
+	long long strides[kFlowBatchMax];
+	std::uint32_t *prev[kFlowBatchMax];
+	SceneState *st[kFlowBatchMax];
+	SceneRecord *ring[kFlowBatchMax];
+	const SceneGroupDyn *dyn[kFlowBatchMax];
+	unsigned *ticket;
+	int W, items;
+	long long pixels;
+};
+
+__global__ __launch_bounds__(kSadThreads) void scene_group_kernel(SceneGroupParams p) {
+	__shared__ unsigned waveSums[kSadThreads / 64];
+	__shared__ unsigned lastGroup;
+	const unsigned item = blockIdx.y;
+	const std::uint8_t *__restrict__ src = p.frames[item];
+	const long long srcStride = p.strides[item];
+	std::uint32_t *__restrict__ prev = p.prev[item];
+	const unsigned base = blockIdx.x * static_cast<unsigned>(kSadPerGroup) + threadIdx.x;
+	const unsigned width = static_cast<unsigned>(p.W), count = static_cast<unsigned>(p.pixels);
+	unsigned partial = 0;
+#pragma unroll
+	for (int k = 0; k < kSadPerThread; ++k) {
+		const unsigned i = base + static_cast<unsigned>(k * kSadThreads);
+		if (i < count) {
+			const unsigned row = i / width, x = i - row * width;
+			const unsigned cur = *reinterpret_cast<const std::uint32_t *>(src + static_cast<long long>(row) * srcStride + x * 4u);
+			const unsigned old = prev[i];
+			prev[i] = cur;
+			partial = __builtin_amdgcn_sad_u8(cur & 0x00ffffffu, old & 0x00ffffffu, partial);
+		}
+	}
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) partial += __shfl_down(partial, off, 64);
+	if ((threadIdx.x & 63) == 0) waveSums[threadIdx.x >> 6] = partial;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long groupSum = 0;
+#pragma unroll
+		for (int w = 0; w < kSadThreads / 64; ++w) groupSum += waveSums[w];
+		__hip_atomic_fetch_add(&p.st[item]->acc, groupSum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		// publish the add before the ticket (fence, then its wait, then the ticket: in that order)
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		const unsigned ticket = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		lastGroup = ticket == gridDim.x * gridDim.y - 1 ? 1u : 0u;
+	}
+	__syncthreads();
+	if (lastGroup == 0 || threadIdx.x >= static_cast<unsigned>(p.items)) return;
+	// ---- the last workgroup of the launch: lane j takes item j's decision ----
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	const unsigned j = threadIdx.x;
+	// (the grid's one ticket: every workgroup has drawn, so nothing adds to it any more)
+	if (j == 0) __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	const SceneGroupDyn *dyn = p.dyn[j];
+	const unsigned long long step = __hip_atomic_load(&dyn->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	const unsigned long long slotPrev = __hip_atomic_load(&dyn->slotHasPrev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	const unsigned long long thrMode = __hip_atomic_load(&dyn->thresholdMode, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	const unsigned slot = static_cast<unsigned>(slotPrev) % static_cast<unsigned>(kSceneRing);
+	const unsigned hasPrev = static_cast<unsigned>(slotPrev >> 32);
+	const unsigned thresholdMilli = static_cast<unsigned>(thrMode);
+	const unsigned resetMode = static_cast<unsigned>(thrMode >> 32) == 2u ? 1u : 0u;
+	SceneState *st = p.st[j];
+	// read the sum and re-arm the accumulator in one atomic
+	unsigned long long S = __hip_atomic_exchange(&st->acc, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	if (!(hasPrev & 1)) S = 0;  // no predecessor: what the kept frame held is not a frame of this stream
+	unsigned long long D = 0;
+	if ((hasPrev & 3) == 3) {
+		const unsigned long long before = st->prevSad;
+		const unsigned long long delta = S > before ? S - before : before - S;
+		D = S < delta ? S : delta;
+	}
+	const unsigned long long N = 3ull * static_cast<unsigned long long>(p.pixels);
+	const unsigned cut = 1000ull * D >= static_cast<unsigned long long>(thresholdMilli) * N ? 1u : 0u;
+	const unsigned long long frames = st->frames + 1, cuts = st->cuts + cut;
+	st->prevSad = S;
+	st->frames = frames;
+	st->cuts = cuts;
+	st->resetNow = (cut && resetMode) ? 1u : 0u;
+	SceneRecord *r = p.ring[j] + slot;
+	__hip_atomic_store(&r->step, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&r->sad, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&r->score, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&r->cut, cut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	SceneRecord *totals = p.ring[j] + kSceneRing;
+	__hip_atomic_store(&totals->step, frames, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&totals->sad, cuts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 constexpr int kClearThreads = 256;
 constexpr int kClearVecsPerThread = 4;
 constexpr long long kClearPerGroup = static_cast<long long>(kClearThreads) * kClearVecsPerThread * 16;
@@ -241,6 +341,27 @@ __global__ __launch_bounds__(kClearThreads) void scene_clear_kernel(const unsign
 		clearChunk(a, aBytes, g);
 	} else {
 		clearChunk(b, bBytes, g - aChunks);
+	}
+}
+
+// scene_clear_items_kernel: scene_clear_kernel for all members of a group pass in one launch.  blockIdx.y is the item,
+// blockIdx.x the chunk of its two buffers; every workgroup loads its item's flag once and returns if it is 0 (so do the
+// workgroups past the item's last chunk: the grid is as wide as the largest item).
+struct SceneClearItemsParams {
+	const unsigned *flag[kFlowBatchMax];
+	std::uint8_t *a[kFlowBatchMax], *b[kFlowBatchMax];
+	long long aBytes[kFlowBatchMax], bBytes[kFlowBatchMax];
+	int aChunks[kFlowBatchMax], bChunks[kFlowBatchMax];
+};
+
+__global__ __launch_bounds__(kClearThreads) void scene_clear_items_kernel(SceneClearItemsParams p) {
+	const unsigned item = blockIdx.y;
+	if (*p.flag[item] == 0) return;
+	const int g = static_cast<int>(blockIdx.x), aChunks = p.aChunks[item];
+	if (g < aChunks) {
+		clearChunk(p.a[item], p.aBytes[item], g);
+	} else if (g - aChunks < p.bChunks[item]) {
+		clearChunk(p.b[item], p.bBytes[item], g - aChunks);
 	}
 }
 
@@ -320,7 +441,75 @@ void launchScenePass(const ScenePassLaunch &q, hipStream_t stream) {
 	hipCheckLaunch("scene_pass");
 }
 
-void launchSceneClear(const unsigned *flag, void *a, std::size_t aBytes, void *b, std::size_t bBytes, hipStream_t stream) {
+void launchSceneGroup(const SceneGroupLaunch &q, hipStream_t stream) {
+	if (q.items < 1 || q.items > kFlowBatchMax) throw std::invalid_argument("scene_group: 1 .. " + std::to_string(kFlowBatchMax) + " items");
+	if (q.width < 1 || q.height < 1 || q.width > kSceneAxisMax || q.height > kSceneAxisMax) {
+		throw std::invalid_argument("scene_group: a size outside 1 .. " + std::to_string(kSceneAxisMax));
+	}
+	const auto row = static_cast<std::ptrdiff_t>(q.width) * 4;
+	SceneGroupParams p{};
+	int present = 0;
+	for (int i = 0; i < q.items; ++i) {
+		const SceneGroupItem &it = q.item[i];
+		if (it.frame == nullptr) continue;  // (a member without a detector)
+		const std::string who = "scene_group: item " + std::to_string(i);
+		if (it.prev == nullptr || it.state == nullptr || it.ring == nullptr || it.dyn == nullptr) throw std::invalid_argument(who + ": null buffer");
+		if (reinterpret_cast<std::uintptr_t>(it.frame) % 4 != 0 || it.stride % 4 != 0) {
+			throw std::invalid_argument(who + ": the frame and its stride must be 4-byte aligned");
+		}
+		if (it.stride > -row && it.stride < row) throw std::invalid_argument(who + ": |stride| smaller than a row");
+		for (int k = 0; k < present; ++k) {
+			if (p.prev[k] == it.prev || p.st[k] == it.state) throw std::invalid_argument(who + ": shares its detector memory with another item");
+		}
+		p.frames[present] = it.frame;
+		p.strides[present] = static_cast<long long>(it.stride);
+		p.prev[present] = it.prev;
+		p.st[present] = it.state;
+		p.ring[present] = it.ring;
+		p.dyn[present] = it.dyn;
+		++present;
+	}
+	if (present == 0) return;  // (no member detects: no launch)
+	p.ticket = &p.st[0]->ticket;  // (the grid's one ticket: the first item's)
+	p.W = q.width;
+	p.items = present;
+	p.pixels = static_cast<long long>(q.width) * q.height;
+	const unsigned groups = static_cast<unsigned>((p.pixels + kSadPerGroup - 1) / kSadPerGroup);
+	hipLaunchKernelGGL(scene_group_kernel, dim3(groups, static_cast<unsigned>(present)), dim3(kSadThreads), 0, stream, p);
+	hipCheckLaunch("scene_group");
+}
+
+void launchSceneClearItems(const SceneClearItem *items, int n, hipStream_t stream) {
+	if (n < 0 || n > kFlowBatchMax || (n > 0 && items == nullptr)) {
+		throw std::invalid_argument("scene_clear_items: 0 .. " + std::to_string(kFlowBatchMax) + " items");
+	}
+	SceneClearItemsParams p{};
+	int present = 0, widest = 0;
+	for (int i = 0; i < n; ++i) {
+		const SceneClearItem &it = items[i];
+		if (it.flag == nullptr) continue;  // (a member that does not restart: absent)
+		if ((it.a == nullptr && it.aBytes != 0) || (it.b == nullptr && it.bBytes != 0)) {
+			throw std::invalid_argument("scene_clear_items: item " + std::to_string(i) + ": null buffer");
+		}
+		const int aChunks = clearChunks(it.aBytes), bChunks = clearChunks(it.bBytes);
+		if (aChunks + bChunks == 0) continue;
+		p.flag[present] = it.flag;
+		p.a[present] = static_cast<std::uint8_t *>(it.a);
+		p.b[present] = static_cast<std::uint8_t *>(it.b);
+		p.aBytes[present] = static_cast<long long>(it.aBytes);
+		p.bBytes[present] = static_cast<long long>(it.bBytes);
+		p.aChunks[present] = aChunks;
+		p.bChunks[present] = bChunks;
+		widest = std::max(widest, aChunks + bChunks);
+		++present;
+	}
+	if (present == 0) return;
+	hipLaunchKernelGGL(scene_clear_items_kernel, dim3(static_cast<unsigned>(widest), static_cast<unsigned>(present)), dim3(kClearThreads), 0,
+	    stream, p);
+	hipCheckLaunch("scene_clear_items");
+}
+
+void launchSceneClear(const unsigned *flag, void *a,std::size_t aBytes, void *b, std::size_t bBytes, hipStream_t stream) {
 	if (flag == nullptr || (a == nullptr && aBytes != 0) || (b == nullptr && bBytes != 0)) {
 		throw std::invalid_argument("scene_clear: null buffer");
 	}

@@ -198,6 +198,7 @@ _PRODUCT_SIGS = {
     "ju_process": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
     "ju_process_batch": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage), C.c_int]),
     "ju_process_group": (C.c_int, [_P(C.c_void_p), _P(JuImage), _P(JuImage), C.c_int]),
+    "ju_process_group_frames": (C.c_int, [_P(C.c_void_p), _P(JuFrame), _P(JuFrame), C.c_int]),
     "ju_prepare_batch": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage), C.c_int, _P(C.c_int)]),
     "ju_set_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_enqueue": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
@@ -212,6 +213,7 @@ _PRODUCT_SIGS = {
     "ju_get_scene_detect": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_uint32)]),
     "ju_get_scene_info": (C.c_int, [C.c_void_p, _P(JuSceneInfo), C.c_int, _P(C.c_int)]),
     "ju_set_scene_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
+    "ju_set_scene_group": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_set_stage_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_set_source_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_get_source_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
@@ -259,6 +261,11 @@ _HOOK_SIGS = {
     "ju_debug_scene_pass": (C.c_int, [C.c_int, _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_int, _P(JuSceneInfo), _P(C.c_uint32),
                                       _P(C.c_int32)]),
+    "ju_debug_scene_group": (C.c_int, [C.c_int, _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t, _P(C.c_void_p),
+                                       _P(C.c_void_p), _P(C.c_int), _P(C.c_uint64), _P(C.c_uint32), _P(C.c_int),
+                                       _P(JuSceneInfo), _P(C.c_uint32)]),
+    "ju_debug_scene_clear_items": (C.c_int, [C.c_int, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p),
+                                             _P(C.c_size_t)]),
     "ju_debug_scale": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ju_debug_scale_items": (C.c_int, [C.c_int, C.c_int, _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
@@ -452,6 +459,12 @@ class Runtime:
         value other than 0 or 1 raises :class:`JoshUpscaleError` with the C layer's message."""
         _check(self._lib, self._lib.ju_set_scene_lookahead(self._h, int(on)))
 
+    def set_scene_group(self, on) -> None:
+        """``ju_set_scene_group``: 1 = this runtime rides in the passes of ``process_group`` / ``process_group_frames``
+        while its detector is on, and the passes carry it (docs/scene_detect.md "Group passes"); 0 (the default) = it
+        runs on its own.  A value other than 0 or 1 raises :class:`JoshUpscaleError` with the C layer's message."""
+        _check(self._lib, self._lib.ju_set_scene_group(self._h, int(on)))
+
     def set_stage_lookahead(self, on) -> None:
         """``ju_set_stage_lookahead``: 1 = ``process_batch`` / ``process_frames`` form look-ahead passes while a source
         size, a mask or an output size is set, and the passes carry those stages (docs/source_stage.md and
@@ -642,7 +655,8 @@ class Runtime:
         "resident_tower", "resident_flow", "launches_per_frame", "recurrent", "output_select", "lookahead_frames",
         "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames",
         "output_scaled", "source_filter", "output_filter", "scene_mode", "scene_frames", "scene_cuts", "scene_lookahead",
-        "scene_pass_frames", "stage_lookahead", "lookahead_staged_frames"."""
+        "scene_pass_frames", "stage_lookahead", "lookahead_staged_frames", "group_frames", "group_yuv_frames",
+        "scene_group", "scene_group_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -725,6 +739,27 @@ def process_group(runtimes, inputs, outputs) -> None:
     hs = (C.c_void_p * n)(*[rt._h.value for rt in runtimes])
     ins, outs = (JuImage * n)(*inputs), (JuImage * n)(*outputs)
     _check(lib, lib.ju_process_group(hs, ins, outs, n))
+
+
+def process_group_frames(runtimes, inputs, outputs) -> None:
+    """``ju_process_group_frames``: :func:`process_group` on :class:`JuFrame` frames of any format -- the bytes of
+    ``runtimes[i].process_frame(inputs[i], outputs[i])`` in list order; formats, colour spaces, locations and strides
+    are independent per member and side.  Unequal lists and items that are not :class:`Runtime` raise before any
+    native call."""
+    runtimes, inputs, outputs = list(runtimes), list(inputs), list(outputs)
+    n = len(runtimes)
+    if len(inputs) != n or len(outputs) != n:
+        raise ValueError("process_group_frames: as many inputs and outputs as runtimes")
+    if not all(isinstance(rt, Runtime) for rt in runtimes):
+        raise TypeError("process_group_frames: every member must be a Runtime")
+    if n == 0:
+        return
+    lib = runtimes[0]._lib
+    if any(rt._lib is not lib for rt in runtimes):
+        raise ValueError("process_group_frames: the runtimes were created through different libraries")
+    hs = (C.c_void_p * n)(*[rt._h.value for rt in runtimes])
+    ins, outs = (JuFrame * n)(*inputs), (JuFrame * n)(*outputs)
+    _check(lib, lib.ju_process_group_frames(hs, ins, outs, n))
 
 
 def gl_image(texture: int, output: bool) -> JuImage:

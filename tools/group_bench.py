@@ -9,6 +9,14 @@ shared alike), after a warm-up of every (method, N).  Prints one JSON line: per 
 over the rounds, and (a) / (b) per N.  Every device pair is registered with ju_prepare_frames first, as bench.py does,
 so (b) and (c) replay their graphs; group passes launch eagerly.
 
+--scene report|reset turns every runtime's scene detector on (threshold_milli 22000) and times
+  group: ju_process_group with ju_set_scene_group(rt, 1) (the detector rides in the passes: two launches per pass),
+  group_off: the same call with the setting at 0 (every member on its own, two detector launches per frame),
+  serial: ju_process per runtime.
+--format nv12 hands over device NV12 frames on both sides and times
+  group: ju_process_group_frames, serial: ju_process_frame per runtime.
+Both may be combined; neither runs the threads method.
+
 --trace group|single runs one method alone for a `rocprofv3 --kernel-trace --stats` run: N = 8 group calls, or the
 same number of frames through ju_process on one runtime.  --summarize <kernel_stats.csv> <frames> prints the flow
 net's kernel time per frame of such a run."""
@@ -46,7 +54,7 @@ def summarize(path, frames):
 
 
 class Streams:
-    def __init__(self, n, preset, dtype, inputs_per_stream=4):
+    def __init__(self, n, preset, dtype, inputs_per_stream=4, scene="off", fmt="bgrx"):
         import torch
         from joshupscale_amd import model_file as M
         from joshupscale_amd import runtime as R
@@ -71,6 +79,26 @@ class Streams:
                 rt.prepare_frames(self.ins[i][t], self.outs[i])
         self.lib = self.rts[0]._lib
         self.group_args = {}
+        self.scene, self.fmt = scene, fmt
+        if scene != "off":
+            for rt in self.rts:
+                rt.set_scene_detect({"report": R.SCENE_REPORT, "reset": R.SCENE_RESET}[scene], 22000)
+        if fmt == "nv12":
+            # device NV12 on both sides: any bytes are a frame (noise, as the BGRX clip is)
+            gen = torch.Generator(device="cpu").manual_seed(1234)
+            self.d_y = torch.randint(16, 236, (n, self.k, h, w), dtype=torch.uint8, generator=gen).to(dev)
+            self.d_uv = torch.randint(16, 241, (n, self.k, h // 2, w), dtype=torch.uint8, generator=gen).to(dev)
+            self.d_oy = torch.zeros((n, 4 * h, 4 * w), dtype=torch.uint8, device=dev)
+            self.d_ouv = torch.zeros((n, 2 * h, 4 * w), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            self.fins = [[R.device_frame(R.FMT_NV12, w, h, [self.d_y[i][t], self.d_uv[i][t]]) for t in range(self.k)]
+                         for i in range(n)]
+            self.fouts = [R.device_frame(R.FMT_NV12, 4 * w, 4 * h, [self.d_oy[i], self.d_ouv[i]]) for i in range(n)]
+
+    def set_scene_group(self, on):
+        if self.scene != "off":
+            for rt in self.rts:
+                rt.set_scene_group(on)
 
     def check(self, rc):
         if rc != 0:
@@ -79,20 +107,29 @@ class Streams:
     def group(self, n, ticks, start=0):
         R = self.R
         key = n
+        nv12 = self.fmt == "nv12"
         if key not in self.group_args:
             hs = (C.c_void_p * n)(*[rt._h.value for rt in self.rts[:n]])
-            per_t = [((R.JuImage * n)(*[self.ins[i][t] for i in range(n)]), (R.JuImage * n)(*self.outs[:n]))
-                     for t in range(self.k)]
+            if nv12:
+                per_t = [((R.JuFrame * n)(*[self.fins[i][t] for i in range(n)]), (R.JuFrame * n)(*self.fouts[:n]))
+                         for t in range(self.k)]
+            else:
+                per_t = [((R.JuImage * n)(*[self.ins[i][t] for i in range(n)]), (R.JuImage * n)(*self.outs[:n]))
+                         for t in range(self.k)]
             self.group_args[key] = (hs, per_t)
         hs, per_t = self.group_args[key]
-        call = self.lib.ju_process_group
+        call = self.lib.ju_process_group_frames if nv12 else self.lib.ju_process_group
         for t in range(start, start + ticks):
             a, b = per_t[t % self.k]
             self.check(call(hs, a, b, n))
 
+    group_off = group  # (the same call; timed() leaves ju_set_scene_group at 0 for it)
+
     def serial(self, n, ticks, start=0):
-        call = self.lib.ju_process
-        refs = [[(self.rts[i]._h, C.byref(self.ins[i][t]), C.byref(self.outs[i])) for t in range(self.k)] for i in range(n)]
+        nv12 = self.fmt == "nv12"
+        call = self.lib.ju_process_frame if nv12 else self.lib.ju_process
+        ins, outs = (self.fins, self.fouts) if nv12 else (self.ins, self.outs)
+        refs = [[(self.rts[i]._h, C.byref(ins[i][t]), C.byref(outs[i])) for t in range(self.k)] for i in range(n)]
         for t in range(start, start + ticks):
             for i in range(n):
                 self.check(call(*refs[i][t % self.k]))
@@ -130,6 +167,7 @@ class Streams:
 def timed(streams, method, n, ticks):
     if method == "threads":
         return streams.threads(n, ticks)
+    streams.set_scene_group(1 if method == "group" else 0)  # (waits for the stream: outside the timed region)
     t0 = time.perf_counter()
     getattr(streams, method)(n, ticks)
     return time.perf_counter() - t0
@@ -145,6 +183,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=16, help="ticks of every (method, N) before the first round")
     ap.add_argument("--trace", choices=["group", "single"], default=None)
     ap.add_argument("--ticks", type=int, default=64, help="--trace: timed ticks after a warm-up of as many")
+    ap.add_argument("--scene", choices=["off", "report", "reset"], default="off")
+    ap.add_argument("--format", choices=["bgrx", "nv12"], default="bgrx")
     ap.add_argument("--summarize", nargs=2, metavar=("CSV", "FRAMES"), default=None)
     args = ap.parse_args()
     if args.summarize:
@@ -153,7 +193,8 @@ def main():
     import torch
     torch.zeros(1, device="cuda:0")  # (torch's HIP runtime first, as bench.py does)
     if args.trace:
-        s = Streams(8 if args.trace == "group" else 1, args.preset, args.dtype)
+        s = Streams(8 if args.trace == "group" else 1, args.preset, args.dtype, scene=args.scene, fmt=args.format)
+        s.set_scene_group(1)
         if args.trace == "group":
             s.group(8, args.ticks)
             s.group(8, args.ticks)
@@ -166,8 +207,12 @@ def main():
                           "group_frames": s.rts[0].stat("group_frames")}))
         s.close()
         return
-    s = Streams(max(args.sizes), args.preset, args.dtype)
+    s = Streams(max(args.sizes), args.preset, args.dtype, scene=args.scene, fmt=args.format)
     methods = ("group", "serial", "threads")
+    if args.scene != "off":
+        methods = ("group", "group_off", "serial")
+    elif args.format != "bgrx":
+        methods = ("group", "serial")
     for n in args.sizes:
         for m in methods:
             timed(s, m, n, args.warmup)
@@ -184,15 +229,24 @@ def main():
             v = fps[(n, m)]
             row[m] = {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
         row["group_over_serial"] = round(row["group"]["median"] / row["serial"]["median"], 3)
-        row["group_over_threads"] = round(row["group"]["median"] / row["threads"]["median"], 3)
+        if "threads" in row:
+            row["group_over_threads"] = round(row["group"]["median"] / row["threads"]["median"], 3)
+        if "group_off" in row:
+            row["group_over_group_off"] = round(row["group"]["median"] / row["group_off"]["median"], 3)
         res[str(n)] = row
     group_frames = [rt.stat("group_frames") for rt in s.rts]
+    extra = {"scene": args.scene, "format": args.format,
+             "scene_group_frames": [rt.stat("scene_group_frames") for rt in s.rts],
+             "group_yuv_frames": [rt.stat("group_yuv_frames") for rt in s.rts],
+             "scene_cuts": [rt.stat("scene_cuts") for rt in s.rts]}
     s.close()
     print(json.dumps({"metric": "aggregate frames/s of N streams on one GPU", "preset": args.preset, "dtype": args.dtype,
                       "frames_per_round": args.frames, "rounds": args.rounds,
-                      "methods": {"group": "ju_process_group", "serial": "ju_process per runtime, one thread",
+                      "methods": {"group": "ju_process_group (ju_process_group_frames for --format nv12; ju_set_scene_group 1)",
+                                  "group_off": "the same call with ju_set_scene_group 0: detecting members on their own",
+                                  "serial": "ju_process (ju_process_frame) per runtime, one thread",
                                   "threads": "one thread per runtime, ju_process"},
-                      "fps": res, "group_frames": group_frames}))
+                      "fps": res, "group_frames": group_frames, **extra}))
 
 
 if __name__ == "__main__":
