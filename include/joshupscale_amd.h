@@ -279,7 +279,8 @@ JU_API int ju_prepare_batch(ju_runtime *runtime, const ju_image *inputs, const j
  * flow tensors -- those of ju_process_batch, about 210 MB at 480x270 for 8 frames, shared with its look-ahead
  * passes; the other members allocate nothing.  ju_get_stat "group_frames": frames a runtime got from group passes.
  * A member whose scene detector is on runs on its own unless it asked to ride (ju_set_scene_group); a member under a
- * source size, an output size or a mask always runs on its own, on the staged single-frame route. */
+ * source size, an output size or a mask runs on its own, on the staged single-frame route, unless it asked to ride
+ * (ju_set_stage_group). */
 JU_API int ju_process_group(ju_runtime *const *runtimes, const ju_image *inputs, const ju_image *outputs, int count);
 /* ju_process_group on frames of any format: one frame for each of `count` runtimes, synchronously.  Every plane of every
  * output -- and nothing around it --, every member's recurrent state, frame history and f16 state are those of
@@ -301,9 +302,10 @@ JU_API int ju_process_group(ju_runtime *const *runtimes, const ju_image *inputs,
  * count == 1 is ju_process_frame.
  * ju_get_stat "group_yuv_frames": frames of a runtime that went through a group pass with a non-BGRX side (also counted
  * by "group_frames").
- * Not provided: members under a source size, an output size or a mask inside group passes (they stay on the staged
- * single-frame route); graph capture of group passes (they are eager launches); a ju_prepare_* counterpart; the C++
- * plugin surface. */
+ * Members under a source size, an output size or a mask stay on the staged single-frame route unless they asked to ride
+ * (ju_set_stage_group, behind ju_set_stage_lookahead below): the pass then carries their stages.
+ * Not provided: graph capture of group passes (they are eager launches); a ju_prepare_* counterpart; the C++ plugin
+ * surface. */
 JU_API int ju_process_group_frames(ju_runtime *const *runtimes, const ju_frame *inputs, const ju_frame *outputs, int count);
 
 /* Asynchronous form for JU_LOC_DEVICE images: enqueues the same work on the
@@ -406,8 +408,10 @@ JU_API int ju_reset(ju_runtime *runtime);
  * ("lookahead_frames" / "group_frames" do not count them, "source_stage_frames" does), ju_prepare_frames /
  * ju_prepare_batch capture nothing.  JU_LOC_GRAPHICS_RESOURCE inputs are refused while a source size is set (outputs,
  * and inputs under a mask alone, are taken).  Turning both off restores the other paths.  ju_set_stage_lookahead
- * (below, behind ju_set_output_size) lifts this for the look-ahead passes of ju_process_batch and ju_process_frames.
- * Not provided: scaled or masked frames inside group passes; Lanczos or any other filter whose weights
+ * (below, behind ju_set_output_size) lifts this for the look-ahead passes of ju_process_batch and ju_process_frames,
+ * ju_set_stage_group (behind it) for the group passes of ju_process_group and ju_process_group_frames.
+ * Not provided: scaled or masked frames inside group passes of a runtime that has not asked to ride (the default:
+ * ju_set_stage_group(rt, 1), below, provides them); Lanczos or any other filter whose weights
  * need a transcendental function (they would not be defined bit for bit: docs/source_stage.md); OBS's own
  * OBS_EFFECT_BILINEAR_LOWRES arithmetic (it is not in the reference tree).  The scaler on the output side is
  * ju_set_output_size, below. */
@@ -443,7 +447,8 @@ JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
  * no look-ahead or group pass ("source_stage_frames" counts them), ju_prepare_* capture nothing.  A JU_LOC_DEVICE BGRX
  * output is written in place, any alignment and signed stride.  JU_LOC_GRAPHICS_RESOURCE outputs are refused.
  * ju_get_stat: "output_scaled" (1 / 0), "output_filter" (the JU_SCALE_* value in effect, 0 while off).
- * ju_set_stage_lookahead, below, lifts the "no look-ahead pass" for ju_process_batch and ju_process_frames. */
+ * ju_set_stage_lookahead, below, lifts the "no look-ahead pass" for ju_process_batch and ju_process_frames, and
+ * ju_set_stage_group the "no group pass" for ju_process_group and ju_process_group_frames. */
 JU_API int ju_set_output_size(ju_runtime *runtime, size_t width, size_t height, int filter);
 JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height);
 
@@ -469,8 +474,9 @@ JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *
  * place, then the output scaler and the encode by the rules of ju_set_output_size -- a deep format from that frame's own
  * f16 state, or from the blended / scaled 8-bit frame while a mask is set or "hbd_from_state" is 0.
  *
- * Unchanged by the setting: ju_process, ju_enqueue, ju_process_frame, ju_enqueue_frame, ju_process_group and the C++
- * processImage keep the staged single-frame route while a stage is set; ju_prepare_batch / ju_prepare_frames capture
+ * Unchanged by the setting: ju_process, ju_enqueue, ju_process_frame, ju_enqueue_frame, ju_process_group (whose passes
+ * have a setting of their own, ju_set_stage_group) and the C++ processImage keep the staged single-frame route while a
+ * stage is set; ju_prepare_batch / ju_prepare_frames capture
  * nothing while one is (a staged pass captures its graph at the second sighting of its buffers).
  *
  * Memory.  The pass keeps slots per frame of the look-ahead cap, made when first needed at the sizes set and dropped,
@@ -483,6 +489,53 @@ JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *
  * stage setting was on; "lookahead_frames", "lookahead_host_frames" / "lookahead_yuv_frames" and "source_stage_frames"
  * count them too (the last says what a frame went through, not which route it took). */
 JU_API int ju_set_stage_lookahead(ju_runtime *runtime, int on);
+
+/* ---- scaled and masked members inside group passes (docs/source_stage.md, docs/output_stage.md: "Group passes") ---------
+ * For the stream server whose incoming videos are not the model's size: eight 720p sources, each scaled to the model and
+ * handed back at 1080p or 2160p, one frame of each at every tick.
+ * ju_set_stage_group(rt, 1): this runtime rides in the passes of ju_process_group and ju_process_group_frames while it
+ * has a source size, a mask or an output size set, and the pass carries its stages.  Its frame must then be the sizes
+ * every entry point already demands of it: its own source size on the input side if one is set, its own output size on
+ * the output side if one is set.  For every member, every plane of its output and nothing around it, its recurrent
+ * state, frame history, f16 state, detector records and stats (but the counters below) equal those of
+ * ju_process_frame(runtimes[i], &inputs[i], &outputs[i]) with the same settings.  The default is 0: such a member runs on
+ * its own, as described above, byte for byte and stat for stat.  A value other than 0 or 1 is JU_ERR_INVALID_ARGUMENT
+ * ("ju_set_stage_group: on must be 0 or 1, got N"); the call waits for the stream; ju_reset keeps the setting.  It is
+ * independent of ju_set_stage_lookahead.
+ *
+ * The setting is per member and the members are independent: one call may mix plain members, staged members that ride,
+ * staged members with the setting off (these run alone, as before) and detecting members (ju_set_scene_group); every
+ * member may have its own source size, filter, mask and output size; the lead needs no stage.
+ *
+ * Eligibility of a riding member's pair is that of a staged look-ahead frame (ju_set_stage_lookahead, above): on a side
+ * a scaler of that member touches a JU_LOC_DEVICE BGRX image is taken at any alignment and any signed stride, on a side
+ * none touches it keeps the plain pass's alignment conditions, else the member runs on its own; host and YUV sides are
+ * taken; JU_LOC_GRAPHICS_RESOURCE frames run alone or are refused, as without the setting.  The call-wide overlap test
+ * covers every plane at its true size (source size on the input side, output size on the output side).  All size and
+ * parity checks of every member run before anything is launched or uploaded; a refused call changes no runtime.
+ *
+ * Inside a pass: host planes upload at each member's own source size and ONE launch decodes every non-BGRX input at its
+ * own size; ONE launch then scales the sources of all scaled members, each through its own tables and filter, to the
+ * model's input, in front of the group scene launch and the flow net, which read exactly the model-size frame they read
+ * member by member.  Behind each member's own steps, on the lead's stream: that member's mask blend in place (its source
+ * sampled from its own source rows), its output scaler and its encode by the rules of ju_set_output_size -- a deep format
+ * from that member's own f16 state, or from the blended / scaled 8-bit frame while it has a mask or "hbd_from_state" is
+ * 0.  Host outputs are copied out at output size while the next member's kernels run.  The pass stays synchronous and
+ * its launches eager.
+ *
+ * Memory.  A member contributes one frame per pass, so it owns ONE set of slots (not one per frame of a cap), made when
+ * first needed at its own sizes and dropped whenever ju_set_source_size, ju_set_source_mask, ju_set_output_size or this
+ * call changes anything for it: under a source size a model-size input (4 bytes per pixel; 0.5 MB at 480x270) and, for
+ * a host or non-BGRX source, a source-size BGRX frame (3.7 MB at 1280x720) and its host planes; under an output size a
+ * model-size output (8.3 MB at 1920x1080) and, for a host or non-BGRX output, an 8-bit frame at output size (33 MB at
+ * 3840x2160) and its host planes plus, for a deep format from the state, a 16-bit frame (66 MB at 3840x2160).  A mask
+ * alone needs none.  The slots live in the member: no setter and no ju_destroy touches another runtime's memory.
+ *
+ * ju_get_stat: "stage_group" (1 / 0) and "group_staged_frames", this runtime's frames that went through a group pass
+ * while one of its stage settings was on; "group_frames", "group_yuv_frames" and "source_stage_frames" count them too.
+ * Not provided: graph capture of group passes; a ju_prepare_* counterpart; GL resources under a stage; the C++ plugin
+ * surface. */
+JU_API int ju_set_stage_group(ju_runtime *runtime, int on); /* default 0 */
 
 /* ---- scene cuts: detected on the GPU, the recurrence restarted at them (docs/scene_detect.md) -----------------------------
  * Every frame is built from the previous output warped by a flow field and from three frames of history; across a hard

@@ -214,6 +214,22 @@ JU_API int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, s
 JU_API int ju_debug_scale_items(int count, int filter, void *const *dst, const ptrdiff_t *dst_strides, size_t dst_width,
     size_t dst_height, const void *const *src, const ptrdiff_t *src_strides, size_t src_width, size_t src_height);
 
+/* The sources of a group pass scaled in one launch (scale_bgrx_members_kernel; docs/source_stage.md "Group passes"): ONE
+ * synchronous launch over `count` (1 .. 8) members on caller-supplied device buffers, on the current device.  Member i
+ * reads BGRX rows of src_widths[i] x src_heights[i] at src[i] with the signed stride src_strides[i], through the filter
+ * filters[i] (a JU_SCALE_* value, held to its ratio limits before any device call), and writes dst_width x dst_height --
+ * the one destination size of the launch -- at dst[i] with dst_strides[i]; any byte alignment each, sizes 1 .. 32768.  Per
+ * member the bytes of ju_debug_scale op 0. */
+JU_API int ju_debug_scale_members(int count, const int *filters, void *const *dst, const ptrdiff_t *dst_strides,
+    size_t dst_width, size_t dst_height, const void *const *src, const ptrdiff_t *src_strides, const size_t *src_widths,
+    const size_t *src_heights);
+
+/* The sized form of the passes' decode launch alone (yuv_to_bgrx_items_sized_kernel: the non-BGRX inputs of a group pass
+ * whose members differ in size): ju_debug_yuv_items with a width and a height per item, widths[i] x heights[i] (the parity
+ * rules of item i's format apply to them).  Per item the bytes of ju_debug_yuv_items at that size. */
+JU_API int ju_debug_yuv_items_sized(int count, const int *formats, const int *colorspaces, const size_t *widths,
+    const size_t *heights, void *const *bgrx, const ptrdiff_t *bgrx_strides, void *const *planes, const ptrdiff_t *strides);
+
 /* The temporal output filter alone (launchTemporalFilter: zero_words_kernel, temporal_reduce_kernel, temporal_blend_kernel;
  * tests/temporal_reference.py), on caller-supplied device buffers, on the current device (synchronous).  `state`: the dense
  * f16 tensor [4 height][4 width][4] (8-byte aligned), rewritten in place; `pre_warp`: the same shape, read only; `out`: BGRX

@@ -355,6 +355,10 @@ int ju_set_stage_lookahead(ju_runtime *runtime, int on) {
 	return guarded([&] { engineOf(runtime).setStageLookahead(on); });
 }
 
+int ju_set_stage_group(ju_runtime *runtime, int on) {
+	return guarded([&] { engineOf(runtime).setStageGroup(on); });
+}
+
 int ju_reset(ju_runtime *runtime) {
 	return guarded([&] { engineOf(runtime).reset(); });
 }
@@ -606,6 +610,26 @@ int ju_debug_yuv_items(int count, const int *formats, const int *colorspaces, si
 	});
 }
 
+int ju_debug_yuv_items_sized(int count, const int *formats, const int *colorspaces, const size_t *widths, const size_t *heights,
+    void *const *bgrx, const ptrdiff_t *bgrx_strides, void *const *planes, const ptrdiff_t *strides) {
+	return guarded([&] {
+		const ConversionHook hook{"ju_debug_yuv_items_sized", "a YUV", [](Info) { return true; }, 1, false};
+		if (count < 1 || count > ju::kFlowBatchMax) hook.refuse("1 .. 8 items");
+		if (!formats || !colorspaces || !widths || !heights || !bgrx || !bgrx_strides || !planes || !strides) hook.refuse("null argument");
+		for (int i = 0; i < count; ++i) hook.format(formats[i]);  // (every format before any buffer)
+		ju::YuvDecodeSizedItems items{};
+		for (int i = 0; i < count; ++i) {
+			const ju::YuvPlanes p = hook.planes(hook.format(formats[i]), 0, widths[i], heights[i], bgrx[i], bgrx_strides[i],
+			    planes + 3 * i, strides + 3 * i);
+			items.item[i] = ju::yuvDecodeItem(formats[i], colorspaces[i], p, static_cast<std::uint8_t *>(bgrx[i]), bgrx_strides[i]);
+			items.width[i] = static_cast<int>(widths[i]);
+			items.height[i] = static_cast<int>(heights[i]);
+		}
+		ju::launchYuvToBgrxItemsSized(items, count, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
 int ju_debug_source(int op, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, const void *src,
     ptrdiff_t src_stride, size_t src_width, size_t src_height, const void *mask, ptrdiff_t mask_stride, size_t mask_width,
     size_t mask_height) {
@@ -745,6 +769,41 @@ int ju_debug_scale_items(int count, int filter, void *const *dst, const ptrdiff_
 		ju::Scaler scale;
 		scale.build(src_width, src_height, dst_width, dst_height, filter);
 		scale.scaleBgrxItems(items, count, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_scale_members(int count, const int *filters, void *const *dst, const ptrdiff_t *dst_strides, size_t dst_width,
+    size_t dst_height, const void *const *src, const ptrdiff_t *src_strides, const size_t *src_widths, const size_t *src_heights) {
+	return guarded([&] {
+		if (count < 1 || count > ju::kFlowBatchMax) throw std::invalid_argument("ju_debug_scale_members: count must be 1 .. 8");
+		if (filters == nullptr || dst == nullptr || dst_strides == nullptr || src == nullptr || src_strides == nullptr ||
+		    src_widths == nullptr || src_heights == nullptr) {
+			throw std::invalid_argument("ju_debug_scale_members: NULL array");
+		}
+		constexpr size_t kMost = 1u << 15;
+		if (dst_width < 1 || dst_height < 1 || dst_width > kMost || dst_height > kMost) {
+			throw std::invalid_argument("ju_debug_scale_members: a size outside 1 .. 32768");
+		}
+		for (int i = 0; i < count; ++i) {
+			if (src_widths[i] < 1 || src_heights[i] < 1 || src_widths[i] > kMost || src_heights[i] > kMost) {
+				throw std::invalid_argument("ju_debug_scale_members: a size outside 1 .. 32768");
+			}
+			if (dst[i] == nullptr || src[i] == nullptr) throw std::invalid_argument("ju_debug_scale_members: NULL buffer");
+		}
+		for (int i = 0; i < count; ++i) {  // (every member's filter and ratios before any device call: buildScaleAxis refuses)
+			ju::buildScaleAxis(static_cast<int>(src_widths[i]), static_cast<int>(dst_width), filters[i]);
+			ju::buildScaleAxis(static_cast<int>(src_heights[i]), static_cast<int>(dst_height), filters[i]);
+		}
+		// each member its own scaler, as each runtime of a group pass has
+		ju::Scaler scalers[ju::kFlowBatchMax];
+		ju::ScaleMembers members{};
+		for (int i = 0; i < count; ++i) {
+			scalers[i].build(src_widths[i], src_heights[i], dst_width, dst_height, filters[i]);
+			members.member[i] = scalers[i].member(static_cast<const std::uint8_t *>(src[i]), src_strides[i],
+			    static_cast<std::uint8_t *>(dst[i]), dst_strides[i]);
+		}
+		ju::launchScaleBgrxMembers(members, count, static_cast<int>(dst_width), static_cast<int>(dst_height), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

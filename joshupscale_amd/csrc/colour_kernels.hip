@@ -1568,6 +1568,31 @@ __global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItem
 	       }, it, W, H, idx));
 }
 
+// The sized form (launchYuvToBgrxItemsSized: the members of a group pass): item blockIdx.y at its OWN width and height, read
+// with the item from the kernel arguments.  The grid covers the largest item's strips; every strip body returns beyond its
+// own frame's count, as the upper half of a 4:2:0 item's grid does above.  The strip bodies are the ones above.
+__global__ __launch_bounds__(256) void yuv_to_bgrx_items_sized_kernel(YuvDecodeSizedItems items) {
+	const YuvDecodeItem &it = items.item[blockIdx.y];
+	const int W = items.width[blockIdx.y], H = items.height[blockIdx.y];
+	const int idx = blockIdx.x * 256 + threadIdx.x;
+	using Item = const YuvDecodeItem &;
+	(void)(forFormat(Yuv420{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       yuv420ToBgrxStrip<f() == kNv12>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Yuv420p10{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       yuv420p10ToBgrxStrip<f() == kP010>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Sampled{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       yuvSampledToBgrxStrip<f()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Grouped{}, it.format, [](auto, Item it, int W, int H, int idx) {
+		       v210ToBgrxStrip(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx) ||
+	       forFormat(Rgb{}, it.format, [](auto f, Item it, int W, int H, int idx) {
+		       rgbToBgrxStrip<f()>(it.src, it.dst, it.dstStride, W, H, idx);
+	       }, it, W, H, idx));
+}
+
 int roundHalfAway(double x) { return static_cast<int>(std::copysign(std::floor(std::fabs(x) * 65536.0 + 0.5), x)); }
 
 void colourSpace(int cs, double *kr, double *kb, bool *limited) {
@@ -1701,6 +1726,17 @@ void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, 
 	hipLaunchKernelGGL(yuv420_to_bgrx_items_kernel, dim3(blocksFor(threads), count), dim3(256), 0, stream, items, width,
 	    height);
 	hipCheckLaunch("yuv420_to_bgrx_items");
+}
+
+void launchYuvToBgrxItemsSized(const YuvDecodeSizedItems &items, int count, hipStream_t stream) {
+	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("yuv_to_bgrx_items_sized: 1 .. 8 items");
+	std::size_t threads = 0;  // (the most any item needs at its own size)
+	for (int i = 0; i < count; ++i) {
+		if (items.width[i] < 1 || items.height[i] < 1) throw std::invalid_argument("yuv_to_bgrx_items_sized: a size below 1");
+		threads = std::max(threads, stripThreads(formatInfo(items.item[i].format), items.width[i], items.height[i]));
+	}
+	hipLaunchKernelGGL(yuv_to_bgrx_items_sized_kernel, dim3(blocksFor(threads), count), dim3(256), 0, stream, items);
+	hipCheckLaunch("yuv_to_bgrx_items_sized");
 }
 
 void launchEncodeFrame(int format, int colorspace, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst,

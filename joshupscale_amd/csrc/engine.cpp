@@ -1868,6 +1868,8 @@ double Engine::stat(const std::string &key) const {
 	if (key == "scene_pass_frames") return static_cast<double>(m_ScenePassFrames);
 	if (key == "stage_lookahead") return m_StageLookahead ? 1.0 : 0.0;
 	if (key == "lookahead_staged_frames") return static_cast<double>(m_BatchStagedFrames);  // ... of them under a stage setting
+	if (key == "stage_group") return m_StageGroup ? 1.0 : 0.0;
+	if (key == "group_staged_frames") return static_cast<double>(m_GroupStagedFrames);  // group-pass frames under a stage setting
 	// (the detector's own counters, as of the steps that have completed: the decision writes them to host-mapped memory)
 	if (key == "scene_frames" || key == "scene_cuts") {
 		const bool cuts = key == "scene_cuts";

@@ -107,7 +107,8 @@ public:
 	// width x height from now on and are scaled to the model's input on the GPU ((0, 0): off; filter: a JU_SCALE_* value --
 	// 0 triangle, 2 Catmull-Rom, 3 Mitchell).  setSourceMask: a BGRX image of any size, host or device, copied now (nullptr: no mask); the source is
 	// drawn over every output frame through it.  While either is set every frame of every entry point runs one by one
-	// through the staged path of submitFrame -- but for the look-ahead passes setStageLookahead allows.  reset() keeps both.
+	// through the staged path of submitFrame -- but for the look-ahead passes setStageLookahead allows and the group passes
+	// setStageGroup allows.  reset() keeps both.
 	void setSourceSize(std::size_t width, std::size_t height, int filter);
 	void sourceSize(std::size_t *width, std::size_t *height) const;
 	void setSourceMask(const Frame *mask);
@@ -115,7 +116,7 @@ public:
 	// width x height from now on -- the upscaled frame scaled on the GPU behind the graph and the mask blend ((0, 0): off;
 	// filter: a JU_SCALE_* value, as for the source size).  State, frame history and flow inputs are the unscaled run's.  While it is set
 	// every frame of every entry point runs one by one through submitFrame, as for a source size (setStageLookahead: the
-	// look-ahead passes carry it).  reset() keeps it.
+	// look-ahead passes carry it; setStageGroup: the group passes).  reset() keeps it.
 	void setOutputSize(std::size_t width, std::size_t height, int filter);
 	void outputSize(std::size_t *width, std::size_t *height) const;
 	bool sourceStage() const { return m_SrcScale.set() || m_MaskW != 0 || m_OutScale.set(); }
@@ -138,6 +139,11 @@ public:
 	// "Scaled and masked frames inside a pass"): 0 (default) = such a runtime's frames run one by one through submitFrame,
 	// 1 = processBatch / processFrames form passes that carry the stages.  Waits for the stream; reset() keeps it.
 	void setStageLookahead(int on);
+	// Group passes while a source size, a mask or an output size is set (ju_set_stage_group; engine_passes.cpp, "Scaled and
+	// masked members inside a group pass"): 0 (default) = processGroup / processGroupFrames run such a runtime on its own
+	// through submitFrame, 1 = it rides in the passes, which carry its stages.  Independent of setStageLookahead.  Waits for
+	// the stream; reset() keeps it.
+	void setStageGroup(int on);
 
 	FrameSize frameSize() const;
 	int device() const { return m_Device; }
@@ -552,19 +558,44 @@ private:
 	DeviceBuffer m_StageSrc[kFlowBatchMax], m_StageSrcYuv[kFlowBatchMax], m_StageIn[kFlowBatchMax];
 	DeviceBuffer m_StageModelOut[kFlowBatchMax], m_StageOut8[kFlowBatchMax], m_StageOut16[kFlowBatchMax], m_StageOutYuv[kFlowBatchMax];
 	FrameIO m_PassEnds[kFlowBatchMax];
+	// the size frame i of the pass bound last has on either side (bindBatch: passSizes for all; bindGroup: member i's own)
+	struct PassExtent {
+		std::size_t inW = 0, inH = 0, outW = 0, outH = 0;
+	};
+	PassExtent m_PassSize[kFlowBatchMax];
 	struct PassCopy {
 		DeviceBuffer *image = nullptr, *planes = nullptr;
 	};
 	PassCopy m_PassUp[kFlowBatchMax], m_PassDown[kFlowBatchMax];
 	std::uint64_t m_BatchStagedFrames = 0;
 	void dropStagePasses();
+	// Scaled and masked members inside group passes (setStageGroup; engine_passes.cpp).  groupStage(): what this runtime
+	// brings into a group pass -- stagePass()'s bits under its own setting.  A member contributes one frame per pass, so it
+	// owns ONE set of slots, m_GroupSlots, named as the look-ahead passes' (src / srcYuv at source size, in / modelOut at the
+	// model's sizes, out8 / out16 / outYuv at output size), each made when first needed at THIS runtime's sizes and dropped
+	// by dropStagePasses -- whenever one of its stage setters changes anything.  They live in the member, not the lead: a
+	// setter or the destruction of one runtime touches no other runtime's memory, and the lead keeps no pointer to them
+	// beyond the call (runGroupPass clears m_PassUp / m_PassDown).  m_GroupStagedFrames: "group_staged_frames".
+	bool m_StageGroup = false;
+	int groupStage() const {
+		if (!m_StageGroup || !sourceStage()) return 0;
+		return (m_SrcScale.set() ? 1 : 0) | (m_MaskW != 0 ? 2 : 0) | (m_OutScale.set() ? 4 : 0);
+	}
+	struct GroupSlots {
+		DeviceBuffer src, srcYuv, in, modelOut, out8, out16, outYuv;
+	};
+	GroupSlots m_GroupSlots;
+	std::uint64_t m_GroupStagedFrames = 0;
+	// bindBatch for the members of a group pass, on the lead: member i's pair at member i's own sizes (stage[i] =
+	// m[i]->groupStage()), a side under a scaler through member i's own slots, any other through the lead's
+	void bindGroup(Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n, const int *stage);
 	// the size frames must have on a side of a pass bound with `stage`
 	void passSizes(int stage, std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const;
 	std::unique_ptr<Stream> m_CopyStream;
 	PinnedWords m_PassSignal;
 	unsigned m_PassSignalBase = 0;
 	std::uint64_t m_BatchHostFrames = 0, m_BatchYuvFrames = 0;
-	// group: as a member of a group pass -- no stage (the caller keeps staged members out) and whatever the detector's setting
+	// group: as a member of a group pass -- under groupStage() in place of stagePass(), and the detector's group setting
 	bool passEligible(const AnyFrame &in, const AnyFrame &out, bool group = false) const;
 	void uploadPassInputs(const AnyFrame *in, int n);
 	void drainPassOutputs(const AnyFrame *out, int n);

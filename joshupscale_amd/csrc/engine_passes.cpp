@@ -253,8 +253,9 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 // place (directEligible's conditions) or a host image of the right size (staged through the pass's own device buffers).
 // A YUV side (checked by checkFrame before: processFrames) always can: the conversion kernels take any alignment.
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out, bool group) const {
-	// (scaled / masked frames run one by one through submitFrame unless the passes carry the stages: setStageLookahead)
-	const int stage = group ? 0 : stagePass();
+	// (scaled / masked frames run one by one through submitFrame unless the passes carry the stages: setStageLookahead; a
+	// group pass: setStageGroup)
+	const int stage = group ? groupStage() : stagePass();
 	if (sourceStage() && !stage) return false;
 	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
 	// unless the pass carries the detector and applies the cuts itself: setSceneLookahead; a group pass: setSceneGroup)
@@ -313,6 +314,17 @@ void Engine::dropStagePasses() {
 	for (DeviceBuffer *slots : {m_StageSrc, m_StageSrcYuv, m_StageIn, m_StageModelOut, m_StageOut8, m_StageOut16, m_StageOutYuv}) {
 		for (int i = 0; i < kFlowBatchMax; ++i) slots[i] = DeviceBuffer();
 	}
+	// (this runtime's slots as a member of group passes: of the old sizes too.  A group pass is synchronous, so the lead's
+	// stream, which ran the launches that used them, has drained, and no lead keeps a pointer to them: runGroupPass)
+	m_GroupSlots = GroupSlots();
+}
+
+void Engine::setStageGroup(int on) {
+	if (on != 0 && on != 1) throw std::invalid_argument("ju_set_stage_group: on must be 0 or 1, got " + std::to_string(on));
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();
+	if (m_StageGroup != (on != 0)) m_GroupSlots = GroupSlots();
+	m_StageGroup = on != 0;
 }
 
 // Binds the n frames of a pass: m_BatchIO[i] = what frame i's kernels read and write -- the caller's device memory, or
@@ -348,6 +360,7 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 		FrameIO &io = m_BatchIO[i];
 		PassFrame &pf = m_BatchHost[i];
 		PassKey &k = key[static_cast<std::size_t>(i)];
+		m_PassSize[i] = PassExtent{inW, inH, outW, outH};
 		if (scaledIn) {
 			if (in[i].yuv || locationOf(in[i]) == Location::Host) slots(m_StageSrc, bytes.source);
 			if (in[i].yuv && locationOf(in[i]) == Location::Host) slots(m_StageSrcYuv, yuvStageBytes(kFormatTable, inW, inH));
@@ -383,6 +396,57 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 		if (stage) k.ends = DirectKey{m_PassEnds[i].in, m_PassEnds[i].inStride, m_PassEnds[i].out, m_PassEnds[i].outStride, 0};
 	}
 	return key;
+}
+
+// The members of a group pass, bound on the lead (runGroupPass): bindBatch with member i's own stage bits and sizes in
+// place of the lead's.  A side no scaler of member i touches is bound exactly as a plain group pass binds it -- the caller's
+// device rows, or the lead's slot i (m_PassIn / m_PassOut and their plane buffers, at the model's sizes).  A side under
+// member i's source or output scaler goes through member i's OWN slots (m_GroupSlots), at member i's sizes: the source-size
+// rows the decode / upload fills and the scale launch reads land in m_PassEnds[i].in, the model-size input the scale launch
+// fills in m_BatchIO[i].in; on the output side m_BatchIO[i].out is the model-size frame the member's tail writes (and its
+// blend rewrites) and m_PassEnds[i].out the output-size rows its scaler writes.  No graph key: group passes are eager.
+void Engine::bindGroup(Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n, const int *stage) {
+	const FrameSize fs = frameSize();
+	m_PassStage = 0;
+	for (int i = 0; i < n; ++i) {
+		Engine &e = *m[i];
+		PassExtent &sz = m_PassSize[i];
+		e.passSizes(stage[i], &sz.inW, &sz.inH, &sz.outW, &sz.outH);
+		const bool scaledIn = (stage[i] & 1) != 0, scaledOut = (stage[i] & 4) != 0;
+		GroupSlots &g = e.m_GroupSlots;
+		const GroupSlotNeeds need = groupSlotNeeds(stage[i], in[i].yuv || locationOf(in[i]) == Location::Host,
+		    out[i].yuv || locationOf(out[i]) == Location::Host, out[i].yuv && e.deepFromState(out[i].planes.format));
+		const StageSlotBytes bytes = stageSlotBytes(sz.inW, sz.inH, fs.inputWidth, fs.inputHeight, fs.outputWidth, fs.outputHeight,
+		    sz.outW, sz.outH);
+		auto slot = [](DeviceBuffer &b, std::size_t size) {
+			if (!b.get()) b = DeviceBuffer(size);
+		};
+		if (need.input) slot(g.in, bytes.input);
+		if (need.modelOutput) slot(g.modelOut, bytes.modelOutput);
+		if (need.out16) slot(g.out16, bytes.out16);
+		// (g.src / g.out8 and the plane buffers: made by bindSide, which is handed the member's sizes, when the side needs them)
+		m_PassUp[i] = scaledIn ? PassCopy{&g.src, &g.srcYuv} : PassCopy{&m_PassIn[i], &m_PassYuvIn[i]};
+		m_PassDown[i] = scaledOut ? PassCopy{&g.out8, &g.outYuv} : PassCopy{&m_PassOut[i], &m_PassYuvOut[i]};
+		PassFrame &pf = m_BatchHost[i];
+		YuvKey unusedIn, unusedOut;
+		const BoundRows r = bindSide(in[i], sz.inW, sz.inH, m_PassUp[i].image, m_PassUp[i].planes, &pf.in, &unusedIn);
+		const BoundRows w = bindSide(out[i], sz.outW, sz.outH, m_PassDown[i].image, m_PassDown[i].planes, &pf.out, &unusedOut);
+		FrameIO &io = m_BatchIO[i];
+		io = FrameIO{r.ptr, r.stride, w.ptr, w.stride};
+		m_PassEnds[i] = io;
+		if (scaledIn) {
+			io.in = g.in.as<std::uint8_t>();
+			io.inStride = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
+		}
+		if (scaledOut) {
+			io.out = g.modelOut.as<std::uint8_t>();
+			io.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
+		}
+		if (pf.out.host) {
+			if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
+			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
+		}
+	}
 }
 
 Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::size_t height, DeviceBuffer *image,
@@ -423,11 +487,10 @@ Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::si
 // engine's stream in front of the pass's launches.  Pageable memory: the runtime stages or page-locks per call, as in
 // stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in stageInYuv.
 void Engine::uploadPassInputs(const AnyFrame *in, int n) {
-	std::size_t inW, inH, outW, outH;
-	passSizes(m_PassStage, &inW, &inH, &outW, &outH);  // (a staged pass: at source size, into the source-size slots)
-	const std::size_t rowBytes = inW * 4, rows = inH;
 	for (int i = 0; i < n; ++i) {
 		if (!m_BatchHost[i].in.host) continue;
+		// (a staged frame: at source size, into the source-size slot; a group pass: each member's own size)
+		const std::size_t rowBytes = m_PassSize[i].inW * 4, rows = m_PassSize[i].inH;
 		if (in[i].yuv) {
 			copyPlanes(in[i].planes, m_PassUp[i].planes->as<std::uint8_t>(), true, m_Stream);
 			continue;
@@ -442,9 +505,6 @@ void Engine::uploadPassInputs(const AnyFrame *in, int n) {
 // that has not arrived never will.  A YUV frame goes out plane by plane from its staging slot (3.1 MB at 1080p instead of
 // BGRX's 8.3 MB), as in stageOutYuv.
 void Engine::drainPassOutputs(const AnyFrame *out, int n) {
-	std::size_t inW, inH, outW, outH;
-	passSizes(m_PassStage, &inW, &inH, &outW, &outH);  // (a staged pass: rows and planes at the output size)
-	const std::size_t rowBytes = outW * 4, rows = outH;
 	volatile unsigned *word = m_PassSignal.host();
 	unsigned due = 0;
 	bool any = false;
@@ -465,6 +525,8 @@ void Engine::drainPassOutputs(const AnyFrame *out, int n) {
 			}
 		}
 		any = true;
+		// (a staged frame: rows and planes at the output size; a group pass: each member's own)
+		const std::size_t rowBytes = m_PassSize[i].outW * 4, rows = m_PassSize[i].outH;
 		if (out[i].yuv) {
 			copyPlanes(out[i].planes, m_PassDown[i].planes->as<std::uint8_t>(), false, *m_CopyStream);
 			continue;
@@ -707,7 +769,8 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 // the lead: host planes into the lead's slots m_PassIn / m_PassYuvIn, uploaded up front); ONE decode launch in front of
 // the flow net covers every non-BGRX input of the pass (the items form of processFrames), and each member's encode sits
 // behind that member's own steps on the lead's stream -- a deep format from THAT member's f16 state, the half its step
-// just wrote.  Members under a source size, an output size or a mask stay on the staged single-frame route.
+// just wrote.  Members under a source size, an output size or a mask stay on the staged single-frame route unless they
+// asked to ride (setStageGroup, below).
 //
 // The scene detector inside a group pass (setSceneGroup; docs/scene_detect.md "Group passes").  The members are
 // independent streams, so no cut-aware history is needed: scene_group_kernel takes the decision of every detecting
@@ -717,6 +780,23 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 // that reads m_Packed[set_i] as m_GroupPrev[i].  One exception to "writes nothing it reads", as in a look-ahead pass: those
 // two buffers may be zeroed -- which is what the re-run of the members, whose decisions stand (m_SceneRerun), wants to
 // find there too.
+//
+// Scaled and masked members inside a group pass (setStageGroup; docs/source_stage.md and docs/output_stage.md, "Group
+// passes").  The stages sit outside the recurrence, so a pass takes them as a staged look-ahead pass does, per member
+// instead of per frame: host planes upload and non-BGRX inputs decode at each member's OWN size (the decode launch's sized
+// form), ONE launch (scale_bgrx_members_kernel: every member with its own source size, tables and filter form) scales the
+// sources of all scaled members to the model's input in front of the group scene launch and the flow net, and behind each
+// member's own steps follow that member's blend in place, its output scaler and its encode -- the single-frame launches
+// with the member's own Scaler and mask.  What the network reads and writes in between are the member's own model-size
+// slots (m_GroupSlots; bindGroup).
+//
+// A pass that runs again.  The blend rewrites the model-size frame in place, and the scale launch, the decode and the
+// uploads fill slots -- but every one of those is either a slot the pass alone writes (the lead's, the member's own) or the
+// caller's OUTPUT, never one of the call's inputs: the overlap test of processGroupFrames keeps every output plane, at its
+// true size, off every input plane, and the states and histories go to the other halves.  The re-run of a member goes
+// through its own process(), i.e. submitFrame, which stages again from the caller's source into the member's single-frame
+// staging buffers and recomputes blend, scale and encode from there; it reads nothing the pass wrote.  So the bytes of a
+// re-run are those of the member run alone, and "source_stage_frames" counts the frame once, by submitFrame.
 // ---------------------------------------------------------------------------------------------------------------
 bool Engine::sameModel(const Engine &o) const {
 	return m_Device == o.m_Device && m_ModelDigest == o.m_ModelDigest && m_DtypeOverride == o.m_DtypeOverride;
@@ -775,8 +855,9 @@ void Engine::processGroupFrames(Engine *const *members, const AnyFrame *in, cons
 	std::vector<int> pass, rest;
 	// (a detecting runtime stays member by member unless it asked to ride: setSceneGroup -- the pass then carries its detector)
 	for (int i = 0; i < count; ++i) {
-		// (no stage: a scaled or masked member stays on the staged single-frame route, whatever setStageLookahead says)
-		(!members[i]->sourceStage() && members[i]->passEligible(in[i], out[i], true) ? pass : rest).push_back(i);
+		// (a scaled or masked member stays on the staged single-frame route, whatever setStageLookahead says, unless it asked
+		// to ride: setStageGroup -- passEligible then judges its pair as a staged look-ahead frame's, at its own sizes)
+		(members[i]->passEligible(in[i], out[i], true) ? pass : rest).push_back(i);
 	}
 	const int cap = lead.m_BatchMax;
 	if (clash || pass.size() < 2 || cap < 2) {
@@ -807,8 +888,24 @@ void Engine::processGroupFrames(Engine *const *members, const AnyFrame *in, cons
 void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n) {
 	int sets[kFlowBatchMax];
 	for (int i = 0; i < n; ++i) sets[i] = m[i]->m_Idx;
-	L.bindBatch(in, out, n, 0, 0);  // L.m_BatchIO[i]: member i's frame (a host one through L.m_PassIn[i] / m_PassOut[i])
-	L.uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
+	// what each member brings along (setStageGroup): bit 0 its source scaler, bit 1 its mask, bit 2 its output scaler
+	int stage[kFlowBatchMax];
+	bool anyScaledIn = false;
+	for (int i = 0; i < n; ++i) {
+		stage[i] = m[i]->groupStage();
+		anyScaledIn = anyScaledIn || (stage[i] & 1) != 0;
+	}
+	// L.m_BatchIO[i]: what member i's network reads and writes (a host frame through L.m_PassIn[i] / m_PassOut[i], a scaled
+	// side through member i's own model-size slot); L.m_PassEnds[i]: member i's rows at its own source / output size
+	L.bindGroup(m, in, out, n, stage);
+	struct Unbind {  // (the lead keeps no pointer to a member's slots beyond the pass)
+		Engine &lead;
+		int n;
+		~Unbind() {
+			for (int i = 0; i < n; ++i) lead.m_PassUp[i] = lead.m_PassDown[i] = PassCopy{};
+		}
+	} unbind{L, n};
+	L.uploadPassInputs(in, n);  // (each at its member's own size; outside the chain lock: a pageable upload blocks its caller)
 	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
 	// The detecting members (they ride because they asked to: setSceneGroup).  What their decisions read that varies from
 	// tick to tick goes into each member's own host-mapped words; the pass is synchronous, so nothing reads them now.
@@ -848,17 +945,40 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		bool resident = false;
 		for (int i = 0; i < n; ++i) resident = resident || m[i]->m_Resident;
 		std::unique_lock<std::mutex> chain = L.chainBegin(resident);
-		// 2a. the pass's non-BGRX inputs into their members' BGRX slots of the lead, all in ONE launch (runBatch's)
+		// 2a. the pass's non-BGRX inputs into their members' BGRX slots, all in ONE launch (runBatch's): each at its own
+		// size -- a scaled member's at its source size into its source-size slot, the others' at the model's into the lead's
+		// slots.  While no member of the pass is scaled that is the launch of one size, unchanged.
 		const FrameSize fs = L.frameSize();
-		YuvDecodeItems items{};
+		YuvDecodeSizedItems items{};
 		int decodes = 0;
 		for (int i = 0; i < n; ++i) {
 			const PassFrame &pf = L.m_BatchHost[i];
 			if (!pf.in.yuv) continue;
-			items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(L.m_BatchIO[i].in),
-			    L.m_BatchIO[i].inStride);
+			items.width[decodes] = static_cast<int>(L.m_PassSize[i].inW);
+			items.height[decodes] = static_cast<int>(L.m_PassSize[i].inH);
+			items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(L.m_PassEnds[i].in),
+			    L.m_PassEnds[i].inStride);
 		}
-		if (decodes) launchYuv420ToBgrxItems(items, decodes, static_cast<int>(fs.inputWidth), static_cast<int>(fs.inputHeight), L.m_Stream);
+		if (decodes && anyScaledIn) {
+			launchYuvToBgrxItemsSized(items, decodes, L.m_Stream);
+		} else if (decodes) {
+			YuvDecodeItems same{};
+			for (int k = 0; k < decodes; ++k) same.item[k] = items.item[k];
+			launchYuv420ToBgrxItems(same, decodes, static_cast<int>(fs.inputWidth), static_cast<int>(fs.inputHeight), L.m_Stream);
+		}
+		// 2a'. ONE launch scales the sources of all scaled members -- the caller's device images where they are, the upload
+		// slots, the slots the decode launch above fills -- each through its own member's tables into that member's model-size
+		// input, in front of the detector and the flow net, which therefore read exactly what submitFrame gives them
+		if (anyScaledIn) {
+			ScaleMembers scale{};
+			int scaled = 0;
+			for (int i = 0; i < n; ++i) {
+				if (!(stage[i] & 1)) continue;
+				scale.member[scaled++] = m[i]->m_SrcScale.member(L.m_PassEnds[i].in, L.m_PassEnds[i].inStride,
+				    const_cast<std::uint8_t *>(L.m_BatchIO[i].in), L.m_BatchIO[i].inStride);
+			}
+			launchScaleBgrxMembers(scale, scaled, static_cast<int>(fs.inputWidth), static_cast<int>(fs.inputHeight), L.m_Stream);
+		}
 		// 2b. the scene detector inside a group pass: every member's frame is in place (the caller's device frame, the lead's
 		// upload slot, the slot the decode launch fills), so ONE launch takes the decision of every detecting member -- each
 		// against its OWN kept frame, state and ring (the streams are independent: no cut-aware history) -- and ONE more
@@ -921,13 +1041,36 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 			for (const Step &st : e.m_Program[sets[i]]) {
 				if (st.tag != "flow" && st.tag != "pack") st.run(L.m_Stream);
 			}
-			// a non-BGRX output: member i's BGRX slot of the lead into the caller's device planes / the staging slot, behind
-			// member i's own steps.  A deep format is encoded from the f16 state THIS MEMBER's step just wrote -- its own
-			// m_State[set_i ^ 1] (a flow-free member: its one scratch state), never the lead's
+			// behind member i's own steps, on the lead's stream, what submitFrame strings behind the program -- the existing
+			// single-frame launches with member i's own mask and scaler.  The mask, in place over the model-size frame member
+			// i's tail wrote (a slot the pass alone writes, or the caller's output), its source sampled from member i's own
+			// source rows -- or the model-size input when it has no source size
 			const PassSide &po = L.m_BatchHost[i].out;
+			const PassExtent &sz = L.m_PassSize[i];
+			const FrameIO &ends = L.m_PassEnds[i];
+			void *stateOut = e.m_State[recurrent ? sets[i] ^ 1 : 0].get();
+			if (stage[i] & 2) {
+				launchMaskBlend(L.m_BatchIO[i].out, L.m_BatchIO[i].outStride, static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight),
+				    ends.in, ends.inStride, static_cast<int>(sz.inW), static_cast<int>(sz.inH),
+				    e.m_Mask.as<std::uint8_t>() + (e.m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(e.m_MaskH - 1) * -e.m_MaskStride : 0),
+				    e.m_MaskStride, static_cast<int>(e.m_MaskW), static_cast<int>(e.m_MaskH), L.m_Stream);
+			}
+			const std::uint16_t *frame16 = nullptr;
+			if (stage[i] & 4) {  // stageOutScaled's rules: the 8-bit frame, or for a deep format from the state member i's own state
+				if (po.yuv && e.deepFromState(po.format)) {
+					auto *scaled16 = e.m_GroupSlots.out16.as<std::uint16_t>();
+					e.m_OutScale.scaleState(stateOut, scaled16, L.m_Stream);
+					frame16 = scaled16;
+				} else {
+					e.m_OutScale.scaleBgrx(L.m_BatchIO[i].out, L.m_BatchIO[i].outStride, ends.out, ends.outStride, L.m_Stream);
+				}
+			}
+			// a non-BGRX output: member i's BGRX frame at its own output size (the lead's slot, or member i's scaled slot) into
+			// the caller's device planes / the staging slot.  A deep format is encoded from the f16 state THIS MEMBER's step
+			// just wrote -- its own m_State[set_i ^ 1] (a flow-free member: its one scratch state), never the lead's -- or from
+			// the blended or scaled 8-bit frame while member i has a mask or "hbd_from_state" 0 (deepFromState)
 			if (po.yuv) {
-				e.encodeYuv(po.format, po.colorspace, po.planes, fs.outputWidth, fs.outputHeight, L.m_BatchIO[i].out, L.m_BatchIO[i].outStride,
-				    e.m_State[recurrent ? sets[i] ^ 1 : 0].get(), nullptr, L.m_Stream);
+				e.encodeYuv(po.format, po.colorspace, po.planes, sz.outW, sz.outH, ends.out, ends.outStride, stateOut, frame16, L.m_Stream);
 			}
 			if (L.m_BatchHost[i].out.host) launchSignalHost(L.m_PassSignal.device(), L.m_Stream);
 		}
@@ -969,6 +1112,10 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		m[i]->m_Idx = sets[i] ^ 1;
 		++m[i]->m_GroupFrames;
 		m[i]->m_GroupYuvFrames += L.m_BatchHost[i].yuv() ? 1 : 0;
+		if (stage[i]) {  // (what the frame went through, whichever route it took: "source_stage_frames" counts it too)
+			++m[i]->m_GroupStagedFrames;
+			++m[i]->m_SourceFrames;
+		}
 		m[i]->maybeRestoreResident();
 	}
 }

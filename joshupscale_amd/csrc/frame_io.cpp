@@ -96,6 +96,10 @@ void Scaler::scaleBgrxItems(const ScaleItems &items, int count, hipStream_t stre
 	    static_cast<int>(m_DstH), m_XDev, m_YDev, m_Span, stream);
 }
 
+ScaleMember Scaler::member(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint8_t *dst, std::ptrdiff_t dstStride) const {
+	return scaleMember(src, srcStride, static_cast<int>(m_SrcW), dst, dstStride, m_XDev, m_YDev, m_Span);
+}
+
 void Scaler::scaleState(const void *state, std::uint16_t *dst, hipStream_t stream) const {
 	launchScaleState(state, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), dst, static_cast<int>(m_DstW),
 	    static_cast<int>(m_DstH), m_XDev, m_YDev, m_Span, stream);

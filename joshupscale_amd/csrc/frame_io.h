@@ -105,6 +105,8 @@ public:
 	// launchScaleBgrxItems: `count` frames of the scaler's sizes in one launch
 	void scaleBgrxItems(const ScaleItems &items, int count, hipStream_t stream) const;
 	void scaleState(const void *state, std::uint16_t *dst, hipStream_t stream) const;
+	// this scaler's row of a launchScaleBgrxMembers table: its own source width, tables, tile pitch and form
+	ScaleMember member(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint8_t *dst, std::ptrdiff_t dstStride) const;
 
 private:
 	DeviceBuffer m_X, m_Y;

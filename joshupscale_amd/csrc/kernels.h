@@ -603,6 +603,16 @@ static_assert(sizeof(YuvDecodeItems) <= 832, "the by-value argument of the items
 YuvDecodeItem yuvDecodeItem(int format, int colorspace, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride);
 // (a per-row item in the pass: strips x height threads per item, of which a 4:2:0 item's upper half returns at once)
 void launchYuv420ToBgrxItems(const YuvDecodeItems &items, int count, int width, int height, hipStream_t stream);
+// The sized form (the members of a group pass, Engine::runGroupPass: a scaled member's input is its source size, the
+// others' the model's): every item carries its own width and height.  The grid is sized for the largest item; the
+// workgroups beyond an item's own extent return at once.  Per item the bytes of launchDecodeFrame at that item's size.
+struct YuvDecodeSizedItems {
+	YuvDecodeItem item[kFlowBatchMax];
+	int width[kFlowBatchMax] = {};
+	int height[kFlowBatchMax] = {};
+};
+static_assert(sizeof(YuvDecodeSizedItems) <= 896, "the by-value argument of the sized items kernel must not grow");
+void launchYuvToBgrxItemsSized(const YuvDecodeSizedItems &items, int count, hipStream_t stream);
 
 // ---- source stage (source_kernels.hip; docs/source_stage.md): sources of any size, masked pass-through ---------------
 // One axis of the scaler, N source samples -> M destination samples, in integers (buildScaleAxis is the definition;
@@ -662,6 +672,33 @@ struct ScaleItems {
 static_assert(sizeof(ScaleItems) <= 256, "the by-value argument of the items kernel must not grow");
 void launchScaleBgrxItems(const ScaleItems &items, int count, int srcW, int srcH, int dstW, int dstH, const ScaleAxisDev &x,
     const ScaleAxisDev &y, int spanX, hipStream_t stream);
+// The sources of a group pass scaled in one launch (Engine::runGroupPass; docs/source_stage.md "Group passes"): the members
+// differ in source size, filter and tables, so each carries its own -- source rows and width, both axes' tables, the pitch
+// of its LDS tile and its kernel form -- and only the destination size, the model's input, is the launch's.  Per member
+// the bytes of launchScaleBgrx.  ScaleMembers is the launch's by-value argument.
+struct ScaleMember {
+	const std::uint8_t *src = nullptr;
+	std::ptrdiff_t srcStride = 0;
+	std::uint8_t *dst = nullptr;
+	std::ptrdiff_t dstStride = 0;
+	const int *xStart = nullptr, *yStart = nullptr;
+	const std::uint16_t *xTaps = nullptr, *yTaps = nullptr;
+	int srcW = 0;
+	int pitch = 0;   // words per row of the member's LDS tile: spanX + spanX / 32 + 1
+	int cubic = 0;   // the signed form of the tile (Catmull-Rom, Mitchell)
+	int reserved = 0;
+};
+struct ScaleMembers {
+	ScaleMember member[kFlowBatchMax];
+};
+static_assert(sizeof(ScaleMembers) <= 640, "the by-value argument of the members kernel must not grow");
+// one member's row of the table: std::invalid_argument for a NULL pointer, a width below 1, a span that is no multiple of
+// 4, axes of two filters, or a tile beyond the 64 KB of LDS
+ScaleMember scaleMember(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, std::uint8_t *dst, std::ptrdiff_t dstStride,
+    const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX);
+// bytes of dynamic LDS of a launch over members [0, count): the largest member's tile
+std::size_t scaleMembersLds(const ScaleMembers &members, int count);
+void launchScaleBgrxMembers(const ScaleMembers &members, int count, int dstW, int dstH, hipStream_t stream);
 // The output stage's 16-bit path (docs/output_stage.md): the dense f16 state [srcH][srcW][4] (16-byte aligned) -> the dense
 // u16 frame [dstH][dstW][4] (8-byte aligned; X = 0), out = (sum qy qx P + 2^23) >> 24 with P = floor((s + 0.5) * 65536)
 // saturated, summed exactly (64 bits), clamped to 0 .. 65535 where an axis' filter is cubic.  x / y / spanX as for

@@ -16,6 +16,8 @@
 //                       of-two ratio up to 16 on 32 different banks (and the vertical pass's four-column writes too).
 //   scale_bgrx_items_kernel  the same tile (scaleBgrxTile, the one body of both) over the sources of a look-ahead pass:
 //                       grid.z = item, each with its own pointers and strides from a by-value table.
+//   scale_bgrx_members_kernel  the same tile over the sources of a group pass: grid.z = member, each with its own source
+//                       size, tables, LDS pitch and form from a by-value table; one destination size for all.
 //   mask_blend_kernel   a thread per output pixel; mask and source are point sampled.
 //   scale_state_kernel  the output stage's 16-bit path (docs/output_stage.md): scale_bgrx_kernel's tile over the dense f16
 //                       state, each sample first P = floor((s + 0.5) * 65536) saturated (StateSource::sample of
@@ -27,6 +29,9 @@
 // under the same tile, padding and loads; the horizontal sum is 64 bits signed (2^34 / 2^42 in size), shifted with its
 // sign and clamped to 0 .. 255 / 65535.  The triangle's instantiations are, instruction for instruction, the kernels
 // from before the template (docs/source_stage.md "Filters").
+//
+// Resources (tools/kernel_resources.py): scale_bgrx_kernel and scale_bgrx_items_kernel hold 52 VGPRs in either form and no
+// scratch; scale_bgrx_members_kernel, which carries both forms behind a uniform branch, 52 VGPRs and no scratch too.
 //
 // Rows are addressed with their signed stride; pixels off 4-byte alignment move byte by byte.
 
@@ -378,6 +383,21 @@ __global__ __launch_bounds__(256) void scale_bgrx_items_kernel(ScaleItems items,
 	scaleBgrxTile<kSigned>(it.src, it.srcStride, srcW, it.dst, it.dstStride, dstW, dstH, ax, ay, pitch);
 }
 
+// The sources of a group pass in one launch (Engine::runGroupPass; docs/source_stage.md "Group passes"): grid (tiles x,
+// tiles y, member).  The destination is the model's input for every member, so the tile grid is common; everything else
+// is the member's own, read from the by-value table through blockIdx.z with scalar loads.  The form is a branch on the
+// member's flag, uniform over the workgroup; either side is scaleBgrxTile, so the bytes are those of scale_bgrx_kernel.
+// The launch's dynamic LDS is the largest member's tile; a member addresses its own rows by its own pitch.
+__global__ __launch_bounds__(256) void scale_bgrx_members_kernel(ScaleMembers members, int dstW, int dstH) {
+	const ScaleMember &m = members.member[blockIdx.z];
+	const ScaleTaps ax{m.xStart, m.xTaps}, ay{m.yStart, m.yTaps};
+	if (m.cubic) {
+		scaleBgrxTile<true>(m.src, m.srcStride, m.srcW, m.dst, m.dstStride, dstW, dstH, ax, ay, m.pitch);
+	} else {
+		scaleBgrxTile<false>(m.src, m.srcStride, m.srcW, m.dst, m.dstStride, dstW, dstH, ax, ay, m.pitch);
+	}
+}
+
 // P of one f16 of the state, as StateSource::sample (colour_kernels.hip) forms it: exact in f32
 __device__ inline unsigned stateSample(unsigned bits) {
 	const float s = static_cast<float>(__builtin_bit_cast(f16, static_cast<unsigned short>(bits)));
@@ -525,6 +545,58 @@ void launchScaleBgrxItems(const ScaleItems &items, int count, int srcW, int srcH
 	const auto kernel = x.filter != kScaleTriangle ? scale_bgrx_items_kernel<true> : scale_bgrx_items_kernel<false>;
 	hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, items, srcW, dstW, dstH, tx, ty, pitch);
 	hipCheckLaunch("scale_bgrx_items");
+}
+
+ScaleMember scaleMember(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, std::uint8_t *dst, std::ptrdiff_t dstStride,
+    const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX) {
+	if (src == nullptr || dst == nullptr || srcW < 1 || spanX < 4 || spanX % 4 || x.start == nullptr || x.taps == nullptr ||
+	    y.start == nullptr || y.taps == nullptr) {
+		throw std::invalid_argument("scaleMember: bad arguments");
+	}
+	if (x.filter != y.filter) throw std::invalid_argument("scaleMember: the two axes' tables must be of one filter");
+	ScaleMember m;
+	m.src = src;
+	m.srcStride = srcStride;
+	m.dst = dst;
+	m.dstStride = dstStride;
+	m.xStart = x.start;
+	m.xTaps = x.taps;
+	m.yStart = y.start;
+	m.yTaps = y.taps;
+	m.srcW = srcW;
+	m.pitch = spanX + spanX / 32 + 1;
+	m.cubic = x.filter != kScaleTriangle ? 1 : 0;
+	ScaleMembers one{};
+	one.member[0] = m;
+	if (scaleMembersLds(one, 1) > 64 * 1024) throw std::invalid_argument("scaleMember: the tile does not fit the LDS");
+	return m;
+}
+
+std::size_t scaleMembersLds(const ScaleMembers &members, int count) {
+	if (count < 1 || count > kFlowBatchMax) throw std::invalid_argument("launchScaleBgrxMembers: 1 .. 8 members");
+	std::size_t most = 0;
+	for (int i = 0; i < count; ++i) {
+		if (members.member[i].pitch < 1) throw std::invalid_argument("launchScaleBgrxMembers: bad arguments");
+		most = std::max(most, static_cast<std::size_t>(3) * kScaleTileH * static_cast<std::size_t>(members.member[i].pitch) * sizeof(unsigned));
+	}
+	return most;
+}
+
+void launchScaleBgrxMembers(const ScaleMembers &members, int count, int dstW, int dstH, hipStream_t stream) {
+	const std::size_t lds = scaleMembersLds(members, count);  // (the largest member's tile; refuses a count outside 1 .. 8)
+	if (dstW < 1 || dstH < 1) throw std::invalid_argument("launchScaleBgrxMembers: bad arguments");
+	for (int i = 0; i < count; ++i) {
+		const ScaleMember &m = members.member[i];
+		if (m.src == nullptr || m.dst == nullptr || m.srcW < 1 || m.xStart == nullptr || m.xTaps == nullptr || m.yStart == nullptr ||
+		    m.yTaps == nullptr) {
+			throw std::invalid_argument("launchScaleBgrxMembers: bad arguments");
+		}
+	}
+	if (lds > 64 * 1024) throw std::invalid_argument("launchScaleBgrxMembers: the tile does not fit the LDS");
+	const dim3 grid(static_cast<unsigned>((dstW + kScaleTileW - 1) / kScaleTileW),
+	    static_cast<unsigned>((dstH + kScaleTileH - 1) / kScaleTileH), static_cast<unsigned>(count));
+	hipLaunchKernelGGL(scale_bgrx_members_kernel, grid, dim3(256), lds, stream, members, dstW, dstH);
+	hipCheckLaunch("scale_bgrx_members");
 }
 
 void launchScaleState(const void *state, int srcW, int srcH, std::uint16_t *dst, int dstW, int dstH, const ScaleAxisDev &x,

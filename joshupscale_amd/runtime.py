@@ -215,6 +215,7 @@ _PRODUCT_SIGS = {
     "ju_set_scene_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_set_scene_group": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_set_stage_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
+    "ju_set_stage_group": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_set_source_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_get_source_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
@@ -252,6 +253,8 @@ _HOOK_SIGS = {
                                     _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_yuv_items": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), C.c_size_t, C.c_size_t, _P(C.c_void_p),
                                      _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
+    "ju_debug_yuv_items_sized": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_size_t), _P(C.c_size_t), _P(C.c_void_p),
+                                           _P(C.c_ssize_t), _P(C.c_void_p), _P(C.c_ssize_t)]),
     "ju_debug_source": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
     "ju_debug_output": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
@@ -270,6 +273,8 @@ _HOOK_SIGS = {
                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ju_debug_scale_items": (C.c_int, [C.c_int, C.c_int, _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
                                        _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t]),
+    "ju_debug_scale_members": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
+                                         _P(C.c_void_p), _P(C.c_ssize_t), _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_debug_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                     C.c_float, C.c_float, C.c_float, C.c_int, C.c_uint, C.c_void_p, C.c_size_t]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
@@ -472,6 +477,13 @@ class Runtime:
         :class:`JoshUpscaleError` with the C layer's message."""
         _check(self._lib, self._lib.ju_set_stage_lookahead(self._h, int(on)))
 
+    def set_stage_group(self, on) -> None:
+        """``ju_set_stage_group``: 1 = this runtime rides in the passes of ``process_group`` / ``process_group_frames``
+        while a source size, a mask or an output size is set, and the pass carries its stages (docs/source_stage.md and
+        docs/output_stage.md, "Group passes"); 0 (the default) = such a member runs on its own.  Independent of
+        ``set_stage_lookahead``.  A value other than 0 or 1 raises :class:`JoshUpscaleError` with the C layer's message."""
+        _check(self._lib, self._lib.ju_set_stage_group(self._h, int(on)))
+
     # -- the source stage (docs/source_stage.md) ----------------------------------
     def set_source_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
         """``ju_set_source_size``: input frames are ``width x height`` from now on and are scaled to the model's input on
@@ -656,7 +668,7 @@ class Runtime:
         "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames",
         "output_scaled", "source_filter", "output_filter", "scene_mode", "scene_frames", "scene_cuts", "scene_lookahead",
         "scene_pass_frames", "stage_lookahead", "lookahead_staged_frames", "group_frames", "group_yuv_frames",
-        "scene_group", "scene_group_frames"."""
+        "scene_group", "scene_group_frames", "stage_group", "group_staged_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value

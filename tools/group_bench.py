@@ -16,6 +16,11 @@ so (b) and (c) replay their graphs; group passes launch eagerly.
 --format nv12 hands over device NV12 frames on both sides and times
   group: ju_process_group_frames, serial: ju_process_frame per runtime.
 Both may be combined; neither runs the threads method.
+--source WxH / --output WxH / --mask put every stream under ju_set_source_size / ju_set_output_size / ju_set_source_mask
+(frames are then handed over at those sizes through ju_process_group_frames, in --format's format) and time
+  group: ju_set_stage_group(rt, 1) (the members ride, the pass carries their stages),
+  group_off: the same call with the setting at 0 (every member on its own, on the staged single-frame route),
+  serial: ju_process_frame per runtime.
 
 --trace group|single runs one method alone for a `rocprofv3 --kernel-trace --stats` run: N = 8 group calls, or the
 same number of frames through ju_process on one runtime.  --summarize <kernel_stats.csv> <frames> prints the flow
@@ -54,7 +59,7 @@ def summarize(path, frames):
 
 
 class Streams:
-    def __init__(self, n, preset, dtype, inputs_per_stream=4, scene="off", fmt="bgrx"):
+    def __init__(self, n, preset, dtype, inputs_per_stream=4, scene="off", fmt="bgrx", source=None, output=None, mask=False):
         import torch
         from joshupscale_amd import model_file as M
         from joshupscale_amd import runtime as R
@@ -80,25 +85,52 @@ class Streams:
         self.lib = self.rts[0]._lib
         self.group_args = {}
         self.scene, self.fmt = scene, fmt
+        self.staged = bool(source or output or mask)
+        self.frames_api = fmt == "nv12" or self.staged
+        sw, sh = source or (w, h)                                  # what the frames measure on either side
+        ow, oh = output or (4 * w, 4 * h)
+        if self.staged:
+            import numpy as np
+            for rt in self.rts:
+                if source:
+                    rt.set_source_size(sw, sh)
+                if mask:                                           # a HUD strip along the bottom and a corner box stay the source
+                    m = np.full((90, 160, 4), 255, np.uint8)
+                    m[78:, :, :3] = 0
+                    m[4:20, 4:44, :3] = 0
+                    rt.set_source_mask(m)
+                if output:
+                    rt.set_output_size(ow, oh)
         if scene != "off":
             for rt in self.rts:
                 rt.set_scene_detect({"report": R.SCENE_REPORT, "reset": R.SCENE_RESET}[scene], 22000)
         if fmt == "nv12":
             # device NV12 on both sides: any bytes are a frame (noise, as the BGRX clip is)
             gen = torch.Generator(device="cpu").manual_seed(1234)
-            self.d_y = torch.randint(16, 236, (n, self.k, h, w), dtype=torch.uint8, generator=gen).to(dev)
-            self.d_uv = torch.randint(16, 241, (n, self.k, h // 2, w), dtype=torch.uint8, generator=gen).to(dev)
-            self.d_oy = torch.zeros((n, 4 * h, 4 * w), dtype=torch.uint8, device=dev)
-            self.d_ouv = torch.zeros((n, 2 * h, 4 * w), dtype=torch.uint8, device=dev)
+            self.d_y = torch.randint(16, 236, (n, self.k, sh, sw), dtype=torch.uint8, generator=gen).to(dev)
+            self.d_uv = torch.randint(16, 241, (n, self.k, sh // 2, sw), dtype=torch.uint8, generator=gen).to(dev)
+            self.d_oy = torch.zeros((n, oh, ow), dtype=torch.uint8, device=dev)
+            self.d_ouv = torch.zeros((n, oh // 2, ow), dtype=torch.uint8, device=dev)
             torch.cuda.synchronize()
-            self.fins = [[R.device_frame(R.FMT_NV12, w, h, [self.d_y[i][t], self.d_uv[i][t]]) for t in range(self.k)]
+            self.fins = [[R.device_frame(R.FMT_NV12, sw, sh, [self.d_y[i][t], self.d_uv[i][t]]) for t in range(self.k)]
                          for i in range(n)]
-            self.fouts = [R.device_frame(R.FMT_NV12, 4 * w, 4 * h, [self.d_oy[i], self.d_ouv[i]]) for i in range(n)]
+            self.fouts = [R.device_frame(R.FMT_NV12, ow, oh, [self.d_oy[i], self.d_ouv[i]]) for i in range(n)]
+        elif self.staged:
+            # device BGRX at the sizes set, through the frames entry points
+            gen = torch.Generator(device="cpu").manual_seed(1234)
+            self.d_src = torch.randint(0, 256, (n, self.k, sh, sw, 4), dtype=torch.uint8, generator=gen).to(dev)
+            self.d_dst = torch.zeros((n, oh, ow, 4), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            self.fins = [[R.device_frame(R.FMT_BGRX, sw, sh, [self.d_src[i][t]]) for t in range(self.k)] for i in range(n)]
+            self.fouts = [R.device_frame(R.FMT_BGRX, ow, oh, [self.d_dst[i]]) for i in range(n)]
 
     def set_scene_group(self, on):
-        if self.scene != "off":
-            for rt in self.rts:
+        """The settings that decide whether the members ride: ju_set_scene_group and, under a stage, ju_set_stage_group."""
+        for rt in self.rts:
+            if self.scene != "off":
                 rt.set_scene_group(on)
+            if self.staged:
+                rt.set_stage_group(on)
 
     def check(self, rc):
         if rc != 0:
@@ -107,7 +139,7 @@ class Streams:
     def group(self, n, ticks, start=0):
         R = self.R
         key = n
-        nv12 = self.fmt == "nv12"
+        nv12 = self.frames_api
         if key not in self.group_args:
             hs = (C.c_void_p * n)(*[rt._h.value for rt in self.rts[:n]])
             if nv12:
@@ -126,7 +158,7 @@ class Streams:
     group_off = group  # (the same call; timed() leaves ju_set_scene_group at 0 for it)
 
     def serial(self, n, ticks, start=0):
-        nv12 = self.fmt == "nv12"
+        nv12 = self.frames_api
         call = self.lib.ju_process_frame if nv12 else self.lib.ju_process
         ins, outs = (self.fins, self.fouts) if nv12 else (self.ins, self.outs)
         refs = [[(self.rts[i]._h, C.byref(ins[i][t]), C.byref(outs[i])) for t in range(self.k)] for i in range(n)]
@@ -185,15 +217,21 @@ def main():
     ap.add_argument("--ticks", type=int, default=64, help="--trace: timed ticks after a warm-up of as many")
     ap.add_argument("--scene", choices=["off", "report", "reset"], default="off")
     ap.add_argument("--format", choices=["bgrx", "nv12"], default="bgrx")
+    ap.add_argument("--source", default=None, metavar="WxH", help="ju_set_source_size on every stream")
+    ap.add_argument("--output", default=None, metavar="WxH", help="ju_set_output_size on every stream")
+    ap.add_argument("--mask", action="store_true", help="ju_set_source_mask on every stream")
     ap.add_argument("--summarize", nargs=2, metavar=("CSV", "FRAMES"), default=None)
     args = ap.parse_args()
     if args.summarize:
         summarize(args.summarize[0], int(args.summarize[1]))
         return
+    size = lambda text: tuple(int(v) for v in text.lower().split("x")) if text else None  # noqa: E731
+    stage = dict(source=size(args.source), output=size(args.output), mask=args.mask)
+    staged = bool(args.source or args.output or args.mask)
     import torch
     torch.zeros(1, device="cuda:0")  # (torch's HIP runtime first, as bench.py does)
     if args.trace:
-        s = Streams(8 if args.trace == "group" else 1, args.preset, args.dtype, scene=args.scene, fmt=args.format)
+        s = Streams(8 if args.trace == "group" else 1, args.preset, args.dtype, scene=args.scene, fmt=args.format, **stage)
         s.set_scene_group(1)
         if args.trace == "group":
             s.group(8, args.ticks)
@@ -204,12 +242,13 @@ def main():
             s.serial(1, 8 * args.ticks)
             frames = 8 * args.ticks
         print(json.dumps({"trace": args.trace, "frames_per_half": frames,
-                          "group_frames": s.rts[0].stat("group_frames")}))
+                          "group_frames": s.rts[0].stat("group_frames"),
+                          "group_staged_frames": s.rts[0].stat("group_staged_frames")}))
         s.close()
         return
-    s = Streams(max(args.sizes), args.preset, args.dtype, scene=args.scene, fmt=args.format)
+    s = Streams(max(args.sizes), args.preset, args.dtype, scene=args.scene, fmt=args.format, **stage)
     methods = ("group", "serial", "threads")
-    if args.scene != "off":
+    if args.scene != "off" or staged:
         methods = ("group", "group_off", "serial")
     elif args.format != "bgrx":
         methods = ("group", "serial")
@@ -235,15 +274,18 @@ def main():
             row["group_over_group_off"] = round(row["group"]["median"] / row["group_off"]["median"], 3)
         res[str(n)] = row
     group_frames = [rt.stat("group_frames") for rt in s.rts]
-    extra = {"scene": args.scene, "format": args.format,
+    extra = {"scene": args.scene, "format": args.format, "source": args.source, "output": args.output, "mask": args.mask,
+             "group_staged_frames": [rt.stat("group_staged_frames") for rt in s.rts],
              "scene_group_frames": [rt.stat("scene_group_frames") for rt in s.rts],
              "group_yuv_frames": [rt.stat("group_yuv_frames") for rt in s.rts],
              "scene_cuts": [rt.stat("scene_cuts") for rt in s.rts]}
     s.close()
     print(json.dumps({"metric": "aggregate frames/s of N streams on one GPU", "preset": args.preset, "dtype": args.dtype,
                       "frames_per_round": args.frames, "rounds": args.rounds,
-                      "methods": {"group": "ju_process_group (ju_process_group_frames for --format nv12; ju_set_scene_group 1)",
-                                  "group_off": "the same call with ju_set_scene_group 0: detecting members on their own",
+                      "methods": {"group": "ju_process_group (ju_process_group_frames for --format nv12 or under a stage; "
+                                           "ju_set_scene_group / ju_set_stage_group 1)",
+                                  "group_off": "the same call with ju_set_scene_group / ju_set_stage_group 0: detecting or "
+                                               "staged members on their own",
                                   "serial": "ju_process (ju_process_frame) per runtime, one thread",
                                   "threads": "one thread per runtime, ju_process"},
                       "fps": res, "group_frames": group_frames, **extra}))
