@@ -9,8 +9,8 @@ OBJ        := build/obj
 CXXFLAGS   := -O3 -std=c++17 -fPIC -fvisibility=hidden -Iinclude -I$(CSRC) -Wall -Wextra \
               -Wno-unused-parameter
 HIPFLAGS   := --offload-arch=$(ARCH) $(CXXFLAGS)
-SRCS_CPP   := model.cpp engine.cpp engine_frames.cpp engine_passes.cpp frame_io.cpp c_api.cpp core_api.cpp log.cpp comm.cpp graphics.cpp dev_switch.cpp
-SRCS_HIP   := conv_kernels.hip tower_kernels.hip frame_kernels.hip fp8_kernels.hip flow_kernels.hip res_block_kernels.hip splitk_kernels.hip tower8_kernels.hip colour_kernels.hip source_kernels.hip scene_kernels.hip
+SRCS_CPP   := model.cpp engine.cpp engine_frames.cpp engine_passes.cpp frame_io.cpp c_api.cpp core_api.cpp log.cpp comm.cpp graphics.cpp dev_switch.cpp tiled.cpp
+SRCS_HIP   := conv_kernels.hip tower_kernels.hip frame_kernels.hip fp8_kernels.hip flow_kernels.hip res_block_kernels.hip splitk_kernels.hip tower8_kernels.hip colour_kernels.hip source_kernels.hip scene_kernels.hip tile_kernels.hip
 OBJS       := $(addprefix $(OBJ)/,$(SRCS_CPP:.cpp=.o)) $(addprefix $(OBJ)/,$(SRCS_HIP:.hip=.o))
 
 # Two libraries from the same objects: the product (exactly the C ABI of include/joshupscale_amd.h + the C++ plugin
@@ -26,7 +26,7 @@ all: $(OUT)/libJoshUpscale.so $(OUT)/libJoshUpscale_test.so
 # consume every accumulator with VALU ops; in AGPR form each value first costs a
 # v_accvgpr_read (128 per layer and lane in the tower kernel, ~2 % of its time).
 KERNELFLAGS := -mllvm -amdgpu-mfma-vgpr-form
-$(OBJ)/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/kernel_common.h $(CSRC)/flow_block_common.h Makefile
+$(OBJ)/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/kernel_common.h $(CSRC)/flow_block_common.h $(CSRC)/tile_geometry.h Makefile
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) -c $< -o $@
 

@@ -606,6 +606,60 @@ JU_API int ju_get_scene_info(ju_runtime *runtime, ju_scene_info *out, int count,
 JU_API int ju_set_scene_lookahead(ju_runtime *runtime, int on);
 JU_API int ju_set_scene_group(ju_runtime *runtime, int on); /* default 0 */
 
+/* ---- tiled upscaling: sources larger than the model (no reference counterpart: the reference upscales exactly the
+ * model's size -- its AviSynth caller "must be in RGB32 format, 480x270") ------------------------------------------------
+ * A ju_tiled upscales frames of src_width x src_height to four times that size with a model of W x H: the source is cut
+ * into W x H tiles that overlap by at least `overlap` source pixels, every tile is an independent recurrent stream with a
+ * runtime of its own, and the tiles' 4W x 4H outputs are blended into the frame across their seams -- cut and blend are
+ * one GPU launch each, the tiles advance together as ju_process_group passes (the flow nets of up to 8 tiles in one
+ * pass of their launches; more tiles split evenly into several passes).  docs/tiled.md holds the definition:
+ *   per axis (S source length, t tile length, ov overlap): n = 1 tiles if S == t, else ceil((S - ov) / (t - ov)), at
+ *   x_i = floor(i (S - t) / (n - 1)); between tiles i and i + 1 a linear ramp of 4 ov output pixels centred in their
+ *   overlap, tile i alone in front of it and tile i + 1 alone behind it (ov = 0: a hard cut);
+ *   out = (sum wy wx v + 32768) >> 16 per byte of B, G, R over the up to four tiles the two axes name, X = 0.
+ * A pixel under one tile is that tile's byte; a source of exactly W x H is ONE tile, and its frames are ju_process's
+ * byte for byte.  In general every frame equals, byte for byte, the blend of what ju_process gives n runtimes fed the
+ * tiles (tests/tiled_reference.py).
+ * Limits (JU_ERR_INVALID_ARGUMENT): 0 <= overlap <= min(W, H) / 4; W <= src_width <= 8 W and H <= src_height <= 8 H; at
+ * most 64 tiles.  Memory: every tile holds a whole runtime (weights and activations, about what ju_create takes) plus
+ * 68 W H bytes of tile frames; host frames and frames that are not BGRX add one staging frame per side. */
+typedef struct ju_tiled ju_tiled;
+typedef struct ju_tiled_info {
+	size_t src_width, src_height, out_width, out_height, tile_width, tile_height;
+	int tiles_x, tiles_y, overlap;
+} ju_tiled_info;
+/* The arguments of ju_create_from_memory (dtype: JU_DTYPE_*), then the source size and the overlap.  The model bytes are
+ * checked first, then the limits above -- both before any runtime is created.  *out_tiled is NULL on failure. */
+JU_API int ju_tiled_create_from_memory(int device_id, const void *model_bytes, size_t model_size, int dtype,
+    size_t src_width, size_t src_height, int overlap, ju_tiled **out_tiled);
+/* ju_tiled_create_from_memory on the bytes of a model file, with the container's dtype (JU_ERR_IO: the file). */
+JU_API int ju_tiled_create(int device_id, const char *model_path, size_t src_width, size_t src_height, int overlap,
+    ju_tiled **out_tiled);
+JU_API void ju_tiled_destroy(ju_tiled *tiled); /* NULL: nothing */
+/* Zeroes every tile's recurrent state: the next frame is the first of a fresh object. */
+JU_API int ju_tiled_reset(ju_tiled *tiled);
+/* One frame, synchronously: `input` a BGRX image of src_width x src_height, `output` one of four times that; each
+ * JU_LOC_CPU or JU_LOC_DEVICE with a stride of any sign.  A JU_LOC_DEVICE image at a 4-byte-aligned address and stride
+ * is read / written where it is; any other goes through a staging frame.
+ * JU_ERR_INVALID_ARGUMENT, before anything is launched and with every tile's state unchanged: a NULL pointer, an image
+ * that is not exactly that size, |stride| smaller than a row, an unknown location, a graphics resource, an output that
+ * overlaps the input (same address space). */
+JU_API int ju_tiled_process(ju_tiled *tiled, const ju_image *input, const ju_image *output);
+/* ju_tiled_process on frames of any JU_FMT_* format, host or device: the input is decoded at source size by the
+ * conversion ju_process_frame uses, the blended 8-bit frame is encoded at output size -- also a deep format (P010,
+ * BGRX64, ...), which ju_process_frame would take from the f16 state: a tiled frame has no single state.  Refused as
+ * above, and whatever ju_process_frame refuses for a frame of that size (an odd size for a subsampled format, an unknown
+ * format or colour space, a NULL or misaligned plane, |stride| smaller than a row). */
+JU_API int ju_tiled_process_frame(ju_tiled *tiled, const ju_frame *input, const ju_frame *output);
+JU_API int ju_tiled_get_info(const ju_tiled *tiled, ju_tiled_info *info);
+/* The origin of tile `index` (0 .. tiles_x tiles_y - 1, row-major over the tile grid) in source pixels. */
+JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t *y);
+/* "tiles"; "frames": frames processed; "group_frames": the tiles' frames that ran inside group passes, summed over the
+ * tiles (tiles x frames while every pass holds at least two tiles).  An unknown key is JU_ERR_INVALID_ARGUMENT. */
+JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value);
+/* Not provided for a tiled object: look-ahead passes, ju_set_source_size / ju_set_output_size / the mask / the scene
+ * detector, graphics resources, graph capture, the C++ plugin surface. */
+
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing
  * call on the same thread. */

@@ -245,6 +245,22 @@ JU_API int ju_debug_temporal(void *state, const void *pre_warp, void *out, ptrdi
     size_t width, size_t height, float strength, float threshold, float gain, int window, unsigned flags,
     uint64_t *acc, size_t acc_capacity);
 
+/* The two kernels of tiled upscaling alone (tile_split_kernel, tile_stitch_kernel; docs/tiled.md; the definitions:
+ * tests/tiled_reference.py split / stitch), each ONE synchronous launch on caller-supplied device buffers, on the current
+ * device, for a source of src_width x src_height tiled by tile_width x tile_height at `overlap` -- the layout ju_tiled
+ * builds, held to its limits.  `tiles`: `count` dense images, 16-byte aligned, row-major over the tile grid; count must be
+ * the layout's tile count.
+ * ju_debug_tile_split reads BGRX rows of the source at `src` (address and signed stride multiples of 4) and writes every
+ * tile's tile_width x tile_height input, X = 0.
+ * ju_debug_tile_stitch reads every tile's 4 tile_width x 4 tile_height output and writes BGRX rows of 4 src_width x
+ * 4 src_height at `dst` (address and signed stride multiples of 4; any 16-byte phase), X = 0, and nothing around them.
+ * A NULL buffer, a misaligned pointer or stride, |stride| smaller than a row, sizes or an overlap outside the limits or
+ * a wrong count is JU_ERR_INVALID_ARGUMENT before any device call. */
+JU_API int ju_debug_tile_split(const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height, size_t tile_width,
+    size_t tile_height, int overlap, void *const *tiles, int count);
+JU_API int ju_debug_tile_stitch(void *dst, ptrdiff_t dst_stride, size_t src_width, size_t src_height, size_t tile_width,
+    size_t tile_height, int overlap, void *const *tiles, int count);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -21,9 +21,14 @@
 #include "graphics.h"
 #include "log.h"
 #include "model.h"
+#include "tiled.h"
 
 struct ju_runtime {
 	std::unique_ptr<ju::Engine> engine;
+};
+
+struct ju_tiled {
+	std::unique_ptr<ju::TiledRuntime> tiled;
 };
 
 namespace {
@@ -111,6 +116,23 @@ ju::Engine &engineOf(ju_runtime *rt) {
 	return *rt->engine;
 }
 
+ju::TiledRuntime &tiledOf(ju_tiled *t) {
+	if (t == nullptr || !t->tiled) throw std::invalid_argument("tiled runtime is NULL");
+	return *t->tiled;
+}
+
+// whole-file read with failbit/badbit exceptions, as core/src/core.cc:156-167
+std::vector<char> readModelFile(const char *path) {
+	std::ifstream f(path, std::ifstream::in | std::ifstream::binary | std::ifstream::ate);
+	if (!f) throw std::ios_base::failure(std::string("cannot open model file ") + path);
+	f.exceptions(std::ifstream::badbit | std::ifstream::failbit);
+	const auto size = static_cast<std::size_t>(f.tellg());
+	std::vector<char> bytes(size);
+	f.seekg(0);
+	f.read(bytes.data(), static_cast<std::streamsize>(size));
+	return bytes;
+}
+
 int createFromBytes(int device, const void *bytes, std::size_t size, int dtype, ju_runtime **out) {
 	return guarded([&] {
 		if (out == nullptr) throw std::invalid_argument("out_runtime is NULL");
@@ -136,14 +158,7 @@ int ju_create(int device_id, const char *model_path, ju_runtime **out_runtime) {
 	std::vector<char> bytes;
 	int rc = guarded([&] {
 		if (model_path == nullptr) throw std::invalid_argument("model_path is NULL");
-		// whole-file read with failbit/badbit exceptions, as core/src/core.cc:156-167
-		std::ifstream f(model_path, std::ifstream::in | std::ifstream::binary | std::ifstream::ate);
-		if (!f) throw std::ios_base::failure(std::string("cannot open model file ") + model_path);
-		f.exceptions(std::ifstream::badbit | std::ifstream::failbit);
-		const auto size = static_cast<std::size_t>(f.tellg());
-		bytes.resize(size);
-		f.seekg(0);
-		f.read(bytes.data(), static_cast<std::streamsize>(size));
+		bytes = readModelFile(model_path);
 	});
 	if (rc != JU_OK) return rc;
 	return createFromBytes(device_id, bytes.data(), bytes.size(), JU_DTYPE_DEFAULT, out_runtime);
@@ -362,6 +377,145 @@ int ju_set_stage_group(ju_runtime *runtime, int on) {
 int ju_reset(ju_runtime *runtime) {
 	return guarded([&] { engineOf(runtime).reset(); });
 }
+
+// ---- tiled upscaling (tiled.h; docs/tiled.md) ----
+int ju_tiled_create_from_memory(int device_id, const void *model_bytes, size_t model_size, int dtype, size_t src_width,
+    size_t src_height, int overlap, ju_tiled **out_tiled) {
+	return guarded([&] {
+		if (out_tiled == nullptr) throw std::invalid_argument("ju_tiled_create: out_tiled is NULL");
+		*out_tiled = nullptr;
+		if (model_bytes == nullptr) throw std::invalid_argument("ju_tiled_create: model_bytes is NULL");
+		int count = 0;
+		JU_HIP(hipGetDeviceCount(&count));
+		if (device_id < 0 || device_id >= count) {
+			throw std::invalid_argument("device " + std::to_string(device_id) + " does not exist (" + std::to_string(count) +
+			                            " HIP devices visible)");
+		}
+		ju::DeviceGuard guard(device_id);
+		auto t = std::make_unique<ju_tiled>();
+		t->tiled = std::make_unique<ju::TiledRuntime>(device_id, model_bytes, model_size, dtype, src_width, src_height, overlap);
+		*out_tiled = t.release();
+	});
+}
+
+int ju_tiled_create(int device_id, const char *model_path, size_t src_width, size_t src_height, int overlap, ju_tiled **out_tiled) {
+	std::vector<char> bytes;
+	const int rc = guarded([&] {
+		if (out_tiled == nullptr) throw std::invalid_argument("ju_tiled_create: out_tiled is NULL");
+		*out_tiled = nullptr;
+		if (model_path == nullptr) throw std::invalid_argument("ju_tiled_create: model_path is NULL");
+		bytes = readModelFile(model_path);
+	});
+	if (rc != JU_OK) return rc;
+	return ju_tiled_create_from_memory(device_id, bytes.data(), bytes.size(), JU_DTYPE_DEFAULT, src_width, src_height, overlap,
+	    out_tiled);
+}
+
+void ju_tiled_destroy(ju_tiled *tiled) {
+	delete tiled;
+}
+
+int ju_tiled_reset(ju_tiled *tiled) {
+	return guarded([&] { tiledOf(tiled).reset(); });
+}
+
+int ju_tiled_process(ju_tiled *tiled, const ju_image *input, const ju_image *output) {
+	return guarded([&] {
+		ju::TiledRuntime &t = tiledOf(tiled);
+		if (input == nullptr || output == nullptr) throw std::invalid_argument("ju_tiled_process: image is NULL");
+		t.process(ju::anyOf(toFrame(input)), ju::anyOf(toFrame(output)), "ju_tiled_process");
+	});
+}
+
+int ju_tiled_process_frame(ju_tiled *tiled, const ju_frame *input, const ju_frame *output) {
+	return guarded([&] {
+		ju::TiledRuntime &t = tiledOf(tiled);
+		if (input == nullptr || output == nullptr) throw std::invalid_argument("ju_tiled_process_frame: frame is NULL");
+		t.process(toAnyFrame(input), toAnyFrame(output), "ju_tiled_process_frame");
+	});
+}
+
+int ju_tiled_get_info(const ju_tiled *tiled, ju_tiled_info *info) {
+	return guarded([&] {
+		const ju::TiledRuntime &t = tiledOf(const_cast<ju_tiled *>(tiled));
+		if (info == nullptr) throw std::invalid_argument("ju_tiled_get_info: info is NULL");
+		*info = ju_tiled_info{t.srcWidth(), t.srcHeight(), 4 * t.srcWidth(), 4 * t.srcHeight(), t.tileWidth(), t.tileHeight(),
+		    t.tilesX(), t.tilesY(), t.overlap()};
+	});
+}
+
+int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t *y) {
+	return guarded([&] { tiledOf(const_cast<ju_tiled *>(tiled)).tile(index, x, y); });
+}
+
+int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value) {
+	return guarded([&] {
+		if (key == nullptr || value == nullptr) throw std::invalid_argument("ju_tiled_get_stat: null argument");
+		*value = tiledOf(const_cast<ju_tiled *>(tiled)).stat(key);
+	});
+}
+
+#ifdef JU_TEST_HOOKS
+namespace {
+// what both tile hooks check before a launch: the layout's limits, the tile count, the frame's rows; then the TileSet
+void debugTileSet(const char *who, size_t src_width, size_t src_height, size_t tile_width, size_t tile_height, int overlap,
+    void *const *tiles, int count, const void *frame, ptrdiff_t stride, size_t row_pixels, ju::TileSet *out, int *nx, int *ny) {
+	const std::string name = who;
+	constexpr size_t kMost = 1u << 13;
+	if (tile_width < 1 || tile_height < 1 || tile_width > kMost || tile_height > kMost) {
+		throw std::invalid_argument(name + ": a tile size outside 1 .. 8192");
+	}
+	const std::string problem = ju::tileLayoutProblem(src_width, src_height, tile_width, tile_height, overlap);
+	if (!problem.empty()) throw std::invalid_argument(name + ": " + problem);
+	const ju::TileAxis x = ju::tileAxis(static_cast<long>(src_width), static_cast<long>(tile_width), overlap);
+	const ju::TileAxis y = ju::tileAxis(static_cast<long>(src_height), static_cast<long>(tile_height), overlap);
+	if (tiles == nullptr || frame == nullptr) throw std::invalid_argument(name + ": null buffer");
+	if (count != x.tiles() * y.tiles()) {
+		throw std::invalid_argument(name + ": the layout has " + std::to_string(x.tiles() * y.tiles()) + " tiles, not " + std::to_string(count));
+	}
+	const auto row = static_cast<ptrdiff_t>(4 * row_pixels);
+	if (stride > -row && stride < row) throw std::invalid_argument(name + ": |stride| smaller than a row");
+	for (int k = 0; k < count; ++k) {
+		out->ptr[k] = static_cast<std::uint8_t *>(tiles[k]);
+		out->x[k] = x.origin[static_cast<size_t>(k % x.tiles())];
+		out->y[k] = y.origin[static_cast<size_t>(k / x.tiles())];
+	}
+	*nx = x.tiles();
+	*ny = y.tiles();
+}
+}  // namespace
+
+int ju_debug_tile_split(const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height, size_t tile_width,
+    size_t tile_height, int overlap, void *const *tiles, int count) {
+	return guarded([&] {
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		debugTileSet("ju_debug_tile_split", src_width, src_height, tile_width, tile_height, overlap, tiles, count, src, src_stride,
+		    src_width, &set, &nx, &ny);
+		ju::launchTileSplit(static_cast<const std::uint8_t *>(src), src_stride, set, count, static_cast<int>(tile_width),
+		    static_cast<int>(tile_height), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_tile_stitch(void *dst, ptrdiff_t dst_stride, size_t src_width, size_t src_height, size_t tile_width,
+    size_t tile_height, int overlap, void *const *tiles, int count) {
+	return guarded([&] {
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		debugTileSet("ju_debug_tile_stitch", src_width, src_height, tile_width, tile_height, overlap, tiles, count, dst, dst_stride,
+		    4 * src_width, &set, &nx, &ny);
+		const ju::TileAxis x = ju::tileAxis(static_cast<long>(src_width), static_cast<long>(tile_width), overlap);
+		const ju::TileAxis y = ju::tileAxis(static_cast<long>(src_height), static_cast<long>(tile_height), overlap);
+		ju::DeviceBuffer xTable(x.table.size() * sizeof(ju::TileAxisEntry)), yTable(y.table.size() * sizeof(ju::TileAxisEntry));
+		xTable.upload(x.table.data(), x.table.size() * sizeof(ju::TileAxisEntry));
+		yTable.upload(y.table.data(), y.table.size() * sizeof(ju::TileAxisEntry));
+		ju::launchTileStitch(static_cast<std::uint8_t *>(dst), dst_stride, static_cast<int>(4 * src_width), static_cast<int>(4 * src_height),
+		    set, nx, ny, static_cast<int>(4 * tile_width), xTable.as<unsigned>(), yTable.as<unsigned>(), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+#endif  // JU_TEST_HOOKS
 
 const char *ju_last_error(void) {
 	return g_LastError.c_str();

@@ -68,6 +68,7 @@ public:
 	int prepareBatch(const Frame *in, const Frame *out, int count);
 	// Frames per look-ahead pass, 1 (off) .. kFlowBatchMax, clamped.  Default: kFlowBatchMax, or JU_LOOKAHEAD at creation.
 	void setLookahead(int frames);
+	int lookahead() const { return m_BatchMax; }  // (also the most members one group pass holds)
 	// One frame for each of `count` runtimes, synchronously: the bytes process(in[i], out[i]) for i = 0 .. count - 1 would
 	// write, in every output and every member's state.  The members (distinct, one device, byte-identical model data,
 	// one dtype override: std::invalid_argument otherwise, before anything is launched) share a pass where they can:

@@ -145,7 +145,13 @@ void Engine::checkFrame(const AnyFrame &f, bool input, const char *who, bool dec
 		if (!resource && b.stride > -row && b.stride < row) refuse("|stride| smaller than a row");
 		return;
 	}
-	const YuvFrame &y = f.planes;
+	checkPlanes(f.planes, side, w, h, size, who);
+}
+
+// The non-BGRX half of the one frame check, for a frame that must be w x h (`size`: how the messages call that size):
+// shared with the tiled runtime (tiled.cpp), whose frames have its own sizes.
+void checkPlanes(const YuvFrame &y, const std::string &side, std::size_t w, std::size_t h, const std::string &size, const char *who) {
+	auto refuse = [who](const std::string &why) { throw std::invalid_argument(std::string(who) + ": " + why); };
 	const YuvFormatInfo *known = yuvFormatInfo(fmt(y.format));
 	if (known == nullptr) refuse("unknown " + side + " pixel format");
 	const YuvFormatInfo &info = *known;

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "frame_geometry.h"
@@ -68,6 +69,11 @@ inline FrameExtent extentOf(const AnyFrame &a) {
 	if (a.bgrx.location == Location::GraphicsResource) return FrameExtent{};
 	return imageExtent(a.bgrx.ptr, a.bgrx.stride, a.bgrx.width, a.bgrx.height, static_cast<int>(a.bgrx.location));
 }
+
+// Everything a frame call refuses about a frame that is not BGRX and must be w x h, before anything is launched
+// (std::invalid_argument "<who>: <why>"; side: "input" / "output"; size: how the messages call w x h).  The non-BGRX half
+// of Engine::checkFrame, which the tiled runtime shares at its own sizes (engine_frames.cpp).
+void checkPlanes(const YuvFrame &y, const std::string &side, std::size_t w, std::size_t h, const std::string &size, const char *who);
 
 // THE row copy: `rows` rows of `rowBytes` from `src` to `dst` (each the row lowest in memory and the pitch between rows:
 // rowSpan), enqueued on `stream` -- one contiguous copy when both sides are dense, a 2-D copy otherwise.  Pageable host

@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "tile_geometry.h"
+
 namespace ju {
 
 enum DType : int { kF16 = 0, kBF16 = 1 };
@@ -716,6 +718,24 @@ std::string outputSizeProblem(std::size_t outW, std::size_t outH, std::size_t mo
 void launchMaskBlend(std::uint8_t *gen, std::ptrdiff_t genStride, int outW, int outH, const std::uint8_t *src,
     std::ptrdiff_t srcStride, int srcW, int srcH, const std::uint8_t *mask, std::ptrdiff_t maskStride, int maskW,
     int maskH, hipStream_t stream);
+
+// ---- tiled upscaling (tile_kernels.hip; docs/tiled.md; the layout: tile_geometry.h) -----------------------------------
+// The tiles of one frame, row-major over the tile grid: tile k's dense BGRX image (16-byte aligned) and its origin in
+// SOURCE pixels.  The by-value argument of both kernels.
+struct TileSet {
+	std::uint8_t *ptr[kTileMax] = {};
+	int x[kTileMax] = {}, y[kTileMax] = {};
+};
+static_assert(sizeof(TileSet) <= 1024, "the by-value argument of the tile kernels must not grow");
+// BGRX rows of the source (address and signed stride multiples of 4) -> the `count` dense tileW x tileH inputs, X = 0:
+// tile k = the source's pixels from (x[k], y[k]) on.  One launch.
+void launchTileSplit(const std::uint8_t *src, std::ptrdiff_t srcStride, const TileSet &tiles, int count, int tileW, int tileH,
+    hipStream_t stream);
+// The nx x ny dense tile outputs (tileOutW pixels per row each) -> BGRX rows of outW x outH (address and signed stride
+// multiples of 4; X = 0): out = (sum wy wx v + 32768) >> 16 per byte over the tiles the two tables name -- the device
+// copies of TileAxis::table for the x and the y axis, one 32-bit word per output coordinate.  One launch.
+void launchTileStitch(std::uint8_t *dst, std::ptrdiff_t dstStride, int outW, int outH, const TileSet &tiles, int nx, int ny,
+    int tileOutW, const unsigned *xTable, const unsigned *yTable, hipStream_t stream);
 
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).

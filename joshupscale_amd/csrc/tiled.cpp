@@ -1,0 +1,190 @@
+// The tiled runtime (tiled.h; docs/tiled.md).  One frame: the source becomes BGRX rows on the device (the caller's image
+// where it is, an upload, or the existing decode at source size), ONE launch cuts it into the tiles' inputs, the tiles'
+// engines advance by one frame each as group passes (Engine::processGroup: the flow net of a pass's tiles in one pass of
+// its launches), ONE launch blends the tiles' outputs into the frame -- straight into a device BGRX image, else into a
+// staging frame that is copied out or encoded by the existing encode at output size.  The call is synchronous.
+#include "tiled.h"
+
+#include <algorithm>
+#include <stdexcept>
+
+namespace ju {
+
+namespace {
+std::size_t roundUp(std::size_t n, std::size_t to) { return (n + to - 1) / to * to; }
+
+ModelConfig configOf(const void *blob, std::size_t size) {
+	const ModelFile model(blob, size);
+	return model.config();
+}
+}  // namespace
+
+TiledRuntime::TiledRuntime(int device, const void *blob, std::size_t size, int dtypeOverride, std::size_t srcWidth,
+    std::size_t srcHeight, int overlap)
+    : m_Device(device), m_Overlap(overlap), m_SrcW(srcWidth), m_SrcH(srcHeight) {
+	const ModelConfig config = configOf(blob, size);  // (the loader's refusals first, then the layout's: no device yet)
+	m_TileW = static_cast<std::size_t>(config.frameWidth);
+	m_TileH = static_cast<std::size_t>(config.frameHeight);
+	const std::string problem = tileLayoutProblem(srcWidth, srcHeight, m_TileW, m_TileH, overlap);
+	if (!problem.empty()) throw std::invalid_argument("ju_tiled_create: " + problem);
+	m_X = tileAxis(static_cast<long>(srcWidth), static_cast<long>(m_TileW), overlap);
+	m_Y = tileAxis(static_cast<long>(srcHeight), static_cast<long>(m_TileH), overlap);
+	const int n = tiles();
+	for (int k = 0; k < n; ++k) m_Engines.push_back(std::make_unique<Engine>(device, blob, size, dtypeOverride));
+	m_Stream = std::make_unique<Stream>();
+	// (each tile's slot a multiple of 256 bytes: the kernels' 16-byte accesses, the group passes' 4- and 8-byte ones)
+	m_TileInBytes = roundUp(m_TileW * m_TileH * 4, 256);
+	m_TileOutBytes = roundUp(m_TileW * m_TileH * 64, 256);
+	m_TileIn = DeviceBuffer(m_TileInBytes * static_cast<std::size_t>(n));
+	m_TileOut = DeviceBuffer(m_TileOutBytes * static_cast<std::size_t>(n));
+	for (int k = 0; k < n; ++k) {
+		m_In.ptr[k] = m_TileIn.as<std::uint8_t>() + m_TileInBytes * static_cast<std::size_t>(k);
+		m_Out.ptr[k] = m_TileOut.as<std::uint8_t>() + m_TileOutBytes * static_cast<std::size_t>(k);
+		m_In.x[k] = m_Out.x[k] = m_X.origin[static_cast<std::size_t>(k % tilesX())];
+		m_In.y[k] = m_Out.y[k] = m_Y.origin[static_cast<std::size_t>(k / tilesX())];
+	}
+	// both axes' tables, uploaded once
+	m_XTable = DeviceBuffer(m_X.table.size() * sizeof(TileAxisEntry));
+	m_YTable = DeviceBuffer(m_Y.table.size() * sizeof(TileAxisEntry));
+	m_XTable.upload(m_X.table.data(), m_X.table.size() * sizeof(TileAxisEntry));
+	m_YTable.upload(m_Y.table.data(), m_Y.table.size() * sizeof(TileAxisEntry));
+}
+
+void TiledRuntime::tile(int index, std::size_t *x, std::size_t *y) const {
+	if (index < 0 || index >= tiles()) {
+		throw std::invalid_argument("ju_tiled_get_tile: index " + std::to_string(index) + " outside 0 .. " + std::to_string(tiles() - 1));
+	}
+	if (x) *x = static_cast<std::size_t>(m_In.x[index]);
+	if (y) *y = static_cast<std::size_t>(m_In.y[index]);
+}
+
+double TiledRuntime::stat(const std::string &key) const {
+	if (key == "tiles") return tiles();
+	if (key == "frames") return static_cast<double>(m_Frames);
+	if (key == "group_frames") {
+		double sum = 0;
+		for (const auto &e : m_Engines) sum += e->stat("group_frames");
+		return sum;
+	}
+	throw std::invalid_argument("ju_tiled_get_stat: unknown stat " + key);
+}
+
+void TiledRuntime::reset() {
+	for (const auto &e : m_Engines) e->reset();
+}
+
+// What ju_process_frame refuses for a frame of this size, and what a tiled frame cannot be: a graphics resource
+void TiledRuntime::check(const AnyFrame &f, bool input, const char *who) const {
+	const std::size_t w = input ? m_SrcW : kTileScale * m_SrcW, h = input ? m_SrcH : kTileScale * m_SrcH;
+	const std::string side = input ? "input" : "output";
+	const std::string size = std::to_string(w) + "x" + std::to_string(h) + (input ? " (the tiled source size)" : " (four times the tiled source size)");
+	if (f.yuv) return checkPlanes(f.planes, side, w, h, size, who);
+	auto refuse = [who](const std::string &why) { throw std::invalid_argument(std::string(who) + ": " + why); };
+	const Frame &b = f.bgrx;
+	if (b.location == Location::GraphicsResource) {
+		refuse("graphics resources cannot be tiled " + side + "s (the tile kernels read and write host or device memory)");
+	}
+	if (b.ptr == nullptr) refuse("NULL " + side + " image");
+	if (b.width != w || b.height != h) refuse(side + " image must be exactly " + size);
+	const auto row = static_cast<std::ptrdiff_t>(w * 4);
+	if (b.stride > -row && b.stride < row) refuse("|stride| smaller than a row");
+}
+
+DeviceBuffer &TiledRuntime::lazy(DeviceBuffer &b, std::size_t bytes) {
+	if (b.bytes() < bytes) b = DeviceBuffer(bytes);
+	return b;
+}
+
+TiledRuntime::Rows TiledRuntime::stageIn(const AnyFrame &in) {
+	const std::size_t rowBytes = m_SrcW * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	if (in.yuv) {  // the existing decode at source size; host planes through their staging layout first
+		const YuvFrame &y = in.planes;
+		auto *stage = lazy(m_SrcStage, rowBytes * m_SrcH).as<std::uint8_t>();
+		YuvPlanes planes = callerPlanes(y);
+		if (y.location == Location::Host) {
+			auto *yuv = lazy(m_YuvIn, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>();
+			copyPlanes(y, yuv, true, *m_Stream);
+			planes = stagedPlanes(y, yuv);
+		}
+		launchDecodeFrame(fmt(y.format), y.colorspace, planes, stage, plain, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), *m_Stream);
+		return {stage, plain};
+	}
+	const Frame &b = in.bgrx;
+	const bool device = b.location == Location::Device;
+	if (device && reinterpret_cast<std::uintptr_t>(b.ptr) % 4 == 0 && b.stride % 4 == 0) {
+		return {static_cast<std::uint8_t *>(b.ptr), b.stride};
+	}
+	// a host image, or a device image off the kernel's alignment: copied in its memory order, so a bottom-up image stays
+	// bottom-up and is read with a negative stride
+	auto *stage = lazy(m_SrcStage, rowBytes * m_SrcH).as<std::uint8_t>();
+	const RowSpan rows = rowSpan(b.ptr, b.stride, m_SrcH);
+	copyRows(stage, rowBytes, rows.lowest, rows.pitch, rowBytes, m_SrcH, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+	    *m_Stream);
+	if (rows.topDown) return {stage, plain};
+	return {stage + static_cast<std::ptrdiff_t>(m_SrcH - 1) * plain, -plain};
+}
+
+void TiledRuntime::stitchOut(const AnyFrame &out) {
+	const std::size_t ow = kTileScale * m_SrcW, oh = kTileScale * m_SrcH, rowBytes = ow * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	auto stitch = [&](std::uint8_t *dst, std::ptrdiff_t stride) {
+		launchTileStitch(dst, stride, static_cast<int>(ow), static_cast<int>(oh), m_Out, tilesX(), tilesY(),
+		    static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(), *m_Stream);
+	};
+	if (out.yuv) {  // the existing encode at output size, from the stitched 8-bit frame
+		const YuvFrame &y = out.planes;
+		auto *stage = lazy(m_OutStage, rowBytes * oh).as<std::uint8_t>();
+		stitch(stage, plain);
+		const bool host = y.location == Location::Host;
+		std::uint8_t *yuv = host ? lazy(m_YuvOut, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
+		launchEncodeFrame(fmt(y.format), y.colorspace, stage, plain, host ? stagedPlanes(y, yuv) : callerPlanes(y), static_cast<int>(ow),
+		    static_cast<int>(oh), *m_Stream);
+		if (host) copyPlanes(y, yuv, false, *m_Stream);
+		return;
+	}
+	const Frame &b = out.bgrx;
+	const bool device = b.location == Location::Device;
+	if (device && reinterpret_cast<std::uintptr_t>(b.ptr) % 4 == 0 && b.stride % 4 == 0) return stitch(static_cast<std::uint8_t *>(b.ptr), b.stride);
+	// stitched in the caller's row order, copied out in memory order
+	auto *stage = lazy(m_OutStage, rowBytes * oh).as<std::uint8_t>();
+	const RowSpan rows = rowSpan(b.ptr, b.stride, oh);
+	if (rows.topDown) {
+		stitch(stage, plain);
+	} else {
+		stitch(stage + static_cast<std::ptrdiff_t>(oh - 1) * plain, -plain);
+	}
+	copyRows(rows.lowest, rows.pitch, stage, rowBytes, rowBytes, oh, device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, *m_Stream);
+}
+
+void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *who) {
+	check(in, true, who);
+	check(out, false, who);
+	if (ju::overlap(extentOf(out), extentOf(in))) {
+		throw std::invalid_argument(std::string(who) + ": the output overlaps the input (the tiles read the source while the frame is written)");
+	}
+	DeviceGuard guard(m_Device);
+	const Rows src = stageIn(in);
+	const int n = tiles();
+	launchTileSplit(src.ptr, src.stride, m_In, n, static_cast<int>(m_TileW), static_cast<int>(m_TileH), *m_Stream);
+	// the group passes run on their lead's stream: the tiles' inputs are complete before the first of them starts
+	m_Stream->synchronize();
+	std::vector<Engine *> members(static_cast<std::size_t>(n));
+	std::vector<Frame> tin(static_cast<std::size_t>(n)), tout(static_cast<std::size_t>(n));
+	for (int k = 0; k < n; ++k) {
+		members[k] = m_Engines[static_cast<std::size_t>(k)].get();
+		tin[k] = Frame{m_In.ptr[k], Location::Device, static_cast<std::ptrdiff_t>(m_TileW * 4), m_TileW, m_TileH};
+		tout[k] = Frame{m_Out.ptr[k], Location::Device, static_cast<std::ptrdiff_t>(m_TileW * 16), m_TileW * kTileScale, m_TileH * kTileScale};
+	}
+	// a call of more tiles than one pass holds: the fewest passes, filled evenly (tilePasses) -- each call is synchronous
+	const TilePasses passes = tilePasses(n, std::max(members[0]->lookahead(), 1));
+	for (int p = 0; p < passes.passes; ++p) {
+		const int at = passes.begin(p);
+		Engine::processGroup(members.data() + at, tin.data() + at, tout.data() + at, passes.count(p));
+	}
+	stitchOut(out);
+	m_Stream->synchronize();
+	++m_Frames;
+}
+
+}  // namespace ju

@@ -1,0 +1,72 @@
+// Tiled upscaling (docs/tiled.md): a source larger than the model, cut into model-size tiles that overlap, each tile an
+// independent recurrent stream of its own Engine, the tiles' outputs blended into one frame on the GPU.  No reference
+// counterpart: the reference upscales exactly the model's size.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "engine.h"
+#include "tile_geometry.h"
+
+namespace ju {
+
+class TiledRuntime {
+public:
+	// srcWidth x srcHeight: the size of every input frame; overlap: source pixels neighbouring tiles share at least.
+	// std::invalid_argument for sizes or an overlap outside the limits (tileLayoutProblem), before any engine is built.
+	TiledRuntime(int device, const void *blob, std::size_t size, int dtypeOverride, std::size_t srcWidth, std::size_t srcHeight,
+	    int overlap);
+	TiledRuntime(const TiledRuntime &) = delete;
+	TiledRuntime &operator=(const TiledRuntime &) = delete;
+
+	// One frame, synchronously: `in` of the source size, `out` of four times that, any format, host or device.  Both are
+	// checked before anything is launched (std::invalid_argument "<who>: <why>"; every tile's state as it was).
+	void process(const AnyFrame &in, const AnyFrame &out, const char *who);
+	// zeroes every tile's recurrent state
+	void reset();
+
+	std::size_t srcWidth() const { return m_SrcW; }
+	std::size_t srcHeight() const { return m_SrcH; }
+	std::size_t tileWidth() const { return m_TileW; }
+	std::size_t tileHeight() const { return m_TileH; }
+	int tilesX() const { return m_X.tiles(); }
+	int tilesY() const { return m_Y.tiles(); }
+	int tiles() const { return tilesX() * tilesY(); }
+	int overlap() const { return m_Overlap; }
+	// the origin of tile `index` (row-major over the tile grid) in source pixels
+	void tile(int index, std::size_t *x, std::size_t *y) const;
+	// "tiles", "frames" (frames processed), "group_frames" (the members' frames that ran inside group passes, summed)
+	double stat(const std::string &key) const;
+
+private:
+	void check(const AnyFrame &f, bool input, const char *who) const;
+	// the source as 4-byte-aligned BGRX rows on the device: the caller's image where it is, or m_SrcStage
+	struct Rows {
+		std::uint8_t *ptr;
+		std::ptrdiff_t stride;
+	};
+	Rows stageIn(const AnyFrame &in);
+	void stitchOut(const AnyFrame &out);
+	DeviceBuffer &lazy(DeviceBuffer &b, std::size_t bytes);
+
+	int m_Device;
+	int m_Overlap;
+	std::size_t m_SrcW, m_SrcH, m_TileW = 0, m_TileH = 0;
+	TileAxis m_X, m_Y;
+	std::vector<std::unique_ptr<Engine>> m_Engines;
+	std::unique_ptr<Stream> m_Stream;
+	// every tile's dense input / output, one after the other (m_In / m_Out name them for the kernels)
+	DeviceBuffer m_TileIn, m_TileOut;
+	std::size_t m_TileInBytes = 0, m_TileOutBytes = 0;
+	TileSet m_In, m_Out;
+	DeviceBuffer m_XTable, m_YTable;
+	// frames that are not device BGRX: the BGRX source and result, and the planes of host frames of another format
+	DeviceBuffer m_SrcStage, m_OutStage, m_YuvIn, m_YuvOut;
+	std::uint64_t m_Frames = 0;
+};
+
+}  // namespace ju

@@ -172,6 +172,13 @@ SCENE_OFF, SCENE_REPORT, SCENE_RESET = 0, 1, 2
 SCENE_RING = 64
 
 
+class JuTiledInfo(C.Structure):
+    """``ju_tiled_info``: the sizes and the tile grid of a tiled runtime (docs/tiled.md)."""
+    _fields_ = [("src_width", C.c_size_t), ("src_height", C.c_size_t), ("out_width", C.c_size_t),
+                ("out_height", C.c_size_t), ("tile_width", C.c_size_t), ("tile_height", C.c_size_t),
+                ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("overlap", C.c_int)]
+
+
 def hooks_default() -> bool:
     """``JU_TEST_HOOKS=1`` (set by tests/conftest.py and the developer tools): the process works
     through libJoshUpscale_test.so.  Unset -- every caller of the product -- it is the product library."""
@@ -221,6 +228,16 @@ _PRODUCT_SIGS = {
     "ju_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
     "ju_set_output_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_get_output_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
+    "ju_tiled_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p)]),
+    "ju_tiled_create_from_memory": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int,
+                                              _P(C.c_void_p)]),
+    "ju_tiled_destroy": (None, [C.c_void_p]),
+    "ju_tiled_reset": (C.c_int, [C.c_void_p]),
+    "ju_tiled_process": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
+    "ju_tiled_process_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
+    "ju_tiled_get_info": (C.c_int, [C.c_void_p, _P(JuTiledInfo)]),
+    "ju_tiled_get_tile": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_size_t), _P(C.c_size_t)]),
+    "ju_tiled_get_stat": (C.c_int, [C.c_void_p, C.c_char_p, _P(C.c_double)]),
     "ju_last_error": (C.c_char_p, []),
     "ju_set_log_callback": (None, [LOG_CALLBACK, C.c_void_p]),
     "ju_get_gl_device_index": (C.c_int, [_P(C.c_int)]),
@@ -277,6 +294,10 @@ _HOOK_SIGS = {
                                          _P(C.c_void_p), _P(C.c_ssize_t), _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_debug_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                     C.c_float, C.c_float, C.c_float, C.c_int, C.c_uint, C.c_void_p, C.c_size_t]),
+    "ju_debug_tile_split": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                                      _P(C.c_void_p), C.c_int]),
+    "ju_debug_tile_stitch": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                                       _P(C.c_void_p), C.c_int]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_plan_report": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, _P(C.c_size_t)]),
@@ -772,6 +793,88 @@ def process_group_frames(runtimes, inputs, outputs) -> None:
     hs = (C.c_void_p * n)(*[rt._h.value for rt in runtimes])
     ins, outs = (JuFrame * n)(*inputs), (JuFrame * n)(*outputs)
     _check(lib, lib.ju_process_group_frames(hs, ins, outs, n))
+
+
+class TiledRuntime:
+    """``ju_tiled``: frames of ``src_width x src_height`` -- larger than the model -- upscaled tile by tile, the tiles
+    blended across their seams on the GPU (docs/tiled.md).  ``model``: the bytes of a .jupw file (or its path);
+    ``overlap``: source pixels neighbouring tiles share at least, ``0 .. min(W, H) // 4`` for a model of ``W x H``."""
+
+    def __init__(self, model, device: int = 0, dtype: int = DTYPE_DEFAULT, src_width: int = 0, src_height: int = 0,
+                 overlap: int = 16, hooks: Optional[bool] = None):
+        self._lib = load_library(hooks)
+        self._h = C.c_void_p()
+        if not isinstance(model, (bytes, bytearray, memoryview)):
+            with open(model, "rb") as f:
+                model = f.read()
+        buf = bytes(model)
+        _check(self._lib, self._lib.ju_tiled_create_from_memory(device, buf, len(buf), dtype, int(src_width), int(src_height),
+                                                                int(overlap), C.byref(self._h)))
+        self.device = device
+        i = self.info()
+        self.src_width, self.src_height, self.out_width, self.out_height = (i["src_width"], i["src_height"],
+                                                                            i["out_width"], i["out_height"])
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.ju_tiled_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def process(self, inp: JuImage, out: JuImage) -> None:
+        """``ju_tiled_process``: one frame on two BGRX image descriptors, host or device (synchronous)."""
+        _check(self._lib, self._lib.ju_tiled_process(self._h, C.byref(inp), C.byref(out)))
+
+    def process_frame(self, inp: JuFrame, out: JuFrame) -> None:
+        """``ju_tiled_process_frame``: one frame on frames of any format, host or device (synchronous)."""
+        _check(self._lib, self._lib.ju_tiled_process_frame(self._h, C.byref(inp), C.byref(out)))
+
+    def run(self, frame_bgrx: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host frames: ``[src_height, src_width, 4]`` uint8 BGRX in, ``[4 src_height, 4 src_width, 4]`` out.  Any row
+        stride (also negative, i.e. a ``[::-1]`` view) is passed through."""
+        if frame_bgrx.dtype != np.uint8 or frame_bgrx.ndim != 3 or frame_bgrx.shape[2] != 4:
+            raise ValueError("expected a [H, W, 4] uint8 BGRX frame")
+        if frame_bgrx.strides[2] != 1 or frame_bgrx.strides[1] != 4:
+            frame_bgrx = np.ascontiguousarray(frame_bgrx)
+        if out is None:
+            out = np.empty((self.out_height, self.out_width, 4), np.uint8)
+        if out.strides[2] != 1 or out.strides[1] != 4:
+            raise ValueError("output must have contiguous pixels")
+        self.process(host_image(frame_bgrx), host_image(out))
+        return out
+
+    def reset(self) -> None:
+        """``ju_tiled_reset``: zeroes every tile's recurrent state."""
+        _check(self._lib, self._lib.ju_tiled_reset(self._h))
+
+    def info(self) -> dict:
+        """``ju_tiled_get_info`` as a dict of the struct's fields."""
+        i = JuTiledInfo()
+        _check(self._lib, self._lib.ju_tiled_get_info(self._h, C.byref(i)))
+        return {name: int(getattr(i, name)) for name, _ in JuTiledInfo._fields_}
+
+    def tile(self, index: int) -> Tuple[int, int]:
+        """``ju_tiled_get_tile``: the origin ``(x, y)`` of a tile (row-major over the tile grid) in source pixels."""
+        x, y = C.c_size_t(), C.c_size_t()
+        _check(self._lib, self._lib.ju_tiled_get_tile(self._h, int(index), C.byref(x), C.byref(y)))
+        return x.value, y.value
+
+    def stat(self, key: str) -> float:
+        """``ju_tiled_get_stat``: "tiles", "frames", "group_frames" (summed over the tiles)."""
+        v = C.c_double()
+        _check(self._lib, self._lib.ju_tiled_get_stat(self._h, key.encode(), C.byref(v)))
+        return v.value
 
 
 def gl_image(texture: int, output: bool) -> JuImage:
