@@ -646,16 +646,32 @@ JU_API int ju_tiled_reset(ju_tiled *tiled);
  * overlaps the input (same address space). */
 JU_API int ju_tiled_process(ju_tiled *tiled, const ju_image *input, const ju_image *output);
 /* ju_tiled_process on frames of any JU_FMT_* format, host or device: the input is decoded at source size by the
- * conversion ju_process_frame uses, the blended 8-bit frame is encoded at output size -- also a deep format (P010,
- * BGRX64, ...), which ju_process_frame would take from the f16 state: a tiled frame has no single state.  Refused as
- * above, and whatever ju_process_frame refuses for a frame of that size (an odd size for a subsampled format, an unknown
- * format or colour space, a NULL or misaligned plane, |stride| smaller than a row). */
+ * conversion ju_process_frame uses, the blended 8-bit frame is encoded at output size -- by default also a deep format
+ * (P010, BGRX64, ...), which ju_process_frame would take from the f16 state (ju_tiled_set_deep_from_state below).  Refused
+ * as above, and whatever ju_process_frame refuses for a frame of that size (an odd size for a subsampled format, an
+ * unknown format or colour space, a NULL or misaligned plane, |stride| smaller than a row). */
 JU_API int ju_tiled_process_frame(ju_tiled *tiled, const ju_frame *input, const ju_frame *output);
+/* Deep outputs from the tiles' f16 states (no reference counterpart: the reference has no tiles and writes 8-bit frames).
+ * on = 1: a deep output format (P010, I010, P210, I210, I410, V210, Y210, Y410, BGRX64, RGBP10, RGBP16, RGBPH, RGBPS,
+ * BGR96F, X2RGB10, X2BGR10) is encoded from the blend of the tiles' states instead of the blended 8-bit frame: with P the
+ * 16-bit sample floor((s + 0.5) 65536), saturated, of a tile's state, out16 = (sum wy wx P + 32768) >> 16 per channel over
+ * the same weights, and the planes are what ju_process_frame's encode makes of such a 16-bit frame -- so the low bits are
+ * the network's, as on every other route (docs/tiled.md "Deep outputs"; tests/tiled_deep_reference.py).  A source of
+ * exactly W x H, ONE tile, is encoded straight from that tile's state: ju_process_frame's bytes.  It costs one more frame
+ * of 8 bytes per output pixel in device memory, made at the first such frame of two tiles or more.  on = 0 (the default): every
+ * format from the 8-bit frame, the bytes of earlier versions.  The setting has no effect on 8-bit formats, on the tiles'
+ * states, or for a model whose state is not its frame in float (normalize_brightness, output = "pre_warp":
+ * ju_tiled_get_stat "hbd_from_state" 0), whose deep frames stay the 8-bit route's.  ju_tiled_reset keeps it.  Another value
+ * is JU_ERR_INVALID_ARGUMENT and leaves the setting as it was. */
+JU_API int ju_tiled_set_deep_from_state(ju_tiled *tiled, int on);
 JU_API int ju_tiled_get_info(const ju_tiled *tiled, ju_tiled_info *info);
 /* The origin of tile `index` (0 .. tiles_x tiles_y - 1, row-major over the tile grid) in source pixels. */
 JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t *y);
 /* "tiles"; "frames": frames processed; "group_frames": the tiles' frames that ran inside group passes, summed over the
- * tiles (tiles x frames while every pass holds at least two tiles).  An unknown key is JU_ERR_INVALID_ARGUMENT. */
+ * tiles (tiles x frames while every pass holds at least two tiles); "deep_from_state": the setting of
+ * ju_tiled_set_deep_from_state; "hbd_from_state": 1 where the model's f16 state is its frame in float (ju_get_stat's key,
+ * every tile's alike); "deep_state_frames": the frames whose output was blended from the tiles' states.  An unknown key is
+ * JU_ERR_INVALID_ARGUMENT. */
 JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value);
 /* Not provided for a tiled object: look-ahead passes, ju_set_source_size / ju_set_output_size / the mask / the scene
  * detector, graphics resources, graph capture, the C++ plugin surface. */

@@ -260,6 +260,15 @@ JU_API int ju_debug_tile_split(const void *src, ptrdiff_t src_stride, size_t src
     size_t tile_height, int overlap, void *const *tiles, int count);
 JU_API int ju_debug_tile_stitch(void *dst, ptrdiff_t dst_stride, size_t src_width, size_t src_height, size_t tile_width,
     size_t tile_height, int overlap, void *const *tiles, int count);
+/* The blend of the tiles' f16 states alone (tile_stitch_state_kernel; docs/tiled.md "Deep outputs"; the definition:
+ * tests/tiled_deep_reference.py stitch16 over p_from_state), ONE synchronous launch on caller-supplied device buffers, on
+ * the current device, for the same layout, held to the same limits.  `tiles`: `count` dense states [4 tile_height]
+ * [4 tile_width][4] f16 (B, G, R and a fourth value that is ignored), 16-byte aligned, row-major over the tile grid.  It
+ * writes the dense frame [4 src_height][4 src_width][4] of 16-bit words at `dst16` (16-byte aligned), X = 0, and nothing
+ * behind it.  A NULL buffer, a misaligned pointer, sizes or an overlap outside the limits or a wrong count is
+ * JU_ERR_INVALID_ARGUMENT before any device call. */
+JU_API int ju_debug_tile_stitch_state(void *dst16, size_t src_width, size_t src_height, size_t tile_width, size_t tile_height,
+    int overlap, void *const *tiles, int count);
 
 #ifdef __cplusplus
 } /* extern "C" */

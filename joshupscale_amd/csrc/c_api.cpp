@@ -419,6 +419,10 @@ int ju_tiled_reset(ju_tiled *tiled) {
 	return guarded([&] { tiledOf(tiled).reset(); });
 }
 
+int ju_tiled_set_deep_from_state(ju_tiled *tiled, int on) {
+	return guarded([&] { tiledOf(tiled).setDeepFromState(on); });
+}
+
 int ju_tiled_process(ju_tiled *tiled, const ju_image *input, const ju_image *output) {
 	return guarded([&] {
 		ju::TiledRuntime &t = tiledOf(tiled);
@@ -511,6 +515,33 @@ int ju_debug_tile_stitch(void *dst, ptrdiff_t dst_stride, size_t src_width, size
 		xTable.upload(x.table.data(), x.table.size() * sizeof(ju::TileAxisEntry));
 		yTable.upload(y.table.data(), y.table.size() * sizeof(ju::TileAxisEntry));
 		ju::launchTileStitch(static_cast<std::uint8_t *>(dst), dst_stride, static_cast<int>(4 * src_width), static_cast<int>(4 * src_height),
+		    set, nx, ny, static_cast<int>(4 * tile_width), xTable.as<unsigned>(), yTable.as<unsigned>(), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_tile_stitch_state(void *dst16, size_t src_width, size_t src_height, size_t tile_width, size_t tile_height, int overlap,
+    void *const *tiles, int count) {
+	return guarded([&] {
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		const std::string name = "ju_debug_tile_stitch_state";
+		// (the dense 16-bit frame: rows of 8 bytes per pixel)
+		debugTileSet(name.c_str(), src_width, src_height, tile_width, tile_height, overlap, tiles, count, dst16,
+		    static_cast<ptrdiff_t>(32 * src_width), 4 * src_width, &set, &nx, &ny);
+		// what the launcher would refuse, in front of the tables' device memory
+		if (reinterpret_cast<std::uintptr_t>(dst16) % 16) throw std::invalid_argument(name + ": the 16-bit frame is not 16-byte aligned");
+		for (int k = 0; k < count; ++k) {
+			if (set.ptr[k] == nullptr || reinterpret_cast<std::uintptr_t>(set.ptr[k]) % 16) {
+				throw std::invalid_argument(name + ": tile " + std::to_string(k) + " is NULL or not 16-byte aligned");
+			}
+		}
+		const ju::TileAxis x = ju::tileAxis(static_cast<long>(src_width), static_cast<long>(tile_width), overlap);
+		const ju::TileAxis y = ju::tileAxis(static_cast<long>(src_height), static_cast<long>(tile_height), overlap);
+		ju::DeviceBuffer xTable(x.table.size() * sizeof(ju::TileAxisEntry)), yTable(y.table.size() * sizeof(ju::TileAxisEntry));
+		xTable.upload(x.table.data(), x.table.size() * sizeof(ju::TileAxisEntry));
+		yTable.upload(y.table.data(), y.table.size() * sizeof(ju::TileAxisEntry));
+		ju::launchTileStitchState(static_cast<std::uint16_t *>(dst16), static_cast<int>(4 * src_width), static_cast<int>(4 * src_height),
 		    set, nx, ny, static_cast<int>(4 * tile_width), xTable.as<unsigned>(), yTable.as<unsigned>(), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});

@@ -152,6 +152,10 @@ public:
 	// JU_DTYPE_* as reported to the caller: 2 when the block convolutions run in e4m3
 	int reportedDtype() const { return m_Fp8Tower ? 2 : static_cast<int>(m_DType); }
 	const ModelConfig &config() const { return m_Config; }
+	// The f16 state [4H][4W][4] (B, G, R, 0) the last frame left, on the device; valid after a synchronous call.  A frame
+	// writes m_State[m_Idx ^ 1] and its call then flips m_Idx (what stageOutScaled and submitFrame read BEFORE the flip), so
+	// behind the call it is m_State[m_Idx] -- readTensor's "state".  A flow-free model: its one scratch state.
+	const void *lastState() const { return m_State[m_Config.recurrent() ? m_Idx : 0].get(); }
 	void setUseGraph(bool on) { m_UseGraph = on; }
 
 	// ---- introspection (tests, bench) ----

@@ -736,6 +736,13 @@ void launchTileSplit(const std::uint8_t *src, std::ptrdiff_t srcStride, const Ti
 // copies of TileAxis::table for the x and the y axis, one 32-bit word per output coordinate.  One launch.
 void launchTileStitch(std::uint8_t *dst, std::ptrdiff_t dstStride, int outW, int outH, const TileSet &tiles, int nx, int ny,
     int tileOutW, const unsigned *xTable, const unsigned *yTable, hipStream_t stream);
+// The blend of the tiles' f16 STATES (docs/tiled.md "Deep outputs"; tests/tiled_deep_reference.py stitch16): `states` names
+// the nx x ny dense states [..][tileOutW][4] f16 (B, G, R, unused; 16-byte aligned) by their ptr fields, origins as above
+// -> the dense u16 frame [outH][outW][4] at dst16 (16-byte aligned; outW a multiple of 4; X = 0): per channel
+// out16 = (sum wy wx P + 32768) >> 16 with P = floor((s + 0.5) * 65536) saturated, at most 65535 * 65536 + 32768 < 2^32.
+// The layout launchScaleState writes and launchEncodeFrame16 reads.  One launch.
+void launchTileStitchState(std::uint16_t *dst16, int outW, int outH, const TileSet &states, int nx, int ny, int tileOutW,
+    const unsigned *xTable, const unsigned *yTable, hipStream_t stream);
 
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).

@@ -13,9 +13,13 @@
 //                       tile and the weight of the next one; a group that lies under ONE tile -- all of a frame but
 //                       its seams -- is one 16-byte load and one 16-byte store, a pixel on a seam reads two or four
 //                       tiles: out = (sum wy wx v + 32768) >> 16 per byte, at most 65536 * 255 < 2^32.
+//   tile_stitch_state_kernel  the same blend over the tiles' f16 STATES, per 16-bit sample P of a state, into a dense
+//                       u16 frame that launchEncodeFrame16 encodes (deep outputs; tests/tiled_deep_reference.py): no
+//                       head or tail groups, a capped grid that strides over the rows, 2 x 8 x 4 Ws x 4 Hs bytes.
 //
 // Both are bound by memory: the split moves 2 x 4 Ws Hs bytes and a little more (the overlaps are read and written
-// twice), the stitch 2 x 64 Ws Hs.  Tile pointers and origins travel by value in the kernel arguments (TileSet).
+// twice), the stitch 2 x 64 Ws Hs.  Tile pointers and origins travel by value in the kernel arguments (TileSet); the
+// state stitch copies them into LDS once per workgroup.
 // Rows are addressed with their signed stride; every address and stride is a multiple of 4 (the launchers refuse others).
 
 #include <hip/hip_runtime.h>
@@ -146,6 +150,107 @@ __global__ __launch_bounds__(256) void tile_stitch_kernel(std::uint8_t *__restri
 	}
 }
 
+// ---- the blend of the tiles' f16 states (docs/tiled.md "Deep outputs"; tests/tiled_deep_reference.py stitch16) ----------
+// P of one f16 of a state, as StateSource::sample (colour_kernels.hip) forms it: exact in f32
+__device__ __forceinline__ unsigned stateP(unsigned bits) {
+	const float s = static_cast<float>(__builtin_bit_cast(f16, static_cast<unsigned short>(bits)));
+	return static_cast<unsigned>(fminf(fmaxf(floorf((s + 0.5f) * 65536.0f), 0.0f), 65535.0f));
+}
+
+// two pixels of a state (eight f16: B, G, R, unused twice) as two pixels of the 16-bit frame (P_B | P_G << 16, P_R, twice)
+__device__ __forceinline__ uint4 statePair(uint4 v) {
+	return make_uint4(stateP(v.x & 0xffffu) | (stateP(v.x >> 16) << 16), stateP(v.y & 0xffffu),
+	    stateP(v.z & 0xffffu) | (stateP(v.z >> 16) << 16), stateP(v.w & 0xffffu));
+}
+
+// the tiles as a workgroup holds them in LDS (below)
+struct TileView {
+	const std::uint8_t *const *ptr;
+	const int *x, *y;
+};
+
+// one pixel of the 16-bit frame from the up to four states its two table entries name (8-byte loads)
+__device__ __forceinline__ uint2 stitchStatePixel(const TileView &tiles, int nx, unsigned ex, unsigned ey, int X, int Y,
+    int tileOutW) {
+	const int tx = ex & 0xffffu, ty = ey & 0xffffu;
+	const unsigned qx = ex >> 16, qy = ey >> 16;
+	const unsigned wx[2] = {256u - qx, qx}, wy[2] = {256u - qy, qy};
+	unsigned b = 32768u, g = 32768u, c = 32768u;
+#pragma unroll
+	for (int j = 0; j < 2; ++j) {
+#pragma unroll
+		for (int i = 0; i < 2; ++i) {
+			const unsigned w = wy[j] * wx[i];
+			if (w == 0) continue;  // (a tile without weight is not read: it may not cover the pixel, or not exist)
+			const int k = (ty + j) * nx + tx + i;
+			const uint2 v = *reinterpret_cast<const uint2 *>(
+			    tiles.ptr[k] + (static_cast<std::size_t>(Y - kTileScale * tiles.y[k]) * tileOutW + (X - kTileScale * tiles.x[k])) * 8);
+			b += w * stateP(v.x & 0xffffu);
+			g += w * stateP(v.x >> 16);
+			c += w * stateP(v.y & 0xffffu);
+		}
+	}
+	return make_uint2((b >> 16) | (g & 0xffff0000u), c >> 16);
+}
+
+// A lane takes four pixels of a row from X0 = 0 (mod 4) -- 32 bytes of the destination, and 32-byte aligned in it and in
+// every state that covers them (outW, tileOutW and every tile origin are multiples of four pixels): no head, no tail.  The
+// grid is capped and strides over the rows, so the lane's four column entries are fetched ONCE, in front of the loop, and
+// the next row's entry while this row's pixels are on their way: only the states' pointers and the pixels themselves are
+// behind a dependent load.  Four pixels under one tile: two 16-byte loads, twelve samples, two 16-byte stores.
+// The tiles' pointers and origins go from the kernel arguments into LDS once per workgroup: a lane's lookup by its own
+// index is then an LDS read, not a load from the argument segment in every row.
+__global__ __launch_bounds__(256) void tile_stitch_state_kernel(std::uint16_t *__restrict__ dst, int outW, int outH,
+    const TileSet set, int nx, int count, int tileOutW, const unsigned *__restrict__ xTable,
+    const unsigned *__restrict__ yTable) {
+	__shared__ const std::uint8_t *sPtr[kTileMax];
+	__shared__ int sX[kTileMax], sY[kTileMax];
+	const int lane = threadIdx.y * 64 + threadIdx.x;
+	if (lane < count) {
+		sPtr[lane] = set.ptr[lane];
+		sX[lane] = set.x[lane];
+		sY[lane] = set.y[lane];
+	}
+	__syncthreads();
+	const TileView tiles{sPtr, sX, sY};
+	const int X0 = (blockIdx.x * 64 + threadIdx.x) * 4;
+	int Y = blockIdx.y * 4 + threadIdx.y;
+	if (X0 >= outW || Y >= outH) return;
+	const int step = gridDim.y * 4;
+	unsigned ey = yTable[Y];
+	const uint4 ex = *reinterpret_cast<const uint4 *>(xTable + X0);
+	// (equal entries without weight: the four columns lie under one tile column, whose origin every tile row shares)
+	const bool oneColumn = (ex.x >> 16) == 0 && ex.x == ex.y && ex.x == ex.z && ex.x == ex.w;
+	const int tx = ex.x & 0xffffu;
+	const int xIn = X0 - kTileScale * tiles.x[tx];
+	for (;;) {
+		const int next = Y + step;
+		const unsigned eyNext = next < outH ? yTable[next] : 0u;
+		uint4 lo, hi;
+		if (oneColumn && (ey >> 16) == 0) {
+			const int k = (ey & 0xffffu) * nx + tx;
+			const uint4 *s = reinterpret_cast<const uint4 *>(
+			    tiles.ptr[k] + (static_cast<std::size_t>(Y - kTileScale * tiles.y[k]) * tileOutW + xIn) * 8);
+			const uint4 a = s[0], b = s[1];
+			lo = statePair(a);
+			hi = statePair(b);
+		} else {
+			const uint2 p0 = stitchStatePixel(tiles, nx, ex.x, ey, X0, Y, tileOutW);
+			const uint2 p1 = stitchStatePixel(tiles, nx, ex.y, ey, X0 + 1, Y, tileOutW);
+			const uint2 p2 = stitchStatePixel(tiles, nx, ex.z, ey, X0 + 2, Y, tileOutW);
+			const uint2 p3 = stitchStatePixel(tiles, nx, ex.w, ey, X0 + 3, Y, tileOutW);
+			lo = make_uint4(p0.x, p0.y, p1.x, p1.y);
+			hi = make_uint4(p2.x, p2.y, p3.x, p3.y);
+		}
+		uint4 *d = reinterpret_cast<uint4 *>(dst + (static_cast<std::size_t>(Y) * outW + X0) * 4);
+		d[0] = lo;
+		d[1] = hi;
+		if (next >= outH) break;
+		Y = next;
+		ey = eyNext;
+	}
+}
+
 void checkTileSet(const char *who, const TileSet &tiles, int count, unsigned align) {
 	if (count < 1 || count > kTileMax) throw std::invalid_argument(std::string(who) + ": 1 .. 64 tiles");
 	for (int k = 0; k < count; ++k) {
@@ -189,6 +294,29 @@ void launchTileStitch(std::uint8_t *dst, std::ptrdiff_t dstStride, int outW, int
 	hipLaunchKernelGGL(tile_stitch_kernel, grid, dim3(64, 4), 0, stream, dst, dstStride, outW, outH, tiles, nx, tileOutW, xTable,
 	    yTable);
 	hipCheckLaunch("tile_stitch");
+}
+
+void launchTileStitchState(std::uint16_t *dst16, int outW, int outH, const TileSet &states, int nx, int ny, int tileOutW,
+    const unsigned *xTable, const unsigned *yTable, hipStream_t stream) {
+	if (nx < 1 || ny < 1) throw std::invalid_argument("tile_stitch_state: 1 .. 64 tiles");
+	checkTileSet("tile_stitch_state", states, nx * ny, 16);
+	if (dst16 == nullptr || reinterpret_cast<std::uintptr_t>(dst16) % 16) {
+		throw std::invalid_argument("tile_stitch_state: the 16-bit frame is NULL or not 16-byte aligned");
+	}
+	if (outW < 4 || outW % 4 || outH < 1 || tileOutW < 4 || tileOutW % 4) {
+		throw std::invalid_argument("tile_stitch_state: widths must be multiples of four pixels");
+	}
+	if (xTable == nullptr || yTable == nullptr || reinterpret_cast<std::uintptr_t>(xTable) % 16) {
+		throw std::invalid_argument("tile_stitch_state: NULL table, or an x table that is not 16-byte aligned");
+	}
+	// memory-bound: about 2048 workgroups at the most, which stride over the rows
+	const unsigned gx = (static_cast<unsigned>(outW) / 4 + 63) / 64;
+	const unsigned rows = (static_cast<unsigned>(outH) + 3) / 4;
+	const unsigned cap = gx < 2048u ? 2048u / gx : 1u;
+	const dim3 grid(gx, rows < cap ? rows : cap);
+	hipLaunchKernelGGL(tile_stitch_state_kernel, grid, dim3(64, 4), 0, stream, dst16, outW, outH, states, nx, nx * ny, tileOutW,
+	    xTable, yTable);
+	hipCheckLaunch("tile_stitch_state");
 }
 
 }  // namespace ju

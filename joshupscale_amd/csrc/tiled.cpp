@@ -2,7 +2,8 @@
 // where it is, an upload, or the existing decode at source size), ONE launch cuts it into the tiles' inputs, the tiles'
 // engines advance by one frame each as group passes (Engine::processGroup: the flow net of a pass's tiles in one pass of
 // its launches), ONE launch blends the tiles' outputs into the frame -- straight into a device BGRX image, else into a
-// staging frame that is copied out or encoded by the existing encode at output size.  The call is synchronous.
+// staging frame that is copied out or encoded by the existing encode at output size.  With setDeepFromState a deep format
+// is instead encoded from ONE launch's blend of the tiles' f16 states (stitchOutDeep).  The call is synchronous.
 #include "tiled.h"
 
 #include <algorithm>
@@ -31,6 +32,7 @@ TiledRuntime::TiledRuntime(int device, const void *blob, std::size_t size, int d
 	m_Y = tileAxis(static_cast<long>(srcHeight), static_cast<long>(m_TileH), overlap);
 	const int n = tiles();
 	for (int k = 0; k < n; ++k) m_Engines.push_back(std::make_unique<Engine>(device, blob, size, dtypeOverride));
+	m_HbdFromState = m_Engines[0]->stat("hbd_from_state") != 0;  // (the model's property: every tile's alike)
 	m_Stream = std::make_unique<Stream>();
 	// (each tile's slot a multiple of 256 bytes: the kernels' 16-byte accesses, the group passes' 4- and 8-byte ones)
 	m_TileInBytes = roundUp(m_TileW * m_TileH * 4, 256);
@@ -61,6 +63,9 @@ void TiledRuntime::tile(int index, std::size_t *x, std::size_t *y) const {
 double TiledRuntime::stat(const std::string &key) const {
 	if (key == "tiles") return tiles();
 	if (key == "frames") return static_cast<double>(m_Frames);
+	if (key == "deep_from_state") return m_DeepFromState ? 1.0 : 0.0;
+	if (key == "hbd_from_state") return m_HbdFromState ? 1.0 : 0.0;
+	if (key == "deep_state_frames") return static_cast<double>(m_DeepStateFrames);
 	if (key == "group_frames") {
 		double sum = 0;
 		for (const auto &e : m_Engines) sum += e->stat("group_frames");
@@ -71,6 +76,11 @@ double TiledRuntime::stat(const std::string &key) const {
 
 void TiledRuntime::reset() {
 	for (const auto &e : m_Engines) e->reset();
+}
+
+void TiledRuntime::setDeepFromState(int on) {
+	if (on != 0 && on != 1) throw std::invalid_argument("ju_tiled_set_deep_from_state: " + std::to_string(on) + " is neither 0 nor 1");
+	m_DeepFromState = on == 1;
 }
 
 // What ju_process_frame refuses for a frame of this size, and what a tiled frame cannot be: a graphics resource
@@ -125,7 +135,38 @@ TiledRuntime::Rows TiledRuntime::stageIn(const AnyFrame &in) {
 	return {stage + static_cast<std::ptrdiff_t>(m_SrcH - 1) * plain, -plain};
 }
 
+bool TiledRuntime::deepFromState(const AnyFrame &out) const {
+	return out.yuv && m_DeepFromState && m_HbdFromState && formatInfo(out.planes.format).deep();
+}
+
+// The 16-bit path: ONE launch blends the states the tiles' last frames left -- the group passes are synchronous, so they
+// are complete -- into the dense 16-bit frame, which the existing encode from such a frame turns into the caller's planes
+// (a host frame's through their staging layout, as on the 8-bit route).
+void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
+	const std::size_t ow = kTileScale * m_SrcW, oh = kTileScale * m_SrcH;
+	TileSet states = m_Out;  // (the origins; the pointers: each tile's state, whichever half its last frame wrote)
+	for (int k = 0; k < tiles(); ++k) {
+		states.ptr[k] = static_cast<std::uint8_t *>(const_cast<void *>(m_Engines[static_cast<std::size_t>(k)]->lastState()));
+	}
+	const bool host = y.location == Location::Host;
+	std::uint8_t *yuv = host ? lazy(m_YuvOut, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
+	const YuvPlanes planes = host ? stagedPlanes(y, yuv) : callerPlanes(y);
+	if (tiles() == 1) {
+		// ONE tile: nothing to blend, and the frame is ju_process_frame's -- its encode from the state, which for the float
+		// formats (RGBPH, RGBPS, BGR96F) is clamp(s + 0.5), not P / 65535 as from a 16-bit frame (docs/output_stage.md)
+		launchEncodeState(fmt(y.format), y.colorspace, states.ptr[0], planes, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
+	} else {
+		auto *frame16 = lazy(m_Out16, ow * oh * 8).as<std::uint16_t>();
+		launchTileStitchState(frame16, static_cast<int>(ow), static_cast<int>(oh), states, tilesX(), tilesY(),
+		    static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(), *m_Stream);
+		launchEncodeFrame16(fmt(y.format), y.colorspace, frame16, planes, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
+	}
+	if (host) copyPlanes(y, yuv, false, *m_Stream);
+	++m_DeepStateFrames;
+}
+
 void TiledRuntime::stitchOut(const AnyFrame &out) {
+	if (deepFromState(out)) return stitchOutDeep(out.planes);
 	const std::size_t ow = kTileScale * m_SrcW, oh = kTileScale * m_SrcH, rowBytes = ow * 4;
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
 	auto stitch = [&](std::uint8_t *dst, std::ptrdiff_t stride) {

@@ -26,8 +26,12 @@ public:
 	// One frame, synchronously: `in` of the source size, `out` of four times that, any format, host or device.  Both are
 	// checked before anything is launched (std::invalid_argument "<who>: <why>"; every tile's state as it was).
 	void process(const AnyFrame &in, const AnyFrame &out, const char *who);
-	// zeroes every tile's recurrent state
+	// zeroes every tile's recurrent state (keeps setDeepFromState)
 	void reset();
+	// Deep outputs (docs/tiled.md "Deep outputs"): 1 = a deep format (P010, BGRX64, RGBPH, ...) is encoded from the blend of
+	// the tiles' f16 states where the model's state is the frame in float ("hbd_from_state" 1; else the setting has no
+	// effect); 0 (default) = from the blended 8-bit frame.  std::invalid_argument for another value.
+	void setDeepFromState(int on);
 
 	std::size_t srcWidth() const { return m_SrcW; }
 	std::size_t srcHeight() const { return m_SrcH; }
@@ -39,7 +43,9 @@ public:
 	int overlap() const { return m_Overlap; }
 	// the origin of tile `index` (row-major over the tile grid) in source pixels
 	void tile(int index, std::size_t *x, std::size_t *y) const;
-	// "tiles", "frames" (frames processed), "group_frames" (the members' frames that ran inside group passes, summed)
+	// "tiles", "frames" (frames processed), "group_frames" (the members' frames that ran inside group passes, summed),
+	// "deep_from_state" (the setting), "hbd_from_state" (the model's property, every tile's alike), "deep_state_frames"
+	// (frames whose output was blended from the states)
 	double stat(const std::string &key) const;
 
 private:
@@ -51,6 +57,9 @@ private:
 	};
 	Rows stageIn(const AnyFrame &in);
 	void stitchOut(const AnyFrame &out);
+	// a deep format while the setting is on and the tiles' states are their frames in float: the 16-bit path of stitchOut
+	bool deepFromState(const AnyFrame &out) const;
+	void stitchOutDeep(const YuvFrame &y);
 	DeviceBuffer &lazy(DeviceBuffer &b, std::size_t bytes);
 
 	int m_Device;
@@ -66,6 +75,11 @@ private:
 	DeviceBuffer m_XTable, m_YTable;
 	// frames that are not device BGRX: the BGRX source and result, and the planes of host frames of another format
 	DeviceBuffer m_SrcStage, m_OutStage, m_YuvIn, m_YuvOut;
+	// deep outputs from the states: the setting, the model's property, the blended 16-bit frame (8 bytes per output pixel,
+	// made at first use) and the frames that took the path
+	bool m_DeepFromState = false, m_HbdFromState = false;
+	DeviceBuffer m_Out16;
+	std::uint64_t m_DeepStateFrames = 0;
 	std::uint64_t m_Frames = 0;
 };
 

@@ -233,6 +233,7 @@ _PRODUCT_SIGS = {
                                               _P(C.c_void_p)]),
     "ju_tiled_destroy": (None, [C.c_void_p]),
     "ju_tiled_reset": (C.c_int, [C.c_void_p]),
+    "ju_tiled_set_deep_from_state": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_tiled_process": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
     "ju_tiled_process_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
     "ju_tiled_get_info": (C.c_int, [C.c_void_p, _P(JuTiledInfo)]),
@@ -298,6 +299,8 @@ _HOOK_SIGS = {
                                       _P(C.c_void_p), C.c_int]),
     "ju_debug_tile_stitch": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                        _P(C.c_void_p), C.c_int]),
+    "ju_debug_tile_stitch_state": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                                             _P(C.c_void_p), C.c_int]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_plan_report": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, _P(C.c_size_t)]),
@@ -855,8 +858,14 @@ class TiledRuntime:
         return out
 
     def reset(self) -> None:
-        """``ju_tiled_reset``: zeroes every tile's recurrent state."""
+        """``ju_tiled_reset``: zeroes every tile's recurrent state (keeps ``set_deep_from_state``)."""
         _check(self._lib, self._lib.ju_tiled_reset(self._h))
+
+    def set_deep_from_state(self, on) -> None:
+        """``ju_tiled_set_deep_from_state``: 1 = a deep output format (P010, BGRX64, RGBPH, ...) is encoded from the blend
+        of the tiles' f16 states, where the model's state is its frame in float (``stat("hbd_from_state")``); 0, the
+        default, = from the blended 8-bit frame (docs/tiled.md "Deep outputs").  Another value is refused."""
+        _check(self._lib, self._lib.ju_tiled_set_deep_from_state(self._h, int(on)))
 
     def info(self) -> dict:
         """``ju_tiled_get_info`` as a dict of the struct's fields."""
@@ -871,7 +880,8 @@ class TiledRuntime:
         return x.value, y.value
 
     def stat(self, key: str) -> float:
-        """``ju_tiled_get_stat``: "tiles", "frames", "group_frames" (summed over the tiles)."""
+        """``ju_tiled_get_stat``: "tiles", "frames", "group_frames" (summed over the tiles), "deep_from_state" (the
+        setting), "hbd_from_state" (the model's property), "deep_state_frames" (frames blended from the states)."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_tiled_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -9,9 +9,16 @@ process (the clock and the machine's other work are shared alike), after a warm-
 size and variant the median, min and max frames/s over the rounds and tiled / serial; the "group_frames" stat shows that
 each variant took its route.
 
---trace WxH runs the tiled variant alone for a `rocprofv3 --kernel-trace --stats` run; --summarize <kernel_stats.csv> WxH
-prints the two tile kernels' time per call from such a run, and the least time the bytes they must move would take at
-the copy bandwidth measured for the MI355X (6.29 TB/s, a float4 copy): their share of it."""
+--out-format names the output frames' format (default bgrx; nv12, p010, i410, bgrx64, rgbph: device planes through
+ju_tiled_process_frame).  --compare deep runs, instead of tiled / serial, two objects that both advance as group passes:
+  deep_off:  ju_tiled_set_deep_from_state 0 -- a deep format encoded from the blended 8-bit frame (the yardstick);
+  deep_on:   the setting at 1 -- from the blend of the tiles' f16 states (docs/tiled.md "Deep outputs");
+"deep_state_frames" shows that each took its route.
+
+--trace WxH runs one variant alone (--deep-from-state 0 | 1, --out-format) for a `rocprofv3 --kernel-trace --stats` run;
+--summarize <kernel_stats.csv> WxH prints the tile kernels' and the 10-bit 4:2:0 encodes' time per call from such a run,
+and the least time the bytes they must move would take at the copy bandwidth measured for the MI355X (6.29 TB/s, a
+float4 copy): their share of it."""
 
 import argparse
 import csv
@@ -26,7 +33,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 COPY_BYTES_PER_S = 6.29e12
-TILE_KERNELS = ("tile_split_kernel", "tile_stitch_kernel")
+TILE_KERNELS = ("tile_split_kernel", "tile_stitch_kernel", "tile_stitch_state_kernel", "frame16_to_yuv420p10_kernel",
+                "bgrx_to_yuv420p10_kernel")
+# what a variant is: created under JU_LOOKAHEAD=1 (no passes), and its ju_tiled_set_deep_from_state
+VARIANTS = {"tiled": (False, 0), "serial": (True, 0), "deep_off": (False, 0), "deep_on": (False, 1)}
+# output formats: (the runtime's FMT_ name, per plane (rows per output row, bytes per output pixel of a row))
+OUT_FORMATS = {"bgrx": ("FMT_BGRX", [(1, 4)]), "nv12": ("FMT_NV12", [(1, 1), (0.5, 1)]), "p010": ("FMT_P010", [(1, 2), (0.5, 2)]),
+               "i410": ("FMT_I410", [(1, 2)] * 3), "bgrx64": ("FMT_BGRX64", [(1, 8)]), "rgbph": ("FMT_RGBPH", [(1, 2)] * 3)}
 
 
 def size(text):
@@ -36,7 +49,9 @@ def size(text):
 
 def kernel_bytes(sw, sh, w, h, ov):
     """The bytes each kernel must move: the split reads the source once and writes every tile; the stitch reads every
-    output pixel once where one tile covers it -- and the seams' pixels from two or four -- and writes the frame."""
+    output pixel once where one tile covers it -- and the seams' pixels from two or four -- and writes the frame; the
+    stitch of the states the same at 8 bytes per pixel; a P010 encode reads its frame (8 or 4 bytes per pixel) and writes
+    3 bytes per pixel."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import tiled_reference as T
     nx, ny = len(T.origins(sw, w, ov)), len(T.origins(sh, h, ov))
@@ -46,7 +61,8 @@ def kernel_bytes(sw, sh, w, h, ov):
         return int((1 + (q != 0)).sum())
     split = 4 * sw * sh + 4 * w * h * nx * ny
     stitch = 4 * reads(sw, w) * reads(sh, h) + 64 * sw * sh
-    return {"tiles": [nx, ny], "tile_split_kernel": split, "tile_stitch_kernel": stitch}
+    return {"tiles": [nx, ny], "tile_split_kernel": split, "tile_stitch_kernel": stitch, "tile_stitch_state_kernel": 2 * stitch,
+            "frame16_to_yuv420p10_kernel": (8 + 3) * 16 * sw * sh, "bgrx_to_yuv420p10_kernel": (4 + 3) * 16 * sw * sh}
 
 
 def summarize(path, sw, sh, w, h, ov):
@@ -55,7 +71,7 @@ def summarize(path, sw, sh, w, h, ov):
     with open(path) as f:
         for r in csv.DictReader(f):
             for k in TILE_KERNELS:
-                if k in r["Name"]:
+                if k in r["Name"]:                                 # (no name of the list is part of another)
                     us = float(r["TotalDurationNs"]) / 1e3 / int(r["Calls"])
                     least = need[k] / COPY_BYTES_PER_S * 1e6
                     out[k] = {"calls": int(r["Calls"]), "us_per_call": round(us, 2), "bytes": need[k],
@@ -64,9 +80,9 @@ def summarize(path, sw, sh, w, h, ov):
 
 
 class Pair:
-    """The two variants for one source size, with their device frames."""
+    """The variants for one source size, with their device frames."""
 
-    def __init__(self, sw, sh, preset, dtype, ov, only=None):
+    def __init__(self, sw, sh, preset, dtype, ov, names=("tiled", "serial"), out_format="bgrx"):
         import torch
         from joshupscale_amd import model_file as M
         from joshupscale_amd import runtime as R
@@ -75,28 +91,35 @@ class Pair:
         blob = M.serialize(cfg, M.make_seeded_weights(cfg))
         dt = {"bf16": R.DTYPE_BF16, "fp16": R.DTYPE_F16, "fp8": R.DTYPE_FP8}[dtype]
         self.obj = {}
-        for name in ("tiled", "serial"):
-            if only and name != only:
-                continue
-            if name == "serial":
+        for name in names:
+            serial, deep = VARIANTS[name]
+            if serial:
                 os.environ["JU_LOOKAHEAD"] = "1"
             try:
                 self.obj[name] = R.TiledRuntime(blob, 0, dt, sw, sh, ov, hooks=False)
             finally:
                 os.environ.pop("JU_LOOKAHEAD", None)
+            self.obj[name].set_deep_from_state(deep)
         clip = M.synthetic_frames(4, sh, sw, seed=1234, kind="noise")
         self.d_in = torch.from_numpy(clip).to(dev)
-        self.d_out = torch.zeros((4 * sh, 4 * sw, 4), dtype=torch.uint8, device=dev)
+        fmt_name, planes = OUT_FORMATS[out_format]
+        self.d_out = [torch.zeros((int(4 * sh * rows), 4 * sw * width), dtype=torch.uint8, device=dev) for rows, width in planes]
         torch.cuda.synchronize()
-        self.ins = [R.JuImage(self.d_in[t].data_ptr(), R.LOC_DEVICE, 4 * sw, sw, sh) for t in range(4)]
-        self.out = R.JuImage(self.d_out.data_ptr(), R.LOC_DEVICE, 16 * sw, 4 * sw, 4 * sh)
+        self.frames = out_format != "bgrx"       # (ju_tiled_process_frame; else ju_tiled_process on two images)
+        if self.frames:
+            self.ins = [R.device_frame(R.FMT_BGRX, sw, sh, [self.d_in[t].data_ptr()]) for t in range(4)]
+            self.out = R.device_frame(getattr(R, fmt_name), 4 * sw, 4 * sh, self.d_out)
+        else:
+            self.ins = [R.JuImage(self.d_in[t].data_ptr(), R.LOC_DEVICE, 4 * sw, sw, sh) for t in range(4)]
+            self.out = R.JuImage(self.d_out[0].data_ptr(), R.LOC_DEVICE, 16 * sw, 4 * sw, 4 * sh)
         self.lib = next(iter(self.obj.values()))._lib
 
     def run(self, name, frames):
         h = self.obj[name]._h
+        call = self.lib.ju_tiled_process_frame if self.frames else self.lib.ju_tiled_process
         t0 = time.perf_counter()
         for t in range(frames):
-            if self.lib.ju_tiled_process(h, C.byref(self.ins[t % 4]), C.byref(self.out)) != 0:
+            if call(h, C.byref(self.ins[t % 4]), C.byref(self.out)) != 0:
                 raise RuntimeError(self.lib.ju_last_error().decode())
         return time.perf_counter() - t0          # (every call is synchronous)
 
@@ -114,6 +137,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=240, help="frames per variant and round")
     ap.add_argument("--warmup", type=int, default=24)
+    ap.add_argument("--out-format", default="bgrx", choices=sorted(OUT_FORMATS))
+    ap.add_argument("--compare", default="passes", choices=["passes", "deep"],
+                    help="passes: tiled against serial; deep: ju_tiled_set_deep_from_state 0 against 1")
+    ap.add_argument("--deep-from-state", type=int, default=0, choices=[0, 1], help="--trace: the setting of the one variant")
     ap.add_argument("--trace", default=None, metavar="WxH")
     ap.add_argument("--summarize", nargs=2, metavar=("CSV", "WxH"), default=None)
     args = ap.parse_args()
@@ -125,17 +152,20 @@ def main():
     import torch
     torch.zeros(1, device="cuda:0")  # (torch's HIP runtime first, as bench.py does)
     if args.trace:
-        p = Pair(*size(args.trace), args.preset, args.dtype, args.overlap, only="tiled")
-        p.run("tiled", args.warmup)
-        p.run("tiled", args.frames)
-        print(json.dumps({"trace": args.trace, "frames": args.warmup + args.frames,
-                          "group_frames": p.obj["tiled"].stat("group_frames")}))
+        name = "deep_on" if args.deep_from_state else "tiled"
+        p = Pair(*size(args.trace), args.preset, args.dtype, args.overlap, (name,), args.out_format)
+        p.run(name, args.warmup)
+        p.run(name, args.frames)
+        print(json.dumps({"trace": args.trace, "variant": name, "out_format": args.out_format, "frames": args.warmup + args.frames,
+                          "group_frames": p.obj[name].stat("group_frames"),
+                          "deep_state_frames": p.obj[name].stat("deep_state_frames")}))
         p.close()
         return
     res = {}
+    names = ("deep_off", "deep_on") if args.compare == "deep" else ("tiled", "serial")
     for text in args.sizes:
         sw, sh = size(text)
-        p = Pair(sw, sh, args.preset, args.dtype, args.overlap)
+        p = Pair(sw, sh, args.preset, args.dtype, args.overlap, names, args.out_format)
         for name in p.obj:
             p.run(name, args.warmup)
         fps = {name: [] for name in p.obj}
@@ -144,17 +174,19 @@ def main():
                 fps[name].append(args.frames / p.run(name, args.frames))
         row = {name: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
                for name, v in fps.items()}
-        row["tiled_over_serial"] = round(row["tiled"]["median"] / row["serial"]["median"], 3)
-        row["tiles"] = p.obj["tiled"].info()["tiles_x"] * p.obj["tiled"].info()["tiles_y"]
+        row[names[0] + "_over_" + names[1]] = round(row[names[0]]["median"] / row[names[1]]["median"], 3)
+        row["tiles"] = p.obj[names[0]].info()["tiles_x"] * p.obj[names[0]].info()["tiles_y"]
         row["group_frames"] = {name: o.stat("group_frames") for name, o in p.obj.items()}
+        row["deep_state_frames"] = {name: o.stat("deep_state_frames") for name, o in p.obj.items()}
         row["frames"] = {name: o.stat("frames") for name, o in p.obj.items()}
         res[text] = row
         p.close()
-    print(json.dumps({"metric": "frames/s of ju_tiled_process, device BGRX in and out", "preset": args.preset,
-                      "dtype": args.dtype, "overlap": args.overlap, "frames_per_round": args.frames, "rounds": args.rounds,
-                      "variants": {"tiled": "the tiles as group passes", "serial": "the same object created under "
-                                   "JU_LOOKAHEAD=1: every tile through ju_process, the same two kernels"},
-                      "fps": res}))
+    what = {"tiled": "the tiles as group passes", "serial": "the same object created under JU_LOOKAHEAD=1: every tile "
+            "through ju_process, the same two kernels", "deep_off": "ju_tiled_set_deep_from_state 0: a deep format from the "
+            "blended 8-bit frame", "deep_on": "ju_tiled_set_deep_from_state 1: from the blend of the tiles' f16 states"}
+    print(json.dumps({"metric": "frames/s of ju_tiled_process, device BGRX in, device " + args.out_format.upper() + " out",
+                      "preset": args.preset, "dtype": args.dtype, "overlap": args.overlap, "frames_per_round": args.frames,
+                      "rounds": args.rounds, "variants": {name: what[name] for name in names}, "fps": res}))
 
 
 if __name__ == "__main__":
