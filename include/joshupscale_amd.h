@@ -670,9 +670,27 @@ JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t
 /* "tiles"; "frames": frames processed; "group_frames": the tiles' frames that ran inside group passes, summed over the
  * tiles (tiles x frames while every pass holds at least two tiles); "deep_from_state": the setting of
  * ju_tiled_set_deep_from_state; "hbd_from_state": 1 where the model's f16 state is its frame in float (ju_get_stat's key,
- * every tile's alike); "deep_state_frames": the frames whose output was blended from the tiles' states.  An unknown key is
- * JU_ERR_INVALID_ARGUMENT. */
+ * every tile's alike); "deep_state_frames": the frames whose output was blended from the tiles' states;
+ * "scene_mode", "scene_frames", "scene_cuts": the detector below, the two counters cumulative as ju_get_stat's.  An unknown
+ * key is JU_ERR_INVALID_ARGUMENT. */
 JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value);
+/* The scene detector of a tiled stream (docs/tiled.md "Scene cuts"; no reference counterpart).  ju_set_scene_detect's
+ * definition, modes, threshold, refusals and records, with ONE detector on the tiled object that looks at the SOURCE frame:
+ * c_t is the src_width x src_height BGRX frame of call t as the split reads it (a device BGRX image in place, a host
+ * image as staged, any other format as decoded at source size), N = 3 src_width src_height.  The sum is taken inside the
+ * split's launch -- every source pixel counted by one tile, its owner -- and the decision never visits the host.  In
+ * JU_SCENE_RESET mode a cut zeroes the recurrent inputs of ALL tiles in one launch in front of the group passes: from that
+ * frame on every output byte (8-bit, and deep with ju_tiled_set_deep_from_state) equals that of an object with the
+ * detector off on which ju_tiled_reset was called before exactly that frame.  JU_SCENE_REPORT changes no byte; a flow-free
+ * model takes RESET as REPORT.  The tiles' own detectors stay off.  The same mode again changes only the threshold; a mode
+ * change, ju_tiled_create* and ju_tiled_reset start the detector (no predecessor); `step` counts from the call that turned
+ * it on and continues across ju_tiled_reset; turning the mode off frees its memory (4 src_width src_height bytes on the
+ * device, 65 records and a table of 64 entries in host-mapped memory).  A refused frame does not reach the detector.
+ * ju_tiled_get_scene_info: the last min(count, 64, steps seen) records, oldest first.  A source of exactly W x H gives the
+ * frames and records of ju_process under ju_set_scene_detect with the same arguments. */
+JU_API int ju_tiled_set_scene_detect(ju_tiled *tiled, int mode, uint32_t threshold_milli);
+JU_API int ju_tiled_get_scene_detect(const ju_tiled *tiled, int *mode, uint32_t *threshold_milli);
+JU_API int ju_tiled_get_scene_info(ju_tiled *tiled, ju_scene_info *out, int count, int *written);
 /* Not provided for a tiled object: look-ahead passes, ju_set_source_size / ju_set_output_size / the mask / the scene
  * detector, graphics resources, graph capture, the C++ plugin surface. */
 

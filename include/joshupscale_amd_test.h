@@ -270,6 +270,25 @@ JU_API int ju_debug_tile_stitch(void *dst, ptrdiff_t dst_stride, size_t src_widt
 JU_API int ju_debug_tile_stitch_state(void *dst16, size_t src_width, size_t src_height, size_t tile_width, size_t tile_height,
     int overlap, void *const *tiles, int count);
 
+/* The two kernels of a tiled stream's scene detector alone (docs/tiled.md "Scene cuts"), each ONE synchronous launch on
+ * caller-supplied device buffers, on the current device.
+ * ju_debug_tile_split_scene: tile_split_scene_kernel -- the source, the layout and the tiles of ju_debug_tile_split (the
+ * same tile bytes), and the detector's step on the source frame as op 0 of ju_debug_scene takes it: `prev`, the dense
+ * device BGRX frame of src_width x src_height kept so far (4-byte aligned), is rewritten with the source, X = 0; `state`:
+ * the 40 bytes of ju_debug_scene (8-byte aligned; zero before the first call; the accumulator and the ticket are zero
+ * again when the call returns, word 3 is the reset flag, bytes 16 .. 23 the S the next call compares with, frames and cuts
+ * behind it); has_prev 0, 1 or 3; threshold_milli 1 .. 255000; *record receives the decision (step 0) with
+ * N = 3 src_width src_height.  Refused before any device call: what ju_debug_tile_split refuses, a NULL or misaligned
+ * detector buffer, another has_prev, a threshold out of range.
+ * ju_debug_scene_clear_tiles: scene_clear_tiles_kernel -- `flag`: the device address of ONE 32-bit flag word; if it is
+ * not 0, a[i][0 .. a_bytes[i]) and b[i][0 .. b_bytes[i]) become 0 for every i < count (1 .. 64), any alignment and any
+ * sizes; if it is 0 no byte changes. */
+JU_API int ju_debug_tile_split_scene(const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height,
+    size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count, void *prev, void *state,
+    ju_scene_info *record, int has_prev, uint32_t threshold_milli, int reset_mode);
+JU_API int ju_debug_scene_clear_tiles(int count, const void *flag, void *const *a, const size_t *a_bytes, void *const *b,
+    const size_t *b_bytes);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -459,6 +459,22 @@ int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value) {
 	});
 }
 
+int ju_tiled_set_scene_detect(ju_tiled *tiled, int mode, uint32_t threshold_milli) {
+	return guarded([&] { tiledOf(tiled).setSceneDetect(mode, threshold_milli); });
+}
+
+int ju_tiled_get_scene_detect(const ju_tiled *tiled, int *mode, uint32_t *threshold_milli) {
+	return guarded([&] { tiledOf(const_cast<ju_tiled *>(tiled)).sceneDetect(mode, threshold_milli); });
+}
+
+int ju_tiled_get_scene_info(ju_tiled *tiled, ju_scene_info *out, int count, int *written) {
+	return guarded([&] {
+		if (written) *written = 0;
+		const int n = tiledOf(tiled).sceneInfo(reinterpret_cast<ju::SceneRecord *>(out), count);
+		if (written) *written = n;
+	});
+}
+
 #ifdef JU_TEST_HOOKS
 namespace {
 // what both tile hooks check before a launch: the layout's limits, the tile count, the frame's rows; then the TileSet
@@ -498,6 +514,83 @@ int ju_debug_tile_split(const void *src, ptrdiff_t src_stride, size_t src_width,
 		    src_width, &set, &nx, &ny);
 		ju::launchTileSplit(static_cast<const std::uint8_t *>(src), src_stride, set, count, static_cast<int>(tile_width),
 		    static_cast<int>(tile_height), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_tile_split_scene(const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height, size_t tile_width,
+    size_t tile_height, int overlap, void *const *tiles, int count, void *prev, void *state, ju_scene_info *record,
+    int has_prev, uint32_t threshold_milli, int reset_mode) {
+	return guarded([&] {
+		static_assert(sizeof(ju::SceneState) == 40, "the layout include/joshupscale_amd_test.h describes");
+		const std::string name = "ju_debug_tile_split_scene";
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		debugTileSet(name.c_str(), src_width, src_height, tile_width, tile_height, overlap, tiles, count, src, src_stride, src_width,
+		    &set, &nx, &ny);
+		if (prev == nullptr || state == nullptr || record == nullptr) throw std::invalid_argument(name + ": null detector buffer");
+		if (reinterpret_cast<std::uintptr_t>(src) % 4 || src_stride % 4) {
+			throw std::invalid_argument(name + ": the frame's address and stride must be multiples of 4");
+		}
+		if (reinterpret_cast<std::uintptr_t>(prev) % 4 || reinterpret_cast<std::uintptr_t>(state) % 8) {
+			throw std::invalid_argument(name + ": the kept frame must be 4-byte, the state 8-byte aligned");
+		}
+		if (has_prev != 0 && has_prev != 1 && has_prev != 3) throw std::invalid_argument(name + ": has_prev must be 0, 1 or 3");
+		const std::string problem = ju::sceneDetectProblem(reset_mode ? 2 : 1, threshold_milli);
+		if (!problem.empty()) throw std::invalid_argument(name + ": " + problem);
+		for (int k = 0; k < count; ++k) {
+			if (set.ptr[k] == nullptr || reinterpret_cast<std::uintptr_t>(set.ptr[k]) % 16) {
+				throw std::invalid_argument(name + ": tile " + std::to_string(k) + " is NULL or not 16-byte aligned");
+			}
+		}
+		const std::vector<int> endX = ju::tileOwnedEnds(ju::tileOrigins(static_cast<long>(src_width), static_cast<long>(tile_width), overlap),
+		    static_cast<long>(src_width));
+		const std::vector<int> endY = ju::tileOwnedEnds(ju::tileOrigins(static_cast<long>(src_height), static_cast<long>(tile_height), overlap),
+		    static_cast<long>(src_height));
+		ju::TileOwn own;
+		for (int k = 0; k < count; ++k) {
+			own.x1[k] = endX[static_cast<size_t>(k % nx)];
+			own.y1[k] = endY[static_cast<size_t>(k / nx)];
+		}
+		ju::PinnedWords ring(sizeof(ju::SceneRecord) * (ju::kSceneRing + 1));
+		ju::SceneSadLaunch q;
+		q.prev = static_cast<std::uint32_t *>(prev);
+		q.state = static_cast<ju::SceneState *>(state);
+		q.ring = reinterpret_cast<ju::SceneRecord *>(ring.device());
+		q.hasPrev = has_prev;
+		q.thresholdMilli = threshold_milli;
+		q.resetMode = reset_mode != 0;
+		ju::launchTileSplitScene(static_cast<const std::uint8_t *>(src), src_stride, static_cast<int>(src_width), static_cast<int>(src_height),
+		    set, own, count, static_cast<int>(tile_width), static_cast<int>(tile_height), q, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+		const auto *r = reinterpret_cast<const volatile ju::SceneRecord *>(ring.host());
+		record->step = r->step;
+		record->sad = r->sad;
+		record->score = r->score;
+		record->cut = r->cut;
+		record->reserved = 0;
+	});
+}
+
+int ju_debug_scene_clear_tiles(int count, const void *flag, void *const *a, const size_t *a_bytes, void *const *b,
+    const size_t *b_bytes) {
+	return guarded([&] {
+		const std::string name = "ju_debug_scene_clear_tiles";
+		if (count < 1 || count > ju::kTileMax) throw std::invalid_argument(name + ": count must be 1 .. 64");
+		if (flag == nullptr || a == nullptr || a_bytes == nullptr || b == nullptr || b_bytes == nullptr) {
+			throw std::invalid_argument(name + ": NULL flag or array");
+		}
+		if (reinterpret_cast<std::uintptr_t>(flag) % 4) throw std::invalid_argument(name + ": the flag word must be 4-byte aligned");
+		ju::SceneClearItem items[ju::kTileMax];
+		for (int i = 0; i < count; ++i) {
+			if ((a[i] == nullptr && a_bytes[i] != 0) || (b[i] == nullptr && b_bytes[i] != 0)) {
+				throw std::invalid_argument(name + ": tile " + std::to_string(i) + ": null buffer");
+			}
+			items[i] = ju::SceneClearItem{nullptr, a[i], a_bytes[i], b[i], b_bytes[i]};
+		}
+		ju::PinnedWords table(sizeof(ju::SceneClearTile) * ju::kTileMax);
+		ju::launchSceneClearTiles(static_cast<const unsigned *>(flag), items, count, reinterpret_cast<volatile ju::SceneClearTile *>(table.host()),
+		    reinterpret_cast<const ju::SceneClearTile *>(table.device()), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

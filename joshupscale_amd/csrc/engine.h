@@ -156,6 +156,12 @@ public:
 	// writes m_State[m_Idx ^ 1] and its call then flips m_Idx (what stageOutScaled and submitFrame read BEFORE the flip), so
 	// behind the call it is m_State[m_Idx] -- readTensor's "state".  A flow-free model: its one scratch state.
 	const void *lastState() const { return m_State[m_Config.recurrent() ? m_Idx : 0].get(); }
+	// The two buffers the NEXT frame of a recurrent model reads as its recurrent inputs -- m_State[m_Idx] and m_Packed[m_Idx],
+	// what sceneStep clears at a cut and reset() leaves zero -- as a conditional clear takes them (its flag left null).  The
+	// tiled runtime's scene detector (tiled.cpp); valid between synchronous calls.
+	SceneClearItem recurrentInputs() const {
+		return SceneClearItem{nullptr, m_State[m_Idx].get(), m_State[m_Idx].bytes(), m_Packed[m_Idx].get(), m_Packed[m_Idx].bytes()};
+	}
 	void setUseGraph(bool on) { m_UseGraph = on; }
 
 	// ---- introspection (tests, bench) ----

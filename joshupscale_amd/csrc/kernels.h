@@ -731,6 +731,16 @@ static_assert(sizeof(TileSet) <= 1024, "the by-value argument of the tile kernel
 // tile k = the source's pixels from (x[k], y[k]) on.  One launch.
 void launchTileSplit(const std::uint8_t *src, std::ptrdiff_t srcStride, const TileSet &tiles, int count, int tileW, int tileH,
     hipStream_t stream);
+// The split and the scene detector of the tiled stream in ONE launch (tile_split_scene_kernel; docs/tiled.md "Scene cuts"):
+// the tile bytes of launchTileSplit, and over the source of srcW x srcH the sum, the decision and the record of
+// launchSceneSad (SceneSadLaunch's prev .. resetMode; its src, stride and size are ignored) -- `prev` is the dense
+// srcW x srcH kept frame, rewritten with the masked source (X = 0).  Every source pixel is counted by ONE tile, its owner:
+// tile k owns [x[k], own.x1[k]) x [y[k], own.y1[k]) (tile_geometry.h tileOwnedEnds), which lies inside the tile.
+struct TileOwn {
+	int x1[kTileMax] = {}, y1[kTileMax] = {};
+};
+void launchTileSplitScene(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, int srcH, const TileSet &tiles,
+    const TileOwn &own, int count, int tileW, int tileH, const struct SceneSadLaunch &scene, hipStream_t stream);
 // The nx x ny dense tile outputs (tileOutW pixels per row each) -> BGRX rows of outW x outH (address and signed stride
 // multiples of 4; X = 0): out = (sum wy wx v + 32768) >> 16 per byte over the tiles the two tables name -- the device
 // copies of TileAxis::table for the x and the y axis, one 32-bit word per output coordinate.  One launch.
@@ -848,6 +858,19 @@ struct SceneClearItem {
 	std::size_t bBytes = 0;
 };
 void launchSceneClearItems(const SceneClearItem *items, int n, hipStream_t stream);
+// The conditional clear of all tiles of a tiled frame in ONE launch under ONE flag (scene_clear_tiles_kernel; docs/tiled.md
+// "Scene cuts"): if (*flag) items[i].a[0 .. aBytes) = items[i].b[0 .. bBytes) = 0 for every i < n (1 .. kTileMax; any
+// alignment; items[i].flag is not read).  Pointers and sizes of 64 tiles x 2 buffers do not fit kernel arguments: they go
+// into a table of kTileMax SceneClearTile in host-mapped memory (tableHost / tableDev: its two addresses), rewritten here
+// in front of the launch -- no earlier launch that reads the table may still be pending -- and read by a workgroup only
+// behind a raised flag.
+struct SceneClearTile {
+	std::uint8_t *a, *b;
+	long long aBytes, bBytes;
+	int aChunks, bChunks;
+};
+void launchSceneClearTiles(const unsigned *flag, const SceneClearItem *items, int n, volatile SceneClearTile *tableHost,
+    const SceneClearTile *tableDev, hipStream_t stream);
 // The refusals of ju_set_scene_detect as one message ("" when mode and threshold are fine): mode 0 .. 2, and while the
 // mode is not off a threshold of 1 .. 255000 thousandths of a code value
 std::string sceneDetectProblem(int mode, std::uint32_t thresholdMilli);

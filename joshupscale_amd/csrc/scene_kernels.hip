@@ -18,12 +18,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
 
 #include "kernel_common.h"
 #include "kernels.h"
+#include "scene_decision.h"
 
 namespace ju {
 
@@ -68,34 +70,8 @@ __global__ __launch_bounds__(kSadThreads) void scene_sad_kernel(const std::uint8
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	const unsigned ticket = __hip_atomic_fetch_add(&st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	if (ticket != gridDim.x - 1) return;
-	// ---- the last workgroup of the launch: the decision ----
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	// read the sum and re-arm the accumulator in one atomic; then the ticket
-	unsigned long long S = __hip_atomic_exchange(&st->acc, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	__hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	if (!(hasPrev & 1)) S = 0;  // no predecessor: what the kept frame held is not a frame of this stream
-	unsigned long long D = 0;
-	if ((hasPrev & 3) == 3) {
-		const unsigned long long before = st->prevSad;
-		const unsigned long long delta = S > before ? S - before : before - S;
-		D = S < delta ? S : delta;
-	}
-	const unsigned long long N = 3ull * static_cast<unsigned long long>(pixels);
-	const unsigned cut = 1000ull * D >= static_cast<unsigned long long>(thresholdMilli) * N ? 1u : 0u;
-	st->prevSad = S;
-	st->frames += 1;
-	st->cuts += cut;
-	st->resetNow = (cut && resetMode) ? 1u : 0u;
-	SceneRecord *r = ring + slot;
-	__hip_atomic_store(&r->step, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-	__hip_atomic_store(&r->sad, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-	__hip_atomic_store(&r->score, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-	__hip_atomic_store(&r->cut, cut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-	// the cumulative counters, behind the ring's 64 records (ju_get_stat reads them without a synchronisation)
-	SceneRecord *totals = ring + kSceneRing;
-	__hip_atomic_store(&totals->step, st->frames, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-	__hip_atomic_store(&totals->sad, st->cuts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	// ---- the last workgroup of the launch: the decision (scene_decision.h) ----
+	sceneDecide(st, ring, slot, step, hasPrev, thresholdMilli, resetMode, pixels);
 }
 
 // scene_pass_kernel: scene_sad_kernel over the N frames of a look-ahead pass.  A thread owns its four pixels across ALL
@@ -365,6 +341,23 @@ __global__ __launch_bounds__(kClearThreads) void scene_clear_items_kernel(SceneC
 	}
 }
 
+// scene_clear_tiles_kernel: the conditional clear of ALL tiles of a tiled frame (docs/tiled.md "Scene cuts") under ONE
+// flag -- the tiled stream's SceneState::resetNow.  blockIdx.y is the tile, blockIdx.x the chunk of its two buffers; every
+// workgroup loads the flag once and returns if it is 0 -- in front of any read of the table, which holds up to kTileMax
+// entries (too many for kernel arguments) and which the host rewrites in front of every launch.  The arithmetic is
+// scene_clear_items_kernel's.
+__global__ __launch_bounds__(kClearThreads) void scene_clear_tiles_kernel(const unsigned *__restrict__ flag,
+    const SceneClearTile *__restrict__ table) {
+	if (*flag == 0) return;
+	const SceneClearTile &t = table[blockIdx.y];
+	const int g = static_cast<int>(blockIdx.x), aChunks = t.aChunks;
+	if (g < aChunks) {
+		clearChunk(t.a, t.aBytes, g);
+	} else if (g - aChunks < t.bChunks) {
+		clearChunk(t.b, t.bBytes, g - aChunks);
+	}
+}
+
 int clearChunks(std::size_t bytes) {
 	// (15 bytes of head at most; one chunk more than the vectors need never hurts: its stores are bounds-checked)
 	return bytes == 0 ? 0 : static_cast<int>((bytes + static_cast<std::size_t>(kClearPerGroup) - 1) / static_cast<std::size_t>(kClearPerGroup));
@@ -507,6 +500,33 @@ void launchSceneClearItems(const SceneClearItem *items, int n, hipStream_t strea
 	hipLaunchKernelGGL(scene_clear_items_kernel, dim3(static_cast<unsigned>(widest), static_cast<unsigned>(present)), dim3(kClearThreads), 0,
 	    stream, p);
 	hipCheckLaunch("scene_clear_items");
+}
+
+void launchSceneClearTiles(const unsigned *flag, const SceneClearItem *items, int n, volatile SceneClearTile *tableHost,
+    const SceneClearTile *tableDev, hipStream_t stream) {
+	if (n < 1 || n > kTileMax || items == nullptr) throw std::invalid_argument("scene_clear_tiles: 1 .. " + std::to_string(kTileMax) + " tiles");
+	if (flag == nullptr || tableHost == nullptr || tableDev == nullptr) throw std::invalid_argument("scene_clear_tiles: null flag or table");
+	int widest = 0;
+	for (int i = 0; i < n; ++i) {
+		const SceneClearItem &it = items[i];
+		if ((it.a == nullptr && it.aBytes != 0) || (it.b == nullptr && it.bBytes != 0)) {
+			throw std::invalid_argument("scene_clear_tiles: tile " + std::to_string(i) + ": null buffer");
+		}
+		const int aChunks = clearChunks(it.aBytes), bChunks = clearChunks(it.bBytes);
+		volatile SceneClearTile &t = tableHost[i];
+		t.a = static_cast<std::uint8_t *>(it.a);
+		t.b = static_cast<std::uint8_t *>(it.b);
+		t.aBytes = static_cast<long long>(it.aBytes);
+		t.bBytes = static_cast<long long>(it.bBytes);
+		t.aChunks = aChunks;
+		t.bChunks = bChunks;
+		widest = std::max(widest, aChunks + bChunks);
+	}
+	if (widest == 0) return;
+	std::atomic_thread_fence(std::memory_order_seq_cst);  // (the table is in place before the launch is enqueued)
+	hipLaunchKernelGGL(scene_clear_tiles_kernel, dim3(static_cast<unsigned>(widest), static_cast<unsigned>(n)), dim3(kClearThreads), 0,
+	    stream, flag, tableDev);
+	hipCheckLaunch("scene_clear_tiles");
 }
 
 void launchSceneClear(const unsigned *flag, void *a,std::size_t aBytes, void *b, std::size_t bBytes, hipStream_t stream) {

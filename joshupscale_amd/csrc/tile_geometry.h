@@ -44,6 +44,16 @@ inline std::vector<int> tileOrigins(long S, long t, long ov) {
 	return x;
 }
 
+// Ownership (docs/tiled.md "Scene cuts"): what counts every source coordinate of an axis exactly once although tiles
+// overlap -- and three of them may cover one coordinate (t = 48, ov = 7, S = 90: origins 0, 21, 42).  Tile i owns
+// [x_i, x_{i+1}), the last tile up to S; the interval lies inside the tile because neighbours overlap (L_i >= 0).
+// Returns the intervals' ends, one per tile.
+inline std::vector<int> tileOwnedEnds(const std::vector<int> &origin, long S) {
+	std::vector<int> end(origin.size());
+	for (std::size_t i = 0; i < origin.size(); ++i) end[i] = i + 1 < origin.size() ? origin[i + 1] : static_cast<int>(S);
+	return end;
+}
+
 inline TileAxis tileAxis(long S, long t, long ov) {
 	TileAxis a;
 	a.origin = tileOrigins(S, t, ov);

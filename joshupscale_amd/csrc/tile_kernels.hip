@@ -7,6 +7,9 @@
 //                       address is 16-byte aligned (a tile origin that is a multiple of four pixels in an aligned
 //                       source), four 4-byte loads otherwise -- a wave reads one contiguous row segment either way --
 //                       and one 16-byte store into the dense tile (X = 0).
+//   tile_split_scene_kernel  the split with the tiled stream's scene detector in the same pass (docs/tiled.md "Scene
+//                       cuts"): the same grid and tile bytes, and per OWNED source pixel the kept frame read, summed
+//                       against and rewritten -- 2 x 4 Ws Hs bytes on top of the split's.
 //   tile_stitch_kernel  a lane takes four output pixels of one row, the groups laid so that every whole group begins
 //                       on a 16-byte boundary of the DESTINATION row (a row that starts off 16 bytes has a short head
 //                       group, written pixel by pixel, as is the tail).  Per pixel the two axis tables name the first
@@ -30,6 +33,7 @@
 
 #include "kernel_common.h"
 #include "kernels.h"
+#include "scene_decision.h"
 
 namespace ju {
 
@@ -74,6 +78,105 @@ __global__ __launch_bounds__(256) void tile_split_kernel(const std::uint8_t *__r
 	for (int i = 0; x0 + i < tileW; ++i) {  // the last group of a width that is no multiple of four
 		reinterpret_cast<unsigned *>(d)[i] = reinterpret_cast<const unsigned *>(s)[i] & kOpaqueMask;
 	}
+}
+
+// ---- the split with the tiled stream's scene detector (docs/tiled.md "Scene cuts") --------------------------------------
+// tile_split_scene_kernel: tile_split_kernel's grid and tile bytes, and in the same pass over the source scene_sad_kernel's
+// sum against the kept SOURCE-size frame.  Tiles overlap, so a source pixel is COUNTED by one tile only, its owner: tile k
+// owns [x[k], own.x1[k]) x [y[k], own.y1[k]) -- on a row a prefix of the tile's pixels, so a lane's group of four owns its
+// first m pixels, 0 <= m <= 4 (a group may straddle the edge, or be a row's tail).  For an owned pixel the lane loads the
+// kept pixel, adds |d| of B, G and R (v_sad_u8 on the three low bytes, 32-bit partials) and writes the masked pixel over
+// it: no other lane of the grid touches that kept pixel.  Then scene_sad_kernel's reduction: wave sum, workgroup sum, one
+// 64-bit atomic add per workgroup at agent scope, release, ticket; the workgroup that draws the last of sc.groups tickets
+// takes the decision (sceneDecide).  No lane returns early -- a workgroup whose lanes own nothing, or lie outside the tile,
+// still draws its ticket -- and no workgroup waits for another.
+struct TileSceneArgs {
+	std::uint32_t *prev;
+	SceneState *st;
+	SceneRecord *ring;
+	unsigned long long step;
+	long long pixels;
+	int srcW, slot, hasPrev, resetMode;
+	unsigned thresholdMilli, groups;
+};
+
+__global__ __launch_bounds__(256) void tile_split_scene_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
+    const TileSet tiles, const TileOwn own, int tileW, int tileH, const TileSceneArgs sc) {
+	__shared__ unsigned waveSums[4];
+	const int k = blockIdx.z;
+	const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4;
+	const int r = blockIdx.y * 4 + threadIdx.y;
+	unsigned partial = 0;
+	if (x0 < tileW && r < tileH) {
+		const int sx = tiles.x[k] + x0, sy = tiles.y[k] + r;
+		const std::uint8_t *s = src + static_cast<std::ptrdiff_t>(sy) * srcStride + static_cast<std::ptrdiff_t>(sx) * 4;
+		std::uint8_t *d = tiles.ptr[k] + (static_cast<std::size_t>(r) * tileW + x0) * 4;
+		std::uint32_t *kept = sc.prev + static_cast<std::size_t>(sy) * static_cast<std::size_t>(sc.srcW) + sx;
+		const int n = min(4, tileW - x0);
+		const int m = sy < own.y1[k] ? max(0, min(n, own.x1[k] - sx)) : 0;
+		if (n == 4) {
+			uint4 v;
+			if (aligned16(s)) {
+				v = *reinterpret_cast<const uint4 *>(s);
+			} else {
+				const unsigned *w = reinterpret_cast<const unsigned *>(s);
+				v = make_uint4(w[0], w[1], w[2], w[3]);
+			}
+			v.x &= kOpaqueMask;
+			v.y &= kOpaqueMask;
+			v.z &= kOpaqueMask;
+			v.w &= kOpaqueMask;
+			if (aligned16(d)) {
+				*reinterpret_cast<uint4 *>(d) = v;
+			} else {
+				unsigned *w = reinterpret_cast<unsigned *>(d);
+				w[0] = v.x;
+				w[1] = v.y;
+				w[2] = v.z;
+				w[3] = v.w;
+			}
+			if (m == 4 && aligned16(kept)) {
+				const uint4 o = *reinterpret_cast<const uint4 *>(kept);
+				*reinterpret_cast<uint4 *>(kept) = v;
+				partial = __builtin_amdgcn_sad_u8(v.x, o.x & kOpaqueMask, partial);
+				partial = __builtin_amdgcn_sad_u8(v.y, o.y & kOpaqueMask, partial);
+				partial = __builtin_amdgcn_sad_u8(v.z, o.z & kOpaqueMask, partial);
+				partial = __builtin_amdgcn_sad_u8(v.w, o.w & kOpaqueMask, partial);
+			} else {
+				const unsigned px[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					if (i < m) {
+						partial = __builtin_amdgcn_sad_u8(px[i], kept[i] & kOpaqueMask, partial);
+						kept[i] = px[i];
+					}
+				}
+			}
+		} else {
+			for (int i = 0; i < n; ++i) {  // the last group of a width that is no multiple of four
+				const unsigned p = reinterpret_cast<const unsigned *>(s)[i] & kOpaqueMask;
+				reinterpret_cast<unsigned *>(d)[i] = p;
+				if (i < m) {
+					partial = __builtin_amdgcn_sad_u8(p, kept[i] & kOpaqueMask, partial);
+					kept[i] = p;
+				}
+			}
+		}
+	}
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) partial += __shfl_down(partial, off, 64);
+	if (threadIdx.x == 0) waveSums[threadIdx.y] = partial;  // (a wave is one row of the 64 x 4 workgroup)
+	__syncthreads();
+	if (threadIdx.x != 0 || threadIdx.y != 0) return;
+	const unsigned long long groupSum = static_cast<unsigned long long>(waveSums[0]) + waveSums[1] + waveSums[2] + waveSums[3];
+	__hip_atomic_fetch_add(&sc.st->acc, groupSum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	// publish the add before the ticket (fence, then its wait, then the ticket: in that order)
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	const unsigned ticket = __hip_atomic_fetch_add(&sc.st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	if (ticket != sc.groups - 1) return;
+	// ---- the last workgroup of the launch: the decision (scene_decision.h) ----
+	sceneDecide(sc.st, sc.ring, sc.slot, sc.step, sc.hasPrev, sc.thresholdMilli, sc.resetMode, sc.pixels);
 }
 
 // pixel (X, Y) of the frame as tile k holds it
@@ -277,6 +380,44 @@ void launchTileSplit(const std::uint8_t *src, std::ptrdiff_t srcStride, const Ti
 	const dim3 grid((static_cast<unsigned>(tileW) + 255) / 256, (static_cast<unsigned>(tileH) + 3) / 4, static_cast<unsigned>(count));
 	hipLaunchKernelGGL(tile_split_kernel, grid, dim3(64, 4), 0, stream, src, srcStride, tiles, tileW, tileH);
 	hipCheckLaunch("tile_split");
+}
+
+void launchTileSplitScene(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, int srcH, const TileSet &tiles,
+    const TileOwn &own, int count, int tileW, int tileH, const SceneSadLaunch &q, hipStream_t stream) {
+	checkTileSet("tile_split_scene", tiles, count, 16);
+	checkRows("tile_split_scene", src, srcStride);
+	if (tileW < 1 || tileH < 1) throw std::invalid_argument("tile_split_scene: empty tiles");
+	if (srcW < tileW || srcH < tileH || srcW > kTileRatioMax * tileW || srcH > kTileRatioMax * tileH) {
+		throw std::invalid_argument("tile_split_scene: a source size outside the tile's .. " + std::to_string(kTileRatioMax) + " times the tile's");
+	}
+	if (q.prev == nullptr || q.state == nullptr || q.ring == nullptr) throw std::invalid_argument("tile_split_scene: null detector buffer");
+	if (reinterpret_cast<std::uintptr_t>(q.prev) % 4 || reinterpret_cast<std::uintptr_t>(q.state) % 8) {
+		throw std::invalid_argument("tile_split_scene: the kept frame must be 4-byte, the detector's state 8-byte aligned");
+	}
+	if (q.slot < 0 || q.slot >= kSceneRing) throw std::invalid_argument("tile_split_scene: ring slot outside 0 .. 63");
+	// the kept frame is written at source coordinates: every tile and its ownership rectangle inside the source
+	for (int k = 0; k < count; ++k) {
+		if (tiles.x[k] < 0 || tiles.y[k] < 0 || tiles.x[k] + tileW > srcW || tiles.y[k] + tileH > srcH || own.x1[k] < tiles.x[k] ||
+		    own.y1[k] < tiles.y[k] || own.x1[k] > tiles.x[k] + tileW || own.y1[k] > tiles.y[k] + tileH) {
+			throw std::invalid_argument("tile_split_scene: tile " + std::to_string(k) + " or what it owns lies outside the source");
+		}
+	}
+	// the split's grid; the ticket count the kernel compares with is this grid's workgroup count
+	const dim3 grid((static_cast<unsigned>(tileW) + 255) / 256, (static_cast<unsigned>(tileH) + 3) / 4, static_cast<unsigned>(count));
+	TileSceneArgs sc{};
+	sc.prev = q.prev;
+	sc.st = q.state;
+	sc.ring = q.ring;
+	sc.step = static_cast<unsigned long long>(q.step);
+	sc.pixels = static_cast<long long>(srcW) * srcH;
+	sc.srcW = srcW;
+	sc.slot = q.slot;
+	sc.hasPrev = q.hasPrev;
+	sc.resetMode = q.resetMode ? 1 : 0;
+	sc.thresholdMilli = q.thresholdMilli;
+	sc.groups = grid.x * grid.y * grid.z;
+	hipLaunchKernelGGL(tile_split_scene_kernel, grid, dim3(64, 4), 0, stream, src, srcStride, tiles, own, tileW, tileH, sc);
+	hipCheckLaunch("tile_split_scene");
 }
 
 void launchTileStitch(std::uint8_t *dst, std::ptrdiff_t dstStride, int outW, int outH, const TileSet &tiles, int nx, int ny,

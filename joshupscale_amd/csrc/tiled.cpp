@@ -26,6 +26,7 @@ TiledRuntime::TiledRuntime(int device, const void *blob, std::size_t size, int d
 	const ModelConfig config = configOf(blob, size);  // (the loader's refusals first, then the layout's: no device yet)
 	m_TileW = static_cast<std::size_t>(config.frameWidth);
 	m_TileH = static_cast<std::size_t>(config.frameHeight);
+	m_Recurrent = config.recurrent();
 	const std::string problem = tileLayoutProblem(srcWidth, srcHeight, m_TileW, m_TileH, overlap);
 	if (!problem.empty()) throw std::invalid_argument("ju_tiled_create: " + problem);
 	m_X = tileAxis(static_cast<long>(srcWidth), static_cast<long>(m_TileW), overlap);
@@ -44,6 +45,13 @@ TiledRuntime::TiledRuntime(int device, const void *blob, std::size_t size, int d
 		m_Out.ptr[k] = m_TileOut.as<std::uint8_t>() + m_TileOutBytes * static_cast<std::size_t>(k);
 		m_In.x[k] = m_Out.x[k] = m_X.origin[static_cast<std::size_t>(k % tilesX())];
 		m_In.y[k] = m_Out.y[k] = m_Y.origin[static_cast<std::size_t>(k / tilesX())];
+	}
+	// what each tile counts for the scene detector: every source pixel has one owner
+	const std::vector<int> endX = tileOwnedEnds(m_X.origin, static_cast<long>(srcWidth));
+	const std::vector<int> endY = tileOwnedEnds(m_Y.origin, static_cast<long>(srcHeight));
+	for (int k = 0; k < n; ++k) {
+		m_Own.x1[k] = endX[static_cast<std::size_t>(k % tilesX())];
+		m_Own.y1[k] = endY[static_cast<std::size_t>(k / tilesX())];
 	}
 	// both axes' tables, uploaded once
 	m_XTable = DeviceBuffer(m_X.table.size() * sizeof(TileAxisEntry));
@@ -66,6 +74,17 @@ double TiledRuntime::stat(const std::string &key) const {
 	if (key == "deep_from_state") return m_DeepFromState ? 1.0 : 0.0;
 	if (key == "hbd_from_state") return m_HbdFromState ? 1.0 : 0.0;
 	if (key == "deep_state_frames") return static_cast<double>(m_DeepStateFrames);
+	if (key == "scene_mode") return m_SceneMode;
+	if (key == "scene_frames" || key == "scene_cuts") {
+		// (the totals behind the ring: the calls are synchronous, so the last decision is in them)
+		const bool frames = key == "scene_frames";
+		std::uint64_t v = frames ? m_SceneFramesBase : m_SceneCutsBase;
+		if (m_SceneRing.host()) {
+			const auto *totals = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host()) + kSceneRing;
+			v += frames ? totals->step : totals->sad;
+		}
+		return static_cast<double>(v);
+	}
 	if (key == "group_frames") {
 		double sum = 0;
 		for (const auto &e : m_Engines) sum += e->stat("group_frames");
@@ -76,6 +95,100 @@ double TiledRuntime::stat(const std::string &key) const {
 
 void TiledRuntime::reset() {
 	for (const auto &e : m_Engines) e->reset();
+	m_SceneSeen = 0;  // the scene detector has no predecessor after a reset; its setting and its step count stay
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Scene detector (docs/tiled.md "Scene cuts"): Engine::setSceneDetect's rules on the tiled object's own memory.
+// ---------------------------------------------------------------------------------------------------------------
+void TiledRuntime::setSceneDetect(int mode, std::uint32_t thresholdMilli) {
+	const std::string problem = sceneDetectProblem(mode, thresholdMilli);
+	if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_scene_detect: " + problem);
+	DeviceGuard g(m_Device);
+	m_Stream->synchronize();
+	if (mode == m_SceneMode) {  // the same mode: the threshold alone; the detector's memory stays
+		if (mode != 0) m_SceneThreshold = thresholdMilli;
+		return;
+	}
+	if (m_SceneRing.host()) {  // the counters of the period that ends here
+		const auto *totals = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host()) + kSceneRing;
+		m_SceneFramesBase += totals->step;
+		m_SceneCutsBase += totals->sad;
+	}
+	// a start: fresh (zeroed) memory, no predecessor, step 0
+	m_ScenePrev = DeviceBuffer();
+	m_SceneDev = DeviceBuffer();
+	m_SceneRing = PinnedWords();
+	m_SceneClear = PinnedWords();
+	if (mode != 0) {
+		m_ScenePrev = DeviceBuffer(m_SrcW * m_SrcH * 4);
+		m_SceneDev = DeviceBuffer(sizeof(SceneState));
+		m_SceneRing = PinnedWords(sizeof(SceneRecord) * (kSceneRing + 1));
+		// (a flow-free model has no recurrent input to clear: JU_SCENE_RESET reports)
+		if (mode == 2 && m_Recurrent) m_SceneClear = PinnedWords(sizeof(SceneClearTile) * kTileMax);
+	}
+	m_SceneMode = mode;
+	m_SceneThreshold = mode != 0 ? thresholdMilli : 0;
+	m_SceneSeen = 0;
+	m_SceneSteps = 0;
+}
+
+void TiledRuntime::sceneDetect(int *mode, std::uint32_t *thresholdMilli) const {
+	if (mode) *mode = m_SceneMode;
+	if (thresholdMilli) *thresholdMilli = m_SceneThreshold;
+}
+
+int TiledRuntime::sceneInfo(SceneRecord *out, int count) {
+	if (count < 0 || (count > 0 && out == nullptr)) throw std::invalid_argument("ju_tiled_get_scene_info: NULL records or a negative count");
+	DeviceGuard g(m_Device);
+	m_Stream->synchronize();
+	if (m_SceneMode == 0 || m_SceneRing.host() == nullptr) return 0;
+	const std::uint64_t have = std::min<std::uint64_t>(m_SceneSteps, kSceneRing);
+	const int n = static_cast<int>(std::min<std::uint64_t>(have, static_cast<std::uint64_t>(count)));
+	const auto *ring = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host());
+	for (int k = 0; k < n; ++k) {
+		const std::uint64_t step = m_SceneSteps - static_cast<std::uint64_t>(n) + static_cast<std::uint64_t>(k);
+		const volatile SceneRecord &r = ring[step % kSceneRing];
+		out[k].step = r.step;
+		out[k].sad = r.sad;
+		out[k].score = r.score;
+		out[k].cut = r.cut;
+		out[k].reserved = 0;
+	}
+	return n;
+}
+
+// The source into the tiles' inputs.  Detector off: the split alone, as ever.  On: ONE launch splits and takes the
+// detector's step on the source frame (the split reads every source pixel anyway); in RESET mode on a recurrent model ONE
+// more, behind it on the same stream, zeroes under the flag that step left what every tile's frame is about to read --
+// m_State[m_Idx] and m_Packed[m_Idx] of each engine, the two buffers scene_clear_items_kernel covers for a group member.
+// The host reads no decision.  A group pass that has to be run again (a resident-tower report) needs nothing new: the
+// members have no detector of their own, and the pass wrote the OTHER halves only, so the cleared inputs are still in place.
+void TiledRuntime::splitIn(const Rows &src) {
+	const int n = tiles();
+	if (m_SceneMode == 0) {
+		return launchTileSplit(src.ptr, src.stride, m_In, n, static_cast<int>(m_TileW), static_cast<int>(m_TileH), *m_Stream);
+	}
+	SceneSadLaunch q;
+	q.prev = m_ScenePrev.as<std::uint32_t>();
+	q.state = m_SceneDev.as<SceneState>();
+	q.ring = reinterpret_cast<SceneRecord *>(m_SceneRing.device());
+	q.slot = static_cast<int>(m_SceneSteps % kSceneRing);
+	q.step = m_SceneSteps;
+	q.hasPrev = (m_SceneSeen >= 1 ? 1 : 0) | (m_SceneSeen >= 2 ? 2 : 0);
+	q.thresholdMilli = m_SceneThreshold;
+	q.resetMode = m_SceneMode == 2 && m_Recurrent;
+	launchTileSplitScene(src.ptr, src.stride, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), m_In, m_Own, n,
+	    static_cast<int>(m_TileW), static_cast<int>(m_TileH), q, *m_Stream);
+	if (q.resetMode) {
+		// (rewritten every frame: the half a tile reads alternates.  The last frame's clear has completed: process() is synchronous)
+		SceneClearItem items[kTileMax];
+		for (int k = 0; k < n; ++k) items[k] = m_Engines[static_cast<std::size_t>(k)]->recurrentInputs();
+		launchSceneClearTiles(&q.state->resetNow, items, n, reinterpret_cast<volatile SceneClearTile *>(m_SceneClear.host()),
+		    reinterpret_cast<const SceneClearTile *>(m_SceneClear.device()), *m_Stream);
+	}
+	++m_SceneSeen;
+	++m_SceneSteps;
 }
 
 void TiledRuntime::setDeepFromState(int on) {
@@ -207,8 +320,9 @@ void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *
 	DeviceGuard guard(m_Device);
 	const Rows src = stageIn(in);
 	const int n = tiles();
-	launchTileSplit(src.ptr, src.stride, m_In, n, static_cast<int>(m_TileW), static_cast<int>(m_TileH), *m_Stream);
-	// the group passes run on their lead's stream: the tiles' inputs are complete before the first of them starts
+	splitIn(src);
+	// the group passes run on their lead's stream: the tiles' inputs (and at a scene cut their cleared recurrent inputs)
+	// are complete before the first of them starts
 	m_Stream->synchronize();
 	std::vector<Engine *> members(static_cast<std::size_t>(n));
 	std::vector<Frame> tin(static_cast<std::size_t>(n)), tout(static_cast<std::size_t>(n));

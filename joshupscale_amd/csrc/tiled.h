@@ -32,6 +32,15 @@ public:
 	// the tiles' f16 states where the model's state is the frame in float ("hbd_from_state" 1; else the setting has no
 	// effect); 0 (default) = from the blended 8-bit frame.  std::invalid_argument for another value.
 	void setDeepFromState(int on);
+	// The scene detector of the tiled stream (docs/tiled.md "Scene cuts"): ONE detector on the source-size frame, its
+	// decision taken on the GPU inside the split's launch; mode 2 zeroes the recurrent inputs of ALL tiles at a cut, in one
+	// launch in front of the group passes.  The member engines' own detectors stay off.  std::invalid_argument with
+	// sceneDetectProblem's words; the same mode again changes only the threshold; a mode change is a detector start, and
+	// turning the mode off frees the detector's memory.  reset() keeps mode and threshold and is a detector start.
+	void setSceneDetect(int mode, std::uint32_t thresholdMilli);
+	void sceneDetect(int *mode, std::uint32_t *thresholdMilli) const;
+	// the last min(count, kSceneRing, steps seen) decisions, oldest first; returns how many
+	int sceneInfo(SceneRecord *out, int count);
 
 	std::size_t srcWidth() const { return m_SrcW; }
 	std::size_t srcHeight() const { return m_SrcH; }
@@ -45,7 +54,8 @@ public:
 	void tile(int index, std::size_t *x, std::size_t *y) const;
 	// "tiles", "frames" (frames processed), "group_frames" (the members' frames that ran inside group passes, summed),
 	// "deep_from_state" (the setting), "hbd_from_state" (the model's property, every tile's alike), "deep_state_frames"
-	// (frames whose output was blended from the states)
+	// (frames whose output was blended from the states), "scene_mode", "scene_frames" / "scene_cuts" (the detector's
+	// decisions and cuts, cumulative over its on-periods)
 	double stat(const std::string &key) const;
 
 private:
@@ -81,6 +91,20 @@ private:
 	DeviceBuffer m_Out16;
 	std::uint64_t m_DeepStateFrames = 0;
 	std::uint64_t m_Frames = 0;
+	// The scene detector, made when the mode is turned on: m_ScenePrev the kept source-size frame (4 Ws Hs bytes), m_SceneDev
+	// the SceneState, m_SceneRing kSceneRing records + the totals (host-mapped), m_SceneClear the clear's table of kTileMax
+	// SceneClearTile (host-mapped; RESET on a recurrent model only).  m_Own: what each tile counts (tileOwnedEnds).
+	// m_SceneSeen: steps since the last start (the "has predecessor" bits); m_SceneSteps: steps since the mode was turned on
+	// (the record's `step`, the ring slot).
+	void splitIn(const Rows &src);
+	bool m_Recurrent = true;
+	int m_SceneMode = 0;
+	std::uint32_t m_SceneThreshold = 0;
+	TileOwn m_Own;
+	DeviceBuffer m_ScenePrev, m_SceneDev;
+	PinnedWords m_SceneRing, m_SceneClear;
+	std::uint64_t m_SceneSeen = 0, m_SceneSteps = 0;
+	std::uint64_t m_SceneFramesBase = 0, m_SceneCutsBase = 0;  // "scene_frames" / "scene_cuts" of earlier on-periods
 };
 
 }  // namespace ju

@@ -239,6 +239,9 @@ _PRODUCT_SIGS = {
     "ju_tiled_get_info": (C.c_int, [C.c_void_p, _P(JuTiledInfo)]),
     "ju_tiled_get_tile": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_tiled_get_stat": (C.c_int, [C.c_void_p, C.c_char_p, _P(C.c_double)]),
+    "ju_tiled_set_scene_detect": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "ju_tiled_get_scene_detect": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_uint32)]),
+    "ju_tiled_get_scene_info": (C.c_int, [C.c_void_p, _P(JuSceneInfo), C.c_int, _P(C.c_int)]),
     "ju_last_error": (C.c_char_p, []),
     "ju_set_log_callback": (None, [LOG_CALLBACK, C.c_void_p]),
     "ju_get_gl_device_index": (C.c_int, [_P(C.c_int)]),
@@ -301,6 +304,11 @@ _HOOK_SIGS = {
                                        _P(C.c_void_p), C.c_int]),
     "ju_debug_tile_stitch_state": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                              _P(C.c_void_p), C.c_int]),
+    "ju_debug_tile_split_scene": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                                            _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, _P(JuSceneInfo), C.c_int,
+                                            C.c_uint32, C.c_int]),
+    "ju_debug_scene_clear_tiles": (C.c_int, [C.c_int, C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p),
+                                             _P(C.c_size_t)]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_plan_report": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, _P(C.c_size_t)]),
@@ -867,6 +875,32 @@ class TiledRuntime:
         default, = from the blended 8-bit frame (docs/tiled.md "Deep outputs").  Another value is refused."""
         _check(self._lib, self._lib.ju_tiled_set_deep_from_state(self._h, int(on)))
 
+    # -- the scene detector of the tiled stream (docs/tiled.md "Scene cuts") ----------
+    def set_scene_detect(self, mode: int, threshold_milli: int = 10000) -> None:
+        """``ju_tiled_set_scene_detect``: ``SCENE_OFF``, ``SCENE_REPORT`` (record cuts) or ``SCENE_RESET`` (and restart
+        every tile's recurrence at them, on the GPU).  ONE detector on the source frame; ``threshold_milli`` as for
+        :meth:`Runtime.set_scene_detect`.  An unknown mode or a threshold out of range raises
+        :class:`JoshUpscaleError` with the C layer's message."""
+        mode, threshold_milli = int(mode), int(threshold_milli)
+        if not 0 <= threshold_milli < 2 ** 32:
+            raise ValueError("threshold_milli must fit 32 bits")
+        _check(self._lib, self._lib.ju_tiled_set_scene_detect(self._h, mode, threshold_milli))
+
+    def get_scene_detect(self) -> Tuple[int, int]:
+        """``ju_tiled_get_scene_detect``: ``(mode, threshold_milli)``; the threshold is 0 while the mode is off."""
+        mode, thr = C.c_int(), C.c_uint32()
+        _check(self._lib, self._lib.ju_tiled_get_scene_detect(self._h, C.byref(mode), C.byref(thr)))
+        return mode.value, thr.value
+
+    def scene_info(self, count: int = SCENE_RING) -> list:
+        """``ju_tiled_get_scene_info``: the most recent ``min(count, 64, steps seen)`` decisions of the tiled stream,
+        oldest first, as dicts ``{"step", "sad", "score", "cut"}``."""
+        count = max(0, int(count))
+        recs = (JuSceneInfo * max(count, 1))()
+        got = C.c_int()
+        _check(self._lib, self._lib.ju_tiled_get_scene_info(self._h, recs, count, C.byref(got)))
+        return [{"step": r.step, "sad": r.sad, "score": r.score, "cut": int(r.cut)} for r in recs[:got.value]]
+
     def info(self) -> dict:
         """``ju_tiled_get_info`` as a dict of the struct's fields."""
         i = JuTiledInfo()
@@ -881,7 +915,8 @@ class TiledRuntime:
 
     def stat(self, key: str) -> float:
         """``ju_tiled_get_stat``: "tiles", "frames", "group_frames" (summed over the tiles), "deep_from_state" (the
-        setting), "hbd_from_state" (the model's property), "deep_state_frames" (frames blended from the states)."""
+        setting), "hbd_from_state" (the model's property), "deep_state_frames" (frames blended from the states),
+        "scene_mode", "scene_frames" and "scene_cuts" (the tiled stream's detector; the counters are cumulative)."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_tiled_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
