@@ -755,6 +755,7 @@ int ju_debug_set(const char *key, int value) {
 		if (k == "tower_variant") ju::setTowerVariant(value);
 		else if (k == "resident_fault") ju::setResidentFault(value);
 		else if (k == "tower_fast") ju::setResidentTowerFast(value);
+		else if (k == "tower_unit_rows") ju::setResidentTowerUnitRows(value);
 		else if (k == "res_block_plain") ju::setResBlockPlain(value);
 		else if (k == "fp8_block_form") ju::setFp8BlockForm(value);
 		else if (k == "pass_rerun") ju::setPassRerun(value);

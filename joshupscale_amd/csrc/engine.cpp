@@ -1847,6 +1847,10 @@ double Engine::stat(const std::string &key) const {
 		return (m_Resident && !m_Fp8Tower && residentTowerFast() && !m_Calibrate &&
 		        residentTowerFastGeometry(m_Config.frameHeight, m_Config.frameWidth, m_ResGX, m_ResGY, m_ResRH)) ? 1.0 : 0.0;
 	}
+	if (key == "tower_unit_rows") {  // rows of the resident tower's work unit: 4 = the fast schedule's row-quad form (ReLU towers), else 2
+		const bool fast = stat("tower_fast") != 0.0;
+		return (fast && m_Config.genActivation != 1) ? static_cast<double>(residentTowerUnitRows(m_Config.frameHeight, m_Config.frameWidth, m_ResGX, m_ResGY, m_ResRH)) : 2.0;
+	}
 	if (key == "fallbacks") return static_cast<double>(m_Fallbacks);
 	if (key == "lookahead_frames") return static_cast<double>(m_BatchFrames);  // frames that went through look-ahead passes
 	if (key == "lookahead_host_frames") return static_cast<double>(m_BatchHostFrames);  // ... of them with a host image

@@ -333,6 +333,10 @@ bool resBlockPlain();
 void setResidentTowerFast(int on);  // tests / JU_TOWER_FAST=0: the general schedule everywhere
 void setFp8BlockForm(int form);     // tests / JU_FP8_BLOCK: res_block_fp8_kernel as 0 = by geometry, 1 = solo, 2 = duo
 bool residentTowerFast();
+// rows of the fast schedule's work unit for this geometry: 4 (row quads: every region 32 x 16 or 32 x 14) or 2 (row
+// pairs); ReLU towers only -- LeakyReLU towers always run pairs
+int residentTowerUnitRows(int H, int W, int GX, int GY, int RH);
+void setResidentTowerUnitRows(int rows);  // tests: 2 = row pairs everywhere, anything else the default
 inline std::size_t residentCounterBytes(int GX, int GY) {
 	return (static_cast<std::size_t>(GX) * GY * 2 * sizeof(unsigned) + 63) / 64 * 64;
 }

@@ -454,6 +454,11 @@ __host__ __device__ inline bool residentFastShape(int rhv, int rwv) {
 	return true;
 }
 
+// The row-quad form of the fast schedule (tower_resident_kernel, UROWS == 4): each quad parity needs one interior quad
+// and one edge unit -- 16-row regions (quads 0 | 2 and 1 | 3) and 14-row ones (the last unit a row pair), full width.
+// A 12-row region has no interior quad for parity 0: frames with one keep the pair form.
+__host__ __device__ inline bool residentFastQuadShape(int rhv, int rwv) { return rwv == 32 && (rhv == 16 || rhv == 14); }
+
 struct ResidentParams {
 	const void *in;           // first layer's input, addressed at image pixel (0,0)
 	int inPitch;              // its row pitch in pixels (dense W, or towerPitch(W))
@@ -499,9 +504,20 @@ typedef __attribute__((address_space(1))) unsigned gu32;
 // holds ONLY that schedule: epilogues behind the next unit's MFMAs, edges published from the
 // epilogues.  The general schedule below it serves every other geometry (and LeakyReLU models,
 // calibration, the ablation variants) and is what it was.
-template <typename T, int VARIANT, bool HEAD, bool TAIL = false, bool LEAKY = false, bool FAST = false>
+// UROWS: the fast schedule's work unit, 2 = a row pair, 4 = a row quad (residentFastQuadShape: ReLU towers whose regions
+// are all 32 wide and 16 or 14 rows high).  Per macro-step six row fragments feed 24 MFMAs (0.5 LDS reads per MFMA against
+// 0.67) and a wave starts three units per layer instead of five (tools/probes/mfma_shape.hip, "4-row, epilogue filler").
+// A wave = {cout half} x {quad parity}: parity 0 owns rows 0-3 and 8-11, parity 1 rows 4-7 and 12-15.  The INTERIOR quad
+// (rows 8-11 / 4-7: no halo row) is the pre-run, its two halves around the halo loads; it finishes behind the sweep, and
+// the EDGE quad runs whole behind it, carrying the interior quad's epilogue and the next layer's weight stream; its own
+// epilogue is the layer's one exposed epilogue.  In a 14-row region the parity-1 wave's edge unit is the row pair 12-13
+// (both epilogues exposed there: such regions do less work and never set the pace).  Every accumulator sees the same
+// sequence of MFMAs as in the pair form, so the bytes are equal (tests/test_gpu_tower_units.py).
+template <typename T, int VARIANT, bool HEAD, bool TAIL = false, bool LEAKY = false, bool FAST = false, int UROWS = 2>
 __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p) {
 	static_assert(!FAST || ((VARIANT == 0 || VARIANT == 4) && (JU_FAST_PRERUN == 2 || JU_FAST_PRERUN == 3)), "the fast schedule is built for the product only");
+	static_assert(UROWS == 2 || (UROWS == 4 && FAST && !LEAKY && JU_TOWER_M16 && JU_FAST_PRERUN == 2 && JU_PREBEFORE == 1),
+	    "row quads are a form of the ReLU fast schedule in the 16x16x32 shape");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	// (variants 1 .. 3 are bit masks; 4, 5, 8 are NOT -- round 2 tested `VARIANT & 1` and ran the
 	// calibration build, variant 5, without the halo exchange: its maxima drifted by up to 10 %)
@@ -704,7 +720,8 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 	constexpr int kPreBefore = kPlain ? 0 : JU_PREBEFORE;  // how many of them run BEFORE the halo loads are issued
 	TowerAcc accPre0[2], accPre1[2], accPre2[2];  // (separate objects: an array indexed by the slot would live in scratch)
 	static_assert(kPreRun >= 0 && kPreRun <= 3, "at most three interior units per wave");
-	Vec8<T> fb[2][4];
+	TowerAcc accQ0[4], accQ1[4];  // UROWS == 4: the interior quad's and the edge quad's accumulators
+	Vec8<T> fb[2][UROWS + 2];
 	// (The reads are asm so that they can be issued a macro-step ahead with counted waits.  To the
 	// compiler an asm output is defined when the statement ends -- it may copy the register before
 	// the data has landed -- so a fragment's live range is kept to the one macro-step between its
@@ -721,7 +738,11 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 			if (j == 0) asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(fb[set][0]) : "v"(a));
 			else if (j == 1) asm volatile("ds_read_b128 %0, %1 offset:6400" : "=v"(fb[set][1]) : "v"(a));
 			else if (j == 2) asm volatile("ds_read_b128 %0, %1 offset:10752" : "=v"(fb[set][2]) : "v"(a));
-			else asm volatile("ds_read_b128 %0, %1 offset:15104" : "=v"(fb[set][3]) : "v"(a));
+			else if (j == 3) asm volatile("ds_read_b128 %0, %1 offset:15104" : "=v"(fb[set][3]) : "v"(a));
+			else if constexpr (UROWS == 4) {
+				if (j == 4) asm volatile("ds_read_b128 %0, %1 offset:19456" : "=v"(fb[set][4]) : "v"(a));
+				else asm volatile("ds_read_b128 %0, %1 offset:23808" : "=v"(fb[set][5]) : "v"(a));
+			}
 			return;
 		}
 #else
@@ -731,20 +752,27 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 		if (j == 0) asm volatile("ds_read_b128 %0, %1" : "=v"(fb[set][0]) : "v"(a));
 		else if (j == 1) asm volatile("ds_read_b128 %0, %1 offset:4352" : "=v"(fb[set][1]) : "v"(a));
 		else if (j == 2) asm volatile("ds_read_b128 %0, %1 offset:8704" : "=v"(fb[set][2]) : "v"(a));
-		else asm volatile("ds_read_b128 %0, %1 offset:13056" : "=v"(fb[set][3]) : "v"(a));
+		else if (j == 3) asm volatile("ds_read_b128 %0, %1 offset:13056" : "=v"(fb[set][3]) : "v"(a));
+		else if constexpr (UROWS == 4) {
+			if (j == 4) asm volatile("ds_read_b128 %0, %1 offset:17408" : "=v"(fb[set][4]) : "v"(a));
+			else asm volatile("ds_read_b128 %0, %1 offset:21760" : "=v"(fb[set][5]) : "v"(a));
+		}
 	};
 	// rows of this wave: full pairs u = rp, rp+2, ... and, for an odd region height, the
 	// last row as a single-row unit on the wave group with fewer pairs
 	const int np2 = rhv >> 1;
 	const bool mySingle = (rhv & 1) && rp == (np2 & 1);
 	// pre-run units: preFirst, preFirst + 2, ... (pairs whose four input rows are interior)
-	const int preFirst = rp ? 1 : 2;
+	// (UROWS == 4: units are still numbered as row pairs -- a quad is named by its first pair; the interior quad is pair
+	// 4 (parity 0: rows 8-11) or pair 2 (parity 1: rows 4-7), the one pre-run unit, in two halves)
+	const int preFirst = UROWS == 4 ? (rp ? 2 : 4) : (rp ? 1 : 2);
 	int nPre = 0;
 #pragma unroll
 	for (int k = 0; k < kPreRun; ++k) {
 		const int u = preFirst + 2 * k;
 		if (u < np2 && 2 * u + 3 <= rhv) nPre = k + 1;
 	}
+	if constexpr (UROWS == 4) nPre = 1;
 	if constexpr (FAST && kPreRun == 3) {
 		// (one whole unit stays: the next layer's weights stream behind it)
 		const int mine = (np2 - rp + 1) >> 1;
@@ -759,9 +787,9 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 		return v < np2 ? v : -1;
 	};
 	const int firstWhole = isPre(rp) ? (preEnd < np2 ? preEnd : -1) : (rp < np2 ? rp : -1);
-	const bool streamsInUnit = (firstWhole >= 0 || mySingle) && !kNoMfma && !kPlain;  // the next layer's weights stream behind the last unit
+	const bool streamsInUnit = UROWS == 4 || ((firstWhole >= 0 || mySingle) && !kNoMfma && !kPlain);  // the next layer's weights stream behind the last unit
 	constexpr bool kDefer = FAST;
-	const bool deferShape = residentFastShape(rhv, rwv);  // (region-uniform: a function of the region's size only)
+	const bool deferShape = UROWS == 4 ? residentFastQuadShape(rhv, rwv) : residentFastShape(rhv, rwv);  // (region-uniform: a function of the region's size only)
 	if constexpr (FAST) {
 		if (!deferShape) {  // (the host chose the wrong instantiation: fail loudly, never compute something else)
 			if (tid == 0) __hip_atomic_store((gu32 *)p.error, 0x6f0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -796,7 +824,7 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 	// sparse write-through store costs ~90 cycles of issue wherever it stands
 	// (tools/probes/mfma_valu_overlap.hip: the chip accepts ~13 such instructions per clock), and the
 	// epilogues need 36 per wave and layer where the cooperative publish needs 4 dense ones.)
-	Vec4<T> rvNext[2][4];  // residual of the unit whose epilogue is pending
+	Vec4<T> rvNext[UROWS][4];  // residual of the unit whose epilogue is pending
 	auto epiValue = [&](auto resTag, const TowerAcc &a, const int g, const Vec4<T> &rv, float(&v)[4]) __attribute__((always_inline)) {
 #pragma unroll
 		for (int i = 0; i < 4; ++i) v[i] = accElem(a, 4 * g + i);
@@ -827,10 +855,12 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 			    reluPacked<T>(pack4<T>(v[0], v[1], v[2], v[3]));
 		}
 	};
-	auto unitSeg = [&](auto rowsTag, auto kindTag, auto resTag, auto inTag, auto outTag, TowerAcc(&acc)[2],
+	// Row quads (ROWS == 4): KIND 0 / 3 are the pre-run's two halves (positions 0..1 and 2..3); nextPos >= 0 names the
+	// position the successor is primed at (default: 4 for a finish, 0 otherwise) and nextNR its fragment count.
+	auto unitSeg = [&](auto rowsTag, auto kindTag, auto resTag, auto inTag, auto outTag, auto &acc,
 	                   const int layer, const int unit, const bool primed, const int nextUnit,
-	                   const bool nextFinish, auto streamTag, auto defTag, TowerAcc(&dacc)[2], const int dunit,
-	                   auto epiTag) __attribute__((always_inline)) {
+	                   const bool nextFinish, auto streamTag, auto defTag, auto &dacc, const int dunit,
+	                   auto epiTag, const int nextPos = -1, const int nextNR = 4) __attribute__((always_inline)) {
 		constexpr bool streamNext = decltype(streamTag)::value;  // (compile-time: no branch per macro-step)
 		constexpr bool DEF = decltype(defTag)::value;   // (a deferring segment is always primed and deferred units are row pairs)
 		constexpr bool EPI = decltype(epiTag)::value;
@@ -839,13 +869,15 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 		constexpr bool residual = decltype(resTag)::value;
 		constexpr int inOff = decltype(inTag)::value;
 		constexpr int outOff = decltype(outTag)::value;
-		constexpr int P0 = KIND == 1 ? 4 : 0;
-		constexpr int P1 = KIND == 0 ? 4 : 12;
+		constexpr bool kPreKind = KIND == 0 || KIND == 3;
+		constexpr int P0 = KIND == 1 ? 4 : KIND == 3 ? 2 : 0;
+		constexpr int P1 = KIND == 0 ? (ROWS == 4 ? 2 : 4) : KIND == 3 ? 4 : 12;
+		static_assert(KIND != 3 || ROWS == 4, "only a quad's pre-run is split");
 		const u64 tu0 = stamp();
 		constexpr int NR = ROWS + 2;      // input rows / fragment reads per macro-step
 		constexpr int NM = 3 * ROWS;      // MFMAs per macro-step
 		const int ra = 1 + 2 * unit;      // first output row (buffer row index)
-		if constexpr (KIND != 1 && kNoMfma) {
+		if constexpr ((KIND == 0 || KIND == 2) && kNoMfma) {
 #pragma unroll
 			for (int r = 0; r < ROWS; ++r) acc[r] = biasVec;
 		}
@@ -857,11 +889,12 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 		// A unit whose epilogue is deferred (EPI false) fetches its residual behind the MFMAs of its own
 		// last macro-step into rvNext (plain C++ loads: the compiler's own waits count only what it
 		// knows of and are therefore never too lenient); its successor (DEF) consumes them.
-		constexpr bool kFetchRes = !EPI && residual && KIND != 0;
+		constexpr bool kFetchRes = !EPI && residual && !kPreKind;
 		const int dra = 1 + 2 * dunit;
 		// (by value, constant indices: an element read of `dacc[j >> 2]` is a dynamic index until the loops
 		// are unrolled, by when the loads had been merged into partial vectors and the array stayed in scratch)
 		const TowerAcc dacc0 = dacc[0], dacc1 = dacc[1];
+		const TowerAcc dacc2 = dacc[ROWS == 4 ? 2 : 0], dacc3 = dacc[ROWS == 4 ? 3 : 1];  // (a quad's deferred epilogue: four rows)
 		float dv[4];
 		unsigned dlo = 0, dhi = 0;
 		// The deferred epilogue's slot behind MFMA group k of macro-step `pos` (DEF segments): the previous unit's group
@@ -876,40 +909,45 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 						// MFMA 0..3 value i = accumulator (+ residual), 4 convert, 5 ReLU + write
 						const int j = pos - P0;
 						if (j < 8) {
-							const int r = j >> 2, g = j & 3;
-							if (k < 5 && part == 1) {
-							} else if (k < 4) {
-								dv[k] = accElem(r ? dacc1 : dacc0, 4 * g + k);
-								if constexpr (residual) {
-									dv[k] += static_cast<float>(rvNext[r][g][k]);
-									asm volatile("" : "+v"(dv[k]));  // (keeps the four adds scalar and in their slots)
-								}
-								if constexpr (LEAKY) {
-									// max(x, slope x), slope in [0, 1]; the instruction itself (fmaxf() canonicalises
-									// both operands first: two more instructions in a slot that has room for three)
-									const float t = dv[k] * p.slope;
-									asm volatile("v_max_f32 %0, %1, %2" : "=v"(dv[k]) : "v"(dv[k]), "v"(t));
-								}
-							} else if (k == 4) {
-								const Vec4<T> pk = pack4<T>(dv[0], dv[1], dv[2], dv[3]);
-								typedef unsigned u32x2d __attribute__((ext_vector_type(2)));
-								const u32x2d w = __builtin_bit_cast(u32x2d, pk);
-								dlo = w[0];
-								dhi = w[1];
-								asm volatile("" : "+v"(dlo), "+v"(dhi));
-							} else {
-								typedef unsigned u32x2d __attribute__((ext_vector_type(2)));
-								if (part != 1) {
+							// A quad's 16 groups go two per macro-step: MFMA groups 0..5 carry group 2j, 6..11 group 2j + 1.  The
+							// first one's LDS write waits for MFMA group 6: behind the six fragment reads of the next step (one
+							// behind each of groups 0..5), so the counted waits know where it stands in the LDS queue.
+							const int kk = ROWS == 4 ? k % 6 : k;
+							const int gi = ROWS == 4 ? 2 * j + k / 6 : j;
+							const int r = gi >> 2, g = gi & 3;
+							typedef unsigned u32x2d __attribute__((ext_vector_type(2)));
+							if (part != 1) {
+								if (kk < 4) {
+									dv[kk] = accElem(r == 0 ? dacc0 : r == 1 ? dacc1 : r == 2 ? dacc2 : dacc3, 4 * g + kk);
+									if constexpr (residual) {
+										dv[kk] += static_cast<float>(rvNext[r][g][kk]);
+										asm volatile("" : "+v"(dv[kk]));  // (keeps the four adds scalar and in their slots)
+									}
+									if constexpr (LEAKY) {
+										// max(x, slope x), slope in [0, 1]; the instruction itself (fmaxf() canonicalises
+										// both operands first: two more instructions in a slot that has room for three)
+										const float t = dv[kk] * p.slope;
+										asm volatile("v_max_f32 %0, %1, %2" : "=v"(dv[kk]) : "v"(dv[kk]), "v"(t));
+									}
+								} else if (kk == 4) {
+									const Vec4<T> pk = pack4<T>(dv[0], dv[1], dv[2], dv[3]);
+									const u32x2d w = __builtin_bit_cast(u32x2d, pk);
+									dlo = w[0];
+									dhi = w[1];
+									asm volatile("" : "+v"(dlo), "+v"(dhi));
+								} else {
 									const Vec4<T> pk = __builtin_bit_cast(Vec4<T>, u32x2d{dlo, dhi});
 									const u32x2d w = __builtin_bit_cast(u32x2d, LEAKY ? pk : reluPacked<T>(pk));
 									dlo = w[0];
 									dhi = w[1];
 									if (part == 0) asm volatile("" : "+v"(dlo), "+v"(dhi));
 								}
-								if (part != 0) {
-									const Vec4<T> o = __builtin_bit_cast(Vec4<T>, u32x2d{dlo, dhi});
-									if (groupValid(g)) *reinterpret_cast<Vec4<T> *>(smem + outOff + (dra + r) * kResRowBytes + outsw[g]) = o;
-								}
+							}
+							if (part != 0 && (ROWS == 4 ? (k == 6 || k == 11) : k == 5)) {
+								const int wi = (ROWS == 4 && k == 6) ? gi - 1 : gi;  // (the group dlo / dhi hold)
+								const int wr = wi >> 2, wg = wi & 3;
+								const Vec4<T> o = __builtin_bit_cast(Vec4<T>, u32x2d{dlo, dhi});
+								if (groupValid(wg)) *reinterpret_cast<Vec4<T> *>(smem + outOff + (dra + wr) * kResRowBytes + outsw[wg]) = o;
 							}
 						}
 					}
@@ -932,17 +970,20 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 				for (int k = 0; k < NM; ++k) {
 					// MFMA k = (dy, r): ROWS=2 -> (k>>1, k&1); ROWS=1 -> (k, 0); it needs
 					// fragment r+dy, fragments are read (and return) in order 0..NR-1
-					const int dy = ROWS == 2 ? (k >> 1) : k;
-					const int r = ROWS == 2 ? (k & 1) : 0;
+					// (ROWS=4 -> (k>>2, k&3): the first use of fragment r+dy is at k = 0..3, 7, 11)
+					const int dy = k / ROWS;
+					const int r = k % ROWS;
 					const int need = r + dy;
-					const bool fresh = ROWS == 2 ? (k == 0 || k == 1 || k == 3 || k == 5) : true;
+					const bool fresh = dy == 0 || r == ROWS - 1;
 					if (fresh) {
 						// outstanding allowed = younger reads of this step + next step's issued so far
 						const int issuedNext = more ? (k < NR ? k : NR) : 0;
 						// deferred epilogue: the residual reads sit behind the first step's fragments, a
-						// group's LDS write behind the fragments of the step after it
-						const int younger = (DEF && pos > P0 && pos - P0 <= 8 ? 1 : 0) +
-						                    (kFetchRes && pos == P1 - 1 ? 2 * (k < 4 ? k : 4) : 0);
+						// group's LDS write behind the fragments of the step after it (a quad: both writes of the previous
+						// step, and this step's first one once MFMA group 6 has issued it)
+						const bool prevDef = DEF && pos > P0 && pos - P0 <= 8;
+						const int younger = (ROWS == 4 ? (prevDef ? 2 : 0) + (DEF && pos - P0 < 8 && k >= 7 ? 1 : 0) : (prevDef ? 1 : 0)) +
+						                    (kFetchRes && pos == P1 - 1 ? 2 * (k < 2 * ROWS ? k : 2 * ROWS) : 0);
 						const int allowed = (NR - 1 - need) + issuedNext + younger;
 						if (allowed >= 12) asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
 						else if (allowed == 11) asm volatile("s_waitcnt lgkmcnt(11)" ::: "memory");
@@ -964,7 +1005,7 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 						// the same 12 macro-steps as (dx, ks32, pixel half): two 16x16x32 MFMAs (cout halves) on
 						// quarters (ph, c16) of the row's accumulator; A fragment index ks = ks32 * 2 + c16
 						const int ks32 = (m >> 1) & 1, ph = m & 1;
-						const bool first = KIND != 1 && (pos == P0 || pos == P0 + 1) && dy == 0;
+						const bool first = pos < 2 && dy == 0;  // (positions 0 and 1: a pre-run's or a whole unit's first two steps)
 #pragma unroll
 						for (int c16 = 0; c16 < 2; ++c16) {
 							const int kf = ks32 * 2 + c16, sl = ph * 2 + c16;
@@ -982,8 +1023,8 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 							// The wave's LAST unit of the layer, second pixel half of (dx, ks32): vertical tap dy's two fragments
 							// have fed their last MFMA (group k = 2 dy + 1) -- the next layer's go into the same registers now,
 							// two loads behind this group instead of six in a row behind the step
-							if (streamNext && (m & 1) && (ROWS == 2 ? (k & 1) : true)) {
-								const int sdy = ROWS == 2 ? (k >> 1) : k;
+							if (streamNext && (m & 1) && r == ROWS - 1) {
+								const int sdy = dy;
 #pragma unroll
 								for (int c16 = 0; c16 < 2; ++c16) {
 									const int kf = ks32 * 2 + c16;
@@ -1004,7 +1045,7 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 					defSlot(pos, k);
 #endif
 					if constexpr (kFetchRes) {
-						if (pos == P1 - 1 && k < 4) {
+						if (pos == P1 - 1 && k < 2 * ROWS) {
 							const int ra0 = 1 + 2 * unit;
 							rvNext[(2 * k) >> 2][(2 * k) & 3] = *reinterpret_cast<const Vec4<T> *>(
 							    smem + outOff + (ra0 + ((2 * k) >> 2)) * kResRowBytes + outsw[(2 * k) & 3]);
@@ -1045,7 +1086,13 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 			if (nextUnit >= 0) {
 				const unsigned na = ldsBase + inOff + (2 * nextUnit) * kResRowBytes;
 				const bool nextSingle = (nextUnit == np2);
-				if (nextFinish) {
+				if constexpr (UROWS == 4) {
+					const int npos = nextPos >= 0 ? nextPos : (nextFinish ? 4 : 0);
+#pragma unroll
+					for (int j = 0; j < 6; ++j) {
+						if (j < nextNR) issue(na, kOrder[npos], 0, j);
+					}
+				} else if (nextFinish) {
 #pragma unroll
 					for (int j = 0; j < 4; ++j) issue(na, kOrder[4], 0, j);
 				} else {
@@ -1057,7 +1104,7 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 			}
 		}
 		const u64 tu1 = stamp();
-		if constexpr (KIND == 0) prof[7] += tu1 - tu0;
+		if constexpr (kPreKind) prof[7] += tu1 - tu0;
 #ifdef JU_TOWER_SEGPROF  // developer builds: the finish segments one by one (slots 3..6 carry them instead of their usual sums)
 		else if constexpr (KIND == 1 && !DEF) prof[3] += tu1 - tu0;
 		else if constexpr (KIND == 1 && DEF) prof[4] += tu1 - tu0;
@@ -1066,7 +1113,7 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 #else
 		else prof[5] += tu1 - tu0;
 #endif
-		if constexpr (KIND != 0 && EPI) {
+		if constexpr (!kPreKind && EPI) {
 			// ---- epilogue: (+residual) ReLU, 16-bit, into the output buffer interior ----
 			// (row ra + r <= rhv always: units are whole pairs, or the odd last row)
 			{
@@ -1108,11 +1155,25 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 	using KPre = std::integral_constant<int, 0>;
 	using KFin = std::integral_constant<int, 1>;
 	using KWhole = std::integral_constant<int, 2>;
+	using R4 = std::integral_constant<int, 4>;
+	using KPre2 = std::integral_constant<int, 3>;
 	// the halo-independent third of up to kPreRun units of `layer` (input buffer inTag)
 	// slots [LO, HI) of the pre-run
 	auto preRun = [&](auto inTag, auto outTag, auto loTag, auto hiTag, const int layer, const bool primedFirst)
 	                  __attribute__((always_inline)) {
 		constexpr int LO = decltype(loTag)::value, HI = decltype(hiTag)::value;
+		if constexpr (UROWS == 4) {
+			// the interior quad's dx = 1 steps, as many MFMAs as two pairs': slot 0 = positions 0..1 (it primes position 2),
+			// slot 1 = positions 2..3
+			if constexpr (LO <= 0 && 0 < HI) {
+				unitSeg(R4{}, KPre{}, std::false_type{}, inTag, outTag, accQ0, layer, preFirst, primedFirst, preFirst, false,
+				    std::false_type{}, std::false_type{}, accQ0, 0, std::true_type{}, 2, 6);
+			}
+			if constexpr (LO <= 1 && 1 < HI) {
+				unitSeg(R4{}, KPre2{}, std::false_type{}, inTag, outTag, accQ0, layer, preFirst, true, -1, false,
+				    std::false_type{}, std::false_type{}, accQ0, 0, std::true_type{});
+			}
+		} else {
 		auto slot = [&](TowerAcc(&acc)[2], const int k) __attribute__((always_inline)) {
 			if (k < nPre) {
 				// (k + 1 < kPreRun folds at compile time: without it the last slot carries a never-taken branch that
@@ -1126,11 +1187,46 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 		if constexpr (LO <= 0 && 0 < HI) slot(accPre0, 0);
 		if constexpr (LO <= 1 && 1 < HI) slot(accPre1, 1);
 		if constexpr (LO <= 2 && 2 < HI) slot(accPre2, 2);
+		}
 	};
 	// the rest of the layer: the pre-run units' remaining steps, then the other units whole
 	auto finishLayer = [&](auto resTag, auto inTag, auto outTag, const int layer, const bool streamW) __attribute__((always_inline)) {
 		const int afterPre = firstWhole >= 0 ? firstWhole : (mySingle ? np2 : -1);
-		if constexpr (kDefer) {
+		if constexpr (UROWS == 4) {
+			using Y = std::true_type;
+			using N = std::false_type;
+			const int edge = rp ? 6 : 0;  // (first pair of the edge unit: rows 12.. or 0..)
+			if (rhv == 16 || rp == 0) {
+				// interior quad: positions 4..11, epilogue left to the edge quad, whose first fragments it primes
+				unitSeg(R4{}, KFin{}, resTag, inTag, outTag, accQ0, layer, preFirst, false, edge, false, N{}, N{}, accQ0, 0, N{}, 0, 6);
+				if (streamW) unitSeg(R4{}, KWhole{}, resTag, inTag, outTag, accQ1, layer, edge, true, -1, false, Y{}, Y{}, accQ0, preFirst, N{});
+				else unitSeg(R4{}, KWhole{}, resTag, inTag, outTag, accQ1, layer, edge, true, -1, false, N{}, Y{}, accQ0, preFirst, N{});
+				// the one exposed epilogue of the layer (its residual was fetched behind the quad's last MFMAs)
+				const u64 te0 = stamp();
+				const int ra = 1 + 2 * edge;
+#pragma unroll
+				for (int r = 0; r < 4; ++r) {
+#pragma unroll
+					for (int g = 0; g < 4; ++g) {
+						float v[4];
+						epiValue(resTag, accQ1[r], g, rvNext[r][g], v);
+						epiStore(outTag, ra + r, g, v);
+					}
+				}
+#ifndef JU_TOWER_SEGPROF
+				prof[6] += stamp() - te0;
+#else
+				(void)te0;
+#endif
+			} else {
+				// a 14-row region's parity-1 waves: the interior quad, then rows 12-13 as a whole pair -- each with its
+				// own epilogue (these regions do less work than the 16-row ones and never set the pace)
+				TowerAcc accPair[2];
+				unitSeg(R4{}, KFin{}, resTag, inTag, outTag, accQ0, layer, preFirst, false, edge, false, N{}, N{}, accQ0, 0, Y{}, 0, 4);
+				if (streamW) unitSeg(R2{}, KWhole{}, resTag, inTag, outTag, accPair, layer, edge, true, -1, false, Y{}, N{}, accPair, 0, Y{});
+				else unitSeg(R2{}, KWhole{}, resTag, inTag, outTag, accPair, layer, edge, true, -1, false, N{}, N{}, accPair, 0, Y{});
+			}
+		} else if constexpr (kDefer) {
 			// The fast schedule's shape (two pre-run pairs, then one or two whole pairs: every wave of a
 			// 16- or 14-row region): each unit's epilogue runs behind its successor's MFMAs, only the
 			// last one is exposed.  The accumulators rotate through the two pre-run sets -- a set is
@@ -1563,7 +1659,7 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 		if (primePre) {
 			const unsigned na = ldsBase + OutT::value + (2 * preFirst) * kResRowBytes;
 #pragma unroll
-			for (int j = 0; j < 4; ++j) issue(na, kOrder[0], 0, j);
+			for (int j = 0; j < UROWS + 2; ++j) issue(na, kOrder[0], 0, j);
 			__builtin_amdgcn_sched_barrier(0);
 		}
 		const u64 t3 = stamp();
@@ -1694,9 +1790,9 @@ __global__ __launch_bounds__(256, 1) void tower_resident_kernel(ResidentParams p
 	}
 }
 
-template <typename T, int VARIANT, bool HEAD, bool TAIL = false, bool LEAKY = false, bool FAST = false>
+template <typename T, int VARIANT, bool HEAD, bool TAIL = false, bool LEAKY = false, bool FAST = false, int UROWS = 2>
 void launchResidentT(const ResidentParams &p, hipStream_t stream) {
-	auto kern = tower_resident_kernel<T, VARIANT, HEAD, TAIL, LEAKY, FAST>;
+	auto kern = tower_resident_kernel<T, VARIANT, HEAD, TAIL, LEAKY, FAST, UROWS>;
 	static std::atomic<std::uint64_t> ldsDone{0};
 	ensureDynamicLds(reinterpret_cast<const void *>(kern), kResLds, &ldsDone, "resident tower");
 	// (g_ResidentFault > 0, tests only: some regions are never computed, their neighbours'
@@ -1757,6 +1853,17 @@ bool residentTowerFastGeometry(int H, int W, int GX, int GY, int RH) {
 	       residentFastShape(lastH, lastW);
 }
 
+// the fast schedule's work unit: row quads (default) where every region of the frame has their shape, else row pairs;
+// 2 (the tests' switch): row pairs everywhere
+static std::atomic<int> g_TowerUnitRows{4};
+void setResidentTowerUnitRows(int rows) { g_TowerUnitRows = rows == 2 ? 2 : 4; }
+int residentTowerUnitRows(int H, int W, int GX, int GY, int RH) {
+	const int lastH = H - (GY - 1) * RH, lastW = W - (GX - 1) * kResRW;
+	const bool quads = JU_TOWER_M16 != 0 && residentFastQuadShape(RH, kResRW) && residentFastQuadShape(lastH, kResRW) &&
+	                   residentFastQuadShape(RH, lastW) && residentFastQuadShape(lastH, lastW);
+	return quads && g_TowerUnitRows.load() == 4 ? 4 : 2;
+}
+
 std::size_t residentMailboxBytes(int GX, int GY, bool leaky) {
 	return static_cast<std::size_t>(GX) * GY * 2 * kResMailSlots * 16 * (leaky ? 2 : 1);
 }
@@ -1797,16 +1904,21 @@ void launchResidentTower(DType dt, const ResidentTowerParams &q, hipStream_t str
 	}
 	// the fast schedule where every region has its shape (JU_TOWER_FAST=0: the general one, for A/B runs)
 	const bool fast = residentTowerFast() && residentTowerFastGeometry(p.H, p.W, p.GX, p.GY, p.RH);
+	// ... in its row-quad form where every region is 32 x 16 or 32 x 14 and the tower is a ReLU one
+	const bool quad = fast && !q.leaky && residentTowerUnitRows(p.H, p.W, p.GX, p.GY, p.RH) == 4;
 #ifdef JU_TOWER_DEV  // developer builds: the bf16 ReLU instantiations only (compile time)
 	if (q.leaky || dt == kF16 || !p.hasHead) throw std::invalid_argument("resident tower: developer build");
 	if (p.tailW1 != nullptr) {
-		if (fast) launchResidentT<bf16, 0, true, true, false, true>(p, stream);
+		if (quad) launchResidentT<bf16, 0, true, true, false, true, 4>(p, stream);
+		else if (fast) launchResidentT<bf16, 0, true, true, false, true>(p, stream);
 		else launchResidentT<bf16, 0, true, true>(p, stream);
 	} else if (g_TowerVariant == 8) launchResidentT<bf16, 8, true>(p, stream);
 	else if (g_TowerVariant == 4) {
-		if (fast) launchResidentT<bf16, 4, true, false, false, true>(p, stream);
+		if (quad) launchResidentT<bf16, 4, true, false, false, true, 4>(p, stream);
+		else if (fast) launchResidentT<bf16, 4, true, false, false, true>(p, stream);
 		else launchResidentT<bf16, 4, true>(p, stream);
-	} else if (fast) launchResidentT<bf16, 0, true, false, false, true>(p, stream);
+	} else if (quad) launchResidentT<bf16, 0, true, false, false, true, 4>(p, stream);
+	else if (fast) launchResidentT<bf16, 0, true, false, false, true>(p, stream);
 	else launchResidentT<bf16, 0, true>(p, stream);
 	return;
 #else
@@ -1839,6 +1951,9 @@ void launchResidentTower(DType dt, const ResidentTowerParams &q, hipStream_t str
 		return;
 	}
 	if (!p.hasHead) {
+		// (a tower without a head layer keeps the row-pair form: the engine launches none, and under that
+		// instantiation's register allocation hipcc parks primed fragments in AGPRs before they have landed --
+		// tools/lds_wait_check.py)
 		if (fast) {
 			if (dt == kF16) launchResidentT<f16, 0, false, false, false, true>(p, stream);
 			else launchResidentT<bf16, 0, false, false, false, true>(p, stream);
@@ -1849,7 +1964,10 @@ void launchResidentTower(DType dt, const ResidentTowerParams &q, hipStream_t str
 		return;
 	}
 	if (p.tailW1 != nullptr) {  // fused tail: product kernel only (the ablation variants keep the split)
-		if (fast) {
+		if (quad) {
+			if (dt == kF16) launchResidentT<f16, 0, true, true, false, true, 4>(p, stream);
+			else launchResidentT<bf16, 0, true, true, false, true, 4>(p, stream);
+		} else if (fast) {
 			if (dt == kF16) launchResidentT<f16, 0, true, true, false, true>(p, stream);
 			else launchResidentT<bf16, 0, true, true, false, true>(p, stream);
 		} else {
@@ -1860,6 +1978,7 @@ void launchResidentTower(DType dt, const ResidentTowerParams &q, hipStream_t str
 	}
 	if (dt == kF16) {
 		if (g_TowerVariant == 8) launchResidentT<f16, 8, true>(p, stream);
+		else if (quad) launchResidentT<f16, 0, true, false, false, true, 4>(p, stream);
 		else if (fast) launchResidentT<f16, 0, true, false, false, true>(p, stream);
 		else launchResidentT<f16, 0, true>(p, stream);
 		return;
@@ -1870,7 +1989,8 @@ void launchResidentTower(DType dt, const ResidentTowerParams &q, hipStream_t str
 	case 2: launchResidentT<bf16, 2, true>(p, stream); break;
 	case 3: launchResidentT<bf16, 3, true>(p, stream); break;
 	case 4:
-		if (fast) launchResidentT<bf16, 4, true, false, false, true>(p, stream);
+		if (quad) launchResidentT<bf16, 4, true, false, false, true, 4>(p, stream);
+		else if (fast) launchResidentT<bf16, 4, true, false, false, true>(p, stream);
 		else launchResidentT<bf16, 4, true>(p, stream);
 		break;
 	case 5:  // calibration: per-layer output maxima of this frame in debug[0 .. nLayers)
@@ -1878,7 +1998,8 @@ void launchResidentTower(DType dt, const ResidentTowerParams &q, hipStream_t str
 		launchResidentT<bf16, 5, true>(p, stream);
 		break;
 	default:
-		if (fast) launchResidentT<bf16, 0, true, false, false, true>(p, stream);
+		if (quad) launchResidentT<bf16, 0, true, false, false, true, 4>(p, stream);
+		else if (fast) launchResidentT<bf16, 0, true, false, false, true>(p, stream);
 		else launchResidentT<bf16, 0, true>(p, stream);
 		break;
 	}

@@ -10,6 +10,9 @@
 //   shape 1: v_mfma_f32_16x16x32_bf16, same unit; per (dx, ks32, pixel half) macro-step ROWS+2 row fragments
 //            (16 px x 32 ch each) feed 3*ROWS*2 MFMAs (both cout halves): the same LDS bytes per FLOP
 //
+//   "epilogue filler": the tower's deferred epilogue as VALU + LDS-write filler behind the MFMAs, one group of four values per
+//            twelve 16x16x32 MFMAs -- 8 groups per 2-row unit (one per macro-step), 16 per 4-row unit (two per macro-step)
+//
 // Printed per variant: us per launch, TFLOP/s, cycles per unit (s_memtime) and the in-kernel clock
 // (s_memtime / s_memrealtime), after a warm-up of back-to-back launches.
 //
@@ -182,8 +185,10 @@ __device__ __forceinline__ void unit16(unsigned rowAddr, const unsigned (&colBas
 				acc[r][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[((dy * 3 + dx) * 2 + ks) * 2 + ch], fb[set][need], acc[r][ph][ch], 0, 0, 0);
 				if (ch == 0 && more && k < NR) issueRow<NR>(fb[set ^ 1], addr(m + 1), k);
 				if constexpr (FILL) {
-					const int kk = 2 * k + ch;  // 0 .. 6 ROWS - 1: the same 12 VALU + 1 LDS write per macro-step, two behind every second MFMA
-					if (m < 8 && kk < 12) {
+					// one accumulator group's epilogue = 12 VALU + 1 LDS write behind 12 MFMAs, two behind every second MFMA:
+					// ROWS = 2: 8 groups, one per macro-step;  ROWS = 4: 16 groups, two per macro-step (behind MFMAs 0..11 and 12..23)
+					const int kk = (2 * k + ch) % 12;
+					if (m < 8) {
 						if (kk < 8) {
 							if ((kk & 1) == 0) asm volatile("v_lshlrev_b32 %0, 16, %1\n\tv_add_f32 %0, %0, %2" : "=&v"(fx[kk >> 1]) : "v"(fx[((kk >> 1) + 1) & 3]), "v"(fx[((kk >> 1) + 2) & 3]));
 						} else if (kk == 8) {
@@ -387,6 +392,7 @@ int main(int argc, char **argv) {
 		run<1, 2, true>("16x16x32, 2-row, epilogue filler", tile, wgt, out, stamps, units, cus);
 		run<0, 4, false>("32x32x16, 4-row units", tile, wgt, out, stamps, units / 2, cus);
 		run<1, 4, false>("16x16x32, 4-row units", tile, wgt, out, stamps, units / 2, cus);
+		run<1, 4, true>("16x16x32, 4-row, epilogue filler", tile, wgt, out, stamps, units / 2, cus);
 	}
 	return 0;
 }
