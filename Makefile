@@ -26,7 +26,7 @@ all: $(OUT)/libJoshUpscale.so $(OUT)/libJoshUpscale_test.so
 # consume every accumulator with VALU ops; in AGPR form each value first costs a
 # v_accvgpr_read (128 per layer and lane in the tower kernel, ~2 % of its time).
 KERNELFLAGS := -mllvm -amdgpu-mfma-vgpr-form
-$(OBJ)/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/kernel_common.h $(CSRC)/flow_block_common.h $(CSRC)/tile_geometry.h $(CSRC)/scene_decision.h Makefile
+$(OBJ)/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/kernel_common.h $(CSRC)/flow_block_common.h $(CSRC)/tile_geometry.h $(CSRC)/scene_decision.h $(CSRC)/scale_tile.h Makefile
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) -c $< -o $@
 

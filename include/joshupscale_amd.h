@@ -638,7 +638,8 @@ JU_API int ju_tiled_create(int device_id, const char *model_path, size_t src_wid
 JU_API void ju_tiled_destroy(ju_tiled *tiled); /* NULL: nothing */
 /* Zeroes every tile's recurrent state: the next frame is the first of a fresh object. */
 JU_API int ju_tiled_reset(ju_tiled *tiled);
-/* One frame, synchronously: `input` a BGRX image of src_width x src_height, `output` one of four times that; each
+/* One frame, synchronously: `input` a BGRX image of src_width x src_height, `output` one of four times that (or of the
+ * output size set: ju_tiled_set_output_size below); each
  * JU_LOC_CPU or JU_LOC_DEVICE with a stride of any sign.  A JU_LOC_DEVICE image at a 4-byte-aligned address and stride
  * is read / written where it is; any other goes through a staging frame.
  * JU_ERR_INVALID_ARGUMENT, before anything is launched and with every tile's state unchanged: a NULL pointer, an image
@@ -664,6 +665,34 @@ JU_API int ju_tiled_process_frame(ju_tiled *tiled, const ju_frame *input, const 
  * ju_tiled_get_stat "hbd_from_state" 0), whose deep frames stay the 8-bit route's.  ju_tiled_reset keeps it.  Another value
  * is JU_ERR_INVALID_ARGUMENT and leaves the setting as it was. */
 JU_API int ju_tiled_set_deep_from_state(ju_tiled *tiled, int on);
+/* An output size for tiled frames (docs/tiled.md "An output size"; no reference counterpart: the reference has no tiles and
+ * hands out the model's size).  ju_tiled_set_output_size: output frames are width x height from now on, exactly that size
+ * (the YUV parity rules apply to it; anything else is JU_ERR_INVALID_ARGUMENT naming "the output size set", before anything
+ * is launched and with every tile's state unchanged).  The blended frame of B x Bh = 4 src_width x 4 src_height is scaled
+ * by ju_set_output_size's scaler and filters INSIDE the blend's launch: the scaler's vertical pass reads the tiles' outputs
+ * (states) and forms each blended sample in registers, so the B x Bh frame is never stored and no buffer of that size is
+ * allocated.  By definition (tests/tiled_output_reference.py), with no tolerance:
+ *   8-bit frame: the blend rounds to bytes first, (sum wy wx v + 32768) >> 16, and the scaler runs on those bytes,
+ *   (sum qy qx v + 2^23) >> 24, clamped to 0 .. 255 with a cubic filter; BGRX is that frame (X = 0), every other format its
+ *   encode -- a deep format on this route carries 257 x u8;
+ *   16-bit frame, for a deep format while ju_tiled_set_deep_from_state is 1 and "hbd_from_state" is 1: the same two steps
+ *   on the 16-bit samples P of the tiles' states, encoded as ju_set_output_size encodes a scaled 16-bit frame.
+ * An output size of exactly B x Bh gives the unscaled frame with the triangle and with Catmull-Rom; Mitchell filters it.  A
+ * source of exactly W x H, ONE tile, gives byte for byte the frames of ju_process_frame under ju_set_output_size with the
+ * same arguments (the float formats included: both sides are f32(P) / 65535 of a 16-bit frame).
+ * (0, 0) turns it off (the filter must still be a known one, as for ju_set_output_size).  Limits (JU_ERR_INVALID_ARGUMENT,
+ * the message names B x Bh as four times the tiled source size; the setting stays as it was): each axis 2 .. 16384, at
+ * most 16 times the blended axis and at least a 16th of it -- an 8th with a cubic filter; filter one of JU_SCALE_TRIANGLE,
+ * JU_SCALE_CATMULL_ROM, JU_SCALE_MITCHELL (1 and every other value: refused).  The setter waits for the tiled stream and
+ * drops the staging frames, whose sizes follow the output size; ju_tiled_reset keeps the setting.  A JU_LOC_DEVICE BGRX
+ * output at a 4-byte-aligned address and stride is written in place, with a stride of either sign.  ju_tiled_get_info keeps
+ * reporting out_width = 4 src_width, the blended size, as ju_get_size keeps reporting the model's; tile states, frame
+ * history, group passes and the scene detector do not know about the setting.
+ * ju_tiled_get_output_size: (0, 0) while off.
+ * ju_tiled_get_stat: "output_scaled" (1 / 0), "output_filter" (the JU_SCALE_* value in effect, 0 while off),
+ * "output_scaled_frames" (the frames that took a fused blend-and-scale kernel). */
+JU_API int ju_tiled_set_output_size(ju_tiled *tiled, size_t width, size_t height, int filter);
+JU_API int ju_tiled_get_output_size(const ju_tiled *tiled, size_t *width, size_t *height);
 JU_API int ju_tiled_get_info(const ju_tiled *tiled, ju_tiled_info *info);
 /* The origin of tile `index` (0 .. tiles_x tiles_y - 1, row-major over the tile grid) in source pixels. */
 JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t *y);
@@ -671,8 +700,9 @@ JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t
  * tiles (tiles x frames while every pass holds at least two tiles); "deep_from_state": the setting of
  * ju_tiled_set_deep_from_state; "hbd_from_state": 1 where the model's f16 state is its frame in float (ju_get_stat's key,
  * every tile's alike); "deep_state_frames": the frames whose output was blended from the tiles' states;
- * "scene_mode", "scene_frames", "scene_cuts": the detector below, the two counters cumulative as ju_get_stat's.  An unknown
- * key is JU_ERR_INVALID_ARGUMENT. */
+ * "scene_mode", "scene_frames", "scene_cuts": the detector below, the two counters cumulative as ju_get_stat's;
+ * "output_scaled", "output_filter", "output_scaled_frames": ju_tiled_set_output_size above.  An unknown key is
+ * JU_ERR_INVALID_ARGUMENT. */
 JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value);
 /* The scene detector of a tiled stream (docs/tiled.md "Scene cuts"; no reference counterpart).  ju_set_scene_detect's
  * definition, modes, threshold, refusals and records, with ONE detector on the tiled object that looks at the SOURCE frame:
@@ -691,8 +721,9 @@ JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *val
 JU_API int ju_tiled_set_scene_detect(ju_tiled *tiled, int mode, uint32_t threshold_milli);
 JU_API int ju_tiled_get_scene_detect(const ju_tiled *tiled, int *mode, uint32_t *threshold_milli);
 JU_API int ju_tiled_get_scene_info(ju_tiled *tiled, ju_scene_info *out, int count, int *written);
-/* Not provided for a tiled object: look-ahead passes, ju_set_source_size / ju_set_output_size / the mask / the scene
- * detector, graphics resources, graph capture, the C++ plugin surface. */
+/* Not provided for a tiled object: look-ahead passes, ju_set_source_size and the mask (the output size is
+ * ju_tiled_set_output_size, the scene detector ju_tiled_set_scene_detect), graphics resources, graph capture, the C++
+ * plugin surface. */
 
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing

@@ -269,6 +269,20 @@ JU_API int ju_debug_tile_stitch(void *dst, ptrdiff_t dst_stride, size_t src_widt
  * JU_ERR_INVALID_ARGUMENT before any device call. */
 JU_API int ju_debug_tile_stitch_state(void *dst16, size_t src_width, size_t src_height, size_t tile_width, size_t tile_height,
     int overlap, void *const *tiles, int count);
+/* The two fused kernels of a tiled object's output size alone (tile_stitch_scale_kernel, tile_stitch_scale_state_kernel;
+ * docs/tiled.md "An output size"; the definitions: tests/tiled_output_reference.py frame8 / frame16), each ONE synchronous
+ * launch on caller-supplied device buffers, on the current device, for the layout and the tiles of ju_debug_tile_stitch /
+ * ju_debug_tile_stitch_state, held to the same limits, and an output of dst_width x dst_height through `filter`
+ * (JU_SCALE_*), held to ju_tiled_set_output_size's limits with its message.
+ * ju_debug_tile_stitch_scale writes BGRX rows at `dst` -- any byte alignment, signed stride -- X = 0, and nothing around them.
+ * ju_debug_tile_stitch_scale_state writes the dense frame [dst_height][dst_width][4] of 16-bit words at `dst16` (8-byte
+ * aligned), X = 0, and nothing behind it.  A NULL buffer, a misaligned tile or 16-bit frame, |stride| smaller than a row,
+ * sizes, an overlap, an output size or a filter outside the limits or a wrong count is JU_ERR_INVALID_ARGUMENT before any
+ * device call. */
+JU_API int ju_debug_tile_stitch_scale(void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, int filter,
+    size_t src_width, size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count);
+JU_API int ju_debug_tile_stitch_scale_state(void *dst16, size_t dst_width, size_t dst_height, int filter, size_t src_width,
+    size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count);
 
 /* The two kernels of a tiled stream's scene detector alone (docs/tiled.md "Scene cuts"), each ONE synchronous launch on
  * caller-supplied device buffers, on the current device.

@@ -423,6 +423,14 @@ int ju_tiled_set_deep_from_state(ju_tiled *tiled, int on) {
 	return guarded([&] { tiledOf(tiled).setDeepFromState(on); });
 }
 
+int ju_tiled_set_output_size(ju_tiled *tiled, size_t width, size_t height, int filter) {
+	return guarded([&] { tiledOf(tiled).setOutputSize(width, height, filter); });
+}
+
+int ju_tiled_get_output_size(const ju_tiled *tiled, size_t *width, size_t *height) {
+	return guarded([&] { tiledOf(const_cast<ju_tiled *>(tiled)).outputSize(width, height); });
+}
+
 int ju_tiled_process(ju_tiled *tiled, const ju_image *input, const ju_image *output) {
 	return guarded([&] {
 		ju::TiledRuntime &t = tiledOf(tiled);
@@ -636,6 +644,68 @@ int ju_debug_tile_stitch_state(void *dst16, size_t src_width, size_t src_height,
 		yTable.upload(y.table.data(), y.table.size() * sizeof(ju::TileAxisEntry));
 		ju::launchTileStitchState(static_cast<std::uint16_t *>(dst16), static_cast<int>(4 * src_width), static_cast<int>(4 * src_height),
 		    set, nx, ny, static_cast<int>(4 * tile_width), xTable.as<unsigned>(), yTable.as<unsigned>(), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+namespace {
+// What both fused hooks share behind debugTileSet: the output size's limits, the tiles' alignment, the blend's tables and
+// the scaler's, all in front of the launch.
+struct DebugStitchScale {
+	ju::DeviceBuffer xTable, yTable;
+	ju::Scaler scale;
+};
+void debugStitchScale(const std::string &name, size_t dst_width, size_t dst_height, int filter, size_t src_width, size_t src_height,
+    size_t tile_width, size_t tile_height, int overlap, const ju::TileSet &set, int count, DebugStitchScale *out) {
+	const std::string problem = ju::tiledOutputSizeProblem(dst_width, dst_height, src_width, src_height, filter);
+	if (!problem.empty()) throw std::invalid_argument(name + ": " + problem);
+	for (int k = 0; k < count; ++k) {
+		if (set.ptr[k] == nullptr || reinterpret_cast<std::uintptr_t>(set.ptr[k]) % 16) {
+			throw std::invalid_argument(name + ": tile " + std::to_string(k) + " is NULL or not 16-byte aligned");
+		}
+	}
+	const ju::TileAxis x = ju::tileAxis(static_cast<long>(src_width), static_cast<long>(tile_width), overlap);
+	const ju::TileAxis y = ju::tileAxis(static_cast<long>(src_height), static_cast<long>(tile_height), overlap);
+	out->xTable = ju::DeviceBuffer(x.table.size() * sizeof(ju::TileAxisEntry));
+	out->yTable = ju::DeviceBuffer(y.table.size() * sizeof(ju::TileAxisEntry));
+	out->xTable.upload(x.table.data(), x.table.size() * sizeof(ju::TileAxisEntry));
+	out->yTable.upload(y.table.data(), y.table.size() * sizeof(ju::TileAxisEntry));
+	out->scale.build(4 * src_width, 4 * src_height, dst_width, dst_height, filter);
+}
+}  // namespace
+
+int ju_debug_tile_stitch_scale(void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, int filter, size_t src_width,
+    size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count) {
+	return guarded([&] {
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		const std::string name = "ju_debug_tile_stitch_scale";
+		// (the layout's refusals, then |stride| against a row of the OUTPUT size)
+		debugTileSet(name.c_str(), src_width, src_height, tile_width, tile_height, overlap, tiles, count, dst, dst_stride, dst_width, &set,
+		    &nx, &ny);
+		DebugStitchScale d;
+		debugStitchScale(name, dst_width, dst_height, filter, src_width, src_height, tile_width, tile_height, overlap, set, count, &d);
+		ju::launchTileStitchScale(static_cast<std::uint8_t *>(dst), dst_stride, static_cast<int>(dst_width), static_cast<int>(dst_height),
+		    static_cast<int>(4 * src_width), static_cast<int>(4 * src_height), set, nx, ny, static_cast<int>(4 * tile_width),
+		    d.xTable.as<unsigned>(), d.yTable.as<unsigned>(), d.scale.xAxis(), d.scale.yAxis(), d.scale.span(), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_tile_stitch_scale_state(void *dst16, size_t dst_width, size_t dst_height, int filter, size_t src_width, size_t src_height,
+    size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count) {
+	return guarded([&] {
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		const std::string name = "ju_debug_tile_stitch_scale_state";
+		// (the dense 16-bit frame: rows of 8 bytes per pixel)
+		debugTileSet(name.c_str(), src_width, src_height, tile_width, tile_height, overlap, tiles, count, dst16,
+		    static_cast<ptrdiff_t>(8 * dst_width), 2 * dst_width, &set, &nx, &ny);
+		if (reinterpret_cast<std::uintptr_t>(dst16) % 8) throw std::invalid_argument(name + ": the 16-bit frame is not 8-byte aligned");
+		DebugStitchScale d;
+		debugStitchScale(name, dst_width, dst_height, filter, src_width, src_height, tile_width, tile_height, overlap, set, count, &d);
+		ju::launchTileStitchScaleState(static_cast<std::uint16_t *>(dst16), static_cast<int>(dst_width), static_cast<int>(dst_height),
+		    static_cast<int>(4 * src_width), static_cast<int>(4 * src_height), set, nx, ny, static_cast<int>(4 * tile_width),
+		    d.xTable.as<unsigned>(), d.yTable.as<unsigned>(), d.scale.xAxis(), d.scale.yAxis(), d.scale.span(), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }

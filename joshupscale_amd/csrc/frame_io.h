@@ -105,6 +105,11 @@ public:
 	std::size_t dstW() const { return m_DstW; }
 	std::size_t dstH() const { return m_DstH; }
 	int filter() const { return m_Filter; }  // (JU_SCALE_*; 0 while not set)
+	// the two axes' device tables and the x axis' scaleSpan, for a launch that scales from another source than rows in
+	// memory (the tiled object's fused kernels: launchTileStitchScale / launchTileStitchScaleState)
+	const ScaleAxisDev &xAxis() const { return m_XDev; }
+	const ScaleAxisDev &yAxis() const { return m_YDev; }
+	int span() const { return m_Span; }
 	// launchScaleBgrx / launchScaleState (kernels.h) with the scaler's sizes and tables
 	void scaleBgrx(const std::uint8_t *src, std::ptrdiff_t srcStride, std::uint8_t *dst, std::ptrdiff_t dstStride,
 	    hipStream_t stream) const;

@@ -757,6 +757,20 @@ void launchTileStitch(std::uint8_t *dst, std::ptrdiff_t dstStride, int outW, int
 // The layout launchScaleState writes and launchEncodeFrame16 reads.  One launch.
 void launchTileStitchState(std::uint16_t *dst16, int outW, int outH, const TileSet &states, int nx, int ny, int tileOutW,
     const unsigned *xTable, const unsigned *yTable, hipStream_t stream);
+// Blend and scale in ONE launch (docs/tiled.md "An output size"; tests/tiled_output_reference.py): the bytes of
+// launchTileStitch into a frame of outW x outH followed by launchScaleBgrx to dstW x dstH -- that frame is formed in
+// registers inside the scaler's vertical pass and never stored.  dst: BGRX rows at any byte alignment, signed stride, X = 0.
+// x / y / spanX: the device copies of buildScaleAxis(outW, dstW) / (outH, dstH) and scaleSpan of the x axis; outW and
+// tileOutW multiples of four pixels; the x table 16-byte aligned.  The scaler's tile and 1 KB of tile pointers and
+// origins must fit the LDS (std::invalid_argument).
+void launchTileStitchScale(std::uint8_t *dst, std::ptrdiff_t dstStride, int dstW, int dstH, int outW, int outH, const TileSet &tiles,
+    int nx, int ny, int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y,
+    int spanX, hipStream_t stream);
+// The same over the tiles' f16 states: the words of launchTileStitchState followed by a 16-bit scale of that frame (the
+// arithmetic of launchScaleState on its words P) -> the dense u16 frame [dstH][dstW][4] at dst16 (8-byte aligned; X = 0).
+void launchTileStitchScaleState(std::uint16_t *dst16, int dstW, int dstH, int outW, int outH, const TileSet &states, int nx, int ny,
+    int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX,
+    hipStream_t stream);
 
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).

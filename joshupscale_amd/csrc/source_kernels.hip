@@ -30,6 +30,10 @@
 // sign and clamped to 0 .. 255 / 65535.  The triangle's instantiations are, instruction for instruction, the kernels
 // from before the template (docs/source_stage.md "Filters").
 //
+// The tile itself -- both passes, the two forms, the LDS layout -- is scale_tile.h, with the source of the vertical pass
+// as a template parameter: the kernels here read rows in memory (ScaleRows8, ScaleState16); the tiled object's fused
+// kernels (tile_kernels.hip) run the same tile over the blend of its tiles.
+//
 // Resources (tools/kernel_resources.py): scale_bgrx_kernel and scale_bgrx_items_kernel hold 52 VGPRs in either form and no
 // scratch; scale_bgrx_members_kernel, which carries both forms behind a uniform branch, 52 VGPRs and no scratch too.
 //
@@ -45,6 +49,7 @@
 
 #include "kernel_common.h"
 #include "kernels.h"
+#include "scale_tile.h"
 
 namespace ju {
 
@@ -211,21 +216,6 @@ std::string outputSizeProblem(std::size_t outW, std::size_t outH, std::size_t mo
 	       " the model's output " + std::to_string(modelW) + "x" + std::to_string(modelH);
 }
 
-namespace {
-// The source columns of a tile of destination columns d0 .. d1: from the first tap of d0 to the last tap of d1 for the
-// triangle, whose rows start and end in ascending order.  A cubic row loses a tap whose weight is exactly 0 at either
-// end (Catmull-Rom at distance 1, Mitchell at 8/7), at most one per end, so a row inside the tile can reach one column
-// further than the tile's outer rows (buildCubicAxis checks that it is never more): one column of slack on either side.
-template <bool kSigned>
-__host__ __device__ inline int tileFirst(int first) {
-	return kSigned ? (first > 0 ? first - 1 : 0) : first;
-}
-template <bool kSigned>
-__host__ __device__ inline int tileEnd(int end, int n) {
-	return kSigned ? (end < n ? end + 1 : n) : end;
-}
-}  // namespace
-
 int scaleSpan(const ScaleAxisHost &x) {
 	int span = 4;
 	for (int d0 = 0; d0 < x.m; d0 += kScaleTileW) {
@@ -241,128 +231,13 @@ int scaleSpan(const ScaleAxisHost &x) {
 
 namespace {
 
-__device__ inline unsigned loadPixel(const std::uint8_t *p) {
-	if ((reinterpret_cast<std::uintptr_t>(p) & 3) == 0) return *reinterpret_cast<const unsigned *>(p);
-	return static_cast<unsigned>(p[0]) | (static_cast<unsigned>(p[1]) << 8) | (static_cast<unsigned>(p[2]) << 16) |
-	       (static_cast<unsigned>(p[3]) << 24);
-}
-
-__device__ inline void storePixel(std::uint8_t *p, unsigned v) {
-	if ((reinterpret_cast<std::uintptr_t>(p) & 3) == 0) {
-		*reinterpret_cast<unsigned *>(p) = v;
-		return;
-	}
-	p[0] = static_cast<std::uint8_t>(v);
-	p[1] = static_cast<std::uint8_t>(v >> 8);
-	p[2] = static_cast<std::uint8_t>(v >> 16);
-	p[3] = static_cast<std::uint8_t>(v >> 24);
-}
-
-// LDS column of tile column c: one word of padding per 32 columns (see the head of the file)
-__device__ inline int ldsColumn(int c) { return c + (c >> 5); }
-
-// the tables of one axis as the kernels take them (ScaleAxisDev without the host's choice of form)
-struct ScaleTaps {
-	const int *start;
-	const std::uint16_t *taps;
-};
-
-// The two forms of a scale kernel.  Unsigned, the triangle: u16 taps, unsigned sums, no clamp (rows of non-negative taps
-// summing to 4096 cannot leave the range).  Signed, the cubic filters: the same words read as i16, signed 32-bit
-// vertical sums in LDS (|sum| <= top * 6144: < 2^21 for 8-bit samples, < 2^29 for 16-bit ones), a signed 64-bit horizontal
-// sum (|sum| < 2^34 / 2^42), and the shifted result -- narrow again: below 2^18 in size -- clamped to 0 .. top.
-template <bool kSigned>
-struct ScaleForm {
-	using Tap = std::conditional_t<kSigned, std::int16_t, std::uint16_t>;
-	using Sum = std::conditional_t<kSigned, int, unsigned>;                    // a tap in a register; a vertical sum
-	using Sum8 = std::conditional_t<kSigned, long long, unsigned>;             // the horizontal sum of 8-bit samples
-	using Sum16 = std::conditional_t<kSigned, long long, unsigned long long>;  // ... of 16-bit samples
-};
-
-// (sum + 2^23) >> 24 of a horizontal sum that already holds the 2^23: floor; the signed form clamps to 0 .. kTop
-template <bool kSigned, int kTop, typename T>
-__device__ inline unsigned scaleResult(T sum) {
-	if constexpr (kSigned) {
-		return static_cast<unsigned>(min(max(static_cast<int>(sum >> 24), 0), kTop));
-	} else {
-		return static_cast<unsigned>(sum >> 24);
-	}
-}
-
-// One tile of scale_bgrx_kernel (the head of the file): the workgroup's tile is blockIdx.x, blockIdx.y.  THE body of both
-// launch forms -- the single frame and the items of a look-ahead pass -- so their bytes are equal by construction.
+// One tile of scale_bgrx_kernel (the head of the file; scale_tile.h holds the body) over BGRX rows in memory.  THE body of
+// all three launch forms -- the single frame, the items of a look-ahead pass, the members of a group pass -- so their
+// bytes are equal by construction.
 template <bool kSigned>
 __device__ __forceinline__ void scaleBgrxTile(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride, int srcW,
     std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW, int dstH, ScaleTaps ax, ScaleTaps ay, int pitch) {
-	using Tap = typename ScaleForm<kSigned>::Tap;
-	using Sum = typename ScaleForm<kSigned>::Sum;
-	using Wide = typename ScaleForm<kSigned>::Sum8;
-	extern __shared__ unsigned tileWords[];  // [3][kScaleTileH][pitch]: sum qy * src per channel
-	Sum *tile = reinterpret_cast<Sum *>(tileWords);
-	const int tid = threadIdx.x;
-	const int dx0 = blockIdx.x * kScaleTileW, dy0 = blockIdx.y * kScaleTileH;
-	const int dxLast = min(dx0 + kScaleTileW, dstW) - 1;
-	const int xs0 = tileFirst<kSigned>(ax.start[dx0]) & ~3;
-	const int xs1 = tileEnd<kSigned>(ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps], srcW);
-	const int quads = (xs1 - xs0 + 3) >> 2;
-	const bool aligned = ((reinterpret_cast<std::uintptr_t>(src) | static_cast<std::uintptr_t>(srcStride)) & 15) == 0;
-
-	// vertical pass: item = (tile row, four source columns)
-	for (int item = tid; item < kScaleTileH * quads; item += 256) {
-		const int r = item / quads, q = item - r * quads;
-		const int dy = dy0 + r;
-		if (dy >= dstH) continue;
-		const int x = xs0 + 4 * q;
-		const Tap *qy = reinterpret_cast<const Tap *>(ay.taps) + dy * kScaleTapPitch;
-		const int count = qy[kScaleMaxTaps];
-		const std::uint8_t *row = src + static_cast<std::ptrdiff_t>(ay.start[dy]) * srcStride;
-		Sum acc[12];
-#pragma unroll
-		for (int i = 0; i < 12; ++i) acc[i] = 0;
-		for (int t = 0; t < count; ++t, row += srcStride) {
-			const Sum w = qy[t];
-			unsigned px[4];
-			if (aligned && x + 4 <= srcW) {
-				const uint4 v = *reinterpret_cast<const uint4 *>(row + 4 * x);
-				px[0] = v.x, px[1] = v.y, px[2] = v.z, px[3] = v.w;
-			} else {
-#pragma unroll
-				for (int k = 0; k < 4; ++k) px[k] = loadPixel(row + 4 * min(x + k, srcW - 1));  // (past the row: never a tap)
-			}
-#pragma unroll
-			for (int k = 0; k < 4; ++k) {
-				acc[3 * k] += w * static_cast<Sum>(px[k] & 255);
-				acc[3 * k + 1] += w * static_cast<Sum>((px[k] >> 8) & 255);
-				acc[3 * k + 2] += w * static_cast<Sum>((px[k] >> 16) & 255);
-			}
-		}
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const int col = ldsColumn(4 * q + k);
-#pragma unroll
-			for (int c = 0; c < 3; ++c) tile[(c * kScaleTileH + r) * pitch + col] = acc[3 * k + c];
-		}
-	}
-	__syncthreads();
-
-	// horizontal pass: a thread per destination pixel
-	const int tx = tid & (kScaleTileW - 1), ty = tid / kScaleTileW;
-	const int dx = dx0 + tx, dy = dy0 + ty;
-	if (dx >= dstW || dy >= dstH) return;
-	const Tap *qx = reinterpret_cast<const Tap *>(ax.taps) + dx * kScaleTapPitch;
-	const int count = qx[kScaleMaxTaps];
-	const int first = ax.start[dx] - xs0;
-	Wide b = 1u << 23, g = 1u << 23, r = 1u << 23;
-	const Sum *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
-	for (int t = 0; t < count; ++t) {
-		const Wide w = qx[t];
-		const int col = ldsColumn(first + t);
-		b += w * tb[col];  // (the signed form: i32 x i32 + i64, one v_mad_i64_i32)
-		g += w * tg[col];
-		r += w * tr[col];
-	}
-	storePixel(dst + static_cast<std::ptrdiff_t>(dy) * dstStride + 4 * dx, scaleResult<kSigned, 255>(b) |
-	    (scaleResult<kSigned, 255>(g) << 8) | (scaleResult<kSigned, 255>(r) << 16));
+	scaleTile8<kSigned, ScaleRows8>({src, srcStride, srcW}, srcW, dst, dstStride, dstW, dstH, ax, ay, pitch);
 }
 
 template <bool kSigned>
@@ -398,89 +273,15 @@ __global__ __launch_bounds__(256) void scale_bgrx_members_kernel(ScaleMembers me
 	}
 }
 
-// P of one f16 of the state, as StateSource::sample (colour_kernels.hip) forms it: exact in f32
-__device__ inline unsigned stateSample(unsigned bits) {
-	const float s = static_cast<float>(__builtin_bit_cast(f16, static_cast<unsigned short>(bits)));
-	return static_cast<unsigned>(fminf(fmaxf(floorf((s + 0.5f) * 65536.0f), 0.0f), 65535.0f));
-}
-
 // The dense f16 state [srcH][srcW][4] (B, G, R, unused) -> the dense u16 frame [dstH][dstW][4] (B, G, R, 0):
-// out = (sum qy qx P + 2^23) >> 24.  The tile, the tables and the LDS layout of scale_bgrx_kernel; an item of the
-// vertical pass is (tile row, two source columns): 16 bytes per tap where that pair is 16-byte aligned (every pair of
-// an even width, every other row of an odd one), else two 8-byte loads, the column clamped to the row.
+// out = (sum qy qx P + 2^23) >> 24.  The tile, the tables and the LDS layout of scale_bgrx_kernel (scaleTile16 of
+// scale_tile.h); an item of the vertical pass is (tile row, two source columns): 16 bytes per tap where that pair is
+// 16-byte aligned (every pair of an even width, every other row of an odd one), else two 8-byte loads, the column clamped
+// to the row.
 template <bool kSigned>
 __global__ __launch_bounds__(256) void scale_state_kernel(const f16 *__restrict__ src, int srcW,
     std::uint16_t *__restrict__ dst, int dstW, int dstH, ScaleTaps ax, ScaleTaps ay, int pitch) {
-	using Tap = typename ScaleForm<kSigned>::Tap;
-	using Sum = typename ScaleForm<kSigned>::Sum;
-	using Wide = typename ScaleForm<kSigned>::Sum16;
-	extern __shared__ unsigned tileWords[];  // [3][kScaleTileH][pitch]: sum qy * P per channel, below 2^28 (signed: 2^29 in size)
-	Sum *tile = reinterpret_cast<Sum *>(tileWords);
-	const int tid = threadIdx.x;
-	const int dx0 = blockIdx.x * kScaleTileW, dy0 = blockIdx.y * kScaleTileH;
-	const int dxLast = min(dx0 + kScaleTileW, dstW) - 1;
-	const int xs0 = tileFirst<kSigned>(ax.start[dx0]) & ~3;
-	const int xs1 = tileEnd<kSigned>(ax.start[dxLast] + ax.taps[dxLast * kScaleTapPitch + kScaleMaxTaps], srcW);
-	const int pairs = (xs1 - xs0 + 1) >> 1;
-	const std::size_t rowWords = static_cast<std::size_t>(srcW) * 4;  // f16 per state row
-
-	for (int item = tid; item < kScaleTileH * pairs; item += 256) {
-		const int r = item / pairs, q = item - r * pairs;
-		const int dy = dy0 + r;
-		if (dy >= dstH) continue;
-		const int x = xs0 + 2 * q;
-		const Tap *qy = reinterpret_cast<const Tap *>(ay.taps) + dy * kScaleTapPitch;
-		const int count = qy[kScaleMaxTaps];
-		const f16 *row = src + static_cast<std::size_t>(ay.start[dy]) * rowWords;
-		Sum acc[6];
-#pragma unroll
-		for (int i = 0; i < 6; ++i) acc[i] = 0;
-		for (int t = 0; t < count; ++t, row += rowWords) {
-			const Sum w = qy[t];
-			uint2 px[2];
-			const f16 *p = row + 4 * static_cast<std::size_t>(x);
-			if (x + 2 <= srcW && (reinterpret_cast<std::uintptr_t>(p) & 15) == 0) {
-				const uint4 v = *reinterpret_cast<const uint4 *>(p);
-				px[0] = make_uint2(v.x, v.y), px[1] = make_uint2(v.z, v.w);
-			} else {
-#pragma unroll
-				for (int k = 0; k < 2; ++k) {  // (past the row: never a tap)
-					px[k] = *reinterpret_cast<const uint2 *>(row + 4 * static_cast<std::size_t>(min(x + k, srcW - 1)));
-				}
-			}
-#pragma unroll
-			for (int k = 0; k < 2; ++k) {
-				acc[3 * k] += w * static_cast<Sum>(stateSample(px[k].x & 0xffff));
-				acc[3 * k + 1] += w * static_cast<Sum>(stateSample(px[k].x >> 16));
-				acc[3 * k + 2] += w * static_cast<Sum>(stateSample(px[k].y & 0xffff));
-			}
-		}
-#pragma unroll
-		for (int k = 0; k < 2; ++k) {
-			const int col = ldsColumn(2 * q + k);
-#pragma unroll
-			for (int c = 0; c < 3; ++c) tile[(c * kScaleTileH + r) * pitch + col] = acc[3 * k + c];
-		}
-	}
-	__syncthreads();
-
-	const int tx = tid & (kScaleTileW - 1), ty = tid / kScaleTileW;
-	const int dx = dx0 + tx, dy = dy0 + ty;
-	if (dx >= dstW || dy >= dstH) return;
-	const Tap *qx = reinterpret_cast<const Tap *>(ax.taps) + dx * kScaleTapPitch;
-	const int count = qx[kScaleMaxTaps];
-	const int first = ax.start[dx] - xs0;
-	Wide b = 1u << 23, g = 1u << 23, r = 1u << 23;  // (each sum stays below 2^40; the signed form: 2^42 in size)
-	const Sum *tb = tile + ty * pitch, *tg = tile + (kScaleTileH + ty) * pitch, *tr = tile + (2 * kScaleTileH + ty) * pitch;
-	for (int t = 0; t < count; ++t) {
-		const Wide w = qx[t];
-		const int col = ldsColumn(first + t);
-		b += w * tb[col];
-		g += w * tg[col];
-		r += w * tr[col];
-	}
-	const unsigned lo = scaleResult<kSigned, 65535>(b) | (scaleResult<kSigned, 65535>(g) << 16);
-	*reinterpret_cast<uint2 *>(dst + (static_cast<std::size_t>(dy) * dstW + dx) * 4) = make_uint2(lo, scaleResult<kSigned, 65535>(r));
+	scaleTile16<kSigned, ScaleState16>({src, srcW}, srcW, dst, dstW, dstH, ax, ay, pitch);
 }
 
 __global__ __launch_bounds__(256) void mask_blend_kernel(std::uint8_t *__restrict__ gen, std::ptrdiff_t genStride,

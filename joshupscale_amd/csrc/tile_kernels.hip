@@ -19,10 +19,13 @@
 //   tile_stitch_state_kernel  the same blend over the tiles' f16 STATES, per 16-bit sample P of a state, into a dense
 //                       u16 frame that launchEncodeFrame16 encodes (deep outputs; tests/tiled_deep_reference.py): no
 //                       head or tail groups, a capped grid that strides over the rows, 2 x 8 x 4 Ws x 4 Hs bytes.
+//   tile_stitch_scale_kernel, tile_stitch_scale_state_kernel  the two blends FUSED into the output scaler (docs/tiled.md
+//                       "An output size"; tests/tiled_output_reference.py): the scale kernels' tile (scale_tile.h) whose
+//                       vertical pass forms each blended sample in registers, so the frame of 4 Ws x 4 Hs is never stored.
 //
-// Both are bound by memory: the split moves 2 x 4 Ws Hs bytes and a little more (the overlaps are read and written
-// twice), the stitch 2 x 64 Ws Hs.  Tile pointers and origins travel by value in the kernel arguments (TileSet); the
-// state stitch copies them into LDS once per workgroup.
+// Split and stitch are bound by memory: the split moves 2 x 4 Ws Hs bytes and a little more (the overlaps are read and
+// written twice), the stitch 2 x 64 Ws Hs.  Tile pointers and origins travel by value in the kernel arguments (TileSet); the
+// state stitch and the fused kernels copy them into LDS once per workgroup.
 // Rows are addressed with their signed stride; every address and stride is a multiple of 4 (the launchers refuse others).
 
 #include <hip/hip_runtime.h>
@@ -33,6 +36,7 @@
 
 #include "kernel_common.h"
 #include "kernels.h"
+#include "scale_tile.h"
 #include "scene_decision.h"
 
 namespace ju {
@@ -179,13 +183,15 @@ __global__ __launch_bounds__(256) void tile_split_scene_kernel(const std::uint8_
 	sceneDecide(sc.st, sc.ring, sc.slot, sc.step, sc.hasPrev, sc.thresholdMilli, sc.resetMode, sc.pixels);
 }
 
-// pixel (X, Y) of the frame as tile k holds it
-__device__ __forceinline__ const std::uint8_t *tileAt(const TileSet &tiles, int k, int X, int Y, int tileOutW) {
+// pixel (X, Y) of the frame as tile k holds it (Tiles: the launch's TileSet, or the workgroup's TileView of it in LDS)
+template <typename Tiles>
+__device__ __forceinline__ const std::uint8_t *tileAt(const Tiles &tiles, int k, int X, int Y, int tileOutW) {
 	return tiles.ptr[k] + (static_cast<std::size_t>(Y - kTileScale * tiles.y[k]) * tileOutW + (X - kTileScale * tiles.x[k])) * 4;
 }
 
 // one output pixel from the up to four tiles its two table entries name
-__device__ __forceinline__ unsigned stitchPixel(const TileSet &tiles, int nx, unsigned ex, unsigned ey, int X, int Y,
+template <typename Tiles>
+__device__ __forceinline__ unsigned stitchPixel(const Tiles &tiles, int nx, unsigned ex, unsigned ey, int X, int Y,
     int tileOutW) {
 	const int tx = ex & 0xffffu, ty = ey & 0xffffu;
 	const unsigned qx = ex >> 16, qy = ey >> 16;
@@ -354,6 +360,132 @@ __global__ __launch_bounds__(256) void tile_stitch_state_kernel(std::uint16_t *_
 	}
 }
 
+// ---- blend and scale in one launch (docs/tiled.md "An output size"; tests/tiled_output_reference.py) --------------------
+// The scale kernels' tile (scale_tile.h: scaleTile8 / scaleTile16, the body of scale_bgrx_kernel / scale_state_kernel) with
+// a source that FORMS each sample of the blended frame in registers from the tiles' outputs (states): the blended frame of
+// 4 Ws x 4 Hs is never stored.  Only the vertical pass's loads differ from the scaler's, so the scaled bytes are its by
+// construction, and the blended samples are tile_stitch_kernel's (tile_stitch_state_kernel's): stitchPixel /
+// stitchStatePixel, rounded to bytes (16-bit words) BEFORE the scaler multiplies them.
+// A lane's column is four (two) blended columns from X = 0 mod 4 (mod 2): the frame's width is a multiple of four, so the
+// group never crosses its end, and its column entries are fetched ONCE, in front of the tap loop; per tap the entry of
+// the blended row.  Equal column entries without weight under a row entry without weight -- all of a frame but its seams
+// -- are ONE 16-byte load from that tile, 16-byte aligned (tiles are dense and aligned, origins and X multiples of four
+// pixels); else per pixel the two or four tiles that have weight.
+
+// the tiles and the two blend tables as a fused kernel's source takes them
+struct StitchArgs {
+	TileView tiles;
+	int nx, tileOutW;
+	const unsigned *xTable, *yTable;
+};
+
+struct StitchColumn {
+	unsigned ex[4];  // the columns' entries (the 16-bit source: two)
+	int Y;           // the current blended row
+	int tx, xIn;     // the first entry's tile column, and X inside it
+	bool oneColumn;  // equal entries without weight: the group lies under one tile column
+};
+
+// the blended 8-bit frame: tile_stitch_kernel's pixels
+struct StitchSource8 {
+	using Args = StitchArgs;
+	using Column = StitchColumn;
+	StitchArgs a;
+	__device__ __forceinline__ explicit StitchSource8(const Args &args) : a(args) {}
+	__device__ __forceinline__ Column column(int x, int row) const {
+		const uint4 e = *reinterpret_cast<const uint4 *>(a.xTable + x);
+		Column c;
+		c.ex[0] = e.x, c.ex[1] = e.y, c.ex[2] = e.z, c.ex[3] = e.w;
+		c.Y = row;
+		c.tx = e.x & 0xffffu;
+		c.xIn = x - kTileScale * a.tiles.x[c.tx];
+		c.oneColumn = (e.x >> 16) == 0 && e.x == e.y && e.x == e.z && e.x == e.w;
+		return c;
+	}
+	__device__ __forceinline__ uint4 load(const Column &c, int x) const {
+		const unsigned ey = a.yTable[c.Y];
+		if (c.oneColumn && (ey >> 16) == 0) {
+			const int k = (ey & 0xffffu) * a.nx + c.tx;
+			return *reinterpret_cast<const uint4 *>(
+			    a.tiles.ptr[k] + (static_cast<std::size_t>(c.Y - kTileScale * a.tiles.y[k]) * a.tileOutW + c.xIn) * 4);
+		}
+		return make_uint4(stitchPixel(a.tiles, a.nx, c.ex[0], ey, x, c.Y, a.tileOutW), stitchPixel(a.tiles, a.nx, c.ex[1], ey, x + 1, c.Y, a.tileOutW),
+		    stitchPixel(a.tiles, a.nx, c.ex[2], ey, x + 2, c.Y, a.tileOutW), stitchPixel(a.tiles, a.nx, c.ex[3], ey, x + 3, c.Y, a.tileOutW));
+	}
+	__device__ __forceinline__ Column next(Column c) const {
+		++c.Y;
+		return c;
+	}
+};
+
+// the blended 16-bit frame: tile_stitch_state_kernel's words, (P_B | P_G << 16, P_R) per pixel as statePair packs them
+struct StitchSource16 {
+	using Args = StitchArgs;
+	using Column = StitchColumn;
+	StitchArgs a;
+	__device__ __forceinline__ explicit StitchSource16(const Args &args) : a(args) {}
+	__device__ __forceinline__ Column column(int x, int row) const {
+		const uint2 e = *reinterpret_cast<const uint2 *>(a.xTable + x);
+		Column c;
+		c.ex[0] = e.x, c.ex[1] = e.y, c.ex[2] = 0, c.ex[3] = 0;
+		c.Y = row;
+		c.tx = e.x & 0xffffu;
+		c.xIn = x - kTileScale * a.tiles.x[c.tx];
+		c.oneColumn = (e.x >> 16) == 0 && e.x == e.y;
+		return c;
+	}
+	__device__ __forceinline__ uint4 load(const Column &c, int x) const {
+		const unsigned ey = a.yTable[c.Y];
+		if (c.oneColumn && (ey >> 16) == 0) {
+			const int k = (ey & 0xffffu) * a.nx + c.tx;
+			return statePair(*reinterpret_cast<const uint4 *>(
+			    a.tiles.ptr[k] + (static_cast<std::size_t>(c.Y - kTileScale * a.tiles.y[k]) * a.tileOutW + c.xIn) * 8));
+		}
+		const uint2 p0 = stitchStatePixel(a.tiles, a.nx, c.ex[0], ey, x, c.Y, a.tileOutW);
+		const uint2 p1 = stitchStatePixel(a.tiles, a.nx, c.ex[1], ey, x + 1, c.Y, a.tileOutW);
+		return make_uint4(p0.x, p0.y, p1.x, p1.y);
+	}
+	__device__ static __forceinline__ unsigned sample(unsigned p) { return p; }  // (already a 16-bit sample)
+	__device__ __forceinline__ Column next(Column c) const {
+		++c.Y;
+		return c;
+	}
+};
+
+// The tiles' pointers and origins from the kernel arguments into LDS, once per workgroup (1 KB in front of the scaler's
+// tile), as tile_stitch_state_kernel does: a lane's lookup by its own index is then an LDS read.  All 256 lanes reach the
+// barrier.
+__device__ __forceinline__ TileView tilesToLds(const TileSet &set, int count) {
+	__shared__ const std::uint8_t *sPtr[kTileMax];
+	__shared__ int sX[kTileMax], sY[kTileMax];
+	const int lane = threadIdx.x;
+	if (lane < count) {
+		sPtr[lane] = set.ptr[lane];
+		sX[lane] = set.x[lane];
+		sY[lane] = set.y[lane];
+	}
+	__syncthreads();
+	return {sPtr, sX, sY};
+}
+
+// outW: the blended frame's width (4 Ws); dst: BGRX rows of dstW x dstH at any byte alignment, signed stride
+template <bool kSigned>
+__global__ __launch_bounds__(256) void tile_stitch_scale_kernel(std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW,
+    int dstH, int outW, const TileSet set, int nx, int count, int tileOutW, const unsigned *__restrict__ xTable,
+    const unsigned *__restrict__ yTable, ScaleTaps ax, ScaleTaps ay, int pitch) {
+	const TileView tiles = tilesToLds(set, count);
+	scaleTile8<kSigned, StitchSource8>({tiles, nx, tileOutW, xTable, yTable}, outW, dst, dstStride, dstW, dstH, ax, ay, pitch);
+}
+
+// dst: the dense u16 frame [dstH][dstW][4], 8-byte aligned, X = 0
+template <bool kSigned>
+__global__ __launch_bounds__(256) void tile_stitch_scale_state_kernel(std::uint16_t *__restrict__ dst, int dstW, int dstH, int outW,
+    const TileSet set, int nx, int count, int tileOutW, const unsigned *__restrict__ xTable, const unsigned *__restrict__ yTable,
+    ScaleTaps ax, ScaleTaps ay, int pitch) {
+	const TileView tiles = tilesToLds(set, count);
+	scaleTile16<kSigned, StitchSource16>({tiles, nx, tileOutW, xTable, yTable}, outW, dst, dstW, dstH, ax, ay, pitch);
+}
+
 void checkTileSet(const char *who, const TileSet &tiles, int count, unsigned align) {
 	if (count < 1 || count > kTileMax) throw std::invalid_argument(std::string(who) + ": 1 .. 64 tiles");
 	for (int k = 0; k < count; ++k) {
@@ -458,6 +590,64 @@ void launchTileStitchState(std::uint16_t *dst16, int outW, int outH, const TileS
 	hipLaunchKernelGGL(tile_stitch_state_kernel, grid, dim3(64, 4), 0, stream, dst16, outW, outH, states, nx, nx * ny, tileOutW,
 	    xTable, yTable);
 	hipCheckLaunch("tile_stitch_state");
+}
+
+namespace {
+// what both fused launches check, and the scaler's tile in LDS behind the 1 KB of tile pointers and origins
+struct StitchScaleLaunch {
+	dim3 grid;
+	std::size_t lds;
+	int pitch;
+};
+StitchScaleLaunch stitchScaleLaunch(const std::string &who, const void *dst, int dstW, int dstH, int outW, int outH, const TileSet &tiles,
+    int nx, int ny, int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y,
+    int spanX) {
+	if (nx < 1 || ny < 1) throw std::invalid_argument(who + ": 1 .. 64 tiles");
+	checkTileSet(who.c_str(), tiles, nx * ny, 16);
+	if (dst == nullptr || dstW < 1 || dstH < 1) throw std::invalid_argument(who + ": NULL or empty destination");
+	if (outW < 4 || outW % 4 || outH < 1 || tileOutW < 4 || tileOutW % 4) {
+		throw std::invalid_argument(who + ": widths must be multiples of four pixels");
+	}
+	if (xTable == nullptr || yTable == nullptr || reinterpret_cast<std::uintptr_t>(xTable) % 16) {
+		throw std::invalid_argument(who + ": NULL table, or an x table that is not 16-byte aligned");
+	}
+	if (x.start == nullptr || x.taps == nullptr || y.start == nullptr || y.taps == nullptr || spanX < 4 || spanX % 4) {
+		throw std::invalid_argument(who + ": bad scaler tables");
+	}
+	if (x.filter != y.filter) throw std::invalid_argument(who + ": the two axes' tables must be of one filter");
+	StitchScaleLaunch l;
+	l.pitch = spanX + spanX / 32 + 1;
+	l.lds = static_cast<std::size_t>(3) * kScaleTileH * static_cast<std::size_t>(l.pitch) * sizeof(unsigned);
+	constexpr std::size_t kTilesLds = kTileMax * (sizeof(void *) + 2 * sizeof(int));
+	if (l.lds + kTilesLds > 64 * 1024) throw std::invalid_argument(who + ": the tile does not fit the LDS");
+	l.grid = dim3(static_cast<unsigned>((dstW + kScaleTileW - 1) / kScaleTileW), static_cast<unsigned>((dstH + kScaleTileH - 1) / kScaleTileH));
+	return l;
+}
+}  // namespace
+
+void launchTileStitchScale(std::uint8_t *dst, std::ptrdiff_t dstStride, int dstW, int dstH, int outW, int outH, const TileSet &tiles,
+    int nx, int ny, int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y,
+    int spanX, hipStream_t stream) {
+	const StitchScaleLaunch l = stitchScaleLaunch("tile_stitch_scale", dst, dstW, dstH, outW, outH, tiles, nx, ny, tileOutW, xTable, yTable,
+	    x, y, spanX);
+	const ScaleTaps tx{x.start, x.taps}, ty{y.start, y.taps};
+	const auto kernel = x.filter != kScaleTriangle ? tile_stitch_scale_kernel<true> : tile_stitch_scale_kernel<false>;
+	hipLaunchKernelGGL(kernel, l.grid, dim3(256), l.lds, stream, dst, dstStride, dstW, dstH, outW, tiles, nx, nx * ny, tileOutW, xTable,
+	    yTable, tx, ty, l.pitch);
+	hipCheckLaunch("tile_stitch_scale");
+}
+
+void launchTileStitchScaleState(std::uint16_t *dst16, int dstW, int dstH, int outW, int outH, const TileSet &states, int nx, int ny,
+    int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX,
+    hipStream_t stream) {
+	const StitchScaleLaunch l = stitchScaleLaunch("tile_stitch_scale_state", dst16, dstW, dstH, outW, outH, states, nx, ny, tileOutW,
+	    xTable, yTable, x, y, spanX);
+	if (reinterpret_cast<std::uintptr_t>(dst16) % 8) throw std::invalid_argument("tile_stitch_scale_state: the 16-bit frame is not 8-byte aligned");
+	const ScaleTaps tx{x.start, x.taps}, ty{y.start, y.taps};
+	const auto kernel = x.filter != kScaleTriangle ? tile_stitch_scale_state_kernel<true> : tile_stitch_scale_state_kernel<false>;
+	hipLaunchKernelGGL(kernel, l.grid, dim3(256), l.lds, stream, dst16, dstW, dstH, outW, states, nx, nx * ny, tileOutW, xTable, yTable,
+	    tx, ty, l.pitch);
+	hipCheckLaunch("tile_stitch_scale_state");
 }
 
 }  // namespace ju

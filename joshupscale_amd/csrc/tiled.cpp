@@ -85,6 +85,9 @@ double TiledRuntime::stat(const std::string &key) const {
 		}
 		return static_cast<double>(v);
 	}
+	if (key == "output_scaled") return m_OutScale.set() ? 1.0 : 0.0;
+	if (key == "output_filter") return m_OutScale.filter();
+	if (key == "output_scaled_frames") return static_cast<double>(m_OutputScaledFrames);
 	if (key == "group_frames") {
 		double sum = 0;
 		for (const auto &e : m_Engines) sum += e->stat("group_frames");
@@ -191,6 +194,38 @@ void TiledRuntime::splitIn(const Rows &src) {
 	++m_SceneSteps;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// An output size (docs/tiled.md "An output size"): Engine::setOutputSize's rules with the blended frame in the place of the
+// model's output.  The frame is scaled inside the blend's launch (stitchOut / stitchOutDeep), so all that is kept here is
+// the scaler's two tables.
+// ---------------------------------------------------------------------------------------------------------------
+std::string tiledOutputSizeProblem(std::size_t width, std::size_t height, std::size_t srcW, std::size_t srcH, int filter) {
+	const std::size_t bw = kTileScale * srcW, bh = kTileScale * srcH;
+	const std::string problem = outputSizeProblem(width, height, bw, bh, filter);
+	if (problem.empty() || !scaleFilterProblem(filter).empty()) return problem;
+	return problem + " (of a tiled object: the blended frame " + std::to_string(bw) + "x" + std::to_string(bh) +
+	       ", four times the tiled source size)";
+}
+
+void TiledRuntime::setOutputSize(std::size_t width, std::size_t height, int filter) {
+	const bool off = width == 0 && height == 0;
+	// (turning it off checks the filter all the same, as ju_set_output_size does)
+	const std::string problem = tiledOutputSizeProblem(off ? kTileScale * m_SrcW : width, off ? kTileScale * m_SrcH : height, m_SrcW,
+	    m_SrcH, filter);
+	if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_output_size: " + problem);
+	DeviceGuard g(m_Device);
+	Scaler scale;
+	if (!off) scale.build(kTileScale * m_SrcW, kTileScale * m_SrcH, width, height, filter);
+	m_Stream->synchronize();  // (the call is synchronous, so nothing reads the old tables; kept for a stream shared later)
+	m_OutScale = std::move(scale);
+	for (DeviceBuffer *b : {&m_OutStage, &m_Out16, &m_YuvOut}) *b = DeviceBuffer();  // (their sizes follow the output size)
+}
+
+void TiledRuntime::outputSize(std::size_t *width, std::size_t *height) const {
+	if (width) *width = m_OutScale.dstW();
+	if (height) *height = m_OutScale.dstH();
+}
+
 void TiledRuntime::setDeepFromState(int on) {
 	if (on != 0 && on != 1) throw std::invalid_argument("ju_tiled_set_deep_from_state: " + std::to_string(on) + " is neither 0 nor 1");
 	m_DeepFromState = on == 1;
@@ -198,9 +233,12 @@ void TiledRuntime::setDeepFromState(int on) {
 
 // What ju_process_frame refuses for a frame of this size, and what a tiled frame cannot be: a graphics resource
 void TiledRuntime::check(const AnyFrame &f, bool input, const char *who) const {
-	const std::size_t w = input ? m_SrcW : kTileScale * m_SrcW, h = input ? m_SrcH : kTileScale * m_SrcH;
+	const bool resized = !input && m_OutScale.set();  // (output frames are the output size while one is set)
+	const std::size_t w = input ? m_SrcW : (resized ? m_OutScale.dstW() : kTileScale * m_SrcW);
+	const std::size_t h = input ? m_SrcH : (resized ? m_OutScale.dstH() : kTileScale * m_SrcH);
 	const std::string side = input ? "input" : "output";
-	const std::string size = std::to_string(w) + "x" + std::to_string(h) + (input ? " (the tiled source size)" : " (four times the tiled source size)");
+	const std::string size = std::to_string(w) + "x" + std::to_string(h) +
+	                         (input ? " (the tiled source size)" : (resized ? " (the output size set)" : " (four times the tiled source size)"));
 	if (f.yuv) return checkPlanes(f.planes, side, w, h, size, who);
 	auto refuse = [who](const std::string &why) { throw std::invalid_argument(std::string(who) + ": " + why); };
 	const Frame &b = f.bgrx;
@@ -256,7 +294,9 @@ bool TiledRuntime::deepFromState(const AnyFrame &out) const {
 // are complete -- into the dense 16-bit frame, which the existing encode from such a frame turns into the caller's planes
 // (a host frame's through their staging layout, as on the 8-bit route).
 void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
-	const std::size_t ow = kTileScale * m_SrcW, oh = kTileScale * m_SrcH;
+	const bool scaled = m_OutScale.set();
+	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
+	const std::size_t ow = scaled ? m_OutScale.dstW() : bw, oh = scaled ? m_OutScale.dstH() : bh;
 	TileSet states = m_Out;  // (the origins; the pointers: each tile's state, whichever half its last frame wrote)
 	for (int k = 0; k < tiles(); ++k) {
 		states.ptr[k] = static_cast<std::uint8_t *>(const_cast<void *>(m_Engines[static_cast<std::size_t>(k)]->lastState()));
@@ -264,14 +304,22 @@ void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
 	const bool host = y.location == Location::Host;
 	std::uint8_t *yuv = host ? lazy(m_YuvOut, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
 	const YuvPlanes planes = host ? stagedPlanes(y, yuv) : callerPlanes(y);
-	if (tiles() == 1) {
+	if (tiles() == 1 && !scaled) {
 		// ONE tile: nothing to blend, and the frame is ju_process_frame's -- its encode from the state, which for the float
 		// formats (RGBPH, RGBPS, BGR96F) is clamp(s + 0.5), not P / 65535 as from a 16-bit frame (docs/output_stage.md)
 		launchEncodeState(fmt(y.format), y.colorspace, states.ptr[0], planes, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
 	} else {
 		auto *frame16 = lazy(m_Out16, ow * oh * 8).as<std::uint16_t>();
-		launchTileStitchState(frame16, static_cast<int>(ow), static_cast<int>(oh), states, tilesX(), tilesY(),
-		    static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(), *m_Stream);
+		if (scaled) {
+			// ONE launch blends and scales (one tile too: ju_process_frame's bytes under ju_set_output_size, which also come
+			// from a scaled 16-bit frame); nothing of the blended size is stored
+			launchTileStitchScaleState(frame16, static_cast<int>(ow), static_cast<int>(oh), static_cast<int>(bw), static_cast<int>(bh), states,
+			    tilesX(), tilesY(), static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(),
+			    m_OutScale.xAxis(), m_OutScale.yAxis(), m_OutScale.span(), *m_Stream);
+		} else {
+			launchTileStitchState(frame16, static_cast<int>(ow), static_cast<int>(oh), states, tilesX(), tilesY(),
+			    static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(), *m_Stream);
+		}
 		launchEncodeFrame16(fmt(y.format), y.colorspace, frame16, planes, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
 	}
 	if (host) copyPlanes(y, yuv, false, *m_Stream);
@@ -279,10 +327,21 @@ void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
 }
 
 void TiledRuntime::stitchOut(const AnyFrame &out) {
+	// While an output size is set the frame is ow x oh of it and the blend's launch is the fused one, which forms the
+	// blended frame in registers and writes the scaled one; everything behind the launch -- the staging frame, the copy
+	// out, the encode -- is the same code at that size.  Off: exactly the launches of before.
+	const bool scaled = m_OutScale.set();
+	if (scaled) ++m_OutputScaledFrames;
 	if (deepFromState(out)) return stitchOutDeep(out.planes);
-	const std::size_t ow = kTileScale * m_SrcW, oh = kTileScale * m_SrcH, rowBytes = ow * 4;
+	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
+	const std::size_t ow = scaled ? m_OutScale.dstW() : bw, oh = scaled ? m_OutScale.dstH() : bh, rowBytes = ow * 4;
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
 	auto stitch = [&](std::uint8_t *dst, std::ptrdiff_t stride) {
+		if (scaled) {
+			return launchTileStitchScale(dst, stride, static_cast<int>(ow), static_cast<int>(oh), static_cast<int>(bw), static_cast<int>(bh),
+			    m_Out, tilesX(), tilesY(), static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(),
+			    m_OutScale.xAxis(), m_OutScale.yAxis(), m_OutScale.span(), *m_Stream);
+		}
 		launchTileStitch(dst, stride, static_cast<int>(ow), static_cast<int>(oh), m_Out, tilesX(), tilesY(),
 		    static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(), *m_Stream);
 	};

@@ -14,6 +14,10 @@
 
 namespace ju {
 
+// The limits of ju_tiled_set_output_size as one message shared with its Python twin: outputSizeProblem's for the blended
+// frame of 4 srcW x 4 srcH, which a limit's message then names as such; "" when width x height may be set.
+std::string tiledOutputSizeProblem(std::size_t width, std::size_t height, std::size_t srcW, std::size_t srcH, int filter);
+
 class TiledRuntime {
 public:
 	// srcWidth x srcHeight: the size of every input frame; overlap: source pixels neighbouring tiles share at least.
@@ -23,7 +27,7 @@ public:
 	TiledRuntime(const TiledRuntime &) = delete;
 	TiledRuntime &operator=(const TiledRuntime &) = delete;
 
-	// One frame, synchronously: `in` of the source size, `out` of four times that, any format, host or device.  Both are
+	// One frame, synchronously: `in` of the source size, `out` of four times that (or the output size set), any format, host or device.  Both are
 	// checked before anything is launched (std::invalid_argument "<who>: <why>"; every tile's state as it was).
 	void process(const AnyFrame &in, const AnyFrame &out, const char *who);
 	// zeroes every tile's recurrent state (keeps setDeepFromState)
@@ -41,6 +45,14 @@ public:
 	void sceneDetect(int *mode, std::uint32_t *thresholdMilli) const;
 	// the last min(count, kSceneRing, steps seen) decisions, oldest first; returns how many
 	int sceneInfo(SceneRecord *out, int count);
+	// An output size (docs/tiled.md "An output size"): output frames are width x height from now on, the blended frame of
+	// 4 srcWidth x 4 srcHeight scaled by `filter` (kScale*) INSIDE the blend's launch -- the blended frame is never stored.
+	// (0, 0) turns it off.  The limits are outputSizeProblem's with the blended frame in the model output's place
+	// (std::invalid_argument; the setting stays as it was).  Waits for the tiled stream, builds and uploads the two axes'
+	// tables and drops the staging frames, whose sizes follow the output size.  reset() keeps it; tile states, frame
+	// history, group passes and the scene detector do not know about it.
+	void setOutputSize(std::size_t width, std::size_t height, int filter);
+	void outputSize(std::size_t *width, std::size_t *height) const;  // (0, 0) while off
 
 	std::size_t srcWidth() const { return m_SrcW; }
 	std::size_t srcHeight() const { return m_SrcH; }
@@ -55,7 +67,8 @@ public:
 	// "tiles", "frames" (frames processed), "group_frames" (the members' frames that ran inside group passes, summed),
 	// "deep_from_state" (the setting), "hbd_from_state" (the model's property, every tile's alike), "deep_state_frames"
 	// (frames whose output was blended from the states), "scene_mode", "scene_frames" / "scene_cuts" (the detector's
-	// decisions and cuts, cumulative over its on-periods)
+	// decisions and cuts, cumulative over its on-periods), "output_scaled" (1 while an output size is set), "output_filter"
+	// (its kScale* value, 0 while off), "output_scaled_frames" (frames that took a fused blend-and-scale kernel)
 	double stat(const std::string &key) const;
 
 private:
@@ -91,6 +104,10 @@ private:
 	DeviceBuffer m_Out16;
 	std::uint64_t m_DeepStateFrames = 0;
 	std::uint64_t m_Frames = 0;
+	// the output size: the scaler's tables from the blended frame to it (set() while one is in effect) and the frames that
+	// took a fused kernel.  m_OutStage, m_Out16 and m_YuvOut are then of the output size.
+	Scaler m_OutScale;
+	std::uint64_t m_OutputScaledFrames = 0;
 	// The scene detector, made when the mode is turned on: m_ScenePrev the kept source-size frame (4 Ws Hs bytes), m_SceneDev
 	// the SceneState, m_SceneRing kSceneRing records + the totals (host-mapped), m_SceneClear the clear's table of kTileMax
 	// SceneClearTile (host-mapped; RESET on a recurrent model only).  m_Own: what each tile counts (tileOwnedEnds).

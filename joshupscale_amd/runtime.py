@@ -152,6 +152,17 @@ def output_size_problem(width: int, height: int, model_width: int, model_height:
             f"{_ratio_words(filter, False)} the model's output {model_width}x{model_height}")
 
 
+def tiled_output_size_problem(width: int, height: int, src_width: int, src_height: int, filter: int = SCALE_TRIANGLE) -> str:
+    """The limits of ``ju_tiled_set_output_size`` for a tiled source of ``src_width x src_height``, with the C layer's
+    message: those of ``ju_set_output_size`` with the blended frame, four times the source, in the model output's place;
+    ``""`` when the output size may be set."""
+    bw, bh = 4 * src_width, 4 * src_height
+    problem = output_size_problem(width, height, bw, bh, filter)
+    if not problem or scale_filter_problem(filter):
+        return problem
+    return f"{problem} (of a tiled object: the blended frame {bw}x{bh}, four times the tiled source size)"
+
+
 LOG_CALLBACK = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p)
 
 
@@ -234,6 +245,8 @@ _PRODUCT_SIGS = {
     "ju_tiled_destroy": (None, [C.c_void_p]),
     "ju_tiled_reset": (C.c_int, [C.c_void_p]),
     "ju_tiled_set_deep_from_state": (C.c_int, [C.c_void_p, C.c_int]),
+    "ju_tiled_set_output_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
+    "ju_tiled_get_output_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_tiled_process": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
     "ju_tiled_process_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
     "ju_tiled_get_info": (C.c_int, [C.c_void_p, _P(JuTiledInfo)]),
@@ -304,6 +317,10 @@ _HOOK_SIGS = {
                                        _P(C.c_void_p), C.c_int]),
     "ju_debug_tile_stitch_state": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                              _P(C.c_void_p), C.c_int]),
+    "ju_debug_tile_stitch_scale": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t,
+                                             C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p), C.c_int]),
+    "ju_debug_tile_stitch_scale_state": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t,
+                                                   C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p), C.c_int]),
     "ju_debug_tile_split_scene": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                             _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, _P(JuSceneInfo), C.c_int,
                                             C.c_uint32, C.c_int]),
@@ -852,14 +869,16 @@ class TiledRuntime:
         _check(self._lib, self._lib.ju_tiled_process_frame(self._h, C.byref(inp), C.byref(out)))
 
     def run(self, frame_bgrx: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
-        """Host frames: ``[src_height, src_width, 4]`` uint8 BGRX in, ``[4 src_height, 4 src_width, 4]`` out.  Any row
-        stride (also negative, i.e. a ``[::-1]`` view) is passed through."""
+        """Host frames: ``[src_height, src_width, 4]`` uint8 BGRX in, ``[4 src_height, 4 src_width, 4]`` out -- or
+        :meth:`frame_output_size` while an output size is set.  Any row stride (also negative, i.e. a ``[::-1]`` view) is
+        passed through."""
         if frame_bgrx.dtype != np.uint8 or frame_bgrx.ndim != 3 or frame_bgrx.shape[2] != 4:
             raise ValueError("expected a [H, W, 4] uint8 BGRX frame")
         if frame_bgrx.strides[2] != 1 or frame_bgrx.strides[1] != 4:
             frame_bgrx = np.ascontiguousarray(frame_bgrx)
         if out is None:
-            out = np.empty((self.out_height, self.out_width, 4), np.uint8)
+            ow, oh = self.frame_output_size()
+            out = np.empty((oh, ow, 4), np.uint8)
         if out.strides[2] != 1 or out.strides[1] != 4:
             raise ValueError("output must have contiguous pixels")
         self.process(host_image(frame_bgrx), host_image(out))
@@ -874,6 +893,31 @@ class TiledRuntime:
         of the tiles' f16 states, where the model's state is its frame in float (``stat("hbd_from_state")``); 0, the
         default, = from the blended 8-bit frame (docs/tiled.md "Deep outputs").  Another value is refused."""
         _check(self._lib, self._lib.ju_tiled_set_deep_from_state(self._h, int(on)))
+
+    # -- an output size (docs/tiled.md "An output size") ----------
+    def set_output_size(self, width: int, height: int, filter: int = SCALE_TRIANGLE) -> None:
+        """``ju_tiled_set_output_size``: output frames are ``width x height`` from now on, the blended frame scaled by
+        ``filter`` (``SCALE_TRIANGLE``, ``SCALE_CATMULL_ROM`` or ``SCALE_MITCHELL``) inside the blend's launch; ``(0, 0)``
+        turns it off.  The limits raise ``ValueError`` with the C layer's message before any native call.
+        ``out_width`` / ``out_height`` stay the blended size."""
+        width, height, filter = int(width), int(height), int(filter)
+        off = (width, height) == (0, 0)
+        problem = tiled_output_size_problem(self.out_width if off else width, self.out_height if off else height,
+                                            self.src_width, self.src_height, filter)
+        if problem:
+            raise ValueError("ju_tiled_set_output_size: " + problem)
+        _check(self._lib, self._lib.ju_tiled_set_output_size(self._h, width, height, filter))
+
+    def get_output_size(self) -> Tuple[int, int]:
+        """``ju_tiled_get_output_size``: ``(width, height)``, ``(0, 0)`` while no output size is set."""
+        w, h = C.c_size_t(), C.c_size_t()
+        _check(self._lib, self._lib.ju_tiled_get_output_size(self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def frame_output_size(self) -> Tuple[int, int]:
+        """``(width, height)`` of the frames the object hands out now: the output size set, else the blended size."""
+        w, h = self.get_output_size()
+        return (w, h) if w else (self.out_width, self.out_height)
 
     # -- the scene detector of the tiled stream (docs/tiled.md "Scene cuts") ----------
     def set_scene_detect(self, mode: int, threshold_milli: int = 10000) -> None:
@@ -916,7 +960,9 @@ class TiledRuntime:
     def stat(self, key: str) -> float:
         """``ju_tiled_get_stat``: "tiles", "frames", "group_frames" (summed over the tiles), "deep_from_state" (the
         setting), "hbd_from_state" (the model's property), "deep_state_frames" (frames blended from the states),
-        "scene_mode", "scene_frames" and "scene_cuts" (the tiled stream's detector; the counters are cumulative)."""
+        "scene_mode", "scene_frames" and "scene_cuts" (the tiled stream's detector; the counters are cumulative),
+        "output_scaled", "output_filter" and "output_scaled_frames" (``set_output_size``; frames that took a fused
+        blend-and-scale kernel)."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_tiled_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -19,7 +19,16 @@ ju_tiled_process_frame).  --compare deep runs, instead of tiled / serial, two ob
 "scene_cuts" shows what each saw.  --clip cuts replaces the four noise frames (no cut: S_t is large and constant) by four
 smooth scenes of four frames each, a cut every fourth frame.
 
---trace WxH runs one variant alone (--deep-from-state 0 | 1, --scene off | report | reset, --out-format, --clip) for a `rocprofv3 --kernel-trace --stats` run;
+--compare output --output WxH --filter triangle | catmull-rom | mitchell runs two objects that both advance as group passes:
+  output_off:  no output size -- the blended frame of four times the source (the yardstick);
+  output_on:   ju_tiled_set_output_size(W, H, filter) -- blend and scale in one launch (docs/tiled.md "An output size");
+both with --deep-from-state (with --out-format p010 and 1: the 16-bit route); "output_scaled_frames" shows each one's route.
+
+--trace WxH runs one variant alone (--deep-from-state 0 | 1, --scene off | report | reset, --out-format, --clip, --output
+and --filter: the output size set) for a `rocprofv3 --kernel-trace --stats` run; with --two-launch the output size is NOT
+set and every frame is followed by the existing scaler alone, through its hook, at the sizes --output names: scale_bgrx_kernel
+over the blended BGRX frame, or (an --out-format other than bgrx) scale_state_kernel over a state of the blended size --
+what a route of two launches would add to the blend;
 --summarize <kernel_stats.csv> WxH prints the tile kernels' and the 10-bit 4:2:0 encodes' time per call from such a run,
 and the least time the bytes they must move would take at the copy bandwidth measured for the MI355X (6.29 TB/s, a
 float4 copy): their share of it."""
@@ -38,10 +47,12 @@ sys.path.insert(0, ROOT)
 
 COPY_BYTES_PER_S = 6.29e12
 TILE_KERNELS = ("tile_split_kernel", "tile_split_scene_kernel", "scene_clear_tiles_kernel", "tile_stitch_kernel", "tile_stitch_state_kernel", "frame16_to_yuv420p10_kernel",
-                "bgrx_to_yuv420p10_kernel")
+                "bgrx_to_yuv420p10_kernel", "tile_stitch_scale_kernel", "tile_stitch_scale_state_kernel", "scale_bgrx_kernel", "scale_state_kernel")
 # what a variant is: created under JU_LOOKAHEAD=1 (no passes), its ju_tiled_set_deep_from_state, its scene mode
 VARIANTS = {"tiled": (False, 0, 0), "serial": (True, 0, 0), "deep_off": (False, 0, 0), "deep_on": (False, 1, 0),
-            "scene_off": (False, 0, 0), "scene_report": (False, 0, 1), "scene_reset": (False, 0, 2)}
+            "scene_off": (False, 0, 0), "scene_report": (False, 0, 1), "scene_reset": (False, 0, 2),
+            "output_off": (False, 0, 0), "output_on": (False, 0, 0)}
+FILTERS = {"triangle": 0, "catmull-rom": 2, "mitchell": 3}
 SCENE_NAMES = {"off": "scene_off", "report": "scene_report", "reset": "scene_reset"}
 # output formats: (the runtime's FMT_ name, per plane (rows per output row, bytes per output pixel of a row))
 OUT_FORMATS = {"bgrx": ("FMT_BGRX", [(1, 4)]), "nv12": ("FMT_NV12", [(1, 1), (0.5, 1)]), "p010": ("FMT_P010", [(1, 2), (0.5, 2)]),
@@ -53,8 +64,10 @@ def size(text):
     return w, h
 
 
-def kernel_bytes(sw, sh, w, h, ov):
-    """The bytes each kernel must move: the split reads the source once and writes every tile; the stitch reads every
+def kernel_bytes(sw, sh, w, h, ov, output=None):
+    """The bytes each kernel must move (output: (OW, OH) for the kernels of an output size -- a fused kernel reads what
+    the stitch reads and writes the scaled frame, the scaler alone reads the blended frame and writes the scaled one; 4
+    bytes per pixel for the 8-bit kernels, 8 for the 16-bit ones): the split reads the source once and writes every tile; the stitch reads every
     output pixel once where one tile covers it -- and the seams' pixels from two or four -- and writes the frame; the
     stitch of the states the same at 8 bytes per pixel; a P010 encode reads its frame (8 or 4 bytes per pixel) and writes
     3 bytes per pixel.  The split with the detector also reads and rewrites the kept source-size frame; the conditional
@@ -68,17 +81,30 @@ def kernel_bytes(sw, sh, w, h, ov):
         return int((1 + (q != 0)).sum())
     split = 4 * sw * sh + 4 * w * h * nx * ny
     stitch = 4 * reads(sw, w) * reads(sh, h) + 64 * sw * sh
+    scaled = {}
+    if output:
+        out_px, read = output[0] * output[1], reads(sw, w) * reads(sh, h)
+        scaled = {"tile_stitch_scale_kernel": 4 * read + 4 * out_px, "tile_stitch_scale_state_kernel": 8 * read + 8 * out_px,
+                  "scale_bgrx_kernel": 64 * sw * sh + 4 * out_px, "scale_state_kernel": 128 * sw * sh + 8 * out_px}
+        # (the encode then runs at one of two sizes, which a stats file does not tell: its time alone)
+        return {**scaled, "tiles": [nx, ny], "tile_split_kernel": split, "tile_split_scene_kernel": split + 8 * sw * sh,
+                "tile_stitch_kernel": stitch, "tile_stitch_state_kernel": 2 * stitch}
     return {"tiles": [nx, ny], "tile_split_kernel": split, "tile_split_scene_kernel": split + 8 * sw * sh, "tile_stitch_kernel": stitch, "tile_stitch_state_kernel": 2 * stitch,
             "frame16_to_yuv420p10_kernel": (8 + 3) * 16 * sw * sh, "bgrx_to_yuv420p10_kernel": (4 + 3) * 16 * sw * sh}
 
 
-def summarize(path, sw, sh, w, h, ov):
-    need = kernel_bytes(sw, sh, w, h, ov)
+def summarize(path, sw, sh, w, h, ov, output=None):
+    import re
+    need = kernel_bytes(sw, sh, w, h, ov, output)
     out = {"stats": path, "source": f"{sw}x{sh}", "tiles": need["tiles"], "copy_bandwidth_TBps": COPY_BYTES_PER_S / 1e12}
+    if output:
+        out["output"] = f"{output[0]}x{output[1]}"
     with open(path) as f:
         for r in csv.DictReader(f):
             for k in TILE_KERNELS:
-                if k in r["Name"]:                                 # (no name of the list is part of another)
+                # (the whole name: some end in another's; a name left mangled carries it behind its length)
+                if re.search(r"(^|[^A-Za-z0-9_])" + k + r"($|[^A-Za-z0-9_])", r["Name"]) or \
+                        (r["Name"].startswith("_Z") and f"{len(k)}{k}" in r["Name"]):
                     us = float(r["TotalDurationNs"]) / 1e3 / int(r["Calls"])
                     if k not in need:
                         out[k] = {"calls": int(r["Calls"]), "us_per_call": round(us, 2)}
@@ -92,7 +118,8 @@ def summarize(path, sw, sh, w, h, ov):
 class Pair:
     """The variants for one source size, with their device frames."""
 
-    def __init__(self, sw, sh, preset, dtype, ov, names=("tiled", "serial"), out_format="bgrx", clip="noise", threshold=10000):
+    def __init__(self, sw, sh, preset, dtype, ov, names=("tiled", "serial"), out_format="bgrx", clip="noise", threshold=10000,
+                 output=None, deep=None, two_launch=None):
         import torch
         from joshupscale_amd import model_file as M
         from joshupscale_amd import runtime as R
@@ -101,15 +128,18 @@ class Pair:
         blob = M.serialize(cfg, M.make_seeded_weights(cfg))
         dt = {"bf16": R.DTYPE_BF16, "fp16": R.DTYPE_F16, "fp8": R.DTYPE_FP8}[dtype]
         self.obj = {}
+        deep_all = deep
         for name in names:
             serial, deep, scene = VARIANTS[name]
             if serial:
                 os.environ["JU_LOOKAHEAD"] = "1"
             try:
-                self.obj[name] = R.TiledRuntime(blob, 0, dt, sw, sh, ov, hooks=False)
+                self.obj[name] = R.TiledRuntime(blob, 0, dt, sw, sh, ov, hooks=two_launch is not None)
             finally:
                 os.environ.pop("JU_LOOKAHEAD", None)
-            self.obj[name].set_deep_from_state(deep)
+            self.obj[name].set_deep_from_state(deep_all if deep_all is not None else deep)
+            if output and name != "output_off":
+                self.obj[name].set_output_size(*output)
             if scene:
                 self.obj[name].set_scene_detect(scene, threshold)
         if clip == "cuts":
@@ -121,24 +151,41 @@ class Pair:
         self.count = len(clip)
         self.d_in = torch.from_numpy(clip).to(dev)
         fmt_name, planes = OUT_FORMATS[out_format]
-        self.d_out = [torch.zeros((int(4 * sh * rows), 4 * sw * width), dtype=torch.uint8, device=dev) for rows, width in planes]
-        torch.cuda.synchronize()
         self.frames = out_format != "bgrx"       # (ju_tiled_process_frame; else ju_tiled_process on two images)
+        self.d_out, self.out = {}, {}
+        for name, o in self.obj.items():         # (each variant's frames at the size it hands out)
+            fw, fh = o.frame_output_size()
+            self.d_out[name] = [torch.zeros((int(fh * rows), fw * width), dtype=torch.uint8, device=dev) for rows, width in planes]
+            if self.frames:
+                self.out[name] = R.device_frame(getattr(R, fmt_name), fw, fh, self.d_out[name])
+            else:
+                self.out[name] = R.JuImage(self.d_out[name][0].data_ptr(), R.LOC_DEVICE, 4 * fw, fw, fh)
         if self.frames:
             self.ins = [R.device_frame(R.FMT_BGRX, sw, sh, [self.d_in[t].data_ptr()]) for t in range(self.count)]
-            self.out = R.device_frame(getattr(R, fmt_name), 4 * sw, 4 * sh, self.d_out)
         else:
             self.ins = [R.JuImage(self.d_in[t].data_ptr(), R.LOC_DEVICE, 4 * sw, sw, sh) for t in range(self.count)]
-            self.out = R.JuImage(self.d_out[0].data_ptr(), R.LOC_DEVICE, 16 * sw, 4 * sw, 4 * sh)
         self.lib = next(iter(self.obj.values()))._lib
+        # --two-launch: the existing scaler alone behind every frame (its hook), blended size -> (OW, OH, filter)
+        self.two = None
+        if two_launch is not None:
+            ow, oh, filt = two_launch
+            op = 1 if self.frames else 0
+            src = torch.zeros((4 * sh, 4 * sw * 8), dtype=torch.uint8, device=dev) if op else self.d_out[names[0]][0]
+            dst = torch.zeros((oh, ow * (8 if op else 4)), dtype=torch.uint8, device=dev)
+            self.two = (op, filt, dst, 4 * ow, ow, oh, src, 16 * sw, 4 * sw, 4 * sh)
+        torch.cuda.synchronize()
 
     def run(self, name, frames):
         h = self.obj[name]._h
         call = self.lib.ju_tiled_process_frame if self.frames else self.lib.ju_tiled_process
         t0 = time.perf_counter()
         for t in range(frames):
-            if call(h, C.byref(self.ins[t % self.count]), C.byref(self.out)) != 0:
+            if call(h, C.byref(self.ins[t % self.count]), C.byref(self.out[name])) != 0:
                 raise RuntimeError(self.lib.ju_last_error().decode())
+            if self.two:
+                op, filt, dst, stride, ow, oh, src, src_stride, bw, bh = self.two
+                if self.lib.ju_debug_scale(op, filt, dst.data_ptr(), stride, ow, oh, src.data_ptr(), src_stride, bw, bh, None, None, None) != 0:
+                    raise RuntimeError(self.lib.ju_last_error().decode())
         return time.perf_counter() - t0          # (every call is synchronous)
 
     def close(self):
@@ -156,39 +203,52 @@ def main():
     ap.add_argument("--frames", type=int, default=240, help="frames per variant and round")
     ap.add_argument("--warmup", type=int, default=24)
     ap.add_argument("--out-format", default="bgrx", choices=sorted(OUT_FORMATS))
-    ap.add_argument("--compare", default="passes", choices=["passes", "deep", "scene"],
+    ap.add_argument("--compare", default="passes", choices=["passes", "deep", "scene", "output"],
                     help="passes: tiled against serial; deep: ju_tiled_set_deep_from_state 0 against 1; scene: the scene "
-                         "detector off, JU_SCENE_REPORT and JU_SCENE_RESET")
+                         "detector off, JU_SCENE_REPORT and JU_SCENE_RESET; output: no output size against --output")
+    ap.add_argument("--output", default=None, metavar="WxH", help="--compare output, --trace, --summarize: the output size")
+    ap.add_argument("--filter", default="triangle", choices=sorted(FILTERS), help="the output size's filter")
+    ap.add_argument("--two-launch", action="store_true", help="--trace: the existing scaler alone behind every frame")
     ap.add_argument("--scene", default="off", choices=sorted(SCENE_NAMES), help="--trace: the scene mode of the one variant")
     ap.add_argument("--clip", default="noise", choices=["noise", "cuts"])
     ap.add_argument("--threshold", type=int, default=10000, help="threshold_milli of the scene detector")
-    ap.add_argument("--deep-from-state", type=int, default=0, choices=[0, 1], help="--trace: the setting of the one variant")
+    ap.add_argument("--deep-from-state", type=int, default=0, choices=[0, 1],
+                    help="--trace: the setting of the one variant; --compare output: of both")
     ap.add_argument("--trace", default=None, metavar="WxH")
     ap.add_argument("--summarize", nargs=2, metavar=("CSV", "WxH"), default=None)
     args = ap.parse_args()
     from joshupscale_amd import model_file as M
     cfg = M.PRESETS[args.preset]
     if args.summarize:
-        summarize(args.summarize[0], *size(args.summarize[1]), cfg.frame_width, cfg.frame_height, args.overlap)
+        summarize(args.summarize[0], *size(args.summarize[1]), cfg.frame_width, cfg.frame_height, args.overlap,
+                  size(args.output) if args.output else None)
         return
+    output = (*size(args.output), FILTERS[args.filter]) if args.output else None
+    if (args.compare == "output" or args.two_launch) and not output:
+        ap.error("--compare output and --two-launch need --output WxH")
     import torch
     torch.zeros(1, device="cuda:0")  # (torch's HIP runtime first, as bench.py does)
     if args.trace:
         name = "deep_on" if args.deep_from_state else SCENE_NAMES[args.scene] if args.scene != "off" else "tiled"
-        p = Pair(*size(args.trace), args.preset, args.dtype, args.overlap, (name,), args.out_format, args.clip, args.threshold)
+        p = Pair(*size(args.trace), args.preset, args.dtype, args.overlap, (name,), args.out_format, args.clip, args.threshold,
+                 output=None if args.two_launch else output, two_launch=output if args.two_launch else None)
         p.run(name, args.warmup)
         p.run(name, args.frames)
         print(json.dumps({"trace": args.trace, "variant": name, "out_format": args.out_format, "frames": args.warmup + args.frames,
+                          "output": args.output, "filter": args.filter, "two_launch": args.two_launch,
+                          "output_scaled_frames": p.obj[name].stat("output_scaled_frames"),
                           "group_frames": p.obj[name].stat("group_frames"),
                           "deep_state_frames": p.obj[name].stat("deep_state_frames"), "clip": args.clip,
                           "scene_cuts": p.obj[name].stat("scene_cuts")}))
         p.close()
         return
     res = {}
-    names = {"deep": ("deep_off", "deep_on"), "scene": ("scene_off", "scene_report", "scene_reset")}.get(args.compare, ("tiled", "serial"))
+    names = {"deep": ("deep_off", "deep_on"), "scene": ("scene_off", "scene_report", "scene_reset"),
+             "output": ("output_off", "output_on")}.get(args.compare, ("tiled", "serial"))
     for text in args.sizes:
         sw, sh = size(text)
-        p = Pair(sw, sh, args.preset, args.dtype, args.overlap, names, args.out_format, args.clip, args.threshold)
+        p = Pair(sw, sh, args.preset, args.dtype, args.overlap, names, args.out_format, args.clip, args.threshold,
+                 output=output if args.compare == "output" else None, deep=args.deep_from_state if args.compare == "output" else None)
         for name in p.obj:
             p.run(name, args.warmup)
         fps = {name: [] for name in p.obj}
@@ -207,13 +267,18 @@ def main():
         row["frames"] = {name: o.stat("frames") for name, o in p.obj.items()}
         if args.compare == "scene":
             row["scene_cuts"] = {name: o.stat("scene_cuts") for name, o in p.obj.items()}
+        if args.compare == "output":
+            row["output_scaled_frames"] = {name: o.stat("output_scaled_frames") for name, o in p.obj.items()}
+            row["output"], row["filter"], row["deep_from_state"] = args.output, args.filter, args.deep_from_state
         res[text] = row
         p.close()
     what = {"tiled": "the tiles as group passes", "serial": "the same object created under JU_LOOKAHEAD=1: every tile "
             "through ju_process, the same two kernels", "deep_off": "ju_tiled_set_deep_from_state 0: a deep format from the "
             "blended 8-bit frame", "deep_on": "ju_tiled_set_deep_from_state 1: from the blend of the tiles' f16 states",
             "scene_off": "the scene detector off: the split alone", "scene_report": "JU_SCENE_REPORT: the split and the "
-            "detector in one launch", "scene_reset": "JU_SCENE_RESET: that launch and the conditional clear of all tiles"}
+            "detector in one launch", "scene_reset": "JU_SCENE_RESET: that launch and the conditional clear of all tiles",
+            "output_off": "no output size: the blended frame of four times the source",
+            "output_on": "ju_tiled_set_output_size: blend and scale in one launch"}
     print(json.dumps({"metric": "frames/s of ju_tiled_process, device BGRX in, device " + args.out_format.upper() + " out",
                       "preset": args.preset, "dtype": args.dtype, "overlap": args.overlap, "frames_per_round": args.frames,
                       "rounds": args.rounds, "clip": args.clip, "variants": {name: what[name] for name in names}, "fps": res}))
