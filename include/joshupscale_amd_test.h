@@ -303,6 +303,95 @@ JU_API int ju_debug_tile_split_scene(const void *src, ptrdiff_t src_stride, size
 JU_API int ju_debug_scene_clear_tiles(int count, const void *flag, void *const *a, const size_t *a_bytes, void *const *b,
     const size_t *b_bytes);
 
+/* ---- the network's compute kernels alone (docs/exact_tests.md; the definitions: tests/exact_reference.py) ----------------
+ * Each hook is ONE synchronous launch of a product launcher on caller-supplied device buffers, on the current device, with
+ * its arguments in a struct.  Whatever the launcher would throw on, a NULL or misaligned buffer (16 bytes for 16-bit
+ * tensors), a size outside 1 .. 4096, a pitch below the row or an item stride below the tensor is
+ * JU_ERR_INVALID_ARGUMENT with a message, before any device call.
+ * Weights and bias are HOST f32 arrays in the folded order [taps][cin_real][cout] / [cout]; cin_real (1 .. cin) may be
+ * below the padded channel count `cin` of the tensor.  The hook packs them with the product's packConvWeights (cinMap =
+ * 0 .. cin_real - 1, then -1) for the kernel's nb and uploads them: the packer is part of what runs.
+ * ju_debug_plan: the developer launch plan (the fields of DevPlan, csrc/kernels.h: JU_FLOW_TILE, JU_RES_BLOCK,
+ * JU_CONV_DBUF, JU_SPLITK_PLAN, JU_CONV_TILE); conv_stages -1 and every other field 0 = the launcher's own choice.
+ * plan_text / plan_capacity (NULL / 0: not wanted): receives the launch's lines of ju_plan_report, NUL-terminated,
+ * cut at the capacity. */
+typedef struct ju_debug_plan {
+	int flow_tile, res_block, conv_stages, splitk_rows, splitk_blocks, conv_nb, conv_rw;
+} ju_debug_plan;
+
+/* kernel 0: launchConv (conv_mfma_kernel); 1: launchConvSplitK (conv_splitk_kernel; the hook supplies the zero page);
+ * 2: launchConvTower (conv_tower_kernel) -- in / res / out are then the INTERIOR ORIGINS of tower-layout tensors
+ * [8 ceil(H / 8) + 2][32 ceil(W / 32) + 2][64] whose border and surplus rows / columns are zero, every pitch is
+ * 32 ceil(W / 32) + 2, and a shape launchConvTower would hand to launchConv is refused.  The other fields are
+ * ConvParams' (csrc/kernels.h): pitches in pixels (0: dense), `upsample`: `in` is [H / 2][W / 2][cin] with in_pitch in its
+ * pixels, `pool`: `out` is [H / 2][W / 2][cout] with out_pitch in its pixels, out_head: `out` is f16 whatever the dtype;
+ * items 1 .. 8 with the byte strides between the items' tensors (multiples of 16, at least a tensor; items > 1 takes no
+ * res and no tower).  dtype: JU_DTYPE_F16 / JU_DTYPE_BF16. */
+typedef struct ju_debug_conv_args {
+	int kernel, dtype;
+	const void *in, *res;
+	void *out;
+	const float *weights, *bias;
+	int H, W, cin, cin_real, cout, taps, relu;
+	float slope;
+	int out_head, pool, upsample, nb, rw;
+	int in_pitch, out_pitch, res_pitch;
+	int items;
+	long long in_item_bytes, out_item_bytes;
+	ju_debug_plan plan;
+	char *plan_text;
+	size_t plan_capacity;
+} ju_debug_conv_args;
+JU_API int ju_debug_conv(const ju_debug_conv_args *args);
+
+/* launchFlowBlock (flow_block_kernel; residual: res_block_pipe_kernel, with plan.res_block 1 or a LeakyReLU res_block_kernel,
+ * with plan.res_block 2 flow_block_kernel's residual form): conv A 3x3 cin -> cmid, act1, conv B 3x3 cmid -> cmid,
+ * [+ in], act2, [2x2 max-pool].  weights1 [9][cin_real][cmid], weights2 [9][cmid][cmid].  The shapes are the launcher's
+ * table (flow_kernels.hip JU_FB_CASE); the input-packing, independent-item and cut-aware forms of the first block are not
+ * reachable from here.  A residual launch takes one item. */
+typedef struct ju_debug_flow_block_args {
+	int dtype;
+	const void *in;
+	void *out;
+	const float *weights1, *bias1, *weights2, *bias2;
+	int H, W, cin, cin_real, cmid;
+	int upsample, pool, out_head, residual, act1, act2;
+	float slope;
+	int in_pitch, out_pitch;
+	int items;
+	long long in_item_bytes, out_item_bytes;
+	ju_debug_plan plan;
+	char *plan_text;
+	size_t plan_capacity;
+} ju_debug_flow_block_args;
+JU_API int ju_debug_flow_block(const ju_debug_flow_block_args *args);
+
+/* op 0: launchUpsample2 -- `items` dense tensors [H][W][C] one after the other -> [2 H][2 W][C] each; op 1: launchMaxPool2 --
+ * [H][W][C] (H, W even) -> [H / 2][W / 2][C], items 1.  C a multiple of 8. */
+typedef struct ju_debug_resample_args {
+	int op, dtype;
+	const void *in;
+	void *out;
+	int H, W, C, items;
+} ju_debug_resample_args;
+JU_API int ju_debug_resample(const ju_debug_resample_args *args);
+
+/* launchWarpPack with every argument (csrc/kernels.h): state f16 [4 H][4 W][4] (8-byte aligned), flow f16 [..][PW][32]
+ * read at (h + pad_top, w + pad_left), frame BGRX rows (4-byte aligned, signed stride a multiple of 4), out: the 64-slot
+ * records at image pixel (0, 0), out_pitch in pixels (0: W); sums (may be NULL; passed through), pre_warp_out (may be
+ * NULL) f16 [4 H][4 W][4], out_u8 (may be NULL) BGRX rows of 4 W x 4 H, 4-byte aligned, signed stride a multiple of 4. */
+typedef struct ju_debug_warp_args {
+	int dtype;
+	const void *state, *flow, *frame;
+	ptrdiff_t frame_stride;
+	void *out;
+	int out_pitch, H, W, PW, pad_top, pad_left;
+	const void *sums;
+	void *pre_warp_out, *out_u8;
+	ptrdiff_t out_stride;
+} ju_debug_warp_args;
+JU_API int ju_debug_warp(const ju_debug_warp_args *args);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

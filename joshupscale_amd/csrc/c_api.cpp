@@ -1363,6 +1363,308 @@ int ju_debug_e4m3(const float *values, unsigned char *codes, size_t count) {
 		for (size_t i = 0; i < count; ++i) codes[i] = ju::e4m3FromFloat(values[i]);
 	});
 }
+
+// ---- the network's compute kernels alone (docs/exact_tests.md) --------------------------------------------------------------
+}  // extern "C"
+namespace {
+
+constexpr int kDebugAxisMax = 4096;
+
+struct DebugRefuse {
+	const char *hook;
+	[[noreturn]] void operator()(const std::string &why) const { throw std::invalid_argument(std::string(hook) + ": " + why); }
+};
+
+bool misaligned(const void *p, std::uintptr_t a) { return reinterpret_cast<std::uintptr_t>(p) % a != 0; }
+
+ju::DType debugDType(const DebugRefuse &refuse, int dtype) {
+	if (dtype != JU_DTYPE_F16 && dtype != JU_DTYPE_BF16) refuse("dtype must be JU_DTYPE_F16 or JU_DTYPE_BF16");
+	return dtype == JU_DTYPE_F16 ? ju::kF16 : ju::kBF16;
+}
+
+void debugActivation(const DebugRefuse &refuse, int act, float slope) {
+	if (act < 0 || act > 2) refuse("an activation code outside 0 .. 2");
+	// the model loader's bound (model.cpp): max(x, slope x) is LeakyReLU only for a slope in [0, 1]
+	if (act == 2 && !(slope >= 0.0f && slope <= 1.0f)) refuse("a LeakyReLU slope outside [0, 1]");
+}
+
+ju::DevPlan debugPlan(const DebugRefuse &refuse, const ju_debug_plan &p, ju::PlanLog *log) {
+	if (p.flow_tile < 0 || p.res_block < 0 || p.res_block > 2 || p.conv_stages < -1 || p.conv_stages > 2 || p.splitk_rows < 0 ||
+	    p.splitk_blocks < 0 || p.splitk_blocks > 2 || p.conv_nb < 0 || p.conv_nb > 2 || p.conv_rw < 0 || p.conv_rw > 2) {
+		refuse("a plan field out of range");
+	}
+	ju::DevPlan plan;
+	plan.flowTile = p.flow_tile;
+	plan.resBlock = p.res_block;
+	plan.convStages = p.conv_stages;
+	plan.splitkRows = p.splitk_rows;
+	plan.splitkBlocks = p.splitk_blocks;
+	plan.convNb = p.conv_nb;
+	plan.convRw = p.conv_rw;
+	plan.log = log;
+	return plan;
+}
+
+void debugPlanText(const ju::PlanLog &log, char *dst, std::size_t capacity) {
+	if (dst == nullptr || capacity == 0) return;
+	const std::string text = log.text();
+	const std::size_t n = std::min(text.size(), capacity - 1);
+	std::memcpy(dst, text.data(), n);
+	dst[n] = '\0';
+}
+
+// host f32 [taps][cinReal][cout] -> the kernel-ready weights on the device, through the product's packer
+ju::DeviceBuffer debugPackWeights(const float *w, int taps, int cinReal, int cinPadded, int cout, int nb, ju::DType dt) {
+	ju::FoldedConv conv;
+	conv.taps = taps;
+	conv.cin = cinReal;
+	conv.cout = cout;
+	conv.w.assign(w, w + static_cast<std::size_t>(taps) * cinReal * cout);
+	std::vector<int> cinMap(static_cast<std::size_t>(cinPadded), -1);
+	for (int c = 0; c < cinReal; ++c) cinMap[static_cast<std::size_t>(c)] = c;
+	const std::vector<std::uint16_t> packed = ju::packConvWeights(conv, cinMap, nb, dt);
+	ju::DeviceBuffer dev(packed.size() * 2);
+	dev.upload(packed.data(), packed.size() * 2);
+	return dev;
+}
+
+ju::DeviceBuffer debugUploadBias(const float *bias, int cout) {
+	ju::DeviceBuffer dev(static_cast<std::size_t>(cout) * 4);
+	dev.upload(bias, static_cast<std::size_t>(cout) * 4);
+	return dev;
+}
+
+// pitch (pixels, 0 = dense) of a tensor `width` pixels wide; item stride of `rows` such rows of `channels` 16-bit values
+void debugPitch(const DebugRefuse &refuse, int pitch, int width, const char *what) {
+	if (pitch != 0 && (pitch < width || pitch > 2 * kDebugAxisMax)) refuse(std::string(what) + " pitch below the row (or beyond 8192)");
+}
+void debugItemStride(const DebugRefuse &refuse, int items, long long stride, int pitch, int width, int rows, int channels, const char *what) {
+	if (items <= 1) return;
+	const long long tensor = 2ll * (pitch ? pitch : width) * rows * channels;
+	if (stride < tensor || stride % 16 != 0 || stride > (1ll << 32)) {
+		refuse(std::string(what) + " item stride must be a multiple of 16, at least the tensor");
+	}
+}
+
+}  // namespace
+extern "C" {
+
+int ju_debug_conv(const ju_debug_conv_args *a) {
+	return guarded([&] {
+		const DebugRefuse refuse{"ju_debug_conv"};
+		if (a == nullptr) refuse("null arguments");
+		const ju::DType dt = debugDType(refuse, a->dtype);
+		if (a->kernel < 0 || a->kernel > 2) refuse("kernel must be 0 (conv), 1 (split-K) or 2 (tower)");
+		if (a->in == nullptr || a->out == nullptr || a->weights == nullptr || a->bias == nullptr) refuse("null buffer");
+		if ((a->plan_text == nullptr) != (a->plan_capacity == 0)) refuse("plan_text and plan_capacity go together");
+		if (misaligned(a->in, 16) || misaligned(a->out, 16) || misaligned(a->res, 16)) refuse("tensors must be 16-byte aligned");
+		if (a->H < 1 || a->W < 1 || a->H > kDebugAxisMax || a->W > kDebugAxisMax) refuse("a size outside 1 .. 4096");
+		if (a->cin < 16 || a->cin > 1024 || a->cout < 32 || a->cout > 1024 || a->cin_real < 1 || a->cin_real > a->cin) {
+			refuse("channels: cin 16 .. 1024, cin_real 1 .. cin, cout 32 .. 1024");
+		}
+		debugActivation(refuse, a->relu, a->slope);
+		const int items = a->items;
+		if (items < 1 || items > ju::kFlowBatchMax) refuse("items must be 1 .. 8");
+		// launchConvT's own checks, in its words
+		if (a->cin % 16 != 0 || a->cout % 32 != 0 || (a->nb != 1 && a->nb != 2) || (a->rw != 1 && a->rw != 2) ||
+		    a->cout % (32 * a->nb) != 0) {
+			refuse("conv: cin must be a multiple of 16, cout of 32*nb");
+		}
+		if (a->taps != 9 && a->taps != 1) refuse("conv: unsupported shape");
+		if (a->taps == 1 && ju::convCK(a->cin) == 16) refuse("conv: unsupported shape");
+		// (the tile form is launchConv's: the split-K kernel has its own and is held to convSplitKSupported below)
+		if (a->pool && ((a->kernel != 1 && a->rw != 2) || a->H % 2 || a->W % 2 || a->res != nullptr || a->out_head)) {
+			refuse("conv: fused max-pool needs rw = 2, even H and W, 16-bit output");
+		}
+		if (a->upsample && (a->taps != 9 || ju::convCK(a->cin) != 64 || a->nb != 1 || a->H % 2 || a->W % 2 || a->pool)) {
+			refuse("conv: fused upsampling needs 3x3, cin % 64 == 0, nb = 1, even H and W");
+		}
+		if (items > 1 && a->res != nullptr) refuse("launchConv: a look-ahead launch (items > 1) takes no residual");
+		const int inW = a->upsample ? a->W / 2 : a->W, inH = a->upsample ? a->H / 2 : a->H;
+		const int outW = a->pool ? a->W / 2 : a->W, outH = a->pool ? a->H / 2 : a->H;
+		debugPitch(refuse, a->in_pitch, inW, "input");
+		debugPitch(refuse, a->out_pitch, outW, "output");
+		debugPitch(refuse, a->res_pitch, a->W, "residual");
+		debugItemStride(refuse, items, a->in_item_bytes, a->in_pitch, inW, inH, a->cin, "input");
+		debugItemStride(refuse, items, a->out_item_bytes, a->out_pitch, outW, outH, a->cout, "output");
+
+		ju::PlanLog log;
+		const ju::DevPlan plan = debugPlan(refuse, a->plan, &log);
+		ju::ConvParams p{};
+		p.in = a->in;
+		p.res = a->res;
+		p.out = a->out;
+		p.H = a->H;
+		p.W = a->W;
+		p.cin = a->cin;
+		p.cout = a->cout;
+		p.taps = a->taps;
+		p.relu = a->relu;
+		p.slope = a->slope;
+		p.outHead = a->out_head ? 1 : 0;
+		p.pool = a->pool ? 1 : 0;
+		p.upsample = a->upsample ? 1 : 0;
+		p.inPitch = a->in_pitch;
+		p.outPitch = a->out_pitch;
+		p.resPitch = a->res_pitch;
+		p.nb = a->nb;
+		p.rw = a->rw;
+		p.items = items;
+		p.inItemBytes = static_cast<long>(a->in_item_bytes);
+		p.outItemBytes = static_cast<long>(a->out_item_bytes);
+		p.plan = &plan;
+		if (a->kernel == 1 && !ju::convSplitKSupported(p)) refuse("split-K conv: unsupported layer");
+		if (a->kernel == 2) {
+			const int pitch = ju::towerPitch(a->W);
+			const bool fits = a->taps == 9 && a->cin == 64 && a->cout == 64 && !a->out_head && a->nb == 2 && a->in_pitch == pitch &&
+			                  a->out_pitch == pitch && (a->res == nullptr || a->res_pitch == pitch);
+			if (!fits || a->pool || a->upsample || items > 1) {
+				refuse("the tower kernel needs 3x3 64 -> 64, nb = 2, one item, no pool or upsampling, and every pitch towerPitch(W)");
+			}
+		}
+
+		const ju::DeviceBuffer wgt = debugPackWeights(a->weights, a->taps, a->cin_real, a->cin, a->cout, a->nb, dt);
+		const ju::DeviceBuffer bias = debugUploadBias(a->bias, a->cout);
+		p.wgt = wgt.get();
+		p.bias = bias.as<float>();
+		if (a->kernel == 0) {
+			ju::launchConv(dt, p, nullptr);
+		} else if (a->kernel == 1) {
+			const ju::DeviceBuffer zeros(256);  // (DeviceBuffer memory starts zeroed)
+			ju::launchConvSplitK(dt, p, zeros.get(), nullptr);
+			JU_HIP(hipStreamSynchronize(nullptr));
+		} else {
+			ju::launchConvTower(dt, p, nullptr);
+		}
+		JU_HIP(hipStreamSynchronize(nullptr));
+		debugPlanText(log, a->plan_text, a->plan_capacity);
+	});
+}
+
+int ju_debug_flow_block(const ju_debug_flow_block_args *a) {
+	return guarded([&] {
+		const DebugRefuse refuse{"ju_debug_flow_block"};
+		if (a == nullptr) refuse("null arguments");
+		const ju::DType dt = debugDType(refuse, a->dtype);
+		if (a->in == nullptr || a->out == nullptr || a->weights1 == nullptr || a->bias1 == nullptr || a->weights2 == nullptr ||
+		    a->bias2 == nullptr) {
+			refuse("null buffer");
+		}
+		if ((a->plan_text == nullptr) != (a->plan_capacity == 0)) refuse("plan_text and plan_capacity go together");
+		if (misaligned(a->in, 16) || misaligned(a->out, 16)) refuse("tensors must be 16-byte aligned");
+		if (a->H < 1 || a->W < 1 || a->H > kDebugAxisMax || a->W > kDebugAxisMax) refuse("a size outside 1 .. 4096");
+		debugActivation(refuse, a->act1, a->slope);
+		debugActivation(refuse, a->act2, a->slope);
+		const int items = a->items;
+		if (items < 1) refuse("items must be 1 .. 8");
+		if (items > ju::kFlowBatchMax) refuse("flow block: more look-ahead frames than kFlowBatchMax");
+		if (items > 1 && a->residual) refuse("flow block: the residual form has no look-ahead launch");
+		if (a->upsample && (a->H % 2 || a->W % 2)) refuse("flow block: fused upsampling needs even H and W");
+		if (a->pool && (a->H % 2 || a->W % 2)) refuse("flow block: fused max-pool needs even H and W");
+		// the launcher's table (flow_kernels.hip JU_FB_CASE): cin, cmid, upsample, pool, 0 plain / 1 flow head / 2 residual
+		static const int table[10][5] = {{16, 32, 0, 1, 0}, {32, 64, 0, 1, 0}, {64, 128, 0, 1, 0}, {256, 128, 1, 0, 0},
+		    {256, 128, 0, 0, 0}, {128, 64, 1, 0, 0}, {128, 64, 0, 0, 0}, {64, 32, 1, 0, 1}, {64, 32, 0, 0, 1}, {64, 64, 0, 0, 2}};
+		if (a->residual && a->out_head) refuse("flow block: unsupported shape");
+		const int outk = a->residual ? 2 : (a->out_head ? 1 : 0);
+		bool known = false;
+		for (const auto &t : table) {
+			known = known || (a->cin == t[0] && a->cmid == t[1] && (a->upsample != 0) == (t[2] != 0) && (a->pool != 0) == (t[3] != 0) &&
+			                     outk == t[4]);
+		}
+		if (!known) refuse("flow block: unsupported shape");
+		if (a->cin_real < 1 || a->cin_real > a->cin) refuse("cin_real must be 1 .. cin");
+		const int inW = a->upsample ? a->W / 2 : a->W, inH = a->upsample ? a->H / 2 : a->H;
+		const int outW = a->pool ? a->W / 2 : a->W, outH = a->pool ? a->H / 2 : a->H;
+		debugPitch(refuse, a->in_pitch, inW, "input");
+		debugPitch(refuse, a->out_pitch, outW, "output");
+		debugItemStride(refuse, items, a->in_item_bytes, a->in_pitch, inW, inH, a->cin, "input");
+		debugItemStride(refuse, items, a->out_item_bytes, a->out_pitch, outW, outH, a->cmid, "output");
+
+		ju::PlanLog log;
+		const ju::DevPlan plan = debugPlan(refuse, a->plan, &log);
+		const ju::DeviceBuffer w1 = debugPackWeights(a->weights1, 9, a->cin_real, a->cin, a->cmid, 1, dt);
+		const ju::DeviceBuffer w2 = debugPackWeights(a->weights2, 9, a->cmid, a->cmid, a->cmid, 1, dt);
+		const ju::DeviceBuffer b1 = debugUploadBias(a->bias1, a->cmid);
+		const ju::DeviceBuffer b2 = debugUploadBias(a->bias2, a->cmid);
+		ju::FlowBlockLaunch q{};
+		q.in = a->in;
+		q.w1 = w1.get();
+		q.b1 = b1.as<float>();
+		q.w2 = w2.get();
+		q.b2 = b2.as<float>();
+		q.out = a->out;
+		q.H = a->H;
+		q.W = a->W;
+		q.inPitch = a->in_pitch;
+		q.outPitch = a->out_pitch;
+		q.cin = a->cin;
+		q.cmid = a->cmid;
+		q.upsample = a->upsample != 0;
+		q.pool = a->pool != 0;
+		q.outHead = a->out_head != 0;
+		q.residual = a->residual != 0;
+		q.act1 = a->act1;
+		q.act2 = a->act2;
+		q.slope = a->slope;
+		q.items = items;
+		q.inItemBytes = static_cast<long>(a->in_item_bytes);
+		q.outItemBytes = static_cast<long>(a->out_item_bytes);
+		q.plan = &plan;
+		ju::launchFlowBlock(dt, q, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+		debugPlanText(log, a->plan_text, a->plan_capacity);
+	});
+}
+
+int ju_debug_resample(const ju_debug_resample_args *a) {
+	return guarded([&] {
+		const DebugRefuse refuse{"ju_debug_resample"};
+		if (a == nullptr) refuse("null arguments");
+		const ju::DType dt = debugDType(refuse, a->dtype);
+		if (a->op != 0 && a->op != 1) refuse("op must be 0 (upsample) or 1 (max-pool)");
+		if (a->in == nullptr || a->out == nullptr) refuse("null buffer");
+		if (misaligned(a->in, 16) || misaligned(a->out, 16)) refuse("tensors must be 16-byte aligned");
+		if (a->H < 1 || a->W < 1 || a->H > kDebugAxisMax || a->W > kDebugAxisMax) refuse("a size outside 1 .. 4096");
+		if (a->C < 8 || a->C > 1024 || a->C % 8 != 0) refuse("C must be a multiple of 8, 8 .. 1024");
+		if (a->items < 1 || a->items > ju::kFlowBatchMax) refuse("items must be 1 .. 8");
+		if (a->op == 1 && (a->H % 2 || a->W % 2)) refuse("the max-pool needs even H and W");
+		if (a->op == 1 && a->items != 1) refuse("the max-pool takes one item");
+		if (a->op == 0) ju::launchUpsample2(dt, a->in, a->out, a->H, a->W, a->C, nullptr, a->items);
+		else ju::launchMaxPool2(dt, a->in, a->out, a->H, a->W, a->C, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_warp(const ju_debug_warp_args *a) {
+	return guarded([&] {
+		const DebugRefuse refuse{"ju_debug_warp"};
+		if (a == nullptr) refuse("null arguments");
+		const ju::DType dt = debugDType(refuse, a->dtype);
+		if (a->state == nullptr || a->flow == nullptr || a->frame == nullptr || a->out == nullptr) refuse("null buffer");
+		if (a->H < 1 || a->W < 1 || a->H > kDebugAxisMax || a->W > kDebugAxisMax) refuse("a size outside 1 .. 4096");
+		if (a->pad_top < 0 || a->pad_left < 0 || a->pad_top > kDebugAxisMax || a->pad_left > kDebugAxisMax ||
+		    a->PW < a->W + a->pad_left || a->PW > 2 * kDebugAxisMax) {
+			refuse("the flow field: pads 0 .. 4096 and PW at least W + pad_left");
+		}
+		if (a->out_pitch != 0 && (a->out_pitch < a->W || a->out_pitch > 2 * kDebugAxisMax)) refuse("output pitch below the row (or beyond 8192)");
+		if (misaligned(a->state, 8) || misaligned(a->pre_warp_out, 8)) refuse("the f16 state tensors must be 8-byte aligned");
+		if (misaligned(a->flow, 16) || misaligned(a->out, 16)) refuse("the flow field and the records must be 16-byte aligned");
+		const auto rowOk = [](std::ptrdiff_t stride, std::ptrdiff_t row) { return stride % 4 == 0 && (stride >= row || -stride >= row); };
+		if (misaligned(a->frame, 4) || !rowOk(a->frame_stride, 4 * static_cast<std::ptrdiff_t>(a->W))) {
+			refuse("the LR frame must be 4-byte aligned with a stride that is a multiple of 4 and at least a row");
+		}
+		if (misaligned(a->sums, 4)) refuse("sums must be 4-byte aligned");
+		if (a->out_u8 != nullptr) {
+			// (the launcher's own refusal, in its words)
+			if (misaligned(a->out_u8, 4) || a->out_stride % 4 != 0) refuse("warp_pack: the frame output must be 4-byte aligned");
+			if (!rowOk(a->out_stride, 16 * static_cast<std::ptrdiff_t>(a->W))) refuse("the frame output's stride is below its row");
+		}
+		ju::launchWarpPack(dt, a->state, a->flow, static_cast<const std::uint8_t *>(a->frame), a->frame_stride, a->out, a->out_pitch,
+		    a->H, a->W, a->PW, a->pad_top, a->pad_left, static_cast<const unsigned *>(a->sums), a->pre_warp_out,
+		    static_cast<std::uint8_t *>(a->out_u8), a->out_stride, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
 #endif  // JU_TEST_HOOKS
 
 const char *ju_version(void) {

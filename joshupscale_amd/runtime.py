@@ -190,6 +190,48 @@ class JuTiledInfo(C.Structure):
                 ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("overlap", C.c_int)]
 
 
+# the argument structs of the compute-kernel hooks (include/joshupscale_amd_test.h; docs/exact_tests.md)
+class JuDebugPlan(C.Structure):
+    """``ju_debug_plan``: the developer launch plan of one hook launch (conv_stages -1, the rest 0: the launcher's choice)."""
+    _fields_ = [(n, C.c_int) for n in ("flow_tile", "res_block", "conv_stages", "splitk_rows", "splitk_blocks", "conv_nb",
+                                       "conv_rw")]
+
+
+class JuDebugConv(C.Structure):
+    """``ju_debug_conv_args``."""
+    _fields_ = [("kernel", C.c_int), ("dtype", C.c_int), ("inp", C.c_void_p), ("res", C.c_void_p), ("out", C.c_void_p),
+                ("weights", C.c_void_p), ("bias", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("H", "W", "cin", "cin_real", "cout", "taps", "relu")] + [("slope", C.c_float)] + \
+               [(n, C.c_int) for n in ("out_head", "pool", "upsample", "nb", "rw", "in_pitch", "out_pitch", "res_pitch", "items")] + \
+               [("in_item_bytes", C.c_longlong), ("out_item_bytes", C.c_longlong), ("plan", JuDebugPlan),
+                ("plan_text", C.c_void_p), ("plan_capacity", C.c_size_t)]
+
+
+class JuDebugFlowBlock(C.Structure):
+    """``ju_debug_flow_block_args``."""
+    _fields_ = [("dtype", C.c_int), ("inp", C.c_void_p), ("out", C.c_void_p), ("weights1", C.c_void_p), ("bias1", C.c_void_p),
+                ("weights2", C.c_void_p), ("bias2", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("H", "W", "cin", "cin_real", "cmid", "upsample", "pool", "out_head", "residual", "act1",
+                                       "act2")] + [("slope", C.c_float)] + \
+               [(n, C.c_int) for n in ("in_pitch", "out_pitch", "items")] + \
+               [("in_item_bytes", C.c_longlong), ("out_item_bytes", C.c_longlong), ("plan", JuDebugPlan),
+                ("plan_text", C.c_void_p), ("plan_capacity", C.c_size_t)]
+
+
+class JuDebugResample(C.Structure):
+    """``ju_debug_resample_args``."""
+    _fields_ = [("op", C.c_int), ("dtype", C.c_int), ("inp", C.c_void_p), ("out", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("H", "W", "C", "items")]
+
+
+class JuDebugWarp(C.Structure):
+    """``ju_debug_warp_args``."""
+    _fields_ = [("dtype", C.c_int), ("state", C.c_void_p), ("flow", C.c_void_p), ("frame", C.c_void_p),
+                ("frame_stride", C.c_ssize_t), ("out", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("out_pitch", "H", "W", "PW", "pad_top", "pad_left")] + \
+               [("sums", C.c_void_p), ("pre_warp_out", C.c_void_p), ("out_u8", C.c_void_p), ("out_stride", C.c_ssize_t)]
+
+
 def hooks_default() -> bool:
     """``JU_TEST_HOOKS=1`` (set by tests/conftest.py and the developer tools): the process works
     through libJoshUpscale_test.so.  Unset -- every caller of the product -- it is the product library."""
@@ -326,6 +368,10 @@ _HOOK_SIGS = {
                                             C.c_uint32, C.c_int]),
     "ju_debug_scene_clear_tiles": (C.c_int, [C.c_int, C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p),
                                              _P(C.c_size_t)]),
+    "ju_debug_conv": (C.c_int, [_P(JuDebugConv)]),
+    "ju_debug_flow_block": (C.c_int, [_P(JuDebugFlowBlock)]),
+    "ju_debug_resample": (C.c_int, [_P(JuDebugResample)]),
+    "ju_debug_warp": (C.c_int, [_P(JuDebugWarp)]),
     "ju_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "ju_time_steps": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),
     "ju_plan_report": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, _P(C.c_size_t)]),

@@ -43,6 +43,12 @@ depth; bounds 1.4 x those.  8-bit towers of 1-2 blocks: 0.341 / 620 / 0.057 (bou
 the first part of that measurement: 1.1-1.4 x).  The 8-bit deviation is larger because the e4m3 matrix instruction
 does not return correctly rounded sums (tools/probes/fp8_mfma_accumulation_probe.hip); deeper 8-bit towers are not
 compared element for element.
+
+The network's compute kernels alone have no tolerance at all (docs/exact_tests.md): test_gpu_exact_conv.py and
+test_gpu_exact_warp.py run the convolution, flow-block, resampling and warp kernels one launch at a time on dyadic inputs,
+for which every partial sum is exact in f32 whatever the order, against integer arithmetic plus one round to nearest even
+(tests/exact_reference.py), word for word.  Their records here (`record(("exact", case), ...)`) carry no PSNR but three
+counts: zeros mapped (-0 is not told from +0), outputs the final rounding changed, exact ties among them.
 """
 
 import json
