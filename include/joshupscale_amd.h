@@ -693,6 +693,33 @@ JU_API int ju_tiled_set_deep_from_state(ju_tiled *tiled, int on);
  * "output_scaled_frames" (the frames that took a fused blend-and-scale kernel). */
 JU_API int ju_tiled_set_output_size(ju_tiled *tiled, size_t width, size_t height, int filter);
 JU_API int ju_tiled_get_output_size(const ju_tiled *tiled, size_t *width, size_t *height);
+/* A source mask for tiled frames (docs/tiled.md "A mask"; no reference counterpart in the core; the OBS filter's
+ * blend.effect: obs_plugin/src/filter.cc:215-217, 393-402, as ju_set_source_mask).  From now on the source frame of each
+ * call is drawn back over the blended frame through `mask`, so HUD, subtitles and text stay the crisp source: a BGRX image
+ * of any size, each axis 1 .. 16384, JU_LOC_CPU or JU_LOC_DEVICE, any stride of either sign; copied to device memory now.
+ * NULL turns it off.  By definition (tests/tiled_mask_reference.py), in integers, with B x Bh = 4 src_width x 4 src_height
+ * the blended frame and c the source frame of the call as the split reads it (a device BGRX image in place, a host image as
+ * staged, any other format as decoded at source size):
+ *   masked = ju_set_source_mask's blend of the blended 8-bit frame: a = 765 - (Bm + Gm + Rm) at the mask texel
+ *   floor((2 X + 1) MW / (2 B)), likewise in y; out = (c a + blend (765 - a) + 382) / 765 per byte of B, G, R with c the
+ *   source texel (X >> 2, Y >> 2); X = 0; a pixel with a == 0 is the blended pixel unchanged.  The blend rounds to bytes
+ *   first, the mask works on those bytes, and under ju_tiled_set_output_size the scaler follows: mask at the blended size,
+ *   then the scale, as a plain runtime does.  The blend is applied to the blended sample in registers inside the stitch's
+ *   launch -- also the fused blend-and-scale launch, which never stores the blended frame.
+ * Every other format is the 8-bit encode of that frame; while a mask is set a deep format is encoded from the 8-bit frame
+ * (257 x u8), the rule of ju_process_frame under a mask: ju_tiled_set_deep_from_state is accepted and has no effect, and
+ * "deep_state_frames" does not advance.  Tile inputs and states, frame history, group passes and the scene detector do not
+ * know about the mask.  A source of exactly W x H, ONE tile, gives the frames of ju_process / ju_process_frame under
+ * ju_set_source_mask with the same mask (and ju_set_output_size where one is set).
+ * At set time the host computes the box, the rectangle of blended coordinates that holds every pixel whose mask texel is
+ * not white (a device mask is read back once for it); outside it the kernels read no mask and no source and do what the
+ * unmasked kernels do, and a mask without such a pixel costs nothing.
+ * JU_ERR_INVALID_ARGUMENT, the setting as it was: a graphics resource, a NULL image, a size out of range, |stride| smaller
+ * than a row, 2 B MW >= 2^32 or 2 Bh MH >= 2^32.  ju_tiled_reset, ju_tiled_set_output_size and ju_tiled_set_scene_detect
+ * keep the mask.
+ * ju_tiled_get_stat: "source_mask" (1 / 0), "source_mask_frames" (the frames processed while a mask was set),
+ * "mask_box_x0", "mask_box_y0", "mask_box_x1", "mask_box_y1" (the box; all 0 while the mask is off or the box is empty). */
+JU_API int ju_tiled_set_source_mask(ju_tiled *tiled, const ju_image *mask);
 JU_API int ju_tiled_get_info(const ju_tiled *tiled, ju_tiled_info *info);
 /* The origin of tile `index` (0 .. tiles_x tiles_y - 1, row-major over the tile grid) in source pixels. */
 JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t *y);
@@ -701,7 +728,8 @@ JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t
  * ju_tiled_set_deep_from_state; "hbd_from_state": 1 where the model's f16 state is its frame in float (ju_get_stat's key,
  * every tile's alike); "deep_state_frames": the frames whose output was blended from the tiles' states;
  * "scene_mode", "scene_frames", "scene_cuts": the detector below, the two counters cumulative as ju_get_stat's;
- * "output_scaled", "output_filter", "output_scaled_frames": ju_tiled_set_output_size above.  An unknown key is
+ * "output_scaled", "output_filter", "output_scaled_frames": ju_tiled_set_output_size above; "source_mask",
+ * "source_mask_frames", "mask_box_x0" .. "mask_box_y1": ju_tiled_set_source_mask above.  An unknown key is
  * JU_ERR_INVALID_ARGUMENT. */
 JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value);
 /* The scene detector of a tiled stream (docs/tiled.md "Scene cuts"; no reference counterpart).  ju_set_scene_detect's
@@ -721,9 +749,9 @@ JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *val
 JU_API int ju_tiled_set_scene_detect(ju_tiled *tiled, int mode, uint32_t threshold_milli);
 JU_API int ju_tiled_get_scene_detect(const ju_tiled *tiled, int *mode, uint32_t *threshold_milli);
 JU_API int ju_tiled_get_scene_info(ju_tiled *tiled, ju_scene_info *out, int count, int *written);
-/* Not provided for a tiled object: look-ahead passes, ju_set_source_size and the mask (the output size is
- * ju_tiled_set_output_size, the scene detector ju_tiled_set_scene_detect), graphics resources, graph capture, the C++
- * plugin surface. */
+/* Not provided for a tiled object: look-ahead passes and ju_set_source_size (the output size is
+ * ju_tiled_set_output_size, the mask ju_tiled_set_source_mask, the scene detector ju_tiled_set_scene_detect), graphics
+ * resources, graph capture, the C++ plugin surface. */
 
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing

@@ -283,6 +283,25 @@ JU_API int ju_debug_tile_stitch_scale(void *dst, ptrdiff_t dst_stride, size_t ds
     size_t src_width, size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count);
 JU_API int ju_debug_tile_stitch_scale_state(void *dst16, size_t dst_width, size_t dst_height, int filter, size_t src_width,
     size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count);
+/* The two kernels of a tiled object's source mask alone (tile_stitch_mask_kernel, tile_stitch_mask_scale_kernel;
+ * docs/tiled.md "A mask"; the definitions: tests/tiled_mask_reference.py masked / frame8), each ONE synchronous launch on
+ * caller-supplied device buffers, on the current device: the arguments of ju_debug_tile_stitch / ju_debug_tile_stitch_scale,
+ * held to the same limits, then `source`, the device BGRX rows of the src_width x src_height source, and `mask`, device
+ * BGRX rows of mask_width x mask_height (1 .. 16384 each) -- addresses and signed strides multiples of 4.  The hooks compute
+ * the box themselves, by the product's function, from the mask read back to the host.  A NULL `mask` is no mask: the
+ * unmasked hook's launch.  Refused with JU_ERR_INVALID_ARGUMENT before any device call: what the unmasked hooks refuse, a
+ * NULL source, a misaligned source, mask or (unscaled) destination, |stride| smaller than a row, a mask size out of range,
+ * 2 x blended extent x mask extent not below 2^32.
+ * ju_debug_mask_box touches no device: the box (x0, y0, x1, y1 into box[4]; all 0: empty) of a HOST mask over a blended
+ * frame of width x height (csrc/mask_box.h; tests/tiled_mask_reference.py box). */
+JU_API int ju_debug_tile_stitch_mask(void *dst, ptrdiff_t dst_stride, size_t src_width, size_t src_height, size_t tile_width,
+    size_t tile_height, int overlap, void *const *tiles, int count, const void *source, ptrdiff_t source_stride, const void *mask,
+    ptrdiff_t mask_stride, size_t mask_width, size_t mask_height);
+JU_API int ju_debug_tile_stitch_mask_scale(void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, int filter,
+    size_t src_width, size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count,
+    const void *source, ptrdiff_t source_stride, const void *mask, ptrdiff_t mask_stride, size_t mask_width, size_t mask_height);
+JU_API int ju_debug_mask_box(const void *mask, ptrdiff_t mask_stride, size_t mask_width, size_t mask_height, size_t width,
+    size_t height, int *box);
 
 /* The two kernels of a tiled stream's scene detector alone (docs/tiled.md "Scene cuts"), each ONE synchronous launch on
  * caller-supplied device buffers, on the current device.

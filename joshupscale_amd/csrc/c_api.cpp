@@ -427,6 +427,15 @@ int ju_tiled_set_output_size(ju_tiled *tiled, size_t width, size_t height, int f
 	return guarded([&] { tiledOf(tiled).setOutputSize(width, height, filter); });
 }
 
+int ju_tiled_set_source_mask(ju_tiled *tiled, const ju_image *mask) {
+	return guarded([&] {
+		ju::TiledRuntime &t = tiledOf(tiled);
+		if (mask == nullptr) return t.setSourceMask(nullptr);
+		const ju::Frame f = toFrame(mask);
+		t.setSourceMask(&f);
+	});
+}
+
 int ju_tiled_get_output_size(const ju_tiled *tiled, size_t *width, size_t *height) {
 	return guarded([&] { tiledOf(const_cast<ju_tiled *>(tiled)).outputSize(width, height); });
 }
@@ -1663,6 +1672,121 @@ int ju_debug_warp(const ju_debug_warp_args *a) {
 		    a->H, a->W, a->PW, a->pad_top, a->pad_left, static_cast<const unsigned *>(a->sums), a->pre_warp_out,
 		    static_cast<std::uint8_t *>(a->out_u8), a->out_stride, nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+namespace {
+// What both masked hooks check behind debugTileSet, before any device call: the source's and the mask's rows and the mask's
+// size against the blended frame.  Then the box, by the product's function, from the mask read back to the host.
+void debugTileMask(const std::string &name, size_t src_width, size_t src_height, const void *source, ptrdiff_t source_stride,
+    const void *mask, ptrdiff_t mask_stride, size_t mask_width, size_t mask_height, ju::TileMask *out) {
+	if (source == nullptr) throw std::invalid_argument(name + ": null source");
+	const std::string problem = ju::maskSizeProblem(mask_width, mask_height, 4 * src_width, 4 * src_height);
+	if (!problem.empty()) throw std::invalid_argument(name + ": " + problem);
+	if (reinterpret_cast<std::uintptr_t>(source) % 4 || source_stride % 4 || reinterpret_cast<std::uintptr_t>(mask) % 4 || mask_stride % 4) {
+		throw std::invalid_argument(name + ": the source's and the mask's address and stride must be multiples of 4");
+	}
+	const auto srcRow = static_cast<ptrdiff_t>(4 * src_width), maskRow = static_cast<ptrdiff_t>(4 * mask_width);
+	if ((source_stride > -srcRow && source_stride < srcRow) || (mask_stride > -maskRow && mask_stride < maskRow)) {
+		throw std::invalid_argument(name + ": |stride| of the source or the mask smaller than a row");
+	}
+	// the mask's rows in memory order, read back once; the box from them
+	const ju::RowSpan rows = ju::rowSpan(const_cast<void *>(mask), mask_stride, mask_height);
+	const size_t pitch = rows.pitch, bytes = pitch * (mask_height - 1) + static_cast<size_t>(maskRow);
+	std::vector<std::uint8_t> back(bytes);
+	JU_HIP(hipMemcpy(back.data(), rows.lowest, bytes, hipMemcpyDeviceToHost));
+	const std::uint8_t *first = rows.topDown ? back.data() : back.data() + (mask_height - 1) * pitch;
+	const ju::MaskBox box = ju::maskBox(first, mask_stride, static_cast<int>(mask_width), static_cast<int>(mask_height),
+	    static_cast<int>(4 * src_width), static_cast<int>(4 * src_height));
+	ju::TileMask &m = *out;
+	m.src = static_cast<const std::uint8_t *>(source);
+	m.srcStride = source_stride;
+	m.mask = static_cast<const std::uint8_t *>(mask);
+	m.maskStride = mask_stride;
+	m.maskW = static_cast<int>(mask_width);
+	m.maskH = static_cast<int>(mask_height);
+	m.x0 = box.x0, m.y0 = box.y0, m.x1 = box.x1, m.y1 = box.y1;
+}
+}  // namespace
+
+int ju_debug_tile_stitch_mask(void *dst, ptrdiff_t dst_stride, size_t src_width, size_t src_height, size_t tile_width,
+    size_t tile_height, int overlap, void *const *tiles, int count, const void *source, ptrdiff_t source_stride, const void *mask,
+    ptrdiff_t mask_stride, size_t mask_width, size_t mask_height) {
+	if (mask == nullptr) {  // no mask: the unmasked launch, as the object routes it
+		return ju_debug_tile_stitch(dst, dst_stride, src_width, src_height, tile_width, tile_height, overlap, tiles, count);
+	}
+	return guarded([&] {
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		const std::string name = "ju_debug_tile_stitch_mask";
+		debugTileSet(name.c_str(), src_width, src_height, tile_width, tile_height, overlap, tiles, count, dst, dst_stride, 4 * src_width, &set,
+		    &nx, &ny);
+		if (reinterpret_cast<std::uintptr_t>(dst) % 4 || dst_stride % 4) {
+			throw std::invalid_argument(name + ": the frame's address and stride must be multiples of 4");
+		}
+		for (int k = 0; k < count; ++k) {
+			if (set.ptr[k] == nullptr || reinterpret_cast<std::uintptr_t>(set.ptr[k]) % 16) {
+				throw std::invalid_argument(name + ": tile " + std::to_string(k) + " is NULL or not 16-byte aligned");
+			}
+		}
+		ju::TileMask m;
+		debugTileMask(name, src_width, src_height, source, source_stride, mask, mask_stride, mask_width, mask_height, &m);
+		const ju::TileAxis x = ju::tileAxis(static_cast<long>(src_width), static_cast<long>(tile_width), overlap);
+		const ju::TileAxis y = ju::tileAxis(static_cast<long>(src_height), static_cast<long>(tile_height), overlap);
+		ju::DeviceBuffer xTable(x.table.size() * sizeof(ju::TileAxisEntry)), yTable(y.table.size() * sizeof(ju::TileAxisEntry));
+		xTable.upload(x.table.data(), x.table.size() * sizeof(ju::TileAxisEntry));
+		yTable.upload(y.table.data(), y.table.size() * sizeof(ju::TileAxisEntry));
+		ju::launchTileStitchMask(static_cast<std::uint8_t *>(dst), dst_stride, static_cast<int>(4 * src_width), static_cast<int>(4 * src_height),
+		    set, nx, ny, static_cast<int>(4 * tile_width), xTable.as<unsigned>(), yTable.as<unsigned>(), m, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_tile_stitch_mask_scale(void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height, int filter, size_t src_width,
+    size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, int count, const void *source,
+    ptrdiff_t source_stride, const void *mask, ptrdiff_t mask_stride, size_t mask_width, size_t mask_height) {
+	if (mask == nullptr) {  // no mask: the unmasked launch, as the object routes it
+		return ju_debug_tile_stitch_scale(dst, dst_stride, dst_width, dst_height, filter, src_width, src_height, tile_width, tile_height,
+		    overlap, tiles, count);
+	}
+	return guarded([&] {
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		const std::string name = "ju_debug_tile_stitch_mask_scale";
+		debugTileSet(name.c_str(), src_width, src_height, tile_width, tile_height, overlap, tiles, count, dst, dst_stride, dst_width, &set,
+		    &nx, &ny);
+		// (the size limits and the tiles' alignment first, then the mask's; the tables' device memory behind both)
+		const std::string problem = ju::tiledOutputSizeProblem(dst_width, dst_height, src_width, src_height, filter);
+		if (!problem.empty()) throw std::invalid_argument(name + ": " + problem);
+		for (int k = 0; k < count; ++k) {
+			if (set.ptr[k] == nullptr || reinterpret_cast<std::uintptr_t>(set.ptr[k]) % 16) {
+				throw std::invalid_argument(name + ": tile " + std::to_string(k) + " is NULL or not 16-byte aligned");
+			}
+		}
+		ju::TileMask m;
+		debugTileMask(name, src_width, src_height, source, source_stride, mask, mask_stride, mask_width, mask_height, &m);
+		DebugStitchScale d;
+		debugStitchScale(name, dst_width, dst_height, filter, src_width, src_height, tile_width, tile_height, overlap, set, count, &d);
+		ju::launchTileStitchMaskScale(static_cast<std::uint8_t *>(dst), dst_stride, static_cast<int>(dst_width), static_cast<int>(dst_height),
+		    static_cast<int>(4 * src_width), static_cast<int>(4 * src_height), set, nx, ny, static_cast<int>(4 * tile_width),
+		    d.xTable.as<unsigned>(), d.yTable.as<unsigned>(), d.scale.xAxis(), d.scale.yAxis(), d.scale.span(), m, nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_mask_box(const void *mask, ptrdiff_t mask_stride, size_t mask_width, size_t mask_height, size_t width, size_t height,
+    int *box) {
+	return guarded([&] {
+		const std::string name = "ju_debug_mask_box";
+		if (mask == nullptr || box == nullptr) throw std::invalid_argument(name + ": null argument");
+		if (width < 1 || height < 1 || width > (1u << 20) || height > (1u << 20)) throw std::invalid_argument(name + ": a frame size outside 1 .. 2^20");
+		const std::string problem = ju::maskSizeProblem(mask_width, mask_height, width, height);
+		if (!problem.empty()) throw std::invalid_argument(name + ": " + problem);
+		const auto row = static_cast<ptrdiff_t>(4 * mask_width);
+		if (mask_stride > -row && mask_stride < row) throw std::invalid_argument(name + ": |stride| smaller than a row");
+		const ju::MaskBox b = ju::maskBox(static_cast<const std::uint8_t *>(mask), mask_stride, static_cast<int>(mask_width),
+		    static_cast<int>(mask_height), static_cast<int>(width), static_cast<int>(height));
+		box[0] = b.x0, box[1] = b.y0, box[2] = b.x1, box[3] = b.y1;
 	});
 }
 #endif  // JU_TEST_HOOKS

@@ -771,6 +771,25 @@ void launchTileStitchScale(std::uint8_t *dst, std::ptrdiff_t dstStride, int dstW
 void launchTileStitchScaleState(std::uint16_t *dst16, int dstW, int dstH, int outW, int outH, const TileSet &states, int nx, int ny,
     int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y, int spanX,
     hipStream_t stream);
+// A tiled object's source mask (docs/tiled.md "A mask"; tests/tiled_mask_reference.py): launchMaskBlend's arithmetic on
+// the BLENDED sample while it is in registers.  src: BGRX rows of the source, outW / 4 x outH / 4, whose texel under
+// blended pixel (X, Y) is (X >> 2, Y >> 2); mask: BGRX rows of maskW x maskH, point sampled at floor((2 X + 1) maskW /
+// (2 outW)) -- addresses and signed strides multiples of 4, 2 x blended extent x mask extent below 2^32 on both axes.
+// [x0, x1) x [y0, y1): the box (mask_box.h), inside the blended frame; outside it the kernels read neither and take the
+// unmasked kernels' path.
+struct TileMask {
+	const std::uint8_t *src = nullptr, *mask = nullptr;
+	std::ptrdiff_t srcStride = 0, maskStride = 0;
+	int maskW = 0, maskH = 0;
+	int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+};
+// launchTileStitch with the mask: masked = blend(stitch(tiles), src, mask), X = 0.  outW and outH multiples of four.
+void launchTileStitchMask(std::uint8_t *dst, std::ptrdiff_t dstStride, int outW, int outH, const TileSet &tiles, int nx, int ny,
+    int tileOutW, const unsigned *xTable, const unsigned *yTable, const TileMask &mask, hipStream_t stream);
+// launchTileStitchScale with the mask applied to each blended pixel, at the blended size, BEFORE the scaler multiplies it.
+void launchTileStitchMaskScale(std::uint8_t *dst, std::ptrdiff_t dstStride, int dstW, int dstH, int outW, int outH, const TileSet &tiles,
+    int nx, int ny, int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y,
+    int spanX, const TileMask &mask, hipStream_t stream);
 
 // *word += 1 (system scope) once everything enqueued before it on `stream` has completed: `word` is the device address of
 // host-mapped memory (PinnedWords) that the host polls.  Host frames inside look-ahead passes (Engine::processBatch).

@@ -22,6 +22,10 @@
 //   tile_stitch_scale_kernel, tile_stitch_scale_state_kernel  the two blends FUSED into the output scaler (docs/tiled.md
 //                       "An output size"; tests/tiled_output_reference.py): the scale kernels' tile (scale_tile.h) whose
 //                       vertical pass forms each blended sample in registers, so the frame of 4 Ws x 4 Hs is never stored.
+//   tile_stitch_mask_kernel, tile_stitch_mask_scale_kernel  the 8-bit stitch and its fused form under a SOURCE MASK
+//                       (docs/tiled.md "A mask"; tests/tiled_mask_reference.py): inside the mask's box (mask_box.h) the
+//                       blended pixel is mixed with the source pixel through its mask texel while it is in registers --
+//                       mask_blend_kernel's integers; outside the box the unmasked kernels' path, no mask or source read.
 //
 // Split and stitch are bound by memory: the split moves 2 x 4 Ws Hs bytes and a little more (the overlaps are read and
 // written twice), the stitch 2 x 64 Ws Hs.  Tile pointers and origins travel by value in the kernel arguments (TileSet); the
@@ -259,6 +263,107 @@ __global__ __launch_bounds__(256) void tile_stitch_kernel(std::uint8_t *__restri
 	}
 }
 
+// ---- the source mask (docs/tiled.md "A mask"; tests/tiled_mask_reference.py) ---------------------------------------------
+// mask_blend_kernel's arithmetic (source_kernels.hip) on a blended pixel g in registers: m the mask texel, s the source
+// pixel; a = 765 - (Bm + Gm + Rm), out = (s a + g (765 - a) + 382) / 765 per byte of B, G, R, X = 0; a == 0: g as it is.
+__device__ __forceinline__ unsigned maskPixel(unsigned g, unsigned s, unsigned m) {
+	const unsigned a = 765u - ((m & 255u) + ((m >> 8) & 255u) + ((m >> 16) & 255u));
+	if (a == 0) return g;
+	unsigned out = 0;
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const unsigned sc = (s >> (8 * c)) & 255u, gc = (g >> (8 * c)) & 255u;
+		out |= ((sc * a + gc * (765u - a) + 382u) / 765u) << (8 * c);
+	}
+	return out;
+}
+
+constexpr unsigned kWhiteTexel = 0x00ffffffu;  // a == 0: what a pixel outside the box takes for its mask texel
+
+// The mask texels and the source pixels of up to four blended pixels X .. X + 3 of row Y, those inside [X, xEnd) and inside
+// the box; the others white.  The addresses depend on coordinates only, so the loads are issued in front of the tile loads
+// of the same pixels.  The source texel of (X, Y) is (X >> 2, Y >> 2): the blended frame is exactly four times the source.
+struct MaskTaps {
+	unsigned m[4], s[4];
+};
+__device__ __forceinline__ MaskTaps maskTaps(const TileMask &mk, int X, int xEnd, int Y, unsigned outW, unsigned outH) {
+	const unsigned my = (2u * static_cast<unsigned>(Y) + 1u) * static_cast<unsigned>(mk.maskH) / (2u * outH);
+	const std::uint8_t *mrow = mk.mask + static_cast<std::ptrdiff_t>(my) * mk.maskStride;
+	const std::uint8_t *srow = mk.src + static_cast<std::ptrdiff_t>(Y >> 2) * mk.srcStride;
+	MaskTaps t;
+#pragma unroll
+	for (int i = 0; i < 4; ++i) {
+		const int x = X + i;
+		const bool in = x < xEnd && x >= mk.x0 && x < mk.x1;
+		const unsigned mx = (2u * static_cast<unsigned>(x) + 1u) * static_cast<unsigned>(mk.maskW) / (2u * outW);
+		t.m[i] = in ? *reinterpret_cast<const unsigned *>(mrow + 4 * static_cast<std::size_t>(mx)) : kWhiteTexel;
+		t.s[i] = in ? *reinterpret_cast<const unsigned *>(srow + 4 * static_cast<std::size_t>(x >> 2)) : 0u;
+	}
+	return t;
+}
+
+// tile_stitch_kernel with the mask: the same grid, groups, head and tail rules and stores.  A group wholly outside the box
+// takes tile_stitch_kernel's path as it stands; a group that touches the box forms its pixels the same way and then blends
+// those inside the box with the source through their mask texels.
+__global__ __launch_bounds__(256) void tile_stitch_mask_kernel(std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int outW,
+    int outH, const TileSet tiles, int nx, int tileOutW, const unsigned *__restrict__ xTable,
+    const unsigned *__restrict__ yTable, const TileMask mk) {
+	const int group = blockIdx.x * 64 + threadIdx.x;
+	for (int Y = blockIdx.y * 4 + threadIdx.y; Y < outH; Y += gridDim.y * 4) {
+		std::uint8_t *row = dst + static_cast<std::ptrdiff_t>(Y) * dstStride;
+		const int head = static_cast<int>(((16u - (reinterpret_cast<std::uintptr_t>(row) & 15u)) & 15u) >> 2);
+		const int X0 = group == 0 ? 0 : head + 4 * (group - 1);
+		const int X1 = group == 0 ? min(head, outW) : min(X0 + 4, outW);
+		if (X0 >= X1) continue;
+		const bool boxed = Y >= mk.y0 && Y < mk.y1 && X0 < mk.x1 && X1 > mk.x0;
+		MaskTaps t;
+		if (boxed) t = maskTaps(mk, X0, X1, Y, static_cast<unsigned>(outW), static_cast<unsigned>(outH));
+		const unsigned ey = yTable[Y];
+		if (X1 - X0 == 4) {
+			const unsigned e0 = xTable[X0], e1 = xTable[X0 + 1], e2 = xTable[X0 + 2], e3 = xTable[X0 + 3];
+			uint4 v;
+			const std::uint8_t *one = tileAt(tiles, (ey & 0xffffu) * nx + (e0 & 0xffffu), X0, Y, tileOutW);
+			if ((ey >> 16) == 0 && (e0 >> 16) == 0 && e0 == e1 && e0 == e2 && e0 == e3 && aligned16(one)) {
+				v = *reinterpret_cast<const uint4 *>(one);
+				v.x &= kOpaqueMask;
+				v.y &= kOpaqueMask;
+				v.z &= kOpaqueMask;
+				v.w &= kOpaqueMask;
+			} else {
+				v.x = stitchPixel(tiles, nx, e0, ey, X0, Y, tileOutW);
+				v.y = stitchPixel(tiles, nx, e1, ey, X0 + 1, Y, tileOutW);
+				v.z = stitchPixel(tiles, nx, e2, ey, X0 + 2, Y, tileOutW);
+				v.w = stitchPixel(tiles, nx, e3, ey, X0 + 3, Y, tileOutW);
+			}
+			if (boxed) {
+				v.x = maskPixel(v.x, t.s[0], t.m[0]);
+				v.y = maskPixel(v.y, t.s[1], t.m[1]);
+				v.z = maskPixel(v.z, t.s[2], t.m[2]);
+				v.w = maskPixel(v.w, t.s[3], t.m[3]);
+			}
+			std::uint8_t *d = row + static_cast<std::ptrdiff_t>(X0) * 4;
+			if (aligned16(d)) {
+				*reinterpret_cast<uint4 *>(d) = v;
+			} else {  // (a frame narrower than its head: four pixels, but not on a boundary)
+				unsigned *w = reinterpret_cast<unsigned *>(d);
+				w[0] = v.x;
+				w[1] = v.y;
+				w[2] = v.z;
+				w[3] = v.w;
+			}
+			continue;
+		}
+#pragma unroll
+		for (int i = 0; i < 3; ++i) {  // a head or a tail: one to three pixels
+			const int X = X0 + i;
+			if (X >= X1) break;
+			unsigned p = stitchPixel(tiles, nx, xTable[X], ey, X, Y, tileOutW);
+			if (boxed) p = maskPixel(p, t.s[i], t.m[i]);
+			reinterpret_cast<unsigned *>(row)[X] = p;
+		}
+	}
+}
+
 // ---- the blend of the tiles' f16 states (docs/tiled.md "Deep outputs"; tests/tiled_deep_reference.py stitch16) ----------
 // P of one f16 of a state, as StateSource::sample (colour_kernels.hip) forms it: exact in f32
 __device__ __forceinline__ unsigned stateP(unsigned bits) {
@@ -486,6 +591,79 @@ __global__ __launch_bounds__(256) void tile_stitch_scale_state_kernel(std::uint1
 	scaleTile16<kSigned, StitchSource16>({tiles, nx, tileOutW, xTable, yTable}, outW, dst, dstW, dstH, ax, ay, pitch);
 }
 
+// The masked blended 8-bit frame (docs/tiled.md "A mask"): StitchSource8's pixels, and for a quad that touches the box the
+// mask blend of its four pixels -- at the blended size, on the rounded bytes, BEFORE the scaler multiplies them.  A quad
+// starts at x = 0 (mod 4): ONE source texel, (x >> 2, Y >> 2), and four mask texels -- loaded BEHIND the tile loads here:
+// in front of them they stay live across stitchPixel's loads and cost the whole kernel a wave per SIMD (docs/tiled.md).
+struct StitchMaskArgs {
+	StitchArgs stitch;
+	TileMask mask;
+	unsigned outW, outH;  // the blended frame
+};
+
+// what a lane keeps for its quad beside StitchColumn: whether the quad's columns touch the box, and if so the byte offsets
+// of its four mask texels in a mask row -- the divisions are done ONCE, in front of the tap loop (a column outside the box
+// keeps the offset of its neighbour inside: never read)
+struct StitchMaskColumn {
+	StitchColumn c;
+	unsigned mx[4];
+	bool boxed;
+};
+
+struct StitchMaskSource8 {
+	using Args = StitchMaskArgs;
+	using Column = StitchMaskColumn;
+	StitchSource8 base;
+	TileMask mk;
+	unsigned outW, outH;
+	__device__ __forceinline__ explicit StitchMaskSource8(const Args &args) : base(args.stitch), mk(args.mask), outW(args.outW), outH(args.outH) {}
+	__device__ __forceinline__ Column column(int x, int row) const {
+		Column m;
+		m.c = base.column(x, row);
+		m.boxed = x < mk.x1 && x + 4 > mk.x0;
+#pragma unroll
+		for (int i = 0; i < 4; ++i) m.mx[i] = 0;
+		if (m.boxed) {
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				const unsigned X = static_cast<unsigned>(min(max(x + i, mk.x0), mk.x1 - 1));
+				m.mx[i] = (2u * X + 1u) * static_cast<unsigned>(mk.maskW) / (2u * outW) * 4u;
+			}
+		}
+		return m;
+	}
+	__device__ __forceinline__ uint4 load(const Column &m, int x) const {
+		const int Y = m.c.Y;
+		if (!m.boxed || Y < mk.y0 || Y >= mk.y1) return base.load(m.c, x);
+		const uint4 v = base.load(m.c, x);
+		const unsigned my = (2u * static_cast<unsigned>(Y) + 1u) * static_cast<unsigned>(mk.maskH) / (2u * outH);
+		const std::uint8_t *mrow = mk.mask + static_cast<std::ptrdiff_t>(my) * mk.maskStride;
+		const unsigned s = *reinterpret_cast<const unsigned *>(mk.src + static_cast<std::ptrdiff_t>(Y >> 2) * mk.srcStride + x);  // (texel x >> 2 at 4 bytes: x itself)
+		unsigned t[4];
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			const bool in = x + i >= mk.x0 && x + i < mk.x1;
+			t[i] = in ? *reinterpret_cast<const unsigned *>(mrow + m.mx[i]) : kWhiteTexel;
+		}
+		return make_uint4(maskPixel(v.x & kOpaqueMask, s, t[0]), maskPixel(v.y & kOpaqueMask, s, t[1]),
+		    maskPixel(v.z & kOpaqueMask, s, t[2]), maskPixel(v.w & kOpaqueMask, s, t[3]));
+	}
+	__device__ __forceinline__ Column next(Column m) const {
+		m.c = base.next(m.c);
+		return m;
+	}
+};
+
+// tile_stitch_scale_kernel over the masked frame
+template <bool kSigned>
+__global__ __launch_bounds__(256) void tile_stitch_mask_scale_kernel(std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int dstW,
+    int dstH, int outW, int outH, const TileSet set, int nx, int count, int tileOutW, const unsigned *__restrict__ xTable,
+    const unsigned *__restrict__ yTable, ScaleTaps ax, ScaleTaps ay, int pitch, const TileMask mk) {
+	const TileView tiles = tilesToLds(set, count);
+	scaleTile8<kSigned, StitchMaskSource8>({{tiles, nx, tileOutW, xTable, yTable}, mk, static_cast<unsigned>(outW), static_cast<unsigned>(outH)},
+	    outW, dst, dstStride, dstW, dstH, ax, ay, pitch);
+}
+
 void checkTileSet(const char *who, const TileSet &tiles, int count, unsigned align) {
 	if (count < 1 || count > kTileMax) throw std::invalid_argument(std::string(who) + ": 1 .. 64 tiles");
 	for (int k = 0; k < count; ++k) {
@@ -648,6 +826,56 @@ void launchTileStitchScaleState(std::uint16_t *dst16, int dstW, int dstH, int ou
 	hipLaunchKernelGGL(kernel, l.grid, dim3(256), l.lds, stream, dst16, dstW, dstH, outW, states, nx, nx * ny, tileOutW, xTable, yTable,
 	    tx, ty, l.pitch);
 	hipCheckLaunch("tile_stitch_scale_state");
+}
+
+namespace {
+// what both masked launches check: the rows, the 32-bit texel arithmetic, and the box inside the blended frame -- whose
+// pixels' source texels (X >> 2, Y >> 2) then lie inside the source of outW / 4 x outH / 4
+void checkTileMask(const std::string &who, const TileMask &m, int outW, int outH) {
+	if (outW < 4 || outW % 4 || outH < 4 || outH % 4) throw std::invalid_argument(who + ": the blended frame must be four times a source");
+	checkRows(who.c_str(), m.src, m.srcStride);
+	checkRows(who.c_str(), m.mask, m.maskStride);
+	if (m.maskW < 1 || m.maskH < 1) throw std::invalid_argument(who + ": empty mask");
+	const auto below32 = [](int out, int tex) { return 2ull * static_cast<unsigned>(out) * static_cast<unsigned>(tex) < (1ull << 32); };
+	if (!below32(outW, m.maskW) || !below32(outH, m.maskH)) {
+		throw std::invalid_argument(who + ": 2 x blended extent x mask extent must stay below 2^32");
+	}
+	if (m.x0 < 0 || m.y0 < 0 || m.x0 > m.x1 || m.y0 > m.y1 || m.x1 > outW || m.y1 > outH) {
+		throw std::invalid_argument(who + ": the mask's box lies outside the blended frame");
+	}
+}
+}  // namespace
+
+void launchTileStitchMask(std::uint8_t *dst, std::ptrdiff_t dstStride, int outW, int outH, const TileSet &tiles, int nx, int ny,
+    int tileOutW, const unsigned *xTable, const unsigned *yTable, const TileMask &mask, hipStream_t stream) {
+	if (nx < 1 || ny < 1) throw std::invalid_argument("tile_stitch_mask: 1 .. 64 tiles");
+	checkTileSet("tile_stitch_mask", tiles, nx * ny, 16);
+	checkRows("tile_stitch_mask", dst, dstStride);
+	if (outW < 1 || outH < 1 || tileOutW < 1 || xTable == nullptr || yTable == nullptr) {
+		throw std::invalid_argument("tile_stitch_mask: empty frame or NULL table");
+	}
+	checkTileMask("tile_stitch_mask", mask, outW, outH);
+	// (tile_stitch_kernel's grid)
+	const unsigned groups = static_cast<unsigned>(outW) / 4 + 2;
+	const unsigned rows = (static_cast<unsigned>(outH) + 3) / 4;
+	const dim3 grid((groups + 63) / 64, rows < 65535u ? rows : 65535u);
+	hipLaunchKernelGGL(tile_stitch_mask_kernel, grid, dim3(64, 4), 0, stream, dst, dstStride, outW, outH, tiles, nx, tileOutW, xTable,
+	    yTable, mask);
+	hipCheckLaunch("tile_stitch_mask");
+}
+
+void launchTileStitchMaskScale(std::uint8_t *dst, std::ptrdiff_t dstStride, int dstW, int dstH, int outW, int outH, const TileSet &tiles,
+    int nx, int ny, int tileOutW, const unsigned *xTable, const unsigned *yTable, const ScaleAxisDev &x, const ScaleAxisDev &y,
+    int spanX, const TileMask &mask, hipStream_t stream) {
+	// (the 1 KB of tile pointers and origins in LDS is counted with the scaler's tile: stitchScaleLaunch)
+	const StitchScaleLaunch l = stitchScaleLaunch("tile_stitch_mask_scale", dst, dstW, dstH, outW, outH, tiles, nx, ny, tileOutW, xTable,
+	    yTable, x, y, spanX);
+	checkTileMask("tile_stitch_mask_scale", mask, outW, outH);
+	const ScaleTaps tx{x.start, x.taps}, ty{y.start, y.taps};
+	const auto kernel = x.filter != kScaleTriangle ? tile_stitch_mask_scale_kernel<true> : tile_stitch_mask_scale_kernel<false>;
+	hipLaunchKernelGGL(kernel, l.grid, dim3(256), l.lds, stream, dst, dstStride, dstW, dstH, outW, outH, tiles, nx, nx * ny, tileOutW,
+	    xTable, yTable, tx, ty, l.pitch, mask);
+	hipCheckLaunch("tile_stitch_mask_scale");
 }
 
 }  // namespace ju

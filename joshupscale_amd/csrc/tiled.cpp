@@ -3,7 +3,9 @@
 // engines advance by one frame each as group passes (Engine::processGroup: the flow net of a pass's tiles in one pass of
 // its launches), ONE launch blends the tiles' outputs into the frame -- straight into a device BGRX image, else into a
 // staging frame that is copied out or encoded by the existing encode at output size.  With setDeepFromState a deep format
-// is instead encoded from ONE launch's blend of the tiles' f16 states (stitchOutDeep).  The call is synchronous.
+// is instead encoded from ONE launch's blend of the tiles' f16 states (stitchOutDeep).  Under a source mask (setSourceMask)
+// the blend's launch also draws the source rows of step one back over the blended pixels, inside the mask's box.  The call
+// is synchronous.
 #include "tiled.h"
 
 #include <algorithm>
@@ -88,6 +90,12 @@ double TiledRuntime::stat(const std::string &key) const {
 	if (key == "output_scaled") return m_OutScale.set() ? 1.0 : 0.0;
 	if (key == "output_filter") return m_OutScale.filter();
 	if (key == "output_scaled_frames") return static_cast<double>(m_OutputScaledFrames);
+	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
+	if (key == "source_mask_frames") return static_cast<double>(m_MaskFrames);
+	if (key == "mask_box_x0") return m_MaskBox.x0;
+	if (key == "mask_box_y0") return m_MaskBox.y0;
+	if (key == "mask_box_x1") return m_MaskBox.x1;
+	if (key == "mask_box_y1") return m_MaskBox.y1;
 	if (key == "group_frames") {
 		double sum = 0;
 		for (const auto &e : m_Engines) sum += e->stat("group_frames");
@@ -226,6 +234,59 @@ void TiledRuntime::outputSize(std::size_t *width, std::size_t *height) const {
 	if (height) *height = m_OutScale.dstH();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// A source mask (docs/tiled.md "A mask"): Engine::setSourceMask's copy and refusals; the box is computed here, once.
+// ---------------------------------------------------------------------------------------------------------------
+void TiledRuntime::setSourceMask(const Frame *mask) {
+	DeviceGuard g(m_Device);
+	if (mask == nullptr) {
+		m_Stream->synchronize();
+		m_Mask = DeviceBuffer();
+		m_MaskW = m_MaskH = 0;
+		m_MaskStride = 0;
+		m_MaskBox = MaskBox();
+		return;
+	}
+	if (mask->location != Location::Host && mask->location != Location::Device) {
+		throw std::invalid_argument("ju_tiled_set_source_mask: the mask must be host or device memory");
+	}
+	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
+	const std::string problem = maskSizeProblem(mask->width, mask->height, bw, bh);
+	if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_source_mask: " + problem);
+	if (mask->ptr == nullptr) throw std::invalid_argument("ju_tiled_set_source_mask: NULL mask image");
+	const std::size_t rowBytes = mask->width * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	if (mask->stride > -plain && mask->stride < plain) {
+		throw std::invalid_argument("ju_tiled_set_source_mask: |stride| smaller than a row");
+	}
+	// copied once, in the caller's memory order (a bottom-up mask stays bottom-up and is read with a negative stride)
+	DeviceBuffer buf(rowBytes * mask->height);
+	const RowSpan rows = rowSpan(mask->ptr, mask->stride, mask->height);
+	const bool host = mask->location == Location::Host;
+	copyRows(buf.get(), rowBytes, rows.lowest, rows.pitch, rowBytes, mask->height, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+	    nullptr);
+	// (on the null stream and waited for, as a blocking copy is: behind what the caller's own default-stream work wrote)
+	JU_HIP(hipStreamSynchronize(nullptr));
+	// the box, from host memory: the caller's own rows, or the copy read back once (set time, not the frame path)
+	MaskBox box;
+	if (host) {
+		box = maskBox(static_cast<const std::uint8_t *>(mask->ptr), mask->stride, static_cast<int>(mask->width), static_cast<int>(mask->height),
+		    static_cast<int>(bw), static_cast<int>(bh));
+	} else {
+		std::vector<std::uint8_t> back(rowBytes * mask->height);
+		JU_HIP(hipMemcpy(back.data(), buf.get(), back.size(), hipMemcpyDeviceToHost));
+		const std::uint8_t *first = rows.topDown ? back.data() : back.data() + (mask->height - 1) * rowBytes;
+		box = maskBox(first, rows.topDown ? plain : -plain, static_cast<int>(mask->width), static_cast<int>(mask->height), static_cast<int>(bw),
+		    static_cast<int>(bh));
+	}
+	m_Stream->synchronize();
+	m_Mask = std::move(buf);
+	m_MaskW = mask->width;
+	m_MaskH = mask->height;
+	m_MaskStride = rows.topDown ? plain : -plain;
+	m_MaskBox = box;
+}
+
 void TiledRuntime::setDeepFromState(int on) {
 	if (on != 0 && on != 1) throw std::invalid_argument("ju_tiled_set_deep_from_state: " + std::to_string(on) + " is neither 0 nor 1");
 	m_DeepFromState = on == 1;
@@ -287,7 +348,8 @@ TiledRuntime::Rows TiledRuntime::stageIn(const AnyFrame &in) {
 }
 
 bool TiledRuntime::deepFromState(const AnyFrame &out) const {
-	return out.yuv && m_DeepFromState && m_HbdFromState && formatInfo(out.planes.format).deep();
+	// (a mask: the masked frame exists in 8 bits only, as Engine::deepFromState has it)
+	return out.yuv && m_DeepFromState && m_HbdFromState && m_MaskW == 0 && formatInfo(out.planes.format).deep();
 }
 
 // The 16-bit path: ONE launch blends the states the tiles' last frames left -- the group passes are synchronous, so they
@@ -326,7 +388,7 @@ void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
 	++m_DeepStateFrames;
 }
 
-void TiledRuntime::stitchOut(const AnyFrame &out) {
+void TiledRuntime::stitchOut(const AnyFrame &out, const Rows &src) {
 	// While an output size is set the frame is ow x oh of it and the blend's launch is the fused one, which forms the
 	// blended frame in registers and writes the scaled one; everything behind the launch -- the staging frame, the copy
 	// out, the encode -- is the same code at that size.  Off: exactly the launches of before.
@@ -336,7 +398,29 @@ void TiledRuntime::stitchOut(const AnyFrame &out) {
 	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
 	const std::size_t ow = scaled ? m_OutScale.dstW() : bw, oh = scaled ? m_OutScale.dstH() : bh, rowBytes = ow * 4;
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	// A mask whose box is not empty: the two masked launchers in the place of the two below, with the source rows stageIn
+	// returned -- valid until the call returns.  No mask, or a white one: exactly the launches of before.
+	const bool masked = m_MaskW != 0 && !m_MaskBox.empty();
+	TileMask mk;
+	if (masked) {
+		mk.src = src.ptr;
+		mk.srcStride = src.stride;
+		mk.mask = m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0);
+		mk.maskStride = m_MaskStride;
+		mk.maskW = static_cast<int>(m_MaskW);
+		mk.maskH = static_cast<int>(m_MaskH);
+		mk.x0 = m_MaskBox.x0, mk.y0 = m_MaskBox.y0, mk.x1 = m_MaskBox.x1, mk.y1 = m_MaskBox.y1;
+	}
 	auto stitch = [&](std::uint8_t *dst, std::ptrdiff_t stride) {
+		if (masked && scaled) {
+			return launchTileStitchMaskScale(dst, stride, static_cast<int>(ow), static_cast<int>(oh), static_cast<int>(bw), static_cast<int>(bh),
+			    m_Out, tilesX(), tilesY(), static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(),
+			    m_OutScale.xAxis(), m_OutScale.yAxis(), m_OutScale.span(), mk, *m_Stream);
+		}
+		if (masked) {
+			return launchTileStitchMask(dst, stride, static_cast<int>(ow), static_cast<int>(oh), m_Out, tilesX(), tilesY(),
+			    static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(), mk, *m_Stream);
+		}
 		if (scaled) {
 			return launchTileStitchScale(dst, stride, static_cast<int>(ow), static_cast<int>(oh), static_cast<int>(bw), static_cast<int>(bh),
 			    m_Out, tilesX(), tilesY(), static_cast<int>(kTileScale * m_TileW), m_XTable.as<unsigned>(), m_YTable.as<unsigned>(),
@@ -396,9 +480,10 @@ void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *
 		const int at = passes.begin(p);
 		Engine::processGroup(members.data() + at, tin.data() + at, tout.data() + at, passes.count(p));
 	}
-	stitchOut(out);
+	stitchOut(out, src);
 	m_Stream->synchronize();
 	++m_Frames;
+	if (m_MaskW != 0) ++m_MaskFrames;
 }
 
 }  // namespace ju

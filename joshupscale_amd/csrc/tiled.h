@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "mask_box.h"
 #include "tile_geometry.h"
 
 namespace ju {
@@ -53,6 +54,15 @@ public:
 	// history, group passes and the scene detector do not know about it.
 	void setOutputSize(std::size_t width, std::size_t height, int filter);
 	void outputSize(std::size_t *width, std::size_t *height) const;  // (0, 0) while off
+	// A source mask (docs/tiled.md "A mask"): from now on the source frame of each call is drawn back over the blended frame
+	// through `mask` -- Engine::setSourceMask's definition at the blended size, applied to the blended sample in registers
+	// inside the stitch's launch, in front of the output scaler.  A BGRX image of any size 1 .. 16384 per axis, host or
+	// device, any stride of either sign, copied now; its box (mask_box.h) is computed now (a device mask is read back once
+	// for it).  nullptr: no mask.  std::invalid_argument, the setting as it was: a graphics resource, a size out of range,
+	// 2 x blended extent x mask extent not below 2^32.  reset(), setOutputSize and setSceneDetect keep it; tile inputs and
+	// states, the group passes and the scene detector do not know about it; deep formats are encoded from the 8-bit frame
+	// while it is set.
+	void setSourceMask(const Frame *mask);
 
 	std::size_t srcWidth() const { return m_SrcW; }
 	std::size_t srcHeight() const { return m_SrcH; }
@@ -68,7 +78,9 @@ public:
 	// "deep_from_state" (the setting), "hbd_from_state" (the model's property, every tile's alike), "deep_state_frames"
 	// (frames whose output was blended from the states), "scene_mode", "scene_frames" / "scene_cuts" (the detector's
 	// decisions and cuts, cumulative over its on-periods), "output_scaled" (1 while an output size is set), "output_filter"
-	// (its kScale* value, 0 while off), "output_scaled_frames" (frames that took a fused blend-and-scale kernel)
+	// (its kScale* value, 0 while off), "output_scaled_frames" (frames that took a fused blend-and-scale kernel),
+	// "source_mask" (1 while a mask is set), "source_mask_frames" (frames processed while one was set), "mask_box_x0" /
+	// "_y0" / "_x1" / "_y1" (the box in blended coordinates; all 0 while the mask is off or the box is empty)
 	double stat(const std::string &key) const;
 
 private:
@@ -79,7 +91,7 @@ private:
 		std::ptrdiff_t stride;
 	};
 	Rows stageIn(const AnyFrame &in);
-	void stitchOut(const AnyFrame &out);
+	void stitchOut(const AnyFrame &out, const Rows &src);
 	// a deep format while the setting is on and the tiles' states are their frames in float: the 16-bit path of stitchOut
 	bool deepFromState(const AnyFrame &out) const;
 	void stitchOutDeep(const YuvFrame &y);
@@ -108,6 +120,13 @@ private:
 	// took a fused kernel.  m_OutStage, m_Out16 and m_YuvOut are then of the output size.
 	Scaler m_OutScale;
 	std::uint64_t m_OutputScaledFrames = 0;
+	// the source mask in device memory, in the caller's row order (m_MaskStride < 0: bottom-up; m_MaskW == 0: none), its
+	// box in blended coordinates and the frames processed while one was set
+	DeviceBuffer m_Mask;
+	std::size_t m_MaskW = 0, m_MaskH = 0;
+	std::ptrdiff_t m_MaskStride = 0;
+	MaskBox m_MaskBox;
+	std::uint64_t m_MaskFrames = 0;
 	// The scene detector, made when the mode is turned on: m_ScenePrev the kept source-size frame (4 Ws Hs bytes), m_SceneDev
 	// the SceneState, m_SceneRing kSceneRing records + the totals (host-mapped), m_SceneClear the clear's table of kTileMax
 	// SceneClearTile (host-mapped; RESET on a recurrent model only).  m_Own: what each tile counts (tileOwnedEnds).

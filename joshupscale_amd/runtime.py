@@ -289,6 +289,7 @@ _PRODUCT_SIGS = {
     "ju_tiled_set_deep_from_state": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_tiled_set_output_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_tiled_get_output_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
+    "ju_tiled_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
     "ju_tiled_process": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
     "ju_tiled_process_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
     "ju_tiled_get_info": (C.c_int, [C.c_void_p, _P(JuTiledInfo)]),
@@ -363,6 +364,13 @@ _HOOK_SIGS = {
                                              C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p), C.c_int]),
     "ju_debug_tile_stitch_scale_state": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t,
                                                    C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p), C.c_int]),
+    "ju_debug_tile_stitch_mask": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                                            _P(C.c_void_p), C.c_int, C.c_void_p, C.c_ssize_t, C.c_void_p, C.c_ssize_t,
+                                            C.c_size_t, C.c_size_t]),
+    "ju_debug_tile_stitch_mask_scale": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t,
+                                                  C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p), C.c_int,
+                                                  C.c_void_p, C.c_ssize_t, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
+    "ju_debug_mask_box": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P(C.c_int)]),
     "ju_debug_tile_split_scene": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                             _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, _P(JuSceneInfo), C.c_int,
                                             C.c_uint32, C.c_int]),
@@ -965,6 +973,20 @@ class TiledRuntime:
         w, h = self.get_output_size()
         return (w, h) if w else (self.out_width, self.out_height)
 
+    # -- a source mask (docs/tiled.md "A mask") ----------
+    def set_source_mask(self, mask) -> None:
+        """``ju_tiled_set_source_mask``: ``mask`` is a ``[MH, MW, 4]`` uint8 BGRX array of any size, a :class:`JuImage`
+        (host or device), or ``None`` to remove the mask, as :meth:`Runtime.set_source_mask` takes it.  From now on the
+        source frame is drawn back over the blended frame through it, inside the stitch's launch.  The object copies it."""
+        if mask is None:
+            _check(self._lib, self._lib.ju_tiled_set_source_mask(self._h, None))
+            return
+        if not isinstance(mask, JuImage):
+            if mask.dtype != np.uint8 or mask.ndim != 3 or mask.shape[2] != 4 or mask.strides[2] != 1 or mask.strides[1] != 4:
+                raise ValueError("expected a [H, W, 4] uint8 BGRX mask with contiguous pixels")
+            mask = host_image(mask)
+        _check(self._lib, self._lib.ju_tiled_set_source_mask(self._h, C.byref(mask)))
+
     # -- the scene detector of the tiled stream (docs/tiled.md "Scene cuts") ----------
     def set_scene_detect(self, mode: int, threshold_milli: int = 10000) -> None:
         """``ju_tiled_set_scene_detect``: ``SCENE_OFF``, ``SCENE_REPORT`` (record cuts) or ``SCENE_RESET`` (and restart
@@ -1008,7 +1030,8 @@ class TiledRuntime:
         setting), "hbd_from_state" (the model's property), "deep_state_frames" (frames blended from the states),
         "scene_mode", "scene_frames" and "scene_cuts" (the tiled stream's detector; the counters are cumulative),
         "output_scaled", "output_filter" and "output_scaled_frames" (``set_output_size``; frames that took a fused
-        blend-and-scale kernel)."""
+        blend-and-scale kernel), "source_mask", "source_mask_frames" and "mask_box_x0" .. "mask_box_y1"
+        (``set_source_mask``; the box in blended coordinates)."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_tiled_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -24,8 +24,19 @@ smooth scenes of four frames each, a cut every fourth frame.
   output_on:   ju_tiled_set_output_size(W, H, filter) -- blend and scale in one launch (docs/tiled.md "An output size");
 both with --deep-from-state (with --out-format p010 and 1: the 16-bit route); "output_scaled_frames" shows each one's route.
 
---trace WxH runs one variant alone (--deep-from-state 0 | 1, --scene off | report | reset, --out-format, --clip, --output
-and --filter: the output size set) for a `rocprofv3 --kernel-trace --stats` run; with --two-launch the output size is NOT
+--compare mask [--mask obs black ...] [--output WxH --filter NAME] runs objects that all advance as group passes, all under
+the output size where one is named:
+  mask_off:    no mask (the yardstick: today's route);
+  mask_obs:    ju_tiled_set_source_mask with tests/golden/obs_mask.png -- a HUD: the box is a few per cent of the frame;
+  mask_black:  a black mask -- every pixel is rewritten with the source;
+  mask_grey:   random grey levels at the source size -- every pixel blended;
+  mask_none:   no mask again, a second yardstick at another place in the round (what the place alone costs);
+"source_mask_frames" and "mask_box" show each one's route (docs/tiled.md "A mask").
+
+--trace WxH runs one variant alone (--deep-from-state 0 | 1, --scene off | report | reset, --mask KIND, --out-format, --clip,
+--output and --filter: the output size set) for a `rocprofv3 --kernel-trace --stats` run; with --two-launch and --mask no
+mask is set and every frame is followed by mask_blend_kernel alone, through its hook, over the blended BGRX frame the object
+wrote (and with --output by the scaler below: the route of three launches); with --two-launch the output size is NOT
 set and every frame is followed by the existing scaler alone, through its hook, at the sizes --output names: scale_bgrx_kernel
 over the blended BGRX frame, or (an --out-format other than bgrx) scale_state_kernel over a state of the blended size --
 what a route of two launches would add to the blend;
@@ -47,11 +58,14 @@ sys.path.insert(0, ROOT)
 
 COPY_BYTES_PER_S = 6.29e12
 TILE_KERNELS = ("tile_split_kernel", "tile_split_scene_kernel", "scene_clear_tiles_kernel", "tile_stitch_kernel", "tile_stitch_state_kernel", "frame16_to_yuv420p10_kernel",
-                "bgrx_to_yuv420p10_kernel", "tile_stitch_scale_kernel", "tile_stitch_scale_state_kernel", "scale_bgrx_kernel", "scale_state_kernel")
+                "bgrx_to_yuv420p10_kernel", "tile_stitch_scale_kernel", "tile_stitch_scale_state_kernel", "scale_bgrx_kernel", "scale_state_kernel",
+                "tile_stitch_mask_kernel", "tile_stitch_mask_scale_kernel", "mask_blend_kernel")
 # what a variant is: created under JU_LOOKAHEAD=1 (no passes), its ju_tiled_set_deep_from_state, its scene mode
 VARIANTS = {"tiled": (False, 0, 0), "serial": (True, 0, 0), "deep_off": (False, 0, 0), "deep_on": (False, 1, 0),
             "scene_off": (False, 0, 0), "scene_report": (False, 0, 1), "scene_reset": (False, 0, 2),
-            "output_off": (False, 0, 0), "output_on": (False, 0, 0)}
+            "output_off": (False, 0, 0), "output_on": (False, 0, 0),
+            "mask_off": (False, 0, 0), "mask_obs": (False, 0, 0), "mask_black": (False, 0, 0), "mask_grey": (False, 0, 0), "mask_none": (False, 0, 0)}
+MASKS = ("obs", "black", "grey", "none")
 FILTERS = {"triangle": 0, "catmull-rom": 2, "mitchell": 3}
 SCENE_NAMES = {"off": "scene_off", "report": "scene_report", "reset": "scene_reset"}
 # output formats: (the runtime's FMT_ name, per plane (rows per output row, bytes per output pixel of a row))
@@ -115,11 +129,23 @@ def summarize(path, sw, sh, w, h, ov, output=None):
     print(json.dumps(out))
 
 
+def make_mask(kind, sw, sh):
+    """The BGRX mask of a variant: the reference's HUD mask, all black, or random grey levels at the source size."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    if kind == "obs":
+        import source_reference as S
+        return S.read_png_palette_1bit(os.path.join(ROOT, "tests", "golden", "obs_mask.png"))
+    if kind == "black":
+        return np.zeros((2, 2, 4), np.uint8)
+    return np.random.default_rng(77).integers(0, 256, (sh, sw, 4), dtype=np.uint8)
+
+
 class Pair:
     """The variants for one source size, with their device frames."""
 
     def __init__(self, sw, sh, preset, dtype, ov, names=("tiled", "serial"), out_format="bgrx", clip="noise", threshold=10000,
-                 output=None, deep=None, two_launch=None):
+                 output=None, deep=None, two_launch=None, two_mask=None):
         import torch
         from joshupscale_amd import model_file as M
         from joshupscale_amd import runtime as R
@@ -134,7 +160,7 @@ class Pair:
             if serial:
                 os.environ["JU_LOOKAHEAD"] = "1"
             try:
-                self.obj[name] = R.TiledRuntime(blob, 0, dt, sw, sh, ov, hooks=two_launch is not None)
+                self.obj[name] = R.TiledRuntime(blob, 0, dt, sw, sh, ov, hooks=two_launch is not None or two_mask is not None)
             finally:
                 os.environ.pop("JU_LOOKAHEAD", None)
             self.obj[name].set_deep_from_state(deep_all if deep_all is not None else deep)
@@ -142,6 +168,8 @@ class Pair:
                 self.obj[name].set_output_size(*output)
             if scene:
                 self.obj[name].set_scene_detect(scene, threshold)
+            if name.startswith("mask_") and name not in ("mask_off", "mask_none"):
+                self.obj[name].set_source_mask(make_mask(name[len("mask_"):], sw, sh))
         if clip == "cuts":
             import numpy as np
             clip = np.ascontiguousarray(np.concatenate([M.synthetic_frames(4, sh, sw, seed=seed, kind="smooth")
@@ -173,6 +201,11 @@ class Pair:
             src = torch.zeros((4 * sh, 4 * sw * 8), dtype=torch.uint8, device=dev) if op else self.d_out[names[0]][0]
             dst = torch.zeros((oh, ow * (8 if op else 4)), dtype=torch.uint8, device=dev)
             self.two = (op, filt, dst, 4 * ow, ow, oh, src, 16 * sw, 4 * sw, 4 * sh)
+        # --two-launch --mask: mask_blend_kernel alone behind every frame (its hook), over the blended frame just written
+        self.two_mask = None
+        if two_mask is not None:
+            m = make_mask(two_mask, sw, sh)
+            self.two_mask = (torch.from_numpy(m.copy()).to(dev), m.shape[1], m.shape[0], self.d_out[names[0]][0], sw, sh)
         torch.cuda.synchronize()
 
     def run(self, name, frames):
@@ -182,6 +215,11 @@ class Pair:
         for t in range(frames):
             if call(h, C.byref(self.ins[t % self.count]), C.byref(self.out[name])) != 0:
                 raise RuntimeError(self.lib.ju_last_error().decode())
+            if self.two_mask:
+                d_mask, mw, mh, gen, sw, sh = self.two_mask
+                if self.lib.ju_debug_source(1, gen.data_ptr(), 16 * sw, 4 * sw, 4 * sh, self.d_in[t % self.count].data_ptr(), 4 * sw, sw, sh,
+                                            d_mask.data_ptr(), 4 * mw, mw, mh) != 0:
+                    raise RuntimeError(self.lib.ju_last_error().decode())
             if self.two:
                 op, filt, dst, stride, ow, oh, src, src_stride, bw, bh = self.two
                 if self.lib.ju_debug_scale(op, filt, dst.data_ptr(), stride, ow, oh, src.data_ptr(), src_stride, bw, bh, None, None, None) != 0:
@@ -203,9 +241,12 @@ def main():
     ap.add_argument("--frames", type=int, default=240, help="frames per variant and round")
     ap.add_argument("--warmup", type=int, default=24)
     ap.add_argument("--out-format", default="bgrx", choices=sorted(OUT_FORMATS))
-    ap.add_argument("--compare", default="passes", choices=["passes", "deep", "scene", "output"],
+    ap.add_argument("--compare", default="passes", choices=["passes", "deep", "scene", "output", "mask"],
                     help="passes: tiled against serial; deep: ju_tiled_set_deep_from_state 0 against 1; scene: the scene "
-                         "detector off, JU_SCENE_REPORT and JU_SCENE_RESET; output: no output size against --output")
+                         "detector off, JU_SCENE_REPORT and JU_SCENE_RESET; output: no output size against --output; "
+                         "mask: no mask against the masks of --mask (all under --output where given)")
+    ap.add_argument("--mask", nargs="+", default=None, choices=MASKS,
+                    help="--compare mask: the masks to run beside no mask (default obs black); --trace: the one mask set")
     ap.add_argument("--output", default=None, metavar="WxH", help="--compare output, --trace, --summarize: the output size")
     ap.add_argument("--filter", default="triangle", choices=sorted(FILTERS), help="the output size's filter")
     ap.add_argument("--two-launch", action="store_true", help="--trace: the existing scaler alone behind every frame")
@@ -224,18 +265,22 @@ def main():
                   size(args.output) if args.output else None)
         return
     output = (*size(args.output), FILTERS[args.filter]) if args.output else None
-    if (args.compare == "output" or args.two_launch) and not output:
-        ap.error("--compare output and --two-launch need --output WxH")
+    if (args.compare == "output" or (args.two_launch and not args.mask)) and not output:
+        ap.error("--compare output and --two-launch without --mask need --output WxH")
     import torch
     torch.zeros(1, device="cuda:0")  # (torch's HIP runtime first, as bench.py does)
     if args.trace:
         name = "deep_on" if args.deep_from_state else SCENE_NAMES[args.scene] if args.scene != "off" else "tiled"
+        if args.mask and not args.two_launch:
+            name = "mask_" + args.mask[0]
         p = Pair(*size(args.trace), args.preset, args.dtype, args.overlap, (name,), args.out_format, args.clip, args.threshold,
-                 output=None if args.two_launch else output, two_launch=output if args.two_launch else None)
+                 output=None if args.two_launch else output, two_launch=output if args.two_launch else None,
+                 two_mask=args.mask[0] if args.mask and args.two_launch else None)
         p.run(name, args.warmup)
         p.run(name, args.frames)
         print(json.dumps({"trace": args.trace, "variant": name, "out_format": args.out_format, "frames": args.warmup + args.frames,
-                          "output": args.output, "filter": args.filter, "two_launch": args.two_launch,
+                          "output": args.output, "filter": args.filter, "two_launch": args.two_launch, "mask": args.mask,
+                          "source_mask_frames": p.obj[name].stat("source_mask_frames"),
                           "output_scaled_frames": p.obj[name].stat("output_scaled_frames"),
                           "group_frames": p.obj[name].stat("group_frames"),
                           "deep_state_frames": p.obj[name].stat("deep_state_frames"), "clip": args.clip,
@@ -244,11 +289,13 @@ def main():
         return
     res = {}
     names = {"deep": ("deep_off", "deep_on"), "scene": ("scene_off", "scene_report", "scene_reset"),
-             "output": ("output_off", "output_on")}.get(args.compare, ("tiled", "serial"))
+             "output": ("output_off", "output_on"),
+             "mask": ("mask_off",) + tuple("mask_" + m for m in (args.mask or ("obs", "black")))}.get(args.compare, ("tiled", "serial"))
     for text in args.sizes:
         sw, sh = size(text)
         p = Pair(sw, sh, args.preset, args.dtype, args.overlap, names, args.out_format, args.clip, args.threshold,
-                 output=output if args.compare == "output" else None, deep=args.deep_from_state if args.compare == "output" else None)
+                 output=output if args.compare in ("output", "mask") else None,
+                 deep=args.deep_from_state if args.compare == "output" else None)
         for name in p.obj:
             p.run(name, args.warmup)
         fps = {name: [] for name in p.obj}
@@ -270,6 +317,11 @@ def main():
         if args.compare == "output":
             row["output_scaled_frames"] = {name: o.stat("output_scaled_frames") for name, o in p.obj.items()}
             row["output"], row["filter"], row["deep_from_state"] = args.output, args.filter, args.deep_from_state
+        if args.compare == "mask":
+            row["source_mask_frames"] = {name: o.stat("source_mask_frames") for name, o in p.obj.items()}
+            row["mask_box"] = {name: [int(o.stat("mask_box_" + k)) for k in ("x0", "y0", "x1", "y1")] for name, o in p.obj.items()}
+            row["output_scaled_frames"] = {name: o.stat("output_scaled_frames") for name, o in p.obj.items()}
+            row["output"], row["filter"] = args.output, args.filter
         res[text] = row
         p.close()
     what = {"tiled": "the tiles as group passes", "serial": "the same object created under JU_LOOKAHEAD=1: every tile "
@@ -278,7 +330,11 @@ def main():
             "scene_off": "the scene detector off: the split alone", "scene_report": "JU_SCENE_REPORT: the split and the "
             "detector in one launch", "scene_reset": "JU_SCENE_RESET: that launch and the conditional clear of all tiles",
             "output_off": "no output size: the blended frame of four times the source",
-            "output_on": "ju_tiled_set_output_size: blend and scale in one launch"}
+            "output_on": "ju_tiled_set_output_size: blend and scale in one launch",
+            "mask_off": "no mask: the unmasked launches", "mask_obs": "ju_tiled_set_source_mask, the reference's HUD mask: the "
+            "box is a few per cent of the frame", "mask_black": "a black mask: every pixel rewritten with the source",
+            "mask_grey": "random grey levels at the source size: every pixel blended",
+            "mask_none": "no mask, as mask_off: a second yardstick at another place in the round"}
     print(json.dumps({"metric": "frames/s of ju_tiled_process, device BGRX in, device " + args.out_format.upper() + " out",
                       "preset": args.preset, "dtype": args.dtype, "overlap": args.overlap, "frames_per_round": args.frames,
                       "rounds": args.rounds, "clip": args.clip, "variants": {name: what[name] for name in names}, "fps": res}))
