@@ -652,6 +652,33 @@ JU_API int ju_tiled_process(ju_tiled *tiled, const ju_image *input, const ju_ima
  * as above, and whatever ju_process_frame refuses for a frame of that size (an odd size for a subsampled format, an
  * unknown format or colour space, a NULL or misaligned plane, |stride| smaller than a row). */
 JU_API int ju_tiled_process_frame(ju_tiled *tiled, const ju_frame *input, const ju_frame *output);
+/* Look-ahead passes of a tiled stream (docs/tiled.md "Look-ahead passes"; no reference counterpart): ju_process_batch /
+ * ju_process_frames restated for a tiled object.  `count` CONSECUTIVE frames of the tiled stream in one synchronous call:
+ * every plane of outputs[i] holds exactly the bytes ju_tiled_process_frame(&inputs[i], &outputs[i]), called in order, would
+ * have written, and nothing around those planes is written; every tile's recurrent state and frame history, the
+ * detector's memory and records and every counter that frame-by-frame calls advance are the same afterwards -- under
+ * ju_tiled_set_deep_from_state, an output size, a source mask and the scene detector in either mode alike.  All inputs
+ * must hold their pixels when the call is made.  Formats, colour spaces, locations and strides of either sign are
+ * independent per frame and per side; a call of BGRX frames behaves as ju_tiled_process_batch with the same pointers.
+ * count == 0 does nothing, count == 1 is ju_tiled_process_frame, and calls longer than the cap split into consecutive
+ * passes.  ju_tiled_set_lookahead caps the frames per pass (1 .. 8, clamped; 1 = every frame as ju_tiled_process_frame);
+ * the default is the members' look-ahead: 8, or JU_LOOKAHEAD=<1..8> at creation.  ju_tiled_reset keeps the cap.
+ * A pass of K frames uploads and decodes its sources up front, cuts all of them into the tiles' inputs in ONE launch
+ * (per frame, fused with the detector, while ju_tiled_set_scene_detect is on), then runs per frame the tiles' group
+ * passes and the blend; a JU_LOC_CPU output is copied out while the NEXT frame's group passes run.  A frame starts a new
+ * pass if one of its input planes overlaps an output plane of an earlier frame of the pass (same address space) or one of
+ * its output planes an earlier frame's input plane; outputs may repeat (the same buffer for frames i and i + 2 ends up
+ * holding frame i + 2).  Device memory, made at the first pass and sized by the cap: K source slots of 4 src_width
+ * src_height bytes, K x tiles tile inputs, and a second staging frame per side in use.
+ * JU_ERR_INVALID_ARGUMENT: a NULL array, count < 0, and whatever ju_tiled_process_frame refuses for ANY frame of the call
+ * -- every pair is checked before anything is uploaded or launched, the message names the frame ("frame i: ..."), and
+ * the object, its tiles, the detector and the stats stay as they were.
+ * ju_tiled_get_stat: "lookahead" (the cap), "pass_calls" (passes run), "pass_frames" (frames that ran inside a pass of
+ * two or more frames), "pass_split_launches" (multi-frame split launches), "pass_overlapped_copies" (host outputs copied
+ * out while a group pass of a later frame was in flight: not where the tiles run one by one, as in a one-tile object). */
+JU_API int ju_tiled_process_batch(ju_tiled *tiled, const ju_image *inputs, const ju_image *outputs, int count);
+JU_API int ju_tiled_process_frames(ju_tiled *tiled, const ju_frame *inputs, const ju_frame *outputs, int count);
+JU_API int ju_tiled_set_lookahead(ju_tiled *tiled, int frames);
 /* Deep outputs from the tiles' f16 states (no reference counterpart: the reference has no tiles and writes 8-bit frames).
  * on = 1: a deep output format (P010, I010, P210, I210, I410, V210, Y210, Y410, BGRX64, RGBP10, RGBP16, RGBPH, RGBPS,
  * BGR96F, X2RGB10, X2BGR10) is encoded from the blend of the tiles' states instead of the blended 8-bit frame: with P the
@@ -726,7 +753,8 @@ JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t
 /* "tiles"; "frames": frames processed; "group_frames": the tiles' frames that ran inside group passes, summed over the
  * tiles (tiles x frames while every pass holds at least two tiles); "deep_from_state": the setting of
  * ju_tiled_set_deep_from_state; "hbd_from_state": 1 where the model's f16 state is its frame in float (ju_get_stat's key,
- * every tile's alike); "deep_state_frames": the frames whose output was blended from the tiles' states;
+ * every tile's alike); "deep_state_frames": the frames whose output was blended from the tiles' states; "lookahead",
+ * "pass_calls", "pass_frames", "pass_split_launches", "pass_overlapped_copies": ju_tiled_process_frames above;
  * "scene_mode", "scene_frames", "scene_cuts": the detector below, the two counters cumulative as ju_get_stat's;
  * "output_scaled", "output_filter", "output_scaled_frames": ju_tiled_set_output_size above; "source_mask",
  * "source_mask_frames", "mask_box_x0" .. "mask_box_y1": ju_tiled_set_source_mask above.  An unknown key is
@@ -749,9 +777,9 @@ JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *val
 JU_API int ju_tiled_set_scene_detect(ju_tiled *tiled, int mode, uint32_t threshold_milli);
 JU_API int ju_tiled_get_scene_detect(const ju_tiled *tiled, int *mode, uint32_t *threshold_milli);
 JU_API int ju_tiled_get_scene_info(ju_tiled *tiled, ju_scene_info *out, int count, int *written);
-/* Not provided for a tiled object: look-ahead passes and ju_set_source_size (the output size is
- * ju_tiled_set_output_size, the mask ju_tiled_set_source_mask, the scene detector ju_tiled_set_scene_detect), graphics
- * resources, graph capture, the C++ plugin surface. */
+/* Not provided for a tiled object: ju_set_source_size (the output size is ju_tiled_set_output_size, the mask
+ * ju_tiled_set_source_mask, the scene detector ju_tiled_set_scene_detect, look-ahead passes ju_tiled_process_frames),
+ * ju_prepare_* and ju_enqueue counterparts, graphics resources, graph capture, the C++ plugin surface. */
 
 /* Replaces getExceptionString() (core.h:94): message of the last failed call on
  * this thread ("" if none). The pointer stays valid until the next failing

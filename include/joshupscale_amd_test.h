@@ -303,6 +303,20 @@ JU_API int ju_debug_tile_stitch_mask_scale(void *dst, ptrdiff_t dst_stride, size
 JU_API int ju_debug_mask_box(const void *mask, ptrdiff_t mask_stride, size_t mask_width, size_t mask_height, size_t width,
     size_t height, int *box);
 
+/* The split of a look-ahead pass alone (tile_split_frames_kernel; docs/tiled.md "Look-ahead passes"; the definition:
+ * tests/tiled_reference.py split, frame by frame): ONE synchronous launch over `frames` (1 .. 8) sources of src_width x
+ * src_height -- srcs[f] / src_strides[f], each frame's own device BGRX rows, address and signed stride multiples of 4 --
+ * into the layout of ju_debug_tile_split: tile k's input of frame f is written at tiles[k] + f * slot_bytes (a multiple of
+ * 16 that holds a tile), X = 0, and nothing around it.  Refused with JU_ERR_INVALID_ARGUMENT before any device call: what
+ * ju_debug_tile_split refuses, for any frame (the message names it), a frame count outside 1 .. 8, a NULL array, a slot
+ * stride that is no multiple of 16 or smaller than a tile.
+ * ju_debug_tiled_pass_plan touches no device: where the passes of a call of `count` (0 .. 4096) frames start under the cap
+ * `cap` (csrc/tile_pass_plan.h; tests/tiled_pass_reference.py plan) -- clash[i * count + j] != 0 for i < j: frames i and j
+ * cannot share a pass.  *passes: how many; starts[0 .. min(capacity, *passes)): their first frames. */
+JU_API int ju_debug_tile_split_frames(const void *const *srcs, const ptrdiff_t *src_strides, int frames, size_t src_width,
+    size_t src_height, size_t tile_width, size_t tile_height, int overlap, void *const *tiles, size_t slot_bytes, int count);
+JU_API int ju_debug_tiled_pass_plan(int count, int cap, const unsigned char *clash, int *starts, int capacity, int *passes);
+
 /* The two kernels of a tiled stream's scene detector alone (docs/tiled.md "Scene cuts"), each ONE synchronous launch on
  * caller-supplied device buffers, on the current device.
  * ju_debug_tile_split_scene: tile_split_scene_kernel -- the source, the layout and the tiles of ju_debug_tile_split (the

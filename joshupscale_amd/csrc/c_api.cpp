@@ -456,6 +456,48 @@ int ju_tiled_process_frame(ju_tiled *tiled, const ju_frame *input, const ju_fram
 	});
 }
 
+int ju_tiled_process_batch(ju_tiled *tiled, const ju_image *inputs, const ju_image *outputs, int count) {
+	return guarded([&] {
+		ju::TiledRuntime &t = tiledOf(tiled);
+		if (count < 0 || (count > 0 && (inputs == nullptr || outputs == nullptr))) {
+			throw std::invalid_argument("ju_tiled_process_batch: NULL images or a negative count");
+		}
+		std::vector<ju::AnyFrame> in(static_cast<std::size_t>(count)), out(static_cast<std::size_t>(count));
+		for (int i = 0; i < count; ++i) {
+			try {
+				in[i] = ju::anyOf(toFrame(inputs + i));
+				out[i] = ju::anyOf(toFrame(outputs + i));
+			} catch (const std::invalid_argument &err) {
+				throw std::invalid_argument("ju_tiled_process_batch: frame " + std::to_string(i) + ": " + err.what());
+			}
+		}
+		t.processFrames(in.data(), out.data(), count, "ju_tiled_process_batch");
+	});
+}
+
+int ju_tiled_process_frames(ju_tiled *tiled, const ju_frame *inputs, const ju_frame *outputs, int count) {
+	return guarded([&] {
+		ju::TiledRuntime &t = tiledOf(tiled);
+		if (count < 0 || (count > 0 && (inputs == nullptr || outputs == nullptr))) {
+			throw std::invalid_argument("ju_tiled_process_frames: NULL frames or a negative count");
+		}
+		std::vector<ju::AnyFrame> in(static_cast<std::size_t>(count)), out(static_cast<std::size_t>(count));
+		for (int i = 0; i < count; ++i) {
+			try {
+				in[i] = toAnyFrame(inputs + i);
+				out[i] = toAnyFrame(outputs + i);
+			} catch (const std::invalid_argument &err) {
+				throw std::invalid_argument("ju_tiled_process_frames: frame " + std::to_string(i) + ": " + err.what());
+			}
+		}
+		t.processFrames(in.data(), out.data(), count, "ju_tiled_process_frames");
+	});
+}
+
+int ju_tiled_set_lookahead(ju_tiled *tiled, int frames) {
+	return guarded([&] { tiledOf(tiled).setLookahead(frames); });
+}
+
 int ju_tiled_get_info(const ju_tiled *tiled, ju_tiled_info *info) {
 	return guarded([&] {
 		const ju::TiledRuntime &t = tiledOf(const_cast<ju_tiled *>(tiled));
@@ -531,6 +573,33 @@ int ju_debug_tile_split(const void *src, ptrdiff_t src_stride, size_t src_width,
 		    src_width, &set, &nx, &ny);
 		ju::launchTileSplit(static_cast<const std::uint8_t *>(src), src_stride, set, count, static_cast<int>(tile_width),
 		    static_cast<int>(tile_height), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_tile_split_frames(const void *const *srcs, const ptrdiff_t *src_strides, int frames, size_t src_width, size_t src_height,
+    size_t tile_width, size_t tile_height, int overlap, void *const *tiles, size_t slot_bytes, int count) {
+	return guarded([&] {
+		const std::string name = "ju_debug_tile_split_frames";
+		if (frames < 1 || frames > ju::kFlowBatchMax) throw std::invalid_argument(name + ": 1 .. 8 frames");
+		if (srcs == nullptr || src_strides == nullptr) throw std::invalid_argument(name + ": null buffer");
+		int nx = 0, ny = 0;
+		ju::TileSet set;
+		ju::TileFrames list;
+		for (int f = 0; f < frames; ++f) {  // every frame's rows, as ju_debug_tile_split checks its one frame's
+			try {
+				debugTileSet(name.c_str(), src_width, src_height, tile_width, tile_height, overlap, tiles, count, srcs[f], src_strides[f], src_width,
+				    &set, &nx, &ny);
+			} catch (const std::invalid_argument &err) {
+				throw std::invalid_argument(std::string(err.what()) + " (frame " + std::to_string(f) + ")");
+			}
+			list.src[f] = static_cast<const std::uint8_t *>(srcs[f]);
+			list.stride[f] = static_cast<long long>(src_strides[f]);
+		}
+		if (slot_bytes % 16 || slot_bytes < 4 * tile_width * tile_height) {
+			throw std::invalid_argument(name + ": the slot stride must be a multiple of 16 and hold a tile");
+		}
+		ju::launchTileSplitFrames(list, frames, set, slot_bytes, count, static_cast<int>(tile_width), static_cast<int>(tile_height), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
 	});
 }
@@ -1787,6 +1856,20 @@ int ju_debug_mask_box(const void *mask, ptrdiff_t mask_stride, size_t mask_width
 		const ju::MaskBox b = ju::maskBox(static_cast<const std::uint8_t *>(mask), mask_stride, static_cast<int>(mask_width),
 		    static_cast<int>(mask_height), static_cast<int>(width), static_cast<int>(height));
 		box[0] = b.x0, box[1] = b.y0, box[2] = b.x1, box[3] = b.y1;
+	});
+}
+
+int ju_debug_tiled_pass_plan(int count, int cap, const unsigned char *clash, int *starts, int capacity, int *passes) {
+	return guarded([&] {
+		const std::string name = "ju_debug_tiled_pass_plan";
+		if (passes == nullptr || (capacity > 0 && starts == nullptr) || capacity < 0) throw std::invalid_argument(name + ": null argument");
+		if (count < 0 || count > 4096) throw std::invalid_argument(name + ": count outside 0 .. 4096");
+		if (count > 0 && clash == nullptr) throw std::invalid_argument(name + ": null argument");
+		const std::vector<int> plan = ju::tilePassPlan(count, cap, [&](int i, int j) {
+			return clash[static_cast<std::size_t>(i) * static_cast<std::size_t>(count) + static_cast<std::size_t>(j)] != 0;
+		});
+		*passes = static_cast<int>(plan.size());
+		for (int k = 0; k < capacity && k < *passes; ++k) starts[k] = plan[static_cast<std::size_t>(k)];
 	});
 }
 #endif  // JU_TEST_HOOKS

@@ -74,14 +74,24 @@ public:
 	// one dtype override: std::invalid_argument otherwise, before anything is launched) share a pass where they can:
 	// members[0] (the lead) runs the flow net ONCE over up to its look-ahead cap of frames, each the next frame of its
 	// own stream, then every member's own recurrent steps, all on the lead's stream (engine_passes.cpp, "Group passes").
-	static void processGroup(Engine *const *members, const Frame *in, const Frame *out, int count);
+	// underPass (empty by default: exactly the launches of before): host work of the caller's to run ONCE per call while
+	// the GPU runs the call's frames -- a group pass runs it between its last enqueue and its wait, behind chainEnd (it may
+	// block: a pageable copy), with `true`; a call that forms no pass runs it exactly once all the same, before returning,
+	// with `false` (nothing ran under it); a pass that has to be run again does not repeat it (the tiled runtime's deferred
+	// copy-out: tiled.cpp).
+	// after (null by default): everything the call launches runs behind that event -- a wait of the pass's lead's stream, or
+	// of a member's own stream where the member runs on its own; no host wait (the tiled runtime orders a frame's group
+	// passes behind the previous frame's stitch with it: tiled.cpp).
+	static void processGroup(Engine *const *members, const Frame *in, const Frame *out, int count,
+	    const std::function<void(bool)> &underPass = {}, hipEvent_t after = nullptr);
 	// processGroup for frames of any format (ju_process_group_frames): formats, colour spaces, locations and strides are
 	// independent per member and side.  EVERY pair is checked before anything is launched or uploaded (std::invalid_argument
 	// names the member).  A pass decodes all its non-BGRX inputs in one launch in front of the flow net's and encodes each
 	// member's output behind that member's own steps -- a deep format from THAT member's f16 state (engine_passes.cpp,
 	// "Group passes").  who: the entry point in the messages; indexed: checkFrame's refusals name the member too.
 	static void processGroupFrames(Engine *const *members, const AnyFrame *in, const AnyFrame *out, int count,
-	    const char *who = "ju_process_group_frames", bool indexed = true);
+	    const char *who = "ju_process_group_frames", bool indexed = true, const std::function<void(bool)> &underPass = {},
+	    hipEvent_t after = nullptr);
 	// process() for device-resident frames without the wait (ju_enqueue, ju_enqueue_frame): enqueue only.
 	void enqueue(const AnyFrame &in, const AnyFrame &out);
 	void synchronize();
@@ -636,7 +646,10 @@ private:
 	std::uint64_t m_GroupFrames = 0, m_GroupYuvFrames = 0;  // ("group_yuv_frames": those of them with a non-BGRX side)
 	bool sameModel(const Engine &o) const;
 	// one pass over members m[0 .. n) on `lead`'s stream and tensors (the lead need not be one of them)
-	static void runGroupPass(Engine &lead, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n);
+	static void runGroupPass(Engine &lead, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n,
+	    const std::function<void(bool)> &underPass, hipEvent_t after);
+	static void runGroups(Engine *const *members, const AnyFrame *in, const AnyFrame *out, int count, const char *who, bool indexed,
+	    const std::function<void(bool)> &underPass, hipEvent_t after);
 	std::uint64_t m_DirectClock = 0;
 	bool m_DirectGraph = true;  // JU_DIRECT_GRAPH=0: device frames always launch eagerly
 	static constexpr std::size_t kMaxDirectGraphs = 64;     // unregistered tuples (LRU)

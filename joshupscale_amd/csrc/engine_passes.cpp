@@ -802,17 +802,33 @@ bool Engine::sameModel(const Engine &o) const {
 	return m_Device == o.m_Device && m_ModelDigest == o.m_ModelDigest && m_DtypeOverride == o.m_DtypeOverride;
 }
 
-void Engine::processGroup(Engine *const *members, const Frame *bgrxIn, const Frame *bgrxOut, int count) {
+void Engine::processGroup(Engine *const *members, const Frame *bgrxIn, const Frame *bgrxOut, int count,
+    const std::function<void(bool)> &underPass, hipEvent_t after) {
 	if (count < 0 || (count > 0 && (members == nullptr || bgrxIn == nullptr || bgrxOut == nullptr))) {
 		throw std::invalid_argument("ju_process_group: NULL arguments or a negative count");
 	}
 	if (count == 0) return;
 	const std::vector<AnyFrame> in = anyOf(bgrxIn, count), out = anyOf(bgrxOut, count);
-	processGroupFrames(members, in.data(), out.data(), count, "ju_process_group", false);
+	processGroupFrames(members, in.data(), out.data(), count, "ju_process_group", false, underPass, after);
 }
 
+// The caller's host work (underPass) exactly once per call: under the first group pass the call forms, else -- no pass, or
+// an argument refused before one -- not at all (a refusal) or behind the members' frames, before the call returns.
 void Engine::processGroupFrames(Engine *const *members, const AnyFrame *in, const AnyFrame *out, int count, const char *who,
-    bool indexed) {
+    bool indexed, const std::function<void(bool)> &underPass, hipEvent_t after) {
+	if (!underPass) return runGroups(members, in, out, count, who, indexed, underPass, after);
+	bool ran = false;
+	const std::function<void(bool)> once = [&](bool inPass) {
+		if (ran) return;
+		ran = true;
+		underPass(inPass);
+	};
+	runGroups(members, in, out, count, who, indexed, once, after);
+	if (count > 0) once(false);
+}
+
+void Engine::runGroups(Engine *const *members, const AnyFrame *in, const AnyFrame *out, int count, const char *who, bool indexed,
+    const std::function<void(bool)> &underPass, hipEvent_t after) {
 	const std::string name = who;
 	if (count < 0 || (count > 0 && (members == nullptr || in == nullptr || out == nullptr))) {
 		throw std::invalid_argument(name + ": NULL arguments or a negative count");
@@ -842,7 +858,11 @@ void Engine::processGroupFrames(Engine *const *members, const AnyFrame *in, cons
 	}
 	Engine &lead = *members[0];
 	DeviceGuard g(lead.m_Device);
-	auto alone = [&](int i) { members[i]->process(in[i], out[i]); };
+	auto alone = [&](int i) {
+		// (a member on its own runs on its own stream: behind `after` there)
+		if (after) JU_HIP(hipStreamWaitEvent(members[i]->m_Stream, after, 0));
+		members[i]->process(in[i], out[i]);
+	};
 	if (count == 1) return alone(0);
 	// An output over an input of the call (same address space; any two members, also one member's own pair; every plane
 	// of a frame counts): member by member in list order, as ju_process_frame calls would run -- a pass reads every input
@@ -878,14 +898,17 @@ void Engine::processGroupFrames(Engine *const *members, const AnyFrame *in, cons
 			fi[j] = in[pass[k + j]];
 			fo[j] = out[pass[k + j]];
 		}
-		runGroupPass(lead, m, fi, fo, n);
+		runGroupPass(lead, m, fi, fo, n, underPass, after);
 	}
 	// frames a pass cannot take (graphics resources, device frames off the kernels' alignment): on their own.  No
 	// buffer of the call overlaps another here, so the order changes no byte.
 	for (int i : rest) alone(i);
 }
 
-void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n) {
+void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n,
+    const std::function<void(bool)> &underPass, hipEvent_t after) {
+	// everything of the pass runs on the lead's stream (the uploads too): ONE wait puts it behind `after`
+	if (after) JU_HIP(hipStreamWaitEvent(L.m_Stream, after, 0));
 	int sets[kFlowBatchMax];
 	for (int i = 0; i < n; ++i) sets[i] = m[i]->m_Idx;
 	// what each member brings along (setStageGroup): bit 0 its source scaler, bit 1 its mask, bit 2 its output scaler
@@ -1082,6 +1105,9 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		if (m[i] != &L) JU_HIP(hipStreamWaitEvent(m[i]->m_Stream, L.m_GroupEvent.get(), 0));
 	}
 	L.drainPassOutputs(out, n);  // host frames: each copied out while the next member runs
+	// the caller's host work under the pass: everything is enqueued and the chain lock is released, so it may block (a
+	// pageable copy) while the GPU runs the pass.  Here and nowhere else: the re-run below does not repeat it.
+	if (underPass) underPass(true);
 	L.m_Stream.synchronizeSpin(L.m_SpinUs);
 	// one synchronisation; then every member's resident-tower error word
 	unsigned codes[kFlowBatchMax];

@@ -735,6 +735,16 @@ static_assert(sizeof(TileSet) <= 1024, "the by-value argument of the tile kernel
 // tile k = the source's pixels from (x[k], y[k]) on.  One launch.
 void launchTileSplit(const std::uint8_t *src, std::ptrdiff_t srcStride, const TileSet &tiles, int count, int tileW, int tileH,
     hipStream_t stream);
+// The split of the frames of a look-ahead pass in ONE launch (tile_split_frames_kernel; docs/tiled.md "Look-ahead passes"):
+// for f < frameCount (1 .. kFlowBatchMax) launchTileSplit's bytes of the source frames.src[f] / frames.stride[f] (each frame's
+// own address and signed stride, multiples of 4, of any 16-byte phase) into tile k's input at
+// tiles.ptr[k] + f * slotBytes (a multiple of 16).  The by-value argument: per-frame pointers and strides.
+struct TileFrames {
+	const std::uint8_t *src[kFlowBatchMax] = {};
+	long long stride[kFlowBatchMax] = {};
+};
+void launchTileSplitFrames(const TileFrames &frames, int frameCount, const TileSet &tiles, std::size_t slotBytes, int count, int tileW,
+    int tileH, hipStream_t stream);
 // The split and the scene detector of the tiled stream in ONE launch (tile_split_scene_kernel; docs/tiled.md "Scene cuts"):
 // the tile bytes of launchTileSplit, and over the source of srcW x srcH the sum, the decision and the record of
 // launchSceneSad (SceneSadLaunch's prev .. resetMode; its src, stride and size are ignored) -- `prev` is the dense

@@ -3,10 +3,12 @@
 // tests/tiled_reference.py; the host builds the layout (tile_geometry.h) and the device only copies, multiplies and adds
 // integers.
 //
-//   tile_split_kernel   grid.z = tile; a lane takes four pixels of one tile row: 16 bytes per load where the source
-//                       address is 16-byte aligned (a tile origin that is a multiple of four pixels in an aligned
-//                       source), four 4-byte loads otherwise -- a wave reads one contiguous row segment either way --
-//                       and one 16-byte store into the dense tile (X = 0).
+//   tile_split_kernel   grid.z = tile; a lane takes four pixels of one tile row: ONE 16-byte load at the source's 4-byte-
+//                       aligned address (gfx950 takes it at any such address; a wave reads one contiguous row segment)
+//                       and ONE 16-byte store into the dense tile (X = 0); pixel by pixel only for a row's last group
+//                       and for the rows of a tile width that is no multiple of four.
+//   tile_split_frames_kernel  the split of the K frames of a look-ahead pass in ONE launch (docs/tiled.md "Look-ahead
+//                       passes"): grid.z = frame * tiles + tile, each frame its own source, stride and alignment.
 //   tile_split_scene_kernel  the split with the tiled stream's scene detector in the same pass (docs/tiled.md "Scene
 //                       cuts"): the same grid and tile bytes, and per OWNED source pixel the kept frame read, summed
 //                       against and rewritten -- 2 x 4 Ws Hs bytes on top of the split's.
@@ -51,41 +53,58 @@ constexpr unsigned kOpaqueMask = 0x00ffffffu;  // B, G, R kept, X = 0
 
 __device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<std::uintptr_t>(p) & 15u) == 0; }
 
+// what one lane of the split does: four pixels of row r of one tile, from x0 on (tile_split_kernel, tile_split_frames_kernel)
+// -- into tile k's image, `at` bytes behind tiles.ptr[k] (a look-ahead pass's slot of the frame; 0: the tile itself)
+__device__ __forceinline__ void splitLane(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride, const TileSet &tiles, int k,
+    std::size_t at, int x0, int r, int tileW) {
+	const std::uint8_t *s = src + static_cast<std::ptrdiff_t>(tiles.y[k] + r) * srcStride +
+	                        static_cast<std::ptrdiff_t>(tiles.x[k] + x0) * 4;
+	std::uint8_t *d = tiles.ptr[k] + at + (static_cast<std::size_t>(r) * tileW + x0) * 4;
+	// A whole group into a 16-byte-aligned place -- every group of a tile whose width is a multiple of four: the tiles and a
+	// pass's slots are 16-byte aligned (checkTileSet, launchTileSplitFrames) -- is ONE 16-byte store.  The source is read
+	// as one 16-byte load whatever its address: gfx950 takes a dwordx4 load at a 4-byte-aligned address, so a frame's
+	// alignment costs no other instruction, only the memory system's handling of the split access.
+	if (x0 + 4 <= tileW && aligned16(d)) {
+		const unsigned *w = reinterpret_cast<const unsigned *>(s);
+		uint4 v = make_uint4(w[0], w[1], w[2], w[3]);
+		v.x &= kOpaqueMask;
+		v.y &= kOpaqueMask;
+		v.z &= kOpaqueMask;
+		v.w &= kOpaqueMask;
+		*reinterpret_cast<uint4 *>(__builtin_assume_aligned(d, 16)) = v;
+		return;
+	}
+	// pixel by pixel: the last group of a width that is no multiple of four, and every group of such a tile's rows that
+	// do not start on a 16-byte boundary
+	for (int i = 0; i < 4 && x0 + i < tileW; ++i) {
+		reinterpret_cast<unsigned *>(d)[i] = reinterpret_cast<const unsigned *>(s)[i] & kOpaqueMask;
+	}
+}
+
 __global__ __launch_bounds__(256) void tile_split_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
     const TileSet tiles, int tileW, int tileH) {
 	const int k = blockIdx.z;
 	const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4;
 	const int r = blockIdx.y * 4 + threadIdx.y;
 	if (x0 >= tileW || r >= tileH) return;
-	const std::uint8_t *s = src + static_cast<std::ptrdiff_t>(tiles.y[k] + r) * srcStride +
-	                        static_cast<std::ptrdiff_t>(tiles.x[k] + x0) * 4;
-	std::uint8_t *d = tiles.ptr[k] + (static_cast<std::size_t>(r) * tileW + x0) * 4;
-	if (x0 + 4 <= tileW) {
-		uint4 v;
-		if (aligned16(s)) {
-			v = *reinterpret_cast<const uint4 *>(s);
-		} else {
-			const unsigned *w = reinterpret_cast<const unsigned *>(s);
-			v = make_uint4(w[0], w[1], w[2], w[3]);
-		}
-		v.x &= kOpaqueMask;
-		v.y &= kOpaqueMask;
-		v.z &= kOpaqueMask;
-		v.w &= kOpaqueMask;
-		if (aligned16(d)) {
-			*reinterpret_cast<uint4 *>(d) = v;
-		} else {
-			unsigned *w = reinterpret_cast<unsigned *>(d);
-			w[0] = v.x;
-			w[1] = v.y;
-			w[2] = v.z;
-			w[3] = v.w;
-		}
-		return;
-	}
-	for (int i = 0; x0 + i < tileW; ++i) {  // the last group of a width that is no multiple of four
-		reinterpret_cast<unsigned *>(d)[i] = reinterpret_cast<const unsigned *>(s)[i] & kOpaqueMask;
-	}
+	splitLane(src, srcStride, tiles, k, 0, x0, r, tileW);
+}
+
+// ---- the split of a look-ahead pass (docs/tiled.md "Look-ahead passes") -------------------------------------------------
+// tile_split_frames_kernel: tile_split_kernel over the K frames of a pass in ONE launch, grid.z = f * count + k (at most
+// 8 x 64 slices).  Frame f's source and signed stride are frames.src[f] / frames.stride[f]; tile k's input of frame f lies at
+// tiles.ptr[k] + f * slot.  f and k come from blockIdx alone, so what a workgroup reads of the two by-value arguments is
+// uniform: scalar loads from the kernel-argument segment, no per-lane table and no scratch.  Nothing in the launch depends
+// on a frame's alignment: each lane loads from its own frame's address, as in tile_split_kernel, so the frames of one pass
+// may differ in alignment, stride, sign and padding.
+__global__ __launch_bounds__(256) void tile_split_frames_kernel(const TileFrames frames, const TileSet tiles, std::size_t slot,
+    int count, int tileW, int tileH) {
+	const int f = blockIdx.z / static_cast<unsigned>(count);
+	const int k = blockIdx.z - f * count;
+	const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4;
+	const int r = blockIdx.y * 4 + threadIdx.y;
+	if (x0 >= tileW || r >= tileH) return;
+	splitLane(frames.src[f], static_cast<std::ptrdiff_t>(frames.stride[f]), tiles, k, static_cast<std::size_t>(f) * slot, x0, r, tileW);
 }
 
 // ---- the split with the tiled stream's scene detector (docs/tiled.md "Scene cuts") --------------------------------------
@@ -690,6 +709,28 @@ void launchTileSplit(const std::uint8_t *src, std::ptrdiff_t srcStride, const Ti
 	const dim3 grid((static_cast<unsigned>(tileW) + 255) / 256, (static_cast<unsigned>(tileH) + 3) / 4, static_cast<unsigned>(count));
 	hipLaunchKernelGGL(tile_split_kernel, grid, dim3(64, 4), 0, stream, src, srcStride, tiles, tileW, tileH);
 	hipCheckLaunch("tile_split");
+}
+
+void launchTileSplitFrames(const TileFrames &frames, int frameCount, const TileSet &tiles, std::size_t slotBytes, int count, int tileW,
+    int tileH, hipStream_t stream) {
+	if (frameCount < 1 || frameCount > kFlowBatchMax) throw std::invalid_argument("tile_split_frames: 1 .. 8 frames");
+	checkTileSet("tile_split_frames", tiles, count, 16);
+	for (int f = 0; f < frameCount; ++f) {
+		try {
+			checkRows("tile_split_frames", frames.src[f], static_cast<std::ptrdiff_t>(frames.stride[f]));
+		} catch (const std::invalid_argument &e) {
+			throw std::invalid_argument(std::string(e.what()) + " (frame " + std::to_string(f) + ")");
+		}
+	}
+	if (tileW < 1 || tileH < 1) throw std::invalid_argument("tile_split_frames: empty tiles");
+	// (every frame's slot of a tile as aligned as the tile: the 16-byte stores)
+	if (frameCount > 1 && (slotBytes % 16 || slotBytes < static_cast<std::size_t>(tileW) * static_cast<std::size_t>(tileH) * 4)) {
+		throw std::invalid_argument("tile_split_frames: the slot stride must be a multiple of 16 and hold a tile");
+	}
+	const dim3 grid((static_cast<unsigned>(tileW) + 255) / 256, (static_cast<unsigned>(tileH) + 3) / 4,
+	    static_cast<unsigned>(count) * static_cast<unsigned>(frameCount));
+	hipLaunchKernelGGL(tile_split_frames_kernel, grid, dim3(64, 4), 0, stream, frames, tiles, slotBytes, count, tileW, tileH);
+	hipCheckLaunch("tile_split_frames");
 }
 
 void launchTileSplitScene(const std::uint8_t *src, std::ptrdiff_t srcStride, int srcW, int srcH, const TileSet &tiles,

@@ -5,7 +5,8 @@
 // staging frame that is copied out or encoded by the existing encode at output size.  With setDeepFromState a deep format
 // is instead encoded from ONE launch's blend of the tiles' f16 states (stitchOutDeep).  Under a source mask (setSourceMask)
 // the blend's launch also draws the source rows of step one back over the blended pixels, inside the mask's box.  The call
-// is synchronous.
+// is synchronous.  Several consecutive frames in one call (processFrames): the same steps as look-ahead passes -- all
+// sources staged and cut up front, in ONE launch, a host frame copied out under the next frame's group passes (runPass).
 #include "tiled.h"
 
 #include <algorithm>
@@ -36,6 +37,7 @@ TiledRuntime::TiledRuntime(int device, const void *blob, std::size_t size, int d
 	const int n = tiles();
 	for (int k = 0; k < n; ++k) m_Engines.push_back(std::make_unique<Engine>(device, blob, size, dtypeOverride));
 	m_HbdFromState = m_Engines[0]->stat("hbd_from_state") != 0;  // (the model's property: every tile's alike)
+	m_Lookahead = clampTilePassCap(m_Engines[0]->lookahead());    // (8, or JU_LOOKAHEAD at creation)
 	m_Stream = std::make_unique<Stream>();
 	// (each tile's slot a multiple of 256 bytes: the kernels' 16-byte accesses, the group passes' 4- and 8-byte ones)
 	m_TileInBytes = roundUp(m_TileW * m_TileH * 4, 256);
@@ -76,6 +78,11 @@ double TiledRuntime::stat(const std::string &key) const {
 	if (key == "deep_from_state") return m_DeepFromState ? 1.0 : 0.0;
 	if (key == "hbd_from_state") return m_HbdFromState ? 1.0 : 0.0;
 	if (key == "deep_state_frames") return static_cast<double>(m_DeepStateFrames);
+	if (key == "lookahead") return m_Lookahead;
+	if (key == "pass_calls") return static_cast<double>(m_PassCalls);
+	if (key == "pass_frames") return static_cast<double>(m_PassFrames);
+	if (key == "pass_split_launches") return static_cast<double>(m_PassSplitLaunches);
+	if (key == "pass_overlapped_copies") return static_cast<double>(m_PassOverlappedCopies);
 	if (key == "scene_mode") return m_SceneMode;
 	if (key == "scene_frames" || key == "scene_cuts") {
 		// (the totals behind the ring: the calls are synchronous, so the last decision is in them)
@@ -175,10 +182,11 @@ int TiledRuntime::sceneInfo(SceneRecord *out, int count) {
 // m_State[m_Idx] and m_Packed[m_Idx] of each engine, the two buffers scene_clear_items_kernel covers for a group member.
 // The host reads no decision.  A group pass that has to be run again (a resident-tower report) needs nothing new: the
 // members have no detector of their own, and the pass wrote the OTHER halves only, so the cleared inputs are still in place.
-void TiledRuntime::splitIn(const Rows &src) {
+// `into`: the tile inputs to fill -- m_In, or inside a look-ahead pass the frame's slot of m_PassIn.
+void TiledRuntime::splitIn(const Rows &src, const TileSet &into) {
 	const int n = tiles();
 	if (m_SceneMode == 0) {
-		return launchTileSplit(src.ptr, src.stride, m_In, n, static_cast<int>(m_TileW), static_cast<int>(m_TileH), *m_Stream);
+		return launchTileSplit(src.ptr, src.stride, into, n, static_cast<int>(m_TileW), static_cast<int>(m_TileH), *m_Stream);
 	}
 	SceneSadLaunch q;
 	q.prev = m_ScenePrev.as<std::uint32_t>();
@@ -189,10 +197,10 @@ void TiledRuntime::splitIn(const Rows &src) {
 	q.hasPrev = (m_SceneSeen >= 1 ? 1 : 0) | (m_SceneSeen >= 2 ? 2 : 0);
 	q.thresholdMilli = m_SceneThreshold;
 	q.resetMode = m_SceneMode == 2 && m_Recurrent;
-	launchTileSplitScene(src.ptr, src.stride, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), m_In, m_Own, n,
+	launchTileSplitScene(src.ptr, src.stride, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), into, m_Own, n,
 	    static_cast<int>(m_TileW), static_cast<int>(m_TileH), q, *m_Stream);
 	if (q.resetMode) {
-		// (rewritten every frame: the half a tile reads alternates.  The last frame's clear has completed: process() is synchronous)
+		// (rewritten every frame: the half a tile reads alternates.  The last frame's clear has completed: it ran in front of that frame's group passes, which are synchronous)
 		SceneClearItem items[kTileMax];
 		for (int k = 0; k < n; ++k) items[k] = m_Engines[static_cast<std::size_t>(k)]->recurrentInputs();
 		launchSceneClearTiles(&q.state->resetNow, items, n, reinterpret_cast<volatile SceneClearTile *>(m_SceneClear.host()),
@@ -226,7 +234,7 @@ void TiledRuntime::setOutputSize(std::size_t width, std::size_t height, int filt
 	if (!off) scale.build(kTileScale * m_SrcW, kTileScale * m_SrcH, width, height, filter);
 	m_Stream->synchronize();  // (the call is synchronous, so nothing reads the old tables; kept for a stream shared later)
 	m_OutScale = std::move(scale);
-	for (DeviceBuffer *b : {&m_OutStage, &m_Out16, &m_YuvOut}) *b = DeviceBuffer();  // (their sizes follow the output size)
+	for (DeviceBuffer *b : {&m_OutStage[0], &m_OutStage[1], &m_Out16, &m_YuvOut[0], &m_YuvOut[1]}) *b = DeviceBuffer();  // (their sizes follow the output size)
 }
 
 void TiledRuntime::outputSize(std::size_t *width, std::size_t *height) const {
@@ -317,15 +325,15 @@ DeviceBuffer &TiledRuntime::lazy(DeviceBuffer &b, std::size_t bytes) {
 	return b;
 }
 
-TiledRuntime::Rows TiledRuntime::stageIn(const AnyFrame &in) {
+TiledRuntime::Rows TiledRuntime::stageIn(const AnyFrame &in, DeviceBuffer &srcStage, DeviceBuffer &yuvStage) {
 	const std::size_t rowBytes = m_SrcW * 4;
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
 	if (in.yuv) {  // the existing decode at source size; host planes through their staging layout first
 		const YuvFrame &y = in.planes;
-		auto *stage = lazy(m_SrcStage, rowBytes * m_SrcH).as<std::uint8_t>();
+		auto *stage = lazy(srcStage, rowBytes * m_SrcH).as<std::uint8_t>();
 		YuvPlanes planes = callerPlanes(y);
 		if (y.location == Location::Host) {
-			auto *yuv = lazy(m_YuvIn, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>();
+			auto *yuv = lazy(yuvStage, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>();
 			copyPlanes(y, yuv, true, *m_Stream);
 			planes = stagedPlanes(y, yuv);
 		}
@@ -339,7 +347,7 @@ TiledRuntime::Rows TiledRuntime::stageIn(const AnyFrame &in) {
 	}
 	// a host image, or a device image off the kernel's alignment: copied in its memory order, so a bottom-up image stays
 	// bottom-up and is read with a negative stride
-	auto *stage = lazy(m_SrcStage, rowBytes * m_SrcH).as<std::uint8_t>();
+	auto *stage = lazy(srcStage, rowBytes * m_SrcH).as<std::uint8_t>();
 	const RowSpan rows = rowSpan(b.ptr, b.stride, m_SrcH);
 	copyRows(stage, rowBytes, rows.lowest, rows.pitch, rowBytes, m_SrcH, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
 	    *m_Stream);
@@ -355,7 +363,7 @@ bool TiledRuntime::deepFromState(const AnyFrame &out) const {
 // The 16-bit path: ONE launch blends the states the tiles' last frames left -- the group passes are synchronous, so they
 // are complete -- into the dense 16-bit frame, which the existing encode from such a frame turns into the caller's planes
 // (a host frame's through their staging layout, as on the 8-bit route).
-void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
+void TiledRuntime::stitchOutDeep(const YuvFrame &y, int slot, HostCopy *defer) {
 	const bool scaled = m_OutScale.set();
 	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
 	const std::size_t ow = scaled ? m_OutScale.dstW() : bw, oh = scaled ? m_OutScale.dstH() : bh;
@@ -364,7 +372,7 @@ void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
 		states.ptr[k] = static_cast<std::uint8_t *>(const_cast<void *>(m_Engines[static_cast<std::size_t>(k)]->lastState()));
 	}
 	const bool host = y.location == Location::Host;
-	std::uint8_t *yuv = host ? lazy(m_YuvOut, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
+	std::uint8_t *yuv = host ? lazy(m_YuvOut[slot], stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
 	const YuvPlanes planes = host ? stagedPlanes(y, yuv) : callerPlanes(y);
 	if (tiles() == 1 && !scaled) {
 		// ONE tile: nothing to blend, and the frame is ju_process_frame's -- its encode from the state, which for the float
@@ -384,17 +392,17 @@ void TiledRuntime::stitchOutDeep(const YuvFrame &y) {
 		}
 		launchEncodeFrame16(fmt(y.format), y.colorspace, frame16, planes, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
 	}
-	if (host) copyPlanes(y, yuv, false, *m_Stream);
+	if (host) deferOrCopyPlanes(y, yuv, defer);
 	++m_DeepStateFrames;
 }
 
-void TiledRuntime::stitchOut(const AnyFrame &out, const Rows &src) {
+void TiledRuntime::stitchOut(const AnyFrame &out, const Rows &src, int slot, HostCopy *defer) {
 	// While an output size is set the frame is ow x oh of it and the blend's launch is the fused one, which forms the
 	// blended frame in registers and writes the scaled one; everything behind the launch -- the staging frame, the copy
 	// out, the encode -- is the same code at that size.  Off: exactly the launches of before.
 	const bool scaled = m_OutScale.set();
 	if (scaled) ++m_OutputScaledFrames;
-	if (deepFromState(out)) return stitchOutDeep(out.planes);
+	if (deepFromState(out)) return stitchOutDeep(out.planes, slot, defer);
 	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
 	const std::size_t ow = scaled ? m_OutScale.dstW() : bw, oh = scaled ? m_OutScale.dstH() : bh, rowBytes = ow * 4;
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
@@ -431,59 +439,249 @@ void TiledRuntime::stitchOut(const AnyFrame &out, const Rows &src) {
 	};
 	if (out.yuv) {  // the existing encode at output size, from the stitched 8-bit frame
 		const YuvFrame &y = out.planes;
-		auto *stage = lazy(m_OutStage, rowBytes * oh).as<std::uint8_t>();
+		auto *stage = lazy(m_OutStage[slot], rowBytes * oh).as<std::uint8_t>();
 		stitch(stage, plain);
 		const bool host = y.location == Location::Host;
-		std::uint8_t *yuv = host ? lazy(m_YuvOut, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
+		std::uint8_t *yuv = host ? lazy(m_YuvOut[slot], stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
 		launchEncodeFrame(fmt(y.format), y.colorspace, stage, plain, host ? stagedPlanes(y, yuv) : callerPlanes(y), static_cast<int>(ow),
 		    static_cast<int>(oh), *m_Stream);
-		if (host) copyPlanes(y, yuv, false, *m_Stream);
+		if (host) deferOrCopyPlanes(y, yuv, defer);
 		return;
 	}
 	const Frame &b = out.bgrx;
 	const bool device = b.location == Location::Device;
 	if (device && reinterpret_cast<std::uintptr_t>(b.ptr) % 4 == 0 && b.stride % 4 == 0) return stitch(static_cast<std::uint8_t *>(b.ptr), b.stride);
 	// stitched in the caller's row order, copied out in memory order
-	auto *stage = lazy(m_OutStage, rowBytes * oh).as<std::uint8_t>();
+	auto *stage = lazy(m_OutStage[slot], rowBytes * oh).as<std::uint8_t>();
 	const RowSpan rows = rowSpan(b.ptr, b.stride, oh);
 	if (rows.topDown) {
 		stitch(stage, plain);
 	} else {
 		stitch(stage + static_cast<std::ptrdiff_t>(oh - 1) * plain, -plain);
 	}
+	if (defer != nullptr && !device) {  // a host frame of a pass: copied out by the caller, under the next frame's group passes
+		defer->pending = true;
+		defer->yuv = false;
+		defer->rows = rows;
+		defer->stage = stage;
+		defer->rowBytes = rowBytes;
+		defer->height = oh;
+		return;
+	}
 	copyRows(rows.lowest, rows.pitch, stage, rowBytes, rowBytes, oh, device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, *m_Stream);
 }
 
-void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *who) {
+// a host frame's planes out of their staging layout: now, on the tiled stream, or left to the pass (defer)
+void TiledRuntime::deferOrCopyPlanes(const YuvFrame &y, std::uint8_t *yuv, HostCopy *defer) {
+	if (defer == nullptr) return copyPlanes(y, yuv, false, *m_Stream);
+	defer->pending = true;
+	defer->yuv = true;
+	defer->planes = y;
+	defer->stage = yuv;
+}
+
+void TiledRuntime::copyOut(const HostCopy &c, int part, int parts, hipStream_t stream) {
+	if (c.yuv) {  // (3.1 bytes per pixel or fewer against BGRX's 4, and plane by plane already: whole, with the first part)
+		if (part == 0) copyPlanes(c.planes, c.stage, false, stream);
+		return;
+	}
+	const std::size_t r0 = c.height * static_cast<std::size_t>(part) / static_cast<std::size_t>(parts);
+	const std::size_t r1 = c.height * static_cast<std::size_t>(part + 1) / static_cast<std::size_t>(parts);
+	if (r1 == r0) return;
+	// (both sides in memory order: row r of the staging frame is row r of the caller's rows from their lowest)
+	copyRows(c.rows.lowest + r0 * c.rows.pitch, c.rows.pitch, c.stage + r0 * c.rowBytes, c.rowBytes, c.rowBytes, r1 - r0,
+	    hipMemcpyDeviceToHost, stream);
+}
+
+void TiledRuntime::checkPair(const AnyFrame &in, const AnyFrame &out, const char *who) const {
 	check(in, true, who);
 	check(out, false, who);
 	if (ju::overlap(extentOf(out), extentOf(in))) {
 		throw std::invalid_argument(std::string(who) + ": the output overlaps the input (the tiles read the source while the frame is written)");
 	}
-	DeviceGuard guard(m_Device);
-	const Rows src = stageIn(in);
+}
+
+// Every tile's engine by one frame over the tile inputs `in`: a call of more tiles than one pass holds runs as the fewest
+// passes, filled evenly (tilePasses) -- each call is synchronous.  under(p, passes), if any: the caller's host work under
+// group pass p (Engine::processGroup runs it once: between the pass's last enqueue and its wait, or, where no pass was
+// formed, behind the members' frames with inPass false).
+void TiledRuntime::groupPasses(const TileSet &in, const std::function<void(int, int, bool)> &under, hipEvent_t after) {
 	const int n = tiles();
-	splitIn(src);
-	// the group passes run on their lead's stream: the tiles' inputs (and at a scene cut their cleared recurrent inputs)
-	// are complete before the first of them starts
-	m_Stream->synchronize();
 	std::vector<Engine *> members(static_cast<std::size_t>(n));
 	std::vector<Frame> tin(static_cast<std::size_t>(n)), tout(static_cast<std::size_t>(n));
 	for (int k = 0; k < n; ++k) {
 		members[k] = m_Engines[static_cast<std::size_t>(k)].get();
-		tin[k] = Frame{m_In.ptr[k], Location::Device, static_cast<std::ptrdiff_t>(m_TileW * 4), m_TileW, m_TileH};
+		tin[k] = Frame{in.ptr[k], Location::Device, static_cast<std::ptrdiff_t>(m_TileW * 4), m_TileW, m_TileH};
 		tout[k] = Frame{m_Out.ptr[k], Location::Device, static_cast<std::ptrdiff_t>(m_TileW * 16), m_TileW * kTileScale, m_TileH * kTileScale};
 	}
-	// a call of more tiles than one pass holds: the fewest passes, filled evenly (tilePasses) -- each call is synchronous
 	const TilePasses passes = tilePasses(n, std::max(members[0]->lookahead(), 1));
 	for (int p = 0; p < passes.passes; ++p) {
 		const int at = passes.begin(p);
-		Engine::processGroup(members.data() + at, tin.data() + at, tout.data() + at, passes.count(p));
+		if (under) {
+			Engine::processGroup(members.data() + at, tin.data() + at, tout.data() + at, passes.count(p), [&](bool inPass) { under(p, passes.passes, inPass); },
+			    after);
+		} else {
+			Engine::processGroup(members.data() + at, tin.data() + at, tout.data() + at, passes.count(p), {}, after);
+		}
 	}
+}
+
+void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *who) {
+	checkPair(in, out, who);
+	DeviceGuard guard(m_Device);
+	const Rows src = stageIn(in, m_SrcStage, m_YuvIn);
+	splitIn(src, m_In);
+	// the group passes run on their lead's stream: the tiles' inputs (and at a scene cut their cleared recurrent inputs)
+	// are complete before the first of them starts
+	m_Stream->synchronize();
+	groupPasses(m_In, {});
 	stitchOut(out, src);
 	m_Stream->synchronize();
 	++m_Frames;
 	if (m_MaskW != 0) ++m_MaskFrames;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Look-ahead passes (docs/tiled.md "Look-ahead passes").  The tiles' engines are driven exactly as process() drives them,
+// frame by frame through the same group passes, so their states, histories and counters are process()'s; what a pass saves
+// lies around them: K uploads and decodes issued up front, ONE split launch and ONE host wait for K frames, and a host
+// frame's copy-out -- the largest single item of a 4K host frame -- under the next frame's group passes.
+// ---------------------------------------------------------------------------------------------------------------
+void TiledRuntime::processFrames(const AnyFrame *in, const AnyFrame *out, int count, const char *who) {
+	const std::string name = who;
+	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) {
+		throw std::invalid_argument(name + ": NULL frames or a negative count");
+	}
+	if (count == 0) return;
+	// every pair, before anything is uploaded or launched ("<who>: <why>" -> "<who>: frame i: <why>")
+	for (int i = 0; i < count; ++i) {
+		try {
+			checkPair(in[i], out[i], who);
+		} catch (const std::invalid_argument &e) {
+			const std::string what = e.what(), prefix = name + ": ";
+			throw std::invalid_argument(prefix + "frame " + std::to_string(i) + ": " +
+			                            (what.compare(0, prefix.size(), prefix) == 0 ? what.substr(prefix.size()) : what));
+		}
+	}
+	if (count == 1 || m_Lookahead < 2) {
+		for (int i = 0; i < count; ++i) process(in[i], out[i], who);
+		return;
+	}
+	// A pass reads all its sources up front and writes its outputs frame by frame: an input plane over an output plane of
+	// another frame of the call (one address space) keeps the two in different passes.  Outputs may repeat.
+	std::vector<FrameExtent> ein(static_cast<std::size_t>(count)), eout(static_cast<std::size_t>(count));
+	for (int i = 0; i < count; ++i) {
+		ein[i] = extentOf(in[i]);
+		eout[i] = extentOf(out[i]);
+	}
+	std::vector<int> starts = tilePassPlan(count, m_Lookahead, [&](int i, int j) {
+		return ju::overlap(ein[j], eout[i]) || ju::overlap(eout[j], ein[i]);
+	});
+	starts.push_back(count);
+	for (std::size_t p = 0; p + 1 < starts.size(); ++p) {
+		const int at = starts[p], n = starts[p + 1] - at;
+		if (n == 1) {
+			process(in[at], out[at], who);
+		} else {
+			runPass(in + at, out + at, n);
+		}
+	}
+}
+
+void TiledRuntime::runPass(const AnyFrame *in, const AnyFrame *out, int count) {
+	static_assert(kTilePassMax == kFlowBatchMax, "a pass's frames are the by-value argument of tile_split_frames_kernel");
+	DeviceGuard guard(m_Device);
+	const int n = tiles();
+	// memory of the passes, made at the first one and sized by the cap: K source slots and K x T tile inputs
+	const auto cap = static_cast<std::size_t>(std::max(m_Lookahead, count));
+	if (m_PassSrc.size() < cap) {
+		m_PassSrc.resize(cap);
+		m_PassYuvIn.resize(cap);
+	}
+	m_PassSlot = m_TileInBytes * static_cast<std::size_t>(n);
+	if (m_PassIn.bytes() < m_PassSlot * cap) {
+		m_PassIn = DeviceBuffer(m_PassSlot * cap);
+		for (int k = 0; k < n; ++k) {
+			m_PassSet.ptr[k] = m_PassIn.as<std::uint8_t>() + m_TileInBytes * static_cast<std::size_t>(k);
+			m_PassSet.x[k] = m_In.x[k];
+			m_PassSet.y[k] = m_In.y[k];
+		}
+	}
+	if (!m_CopyStream) {
+		m_CopyStream = std::make_unique<Stream>();
+		for (auto &e : m_Stitched) e = std::make_unique<Event>(hipEventDisableTiming);
+	}
+	// 1. the sources, all up front on the tiled stream: a device BGRX image on the kernels' alignment where it is, every
+	// other one into its own slot.  (d) The slots, and the rule that inputs hold their pixels, keep the split's source rows
+	// -- which a masked stitch reads again -- valid until stitch f.
+	Rows src[kTilePassMax];
+	for (int f = 0; f < count; ++f) src[f] = stageIn(in[f], m_PassSrc[static_cast<std::size_t>(f)], m_PassYuvIn[static_cast<std::size_t>(f)]);
+	auto slotOf = [&](int f) {
+		TileSet t = m_PassSet;
+		for (int k = 0; k < n; ++k) t.ptr[k] += m_PassSlot * static_cast<std::size_t>(f);
+		return t;
+	};
+	// 2. the split: ONE launch for the whole pass while the detector is off (with it on: its decisions are sequential, so
+	// the fused per-frame launch stays, in front of each frame's group passes -- step 3)
+	const bool detects = m_SceneMode != 0;
+	if (!detects) {
+		TileFrames frames;
+		for (int f = 0; f < count; ++f) {
+			frames.src[f] = src[f].ptr;
+			frames.stride[f] = static_cast<long long>(src[f].stride);
+		}
+		launchTileSplitFrames(frames, count, m_PassSet, m_PassSlot, n, static_cast<int>(m_TileW), static_cast<int>(m_TileH), *m_Stream);
+		++m_PassSplitLaunches;
+		// (b) the group passes run on their leads' streams: ONE host wait per pass puts every frame's tile inputs in front
+		// of the first of them
+		m_Stream->synchronize();
+	}
+	HostCopy copy[2];
+	for (int f = 0; f < count; ++f) {
+		const TileSet tin = slotOf(f);
+		if (detects) {
+			// 3. (b) with the detector on: the frame's split, decision and clear, and one host wait per frame as in process()
+			splitIn(src[f], tin);
+			m_Stream->synchronize();
+		}
+		// (a) frame f's group passes overwrite the tile outputs, and write the state halves, that stitch f - 1 reads: each
+		// group pass's lead's stream -- a member's own on the member-by-member routes -- waits for the event behind
+		// stitch f - 1 (Engine::processGroup's `after`); no host wait
+		const hipEvent_t after = f > 0 ? m_Stitched[(f - 1) & 1]->get() : nullptr;
+		// 5. the deferred copy: frame f - 1's host output goes out on the copy stream, behind the same event, while frame f's
+		// group passes run -- a BGRX frame's rows divided among the passes, so that no pass is held up behind a whole frame
+		const HostCopy &prev = copy[(f - 1) & 1];
+		const bool overlapped = f > 0 && prev.pending;
+		if (overlapped) {
+			JU_HIP(hipStreamWaitEvent(*m_CopyStream, m_Stitched[(f - 1) & 1]->get(), 0));
+			bool under = false;  // (whether any part ran while a group pass was in flight: the member-by-member routes do not overlap)
+			groupPasses(tin, [&](int p, int passes, bool inPass) {
+				under = under || inPass;
+				copyOut(prev, p, passes, *m_CopyStream);
+			}, after);
+			// (c) staging slot (f - 1) & 1 is rewritten by stitch f + 1: copy f - 1 has completed here
+			m_CopyStream->synchronize();
+			copy[(f - 1) & 1].pending = false;
+			if (under) ++m_PassOverlappedCopies;
+		} else {
+			groupPasses(tin, {}, after);
+		}
+		// 4. the blend, on the tiled stream; the group passes are synchronous, so the tiles' outputs and states are complete
+		copy[f & 1] = HostCopy{};
+		stitchOut(out[f], src[f], f & 1, &copy[f & 1]);
+		m_Stitched[f & 1]->record(*m_Stream);
+		++m_Frames;
+		if (m_MaskW != 0) ++m_MaskFrames;
+	}
+	// the last frame's copy runs behind the pass
+	const HostCopy &last = copy[(count - 1) & 1];
+	m_Stream->synchronize();
+	if (last.pending) {
+		copyOut(last, 0, 1, *m_CopyStream);
+		m_CopyStream->synchronize();
+	}
+	++m_PassCalls;
+	m_PassFrames += static_cast<std::uint64_t>(count);
 }
 
 }  // namespace ju

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -12,6 +13,7 @@
 #include "engine.h"
 #include "mask_box.h"
 #include "tile_geometry.h"
+#include "tile_pass_plan.h"
 
 namespace ju {
 
@@ -31,7 +33,19 @@ public:
 	// One frame, synchronously: `in` of the source size, `out` of four times that (or the output size set), any format, host or device.  Both are
 	// checked before anything is launched (std::invalid_argument "<who>: <why>"; every tile's state as it was).
 	void process(const AnyFrame &in, const AnyFrame &out, const char *who);
-	// zeroes every tile's recurrent state (keeps setDeepFromState)
+	// `count` CONSECUTIVE frames of the tiled stream in one synchronous call (docs/tiled.md "Look-ahead passes"): in every
+	// output plane, every tile's state and history, the detector's memory and records and every counter exactly what
+	// process(in[i], out[i], ..) called in order would have left, under every setting -- but every input must hold its
+	// pixels when the call is made.  Every pair is checked before anything is uploaded or launched (std::invalid_argument
+	// "<who>: frame i: <why>"; the object as it was).  Runs as passes of at most lookahead() frames (tile_pass_plan.h): a
+	// pass stages and splits all its sources up front, in ONE launch while the scene detector is off, then per frame the
+	// group passes and the stitch, a host frame's copy-out deferred under the next frame's group passes.
+	void processFrames(const AnyFrame *in, const AnyFrame *out, int count, const char *who);
+	// Frames per look-ahead pass, 1 (every frame as process()) .. kTilePassMax, clamped.  Default: the members' look-ahead
+	// (8, or JU_LOOKAHEAD at creation).  reset() keeps it.
+	void setLookahead(int frames) { m_Lookahead = clampTilePassCap(frames); }
+	int lookahead() const { return m_Lookahead; }
+	// zeroes every tile's recurrent state (keeps setDeepFromState and setLookahead)
 	void reset();
 	// Deep outputs (docs/tiled.md "Deep outputs"): 1 = a deep format (P010, BGRX64, RGBPH, ...) is encoded from the blend of
 	// the tiles' f16 states where the model's state is the frame in float ("hbd_from_state" 1; else the setting has no
@@ -76,7 +90,9 @@ public:
 	void tile(int index, std::size_t *x, std::size_t *y) const;
 	// "tiles", "frames" (frames processed), "group_frames" (the members' frames that ran inside group passes, summed),
 	// "deep_from_state" (the setting), "hbd_from_state" (the model's property, every tile's alike), "deep_state_frames"
-	// (frames whose output was blended from the states), "scene_mode", "scene_frames" / "scene_cuts" (the detector's
+	// (frames whose output was blended from the states), "lookahead" (the cap), "pass_calls" (passes run), "pass_frames"
+	// (frames that ran inside a pass of two or more), "pass_split_launches" (multi-frame split launches),
+	// "pass_overlapped_copies" (host outputs copied out under a later frame's group passes), "scene_mode", "scene_frames" / "scene_cuts" (the detector's
 	// decisions and cuts, cumulative over its on-periods), "output_scaled" (1 while an output size is set), "output_filter"
 	// (its kScale* value, 0 while off), "output_scaled_frames" (frames that took a fused blend-and-scale kernel),
 	// "source_mask" (1 while a mask is set), "source_mask_frames" (frames processed while one was set), "mask_box_x0" /
@@ -90,12 +106,31 @@ private:
 		std::uint8_t *ptr;
 		std::ptrdiff_t stride;
 	};
-	Rows stageIn(const AnyFrame &in);
-	void stitchOut(const AnyFrame &out, const Rows &src);
+	// (stage, yuv: where a source that is not read in place goes -- m_SrcStage / m_YuvIn, or a pass's slot of each)
+	Rows stageIn(const AnyFrame &in, DeviceBuffer &stage, DeviceBuffer &yuv);
+	// A host frame's copy-out, deferred (a pass): what stitchOut left in staging slot `slot` and where it goes
+	struct HostCopy {
+		bool pending = false, yuv = false;
+		YuvFrame planes;                   // yuv: the caller's planes, and their staging layout at `stage`
+		RowSpan rows{nullptr, 0, true};  // BGRX: the caller's rows in memory order, `height` of `rowBytes` from `stage`
+		std::uint8_t *stage = nullptr;
+		std::size_t rowBytes = 0, height = 0;
+	};
+	// part `part` of `parts` of a deferred copy, on `stream`: a BGRX frame's rows divided evenly, planes whole with part 0
+	void copyOut(const HostCopy &c, int part, int parts, hipStream_t stream);
+	void deferOrCopyPlanes(const YuvFrame &y, std::uint8_t *yuv, HostCopy *defer);
+	// slot: which of the two staging frames per side (0 outside a pass); defer: null = a host frame is copied out on the
+	// tiled stream behind its stitch (process()), else the copy is left to the caller in *defer
+	void stitchOut(const AnyFrame &out, const Rows &src, int slot = 0, HostCopy *defer = nullptr);
 	// a deep format while the setting is on and the tiles' states are their frames in float: the 16-bit path of stitchOut
 	bool deepFromState(const AnyFrame &out) const;
-	void stitchOutDeep(const YuvFrame &y);
+	void stitchOutDeep(const YuvFrame &y, int slot, HostCopy *defer);
 	DeviceBuffer &lazy(DeviceBuffer &b, std::size_t bytes);
+	void checkPair(const AnyFrame &in, const AnyFrame &out, const char *who) const;
+	// every tile's engine by one frame, as group passes over the tile inputs `in`; under(p, passes, inPass): host work under
+	// pass p (inPass false: no group pass was formed and the members have finished); after: the event the passes run behind
+	void groupPasses(const TileSet &in, const std::function<void(int, int, bool)> &under, hipEvent_t after = nullptr);
+	void runPass(const AnyFrame *in, const AnyFrame *out, int count);
 
 	int m_Device;
 	int m_Overlap;
@@ -109,7 +144,20 @@ private:
 	TileSet m_In, m_Out;
 	DeviceBuffer m_XTable, m_YTable;
 	// frames that are not device BGRX: the BGRX source and result, and the planes of host frames of another format
-	DeviceBuffer m_SrcStage, m_OutStage, m_YuvIn, m_YuvOut;
+	// (m_OutStage[1] / m_YuvOut[1]: the second staging slot of a look-ahead pass, made at the first pass that needs it)
+	DeviceBuffer m_SrcStage, m_OutStage[2], m_YuvIn, m_YuvOut[2];
+	// Look-ahead passes (processFrames), made at the first pass and sized by the cap: m_PassSrc / m_PassYuvIn the K source
+	// slots (4 Ws Hs bytes each; a host frame's planes), m_PassIn K x T tile inputs -- frame f of tile k at m_PassSet.ptr[k]
+	// + f * m_PassSlot -- m_CopyStream the stream of the deferred copies, m_Stitched[f & 1] the event behind frame f's last
+	// output launch.
+	int m_Lookahead = kTilePassMax;
+	std::vector<DeviceBuffer> m_PassSrc, m_PassYuvIn;
+	DeviceBuffer m_PassIn;
+	TileSet m_PassSet;
+	std::size_t m_PassSlot = 0;
+	std::unique_ptr<Stream> m_CopyStream;
+	std::unique_ptr<Event> m_Stitched[2];
+	std::uint64_t m_PassCalls = 0, m_PassFrames = 0, m_PassSplitLaunches = 0, m_PassOverlappedCopies = 0;
 	// deep outputs from the states: the setting, the model's property, the blended 16-bit frame (8 bytes per output pixel,
 	// made at first use) and the frames that took the path
 	bool m_DeepFromState = false, m_HbdFromState = false;
@@ -132,7 +180,7 @@ private:
 	// SceneClearTile (host-mapped; RESET on a recurrent model only).  m_Own: what each tile counts (tileOwnedEnds).
 	// m_SceneSeen: steps since the last start (the "has predecessor" bits); m_SceneSteps: steps since the mode was turned on
 	// (the record's `step`, the ring slot).
-	void splitIn(const Rows &src);
+	void splitIn(const Rows &src, const TileSet &into);
 	bool m_Recurrent = true;
 	int m_SceneMode = 0;
 	std::uint32_t m_SceneThreshold = 0;

@@ -292,6 +292,9 @@ _PRODUCT_SIGS = {
     "ju_tiled_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
     "ju_tiled_process": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage)]),
     "ju_tiled_process_frame": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame)]),
+    "ju_tiled_process_batch": (C.c_int, [C.c_void_p, _P(JuImage), _P(JuImage), C.c_int]),
+    "ju_tiled_process_frames": (C.c_int, [C.c_void_p, _P(JuFrame), _P(JuFrame), C.c_int]),
+    "ju_tiled_set_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "ju_tiled_get_info": (C.c_int, [C.c_void_p, _P(JuTiledInfo)]),
     "ju_tiled_get_tile": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_tiled_get_stat": (C.c_int, [C.c_void_p, C.c_char_p, _P(C.c_double)]),
@@ -374,6 +377,9 @@ _HOOK_SIGS = {
     "ju_debug_tile_split_scene": (C.c_int, [C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
                                             _P(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, _P(JuSceneInfo), C.c_int,
                                             C.c_uint32, C.c_int]),
+    "ju_debug_tile_split_frames": (C.c_int, [_P(C.c_void_p), _P(C.c_ssize_t), C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
+                                             C.c_size_t, C.c_int, _P(C.c_void_p), C.c_size_t, C.c_int]),
+    "ju_debug_tiled_pass_plan": (C.c_int, [C.c_int, C.c_int, C.c_char_p, _P(C.c_int), C.c_int, _P(C.c_int)]),
     "ju_debug_scene_clear_tiles": (C.c_int, [C.c_int, C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p),
                                              _P(C.c_size_t)]),
     "ju_debug_conv": (C.c_int, [_P(JuDebugConv)]),
@@ -922,6 +928,34 @@ class TiledRuntime:
         """``ju_tiled_process_frame``: one frame on frames of any format, host or device (synchronous)."""
         _check(self._lib, self._lib.ju_tiled_process_frame(self._h, C.byref(inp), C.byref(out)))
 
+    # -- look-ahead passes (docs/tiled.md "Look-ahead passes") ----------
+    def process_batch(self, inputs, outputs) -> None:
+        """``ju_tiled_process_batch``: consecutive frames of the tiled stream as BGRX image descriptors in one synchronous
+        call (every input must hold its pixels now); the bytes and the state of ``process`` called frame by frame."""
+        inputs, outputs = list(inputs), list(outputs)
+        n = len(inputs)
+        if len(outputs) != n:
+            raise ValueError("process_batch: as many outputs as inputs")
+        ins, outs = (JuImage * n)(*inputs), (JuImage * n)(*outputs)
+        _check(self._lib, self._lib.ju_tiled_process_batch(self._h, ins, outs, n))
+
+    def process_frames(self, inputs, outputs) -> None:
+        """``ju_tiled_process_frames``: consecutive frames of the tiled stream, of any format, host or device, in one
+        synchronous call (every input must hold its pixels now); the bytes and the state of ``process_frame`` called
+        frame by frame.  Passes of at most :meth:`set_lookahead` frames: one split launch per pass, a host output copied
+        out under the next frame's group passes.  Lists of unequal length raise before any native call."""
+        inputs, outputs = list(inputs), list(outputs)
+        n = len(inputs)
+        if len(outputs) != n:
+            raise ValueError("process_frames: as many outputs as inputs")
+        ins, outs = (JuFrame * n)(*inputs), (JuFrame * n)(*outputs)
+        _check(self._lib, self._lib.ju_tiled_process_frames(self._h, ins, outs, n))
+
+    def set_lookahead(self, frames: int) -> None:
+        """``ju_tiled_set_lookahead``: frames per look-ahead pass, 1 .. 8, clamped (1 = every frame as
+        ``process_frame``).  ``reset`` keeps it."""
+        _check(self._lib, self._lib.ju_tiled_set_lookahead(self._h, int(frames)))
+
     def run(self, frame_bgrx: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
         """Host frames: ``[src_height, src_width, 4]`` uint8 BGRX in, ``[4 src_height, 4 src_width, 4]`` out -- or
         :meth:`frame_output_size` while an output size is set.  Any row stride (also negative, i.e. a ``[::-1]`` view) is
@@ -1028,6 +1062,7 @@ class TiledRuntime:
     def stat(self, key: str) -> float:
         """``ju_tiled_get_stat``: "tiles", "frames", "group_frames" (summed over the tiles), "deep_from_state" (the
         setting), "hbd_from_state" (the model's property), "deep_state_frames" (frames blended from the states),
+        "lookahead", "pass_calls", "pass_frames", "pass_split_launches" and "pass_overlapped_copies" (``process_frames``),
         "scene_mode", "scene_frames" and "scene_cuts" (the tiled stream's detector; the counters are cumulative),
         "output_scaled", "output_filter" and "output_scaled_frames" (``set_output_size``; frames that took a fused
         blend-and-scale kernel), "source_mask", "source_mask_frames" and "mask_box_x0" .. "mask_box_y1"

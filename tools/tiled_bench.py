@@ -33,6 +33,16 @@ the output size where one is named:
   mask_none:   no mask again, a second yardstick at another place in the round (what the place alone costs);
 "source_mask_frames" and "mask_box" show each one's route (docs/tiled.md "A mask").
 
+--compare pass [--place host | device] [--in-format bgrx | nv12] [--out-format ...] [--pass-frames N] [--output WxH] runs
+three objects of one model (docs/tiled.md "Look-ahead passes"), over N input and N output buffers each, host (pageable numpy
+memory) or device:
+  frame:  ju_tiled_process_frame, frame by frame (the yardstick);
+  pass:   ju_tiled_process_frames in calls of N frames (default 8);
+  frame_last:  frame by frame again, a second yardstick at the END of the round (what the place in the round alone costs:
+          docs/tiled.md "A mask" met 1.5 % between the first and the last place);
+"pass_frames", "pass_split_launches" and "pass_overlapped_copies" show each one's route.  With --pass-frames N, --trace runs
+the `pass` variant alone.
+
 --trace WxH runs one variant alone (--deep-from-state 0 | 1, --scene off | report | reset, --mask KIND, --out-format, --clip,
 --output and --filter: the output size set) for a `rocprofv3 --kernel-trace --stats` run; with --two-launch and --mask no
 mask is set and every frame is followed by mask_blend_kernel alone, through its hook, over the blended BGRX frame the object
@@ -57,7 +67,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 COPY_BYTES_PER_S = 6.29e12
-TILE_KERNELS = ("tile_split_kernel", "tile_split_scene_kernel", "scene_clear_tiles_kernel", "tile_stitch_kernel", "tile_stitch_state_kernel", "frame16_to_yuv420p10_kernel",
+TILE_KERNELS = ("tile_split_kernel", "tile_split_frames_kernel", "tile_split_scene_kernel", "scene_clear_tiles_kernel", "tile_stitch_kernel", "tile_stitch_state_kernel", "frame16_to_yuv420p10_kernel",
                 "bgrx_to_yuv420p10_kernel", "tile_stitch_scale_kernel", "tile_stitch_scale_state_kernel", "scale_bgrx_kernel", "scale_state_kernel",
                 "tile_stitch_mask_kernel", "tile_stitch_mask_scale_kernel", "mask_blend_kernel")
 # what a variant is: created under JU_LOOKAHEAD=1 (no passes), its ju_tiled_set_deep_from_state, its scene mode
@@ -78,14 +88,15 @@ def size(text):
     return w, h
 
 
-def kernel_bytes(sw, sh, w, h, ov, output=None):
+def kernel_bytes(sw, sh, w, h, ov, output=None, frames=8):
     """The bytes each kernel must move (output: (OW, OH) for the kernels of an output size -- a fused kernel reads what
     the stitch reads and writes the scaled frame, the scaler alone reads the blended frame and writes the scaled one; 4
     bytes per pixel for the 8-bit kernels, 8 for the 16-bit ones): the split reads the source once and writes every tile; the stitch reads every
     output pixel once where one tile covers it -- and the seams' pixels from two or four -- and writes the frame; the
     stitch of the states the same at 8 bytes per pixel; a P010 encode reads its frame (8 or 4 bytes per pixel) and writes
     3 bytes per pixel.  The split with the detector also reads and rewrites the kept source-size frame; the conditional
-    clear reads one flag word per workgroup while no cut is flagged (its bytes at a cut depend on the model: not listed)."""
+    clear reads one flag word per workgroup while no cut is flagged (its bytes at a cut depend on the model: not listed).
+    The split of a look-ahead pass moves the split's bytes once per frame of the pass (`frames`)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import tiled_reference as T
     nx, ny = len(T.origins(sw, w, ov)), len(T.origins(sh, h, ov))
@@ -101,15 +112,15 @@ def kernel_bytes(sw, sh, w, h, ov, output=None):
         scaled = {"tile_stitch_scale_kernel": 4 * read + 4 * out_px, "tile_stitch_scale_state_kernel": 8 * read + 8 * out_px,
                   "scale_bgrx_kernel": 64 * sw * sh + 4 * out_px, "scale_state_kernel": 128 * sw * sh + 8 * out_px}
         # (the encode then runs at one of two sizes, which a stats file does not tell: its time alone)
-        return {**scaled, "tiles": [nx, ny], "tile_split_kernel": split, "tile_split_scene_kernel": split + 8 * sw * sh,
+        return {**scaled, "tiles": [nx, ny], "tile_split_kernel": split, "tile_split_frames_kernel": frames * split, "tile_split_scene_kernel": split + 8 * sw * sh,
                 "tile_stitch_kernel": stitch, "tile_stitch_state_kernel": 2 * stitch}
-    return {"tiles": [nx, ny], "tile_split_kernel": split, "tile_split_scene_kernel": split + 8 * sw * sh, "tile_stitch_kernel": stitch, "tile_stitch_state_kernel": 2 * stitch,
+    return {"tiles": [nx, ny], "tile_split_kernel": split, "tile_split_frames_kernel": frames * split, "tile_split_scene_kernel": split + 8 * sw * sh, "tile_stitch_kernel": stitch, "tile_stitch_state_kernel": 2 * stitch,
             "frame16_to_yuv420p10_kernel": (8 + 3) * 16 * sw * sh, "bgrx_to_yuv420p10_kernel": (4 + 3) * 16 * sw * sh}
 
 
-def summarize(path, sw, sh, w, h, ov, output=None):
+def summarize(path, sw, sh, w, h, ov, output=None, frames=8):
     import re
-    need = kernel_bytes(sw, sh, w, h, ov, output)
+    need = kernel_bytes(sw, sh, w, h, ov, output, frames)
     out = {"stats": path, "source": f"{sw}x{sh}", "tiles": need["tiles"], "copy_bandwidth_TBps": COPY_BYTES_PER_S / 1e12}
     if output:
         out["output"] = f"{output[0]}x{output[1]}"
@@ -231,6 +242,100 @@ class Pair:
             o.close()
 
 
+class PassPair:
+    """--compare pass: `frame` (ju_tiled_process_frame) and `pass` (ju_tiled_process_frames in calls of n frames), each over
+    n input and n output buffers of its own, host or device."""
+
+    def __init__(self, sw, sh, preset, dtype, ov, place, in_format, out_format, output, n, names=("frame", "pass", "frame_last")):
+        import numpy as np
+        import torch
+        from joshupscale_amd import model_file as M
+        from joshupscale_amd import runtime as R
+        dev = torch.device("cuda", 0)
+        cfg = M.PRESETS[preset]
+        blob = M.serialize(cfg, M.make_seeded_weights(cfg))
+        dt = {"bf16": R.DTYPE_BF16, "fp16": R.DTYPE_F16, "fp8": R.DTYPE_FP8}[dtype]
+        self.n, self.obj, self.keep, self.ins, self.outs = n, {}, [], {}, {}
+        rng = np.random.default_rng(1234)
+        in_name, in_planes = OUT_FORMATS[in_format]
+        out_name, out_planes = OUT_FORMATS[out_format]
+
+        def frames_of(fmt_name, planes, w, h, fill):
+            out = []
+            for _ in range(n):
+                arrays = [fill((int(h * rows), w * width)) for rows, width in planes]
+                if fmt_name == "FMT_BGRX":
+                    arrays = [arrays[0].reshape(h, w, 4)]
+                elif planes[0][1] == 2:                            # (the 10-bit formats: 16-bit samples)
+                    arrays = [a.view(np.uint16) for a in arrays]
+                if place == "host":
+                    self.keep.append(arrays)
+                    out.append(R.host_frame(getattr(R, fmt_name), arrays))
+                else:
+                    tensors = [torch.from_numpy(a.view(np.uint8).reshape(a.shape[0], -1)).to(dev) for a in arrays]
+                    self.keep.append(tensors)
+                    out.append(R.device_frame(getattr(R, fmt_name), w, h, tensors))
+            return (R.JuFrame * n)(*out)
+        for name in names:
+            o = self.obj[name] = R.TiledRuntime(blob, 0, dt, sw, sh, ov)
+            if output:
+                o.set_output_size(*output)
+            fw, fh = o.frame_output_size()
+            self.ins[name] = frames_of(in_name, in_planes, sw, sh, lambda shape: rng.integers(0, 256, shape, dtype=np.uint8))
+            self.outs[name] = frames_of(out_name, out_planes, fw, fh, lambda shape: np.zeros(shape, np.uint8))
+        self.lib = next(iter(self.obj.values()))._lib
+        torch.cuda.synchronize()
+
+    def run(self, name, frames):
+        h, ins, outs, n = self.obj[name]._h, self.ins[name], self.outs[name], self.n
+        assert frames % n == 0
+        t0 = time.perf_counter()
+        if name == "pass":
+            for _ in range(frames // n):
+                if self.lib.ju_tiled_process_frames(h, ins, outs, n) != 0:
+                    raise RuntimeError(self.lib.ju_last_error().decode())
+        else:
+            for t in range(frames):
+                if self.lib.ju_tiled_process_frame(h, C.byref(ins[t % n]), C.byref(outs[t % n])) != 0:
+                    raise RuntimeError(self.lib.ju_last_error().decode())
+        return time.perf_counter() - t0          # (every call is synchronous)
+
+    def stats(self, name):
+        keys = ("frames", "group_frames", "lookahead", "pass_calls", "pass_frames", "pass_split_launches", "pass_overlapped_copies",
+                "output_scaled_frames")
+        return {k: self.obj[name].stat(k) for k in keys}
+
+    def close(self):
+        for o in self.obj.values():
+            o.close()
+
+
+def compare_pass(args, output):
+    res = {}
+    for text in args.sizes:
+        sw, sh = size(text)
+        p = PassPair(sw, sh, args.preset, args.dtype, args.overlap, args.place, args.in_format, args.out_format, output, args.pass_frames)
+        for name in p.obj:
+            p.run(name, args.warmup)
+        fps = {name: [] for name in p.obj}
+        for _ in range(args.rounds):
+            for name in p.obj:
+                fps[name].append(args.frames / p.run(name, args.frames))
+        row = {name: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)} for name, v in fps.items()}
+        row["pass_over_frame"] = round(row["pass"]["median"] / row["frame"]["median"], 4)
+        row["pass_over_frame_last"] = round(row["pass"]["median"] / row["frame_last"]["median"], 4)
+        row["stats"] = {name: p.stats(name) for name in p.obj}
+        res[text] = row
+        p.close()
+    print(json.dumps({"metric": "frames/s of a tiled object, " + args.place + " " + args.in_format.upper() + " in, " + args.place + " " +
+                      args.out_format.upper() + " out", "preset": args.preset, "dtype": args.dtype, "overlap": args.overlap,
+                      "frames_per_round": args.frames, "rounds": args.rounds, "pass_frames": args.pass_frames, "output": args.output,
+                      "filter": args.filter if args.output else None,
+                      "variants": {"frame": "ju_tiled_process_frame, frame by frame, first in the round",
+                                   "pass": "ju_tiled_process_frames in calls of " + str(args.pass_frames) + " frames",
+                                   "frame_last": "frame by frame again, last in the round"}, "fps": res}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--preset", default="psp-quality")
@@ -241,7 +346,11 @@ def main():
     ap.add_argument("--frames", type=int, default=240, help="frames per variant and round")
     ap.add_argument("--warmup", type=int, default=24)
     ap.add_argument("--out-format", default="bgrx", choices=sorted(OUT_FORMATS))
-    ap.add_argument("--compare", default="passes", choices=["passes", "deep", "scene", "output", "mask"],
+    ap.add_argument("--place", default="device", choices=["host", "device"], help="--compare pass, --trace --pass-frames: where the frames lie")
+    ap.add_argument("--in-format", default="bgrx", choices=["bgrx", "nv12"], help="--compare pass, --trace --pass-frames: the input frames' format")
+    ap.add_argument("--pass-frames", type=int, default=None, metavar="N",
+                    help="--compare pass: frames per ju_tiled_process_frames call (default 8); --trace: run the pass variant alone")
+    ap.add_argument("--compare", default="passes", choices=["passes", "deep", "scene", "output", "mask", "pass"],
                     help="passes: tiled against serial; deep: ju_tiled_set_deep_from_state 0 against 1; scene: the scene "
                          "detector off, JU_SCENE_REPORT and JU_SCENE_RESET; output: no output size against --output; "
                          "mask: no mask against the masks of --mask (all under --output where given)")
@@ -262,13 +371,28 @@ def main():
     cfg = M.PRESETS[args.preset]
     if args.summarize:
         summarize(args.summarize[0], *size(args.summarize[1]), cfg.frame_width, cfg.frame_height, args.overlap,
-                  size(args.output) if args.output else None)
+                  size(args.output) if args.output else None, args.pass_frames or 8)
         return
     output = (*size(args.output), FILTERS[args.filter]) if args.output else None
     if (args.compare == "output" or (args.two_launch and not args.mask)) and not output:
         ap.error("--compare output and --two-launch without --mask need --output WxH")
     import torch
     torch.zeros(1, device="cuda:0")  # (torch's HIP runtime first, as bench.py does)
+    if args.compare == "pass" or (args.trace and args.pass_frames):
+        args.pass_frames = args.pass_frames or 8
+        if args.pass_frames < 1 or args.frames % args.pass_frames or args.warmup % args.pass_frames:
+            ap.error("--frames and --warmup must be multiples of --pass-frames")
+    if args.trace and args.pass_frames:
+        p = PassPair(*size(args.trace), args.preset, args.dtype, args.overlap, args.place, args.in_format, args.out_format, output,
+                     args.pass_frames, names=("pass",))
+        p.run("pass", args.warmup)
+        p.run("pass", args.frames)
+        print(json.dumps({"trace": args.trace, "variant": "pass", "place": args.place, "in_format": args.in_format,
+                          "out_format": args.out_format, "frames": args.warmup + args.frames, "output": args.output, **p.stats("pass")}))
+        p.close()
+        return
+    if args.compare == "pass":
+        return compare_pass(args, output)
     if args.trace:
         name = "deep_on" if args.deep_from_state else SCENE_NAMES[args.scene] if args.scene != "off" else "tiled"
         if args.mask and not args.two_launch:
