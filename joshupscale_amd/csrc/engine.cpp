@@ -327,7 +327,7 @@ void Engine::addConvStep(std::vector<Step> *prog, const std::string &tag,
 
 // The flow auto-encoder (models.py:334-481) as launches: `items` = 1 for the per-frame program of binding set `set`,
 // > 1 for a look-ahead pass -- the same launches over `items` consecutive frames (grid.z), on the batch tensors, the
-// first block reading the frames of m_BatchIO (submitBatch).  A look-ahead pass exists only where every launch of
+// first block reading the frames of m_Pass (submitBatch).  A look-ahead pass exists only where every launch of
 // the plan has an item dimension (the one-launch blocks and the split-K convolutions): std::logic_error otherwise.
 void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, bool group, bool cut) {
 	std::vector<Step> &prog = *progOut;
@@ -338,9 +338,7 @@ void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, 
 	const int PH = c.paddedHeight(), PW = c.paddedWidth();
 	const int padTop = (PH - H) / 2, padLeft = (PW - W) / 2;  // models.py:783-787
 	const FrameIO *io = &m_IO;
-	const FrameIO *batchIO = m_BatchIO;
-	const void *const *groupPrev = m_GroupPrev;
-	void *const *groupOut = m_GroupOut;
+	const PassFrame *pass = m_Pass;
 	const void *packedIn = m_Packed[set].get();
 	void *packedOut = m_Packed[set ^ 1].get();
 	const int nIn = c.numFlowInputs;
@@ -415,16 +413,16 @@ void Engine::addFlowAutoencoder(std::vector<Step> *progOut, int set, int items, 
 				fb.independentItems = true;
 			}
 			if (cut) fb.cutAt = m_ScenePassDev.as<ScenePassState>()->cutAt;
-			prog.push_back({"flow", flops, [dt, fb, io, batchIO, groupPrev, groupOut, items, group](hipStream_t s) {
+			prog.push_back({"flow", flops, [dt, fb, io, pass, items, group](hipStream_t s) {
 				                FlowBlockLaunch f = fb;  // the caller's frames are known at launch time only
 				                f.packFrame = io->in;
 				                f.packFrameStride = io->inStride;
 				                for (int i = 0; i < items && (items > 1 || group); ++i) {
-					                f.packFrames[i] = batchIO[i].in;
-					                f.packFrameStrides[i] = batchIO[i].inStride;
+					                f.packFrames[i] = pass[i].io.in;
+					                f.packFrameStrides[i] = pass[i].io.inStride;
 					                if (group) {
-						                f.packPrevs[i] = groupPrev[i];
-						                f.packOuts[i] = groupOut[i];
+						                f.packPrevs[i] = pass[i].groupPrev;
+						                f.packOuts[i] = pass[i].groupOut;
 					                }
 				                }
 				                launchFlowBlock(dt, f, s);
@@ -1765,9 +1763,10 @@ double Engine::timeSteps(const std::string &tagSpecIn, int iters, int *launches)
 	std::unique_lock<std::mutex> chain = chainBegin(m_Resident);  // (the timed launches may be resident towers)
 	if (inPass) {
 		const int n = m_BatchMax, set = m_Idx;
+		m_PassStage = 0;  // (a plain pass, whatever the pass bound last carried: nothing of it is left to launch on)
 		for (int i = 0; i < n; ++i) {  // (every frame of the pass on the staging buffers)
-			m_BatchIO[i] = m_IO;
-			m_BatchHost[i] = PassFrame{};
+			m_Pass[i] = PassFrame{};
+			m_Pass[i].io = m_Pass[i].ends = m_IO;
 		}
 		std::vector<std::unique_ptr<Event>> ev;
 		const std::function<void(const Step &, bool)> around = [&](const Step &s, bool) {

@@ -486,12 +486,11 @@ private:
 	bool directEligible(const Frame &in, const Frame &out) const;
 	DirectEntry &directEntry(const DirectKey &key);
 	void captureDirect(DirectEntry *e, int idx);
-	// frame look-ahead (processBatch; engine_passes.cpp): the frames of the pass being recorded, the flow net's tensors for
-	// m_BatchCap frames, the state buffers between the frames of a pass, the flow launches per (frames, binding set)
-	// and the graphs per tuple of frame buffers
-	FrameIO m_BatchIO[kFlowBatchMax];
+	// frame look-ahead (processBatch; engine_passes.cpp): the flow net's tensors for m_BatchCap frames, the state buffers
+	// between the frames of a pass, the flow launches per (frames, binding set) and the graphs per tuple of frame buffers;
+	// the frames of the pass being recorded: m_Pass, below
 	// The key of a pass's graph: per frame, everything a launch of the pass bakes in.  `io`: what the frame's kernels read
-	// and write (bindBatch).  A YUV side adds its format and colour space and, for device planes, their pointers and
+	// and write (bindFrame).  A YUV side adds its format and colour space and, for device planes, their pointers and
 	// strides; for host planes (staged in the pass's own buffers) only the sign of each stride -- all-host passes of one
 	// shape share one graph whatever the caller's addresses.  BGRX sides leave their YuvKey zero.
 	struct YuvKey {
@@ -504,7 +503,7 @@ private:
 		DirectKey io;
 		YuvKey in, out;
 		int scene = 0;  // scenePass() when the pass was bound: no graph serves another detector configuration
-		// stagePass() when the pass was bound: a staged pass and a plain pass over the same buffers never share a graph.
+		// stageBits(false) when the pass was bound: a staged pass and a plain pass over the same buffers never share a graph.
 		// `ends`: what a staged frame's scale, blend and encode launches read and write at the frame's own size -- the
 		// caller's device image or the pass's slot (`io` is then the model-size pair in between)
 		int stage = 0;
@@ -529,28 +528,48 @@ private:
 	// the only path the reference's own timer measures, scripts/inference/tensorrt/inference.py:245-251).  Frame by frame
 	// the 8.3 MB of an output cross the PCIe link while the GPU idles -- the frame's rows all appear in its last
 	// microseconds and the next frame needs this one's state.  Inside a pass that is no longer so: every input of the
-	// pass is uploaded up front into the pass's own device buffers (m_PassIn), frame i's kernels write m_PassOut[i], a
-	// one-thread kernel behind frame i's last launch counts it done in host-mapped memory (m_PassSignal), and the thread
+	// pass is uploaded up front into the pass's own device buffers (m_PassSlots[i].in), frame i's kernels write
+	// m_PassSlots[i].out, a one-thread kernel behind frame i's last launch counts it done in host-mapped memory (m_PassSignal), and the thread
 	// blocked in processBatch copies frame i out on a second stream (SDMA, no CU) while frame i + 1 runs: only the last
 	// frame's copy is exposed.  The copies go from / to the caller's pageable rows through the HIP runtime as in
 	// stageIn / stageOut (cuda_convert.cc.cu:360-459); nothing of the caller's is page-locked (section 7 of DESIGN.md).
-	// YUV sides: the frame's kernels read / write BGRX in m_PassIn[i] / m_PassOut[i] whatever the side's location;
-	// `planes` are what the side's conversion launch of the pass reads (in: decode) / writes (out: encode) -- the caller's
-	// device planes, or for host planes slot i of m_PassYuvIn / m_PassYuvOut (rows padded to stagePitch, in the caller's
-	// memory order).
+	// YUV sides: the frame's kernels read / write BGRX in those two slots whatever the side's location; `planes` are what
+	// the side's conversion launch of the pass reads (in: decode) / writes (out: encode) -- the caller's device planes, or
+	// for host planes m_PassSlots[i].yuvIn / .yuvOut (rows padded to stagePitch, in the caller's memory order).
 	struct PassSide {
 		bool host = false, yuv = false;
 		PixelFormat format = PixelFormat::Bgrx;
 		int colorspace = 0;
 		YuvPlanes planes;
 	};
+	struct PassExtent {
+		std::size_t inW = 0, inH = 0, outW = 0, outH = 0;
+	};
+	struct PassCopy {
+		DeviceBuffer *image = nullptr, *planes = nullptr;
+	};
+	// Frame i (a group pass: member i) of the pass bound last, as bindFrame left it -- everything the pass's launches and
+	// host copies know about it.  io: what the network reads and writes, addressed with the sign of a host caller's stride.
+	// ends: the frame's rows at its own size (PassKey::ends) -- the same rows as io on a side without a scaler, else what
+	// the scaler reads / writes there while io is the model-size staged slot in between.  size: the frame's size on either
+	// side (passSizes under the owner's stage bits).  up / down: the device buffers the host copies of the frame go to /
+	// come from.  groupPrev / groupOut: on the lead of a group pass, the history item i's first flow block reads / writes.
+	// m_PassStage heads the array: the stage bits the look-ahead pass was bound with (a group pass: 0 -- each member
+	// brings its own).  A fixed-address member: the step lambdas and the captured graphs hold pointers into it and read it
+	// at launch time.
 	struct PassFrame {
 		PassSide in, out;
+		FrameIO io, ends;
+		PassExtent size;
+		PassCopy up, down;
+		const void *groupPrev = nullptr;
+		void *groupOut = nullptr;
 		bool host() const { return in.host || out.host; }
 		bool yuv() const { return in.yuv || out.yuv; }
 	};
-	PassFrame m_BatchHost[kFlowBatchMax];
-	// binds one side of a pass's frame (bindBatch): fills `side` and the side's part of the graph key, returns what the
+	int m_PassStage = 0;
+	PassFrame m_Pass[kFlowBatchMax];
+	// binds one side of a pass's frame (bindFrame): fills `side` and the side's part of the graph key, returns what the
 	// frame's kernels read / write there.  image / planes: the pass's own device buffers of that side and frame, made here
 	// when first needed.
 	struct BoundRows {
@@ -559,64 +578,56 @@ private:
 	};
 	BoundRows bindSide(const AnyFrame &a, std::size_t width, std::size_t height, DeviceBuffer *image, DeviceBuffer *planes,
 	    PassSide *side, YuvKey *key);
-	DeviceBuffer m_PassIn[kFlowBatchMax], m_PassOut[kFlowBatchMax];
-	DeviceBuffer m_PassYuvIn[kFlowBatchMax], m_PassYuvOut[kFlowBatchMax];
-	// Scaled and masked frames inside look-ahead passes (setStageLookahead; engine_passes.cpp).  stagePass(): what a pass
-	// formed now carries -- 0 nothing, else bit 0 the source scaler, bit 1 the mask, bit 2 the output scaler; m_PassStage:
-	// that value for the pass bound last (bindBatch; a group pass: 0).  Per frame of the cap, made when first needed at
-	// the sizes set and dropped with the staged passes' graphs whenever a stage setter changes anything (dropStagePasses):
-	// m_StageSrc / m_StageSrcYuv the source-size BGRX frame and host planes, m_StageIn the model-size input the one scale
-	// launch fills, m_StageModelOut the model-size output the network writes under an output size, m_StageOut8 /
-	// m_StageOut16 / m_StageOutYuv the 8-bit frame, the 16-bit frame and the host planes at output size.
-	// m_PassEnds[i]: the frame's rows at its own size (PassKey::ends); m_PassUp / m_PassDown: the device buffers the host
-	// copies of frame i go to / come from (image, planes).
-	bool m_StageLookahead = false;
-	int m_PassStage = 0;
-	int stagePass() const {
-		if (!m_StageLookahead || !sourceStage()) return 0;
+	// the pass's own buffers of frame i at the model's sizes: the BGRX image and the host planes of either side
+	struct PassSlots {
+		DeviceBuffer in, out, yuvIn, yuvOut;
+	};
+	PassSlots m_PassSlots[kFlowBatchMax];
+	// Scaled and masked frames inside passes (setStageLookahead, setStageGroup; engine_passes.cpp).  stageBits(group): what
+	// a look-ahead pass formed now carries -- group: what this runtime brings into a group pass, the same bits under its
+	// own setting -- 0 nothing, else bit 0 the source scaler, bit 1 the mask, bit 2 the output scaler.
+	// StageSlots: the buffers of one frame under a scaler, each made when first needed at the sizes set -- src / srcYuv the
+	// source-size BGRX frame and host planes, `in` the model-size input the one scale launch fills, modelOut the model-size
+	// output the network writes under an output size, out8 / out16 / outYuv the 8-bit frame, the 16-bit frame and the host
+	// planes at output size.  m_StageSlots: one per frame of the cap, for look-ahead passes.  m_GroupSlots: a member
+	// contributes one frame per group pass, so it owns ONE, at THIS runtime's sizes.  All dropped by dropStagePasses, with
+	// the staged passes' graphs, whenever one of this runtime's stage setters changes anything.  A member's slots live in
+	// the member, not the lead: a setter or the destruction of one runtime touches no other runtime's memory, and the lead
+	// keeps no pointer to them beyond the call (runGroupPass clears the records' up / down).
+	// m_BatchStagedFrames: "lookahead_staged_frames"; m_GroupStagedFrames: "group_staged_frames".
+	bool m_StageLookahead = false, m_StageGroup = false;
+	int stageBits(bool group) const {
+		if (!(group ? m_StageGroup : m_StageLookahead) || !sourceStage()) return 0;
 		return (m_SrcScale.set() ? 1 : 0) | (m_MaskW != 0 ? 2 : 0) | (m_OutScale.set() ? 4 : 0);
 	}
-	DeviceBuffer m_StageSrc[kFlowBatchMax], m_StageSrcYuv[kFlowBatchMax], m_StageIn[kFlowBatchMax];
-	DeviceBuffer m_StageModelOut[kFlowBatchMax], m_StageOut8[kFlowBatchMax], m_StageOut16[kFlowBatchMax], m_StageOutYuv[kFlowBatchMax];
-	FrameIO m_PassEnds[kFlowBatchMax];
-	// the size frame i of the pass bound last has on either side (bindBatch: passSizes for all; bindGroup: member i's own)
-	struct PassExtent {
-		std::size_t inW = 0, inH = 0, outW = 0, outH = 0;
-	};
-	PassExtent m_PassSize[kFlowBatchMax];
-	struct PassCopy {
-		DeviceBuffer *image = nullptr, *planes = nullptr;
-	};
-	PassCopy m_PassUp[kFlowBatchMax], m_PassDown[kFlowBatchMax];
-	std::uint64_t m_BatchStagedFrames = 0;
-	void dropStagePasses();
-	// Scaled and masked members inside group passes (setStageGroup; engine_passes.cpp).  groupStage(): what this runtime
-	// brings into a group pass -- stagePass()'s bits under its own setting.  A member contributes one frame per pass, so it
-	// owns ONE set of slots, m_GroupSlots, named as the look-ahead passes' (src / srcYuv at source size, in / modelOut at the
-	// model's sizes, out8 / out16 / outYuv at output size), each made when first needed at THIS runtime's sizes and dropped
-	// by dropStagePasses -- whenever one of its stage setters changes anything.  They live in the member, not the lead: a
-	// setter or the destruction of one runtime touches no other runtime's memory, and the lead keeps no pointer to them
-	// beyond the call (runGroupPass clears m_PassUp / m_PassDown).  m_GroupStagedFrames: "group_staged_frames".
-	bool m_StageGroup = false;
-	int groupStage() const {
-		if (!m_StageGroup || !sourceStage()) return 0;
-		return (m_SrcScale.set() ? 1 : 0) | (m_MaskW != 0 ? 2 : 0) | (m_OutScale.set() ? 4 : 0);
-	}
-	struct GroupSlots {
+	struct StageSlots {
 		DeviceBuffer src, srcYuv, in, modelOut, out8, out16, outYuv;
 	};
-	GroupSlots m_GroupSlots;
-	std::uint64_t m_GroupStagedFrames = 0;
-	// bindBatch for the members of a group pass, on the lead: member i's pair at member i's own sizes (stage[i] =
-	// m[i]->groupStage()), a side under a scaler through member i's own slots, any other through the lead's
+	StageSlots m_StageSlots[kFlowBatchMax], m_GroupSlots;
+	std::uint64_t m_BatchStagedFrames = 0, m_GroupStagedFrames = 0;
+	void dropStagePasses();
+	// Binds one frame of a pass, on the runtime whose stream runs it (the lead): fills `f` and, if asked, the sides' parts
+	// of the frame's graph key.  owner: whose scalers, sizes and format rules apply -- this runtime for a look-ahead pass,
+	// member i for a group pass; staged: the owner's slots for the sides under one of its scalers; plain: this runtime's
+	// slots for the others.
+	void bindFrame(PassFrame *f, const Engine &owner, int stage, const AnyFrame &in, const AnyFrame &out, StageSlots *staged,
+	    PassSlots *plain, PassKey *key);
+	// the members of a group pass, on the lead: member i's pair under member i's own stage bits, sizes and slots
 	void bindGroup(Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n, const int *stage);
+	// What follows a frame's own steps in a pass, on this runtime's stream (the lead's): the owner's mask blend in place,
+	// its output scaler, the encode and the host signal.  stateOut: the state the frame's steps wrote; out16: the frame's
+	// 16-bit slot at output size.
+	void passTail(Engine &owner, const PassFrame &f, int stage, void *stateOut, const DeviceBuffer &out16);
+	// this runtime's mask over the model-size frame `gen`, letting through the source rows `src` of srcW x srcH
+	void blendMask(std::uint8_t *gen, std::ptrdiff_t genStride, const std::uint8_t *src, std::ptrdiff_t srcStride, std::size_t srcW,
+	    std::size_t srcH, hipStream_t stream);
 	// the size frames must have on a side of a pass bound with `stage`
 	void passSizes(int stage, std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const;
 	std::unique_ptr<Stream> m_CopyStream;
 	PinnedWords m_PassSignal;
 	unsigned m_PassSignalBase = 0;
 	std::uint64_t m_BatchHostFrames = 0, m_BatchYuvFrames = 0;
-	// group: as a member of a group pass -- under groupStage() in place of stagePass(), and the detector's group setting
+	// group: as a member of a group pass -- under stageBits(true) and the detector's group setting
 	bool passEligible(const AnyFrame &in, const AnyFrame &out, bool group = false) const;
 	void uploadPassInputs(const AnyFrame *in, int n);
 	void drainPassOutputs(const AnyFrame *out, int n);
@@ -631,17 +642,14 @@ private:
 	void submitBatch(const AnyFrame *in, const AnyFrame *out, int n);
 	void runBatch(int set, int n, const std::function<void(const Step &, bool)> *around = nullptr);
 	void dropBatchGraphs();
-	// stage: stagePass() for a look-ahead pass, 0 for a group pass (which carries no stage, whatever the lead's settings)
+	// the n frames of a look-ahead pass under stage = stageBits(false); returns the key of the pass's graph
 	std::vector<PassKey> bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set, int stage);
 	DirectEntry &batchEntry(const std::vector<PassKey> &key);
 	// Group passes (processGroup).  The model's identity: FNV-1a of the container bytes the engine was built from, and
-	// the dtype it was asked for.  As the lead of a pass: the history each item's first flow block reads / writes (read
-	// at launch time).  As a member: an event its stream records for the lead to wait on, and the frames it got from
-	// passes ("group_frames").
+	// the dtype it was asked for.  As a member: an event its stream records for the lead to wait on, and the frames it got
+	// from passes ("group_frames").  (As the lead: the history each item's first flow block reads and writes is in m_Pass.)
 	std::uint64_t m_ModelDigest = 0;
 	int m_DtypeOverride = -1;
-	const void *m_GroupPrev[kFlowBatchMax] = {};
-	void *m_GroupOut[kFlowBatchMax] = {};
 	Event m_GroupEvent;
 	std::uint64_t m_GroupFrames = 0, m_GroupYuvFrames = 0;  // ("group_yuv_frames": those of them with a non-BGRX side)
 	bool sameModel(const Engine &o) const;

@@ -387,7 +387,6 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 	m_DirectIO = false;
 	bindStaging();
 	const FrameSize fs = frameSize();
-	const int inW = static_cast<int>(fs.inputWidth), inH = static_cast<int>(fs.inputHeight);
 	// what the mask lets through: the source frame at source size, or the model-size input frame
 	SourceView source{m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4)};
 	if (m_SrcScale.set()) {
@@ -407,11 +406,8 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 	}
 	if (m_MaskW != 0) {
 		// over the frame handed to the caller only: state and history are the unmasked run's
-		launchMaskBlend(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4),
-		    static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight), source.ptr, source.stride,
-		    m_SrcScale.set() ? static_cast<int>(m_SrcScale.srcW()) : inW, m_SrcScale.set() ? static_cast<int>(m_SrcScale.srcH()) : inH,
-		    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0),
-		    m_MaskStride, static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), m_Stream);
+		blendMask(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4), source.ptr, source.stride,
+		    m_SrcScale.set() ? m_SrcScale.srcW() : fs.inputWidth, m_SrcScale.set() ? m_SrcScale.srcH() : fs.inputHeight, m_Stream);
 	}
 	if (sourceStage()) ++m_SourceFrames;
 	// (behind the frame's program and before the flip: the state this frame wrote is the binding set's output)

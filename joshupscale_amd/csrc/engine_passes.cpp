@@ -12,6 +12,17 @@
 
 namespace ju {
 
+namespace {
+// runs f when the scope ends, also by an exception: what a pass rebinds for its launches goes back to what it was
+template <typename F>
+struct AtExit {
+	F f;
+	~AtExit() { f(); }
+};
+template <typename F>
+AtExit(F) -> AtExit<F>;
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------------------------
 // Frame look-ahead.  The flow net reads LR frames only -- never the HR state (models.py:790, 823: its input is the
 // packed history of the last num_flow_inputs frames) -- so the flow fields of n consecutive frames can be computed
@@ -129,7 +140,7 @@ void Engine::dropBatchGraphs() {
 	m_BatchGraphs.clear();
 }
 
-// The launches of one look-ahead pass over the n frames of m_BatchIO, in stream order (recorded when m_Stream is
+// The launches of one look-ahead pass over the n frames of m_Pass, in stream order (recorded when m_Stream is
 // capturing): the flow net over all frames, then frame by frame the rest of binding set `set`'s per-frame program,
 // bound to the frame's buffers, its flow field and its link of the state chain.
 void Engine::runBatch(int set, int n, const std::function<void(const Step &, bool)> *around) {
@@ -143,29 +154,24 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 	const bool recurrent = m_Config.recurrent();  // (flow-free: no flow fields, no state chain)
 	const long flowItem = recurrent ? static_cast<long>(m_Tensors.at("flow").count) * 2 : 0;
 	const unsigned char *flowBase = recurrent ? m_BatchTensors.at("flow").buf.as<unsigned char>() : nullptr;
-	const FrameIO keepIO = m_IO;
 	const StateBind keepBind = m_StateBind[set];
-	const void *keepFlow = m_FlowCur;
-	struct Restore {
-		std::function<void()> f;
-		~Restore() { f(); }
-	} restore{[&] {
+	AtExit restore{[this, set, keepBind, keepIO = m_IO, keepFlow = m_FlowCur] {
 		m_IO = keepIO;
 		m_StateBind[set] = keepBind;
 		m_FlowCur = keepFlow;
 	}};
 	// the pass's YUV inputs into their frames' BGRX buffers, all in one launch (a flow-free pass has no launch before it):
-	// at the frames' own size -- the model's input, or under a source size the source-size slots (m_PassEnds)
+	// at the frames' own size -- the model's input, or under a source size the source-size slots (PassFrame::ends)
 	const int stage = m_PassStage;
 	std::size_t inW, inH, outW, outH;
 	passSizes(stage, &inW, &inH, &outW, &outH);
 	YuvDecodeItems items{};
 	int decodes = 0;
 	for (int i = 0; i < n; ++i) {
-		const PassFrame &pf = m_BatchHost[i];
-		if (!pf.in.yuv) continue;
-		items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(m_PassEnds[i].in),
-		    m_PassEnds[i].inStride);
+		const PassFrame &f = m_Pass[i];
+		if (!f.in.yuv) continue;
+		items.item[decodes++] = yuvDecodeItem(fmt(f.in.format), f.in.colorspace, f.in.planes, const_cast<std::uint8_t *>(f.ends.in),
+		    f.ends.inStride);
 	}
 	if (decodes) launchYuv420ToBgrxItems(items, decodes, static_cast<int>(inW), static_cast<int>(inH), m_Stream);
 	// a source size: ONE launch scales all n sources -- the caller's device images where they are, the upload slots, the
@@ -174,7 +180,8 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 	if (stage & 1) {
 		ScaleItems scale{};
 		for (int i = 0; i < n; ++i) {
-			scale.item[i] = ScaleItem{m_PassEnds[i].in, m_PassEnds[i].inStride, const_cast<std::uint8_t *>(m_BatchIO[i].in), m_BatchIO[i].inStride};
+			const PassFrame &f = m_Pass[i];
+			scale.item[i] = ScaleItem{f.ends.in, f.ends.inStride, const_cast<std::uint8_t *>(f.io.in), f.io.inStride};
 		}
 		m_SrcScale.scaleBgrxItems(scale, n, m_Stream);
 	}
@@ -188,8 +195,8 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		ScenePassLaunch q;
 		q.items = n;
 		for (int i = 0; i < n; ++i) {
-			q.frames[i] = m_BatchIO[i].in;
-			q.strides[i] = m_BatchIO[i].inStride;
+			q.frames[i] = m_Pass[i].io.in;
+			q.strides[i] = m_Pass[i].io.inStride;
 		}
 		q.width = static_cast<int>(fs.inputWidth);
 		q.height = static_cast<int>(fs.inputHeight);
@@ -203,7 +210,7 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 	}
 	for (const Step &st : flow) run(st);
 	for (int i = 0; i < n; ++i) {
-		m_IO = m_BatchIO[i];
+		m_IO = m_Pass[i].io;
 		if (recurrent) {
 			m_FlowCur = flowBase + i * flowItem;
 			m_StateBind[set].in = i == 0 ? keepBind.in : m_BatchState[i - 1].get();
@@ -217,36 +224,51 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		for (const Step &st : m_Program[set]) {
 			if (st.tag != "flow" && st.tag != "pack") run(st);
 		}
-		const FrameIO &ends = m_PassEnds[i];
-		const PassSide &po = m_BatchHost[i].out;
-		if (stage & 2) {
-			// the mask, in place over the model-size frame the tail wrote, through submitFrame's `source`: the frame's own
-			// source rows, or the model-size input when no source size is set
-			const FrameSize fs = frameSize();
-			launchMaskBlend(m_BatchIO[i].out, m_BatchIO[i].outStride, static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight),
-			    ends.in, ends.inStride, static_cast<int>(inW), static_cast<int>(inH),
-			    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0),
-			    m_MaskStride, static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), m_Stream);
-		}
-		const std::uint16_t *frame16 = nullptr;
-		if (stage & 4) {  // stageOutScaled's rules: the 8-bit frame, or for a deep format from the state this frame's link
-			if (po.yuv && deepFromState(po.format)) {
-				auto *scaled16 = m_StageOut16[i].as<std::uint16_t>();
-				m_OutScale.scaleState(m_StateBind[set].out, scaled16, m_Stream);
-				frame16 = scaled16;
-			} else {
-				m_OutScale.scaleBgrx(m_BatchIO[i].out, m_BatchIO[i].outStride, ends.out, ends.outStride, m_Stream);
-			}
-		}
-		if (po.yuv) {  // the frame's BGRX output (its slot) into the caller's device planes / the staging slot
-			// (a 10-bit output from the state: THIS frame's link of the chain -- m_BatchState[i], the last frame's
-			// m_State[set ^ 1]; a flow-free pass has one scratch state that the next frame's tail overwrites, so the encode
-			// stays on this stream in front of the next frame's kernels)
-			encodeYuv(po.format, po.colorspace, po.planes, outW, outH, ends.out, ends.outStride, m_StateBind[set].out, frame16);
-		}
-		// (a host frame: its bytes are complete in m_PassOut[i] / m_PassYuvOut[i] -- tell the thread that copies them out)
-		if (m_BatchHost[i].out.host) launchSignalHost(m_PassSignal.device(), m_Stream);
+		// (a 10-bit output from the state: THIS frame's link of the chain -- m_BatchState[i], the last frame's
+		// m_State[set ^ 1]; a flow-free pass has one scratch state that the next frame's tail overwrites, so the encode
+		// stays on this stream in front of the next frame's kernels)
+		passTail(*this, m_Pass[i], stage, m_StateBind[set].out, m_StageSlots[i].out16);
 	}
+}
+
+// Behind a frame's own steps, what submitFrame strings behind the program -- the single-frame launches with the owner's
+// own mask and scaler, in stream order on this runtime's stream.
+void Engine::passTail(Engine &owner, const PassFrame &f, int stage, void *stateOut, const DeviceBuffer &out16) {
+	if (stage & 2) {
+		// the mask, in place over the model-size frame the tail wrote (a slot the pass alone writes, or the caller's output),
+		// through submitFrame's `source`: the frame's own source rows, or the model-size input when no source size is set
+		owner.blendMask(f.io.out, f.io.outStride, f.ends.in, f.ends.inStride, f.size.inW, f.size.inH, m_Stream);
+	}
+	const std::uint16_t *frame16 = nullptr;
+	if (stage & 4) {  // stageOutScaled's rules: the 8-bit frame, or for a deep format from the state the frame's steps wrote
+		if (f.out.yuv && owner.deepFromState(f.out.format)) {
+			auto *scaled16 = out16.as<std::uint16_t>();
+			owner.m_OutScale.scaleState(stateOut, scaled16, m_Stream);
+			frame16 = scaled16;
+		} else {
+			owner.m_OutScale.scaleBgrx(f.io.out, f.io.outStride, f.ends.out, f.ends.outStride, m_Stream);
+		}
+	}
+	// a non-BGRX output: the frame's BGRX output at its own output size (a plain slot, or the owner's scaled slot) into the
+	// caller's device planes / the staging slot.  A deep format is encoded from the f16 state THE OWNER's step just wrote
+	// -- in a group pass never the lead's -- or from the blended or scaled 8-bit frame while the owner has a mask or
+	// "hbd_from_state" 0 (deepFromState)
+	if (f.out.yuv) {
+		owner.encodeYuv(f.out.format, f.out.colorspace, f.out.planes, f.size.outW, f.size.outH, f.ends.out, f.ends.outStride, stateOut,
+		    frame16, m_Stream);
+	}
+	// (a host frame: its bytes are complete in the slot `down` names -- tell the thread that copies them out)
+	if (f.out.host) launchSignalHost(m_PassSignal.device(), m_Stream);
+}
+
+void Engine::blendMask(std::uint8_t *gen, std::ptrdiff_t genStride, const std::uint8_t *src, std::ptrdiff_t srcStride, std::size_t srcW,
+    std::size_t srcH, hipStream_t stream) {
+	const FrameSize fs = frameSize();
+	// (a bottom-up mask: from its last row in memory, with the negative stride)
+	launchMaskBlend(gen, genStride, static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight), src, srcStride,
+	    static_cast<int>(srcW), static_cast<int>(srcH),
+	    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0), m_MaskStride,
+	    static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), stream);
 }
 
 // A frame may go into a pass when each of its two images is either a device-resident one the kernels can read / write in
@@ -255,7 +277,7 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out, bool group) const {
 	// (scaled / masked frames run one by one through submitFrame unless the passes carry the stages: setStageLookahead; a
 	// group pass: setStageGroup)
-	const int stage = group ? groupStage() : stagePass();
+	const int stage = stageBits(group);
 	if (sourceStage() && !stage) return false;
 	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
 	// unless the pass carries the detector and applies the cuts itself: setSceneLookahead; a group pass: setSceneGroup)
@@ -293,7 +315,7 @@ void Engine::passSizes(int stage, std::size_t *inW, std::size_t *inH, std::size_
 // frame the tail wrote -- so a pass takes them as it takes the colour conversions: the n sources are scaled by ONE launch
 // (scale_bgrx_items_kernel) behind the one decode launch and in front of the detector and the flow net; blend, output
 // scale and encode follow each frame's tail in stream order, reading that frame's link of the state chain.  What the
-// network reads and writes in between are the pass's model-size slots (m_StageIn / m_StageModelOut); every launch is the
+// network reads and writes in between are the pass's model-size slots (m_StageSlots[i].in / .modelOut); every launch is the
 // one submitFrame makes, with the same arguments but the buffers, so the bytes are the frame-by-frame route's.
 // ---------------------------------------------------------------------------------------------------------------
 void Engine::setStageLookahead(int on) {
@@ -311,142 +333,105 @@ void Engine::dropStagePasses() {
 	for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
 		it = (!it->first.empty() && it->first.front().stage != 0) ? m_BatchGraphs.erase(it) : std::next(it);
 	}
-	for (DeviceBuffer *slots : {m_StageSrc, m_StageSrcYuv, m_StageIn, m_StageModelOut, m_StageOut8, m_StageOut16, m_StageOutYuv}) {
-		for (int i = 0; i < kFlowBatchMax; ++i) slots[i] = DeviceBuffer();
-	}
+	for (StageSlots &slots : m_StageSlots) slots = StageSlots();
 	// (this runtime's slots as a member of group passes: of the old sizes too.  A group pass is synchronous, so the lead's
 	// stream, which ran the launches that used them, has drained, and no lead keeps a pointer to them: runGroupPass)
-	m_GroupSlots = GroupSlots();
+	m_GroupSlots = StageSlots();
 }
 
 void Engine::setStageGroup(int on) {
 	if (on != 0 && on != 1) throw std::invalid_argument("ju_set_stage_group: on must be 0 or 1, got " + std::to_string(on));
 	DeviceGuard g(m_Device);
 	m_Stream.synchronize();
-	if (m_StageGroup != (on != 0)) m_GroupSlots = GroupSlots();
+	if (m_StageGroup != (on != 0)) m_GroupSlots = StageSlots();
 	m_StageGroup = on != 0;
 }
 
-// Binds the n frames of a pass: m_BatchIO[i] = what frame i's kernels read and write -- the caller's device memory, or
-// for a host image the pass's device buffer i, addressed with the SIGN of the caller's stride (a bottom-up host frame is
-// uploaded / downloaded in memory order and read / written bottom-up by the kernels: no flip pass).  The key of the
-// pass's graph is made of those bindings, so all-host passes of one length and orientation share one graph.
+// Binds one frame of a pass: f->io = what the frame's kernels read and write -- the caller's device memory, or for a
+// host image the pass's device buffer, addressed with the SIGN of the caller's stride (a bottom-up host frame is
+// uploaded / downloaded in memory order and read / written bottom-up by the kernels: no flip pass).
 //
-// YUV frames in look-ahead passes (processFrames).  A YUV input of frame i is decoded into m_PassIn[i], a YUV output
-// encoded from m_PassOut[i] (top-down BGRX rows both), whatever the planes' location: m_BatchHost[i].in / .out hold
-// the planes those conversion launches read / write.  Device planes: the caller's, in place.  Host planes: slot i of
-// m_PassYuvIn / m_PassYuvOut, plane after plane with rows padded to stagePitch and in the caller's MEMORY order, so a
-// bottom-up plane is addressed from its last row with a negative pitch -- the layout of stageInYuv / stageOutYuv.
+// YUV frames (processFrames, processGroupFrames).  A YUV input is decoded into plain->in, a YUV output encoded from
+// plain->out (top-down BGRX rows both), whatever the planes' location: f->in / f->out hold the planes those conversion
+// launches read / write.  Device planes: the caller's, in place.  Host planes: plain->yuvIn / plain->yuvOut, plane
+// after plane with rows padded to stagePitch and in the caller's MEMORY order, so a bottom-up plane is addressed from
+// its last row with a negative pitch -- the layout of stageInYuv / stageOutYuv.
 //
-// A staged pass (stage != 0): a side under a scaler is bound at the size set, to slots of its own (m_StageSrc ... /
-// m_StageOut8 ...), and lands in m_PassEnds[i]; m_BatchIO[i] is then the model-size slot between that scaler and the
-// network.  Without a scaler on a side the two are the same rows.  The slots of a kind are made for the whole cap when
-// the first of them is needed, so no later pass moves what a captured one is bound to.
-std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set, int stage) {
+// A staged frame (stage != 0): a side under one of the owner's scalers is bound at the size set there, to the owner's
+// slots (`staged`) in place of the plain ones, and lands in f->ends: the source-size rows the decode / upload fills and
+// the scale launch reads, the output-size rows the output scaler writes.  f->io is then the model-size slot between that
+// scaler and the network -- the input the scale launch fills, the frame the tail writes and the blend rewrites.  Without
+// a scaler on a side the two are the same rows.
+void Engine::bindFrame(PassFrame *f, const Engine &owner, int stage, const AnyFrame &in, const AnyFrame &out, StageSlots *staged,
+    PassSlots *plain, PassKey *key) {
 	const FrameSize fs = frameSize();
-	m_PassStage = stage;
-	std::size_t inW, inH, outW, outH;
-	passSizes(stage, &inW, &inH, &outW, &outH);
+	PassExtent &sz = f->size;
+	owner.passSizes(stage, &sz.inW, &sz.inH, &sz.outW, &sz.outH);
 	const bool scaledIn = (stage & 1) != 0, scaledOut = (stage & 4) != 0;
-	const int cap = std::max(n, m_BatchMax);
-	const StageSlotBytes bytes = stageSlotBytes(inW, inH, fs.inputWidth, fs.inputHeight, fs.outputWidth, fs.outputHeight, outW, outH);
-	auto slots = [cap](DeviceBuffer *kind, std::size_t bytes) {
-		for (int k = 0; k < cap; ++k) {
-			if (!kind[k].get()) kind[k] = DeviceBuffer(bytes);
-		}
+	const StageSlotNeeds need = stageSlotNeeds(stage, in.yuv || locationOf(in) == Location::Host,
+	    out.yuv || locationOf(out) == Location::Host, out.yuv && owner.deepFromState(out.planes.format));
+	const StageSlotBytes bytes = stageSlotBytes(sz.inW, sz.inH, fs.inputWidth, fs.inputHeight, fs.outputWidth, fs.outputHeight, sz.outW,
+	    sz.outH);
+	auto slot = [](DeviceBuffer &b, std::size_t size) {
+		if (!b.get()) b = DeviceBuffer(size);
 	};
+	if (need.input) slot(staged->in, bytes.input);
+	if (need.modelOutput) slot(staged->modelOut, bytes.modelOutput);
+	if (need.out16) slot(staged->out16, bytes.out16);
+	// (src / out8 and the plane buffers: made by bindSide, which is handed the frame's sizes, when the side needs them)
+	f->up = scaledIn ? PassCopy{&staged->src, &staged->srcYuv} : PassCopy{&plain->in, &plain->yuvIn};
+	f->down = scaledOut ? PassCopy{&staged->out8, &staged->outYuv} : PassCopy{&plain->out, &plain->yuvOut};
+	YuvKey unusedIn, unusedOut;
+	const BoundRows r = bindSide(in, sz.inW, sz.inH, f->up.image, f->up.planes, &f->in, key ? &key->in : &unusedIn);
+	const BoundRows w = bindSide(out, sz.outW, sz.outH, f->down.image, f->down.planes, &f->out, key ? &key->out : &unusedOut);
+	f->io = f->ends = FrameIO{r.ptr, r.stride, w.ptr, w.stride};
+	if (scaledIn) {
+		f->io.in = staged->in.as<std::uint8_t>();
+		f->io.inStride = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
+	}
+	if (scaledOut) {
+		f->io.out = staged->modelOut.as<std::uint8_t>();
+		f->io.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
+	}
+	if (f->out.host) {
+		if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
+		if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
+	}
+}
+
+// The n frames of a look-ahead pass, each through this runtime's own slot i.  The key of the pass's graph is made of the
+// bindings, so all-host passes of one length and orientation share one graph.  The staged slots of a kind are made for
+// the whole cap when the first of them is needed, so no later pass moves what a captured one is bound to.
+std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set, int stage) {
+	m_PassStage = stage;
+	const int cap = std::max(n, m_BatchMax);
 	std::vector<PassKey> key(static_cast<std::size_t>(n));
 	for (int i = 0; i < n; ++i) {
-		FrameIO &io = m_BatchIO[i];
-		PassFrame &pf = m_BatchHost[i];
+		PassFrame &f = m_Pass[i];
 		PassKey &k = key[static_cast<std::size_t>(i)];
-		m_PassSize[i] = PassExtent{inW, inH, outW, outH};
-		if (scaledIn) {
-			if (in[i].yuv || locationOf(in[i]) == Location::Host) slots(m_StageSrc, bytes.source);
-			if (in[i].yuv && locationOf(in[i]) == Location::Host) slots(m_StageSrcYuv, yuvStageBytes(kFormatTable, inW, inH));
-			slots(m_StageIn, bytes.input);
+		bindFrame(&f, *this, stage, in[i], out[i], &m_StageSlots[i], &m_PassSlots[i], &k);
+		for (auto kind : {&StageSlots::src, &StageSlots::srcYuv, &StageSlots::in, &StageSlots::modelOut, &StageSlots::out8,
+		         &StageSlots::out16, &StageSlots::outYuv}) {
+			const std::size_t size = (m_StageSlots[i].*kind).bytes();
+			for (int j = 0; size != 0 && j < cap; ++j) {
+				if (!(m_StageSlots[j].*kind).get()) m_StageSlots[j].*kind = DeviceBuffer(size);
+			}
 		}
-		if (scaledOut) {
-			if (out[i].yuv || locationOf(out[i]) == Location::Host) slots(m_StageOut8, bytes.out8);
-			if (out[i].yuv && locationOf(out[i]) == Location::Host) slots(m_StageOutYuv, yuvStageBytes(kFormatTable, outW, outH));
-			if (out[i].yuv && deepFromState(out[i].planes.format)) slots(m_StageOut16, bytes.out16);
-			slots(m_StageModelOut, bytes.modelOutput);
-		}
-		m_PassUp[i] = scaledIn ? PassCopy{&m_StageSrc[i], &m_StageSrcYuv[i]} : PassCopy{&m_PassIn[i], &m_PassYuvIn[i]};
-		m_PassDown[i] = scaledOut ? PassCopy{&m_StageOut8[i], &m_StageOutYuv[i]} : PassCopy{&m_PassOut[i], &m_PassYuvOut[i]};
-		const BoundRows r = bindSide(in[i], inW, inH, m_PassUp[i].image, m_PassUp[i].planes, &pf.in, &k.in);
-		const BoundRows w = bindSide(out[i], outW, outH, m_PassDown[i].image, m_PassDown[i].planes, &pf.out, &k.out);
-		io = FrameIO{r.ptr, r.stride, w.ptr, w.stride};
-		m_PassEnds[i] = io;
-		if (scaledIn) {
-			io.in = m_StageIn[i].as<std::uint8_t>();
-			io.inStride = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
-		}
-		if (scaledOut) {
-			io.out = m_StageModelOut[i].as<std::uint8_t>();
-			io.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
-		}
-		if (pf.out.host) {
-			if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
-			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
-		}
-		k.io = DirectKey{io.in, io.inStride, io.out, io.outStride, set};
+		k.io = DirectKey{f.io.in, f.io.inStride, f.io.out, f.io.outStride, set};
 		k.scene = scenePass();
 		k.stage = stage;
-		if (stage) k.ends = DirectKey{m_PassEnds[i].in, m_PassEnds[i].inStride, m_PassEnds[i].out, m_PassEnds[i].outStride, 0};
+		if (stage) k.ends = DirectKey{f.ends.in, f.ends.inStride, f.ends.out, f.ends.outStride, 0};
 	}
 	return key;
 }
 
-// The members of a group pass, bound on the lead (runGroupPass): bindBatch with member i's own stage bits and sizes in
-// place of the lead's.  A side no scaler of member i touches is bound exactly as a plain group pass binds it -- the caller's
-// device rows, or the lead's slot i (m_PassIn / m_PassOut and their plane buffers, at the model's sizes).  A side under
-// member i's source or output scaler goes through member i's OWN slots (m_GroupSlots), at member i's sizes: the source-size
-// rows the decode / upload fills and the scale launch reads land in m_PassEnds[i].in, the model-size input the scale launch
-// fills in m_BatchIO[i].in; on the output side m_BatchIO[i].out is the model-size frame the member's tail writes (and its
-// blend rewrites) and m_PassEnds[i].out the output-size rows its scaler writes.  No graph key: group passes are eager.
+// The members of a group pass, bound on the lead (runGroupPass): member i's pair under member i's own stage bits and sizes
+// in place of the lead's.  A side no scaler of member i touches is bound exactly as a plain group pass binds it -- the
+// caller's device rows, or the lead's slot i (m_PassSlots, at the model's sizes).  A side under member i's source or output
+// scaler goes through member i's OWN slots (m_GroupSlots), at member i's sizes.  No graph key: group passes are eager.
 void Engine::bindGroup(Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n, const int *stage) {
-	const FrameSize fs = frameSize();
 	m_PassStage = 0;
-	for (int i = 0; i < n; ++i) {
-		Engine &e = *m[i];
-		PassExtent &sz = m_PassSize[i];
-		e.passSizes(stage[i], &sz.inW, &sz.inH, &sz.outW, &sz.outH);
-		const bool scaledIn = (stage[i] & 1) != 0, scaledOut = (stage[i] & 4) != 0;
-		GroupSlots &g = e.m_GroupSlots;
-		const GroupSlotNeeds need = groupSlotNeeds(stage[i], in[i].yuv || locationOf(in[i]) == Location::Host,
-		    out[i].yuv || locationOf(out[i]) == Location::Host, out[i].yuv && e.deepFromState(out[i].planes.format));
-		const StageSlotBytes bytes = stageSlotBytes(sz.inW, sz.inH, fs.inputWidth, fs.inputHeight, fs.outputWidth, fs.outputHeight,
-		    sz.outW, sz.outH);
-		auto slot = [](DeviceBuffer &b, std::size_t size) {
-			if (!b.get()) b = DeviceBuffer(size);
-		};
-		if (need.input) slot(g.in, bytes.input);
-		if (need.modelOutput) slot(g.modelOut, bytes.modelOutput);
-		if (need.out16) slot(g.out16, bytes.out16);
-		// (g.src / g.out8 and the plane buffers: made by bindSide, which is handed the member's sizes, when the side needs them)
-		m_PassUp[i] = scaledIn ? PassCopy{&g.src, &g.srcYuv} : PassCopy{&m_PassIn[i], &m_PassYuvIn[i]};
-		m_PassDown[i] = scaledOut ? PassCopy{&g.out8, &g.outYuv} : PassCopy{&m_PassOut[i], &m_PassYuvOut[i]};
-		PassFrame &pf = m_BatchHost[i];
-		YuvKey unusedIn, unusedOut;
-		const BoundRows r = bindSide(in[i], sz.inW, sz.inH, m_PassUp[i].image, m_PassUp[i].planes, &pf.in, &unusedIn);
-		const BoundRows w = bindSide(out[i], sz.outW, sz.outH, m_PassDown[i].image, m_PassDown[i].planes, &pf.out, &unusedOut);
-		FrameIO &io = m_BatchIO[i];
-		io = FrameIO{r.ptr, r.stride, w.ptr, w.stride};
-		m_PassEnds[i] = io;
-		if (scaledIn) {
-			io.in = g.in.as<std::uint8_t>();
-			io.inStride = static_cast<std::ptrdiff_t>(fs.inputWidth * 4);
-		}
-		if (scaledOut) {
-			io.out = g.modelOut.as<std::uint8_t>();
-			io.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
-		}
-		if (pf.out.host) {
-			if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
-			if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
-		}
-	}
+	for (int i = 0; i < n; ++i) bindFrame(&m_Pass[i], *m[i], stage[i], in[i], out[i], &m[i]->m_GroupSlots, &m_PassSlots[i], nullptr);
 }
 
 Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::size_t height, DeviceBuffer *image,
@@ -488,15 +473,16 @@ Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::si
 // stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in stageInYuv.
 void Engine::uploadPassInputs(const AnyFrame *in, int n) {
 	for (int i = 0; i < n; ++i) {
-		if (!m_BatchHost[i].in.host) continue;
+		const PassFrame &f = m_Pass[i];
+		if (!f.in.host) continue;
 		// (a staged frame: at source size, into the source-size slot; a group pass: each member's own size)
-		const std::size_t rowBytes = m_PassSize[i].inW * 4, rows = m_PassSize[i].inH;
+		const std::size_t rowBytes = f.size.inW * 4, rows = f.size.inH;
 		if (in[i].yuv) {
-			copyPlanes(in[i].planes, m_PassUp[i].planes->as<std::uint8_t>(), true, m_Stream);
+			copyPlanes(in[i].planes, f.up.planes->as<std::uint8_t>(), true, m_Stream);
 			continue;
 		}
 		const RowSpan host = rowSpan(in[i].bgrx.ptr, in[i].bgrx.stride, rows);
-		copyRows(m_PassUp[i].image->get(), rowBytes, host.lowest, host.pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream);
+		copyRows(f.up.image->get(), rowBytes, host.lowest, host.pitch, rowBytes, rows, hipMemcpyHostToDevice, m_Stream);
 	}
 }
 
@@ -509,7 +495,8 @@ void Engine::drainPassOutputs(const AnyFrame *out, int n) {
 	unsigned due = 0;
 	bool any = false;
 	for (int i = 0; i < n; ++i) {
-		if (!m_BatchHost[i].out.host) continue;
+		const PassFrame &f = m_Pass[i];
+		if (!f.out.host) continue;
 		++due;
 		auto arrived = [&] { return static_cast<int>(*word - m_PassSignalBase) >= static_cast<int>(due); };
 		for (unsigned spins = 1; !arrived(); ++spins) {
@@ -526,13 +513,13 @@ void Engine::drainPassOutputs(const AnyFrame *out, int n) {
 		}
 		any = true;
 		// (a staged frame: rows and planes at the output size; a group pass: each member's own)
-		const std::size_t rowBytes = m_PassSize[i].outW * 4, rows = m_PassSize[i].outH;
+		const std::size_t rowBytes = f.size.outW * 4, rows = f.size.outH;
 		if (out[i].yuv) {
-			copyPlanes(out[i].planes, m_PassDown[i].planes->as<std::uint8_t>(), false, *m_CopyStream);
+			copyPlanes(out[i].planes, f.down.planes->as<std::uint8_t>(), false, *m_CopyStream);
 			continue;
 		}
 		const RowSpan host = rowSpan(out[i].bgrx.ptr, out[i].bgrx.stride, rows);
-		copyRows(host.lowest, host.pitch, m_PassDown[i].image->get(), rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, *m_CopyStream);
+		copyRows(host.lowest, host.pitch, f.down.image->get(), rowBytes, rowBytes, rows, hipMemcpyDeviceToHost, *m_CopyStream);
 	}
 	if (any) JU_HIP(hipStreamSynchronize(*m_CopyStream));
 }
@@ -591,11 +578,11 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 	return captured;
 }
 
-// One look-ahead pass over frames [0, n): enqueue only.  On return the binding set is flipped ONCE (see above).
+// One look-ahead pass over frames [0, n): enqueue only.  On return the binding set is flipped ONCE (see above).  The frames
+// are counted by runPasses, once the pass has completed.
 void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	const int set = m_Idx;
-	const int stage = stagePass();
-	const std::vector<PassKey> key = bindBatch(in, out, n, set, stage);
+	const std::vector<PassKey> key = bindBatch(in, out, n, set, stageBits(false));
 	uploadPassInputs(in, n);  // (outside the chain lock: a pageable upload blocks its caller)
 	m_PassSignalBase = m_PassSignal.host() ? *m_PassSignal.host() : 0u;
 	const int scene = scenePass();
@@ -608,10 +595,6 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 		dyn->thresholdMilli = m_SceneThreshold;
 		dyn->slot = static_cast<unsigned>(m_SceneSteps % kSceneRing);
 		std::atomic_thread_fence(std::memory_order_seq_cst);
-	}
-	for (int i = 0; i < n; ++i) {
-		m_BatchHostFrames += m_BatchHost[i].host() ? 1 : 0;
-		m_BatchYuvFrames += m_BatchHost[i].yuv() ? 1 : 0;
 	}
 	{
 		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
@@ -637,11 +620,6 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 		chainEnd(chain, m_Resident);
 	}
 	m_Idx = set ^ 1;
-	m_BatchFrames += static_cast<std::uint64_t>(n);
-	if (stage) {  // (what the frames went through, whichever route they took: "source_stage_frames" counts them too)
-		m_BatchStagedFrames += static_cast<std::uint64_t>(n);
-		m_SourceFrames += static_cast<std::uint64_t>(n);
-	}
 	if (scene) {  // n detector steps, taken by the pass's one launch
 		m_SceneSeen += static_cast<std::uint64_t>(n);
 		m_SceneSteps += static_cast<std::uint64_t>(n);
@@ -713,21 +691,10 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 		if (code || g_PassRerun.load(std::memory_order_relaxed)) {
 			// nothing the pass wrote was one of its inputs -- neither the state (see above) nor a frame buffer (the pass
 			// splitter): the same frames again, one by one, on the per-block kernels
+			// (the frames count as frames, not as a pass's: submitFrame adds a staged one to "source_stage_frames")
 			m_Idx = set;
-			m_BatchFrames -= static_cast<std::uint64_t>(n);
-			if (m_PassStage) {  // (submitFrame counts the frames again)
-				m_BatchStagedFrames -= static_cast<std::uint64_t>(n);
-				m_SourceFrames -= static_cast<std::uint64_t>(n);
-			}
-			for (int k = 0; k < n; ++k) {
-				m_BatchHostFrames -= m_BatchHost[k].host() ? 1 : 0;
-				m_BatchYuvFrames -= m_BatchHost[k].yuv() ? 1 : 0;
-			}
 			if (code) fallbackToLayers(code);
-			struct Rerun {  // (the pass's detector has run: its n decisions stand, no frame meets it again)
-				bool &flag;
-				~Rerun() { flag = false; }
-			} rerun{m_SceneRerun};
+			AtExit rerun{[this] { m_SceneRerun = false; }};  // (the pass's detector has run: its n decisions stand, no frame meets it again)
 			for (int k = 0; k < n; ++k) {
 				if (scene) {
 					m_SceneRerun = true;
@@ -747,7 +714,17 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 				}
 			}
 		} else {
-			for (int k = 0; k < n; ++k) maybeRestoreResident();
+			// the pass has completed: its frames count as a pass's
+			m_BatchFrames += static_cast<std::uint64_t>(n);
+			if (m_PassStage) {  // (what the frames went through, whichever route they took: "source_stage_frames" counts them too)
+				m_BatchStagedFrames += static_cast<std::uint64_t>(n);
+				m_SourceFrames += static_cast<std::uint64_t>(n);
+			}
+			for (int k = 0; k < n; ++k) {
+				m_BatchHostFrames += m_Pass[k].host() ? 1 : 0;
+				m_BatchYuvFrames += m_Pass[k].yuv() ? 1 : 0;
+				maybeRestoreResident();
+			}
 		}
 		i += n;
 	}
@@ -757,7 +734,7 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 // Group passes (processGroup).  A server of N live streams has N frames at every tick, one per stream, and their flow
 // nets are as independent as a look-ahead pass's: the flow net reads LR frames and each stream's own history only.  So
 // the lead (members[0]) runs the flow net's launches ONCE over the n frames of a pass, on its batch tensors -- item i is
-// member i's frame with member i's history (flow_block_kernel's independent-items form: m_GroupPrev / m_GroupOut) --
+// member i's frame with member i's history (flow_block_kernel's independent-items form: PassFrame::groupPrev / groupOut) --
 // and then, member by member on the lead's stream, each member's own non-flow steps, bound to its frame, flow item i
 // and its state m_State[set_i] -> m_State[set_i ^ 1].  Per member that is the arithmetic of process(): the same kernels
 // add the same terms in the same order whatever the launch's size.  Like a look-ahead pass, the pass writes nothing it
@@ -765,8 +742,8 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 // off inputs), so a pass whose resident tower timed out runs again member by member.  The launches are eager: round 6
 // measured eager launches per frame equal to graph replay.
 //
-// Frames of any format (processGroupFrames).  A member's pair is bound as a look-ahead pass binds a frame's (bindBatch on
-// the lead: host planes into the lead's slots m_PassIn / m_PassYuvIn, uploaded up front); ONE decode launch in front of
+// Frames of any format (processGroupFrames).  A member's pair is bound as a look-ahead pass binds a frame's (bindFrame on
+// the lead: host planes into the lead's slots m_PassSlots, uploaded up front); ONE decode launch in front of
 // the flow net covers every non-BGRX input of the pass (the items form of processFrames), and each member's encode sits
 // behind that member's own steps on the lead's stream -- a deep format from THAT member's f16 state, the half its step
 // just wrote.  Members under a source size, an output size or a mask stay on the staged single-frame route unless they
@@ -777,7 +754,7 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 // member in ONE launch behind the decode launch -- item i against member i's own kept frame, from and into member i's
 // own SceneState and ring -- and scene_clear_items_kernel zeroes, in ONE more launch, m_State[set_i] and m_Packed[set_i]
 // of the members whose flag was raised: exactly what the per-frame scene_clear_kernel covers, in front of the flow net
-// that reads m_Packed[set_i] as m_GroupPrev[i].  One exception to "writes nothing it reads", as in a look-ahead pass: those
+// that reads m_Packed[set_i] as item i's groupPrev.  One exception to "writes nothing it reads", as in a look-ahead pass: those
 // two buffers may be zeroed -- which is what the re-run of the members, whose decisions stand (m_SceneRerun), wants to
 // find there too.
 //
@@ -915,19 +892,15 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 	int stage[kFlowBatchMax];
 	bool anyScaledIn = false;
 	for (int i = 0; i < n; ++i) {
-		stage[i] = m[i]->groupStage();
+		stage[i] = m[i]->stageBits(true);
 		anyScaledIn = anyScaledIn || (stage[i] & 1) != 0;
 	}
-	// L.m_BatchIO[i]: what member i's network reads and writes (a host frame through L.m_PassIn[i] / m_PassOut[i], a scaled
-	// side through member i's own model-size slot); L.m_PassEnds[i]: member i's rows at its own source / output size
+	// L.m_Pass[i].io: what member i's network reads and writes (a host frame through L.m_PassSlots[i], a scaled side through
+	// member i's own model-size slot); .ends: member i's rows at its own source / output size
 	L.bindGroup(m, in, out, n, stage);
-	struct Unbind {  // (the lead keeps no pointer to a member's slots beyond the pass)
-		Engine &lead;
-		int n;
-		~Unbind() {
-			for (int i = 0; i < n; ++i) lead.m_PassUp[i] = lead.m_PassDown[i] = PassCopy{};
-		}
-	} unbind{L, n};
+	AtExit unbind{[&L, n] {  // (the lead keeps no pointer to a member's slots beyond the pass)
+		for (int i = 0; i < n; ++i) L.m_Pass[i].up = L.m_Pass[i].down = PassCopy{};
+	}};
 	L.uploadPassInputs(in, n);  // (each at its member's own size; outside the chain lock: a pageable upload blocks its caller)
 	L.m_PassSignalBase = L.m_PassSignal.host() ? *L.m_PassSignal.host() : 0u;
 	// The detecting members (they ride because they asked to: setSceneGroup).  What their decisions read that varies from
@@ -975,12 +948,12 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		YuvDecodeSizedItems items{};
 		int decodes = 0;
 		for (int i = 0; i < n; ++i) {
-			const PassFrame &pf = L.m_BatchHost[i];
-			if (!pf.in.yuv) continue;
-			items.width[decodes] = static_cast<int>(L.m_PassSize[i].inW);
-			items.height[decodes] = static_cast<int>(L.m_PassSize[i].inH);
-			items.item[decodes++] = yuvDecodeItem(fmt(pf.in.format), pf.in.colorspace, pf.in.planes, const_cast<std::uint8_t *>(L.m_PassEnds[i].in),
-			    L.m_PassEnds[i].inStride);
+			const PassFrame &f = L.m_Pass[i];
+			if (!f.in.yuv) continue;
+			items.width[decodes] = static_cast<int>(f.size.inW);
+			items.height[decodes] = static_cast<int>(f.size.inH);
+			items.item[decodes++] = yuvDecodeItem(fmt(f.in.format), f.in.colorspace, f.in.planes, const_cast<std::uint8_t *>(f.ends.in),
+			    f.ends.inStride);
 		}
 		if (decodes && anyScaledIn) {
 			launchYuvToBgrxItemsSized(items, decodes, L.m_Stream);
@@ -997,8 +970,8 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 			int scaled = 0;
 			for (int i = 0; i < n; ++i) {
 				if (!(stage[i] & 1)) continue;
-				scale.member[scaled++] = m[i]->m_SrcScale.member(L.m_PassEnds[i].in, L.m_PassEnds[i].inStride,
-				    const_cast<std::uint8_t *>(L.m_BatchIO[i].in), L.m_BatchIO[i].inStride);
+				const PassFrame &f = L.m_Pass[i];
+				scale.member[scaled++] = m[i]->m_SrcScale.member(f.ends.in, f.ends.inStride, const_cast<std::uint8_t *>(f.io.in), f.io.inStride);
 			}
 			launchScaleBgrxMembers(scale, scaled, static_cast<int>(fs.inputWidth), static_cast<int>(fs.inputHeight), L.m_Stream);
 		}
@@ -1006,7 +979,7 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		// upload slot, the slot the decode launch fills), so ONE launch takes the decision of every detecting member -- each
 		// against its OWN kept frame, state and ring (the streams are independent: no cut-aware history) -- and ONE more
 		// clears, for the members whose flag it raised, what their step is about to read as its recurrent inputs:
-		// m_State[set_i] and m_Packed[set_i], the half the first flow block reads as m_GroupPrev[i].  After it a cut
+		// m_State[set_i] and m_Packed[set_i], the half the first flow block reads as its groupPrev.  After it a cut
 		// member's whole history is zero, which is what reset() leaves.
 		if (anyDetects) {
 			SceneGroupLaunch q;
@@ -1018,8 +991,8 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 				if (!detects[i]) continue;
 				Engine &e = *m[i];
 				SceneGroupItem &it = q.item[i];
-				it.frame = L.m_BatchIO[i].in;
-				it.stride = L.m_BatchIO[i].inStride;
+				it.frame = L.m_Pass[i].io.in;
+				it.stride = L.m_Pass[i].io.inStride;
 				it.prev = e.m_ScenePrev.as<std::uint32_t>();
 				it.state = e.m_SceneDev.as<SceneState>();
 				it.ring = reinterpret_cast<SceneRecord *>(e.m_SceneRing.device());
@@ -1041,61 +1014,25 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		}
 		// 2. the flow net once over all items
 		for (int i = 0; i < n; ++i) {
-			L.m_GroupPrev[i] = m[i]->m_Packed[sets[i]].get();
-			L.m_GroupOut[i] = m[i]->m_Packed[sets[i] ^ 1].get();
+			L.m_Pass[i].groupPrev = m[i]->m_Packed[sets[i]].get();
+			L.m_Pass[i].groupOut = m[i]->m_Packed[sets[i] ^ 1].get();
 		}
 		for (const Step &st : L.m_BatchFlow.at({n, kGroupSet})) st.run(L.m_Stream);
 		// 3. member by member, its own steps on the lead's stream, bound to its frame and its flow item
 		for (int i = 0; i < n; ++i) {
 			Engine &e = *m[i];
-			const FrameIO keepIO = e.m_IO;
-			const void *keepFlow = e.m_FlowCur;
-			struct Restore {
-				Engine &e;
-				FrameIO io;
-				const void *flow;
-				~Restore() {
-					e.m_IO = io;
-					e.m_FlowCur = flow;
-				}
-			} restore{e, keepIO, keepFlow};
-			e.m_IO = L.m_BatchIO[i];
+			AtExit restore{[&e, keepIO = e.m_IO, keepFlow = e.m_FlowCur] {
+				e.m_IO = keepIO;
+				e.m_FlowCur = keepFlow;
+			}};
+			e.m_IO = L.m_Pass[i].io;
 			if (recurrent) e.m_FlowCur = flowBase + i * flowItem;
 			for (const Step &st : e.m_Program[sets[i]]) {
 				if (st.tag != "flow" && st.tag != "pack") st.run(L.m_Stream);
 			}
-			// behind member i's own steps, on the lead's stream, what submitFrame strings behind the program -- the existing
-			// single-frame launches with member i's own mask and scaler.  The mask, in place over the model-size frame member
-			// i's tail wrote (a slot the pass alone writes, or the caller's output), its source sampled from member i's own
-			// source rows -- or the model-size input when it has no source size
-			const PassSide &po = L.m_BatchHost[i].out;
-			const PassExtent &sz = L.m_PassSize[i];
-			const FrameIO &ends = L.m_PassEnds[i];
-			void *stateOut = e.m_State[recurrent ? sets[i] ^ 1 : 0].get();
-			if (stage[i] & 2) {
-				launchMaskBlend(L.m_BatchIO[i].out, L.m_BatchIO[i].outStride, static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight),
-				    ends.in, ends.inStride, static_cast<int>(sz.inW), static_cast<int>(sz.inH),
-				    e.m_Mask.as<std::uint8_t>() + (e.m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(e.m_MaskH - 1) * -e.m_MaskStride : 0),
-				    e.m_MaskStride, static_cast<int>(e.m_MaskW), static_cast<int>(e.m_MaskH), L.m_Stream);
-			}
-			const std::uint16_t *frame16 = nullptr;
-			if (stage[i] & 4) {  // stageOutScaled's rules: the 8-bit frame, or for a deep format from the state member i's own state
-				if (po.yuv && e.deepFromState(po.format)) {
-					auto *scaled16 = e.m_GroupSlots.out16.as<std::uint16_t>();
-					e.m_OutScale.scaleState(stateOut, scaled16, L.m_Stream);
-					frame16 = scaled16;
-				} else {
-					e.m_OutScale.scaleBgrx(L.m_BatchIO[i].out, L.m_BatchIO[i].outStride, ends.out, ends.outStride, L.m_Stream);
-				}
-			}
-			// a non-BGRX output: member i's BGRX frame at its own output size (the lead's slot, or member i's scaled slot) into
-			// the caller's device planes / the staging slot.  A deep format is encoded from the f16 state THIS MEMBER's step
-			// just wrote -- its own m_State[set_i ^ 1] (a flow-free member: its one scratch state), never the lead's -- or from
-			// the blended or scaled 8-bit frame while member i has a mask or "hbd_from_state" 0 (deepFromState)
-			if (po.yuv) {
-				e.encodeYuv(po.format, po.colorspace, po.planes, sz.outW, sz.outH, ends.out, ends.outStride, stateOut, frame16, L.m_Stream);
-			}
-			if (L.m_BatchHost[i].out.host) launchSignalHost(L.m_PassSignal.device(), L.m_Stream);
+			// behind member i's own steps, on the lead's stream, with member i's own mask, scaler and 16-bit slot; the state
+			// its step just wrote: its own m_State[set_i ^ 1] (a flow-free member: its one scratch state)
+			L.passTail(e, L.m_Pass[i], stage[i], e.m_State[recurrent ? sets[i] ^ 1 : 0].get(), e.m_GroupSlots.out16);
 		}
 		L.chainEnd(chain, resident);
 	}
@@ -1125,10 +1062,7 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		for (int i = 0; i < n; ++i) {
 			// (the pass's detector has run: the member's decision stands, its kept frame is this frame already and, after a
 			// cut, its cleared inputs are still in place -- the pass wrote the other halves only; no step meets it again)
-			struct Rerun {
-				bool &flag;
-				~Rerun() { flag = false; }
-			} rerun{m[i]->m_SceneRerun};
+			AtExit rerun{[e = m[i]] { e->m_SceneRerun = false; }};
 			m[i]->m_SceneRerun = detects[i];
 			m[i]->process(in[i], out[i]);
 		}
@@ -1137,7 +1071,7 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 	for (int i = 0; i < n; ++i) {
 		m[i]->m_Idx = sets[i] ^ 1;
 		++m[i]->m_GroupFrames;
-		m[i]->m_GroupYuvFrames += L.m_BatchHost[i].yuv() ? 1 : 0;
+		m[i]->m_GroupYuvFrames += L.m_Pass[i].yuv() ? 1 : 0;
 		if (stage[i]) {  // (what the frame went through, whichever route it took: "source_stage_frames" counts it too)
 			++m[i]->m_GroupStagedFrames;
 			++m[i]->m_SourceFrames;

@@ -142,8 +142,8 @@ inline SlotRows slotRows(std::size_t width, std::size_t height, bool topDown) {
 	return topDown ? SlotRows{0, static_cast<std::ptrdiff_t>(row)} : SlotRows{(height - 1) * row, -static_cast<std::ptrdiff_t>(row)};
 }
 
-// Bytes of the per-frame slots of a staged look-ahead pass (Engine::bindBatch; docs/output_stage.md "Passes"): the BGRX
-// frame at source size, the model-size input and output, the 8-bit and the 16-bit frame at output size.
+// Bytes of the slots of one frame of a staged pass (Engine::bindFrame; docs/output_stage.md "Passes"): the BGRX frame at
+// source size, the model-size input and output, the 8-bit and the 16-bit frame at output size.
 struct StageSlotBytes {
 	std::size_t source, input, modelOutput, out8, out16;
 };
@@ -152,18 +152,19 @@ inline StageSlotBytes stageSlotBytes(std::size_t srcW, std::size_t srcH, std::si
 	return {srcW * srcH * 4, inW * inH * 4, modelW * modelH * 4, outW * outH * 4, outW * outH * 8};
 }
 
-// Which of those slots one member of a staged group pass needs (Engine::bindGroup; docs/source_stage.md "Group passes"):
-// stage = bit 0 a source size, bit 1 a mask, bit 2 an output size; stagedIn / stagedOut: the side is a host image or not
-// BGRX (a device BGRX image is read / written where it is); deepOut: a deep format encoded from the f16 state.  A mask
-// alone needs none: the blend is in place over the frame the plain pass binds.
-struct GroupSlotNeeds {
+// Which of those slots one frame of a staged look-ahead pass, or one member of a staged group pass, needs
+// (Engine::bindFrame; docs/source_stage.md "Group passes"): stage = bit 0 a source size, bit 1 a mask, bit 2 an output
+// size; stagedIn / stagedOut: the side is a host image or not BGRX (a device BGRX image is read / written where it is);
+// deepOut: a deep format encoded from the f16 state.  A mask alone needs none: the blend is in place over the frame the
+// plain pass binds.
+struct StageSlotNeeds {
 	bool source, input, modelOutput, out8, out16;
 };
-inline GroupSlotNeeds groupSlotNeeds(int stage, bool stagedIn, bool stagedOut, bool deepOut) {
+inline StageSlotNeeds stageSlotNeeds(int stage, bool stagedIn, bool stagedOut, bool deepOut) {
 	const bool scaledIn = (stage & 1) != 0, scaledOut = (stage & 4) != 0;
 	return {scaledIn && stagedIn, scaledIn, scaledOut, scaledOut && stagedOut, scaledOut && deepOut};
 }
-inline std::size_t groupSlotTotal(const StageSlotBytes &b, const GroupSlotNeeds &n) {
+inline std::size_t stageSlotTotal(const StageSlotBytes &b, const StageSlotNeeds &n) {
 	return (n.source ? b.source : 0) + (n.input ? b.input : 0) + (n.modelOutput ? b.modelOutput : 0) + (n.out8 ? b.out8 : 0) +
 	       (n.out16 ? b.out16 : 0);
 }

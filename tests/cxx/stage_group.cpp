@@ -106,28 +106,28 @@ void members() {
 void slots() {
 	// 1280x720 in, 480x270 -> 1920x1080 model, 3840x2160 out: what the documents quote, per member
 	const ju::StageSlotBytes b = ju::stageSlotBytes(1280, 720, 480, 270, 1920, 1080, 3840, 2160);
-	using N = ju::GroupSlotNeeds;
+	using N = ju::StageSlotNeeds;
 	auto same = [](const N &x, const N &y) {
 		return x.source == y.source && x.input == y.input && x.modelOutput == y.modelOutput && x.out8 == y.out8 && x.out16 == y.out16;
 	};
 	// a mask alone: no slot; a plain member: none
-	CHECK(same(ju::groupSlotNeeds(0, true, true, true), N{false, false, false, false, false}));
-	CHECK(same(ju::groupSlotNeeds(2, true, true, false), N{false, false, false, false, false}));
+	CHECK(same(ju::stageSlotNeeds(0, true, true, true), N{false, false, false, false, false}));
+	CHECK(same(ju::stageSlotNeeds(2, true, true, false), N{false, false, false, false, false}));
 	// a source size: the model-size input always, the source-size frame for a host or non-BGRX source only
-	CHECK(same(ju::groupSlotNeeds(1, false, true, true), N{false, true, false, false, false}));
-	CHECK(same(ju::groupSlotNeeds(3, true, false, false), N{true, true, false, false, false}));
+	CHECK(same(ju::stageSlotNeeds(1, false, true, true), N{false, true, false, false, false}));
+	CHECK(same(ju::stageSlotNeeds(3, true, false, false), N{true, true, false, false, false}));
 	// an output size: the model-size output always, the 8-bit frame for a host or non-BGRX output, the 16-bit frame for a deep one
-	CHECK(same(ju::groupSlotNeeds(4, true, false, false), N{false, false, true, false, false}));
-	CHECK(same(ju::groupSlotNeeds(6, false, true, false), N{false, false, true, true, false}));
-	CHECK(same(ju::groupSlotNeeds(7, true, true, true), N{true, true, true, true, true}));
-	CHECK(ju::groupSlotTotal(b, ju::groupSlotNeeds(0, true, true, true)) == 0);
-	CHECK(ju::groupSlotTotal(b, ju::groupSlotNeeds(1, false, false, false)) == 518400);                 // device BGRX 720p in
-	CHECK(ju::groupSlotTotal(b, ju::groupSlotNeeds(1, true, false, false)) == 518400 + 3686400);        // NV12 720p in
-	CHECK(ju::groupSlotTotal(b, ju::groupSlotNeeds(4, false, false, false)) == 8294400);                // device BGRX 2160p out
-	CHECK(ju::groupSlotTotal(b, ju::groupSlotNeeds(5, true, true, false)) == 518400 + 3686400 + 8294400 + 33177600);
-	CHECK(ju::groupSlotTotal(b, ju::groupSlotNeeds(7, true, true, true)) == 518400 + 3686400 + 8294400 + 33177600 + 66355200);
+	CHECK(same(ju::stageSlotNeeds(4, true, false, false), N{false, false, true, false, false}));
+	CHECK(same(ju::stageSlotNeeds(6, false, true, false), N{false, false, true, true, false}));
+	CHECK(same(ju::stageSlotNeeds(7, true, true, true), N{true, true, true, true, true}));
+	CHECK(ju::stageSlotTotal(b, ju::stageSlotNeeds(0, true, true, true)) == 0);
+	CHECK(ju::stageSlotTotal(b, ju::stageSlotNeeds(1, false, false, false)) == 518400);                 // device BGRX 720p in
+	CHECK(ju::stageSlotTotal(b, ju::stageSlotNeeds(1, true, false, false)) == 518400 + 3686400);        // NV12 720p in
+	CHECK(ju::stageSlotTotal(b, ju::stageSlotNeeds(4, false, false, false)) == 8294400);                // device BGRX 2160p out
+	CHECK(ju::stageSlotTotal(b, ju::stageSlotNeeds(5, true, true, false)) == 518400 + 3686400 + 8294400 + 33177600);
+	CHECK(ju::stageSlotTotal(b, ju::stageSlotNeeds(7, true, true, true)) == 518400 + 3686400 + 8294400 + 33177600 + 66355200);
 	const ju::StageSlotBytes big = ju::stageSlotBytes(8192, 8192, 8192, 8192, 16384, 16384, 16384, 16384);
-	CHECK(ju::groupSlotTotal(big, ju::groupSlotNeeds(7, true, true, true)) == 268435456ull * 2 + 1073741824ull * 2 + 2147483648ull);
+	CHECK(ju::stageSlotTotal(big, ju::stageSlotNeeds(7, true, true, true)) == 268435456ull * 2 + 1073741824ull * 2 + 2147483648ull);
 }
 
 }  // namespace

@@ -514,5 +514,13 @@ def test_a_staged_pass_that_is_run_again_gives_the_same_bytes_and_counts_as_fram
         assert a.stat("lookahead_frames") == 0 and a.stat("lookahead_staged_frames") == 0 and a.stat("fallbacks") == 0
         assert a.stat("lookahead_host_frames") == 0 and a.stat("lookahead_yuv_frames") == 0
         assert a.stat("source_stage_frames") == 11
+        # ju_time_steps "...@pass" behind a staged pass: a plain pass of its own on the staging buffers -- it launches on nothing
+        # the staged pass bound (its stage bits, the callers' rows at their own sizes) -- and ends in ju_reset; the next staged
+        # pass is again the frames sent one by one
+        assert a.time_steps("flow@pass", 1)[1] > 0
+        run_calls(a, ins, outs, want, (11,))
+        assert same_as(a, snap)
+        assert a.stat("lookahead_frames") == 11 and a.stat("lookahead_staged_frames") == 11 and a.stat("fallbacks") == 0
+        assert a.stat("source_stage_frames") == 22
         for x in ins:
             x.untouched()
