@@ -164,8 +164,8 @@ typedef struct ju_image {
  * are sized once for the largest format: nothing is regrown behind a captured graph.
  *
  * Limits: 8- and 10-bit YUV (no 12- or 16-bit: P016 and friends need an encode to 16-bit codes that is not defined yet;
- * no NV16 / NV21, no other chroma siting); RGB without 12-bit, without dithering and without alpha (X, and the two top
- * bits of an x2rgb10 / x2bgr10 word, are ignored and written 0); float inputs are quantised to 8 bits like every input,
+ * no NV16 / NV21, no other chroma siting); RGB without 12-bit and without dithering; alpha (X, and the two top bits of an
+ * x2rgb10 / x2bgr10 word) is ignored and written 0 unless ju_set_alpha, below, says otherwise; float inputs are quantised to 8 bits like every input,
  * they do not reach the network unquantised; no YUV or RGB graphics resources (GL textures stay BGRX); look-ahead passes
  * take these frames through ju_process_frames (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX) and
  * group passes through ju_process_group_frames (ju_process_group takes ju_image); the C++ plugin surface
@@ -451,6 +451,40 @@ JU_API int ju_set_source_mask(ju_runtime *runtime, const ju_image *mask);
  * ju_set_stage_group the "no group pass" for ju_process_group and ju_process_group_frames. */
 JU_API int ju_set_output_size(ju_runtime *runtime, size_t width, size_t height, int filter);
 JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height);
+
+/* ---- the alpha channel: opaque, or scaled from the source (docs/alpha.md) -----------------------------------------------
+ * Every four-sample format has an alpha slot -- byte 3 of JU_FMT_BGRX and JU_FMT_RGBX, word 3 of JU_FMT_BGRX64, the two
+ * top bits of JU_FMT_X2RGB10 and JU_FMT_X2BGR10 -- which the reference ignores on input and writes 0 on output.
+ * ju_set_alpha says what output frames hold there.  Opt-in and per runtime; ju_reset keeps the setting.
+ *   JU_ALPHA_ZERO (the default): 0 -- every route byte for byte, launch for launch and stat for stat as without the call.
+ *   JU_ALPHA_OPAQUE: the format's top code, 255 / 65535 / 3, in every output frame that has a slot.
+ *   JU_ALPHA_SOURCE: the input frame's alpha, scaled on the GPU by the project's exact integer scaler from the input
+ *     frame's size (the source size if one is set, else the model's input) STRAIGHT to the output frame's size (the
+ *     output size if one is set, else the model's output), never through the model's size.  The 16-bit plane A of the
+ *     input: 257 a of a byte, a BGRX64 word itself, 21845 a of a two-bit code, 65535 for a format without a slot (every
+ *     YUV format, BGR24 / RGB24, the planar RGB formats, BGR96F).  A' = (sum qy qx A + 2^23) >> 24 with the tables of
+ *     `filter` (clamped to 0 .. 65535 with a cubic filter).  The slot: (A' + 128) / 257 of a byte, A' of a word,
+ *     (A' + 10922) / 21845 of two bits.  Equal sizes under the triangle or Catmull-Rom give the input's alpha back code
+ *     for code.  tests/alpha_reference.py is the definition, in integers.
+ * filter: JU_SCALE_TRIANGLE, JU_SCALE_CATMULL_ROM or JU_SCALE_MITCHELL (anything else: refused); ignored, but still
+ * checked, in the first two modes.  Alpha is independent of everything else: colour samples, state, frame history,
+ * detector records and deep outputs are those of the same runtime in mode 0; the mask does not touch alpha.  An output
+ * format without a slot gets nothing and nothing is launched for it.
+ * Limits (JU_ERR_INVALID_ARGUMENT, the setting as it was): a mode or a filter out of range; under JU_ALPHA_SOURCE each
+ * axis of both frame sizes 2 .. 16384, the input at most 16 times the output (8 with a cubic filter) and the output at
+ * most 16 times the input.  A source size and an output size can together leave these limits (16:1 in, 1:16 out):
+ * whichever of ju_set_alpha, ju_set_source_size and ju_set_output_size would do so is refused, the message names alpha
+ * and both sizes, and all three settings stay as they were.  Under JU_ALPHA_SOURCE a JU_LOC_DEVICE output that overlaps
+ * the JU_LOC_DEVICE input is refused before anything is launched (the alpha is read behind the frame's colour).
+ * Routing: while the mode is not JU_ALPHA_ZERO frames of every entry point run one by one through the staging buffers, in
+ * stream order, with one more launch behind the frame's colour and in front of any copy to the host; no direct device
+ * path, no look-ahead or group pass whatever ju_set_stage_lookahead, ju_set_stage_group and the scene settings say (in a
+ * group call such a runtime runs on its own behind the pass), ju_prepare_* capture nothing.  JU_ALPHA_ZERO restores all of
+ * them.  The setter waits for the stream.  ju_get_stat: "alpha_mode", "alpha_filter", "alpha_frames" (frames whose alpha
+ * slot these launches wrote).  Not covered: alpha inside passes, on a ju_tiled, premultiplied alpha, the C++ surface. */
+enum { JU_ALPHA_ZERO = 0, JU_ALPHA_OPAQUE = 1, JU_ALPHA_SOURCE = 2 };
+JU_API int ju_set_alpha(ju_runtime *runtime, int mode, int filter);
+JU_API int ju_get_alpha(const ju_runtime *runtime, int *mode, int *filter);
 
 /* ---- scaled and masked frames inside look-ahead passes (docs/source_stage.md, docs/output_stage.md: "Passes") ----------
  * ju_set_stage_lookahead(rt, 1): while a source size, a mask or an output size is set, ju_process_batch and
@@ -844,7 +878,8 @@ JU_API int ju_get_dtype(const ju_runtime *runtime);
  * "source_scaled" / "source_mask" (1 while ju_set_source_size / ju_set_source_mask is in effect), "source_stage_frames"
  * (frames that went through the source stage or the output stage), "output_scaled" (1 while ju_set_output_size is in
  * effect), "source_filter" / "output_filter" (the JU_SCALE_* value ju_set_source_size / ju_set_output_size has in effect;
- * 0 while off),
+ * 0 while off), "alpha_mode" / "alpha_filter" (what ju_set_alpha set) and "alpha_frames" (frames whose alpha slot the
+ * alpha launches wrote),
  * "hbd_from_state" (1: this runtime encodes JU_FMT_P010 / JU_FMT_I010 outputs from its f16 state; 0: from the 8-bit
  * frame -- normalize_brightness and output_flow models),
  * "recurrent" (1: the model has a flow net and a recurrent state; 0: a flow-free single-image model,

@@ -206,6 +206,21 @@ JU_API int ju_debug_scene_clear_items(int count, const void *const *flags, void 
 JU_API int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height,
     const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height, int *start, int *count, int16_t *taps);
 
+/* The alpha kernels alone (alpha_kernels.hip; docs/alpha.md; tests/alpha_reference.py): ONE synchronous launch each on
+ * caller-supplied device buffers, on the current device.  A kind says where the slot lies in a side's rows: 0 byte 3 of
+ * four-byte pixels (any byte alignment), 1 word 3 of eight-byte pixels (address and stride multiples of 2), 2 bits 30-31
+ * of 32-bit words (multiples of 4); a source may also be 3, none: the plane is 65535 everywhere and `src` is not read.
+ * Strides are bytes of any sign, sizes 1 .. 32768.  ju_debug_alpha_scale: the source's alpha of src_width x src_height
+ * scaled by `filter` (a JU_SCALE_* value, held to its ratio limits) into the slots of dst_width x dst_height pixels; no
+ * other bit of the destination changes.  ju_debug_alpha_fill: the top code into every slot.  JU_ERR_INVALID_ARGUMENT: an
+ * unknown kind or filter, a NULL side, |stride| smaller than a row, a misaligned side, a size out of range.
+ * ju_debug_alpha_problem: no device -- the limits of ju_set_alpha for a runtime whose input frames are in_width x
+ * in_height and whose output frames are out_width x out_height, with its message (JU_ERR_INVALID_ARGUMENT) or JU_OK. */
+JU_API int ju_debug_alpha_scale(int source_kind, int sink_kind, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width,
+    size_t dst_height, const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height);
+JU_API int ju_debug_alpha_fill(int sink_kind, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height);
+JU_API int ju_debug_alpha_problem(int mode, int filter, size_t in_width, size_t in_height, size_t out_width, size_t out_height);
+
 /* The sources of a look-ahead pass scaled in one launch (scale_bgrx_items_kernel; docs/source_stage.md "Passes"): ONE
  * synchronous launch over `count` (1 .. 8) items on caller-supplied device buffers, on the current device.  Item i reads
  * BGRX rows of src_width x src_height at src[i] with the signed stride src_strides[i] and writes dst_width x dst_height

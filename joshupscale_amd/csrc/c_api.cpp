@@ -341,6 +341,14 @@ int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *height)
 	return guarded([&] { engineOf(const_cast<ju_runtime *>(runtime)).outputSize(width, height); });
 }
 
+int ju_set_alpha(ju_runtime *runtime, int mode, int filter) {
+	return guarded([&] { engineOf(runtime).setAlpha(mode, filter); });
+}
+
+int ju_get_alpha(const ju_runtime *runtime, int *mode, int *filter) {
+	return guarded([&] { engineOf(const_cast<ju_runtime *>(runtime)).alpha(mode, filter); });
+}
+
 int ju_set_scene_detect(ju_runtime *runtime, int mode, uint32_t threshold_milli) {
 	return guarded([&] { engineOf(runtime).setSceneDetect(mode, threshold_milli); });
 }
@@ -1172,6 +1180,41 @@ int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, size_t d
 			scale.scaleState(src, static_cast<std::uint16_t *>(dst), nullptr);
 		}
 		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_alpha_scale(int source_kind, int sink_kind, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width,
+    size_t dst_height, const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height) {
+	return guarded([&] {
+		constexpr size_t kMost = 1u << 15;
+		if (dst_width < 1 || dst_height < 1 || src_width < 1 || src_height < 1 || dst_width > kMost || dst_height > kMost ||
+		    src_width > kMost || src_height > kMost) {
+			throw std::invalid_argument("ju_debug_alpha_scale: a size outside 1 .. 32768");
+		}
+		ju::Scaler scale;
+		scale.build(src_width, src_height, dst_width, dst_height, filter);
+		ju::launchAlphaScale(ju::AlphaRows{source_kind, const_cast<void *>(src), src_stride}, static_cast<int>(src_width),
+		    static_cast<int>(src_height), ju::AlphaRows{sink_kind, dst, dst_stride}, static_cast<int>(dst_width),
+		    static_cast<int>(dst_height), scale.xAxis(), scale.yAxis(), scale.span(), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_alpha_fill(int sink_kind, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height) {
+	return guarded([&] {
+		constexpr size_t kMost = 1u << 15;
+		if (dst_width < 1 || dst_height < 1 || dst_width > kMost || dst_height > kMost) {
+			throw std::invalid_argument("ju_debug_alpha_fill: a size outside 1 .. 32768");
+		}
+		ju::launchAlphaFill(ju::AlphaRows{sink_kind, dst, dst_stride}, static_cast<int>(dst_width), static_cast<int>(dst_height), nullptr);
+		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_alpha_problem(int mode, int filter, size_t in_width, size_t in_height, size_t out_width, size_t out_height) {
+	return guarded([&] {
+		const std::string problem = ju::alphaProblem(mode, filter, in_width, in_height, out_width, out_height);
+		if (!problem.empty()) throw std::invalid_argument("ju_set_alpha: " + problem);
 	});
 }
 

@@ -1419,7 +1419,7 @@ void Engine::captureDirect(DirectEntry *e, int idx) {
 int Engine::prepareFrames(const Frame &in, const Frame &out) {
 	DeviceGuard g(m_Device);
 	const FrameSize fs = frameSize();
-	if (sourceStage()) {  // every frame goes through the staging buffers, whose graphs exist
+	if (sourceStage() || m_AlphaMode != 0) {  // every frame goes through the staging buffers, whose graphs exist
 		checkFrame(anyOf(in), true);
 		checkFrame(anyOf(out), false);
 		return 0;
@@ -1586,6 +1586,7 @@ std::atomic<int> g_StepRerun{0};
 void setStepRerun(int on) { g_StepRerun = on; }
 
 void Engine::runSynchronous(const AnyFrame &in, const AnyFrame &out) {
+	const std::uint64_t alphaFrames = m_AlphaFrames;
 	submitAny(in, out);
 	m_Stream.synchronizeSpin(m_SpinUs);
 	const unsigned code = takeResidentError();
@@ -1596,6 +1597,7 @@ void Engine::runSynchronous(const AnyFrame &in, const AnyFrame &out) {
 		// fallback or the re-run throws, the failed frame must not count as a step either.)
 		m_Idx ^= 1;
 		if (sourceStage()) --m_SourceFrames;  // (submitFrame counts the frame again)
+		m_AlphaFrames = alphaFrames;
 		if (code) fallbackToLayers(code);  // (else the debug switch: the frame was sound)
 		// the scene detector ran with the first submission: its decision stands, the kept frame is this frame already
 		// and, after a cut, the cleared inputs are still in place (the step wrote the other half only)
@@ -1861,6 +1863,9 @@ double Engine::stat(const std::string &key) const {
 	if (key == "source_filter") return static_cast<double>(m_SrcScale.filter());  // (0 while off: the setters clear it)
 	if (key == "output_filter") return static_cast<double>(m_OutScale.filter());
 	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
+	if (key == "alpha_mode") return static_cast<double>(m_AlphaMode);
+	if (key == "alpha_filter") return static_cast<double>(m_AlphaFilter);
+	if (key == "alpha_frames") return static_cast<double>(m_AlphaFrames);  // frames whose alpha slot the alpha kernels wrote
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
 	if (key == "group_yuv_frames") return static_cast<double>(m_GroupYuvFrames);  // ... of them with a non-BGRX side

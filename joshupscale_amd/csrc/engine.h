@@ -130,6 +130,14 @@ public:
 	// look-ahead passes carry it; setStageGroup: the group passes).  reset() keeps it.
 	void setOutputSize(std::size_t width, std::size_t height, int filter);
 	void outputSize(std::size_t *width, std::size_t *height) const;
+	// The alpha channel (docs/alpha.md; engine_frames.cpp, "Alpha").  setAlpha: mode JU_ALPHA_ZERO (the slot stays 0: no
+	// launch, every route as without the setting), JU_ALPHA_OPAQUE (the format's top code) or JU_ALPHA_SOURCE (the input
+	// frame's alpha scaled by `filter`, a JU_SCALE_* value, from the input frame's size straight to the output frame's
+	// size); the filter is checked in every mode.  While the mode is not 0 every frame of every entry point runs one by
+	// one through submitFrame, whatever setStageLookahead / setStageGroup say, and one launch follows the frame's colour.
+	// Waits for the stream; reset() keeps it.
+	void setAlpha(int mode, int filter);
+	void alpha(int *mode, int *filter) const;
 	bool sourceStage() const { return m_SrcScale.set() || m_MaskW != 0 || m_OutScale.set(); }
 	// The scene detector (docs/scene_detect.md; "Scene detector" below).  setSceneDetect: mode 0 off / 1 report / 2 reset
 	// (JU_SCENE_*), thresholdMilli 1 .. 255000 while the mode is not off; waits for the stream; a call that changes the
@@ -280,6 +288,23 @@ private:
 	Scaler m_OutScale;
 	DeviceBuffer m_OutScaled8, m_OutScaled16, m_OutYuvStage, m_OutRawStage;
 	void stageOutScaled(const AnyFrame &out);
+	// Alpha: the mode and the filter set; the scaler from the input frame's size (the source size, else the model's
+	// input) to the output frame's size (the output size, else the model's output) while the mode is JU_ALPHA_SOURCE,
+	// rebuilt by setAlpha, setSourceSize and setOutputSize; where the frame in flight holds its alpha on the device
+	// (submitFrame); frames whose slot the alpha kernels wrote ("alpha_frames").
+	int m_AlphaMode = 0, m_AlphaFilter = 0;
+	Scaler m_AlphaScale;
+	AlphaRows m_AlphaSrc;
+	std::uint64_t m_AlphaFrames = 0;
+	// the alpha scaler the three setters would need for these frame sizes: an empty one unless `mode` is JU_ALPHA_SOURCE;
+	// std::invalid_argument "<who>: <alphaProblem>" when the sizes are beyond it -- before the setter changes anything
+	Scaler alphaScalerFor(const char *who, int mode, int filter, std::size_t inW, std::size_t inH, std::size_t outW, std::size_t outH) const;
+	void frameSizes(std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const;
+	// where the input frame's alpha lies once submitFrame has staged the frame; bgrx: the BGRX rows it staged
+	AlphaRows alphaSource(const AnyFrame &in, const SourceView &bgrx);
+	// the one alpha launch of a frame, behind its colour and in front of any copy to the host: nothing in mode 0 or for a
+	// format without a slot
+	void alphaInto(PixelFormat format, void *rows, std::ptrdiff_t stride);
 	// Scene detector: two eager launches on m_Stream in front of runProgram(), outside the chain lock and never captured
 	// (sceneStep: submit and submitFrame, once m_IO.in holds the frame the program will read).  m_ScenePrev: the frame
 	// compared against; m_SceneDev: the SceneState; m_SceneRing: kSceneRing records + the totals, host-mapped.
@@ -321,8 +346,10 @@ private:
 	void checkFrame(const AnyFrame &f, bool input, const char *who = "processFrame", bool declaredSize = false) const;
 	// THE pair decision (process, enqueue, the frames of runPasses): false = a BGRX pair while no source or output stage
 	// is set -- submit(), unchecked; true = checkPair, then submitFrame()
-	bool staged(const AnyFrame &in, const AnyFrame &out) const { return in.yuv || out.yuv || sourceStage(); }
+	bool staged(const AnyFrame &in, const AnyFrame &out) const { return in.yuv || out.yuv || sourceStage() || m_AlphaMode != 0; }
 	void checkPair(const AnyFrame &in, const AnyFrame &out) const;
+	// JU_ALPHA_SOURCE: a device output over the device input is refused (checkPair, processFrames)
+	void checkAlphaOverlap(const AnyFrame &in, const AnyFrame &out) const;
 	// one frame's launches by that decision, enqueue only
 	void submitAny(const AnyFrame &in, const AnyFrame &out);
 	// one decode launch: the planes of `in` (host planes through `stage` first) -> dense BGRX rows of the frame's own size

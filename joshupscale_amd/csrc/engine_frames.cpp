@@ -182,6 +182,16 @@ void Engine::checkPair(const AnyFrame &in, const AnyFrame &out) const {
 	if (!staged(in, out)) return;  // (a pair that takes submit() is refused where it is staged, as ju_process always did)
 	checkFrame(in, true);
 	checkFrame(out, false);
+	checkAlphaOverlap(in, out);
+}
+
+// alpha from the source is read behind the frame's colour: an output over the input would have rewritten it
+void Engine::checkAlphaOverlap(const AnyFrame &in, const AnyFrame &out) const {
+	if (m_AlphaMode == kAlphaSource && locationOf(in) == Location::Device && locationOf(out) == Location::Device &&
+	    overlap(extentOf(in), extentOf(out))) {
+		throw std::invalid_argument("processFrame: under JU_ALPHA_SOURCE a device output must not overlap the device input (the "
+		                            "input's alpha is read after the output's colour is written)");
+	}
 }
 
 void Engine::stageInYuv(const YuvFrame &in, std::uint8_t *stage, std::uint8_t *bgrx) {
@@ -220,6 +230,7 @@ void Engine::stageOutYuv(const YuvFrame &out, const std::uint8_t *bgrx, const vo
 	const YuvPlanes pl = host ? stagedPlanes(out, stage) : callerPlanes(out);
 	encodeYuv(out.format, out.colorspace, pl, out.width, out.height, bgrx, static_cast<std::ptrdiff_t>(out.width * 4), state,
 	    frame16);
+	alphaInto(out.format, pl.y, pl.yStride);
 	if (host) copyPlanes(out, stage, false, m_Stream);
 }
 
@@ -234,23 +245,29 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	DeviceGuard g(m_Device);
 	const std::string unknown = scaleFilterProblem(filter);
 	if (!unknown.empty()) throw std::invalid_argument("ju_set_source_size: " + unknown);
+	const FrameSize fs = frameSize();
+	std::size_t inW, inH, outW, outH;
+	frameSizes(&inW, &inH, &outW, &outH);
 	if (width == 0 && height == 0) {
+		Scaler alpha = alphaScalerFor("ju_set_source_size", m_AlphaMode, m_AlphaFilter, fs.inputWidth, fs.inputHeight, outW, outH);
 		m_Stream.synchronize();  // (enqueued frames may still read the tables)
 		if (m_SrcScale.set()) dropStagePasses();
 		m_SrcScale.clear();
+		m_AlphaScale = std::move(alpha);
 		m_SrcStage = DeviceBuffer();
 		m_SrcYuvStage = DeviceBuffer();
 		return;
 	}
-	const FrameSize fs = frameSize();
 	const std::string problem = sourceSizeProblem(width, height, fs.inputWidth, fs.inputHeight, filter);
 	if (!problem.empty()) throw std::invalid_argument("ju_set_source_size: " + problem);
+	Scaler alpha = alphaScalerFor("ju_set_source_size", m_AlphaMode, m_AlphaFilter, width, height, outW, outH);
 	Scaler scale;
 	scale.build(width, height, fs.inputWidth, fs.inputHeight, filter);
 	DeviceBuffer stage(width * height * 4), yuvStage(yuvStageBytes(kFormatTable, width, height));
 	m_Stream.synchronize();
 	dropStagePasses();  // (the staged passes' graphs and slots are of the old size and tables)
 	m_SrcScale = std::move(scale);
+	m_AlphaScale = std::move(alpha);
 	m_SrcStage = std::move(stage);
 	m_SrcYuvStage = std::move(yuvStage);
 }
@@ -311,10 +328,15 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 	const std::string problem = outputSizeProblem(off ? fs.outputWidth : width, off ? fs.outputHeight : height, fs.outputWidth,
 	    fs.outputHeight, filter);
 	if (!problem.empty()) throw std::invalid_argument("ju_set_output_size: " + problem);
+	std::size_t inW, inH, outW, outH;
+	frameSizes(&inW, &inH, &outW, &outH);
+	Scaler alpha = alphaScalerFor("ju_set_output_size", m_AlphaMode, m_AlphaFilter, inW, inH, off ? fs.outputWidth : width,
+	    off ? fs.outputHeight : height);
 	if (off) {
 		m_Stream.synchronize();  // (enqueued frames may still read the tables and write the buffers)
 		if (m_OutScale.set()) dropStagePasses();
 		m_OutScale.clear();
+		m_AlphaScale = std::move(alpha);
 		for (DeviceBuffer *b : {&m_OutScaled8, &m_OutScaled16, &m_OutYuvStage, &m_OutRawStage}) *b = DeviceBuffer();
 		return;
 	}
@@ -325,6 +347,7 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 	m_Stream.synchronize();
 	dropStagePasses();
 	m_OutScale = std::move(scale);
+	m_AlphaScale = std::move(alpha);
 	m_OutScaled8 = std::move(scaled8);
 	m_OutScaled16 = std::move(scaled16);
 	m_OutRawStage = std::move(raw);
@@ -348,8 +371,12 @@ void Engine::stageOutScaled(const AnyFrame &out) {
 	const auto plain = static_cast<std::ptrdiff_t>(ow * 4);
 	if (!out.yuv) {
 		const Frame &b = out.bgrx;
-		if (b.location == Location::Device) return scale8(static_cast<std::uint8_t *>(b.ptr), b.stride);
+		if (b.location == Location::Device) {
+			scale8(static_cast<std::uint8_t *>(b.ptr), b.stride);
+			return alphaInto(PixelFormat::Bgrx, b.ptr, b.stride);  // (the caller's rows, where the scaler wrote them)
+		}
 		scale8(scaled8, plain);
+		alphaInto(PixelFormat::Bgrx, scaled8, plain);
 		return stageOut(b, ow, oh, scaled8, m_OutRawStage.as<std::uint8_t>());
 	}
 	auto *yuvStage = m_OutYuvStage.as<std::uint8_t>();
@@ -398,6 +425,7 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 	} else {
 		stageIn(in.bgrx);
 	}
+	if (m_AlphaMode == kAlphaSource) m_AlphaSrc = alphaSource(in, source);
 	sceneStep();  // (the decoded, scaled frame: what the program reads)
 	{
 		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
@@ -417,9 +445,93 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 		stageOutYuv(out.planes, m_OutStage.as<std::uint8_t>(), m_State[m_Config.recurrent() ? m_Idx ^ 1 : 0].get(), nullptr,
 		    m_YuvOutStage.as<std::uint8_t>());
 	} else {
+		alphaInto(PixelFormat::Bgrx, m_OutStage.get(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4));  // (the dense frame stageOut copies)
 		stageOut(out.bgrx, fs.outputWidth, fs.outputHeight, m_OutStage.as<std::uint8_t>(), m_RawStage.as<std::uint8_t>());
 	}
 	m_Idx ^= 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Alpha (docs/alpha.md).  The reference writes X = 0 on every route (cuda_convert.cc.cu:39-45) and so does every kernel
+// here; under ju_set_alpha ONE more launch follows a frame's colour on the staged route and writes the alpha slot of the
+// frame about to be handed out -- the top code (alpha_fill_kernel), or the input frame's alpha scaled from the input
+// frame's size straight to the output frame's size, never through the model's (alpha_scale_kernel).  The decode, encode
+// and scale kernels are untouched: the slot they left 0 is rewritten behind them, before any copy to the host.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// the slot of a format: kAlphaNone for one without
+int alphaKind(PixelFormat f) {
+	switch (f) {
+	case PixelFormat::Bgrx:
+	case PixelFormat::Rgbx: return kAlphaByte;
+	case PixelFormat::Bgrx64: return kAlphaWord;
+	case PixelFormat::X2rgb10:
+	case PixelFormat::X2bgr10: return kAlphaBits;
+	default: return kAlphaNone;
+	}
+}
+}  // namespace
+
+void Engine::frameSizes(std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const {
+	const FrameSize fs = frameSize();
+	*inW = m_SrcScale.set() ? m_SrcScale.srcW() : fs.inputWidth;
+	*inH = m_SrcScale.set() ? m_SrcScale.srcH() : fs.inputHeight;
+	*outW = m_OutScale.set() ? m_OutScale.dstW() : fs.outputWidth;
+	*outH = m_OutScale.set() ? m_OutScale.dstH() : fs.outputHeight;
+}
+
+Scaler Engine::alphaScalerFor(const char *who, int mode, int filter, std::size_t inW, std::size_t inH, std::size_t outW,
+    std::size_t outH) const {
+	const std::string problem = alphaProblem(mode, filter, inW, inH, outW, outH);
+	if (!problem.empty()) throw std::invalid_argument(std::string(who) + ": " + problem);
+	Scaler scale;
+	if (mode == kAlphaSource) scale.build(inW, inH, outW, outH, filter);
+	return scale;
+}
+
+void Engine::setAlpha(int mode, int filter) {
+	DeviceGuard g(m_Device);
+	std::size_t inW, inH, outW, outH;
+	frameSizes(&inW, &inH, &outW, &outH);
+	Scaler alpha = alphaScalerFor("ju_set_alpha", mode, filter, inW, inH, outW, outH);
+	m_Stream.synchronize();  // (enqueued frames may still read the tables)
+	m_AlphaScale = std::move(alpha);
+	m_AlphaMode = mode;
+	m_AlphaFilter = filter;
+}
+
+void Engine::alpha(int *mode, int *filter) const {
+	if (mode) *mode = m_AlphaMode;
+	if (filter) *filter = m_AlphaFilter;
+}
+
+AlphaRows Engine::alphaSource(const AnyFrame &in, const SourceView &bgrx) {
+	if (!in.yuv) {
+		// a device frame in place; a host frame (or a graphics resource) where submitFrame staged it
+		if (in.bgrx.location == Location::Device) return AlphaRows{kAlphaByte, in.bgrx.ptr, in.bgrx.stride};
+		return AlphaRows{kAlphaByte, const_cast<std::uint8_t *>(bgrx.ptr), bgrx.stride};
+	}
+	const int kind = alphaKind(in.planes.format);
+	if (kind == kAlphaNone) return AlphaRows{};
+	if (in.planes.location == Location::Device) return AlphaRows{kind, in.planes.planes[0], in.planes.strides[0]};
+	// a host frame: the planes stageInYuv uploaded, still in their staging buffer
+	const YuvPlanes pl = stagedPlanes(in.planes, (m_SrcScale.set() ? m_SrcYuvStage : m_YuvInStage).as<std::uint8_t>());
+	return AlphaRows{kind, pl.y, pl.yStride};
+}
+
+void Engine::alphaInto(PixelFormat format, void *rows, std::ptrdiff_t stride) {
+	const int kind = alphaKind(format);
+	if (m_AlphaMode == kAlphaZero || kind == kAlphaNone) return;
+	std::size_t inW, inH, outW, outH;
+	frameSizes(&inW, &inH, &outW, &outH);
+	const AlphaRows sink{kind, rows, stride};
+	if (m_AlphaMode == kAlphaOpaque) {
+		launchAlphaFill(sink, static_cast<int>(outW), static_cast<int>(outH), m_Stream);
+	} else {
+		launchAlphaScale(m_AlphaSrc, static_cast<int>(inW), static_cast<int>(inH), sink, static_cast<int>(outW), static_cast<int>(outH),
+		    m_AlphaScale.xAxis(), m_AlphaScale.yAxis(), m_AlphaScale.span(), m_Stream);
+	}
+	++m_AlphaFrames;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -277,6 +277,8 @@ void Engine::blendMask(std::uint8_t *gen, std::ptrdiff_t genStride, const std::u
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out, bool group) const {
 	// (scaled / masked frames run one by one through submitFrame unless the passes carry the stages: setStageLookahead; a
 	// group pass: setStageGroup)
+	// (alpha: the staged single-frame route, whatever the stage and scene settings say -- docs/alpha.md)
+	if (m_AlphaMode != 0) return false;
 	const int stage = stageBits(group);
 	if (sourceStage() && !stage) return false;
 	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
@@ -554,7 +556,7 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 	if (n < 0 || (n > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("prepareBatch: bad arguments");
 	DeviceGuard g(m_Device);
 	if (n < 2 || n > m_BatchMax || !m_UseGraph || !m_DirectGraph) return 0;
-	if (sourceStage()) return 0;  // (nothing is captured while a stage setting is on, whatever setStageLookahead says)
+	if (sourceStage() || m_AlphaMode != 0) return 0;  // (nothing is captured while a stage setting is on, whatever setStageLookahead says)
 	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
 	for (int i = 0; i < n; ++i) {
 		if (!passEligible(anyIn[i], anyOut[i])) return 0;
@@ -637,7 +639,7 @@ void setGroupRerun(int on) { g_GroupRerun = on; }
 void Engine::processBatch(const Frame *in, const Frame *out, int count) {
 	if (count < 0 || (count > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("processBatch: bad arguments");
 	const std::vector<AnyFrame> anyIn = anyOf(in, count), anyOut = anyOf(out, count);
-	if (sourceStage()) return processFrames(anyIn.data(), anyOut.data(), count);  // (every frame checked before the first runs)
+	if (sourceStage() || m_AlphaMode != 0) return processFrames(anyIn.data(), anyOut.data(), count);  // (every frame checked before the first runs)
 	runPasses(anyIn.data(), anyOut.data(), count);
 }
 
@@ -649,6 +651,7 @@ void Engine::processFrames(const AnyFrame *in, const AnyFrame *out, int count) {
 		try {
 			checkFrame(in[i], true);  // (every pair, also those that take submit())
 			checkFrame(out[i], false);
+			checkAlphaOverlap(in[i], out[i]);
 		} catch (const std::invalid_argument &e) {
 			throw std::invalid_argument("ju_process_frames: frame " + std::to_string(i) + ": " + e.what());
 		}
@@ -825,6 +828,7 @@ void Engine::runGroups(Engine *const *members, const AnyFrame *in, const AnyFram
 		try {
 			members[i]->checkFrame(in[i], true, who, true);
 			members[i]->checkFrame(out[i], false, who, true);
+			members[i]->checkAlphaOverlap(in[i], out[i]);
 		} catch (const std::invalid_argument &e) {
 			if (!indexed) throw;
 			// ("<who>: <why>" -> "<who>: member i: <why>")

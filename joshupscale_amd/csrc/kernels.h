@@ -716,6 +716,33 @@ void launchScaleState(const void *state, int srcW, int srcH, std::uint16_t *dst,
 // 16th of it -- an 8th for a cubic filter; a known filter)
 constexpr int kOutputAxisMin = 2, kOutputAxisMax = 16384;
 std::string outputSizeProblem(std::size_t outW, std::size_t outH, std::size_t modelW, std::size_t modelH, int filter);
+// ---- the alpha channel (alpha_kernels.hip; docs/alpha.md; tests/alpha_reference.py) ------------------------------------
+// The modes of ju_set_alpha (JU_ALPHA_*): the slot stays 0, holds the format's top code, or holds the input frame's
+// alpha scaled straight from the input frame's size to the output frame's size.
+constexpr int kAlphaZero = 0, kAlphaOpaque = 1, kAlphaSource = 2;
+// The limits of ju_set_alpha as one message shared with its Python twin, and what ju_set_source_size / ju_set_output_size
+// ask before they change a size under JU_ALPHA_SOURCE: "" when `mode` and `filter` are known and -- in that mode -- the
+// alpha scaler can go from the input frame inW x inH to the output frame outW x outH (each axis 2 .. 16384, the input at
+// most 16 times the output -- 8 with a cubic filter -- and the output at most 16 times the input)
+std::string alphaProblem(int mode, int filter, std::size_t inW, std::size_t inH, std::size_t outW, std::size_t outH);
+// Where an alpha slot lies in rows of pixels: byte 3 of four-byte pixels (any byte alignment), word 3 of eight-byte pixels
+// (2-byte aligned), bits 30-31 of 32-bit words (4-byte aligned); as a source also none -- the plane is 65535 everywhere
+// and nothing is read.  ptr: the first logical row; stride: bytes, any sign.
+constexpr int kAlphaByte = 0, kAlphaWord = 1, kAlphaBits = 2, kAlphaNone = 3;
+struct AlphaRows {
+	int kind = kAlphaNone;
+	void *ptr = nullptr;
+	std::ptrdiff_t stride = 0;
+};
+// One launch: the 16-bit alpha plane of `src` (257 a, the word, 21845 a, or 65535) scaled srcW x srcH -> dstW x dstH,
+// A' = (sum qy qx A + 2^23) >> 24 (clamped to 0 .. 65535 where the filter is cubic), its code ((A' + 128) / 257, A',
+// (A' + 10922) / 21845) stored into the slot of every pixel of `dst`; no other bit of the destination changes.  x / y /
+// spanX as for launchScaleBgrx.  std::invalid_argument: an unknown kind, a NULL side, a stride shorter than a row, a
+// misaligned side, or a tile beyond the LDS.
+void launchAlphaScale(const AlphaRows &src, int srcW, int srcH, const AlphaRows &dst, int dstW, int dstH, const ScaleAxisDev &x,
+    const ScaleAxisDev &y, int spanX, hipStream_t stream);
+// One launch: the top code (255, 65535, 3) into the slot of every pixel of `dst`
+void launchAlphaFill(const AlphaRows &dst, int dstW, int dstH, hipStream_t stream);
 // Masked pass-through over the frame `gen` (outW x outH BGRX rows, rewritten in place): per pixel the point-sampled
 // texel of `src` (srcW x srcH) and of `mask` (maskW x maskH), a = 765 - (Rm + Gm + Bm), out = (src a + gen (765 - a) +
 // 382) / 765 per channel, X = 0; pixels with a == 0 are not rewritten.  Any byte alignment, signed strides.

@@ -163,6 +163,38 @@ def tiled_output_size_problem(width: int, height: int, src_width: int, src_heigh
     return f"{problem} (of a tiled object: the blended frame {bw}x{bh}, four times the tiled source size)"
 
 
+# the alpha channel (docs/alpha.md): the modes of ju_set_alpha (JU_ALPHA_*)
+ALPHA_ZERO, ALPHA_OPAQUE, ALPHA_SOURCE = 0, 1, 2
+ALPHA_MODES = (ALPHA_ZERO, ALPHA_OPAQUE, ALPHA_SOURCE)
+# where an alpha slot lies in rows of pixels (the kinds of ju_debug_alpha_scale / ju_debug_alpha_fill): byte 3 of
+# four-byte pixels, word 3 of eight-byte pixels, bits 30-31 of 32-bit words; a source may have none (opaque)
+ALPHA_KIND_BYTE, ALPHA_KIND_WORD, ALPHA_KIND_BITS, ALPHA_KIND_NONE = 0, 1, 2, 3
+
+
+def alpha_problem(mode: int, filter: int, in_width: int, in_height: int, out_width: int, out_height: int) -> str:
+    """The limits of ``ju_set_alpha`` for a runtime whose input frames are ``in_width x in_height`` and whose output
+    frames are ``out_width x out_height``, with the C layer's message; ``""`` when the setting may be made.  Under
+    ``ALPHA_SOURCE`` ``ju_set_source_size`` and ``ju_set_output_size`` hold the sizes they would leave to the same."""
+    if mode not in ALPHA_MODES:
+        return (f"unknown alpha mode {mode} (the modes are JU_ALPHA_ZERO = 0, JU_ALPHA_OPAQUE = 1 and "
+                "JU_ALPHA_SOURCE = 2)")
+    unknown = scale_filter_problem(filter)
+    if unknown:
+        return unknown
+    if mode != ALPHA_SOURCE:
+        return ""
+    down = SOURCE_RATIO_MAX if filter == SCALE_TRIANGLE else CUBIC_DOWN_MAX
+
+    def ok(n, m):
+        return (OUTPUT_AXIS_MIN <= n <= OUTPUT_AXIS_MAX and OUTPUT_AXIS_MIN <= m <= OUTPUT_AXIS_MAX and n <= down * m and
+                m <= SOURCE_RATIO_MAX * n)
+    if ok(in_width, out_width) and ok(in_height, out_height):
+        return ""
+    return (f"alpha from the source: the input frame {in_width}x{in_height} and the output frame {out_width}x{out_height} "
+            f"must be {OUTPUT_AXIS_MIN} .. {OUTPUT_AXIS_MAX} on each axis, the input at most {down} times the output and "
+            f"the output at most {SOURCE_RATIO_MAX} times the input (the alpha scaler goes from one straight to the other)")
+
+
 LOG_CALLBACK = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p)
 
 
@@ -281,6 +313,8 @@ _PRODUCT_SIGS = {
     "ju_set_source_mask": (C.c_int, [C.c_void_p, _P(JuImage)]),
     "ju_set_output_size": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "ju_get_output_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
+    "ju_set_alpha": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ju_get_alpha": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
     "ju_tiled_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p)]),
     "ju_tiled_create_from_memory": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int,
                                               _P(C.c_void_p)]),
@@ -351,6 +385,10 @@ _HOOK_SIGS = {
                                              _P(C.c_size_t)]),
     "ju_debug_scale": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_ssize_t,
                                  C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ju_debug_alpha_scale": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                       C.c_ssize_t, C.c_size_t, C.c_size_t]),
+    "ju_debug_alpha_fill": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
+    "ju_debug_alpha_problem": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "ju_debug_scale_items": (C.c_int, [C.c_int, C.c_int, _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
                                        _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t]),
     "ju_debug_scale_members": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
@@ -604,6 +642,8 @@ class Runtime:
             source_size_problem(width, height, self.input_width, self.input_height, filter)
         if problem:
             raise ValueError("ju_set_source_size: " + problem)
+        self._alpha_allows("ju_set_source_size", (self.input_width, self.input_height) if off else (width, height),
+                           self.frame_output_size())
         _check(self._lib, self._lib.ju_set_source_size(self._h, width, height, filter))
 
     def get_source_size(self) -> Tuple[int, int]:
@@ -634,6 +674,8 @@ class Runtime:
                                       self.output_width, self.output_height, filter)
         if problem:
             raise ValueError("ju_set_output_size: " + problem)
+        self._alpha_allows("ju_set_output_size", self.frame_input_size(),
+                           (self.output_width, self.output_height) if off else (width, height))
         _check(self._lib, self._lib.ju_set_output_size(self._h, width, height, filter))
 
     def get_output_size(self) -> Tuple[int, int]:
@@ -646,6 +688,38 @@ class Runtime:
         """``(width, height)`` of the frames the runtime hands out now: the output size set, else the model's output."""
         w, h = self.get_output_size()
         return (w, h) if w else (self.output_width, self.output_height)
+
+    def frame_input_size(self) -> Tuple[int, int]:
+        """``(width, height)`` of the frames the runtime takes now: the source size set, else the model's input."""
+        w, h = self.get_source_size()
+        return (w, h) if w else (self.input_width, self.input_height)
+
+    # -- the alpha channel (docs/alpha.md) -----------------------------------------
+    def set_alpha(self, mode: int, filter: int = SCALE_TRIANGLE) -> None:
+        """``ju_set_alpha``: what the alpha slot of output frames holds -- ``ALPHA_ZERO`` (0, the default: every route
+        as without the call), ``ALPHA_OPAQUE`` (the format's top code) or ``ALPHA_SOURCE`` (the input frame's alpha,
+        scaled by ``filter`` from the input frame's size straight to the output frame's size).  The filter is checked in
+        every mode.  An unknown mode or filter and, under ``ALPHA_SOURCE``, frame sizes beyond the scaler raise
+        ``ValueError`` with the C layer's message before any native call; the setting stays as it was."""
+        mode, filter = int(mode), int(filter)
+        problem = alpha_problem(mode, filter, *self.frame_input_size(), *self.frame_output_size())
+        if problem:
+            raise ValueError("ju_set_alpha: " + problem)
+        _check(self._lib, self._lib.ju_set_alpha(self._h, mode, filter))
+
+    def get_alpha(self) -> Tuple[int, int]:
+        """``ju_get_alpha``: ``(mode, filter)`` as set; ``(ALPHA_ZERO, SCALE_TRIANGLE)`` on a fresh runtime."""
+        mode, filter = C.c_int(), C.c_int()
+        _check(self._lib, self._lib.ju_get_alpha(self._h, C.byref(mode), C.byref(filter)))
+        return mode.value, filter.value
+
+    def _alpha_allows(self, who: str, in_size, out_size) -> None:
+        """What ``set_source_size`` / ``set_output_size`` ask before they change a size: under ``ALPHA_SOURCE`` the alpha
+        scaler must still reach from the one frame size to the other."""
+        mode, filter = self.get_alpha()
+        problem = alpha_problem(mode, filter, *in_size, *out_size)
+        if problem:
+            raise ValueError(f"{who}: {problem}")
 
     def process_image(self, frame_bgrx: np.ndarray,
                       out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -777,7 +851,8 @@ class Runtime:
         "lookahead_host_frames", "lookahead_yuv_frames", "source_scaled", "source_mask", "source_stage_frames",
         "output_scaled", "source_filter", "output_filter", "scene_mode", "scene_frames", "scene_cuts", "scene_lookahead",
         "scene_pass_frames", "stage_lookahead", "lookahead_staged_frames", "group_frames", "group_yuv_frames",
-        "scene_group", "scene_group_frames", "stage_group", "group_staged_frames"."""
+        "scene_group", "scene_group_frames", "stage_group", "group_staged_frames", "alpha_mode", "alpha_filter",
+        "alpha_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1222,3 +1297,10 @@ class Session:
 
     def get_output_size(self) -> Tuple[int, int]:
         return self.runtime.get_output_size()
+
+    def set_alpha(self, mode: int, filter: int = SCALE_TRIANGLE) -> None:
+        """The alpha of the ``[H, W, 4]`` images ``run`` returns (``Runtime.set_alpha``)."""
+        self.runtime.set_alpha(mode, filter)
+
+    def get_alpha(self) -> Tuple[int, int]:
+        return self.runtime.get_alpha()
