@@ -1365,7 +1365,7 @@ void Engine::reset() {
 	}
 	m_Stream.synchronize();
 	m_Idx = 0;
-	m_SceneSeen = 0;  // the scene detector has no predecessor after a reset; its setting and its step count stay
+	m_Scene.restart();  // the scene detector has no predecessor after a reset; its setting and its step count stay
 }
 
 FrameSize Engine::frameSize() const {
@@ -1551,7 +1551,7 @@ void Engine::submit(const Frame &in, const Frame &out) {
 		// detector: a refused frame must not reach it (it would overwrite the kept frame, count a step and, at a cut,
 		// clear the inputs of a step that then does not happen).  Off: as ju_process always behaved.  (A graphics
 		// resource's own extent is known only when it is mapped, in stageOut.)
-		if (m_SceneMode != 0) checkFrame(anyOf(out), false, "processImage");
+		if (m_Scene.mode() != 0) checkFrame(anyOf(out), false, "processImage");
 	}
 	sceneStep();
 	{
@@ -1862,7 +1862,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "output_scaled") return m_OutScale.set() ? 1.0 : 0.0;
 	if (key == "source_filter") return static_cast<double>(m_SrcScale.filter());  // (0 while off: the setters clear it)
 	if (key == "output_filter") return static_cast<double>(m_OutScale.filter());
-	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
+	if (key == "source_mask") return m_Mask.on() ? 1.0 : 0.0;
 	if (key == "alpha_mode") return static_cast<double>(m_AlphaMode);
 	if (key == "alpha_filter") return static_cast<double>(m_AlphaFilter);
 	if (key == "alpha_frames") return static_cast<double>(m_AlphaFrames);  // frames whose alpha slot the alpha kernels wrote
@@ -1871,7 +1871,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "group_yuv_frames") return static_cast<double>(m_GroupYuvFrames);  // ... of them with a non-BGRX side
 	if (key == "scene_group") return m_SceneGroup ? 1.0 : 0.0;
 	if (key == "scene_group_frames") return static_cast<double>(m_SceneGroupFrames);  // detector steps taken inside group passes
-	if (key == "scene_mode") return static_cast<double>(m_SceneMode);
+	if (key == "scene_mode") return static_cast<double>(m_Scene.mode());
 	if (key == "scene_lookahead") return m_SceneLookahead ? 1.0 : 0.0;
 	if (key == "scene_pass_frames") return static_cast<double>(m_ScenePassFrames);
 	if (key == "stage_lookahead") return m_StageLookahead ? 1.0 : 0.0;
@@ -1879,15 +1879,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "stage_group") return m_StageGroup ? 1.0 : 0.0;
 	if (key == "group_staged_frames") return static_cast<double>(m_GroupStagedFrames);  // group-pass frames under a stage setting
 	// (the detector's own counters, as of the steps that have completed: the decision writes them to host-mapped memory)
-	if (key == "scene_frames" || key == "scene_cuts") {
-		const bool cuts = key == "scene_cuts";
-		std::uint64_t n = cuts ? m_SceneCutsBase : m_SceneFramesBase;
-		if (const volatile unsigned *w = m_SceneRing.host()) {
-			const auto *totals = reinterpret_cast<const volatile SceneRecord *>(w) + kSceneRing;
-			n += cuts ? totals->sad : totals->step;
-		}
-		return static_cast<double>(n);
-	}
+	if (key == "scene_frames" || key == "scene_cuts") return static_cast<double>(m_Scene.total(key == "scene_cuts"));
 	if (key == "scene_detector_runs") return static_cast<double>(m_SceneRuns);  // launches of the detector (tests: once per step)
 	if (key == "launches_per_frame") return static_cast<double>(m_Program[0].size());
 	if (key == "tower_variant") return static_cast<double>(towerVariant());  // (developer switch, tests)

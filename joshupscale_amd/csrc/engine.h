@@ -25,6 +25,7 @@
 #include "hip_util.h"
 #include "kernels.h"
 #include "model.h"
+#include "scene_detector.h"
 
 namespace ju {
 
@@ -138,7 +139,7 @@ public:
 	// Waits for the stream; reset() keeps it.
 	void setAlpha(int mode, int filter);
 	void alpha(int *mode, int *filter) const;
-	bool sourceStage() const { return m_SrcScale.set() || m_MaskW != 0 || m_OutScale.set(); }
+	bool sourceStage() const { return m_SrcScale.set() || m_Mask.on() || m_OutScale.set(); }
 	// The scene detector (docs/scene_detect.md; "Scene detector" below).  setSceneDetect: mode 0 off / 1 report / 2 reset
 	// (JU_SCENE_*), thresholdMilli 1 .. 255000 while the mode is not off; waits for the stream; a call that changes the
 	// mode starts the detector over (no predecessor, step 0).  reset() keeps the setting and forgets the predecessors.
@@ -263,19 +264,12 @@ private:
 	bool m_HbdFromState = true;
 	// Source stage: the scaler from the size input frames must have (its source size; not set = the model's input) to
 	// the model's input, its filter the one in effect ("source_filter"); the BGRX source frame at source size (host
-	// uploads, decoded YUV) and the host planes of a YUV source; the mask in device memory, in the caller's row order
-	// (m_MaskStride < 0: bottom-up).  m_SourceFrames: frames that went through the stage ("source_stage_frames").
+	// uploads, decoded YUV) and the host planes of a YUV source; the mask's device copy (frame_io.h SourceMask).
+	// m_SourceFrames: frames that went through the stage ("source_stage_frames").
 	Scaler m_SrcScale;
 	DeviceBuffer m_SrcStage, m_SrcYuvStage;
-	DeviceBuffer m_Mask;
-	std::size_t m_MaskW = 0, m_MaskH = 0;
-	std::ptrdiff_t m_MaskStride = 0;
+	SourceMask m_Mask;
 	std::uint64_t m_SourceFrames = 0;
-	struct SourceView {  // the BGRX source frame the scaler and the blend read in this call
-		const std::uint8_t *ptr = nullptr;
-		std::ptrdiff_t stride = 0;
-	};
-	SourceView stageInSource(const AnyFrame &in);
 	// (width x height: the size of the frame encoded; of bgrx / state / frame16 the one the format's path reads)
 	void encodeYuv(PixelFormat format, int colorspace, const YuvPlanes &planes, std::size_t width, std::size_t height,
 	    const std::uint8_t *bgrx, std::ptrdiff_t bgrxStride, const void *state, const std::uint16_t *frame16 = nullptr,
@@ -301,22 +295,17 @@ private:
 	Scaler alphaScalerFor(const char *who, int mode, int filter, std::size_t inW, std::size_t inH, std::size_t outW, std::size_t outH) const;
 	void frameSizes(std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const;
 	// where the input frame's alpha lies once submitFrame has staged the frame; bgrx: the BGRX rows it staged
-	AlphaRows alphaSource(const AnyFrame &in, const SourceView &bgrx);
+	AlphaRows alphaSource(const AnyFrame &in, const BgrxRows &bgrx);
 	// the one alpha launch of a frame, behind its colour and in front of any copy to the host: nothing in mode 0 or for a
 	// format without a slot
 	void alphaInto(PixelFormat format, void *rows, std::ptrdiff_t stride);
 	// Scene detector: two eager launches on m_Stream in front of runProgram(), outside the chain lock and never captured
-	// (sceneStep: submit and submitFrame, once m_IO.in holds the frame the program will read).  m_ScenePrev: the frame
-	// compared against; m_SceneDev: the SceneState; m_SceneRing: kSceneRing records + the totals, host-mapped.
-	// m_SceneSeen: steps since the last start (decides the "has predecessor" bits); m_SceneSteps: steps since the mode was
-	// turned on (the record's `step`, the ring slot).  m_SceneRerun: set around the re-run of a frame (runSynchronous) --
-	// THE one place that keeps a step from running the detector twice; m_SceneRuns counts the runs ("scene_detector_runs").
-	int m_SceneMode = 0;
-	std::uint32_t m_SceneThreshold = 0;
-	DeviceBuffer m_ScenePrev, m_SceneDev;
-	PinnedWords m_SceneRing;
-	std::uint64_t m_SceneSeen = 0, m_SceneSteps = 0, m_SceneRuns = 0;
-	std::uint64_t m_SceneFramesBase = 0, m_SceneCutsBase = 0;  // "scene_frames" / "scene_cuts" of earlier on-periods
+	// (sceneStep: submit and submitFrame, once m_IO.in holds the frame the program will read).  m_Scene: the setting, the
+	// detector's memory on the model-size input and its clock (scene_detector.h).  m_SceneRerun: set around the re-run of a
+	// frame (runSynchronous) -- THE one place that keeps a step from running the detector twice; m_SceneRuns counts the runs
+	// ("scene_detector_runs").
+	SceneDetector m_Scene;
+	std::uint64_t m_SceneRuns = 0;
 	bool m_SceneRerun = false;
 	void sceneStep();
 	// The detector inside look-ahead passes.  m_ScenePassDev: the ScenePassState (accumulators, ticket, resetAt[], cutAt[]),
@@ -329,8 +318,8 @@ private:
 	// what a pass formed now carries: 0 nothing, 1 the detector, 2 the detector and the restart at its cuts (reset mode
 	// on a recurrent model: clear nodes and the cut-aware flow program) -- part of the key of a pass's graph
 	int scenePass() const {
-		if (!m_SceneLookahead || m_SceneMode == 0) return 0;
-		return m_SceneMode == 2 && m_Config.recurrent() ? 2 : 1;
+		if (!m_SceneLookahead || m_Scene.mode() == 0) return 0;
+		return m_Scene.mode() == 2 && m_Config.recurrent() ? 2 : 1;
 	}
 	// binding set of the cut-aware flow launches in m_BatchFlow: {items, kCutSet + set}
 	static constexpr int kCutSet = 4;
@@ -339,7 +328,7 @@ private:
 	bool m_SceneGroup = false;
 	PinnedWords m_SceneGroupDyn;
 	std::uint64_t m_SceneGroupFrames = 0;
-	void dropScenePassGraphs();  // the graphs of passes that carry the detector: bound to m_ScenePrev / m_SceneDev / m_SceneRing
+	void dropScenePassGraphs();  // the graphs of passes that carry the detector: bound to m_Scene's memory
 	// Everything a frame call can refuse, before anything is launched; `who` names the entry point in the message.
 	// declaredSize (ju_process_group): a NULL pointer is refused first and by name, and a graphics resource's DECLARED
 	// size counts too -- otherwise the texture's own extent is checked when it is mapped, behind other members' launches.
@@ -352,8 +341,6 @@ private:
 	void checkAlphaOverlap(const AnyFrame &in, const AnyFrame &out) const;
 	// one frame's launches by that decision, enqueue only
 	void submitAny(const AnyFrame &in, const AnyFrame &out);
-	// one decode launch: the planes of `in` (host planes through `stage` first) -> dense BGRX rows of the frame's own size
-	void stageInYuv(const YuvFrame &in, std::uint8_t *stage, std::uint8_t *bgrx);
 	// (stage: where a host frame's planes are written before they are copied out)
 	void stageOutYuv(const YuvFrame &out, const std::uint8_t *bgrx, const void *state, const std::uint16_t *frame16,
 	    std::uint8_t *stage);
@@ -625,7 +612,7 @@ private:
 	bool m_StageLookahead = false, m_StageGroup = false;
 	int stageBits(bool group) const {
 		if (!(group ? m_StageGroup : m_StageLookahead) || !sourceStage()) return 0;
-		return (m_SrcScale.set() ? 1 : 0) | (m_MaskW != 0 ? 2 : 0) | (m_OutScale.set() ? 4 : 0);
+		return (m_SrcScale.set() ? 1 : 0) | (m_Mask.on() ? 2 : 0) | (m_OutScale.set() ? 4 : 0);
 	}
 	struct StageSlots {
 		DeviceBuffer src, srcYuv, in, modelOut, out8, out16, outYuv;

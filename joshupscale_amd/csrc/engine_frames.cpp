@@ -194,17 +194,9 @@ void Engine::checkAlphaOverlap(const AnyFrame &in, const AnyFrame &out) const {
 	}
 }
 
-void Engine::stageInYuv(const YuvFrame &in, std::uint8_t *stage, std::uint8_t *bgrx) {
-	const bool host = in.location != Location::Device;
-	if (host) copyPlanes(in, stage, true, m_Stream);
-	const YuvPlanes pl = host ? stagedPlanes(in, stage) : callerPlanes(in);
-	launchDecodeFrame(fmt(in.format), in.colorspace, pl, bgrx, static_cast<std::ptrdiff_t>(in.width * 4), static_cast<int>(in.width),
-	    static_cast<int>(in.height), m_Stream);
-}
-
 bool Engine::deepFromState(PixelFormat format) const {
 	// (a mask: the blended frame exists in 8 bits only)
-	return m_HbdFromState && m_MaskW == 0 && formatInfo(format).deep();
+	return m_HbdFromState && !m_Mask.on() && formatInfo(format).deep();
 }
 
 // one encode launch on the engine's stream behind a frame's last kernel: the frame's BGRX rows -- or, for a 10-bit YUV or
@@ -281,37 +273,20 @@ void Engine::setSourceMask(const Frame *mask) {
 	DeviceGuard g(m_Device);
 	if (mask == nullptr) {
 		m_Stream.synchronize();
-		if (m_MaskW != 0) dropStagePasses();
-		m_Mask = DeviceBuffer();
-		m_MaskW = m_MaskH = 0;
-		m_MaskStride = 0;
+		if (m_Mask.on()) dropStagePasses();
+		m_Mask = SourceMask();
 		return;
 	}
 	if (mask->location != Location::Host && mask->location != Location::Device) {
 		throw std::invalid_argument("ju_set_source_mask: the mask must be host or device memory");
 	}
-	constexpr std::size_t kMaskMax = 16384;
-	if (mask->ptr == nullptr || mask->width < 1 || mask->height < 1 || mask->width > kMaskMax || mask->height > kMaskMax) {
+	if (mask->ptr == nullptr || mask->width < 1 || mask->height < 1 || mask->width > kMaskAxisMax || mask->height > kMaskAxisMax) {
 		throw std::invalid_argument("ju_set_source_mask: the mask must be 1 .. 16384 pixels on each axis");
 	}
-	const std::size_t rowBytes = mask->width * 4;
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	if (mask->stride > -plain && mask->stride < plain) {
-		throw std::invalid_argument("ju_set_source_mask: |stride| smaller than a row");
-	}
-	// copied once, in the caller's memory order (a bottom-up mask stays bottom-up and is read with a negative stride)
-	DeviceBuffer buf(rowBytes * mask->height);
-	const RowSpan rows = rowSpan(mask->ptr, mask->stride, mask->height);
-	copyRows(buf.get(), rowBytes, rows.lowest, rows.pitch, rowBytes, mask->height,
-	    mask->location == Location::Host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, nullptr);
-	// (on the null stream and waited for, as a blocking copy is: behind what the caller's own default-stream work wrote)
-	JU_HIP(hipStreamSynchronize(nullptr));
+	SourceMask copy = SourceMask::copyOf(*mask, "ju_set_source_mask");  // (copied once, now)
 	m_Stream.synchronize();
 	dropStagePasses();  // (their blend launches hold the old mask's address)
-	m_Mask = std::move(buf);
-	m_MaskW = mask->width;
-	m_MaskH = mask->height;
-	m_MaskStride = rows.topDown ? plain : -plain;
+	m_Mask = std::move(copy);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -389,24 +364,6 @@ void Engine::stageOutScaled(const AnyFrame &out) {
 	stageOutYuv(out.planes, scaled8, nullptr, nullptr, yuvStage);
 }
 
-// The input of a frame while a source size is set, as BGRX rows at source size: a device image is read where it is, a
-// host image is uploaded in its memory order, YUV planes are decoded by the existing conversion, unchanged.
-Engine::SourceView Engine::stageInSource(const AnyFrame &in) {
-	const std::size_t rowBytes = m_SrcScale.srcW() * 4, height = m_SrcScale.srcH();
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	auto *stage = m_SrcStage.as<std::uint8_t>();
-	if (in.yuv) {
-		stageInYuv(in.planes, m_SrcYuvStage.as<std::uint8_t>(), stage);
-		return {stage, plain};
-	}
-	const Frame &b = in.bgrx;
-	if (b.location == Location::Device) return {static_cast<std::uint8_t *>(b.ptr), b.stride};
-	const RowSpan rows = rowSpan(b.ptr, b.stride, height);
-	copyRows(stage, rowBytes, rows.lowest, rows.pitch, rowBytes, height, hipMemcpyHostToDevice, m_Stream);
-	if (rows.topDown) return {stage, plain};
-	return {stage + static_cast<std::ptrdiff_t>(height - 1) * plain, -plain};
-}
-
 // Staged frames (a YUV side; any pair while a source or output stage is set): always through the staging buffers -- the conversion kernel takes the place of the
 // staging copy on its side and the binding set's staged graph replays unchanged.  The conversions are eager launches
 // on m_Stream OUTSIDE the per-device chain lock, like the staging copies of submit().
@@ -415,13 +372,15 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 	bindStaging();
 	const FrameSize fs = frameSize();
 	// what the mask lets through: the source frame at source size, or the model-size input frame
-	SourceView source{m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4)};
+	BgrxRows source{m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4)};
 	if (m_SrcScale.set()) {
-		source = stageInSource(in);
+		// the frame at source size: a device image where it is (the scaler takes any alignment), else through m_SrcStage
+		source = stageInBgrx(in, m_SrcScale.srcW(), m_SrcScale.srcH(), m_SrcStage.as<std::uint8_t>(), m_SrcYuvStage.as<std::uint8_t>(),
+		    false, m_Stream);
 		m_SrcScale.scaleBgrx(source.ptr, source.stride, m_InStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.inputWidth * 4),
 		    m_Stream);
 	} else if (in.yuv) {
-		stageInYuv(in.planes, m_YuvInStage.as<std::uint8_t>(), m_InStage.as<std::uint8_t>());
+		decodePlanes(in.planes, m_YuvInStage.as<std::uint8_t>(), m_InStage.as<std::uint8_t>(), m_Stream);
 	} else {
 		stageIn(in.bgrx);
 	}
@@ -432,7 +391,7 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 		runProgram();
 		chainEnd(chain, m_Resident);
 	}
-	if (m_MaskW != 0) {
+	if (m_Mask.on()) {
 		// over the frame handed to the caller only: state and history are the unmasked run's
 		blendMask(m_OutStage.as<std::uint8_t>(), static_cast<std::ptrdiff_t>(fs.outputWidth * 4), source.ptr, source.stride,
 		    m_SrcScale.set() ? m_SrcScale.srcW() : fs.inputWidth, m_SrcScale.set() ? m_SrcScale.srcH() : fs.inputHeight, m_Stream);
@@ -505,7 +464,7 @@ void Engine::alpha(int *mode, int *filter) const {
 	if (filter) *filter = m_AlphaFilter;
 }
 
-AlphaRows Engine::alphaSource(const AnyFrame &in, const SourceView &bgrx) {
+AlphaRows Engine::alphaSource(const AnyFrame &in, const BgrxRows &bgrx) {
 	if (!in.yuv) {
 		// a device frame in place; a host frame (or a graphics resource) where submitFrame staged it
 		if (in.bgrx.location == Location::Device) return AlphaRows{kAlphaByte, in.bgrx.ptr, in.bgrx.stride};
@@ -514,7 +473,7 @@ AlphaRows Engine::alphaSource(const AnyFrame &in, const SourceView &bgrx) {
 	const int kind = alphaKind(in.planes.format);
 	if (kind == kAlphaNone) return AlphaRows{};
 	if (in.planes.location == Location::Device) return AlphaRows{kind, in.planes.planes[0], in.planes.strides[0]};
-	// a host frame: the planes stageInYuv uploaded, still in their staging buffer
+	// a host frame: the planes decodePlanes uploaded, still in their staging buffer
 	const YuvPlanes pl = stagedPlanes(in.planes, (m_SrcScale.set() ? m_SrcYuvStage : m_YuvInStage).as<std::uint8_t>());
 	return AlphaRows{kind, pl.y, pl.yStride};
 }
@@ -546,31 +505,11 @@ void Engine::setSceneDetect(int mode, std::uint32_t thresholdMilli) {
 	if (!problem.empty()) throw std::invalid_argument("ju_set_scene_detect: " + problem);
 	DeviceGuard g(m_Device);
 	m_Stream.synchronize();
-	if (mode == m_SceneMode) {  // the same mode: the threshold alone; the detector's memory stays
-		if (mode != 0) m_SceneThreshold = thresholdMilli;
-		return;
-	}
-	if (m_SceneRing.host()) {  // the counters of the period that ends here
-		const auto *totals = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host()) + kSceneRing;
-		m_SceneFramesBase += totals->step;
-		m_SceneCutsBase += totals->sad;
-	}
-	// a start: fresh (zeroed) memory, no predecessor, step 0.  The only captured graphs bound to these buffers are those
-	// of passes that carry the detector (PassKey::scene != 0): they go with them.
-	dropScenePassGraphs();
-	m_ScenePrev = DeviceBuffer();
-	m_SceneDev = DeviceBuffer();
-	m_SceneRing = PinnedWords();
-	if (mode != 0) {
-		const FrameSize fs = frameSize();
-		m_ScenePrev = DeviceBuffer(fs.inputWidth * fs.inputHeight * 4);
-		m_SceneDev = DeviceBuffer(sizeof(SceneState));
-		m_SceneRing = PinnedWords(sizeof(SceneRecord) * (kSceneRing + 1));
-	}
-	m_SceneMode = mode;
-	m_SceneThreshold = mode != 0 ? thresholdMilli : 0;
-	m_SceneSeen = 0;
-	m_SceneSteps = 0;
+	// A mode change is a start: fresh memory for the model-size input, no predecessor, step 0.  The only captured graphs
+	// bound to the old buffers are those of passes that carry the detector (PassKey::scene != 0): they go first.
+	if (mode != m_Scene.mode()) dropScenePassGraphs();
+	const FrameSize fs = frameSize();
+	m_Scene.configure(mode, thresholdMilli, fs.inputWidth * fs.inputHeight * 4);
 }
 
 void Engine::dropScenePassGraphs() {
@@ -599,56 +538,36 @@ void Engine::setSceneGroup(int on) {
 }
 
 void Engine::sceneDetect(int *mode, std::uint32_t *thresholdMilli) const {
-	if (mode) *mode = m_SceneMode;
-	if (thresholdMilli) *thresholdMilli = m_SceneThreshold;
+	if (mode) *mode = m_Scene.mode();
+	if (thresholdMilli) *thresholdMilli = m_Scene.threshold();
 }
 
 int Engine::sceneInfo(SceneRecord *out, int count) {
 	if (count < 0 || (count > 0 && out == nullptr)) throw std::invalid_argument("ju_get_scene_info: NULL records or a negative count");
 	DeviceGuard g(m_Device);
 	m_Stream.synchronize();
-	if (m_SceneMode == 0 || m_SceneRing.host() == nullptr) return 0;
-	const std::uint64_t have = std::min<std::uint64_t>(m_SceneSteps, kSceneRing);
-	const int n = static_cast<int>(std::min<std::uint64_t>(have, static_cast<std::uint64_t>(count)));
-	const auto *ring = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host());
-	for (int k = 0; k < n; ++k) {
-		const std::uint64_t step = m_SceneSteps - static_cast<std::uint64_t>(n) + static_cast<std::uint64_t>(k);
-		const volatile SceneRecord &r = ring[step % kSceneRing];
-		out[k].step = r.step;
-		out[k].sad = r.sad;
-		out[k].score = r.score;
-		out[k].cut = r.cut;
-		out[k].reserved = 0;
-	}
-	return n;
+	return m_Scene.records(out, count);
 }
 
 // One detector step on the frame m_IO.in holds when the program runs.  Called by submit / submitFrame for every step
 // exactly once: the re-run of a frame (runSynchronous) comes through here with m_SceneRerun set and launches nothing.
 void Engine::sceneStep() {
-	if (m_SceneMode == 0 || m_SceneRerun) return;
+	if (m_Scene.mode() == 0 || m_SceneRerun) return;
 	const FrameSize fs = frameSize();
 	SceneSadLaunch q;
 	q.src = m_IO.in;
 	q.srcStride = m_IO.inStride;
 	q.width = static_cast<int>(fs.inputWidth);
 	q.height = static_cast<int>(fs.inputHeight);
-	q.prev = m_ScenePrev.as<std::uint32_t>();
-	q.state = m_SceneDev.as<SceneState>();
-	q.ring = reinterpret_cast<SceneRecord *>(m_SceneRing.device());
-	q.slot = static_cast<int>(m_SceneSteps % kSceneRing);
-	q.step = m_SceneSteps;
-	q.hasPrev = (m_SceneSeen >= 1 ? 1 : 0) | (m_SceneSeen >= 2 ? 2 : 0);
-	q.thresholdMilli = m_SceneThreshold;
+	m_Scene.fill(q);
 	// (a flow-free model has no recurrent input to clear: JU_SCENE_RESET reports)
-	q.resetMode = m_SceneMode == 2 && m_Config.recurrent();
+	q.resetMode = m_Scene.mode() == 2 && m_Config.recurrent();
 	launchSceneSad(q, m_Stream);
 	if (q.resetMode) {
 		launchSceneClear(&q.state->resetNow, m_State[m_Idx].get(), m_State[m_Idx].bytes(), m_Packed[m_Idx].get(),
 		    m_Packed[m_Idx].bytes(), m_Stream);
 	}
-	++m_SceneSeen;
-	++m_SceneSteps;
+	m_Scene.advance();
 	++m_SceneRuns;
 }
 

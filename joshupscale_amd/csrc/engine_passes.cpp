@@ -200,11 +200,11 @@ void Engine::runBatch(int set, int n, const std::function<void(const Step &, boo
 		}
 		q.width = static_cast<int>(fs.inputWidth);
 		q.height = static_cast<int>(fs.inputHeight);
-		q.prev = m_ScenePrev.as<std::uint32_t>();
-		q.state = m_SceneDev.as<SceneState>();
+		q.prev = m_Scene.prev();
+		q.state = m_Scene.state();
 		q.pass = passState;
 		q.dyn = reinterpret_cast<const ScenePassDyn *>(m_ScenePassDyn.device());
-		q.ring = reinterpret_cast<SceneRecord *>(m_SceneRing.device());
+		q.ring = m_Scene.ring();
 		q.resetMode = scene == 2;
 		launchScenePass(q, m_Stream);
 	}
@@ -264,11 +264,9 @@ void Engine::passTail(Engine &owner, const PassFrame &f, int stage, void *stateO
 void Engine::blendMask(std::uint8_t *gen, std::ptrdiff_t genStride, const std::uint8_t *src, std::ptrdiff_t srcStride, std::size_t srcW,
     std::size_t srcH, hipStream_t stream) {
 	const FrameSize fs = frameSize();
-	// (a bottom-up mask: from its last row in memory, with the negative stride)
 	launchMaskBlend(gen, genStride, static_cast<int>(fs.outputWidth), static_cast<int>(fs.outputHeight), src, srcStride,
-	    static_cast<int>(srcW), static_cast<int>(srcH),
-	    m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0), m_MaskStride,
-	    static_cast<int>(m_MaskW), static_cast<int>(m_MaskH), stream);
+	    static_cast<int>(srcW), static_cast<int>(srcH), m_Mask.first(), m_Mask.stride(), static_cast<int>(m_Mask.width()),
+	    static_cast<int>(m_Mask.height()), stream);
 }
 
 // A frame may go into a pass when each of its two images is either a device-resident one the kernels can read / write in
@@ -283,7 +281,7 @@ bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out, bool group) c
 	if (sourceStage() && !stage) return false;
 	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
 	// unless the pass carries the detector and applies the cuts itself: setSceneLookahead; a group pass: setSceneGroup)
-	if (m_SceneMode != 0 && !(group ? m_SceneGroup : m_SceneLookahead)) return false;
+	if (m_Scene.mode() != 0 && !(group ? m_SceneGroup : m_SceneLookahead)) return false;
 	std::size_t inW, inH, outW, outH;
 	passSizes(stage, &inW, &inH, &outW, &outH);
 	// scaled: the side's device image is read / written by a scale kernel, which takes any alignment and signed stride
@@ -357,7 +355,7 @@ void Engine::setStageGroup(int on) {
 // plain->out (top-down BGRX rows both), whatever the planes' location: f->in / f->out hold the planes those conversion
 // launches read / write.  Device planes: the caller's, in place.  Host planes: plain->yuvIn / plain->yuvOut, plane
 // after plane with rows padded to stagePitch and in the caller's MEMORY order, so a bottom-up plane is addressed from
-// its last row with a negative pitch -- the layout of stageInYuv / stageOutYuv.
+// its last row with a negative pitch -- the layout of decodePlanes / stageOutYuv.
 //
 // A staged frame (stage != 0): a side under one of the owner's scalers is bound at the size set there, to the owner's
 // slots (`staged`) in place of the plain ones, and lands in f->ends: the source-size rows the decode / upload fills and
@@ -472,7 +470,7 @@ Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::si
 
 // Every host input of the pass into its device buffer, rows in MEMORY order (the binding carries the orientation), on the
 // engine's stream in front of the pass's launches.  Pageable memory: the runtime stages or page-locks per call, as in
-// stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in stageInYuv.
+// stageIn; 0.52 MB per BGRX frame, 0.19 MB per 4:2:0 frame -- plane by plane, as in decodePlanes.
 void Engine::uploadPassInputs(const AnyFrame *in, int n) {
 	for (int i = 0; i < n; ++i) {
 		const PassFrame &f = m_Pass[i];
@@ -592,10 +590,11 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 		// what a captured pass cannot bake in: the detector's kernel reads it from host-mapped memory.  Passes are
 		// synchronous, so no launch that reads the block is in flight while it is written.
 		auto *dyn = reinterpret_cast<volatile ScenePassDyn *>(m_ScenePassDyn.host());
-		dyn->stepBase = m_SceneSteps;
-		dyn->seen = static_cast<unsigned>(std::min<std::uint64_t>(m_SceneSeen, 2));
-		dyn->thresholdMilli = m_SceneThreshold;
-		dyn->slot = static_cast<unsigned>(m_SceneSteps % kSceneRing);
+		const SceneClock &clock = m_Scene.clock();
+		dyn->stepBase = clock.steps;
+		dyn->seen = clock.memory();
+		dyn->thresholdMilli = m_Scene.threshold();
+		dyn->slot = static_cast<unsigned>(clock.slot());
 		std::atomic_thread_fence(std::memory_order_seq_cst);
 	}
 	{
@@ -623,8 +622,7 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	}
 	m_Idx = set ^ 1;
 	if (scene) {  // n detector steps, taken by the pass's one launch
-		m_SceneSeen += static_cast<std::uint64_t>(n);
-		m_SceneSteps += static_cast<std::uint64_t>(n);
+		m_Scene.advance(static_cast<std::uint64_t>(n));
 		m_SceneRuns += static_cast<std::uint64_t>(n);
 		m_ScenePassFrames += static_cast<std::uint64_t>(n);
 	}
@@ -686,7 +684,7 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 		}
 		const int set = m_Idx;
 		const int scene = scenePass();
-		const std::uint64_t firstStep = m_SceneSteps;
+		const std::uint64_t firstStep = m_Scene.clock().steps;
 		submitBatch(in + i, out + i, n);
 		drainPassOutputs(out + i, n);  // host frames: each copied out while the next one runs
 		m_Stream.synchronizeSpin(m_SpinUs);
@@ -703,8 +701,7 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 					m_SceneRerun = true;
 					// the restart at a cut, as the per-frame detector does it: what this frame is about to read as its
 					// recurrent inputs is zero in front of exactly the frames whose record says so (the stream has drained)
-					const auto *ring = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host());
-					if (scene == 2 && ring[(firstStep + static_cast<std::uint64_t>(k)) % kSceneRing].cut) {
+					if (scene == 2 && m_Scene.cutAt(firstStep + static_cast<std::uint64_t>(k))) {
 						m_State[m_Idx].zeroAsync(m_Stream);
 						m_Packed[m_Idx].zeroAsync(m_Stream);
 					}
@@ -913,17 +910,17 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 	bool anyDetects = false, anyRestarts = false;
 	for (int i = 0; i < n; ++i) {
 		Engine &e = *m[i];
-		detects[i] = e.m_SceneMode != 0;
+		detects[i] = e.m_Scene.mode() != 0;
 		if (!detects[i]) continue;
 		anyDetects = true;
 		// (a flow-free model has no recurrent input to clear: JU_SCENE_RESET reports)
-		const bool restarts = e.m_SceneMode == 2 && e.m_Config.recurrent();
+		const bool restarts = e.m_Scene.mode() == 2 && e.m_Config.recurrent();
 		anyRestarts = anyRestarts || restarts;
 		auto *dyn = reinterpret_cast<volatile SceneGroupDyn *>(e.m_SceneGroupDyn.host());
-		const unsigned long long hasPrev = (e.m_SceneSeen >= 1 ? 1u : 0u) | (e.m_SceneSeen >= 2 ? 2u : 0u);
-		dyn->step = e.m_SceneSteps;
-		dyn->slotHasPrev = (e.m_SceneSteps % kSceneRing) | (hasPrev << 32);
-		dyn->thresholdMode = static_cast<unsigned long long>(e.m_SceneThreshold) | (static_cast<unsigned long long>(restarts ? 2 : 1) << 32);
+		const SceneClock &clock = e.m_Scene.clock();
+		dyn->step = clock.steps;
+		dyn->slotHasPrev = static_cast<unsigned long long>(clock.slot()) | (static_cast<unsigned long long>(clock.hasPrev()) << 32);
+		dyn->thresholdMode = static_cast<unsigned long long>(e.m_Scene.threshold()) | (static_cast<unsigned long long>(restarts ? 2 : 1) << 32);
 	}
 	if (anyDetects) std::atomic_thread_fence(std::memory_order_seq_cst);
 	// 1. work a member has pending on its own stream (ju_enqueue) runs first
@@ -997,11 +994,11 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 				SceneGroupItem &it = q.item[i];
 				it.frame = L.m_Pass[i].io.in;
 				it.stride = L.m_Pass[i].io.inStride;
-				it.prev = e.m_ScenePrev.as<std::uint32_t>();
-				it.state = e.m_SceneDev.as<SceneState>();
-				it.ring = reinterpret_cast<SceneRecord *>(e.m_SceneRing.device());
+				it.prev = e.m_Scene.prev();
+				it.state = e.m_Scene.state();
+				it.ring = e.m_Scene.ring();
 				it.dyn = reinterpret_cast<const SceneGroupDyn *>(e.m_SceneGroupDyn.device());
-				if (e.m_SceneMode == 2 && recurrent) {
+				if (e.m_Scene.mode() == 2 && recurrent) {
 					clears[i] = SceneClearItem{&it.state->resetNow, e.m_State[sets[i]].get(), e.m_State[sets[i]].bytes(),
 					    e.m_Packed[sets[i]].get(), e.m_Packed[sets[i]].bytes()};
 				}
@@ -1010,8 +1007,7 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 			if (anyRestarts) launchSceneClearItems(clears, n, L.m_Stream);
 			for (int i = 0; i < n; ++i) {  // one detector step per detecting member, taken by the pass's one launch
 				if (!detects[i]) continue;
-				++m[i]->m_SceneSeen;
-				++m[i]->m_SceneSteps;
+				m[i]->m_Scene.advance();
 				++m[i]->m_SceneRuns;
 				++m[i]->m_SceneGroupFrames;
 			}

@@ -1,6 +1,7 @@
 #include "frame_io.h"
 
 #include <cstring>
+#include <stdexcept>
 
 namespace ju {
 
@@ -51,6 +52,71 @@ void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream
 			copyRows(host.lowest, host.pitch, staged, pitch, p.rowBytes, p.rows, hipMemcpyDeviceToHost, stream);
 		}
 	}
+}
+
+bool readsInPlace(const AnyFrame &in, bool aligned) {
+	if (in.yuv || in.bgrx.location != Location::Device) return false;
+	return !aligned || (reinterpret_cast<std::uintptr_t>(in.bgrx.ptr) % 4 == 0 && in.bgrx.stride % 4 == 0);
+}
+
+std::size_t hostPlaneBytes(const AnyFrame &in) {
+	const YuvFrame &y = in.planes;
+	if (!in.yuv || y.location == Location::Device) return 0;
+	return stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes;
+}
+
+void decodePlanes(const YuvFrame &in, std::uint8_t *planeStage, std::uint8_t *bgrx, hipStream_t stream) {
+	const bool host = in.location != Location::Device;
+	if (host) copyPlanes(in, planeStage, true, stream);
+	const YuvPlanes pl = host ? stagedPlanes(in, planeStage) : callerPlanes(in);
+	launchDecodeFrame(fmt(in.format), in.colorspace, pl, bgrx, static_cast<std::ptrdiff_t>(in.width * 4), static_cast<int>(in.width),
+	    static_cast<int>(in.height), stream);
+}
+
+BgrxRows stageInBgrx(const AnyFrame &in, std::size_t width, std::size_t height, std::uint8_t *stage, std::uint8_t *planeStage,
+    bool aligned, hipStream_t stream) {
+	const std::size_t rowBytes = width * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	if (in.yuv) {
+		decodePlanes(in.planes, planeStage, stage, stream);
+		return {stage, plain};
+	}
+	const Frame &b = in.bgrx;
+	if (readsInPlace(in, aligned)) return {static_cast<const std::uint8_t *>(b.ptr), b.stride};
+	const RowSpan rows = rowSpan(b.ptr, b.stride, height);
+	copyRows(stage, rowBytes, rows.lowest, rows.pitch, rowBytes, height,
+	    b.location == Location::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream);
+	if (rows.topDown) return {stage, plain};
+	return {stage + static_cast<std::ptrdiff_t>(height - 1) * plain, -plain};
+}
+
+SourceMask SourceMask::copyOf(const Frame &mask, const char *who) {
+	const std::size_t rowBytes = mask.width * 4;
+	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
+	if (mask.stride > -plain && mask.stride < plain) throw std::invalid_argument(std::string(who) + ": |stride| smaller than a row");
+	SourceMask m;
+	m.m_Rows = DeviceBuffer(rowBytes * mask.height);
+	const RowSpan rows = rowSpan(mask.ptr, mask.stride, mask.height);
+	copyRows(m.m_Rows.get(), rowBytes, rows.lowest, rows.pitch, rowBytes, mask.height,
+	    mask.location == Location::Host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, nullptr);
+	JU_HIP(hipStreamSynchronize(nullptr));
+	m.m_Width = mask.width;
+	m.m_Height = mask.height;
+	m.m_Stride = rows.topDown ? plain : -plain;
+	return m;
+}
+
+const std::uint8_t *SourceMask::first() const {
+	// (a bottom-up mask: its last row in memory, read with the negative stride)
+	return m_Rows.as<std::uint8_t>() + (m_Stride < 0 ? static_cast<std::ptrdiff_t>(m_Height - 1) * -m_Stride : 0);
+}
+
+MaskBox SourceMask::box(const Frame &from, std::size_t outW, std::size_t outH) const {
+	const int w = static_cast<int>(m_Width), h = static_cast<int>(m_Height), ow = static_cast<int>(outW), oh = static_cast<int>(outH);
+	if (from.location == Location::Host) return maskBox(static_cast<const std::uint8_t *>(from.ptr), from.stride, w, h, ow, oh);
+	std::vector<std::uint8_t> back(m_Rows.bytes());
+	JU_HIP(hipMemcpy(back.data(), m_Rows.get(), back.size(), hipMemcpyDeviceToHost));
+	return maskBox(back.data() + (first() - m_Rows.as<std::uint8_t>()), m_Stride, w, h, ow, oh);
 }
 
 namespace {

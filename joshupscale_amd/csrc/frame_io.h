@@ -1,6 +1,7 @@
 // Frames at the engine's boundary and the host-side pieces every way in and out shares: the frame descriptors, the one
-// row copy, the planes of a YUV frame as the conversion kernels take them, and the scaler of the source and output
-// stages.  The arithmetic itself is frame_geometry.h.
+// row copy, the planes of a YUV frame as the conversion kernels take them, the stage-in of a source frame as BGRX rows,
+// the source mask's device copy, and the scaler of the source and output stages.  The arithmetic itself is
+// frame_geometry.h.
 #pragma once
 
 #include <cstddef>
@@ -11,6 +12,7 @@
 #include "frame_geometry.h"
 #include "hip_util.h"
 #include "kernels.h"
+#include "mask_box.h"
 
 namespace ju {
 
@@ -88,6 +90,48 @@ YuvPlanes callerPlanes(const YuvFrame &f);
 YuvPlanes stagedPlanes(const YuvFrame &f, std::uint8_t *stage);
 // The pageable copies between a host frame's planes and that staging layout, plane by plane on `stream`
 void copyPlanes(const YuvFrame &f, std::uint8_t *stage, bool toDevice, hipStream_t stream);
+
+// A source frame as BGRX rows on the device: the first logical row and the signed stride, as the kernels read them.
+struct BgrxRows {
+	const std::uint8_t *ptr = nullptr;
+	std::ptrdiff_t stride = 0;
+};
+// Whether stageInBgrx reads `in` where it is: a device BGRX image -- aligned: only on the kernels' 4-byte alignment.
+bool readsInPlace(const AnyFrame &in, bool aligned);
+// The bytes of the staging layout stageInBgrx needs for `in`: a host frame's planes; 0 for every other frame.
+std::size_t hostPlaneBytes(const AnyFrame &in);
+// One decode launch on `stream`: the planes of `in` (host planes through `planeStage` first) -> dense BGRX rows at `bgrx`.
+void decodePlanes(const YuvFrame &in, std::uint8_t *planeStage, std::uint8_t *bgrx, hipStream_t stream);
+// THE stage-in of a source frame: `in`, checked to be width x height, as BGRX rows on the device, enqueued on `stream`.
+// A device image is read in place (readsInPlace); any other image is copied to `stage` in its memory order, so a
+// bottom-up image stays bottom-up and is read through a negative stride; planes are decoded into `stage` (decodePlanes).
+// stage: 4 width height bytes, unused for a frame read in place; planeStage: hostPlaneBytes(in).  Allocates nothing.
+BgrxRows stageInBgrx(const AnyFrame &in, std::size_t width, std::size_t height, std::uint8_t *stage, std::uint8_t *planeStage,
+    bool aligned, hipStream_t stream);
+
+// The source mask of a runtime (docs/source_stage.md; docs/tiled.md "A mask"): a BGRX image in device memory, in the
+// caller's row order -- a bottom-up mask stays bottom-up and is read through a negative stride.  Empty: no mask.
+class SourceMask {
+public:
+	// The copy of `mask` -- host or device memory, its size and pointer already checked by the owner -- made on the null
+	// stream and waited for, as a blocking copy is: behind what the caller's own default-stream work wrote.
+	// std::invalid_argument "<who>: |stride| smaller than a row" before anything is allocated.  The owner waits for its own
+	// stream before it moves the copy into place.
+	static SourceMask copyOf(const Frame &mask, const char *who);
+	bool on() const { return m_Width != 0; }
+	std::size_t width() const { return m_Width; }
+	std::size_t height() const { return m_Height; }
+	std::ptrdiff_t stride() const { return m_Stride; }  // (negative: bottom-up)
+	const std::uint8_t *first() const;                  // texel (0, 0)
+	// maskBox of this copy of `from` over a blended frame of outW x outH, from host memory: the caller's own rows, or the
+	// copy read back once (set time, not the frame path)
+	MaskBox box(const Frame &from, std::size_t outW, std::size_t outH) const;
+
+private:
+	DeviceBuffer m_Rows;
+	std::size_t m_Width = 0, m_Height = 0;
+	std::ptrdiff_t m_Stride = 0;
+};
 
 // The scaler of the source and the output stage (source_kernels.hip; docs/source_stage.md, docs/output_stage.md): both
 // axes' tables on the device -- one buffer per axis, the start indices, then the taps -- and what the launches need

@@ -83,21 +83,13 @@ double TiledRuntime::stat(const std::string &key) const {
 	if (key == "pass_frames") return static_cast<double>(m_PassFrames);
 	if (key == "pass_split_launches") return static_cast<double>(m_PassSplitLaunches);
 	if (key == "pass_overlapped_copies") return static_cast<double>(m_PassOverlappedCopies);
-	if (key == "scene_mode") return m_SceneMode;
-	if (key == "scene_frames" || key == "scene_cuts") {
-		// (the totals behind the ring: the calls are synchronous, so the last decision is in them)
-		const bool frames = key == "scene_frames";
-		std::uint64_t v = frames ? m_SceneFramesBase : m_SceneCutsBase;
-		if (m_SceneRing.host()) {
-			const auto *totals = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host()) + kSceneRing;
-			v += frames ? totals->step : totals->sad;
-		}
-		return static_cast<double>(v);
-	}
+	if (key == "scene_mode") return m_Scene.mode();
+	// (the totals behind the ring: the calls are synchronous, so the last decision is in them)
+	if (key == "scene_frames" || key == "scene_cuts") return static_cast<double>(m_Scene.total(key == "scene_cuts"));
 	if (key == "output_scaled") return m_OutScale.set() ? 1.0 : 0.0;
 	if (key == "output_filter") return m_OutScale.filter();
 	if (key == "output_scaled_frames") return static_cast<double>(m_OutputScaledFrames);
-	if (key == "source_mask") return m_MaskW != 0 ? 1.0 : 0.0;
+	if (key == "source_mask") return m_Mask.on() ? 1.0 : 0.0;
 	if (key == "source_mask_frames") return static_cast<double>(m_MaskFrames);
 	if (key == "mask_box_x0") return m_MaskBox.x0;
 	if (key == "mask_box_y0") return m_MaskBox.y0;
@@ -113,67 +105,34 @@ double TiledRuntime::stat(const std::string &key) const {
 
 void TiledRuntime::reset() {
 	for (const auto &e : m_Engines) e->reset();
-	m_SceneSeen = 0;  // the scene detector has no predecessor after a reset; its setting and its step count stay
+	m_Scene.restart();  // the scene detector has no predecessor after a reset; its setting and its step count stay
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Scene detector (docs/tiled.md "Scene cuts"): Engine::setSceneDetect's rules on the tiled object's own memory.
+// Scene detector (docs/tiled.md "Scene cuts"): the engine's detector (scene_detector.h) on the source-size frame.
 // ---------------------------------------------------------------------------------------------------------------
 void TiledRuntime::setSceneDetect(int mode, std::uint32_t thresholdMilli) {
 	const std::string problem = sceneDetectProblem(mode, thresholdMilli);
 	if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_scene_detect: " + problem);
 	DeviceGuard g(m_Device);
 	m_Stream->synchronize();
-	if (mode == m_SceneMode) {  // the same mode: the threshold alone; the detector's memory stays
-		if (mode != 0) m_SceneThreshold = thresholdMilli;
-		return;
-	}
-	if (m_SceneRing.host()) {  // the counters of the period that ends here
-		const auto *totals = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host()) + kSceneRing;
-		m_SceneFramesBase += totals->step;
-		m_SceneCutsBase += totals->sad;
-	}
-	// a start: fresh (zeroed) memory, no predecessor, step 0
-	m_ScenePrev = DeviceBuffer();
-	m_SceneDev = DeviceBuffer();
-	m_SceneRing = PinnedWords();
-	m_SceneClear = PinnedWords();
-	if (mode != 0) {
-		m_ScenePrev = DeviceBuffer(m_SrcW * m_SrcH * 4);
-		m_SceneDev = DeviceBuffer(sizeof(SceneState));
-		m_SceneRing = PinnedWords(sizeof(SceneRecord) * (kSceneRing + 1));
-		// (a flow-free model has no recurrent input to clear: JU_SCENE_RESET reports)
-		if (mode == 2 && m_Recurrent) m_SceneClear = PinnedWords(sizeof(SceneClearTile) * kTileMax);
-	}
-	m_SceneMode = mode;
-	m_SceneThreshold = mode != 0 ? thresholdMilli : 0;
-	m_SceneSeen = 0;
-	m_SceneSteps = 0;
+	// the clear's table goes and comes with the detector's memory, at a mode change
+	// (a flow-free model has no recurrent input to clear: JU_SCENE_RESET reports)
+	PinnedWords clear;
+	if (mode != m_Scene.mode() && mode == 2 && m_Recurrent) clear = PinnedWords(sizeof(SceneClearTile) * kTileMax);
+	if (m_Scene.configure(mode, thresholdMilli, m_SrcW * m_SrcH * 4)) m_SceneClear = std::move(clear);
 }
 
 void TiledRuntime::sceneDetect(int *mode, std::uint32_t *thresholdMilli) const {
-	if (mode) *mode = m_SceneMode;
-	if (thresholdMilli) *thresholdMilli = m_SceneThreshold;
+	if (mode) *mode = m_Scene.mode();
+	if (thresholdMilli) *thresholdMilli = m_Scene.threshold();
 }
 
 int TiledRuntime::sceneInfo(SceneRecord *out, int count) {
 	if (count < 0 || (count > 0 && out == nullptr)) throw std::invalid_argument("ju_tiled_get_scene_info: NULL records or a negative count");
 	DeviceGuard g(m_Device);
 	m_Stream->synchronize();
-	if (m_SceneMode == 0 || m_SceneRing.host() == nullptr) return 0;
-	const std::uint64_t have = std::min<std::uint64_t>(m_SceneSteps, kSceneRing);
-	const int n = static_cast<int>(std::min<std::uint64_t>(have, static_cast<std::uint64_t>(count)));
-	const auto *ring = reinterpret_cast<const volatile SceneRecord *>(m_SceneRing.host());
-	for (int k = 0; k < n; ++k) {
-		const std::uint64_t step = m_SceneSteps - static_cast<std::uint64_t>(n) + static_cast<std::uint64_t>(k);
-		const volatile SceneRecord &r = ring[step % kSceneRing];
-		out[k].step = r.step;
-		out[k].sad = r.sad;
-		out[k].score = r.score;
-		out[k].cut = r.cut;
-		out[k].reserved = 0;
-	}
-	return n;
+	return m_Scene.records(out, count);
 }
 
 // The source into the tiles' inputs.  Detector off: the split alone, as ever.  On: ONE launch splits and takes the
@@ -183,20 +142,14 @@ int TiledRuntime::sceneInfo(SceneRecord *out, int count) {
 // The host reads no decision.  A group pass that has to be run again (a resident-tower report) needs nothing new: the
 // members have no detector of their own, and the pass wrote the OTHER halves only, so the cleared inputs are still in place.
 // `into`: the tile inputs to fill -- m_In, or inside a look-ahead pass the frame's slot of m_PassIn.
-void TiledRuntime::splitIn(const Rows &src, const TileSet &into) {
+void TiledRuntime::splitIn(const BgrxRows &src, const TileSet &into) {
 	const int n = tiles();
-	if (m_SceneMode == 0) {
+	if (m_Scene.mode() == 0) {
 		return launchTileSplit(src.ptr, src.stride, into, n, static_cast<int>(m_TileW), static_cast<int>(m_TileH), *m_Stream);
 	}
 	SceneSadLaunch q;
-	q.prev = m_ScenePrev.as<std::uint32_t>();
-	q.state = m_SceneDev.as<SceneState>();
-	q.ring = reinterpret_cast<SceneRecord *>(m_SceneRing.device());
-	q.slot = static_cast<int>(m_SceneSteps % kSceneRing);
-	q.step = m_SceneSteps;
-	q.hasPrev = (m_SceneSeen >= 1 ? 1 : 0) | (m_SceneSeen >= 2 ? 2 : 0);
-	q.thresholdMilli = m_SceneThreshold;
-	q.resetMode = m_SceneMode == 2 && m_Recurrent;
+	m_Scene.fill(q);
+	q.resetMode = m_Scene.mode() == 2 && m_Recurrent;
 	launchTileSplitScene(src.ptr, src.stride, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), into, m_Own, n,
 	    static_cast<int>(m_TileW), static_cast<int>(m_TileH), q, *m_Stream);
 	if (q.resetMode) {
@@ -206,8 +159,7 @@ void TiledRuntime::splitIn(const Rows &src, const TileSet &into) {
 		launchSceneClearTiles(&q.state->resetNow, items, n, reinterpret_cast<volatile SceneClearTile *>(m_SceneClear.host()),
 		    reinterpret_cast<const SceneClearTile *>(m_SceneClear.device()), *m_Stream);
 	}
-	++m_SceneSeen;
-	++m_SceneSteps;
+	m_Scene.advance();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -243,15 +195,14 @@ void TiledRuntime::outputSize(std::size_t *width, std::size_t *height) const {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// A source mask (docs/tiled.md "A mask"): Engine::setSourceMask's copy and refusals; the box is computed here, once.
+// A source mask (docs/tiled.md "A mask"): the engine's holder and copy (frame_io.h SourceMask), refused in this object's
+// own order and words; the box is computed here, once.
 // ---------------------------------------------------------------------------------------------------------------
 void TiledRuntime::setSourceMask(const Frame *mask) {
 	DeviceGuard g(m_Device);
 	if (mask == nullptr) {
 		m_Stream->synchronize();
-		m_Mask = DeviceBuffer();
-		m_MaskW = m_MaskH = 0;
-		m_MaskStride = 0;
+		m_Mask = SourceMask();
 		m_MaskBox = MaskBox();
 		return;
 	}
@@ -262,36 +213,10 @@ void TiledRuntime::setSourceMask(const Frame *mask) {
 	const std::string problem = maskSizeProblem(mask->width, mask->height, bw, bh);
 	if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_source_mask: " + problem);
 	if (mask->ptr == nullptr) throw std::invalid_argument("ju_tiled_set_source_mask: NULL mask image");
-	const std::size_t rowBytes = mask->width * 4;
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	if (mask->stride > -plain && mask->stride < plain) {
-		throw std::invalid_argument("ju_tiled_set_source_mask: |stride| smaller than a row");
-	}
-	// copied once, in the caller's memory order (a bottom-up mask stays bottom-up and is read with a negative stride)
-	DeviceBuffer buf(rowBytes * mask->height);
-	const RowSpan rows = rowSpan(mask->ptr, mask->stride, mask->height);
-	const bool host = mask->location == Location::Host;
-	copyRows(buf.get(), rowBytes, rows.lowest, rows.pitch, rowBytes, mask->height, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
-	    nullptr);
-	// (on the null stream and waited for, as a blocking copy is: behind what the caller's own default-stream work wrote)
-	JU_HIP(hipStreamSynchronize(nullptr));
-	// the box, from host memory: the caller's own rows, or the copy read back once (set time, not the frame path)
-	MaskBox box;
-	if (host) {
-		box = maskBox(static_cast<const std::uint8_t *>(mask->ptr), mask->stride, static_cast<int>(mask->width), static_cast<int>(mask->height),
-		    static_cast<int>(bw), static_cast<int>(bh));
-	} else {
-		std::vector<std::uint8_t> back(rowBytes * mask->height);
-		JU_HIP(hipMemcpy(back.data(), buf.get(), back.size(), hipMemcpyDeviceToHost));
-		const std::uint8_t *first = rows.topDown ? back.data() : back.data() + (mask->height - 1) * rowBytes;
-		box = maskBox(first, rows.topDown ? plain : -plain, static_cast<int>(mask->width), static_cast<int>(mask->height), static_cast<int>(bw),
-		    static_cast<int>(bh));
-	}
+	SourceMask copy = SourceMask::copyOf(*mask, "ju_tiled_set_source_mask");  // (copied once, now)
+	const MaskBox box = copy.box(*mask, bw, bh);
 	m_Stream->synchronize();
-	m_Mask = std::move(buf);
-	m_MaskW = mask->width;
-	m_MaskH = mask->height;
-	m_MaskStride = rows.topDown ? plain : -plain;
+	m_Mask = std::move(copy);
 	m_MaskBox = box;
 }
 
@@ -325,39 +250,17 @@ DeviceBuffer &TiledRuntime::lazy(DeviceBuffer &b, std::size_t bytes) {
 	return b;
 }
 
-TiledRuntime::Rows TiledRuntime::stageIn(const AnyFrame &in, DeviceBuffer &srcStage, DeviceBuffer &yuvStage) {
-	const std::size_t rowBytes = m_SrcW * 4;
-	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
-	if (in.yuv) {  // the existing decode at source size; host planes through their staging layout first
-		const YuvFrame &y = in.planes;
-		auto *stage = lazy(srcStage, rowBytes * m_SrcH).as<std::uint8_t>();
-		YuvPlanes planes = callerPlanes(y);
-		if (y.location == Location::Host) {
-			auto *yuv = lazy(yuvStage, stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>();
-			copyPlanes(y, yuv, true, *m_Stream);
-			planes = stagedPlanes(y, yuv);
-		}
-		launchDecodeFrame(fmt(y.format), y.colorspace, planes, stage, plain, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), *m_Stream);
-		return {stage, plain};
-	}
-	const Frame &b = in.bgrx;
-	const bool device = b.location == Location::Device;
-	if (device && reinterpret_cast<std::uintptr_t>(b.ptr) % 4 == 0 && b.stride % 4 == 0) {
-		return {static_cast<std::uint8_t *>(b.ptr), b.stride};
-	}
-	// a host image, or a device image off the kernel's alignment: copied in its memory order, so a bottom-up image stays
-	// bottom-up and is read with a negative stride
-	auto *stage = lazy(srcStage, rowBytes * m_SrcH).as<std::uint8_t>();
-	const RowSpan rows = rowSpan(b.ptr, b.stride, m_SrcH);
-	copyRows(stage, rowBytes, rows.lowest, rows.pitch, rowBytes, m_SrcH, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-	    *m_Stream);
-	if (rows.topDown) return {stage, plain};
-	return {stage + static_cast<std::ptrdiff_t>(m_SrcH - 1) * plain, -plain};
+// a device image on the split kernels' 4-byte alignment where it is; every other source through buffers sized here
+BgrxRows TiledRuntime::stageIn(const AnyFrame &in, DeviceBuffer &srcStage, DeviceBuffer &yuvStage) {
+	auto *stage = readsInPlace(in, true) ? nullptr : lazy(srcStage, m_SrcW * m_SrcH * 4).as<std::uint8_t>();
+	const std::size_t planeBytes = hostPlaneBytes(in);
+	auto *yuv = planeBytes ? lazy(yuvStage, planeBytes).as<std::uint8_t>() : nullptr;
+	return stageInBgrx(in, m_SrcW, m_SrcH, stage, yuv, true, *m_Stream);
 }
 
 bool TiledRuntime::deepFromState(const AnyFrame &out) const {
 	// (a mask: the masked frame exists in 8 bits only, as Engine::deepFromState has it)
-	return out.yuv && m_DeepFromState && m_HbdFromState && m_MaskW == 0 && formatInfo(out.planes.format).deep();
+	return out.yuv && m_DeepFromState && m_HbdFromState && !m_Mask.on() && formatInfo(out.planes.format).deep();
 }
 
 // The 16-bit path: ONE launch blends the states the tiles' last frames left -- the group passes are synchronous, so they
@@ -396,7 +299,7 @@ void TiledRuntime::stitchOutDeep(const YuvFrame &y, int slot, HostCopy *defer) {
 	++m_DeepStateFrames;
 }
 
-void TiledRuntime::stitchOut(const AnyFrame &out, const Rows &src, int slot, HostCopy *defer) {
+void TiledRuntime::stitchOut(const AnyFrame &out, const BgrxRows &src, int slot, HostCopy *defer) {
 	// While an output size is set the frame is ow x oh of it and the blend's launch is the fused one, which forms the
 	// blended frame in registers and writes the scaled one; everything behind the launch -- the staging frame, the copy
 	// out, the encode -- is the same code at that size.  Off: exactly the launches of before.
@@ -408,15 +311,15 @@ void TiledRuntime::stitchOut(const AnyFrame &out, const Rows &src, int slot, Hos
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
 	// A mask whose box is not empty: the two masked launchers in the place of the two below, with the source rows stageIn
 	// returned -- valid until the call returns.  No mask, or a white one: exactly the launches of before.
-	const bool masked = m_MaskW != 0 && !m_MaskBox.empty();
+	const bool masked = m_Mask.on() && !m_MaskBox.empty();
 	TileMask mk;
 	if (masked) {
 		mk.src = src.ptr;
 		mk.srcStride = src.stride;
-		mk.mask = m_Mask.as<std::uint8_t>() + (m_MaskStride < 0 ? static_cast<std::ptrdiff_t>(m_MaskH - 1) * -m_MaskStride : 0);
-		mk.maskStride = m_MaskStride;
-		mk.maskW = static_cast<int>(m_MaskW);
-		mk.maskH = static_cast<int>(m_MaskH);
+		mk.mask = m_Mask.first();
+		mk.maskStride = m_Mask.stride();
+		mk.maskW = static_cast<int>(m_Mask.width());
+		mk.maskH = static_cast<int>(m_Mask.height());
 		mk.x0 = m_MaskBox.x0, mk.y0 = m_MaskBox.y0, mk.x1 = m_MaskBox.x1, mk.y1 = m_MaskBox.y1;
 	}
 	auto stitch = [&](std::uint8_t *dst, std::ptrdiff_t stride) {
@@ -529,7 +432,7 @@ void TiledRuntime::groupPasses(const TileSet &in, const std::function<void(int, 
 void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *who) {
 	checkPair(in, out, who);
 	DeviceGuard guard(m_Device);
-	const Rows src = stageIn(in, m_SrcStage, m_YuvIn);
+	const BgrxRows src = stageIn(in, m_SrcStage, m_YuvIn);
 	splitIn(src, m_In);
 	// the group passes run on their lead's stream: the tiles' inputs (and at a scene cut their cleared recurrent inputs)
 	// are complete before the first of them starts
@@ -538,7 +441,7 @@ void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *
 	stitchOut(out, src);
 	m_Stream->synchronize();
 	++m_Frames;
-	if (m_MaskW != 0) ++m_MaskFrames;
+	if (m_Mask.on()) ++m_MaskFrames;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -614,7 +517,7 @@ void TiledRuntime::runPass(const AnyFrame *in, const AnyFrame *out, int count) {
 	// 1. the sources, all up front on the tiled stream: a device BGRX image on the kernels' alignment where it is, every
 	// other one into its own slot.  (d) The slots, and the rule that inputs hold their pixels, keep the split's source rows
 	// -- which a masked stitch reads again -- valid until stitch f.
-	Rows src[kTilePassMax];
+	BgrxRows src[kTilePassMax];
 	for (int f = 0; f < count; ++f) src[f] = stageIn(in[f], m_PassSrc[static_cast<std::size_t>(f)], m_PassYuvIn[static_cast<std::size_t>(f)]);
 	auto slotOf = [&](int f) {
 		TileSet t = m_PassSet;
@@ -623,7 +526,7 @@ void TiledRuntime::runPass(const AnyFrame *in, const AnyFrame *out, int count) {
 	};
 	// 2. the split: ONE launch for the whole pass while the detector is off (with it on: its decisions are sequential, so
 	// the fused per-frame launch stays, in front of each frame's group passes -- step 3)
-	const bool detects = m_SceneMode != 0;
+	const bool detects = m_Scene.mode() != 0;
 	if (!detects) {
 		TileFrames frames;
 		for (int f = 0; f < count; ++f) {
@@ -671,7 +574,7 @@ void TiledRuntime::runPass(const AnyFrame *in, const AnyFrame *out, int count) {
 		stitchOut(out[f], src[f], f & 1, &copy[f & 1]);
 		m_Stitched[f & 1]->record(*m_Stream);
 		++m_Frames;
-		if (m_MaskW != 0) ++m_MaskFrames;
+		if (m_Mask.on()) ++m_MaskFrames;
 	}
 	// the last frame's copy runs behind the pass
 	const HostCopy &last = copy[(count - 1) & 1];

@@ -101,13 +101,10 @@ public:
 
 private:
 	void check(const AnyFrame &f, bool input, const char *who) const;
-	// the source as 4-byte-aligned BGRX rows on the device: the caller's image where it is, or m_SrcStage
-	struct Rows {
-		std::uint8_t *ptr;
-		std::ptrdiff_t stride;
-	};
-	// (stage, yuv: where a source that is not read in place goes -- m_SrcStage / m_YuvIn, or a pass's slot of each)
-	Rows stageIn(const AnyFrame &in, DeviceBuffer &stage, DeviceBuffer &yuv);
+	// the source as 4-byte-aligned BGRX rows on the device (frame_io.h stageInBgrx): the caller's image where it is, or
+	// `stage`; stage, yuv: where a source that is not read in place goes -- m_SrcStage / m_YuvIn, or a pass's slot of each,
+	// made here when first needed
+	BgrxRows stageIn(const AnyFrame &in, DeviceBuffer &stage, DeviceBuffer &yuv);
 	// A host frame's copy-out, deferred (a pass): what stitchOut left in staging slot `slot` and where it goes
 	struct HostCopy {
 		bool pending = false, yuv = false;
@@ -121,7 +118,7 @@ private:
 	void deferOrCopyPlanes(const YuvFrame &y, std::uint8_t *yuv, HostCopy *defer);
 	// slot: which of the two staging frames per side (0 outside a pass); defer: null = a host frame is copied out on the
 	// tiled stream behind its stitch (process()), else the copy is left to the caller in *defer
-	void stitchOut(const AnyFrame &out, const Rows &src, int slot = 0, HostCopy *defer = nullptr);
+	void stitchOut(const AnyFrame &out, const BgrxRows &src, int slot = 0, HostCopy *defer = nullptr);
 	// a deep format while the setting is on and the tiles' states are their frames in float: the 16-bit path of stitchOut
 	bool deepFromState(const AnyFrame &out) const;
 	void stitchOutDeep(const YuvFrame &y, int slot, HostCopy *defer);
@@ -168,27 +165,19 @@ private:
 	// took a fused kernel.  m_OutStage, m_Out16 and m_YuvOut are then of the output size.
 	Scaler m_OutScale;
 	std::uint64_t m_OutputScaledFrames = 0;
-	// the source mask in device memory, in the caller's row order (m_MaskStride < 0: bottom-up; m_MaskW == 0: none), its
-	// box in blended coordinates and the frames processed while one was set
-	DeviceBuffer m_Mask;
-	std::size_t m_MaskW = 0, m_MaskH = 0;
-	std::ptrdiff_t m_MaskStride = 0;
+	// the source mask's device copy (frame_io.h SourceMask), its box in blended coordinates and the frames processed while
+	// one was set
+	SourceMask m_Mask;
 	MaskBox m_MaskBox;
 	std::uint64_t m_MaskFrames = 0;
-	// The scene detector, made when the mode is turned on: m_ScenePrev the kept source-size frame (4 Ws Hs bytes), m_SceneDev
-	// the SceneState, m_SceneRing kSceneRing records + the totals (host-mapped), m_SceneClear the clear's table of kTileMax
-	// SceneClearTile (host-mapped; RESET on a recurrent model only).  m_Own: what each tile counts (tileOwnedEnds).
-	// m_SceneSeen: steps since the last start (the "has predecessor" bits); m_SceneSteps: steps since the mode was turned on
-	// (the record's `step`, the ring slot).
-	void splitIn(const Rows &src, const TileSet &into);
+	// The scene detector: m_Scene the setting, the memory on the source-size frame (the kept frame: 4 Ws Hs bytes) and the
+	// clock (scene_detector.h); m_SceneClear the clear's table of kTileMax SceneClearTile (host-mapped; RESET on a recurrent
+	// model only), re-made with the detector's memory.  m_Own: what each tile counts (tileOwnedEnds).
+	void splitIn(const BgrxRows &src, const TileSet &into);
 	bool m_Recurrent = true;
-	int m_SceneMode = 0;
-	std::uint32_t m_SceneThreshold = 0;
+	SceneDetector m_Scene;
 	TileOwn m_Own;
-	DeviceBuffer m_ScenePrev, m_SceneDev;
-	PinnedWords m_SceneRing, m_SceneClear;
-	std::uint64_t m_SceneSeen = 0, m_SceneSteps = 0;
-	std::uint64_t m_SceneFramesBase = 0, m_SceneCutsBase = 0;  // "scene_frames" / "scene_cuts" of earlier on-periods
+	PinnedWords m_SceneClear;
 };
 
 }  // namespace ju

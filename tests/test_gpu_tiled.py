@@ -214,6 +214,25 @@ def test_host_frames_give_the_bytes_of_the_device_route(flip):
             assert np.array_equal(got, want[t]), t
 
 
+def test_a_device_source_off_the_kernels_alignment_gives_the_aligned_bytes():
+    """80 x 30 (two tiles): a device BGRX source 1 byte off the split kernel's 4-byte alignment is not read in place but
+    copied, device to device, into the staging frame first -- the bytes of the aligned call."""
+    torch, dev = torch_dev()
+    clip = M.synthetic_frames(3, 30, 80, seed=9, kind="smooth")
+    with R.TiledRuntime(small_blob(), 0, R.DTYPE_F16, 80, 30, 4) as tr:
+        assert tr.stat("tiles") == 2
+        want = [device_run(tr, frame) for frame in clip]
+        tr.reset()
+        for t, frame in enumerate(clip):
+            raw = torch.full((frame.size + 64,), 0xEE, dtype=torch.uint8, device=dev)
+            raw[1:1 + frame.size] = torch.from_numpy(np.ascontiguousarray(frame).reshape(-1)).to(dev)
+            d_out = torch.zeros((120, 320, 4), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            assert (raw.data_ptr() + 1) % 4 == 1
+            tr.process(R.JuImage(raw.data_ptr() + 1, R.LOC_DEVICE, 320, 80, 30), R.JuImage(d_out.data_ptr(), R.LOC_DEVICE, 1280, 320, 120))
+            assert np.array_equal(d_out.cpu().numpy(), want[t]), t
+
+
 def test_nv12_in_and_out():
     """96 x 64 NV12 (3 x 3 tiles): the reference's decode, the tiled route on the decoded frames, the reference's encode."""
     cs = R.CS_BT709_LIMITED
