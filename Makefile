@@ -9,7 +9,7 @@ OBJ        := build/obj
 CXXFLAGS   := -O3 -std=c++17 -fPIC -fvisibility=hidden -Iinclude -I$(CSRC) -Wall -Wextra \
               -Wno-unused-parameter
 HIPFLAGS   := --offload-arch=$(ARCH) $(CXXFLAGS)
-SRCS_CPP   := model.cpp engine.cpp engine_frames.cpp engine_passes.cpp frame_io.cpp c_api.cpp core_api.cpp log.cpp comm.cpp graphics.cpp dev_switch.cpp tiled.cpp
+SRCS_CPP   := model.cpp engine.cpp engine_program.cpp engine_frames.cpp engine_passes.cpp frame_io.cpp c_api.cpp core_api.cpp log.cpp comm.cpp graphics.cpp dev_switch.cpp tiled.cpp
 SRCS_HIP   := conv_kernels.hip tower_kernels.hip frame_kernels.hip fp8_kernels.hip flow_kernels.hip res_block_kernels.hip splitk_kernels.hip tower8_kernels.hip colour_kernels.hip source_kernels.hip scene_kernels.hip tile_kernels.hip alpha_kernels.hip
 OBJS       := $(addprefix $(OBJ)/,$(SRCS_CPP:.cpp=.o)) $(addprefix $(OBJ)/,$(SRCS_HIP:.hip=.o))
 

@@ -242,17 +242,49 @@ private:
 		long in, out;
 		ItemStride(int n = 1, long i = 0, long o = 0) : items(n), in(i), out(o) {}
 	};
-	void addConvStep(std::vector<Step> *prog, const std::string &tag, const std::string &wname,
-	    Operand in, Operand res, Operand out, int H, int W, bool relu, bool outHead,
-	    bool tower = false, bool pool = false, bool upsample = false, ItemStride item = ItemStride());
+	// ---- the program builder (engine_program.cpp) ----
+	// what a convolution's launch does besides the convolution; `tower`: conv_tower_kernel on tower-layout operands
+	struct ConvOpt {
+		bool relu = false, outHead = false, tower = false, pool = false, upsample = false;
+		ItemStride item;
+	};
+	void addConvStep(std::vector<Step> *prog, const std::string &tag, const std::string &wname, Operand in, Operand res,
+	    Operand out, int H, int W, const ConvOpt &opt);
 	// group: the launches of a group pass (independent items: processGroup) -- `set` is then unused
 	// cut: the first block takes its history by ScenePassState::cutAt (a pass that restarts the recurrence at scene cuts)
 	void addFlowAutoencoder(std::vector<Step> *prog, int set, int items, bool group = false, bool cut = false);
+	struct FlowBuild;
+	void addFlowBlockStep(FlowBuild &f, const std::string &convA, const std::string &convB, const std::string &outName,
+	    bool pool, bool outHead, int act2);
+	void addPackingFlowBlockStep(FlowBuild &f, FlowBlockLaunch fb, double flops);
+	void addDecoderUpsample(FlowBuild &f, int block);
 	bool flowPacksInBlock() const;
 	Operand operand(const std::string &name);
 	Tensor &addTowerTensor(const std::string &name, int H, int W, int C);
 	void buildWeights(const ModelFile &model);
+	// Writes m_Program[set]: the stages below in this order, over one ProgramBuild.  Sets m_StateBind[set], m_FlowCur and
+	// m_TrunkOut.
 	void buildProgram(int set);
+	struct ProgramBuild;
+	void addInputSteps(ProgramBuild &b);     // lr_pack (flow-free), frame sums, pack
+	void addFlowNetSteps(ProgramBuild &b);   // the auto-encoder, or a flow-resnet body and the head
+	Operand addResidentFlowResnet(ProgramBuild &b);
+	Operand addLayeredFlowResnet(ProgramBuild &b);
+	void addWarpStep(ProgramBuild &b);
+	void addGeneratorHeadSteps(ProgramBuild &b);  // calibration clear, generator/conv_1 where it is a launch
+	void addTowerSteps(ProgramBuild &b);     // one of the four below
+	void addResidentTower8Step(ProgramBuild &b);
+	void addResidentTowerStep(ProgramBuild &b);
+	void addLayeredTower8Steps(ProgramBuild &b);
+	void addLayeredTowerSteps(ProgramBuild &b);
+	void addTailSteps(ProgramBuild &b);      // nothing (in the tower), fused, or split
+	void addTemporalStep(ProgramBuild &b);
+	void addResBlockStep(std::vector<Step> *prog, const std::string &tag, const std::string &block, Operand in, Operand out,
+	    int H, int W, int activation, float slope);
+	void addCalibStep(std::vector<Step> *prog, int layer, const std::string &tensor);
+	struct ResidentTower;
+	ResidentTowerParams residentTowerParams(const ResidentTower &t, int H, int W, int nLayers, int activation, float slope);
+	TailFusedLaunch fusedTail(Operand x, float slope, const unsigned *sums);
 	void stageIn(const Frame &in);
 	// the dense BGRX frame `src` of width x height -> the caller's image; raw: width x height x 4 bytes of scratch (the
 	// flip of a bottom-up host image)
@@ -431,19 +463,32 @@ private:
 	// output_flow variant only: the u8 frame of the generator's writers, which nobody reads (buildProgram)
 	DeviceBuffer m_DiscardFrame;
 	DeviceBuffer m_State[2], m_Packed[2];
-	// resident tower (one launch for all residual-block convolutions)
+	// A resident tower (one launch for all convolutions of a 64-filter stack): the geometry of its regions, its layers'
+	// weights in execution order -- collected on the host while the weights are built (addConv), uploaded by
+	// setUpResidentTower -- the mailbox of its halo exchange and the publish counts per region.
+	struct ResidentTower {
+		int GX = 0, GY = 0, RH = 0;
+		std::vector<std::uint16_t> hostW;
+		std::vector<float> hostB;
+		DeviceBuffer w, b, mail, flags;
+	};
+	// The constructor's phases, in its order (buildWeights and both buildProgram calls between them: engine.cpp).
+	void readSwitches();
+	bool setUpResidentTower(ResidentTower *t, bool wanted, int H, int W, int cus, bool leaky);
+	void setUpResidentTowers();
+	void allocateBuffers(const ModelFile &model);
+	void packResidentTower8();
+	void warmUpAndCapture();
+	void captureFrameGraphs();  // both binding sets' programs against m_IO (nothing executes)
+	void zeroResidentMailboxes();
+	void dropGraphsAndRebuild();
+	struct StepSpec;
 	bool m_Resident = false;
-	int m_ResGX = 0, m_ResGY = 0, m_ResRH = 0;
-	std::vector<std::uint16_t> m_TowerHostW;
-	std::vector<float> m_TowerHostB;
-	DeviceBuffer m_TowerW, m_TowerB, m_ResMail, m_ResFlags;
+	ResidentTower m_GenTower;  // the generator's: conv_1 and the residual blocks
 	// flow-resnet (models.py:257-331) through the same resident kernel: conv_1 + its
 	// residual blocks are a 64-filter tower too
 	bool m_ResidentFlow = false;
-	int m_FlowGX = 0, m_FlowGY = 0, m_FlowRH = 0;
-	std::vector<std::uint16_t> m_FlowTowerHostW;
-	std::vector<float> m_FlowTowerHostB;
-	DeviceBuffer m_FlowTowerW, m_FlowTowerB, m_FlowMail, m_FlowFlags;
+	ResidentTower m_FlowTower;
 	// The resident tower needs every workgroup co-resident.  When a bounded wait expires the
 	// engine drops to the per-block kernels (fallbackToLayers) -- not for good: after
 	// m_RetryAfter clean frames it tries the resident kernel again (the CUs may have been
