@@ -544,8 +544,7 @@ void Engine::fallbackToLayers(unsigned code) {
 	logMessage(LogLevel::Warning, "Engine", ss.str());
 	m_Resident = false;
 	m_ResidentFlow = false;
-	m_DirectGraphs.clear();  // they replay the resident program
-	dropBatchGraphs();
+	dropAllGraphs();  // they replay the resident program
 	zeroResidentMailboxes();  // the aborted launch left the slot epochs of the regions out of step: start them over
 	m_Stream.synchronize();
 	dropGraphsAndRebuild();
@@ -557,13 +556,12 @@ void Engine::fallbackToLayers(unsigned code) {
 		// buffers: it writes scratch tensors and the OUTPUT half of the state ping-pong,
 		// which the caller's re-run overwrites; the other set's program (same kernels,
 		// other pointers) would overwrite the INPUT half the re-run still needs.
-		const FrameIO keep = m_IO;
+		AtExit restore{[this, keep = m_IO] { m_IO = keep; }};
 		bindStaging();
 		for (const Step &st : m_Program[m_Idx]) st.run(m_Stream);
 		m_Stream.synchronize();
 		captureFrameGraphs();
 		m_Stream.synchronize();
-		m_IO = keep;
 	}
 }
 
@@ -588,15 +586,13 @@ void Engine::restoreResident() {
 	m_Resident = true;
 	m_ResidentFlow = m_ResidentFlowCapable;
 	m_CleanFrames = 0;
-	m_DirectGraphs.clear();
-	dropBatchGraphs();
+	dropAllGraphs();
 	zeroResidentMailboxes();
 	dropGraphsAndRebuild();
 	if (m_UseGraph) {  // (the resident kernels ran before: nothing sets an attribute inside the capture)
-		const FrameIO keep = m_IO;
+		AtExit restore{[this, keep = m_IO] { m_IO = keep; }};
 		bindStaging();
 		captureFrameGraphs();
-		m_IO = keep;
 	}
 	m_Stream.synchronize();
 	logMessage(LogLevel::Info, "Engine", "trying the resident tower kernel again");
@@ -639,34 +635,34 @@ bool Engine::directEligible(const Frame &in, const Frame &out) const {
 	       (reinterpret_cast<std::uintptr_t>(out.ptr) % 8 == 0) && out.stride % 8 == 0;
 }
 
-Engine::DirectEntry &Engine::directEntry(const DirectKey &key) {
-	auto it = m_DirectGraphs.find(key);
-	if (it == m_DirectGraphs.end()) {
-		// evict the least recently used tuple nobody registered
-		if (m_DirectGraphs.size() >= kMaxDirectGraphs + 2 * m_RegisteredPairs.size()) {
-			auto victim = m_DirectGraphs.end();
-			for (auto j = m_DirectGraphs.begin(); j != m_DirectGraphs.end(); ++j) {
-				DirectKey pair = j->first;
-				pair.idx = 0;
-				if (m_RegisteredPairs.count(pair)) continue;
-				if (victim == m_DirectGraphs.end() || j->second.lastUse < victim->second.lastUse) victim = j;
-			}
-			if (victim != m_DirectGraphs.end()) m_DirectGraphs.erase(victim);
-		}
-		it = m_DirectGraphs.emplace(key, DirectEntry{}).first;
+void Engine::replayOrRun(CachedGraph &e, bool registered, const std::function<void()> &launches) {
+	// a registered unit whose graph was dropped (fallback / return to the resident kernel) is captured again at once;
+	// an unknown tuple at its second sighting -- a caller that hands over a fresh pointer every frame never pays a
+	// capture, and a pass's first sighting, eager, also sets the dynamic-LDS attribute of a tile height its launch
+	// sizes choose for the first time, which must not happen inside a capture
+	if (!e.graph.valid() && (++e.seen >= 2 || registered)) {
+		e.graph = GraphExec::capture(m_Stream, launches);  // records the launches (nothing executes here) ...
+		++m_InlineCaptures;
 	}
-	return it->second;
+	if (e.graph.valid()) {  // ... and replay
+		e.graph.launch(m_Stream);
+		++m_GraphReplays;
+		return;
+	}
+	launches();
+	++m_EagerRuns;
 }
 
-// Records binding set idx's launches against m_IO (nothing executes).
-void Engine::captureDirect(DirectEntry *e, int idx) {
-	// ONE graph per frame: replaying the first launches as a graph of their own, so that the GPU
-	// starts while the CPU still submits the rest, was measured and lost 0.5-0.8 % (1943-1947 against
-	// 1926-1933 frames/s, tools/submit_overhead.py): hipGraphLaunch already streams its packets, and
-	// the second graph costs a boundary
-	e->graph = GraphExec::capture(m_Stream, [&] {
-		for (const Step &st : m_Program[idx]) st.run(m_Stream);
-	});
+int Engine::prepareGraph(CachedGraph &e, const std::function<void()> &launches) {
+	if (e.graph.valid()) return 0;
+	e.graph = GraphExec::capture(m_Stream, launches);
+	++m_PreparedCaptures;
+	return 1;
+}
+
+void Engine::dropAllGraphs() {
+	m_DirectGraphs.dropGraphs();  // (the registered pairs stay registered)
+	m_BatchGraphs.clear();
 }
 
 int Engine::prepareFrames(const Frame &in, const Frame &out) {
@@ -688,60 +684,28 @@ int Engine::prepareFrames(const Frame &in, const Frame &out) {
 		                            "x" + std::to_string(fs.outputHeight));
 	}
 	if (!directEligible(in, out) || !m_UseGraph || !m_DirectGraph) return 0;  // staged frames: graphs exist already
-	const DirectKey pair{in.ptr, in.stride, out.ptr, out.stride, 0};
-	if (!m_RegisteredPairs.count(pair)) {
-		if (m_RegisteredPairs.size() >= kMaxRegisteredPairs) {
-			// a caller that keeps registering new buffers (and never the old ones again): forget
-			// the pair whose graphs were used least recently, with its graphs
-			auto victim = m_RegisteredPairs.begin();
-			std::uint64_t oldest = ~std::uint64_t(0);
-			for (auto it = m_RegisteredPairs.begin(); it != m_RegisteredPairs.end(); ++it) {
-				std::uint64_t used = 0;
-				for (int idx = 0; idx < 2; ++idx) {
-					DirectKey key = *it;
-					key.idx = idx;
-					auto g = m_DirectGraphs.find(key);
-					if (g != m_DirectGraphs.end()) used = std::max(used, g->second.lastUse);
-				}
-				if (used < oldest) {
-					oldest = used;
-					victim = it;
-				}
-			}
-			for (int idx = 0; idx < 2; ++idx) {
-				DirectKey key = *victim;
-				key.idx = idx;
-				m_DirectGraphs.erase(key);
-			}
-			m_RegisteredPairs.erase(victim);
-		}
-		m_RegisteredPairs.insert(pair);
-	}
+	DirectKey key{in.ptr, in.stride, out.ptr, out.stride, 0};
+	m_DirectGraphs.registerUnit(key);
 	std::unique_lock<std::mutex> chain = chainBegin(m_Resident);  // (no capture while another engine's constructor drains the device)
-	const FrameIO keep = m_IO;
+	AtExit restore{[this, keep = m_IO] { m_IO = keep; }};
 	m_IO.in = static_cast<const std::uint8_t *>(in.ptr);
 	m_IO.inStride = in.stride;
 	m_IO.out = static_cast<std::uint8_t *>(out.ptr);
 	m_IO.outStride = out.stride;
 	int captured = 0;
-	try {
-		for (int idx = 0; idx < 2; ++idx) {
-			DirectKey key = pair;
-			key.idx = idx;
-			DirectEntry &e = directEntry(key);
-			e.lastUse = ++m_DirectClock;
-			if (!e.graph.valid()) {
-				captureDirect(&e, idx);
-				++captured;
-				++m_PreparedCaptures;
-			}
-		}
-	} catch (...) {
-		m_IO = keep;
-		throw;
+	for (key.idx = 0; key.idx < 2; ++key.idx) {
+		captured += prepareGraph(m_DirectGraphs.use(key), [this, idx = key.idx] { runSteps(idx); });
 	}
-	m_IO = keep;
 	return captured;
+}
+
+// Binding set idx's launches against m_IO, in stream order (recorded when m_Stream is capturing).
+// ONE graph per frame: replaying the first launches as a graph of their own, so that the GPU
+// starts while the CPU still submits the rest, was measured and lost 0.5-0.8 % (1943-1947 against
+// 1926-1933 frames/s, tools/submit_overhead.py): hipGraphLaunch already streams its packets, and
+// the second graph costs a boundary
+void Engine::runSteps(int idx) {
+	for (const Step &st : m_Program[idx]) st.run(m_Stream);
 }
 
 void Engine::runProgram() {
@@ -752,26 +716,9 @@ void Engine::runProgram() {
 	}
 	if (m_UseGraph && m_DirectIO && m_DirectGraph) {
 		const DirectKey key{m_IO.in, m_IO.inStride, m_IO.out, m_IO.outStride, m_Idx};
-		DirectEntry &e = directEntry(key);
-		e.lastUse = ++m_DirectClock;
-		if (!e.graph.valid()) {
-			DirectKey pair = key;
-			pair.idx = 0;
-			// a registered pair whose graph was dropped (fallback / return to the resident
-			// kernel) is captured again at once; an unknown tuple at its second sighting --
-			// a caller that hands over a fresh pointer every frame never pays a capture
-			if (++e.seen >= 2 || m_RegisteredPairs.count(pair)) {
-				captureDirect(&e, m_Idx);  // records the launches (nothing executes here) ...
-				++m_InlineCaptures;
-			}
-		}
-		if (e.graph.valid()) {  // ... and replay
-			e.graph.launch(m_Stream);
-			++m_GraphReplays;
-			return;
-		}
+		return replayOrRun(m_DirectGraphs.use(key), m_DirectGraphs.registered(key), [this] { runSteps(m_Idx); });
 	}
-	for (const Step &st : m_Program[m_Idx]) st.run(m_Stream);
+	runSteps(m_Idx);
 	++m_EagerRuns;
 }
 
@@ -1087,7 +1034,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "eager_runs") return static_cast<double>(m_EagerRuns);
 	if (key == "graph_captures") return static_cast<double>(m_InlineCaptures);
 	if (key == "prepared_captures") return static_cast<double>(m_PreparedCaptures);
-	if (key == "registered_pairs") return static_cast<double>(m_RegisteredPairs.size());
+	if (key == "registered_pairs") return static_cast<double>(m_DirectGraphs.registeredUnits());
 	if (key == "recurrent") return m_Config.recurrent() ? 1.0 : 0.0;  // 0: a flow-free model (stateless)
 	if (key == "output_select") return static_cast<double>(m_Config.outputSelect);  // 1: the output_flow variant (pre_warp)
 	if (key == "resident_tower") return m_Resident ? 1.0 : 0.0;
@@ -1131,11 +1078,7 @@ double Engine::stat(const std::string &key) const {
 	if (key == "scene_detector_runs") return static_cast<double>(m_SceneRuns);  // launches of the detector (tests: once per step)
 	if (key == "launches_per_frame") return static_cast<double>(m_Program[0].size());
 	if (key == "tower_variant") return static_cast<double>(towerVariant());  // (developer switch, tests)
-	if (key == "direct_graphs") {
-		double n = 0;
-		for (const auto &kv : m_DirectGraphs) n += kv.second.graph.valid() ? 1 : 0;
-		return n;
-	}
+	if (key == "direct_graphs") return static_cast<double>(m_DirectGraphs.validGraphs());
 	throw std::invalid_argument("unknown stat " + key);
 }
 

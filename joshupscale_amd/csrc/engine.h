@@ -16,18 +16,27 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <set>
 #include <string>
 #include <tuple>
 #include <vector>
 
 #include "frame_io.h"
+#include "graph_cache.h"
 #include "hip_util.h"
 #include "kernels.h"
 #include "model.h"
 #include "scene_detector.h"
 
 namespace ju {
+
+// runs f when the scope ends, also by an exception: what a call rebinds for its launches goes back to what it was
+template <typename F>
+struct AtExit {
+	F f;
+	~AtExit() { f(); }
+};
+template <typename F>
+AtExit(F) -> AtExit<F>;
 
 struct FrameSize {
 	std::size_t inputWidth, inputHeight, outputWidth, outputHeight;
@@ -382,6 +391,7 @@ private:
 	void runSynchronous(const AnyFrame &in, const AnyFrame &out);
 	DeviceBuffer m_YuvInStage, m_YuvOutStage;
 	void runProgram();
+	void runSteps(int idx);  // binding set idx's launches against m_IO
 	// Frame buffers the kernels read / write in THIS call.  Graph replay always uses
 	// the internal staging buffers (static pointers); eager launches of device-resident
 	// frames use the caller's buffers directly (no staging copies).
@@ -532,19 +542,30 @@ private:
 			       std::tie(o.in, o.inStride, o.out, o.outStride, o.idx);
 		}
 	};
-	struct DirectEntry {
-		GraphExec graph;
-		unsigned seen = 0;
-		std::uint64_t lastUse = 0;
-		bool registered = false;  // a look-ahead tuple handed to prepareBatch: exempt from the LRU eviction
+	// what prepareFrames registers: the pair, idx = 0 in the key -- one unit for the graphs of both binding sets
+	struct PairOf {
+		DirectKey operator()(DirectKey key) const {
+			key.idx = 0;
+			return key;
+		}
 	};
-	std::map<DirectKey, DirectEntry> m_DirectGraphs;
-	// pairs registered through prepareFrames (idx = 0 in the key): captured at their FIRST
-	// sighting also after the cache was dropped (fallback to / return from the per-block path)
-	std::set<DirectKey> m_RegisteredPairs;
+	// The two graph caches (graph_cache.h), over one use clock.  m_DirectGraphs: the per-frame graphs by DirectKey -- at
+	// most 64 of pairs nobody registered (least recently used out) and 256 registered pairs, which stay registered when
+	// the graphs are dropped (fallback to / return from the per-block path: captured again at their FIRST sighting).
+	// m_BatchGraphs (the key: PassKey, below): the graphs of look-ahead passes -- 64 of tuples nobody registered, 256
+	// handed to prepareBatch (a call registers one per binding set), whose registration goes with the graph.
+	using CachedGraph = GraphEntry<GraphExec>;
+	std::uint64_t m_DirectClock = 0;
+	GraphCache<DirectKey, GraphExec, PairOf> m_DirectGraphs{m_DirectClock, 64, 256};
 	bool directEligible(const Frame &in, const Frame &out) const;
-	DirectEntry &directEntry(const DirectKey &key);
-	void captureDirect(DirectEntry *e, int idx);
+	// THE submission of a cached graph's launches (runProgram's device frames, submitBatch): a graph that is there is
+	// replayed; one that is not is captured at the tuple's second sighting -- a registered unit's at its first -- and
+	// replayed; else the launches run eagerly.  Counts "graph_captures", "graph_replays" and "eager_runs".
+	void replayOrRun(CachedGraph &e, bool registered, const std::function<void()> &launches);
+	// prepareFrames / prepareBatch: the graph captured now unless it is there (nothing executes); returns the graphs
+	// captured, counted as "prepared_captures"
+	int prepareGraph(CachedGraph &e, const std::function<void()> &launches);
+	void dropAllGraphs();  // of both caches: they replay the programs of the towers in use
 	// frame look-ahead (processBatch; engine_passes.cpp): the flow net's tensors for m_BatchCap frames, the state buffers
 	// between the frames of a pass, the flow launches per (frames, binding set) and the graphs per tuple of frame buffers;
 	// the frames of the pass being recorded: m_Pass, below
@@ -582,7 +603,7 @@ private:
 	int m_BatchCap = 0, m_BatchMax = kFlowBatchMax;
 	bool m_BatchUnsupported = false;
 	std::map<std::pair<int, int>, std::vector<Step>> m_BatchFlow;
-	std::map<std::vector<PassKey>, DirectEntry> m_BatchGraphs;
+	GraphCache<std::vector<PassKey>, GraphExec, UnitIsKey> m_BatchGraphs{m_DirectClock, 64, 256};
 	// Host frames inside look-ahead passes (round 6; the AviSynth caller's frames, avisynth_plugin/src/main.cc:113-144, and
 	// the only path the reference's own timer measures, scripts/inference/tensorrt/inference.py:245-251).  Frame by frame
 	// the 8.3 MB of an output cross the PCIe link while the GPU idles -- the frame's rows all appear in its last
@@ -692,18 +713,14 @@ private:
 	void drainPassOutputs(const AnyFrame *out, int n);
 	// the passes of processBatch / processFrames (whose staged pairs are checked: processFrames)
 	void runPasses(const AnyFrame *in, const AnyFrame *out, int count);
-	static constexpr std::size_t kMaxBatchGraphs = 64;          // unregistered tuples (LRU)
-	static constexpr std::size_t kMaxRegisteredBatches = 256;   // tuples registered through prepareBatch
 	std::uint64_t m_BatchFrames = 0;
 	// group: the flow launches of a group pass over `items` streams (processGroup), in m_BatchFlow at {items, kGroupSet}
 	bool batchPlanned(int items, bool group = false);
 	static constexpr int kGroupSet = 2;
 	void submitBatch(const AnyFrame *in, const AnyFrame *out, int n);
 	void runBatch(int set, int n, const std::function<void(const Step &, bool)> *around = nullptr);
-	void dropBatchGraphs();
 	// the n frames of a look-ahead pass under stage = stageBits(false); returns the key of the pass's graph
 	std::vector<PassKey> bindBatch(const AnyFrame *in, const AnyFrame *out, int n, int set, int stage);
-	DirectEntry &batchEntry(const std::vector<PassKey> &key);
 	// Group passes (processGroup).  The model's identity: FNV-1a of the container bytes the engine was built from, and
 	// the dtype it was asked for.  As a member: an event its stream records for the lead to wait on, and the frames it got
 	// from passes ("group_frames").  (As the lead: the history each item's first flow block reads and writes is in m_Pass.)
@@ -717,10 +734,7 @@ private:
 	    const std::function<void(bool)> &underPass, hipEvent_t after);
 	static void runGroups(Engine *const *members, const AnyFrame *in, const AnyFrame *out, int count, const char *who, bool indexed,
 	    const std::function<void(bool)> &underPass, hipEvent_t after);
-	std::uint64_t m_DirectClock = 0;
 	bool m_DirectGraph = true;  // JU_DIRECT_GRAPH=0: device frames always launch eagerly
-	static constexpr std::size_t kMaxDirectGraphs = 64;     // unregistered tuples (LRU)
-	static constexpr std::size_t kMaxRegisteredPairs = 256;
 	// Host frames (JU_LOC_CPU: the AviSynth caller, avisynth_plugin/src/main.cc:113-144) are copied from / to pageable
 	// memory through the HIP runtime's own bounce buffers.  Page-locking recycled caller buffers (hipHostRegister at a
 	// buffer's second sighting, JU_PIN_HOST=1) was built in round 5, measured at +2.3 % on that PCIe-bound path

@@ -513,9 +513,7 @@ void Engine::setSceneDetect(int mode, std::uint32_t thresholdMilli) {
 }
 
 void Engine::dropScenePassGraphs() {
-	for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
-		it = (!it->first.empty() && it->first.front().scene != 0) ? m_BatchGraphs.erase(it) : std::next(it);
-	}
+	m_BatchGraphs.eraseIf([](const std::vector<PassKey> &key) { return !key.empty() && key.front().scene != 0; });
 }
 
 void Engine::setSceneLookahead(int on) {

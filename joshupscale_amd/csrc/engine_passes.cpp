@@ -12,17 +12,6 @@
 
 namespace ju {
 
-namespace {
-// runs f when the scope ends, also by an exception: what a pass rebinds for its launches goes back to what it was
-template <typename F>
-struct AtExit {
-	F f;
-	~AtExit() { f(); }
-};
-template <typename F>
-AtExit(F) -> AtExit<F>;
-}  // namespace
-
 // ---------------------------------------------------------------------------------------------------------------
 // Frame look-ahead.  The flow net reads LR frames only -- never the HR state (models.py:790, 823: its input is the
 // packed history of the last num_flow_inputs frames) -- so the flow fields of n consecutive frames can be computed
@@ -129,15 +118,9 @@ void Engine::setLookahead(int frames) {
 	if (cap < m_BatchMax) {
 		// graphs of longer passes can no longer be asked for: drop them (their launches may still be in flight)
 		m_Stream.synchronize();
-		for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
-			it = static_cast<int>(it->first.size()) > cap ? m_BatchGraphs.erase(it) : std::next(it);
-		}
+		m_BatchGraphs.eraseIf([cap](const std::vector<PassKey> &key) { return static_cast<int>(key.size()) > cap; });
 	}
 	m_BatchMax = cap;
-}
-
-void Engine::dropBatchGraphs() {
-	m_BatchGraphs.clear();
 }
 
 // The launches of one look-ahead pass over the n frames of m_Pass, in stream order (recorded when m_Stream is
@@ -330,9 +313,7 @@ void Engine::setStageLookahead(int on) {
 // tables, the mask and the sizes are baked into those graphs).  The stream has drained: passes are synchronous.
 void Engine::dropStagePasses() {
 	m_Stream.synchronize();
-	for (auto it = m_BatchGraphs.begin(); it != m_BatchGraphs.end();) {
-		it = (!it->first.empty() && it->first.front().stage != 0) ? m_BatchGraphs.erase(it) : std::next(it);
-	}
+	m_BatchGraphs.eraseIf([](const std::vector<PassKey> &key) { return !key.empty() && key.front().stage != 0; });
 	for (StageSlots &slots : m_StageSlots) slots = StageSlots();
 	// (this runtime's slots as a member of group passes: of the old sizes too.  A group pass is synchronous, so the lead's
 	// stream, which ran the launches that used them, has drained, and no lead keeps a pointer to them: runGroupPass)
@@ -524,29 +505,6 @@ void Engine::drainPassOutputs(const AnyFrame *out, int n) {
 	if (any) JU_HIP(hipStreamSynchronize(*m_CopyStream));
 }
 
-Engine::DirectEntry &Engine::batchEntry(const std::vector<PassKey> &key) {
-	auto it = m_BatchGraphs.find(key);
-	if (it == m_BatchGraphs.end()) {
-		// least recently used out -- among the tuples nobody registered: a tuple handed to prepareBatch keeps its graphs
-		// (the header promises that process calls on it never capture), as registered pairs do; only a caller that keeps
-		// registering new tuples (more than kMaxRegisteredBatches) loses the registered one it used least recently
-		std::size_t registered = 0;
-		for (const auto &kv : m_BatchGraphs) registered += kv.second.registered ? 1 : 0;
-		if (m_BatchGraphs.size() - registered >= kMaxBatchGraphs || registered >= kMaxRegisteredBatches) {
-			const bool fromRegistered = m_BatchGraphs.size() - registered < kMaxBatchGraphs;
-			auto victim = m_BatchGraphs.end();
-			for (auto j = m_BatchGraphs.begin(); j != m_BatchGraphs.end(); ++j) {
-				if (j->second.registered != fromRegistered) continue;
-				if (victim == m_BatchGraphs.end() || j->second.lastUse < victim->second.lastUse) victim = j;
-			}
-			if (victim != m_BatchGraphs.end()) m_BatchGraphs.erase(victim);
-		}
-		it = m_BatchGraphs.emplace(key, DirectEntry{}).first;
-	}
-	it->second.lastUse = ++m_DirectClock;
-	return it->second;
-}
-
 // ju_prepare_batch: the graphs of a tuple of frame buffers a caller is going to hand to processBatch, one per
 // binding set, captured NOW (as prepareFrames does for one pair): nothing executes, no buffer is touched.  Returns
 // the graphs captured; 0 for a tuple that will not go as one pass.
@@ -563,17 +521,18 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 	std::unique_lock<std::mutex> chain = chainBegin(m_Resident);  // (no capture while another engine's constructor drains the device)
 	int captured = 0;
 	for (int set = 0; set < 2; ++set) {
-		DirectEntry &e = batchEntry(bindBatch(anyIn.data(), anyOut.data(), n, set, 0));
-		e.registered = true;
+		// (a tuple handed over here keeps its graphs, as registered pairs do: the header promises that process calls on it
+		// never capture; only a caller that keeps registering new tuples loses the registered one it used least recently)
+		const std::vector<PassKey> key = bindBatch(anyIn.data(), anyOut.data(), n, set, 0);
+		m_BatchGraphs.registerUnit(key);
+		CachedGraph &e = m_BatchGraphs.use(key);
 		if (e.graph.valid()) continue;
 		{
 			DryLaunchScope dry;  // the attributes of the tile heights this pass's launch sizes choose
 			for (const Step &st : m_BatchFlow.at({n, scenePass() == 2 ? kCutSet + set : set})) st.run(m_Stream);
 		}
-		e.graph = GraphExec::capture(m_Stream, [&] { runBatch(set, n); });
+		captured += prepareGraph(e, [&] { runBatch(set, n); });
 		e.seen = 2;
-		++captured;
-		++m_PreparedCaptures;
 	}
 	return captured;
 }
@@ -599,23 +558,11 @@ void Engine::submitBatch(const AnyFrame *in, const AnyFrame *out, int n) {
 	}
 	{
 		std::unique_lock<std::mutex> chain = chainBegin(m_Resident);
-		bool replayed = false;
+		const auto launches = [&] { runBatch(set, n); };
 		if (m_UseGraph && m_DirectGraph) {
-			DirectEntry &e = batchEntry(key);
-			// (first sighting: eager -- it also sets the dynamic-LDS attribute of a tile height this pass's launch
-			// sizes choose for the first time, which must not happen inside a capture; second: capture and replay)
-			if (!e.graph.valid() && ++e.seen >= 2) {
-				e.graph = GraphExec::capture(m_Stream, [&] { runBatch(set, n); });
-				++m_InlineCaptures;
-			}
-			if (e.graph.valid()) {
-				e.graph.launch(m_Stream);
-				++m_GraphReplays;
-				replayed = true;
-			}
-		}
-		if (!replayed) {
-			runBatch(set, n);
+			replayOrRun(m_BatchGraphs.use(key), m_BatchGraphs.registered(key), launches);
+		} else {
+			launches();
 			++m_EagerRuns;
 		}
 		chainEnd(chain, m_Resident);
