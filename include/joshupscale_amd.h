@@ -479,12 +479,47 @@ JU_API int ju_get_output_size(const ju_runtime *runtime, size_t *width, size_t *
  * Routing: while the mode is not JU_ALPHA_ZERO frames of every entry point run one by one through the staging buffers, in
  * stream order, with one more launch behind the frame's colour and in front of any copy to the host; no direct device
  * path, no look-ahead or group pass whatever ju_set_stage_lookahead, ju_set_stage_group and the scene settings say (in a
- * group call such a runtime runs on its own behind the pass), ju_prepare_* capture nothing.  JU_ALPHA_ZERO restores all of
+ * group call such a runtime runs on its own behind the pass), ju_prepare_* capture nothing -- unless ju_set_alpha_lookahead
+ * / ju_set_alpha_group, below, let the passes carry the launch.  JU_ALPHA_ZERO restores all of
  * them.  The setter waits for the stream.  ju_get_stat: "alpha_mode", "alpha_filter", "alpha_frames" (frames whose alpha
- * slot these launches wrote).  Not covered: alpha inside passes, on a ju_tiled, premultiplied alpha, the C++ surface. */
+ * slot these launches wrote).  Not covered: premultiplied alpha, the direct device path of single frames, the C++ surface. */
 enum { JU_ALPHA_ZERO = 0, JU_ALPHA_OPAQUE = 1, JU_ALPHA_SOURCE = 2 };
 JU_API int ju_set_alpha(ju_runtime *runtime, int mode, int filter);
 JU_API int ju_get_alpha(const ju_runtime *runtime, int *mode, int *filter);
+
+/* ---- alpha inside look-ahead passes and group passes (docs/alpha.md: "Passes") ------------------------------------------
+ * ju_set_alpha_lookahead(rt, 1): while the alpha mode is not JU_ALPHA_ZERO, ju_process_batch and ju_process_frames form
+ * their look-ahead passes again, under all their usual rules -- the mode no longer decides; the stage and scene
+ * conditions decide as for a runtime in mode 0, so a runtime under a source size, a mask or an output size still needs
+ * ju_set_stage_lookahead, and a detecting one ju_set_scene_lookahead.  Inside a pass the frame's one alpha launch follows
+ * its colour -- the tail, the mask blend, the output scaler and the encode -- in stream order, in front of the copy of a
+ * host frame.  It is the launch of the single-frame route: same mode, filter and tables, same source and sink rows by
+ * format and location (a JU_LOC_DEVICE frame where it is, a host frame in the pass's upload slot, plane 0 of an RGBX,
+ * BGRX64 or X2 frame; a format without a slot reads as opaque on the input side and gets no launch on the output side).
+ * Every output byte, the state and the frame history equal those of the same frames sent one by one.  The default is 0:
+ * such frames run one by one, as described above, byte for byte and stat for stat.  A value other than 0 or 1 is
+ * JU_ERR_INVALID_ARGUMENT ("ju_set_alpha_lookahead: on must be 0 or 1, got N") and leaves the setting as it was; the call
+ * waits for the stream; ju_reset and ju_set_alpha keep the setting.
+ * Graphs: a captured pass bakes in the mode, the filter and the tables; ju_set_alpha, this call and every size setter that
+ * rebuilds the alpha scaler drop the graphs of the passes that carry alpha (captured again at the second sighting of their
+ * buffers).  With the setting on ju_prepare_batch captures as in mode 0 (that is, while no stage setting is on);
+ * ju_prepare_frames captures nothing, as before.  A pass that has to run again (the resident tower reported) runs its
+ * frames one by one through the staged route, which writes their alpha.
+ * Unchanged by the setting: ju_process, ju_enqueue, ju_process_frame, ju_enqueue_frame and the C++ processImage keep the
+ * staged single-frame route; under JU_ALPHA_SOURCE a JU_LOC_DEVICE output over its own JU_LOC_DEVICE input stays refused.
+ * ju_get_stat: "alpha_lookahead" (1 / 0) and "lookahead_alpha_frames", the frames whose slot was written inside a pass;
+ * "alpha_frames" counts them too, each frame once. */
+JU_API int ju_set_alpha_lookahead(ju_runtime *runtime, int on); /* default 0 */
+/* ju_set_alpha_group(rt, 1): this runtime rides in the passes of ju_process_group and ju_process_group_frames while its
+ * alpha mode is not JU_ALPHA_ZERO (under a stage setting it also needs ju_set_stage_group, with the detector on
+ * ju_set_scene_group), and the pass makes its alpha launch behind its own steps, blend, scaler and encode, on the lead's
+ * stream, with THIS member's mode, filter, tables and sizes -- never the lead's.  For every member the bytes, the state and
+ * the history equal those of ju_process_frame on that member alone.  The default is 0: such a member runs on its own
+ * behind the pass.  Per member; independent of ju_set_alpha_lookahead; a value other than 0 or 1 is
+ * JU_ERR_INVALID_ARGUMENT ("ju_set_alpha_group: on must be 0 or 1, got N") and leaves the setting as it was; the call waits
+ * for the stream; ju_reset and ju_set_alpha keep the setting.  ju_get_stat: "alpha_group" (1 / 0) and
+ * "group_alpha_frames", this runtime's frames whose slot was written inside a group pass ("alpha_frames" counts them too). */
+JU_API int ju_set_alpha_group(ju_runtime *runtime, int on); /* default 0 */
 
 /* ---- scaled and masked frames inside look-ahead passes (docs/source_stage.md, docs/output_stage.md: "Passes") ----------
  * ju_set_stage_lookahead(rt, 1): while a source size, a mask or an output size is set, ju_process_batch and
@@ -781,6 +816,25 @@ JU_API int ju_tiled_get_output_size(const ju_tiled *tiled, size_t *width, size_t
  * ju_tiled_get_stat: "source_mask" (1 / 0), "source_mask_frames" (the frames processed while a mask was set),
  * "mask_box_x0", "mask_box_y0", "mask_box_x1", "mask_box_y1" (the box; all 0 while the mask is off or the box is empty). */
 JU_API int ju_tiled_set_source_mask(ju_tiled *tiled, const ju_image *mask);
+/* The alpha channel of tiled frames (docs/tiled.md "Alpha"; docs/alpha.md "Tiled").  ju_set_alpha's modes (JU_ALPHA_ZERO,
+ * the default: every launch as without the call; JU_ALPHA_OPAQUE; JU_ALPHA_SOURCE), filter check and definition
+ * (tests/alpha_reference.py, unchanged), with the tiled source size as the input frame and this object's output frame --
+ * four times the source size, or the output size while ju_tiled_set_output_size is set -- as the output frame.  The alpha
+ * plane is scaled straight from one to the other by ONE launch per frame on the tiled stream, behind the stitch (also the
+ * masked, scaled and fused ones) and the encode, in front of the copy out (in a look-ahead pass: in front of what orders
+ * the deferred host copy).  It is never cut into tiles, never blended and never seen by the tiles' engines, which stay in
+ * mode 0: the colour bytes, the tiles' states, the detector, the mask's blend and the deep outputs are those of the same
+ * object in mode 0.  It is read where the source already lies on the device -- a JU_LOC_DEVICE frame in place, the staged
+ * copy of a host frame, plane 0 of an RGBX, BGRX64 or X2 input (never its decoded BGRX copy, whose X is 0); an input
+ * without a slot is opaque; an output format without a slot gets no launch.  The existing refusal of an output that
+ * overlaps the input covers the ordering.  A source of exactly W x H, ONE tile, gives the slots of ju_process_frame under
+ * ju_set_alpha.
+ * JU_ERR_INVALID_ARGUMENT, every setting as it was: a mode or filter out of range; under JU_ALPHA_SOURCE the limits of
+ * ju_set_alpha between those two sizes -- whichever of ju_tiled_set_alpha and ju_tiled_set_output_size would leave them
+ * is refused, and the message names alpha and both sizes.  The setter waits for the tiled stream; ju_tiled_reset keeps the
+ * setting.  ju_tiled_get_stat: "alpha_mode", "alpha_filter", "alpha_frames" (frames whose slot the launch wrote). */
+JU_API int ju_tiled_set_alpha(ju_tiled *tiled, int mode, int filter);
+JU_API int ju_tiled_get_alpha(const ju_tiled *tiled, int *mode, int *filter);
 JU_API int ju_tiled_get_info(const ju_tiled *tiled, ju_tiled_info *info);
 /* The origin of tile `index` (0 .. tiles_x tiles_y - 1, row-major over the tile grid) in source pixels. */
 JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t *y);
@@ -791,7 +845,8 @@ JU_API int ju_tiled_get_tile(const ju_tiled *tiled, int index, size_t *x, size_t
  * "pass_calls", "pass_frames", "pass_split_launches", "pass_overlapped_copies": ju_tiled_process_frames above;
  * "scene_mode", "scene_frames", "scene_cuts": the detector below, the two counters cumulative as ju_get_stat's;
  * "output_scaled", "output_filter", "output_scaled_frames": ju_tiled_set_output_size above; "source_mask",
- * "source_mask_frames", "mask_box_x0" .. "mask_box_y1": ju_tiled_set_source_mask above.  An unknown key is
+ * "source_mask_frames", "mask_box_x0" .. "mask_box_y1": ju_tiled_set_source_mask above; "alpha_mode", "alpha_filter",
+ * "alpha_frames": ju_tiled_set_alpha above.  An unknown key is
  * JU_ERR_INVALID_ARGUMENT. */
 JU_API int ju_tiled_get_stat(const ju_tiled *tiled, const char *key, double *value);
 /* The scene detector of a tiled stream (docs/tiled.md "Scene cuts"; no reference counterpart).  ju_set_scene_detect's

@@ -215,11 +215,15 @@ JU_API int ju_debug_scale(int op, int filter, void *dst, ptrdiff_t dst_stride, s
  * other bit of the destination changes.  ju_debug_alpha_fill: the top code into every slot.  JU_ERR_INVALID_ARGUMENT: an
  * unknown kind or filter, a NULL side, |stride| smaller than a row, a misaligned side, a size out of range.
  * ju_debug_alpha_problem: no device -- the limits of ju_set_alpha for a runtime whose input frames are in_width x
- * in_height and whose output frames are out_width x out_height, with its message (JU_ERR_INVALID_ARGUMENT) or JU_OK. */
+ * in_height and whose output frames are out_width x out_height, with its message (JU_ERR_INVALID_ARGUMENT) or JU_OK.
+ * ju_debug_tiled_alpha_problem: no device -- the limits of ju_tiled_set_alpha for a tiled source of src_width x src_height
+ * whose output size is out_width x out_height ((0, 0): none set, the output frame is four times the source), likewise. */
 JU_API int ju_debug_alpha_scale(int source_kind, int sink_kind, int filter, void *dst, ptrdiff_t dst_stride, size_t dst_width,
     size_t dst_height, const void *src, ptrdiff_t src_stride, size_t src_width, size_t src_height);
 JU_API int ju_debug_alpha_fill(int sink_kind, void *dst, ptrdiff_t dst_stride, size_t dst_width, size_t dst_height);
 JU_API int ju_debug_alpha_problem(int mode, int filter, size_t in_width, size_t in_height, size_t out_width, size_t out_height);
+JU_API int ju_debug_tiled_alpha_problem(int mode, int filter, size_t src_width, size_t src_height, size_t out_width,
+    size_t out_height);
 
 /* The sources of a look-ahead pass scaled in one launch (scale_bgrx_items_kernel; docs/source_stage.md "Passes"): ONE
  * synchronous launch over `count` (1 .. 8) items on caller-supplied device buffers, on the current device.  Item i reads

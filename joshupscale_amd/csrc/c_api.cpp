@@ -349,6 +349,14 @@ int ju_get_alpha(const ju_runtime *runtime, int *mode, int *filter) {
 	return guarded([&] { engineOf(const_cast<ju_runtime *>(runtime)).alpha(mode, filter); });
 }
 
+int ju_set_alpha_lookahead(ju_runtime *runtime, int on) {
+	return guarded([&] { engineOf(runtime).setAlphaLookahead(on); });
+}
+
+int ju_set_alpha_group(ju_runtime *runtime, int on) {
+	return guarded([&] { engineOf(runtime).setAlphaGroup(on); });
+}
+
 int ju_set_scene_detect(ju_runtime *runtime, int mode, uint32_t threshold_milli) {
 	return guarded([&] { engineOf(runtime).setSceneDetect(mode, threshold_milli); });
 }
@@ -446,6 +454,14 @@ int ju_tiled_set_source_mask(ju_tiled *tiled, const ju_image *mask) {
 
 int ju_tiled_get_output_size(const ju_tiled *tiled, size_t *width, size_t *height) {
 	return guarded([&] { tiledOf(const_cast<ju_tiled *>(tiled)).outputSize(width, height); });
+}
+
+int ju_tiled_set_alpha(ju_tiled *tiled, int mode, int filter) {
+	return guarded([&] { tiledOf(tiled).setAlpha(mode, filter); });
+}
+
+int ju_tiled_get_alpha(const ju_tiled *tiled, int *mode, int *filter) {
+	return guarded([&] { tiledOf(const_cast<ju_tiled *>(tiled)).alpha(mode, filter); });
 }
 
 int ju_tiled_process(ju_tiled *tiled, const ju_image *input, const ju_image *output) {
@@ -1208,6 +1224,13 @@ int ju_debug_alpha_fill(int sink_kind, void *dst, ptrdiff_t dst_stride, size_t d
 		}
 		ju::launchAlphaFill(ju::AlphaRows{sink_kind, dst, dst_stride}, static_cast<int>(dst_width), static_cast<int>(dst_height), nullptr);
 		JU_HIP(hipStreamSynchronize(nullptr));
+	});
+}
+
+int ju_debug_tiled_alpha_problem(int mode, int filter, size_t src_width, size_t src_height, size_t out_width, size_t out_height) {
+	return guarded([&] {
+		const std::string problem = ju::tiledAlphaProblem(mode, filter, src_width, src_height, out_width, out_height);
+		if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_alpha: " + problem);
 	});
 }
 

@@ -1061,6 +1061,10 @@ double Engine::stat(const std::string &key) const {
 	if (key == "alpha_mode") return static_cast<double>(m_AlphaMode);
 	if (key == "alpha_filter") return static_cast<double>(m_AlphaFilter);
 	if (key == "alpha_frames") return static_cast<double>(m_AlphaFrames);  // frames whose alpha slot the alpha kernels wrote
+	if (key == "alpha_lookahead") return m_AlphaLookahead ? 1.0 : 0.0;
+	if (key == "alpha_group") return m_AlphaGroup ? 1.0 : 0.0;
+	if (key == "lookahead_alpha_frames") return static_cast<double>(m_BatchAlphaFrames);  // ... of them inside look-ahead passes
+	if (key == "group_alpha_frames") return static_cast<double>(m_GroupAlphaFrames);  // ... of them inside group passes
 	if (key == "source_stage_frames") return static_cast<double>(m_SourceFrames);  // frames through the source stage
 	if (key == "group_frames") return static_cast<double>(m_GroupFrames);  // frames that went through group passes
 	if (key == "group_yuv_frames") return static_cast<double>(m_GroupYuvFrames);  // ... of them with a non-BGRX side

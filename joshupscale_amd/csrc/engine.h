@@ -144,10 +144,19 @@ public:
 	// launch, every route as without the setting), JU_ALPHA_OPAQUE (the format's top code) or JU_ALPHA_SOURCE (the input
 	// frame's alpha scaled by `filter`, a JU_SCALE_* value, from the input frame's size straight to the output frame's
 	// size); the filter is checked in every mode.  While the mode is not 0 every frame of every entry point runs one by
-	// one through submitFrame, whatever setStageLookahead / setStageGroup say, and one launch follows the frame's colour.
-	// Waits for the stream; reset() keeps it.
+	// one through submitFrame, whatever setStageLookahead / setStageGroup say, and one launch follows the frame's colour --
+	// unless setAlphaLookahead / setAlphaGroup let the passes carry that launch.  Waits for the stream; reset() keeps it.
 	void setAlpha(int mode, int filter);
 	void alpha(int *mode, int *filter) const;
+	// Look-ahead passes while the alpha mode is not 0 (ju_set_alpha_lookahead; engine_passes.cpp, "Alpha inside a pass"):
+	// 0 (default) = such a runtime's frames run one by one through submitFrame, 1 = the mode no longer keeps
+	// processBatch / processFrames from forming passes (the stage and scene settings decide as in mode 0), and each
+	// frame's one alpha launch follows its colour inside the pass.  Waits for the stream; reset() and setAlpha() keep it.
+	void setAlphaLookahead(int on);
+	// Group passes while the alpha mode is not 0 (ju_set_alpha_group): 0 (default) = processGroup / processGroupFrames run
+	// this runtime on its own, 1 = it rides, and the pass makes its alpha launch with its own mode, filter and tables.
+	// Independent of setAlphaLookahead.  Waits for the stream; reset() and setAlpha() keep it.
+	void setAlphaGroup(int on);
 	bool sourceStage() const { return m_SrcScale.set() || m_Mask.on() || m_OutScale.set(); }
 	// The scene detector (docs/scene_detect.md; "Scene detector" below).  setSceneDetect: mode 0 off / 1 report / 2 reset
 	// (JU_SCENE_*), thresholdMilli 1 .. 255000 while the mode is not off; waits for the stream; a call that changes the
@@ -340,6 +349,20 @@ private:
 	// the one alpha launch of a frame, behind its colour and in front of any copy to the host: nothing in mode 0 or for a
 	// format without a slot
 	void alphaInto(PixelFormat format, void *rows, std::ptrdiff_t stride);
+	// THE alpha launch of both routes, with this runtime's mode, filter and tables at its frame sizes: the fill, or the
+	// scale from `src`, into `sink` on `stream`.  False, and nothing launched, in mode 0 or for a sink without a slot
+	// (alpha_route.h alphaLaunches).  Counts nothing: alphaInto counts its frame, a pass counts once it has completed.
+	bool launchAlpha(const AlphaRows &src, const AlphaRows &sink, hipStream_t stream);
+	// Alpha inside passes: the two settings; frames whose slot was written inside a look-ahead pass
+	// ("lookahead_alpha_frames") and, as a member, inside a group pass ("group_alpha_frames") -- "alpha_frames" counts
+	// them too.  alphaPass(group): the mode a pass formed now carries for this runtime, 0 when it carries none -- part of
+	// the key of a look-ahead pass's graph, which bakes in the mode, the filter and the tables' addresses.
+	bool m_AlphaLookahead = false, m_AlphaGroup = false;
+	std::uint64_t m_BatchAlphaFrames = 0, m_GroupAlphaFrames = 0;
+	int alphaPass(bool group) const { return (group ? m_AlphaGroup : m_AlphaLookahead) ? m_AlphaMode : 0; }
+	// The graphs of the look-ahead passes that carry alpha: dropped whenever setAlpha, setAlphaLookahead or a size setter
+	// changes what they baked in (the stream has drained: passes are synchronous)
+	void dropAlphaPasses();
 	// Scene detector: two eager launches on m_Stream in front of runProgram(), outside the chain lock and never captured
 	// (sceneStep: submit and submitFrame, once m_IO.in holds the frame the program will read).  m_Scene: the setting, the
 	// detector's memory on the model-size input and its clock (scene_detector.h).  m_SceneRerun: set around the re-run of a
@@ -588,7 +611,12 @@ private:
 		// caller's device image or the pass's slot (`io` is then the model-size pair in between)
 		int stage = 0;
 		DirectKey ends{};
+		// alphaPass(false) when the pass was bound: a pass that carries the alpha launch and one over the same buffers in
+		// mode 0 never share a graph; what else that launch bakes in (the filter, the tables) changes only through setters
+		// that drop these graphs (dropAlphaPasses)
+		int alpha = 0;
 		bool operator<(const PassKey &o) const {
+			if (alpha != o.alpha) return alpha < o.alpha;
 			if (scene != o.scene) return scene < o.scene;
 			if (stage != o.stage) return stage < o.stage;
 			if (ends < o.ends) return true;
@@ -634,6 +662,8 @@ private:
 	// the scaler reads / writes there while io is the model-size staged slot in between.  size: the frame's size on either
 	// side (passSizes under the owner's stage bits).  up / down: the device buffers the host copies of the frame go to /
 	// come from.  groupPrev / groupOut: on the lead of a group pass, the history item i's first flow block reads / writes.
+	// alphaIn / alphaOut: where the frame's alpha slots lie on the device, by alpha_route.h's rule over what was bound above
+	// -- a BGRX side's `ends` rows, plane 0 of another format's planes; kAlphaNone for a format without a slot.
 	// m_PassStage heads the array: the stage bits the look-ahead pass was bound with (a group pass: 0 -- each member
 	// brings its own).  A fixed-address member: the step lambdas and the captured graphs hold pointers into it and read it
 	// at launch time.
@@ -642,6 +672,7 @@ private:
 		FrameIO io, ends;
 		PassExtent size;
 		PassCopy up, down;
+		AlphaRows alphaIn, alphaOut;
 		const void *groupPrev = nullptr;
 		void *groupOut = nullptr;
 		bool host() const { return in.host || out.host; }
@@ -695,7 +726,7 @@ private:
 	// the members of a group pass, on the lead: member i's pair under member i's own stage bits, sizes and slots
 	void bindGroup(Engine *const *m, const AnyFrame *in, const AnyFrame *out, int n, const int *stage);
 	// What follows a frame's own steps in a pass, on this runtime's stream (the lead's): the owner's mask blend in place,
-	// its output scaler, the encode and the host signal.  stateOut: the state the frame's steps wrote; out16: the frame's
+	// its output scaler, the encode, its alpha launch and the host signal.  stateOut: the state the frame's steps wrote; out16: the frame's
 	// 16-bit slot at output size.
 	void passTail(Engine &owner, const PassFrame &f, int stage, void *stateOut, const DeviceBuffer &out16);
 	// this runtime's mask over the model-size frame `gen`, letting through the source rows `src` of srcW x srcH

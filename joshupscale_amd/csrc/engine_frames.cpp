@@ -5,6 +5,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "alpha_route.h"
 #include "engine.h"
 #include "graphics.h"
 
@@ -245,6 +246,7 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 		m_Stream.synchronize();  // (enqueued frames may still read the tables)
 		if (m_SrcScale.set()) dropStagePasses();
 		m_SrcScale.clear();
+		dropAlphaPasses();
 		m_AlphaScale = std::move(alpha);
 		m_SrcStage = DeviceBuffer();
 		m_SrcYuvStage = DeviceBuffer();
@@ -259,6 +261,7 @@ void Engine::setSourceSize(std::size_t width, std::size_t height, int filter) {
 	m_Stream.synchronize();
 	dropStagePasses();  // (the staged passes' graphs and slots are of the old size and tables)
 	m_SrcScale = std::move(scale);
+	dropAlphaPasses();
 	m_AlphaScale = std::move(alpha);
 	m_SrcStage = std::move(stage);
 	m_SrcYuvStage = std::move(yuvStage);
@@ -311,6 +314,7 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 		m_Stream.synchronize();  // (enqueued frames may still read the tables and write the buffers)
 		if (m_OutScale.set()) dropStagePasses();
 		m_OutScale.clear();
+		dropAlphaPasses();
 		m_AlphaScale = std::move(alpha);
 		for (DeviceBuffer *b : {&m_OutScaled8, &m_OutScaled16, &m_OutYuvStage, &m_OutRawStage}) *b = DeviceBuffer();
 		return;
@@ -322,6 +326,7 @@ void Engine::setOutputSize(std::size_t width, std::size_t height, int filter) {
 	m_Stream.synchronize();
 	dropStagePasses();
 	m_OutScale = std::move(scale);
+	dropAlphaPasses();
 	m_AlphaScale = std::move(alpha);
 	m_OutScaled8 = std::move(scaled8);
 	m_OutScaled16 = std::move(scaled16);
@@ -417,20 +422,6 @@ void Engine::submitFrame(const AnyFrame &in, const AnyFrame &out) {
 // frame's size straight to the output frame's size, never through the model's (alpha_scale_kernel).  The decode, encode
 // and scale kernels are untouched: the slot they left 0 is rewritten behind them, before any copy to the host.
 // ---------------------------------------------------------------------------------------------------------------
-namespace {
-// the slot of a format: kAlphaNone for one without
-int alphaKind(PixelFormat f) {
-	switch (f) {
-	case PixelFormat::Bgrx:
-	case PixelFormat::Rgbx: return kAlphaByte;
-	case PixelFormat::Bgrx64: return kAlphaWord;
-	case PixelFormat::X2rgb10:
-	case PixelFormat::X2bgr10: return kAlphaBits;
-	default: return kAlphaNone;
-	}
-}
-}  // namespace
-
 void Engine::frameSizes(std::size_t *inW, std::size_t *inH, std::size_t *outW, std::size_t *outH) const {
 	const FrameSize fs = frameSize();
 	*inW = m_SrcScale.set() ? m_SrcScale.srcW() : fs.inputWidth;
@@ -454,6 +445,7 @@ void Engine::setAlpha(int mode, int filter) {
 	frameSizes(&inW, &inH, &outW, &outH);
 	Scaler alpha = alphaScalerFor("ju_set_alpha", mode, filter, inW, inH, outW, outH);
 	m_Stream.synchronize();  // (enqueued frames may still read the tables)
+	dropAlphaPasses();
 	m_AlphaScale = std::move(alpha);
 	m_AlphaMode = mode;
 	m_AlphaFilter = filter;
@@ -464,33 +456,45 @@ void Engine::alpha(int *mode, int *filter) const {
 	if (filter) *filter = m_AlphaFilter;
 }
 
+// (alpha_route.h: format and location give the kind and the rows -- the rule the passes bind by as well)
 AlphaRows Engine::alphaSource(const AnyFrame &in, const BgrxRows &bgrx) {
-	if (!in.yuv) {
-		// a device frame in place; a host frame (or a graphics resource) where submitFrame staged it
-		if (in.bgrx.location == Location::Device) return AlphaRows{kAlphaByte, in.bgrx.ptr, in.bgrx.stride};
-		return AlphaRows{kAlphaByte, const_cast<std::uint8_t *>(bgrx.ptr), bgrx.stride};
+	AlphaSide side;
+	side.planar = in.yuv;
+	// the BGRX rows: a device frame in place; a host frame (or a graphics resource) where submitFrame staged it
+	side.bgrx = in.yuv ? AlphaSideRows{bgrx.ptr, bgrx.stride}
+	                   : alphaLocated(in.bgrx.location == Location::Device, AlphaSideRows{in.bgrx.ptr, in.bgrx.stride},
+	                         AlphaSideRows{bgrx.ptr, bgrx.stride});
+	if (in.yuv) {
+		side.format = in.planes.format;
+		if (alphaKind(side.format) != kAlphaNone) {
+			// a host frame: the planes decodePlanes uploaded, still in their staging buffer
+			const bool device = in.planes.location == Location::Device;
+			const YuvPlanes pl = device ? YuvPlanes{} : stagedPlanes(in.planes, (m_SrcScale.set() ? m_SrcYuvStage : m_YuvInStage).as<std::uint8_t>());
+			side.plane0 = alphaLocated(device, AlphaSideRows{in.planes.planes[0], in.planes.strides[0]}, AlphaSideRows{pl.y, pl.yStride});
+		}
 	}
-	const int kind = alphaKind(in.planes.format);
-	if (kind == kAlphaNone) return AlphaRows{};
-	if (in.planes.location == Location::Device) return AlphaRows{kind, in.planes.planes[0], in.planes.strides[0]};
-	// a host frame: the planes decodePlanes uploaded, still in their staging buffer
-	const YuvPlanes pl = stagedPlanes(in.planes, (m_SrcScale.set() ? m_SrcYuvStage : m_YuvInStage).as<std::uint8_t>());
-	return AlphaRows{kind, pl.y, pl.yStride};
+	return alphaRowsOf(side);
+}
+
+bool Engine::launchAlpha(const AlphaRows &src, const AlphaRows &sink, hipStream_t stream) {
+	if (!alphaLaunches(m_AlphaMode, sink.kind)) return false;
+	std::size_t inW, inH, outW, outH;
+	frameSizes(&inW, &inH, &outW, &outH);
+	if (m_AlphaMode == kAlphaOpaque) {
+		launchAlphaFill(sink, static_cast<int>(outW), static_cast<int>(outH), stream);
+	} else {
+		launchAlphaScale(src, static_cast<int>(inW), static_cast<int>(inH), sink, static_cast<int>(outW), static_cast<int>(outH),
+		    m_AlphaScale.xAxis(), m_AlphaScale.yAxis(), m_AlphaScale.span(), stream);
+	}
+	return true;
 }
 
 void Engine::alphaInto(PixelFormat format, void *rows, std::ptrdiff_t stride) {
-	const int kind = alphaKind(format);
-	if (m_AlphaMode == kAlphaZero || kind == kAlphaNone) return;
-	std::size_t inW, inH, outW, outH;
-	frameSizes(&inW, &inH, &outW, &outH);
-	const AlphaRows sink{kind, rows, stride};
-	if (m_AlphaMode == kAlphaOpaque) {
-		launchAlphaFill(sink, static_cast<int>(outW), static_cast<int>(outH), m_Stream);
-	} else {
-		launchAlphaScale(m_AlphaSrc, static_cast<int>(inW), static_cast<int>(inH), sink, static_cast<int>(outW), static_cast<int>(outH),
-		    m_AlphaScale.xAxis(), m_AlphaScale.yAxis(), m_AlphaScale.span(), m_Stream);
-	}
-	++m_AlphaFrames;
+	AlphaSide side;
+	side.planar = format != PixelFormat::Bgrx;
+	side.format = format;
+	side.bgrx = side.plane0 = AlphaSideRows{rows, stride};  // (the side's own rows: the dense BGRX frame, or plane 0 as the encode wrote it)
+	if (launchAlpha(m_AlphaSrc, alphaRowsOf(side), m_Stream)) ++m_AlphaFrames;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

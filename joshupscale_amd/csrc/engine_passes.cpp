@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "alpha_route.h"
 #include "engine.h"
 #include "log.h"
 
@@ -240,8 +241,43 @@ void Engine::passTail(Engine &owner, const PassFrame &f, int stage, void *stateO
 		owner.encodeYuv(f.out.format, f.out.colorspace, f.out.planes, f.size.outW, f.size.outH, f.ends.out, f.ends.outStride, stateOut,
 		    frame16, m_Stream);
 	}
+	// alpha (setAlphaLookahead, setAlphaGroup): the owner's one launch behind the frame's colour, the launch alphaInto makes
+	// -- the owner's mode, filter and tables, in a group pass never the lead's -- over the rows bindFrame found; in front of
+	// the signal, so a host frame is copied out with its alpha in place.  (A runtime whose mode is not 0 is in a pass only
+	// under one of the two settings: passEligible.)
+	owner.launchAlpha(f.alphaIn, f.alphaOut, m_Stream);
 	// (a host frame: its bytes are complete in the slot `down` names -- tell the thread that copies them out)
 	if (f.out.host) launchSignalHost(m_PassSignal.device(), m_Stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Alpha inside a pass (setAlphaLookahead, setAlphaGroup; docs/alpha.md "Passes").  Alpha lies outside the recurrence and
+// touches no colour sample, so a pass takes it as it takes the mask blend and the encode: one launch behind the frame's
+// colour, in stream order (passTail).  The input's alpha is read behind the output's colour -- from the caller's device
+// rows, the upload slot or the staged planes, none of which the pass writes: the pass splitter keeps every output of a
+// pass off every input of it, and checkAlphaOverlap refuses a device output over its own device input up front.  A
+// captured pass bakes in the mode, the filter and the tables' addresses: PassKey::alpha keeps such a graph apart from the
+// mode-0 graph over the same buffers, and every setter that changes one of the three drops these graphs (dropAlphaPasses).
+// A pass that runs again goes frame by frame through submitFrame, which writes and counts alpha itself; the pass counts
+// its frames only once it has completed.
+// ---------------------------------------------------------------------------------------------------------------
+void Engine::setAlphaLookahead(int on) {
+	if (on != 0 && on != 1) throw std::invalid_argument("ju_set_alpha_lookahead: on must be 0 or 1, got " + std::to_string(on));
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();
+	if (m_AlphaLookahead != (on != 0)) dropAlphaPasses();
+	m_AlphaLookahead = on != 0;
+}
+
+void Engine::setAlphaGroup(int on) {
+	if (on != 0 && on != 1) throw std::invalid_argument("ju_set_alpha_group: on must be 0 or 1, got " + std::to_string(on));
+	DeviceGuard g(m_Device);
+	m_Stream.synchronize();  // (group passes are eager: nothing is kept that the setting could make stale)
+	m_AlphaGroup = on != 0;
+}
+
+void Engine::dropAlphaPasses() {
+	m_BatchGraphs.eraseIf([](const std::vector<PassKey> &key) { return !key.empty() && key.front().alpha != 0; });
 }
 
 void Engine::blendMask(std::uint8_t *gen, std::ptrdiff_t genStride, const std::uint8_t *src, std::ptrdiff_t srcStride, std::size_t srcW,
@@ -258,8 +294,9 @@ void Engine::blendMask(std::uint8_t *gen, std::ptrdiff_t genStride, const std::u
 bool Engine::passEligible(const AnyFrame &in, const AnyFrame &out, bool group) const {
 	// (scaled / masked frames run one by one through submitFrame unless the passes carry the stages: setStageLookahead; a
 	// group pass: setStageGroup)
-	// (alpha: the staged single-frame route, whatever the stage and scene settings say -- docs/alpha.md)
-	if (m_AlphaMode != 0) return false;
+	// (alpha: the staged single-frame route, whatever the stage and scene settings say -- unless the passes carry its
+	// launch: setAlphaLookahead; a group pass: setAlphaGroup.  The stage and scene conditions then decide as in mode 0)
+	if (m_AlphaMode != 0 && !(group ? m_AlphaGroup : m_AlphaLookahead)) return false;
 	const int stage = stageBits(group);
 	if (sourceStage() && !stage) return false;
 	// (the scene detector: a pass computes the flow of all its frames from a history a cut inside it would invalidate --
@@ -374,6 +411,18 @@ void Engine::bindFrame(PassFrame *f, const Engine &owner, int stage, const AnyFr
 		f->io.out = staged->modelOut.as<std::uint8_t>();
 		f->io.outStride = static_cast<std::ptrdiff_t>(fs.outputWidth * 4);
 	}
+	// the alpha slots (alpha_route.h): a BGRX side's rows at the frame's own size -- the caller's device rows or the slot,
+	// with the sign of a bottom-up host stride -- else plane 0 of the side's planes, the caller's or the staged ones
+	auto alphaSide = [](const PassSide &s, const void *rows, std::ptrdiff_t stride) {
+		AlphaSide a;
+		a.planar = s.yuv;
+		a.format = s.format;
+		a.bgrx = AlphaSideRows{rows, stride};
+		a.plane0 = AlphaSideRows{s.planes.y, s.planes.yStride};
+		return alphaRowsOf(a);
+	};
+	f->alphaIn = alphaSide(f->in, f->ends.in, f->ends.inStride);
+	f->alphaOut = alphaSide(f->out, f->ends.out, f->ends.outStride);
 	if (f->out.host) {
 		if (!m_PassSignal.host()) m_PassSignal = PinnedWords(64);
 		if (!m_CopyStream) m_CopyStream = std::make_unique<Stream>();
@@ -401,6 +450,7 @@ std::vector<Engine::PassKey> Engine::bindBatch(const AnyFrame *in, const AnyFram
 		k.io = DirectKey{f.io.in, f.io.inStride, f.io.out, f.io.outStride, set};
 		k.scene = scenePass();
 		k.stage = stage;
+		k.alpha = alphaPass(false);
 		if (stage) k.ends = DirectKey{f.ends.in, f.ends.inStride, f.ends.out, f.ends.outStride, 0};
 	}
 	return key;
@@ -512,7 +562,9 @@ int Engine::prepareBatch(const Frame *in, const Frame *out, int n) {
 	if (n < 0 || (n > 0 && (in == nullptr || out == nullptr))) throw std::invalid_argument("prepareBatch: bad arguments");
 	DeviceGuard g(m_Device);
 	if (n < 2 || n > m_BatchMax || !m_UseGraph || !m_DirectGraph) return 0;
-	if (sourceStage() || m_AlphaMode != 0) return 0;  // (nothing is captured while a stage setting is on, whatever setStageLookahead says)
+	// (nothing is captured while a stage setting is on, whatever setStageLookahead says; alpha: passEligible, as in mode 0
+	// under setAlphaLookahead)
+	if (sourceStage()) return 0;
 	const std::vector<AnyFrame> anyIn = anyOf(in, n), anyOut = anyOf(out, n);
 	for (int i = 0; i < n; ++i) {
 		if (!passEligible(anyIn[i], anyOut[i])) return 0;
@@ -670,6 +722,10 @@ void Engine::runPasses(const AnyFrame *in, const AnyFrame *out, int count) {
 			for (int k = 0; k < n; ++k) {
 				m_BatchHostFrames += m_Pass[k].host() ? 1 : 0;
 				m_BatchYuvFrames += m_Pass[k].yuv() ? 1 : 0;
+				if (alphaLaunches(alphaPass(false), m_Pass[k].alphaOut.kind)) {  // (the launch passTail made for this frame)
+					++m_BatchAlphaFrames;
+					++m_AlphaFrames;
+				}
 				maybeRestoreResident();
 			}
 		}
@@ -1022,6 +1078,10 @@ void Engine::runGroupPass(Engine &L, Engine *const *m, const AnyFrame *in, const
 		if (stage[i]) {  // (what the frame went through, whichever route it took: "source_stage_frames" counts it too)
 			++m[i]->m_GroupStagedFrames;
 			++m[i]->m_SourceFrames;
+		}
+		if (alphaLaunches(m[i]->alphaPass(true), L.m_Pass[i].alphaOut.kind)) {  // (the launch passTail made for this member)
+			++m[i]->m_GroupAlphaFrames;
+			++m[i]->m_AlphaFrames;
 		}
 		m[i]->maybeRestoreResident();
 	}

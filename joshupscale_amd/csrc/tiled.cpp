@@ -9,6 +9,8 @@
 // sources staged and cut up front, in ONE launch, a host frame copied out under the next frame's group passes (runPass).
 #include "tiled.h"
 
+#include "alpha_route.h"
+
 #include <algorithm>
 #include <stdexcept>
 
@@ -95,6 +97,9 @@ double TiledRuntime::stat(const std::string &key) const {
 	if (key == "mask_box_y0") return m_MaskBox.y0;
 	if (key == "mask_box_x1") return m_MaskBox.x1;
 	if (key == "mask_box_y1") return m_MaskBox.y1;
+	if (key == "alpha_mode") return m_AlphaMode;
+	if (key == "alpha_filter") return m_AlphaFilter;
+	if (key == "alpha_frames") return static_cast<double>(m_AlphaFrames);
 	if (key == "group_frames") {
 		double sum = 0;
 		for (const auto &e : m_Engines) sum += e->stat("group_frames");
@@ -181,11 +186,18 @@ void TiledRuntime::setOutputSize(std::size_t width, std::size_t height, int filt
 	const std::string problem = tiledOutputSizeProblem(off ? kTileScale * m_SrcW : width, off ? kTileScale * m_SrcH : height, m_SrcW,
 	    m_SrcH, filter);
 	if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_output_size: " + problem);
+	// (alpha from the source goes straight from the source size to the new output frame: refused, both settings as they
+	// were, where that leaves the alpha scaler's limits)
+	const std::size_t aw = off ? kTileScale * m_SrcW : width, ah = off ? kTileScale * m_SrcH : height;
+	const std::string alphaLimits = tiledAlphaProblem(m_AlphaMode, m_AlphaFilter, m_SrcW, m_SrcH, width, height);
+	if (!alphaLimits.empty()) throw std::invalid_argument("ju_tiled_set_output_size: " + alphaLimits);
 	DeviceGuard g(m_Device);
-	Scaler scale;
+	Scaler scale, alphaScale;
 	if (!off) scale.build(kTileScale * m_SrcW, kTileScale * m_SrcH, width, height, filter);
+	if (m_AlphaMode == kAlphaSource) alphaScale.build(m_SrcW, m_SrcH, aw, ah, m_AlphaFilter);
 	m_Stream->synchronize();  // (the call is synchronous, so nothing reads the old tables; kept for a stream shared later)
 	m_OutScale = std::move(scale);
+	m_AlphaScale = std::move(alphaScale);
 	for (DeviceBuffer *b : {&m_OutStage[0], &m_OutStage[1], &m_Out16, &m_YuvOut[0], &m_YuvOut[1]}) *b = DeviceBuffer();  // (their sizes follow the output size)
 }
 
@@ -218,6 +230,75 @@ void TiledRuntime::setSourceMask(const Frame *mask) {
 	m_Stream->synchronize();
 	m_Mask = std::move(copy);
 	m_MaskBox = box;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Alpha (docs/tiled.md "Alpha"): tests/alpha_reference.py from the tiled source size to the output frame's size.  The
+// tiles' engines stay in mode 0 and the stitch kernels write X = 0 as ever; ONE launch of the engine's alpha kernels
+// (launchAlphaFill / launchAlphaScale) rewrites the slot behind the frame's last colour launch, on the tiled stream.
+// ---------------------------------------------------------------------------------------------------------------
+std::string tiledAlphaProblem(int mode, int filter, std::size_t srcW, std::size_t srcH, std::size_t outW, std::size_t outH) {
+	const bool off = outW == 0 && outH == 0;
+	return alphaProblem(mode, filter, srcW, srcH, off ? kTileScale * srcW : outW, off ? kTileScale * srcH : outH);
+}
+
+void TiledRuntime::outputFrameSize(std::size_t *width, std::size_t *height) const {
+	*width = m_OutScale.set() ? m_OutScale.dstW() : kTileScale * m_SrcW;
+	*height = m_OutScale.set() ? m_OutScale.dstH() : kTileScale * m_SrcH;
+}
+
+void TiledRuntime::setAlpha(int mode, int filter) {
+	std::size_t ow, oh;
+	outputFrameSize(&ow, &oh);
+	const std::string problem = tiledAlphaProblem(mode, filter, m_SrcW, m_SrcH, m_OutScale.dstW(), m_OutScale.dstH());
+	if (!problem.empty()) throw std::invalid_argument("ju_tiled_set_alpha: " + problem);
+	DeviceGuard g(m_Device);
+	Scaler scale;
+	if (mode == kAlphaSource) scale.build(m_SrcW, m_SrcH, ow, oh, filter);
+	m_Stream->synchronize();
+	m_AlphaScale = std::move(scale);
+	m_AlphaMode = mode;
+	m_AlphaFilter = filter;
+}
+
+void TiledRuntime::alpha(int *mode, int *filter) const {
+	if (mode) *mode = m_AlphaMode;
+	if (filter) *filter = m_AlphaFilter;
+}
+
+AlphaRows TiledRuntime::alphaSource(const AnyFrame &in, const BgrxRows &src, const DeviceBuffer &yuvStage) const {
+	if (m_AlphaMode != kAlphaSource) return AlphaRows{};  // (nothing of the input is read)
+	AlphaSide side;
+	side.planar = in.yuv;
+	side.bgrx = AlphaSideRows{src.ptr, src.stride};
+	if (in.yuv) {
+		side.format = in.planes.format;
+		if (alphaKind(side.format) != kAlphaNone) {
+			const YuvFrame &y = in.planes;
+			const bool device = y.location == Location::Device;
+			const YuvPlanes staged = device ? YuvPlanes{} : stagedPlanes(y, yuvStage.as<std::uint8_t>());
+			side.plane0 = alphaLocated(device, AlphaSideRows{y.planes[0], y.strides[0]}, AlphaSideRows{staged.y, staged.yStride});
+		}
+	}
+	return alphaRowsOf(side);
+}
+
+void TiledRuntime::alphaInto(PixelFormat format, void *rows, std::ptrdiff_t stride, const AlphaRows &alphaSrc) {
+	AlphaSide side;
+	side.planar = format != PixelFormat::Bgrx;
+	side.format = format;
+	side.bgrx = side.plane0 = AlphaSideRows{rows, stride};
+	const AlphaRows sink = alphaRowsOf(side);
+	if (!alphaLaunches(m_AlphaMode, sink.kind)) return;
+	std::size_t ow, oh;
+	outputFrameSize(&ow, &oh);
+	if (m_AlphaMode == kAlphaOpaque) {
+		launchAlphaFill(sink, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
+	} else {
+		launchAlphaScale(alphaSrc, static_cast<int>(m_SrcW), static_cast<int>(m_SrcH), sink, static_cast<int>(ow), static_cast<int>(oh),
+		    m_AlphaScale.xAxis(), m_AlphaScale.yAxis(), m_AlphaScale.span(), *m_Stream);
+	}
+	++m_AlphaFrames;
 }
 
 void TiledRuntime::setDeepFromState(int on) {
@@ -266,7 +347,7 @@ bool TiledRuntime::deepFromState(const AnyFrame &out) const {
 // The 16-bit path: ONE launch blends the states the tiles' last frames left -- the group passes are synchronous, so they
 // are complete -- into the dense 16-bit frame, which the existing encode from such a frame turns into the caller's planes
 // (a host frame's through their staging layout, as on the 8-bit route).
-void TiledRuntime::stitchOutDeep(const YuvFrame &y, int slot, HostCopy *defer) {
+void TiledRuntime::stitchOutDeep(const YuvFrame &y, const AlphaRows &alphaSrc, int slot, HostCopy *defer) {
 	const bool scaled = m_OutScale.set();
 	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
 	const std::size_t ow = scaled ? m_OutScale.dstW() : bw, oh = scaled ? m_OutScale.dstH() : bh;
@@ -295,17 +376,18 @@ void TiledRuntime::stitchOutDeep(const YuvFrame &y, int slot, HostCopy *defer) {
 		}
 		launchEncodeFrame16(fmt(y.format), y.colorspace, frame16, planes, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
 	}
+	alphaInto(y.format, planes.y, planes.yStride, alphaSrc);  // (plane 0 as the encode wrote it, in front of the copy out)
 	if (host) deferOrCopyPlanes(y, yuv, defer);
 	++m_DeepStateFrames;
 }
 
-void TiledRuntime::stitchOut(const AnyFrame &out, const BgrxRows &src, int slot, HostCopy *defer) {
+void TiledRuntime::stitchOut(const AnyFrame &out, const BgrxRows &src, const AlphaRows &alphaSrc, int slot, HostCopy *defer) {
 	// While an output size is set the frame is ow x oh of it and the blend's launch is the fused one, which forms the
 	// blended frame in registers and writes the scaled one; everything behind the launch -- the staging frame, the copy
 	// out, the encode -- is the same code at that size.  Off: exactly the launches of before.
 	const bool scaled = m_OutScale.set();
 	if (scaled) ++m_OutputScaledFrames;
-	if (deepFromState(out)) return stitchOutDeep(out.planes, slot, defer);
+	if (deepFromState(out)) return stitchOutDeep(out.planes, alphaSrc, slot, defer);
 	const std::size_t bw = kTileScale * m_SrcW, bh = kTileScale * m_SrcH;  // the blended frame
 	const std::size_t ow = scaled ? m_OutScale.dstW() : bw, oh = scaled ? m_OutScale.dstH() : bh, rowBytes = ow * 4;
 	const auto plain = static_cast<std::ptrdiff_t>(rowBytes);
@@ -346,22 +428,24 @@ void TiledRuntime::stitchOut(const AnyFrame &out, const BgrxRows &src, int slot,
 		stitch(stage, plain);
 		const bool host = y.location == Location::Host;
 		std::uint8_t *yuv = host ? lazy(m_YuvOut[slot], stagedLayout(formatInfo(y.format), y.width, y.height, y.strides).bytes).as<std::uint8_t>() : nullptr;
-		launchEncodeFrame(fmt(y.format), y.colorspace, stage, plain, host ? stagedPlanes(y, yuv) : callerPlanes(y), static_cast<int>(ow),
-		    static_cast<int>(oh), *m_Stream);
+		const YuvPlanes planes = host ? stagedPlanes(y, yuv) : callerPlanes(y);
+		launchEncodeFrame(fmt(y.format), y.colorspace, stage, plain, planes, static_cast<int>(ow), static_cast<int>(oh), *m_Stream);
+		alphaInto(y.format, planes.y, planes.yStride, alphaSrc);  // (plane 0 as the encode wrote it, in front of the copy out)
 		if (host) deferOrCopyPlanes(y, yuv, defer);
 		return;
 	}
 	const Frame &b = out.bgrx;
 	const bool device = b.location == Location::Device;
-	if (device && reinterpret_cast<std::uintptr_t>(b.ptr) % 4 == 0 && b.stride % 4 == 0) return stitch(static_cast<std::uint8_t *>(b.ptr), b.stride);
+	if (device && reinterpret_cast<std::uintptr_t>(b.ptr) % 4 == 0 && b.stride % 4 == 0) {
+		stitch(static_cast<std::uint8_t *>(b.ptr), b.stride);
+		return alphaInto(PixelFormat::Bgrx, b.ptr, b.stride, alphaSrc);  // (the caller's aligned device rows)
+	}
 	// stitched in the caller's row order, copied out in memory order
 	auto *stage = lazy(m_OutStage[slot], rowBytes * oh).as<std::uint8_t>();
 	const RowSpan rows = rowSpan(b.ptr, b.stride, oh);
-	if (rows.topDown) {
-		stitch(stage, plain);
-	} else {
-		stitch(stage + static_cast<std::ptrdiff_t>(oh - 1) * plain, -plain);
-	}
+	std::uint8_t *first = rows.topDown ? stage : stage + static_cast<std::ptrdiff_t>(oh - 1) * plain;
+	stitch(first, rows.topDown ? plain : -plain);
+	alphaInto(PixelFormat::Bgrx, first, rows.topDown ? plain : -plain, alphaSrc);  // (the staging frame, in front of the copy out)
 	if (defer != nullptr && !device) {  // a host frame of a pass: copied out by the caller, under the next frame's group passes
 		defer->pending = true;
 		defer->yuv = false;
@@ -438,7 +522,7 @@ void TiledRuntime::process(const AnyFrame &in, const AnyFrame &out, const char *
 	// are complete before the first of them starts
 	m_Stream->synchronize();
 	groupPasses(m_In, {});
-	stitchOut(out, src);
+	stitchOut(out, src, alphaSource(in, src, m_YuvIn));
 	m_Stream->synchronize();
 	++m_Frames;
 	if (m_Mask.on()) ++m_MaskFrames;
@@ -571,7 +655,8 @@ void TiledRuntime::runPass(const AnyFrame *in, const AnyFrame *out, int count) {
 		}
 		// 4. the blend, on the tiled stream; the group passes are synchronous, so the tiles' outputs and states are complete
 		copy[f & 1] = HostCopy{};
-		stitchOut(out[f], src[f], f & 1, &copy[f & 1]);
+		// (the alpha launch lies inside stitchOut, in front of the event that orders the deferred host copy)
+		stitchOut(out[f], src[f], alphaSource(in[f], src[f], m_PassYuvIn[static_cast<std::size_t>(f)]), f & 1, &copy[f & 1]);
 		m_Stitched[f & 1]->record(*m_Stream);
 		++m_Frames;
 		if (m_Mask.on()) ++m_MaskFrames;

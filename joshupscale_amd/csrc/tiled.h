@@ -21,6 +21,11 @@ namespace ju {
 // frame of 4 srcW x 4 srcH, which a limit's message then names as such; "" when width x height may be set.
 std::string tiledOutputSizeProblem(std::size_t width, std::size_t height, std::size_t srcW, std::size_t srcH, int filter);
 
+// The limits of ju_tiled_set_alpha as one message shared with its Python twin, and what ju_tiled_set_output_size asks
+// before it changes the size: alphaProblem's with the tiled source size as the input frame and outW x outH -- (0, 0), no
+// output size: the blended frame, four times the source -- as the output frame; "" when the setting may be made.
+std::string tiledAlphaProblem(int mode, int filter, std::size_t srcW, std::size_t srcH, std::size_t outW, std::size_t outH);
+
 class TiledRuntime {
 public:
 	// srcWidth x srcHeight: the size of every input frame; overlap: source pixels neighbouring tiles share at least.
@@ -77,6 +82,15 @@ public:
 	// states, the group passes and the scene detector do not know about it; deep formats are encoded from the 8-bit frame
 	// while it is set.
 	void setSourceMask(const Frame *mask);
+	// The alpha channel (docs/tiled.md "Alpha"; docs/alpha.md "Tiled"): Engine::setAlpha's modes, filter check and
+	// definition with the tiled source size as the input frame and the output frame of this object -- four times the source,
+	// or the output size set -- as the output frame.  The alpha plane is scaled straight from one to the other by ONE launch
+	// per frame behind the stitch and the encode, in front of the copy out: never cut into tiles, never blended, never seen
+	// by the tiles' engines, which stay in mode 0.  std::invalid_argument with alphaProblem's words for those two sizes, the
+	// setting as it was; setOutputSize is refused likewise where it would leave JU_ALPHA_SOURCE outside the limits.  Waits
+	// for the tiled stream; reset() keeps it.
+	void setAlpha(int mode, int filter);
+	void alpha(int *mode, int *filter) const;
 
 	std::size_t srcWidth() const { return m_SrcW; }
 	std::size_t srcHeight() const { return m_SrcH; }
@@ -96,7 +110,8 @@ public:
 	// decisions and cuts, cumulative over its on-periods), "output_scaled" (1 while an output size is set), "output_filter"
 	// (its kScale* value, 0 while off), "output_scaled_frames" (frames that took a fused blend-and-scale kernel),
 	// "source_mask" (1 while a mask is set), "source_mask_frames" (frames processed while one was set), "mask_box_x0" /
-	// "_y0" / "_x1" / "_y1" (the box in blended coordinates; all 0 while the mask is off or the box is empty)
+	// "_y0" / "_x1" / "_y1" (the box in blended coordinates; all 0 while the mask is off or the box is empty), "alpha_mode" /
+	// "alpha_filter" (the setting), "alpha_frames" (frames whose alpha slot the alpha launch wrote)
 	double stat(const std::string &key) const;
 
 private:
@@ -118,10 +133,11 @@ private:
 	void deferOrCopyPlanes(const YuvFrame &y, std::uint8_t *yuv, HostCopy *defer);
 	// slot: which of the two staging frames per side (0 outside a pass); defer: null = a host frame is copied out on the
 	// tiled stream behind its stitch (process()), else the copy is left to the caller in *defer
-	void stitchOut(const AnyFrame &out, const BgrxRows &src, int slot = 0, HostCopy *defer = nullptr);
+	// alphaSrc: where the frame's alpha lies on the device (alphaSource)
+	void stitchOut(const AnyFrame &out, const BgrxRows &src, const AlphaRows &alphaSrc, int slot = 0, HostCopy *defer = nullptr);
 	// a deep format while the setting is on and the tiles' states are their frames in float: the 16-bit path of stitchOut
 	bool deepFromState(const AnyFrame &out) const;
-	void stitchOutDeep(const YuvFrame &y, int slot, HostCopy *defer);
+	void stitchOutDeep(const YuvFrame &y, const AlphaRows &alphaSrc, int slot, HostCopy *defer);
 	DeviceBuffer &lazy(DeviceBuffer &b, std::size_t bytes);
 	void checkPair(const AnyFrame &in, const AnyFrame &out, const char *who) const;
 	// every tile's engine by one frame, as group passes over the tile inputs `in`; under(p, passes, inPass): host work under
@@ -170,6 +186,18 @@ private:
 	SourceMask m_Mask;
 	MaskBox m_MaskBox;
 	std::uint64_t m_MaskFrames = 0;
+	// Alpha: the setting; the scaler from the source size to the output frame's size while the mode is JU_ALPHA_SOURCE,
+	// rebuilt by setAlpha and setOutputSize; the frames whose slot was written.  alphaSource: alpha_route.h's rule on what
+	// stageIn left on the device -- `src`, the BGRX rows it returned (the device frame in place or the staged copy, X as the
+	// caller gave it), or plane 0 of an RGBX, BGRX64 or X2 input, the caller's or the copy staged in `yuvStage`; never the
+	// decoded BGRX rows of such an input, whose X is 0.  alphaInto: the one launch of a frame, into the side of `format`
+	// whose rows (a BGRX frame's, else plane 0 as the encode wrote it) are given; nothing in mode 0 or without a slot.
+	int m_AlphaMode = 0, m_AlphaFilter = 0;
+	Scaler m_AlphaScale;
+	std::uint64_t m_AlphaFrames = 0;
+	void outputFrameSize(std::size_t *width, std::size_t *height) const;  // the output size set, else four times the source
+	AlphaRows alphaSource(const AnyFrame &in, const BgrxRows &src, const DeviceBuffer &yuvStage) const;
+	void alphaInto(PixelFormat format, void *rows, std::ptrdiff_t stride, const AlphaRows &alphaSrc);
 	// The scene detector: m_Scene the setting, the memory on the source-size frame (the kept frame: 4 Ws Hs bytes) and the
 	// clock (scene_detector.h); m_SceneClear the clear's table of kTileMax SceneClearTile (host-mapped; RESET on a recurrent
 	// model only), re-made with the detector's memory.  m_Own: what each tile counts (tileOwnedEnds).

@@ -195,6 +195,16 @@ def alpha_problem(mode: int, filter: int, in_width: int, in_height: int, out_wid
             f"the output at most {SOURCE_RATIO_MAX} times the input (the alpha scaler goes from one straight to the other)")
 
 
+def tiled_alpha_problem(mode: int, filter: int, src_width: int, src_height: int, out_width: int = 0, out_height: int = 0) -> str:
+    """The limits of ``ju_tiled_set_alpha`` for a tiled source of ``src_width x src_height`` whose output size is
+    ``out_width x out_height`` (``(0, 0)``: none set), with the C layer's message: :func:`alpha_problem` with the tiled
+    source size as the input frame and the output size -- else the blended frame, four times the source -- as the output
+    frame.  ``ju_tiled_set_output_size`` holds the size it would leave to the same."""
+    if (out_width, out_height) == (0, 0):
+        out_width, out_height = 4 * src_width, 4 * src_height
+    return alpha_problem(mode, filter, src_width, src_height, out_width, out_height)
+
+
 LOG_CALLBACK = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.c_char_p, C.c_void_p)
 
 
@@ -315,6 +325,10 @@ _PRODUCT_SIGS = {
     "ju_get_output_size": (C.c_int, [C.c_void_p, _P(C.c_size_t), _P(C.c_size_t)]),
     "ju_set_alpha": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ju_get_alpha": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
+    "ju_set_alpha_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
+    "ju_set_alpha_group": (C.c_int, [C.c_void_p, C.c_int]),
+    "ju_tiled_set_alpha": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ju_tiled_get_alpha": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
     "ju_tiled_create": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, _P(C.c_void_p)]),
     "ju_tiled_create_from_memory": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int,
                                               _P(C.c_void_p)]),
@@ -389,6 +403,7 @@ _HOOK_SIGS = {
                                        C.c_ssize_t, C.c_size_t, C.c_size_t]),
     "ju_debug_alpha_fill": (C.c_int, [C.c_int, C.c_void_p, C.c_ssize_t, C.c_size_t, C.c_size_t]),
     "ju_debug_alpha_problem": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "ju_debug_tiled_alpha_problem": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "ju_debug_scale_items": (C.c_int, [C.c_int, C.c_int, _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
                                        _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t]),
     "ju_debug_scale_members": (C.c_int, [C.c_int, _P(C.c_int), _P(C.c_void_p), _P(C.c_ssize_t), C.c_size_t, C.c_size_t,
@@ -713,6 +728,21 @@ class Runtime:
         _check(self._lib, self._lib.ju_get_alpha(self._h, C.byref(mode), C.byref(filter)))
         return mode.value, filter.value
 
+    def set_alpha_lookahead(self, on) -> None:
+        """``ju_set_alpha_lookahead``: 1 = ``process_batch`` / ``process_frames`` form look-ahead passes while the alpha
+        mode is not ``ALPHA_ZERO`` (the stage and scene settings decide as in mode 0), and each frame's alpha launch
+        follows its colour inside the pass (docs/alpha.md "Passes"); 0 (the default) = such frames run one by one.
+        ``reset`` and ``set_alpha`` keep it.  A value other than 0 or 1 raises :class:`JoshUpscaleError` with the C
+        layer's message."""
+        _check(self._lib, self._lib.ju_set_alpha_lookahead(self._h, int(on)))
+
+    def set_alpha_group(self, on) -> None:
+        """``ju_set_alpha_group``: 1 = this runtime rides in the passes of ``process_group`` / ``process_group_frames``
+        while its alpha mode is not ``ALPHA_ZERO``, and the pass makes its alpha launch with this member's own mode,
+        filter and sizes (docs/alpha.md "Passes"); 0 (the default) = such a member runs on its own.  Independent of
+        ``set_alpha_lookahead``.  A value other than 0 or 1 raises :class:`JoshUpscaleError` with the C layer's message."""
+        _check(self._lib, self._lib.ju_set_alpha_group(self._h, int(on)))
+
     def _alpha_allows(self, who: str, in_size, out_size) -> None:
         """What ``set_source_size`` / ``set_output_size`` ask before they change a size: under ``ALPHA_SOURCE`` the alpha
         scaler must still reach from the one frame size to the other."""
@@ -852,7 +882,7 @@ class Runtime:
         "output_scaled", "source_filter", "output_filter", "scene_mode", "scene_frames", "scene_cuts", "scene_lookahead",
         "scene_pass_frames", "stage_lookahead", "lookahead_staged_frames", "group_frames", "group_yuv_frames",
         "scene_group", "scene_group_frames", "stage_group", "group_staged_frames", "alpha_mode", "alpha_filter",
-        "alpha_frames"."""
+        "alpha_frames", "alpha_lookahead", "lookahead_alpha_frames", "alpha_group", "group_alpha_frames"."""
         v = C.c_double()
         _check(self._lib, self._lib.ju_get_stat(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1069,6 +1099,9 @@ class TiledRuntime:
                                             self.src_width, self.src_height, filter)
         if problem:
             raise ValueError("ju_tiled_set_output_size: " + problem)
+        problem = tiled_alpha_problem(*self.get_alpha(), self.src_width, self.src_height, width, height)
+        if problem:                                                       # (alpha from the source: both settings stay)
+            raise ValueError("ju_tiled_set_output_size: " + problem)
         _check(self._lib, self._lib.ju_tiled_set_output_size(self._h, width, height, filter))
 
     def get_output_size(self) -> Tuple[int, int]:
@@ -1081,6 +1114,24 @@ class TiledRuntime:
         """``(width, height)`` of the frames the object hands out now: the output size set, else the blended size."""
         w, h = self.get_output_size()
         return (w, h) if w else (self.out_width, self.out_height)
+
+    # -- the alpha channel (docs/tiled.md "Alpha") ----------
+    def set_alpha(self, mode: int, filter: int = SCALE_TRIANGLE) -> None:
+        """``ju_tiled_set_alpha``: :meth:`Runtime.set_alpha` for tiled frames -- ``ALPHA_SOURCE`` scales the input frame's
+        alpha by ``filter`` from the tiled source size straight to :meth:`frame_output_size`, in one launch behind the
+        stitch; the tiles never see it.  An unknown mode or filter and sizes beyond the alpha scaler raise ``ValueError``
+        with the C layer's message before any native call; the setting stays as it was.  ``reset`` keeps it."""
+        mode, filter = int(mode), int(filter)
+        problem = tiled_alpha_problem(mode, filter, self.src_width, self.src_height, *self.get_output_size())
+        if problem:
+            raise ValueError("ju_tiled_set_alpha: " + problem)
+        _check(self._lib, self._lib.ju_tiled_set_alpha(self._h, mode, filter))
+
+    def get_alpha(self) -> Tuple[int, int]:
+        """``ju_tiled_get_alpha``: ``(mode, filter)`` as set; ``(ALPHA_ZERO, SCALE_TRIANGLE)`` on a fresh object."""
+        mode, filter = C.c_int(), C.c_int()
+        _check(self._lib, self._lib.ju_tiled_get_alpha(self._h, C.byref(mode), C.byref(filter)))
+        return mode.value, filter.value
 
     # -- a source mask (docs/tiled.md "A mask") ----------
     def set_source_mask(self, mask) -> None:

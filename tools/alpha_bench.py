@@ -7,6 +7,13 @@ yardstick of every workload is mode 0 in the same process:
   process_bgrx:  ju_process, device BGRX, the three modes -- here a mode other than 0 also costs the direct device path --
                  and `staged`: mode 0 of a runtime created under JU_DIRECT=0 (a developer switch of the test flavour:
                  every frame through the staging buffers), which is the route without the kernel.
+  pass_bgrx / pass_rgbx: look-ahead passes of 8 device frames (ju_process_batch on BGRX, ju_process_frames on RGBX):
+                 mode 0 in passes, and OPAQUE and SOURCE with ju_set_alpha_lookahead 1 (`_on`: alpha inside the pass) and 0
+                 (`_off`: every frame on its own through the staged route).
+  group:         8 streams of device BGRX frames through ju_process_group: mode 0, and SOURCE and OPAQUE members with
+                 ju_set_alpha_group 1 (`_on`: they ride) and 0 (`_off`: each runs alone behind the pass).
+  tiled_540 / tiled_720: a ju_tiled of 960x540 / 1280x720 on device BGRX frames, ju_tiled_set_alpha ZERO / OPAQUE / SOURCE.
+                 (--workloads names them; profiles/alpha_pass_bench.json holds a run of them)
 Prints one JSON line: per workload and variant the median, min and max frames/s over the rounds, each variant over
 mode 0, and the "alpha_frames" stat that shows each took its route.
 
@@ -127,6 +134,95 @@ class Workload:
             rt.close()
 
 
+class PassWorkload:
+    """Passes of 8 device frames, a group of 8 streams, or a tiled object: the variants over the same device frames.
+    run() counts frames: a pass call advances 8, a group call 8 (one per stream), a tiled call 1."""
+
+    def __init__(self, kind, preset, dtype, filt):
+        import numpy as np
+        import torch
+        from joshupscale_amd import model_file as M
+        from joshupscale_amd import runtime as R
+        self.R, self.kind, self.rt = R, kind, {}
+        dev = torch.device("cuda", 0)
+        cfg = M.PRESETS[preset]
+        blob = M.serialize(cfg, M.make_seeded_weights(cfg))
+        dt = {"bf16": R.DTYPE_BF16, "fp16": R.DTYPE_F16}[dtype]
+        h, w = cfg.frame_height, cfg.frame_width
+        modes = {"mode0": R.ALPHA_ZERO, "opaque": R.ALPHA_OPAQUE, "source": R.ALPHA_SOURCE}
+        self.per_call = 8
+        if kind.startswith("tiled"):
+            sw, sh = {"tiled_540": (960, 540), "tiled_720": (1280, 720)}[kind]
+            self.per_call = 1
+            for name, mode in modes.items():
+                self.rt[name] = R.TiledRuntime(blob, 0, dt, sw, sh, 16, hooks=True)
+                self.rt[name].set_alpha(mode, filt)
+            h, w = sh, sw
+            names = list(modes)
+        else:
+            names = ["mode0", "opaque_on", "opaque_off", "source_on", "source_off"]
+        clip = M.synthetic_frames(8, h, w, seed=1234, kind="noise").copy()
+        clip[..., 3] = np.random.default_rng(5).integers(0, 256, clip.shape[:3], dtype=np.uint8)
+        self.d_in = torch.from_numpy(clip).to(dev)
+        frames_out = 1 if kind.startswith("tiled") else 8            # (a tiled call writes one frame)
+        self.d_out = {n: torch.zeros((frames_out, 4 * h, 4 * w * 4), dtype=torch.uint8, device=dev) for n in names}
+        self.calls = {}
+        for name in names:
+            if kind.startswith("tiled"):
+                tr = self.rt[name]
+                pair = (R.JuImage(self.d_in[0].data_ptr(), R.LOC_DEVICE, 4 * w, w, h),
+                        R.JuImage(self.d_out[name][0].data_ptr(), R.LOC_DEVICE, 16 * w, 4 * w, 4 * h))
+                self.calls[name] = (lambda tr=tr, pair=pair: tr.process(*pair))
+                continue
+            mode = modes[name.split("_")[0]]
+            on = 0 if name.endswith("_off") else 1
+            if kind == "group":
+                rts = [R.Runtime(blob, 0, dt, hooks=True) for _ in range(8)]
+                for rt in rts:
+                    rt.set_alpha(mode, filt)
+                    rt.set_alpha_group(on)
+                self.rt[name] = rts
+                ins = [rts[k].device_image(self.d_in[k].data_ptr(), w, h) for k in range(8)]
+                outs = [rts[k].device_image(self.d_out[name][k].data_ptr(), 4 * w, 4 * h) for k in range(8)]
+                self.calls[name] = (lambda rts=rts, ins=ins, outs=outs: R.process_group(rts, ins, outs))
+                continue
+            rt = R.Runtime(blob, 0, dt, hooks=True)
+            rt.set_alpha(mode, filt)
+            rt.set_alpha_lookahead(on)
+            self.rt[name] = rt
+            if kind == "pass_bgrx":
+                ins = [rt.device_image(self.d_in[k].data_ptr(), w, h) for k in range(8)]
+                outs = [rt.device_image(self.d_out[name][k].data_ptr(), 4 * w, 4 * h) for k in range(8)]
+                self.calls[name] = (lambda rt=rt, ins=ins, outs=outs: rt.process_batch(ins, outs))
+            else:
+                ins = [R.device_frame(R.FMT_RGBX, w, h, [self.d_in[k].data_ptr()]) for k in range(8)]
+                outs = [R.device_frame(R.FMT_RGBX, 4 * w, 4 * h, [self.d_out[name][k].data_ptr()]) for k in range(8)]
+                self.calls[name] = (lambda rt=rt, ins=ins, outs=outs: rt.process_frames(ins, outs))
+        torch.cuda.synchronize()
+
+    def run(self, name, frames):
+        call = self.calls[name]
+        t0 = time.perf_counter()
+        for _ in range(max(1, frames // self.per_call)):
+            call()                                                   # (every call is synchronous)
+        return (time.perf_counter() - t0) * frames / (max(1, frames // self.per_call) * self.per_call)
+
+    def stats(self, name):
+        rt = self.rt[name]
+        one = rt[0] if isinstance(rt, list) else rt
+        keys = ("alpha_frames",) if self.kind.startswith("tiled") else ("alpha_frames", "lookahead_frames", "lookahead_alpha_frames",
+                                                                        "group_frames", "group_alpha_frames", "graph_replays")
+        return {k: one.stat(k) for k in keys}
+
+    def close(self):
+        for rt in self.rt.values():
+            for one in (rt if isinstance(rt, list) else [rt]):
+                one.close()
+
+
+PASS_WORKLOADS = ("pass_bgrx", "pass_rgbx", "group", "tiled_540", "tiled_720")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--preset", default="psp-quality")
@@ -152,7 +248,7 @@ def main():
     result = {"preset": args.preset, "dtype": args.dtype, "filter": args.filter, "frames": args.frames, "rounds": args.rounds,
               "workloads": {}}
     for kind in args.workloads:
-        wl = Workload(kind, args.preset, args.dtype, filt)
+        wl = (PassWorkload if kind in PASS_WORKLOADS else Workload)(kind, args.preset, args.dtype, filt)
         try:
             names = list(wl.rt)
             for name in names:
@@ -164,8 +260,12 @@ def main():
             rows = {}
             for name in names:
                 rows[name] = {"median_fps": round(statistics.median(fps[name]), 1), "min_fps": round(min(fps[name]), 1),
-                              "max_fps": round(max(fps[name]), 1), "alpha_frames": wl.rt[name].stat("alpha_frames"),
-                              "graph_replays": wl.rt[name].stat("graph_replays")}
+                              "max_fps": round(max(fps[name]), 1)}
+                if kind in PASS_WORKLOADS:
+                    rows[name].update(wl.stats(name))
+                else:
+                    rows[name].update({"alpha_frames": wl.rt[name].stat("alpha_frames"),
+                                       "graph_replays": wl.rt[name].stat("graph_replays")})
             for name in names:
                 rows[name]["over_mode0"] = round(rows[name]["median_fps"] / rows["mode0"]["median_fps"], 4)
             result["workloads"][kind] = rows
