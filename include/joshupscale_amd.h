@@ -77,11 +77,24 @@ typedef struct ju_image {
  * step of the same recurrent stream: ju_process, ju_process_frame, ju_process_frames and ju_process_batch may be mixed
  * on one runtime.
  *
- * The conversion is integer arithmetic, defined exactly ("YUV frames"): BT.601 / BT.709 coefficients,
- * limited (16..235 / 16..240) or full range, chroma sited as MPEG-2 / H.264 by default (co-sited horizontally with the
- * even luma columns, centred vertically between two rows); decoding upsamples chroma bilinearly (weights 3:1 vertically,
- * 1:1 horizontally), encoding filters [1,2,1] x [1,1].
+ * The conversion is integer arithmetic, defined exactly ("YUV frames").  ju_frame.colorspace is
+ * JU_CS_* | JU_CHROMA_*, per frame and per side:
  *
+ *   JU_CS_* (the low byte): BT.601, BT.709 or BT.2020 non-constant-luminance coefficients (K_r, K_b = 0.299, 0.114 /
+ *   0.2126, 0.0722 / 0.2627, 0.0593), limited (16..235 / 16..240; 10-bit 64..940 / 64..960) or full range.
+ *
+ *   JU_CHROMA_* (bits 8-9): where chroma sample (i, j) sits among the luma samples at integer (x, y).
+ *     JU_CHROMA_LEFT     (2i,       2j + 1/2)  MPEG-2 / H.264 / most HEVC; 0, so a plain JU_CS_* value means this
+ *     JU_CHROMA_CENTER   (2i + 1/2, 2j + 1/2)  JPEG / MJPEG / MPEG-1 (ffmpeg yuvj420p / yuvj422p, with JU_CS_*_FULL)
+ *     JU_CHROMA_TOPLEFT  (2i,       2j)        UHD HEVC, H.273 chroma_sample_loc_type 2
+ *   Decoding interpolates bilinearly between the two nearest chroma samples of each axis -- a co-sited axis takes c[i] at
+ *   2i and (c[i] + c[i+1]) / 2 at 2i + 1, a centred axis (3 c[i] + c[i-1]) / 4 and (3 c[i] + c[i+1]) / 4 -- and encoding
+ *   filters R, G, B symmetrically about the chroma position: [1,2,1] on a co-sited axis, [1,1] on a centred one.  4:2:2
+ *   has the horizontal axis only (TOPLEFT is LEFT there); a 4:4:4 format accepts a siting and ignores it.
+ *
+ * Refused with JU_ERR_INVALID_ARGUMENT before anything runs: a low byte above 5 ("unknown ... colour space N"), the siting
+ * field 3 ("unknown ... chroma siting 3") and any bit above bit 9.  tests/chroma_siting_reference.py is the definition,
+ * bit for bit.
  *
  * 10-bit 4:2:0 (what HEVC Main10 / AV1 decoders and encoders and high-bit-depth AviSynth+ scripts hold): samples are
  * 16-bit little-endian words.  JU_FMT_P010: planes as NV12, the 10-bit value in the UPPER bits (word = value << 6); on
@@ -164,7 +177,8 @@ typedef struct ju_image {
  * are sized once for the largest format: nothing is regrown behind a captured graph.
  *
  * Limits: 8- and 10-bit YUV (no 12- or 16-bit: P016 and friends need an encode to 16-bit codes that is not defined yet;
- * no NV16 / NV21, no other chroma siting); RGB without 12-bit and without dithering; alpha (X, and the two top bits of an
+ * no NV16 / NV21 / NV24; the three chroma sitings above, none for the alpha plane; BT.2020 non-constant luminance only, no
+ * PQ / HLG transfer function); RGB without 12-bit and without dithering; alpha (X, and the two top bits of an
  * x2rgb10 / x2bgr10 word) is ignored and written 0 unless ju_set_alpha, below, says otherwise; float inputs are quantised to 8 bits like every input,
  * they do not reach the network unquantised; no YUV or RGB graphics resources (GL textures stay BGRX); look-ahead passes
  * take these frames through ju_process_frames (ju_process_batch and ju_prepare_batch take ju_image, i.e. BGRX) and
@@ -180,11 +194,15 @@ enum {
 	JU_FMT_RGBP16 = 38, JU_FMT_RGBPH = 39, JU_FMT_RGBPS = 40, JU_FMT_BGR96F = 41
 };
 enum { JU_FMT_X2BGR10 = 44, JU_FMT_X2RGB10 = 45, JU_FMT_V210 = 48, JU_FMT_Y210 = 49, JU_FMT_Y410 = 50 }; /* packed 10-bit */
-enum { JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3 };
+enum {
+	JU_CS_BT601_LIMITED = 0, JU_CS_BT601_FULL = 1, JU_CS_BT709_LIMITED = 2, JU_CS_BT709_FULL = 3,
+	JU_CS_BT2020_LIMITED = 4, JU_CS_BT2020_FULL = 5
+};
+enum { JU_CHROMA_LEFT = 0, JU_CHROMA_CENTER = 1 << 8, JU_CHROMA_TOPLEFT = 2 << 8 }; /* or-ed into ju_frame.colorspace */
 
 typedef struct ju_frame {
 	int format;            /* JU_FMT_* */
-	int colorspace;        /* JU_CS_*; ignored for JU_FMT_BGRX and the RGB formats (32..45) */
+	int colorspace;        /* JU_CS_* | JU_CHROMA_*; ignored for JU_FMT_BGRX and the RGB formats (32..45) */
 	uint8_t location;      /* JU_LOC_CPU or JU_LOC_DEVICE (BGRX: any location a ju_image takes) */
 	size_t width, height;  /* in pixels (luma); even for the 4:2:0 formats, an even width for 4:2:2 */
 	void *planes[3];       /* BGRX, YUY2, UYVY and the packed RGB formats: [0]; planar formats: Y, U, V or R, G, B; NV12 /

@@ -95,12 +95,37 @@ __device__ inline void storeBytes(std::uint8_t *row, int col, int n, bool fast, 
 	}
 }
 
+// The chroma upsampling of a 4:2:0 decode under siting S (kChroma*; tests/chroma_siting_reference.py), in integers at a
+// scale of 2^kLog2.  Per axis, co-sited: position 2i takes 2 c[i], 2i + 1 takes c[i] + c[i + 1]; centred: 3 c[i] + c[i - 1]
+// and 3 c[i] + c[i + 1].  Left = co-sited x centred (the scale of 8 every kernel here had), centre = centred x centred (16),
+// top-left = co-sited x co-sited (4); the luma term and the rounding shift follow the scale, which leaves the bytes those
+// of the definition's one scale: (2 a + 2^19) >> 20 = (a + 2^18) >> 19.
+template <int S>
+struct Upsample420 {
+	static constexpr int kLog2 = S == kChromaCenter ? 4 : (S == kChromaTopLeft ? 2 : 3);
+	static constexpr int kN = S == kChromaCenter ? 10 : 9;     // samples of a chroma row: [0 .. 8] = columns c0 .. c0 + 8, [9] = c0 - 1
+	static constexpr int kRow0 = S == kChromaTopLeft ? 1 : 0;  // of the rows [0 .. 2] = j - 1, j, j + 1: the first one read
+	// luma row 2j + r from chroma rows j - 1, j, j + 1
+	__device__ static int vertical(int above, int at, int below, int r) {
+		if constexpr (S == kChromaTopLeft) return r == 0 ? 2 * at : at + below;
+		else return 3 * at + (r == 0 ? above : below);
+	}
+	// luma column x0 + p from the row's samples
+	template <int N>
+	__device__ static int horizontal(const int (&v)[N], int p) {
+		const int i = p >> 1;
+		if constexpr (S == kChromaCenter) return 3 * v[i] + ((p & 1) ? v[i + 1] : v[i == 0 ? 9 : i - 1]);
+		else return (p & 1) ? v[i] + v[i + 1] : 2 * v[i];
+	}
+};
+
 // Y, U, V (I420) or Y, UV (NV12) -> BGRX.  Thread = chroma row j (luma rows 2j, 2j + 1) x luma columns x0 .. x0 + 15;
 // it reads chroma rows j - 1 .. j + 1 at columns x0 / 2 .. x0 / 2 + 8 (clamped to the plane).  The strip of thread `idx`:
 // the body of both decode kernels below, so that a frame decoded inside a look-ahead pass has the single frame's bytes.
-template <bool NV12>
+template <bool NV12, int S>
 __device__ inline void yuv420ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H, int idx) {
+	using Up = Upsample420<S>;
 	const int strips = (W + kStrip - 1) / kStrip;
 	if (idx >= strips * (H / 2)) return;
 	const int j = idx / strips;
@@ -109,10 +134,15 @@ __device__ inline void yuv420ToBgrxStrip(const YuvPlanes &src, const YuvDecode &
 	const int c0 = x0 / 2;
 	const bool full = x0 + kStrip <= W;
 
-	// chroma rows j - 1, j, j + 1 (clamped), 9 samples each: columns c0 .. c0 + 8 (clamped)
-	int cu[3][9], cv[3][9];
+	// chroma rows j - 1, j, j + 1 (clamped; top-left: j and j + 1 only), 9 samples each: columns c0 .. c0 + 8 (clamped);
+	// centre: a tenth, [9] = column c0 - 1 (clamped), the last cell of the neighbouring strip
+	int cu[3][Up::kN], cv[3][Up::kN];
+	if constexpr (Up::kRow0 > 0) {  // (row j - 1 is not read and not used)
 #pragma unroll
-	for (int r = 0; r < 3; ++r) {
+		for (int i = 0; i < Up::kN; ++i) cu[0][i] = cv[0][i] = 0;
+	}
+#pragma unroll
+	for (int r = Up::kRow0; r < 3; ++r) {
 		const int jr = min(max(j - 1 + r, 0), CH - 1);
 		const int last = min(c0 + 8, CW - 1);
 		if constexpr (NV12) {
@@ -135,6 +165,11 @@ __device__ inline void yuv420ToBgrxStrip(const YuvPlanes &src, const YuvDecode &
 			}
 			cu[r][8] = row[2 * last];
 			cv[r][8] = row[2 * last + 1];
+			if constexpr (Up::kN > 9) {
+				const int before = max(c0 - 1, 0);
+				cu[r][9] = row[2 * before];
+				cv[r][9] = row[2 * before + 1];
+			}
 		} else {
 			const std::uint8_t *rowU = src.u + static_cast<std::ptrdiff_t>(jr) * src.uStride;
 			const std::uint8_t *rowV = src.v + static_cast<std::ptrdiff_t>(jr) * src.vStride;
@@ -148,6 +183,11 @@ __device__ inline void yuv420ToBgrxStrip(const YuvPlanes &src, const YuvDecode &
 			}
 			cu[r][8] = rowU[last];
 			cv[r][8] = rowV[last];
+			if constexpr (Up::kN > 9) {
+				const int before = max(c0 - 1, 0);
+				cu[r][9] = rowU[before];
+				cv[r][9] = rowV[before];
+			}
 		}
 	}
 
@@ -156,23 +196,21 @@ __device__ inline void yuv420ToBgrxStrip(const YuvPlanes &src, const YuvDecode &
 		const int y = 2 * j + r;
 		unsigned yw[4];
 		loadBytes<16>(src.y + static_cast<std::ptrdiff_t>(y) * src.yStride, x0, W - 1, full, yw);
-		// vertical: 3 x row j + row j - 1 (even luma row) or j + 1 (odd)
-		int vu[9], vv[9];
+		int vu[Up::kN], vv[Up::kN];
 #pragma unroll
-		for (int i = 0; i < 9; ++i) {
-			vu[i] = 3 * cu[1][i] + cu[r == 0 ? 0 : 2][i];
-			vv[i] = 3 * cv[1][i] + cv[r == 0 ? 0 : 2][i];
+		for (int i = 0; i < Up::kN; ++i) {
+			vu[i] = Up::vertical(cu[0][i], cu[1][i], cu[2][i], r);
+			vv[i] = Up::vertical(cv[0][i], cv[1][i], cv[2][i], r);
 		}
 		unsigned px[16];
 #pragma unroll
 		for (int p = 0; p < 16; ++p) {
-			const int i = p >> 1;
-			const int du = ((p & 1) ? vu[i] + vu[i + 1] : 2 * vu[i]) - 1024;
-			const int dv = ((p & 1) ? vv[i] + vv[i + 1] : 2 * vv[i]) - 1024;
-			const int yd = k.ky * (8 * (byteOf(yw, p) - k.oy));
-			const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
-			const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
-			const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+			const int du = Up::horizontal(vu, p) - (128 << Up::kLog2);
+			const int dv = Up::horizontal(vv, p) - (128 << Up::kLog2);
+			const int yd = k.ky * ((1 << Up::kLog2) * (byteOf(yw, p) - k.oy));
+			const int R = clamp255((yd + k.krv * dv + (1 << (15 + Up::kLog2))) >> (16 + Up::kLog2));
+			const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << (15 + Up::kLog2))) >> (16 + Up::kLog2));
+			const int B = clamp255((yd + k.kbu * du + (1 << (15 + Up::kLog2))) >> (16 + Up::kLog2));
 			px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
 		}
 		std::uint8_t *row = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
@@ -185,17 +223,41 @@ __device__ inline void yuv420ToBgrxStrip(const YuvPlanes &src, const YuvDecode &
 	}
 }
 
-template <bool NV12>
+template <bool NV12, int S>
 __global__ __launch_bounds__(256) void yuv420_to_bgrx_kernel(YuvPlanes src, YuvDecode k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H) {
-	yuv420ToBgrxStrip<NV12>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+	yuv420ToBgrxStrip<NV12, S>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
 }
+
+// The chroma sum of an encode under siting S, 4:2:0 (`Rows`: both axes) or 4:2:2 (the horizontal axis only).  Per axis,
+// co-sited: [1, 2, 1] on 2i - 1 (clamped to 0), 2i, 2i + 1, weight 4; centred: [1, 1] on 2i, 2i + 1, weight 2.  The rounding
+// shift of every encode is the coefficients' 16 or 32 bits + kLog2.
+template <int S, bool Rows>
+struct ChromaSum {
+	static constexpr bool kCoH = S != kChromaCenter, kCoV = Rows && S == kChromaTopLeft;
+	static constexpr int kLog2 = (kCoH ? 2 : 1) + (Rows ? (kCoV ? 2 : 1) : 0);  // 4:2:0: 3 (left), 2 (centre), 4 (top-left)
+	static constexpr int kRow0 = kCoV ? -1 : 0;                                 // the luma rows summed: 2j + kRow0 .. 2j + 1
+	__device__ static constexpr int rowWeight(int r) { return (kCoV && r == 0) ? 2 : 1; }
+	// columns 2i - 1, 2i, 2i + 1
+	__device__ static int across(int a, int b, int c) {
+		if constexpr (kCoH) return a + 2 * b + c;
+		else return b + c;
+	}
+	// (the same of get(q), get(q + 1), get(q + 2), each formed where it is summed)
+	template <typename Get>
+	__device__ static int acrossOf(Get get, int q) {
+		if constexpr (kCoH) return get(q) + 2 * get(q + 1) + get(q + 2);
+		else return get(q + 1) + get(q + 2);
+	}
+};
 
 // BGRX -> Y, U, V (I420) or Y, UV (NV12).  Thread = luma rows 2j, 2j + 1 x columns x0 .. x0 + 15 (+ column x0 - 1,
 // clamped to 0, for the chroma filter) -> 2 x 16 luma bytes and chroma cells x0 / 2 .. x0 / 2 + 7 of row j.
-template <bool NV12>
+// (top-left: a third row, 2j - 1 clamped to 0 -- the row above's second -- enters the chroma sums only, accumulated row by row)
+template <bool NV12, int S>
 __global__ __launch_bounds__(256) void bgrx_to_yuv420_kernel(const std::uint8_t *__restrict__ src,
     std::ptrdiff_t srcStride, YuvEncode k, YuvPlanes dst, int W, int H) {
+	using Sum = ChromaSum<S, true>;
 	const int strips = (W + kStrip - 1) / kStrip;
 	const int idx = blockIdx.x * 256 + threadIdx.x;
 	if (idx >= strips * (H / 2)) return;
@@ -204,13 +266,13 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv420_kernel(const std::uint8_t 
 	const bool full = x0 + kStrip <= W;
 	const int n = min(kStrip, W - x0);  // luma columns of this strip (even)
 
-	// per chroma cell: the [1, 2, 1] x [1, 1] sums of R, G, B (8 x C)
+	// per chroma cell: the sums of R, G, B of weight 2^Sum::kLog2 (left: [1, 2, 1] x [1, 1], 8 x C)
 	int sr[8], sg[8], sb[8];
 #pragma unroll
 	for (int i = 0; i < 8; ++i) sr[i] = sg[i] = sb[i] = 0;
 #pragma unroll
-	for (int r = 0; r < 2; ++r) {
-		const int y = 2 * j + r;
+	for (int r = Sum::kRow0; r < 2; ++r) {
+		const int y = r < 0 ? max(2 * j - 1, 0) : 2 * j + r;
 		const std::uint8_t *row = src + static_cast<std::ptrdiff_t>(y) * srcStride;
 		unsigned px[17];  // px[0] = column x0 - 1 (clamped), px[1 + p] = column x0 + p
 #pragma unroll
@@ -229,32 +291,36 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv420_kernel(const std::uint8_t 
 #pragma unroll
 			for (int b = 0; b < 4; ++b) px[1 + 4 * q + b] = w[b];
 		}
-		{
+		if constexpr (Sum::kCoH) {
 			const std::uint8_t *p = row + 4 * max(x0 - 1, 0);
 			px[0] = p[0] | (p[1] << 8) | (p[2] << 16);
+		} else {
+			px[0] = 0;  // (not summed)
 		}
-		unsigned yw[4] = {0, 0, 0, 0};
+		if (r >= 0) {
+			unsigned yw[4] = {0, 0, 0, 0};
 #pragma unroll
-		for (int p = 0; p < 16; ++p) {
-			const int B = px[1 + p] & 255, G = (px[1 + p] >> 8) & 255, R = (px[1 + p] >> 16) & 255;
-			const int Y = clamp255(k.oy + ((k.yr * R + k.yg * G + k.yb * B + (1 << 15)) >> 16));
-			yw[p >> 2] |= static_cast<unsigned>(Y) << (8 * (p & 3));
+			for (int p = 0; p < 16; ++p) {
+				const int B = px[1 + p] & 255, G = (px[1 + p] >> 8) & 255, R = (px[1 + p] >> 16) & 255;
+				const int Y = clamp255(k.oy + ((k.yr * R + k.yg * G + k.yb * B + (1 << 15)) >> 16));
+				yw[p >> 2] |= static_cast<unsigned>(Y) << (8 * (p & 3));
+			}
+			storeBytes<16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, yw);
 		}
-		storeBytes<16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, yw);
 #pragma unroll
 		for (int i = 0; i < 8; ++i) {
 			// columns 2i - 1, 2i, 2i + 1 of the strip = px[2i], px[2i + 1], px[2i + 2]
 			const unsigned a = px[2 * i], b = px[2 * i + 1], c = px[2 * i + 2];
-			sb[i] += (a & 255) + 2 * (b & 255) + (c & 255);
-			sg[i] += ((a >> 8) & 255) + 2 * ((b >> 8) & 255) + ((c >> 8) & 255);
-			sr[i] += ((a >> 16) & 255) + 2 * ((b >> 16) & 255) + ((c >> 16) & 255);
+			sb[i] += Sum::rowWeight(r) * Sum::across(a & 255, b & 255, c & 255);
+			sg[i] += Sum::rowWeight(r) * Sum::across((a >> 8) & 255, (b >> 8) & 255, (c >> 8) & 255);
+			sr[i] += Sum::rowWeight(r) * Sum::across((a >> 16) & 255, (b >> 16) & 255, (c >> 16) & 255);
 		}
 	}
 	unsigned uw[2] = {0, 0}, vw[2] = {0, 0};
 #pragma unroll
 	for (int i = 0; i < 8; ++i) {
-		const int U = clamp255(128 + ((k.ur * sr[i] + k.ug * sg[i] + k.ub * sb[i] + (1 << 18)) >> 19));
-		const int V = clamp255(128 + ((k.vr * sr[i] + k.vg * sg[i] + k.vb * sb[i] + (1 << 18)) >> 19));
+		const int U = clamp255(128 + ((k.ur * sr[i] + k.ug * sg[i] + k.ub * sb[i] + (1 << (15 + Sum::kLog2))) >> (16 + Sum::kLog2)));
+		const int V = clamp255(128 + ((k.vr * sr[i] + k.vg * sg[i] + k.vb * sb[i] + (1 << (15 + Sum::kLog2))) >> (16 + Sum::kLog2)));
 		uw[i >> 2] |= static_cast<unsigned>(U) << (8 * (i & 3));
 		vw[i >> 2] |= static_cast<unsigned>(V) << (8 * (i & 3));
 	}
@@ -331,9 +397,10 @@ __device__ inline void storeSamples(std::uint8_t *row, int col, int n, bool fast
 
 // P010 / I010 -> BGRX (u8): the strip of yuv420ToBgrxStrip with 16-bit samples -- 32 B of Y per row, 16 (+2) B of each
 // chroma plane row or 32 (+4) B of UV, from three chroma rows.  `k`: the coefficients for 10-bit words.
-template <bool P010>
+template <bool P010, int S>
 __device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H, int idx) {
+	using Up = Upsample420<S>;
 	constexpr int kShift = P010 ? 6 : 0;  // (word >> 6, or word & 0x3ff)
 	const int strips = (W + kStrip - 1) / kStrip;
 	if (idx >= strips * (H / 2)) return;
@@ -343,9 +410,13 @@ __device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecod
 	const int c0 = x0 / 2;
 	const bool full = x0 + kStrip <= W;
 
-	int cu[3][9], cv[3][9];
+	int cu[3][Up::kN], cv[3][Up::kN];
+	if constexpr (Up::kRow0 > 0) {  // (row j - 1 is not read and not used)
 #pragma unroll
-	for (int r = 0; r < 3; ++r) {
+		for (int i = 0; i < Up::kN; ++i) cu[0][i] = cv[0][i] = 0;
+	}
+#pragma unroll
+	for (int r = Up::kRow0; r < 3; ++r) {
 		const int jr = min(max(j - 1 + r, 0), CH - 1);
 		const int last = min(c0 + 8, CW - 1);
 		if constexpr (P010) {
@@ -368,6 +439,11 @@ __device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecod
 			}
 			cu[r][8] = wordAt(row, 2 * last) >> kShift;
 			cv[r][8] = wordAt(row, 2 * last + 1) >> kShift;
+			if constexpr (Up::kN > 9) {
+				const int before = max(c0 - 1, 0);
+				cu[r][9] = wordAt(row, 2 * before) >> kShift;
+				cv[r][9] = wordAt(row, 2 * before + 1) >> kShift;
+			}
 		} else {
 			const std::uint8_t *rowU = src.u + static_cast<std::ptrdiff_t>(jr) * src.uStride;
 			const std::uint8_t *rowV = src.v + static_cast<std::ptrdiff_t>(jr) * src.vStride;
@@ -381,6 +457,11 @@ __device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecod
 			}
 			cu[r][8] = wordAt(rowU, last) & 0x3ff;
 			cv[r][8] = wordAt(rowV, last) & 0x3ff;
+			if constexpr (Up::kN > 9) {
+				const int before = max(c0 - 1, 0);
+				cu[r][9] = wordAt(rowU, before) & 0x3ff;
+				cv[r][9] = wordAt(rowV, before) & 0x3ff;
+			}
 		}
 	}
 
@@ -389,23 +470,22 @@ __device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecod
 		const int y = 2 * j + r;
 		unsigned yw[8];
 		loadSamples<16>(src.y + static_cast<std::ptrdiff_t>(y) * src.yStride, x0, W - 1, full, yw);
-		int vu[9], vv[9];
+		int vu[Up::kN], vv[Up::kN];
 #pragma unroll
-		for (int i = 0; i < 9; ++i) {
-			vu[i] = 3 * cu[1][i] + cu[r == 0 ? 0 : 2][i];
-			vv[i] = 3 * cv[1][i] + cv[r == 0 ? 0 : 2][i];
+		for (int i = 0; i < Up::kN; ++i) {
+			vu[i] = Up::vertical(cu[0][i], cu[1][i], cu[2][i], r);
+			vv[i] = Up::vertical(cv[0][i], cv[1][i], cv[2][i], r);
 		}
 		unsigned px[16];
 #pragma unroll
 		for (int p = 0; p < 16; ++p) {
-			const int i = p >> 1;
-			const int du = ((p & 1) ? vu[i] + vu[i + 1] : 2 * vu[i]) - 8 * 512;
-			const int dv = ((p & 1) ? vv[i] + vv[i + 1] : 2 * vv[i]) - 8 * 512;
+			const int du = Up::horizontal(vu, p) - (512 << Up::kLog2);
+			const int dv = Up::horizontal(vv, p) - (512 << Up::kLog2);
 			const int Y = P010 ? sampleOf(yw, p) >> kShift : sampleOf(yw, p) & 0x3ff;
-			const int yd = k.ky * (8 * (Y - k.oy));
-			const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
-			const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
-			const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+			const int yd = k.ky * ((1 << Up::kLog2) * (Y - k.oy));
+			const int R = clamp255((yd + k.krv * dv + (1 << (15 + Up::kLog2))) >> (16 + Up::kLog2));
+			const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << (15 + Up::kLog2))) >> (16 + Up::kLog2));
+			const int B = clamp255((yd + k.kbu * du + (1 << (15 + Up::kLog2))) >> (16 + Up::kLog2));
 			px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
 		}
 		std::uint8_t *row = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
@@ -418,10 +498,10 @@ __device__ inline void yuv420p10ToBgrxStrip(const YuvPlanes &src, const YuvDecod
 	}
 }
 
-template <bool P010>
+template <bool P010, int S>
 __global__ __launch_bounds__(256) void yuv420p10_to_bgrx_kernel(YuvPlanes src, YuvDecode k,
     std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int W, int H) {
-	yuv420p10ToBgrxStrip<P010>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+	yuv420p10ToBgrxStrip<P010, S>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // the sample kinds of the RGB formats ("RGB formats" below)
@@ -617,9 +697,10 @@ struct Bgrx16Source {
 
 // P -> Y, U, V (I010) or Y, UV (P010): the strip body of both 10-bit encodes.  Thread = luma rows 2j, 2j + 1 x columns
 // x0 .. x0 + 15 -> 2 x 32 B of Y and 16 B of U and of V (32 B of UV).  64-bit accumulators: the products reach 2^45.
-template <bool P010, typename Source>
+template <bool P010, int S, typename Source>
 __device__ inline void toYuv420p10Strip(const Source &source, const YuvEncode10 &k, const YuvPlanes &dst, int W, int H,
     int idx) {
+	using Sum = ChromaSum<S, true>;
 	constexpr int kShift = P010 ? 6 : 0;
 	const int strips = (W + kStrip - 1) / kStrip;
 	if (idx >= strips * (H / 2)) return;
@@ -628,41 +709,43 @@ __device__ inline void toYuv420p10Strip(const Source &source, const YuvEncode10 
 	const bool full = x0 + kStrip <= W;
 	const int n = min(kStrip, W - x0);  // luma columns of this strip (even)
 
-	int sr[8], sg[8], sb[8];  // per chroma cell: the [1, 2, 1] x [1, 1] sums of the source's samples (8 x the mean)
+	int sr[8], sg[8], sb[8];  // per chroma cell: the sums of the source's samples, of weight 2^Sum::kLog2 (left: [1, 2, 1] x [1, 1])
 #pragma unroll
 	for (int i = 0; i < 8; ++i) sr[i] = sg[i] = sb[i] = 0;
 #pragma unroll
-	for (int r = 0; r < 2; ++r) {
-		const int y = 2 * j + r;
+	for (int r = Sum::kRow0; r < 2; ++r) {  // (top-left: row 2j - 1, clamped to 0, enters the chroma sums only)
+		const int y = r < 0 ? max(2 * j - 1, 0) : 2 * j + r;
 		typename Source::Pixel px[17];  // [0] = column x0 - 1 (clamped), [1 + p] = column x0 + p
 		source.load(y, x0, W, full, px);
-		unsigned yw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+		if (r >= 0) {
+			unsigned yw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-		for (int p = 0; p < 16; ++p) {
-			const long long acc = (static_cast<long long>(k.yr) * Source::r(px[1 + p]) +
-			                       static_cast<long long>(k.yg) * Source::g(px[1 + p]) +
-			                       static_cast<long long>(k.yb) * Source::b(px[1 + p])) * Source::kScale + (1ll << 31);
-			const int Y = clamp1023(k.oy + static_cast<int>(acc >> 32));
-			yw[p >> 1] |= static_cast<unsigned>(Y << kShift) << (16 * (p & 1));
+			for (int p = 0; p < 16; ++p) {
+				const long long acc = (static_cast<long long>(k.yr) * Source::r(px[1 + p]) +
+				                       static_cast<long long>(k.yg) * Source::g(px[1 + p]) +
+				                       static_cast<long long>(k.yb) * Source::b(px[1 + p])) * Source::kScale + (1ll << 31);
+				const int Y = clamp1023(k.oy + static_cast<int>(acc >> 32));
+				yw[p >> 1] |= static_cast<unsigned>(Y << kShift) << (16 * (p & 1));
+			}
+			storeSamples<16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, yw);
 		}
-		storeSamples<16>(dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride, x0, n, full, yw);
 #pragma unroll
 		for (int i = 0; i < 8; ++i) {
 			// columns 2i - 1, 2i, 2i + 1 of the strip = px[2i], px[2i + 1], px[2i + 2]
-			sb[i] += Source::b(px[2 * i]) + 2 * Source::b(px[2 * i + 1]) + Source::b(px[2 * i + 2]);
-			sg[i] += Source::g(px[2 * i]) + 2 * Source::g(px[2 * i + 1]) + Source::g(px[2 * i + 2]);
-			sr[i] += Source::r(px[2 * i]) + 2 * Source::r(px[2 * i + 1]) + Source::r(px[2 * i + 2]);
+			sb[i] += Sum::rowWeight(r) * Sum::across(Source::b(px[2 * i]), Source::b(px[2 * i + 1]), Source::b(px[2 * i + 2]));
+			sg[i] += Sum::rowWeight(r) * Sum::across(Source::g(px[2 * i]), Source::g(px[2 * i + 1]), Source::g(px[2 * i + 2]));
+			sr[i] += Sum::rowWeight(r) * Sum::across(Source::r(px[2 * i]), Source::r(px[2 * i + 1]), Source::r(px[2 * i + 2]));
 		}
 	}
 	unsigned uw[4] = {0, 0, 0, 0}, vw[4] = {0, 0, 0, 0};
 #pragma unroll
 	for (int i = 0; i < 8; ++i) {
 		const long long au = (static_cast<long long>(k.ur) * sr[i] + static_cast<long long>(k.ug) * sg[i] +
-		                      static_cast<long long>(k.ub) * sb[i]) * Source::kScale + (1ll << 34);
+		                      static_cast<long long>(k.ub) * sb[i]) * Source::kScale + (1ll << (31 + Sum::kLog2));
 		const long long av = (static_cast<long long>(k.vr) * sr[i] + static_cast<long long>(k.vg) * sg[i] +
-		                      static_cast<long long>(k.vb) * sb[i]) * Source::kScale + (1ll << 34);
-		const int U = clamp1023(512 + static_cast<int>(au >> 35));
-		const int V = clamp1023(512 + static_cast<int>(av >> 35));
+		                      static_cast<long long>(k.vb) * sb[i]) * Source::kScale + (1ll << (31 + Sum::kLog2));
+		const int U = clamp1023(512 + static_cast<int>(au >> (32 + Sum::kLog2)));
+		const int V = clamp1023(512 + static_cast<int>(av >> (32 + Sum::kLog2)));
 		uw[i >> 1] |= static_cast<unsigned>(U << kShift) << (16 * (i & 1));
 		vw[i >> 1] |= static_cast<unsigned>(V << kShift) << (16 * (i & 1));
 	}
@@ -680,25 +763,25 @@ __device__ inline void toYuv420p10Strip(const Source &source, const YuvEncode10 
 	}
 }
 
-template <bool P010>
+template <bool P010, int S>
 __global__ __launch_bounds__(256) void state_to_yuv420p10_kernel(const f16 *__restrict__ state, YuvEncode10 k,
     YuvPlanes dst, int W, int H) {
-	toYuv420p10Strip<P010>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toYuv420p10Strip<P010, S>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
-template <bool P010>
+template <bool P010, int S>
 __global__ __launch_bounds__(256) void frame16_to_yuv420p10_kernel(const std::uint16_t *__restrict__ frame, YuvEncode10 k,
     YuvPlanes dst, int W, int H) {
-	toYuv420p10Strip<P010>(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toYuv420p10Strip<P010, S>(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // (214 VGPRs: the scheduler hoists the byte extractions of a row over its 64-bit sums; held to 128 registers with
 // amdgpu_waves_per_eu the kernel spills 352 B per lane, so it is left alone -- at 1920x1080 the grid is 254 workgroups on
 // 256 CUs, one wave per SIMD, and the occupancy limit is never reached)
-template <bool P010>
+template <bool P010, int S>
 __global__ __launch_bounds__(256) void bgrx_to_yuv420p10_kernel(const std::uint8_t *__restrict__ src,
     std::ptrdiff_t srcStride, YuvEncode10 k, YuvPlanes dst, int W, int H) {
-	toYuv420p10Strip<P010>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toYuv420p10Strip<P010, S>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // ---- 4:2:2 and 4:4:4, 8- and 10-bit (tests/yuv_sampled_reference.py; docs/yuv_io.md, "4:2:2 and 4:4:4") ----------------
@@ -875,12 +958,53 @@ __device__ inline void loadSampledStrip(const YuvPlanes &src, int y, int x0, int
 	}
 }
 
-// planes -> BGRX: the strip of thread `idx`; the body of the single-frame kernel and of the items kernel's branch.
-// `k`: decodeCoefficients for the format (8-bit samples or 10-bit words).
+// 4:2:2 chroma at luma column x0 + p from the strip's cells c[0 ..] and the cell before them: left, at a scale of 8, c[i] at
+// even columns and the mean of two at odd ones; centre, at a scale of 4, 3 c[i] + c[i - 1] and 3 c[i] + c[i + 1]
+template <int S, int N>
+__device__ inline int chromaAt422(const int (&c)[N], int before, int p) {
+	const int i = p >> 1;
+	if constexpr (S == kChromaCenter) return 3 * c[i] + ((p & 1) ? c[i + 1] : (i == 0 ? before : c[i - 1]));
+	else return (p & 1) ? 4 * (c[i] + c[i + 1]) : 8 * c[i];
+}
+
+// chroma cell `c` (in range) of row y of a 4:2:2 format: what the centre siting reads of the strip to the left
 template <int F>
+__device__ inline void loadChromaCell(const YuvPlanes &src, int y, int c, int *u, int *v) {
+	using T = SampledTraits<F>;
+	static_assert(!T::kFull, "4:2:2 only");
+	const std::uint8_t *rowY = src.y + static_cast<std::ptrdiff_t>(y) * src.yStride;
+	if constexpr (F == kY210) {
+		*u = wordAt(rowY, 4 * c + 1) >> T::kShift;
+		*v = wordAt(rowY, 4 * c + 3) >> T::kShift;
+	} else if constexpr (T::kPacked) {
+		*u = rowY[4 * c + 1 - T::kYByte];
+		*v = rowY[4 * c + 3 - T::kYByte];
+	} else if constexpr (T::kSemi) {
+		const std::uint8_t *rowU = src.u + static_cast<std::ptrdiff_t>(y) * src.uStride;
+		*u = wordAt(rowU, 2 * c) >> T::kShift;
+		*v = wordAt(rowU, 2 * c + 1) >> T::kShift;
+	} else {
+		const std::uint8_t *rowU = src.u + static_cast<std::ptrdiff_t>(y) * src.uStride;
+		const std::uint8_t *rowV = src.v + static_cast<std::ptrdiff_t>(y) * src.vStride;
+		if constexpr (T::kDeep) {
+			*u = wordAt(rowU, c) & 0x3ff;
+			*v = wordAt(rowV, c) & 0x3ff;
+		} else {
+			*u = rowU[c];
+			*v = rowV[c];
+		}
+	}
+}
+
+// planes -> BGRX: the strip of thread `idx`; the body of the single-frame kernel and of the items kernel's branch.
+// `k`: decodeCoefficients for the format (8-bit samples or 10-bit words).  S: kChromaLeft, or (4:2:2) kChromaCenter -- then
+// the chroma at the pixel is 3 c[i] + c[i -+ 1], at a scale of 4, and cell x0 / 2 - 1 (clamped to 0) is read too.
+template <int F, int S>
 __device__ inline void yuvSampledToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H, int idx) {
 	using T = SampledTraits<F>;
+	static_assert(S == kChromaLeft || (S == kChromaCenter && !T::kFull), "4:2:2: left or centre; 4:4:4 has no siting");
+	constexpr int kLog2 = S == kChromaCenter ? 2 : 3;  // log2 of the scale of the chroma at the pixel
 	const int strips = (W + kStrip - 1) / kStrip;
 	if (idx >= strips * H) return;
 	const int y = idx / strips;
@@ -888,24 +1012,25 @@ __device__ inline void yuvSampledToBgrxStrip(const YuvPlanes &src, const YuvDeco
 	const bool full = x0 + kStrip <= W;
 	int ys[16], cu[17], cv[17];
 	loadSampledStrip<F>(src, y, x0, W, full, ys, cu, cv);
+	int beforeU = 0, beforeV = 0;
+	if constexpr (S == kChromaCenter) loadChromaCell<F>(src, y, max(x0 / 2 - 1, 0), &beforeU, &beforeV);
 	unsigned px[16];
 #pragma unroll
 	for (int p = 0; p < 16; ++p) {
-		int du, dv;  // 8 x chroma at the pixel, less 8 x the mid value
+		int du, dv;  // 2^kLog2 x chroma at the pixel, less 2^kLog2 x the mid value
 		if constexpr (T::kFull) {
 			du = 8 * cu[p];
 			dv = 8 * cv[p];
 		} else {
-			const int i = p >> 1;
-			du = (p & 1) ? 4 * (cu[i] + cu[i + 1]) : 8 * cu[i];
-			dv = (p & 1) ? 4 * (cv[i] + cv[i + 1]) : 8 * cv[i];
+			du = chromaAt422<S>(cu, beforeU, p);
+			dv = chromaAt422<S>(cv, beforeV, p);
 		}
-		du -= 8 * T::kMid;
-		dv -= 8 * T::kMid;
-		const int yd = k.ky * (8 * (ys[p] - k.oy));
-		const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
-		const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
-		const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+		du -= T::kMid << kLog2;
+		dv -= T::kMid << kLog2;
+		const int yd = k.ky * ((1 << kLog2) * (ys[p] - k.oy));
+		const int R = clamp255((yd + k.krv * dv + (1 << (15 + kLog2))) >> (16 + kLog2));
+		const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << (15 + kLog2))) >> (16 + kLog2));
+		const int B = clamp255((yd + k.kbu * du + (1 << (15 + kLog2))) >> (16 + kLog2));
 		px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
 	}
 	std::uint8_t *row = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
@@ -917,10 +1042,10 @@ __device__ inline void yuvSampledToBgrxStrip(const YuvPlanes &src, const YuvDeco
 	}
 }
 
-template <int F>
+template <int F, int S>
 __global__ __launch_bounds__(256) void yuv_sampled_to_bgrx_kernel(YuvPlanes src, YuvDecode k,
     std::uint8_t *__restrict__ dst, std::ptrdiff_t dstStride, int W, int H) {
-	yuvSampledToBgrxStrip<F>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+	yuvSampledToBgrxStrip<F, S>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // The strip's samples (8-bit: bytes, 10-bit: values 0 .. 1023) into the planes of format F: `n` luma columns of row y
@@ -1013,10 +1138,12 @@ __device__ inline void storeSampledStrip(const YuvPlanes &dst, int y, int x0, in
 
 // BGRX u8 -> the 8-bit formats (YUY2, UYVY, I422, I444).  4:2:2: the [1, 2, 1] sum of a row (4 x the mean), 4:4:4: the
 // pixel itself; the rounding constant and the shift follow the sum's weight.
-template <int F>
+template <int F, int S>
 __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled_kernel(const std::uint8_t *__restrict__ src,
     std::ptrdiff_t srcStride, YuvEncode k, YuvPlanes dst, int W, int H) {
 	using T = SampledTraits<F>;
+	using Sum = ChromaSum<S, false>;
+	static_assert(S == kChromaLeft || (S == kChromaCenter && !T::kFull), "4:2:2: left or centre; 4:4:4 has no siting");
 	const int strips = (W + kStrip - 1) / kStrip;
 	const int idx = blockIdx.x * 256 + threadIdx.x;
 	if (idx >= strips * H) return;
@@ -1032,7 +1159,7 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled_kernel(const std::uin
 		const int B = px[1 + p] & 255, G = (px[1 + p] >> 8) & 255, R = (px[1 + p] >> 16) & 255;
 		ys[p] = clamp255(k.oy + ((k.yr * R + k.yg * G + k.yb * B + (1 << 15)) >> 16));
 	}
-	constexpr int kW = T::kFull ? 0 : 2;  // log2 of the chroma sum's weight
+	constexpr int kW = T::kFull ? 0 : Sum::kLog2;  // log2 of the chroma sum's weight
 #pragma unroll
 	for (int i = 0; i < (T::kFull ? 16 : 8); ++i) {
 		int sr, sg, sb;
@@ -1040,9 +1167,9 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled_kernel(const std::uin
 			sb = px[1 + i] & 255, sg = (px[1 + i] >> 8) & 255, sr = (px[1 + i] >> 16) & 255;
 		} else {  // columns 2i - 1, 2i, 2i + 1 of the strip = px[2i], px[2i + 1], px[2i + 2]
 			const unsigned a = px[2 * i], b = px[2 * i + 1], c = px[2 * i + 2];
-			sb = (a & 255) + 2 * (b & 255) + (c & 255);
-			sg = ((a >> 8) & 255) + 2 * ((b >> 8) & 255) + ((c >> 8) & 255);
-			sr = ((a >> 16) & 255) + 2 * ((b >> 16) & 255) + ((c >> 16) & 255);
+			sb = Sum::across(a & 255, b & 255, c & 255);
+			sg = Sum::across((a >> 8) & 255, (b >> 8) & 255, (c >> 8) & 255);
+			sr = Sum::across((a >> 16) & 255, (b >> 16) & 255, (c >> 16) & 255);
 		}
 		cu[i] = clamp255(128 + ((k.ur * sr + k.ug * sg + k.ub * sb + (1 << (15 + kW))) >> (16 + kW)));
 		cv[i] = clamp255(128 + ((k.vr * sr + k.vg * sg + k.vb * sb + (1 << (15 + kW))) >> (16 + kW)));
@@ -1051,10 +1178,12 @@ __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled_kernel(const std::uin
 }
 
 // P -> the 10-bit formats (P210, I210, I410): the strip body of both sources, as toYuv420p10Strip is for 4:2:0.
-template <int F, typename Source>
+template <int F, int S, typename Source>
 __device__ inline void toYuvSampled10Strip(const Source &source, const YuvEncode10 &k, const YuvPlanes &dst, int W, int H,
     int idx) {
 	using T = SampledTraits<F>;
+	using Sum = ChromaSum<S, false>;
+	static_assert(S == kChromaLeft || (S == kChromaCenter && !T::kFull), "4:2:2: left or centre; 4:4:4 has no siting");
 	const int strips = (W + kStrip - 1) / kStrip;
 	if (idx >= strips * H) return;
 	const int y = idx / strips;
@@ -1071,16 +1200,16 @@ __device__ inline void toYuvSampled10Strip(const Source &source, const YuvEncode
 		                       static_cast<long long>(k.yb) * Source::b(px[1 + p])) * Source::kScale + (1ll << 31);
 		ys[p] = clamp1023(k.oy + static_cast<int>(acc >> 32));
 	}
-	constexpr int kW = T::kFull ? 0 : 2;  // log2 of the chroma sum's weight
+	constexpr int kW = T::kFull ? 0 : Sum::kLog2;  // log2 of the chroma sum's weight
 #pragma unroll
 	for (int i = 0; i < (T::kFull ? 16 : 8); ++i) {
 		int sr, sg, sb;
 		if constexpr (T::kFull) {
 			sb = Source::b(px[1 + i]), sg = Source::g(px[1 + i]), sr = Source::r(px[1 + i]);
 		} else {
-			sb = Source::b(px[2 * i]) + 2 * Source::b(px[2 * i + 1]) + Source::b(px[2 * i + 2]);
-			sg = Source::g(px[2 * i]) + 2 * Source::g(px[2 * i + 1]) + Source::g(px[2 * i + 2]);
-			sr = Source::r(px[2 * i]) + 2 * Source::r(px[2 * i + 1]) + Source::r(px[2 * i + 2]);
+			sb = Sum::across(Source::b(px[2 * i]), Source::b(px[2 * i + 1]), Source::b(px[2 * i + 2]));
+			sg = Sum::across(Source::g(px[2 * i]), Source::g(px[2 * i + 1]), Source::g(px[2 * i + 2]));
+			sr = Sum::across(Source::r(px[2 * i]), Source::r(px[2 * i + 1]), Source::r(px[2 * i + 2]));
 		}
 		const long long au = (static_cast<long long>(k.ur) * sr + static_cast<long long>(k.ug) * sg +
 		                      static_cast<long long>(k.ub) * sb) * Source::kScale + (1ll << (31 + kW));
@@ -1092,22 +1221,22 @@ __device__ inline void toYuvSampled10Strip(const Source &source, const YuvEncode
 	storeSampledStrip<F>(dst, y, x0, n, full, ys, cu, cv);
 }
 
-template <int F>
+template <int F, int S>
 __global__ __launch_bounds__(256) void state_to_yuv_sampled10_kernel(const f16 *__restrict__ state, YuvEncode10 k,
     YuvPlanes dst, int W, int H) {
-	toYuvSampled10Strip<F>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toYuvSampled10Strip<F, S>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
-template <int F>
+template <int F, int S>
 __global__ __launch_bounds__(256) void frame16_to_yuv_sampled10_kernel(const std::uint16_t *__restrict__ frame,
     YuvEncode10 k, YuvPlanes dst, int W, int H) {
-	toYuvSampled10Strip<F>(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toYuvSampled10Strip<F, S>(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
-template <int F>
+template <int F, int S>
 __global__ __launch_bounds__(256) void bgrx_to_yuv_sampled10_kernel(const std::uint8_t *__restrict__ src,
     std::ptrdiff_t srcStride, YuvEncode10 k, YuvPlanes dst, int W, int H) {
-	toYuvSampled10Strip<F>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toYuvSampled10Strip<F, S>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // ---- RGB formats: 24-bit, RGBX, planar 8 / 10 / 16 bit, f16, f32 (tests/rgb_reference.py; docs/yuv_io.md, "RGB formats") ----
@@ -1409,8 +1538,11 @@ __device__ inline void storeGroup(std::uint8_t *p, const unsigned *w) {
 // the plane -> BGRX: the strip of thread `idx`; the body of the single-frame kernel and of the items kernel's branch.
 // Chroma cell c0 + 6, the right-hand neighbour of the strip's last odd column, is the first of the NEXT thread's groups;
 // cells beyond W / 2 - 1 -- that one in a row's last strip, and the unused slots of a partial group -- take the last cell's.
+template <int S>
 __device__ inline void v210ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H, int idx) {
+	static_assert(S == kChromaLeft || S == kChromaCenter, "4:2:2: left or centre");
+	constexpr int kLog2 = S == kChromaCenter ? 2 : 3;  // log2 of the scale of the chroma at the pixel
 	const int strips = (W + kGroupStrip - 1) / kGroupStrip;
 	if (idx >= strips * H) return;
 	const int y = idx / strips;
@@ -1430,6 +1562,14 @@ __device__ inline void v210ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k,
 		cv[3 * g + 1] = q[2] & 0x3ff, ys[6 * g + 3] = (q[2] >> 10) & 0x3ff, cu[3 * g + 2] = (q[2] >> 20) & 0x3ff;
 		ys[6 * g + 4] = q[3] & 0x3ff, cv[3 * g + 2] = (q[3] >> 10) & 0x3ff, ys[6 * g + 5] = (q[3] >> 20) & 0x3ff;
 	}
+	int beforeU = cu[0], beforeV = cv[0];  // (centre: cell c0 - 1, the last of the group to the left; clamped to cell 0)
+	if constexpr (S == kChromaCenter) {
+		if (g0 > 0) {
+			const uint2 prev = make_uint2(*reinterpret_cast<const unsigned *>(row + 16 * g0 - 8),
+			    *reinterpret_cast<const unsigned *>(row + 16 * g0 - 4));
+			beforeU = (prev.x >> 20) & 0x3ff, beforeV = (prev.y >> 10) & 0x3ff;
+		}
+	}
 	cu[6] = cv[6] = 0;
 	if (g0 + 2 < groups) {  // (a group that exists begins with a cell that exists)
 		const unsigned next = *reinterpret_cast<const unsigned *>(row + 16 * (g0 + 2));
@@ -1442,13 +1582,13 @@ __device__ inline void v210ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k,
 	unsigned px[kGroupStrip];
 #pragma unroll
 	for (int p = 0; p < kGroupStrip; ++p) {
-		const int i = p >> 1;
-		const int du = ((p & 1) ? 4 * (cu[i] + cu[i + 1]) : 8 * cu[i]) - 8 * 512;
-		const int dv = ((p & 1) ? 4 * (cv[i] + cv[i + 1]) : 8 * cv[i]) - 8 * 512;
-		const int yd = k.ky * (8 * (ys[p] - k.oy));
-		const int R = clamp255((yd + k.krv * dv + (1 << 18)) >> 19);
-		const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << 18)) >> 19);
-		const int B = clamp255((yd + k.kbu * du + (1 << 18)) >> 19);
+		// 2^kLog2 x chroma at the pixel, less 2^kLog2 x the mid value
+		const int du = chromaAt422<S>(cu, beforeU, p) - (512 << kLog2);
+		const int dv = chromaAt422<S>(cv, beforeV, p) - (512 << kLog2);
+		const int yd = k.ky * ((1 << kLog2) * (ys[p] - k.oy));
+		const int R = clamp255((yd + k.krv * dv + (1 << (15 + kLog2))) >> (16 + kLog2));
+		const int G = clamp255((yd - k.kgu * du - k.kgv * dv + (1 << (15 + kLog2))) >> (16 + kLog2));
+		const int B = clamp255((yd + k.kbu * du + (1 << (15 + kLog2))) >> (16 + kLog2));
 		px[p] = static_cast<unsigned>(B) | (static_cast<unsigned>(G) << 8) | (static_cast<unsigned>(R) << 16);
 	}
 	std::uint8_t *out = dst + static_cast<std::ptrdiff_t>(y) * dstStride;
@@ -1460,16 +1600,19 @@ __device__ inline void v210ToBgrxStrip(const YuvPlanes &src, const YuvDecode &k,
 	}
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void v210_to_bgrx_kernel(YuvPlanes src, YuvDecode k, std::uint8_t *__restrict__ dst,
     std::ptrdiff_t dstStride, int W, int H) {
-	v210ToBgrxStrip(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
+	v210ToBgrxStrip<S>(src, k, dst, dstStride, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // P -> the plane: the strip body of the three encodes.  The source's load covers columns x0 - 1 (clamped to 0: the
 // left-hand neighbour of the [1, 2, 1] sum) and x0 .. x0 + 15 (clamped to W - 1), of which the strip uses the first 12; its
 // wide path needs all 16 in range.  Sample slots beyond W are written 0, and a group is written whole.
-template <typename Source>
+template <int S, typename Source>
 __device__ inline void toV210Strip(const Source &source, const YuvEncode10 &k, const YuvPlanes &dst, int W, int H, int idx) {
+	using Sum = ChromaSum<S, false>;
+	static_assert(S == kChromaLeft || S == kChromaCenter, "4:2:2: left or centre");
 	const int strips = (W + kGroupStrip - 1) / kGroupStrip;
 	if (idx >= strips * H) return;
 	const int y = idx / strips;
@@ -1487,15 +1630,15 @@ __device__ inline void toV210Strip(const Source &source, const YuvEncode10 &k, c
 	}
 #pragma unroll
 	for (int i = 0; i < 6; ++i) {
-		const int sb = Source::b(px[2 * i]) + 2 * Source::b(px[2 * i + 1]) + Source::b(px[2 * i + 2]);
-		const int sg = Source::g(px[2 * i]) + 2 * Source::g(px[2 * i + 1]) + Source::g(px[2 * i + 2]);
-		const int sr = Source::r(px[2 * i]) + 2 * Source::r(px[2 * i + 1]) + Source::r(px[2 * i + 2]);
+		const int sb = Sum::acrossOf([&](int q) { return Source::b(px[q]); }, 2 * i);
+		const int sg = Sum::acrossOf([&](int q) { return Source::g(px[q]); }, 2 * i);
+		const int sr = Sum::acrossOf([&](int q) { return Source::r(px[q]); }, 2 * i);
 		const long long au = (static_cast<long long>(k.ur) * sr + static_cast<long long>(k.ug) * sg +
-		                      static_cast<long long>(k.ub) * sb) * Source::kScale + (1ll << 33);
+		                      static_cast<long long>(k.ub) * sb) * Source::kScale + (1ll << (31 + Sum::kLog2));
 		const long long av = (static_cast<long long>(k.vr) * sr + static_cast<long long>(k.vg) * sg +
-		                      static_cast<long long>(k.vb) * sb) * Source::kScale + (1ll << 33);
-		cu[i] = c0 + i < CW ? static_cast<unsigned>(clamp1023(512 + static_cast<int>(au >> 34))) : 0u;
-		cv[i] = c0 + i < CW ? static_cast<unsigned>(clamp1023(512 + static_cast<int>(av >> 34))) : 0u;
+		                      static_cast<long long>(k.vb) * sb) * Source::kScale + (1ll << (31 + Sum::kLog2));
+		cu[i] = c0 + i < CW ? static_cast<unsigned>(clamp1023(512 + static_cast<int>(au >> (32 + Sum::kLog2)))) : 0u;
+		cv[i] = c0 + i < CW ? static_cast<unsigned>(clamp1023(512 + static_cast<int>(av >> (32 + Sum::kLog2)))) : 0u;
 	}
 	std::uint8_t *row = dst.y + static_cast<std::ptrdiff_t>(y) * dst.yStride;
 #pragma unroll
@@ -1509,19 +1652,22 @@ __device__ inline void toV210Strip(const Source &source, const YuvEncode10 &k, c
 	}
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void bgrx_to_v210_kernel(const std::uint8_t *__restrict__ src, std::ptrdiff_t srcStride,
     YuvEncode10 k, YuvPlanes dst, int W, int H) {
-	toV210Strip(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toV210Strip<S>(Bgrx8Source{src, srcStride}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void state_to_v210_kernel(const f16 *__restrict__ state, YuvEncode10 k, YuvPlanes dst, int W,
     int H) {
-	toV210Strip(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toV210Strip<S>(StateSource{state}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void frame16_to_v210_kernel(const std::uint16_t *__restrict__ frame, YuvEncode10 k,
     YuvPlanes dst, int W, int H) {
-	toV210Strip(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
+	toV210Strip<S>(Bgrx16Source{frame}, k, dst, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // The formats each kernel family instantiates, ONE list per family: the launchers below and the items kernel reach a
@@ -1534,73 +1680,86 @@ using Yuv420p10 = Formats<kI010, kP010>;
 using Sampled = Formats<kYuy2, kUyvy, kI422, kP210, kI210, kI444, kI410, kY210, kY410>;
 using Grouped = Formats<kV210>;
 using Rgb = Formats<kBgr24, kRgb24, kRgbx, kBgrx64, kRgbp8, kRgbp10, kRgbp16, kRgbph, kRgbps, kBgr96f, kX2rgb10, kX2bgr10>;
+// (the sitings a family's bodies are instantiated for, dispatched the same way on the frame's effectiveSiting)
+using Sitings420 = Formats<kChromaLeft, kChromaCenter, kChromaTopLeft>;
+using Sitings422 = Formats<kChromaLeft, kChromaCenter>;
 // fn(std::integral_constant<int, F>, args...) for the F of the list that equals `format`; false: the list has no such format
 template <int... Fs, typename Fn, typename... A>
 __host__ __device__ inline bool forFormat(Formats<Fs...>, int format, Fn &&fn, const A &...args) {
 	return ((format == Fs && (fn(std::integral_constant<int, Fs>{}, args...), true)) || ...);
 }
+// fn(std::integral_constant<int, S>) for the siting S of a format of the Sampled list: 4:4:4 has the one body
+template <int F, typename Fn>
+inline void forSampledSiting(int siting, Fn &&fn) {
+	if constexpr (SampledTraits<F>::kFull) fn(std::integral_constant<int, kChromaLeft>{});
+	else (void)forFormat(Sitings422{}, siting, fn);
+}
 
 // The inputs of a look-ahead pass in ONE launch: grid (blocks of one frame, items), blockIdx.y selects the item -- its
 // format, planes, coefficients and destination, from the kernel arguments -- and the format is a branch every lane of the
-// workgroup takes alike.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
+// workgroup takes alike, and so is the item's siting, one level below.  At 480x270 one frame is 16 workgroups on 256 CUs: eight launches of that size would be eight
 // launch latencies for one round of work (the shape addFlowAutoencoder's batched launches fixed for the flow net).
 // (a 4:2:2 / 4:4:4 or RGB item has a strip per row: the grid then covers strips x H threads and a 4:2:0 item's upper half
 // of them returns at once; an RGB item's coefficients are not read)
-__global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
-	const YuvDecodeItem &it = items.item[blockIdx.y];
-	const int idx = blockIdx.x * 256 + threadIdx.x;
-	// (captureless: a strip body sees the item as the kernel's own argument, which is what lets the inliner fold it in)
+__device__ __forceinline__ void decodeItemStrip(const YuvDecodeItem &it, int W, int H, int idx) {
+	// (captureless lambdas over the kernel's own COPY of the item: 96 bytes of scalar registers.  Through a reference into the
+	// by-value argument the two levels of dispatch made the compiler keep all eight items in scratch)
 	using Item = const YuvDecodeItem &;
 	(void)(forFormat(Yuv420{}, it.format, [](auto f, Item it, int W, int H, int idx) {
-		       yuv420ToBgrxStrip<f() == kNv12>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       (void)forFormat(Sitings420{}, it.siting, [](auto s, auto f, Item it, int W, int H, int idx) {
+			       yuv420ToBgrxStrip<f() == kNv12, s()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       }, f, it, W, H, idx);
 	       }, it, W, H, idx) ||
 	       forFormat(Yuv420p10{}, it.format, [](auto f, Item it, int W, int H, int idx) {
-		       yuv420p10ToBgrxStrip<f() == kP010>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       (void)forFormat(Sitings420{}, it.siting, [](auto s, auto f, Item it, int W, int H, int idx) {
+			       yuv420p10ToBgrxStrip<f() == kP010, s()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       }, f, it, W, H, idx);
 	       }, it, W, H, idx) ||
 	       forFormat(Sampled{}, it.format, [](auto f, Item it, int W, int H, int idx) {
-		       yuvSampledToBgrxStrip<f()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       if constexpr (SampledTraits<f()>::kFull) {
+			       yuvSampledToBgrxStrip<f(), kChromaLeft>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       } else {
+			       (void)forFormat(Sitings422{}, it.siting, [](auto s, auto f, Item it, int W, int H, int idx) {
+				       yuvSampledToBgrxStrip<f(), s()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+			       }, f, it, W, H, idx);
+		       }
 	       }, it, W, H, idx) ||
 	       forFormat(Grouped{}, it.format, [](auto, Item it, int W, int H, int idx) {
-		       v210ToBgrxStrip(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       (void)forFormat(Sitings422{}, it.siting, [](auto s, Item it, int W, int H, int idx) {
+			       v210ToBgrxStrip<s()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
+		       }, it, W, H, idx);
 	       }, it, W, H, idx) ||
 	       forFormat(Rgb{}, it.format, [](auto f, Item it, int W, int H, int idx) {
 		       rgbToBgrxStrip<f()>(it.src, it.dst, it.dstStride, W, H, idx);
 	       }, it, W, H, idx));
+}
+
+__global__ __launch_bounds__(256) void yuv420_to_bgrx_items_kernel(YuvDecodeItems items, int W, int H) {
+	const YuvDecodeItem it = items.item[blockIdx.y];
+	decodeItemStrip(it, W, H, blockIdx.x * 256 + threadIdx.x);
 }
 
 // The sized form (launchYuvToBgrxItemsSized: the members of a group pass): item blockIdx.y at its OWN width and height, read
 // with the item from the kernel arguments.  The grid covers the largest item's strips; every strip body returns beyond its
 // own frame's count, as the upper half of a 4:2:0 item's grid does above.  The strip bodies are the ones above.
 __global__ __launch_bounds__(256) void yuv_to_bgrx_items_sized_kernel(YuvDecodeSizedItems items) {
-	const YuvDecodeItem &it = items.item[blockIdx.y];
-	const int W = items.width[blockIdx.y], H = items.height[blockIdx.y];
-	const int idx = blockIdx.x * 256 + threadIdx.x;
-	using Item = const YuvDecodeItem &;
-	(void)(forFormat(Yuv420{}, it.format, [](auto f, Item it, int W, int H, int idx) {
-		       yuv420ToBgrxStrip<f() == kNv12>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	       }, it, W, H, idx) ||
-	       forFormat(Yuv420p10{}, it.format, [](auto f, Item it, int W, int H, int idx) {
-		       yuv420p10ToBgrxStrip<f() == kP010>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	       }, it, W, H, idx) ||
-	       forFormat(Sampled{}, it.format, [](auto f, Item it, int W, int H, int idx) {
-		       yuvSampledToBgrxStrip<f()>(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	       }, it, W, H, idx) ||
-	       forFormat(Grouped{}, it.format, [](auto, Item it, int W, int H, int idx) {
-		       v210ToBgrxStrip(it.src, it.k, it.dst, it.dstStride, W, H, idx);
-	       }, it, W, H, idx) ||
-	       forFormat(Rgb{}, it.format, [](auto f, Item it, int W, int H, int idx) {
-		       rgbToBgrxStrip<f()>(it.src, it.dst, it.dstStride, W, H, idx);
-	       }, it, W, H, idx));
+	const YuvDecodeItem it = items.item[blockIdx.y];
+	decodeItemStrip(it, items.width[blockIdx.y], items.height[blockIdx.y], blockIdx.x * 256 + threadIdx.x);
 }
 
 int roundHalfAway(double x) { return static_cast<int>(std::copysign(std::floor(std::fabs(x) * 65536.0 + 0.5), x)); }
 
-void colourSpace(int cs, double *kr, double *kb, bool *limited) {
-	if (cs < 0 || cs > 3) throw std::invalid_argument("unknown colour space");
-	const bool bt601 = cs == 0 || cs == 1;
-	*kr = bt601 ? 0.299 : 0.2126;
-	*kb = bt601 ? 0.114 : 0.0722;
-	*limited = cs == 0 || cs == 2;
+// K_r, K_b and the range of a frame's `colorspace` (its matrix: BT.601, BT.709, BT.2020 non-constant luminance)
+void colourSpace(int colorspace, double *kr, double *kb, bool *limited) {
+	const int matrix = splitColourSpace(colorspace).matrix;
+	*kr = matrix < 2 ? 0.299 : (matrix < 4 ? 0.2126 : 0.2627);
+	*kb = matrix < 2 ? 0.114 : (matrix < 4 ? 0.0722 : 0.0593);
+	*limited = matrix % 2 == 0;
+}
+
+// the siting of a frame's `colorspace` that the format's kernels distinguish
+int sitingOf(const YuvFormatInfo &info, int colorspace) {
+	return info.rgb() ? kChromaLeft : effectiveSiting(info, splitColourSpace(colorspace).siting);
 }
 
 // x 65536 for 8-bit samples, or for 10-bit words -> u8 (oy 64 | 0); an RGB format has none and its colour space is not read
@@ -1697,14 +1856,19 @@ void launchDecodeFrame(int format, int colorspace, const YuvPlanes &src, std::ui
     int width, int height, hipStream_t stream) {
 	const StripLaunch run{formatInfo(format), width, height, stream};
 	const YuvDecode k = decodeCoefficients(run.info, colorspace);
-	if (!(forFormat(Yuv420{}, format,
-	          [&](auto f) { run("yuv420_to_bgrx", yuv420_to_bgrx_kernel<f() == kNv12>, src, k, dst, dstStride); }) ||
-	        forFormat(Yuv420p10{}, format,
-	            [&](auto f) { run("yuv420p10_to_bgrx", yuv420p10_to_bgrx_kernel<f() == kP010>, src, k, dst, dstStride); }) ||
-	        forFormat(Sampled{}, format,
-	            [&](auto f) { run("yuv_sampled_to_bgrx", yuv_sampled_to_bgrx_kernel<f()>, src, k, dst, dstStride); }) ||
-	        forFormat(Grouped{}, format, [&](auto) { run("v210_to_bgrx", v210_to_bgrx_kernel, src, k, dst, dstStride); }) ||
-	        forFormat(Rgb{}, format, [&](auto f) { run("rgb_to_bgrx", rgb_to_bgrx_kernel<f()>, src, dst, dstStride); }))) {
+	const int siting = sitingOf(run.info, colorspace);
+	if (!(forFormat(Yuv420{}, format, [&](auto f) {
+		      forFormat(Sitings420{}, siting,
+		          [&](auto s) { run("yuv420_to_bgrx", yuv420_to_bgrx_kernel<f() == kNv12, s()>, src, k, dst, dstStride); });
+	      }) || forFormat(Yuv420p10{}, format, [&](auto f) {
+		      forFormat(Sitings420{}, siting,
+		          [&](auto s) { run("yuv420p10_to_bgrx", yuv420p10_to_bgrx_kernel<f() == kP010, s()>, src, k, dst, dstStride); });
+	      }) || forFormat(Sampled{}, format, [&](auto f) {
+		      forSampledSiting<f()>(siting,
+		          [&](auto s) { run("yuv_sampled_to_bgrx", yuv_sampled_to_bgrx_kernel<f(), s()>, src, k, dst, dstStride); });
+	      }) || forFormat(Grouped{}, format, [&](auto) {
+		      forFormat(Sitings422{}, siting, [&](auto s) { run("v210_to_bgrx", v210_to_bgrx_kernel<s()>, src, k, dst, dstStride); });
+	      }) || forFormat(Rgb{}, format, [&](auto f) { run("rgb_to_bgrx", rgb_to_bgrx_kernel<f()>, src, dst, dstStride); }))) {
 		noKernel("decode", format);
 	}
 }
@@ -1716,6 +1880,7 @@ YuvDecodeItem yuvDecodeItem(int format, int colorspace, const YuvPlanes &src, st
 	it.dst = dst;
 	it.dstStride = dstStride;
 	it.format = format;
+	it.siting = sitingOf(formatInfo(format), colorspace);
 	return it;
 }
 
@@ -1742,18 +1907,26 @@ void launchYuvToBgrxItemsSized(const YuvDecodeSizedItems &items, int count, hipS
 void launchEncodeFrame(int format, int colorspace, const std::uint8_t *src, std::ptrdiff_t srcStride, const YuvPlanes &dst,
     int width, int height, hipStream_t stream) {
 	const StripLaunch run{formatInfo(format), width, height, stream};
+	const int siting = sitingOf(run.info, colorspace);
 	const bool done = forFormat(Yuv420{}, format, [&](auto f) {
-		run("bgrx_to_yuv420", bgrx_to_yuv420_kernel<f() == kNv12>, src, srcStride, encodeCoefficients(colorspace), dst);
+		forFormat(Sitings420{}, siting, [&](auto s) {
+			run("bgrx_to_yuv420", bgrx_to_yuv420_kernel<f() == kNv12, s()>, src, srcStride, encodeCoefficients(colorspace), dst);
+		});
 	}) || forFormat(Yuv420p10{}, format, [&](auto f) {
-		run("bgrx_to_yuv420p10", bgrx_to_yuv420p10_kernel<f() == kP010>, src, srcStride, encodeCoefficients10(colorspace), dst);
+		forFormat(Sitings420{}, siting, [&](auto s) {
+			run("bgrx_to_yuv420p10", bgrx_to_yuv420p10_kernel<f() == kP010, s()>, src, srcStride, encodeCoefficients10(colorspace), dst);
+		});
 	}) || forFormat(Sampled{}, format, [&](auto f) {
-		if constexpr (SampledTraits<f()>::kDeep) {
-			run("bgrx_to_yuv_sampled10", bgrx_to_yuv_sampled10_kernel<f()>, src, srcStride, encodeCoefficients10(colorspace), dst);
-		} else {
-			run("bgrx_to_yuv_sampled", bgrx_to_yuv_sampled_kernel<f()>, src, srcStride, encodeCoefficients(colorspace), dst);
-		}
+		forSampledSiting<f()>(siting, [&](auto s) {
+			if constexpr (SampledTraits<f()>::kDeep) {
+				run("bgrx_to_yuv_sampled10", bgrx_to_yuv_sampled10_kernel<f(), s()>, src, srcStride, encodeCoefficients10(colorspace), dst);
+			} else {
+				run("bgrx_to_yuv_sampled", bgrx_to_yuv_sampled_kernel<f(), s()>, src, srcStride, encodeCoefficients(colorspace), dst);
+			}
+		});
 	}) || forFormat(Grouped{}, format, [&](auto) {
-		run("bgrx_to_v210", bgrx_to_v210_kernel, src, srcStride, encodeCoefficients10(colorspace), dst);
+		forFormat(Sitings422{}, siting,
+		    [&](auto s) { run("bgrx_to_v210", bgrx_to_v210_kernel<s()>, src, srcStride, encodeCoefficients10(colorspace), dst); });
 	}) || forFormat(Rgb{}, format, [&](auto f) { run("bgrx_to_rgb", bgrx_to_rgb_kernel<f()>, src, srcStride, dst); });
 	if (!done) noKernel("encode", format);
 }
@@ -1761,19 +1934,25 @@ void launchEncodeFrame(int format, int colorspace, const std::uint8_t *src, std:
 void launchEncodeState(int format, int colorspace, const void *state, const YuvPlanes &dst, int width, int height,
     hipStream_t stream) {
 	const StripLaunch run{formatInfo(format), width, height, stream};
-	const f16 *s = static_cast<const f16 *>(state);
+	const f16 *st = static_cast<const f16 *>(state);
+	const int siting = sitingOf(run.info, colorspace);
 	const bool done = forFormat(Yuv420p10{}, format, [&](auto f) {
-		run("state_to_yuv420p10", state_to_yuv420p10_kernel<f() == kP010>, s, encodeCoefficients10(colorspace), dst);
+		forFormat(Sitings420{}, siting, [&](auto s) {
+			run("state_to_yuv420p10", state_to_yuv420p10_kernel<f() == kP010, s()>, st, encodeCoefficients10(colorspace), dst);
+		});
 	}) || forFormat(Sampled{}, format, [&](auto f) {
 		if constexpr (SampledTraits<f()>::kDeep) {
-			run("state_to_yuv_sampled10", state_to_yuv_sampled10_kernel<f()>, s, encodeCoefficients10(colorspace), dst);
+			forSampledSiting<f()>(siting, [&](auto s) {
+				run("state_to_yuv_sampled10", state_to_yuv_sampled10_kernel<f(), s()>, st, encodeCoefficients10(colorspace), dst);
+			});
 		} else {
 			noKernel("encode from the state", format);
 		}
 	}) || forFormat(Grouped{}, format, [&](auto) {
-		run("state_to_v210", state_to_v210_kernel, s, encodeCoefficients10(colorspace), dst);
+		forFormat(Sitings422{}, siting,
+		    [&](auto s) { run("state_to_v210", state_to_v210_kernel<s()>, st, encodeCoefficients10(colorspace), dst); });
 	}) || forFormat(Rgb{}, format, [&](auto f) {
-		if constexpr (RgbTraits<f()>::kKind != kU8) run("state_to_rgb", state_to_rgb_kernel<f()>, s, dst);
+		if constexpr (RgbTraits<f()>::kKind != kU8) run("state_to_rgb", state_to_rgb_kernel<f()>, st, dst);
 		else noKernel("encode from the state", format);
 	});
 	if (!done) noKernel("encode from the state", format);
@@ -1782,16 +1961,22 @@ void launchEncodeState(int format, int colorspace, const void *state, const YuvP
 void launchEncodeFrame16(int format, int colorspace, const std::uint16_t *frame, const YuvPlanes &dst, int width, int height,
     hipStream_t stream) {
 	const StripLaunch run{formatInfo(format), width, height, stream};
+	const int siting = sitingOf(run.info, colorspace);
 	const bool done = forFormat(Yuv420p10{}, format, [&](auto f) {
-		run("frame16_to_yuv420p10", frame16_to_yuv420p10_kernel<f() == kP010>, frame, encodeCoefficients10(colorspace), dst);
+		forFormat(Sitings420{}, siting, [&](auto s) {
+			run("frame16_to_yuv420p10", frame16_to_yuv420p10_kernel<f() == kP010, s()>, frame, encodeCoefficients10(colorspace), dst);
+		});
 	}) || forFormat(Sampled{}, format, [&](auto f) {
 		if constexpr (SampledTraits<f()>::kDeep) {
-			run("frame16_to_yuv_sampled10", frame16_to_yuv_sampled10_kernel<f()>, frame, encodeCoefficients10(colorspace), dst);
+			forSampledSiting<f()>(siting, [&](auto s) {
+				run("frame16_to_yuv_sampled10", frame16_to_yuv_sampled10_kernel<f(), s()>, frame, encodeCoefficients10(colorspace), dst);
+			});
 		} else {
 			noKernel("encode from a 16-bit frame", format);
 		}
 	}) || forFormat(Grouped{}, format, [&](auto) {
-		run("frame16_to_v210", frame16_to_v210_kernel, frame, encodeCoefficients10(colorspace), dst);
+		forFormat(Sitings422{}, siting,
+		    [&](auto s) { run("frame16_to_v210", frame16_to_v210_kernel<s()>, frame, encodeCoefficients10(colorspace), dst); });
 	}) || forFormat(Rgb{}, format, [&](auto f) {
 		if constexpr (RgbTraits<f()>::kKind != kU8) run("frame16_to_rgb", frame16_to_rgb_kernel<f()>, frame, dst);
 		else noKernel("encode from a 16-bit frame", format);

@@ -158,7 +158,10 @@ void checkPlanes(const YuvFrame &y, const std::string &side, std::size_t w, std:
 	const YuvFormatInfo &info = *known;
 	const std::string name = info.name;
 	// (an RGB frame has no colour space: the field is ignored)
-	if (!info.rgb() && (y.colorspace < 0 || y.colorspace > 3)) refuse("unknown " + side + " colour space " + std::to_string(y.colorspace));
+	if (!info.rgb()) {  // (matrix | siting: kernels.h; a 4:4:4 format takes a valid siting and ignores it)
+		const std::string fault = colourSpaceFault(y.colorspace, side + " ");
+		if (!fault.empty()) refuse(fault);
+	}
 	if (y.location != Location::Host && y.location != Location::Device) {
 		refuse(name + " " + side + " frames must be host or device memory (no graphics resources)");
 	}

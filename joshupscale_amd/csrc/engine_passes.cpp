@@ -485,7 +485,13 @@ Engine::BoundRows Engine::bindSide(const AnyFrame &a, std::size_t width, std::si
 	side->format = y.format;
 	side->colorspace = y.colorspace;
 	key->format = static_cast<int>(y.format);
-	key->colorspace = info.rgb() ? 0 : y.colorspace;  // (ignored for RGB: no second graph for another value)
+	// (ignored for RGB, and so is a siting the format's kernels do not distinguish: no second graph for another value)
+	if (info.rgb()) {
+		key->colorspace = 0;
+	} else {
+		const ColourSpace cs = splitColourSpace(y.colorspace);
+		key->colorspace = cs.matrix | (effectiveSiting(info, cs.siting) << 8);
+	}
 	for (int k = 0; k < info.planes; ++k) {
 		key->planes[k] = side->host ? nullptr : y.planes[k];
 		key->strides[k] = side->host ? (y.strides[k] > 0 ? 1 : -1) : y.strides[k];

@@ -557,6 +557,38 @@ inline const YuvFormatInfo &formatInfo(int value) {
 }
 inline const YuvFormatInfo &formatInfo(PixelFormat f) { return formatInfo(fmt(f)); }
 
+// A frame's `colorspace` = JU_CS_* | JU_CHROMA_* (include/joshupscale_amd.h): the low byte is the matrix and range -- 0
+// BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full, 4 BT.2020 (non-constant luminance) limited, 5 BT.2020
+// full -- and bits 8-9 the chroma siting: where chroma sample (i, j) sits among the luma samples at integer (x, y).  Left
+// (2i, 2j + 1/2): MPEG-2 / H.264; centre (2i + 1/2, 2j + 1/2): JPEG / MPEG-1; top-left (2i, 2j): H.273 type 2.
+constexpr int kChromaLeft = 0, kChromaCenter = 1, kChromaTopLeft = 2;
+constexpr int kColourMatrixEnd = 6;  // (one past the largest matrix value)
+struct ColourSpace {
+	int matrix = 0, siting = kChromaLeft;
+};
+// THE split of the int, for the frame check, the coefficient functions and the launchers: why a value is refused ("" for
+// a good one: then *cs, where given, is set), in the frame check's words -- `side`: "input " / "output " or ""
+inline std::string colourSpaceFault(int colorspace, const std::string &side, ColourSpace *cs = nullptr) {
+	if (colorspace < 0 || (colorspace >> 10) != 0) {
+		return "unknown " + side + "colour space " + std::to_string(colorspace) + " (bits above bit 9 are set)";
+	}
+	if (((colorspace >> 8) & 3) > kChromaTopLeft) return "unknown " + side + "chroma siting " + std::to_string((colorspace >> 8) & 3);
+	if ((colorspace & 0xff) >= kColourMatrixEnd) return "unknown " + side + "colour space " + std::to_string(colorspace & 0xff);
+	if (cs != nullptr) *cs = ColourSpace{colorspace & 0xff, (colorspace >> 8) & 3};
+	return std::string();
+}
+inline ColourSpace splitColourSpace(int colorspace) {
+	ColourSpace cs;
+	const std::string fault = colourSpaceFault(colorspace, "", &cs);
+	if (!fault.empty()) throw std::invalid_argument(fault);
+	return cs;
+}
+// the siting a format's kernels distinguish: 4:4:4 and RGB have none, 4:2:2 has the horizontal axis only (top-left = left)
+inline int effectiveSiting(const YuvFormatInfo &info, int siting) {
+	if (info.sampling == 420) return siting;
+	return (info.sampling == 422 && siting == kChromaCenter) ? kChromaCenter : kChromaLeft;
+}
+
 // Planes of a frame: Y, U, V / R, G, B (planar), Y and one interleaved plane u (semi-planar; v unused) or y alone (packed:
 // rows of pixelBytes x width bytes; V210: 16 x ceil(width / 6)).  Chroma planes have height / 2 (4:2:0) or height rows of width / 2 (4:2:0, 4:2:2;
 // interleaved: width) or width (4:4:4) samples.  Pointers address the first logical row, strides are bytes and may be
@@ -566,11 +598,12 @@ struct YuvPlanes {
 	std::ptrdiff_t yStride = 0, uStride = 0, vStride = 0;
 };
 // The three launches of the colour staging, for any format of the table (std::invalid_argument for another value).  Each
-// chooses the kernel and, from `colorspace` (0 BT.601 limited, 1 BT.601 full, 2 BT.709 limited, 3 BT.709 full;
-// std::invalid_argument otherwise), the coefficients; an RGB format's `colorspace` is not read.  4:2:0 needs an even
-// width and height, 4:2:2 an even width.  The definitions are tests/yuv_reference.py, yuv10_reference.py (10-bit words;
-// the 16-bit sample P of an encode), yuv_sampled_reference.py (4:2:2 / 4:4:4: chroma co-sited with the even luma columns)
-// and rgb_reference.py (inputs reduced to the u8 frame the network consumes; 8-bit outputs permute the frame's bytes).
+// chooses, from `colorspace` (splitColourSpace above; std::invalid_argument for a value it refuses), the coefficients and
+// the kernel's siting; an RGB format's `colorspace` is not read.  4:2:0 needs an even width and height, 4:2:2 an even
+// width.  The definitions are tests/chroma_siting_reference.py (every siting and matrix), which with the left siting is
+// tests/yuv_reference.py, yuv10_reference.py (10-bit words; the 16-bit sample P of an encode) and
+// yuv_sampled_reference.py (4:2:2 / 4:4:4), and rgb_reference.py (inputs reduced to the u8 frame the network consumes;
+// 8-bit outputs permute the frame's bytes).
 // planes -> BGRX rows (X = 0)
 void launchDecodeFrame(int format, int colorspace, const YuvPlanes &src, std::uint8_t *dst, std::ptrdiff_t dstStride,
     int width, int height, hipStream_t stream);
@@ -600,6 +633,7 @@ struct YuvDecodeItem {
 	std::uint8_t *dst = nullptr;
 	std::ptrdiff_t dstStride = 0;
 	int format = 0;
+	int siting = kChromaLeft;  // effectiveSiting of the frame (in what was padding: the item's size is unchanged)
 };
 struct YuvDecodeItems {
 	YuvDecodeItem item[kFlowBatchMax];

@@ -82,6 +82,9 @@ def packed10_shape(fmt: int, width: int, height: int):
 
 
 CS_BT601_LIMITED, CS_BT601_FULL, CS_BT709_LIMITED, CS_BT709_FULL = 0, 1, 2, 3
+CS_BT2020_LIMITED, CS_BT2020_FULL = 4, 5                         # BT.2020 non-constant luminance
+# the chroma siting, or-ed into a frame's colorspace (bits 8-9): MPEG-2 / H.264 (the default), JPEG / MPEG-1, H.273 type 2
+CHROMA_LEFT, CHROMA_CENTER, CHROMA_TOPLEFT = 0 << 8, 1 << 8, 2 << 8
 
 
 class JuFrame(C.Structure):

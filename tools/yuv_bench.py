@@ -8,7 +8,8 @@ through ju_debug_yuv, for a `rocprofv3 --kernel-trace --stats` run (the test fla
 the same run the three 10-bit kernels (ju_debug_yuv10: decode, encode from a u8 frame, encode from an f16 tensor; P010
 and I010) at that size plus their decode at --small-size (default 480x270, the LR frame of the flagship workload), and
 the 4:2:2 / 4:4:4 kernels (ju_debug_yuv_sampled: every format's decode and encodes at that size, its decode at
---small-size), and the RGB kernels alike (ju_debug_rgb: all ten formats).
+--small-size), and the RGB kernels alike (ju_debug_rgb: all ten formats).  --chroma center | topleft runs the YUV kernels'
+instantiations of that siting (docs/yuv_io.md, "Chroma siting and BT.2020").
 
 --passes N adds the look-ahead variants, N frames per call: nv12_host_pass, i420_host_pass, nv12_device_pass
 (ju_process_frames), p010_*_pass, yuy2_*_pass, i444_*_pass, p210_*_pass alike, and bgrx_host_pass, bgrx_device_pass (ju_process_batch), interleaved with the per-call variants in
@@ -42,6 +43,7 @@ FORMATS = {"bgrx": R.FMT_BGRX, "nv12": R.FMT_NV12, "i420": R.FMT_I420, "p010": R
            "i444": R.FMT_I444, "p210": R.FMT_P210, "bgr24": R.FMT_BGR24, "rgbp16": R.FMT_RGBP16, "rgbps": R.FMT_RGBPS,
            "bgr96f": R.FMT_BGR96F}
 TEN = (R.FMT_P010, R.FMT_I010)
+CHROMA = {"left": R.CHROMA_LEFT, "center": R.CHROMA_CENTER, "topleft": R.CHROMA_TOPLEFT}
 
 
 def planes_for(fmt, h, w, bgrx, cs):
@@ -182,6 +184,7 @@ def kernel_bench(args):
     dev = torch.device("cuda", 0)
     w, h = (int(x) for x in args.kernel_size.split("x"))
     lib = R.load_library(True)
+    cs = R.CS_BT709_LIMITED | CHROMA[args.chroma]             # (the RGB kernels have no colour space)
     rng = np.random.default_rng(0)
     bgrx = torch.from_numpy(rng.integers(0, 256, (h, w, 4), dtype=np.uint8)).to(dev)
     out = torch.zeros((h, w, 4), dtype=torch.uint8, device=dev)
@@ -194,7 +197,7 @@ def kernel_bench(args):
         for direction, src in ((1, bgrx), (0, out)):
             t0 = time.perf_counter()
             for _ in range(args.iters):
-                rc = lib.ju_debug_yuv(direction, fmt, R.CS_BT709_LIMITED, w, h, src.data_ptr(), 4 * w, ptrs, strides)
+                rc = lib.ju_debug_yuv(direction, fmt, cs, w, h, src.data_ptr(), 4 * w, ptrs, strides)
                 if rc != 0:
                     raise RuntimeError(lib.ju_last_error().decode())
             res[f"{name}_{'encode' if direction else 'decode'}_ms_per_call"] = \
@@ -214,7 +217,7 @@ def kernel_bench(args):
             for op, what, image, image_stride in ops:
                 t0 = time.perf_counter()
                 for _ in range(args.iters):
-                    rc = lib.ju_debug_yuv10(op, fmt, R.CS_BT709_LIMITED, pw, ph, image.data_ptr(), image_stride, ptrs, strides)
+                    rc = lib.ju_debug_yuv10(op, fmt, cs, pw, ph, image.data_ptr(), image_stride, ptrs, strides)
                     if rc != 0:
                         raise RuntimeError(lib.ju_last_error().decode())
                 res[f"{name}_{what}_ms_per_call"] = round((time.perf_counter() - t0) * 1e3 / args.iters, 4)
@@ -233,7 +236,7 @@ def kernel_bench(args):
             for op, what, image, image_stride in ops:
                 t0 = time.perf_counter()
                 for _ in range(args.iters):
-                    rc = lib.ju_debug_yuv_sampled(op, fmt, R.CS_BT709_LIMITED, pw, ph, image.data_ptr(), image_stride, ptrs, strides)
+                    rc = lib.ju_debug_yuv_sampled(op, fmt, cs, pw, ph, image.data_ptr(), image_stride, ptrs, strides)
                     if rc != 0:
                         raise RuntimeError(lib.ju_last_error().decode())
                 res[f"{name}_{what}_ms_per_call"] = round((time.perf_counter() - t0) * 1e3 / args.iters, 4)
@@ -256,7 +259,7 @@ def kernel_bench(args):
                         raise RuntimeError(lib.ju_last_error().decode())
                 res[f"{name}_{what}_ms_per_call"] = round((time.perf_counter() - t0) * 1e3 / args.iters, 4)
     print(json.dumps({"metric": "ju_debug_yuv / ju_debug_yuv10 / ju_debug_yuv_sampled / ju_debug_rgb host time per synchronous call (kernel time: the trace)",
-                      "size": f"{w}x{h}", "small_size": f"{sw}x{sh}", "iters": args.iters, **res}))
+                      "chroma": args.chroma, "size": f"{w}x{h}", "small_size": f"{sw}x{sh}", "iters": args.iters, **res}))
 
 
 def items_bench(args):
@@ -301,6 +304,8 @@ def main():
     ap.add_argument("--runs", type=int, default=1, help="repeat the whole interleaved measurement")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "yuv_pass_bench.json"))
     ap.add_argument("--only", default="", help="comma-separated variants to run (for a trace), e.g. nv12_host_pass")
+    ap.add_argument("--chroma", default="left", choices=sorted(CHROMA),
+                    help="with --kernels: the chroma siting of the YUV kernels (left: the default's instantiations)")
     ap.add_argument("--items", type=int, default=0, help="with --kernels: the pass's decode kernel over this many frames")
     args = ap.parse_args()
     if args.kernels and args.items:
